@@ -122,6 +122,27 @@ import _native as nat  # noqa: E402
 nat.load_library()
 
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all .npy files of a job together
+
+
+def _dump_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: the state the timed steps left behind -- what a caller of the step path reads back after
+    its last step -- as DIR/<name>.npy in float64 (several ranks: <name>.rank<r>.npy, each rank's local arrays).
+    Within the 64 MB budget (split evenly over the ranks) the arrays are written whole; beyond it every array keeps
+    the same share of its entries, a sample at sorted indices drawn from a fixed seed, so two builds run with the same
+    arguments write the same entries."""
+    if not getattr(args, "dump_outputs", None):
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    budget = DUMP_LIMIT_BYTES // world - 256 * len(arrays)        # (256 bytes per .npy header, generously)
+    share = min(1.0, budget / max(1, sum(a.nbytes for a in arrays.values())))
+    suffix = "" if world == 1 else ".rank%d" % rank
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if share < 1.0:
+            keep = int(a.size * share)
+            a = a[np.sort(np.random.default_rng(1234 + i).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name + suffix + ".npy"), a)
 
 
 def cavity_dirichlet(dm, height):
@@ -275,6 +296,7 @@ def dfg_bdf_bench(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
     sps = args.steps / elapsed
+    _dump_outputs(args, rank, world, {"velocity": ctx.get_state(nat.U1), "pressure": ctx.get_state(nat.P_OLD)})
     # the physical output of the configuration (demo/dfg_benchmark.py:44-66): drag / lift coefficients
     # from the surface traction on the cylinder, c = 2 F / (U_mean^2 D) with U_mean = D = 1.  The
     # reference integrates  -p n + 1/Re sym(grad u) n  (its d lacks the factor 2 of the Newtonian
@@ -518,6 +540,7 @@ def tgv3d_bench(args):
     comm_per_step = {k: v / args.steps for k, v in ctx.comm_stats().items()}
     # the vortex decays like exp(-2 g^2 t / Re): check the run against the analytic solution
     t_end = dt * (args.warmup + args.steps)
+    _dump_outputs(args, rank, world, {"velocity": ctx.get_state(nat.U1), "pressure": ctx.get_state(nat.P_OLD)})
     u = ctx.get_state(nat.U1).reshape(-1, 3)
     err = float(np.abs(u - np.exp(-2.0 * g * g * t_end / 100.0) * u0.reshape(-1, 3)).max())
     if dist is not None:
@@ -650,6 +673,7 @@ def cavity3d_bench(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
     sps = args.steps / elapsed
+    _dump_outputs(args, rank, world, {"velocity": ctx.get_state(nat.U1), "pressure": ctx.get_state(nat.P_OLD)})
     ms_spmv, nbytes = ctx.time_spmv(nat.OP_MOMENTUM_JAC, 100)
     achieved = nbytes / (ms_spmv * 1e-3) / 1e9
     if rank == 0:
@@ -769,6 +793,7 @@ def channel3d_bdf_bench(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
     sps = args.steps / elapsed
+    _dump_outputs(args, rank, world, {"velocity": ctx.get_state(nat.U1), "pressure": ctx.get_state(nat.P_OLD)})
     # ---- invariants of the computed state: boundary facets of the box whose cell lies in this
     # rank's own layers, summed over the ranks
     nu = 1.0 / args.reynolds
@@ -1173,6 +1198,7 @@ def cavity_ipcs_bench(args):
     elapsed, its, comm_per_step = timed_run(opts)
     steps_per_s = args.steps / elapsed
     u_fast, p_fast = ctx.get_state(nat.U1), ctx.get_state(nat.P_OLD)
+    _dump_outputs(args, rank, world, {"velocity": u_fast, "pressure": p_fast})
     if args.timed_only:
         ctx.close()
         _finish_dist(dist)
@@ -1441,6 +1467,11 @@ def solver_surface_run(args, n, u_abi, p_abi):
         def set_initial_conditions(self):
             self._initial_conditions = {"velocity": (0.0, 0.0), "pressure": 0.0}
 
+        def _write_xdmf_file(self, current_time=0.0):
+            # no field output at all (as _output_frequency = 0 asks), not even the driver's initial write at t = 0:
+            # the benchmark writes nothing under its working directory, which may be read-only
+            pass
+
     if args.warmup == 0:
         raise SystemExit("--warmup 0 is not supported by the solver-surface timing (--no-solver-classes)")
     log = io.StringIO()
@@ -1519,6 +1550,9 @@ def main():
     ap.add_argument("--trace-markers", action="store_true",
                     help="profiling aid: one k_cfl launch right before and right after the timed steps, so that a kernel "
                          "trace can be cut to the timed region (scripts/trace_gaps.py --between k_cfl)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the velocity and pressure of the last one as DIR/<name>.npy "
+                         "(float64; at most 64 MB in all, a fixed seeded sample of larger fields) for comparing builds")
     ap.add_argument("--no-multigrid", action="store_true")
     ap.add_argument("--mg-degree", type=int, default=None,
                     help="Chebyshev smoother degree (default: 2 on structured meshes, 3 on the DFG mesh)")
@@ -1633,7 +1667,7 @@ def _run_workload(args):
         a2.other_configs = False
         out = cavity_ipcs_bench(a2)
         a1 = copy.copy(args)
-        a1.n, a1.timed_only = args.n or 512, True
+        a1.n, a1.timed_only, a1.dump_outputs = args.n or 512, True, None
         wk = cavity_ipcs_bench(a1)
         if out is not None and wk is not None:
             out["weak"] = strong_block(wk, a1)
@@ -1644,7 +1678,7 @@ def _run_workload(args):
         if default_job and args.gpus == 1 and out is not None and args.scaling == "weak" and not args.no_strong:
             # the one-GPU point of the strong-scaling curve the N > 1 lines report: the 960 x 960 mesh on one GPU
             a2 = copy.copy(args)
-            a2.scaling, a2.n, a2.timed_only = "strong", args.strong_cells, True
+            a2.scaling, a2.n, a2.timed_only, a2.dump_outputs = "strong", args.strong_cells, True, None
             a2.steps, a2.warmup = min(args.steps, 10), min(args.warmup, 3)
             st = cavity_ipcs_bench(a2)
             out["strong_n1"] = strong_block(st, a2)

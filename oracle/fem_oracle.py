@@ -3,7 +3,7 @@
 Plain numpy/scipy restatement of the arithmetic that the reference hands to
 FEniCS/DOLFIN 2019.1.0 + PETSc LU for the per-time-step Taylor-Hood (P2/P1)
 assembly + sparse solve.  The arithmetic itself lives in third-party packages
-that are NOT under /root/reference (fenics-dolfin/ffc/fiat/ufl 2019.1.0, petsc
+that are NOT part of the reference repository (fenics-dolfin/ffc/fiat/ufl 2019.1.0, petsc
 3.14.5 -- environment.yml:19-25,75), so this file restates the published
 algorithm (Lagrange P2/P1 on affine simplices, exact Gauss quadrature, Newton
 with residual criterion, DirichletBC row replacement, sparse direct LU) and is

@@ -1,5 +1,6 @@
 import os, sys
-sys.path[:0] = ["/root/repo/navierstokes-with-fenics_amd", "/root/repo/tests"]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "navierstokes-with-fenics_amd"), os.path.join(ROOT, "tests")]
 import numpy as np, _native as nat
 from gpu_common import box, context
 from multigrid import attach_hierarchy

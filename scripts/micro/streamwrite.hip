@@ -1,6 +1,6 @@
 // Round trip device -> host after a kernel: (a) a one-block publish kernel that stores a flag to coherent pinned
 // memory, (b) hipStreamWriteValue64 on the same stream (a command-processor write, no kernel dispatch).
-// build: hipcc --offload-arch=gfx950 -O2 scripts/micro/streamwrite.hip -o /tmp/streamwrite
+// build: hipcc --offload-arch=gfx950 -O2 scripts/micro/streamwrite.hip -o scripts/micro/streamwrite
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdint>

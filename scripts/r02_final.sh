@@ -1,6 +1,6 @@
 #!/bin/bash
 # final state of round 2: GPU test suite, smoke, default bench line
-cd /root/repo
+cd "$(dirname "$0")/.."
 O=gpurun_out/r02_d; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/gpu_tests.log 2>&1; tail -3 $O/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log

@@ -1,6 +1,7 @@
 """Generates tests/golden/imex_theta_tables.json by IMPORTING the reference's pure-Python
-modules source/imex_time_stepping.py and source/theta_time_stepping.py (no dolfin import) in
-the build container; only the JSON travels to the GPU box.  Inputs: scheme type, start/end time,
+modules source/imex_time_stepping.py and source/theta_time_stepping.py (no dolfin import); the
+upstream checkout is not part of this repository, only the JSON is.  Usage:
+python gen_imex_theta_golden.py <upstream source/ directory>.  Inputs: scheme type, start/end time,
 sequence of desired step sizes.  Outputs per step: the coefficient sets after
 ``update_coefficients()``."""
 import json
@@ -8,7 +9,7 @@ import os
 import random
 import sys
 
-sys.path.insert(0, "/root/reference/source")
+sys.path.insert(0, sys.argv[1])
 from imex_time_stepping import IMEXTimeStepping, IMEXType  # noqa: E402  (reference modules)
 from theta_time_stepping import GeneralThetaTimeStepping, ThetaTimeSteppingType  # noqa: E402
 

@@ -1,7 +1,8 @@
 """Generates tests/golden/bdf_tables.json by IMPORTING the reference's pure-Python
 time stepping modules (source/discrete_time.py, source/bdf_time_stepping.py -- they
-do not import dolfin) in the build container.  /root/reference does not exist on the
-GPU box: only the JSON travels.  Inputs: start/end time, order, a sequence of desired
+do not import dolfin); the upstream checkout is not part of this repository, only the
+JSON is.  Usage: python gen_time_stepping_golden.py <upstream source/ directory>.
+Inputs: start/end time, order, a sequence of desired
 step sizes.  Outputs per step: times, step number, alpha(1), alpha(2), changed flags.
 Also stores the golden alpha tables written in the reference's
 tests/test_bdf_time_stepping.py:67-114 (data, not code)."""
@@ -10,7 +11,7 @@ import os
 import random
 import sys
 
-sys.path.insert(0, "/root/reference/source")
+sys.path.insert(0, sys.argv[1])
 from bdf_time_stepping import BDFTimeStepping  # noqa: E402  (reference module)
 
 

@@ -750,6 +750,43 @@ def test_bench_through_rccl_single_rank():
     assert line["config"]["comm_per_step_rank0"]["allreduce_bytes"] > 65 * 65 * 8       # (the H x W array of the solve)
 
 
+def test_bench_dump_outputs_are_the_fields_of_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs DIR: the velocity and pressure the timed steps end on (whole at this size, float64),
+    identical in two runs with the same arguments; one more timed step gives other fields"""
+    def run(name, steps):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", str(steps), "--warmup", "1",
+               "--timed-only", "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        assert json.loads(res.stdout.strip().splitlines()[-1])["steps"] == steps
+        return {n: np.load(d / (n + ".npy")) for n in ("velocity", "pressure")}
+
+    a, b, c = run("a", 3), run("b", 3), run("c", 4)
+    assert a["velocity"].shape == (2 * 129 * 129,) and a["pressure"].shape == (65 * 65,)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k])
+    assert not np.array_equal(a["velocity"], c["velocity"])
+
+
+def test_bench_writes_nothing_under_a_read_only_working_directory(tmp_path):
+    """bench.py (including its pass through the solver classes, whose problem driver would write XDMF output) run from
+    a read-only directory: it succeeds and leaves the directory empty"""
+    cwd = tmp_path / "ro"
+    cwd.mkdir()
+    cwd.chmod(0o555)
+    try:
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "2", "--warmup", "1",
+               "--no-cpu-baseline", "--no-other-configs"]
+        res = subprocess.run(cmd, cwd=str(cwd), capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads(res.stdout.strip().splitlines()[-1])
+        assert "ms_per_step_through_solver_classes" in line["config"]
+        assert list(cwd.iterdir()) == []
+    finally:
+        cwd.chmod(0o755)
+
+
 def test_bench_spawns_its_own_rank_processes_on_a_shared_gpu():
     """`python bench.py --gpus 2` AS TYPED (no launcher, no WORLD_SIZE): the parent never touches the GPU, spawns one
     process per rank (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torch.distributed.run would set them), relays rank

@@ -723,6 +723,38 @@ def test_bench_parent_only_spawns_and_supervises_its_ranks():
     assert res.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_whole_or_seeded_sample_within_the_budget(tmp_path):
+    """bench.py --dump-outputs DIR: float64 .npy files, the arrays whole while they fit the 64 MB budget, beyond it a
+    sample at sorted indices that is the same in every run; several ranks split the budget and suffix their files"""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    small = {"velocity": rng.random(2 * 65 * 65), "pressure": rng.random(33 * 33).astype(np.float32)}
+    big = {"velocity": rng.random(6 * 10 ** 6), "pressure": rng.random(3 * 10 ** 6)}
+
+    def dump(name, arrays, world=1):
+        d = tmp_path / name
+        for r in range(world):
+            bench._dump_outputs(types.SimpleNamespace(dump_outputs=str(d)), r, world, arrays)
+        return {f.name: np.load(f) for f in sorted(d.iterdir())}, sum(f.stat().st_size for f in d.iterdir())
+
+    out, _ = dump("small", small)
+    assert sorted(out) == ["pressure.npy", "velocity.npy"] and all(a.dtype == np.float64 for a in out.values())
+    assert np.array_equal(out["velocity.npy"], small["velocity"]) and np.array_equal(out["pressure.npy"], small["pressure"])
+    out1, size1 = dump("big1", big)
+    out2, _ = dump("big2", big)
+    assert size1 <= bench.DUMP_LIMIT_BYTES and out1["velocity.npy"].size > 0.9 * bench.DUMP_LIMIT_BYTES / 8 * 2 / 3
+    for k in out1:
+        assert np.array_equal(out1[k], out2[k]) and np.isin(out1[k], big[k.split(".")[0]]).all()
+    outr, sizer = dump("ranks", big, world=2)
+    assert sorted(outr) == ["pressure.rank0.npy", "pressure.rank1.npy", "velocity.rank0.npy", "velocity.rank1.npy"]
+    assert sizer <= bench.DUMP_LIMIT_BYTES
+    bench._dump_outputs(types.SimpleNamespace(dump_outputs=None), 0, 1, small)       # (no flag: a no-op)
+
+
 def test_row_parallel_sparse_product_equals_the_serial_product_bitwise(monkeypatch):
     """Set-up of the algebraic Schur Laplacian (multigrid.attach_schur_laplacian): the sparse products D W D^T and
     P^T A P run in row blocks on host threads -- same arrays as scipy's serial product, bit for bit, sorted columns,

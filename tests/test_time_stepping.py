@@ -85,41 +85,51 @@ def test_end_snapping():
 
 
 # ---------------------------------------------------------------- IMEX / theta schemes
+IMEX_THETA = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "imex_theta_tables.json")))
+
+
+def check_imex_case(case):
+    """one IMEX trajectory of tests/golden/imex_theta_tables.json, exact equality"""
+    from imex_time_stepping import IMEXTimeStepping, IMEXType
+    ts = IMEXTimeStepping(case["start"], case["end"], IMEXType[case["kind"]],
+                          desired_start_time_step=case["first_step"])
+    assert ts.n_levels == case["n_levels"] and ts.n_substeps == case["n_substeps"]
+    for row, k in zip(case["rows"], case["sizes"]):
+        ts.set_desired_next_step_size(k)
+        ts.update_coefficients()
+        assert ts.step_number == row["step"] and ts.get_next_step_size() == row["next_step"]
+        assert list(ts.alpha) == row["alpha"] and list(ts.beta) == row["beta"]
+        assert list(ts.gamma) == row["gamma"] and list(ts.eta) == row["eta"]
+        assert ts.coefficients_changed == row["changed"]
+        ts.advance_time()
+    ts.restart()
+    assert list(ts.alpha) == [1.0, -1.0, 0.0] and list(ts.eta) == [1.0, 0.0]
+
+
+def check_theta_case(case):
+    """one theta-scheme trajectory of tests/golden/imex_theta_tables.json, exact equality"""
+    from theta_time_stepping import GeneralThetaTimeStepping, ThetaTimeSteppingType
+    ts = GeneralThetaTimeStepping(case["start"], case["end"], ThetaTimeSteppingType[case["kind"]],
+                                  desired_start_time_step=case["first_step"])
+    assert [list(t) for t in ts.theta] == case["theta"]
+    assert ts.n_levels == case["n_levels"] and ts.n_steps == case["n_steps"]
+    for row, k in zip(case["rows"], case["sizes"]):
+        ts.set_desired_next_step_size(k)
+        ts.update_coefficients()
+        assert ts.step_number == row["step"]
+        assert list(ts.intermediate_timesteps) == row["steps"]
+        assert [list(r) for r in ts.intermediate_times] == row["times"]
+        ts.advance_time()
+
+
 def test_imex_and_theta_time_stepping_match_reference_trajectories():
     """coefficient trajectories generated by the reference's own source/imex_time_stepping.py and
     source/theta_time_stepping.py (tests/golden/gen_imex_theta_golden.py): exact equality"""
-    import json
-    import os
     from imex_time_stepping import IMEXTimeStepping, IMEXType
-    from theta_time_stepping import GeneralThetaTimeStepping, ThetaTimeSteppingType
-    here = os.path.dirname(os.path.abspath(__file__))
-    data = json.load(open(os.path.join(here, "golden", "imex_theta_tables.json")))
-    for case in data["imex"]:
-        ts = IMEXTimeStepping(case["start"], case["end"], IMEXType[case["kind"]],
-                              desired_start_time_step=case["first_step"])
-        assert ts.n_levels == case["n_levels"] and ts.n_substeps == case["n_substeps"]
-        for row, k in zip(case["rows"], case["sizes"]):
-            ts.set_desired_next_step_size(k)
-            ts.update_coefficients()
-            assert ts.step_number == row["step"] and ts.get_next_step_size() == row["next_step"]
-            assert list(ts.alpha) == row["alpha"] and list(ts.beta) == row["beta"]
-            assert list(ts.gamma) == row["gamma"] and list(ts.eta) == row["eta"]
-            assert ts.coefficients_changed == row["changed"]
-            ts.advance_time()
-        ts.restart()
-        assert list(ts.alpha) == [1.0, -1.0, 0.0] and list(ts.eta) == [1.0, 0.0]
-    for case in data["theta"]:
-        ts = GeneralThetaTimeStepping(case["start"], case["end"], ThetaTimeSteppingType[case["kind"]],
-                                      desired_start_time_step=case["first_step"])
-        assert [list(t) for t in ts.theta] == case["theta"]
-        assert ts.n_levels == case["n_levels"] and ts.n_steps == case["n_steps"]
-        for row, k in zip(case["rows"], case["sizes"]):
-            ts.set_desired_next_step_size(k)
-            ts.update_coefficients()
-            assert ts.step_number == row["step"]
-            assert list(ts.intermediate_timesteps) == row["steps"]
-            assert [list(r) for r in ts.intermediate_times] == row["times"]
-            ts.advance_time()
+    for case in IMEX_THETA["imex"]:
+        check_imex_case(case)
+    for case in IMEX_THETA["theta"]:
+        check_theta_case(case)
     # second-order consistency of the IMEX weights at a constant step: sum alpha = 0, sum gamma = 1
     ts = IMEXTimeStepping(0.0, 1.0, IMEXType.mCNAB, desired_start_time_step=0.1)
     for _ in range(3):
