@@ -470,7 +470,8 @@ class NsfemContext:
                     longest_row=abs(int(out[2])), bitwise_exact=int(out[2]) < 0, csr_bytes=int(out[3]))
 
     def mg_apply(self, which, r):
-        """one cycle z = M^-1 r of the pressure (which=0) or velocity (which=1) multigrid preconditioner"""
+        """one cycle z = M^-1 r of the pressure (which=0) or velocity (which=1) multigrid preconditioner; which=2: the
+        fast-diagonalisation solve z = A^+ r (strip factors: a collective, every rank calls it)"""
         r = np.ascontiguousarray(r, dtype=np.float64)
         z = np.zeros_like(r)
         self._check(self._lib.nsfem_mg_apply(self._h, int(which), _dp(r), _dp(z)))

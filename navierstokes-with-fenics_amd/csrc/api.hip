@@ -1074,17 +1074,22 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   }
   launch_dot(s, np, w.r.p, w.r.p, parts + PB0 * kParts);
   const double* base = c->state[NSFEM_P_OLD].p;
+  // (local names for the two work vectors: refinement alternates them without permuting the KrylovWork buffers,
+  // whose pointers the captured graphs of the other solvers hold)
+  double* r = w.r.p;
+  double* q = w.q.p;
   info.iterations = 0;
   info.converged = 0;
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
-    if (dist) c->fd_p.apply_strip(s, c->comm, w.r.p, w.z.p);
-    else c->fd_p.apply(s, w.r.p, w.z.p);
+    if (dist) c->fd_p.apply_strip(s, c->comm, r, w.z.p);
+    else c->fd_p.apply(s, r, w.z.p);
     launch_axpby(s, np, 1.0, base, 1.0, w.z.p, c->state[NSFEM_P].p);          // p = p_old + z (later passes: p += z)
     base = c->state[NSFEM_P].p;
     ++info.iterations;
-    launch_residual(s, c->Ap, 1, w.z.p, w.r.p, w.q.p, gm, gm ? MASK_ZERO : MASK_NONE);    // q = r - A z
-    launch_dot(s, np, w.q.p, w.q.p, parts + PR * kParts);
-    if (dist) c->comm->allreduce_sum(s, parts + PR * kParts, (PB0 - PR + 1) * kParts);    // (slots 10 ... 13)
+    launch_residual(s, c->Ap, 1, w.z.p, r, q, gm, gm ? MASK_ZERO : MASK_NONE);    // q = r - A z
+    launch_dot(s, np, q, q, parts + PR * kParts);
+    // (slots 10 ... 13 in the first pass, |r|^2 included; afterwards slot PB0 already holds the global sum)
+    if (dist) c->comm->allreduce_sum(s, parts + PR * kParts, (pass == 0 ? PB0 - PR + 1 : 1) * kParts);
     double qq, rr;
     host_sum_parts2(s, w, PR, PB0, qq, rr);
     if (!std::isfinite(qq)) return NSFEM_ERR_BREAKDOWN;
@@ -1094,7 +1099,7 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
     info.residual = std::sqrt(qq);
     if (pass == 0) info.residual0 = rnorm;
     if (info.residual <= target) { info.converged = 1; break; }
-    std::swap(w.r.p, w.q.p);                                                   // refine: the residual is the next right-hand side
+    std::swap(r, q);                                                           // refine: the residual is the next right-hand side
   }
   return info.converged ? NSFEM_OK : NSFEM_ERR_NOT_CONVERGED;
 }
@@ -2031,7 +2036,12 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   {
     nsfem_solve_info si;
     int rc;
-    if (opts->poisson.precond == 3 && ctx->nbc_p == 0 && ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip()) {
+    // (every rank must take the same branch: the pressure Dirichlet set is judged globally)
+    const bool fd = opts->poisson.precond == 3;
+    NSFEM_REQUIRE(!fd || !ctx->distributed() || !pressure_pinned_anywhere(ctx),
+                  "fast diagonalisation on a partitioned mesh solves the pure Neumann projection step only "
+                  "(pressure Dirichlet nodes are set): use another Poisson preconditioner");
+    if (fd && !pressure_pinned_anywhere(ctx) && ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip()) {
       rc = poisson_direct_step(ctx, opts->poisson, si);
     } else {
       poisson_assemble(ctx, opts->pressure_extrapolation != 0);
@@ -2656,8 +2666,9 @@ extern "C" int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32
 }
 
 // Test hook: one application z = M^-1 r of a multigrid preconditioner on host vectors -- which = 0 pressure Poisson
-// hierarchy (mg_p), 1 velocity hierarchy (mg_v, the identity rows of the Newton preconditioner included).  Lets the
-// parity tests compare the fused multi-level launches (mglegs.hip) with the separate launches cycle by cycle.
+// hierarchy (mg_p), 1 velocity hierarchy (mg_v, the identity rows of the Newton preconditioner included), 2 the
+// fast-diagonalisation solve z = A^+ r (FastDiag::apply; on strip factors FastDiag::apply_strip, a collective).  Lets
+// the parity tests compare the fused multi-level launches (mglegs.hip) with the separate launches cycle by cycle.
 extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double* z) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && r && z && (which == 0 || which == 1 || which == 2), "bad argument");
@@ -2667,7 +2678,13 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
     DevBuf<double> dr, dz;
     dr.upload(r, (size_t)n, s);
     dz.alloc((size_t)n);
-    ctx->fd_p.apply(s, dr.p, dz.p);
+    if (ctx->fd_p.strip()) {           // strips (a collective: every rank calls it): ghost rows zeroed, as the step does
+      NSFEM_REQUIRE(ctx->distributed(), "strip factors need a partitioned context");
+      launch_zero_ghost(s, n, ctx->mask_p.p, dr.p);
+      ctx->fd_p.apply_strip(s, ctx->comm, dr.p, dz.p);
+    } else {
+      ctx->fd_p.apply(s, dr.p, dz.p);
+    }
     NSFEM_HIP(hipMemcpyAsync(z, dz.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     NSFEM_HIP(hipStreamSynchronize(s));
     return NSFEM_OK;

@@ -846,13 +846,17 @@ def TaylorHoodDofMapOf(mesh):
     return TaylorHoodDofMap(mesh)
 
 
-def test_n512_production_solver_options_match_the_exact_solver_run():
+@pytest.mark.parametrize("poisson", ["fd", "mg"])
+def test_n512_production_solver_options_match_the_exact_solver_run(poisson):
     """What bench.py times, at the size it times it (BASELINE configs[1], 2,364,419 dofs):
     geometric multigrid (V(0,3) momentum / V(2,2) Poisson), truncated velocity cycle (4, 0.1),
     Chebyshev mass solve, inexact Newton (forcing 1e-4), Krylov rtol 1e-8, iteration hints --
     against the same mesh and steps with direct-solver accuracy (Krylov rtol 1e-12, exact Newton,
     Jacobi-CG mass solve, untruncated cycle).  Fields must agree to north_star's nonlinear
-    tolerance 1e-6 (pressure modulo a constant: enclosed flow)."""
+    tolerance 1e-6 (pressure modulo a constant: enclosed flow).  poisson = "fd": the production run
+    solves the projection step as bench.py's default does, by fast diagonalisation (precond = 3, one pass per step);
+    the exact run stays multigrid-CG at rtol 1e-12, an independent solver."""
+    import poisson_fd as pf
     from multigrid import attach_hierarchy
     mesh, dm, marks = box(512, 512)
     ctx = context(mesh, dm)
@@ -861,6 +865,9 @@ def test_n512_production_solver_options_match_the_exact_solver_run():
     bd, bv = cavity_bc(dm, marks)
     ctx.set_dirichlet(nat.VELOCITY, bd, bv)
     ctx.set_dirichlet(nat.PRESSURE, np.zeros(0, np.int32), np.zeros(0))
+    if poisson == "fd":
+        xs = np.linspace(0.0, 1.0, 513)
+        ctx.poisson_set_fast_diag(pf.factors(xs, xs, np.zeros(0, np.int64)))
     n_steps, k = 6, 1.0e-3
 
     def run(production):
@@ -876,6 +883,8 @@ def test_n512_production_solver_options_match_the_exact_solver_run():
                 o.rtol = 1.0e-8
             opts.correction.precond = 2
             opts.newton_forcing = 1.0e-4
+            if poisson == "fd":
+                opts.poisson.precond = 3
         else:
             ctx.mg_set_truncation(0.0, 0.1)
         its = []
@@ -892,6 +901,8 @@ def test_n512_production_solver_options_match_the_exact_solver_run():
 
     u_fast, p_fast, its_fast = run(True)
     u_ref, p_ref, its_ref = run(False)
+    if poisson == "fd":
+        assert [i[2] for i in its_fast] == [1] * n_steps
     assert np.abs(u_fast[bd] - bv).max() == 0.0
     assert rel(u_fast, u_ref) < 1e-6
     assert rel(p_fast - p_fast.mean(), p_ref - p_ref.mean()) < 1e-6

@@ -53,7 +53,8 @@ def _run(ctx, dm, nsteps, k, use_mg, out, key, cheb=False):
     out[("comm", key)] = ctx.comm_stats()
 
 
-@pytest.mark.parametrize("n,size,relaxed", [(32, 2, False), (64, 4, True), (48, 3, False)])
+@pytest.mark.parametrize("n,size,relaxed", [(32, 2, False), (64, 4, True), (48, 3, False), (128, 4, False),
+                                             (128, 8, True)])
 def test_partitioned_fast_diagonalisation_projection_equals_single_context(n, size, relaxed):
     """Projection step by fast diagonalisation on strips (nsfem_poisson_set_fast_diag_rows, csrc/fastdiag.hip): every
     rank keeps the rows of V_y of its own lattice lines, the contraction over y is ONE all-reduce of (n + 1)^2 doubles;
