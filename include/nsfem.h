@@ -222,7 +222,17 @@ int nsfem_operator_apply(nsfem_ctx* ctx, int op, const double* x, double* y);
  *            launch), 4 multi-step lattice kernel (all steps in one launch; epilogue 3 only)
  *   epilogue 0  y = A x   1  y = b - A x   3  `steps` steps  d = c1[k] d + c2[k] D^-1 (b - A x), x += d
  *   maskmode 0 none, 1 identity rows, 2 zero rows (flags in `mask`, one per vector entry; flag 2 = ghost)
- * Outputs: y (result / last iterate), d_out, r_out (b - A y when with_residual), and which family ran. */
+ * Outputs: y (result / last iterate), d_out, r_out (b - A y when with_residual), and which family ran.
+ * Family 4 only -- the launches the multigrid cycles make (W x H: the operator's lattice):
+ *   xc          host [((W + 1) / 2) ((H + 1) / 2) nv] or NULL: fused prolongation, start = [x +] P xc (x may be
+ *               NULL: start = P xc alone; rows flagged in the mask start at 0)
+ *   rf          host [(2 W - 1) (2 H - 1) nv] or NULL: fused restriction, b = R rf (flagged rows 0); b is not read
+ *   b_formed    host [n * nv] or NULL: the right-hand side the launch stored (with rf)
+ *   gh_lo, gh_hi, gh_zero   frozen ghost lines of a partitioned strip (flag every component of their rows)
+ *   tile_lines  0 the launcher's choice; 16, 24, 32 or 48 forced (refused when the halo does not fit)
+ *   fixed       -1 default (NSFEM_LATTICE_FIXED), 0 compile-time-offset stages off, 1 on
+ *   lattice_*   out: the geometry of the launch and its fixed_shape */
+
 typedef struct {
   int32_t space, nv, family, epilogue, steps, maskmode, ghost, ident, from_zero, with_residual, dict_ok;
   int32_t used_family;        /* out */
@@ -233,8 +243,18 @@ typedef struct {
   const double *x, *b, *d;    /* host [n * nv]; b, d may be NULL */
   const uint8_t* mask;        /* host [n * nv] or NULL */
   double *y, *d_out, *r_out;  /* host [n * nv]; d_out, r_out may be NULL */
+  const double *xc, *rf;
+  double* b_formed;
+  int32_t gh_lo, gh_hi, gh_zero, tile_lines, fixed;
+  int32_t lattice_tile_lines, lattice_tx, lattice_ty, lattice_tiles, lattice_fixed_shape;   /* out */
 } nsfem_kernel_test;
 int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t);
+/* Test hook: the standalone restrictions of a lattice hierarchy on host data.  levels = 1: b1 = R rf through
+ * k_restrict_lattice, coarse lattice w x h, fine (2 w - 1) x (2 h - 1), rows flagged in mask1 get 0.  levels = 2:
+ * b1 = R rf, b2 = R b1 through k_restrict_lattice2, coarsest lattice w x h (mask2), middle (2 w - 1) x (2 h - 1)
+ * (b1, mask1), fine (4 w - 3) x (4 h - 3).  nv = 1 or 2 interleaved components; masks may be NULL. */
+int nsfem_lattice_restrict(nsfem_ctx* ctx, int nv, int levels, int w, int h, const double* rf, const uint8_t* mask1,
+                           const uint8_t* mask2, double* b1, double* b2);
 
 /* ---- multigrid hierarchy (optional).  Coarse P1 levels are added finest-first; each
  * carries its mesh and the prolongation P (CSR, rows = nodes of the previous finer P1

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_state", "nsfem_get_state", "nsfem_state_size", "nsfem_state_devptr",
     "nsfem_assemble", "nsfem_residual_norm", "nsfem_get_rhs", "nsfem_solve",
     "nsfem_operator_shape", "nsfem_operator_export", "nsfem_operator_apply", "nsfem_kernel_apply",
+    "nsfem_lattice_restrict",
     "nsfem_default_step_opts", "nsfem_step_ipcs", "nsfem_step_bdf", "nsfem_advance",
     "nsfem_shift_mean_pressure", "nsfem_time_spmv", "nsfem_synchronize", "nsfem_mass_solve",
     "nsfem_mg_add_level", "nsfem_mg_finalize", "nsfem_mg_set_global_coarse", "nsfem_mg_set_global_coarse_constrained",
@@ -55,7 +56,10 @@ class KernelTest(C.Structure):
                [("a", C.c_double), ("b_coef", C.c_double), ("c1", C.c_double * 8), ("c2", C.c_double * 8),
                 ("x", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("d", C.POINTER(C.c_double)),
                 ("mask", C.POINTER(C.c_uint8)),
-                ("y", C.POINTER(C.c_double)), ("d_out", C.POINTER(C.c_double)), ("r_out", C.POINTER(C.c_double))]
+                ("y", C.POINTER(C.c_double)), ("d_out", C.POINTER(C.c_double)), ("r_out", C.POINTER(C.c_double)),
+                ("xc", C.POINTER(C.c_double)), ("rf", C.POINTER(C.c_double)), ("b_formed", C.POINTER(C.c_double))] + \
+               [(k, C.c_int32) for k in ("gh_lo", "gh_hi", "gh_zero", "tile_lines", "fixed", "lattice_tile_lines",
+                                          "lattice_tx", "lattice_ty", "lattice_tiles", "lattice_fixed_shape")]
 
 
 class KrylovOpts(C.Structure):
@@ -172,6 +176,8 @@ def load_library(path=None):
         "nsfem_operator_export": (C.c_int, [vp, C.c_int, pi, pi, pd]),
         "nsfem_operator_apply": (C.c_int, [vp, C.c_int, pd, pd]),
         "nsfem_kernel_apply": (C.c_int, [vp, C.POINTER(KernelTest)]),
+        "nsfem_lattice_restrict": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, pd, C.POINTER(C.c_uint8),
+                                             C.POINTER(C.c_uint8), pd, pd]),
         "nsfem_default_step_opts": (C.c_int, [C.POINTER(StepOpts)]),
         "nsfem_step_ipcs": (C.c_int, [vp, C.POINTER(StepOpts), C.POINTER(StepInfo)]),
         "nsfem_step_bdf": (C.c_int, [vp, C.POINTER(StepOpts), C.POINTER(StepInfo)]),
@@ -636,9 +642,14 @@ class NsfemContext:
 
     def kernel_apply(self, space, nv, x, a=1.0, b_coef=0.0, family=0, epilogue=0, b=None, d=None, mask=None,
                      maskmode=0, steps=0, c1=(), c2=(), ghost=0, ident=False, from_zero=False,
-                     with_residual=False, dict_ok=True):
+                     with_residual=False, dict_ok=True, xc=None, rf=None, gh_lo=0, gh_hi=0, gh_zero=False,
+                     tile_lines=0, fixed=-1):
         """test hook (nsfem_kernel_apply): product / residual / smoothing sequence of a M + b K through a chosen
-        kernel family; returns dict(y, d, r, used_family, dict_entries, dict_exact, lattice_w)"""
+        kernel family; returns dict(y, d, r, used_family, dict_entries, dict_exact, lattice_w).  Lattice kernel
+        (family 4) only: xc (fused prolongation; x may then be None), rf (fused restriction: the stored right-hand
+        side comes back as b_formed), frozen ghost lines, a forced tile height and the fixed-offset stages on / off;
+        the launch geometry comes back as lattice_tile_lines, lattice_tx, lattice_ty, lattice_tiles,
+        lattice_fixed_shape"""
         t = KernelTest()
         t.space, t.nv, t.family, t.epilogue, t.steps = int(space), int(nv), int(family), int(epilogue), int(steps)
         t.maskmode, t.ghost, t.ident = int(maskmode), int(ghost), 1 if ident else 0
@@ -657,10 +668,19 @@ class NsfemContext:
             keep.append(v)
             return v
         x = arr(x)
-        n = x.size
+        n = x.size if x is not None else (self.n_p2 if space == 0 else self.n_p1) * int(nv)
         bb, dd, mm = arr(b), arr(d), arr(mask, np.uint8)
-        y, d_out, r_out = np.empty(n), np.empty(n), np.empty(n)
-        t.x, t.y, t.d_out, t.r_out = _dp(x), _dp(y), _dp(d_out), _dp(r_out)
+        y, d_out, r_out, b_formed = np.empty(n), np.empty(n), np.empty(n), np.zeros(n)
+        t.y, t.d_out, t.r_out = _dp(y), _dp(d_out), _dp(r_out)
+        if x is not None:
+            t.x = _dp(x)
+        xcc, rff = arr(xc), arr(rf)
+        if xcc is not None:
+            t.xc = _dp(xcc)
+        if rff is not None:
+            t.rf, t.b_formed = _dp(rff), _dp(b_formed)
+        t.gh_lo, t.gh_hi, t.gh_zero = int(gh_lo), int(gh_hi), 1 if gh_zero else 0
+        t.tile_lines, t.fixed = int(tile_lines), int(fixed)
         if bb is not None:
             assert bb.size == n
             t.b = _dp(bb)
@@ -672,7 +692,30 @@ class NsfemContext:
             t.mask = mm.ctypes.data_as(C.POINTER(C.c_uint8))
         self._check(self._lib.nsfem_kernel_apply(self._h, C.byref(t)))
         return dict(y=y, d=d_out, r=r_out, used_family=int(t.used_family), dict_entries=int(t.dict_entries),
-                    dict_exact=bool(t.dict_exact), lattice_w=int(t.lattice_w))
+                    dict_exact=bool(t.dict_exact), lattice_w=int(t.lattice_w),
+                    b_formed=b_formed if rff is not None else None,
+                    lattice_tile_lines=int(t.lattice_tile_lines), lattice_tx=int(t.lattice_tx),
+                    lattice_ty=int(t.lattice_ty), lattice_tiles=int(t.lattice_tiles),
+                    lattice_fixed_shape=int(t.lattice_fixed_shape))
+
+    def lattice_restrict(self, nv, w, h, rf, mask1=None, mask2=None, levels=1):
+        """test hook (nsfem_lattice_restrict): levels = 1: b1 = R rf (k_restrict_lattice) onto the w x h lattice;
+        levels = 2: b1 = R rf, b2 = R b1 (k_restrict_lattice2), w x h the coarsest lattice.  Returns (b1, b2)."""
+        w1, h1 = (w, h) if levels == 1 else (2 * w - 1, 2 * h - 1)
+        f = np.ascontiguousarray(rf, dtype=np.float64)
+        assert f.size == (2 * w1 - 1) * (2 * h1 - 1) * nv
+        m1 = None if mask1 is None else np.ascontiguousarray(mask1, dtype=np.uint8)
+        m2 = None if mask2 is None else np.ascontiguousarray(mask2, dtype=np.uint8)
+        assert m1 is None or m1.size == w1 * h1 * nv
+        assert m2 is None or m2.size == w * h * nv
+        b1 = np.empty(w1 * h1 * nv)
+        b2 = np.empty(w * h * nv) if levels == 2 else None
+        up = C.POINTER(C.c_uint8)
+        self._check(self._lib.nsfem_lattice_restrict(
+            self._h, int(nv), int(levels), int(w), int(h), _dp(f),
+            None if m1 is None else m1.ctypes.data_as(up), None if m2 is None else m2.ctypes.data_as(up),
+            _dp(b1), None if b2 is None else _dp(b2)))
+        return b1, b2
 
     def set_preconditioner_shift(self, shift):
         self._check(self._lib.nsfem_set_preconditioner_shift(self._h, float(shift)))

@@ -2548,8 +2548,11 @@ extern "C" int nsfem_operator_apply(nsfem_ctx* ctx, int op, const double* x, dou
 // parity tests pin every SpMV kernel family and every epilogue to the oracle's matrices directly.
 extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
   API_BEGIN
-  NSFEM_REQUIRE(ctx && t && t->x && t->y, "null argument");
+  NSFEM_REQUIRE(ctx && t && (t->x || (t->family == 4 && t->epilogue == 3 && (t->xc || t->from_zero))) && t->y,
+                "null argument");
   NSFEM_REQUIRE(t->nv >= 1 && t->nv <= 3 && t->steps >= 0 && t->steps <= 8, "bad kernel test description");
+  NSFEM_REQUIRE(t->family == 4 || !(t->xc || t->rf || t->gh_lo || t->gh_hi || t->tile_lines),
+                "fused transfers, ghost lines and launch overrides are lattice kernel (family 4) inputs");
   hipStream_t s = ctx->stream;
   const bool p2 = t->space == 0;
   const Pattern& pat = p2 ? ctx->p22 : ctx->p11;
@@ -2571,7 +2574,7 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
   const size_t n = (size_t)pat.n_rows * nv;
   DevBuf<double> x, b, d, d2, y, y2, r, dinv;
   DevBuf<uint8_t> mask;
-  x.upload(t->x, n, s);
+  if (t->x) x.upload(t->x, n, s);
   y.alloc(n); y.zero(s);
   y2.alloc(n); y2.zero(s);
   r.alloc(n); r.zero(s);
@@ -2602,14 +2605,39 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
     t->used_family = picked(false);
     launch_residual(s, T, nv, x.p, b.p, y.p, mk, mk ? t->maskmode : MASK_NONE);
   } else {
-    NSFEM_REQUIRE(t->b && t->steps >= 1, "smoothing needs b and steps >= 1");
+    NSFEM_REQUIRE((t->b || (family == 4 && t->rf)) && t->steps >= 1, "smoothing needs b and steps >= 1");
     if (family == 4) {
       t->used_family = 4;
-      NSFEM_REQUIRE(t->steps <= lattice_smoother_max_steps(T, t->from_zero != 0, t->with_residual != 0),
+      NSFEM_REQUIRE(!(t->from_zero && t->xc), "lattice kernel: a zero start takes no coarse correction");
+      const bool fz = t->from_zero != 0;
+      NSFEM_REQUIRE(t->steps <= lattice_smoother_max_steps(T, fz, t->with_residual != 0),
                     "too many steps for one launch of the lattice kernel");
-      launch_cheb_lattice(s, T, nv, t->from_zero ? nullptr : x.p, b.p, (t->d && !t->from_zero) ? d.p : nullptr, y.p,
-                          d2.p, t->with_residual ? r.p : nullptr, mk, t->steps, t->c1, t->c2, t->ident);
+      // fused transfers: the coarse (even-even sublattice) and the finer lattice of this level
+      const StencilDict& D = *T.dict;
+      const size_t nc = (size_t)((D.lat_w + 1) / 2) * ((D.lat_h + 1) / 2) * nv;
+      const size_t nf = (size_t)(2 * D.lat_w - 1) * (2 * D.lat_h - 1) * nv;
+      DevBuf<double> xc, rf, bo;
+      if (t->xc) xc.upload(t->xc, nc, s);
+      if (t->rf) {
+        rf.upload(t->rf, nf, s);
+        bo.alloc(n);
+        bo.zero(s);
+      }
+      LatticeLaunchOverride ov;
+      ov.tile_lines = t->tile_lines;
+      ov.fixed = t->fixed;
+      launch_cheb_lattice(s, T, nv, (fz || !t->x) ? nullptr : x.p, b.p, (t->d && !fz) ? d.p : nullptr, y.p,
+                          d2.p, t->with_residual ? r.p : nullptr, mk, t->steps, t->c1, t->c2, t->ident, nullptr,
+                          t->xc ? xc.p : nullptr, t->rf ? rf.p : nullptr, t->rf ? bo.p : nullptr, t->gh_lo, t->gh_hi,
+                          t->gh_zero, &ov);
       NSFEM_HIP(hipMemcpyAsync(d.p, d2.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+      if (t->rf && t->b_formed) NSFEM_HIP(hipMemcpyAsync(t->b_formed, bo.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+      NSFEM_HIP(hipStreamSynchronize(s));      // (before the transfer buffers go out of scope)
+      t->lattice_tile_lines = ov.used_tile_lines;
+      t->lattice_tx = ov.tx;
+      t->lattice_ty = ov.ty;
+      t->lattice_tiles = ov.tiles;
+      t->lattice_fixed_shape = ov.fixed_shape;
     } else {
       t->used_family = picked(true);
       dinv.alloc(n);
@@ -2633,6 +2661,39 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
   t->dict_entries = have_dict ? dict.n_stencils : 0;
   t->dict_exact = have_dict && dict.exact ? 1 : 0;
   t->lattice_w = have_dict ? dict.lat_w : 0;
+  API_END(ctx)
+}
+
+// Test hook: the standalone restrictions of a lattice hierarchy (k_restrict_lattice, k_restrict_lattice2) on host data
+extern "C" int nsfem_lattice_restrict(nsfem_ctx* ctx, int nv, int levels, int w, int h, const double* rf,
+                                      const uint8_t* mask1, const uint8_t* mask2, double* b1, double* b2) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && rf && b1 && (levels == 1 || (levels == 2 && b2)), "null argument");
+  NSFEM_REQUIRE(nv >= 1 && nv <= 2 && w >= 1 && h >= 1, "bad restriction description");
+  hipStream_t s = ctx->stream;
+  const int w1 = levels == 1 ? w : 2 * w - 1, h1 = levels == 1 ? h : 2 * h - 1;
+  const int wf = 2 * w1 - 1, hf = 2 * h1 - 1;
+  const size_t n1 = (size_t)w1 * h1 * nv, n2 = (size_t)w * h * nv, nf = (size_t)wf * hf * nv;
+  DevBuf<double> f, o1, o2;
+  DevBuf<uint8_t> m1, m2;
+  f.upload(rf, nf, s);
+  o1.alloc(n1);
+  o1.zero(s);
+  if (mask1) m1.upload(mask1, n1, s);
+  if (levels == 1) {
+    NSFEM_REQUIRE(launch_restrict_lattice(s, nv, w1, h1, wf, hf, f.p, mask1 ? m1.p : nullptr, o1.p),
+                  "restriction: lattices do not nest");
+  } else {
+    o2.alloc(n2);
+    o2.zero(s);
+    if (mask2) m2.upload(mask2, n2, s);
+    NSFEM_REQUIRE(launch_restrict_lattice2(s, nv, w, h, w1, h1, wf, hf, f.p, mask1 ? m1.p : nullptr,
+                                           mask2 ? m2.p : nullptr, o1.p, o2.p),
+                  "restriction: lattices do not nest");
+    NSFEM_HIP(hipMemcpyAsync(b2, o2.p, sizeof(double) * n2, hipMemcpyDeviceToHost, s));
+  }
+  NSFEM_HIP(hipMemcpyAsync(b1, o1.p, sizeof(double) * n1, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
   API_END(ctx)
 }
 

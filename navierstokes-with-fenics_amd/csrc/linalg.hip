@@ -1617,7 +1617,7 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
                          const double* d_in, double* x_out, double* d_out, double* r_out,
                          const uint8_t* mask, int steps, const double* c1, const double* c2, int ident,
                          const uint8_t* sidm, const double* xc, const double* rf, double* b_out, int gh_lo, int gh_hi,
-                         int gh_zero) {
+                         int gh_zero, LatticeLaunchOverride* ovr) {
   const StencilDict& d = *A.dict;
   NSFEM_REQUIRE(steps >= 1 && steps <= 8, "lattice smoother: 1..8 steps per launch");
   NSFEM_REQUIRE(gh_lo >= 0 && gh_hi >= 0 && gh_lo + gh_hi < d.lat_h && !((gh_lo || gh_hi) && (xc || rf)),
@@ -1632,7 +1632,8 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   // entries of canonical interior shape (compile-time LDS offsets in the stages; NSFEM_LATTICE_FIXED=0: off)
   ensure_fixed_masks(d);
   static const bool fixed_on = [] { const char* e = std::getenv("NSFEM_LATTICE_FIXED"); return e ? std::atoi(e) != 0 : true; }();
-  a.fixed_shape = (fixed_on && d.fixed_shape > 0) ? d.fixed_shape : 0;
+  const bool fixed_use = (ovr && ovr->fixed >= 0) ? ovr->fixed != 0 : fixed_on;
+  a.fixed_shape = (fixed_use && d.fixed_shape > 0) ? d.fixed_shape : 0;
   for (int c = 0; c < 4; ++c) a.fixed_mask[c] = a.fixed_shape ? d.fixed_mask[c] : 0ull;
   a.Wc = (d.lat_w + 1) / 2; a.Wf = 2 * d.lat_w - 1; a.Hf = 2 * d.lat_h - 1;
   a.Mv = steps - a.from_zero + (r_out ? 1 : 0);
@@ -1656,6 +1657,13 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   static const int tall_from = [] { const char* e = std::getenv("NSFEM_LATTICE_TALL_FROM"); return e ? std::atoi(e) : 2000000; }();
   if (nn >= tall_from && a.H >= 96) eh = 48;
   if (force_eh == 16 || force_eh == 24 || force_eh == 32 || force_eh == 48) eh = force_eh;
+  if (ovr && ovr->tile_lines != 0) {
+    // (a forced height is one the rule below could pick for this halo, or the call is refused)
+    const int f = ovr->tile_lines;
+    NSFEM_REQUIRE(f == 16 || f == 24 || f == 32 || f == 48, "lattice smoother: tile height 16, 24, 32 or 48");
+    NSFEM_REQUIRE(f >= 32 || f - 2 * a.Ge >= 8, "lattice smoother: halo too wide for the forced tile height");
+    eh = f;
+  }
   while (eh < 32 && eh - 2 * a.Ge < 8) eh += 8;
   const int tmx = 64 - 2 * a.Ge, tmy = eh - 2 * a.Ge;
   NSFEM_REQUIRE(tmx >= 2 && tmy >= 2, "lattice smoother: halo too wide for the tile");
@@ -1665,6 +1673,13 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   a.ntx = (a.W + a.TX - 1) / a.TX;
   a.ntiles = a.ntx * ((a.H + a.TY - 1) / a.TY);
   a.EHh = eh / 2;
+  if (ovr) {
+    ovr->used_tile_lines = eh;
+    ovr->tx = a.TX;
+    ovr->ty = a.TY;
+    ovr->tiles = a.ntiles;
+    ovr->fixed_shape = a.fixed_shape;
+  }
   a.ident = ident;
   a.x_in = x_in; a.b = b; a.d_in = d_in; a.x_out = x_out; a.d_out = d_out; a.r_out = r_out;
   a.sid = d.sid8.p; a.mask = mask;

@@ -284,11 +284,18 @@ bool lattice_transfers_enabled();
 bool lattice_smoother_available(const BlockMat& A, int nv);
 bool lattice_tables_available(const BlockMat& A, int nv);   // dictionary tables of a 2D lattice operator are in place
 int lattice_smoother_max_steps(const BlockMat& A, bool from_zero, bool with_resid);
+// test hook only: forced launch choices in, the geometry of the launch out
+struct LatticeLaunchOverride {
+  int tile_lines = 0;       // 0: the launcher's choice; 16, 24, 32, 48: forced (refused when the halo does not fit)
+  int fixed = -1;           // -1: NSFEM_LATTICE_FIXED; 0 / 1: compile-time-offset stages off / on
+  int used_tile_lines = 0, tx = 0, ty = 0, tiles = 0, fixed_shape = 0;   // out
+};
 void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double* x_in, const double* b,
                          const double* d_in, double* x_out, double* d_out, double* r_out,
                          const uint8_t* mask, int steps, const double* c1, const double* c2, int ident,
                          const uint8_t* sidm = nullptr, const double* xc = nullptr, const double* rf = nullptr,
-                         double* b_out = nullptr, int gh_lo = 0, int gh_hi = 0, int gh_zero = 0);
+                         double* b_out = nullptr, int gh_lo = 0, int gh_hi = 0, int gh_zero = 0,
+                         LatticeLaunchOverride* ovr = nullptr);
 // out[row] = dictionary entry | (mask of component c) << (6 + c): one byte per row for the lattice kernel
 void launch_lattice_sidm(hipStream_t s, const BlockMat& A, int nv, const uint8_t* mask, uint8_t* out);
 // out = R rf on a lattice hierarchy (rows flagged in the coarse mask: 0); false = shapes do not nest, nothing launched
