@@ -492,6 +492,21 @@ int nsfem_poisson_set_fast_diag(nsfem_ctx* ctx, int32_t W, int32_t H, const doub
    halo exchanges and dot-product reductions of a multigrid-CG solve, and returns the pressure with valid ghost rows. */
 int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32_t H, int32_t first_line, const double* Vx,
                                      const double* Vy, const double* inv);
+/* The same on 3D box lattices (fem_mesh.box_mesh, six Kuhn tetrahedra per cube, any line spacing, periodic directions
+   allowed): Vx [Nx x Nx], Vy [Ny x Ny], Vz [Nz x Nz] the generalised eigenvectors of the three directions (row-major),
+   inv [Nz x Ny x Nx] = 1 / (lambda_z,k + lambda_y,j + lambda_x,i).  The P1 space must be the Nz x Ny x Nx lattice in
+   lexicographic numbering (x fastest).  T, the tensor sum of the 1D stiffness / lumped-mass pairs, is the P1 stiffness
+   matrix itself when exact != 0 (uniform lines, every box edge between two non-periodic faces next to a Dirichlet
+   face): precond = 3 then solves the projection step directly (one pass plus the residual check); with exact == 0 it
+   runs CG preconditioned by T^+ (mesh-independent iteration counts).  Six dense mode products on the matrix cores
+   (csrc/fastdiag3d.hip).  Refused on partitioned contexts.  Replaces 2D factors set before, and vice versa.  Host side:
+   poisson_fd.factors_3d(). */
+int nsfem_poisson_set_fast_diag_3d(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz, const double* Vx,
+                                   const double* Vy, const double* Vz, const double* inv, int32_t exact);
+/* out = {Nx, Ny, Nz, exact, applications of T^+ issued by the host (CG iterations replayed from a captured graph apply
+   it without the host), projection solves that ran with the 3D factors}; zeros when none are set.
+   nsfem_mg_apply(which = 2) applies z = T^+ r when 3D factors are set. */
+int nsfem_poisson_fast_diag_3d_info(nsfem_ctx* ctx, int64_t out[6]);
 int nsfem_mg_info(nsfem_ctx* ctx, int which, int64_t out[4]);
 /* in-situ HIP-event timing of the matrix-free convection action of the velocity Jacobian inside
  * the Newton-Krylov solves (element kernel k_conv_cell / k3_conv_cell + node gather = the

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_partition", "nsfem_comm_unique_id", "nsfem_comm_attach_rccl",
     "nsfem_comm_local_create", "nsfem_comm_local_destroy", "nsfem_comm_attach_local", "nsfem_comm_attach_shm",
     "nsfem_mg_apply", "nsfem_mg_info", "nsfem_poisson_set_fast_diag", "nsfem_poisson_set_fast_diag_rows",
+    "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_fast_diag_3d_info",
     "nsfem_operator_diagonal",
 )
 
@@ -214,6 +215,8 @@ def load_library(path=None):
         "nsfem_poisson_set_fast_diag": (C.c_int, [vp, i32, i32, pd, pd, pd]),
         "nsfem_operator_diagonal": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_poisson_set_fast_diag_rows": (C.c_int, [vp, i32, i32, i32, pd, pd, pd]),
+        "nsfem_poisson_set_fast_diag_3d": (C.c_int, [vp, i32, i32, i32, pd, pd, pd, pd, i32]),
+        "nsfem_poisson_fast_diag_3d_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_halo_lists": (C.c_int, [vp, C.c_int, C.POINTER(HaloLists)]),
         "nsfem_mg_set_global_index": (C.c_int, [vp, i32, pi]),
         "nsfem_comm_allreduce": (C.c_int, [vp, pd, C.c_int, C.c_int]),
@@ -477,7 +480,7 @@ class NsfemContext:
 
     def mg_apply(self, which, r):
         """one cycle z = M^-1 r of the pressure (which=0) or velocity (which=1) multigrid preconditioner; which=2: the
-        fast-diagonalisation solve z = A^+ r (strip factors: a collective, every rank calls it)"""
+        fast-diagonalisation solve z = A^+ r (strip factors: a collective, every rank calls it; 3D factors: z = T^+ r)"""
         r = np.ascontiguousarray(r, dtype=np.float64)
         z = np.zeros_like(r)
         self._check(self._lib.nsfem_mg_apply(self._h, int(which), _dp(r), _dp(z)))
@@ -497,6 +500,25 @@ class NsfemContext:
         else:
             self._check(self._lib.nsfem_poisson_set_fast_diag_rows(self._h, W, H, int(first_line), _dp(vx), _dp(vy),
                                                                    _dp(inv)))
+
+    def poisson_set_fast_diag_3d(self, factors):
+        """factors of poisson_fd.factors_3d(): the projection step may then run with Krylov option precond = 3 -- a
+        direct solve when factors["exact"], CG preconditioned by T^+ otherwise.  Replaces factors set before."""
+        inv = np.ascontiguousarray(factors["inv"], dtype=np.float64)
+        vx, vy, vz = (np.ascontiguousarray(factors[k], dtype=np.float64) for k in ("Vx", "Vy", "Vz"))
+        Nz, Ny, Nx = inv.shape
+        assert vx.shape == (Nx, Nx) and vy.shape == (Ny, Ny) and vz.shape == (Nz, Nz)
+        self._check(self._lib.nsfem_poisson_set_fast_diag_3d(self._h, Nx, Ny, Nz, _dp(vx), _dp(vy), _dp(vz), _dp(inv),
+                                                             1 if factors["exact"] else 0))
+
+    def poisson_fast_diag_3d_info(self):
+        """dict(shape=(Nx, Ny, Nz), exact, applications, solves) of the 3D factors (zeros when none are set);
+        applications counts the host-issued applications of T^+ (CG iterations replayed from a captured graph
+        apply it without the host), solves the projection solves that ran with the factors"""
+        out = (C.c_int64 * 6)()
+        self._check(self._lib.nsfem_poisson_fast_diag_3d_info(self._h, out))
+        return dict(shape=(int(out[0]), int(out[1]), int(out[2])), exact=bool(out[3]), applications=int(out[4]),
+                    solves=int(out[5]))
 
     def mg_info(self, which):
         """dict(legs, launches_per_cycle, levels, leg_launches): how the cycles of a hierarchy run"""

@@ -1000,8 +1000,13 @@ static bool pressure_pinned_anywhere(nsfem_ctx* c) {
 static int poisson_solve_fast_diag(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_info& info) {
   hipStream_t s = c->stream;
   const int64_t np = npre(c);
-  NSFEM_REQUIRE(c->fd_p.ready() && (int64_t)c->fd_p.W * c->fd_p.H == np,
+  // (3D box lattices: exact factors only -- inexact ones precondition CG, poisson_solve)
+  const bool box = c->fd3_p.ready();
+  NSFEM_REQUIRE(box ? c->fd3_p.exact && (int64_t)c->fd3_p.Nx * c->fd3_p.Ny * c->fd3_p.Nz == np
+                    : c->fd_p.ready() && (int64_t)c->fd_p.W * c->fd_p.H == np,
                 "fast diagonalisation requested but no factors were set (nsfem_poisson_set_fast_diag)");
+  Precond& fd = box ? (Precond&)c->fd3_p : (Precond&)c->fd_p;
+  if (box) ++c->fd3_p.solves;
   NSFEM_REQUIRE(!c->distributed(), "fast diagonalisation: one rank only");
   KrylovWork& w = c->kw;
   w.ensure(std::max<int64_t>(np, nvel(c)));
@@ -1022,7 +1027,7 @@ static int poisson_solve_fast_diag(nsfem_ctx* c, const nsfem_krylov_opts& o, nsf
   double bnorm = 0.0, target = 0.0;
   launch_residual(s, c->Ap, 1, x, rhs, w.r.p, c->mask_p.p, MASK_ZERO);
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
-    c->fd_p.apply(s, w.r.p, w.z.p);
+    fd.apply(s, w.r.p, w.z.p);
     launch_axpby(s, np, 1.0, x, 1.0, w.z.p, x);
     ++info.iterations;
     // the residual of the corrected iterate (the next pass's right-hand side)
@@ -1062,6 +1067,8 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   const bool dist = c->distributed();
   const uint8_t* gm = dist ? c->mask_p.p : nullptr;                            // (flag 2 on ghost rows)
   NSFEM_REQUIRE(!dist || (c->fd_p.strip() && gm), "fast diagonalisation on a partitioned mesh: strip factors not set");
+  const bool box = c->fd3_p.ready();            // exact 3D factors (the caller checks)
+  if (box) ++c->fd3_p.solves;
   launch_spmv_scaled(s, c->Dv, 1, -c->alpha[0] / c->k, c->state[NSFEM_USTAR].p, w.r.p);
   if (dist) {
     launch_zero_ghost(s, np, gm, w.r.p);
@@ -1082,6 +1089,7 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   info.converged = 0;
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
     if (dist) c->fd_p.apply_strip(s, c->comm, r, w.z.p);
+    else if (box) c->fd3_p.apply(s, r, w.z.p);
     else c->fd_p.apply(s, r, w.z.p);
     launch_axpby(s, np, 1.0, base, 1.0, w.z.p, c->state[NSFEM_P].p);          // p = p_old + z (later passes: p += z)
     base = c->state[NSFEM_P].p;
@@ -1105,7 +1113,9 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
 }
 
 static int poisson_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_info& info) {
-  if (o.precond == 3) return poisson_solve_fast_diag(c, o, info);
+  // (3D box lattices with inexact factors: CG preconditioned by T^+ below)
+  const bool box_pcg = o.precond == 3 && c->fd3_p.ready() && !c->fd3_p.exact;
+  if (o.precond == 3 && !box_pcg) return poisson_solve_fast_diag(c, o, info);
   LinOp op;
   op.A = &c->Ap;
   op.nv = 1;
@@ -1117,6 +1127,12 @@ static int poisson_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_i
     NSFEM_REQUIRE(c->mg_built, "multigrid requested but no hierarchy was set (nsfem_mg_finalize)");
     mg_refresh(c, false);
     op.prec = &c->mg_p;
+  }
+  if (box_pcg) {
+    NSFEM_REQUIRE(!c->distributed() && (int64_t)c->fd3_p.Nx * c->fd3_p.Ny * c->fd3_p.Nz == npre(c),
+                  "fast diagonalisation (3D): factors do not fit the pressure space");
+    op.prec = &c->fd3_p;
+    ++c->fd3_p.solves;
   }
   op.graph_epoch = c->graph_epoch;
   return pcg(c->stream, c->kw, op, c->rhs_p.p, c->state[NSFEM_P].p, o, info, !pressure_pinned_anywhere(c));
@@ -2041,7 +2057,10 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     NSFEM_REQUIRE(!fd || !ctx->distributed() || !pressure_pinned_anywhere(ctx),
                   "fast diagonalisation on a partitioned mesh solves the pure Neumann projection step only "
                   "(pressure Dirichlet nodes are set): use another Poisson preconditioner");
-    if (fd && !pressure_pinned_anywhere(ctx) && ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip()) {
+    // (3D box lattices: the pass-plus-check driver for exact factors; inexact ones assemble and run CG with T^+)
+    const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && !ctx->distributed()
+                                           : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
+    if (fd && !pressure_pinned_anywhere(ctx) && direct) {
       rc = poisson_direct_step(ctx, opts->poisson, si);
     } else {
       poisson_assemble(ctx, opts->pressure_extrapolation != 0);
@@ -2707,6 +2726,41 @@ extern "C" int nsfem_poisson_set_fast_diag(nsfem_ctx* ctx, int32_t W, int32_t H,
   NSFEM_REQUIRE((int64_t)W * H == npre(ctx), "fast diagonalisation: W x H must be the number of pressure dofs");
   NSFEM_REQUIRE(!ctx->distributed(), "partitioned context: nsfem_poisson_set_fast_diag_rows");
   ctx->fd_p.set(ctx->stream, W, H, Vx, Vy, inv);
+  if (ctx->fd3_p.ready()) {             // (the factors set last are the ones precond = 3 uses)
+    ctx->fd3_p.release();
+    ctx->graph_epoch++;                 // captured CG bodies may hold the freed 3D buffers (FastDiag3 as op.prec)
+  }
+  API_END(ctx)
+}
+
+// Factors of a 3D box lattice (poisson_fd.factors_3d): the P1 space must be the Nz x Ny x Nx lattice in lexicographic
+// numbering (x fastest), the pressure Dirichlet set a union of whole faces (or empty).  exact != 0: T is the stiffness
+// matrix itself and precond = 3 solves directly; exact == 0: precond = 3 runs CG preconditioned by T^+.
+extern "C" int nsfem_poisson_set_fast_diag_3d(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz, const double* Vx,
+                                              const double* Vy, const double* Vz, const double* inv, int32_t exact) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && Vx && Vy && Vz && inv, "null argument");
+  NSFEM_REQUIRE(!ctx->distributed(), "fast diagonalisation (3D): partitioned contexts are not supported");
+  NSFEM_REQUIRE(Nx >= 2 && Ny >= 2 && Nz >= 2 && (int64_t)Nx * Ny * Nz == npre(ctx),
+                "fast diagonalisation (3D): Nx x Ny x Nz must be the number of pressure dofs");
+  ctx->fd3_p.set(ctx->stream, Nx, Ny, Nz, Vx, Vy, Vz, inv, exact != 0);
+  ctx->fd_p.release();                  // (the factors set last are the ones precond = 3 uses)
+  ctx->graph_epoch++;                   // captured CG bodies hold the addresses of the previous factors / work buffers
+  API_END(ctx)
+}
+
+// out = {Nx, Ny, Nz, exact, host-issued applications of T^+, projection solves with the factors}; zeros when none
+extern "C" int nsfem_poisson_fast_diag_3d_info(nsfem_ctx* ctx, int64_t out[6]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  const nsfem::FastDiag3& f = ctx->fd3_p;
+  const bool on = f.ready();
+  out[0] = on ? f.Nx : 0;
+  out[1] = on ? f.Ny : 0;
+  out[2] = on ? f.Nz : 0;
+  out[3] = on && f.exact ? 1 : 0;
+  out[4] = f.applications;
+  out[5] = f.solves;
   API_END(ctx)
 }
 
@@ -2739,7 +2793,9 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
     DevBuf<double> dr, dz;
     dr.upload(r, (size_t)n, s);
     dz.alloc((size_t)n);
-    if (ctx->fd_p.strip()) {           // strips (a collective: every rank calls it): ghost rows zeroed, as the step does
+    if (ctx->fd3_p.ready()) {          // 3D box lattice: z = T^+ r
+      ctx->fd3_p.apply(s, dr.p, dz.p);
+    } else if (ctx->fd_p.strip()) {    // strips (a collective: every rank calls it): ghost rows zeroed, as the step does
       NSFEM_REQUIRE(ctx->distributed(), "strip factors need a partitioned context");
       launch_zero_ghost(s, n, ctx->mask_p.p, dr.p);
       ctx->fd_p.apply_strip(s, ctx->comm, dr.p, dz.p);

@@ -186,4 +186,18 @@ void FastDiag::apply(hipStream_t s, const double* r, double* z) {
   ++applications;
 }
 
+void FastDiag::release() {
+  W = H = j0 = h_loc = 0;
+  for (DevBuf<double>* b : {&Vx, &Vy, &inv, &t1, &t2}) b->release();
+}
+
+// k_fd_gemm for the other translation units (fastdiag3d.hip: the x and z products of the 3D solve)
+void launch_fd_gemm(hipStream_t s, bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B,
+                    int ldb, double* C, int ldc, const double* scale) {
+  NSFEM_REQUIRE(!(ta && tb), "launch_fd_gemm: op(A) and op(B) transposed together is not instantiated");
+  if (ta) fd_gemm<true, false>(s, M, N, K, A, lda, B, ldb, C, ldc, scale);
+  else if (tb) fd_gemm<false, true>(s, M, N, K, A, lda, B, ldb, C, ldc, scale);
+  else fd_gemm<false, false>(s, M, N, K, A, lda, B, ldb, C, ldc, scale);
+}
+
 }  // namespace nsfem

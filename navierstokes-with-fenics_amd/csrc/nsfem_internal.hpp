@@ -861,10 +861,32 @@ struct FastDiag : Precond {
   void set(hipStream_t s, int W_, int H_, const double* vx, const double* vy, const double* inv_);
   void set_rows(hipStream_t s, int W_, int H_, int j0_, int h_loc_, const double* vx, const double* vy,
                 const double* inv_);
+  void release();                // frees the factors and work buffers (ready() false)
   void apply(hipStream_t s, const double* r, double* z) override;
   // strips: r with zero ghost rows in, z on EVERY local row (ghost lines included) out; one all-reduce of the
   // H x W transformed array in between
   void apply_strip(hipStream_t s, Comm* comm, const double* r, double* z);
+};
+// k_fd_gemm (fastdiag.hip): C = op(A) op(B) (.* scale), row-major; ta: A(m, k) = A[k * lda + m], tb: B(k, n) =
+// B[n * ldb + k] (not both)
+void launch_fd_gemm(hipStream_t s, bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B,
+                    int ldb, double* C, int ldc, const double* scale);
+
+// Fast diagonalisation on 3D box lattices (fastdiag3d.hip, poisson_fd.factors_3d): z = T^+ r, T the tensor sum of the
+// 1D stiffness / lumped mass matrices, by six mode products of the N_z x N_y x N_x array on the matrix cores.  exact:
+// T is the P1 stiffness matrix itself (the projection step is one pass plus the residual check); otherwise T^+
+// preconditions CG.
+struct FastDiag3 : Precond {
+  int Nx = 0, Ny = 0, Nz = 0;
+  bool exact = false;
+  DevBuf<double> Vx, Vy, Vz, inv, t1, t2;
+  int64_t applications = 0;      // apply() calls issued by the host (a CG iteration replayed from a graph: not counted)
+  int64_t solves = 0;            // projection solves that ran with these factors
+  bool ready() const { return Nx > 0 && Vx.p && Vy.p && Vz.p && inv.p; }
+  void set(hipStream_t s, int Nx_, int Ny_, int Nz_, const double* vx, const double* vy, const double* vz,
+           const double* inv_, bool exact_);
+  void release();
+  void apply(hipStream_t s, const double* r, double* z) override;
 };
 // x -= sum(parts) / count on n entries (k_sum fills the slot: launch_sum)
 void launch_sum(hipStream_t s, int64_t n, const double* x, double* parts);
@@ -977,6 +999,7 @@ struct nsfem_ctx {
   bool cor_start_ready = false;                // correction_assemble produced the mass solve's start residual and sums
   uint64_t cor_start_touch = 0;                //   ... and nobody has used the Krylov work vectors since (kw.touch)
   nsfem::FastDiag fd_p;                        // direct projection-step solver on tensor-product lattices
+  nsfem::FastDiag3 fd3_p;                      // the same on 3D box lattices (direct or CG preconditioner)
   bool fd_p_singular = false;
   bool mg_built = false, mg_p_dirty = true, mg_v_dirty = true;
   std::vector<int32_t> h_bc_v, h_bc_p;         // host copies of the Dirichlet dof sets

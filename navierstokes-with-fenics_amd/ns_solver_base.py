@@ -397,13 +397,23 @@ class SolverBase:
 
     def _fast_diagonalization_ready(self):
         """ships the factors of the direct projection-step solver for the current pressure Dirichlet set; False where
-        it does not apply (no rectangle lattice, periodic or partitioned space, conditions on parts of a side)"""
+        it does not apply (no rectangle lattice, periodic or partitioned space, conditions on parts of a side).  3D box
+        lattices (periodic directions allowed, Dirichlet conditions on whole faces): poisson_fd.factors_3d -- a direct
+        solve where the tensor sum is the stiffness matrix, CG preconditioned by it elsewhere"""
         import poisson_fd
         pd = self._dirichlet_bcs["pressure"][0]
         key = pd.tobytes()
         if getattr(self, "_fast_diag_for", None) == key:
             return self._fast_diag_ok
         self._fast_diag_for, self._fast_diag_ok = key, False
+        if len(getattr(self._mesh, "structured", None) or ()) == 5:
+            box = poisson_fd.box_lattice(self._mesh, self._dofmap)
+            f = None if box is None else poisson_fd.factors_3d(*box, dirichlet_nodes=pd)
+            if f is None:
+                return False
+            self._ctx.poisson_set_fast_diag_3d(f)
+            self._fast_diag_ok = True
+            return True
         lines = poisson_fd.lattice_lines(self._mesh)
         if lines is None or hasattr(self, "_constrained_domain") or self._dofmap.n_p1 != lines[0].size * lines[1].size:
             return False
@@ -494,7 +504,9 @@ class InstationarySolverBase(SolverBase):
         self.mass_solver = "chebyshev"
         #: IPCS projection step: "multigrid" (CG preconditioned by the pressure V-cycle) or
         #: "fast_diagonalization" -- the direct solve of poisson_fd.py / csrc/fastdiag.hip where it applies
-        #: (rectangle lattices, pressure Dirichlet conditions on whole sides; elsewhere multigrid runs)
+        #: (rectangle lattices, pressure Dirichlet conditions on whole sides; 3D box lattices with conditions on whole
+        #: faces, periodic directions allowed -- direct where exact, else CG preconditioned by the tensor solve;
+        #: elsewhere multigrid runs)
         self.poisson_solver = "multigrid"
         #: truncated velocity multigrid cycle: None = library default (ratio 4, tolerance 0.1),
         #: 0 / False = full cycle, R or (R, tol) = truncate where c_v K_ii <= R alpha0/k M_ii
