@@ -231,13 +231,14 @@ int nsfem_operator_apply(nsfem_ctx* ctx, int op, const double* x, double* y);
  *   gh_lo, gh_hi, gh_zero   frozen ghost lines of a partitioned strip (flag every component of their rows)
  *   tile_lines  0 the launcher's choice; 16, 24, 32 or 48 forced (refused when the halo does not fit)
  *   fixed       -1 default (NSFEM_LATTICE_FIXED), 0 compile-time-offset stages off, 1 on
- *   lattice_*   out: the geometry of the launch and its fixed_shape */
+ *   lattice_*   out: the geometry of the launch and its fixed_shape
+ * d_out NULL (family 4): the launch stores no direction. */
 
 typedef struct {
   int32_t space, nv, family, epilogue, steps, maskmode, ghost, ident, from_zero, with_residual, dict_ok;
   int32_t used_family;        /* out */
   int32_t dict_entries, dict_exact, lattice_w;   /* out: dictionary of the pattern (0: none) */
-  int32_t reserved;
+  int32_t lattice_kind;       /* out (family 4): launch kind that ran, 64 | operand flags, 0: runtime-flag kernel */
   double a, b_coef;
   double c1[8], c2[8];
   const double *x, *b, *d;    /* host [n * nv]; b, d may be NULL */

@@ -53,7 +53,7 @@ class MeshDesc(C.Structure):
 class KernelTest(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("space", "nv", "family", "epilogue", "steps", "maskmode", "ghost", "ident",
                                           "from_zero", "with_residual", "dict_ok", "used_family", "dict_entries",
-                                          "dict_exact", "lattice_w", "reserved")] + \
+                                          "dict_exact", "lattice_w", "lattice_kind")] + \
                [("a", C.c_double), ("b_coef", C.c_double), ("c1", C.c_double * 8), ("c2", C.c_double * 8),
                 ("x", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)), ("d", C.POINTER(C.c_double)),
                 ("mask", C.POINTER(C.c_uint8)),
@@ -665,13 +665,13 @@ class NsfemContext:
     def kernel_apply(self, space, nv, x, a=1.0, b_coef=0.0, family=0, epilogue=0, b=None, d=None, mask=None,
                      maskmode=0, steps=0, c1=(), c2=(), ghost=0, ident=False, from_zero=False,
                      with_residual=False, dict_ok=True, xc=None, rf=None, gh_lo=0, gh_hi=0, gh_zero=False,
-                     tile_lines=0, fixed=-1):
+                     tile_lines=0, fixed=-1, want_d=True):
         """test hook (nsfem_kernel_apply): product / residual / smoothing sequence of a M + b K through a chosen
         kernel family; returns dict(y, d, r, used_family, dict_entries, dict_exact, lattice_w).  Lattice kernel
         (family 4) only: xc (fused prolongation; x may then be None), rf (fused restriction: the stored right-hand
         side comes back as b_formed), frozen ghost lines, a forced tile height and the fixed-offset stages on / off;
         the launch geometry comes back as lattice_tile_lines, lattice_tx, lattice_ty, lattice_tiles,
-        lattice_fixed_shape"""
+        lattice_fixed_shape, the launch kind as lattice_kind (want_d=False: no direction stored, d comes back None)"""
         t = KernelTest()
         t.space, t.nv, t.family, t.epilogue, t.steps = int(space), int(nv), int(family), int(epilogue), int(steps)
         t.maskmode, t.ghost, t.ident = int(maskmode), int(ghost), 1 if ident else 0
@@ -693,7 +693,11 @@ class NsfemContext:
         n = x.size if x is not None else (self.n_p2 if space == 0 else self.n_p1) * int(nv)
         bb, dd, mm = arr(b), arr(d), arr(mask, np.uint8)
         y, d_out, r_out, b_formed = np.empty(n), np.empty(n), np.empty(n), np.zeros(n)
-        t.y, t.d_out, t.r_out = _dp(y), _dp(d_out), _dp(r_out)
+        t.y, t.r_out = _dp(y), _dp(r_out)
+        if want_d:
+            t.d_out = _dp(d_out)
+        else:
+            d_out = None
         if x is not None:
             t.x = _dp(x)
         xcc, rff = arr(xc), arr(rf)
@@ -718,7 +722,7 @@ class NsfemContext:
                     b_formed=b_formed if rff is not None else None,
                     lattice_tile_lines=int(t.lattice_tile_lines), lattice_tx=int(t.lattice_tx),
                     lattice_ty=int(t.lattice_ty), lattice_tiles=int(t.lattice_tiles),
-                    lattice_fixed_shape=int(t.lattice_fixed_shape))
+                    lattice_fixed_shape=int(t.lattice_fixed_shape), lattice_kind=int(t.lattice_kind))
 
     def lattice_restrict(self, nv, w, h, rf, mask1=None, mask2=None, levels=1):
         """test hook (nsfem_lattice_restrict): levels = 1: b1 = R rf (k_restrict_lattice) onto the w x h lattice;

@@ -2645,11 +2645,13 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
       LatticeLaunchOverride ov;
       ov.tile_lines = t->tile_lines;
       ov.fixed = t->fixed;
+      // (no d_out on the host: the launch stores no direction either -- the launch kinds without d_out)
       launch_cheb_lattice(s, T, nv, (fz || !t->x) ? nullptr : x.p, b.p, (t->d && !fz) ? d.p : nullptr, y.p,
-                          d2.p, t->with_residual ? r.p : nullptr, mk, t->steps, t->c1, t->c2, t->ident, nullptr,
+                          t->d_out ? d2.p : nullptr, t->with_residual ? r.p : nullptr, mk, t->steps, t->c1, t->c2,
+                          t->ident, nullptr,
                           t->xc ? xc.p : nullptr, t->rf ? rf.p : nullptr, t->rf ? bo.p : nullptr, t->gh_lo, t->gh_hi,
                           t->gh_zero, &ov);
-      NSFEM_HIP(hipMemcpyAsync(d.p, d2.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+      if (t->d_out) NSFEM_HIP(hipMemcpyAsync(d.p, d2.p, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
       if (t->rf && t->b_formed) NSFEM_HIP(hipMemcpyAsync(t->b_formed, bo.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
       NSFEM_HIP(hipStreamSynchronize(s));      // (before the transfer buffers go out of scope)
       t->lattice_tile_lines = ov.used_tile_lines;
@@ -2657,6 +2659,7 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
       t->lattice_ty = ov.ty;
       t->lattice_tiles = ov.tiles;
       t->lattice_fixed_shape = ov.fixed_shape;
+      t->lattice_kind = ov.kind;
     } else {
       t->used_family = picked(true);
       dinv.alloc(n);

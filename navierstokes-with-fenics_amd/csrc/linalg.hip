@@ -1026,6 +1026,9 @@ struct LatticeArgs {
   const double* rf;         // right-hand side = R rf  (restriction of the finer level's vector, lattice 2 W - 1 wide),
   double* b_out;            //   stored to b_out on the output tile for the later launches of the level
   int Wc, Wf, Hf;
+  // bytes of the lattice's vectors, of rf and of xc (W H NV, Wf Hf NV, Wc Hc NV doubles): the ranges of the 32-bit
+  // operand streams (LatStream); the host refuses lattices where one does not fit
+  uint32_t lat_bytes, f_bytes, c_bytes;
   // partitioned strips, relaxed halo mode: the first gh_lo and the last gh_hi lattice lines are ghost rows -- their
   // iterate is FROZEN through the stages of the launch (block-Jacobi across the ranks, as the one-step kernels do
   // with SpmvArgs::ghost = 1); gh_zero: the launch ends a smoothing sequence, the ghost rows are stored as zeros
@@ -1048,7 +1051,39 @@ struct LatticeSlots {
   int info[K];
   double bq[K][NV], dq[K][NV];
   __device__ __forceinline__ int self(int q) const { return self0 + 64 * WPC * q; }
-  __device__ __forceinline__ size_t grow(int q) const { return (size_t)(grow0 + q * gstep); }
+  __device__ __forceinline__ uint32_t grow(int q) const { return (uint32_t)(grow0 + q * gstep); }
+};
+
+// Launch kinds of k_cheb_lattice: which operands a launch has.  LK_FIXED: the flags are compile-time (the staging
+// issues only the kind's loads, applies only its selects, keeps only its register arrays); without it every operand
+// is a runtime-uniform branch on its pointer (the fallback for every other combination).  No x_in and no xc: zero start.
+enum : int { LK_XIN = 1, LK_XC = 2, LK_RF = 4, LK_DIN = 8, LK_DOUT = 16, LK_ROUT = 32, LK_FIXED = 64 };
+template <int KIND> struct LatKind {
+  static constexpr bool F = (KIND & LK_FIXED) != 0;
+  static __device__ __forceinline__ bool xin(const LatticeArgs& a) { return F ? (KIND & LK_XIN) != 0 : a.x_in != nullptr; }
+  static __device__ __forceinline__ bool xc(const LatticeArgs& a) { return F ? (KIND & LK_XC) != 0 : a.xc != nullptr; }
+  static __device__ __forceinline__ bool rf(const LatticeArgs& a) { return F ? (KIND & LK_RF) != 0 : a.rf != nullptr; }
+  static __device__ __forceinline__ bool din(const LatticeArgs& a) { return F ? (KIND & LK_DIN) != 0 : a.d_in != nullptr; }
+  static __device__ __forceinline__ bool dout(const LatticeArgs& a) { return F ? (KIND & LK_DOUT) != 0 : a.d_out != nullptr; }
+  static __device__ __forceinline__ bool rout(const LatticeArgs& a) { return F ? (KIND & LK_ROUT) != 0 : a.r_out != nullptr; }
+  static __device__ __forceinline__ int fz(const LatticeArgs& a) { return F ? ((KIND & (LK_XIN | LK_XC)) ? 0 : 1) : a.from_zero; }
+};
+
+// f64 operand stream addressed by 32-bit element offsets from an SGPR buffer resource (buffer_load / buffer_store
+// ... offen: no 64-bit address arithmetic per slot; the host refuses lattices whose byte offsets do not fit, and
+// the resource's range makes an access past the array read 0 / write nothing)
+struct LatStream {
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ LatStream(const void* p, uint32_t bytes)
+      : r(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000)) {}
+  __device__ __forceinline__ double ld(uint32_t i) const {
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, i * 8u, 0, 0));
+  }
+  __device__ __forceinline__ void st(uint32_t i, double v) const {
+    typedef decltype(__builtin_amdgcn_raw_buffer_load_b64(r, 0u, 0, 0)) raw;
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(raw, v), r, i * 8u, 0, 0);
+  }
+  __device__ __forceinline__ uint32_t ld8(uint32_t i) const { return __builtin_amdgcn_raw_buffer_load_b8(r, i, 0, 0); }
 };
 #define LAT_RING(q) ((st.info[q] >> 16) & 255)
 #define LAT_MK(q) ((st.info[q] >> 8) & 255)
@@ -1056,7 +1091,7 @@ struct LatticeSlots {
 
 // stages of a wave whose nodes share ONE dictionary entry: its LP values and LDS offsets (zero padded
 // tables, LP >= the entry's length) are scalar loads issued once, before the first stage
-template <int NV, int K, int LP, int WPC, bool GH>
+template <int NV, int K, int LP, int WPC, bool GH, int KIND>
 __device__ __forceinline__ void lattice_stages_uniform(const LatticeArgs& a, LatticeSlots<NV, K, WPC>& st,
                                                        double* __restrict__ xs0, double* __restrict__ xs1,
                                                        const double* __restrict__ vp,
@@ -1069,11 +1104,11 @@ __device__ __forceinline__ void lattice_stages_uniform(const LatticeArgs& a, Lat
     v[k] = vp[k];
     o[k] = op[k];
   }
-  const int n_smooth = a.S - a.from_zero;
+  const int n_smooth = a.S - LatKind<KIND>::fz(a);
   for (int m = 1; m <= a.Mv; ++m) {
     const int lim = a.R * (a.Mv - m);
     const bool smoothing = m <= n_smooth;
-    const int kstep = m - 1 + a.from_zero;
+    const int kstep = m - 1 + LatKind<KIND>::fz(a);
     const double c1 = smoothing ? a.c1[kstep] : 0.0, c2 = smoothing ? a.c2[kstep] : 0.0;
     const bool last = smoothing && kstep == a.S - 1;
     const double* __restrict__ src = (m & 1) ? xs0 : xs1;
@@ -1129,7 +1164,7 @@ __device__ __forceinline__ void lattice_stages_uniform(const LatticeArgs& a, Lat
       } else {                          // residual of the smoothed iterate (ring 0 only)
 #pragma unroll
         for (int c = 0; c < NV; ++c)
-          a.r_out[(size_t)st.grow(q) * NV + c] = ((LAT_MK(q) >> c) & 1) ? 0.0 : st.bq[q][c] - acc[c];
+          LatStream(a.r_out, a.lat_bytes).st(st.grow(q) * NV + c, ((LAT_MK(q) >> c) & 1) ? 0.0 : st.bq[q][c] - acc[c]);
       }
     }
     if (m < a.Mv) __syncthreads();
@@ -1139,7 +1174,7 @@ __device__ __forceinline__ void lattice_stages_uniform(const LatticeArgs& a, Lat
 // Stages of a wave whose nodes share ONE dictionary entry of canonical shape: the neighbour reads carry their LDS
 // offsets as instruction immediates (ds_read_b128 ... offset:) -- no address arithmetic and no offset table; the
 // values are scalar loads issued once, as in lattice_stages_uniform.  
-template <int NV, int K, int WPC, bool GH, int SHAPE, int CLS>
+template <int NV, int K, int WPC, bool GH, int SHAPE, int CLS, int KIND>
 __device__ __forceinline__ void lattice_stages_fixed(const LatticeArgs& a, LatticeSlots<NV, K, WPC>& st,
                                                      double* __restrict__ xs0, double* __restrict__ xs1,
                                                      const double* __restrict__ vp, double di) {
@@ -1149,11 +1184,11 @@ __device__ __forceinline__ void lattice_stages_fixed(const LatticeArgs& a, Latti
   double v[N];
 #pragma unroll
   for (int k = 0; k < N; ++k) v[k] = vp[k];
-  const int n_smooth = a.S - a.from_zero;
+  const int n_smooth = a.S - LatKind<KIND>::fz(a);
   for (int m = 1; m <= a.Mv; ++m) {
     const int lim = a.R * (a.Mv - m);
     const bool smoothing = m <= n_smooth;
-    const int kstep = m - 1 + a.from_zero;
+    const int kstep = m - 1 + LatKind<KIND>::fz(a);
     const double c1 = smoothing ? a.c1[kstep] : 0.0, c2 = smoothing ? a.c2[kstep] : 0.0;
     const bool last = smoothing && kstep == a.S - 1;
     const double* __restrict__ src = (m & 1) ? xs0 : xs1;
@@ -1211,7 +1246,7 @@ __device__ __forceinline__ void lattice_stages_fixed(const LatticeArgs& a, Latti
       } else {
 #pragma unroll
         for (int c = 0; c < NV; ++c)
-          a.r_out[(size_t)st.grow(q) * NV + c] = ((LAT_MK(q) >> c) & 1) ? 0.0 : st.bq[q][c] - acc[c];
+          LatStream(a.r_out, a.lat_bytes).st(st.grow(q) * NV + c, ((LAT_MK(q) >> c) & 1) ? 0.0 : st.bq[q][c] - acc[c]);
       }
     }
     if (m < a.Mv) __syncthreads();
@@ -1219,7 +1254,7 @@ __device__ __forceinline__ void lattice_stages_fixed(const LatticeArgs& a, Latti
 }
 
 // the same for a wave whose nodes use several entries (tiles at the domain boundary): per-lane loads
-template <int NV, int K, int WPC, bool GH>
+template <int NV, int K, int WPC, bool GH, int KIND>
 __device__ __forceinline__ void lattice_stages_general(const LatticeArgs& a, LatticeSlots<NV, K, WPC>& st,
                                                        double* __restrict__ xs0, double* __restrict__ xs1,
                                                        const double* __restrict__ tval,
@@ -1227,11 +1262,11 @@ __device__ __forceinline__ void lattice_stages_general(const LatticeArgs& a, Lat
                                                        const int32_t* __restrict__ tlen,
                                                        const double* __restrict__ tdinv, int cls) {
   typedef double vec __attribute__((ext_vector_type(2)));
-  const int n_smooth = a.S - a.from_zero;
+  const int n_smooth = a.S - LatKind<KIND>::fz(a);
   for (int m = 1; m <= a.Mv; ++m) {
     const int lim = a.R * (a.Mv - m);
     const bool smoothing = m <= n_smooth;
-    const int kstep = m - 1 + a.from_zero;
+    const int kstep = m - 1 + LatKind<KIND>::fz(a);
     const double c1 = smoothing ? a.c1[kstep] : 0.0, c2 = smoothing ? a.c2[kstep] : 0.0;
     const bool last = smoothing && kstep == a.S - 1;
     const double* __restrict__ src = (m & 1) ? xs0 : xs1;
@@ -1278,7 +1313,7 @@ __device__ __forceinline__ void lattice_stages_general(const LatticeArgs& a, Lat
       } else {
 #pragma unroll
         for (int c = 0; c < NV; ++c)
-          a.r_out[(size_t)st.grow(q) * NV + c] = ((LAT_MK(q) >> c) & 1) ? 0.0 : st.bq[q][c] - acc[c];
+          LatStream(a.r_out, a.lat_bytes).st(st.grow(q) * NV + c, ((LAT_MK(q) >> c) & 1) ? 0.0 : st.bq[q][c] - acc[c]);
       }
     }
     if (m < a.Mv) __syncthreads();
@@ -1290,10 +1325,11 @@ __device__ __forceinline__ void lattice_stages_general(const LatticeArgs& a, Lat
 // the stencil's end), toff[(st * 4 + class) * lp + k] LDS offset of the k-th neighbour, tlen[st],
 // tdinv[st] = 1 / diagonal.  512 threads: waves 2c, 2c + 1 own class c; slot q of wave w covers the plane
 // rows 2 (2 q + (w & 1)) and the next.
-template <int NV, int K, int WPE, int WPC, bool GH>
+template <int NV, int K, int WPE, int WPC, bool GH, int KIND>
 __global__ __launch_bounds__(256 * WPC) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_t* __restrict__ toff,
                     const int32_t* __restrict__ tlen, const double* __restrict__ tdinv) {
+  typedef LatKind<KIND> LK;
   extern __shared__ double sh_lat[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1313,7 +1349,9 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
   const bool in_x = gi >= 0 && gi < a.W;
   const int ex = max(max(i0 - gi, gi - (i1 - 1)), 0);
   const int Go = a.R * max(a.Mv - 1, 0);
-  const int need = (a.from_zero || a.xc) ? a.G : Go;              // nodes whose b / entry / mask are used
+  const int fz = LK::fz(a);
+  const bool has_xin = LK::xin(a), has_xc = LK::xc(a), has_rf = LK::rf(a), has_din = LK::din(a);
+  const int need = (fz || has_xc) ? a.G : Go;                     // nodes whose b / entry / mask are used
   LatticeSlots<NV, K, WPC> st;
   unsigned long long differs = 0;
   int stu = -1;
@@ -1324,8 +1362,11 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
   //   pass 1  rings, clamped node indices, the byte entry | masks of every slot
   //   pass 2  the vector operands of every slot (b or the 7 fine values of R rf; d; x, P xc)
   //   pass 3  masks and conditions applied, slot state filled, start iterate stored to LDS
+  // Operands are 32-bit element offsets into buffer resources (LatStream); a fixed launch kind (LK_FIXED) drops
+  // the loads, selects and register arrays of the operands it does not have.
+  const LatStream s_lat(a.sidm, a.lat_bytes / (8 * NV));
   int ringq[K], smq[K], gjcq[K];
-  size_t gcl[K];
+  uint32_t gcl[K];
   const int gic = min(max(gi, 0), a.W - 1);
 #pragma unroll
   for (int q = 0; q < K; ++q) {
@@ -1341,29 +1382,30 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
     }
     const int gjc = min(max(gj, 0), a.H - 1);
     gjcq[q] = gjc;
-    gcl[q] = (size_t)gjc * a.W + gic;
-    smq[q] = a.sidm[gcl[q]];
+    gcl[q] = (uint32_t)(gjc * a.W + gic);
+    smq[q] = (int)s_lat.ld8(gcl[q]);
   }
   double braw[K][NV], draw[K][NV], xraw[K][NV];
   // (one loop per kernel-uniform case: the loads of all slots sit in one basic block and are issued together)
-  if (a.rf) {
+  if (has_rf) {
+    const LatStream s_rf(a.rf, a.f_bytes);
 #pragma unroll
     for (int q = 0; q < K; ++q) {
       // b = R rf: the node's own fine value + half of its six fine neighbours (ascending fine index, the
       // order of the CSR row of R = P^T); absent neighbours: the own value with weight 0
       const int fi = 2 * gic, fj = 2 * gjcq[q];
-      const size_t fb = (size_t)fj * a.Wf + fi;
+      const uint32_t fb = (uint32_t)(fj * a.Wf + fi), wf = (uint32_t)a.Wf;
       const bool l_ = fi > 0, r_ = fi < a.Wf - 1, d_ = fj > 0, u_ = fj < a.Hf - 1;
-      const size_t n0 = (d_ && l_) ? fb - a.Wf - 1 : fb, n1 = d_ ? fb - a.Wf : fb, n2 = l_ ? fb - 1 : fb;
-      const size_t n4 = r_ ? fb + 1 : fb, n5 = u_ ? fb + a.Wf : fb, n6 = (u_ && r_) ? fb + a.Wf + 1 : fb;
+      const uint32_t n0 = (d_ && l_) ? fb - wf - 1 : fb, n1 = d_ ? fb - wf : fb, n2 = l_ ? fb - 1 : fb;
+      const uint32_t n4 = r_ ? fb + 1 : fb, n5 = u_ ? fb + wf : fb, n6 = (u_ && r_) ? fb + wf + 1 : fb;
       const double w0 = (d_ && l_) ? 0.5 : 0.0, w1 = d_ ? 0.5 : 0.0, w2 = l_ ? 0.5 : 0.0;
       const double w4 = r_ ? 0.5 : 0.0, w5 = u_ ? 0.5 : 0.0, w6 = (u_ && r_) ? 0.5 : 0.0;
       double f[7][NV];
 #pragma unroll
       for (int c = 0; c < NV; ++c) {
-        f[0][c] = a.rf[n0 * NV + c]; f[1][c] = a.rf[n1 * NV + c]; f[2][c] = a.rf[n2 * NV + c];
-        f[3][c] = a.rf[fb * NV + c];
-        f[4][c] = a.rf[n4 * NV + c]; f[5][c] = a.rf[n5 * NV + c]; f[6][c] = a.rf[n6 * NV + c];
+        f[0][c] = s_rf.ld(n0 * NV + c); f[1][c] = s_rf.ld(n1 * NV + c); f[2][c] = s_rf.ld(n2 * NV + c);
+        f[3][c] = s_rf.ld(fb * NV + c);
+        f[4][c] = s_rf.ld(n4 * NV + c); f[5][c] = s_rf.ld(n5 * NV + c); f[6][c] = s_rf.ld(n6 * NV + c);
       }
 #pragma unroll
       for (int c = 0; c < NV; ++c) {
@@ -1379,55 +1421,59 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
       }
     }
   } else {
+    const LatStream s_b(a.b, a.lat_bytes);
 #pragma unroll
     for (int q = 0; q < K; ++q)
 #pragma unroll
-      for (int c = 0; c < NV; ++c) braw[q][c] = a.b[gcl[q] * NV + c];
+      for (int c = 0; c < NV; ++c) braw[q][c] = s_b.ld(gcl[q] * NV + c);
   }
-  if (!a.from_zero && a.d_in) {
+  if (!fz && has_din) {
+    const LatStream s_d(a.d_in, a.lat_bytes);
 #pragma unroll
     for (int q = 0; q < K; ++q)
 #pragma unroll
-      for (int c = 0; c < NV; ++c) draw[q][c] = a.d_in[gcl[q] * NV + c];
+      for (int c = 0; c < NV; ++c) draw[q][c] = s_d.ld(gcl[q] * NV + c);
   } else {
 #pragma unroll
     for (int q = 0; q < K; ++q)
 #pragma unroll
       for (int c = 0; c < NV; ++c) draw[q][c] = 0.0;
   }
-  if (!a.from_zero && a.xc) {
+  if (!fz && has_xc) {
     // start vector = [x_in +] P xc: even-even nodes copy their coarse node, the others average the two
     // coarse nodes (I, J) and (I + pi, J + pj)
+    const LatStream s_x(a.x_in, a.lat_bytes), s_c(a.xc, a.c_bytes);
     double xin[K][NV];
-    if (a.x_in) {
+    if (has_xin) {
 #pragma unroll
       for (int q = 0; q < K; ++q)
 #pragma unroll
-        for (int c = 0; c < NV; ++c) xin[q][c] = a.x_in[gcl[q] * NV + c];
+        for (int c = 0; c < NV; ++c) xin[q][c] = s_x.ld(gcl[q] * NV + c);
     }
-    const size_t cmax = (size_t)a.Wc * ((a.H + 1) >> 1) - 1;
+    const uint32_t cmax = (uint32_t)(a.Wc * ((a.H + 1) >> 1) - 1);
     const double pw0 = cls != 0 ? 0.5 : 1.0, pw1 = cls != 0 ? 0.5 : 0.0;
 #pragma unroll
     for (int q = 0; q < K; ++q) {
-      const size_t c0 = (size_t)(gjcq[q] >> 1) * a.Wc + (gic >> 1);
-      const size_t c1 = min(c0 + pi + (size_t)pj * a.Wc, cmax);
+      const uint32_t c0 = (uint32_t)((gjcq[q] >> 1) * a.Wc + (gic >> 1));
+      const uint32_t c1 = min(c0 + (uint32_t)(pi + pj * a.Wc), cmax);
 #pragma unroll
       for (int c = 0; c < NV; ++c) {
-        const double v0 = a.xc[c0 * NV + c], v1 = a.xc[c1 * NV + c];
+        const double v0 = s_c.ld(c0 * NV + c), v1 = s_c.ld(c1 * NV + c);
         xraw[q][c] = pw0 * v0 + pw1 * v1;            // (1 v0 + 0 v1 on the even-even class: the copy, exactly)
       }
     }
-    if (a.x_in) {
+    if (has_xin) {
 #pragma unroll
       for (int q = 0; q < K; ++q)
 #pragma unroll
         for (int c = 0; c < NV; ++c) xraw[q][c] = xin[q][c] + xraw[q][c];
     }
-  } else if (!a.from_zero) {
+  } else if (!fz) {
+    const LatStream s_x(a.x_in, a.lat_bytes);
 #pragma unroll
     for (int q = 0; q < K; ++q)
 #pragma unroll
-      for (int c = 0; c < NV; ++c) xraw[q][c] = a.x_in[gcl[q] * NV + c];
+      for (int c = 0; c < NV; ++c) xraw[q][c] = s_x.ld(gcl[q] * NV + c);
   } else {
 #pragma unroll
     for (int q = 0; q < K; ++q)
@@ -1436,7 +1482,8 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
   }
   double diq[K];
 #pragma unroll
-  for (int q = 0; q < K; ++q) diq[q] = a.from_zero ? tdinv[smq[q] & 63] : 0.0;
+  for (int q = 0; q < K; ++q) diq[q] = fz ? tdinv[smq[q] & 63] : 0.0;
+  const LatStream s_bo(a.b_out, a.lat_bytes);
 #pragma unroll
   for (int q = 0; q < K; ++q) {
     const int ring = ringq[q];
@@ -1448,13 +1495,13 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
     for (int c = 0; c < NV; ++c) {
       const bool mk = (mkq >> c) & 1;
       double bv = counts ? braw[q][c] : 0.0;
-      if (a.rf) {
+      if (has_rf) {
         if (mk) bv = 0.0;
-        if (counts && ring == 0) a.b_out[st.grow(q) * NV + c] = bv;
+        if (counts && ring == 0) s_bo.st(st.grow(q) * NV + c, bv);
       }
-      st.dq[q][c] = (counts && !a.from_zero && a.d_in && ring <= Go) ? draw[q][c] : 0.0;
+      st.dq[q][c] = (counts && !fz && has_din && ring <= Go) ? draw[q][c] : 0.0;
       double v = 0.0;
-      if (!a.from_zero && ring <= a.G) v = (a.xc && mk) ? 0.0 : xraw[q][c];
+      if (!fz && ring <= a.G) v = (has_xc && mk) ? 0.0 : xraw[q][c];
       xv[c] = v;
       st.bq[q][c] = (GH && (mkq & 4)) ? v : bv;        // (ghost rows carry their frozen iterate in place of b)
     }
@@ -1465,7 +1512,7 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
       if (stu < 0) stu = __builtin_amdgcn_readfirstlane(__shfl(stq, __ffsll((long long)who) - 1, 64));
       differs |= __ballot(counts && stq != stu);
     }
-    if (a.from_zero) {                    // step 0 from a zero start: pointwise
+    if (fz) {                             // step 0 from a zero start: pointwise
       const double di = counts ? diq[q] : 0.0;
 #pragma unroll
       for (int c = 0; c < NV; ++c) {
@@ -1493,37 +1540,38 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
         // (cls is wave-uniform: one of the eight instantiations runs)
         done = true;
         switch (a.fixed_shape * 4 + cls) {
-          case 4: lattice_stages_fixed<NV, K, WPC, GH, 1, 0>(a, st, xs0, xs1, vp, di); break;
-          case 5: lattice_stages_fixed<NV, K, WPC, GH, 1, 1>(a, st, xs0, xs1, vp, di); break;
-          case 6: lattice_stages_fixed<NV, K, WPC, GH, 1, 2>(a, st, xs0, xs1, vp, di); break;
-          case 7: lattice_stages_fixed<NV, K, WPC, GH, 1, 3>(a, st, xs0, xs1, vp, di); break;
-          case 8: lattice_stages_fixed<NV, K, WPC, GH, 2, 0>(a, st, xs0, xs1, vp, di); break;
-          case 9: lattice_stages_fixed<NV, K, WPC, GH, 2, 1>(a, st, xs0, xs1, vp, di); break;
-          case 10: lattice_stages_fixed<NV, K, WPC, GH, 2, 2>(a, st, xs0, xs1, vp, di); break;
-          case 11: lattice_stages_fixed<NV, K, WPC, GH, 2, 3>(a, st, xs0, xs1, vp, di); break;
+          case 4: lattice_stages_fixed<NV, K, WPC, GH, 1, 0, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 5: lattice_stages_fixed<NV, K, WPC, GH, 1, 1, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 6: lattice_stages_fixed<NV, K, WPC, GH, 1, 2, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 7: lattice_stages_fixed<NV, K, WPC, GH, 1, 3, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 8: lattice_stages_fixed<NV, K, WPC, GH, 2, 0, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 9: lattice_stages_fixed<NV, K, WPC, GH, 2, 1, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 10: lattice_stages_fixed<NV, K, WPC, GH, 2, 2, KIND>(a, st, xs0, xs1, vp, di); break;
+          case 11: lattice_stages_fixed<NV, K, WPC, GH, 2, 3, KIND>(a, st, xs0, xs1, vp, di); break;
           default: done = false;
         }
       }
       if (done) {
       } else
-      if (L <= 8 && a.lp >= 8) lattice_stages_uniform<NV, K, 8, WPC, GH>(a, st, xs0, xs1, vp, op, di);
-      else if (L <= 12 && a.lp >= 12) lattice_stages_uniform<NV, K, 12, WPC, GH>(a, st, xs0, xs1, vp, op, di);
-      else if (L <= 20 && a.lp >= 20) lattice_stages_uniform<NV, K, 20, WPC, GH>(a, st, xs0, xs1, vp, op, di);
-      else lattice_stages_general<NV, K, WPC, GH>(a, st, xs0, xs1, tval, toff, tlen, tdinv, cls);
+      if (L <= 8 && a.lp >= 8) lattice_stages_uniform<NV, K, 8, WPC, GH, KIND>(a, st, xs0, xs1, vp, op, di);
+      else if (L <= 12 && a.lp >= 12) lattice_stages_uniform<NV, K, 12, WPC, GH, KIND>(a, st, xs0, xs1, vp, op, di);
+      else if (L <= 20 && a.lp >= 20) lattice_stages_uniform<NV, K, 20, WPC, GH, KIND>(a, st, xs0, xs1, vp, op, di);
+      else lattice_stages_general<NV, K, WPC, GH, KIND>(a, st, xs0, xs1, tval, toff, tlen, tdinv, cls);
     } else {
-      lattice_stages_general<NV, K, WPC, GH>(a, st, xs0, xs1, tval, toff, tlen, tdinv, cls);
+      lattice_stages_general<NV, K, WPC, GH, KIND>(a, st, xs0, xs1, tval, toff, tlen, tdinv, cls);
     }
   }
   // the newest iterate sits in the buffer the last smoothing stage wrote (stage m writes buffer m & 1)
-  const int n_smooth = NSFEM_KO(a.dbg & 1) ? 0 : a.S - a.from_zero;
+  const int n_smooth = NSFEM_KO(a.dbg & 1) ? 0 : a.S - fz;
   const double* __restrict__ fin = (n_smooth & 1) ? xs1 : xs0;
+  const LatStream s_xo(a.x_out, a.lat_bytes), s_do(a.d_out, a.lat_bytes);
 #pragma unroll
   for (int q = 0; q < K; ++q)
     if (LAT_RING(q) == 0) {
 #pragma unroll
       for (int c = 0; c < NV; ++c) {
-        a.x_out[st.grow(q) * NV + c] = (GH && a.gh_zero && (LAT_MK(q) & 4)) ? 0.0 : fin[(size_t)st.self(q) * NV + c];
-        if (a.d_out) a.d_out[st.grow(q) * NV + c] = st.dq[q][c];
+        s_xo.st(st.grow(q) * NV + c, (GH && a.gh_zero && (LAT_MK(q) & 4)) ? 0.0 : fin[(size_t)st.self(q) * NV + c]);
+        if (LK::dout(a)) s_do.st(st.grow(q) * NV + c, st.dq[q][c]);
       }
     }
 }
@@ -1531,12 +1579,34 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
 #undef LAT_MK
 #undef LAT_ST
 
+// launch kind of k_cheb_lattice (LK_* flags): LK_FIXED | operands for the combinations with a specialised
+// instantiation, 0 (the runtime-flag kernel) for all others.  d_in is not read on a zero start.
+int lattice_launch_kind(bool x_in, bool xc, bool rf, bool d_in, bool d_out, bool r_out, bool ghost) {
+  if (ghost) return 0;
+  const bool fz = !x_in && !xc;
+  const int k = (x_in ? LK_XIN : 0) | (xc ? LK_XC : 0) | (rf ? LK_RF : 0) | (d_in && !fz ? LK_DIN : 0) |
+                (d_out ? LK_DOUT : 0) | (r_out ? LK_ROUT : 0);
+  static const int specialised[] = {LK_XC, LK_XIN | LK_XC, LK_RF, LK_RF | LK_ROUT, 0, LK_ROUT, LK_DOUT,
+                                    LK_XIN | LK_DIN | LK_DOUT, LK_XIN | LK_DIN, LK_XIN | LK_DIN | LK_ROUT, LK_XIN};
+  for (int v : specialised)
+    if (k == v) return LK_FIXED | k;
+  return 0;
+}
+// 32-bit operand offsets: the lattice's vectors (and the finer lattice's, under a fused restriction) in bytes < 2^31
+bool lattice_offsets_fit(int64_t w, int64_t h, int nv, bool rf) {
+  const int64_t lim = (int64_t)1 << 31;
+  if (w <= 0 || h <= 0 || w * h * nv * 8 >= lim) return false;
+  return !rf || (2 * w - 1) * (2 * h - 1) * nv * 8 < lim;
+}
+
 // can smoothing steps of this operator run in the lattice kernel?
 // tuning / test switches, re-read whenever a context is created (tests switch them between contexts)
-static bool g_lattice_on = true, g_lattice_transfers_on = true;
+static bool g_lattice_on = true, g_lattice_transfers_on = true, g_lattice_kinds_on = true;
 void refresh_env_switches() {
   const char* e = std::getenv("NSFEM_LATTICE");
   g_lattice_on = e ? std::atoi(e) != 0 : true;
+  e = std::getenv("NSFEM_LATTICE_KINDS");           // 0: every launch runs the runtime-flag kernel (A/B, tests)
+  g_lattice_kinds_on = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_LATTICE_TRANSFERS");
   g_lattice_transfers_on = e ? std::atoi(e) != 0 : true;
 }
@@ -1636,6 +1706,12 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   a.fixed_shape = (fixed_use && d.fixed_shape > 0) ? d.fixed_shape : 0;
   for (int c = 0; c < 4; ++c) a.fixed_mask[c] = a.fixed_shape ? d.fixed_mask[c] : 0ull;
   a.Wc = (d.lat_w + 1) / 2; a.Wf = 2 * d.lat_w - 1; a.Hf = 2 * d.lat_h - 1;
+  // the operand streams are 32-bit byte offsets (LatStream): every vector the launch reads or writes must fit
+  NSFEM_REQUIRE(lattice_offsets_fit(d.lat_w, d.lat_h, nv, rf != nullptr),
+                "lattice smoother: lattice too large for 32-bit operand offsets");
+  a.lat_bytes = (uint32_t)((int64_t)d.lat_w * d.lat_h * nv * 8);
+  a.f_bytes = rf ? (uint32_t)((int64_t)a.Wf * a.Hf * nv * 8) : 0u;
+  a.c_bytes = xc ? (uint32_t)((int64_t)a.Wc * ((d.lat_h + 1) / 2) * nv * 8) : 0u;
   a.Mv = steps - a.from_zero + (r_out ? 1 : 0);
   NSFEM_REQUIRE(a.Mv >= 0 && a.Mv * a.R <= 8, "lattice smoother: halo too wide");
   a.G = a.R * a.Mv;
@@ -1708,39 +1784,66 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   // launch shape (tuning switch NSFEM_LATTICE_SHAPE): 0 = 4 waves per SIMD (<= 128 VGPRs: two workgroups per
   // CU), 1 = 2 waves per SIMD (no register cap: one workgroup per CU)
   static const int shape = [] { const char* e = std::getenv("NSFEM_LATTICE_SHAPE"); return e ? std::atoi(e) : 0; }();
-#define NSFEM_LAT(NV, KK, WPE, WPC, GH)                                                                \
+#define NSFEM_LAT(NV, KK, WPE, WPC, GH, KIND)                                                          \
   do {                                                                                                 \
     static bool attr_dev[64];                                                                          \
     int dev_ = 0;                                                                                      \
     NSFEM_HIP(hipGetDevice(&dev_));                                                                    \
     bool& attr_set = attr_dev[dev_ & 63];                                                              \
     if (!attr_set) {                                                                                   \
-      NSFEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cheb_lattice<NV, KK, WPE, WPC, GH>), \
+      NSFEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cheb_lattice<NV, KK, WPE, WPC, GH, KIND>), \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));         \
       attr_set = true;                                                                                 \
     }                                                                                                  \
-    hipLaunchKernelGGL((k_cheb_lattice<NV, KK, WPE, WPC, GH>), dim3(grid), dim3(256 * WPC), lds, s, a, \
+    hipLaunchKernelGGL((k_cheb_lattice<NV, KK, WPE, WPC, GH, KIND>), dim3(grid), dim3(256 * WPC), lds, s, a, \
                        (const double*)A.lat_vals.p, toff, (const int32_t*)d.len.p,                     \
                        (const double*)A.dict_dinv.p);                                                  \
   } while (0)
-#define NSFEM_LAT_K(NV, WPE, GH)                        \
-  do {                                                  \
-    if (eh == 48) NSFEM_LAT(NV, 3, 4, 4, GH);           \
-    else if (eh == 32) NSFEM_LAT(NV, 4, WPE, 2, GH);    \
-    else if (eh == 24) NSFEM_LAT(NV, 3, WPE, 2, GH);    \
-    else NSFEM_LAT(NV, 2, WPE, 2, GH);                  \
+#define NSFEM_LAT_K(NV, WPE, GH, KIND)                        \
+  do {                                                        \
+    if (eh == 48) NSFEM_LAT(NV, 3, 4, 4, GH, KIND);           \
+    else if (eh == 32) NSFEM_LAT(NV, 4, WPE, 2, GH, KIND);    \
+    else if (eh == 24) NSFEM_LAT(NV, 3, WPE, 2, GH, KIND);    \
+    else NSFEM_LAT(NV, 2, WPE, 2, GH, KIND);                  \
+  } while (0)
+  // launch kind: the specialised instantiations cover what the cycles and the mass solve launch on one context at the
+  // default shape; everything else (strips, tuning shapes, other operand sets) runs the runtime-flag kernel
+  const int kind = (shape == 0 && g_lattice_kinds_on && !(ovr && ovr->generic))
+                       ? lattice_launch_kind(x_in != nullptr, xc != nullptr, rf != nullptr, d_in != nullptr,
+                                             d_out != nullptr, r_out != nullptr, gh_lo > 0 || gh_hi > 0)
+                       : 0;
+  if (ovr) ovr->kind = kind;
+#define NSFEM_LAT_KINDS(NV)                                                                     \
+  do {                                                                                          \
+    switch (kind) {                                                                             \
+      case LK_FIXED | LK_XC: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XC); break;                \
+      case LK_FIXED | LK_XIN | LK_XC: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_XC); break; \
+      case LK_FIXED | LK_RF: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_RF); break;                \
+      case LK_FIXED | LK_RF | LK_ROUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_RF | LK_ROUT); break; \
+      case LK_FIXED: NSFEM_LAT_K(NV, 4, false, LK_FIXED); break;                                \
+      case LK_FIXED | LK_ROUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_ROUT); break;            \
+      case LK_FIXED | LK_DOUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_DOUT); break;            \
+      case LK_FIXED | LK_XIN | LK_DIN | LK_DOUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_DIN | LK_DOUT); break; \
+      case LK_FIXED | LK_XIN | LK_DIN: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_DIN); break; \
+      case LK_FIXED | LK_XIN | LK_DIN | LK_ROUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_DIN | LK_ROUT); break; \
+      case LK_FIXED | LK_XIN: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN); break;              \
+      default: NSFEM_REQUIRE(false, "lattice smoother: launch kind without an instantiation");  \
+    }                                                                                           \
   } while (0)
   // (the frozen ghost lines of partitioned strips are a template flag: the single-context launches do not pay for
   // them -- 811 vs 758 VALU instructions per wave; strips always use the default launch shape)
   const bool gh = gh_lo > 0 || gh_hi > 0;
-  if (gh && nv == 2) NSFEM_LAT_K(2, 4, true);
-  else if (gh) NSFEM_LAT_K(1, 4, true);
-  else if (nv == 2 && shape == 1) NSFEM_LAT_K(2, 2, false);
-  else if (nv == 2 && shape == 2) NSFEM_LAT_K(2, 6, false);
-  else if (nv == 2) NSFEM_LAT_K(2, 4, false);
-  else if (shape == 1) NSFEM_LAT_K(1, 2, false);
-  else if (shape == 2) NSFEM_LAT_K(1, 6, false);
-  else NSFEM_LAT_K(1, 4, false);
+  if (kind != 0 && nv == 2) NSFEM_LAT_KINDS(2);
+  else if (kind != 0) NSFEM_LAT_KINDS(1);
+  else if (gh && nv == 2) NSFEM_LAT_K(2, 4, true, 0);
+  else if (gh) NSFEM_LAT_K(1, 4, true, 0);
+  else if (nv == 2 && shape == 1) NSFEM_LAT_K(2, 2, false, 0);
+  else if (nv == 2 && shape == 2) NSFEM_LAT_K(2, 6, false, 0);
+  else if (nv == 2) NSFEM_LAT_K(2, 4, false, 0);
+  else if (shape == 1) NSFEM_LAT_K(1, 2, false, 0);
+  else if (shape == 2) NSFEM_LAT_K(1, 6, false, 0);
+  else NSFEM_LAT_K(1, 4, false, 0);
+#undef NSFEM_LAT_KINDS
 #undef NSFEM_LAT_K
 #undef NSFEM_LAT
   NSFEM_HIP(hipGetLastError());

@@ -288,8 +288,15 @@ int lattice_smoother_max_steps(const BlockMat& A, bool from_zero, bool with_resi
 struct LatticeLaunchOverride {
   int tile_lines = 0;       // 0: the launcher's choice; 16, 24, 32, 48: forced (refused when the halo does not fit)
   int fixed = -1;           // -1: NSFEM_LATTICE_FIXED; 0 / 1: compile-time-offset stages off / on
+  int generic = 0;          // 1: the runtime-flag kernel even where the launch kind has a specialised instantiation
   int used_tile_lines = 0, tx = 0, ty = 0, tiles = 0, fixed_shape = 0;   // out
+  int kind = 0;             // out: the launch kind that ran (lattice_launch_kind; 0: the runtime-flag kernel)
 };
+// launch kind of k_cheb_lattice for these operands: LK_FIXED (64) | operand flags (x_in 1, xc 2, rf 4, d_in 8, d_out 16,
+// r_out 32) where a specialised instantiation exists, else 0
+int lattice_launch_kind(bool x_in, bool xc, bool rf, bool d_in, bool d_out, bool r_out, bool ghost);
+// do the lattice's vectors (w x h nodes, nv components; with rf also the finer lattice's) fit 32-bit byte offsets?
+bool lattice_offsets_fit(int64_t w, int64_t h, int nv, bool rf);
 void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double* x_in, const double* b,
                          const double* d_in, double* x_out, double* d_out, double* r_out,
                          const uint8_t* mask, int steps, const double* c1, const double* c2, int ident,
