@@ -504,9 +504,19 @@ int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32_t H, int32
    poisson_fd.factors_3d(). */
 int nsfem_poisson_set_fast_diag_3d(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz, const double* Vx,
                                    const double* Vy, const double* Vz, const double* inv, int32_t exact);
+/* The same on partitioned slabs (nsfem_set_partition with a communicator): the factors of the GLOBAL Nz x Ny x Nx
+   lattice; local P1 plane i is global plane (first_plane + i) mod Nz (ghost planes included; periodic partitions
+   only may wrap around), and the owned dofs (the P1 ghost flags) are one contiguous run of whole planes.  precond = 3
+   of the projection step (no pressure Dirichlet dofs) then costs ONE all-reduce of Nz x Ny x Nx doubles -- a direct
+   solve for exact factors, CG preconditioned by T^+ otherwise -- and returns the pressure with valid ghost planes.
+   NSFEM_ERR_ARG: no partition / communicator, n_p1 not a multiple of Nx Ny, Nx Ny Nz != the global P1 count, owned
+   dofs not a run of whole planes, wrapping planes on a non-periodic partition.  Replaces other factors. */
+int nsfem_poisson_set_fast_diag_3d_planes(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz, int32_t first_plane,
+                                          const double* Vx, const double* Vy, const double* Vz, const double* inv,
+                                          int32_t exact);
 /* out = {Nx, Ny, Nz, exact, applications of T^+ issued by the host (CG iterations replayed from a captured graph apply
    it without the host), projection solves that ran with the 3D factors}; zeros when none are set.
-   nsfem_mg_apply(which = 2) applies z = T^+ r when 3D factors are set. */
+   nsfem_mg_apply(which = 2) applies z = T^+ r when 3D factors are set (slab factors: a collective). */
 int nsfem_poisson_fast_diag_3d_info(nsfem_ctx* ctx, int64_t out[6]);
 int nsfem_mg_info(nsfem_ctx* ctx, int which, int64_t out[4]);
 /* in-situ HIP-event timing of the matrix-free convection action of the velocity Jacobian inside

@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_partition", "nsfem_comm_unique_id", "nsfem_comm_attach_rccl",
     "nsfem_comm_local_create", "nsfem_comm_local_destroy", "nsfem_comm_attach_local", "nsfem_comm_attach_shm",
     "nsfem_mg_apply", "nsfem_mg_info", "nsfem_poisson_set_fast_diag", "nsfem_poisson_set_fast_diag_rows",
-    "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_fast_diag_3d_info",
+    "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_set_fast_diag_3d_planes", "nsfem_poisson_fast_diag_3d_info",
     "nsfem_operator_diagonal",
 )
 
@@ -216,6 +216,7 @@ def load_library(path=None):
         "nsfem_operator_diagonal": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_poisson_set_fast_diag_rows": (C.c_int, [vp, i32, i32, i32, pd, pd, pd]),
         "nsfem_poisson_set_fast_diag_3d": (C.c_int, [vp, i32, i32, i32, pd, pd, pd, pd, i32]),
+        "nsfem_poisson_set_fast_diag_3d_planes": (C.c_int, [vp, i32, i32, i32, i32, pd, pd, pd, pd, i32]),
         "nsfem_poisson_fast_diag_3d_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_halo_lists": (C.c_int, [vp, C.c_int, C.POINTER(HaloLists)]),
         "nsfem_mg_set_global_index": (C.c_int, [vp, i32, pi]),
@@ -501,15 +502,22 @@ class NsfemContext:
             self._check(self._lib.nsfem_poisson_set_fast_diag_rows(self._h, W, H, int(first_line), _dp(vx), _dp(vy),
                                                                    _dp(inv)))
 
-    def poisson_set_fast_diag_3d(self, factors):
+    def poisson_set_fast_diag_3d(self, factors, first_plane=None):
         """factors of poisson_fd.factors_3d(): the projection step may then run with Krylov option precond = 3 -- a
-        direct solve when factors["exact"], CG preconditioned by T^+ otherwise.  Replaces factors set before."""
+        direct solve when factors["exact"], CG preconditioned by T^+ otherwise.  Replaces factors set before.
+        first_plane (partitioned slabs): the factors belong to the GLOBAL lattice, this context's pressure space is
+        its planes (first_plane + i) mod N_z (ghost planes included); the solve is then a collective"""
         inv = np.ascontiguousarray(factors["inv"], dtype=np.float64)
         vx, vy, vz = (np.ascontiguousarray(factors[k], dtype=np.float64) for k in ("Vx", "Vy", "Vz"))
         Nz, Ny, Nx = inv.shape
         assert vx.shape == (Nx, Nx) and vy.shape == (Ny, Ny) and vz.shape == (Nz, Nz)
-        self._check(self._lib.nsfem_poisson_set_fast_diag_3d(self._h, Nx, Ny, Nz, _dp(vx), _dp(vy), _dp(vz), _dp(inv),
-                                                             1 if factors["exact"] else 0))
+        exact = 1 if factors["exact"] else 0
+        if first_plane is None:
+            self._check(self._lib.nsfem_poisson_set_fast_diag_3d(self._h, Nx, Ny, Nz, _dp(vx), _dp(vy), _dp(vz),
+                                                                 _dp(inv), exact))
+        else:
+            self._check(self._lib.nsfem_poisson_set_fast_diag_3d_planes(self._h, Nx, Ny, Nz, int(first_plane), _dp(vx),
+                                                                        _dp(vy), _dp(vz), _dp(inv), exact))
 
     def poisson_fast_diag_3d_info(self):
         """dict(shape=(Nx, Ny, Nz), exact, applications, solves) of the 3D factors (zeros when none are set);

@@ -1060,14 +1060,15 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   ++w.touch;
   double* parts = w.parts.p;
   constexpr int PR = 10, PB0 = 13;
-  // Partitioned strips: the same solve with ONE collective (FastDiag::apply_strip).  u* carries valid ghost values
-  // (every Krylov solve fills the ghosts of its solution), so D u* is complete on the owned rows; ghost rows are
-  // zeroed (every node counts once in the sums over the ranks); z comes back on every local row, ghost lines
-  // included, so p = p_old + z needs no halo exchange and the check r - A z none either.
+  // Partitioned strips / slabs: the same solve with ONE collective (FastDiag::apply_strip, FastDiag3::apply_slab).
+  // u* carries valid ghost values (every Krylov solve fills the ghosts of its solution), so D u* is complete on the
+  // owned rows; ghost rows are zeroed (every node counts once in the sums over the ranks); z comes back on every local
+  // row, ghost lines / planes included, so p = p_old + z needs no halo exchange and the check r - A z none either.
   const bool dist = c->distributed();
   const uint8_t* gm = dist ? c->mask_p.p : nullptr;                            // (flag 2 on ghost rows)
-  NSFEM_REQUIRE(!dist || (c->fd_p.strip() && gm), "fast diagonalisation on a partitioned mesh: strip factors not set");
   const bool box = c->fd3_p.ready();            // exact 3D factors (the caller checks)
+  NSFEM_REQUIRE(!dist || ((box ? c->fd3_p.slab() : c->fd_p.strip()) && gm),
+                "fast diagonalisation on a partitioned mesh: strip or slab factors not set");
   if (box) ++c->fd3_p.solves;
   launch_spmv_scaled(s, c->Dv, 1, -c->alpha[0] / c->k, c->state[NSFEM_USTAR].p, w.r.p);
   if (dist) {
@@ -1088,8 +1089,8 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   info.iterations = 0;
   info.converged = 0;
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
-    if (dist) c->fd_p.apply_strip(s, c->comm, r, w.z.p);
-    else if (box) c->fd3_p.apply(s, r, w.z.p);
+    if (box) c->fd3_p.apply(s, r, w.z.p);                                      // (slab factors: a collective)
+    else if (dist) c->fd_p.apply_strip(s, c->comm, r, w.z.p);
     else c->fd_p.apply(s, r, w.z.p);
     launch_axpby(s, np, 1.0, base, 1.0, w.z.p, c->state[NSFEM_P].p);          // p = p_old + z (later passes: p += z)
     base = c->state[NSFEM_P].p;
@@ -1129,7 +1130,11 @@ static int poisson_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_i
     op.prec = &c->mg_p;
   }
   if (box_pcg) {
-    NSFEM_REQUIRE(!c->distributed() && (int64_t)c->fd3_p.Nx * c->fd3_p.Ny * c->fd3_p.Nz == npre(c),
+    // (slab factors: T^+ is a collective with valid ghost planes in z; the CG iteration itself exchanges halos)
+    const FastDiag3& f = c->fd3_p;
+    const int64_t pl = (int64_t)f.Nx * f.Ny;
+    NSFEM_REQUIRE(c->distributed() == f.slab() &&
+                      (f.slab() ? pl * f.Nz == c->n_p1_global && pl * f.n_loc == npre(c) : pl * f.Nz == npre(c)),
                   "fast diagonalisation (3D): factors do not fit the pressure space");
     op.prec = &c->fd3_p;
     ++c->fd3_p.solves;
@@ -1690,6 +1695,7 @@ extern "C" int nsfem_comm_attach_local(nsfem_ctx* ctx, void* group, int rank) {
   ctx->comm = make_local_comm(group, rank);
   ctx->comm->periodic = ctx->partition_periodic;
   ctx->comm->overlap = ctx->overlap;
+  if (ctx->fd3_p.slab()) ctx->fd3_p.comm = ctx->comm;
   API_END(ctx)
 }
 
@@ -1702,6 +1708,7 @@ extern "C" int nsfem_comm_attach_rccl(nsfem_ctx* ctx, const char* id128, int ran
   ctx->comm = make_rccl_comm(id128, rank, size);
   ctx->comm->periodic = ctx->partition_periodic;
   ctx->comm->overlap = ctx->overlap;
+  if (ctx->fd3_p.slab()) ctx->fd3_p.comm = ctx->comm;
   API_END(ctx)
 }
 
@@ -1714,6 +1721,7 @@ extern "C" int nsfem_comm_attach_shm(nsfem_ctx* ctx, const char* name, int rank,
   ctx->comm = make_shm_comm(name, rank, size, slot_bytes);
   ctx->comm->periodic = ctx->partition_periodic;
   ctx->comm->overlap = ctx->overlap;
+  if (ctx->fd3_p.slab()) ctx->fd3_p.comm = ctx->comm;
   API_END(ctx)
 }
 
@@ -2058,7 +2066,7 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
                   "fast diagonalisation on a partitioned mesh solves the pure Neumann projection step only "
                   "(pressure Dirichlet nodes are set): use another Poisson preconditioner");
     // (3D box lattices: the pass-plus-check driver for exact factors; inexact ones assemble and run CG with T^+)
-    const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && !ctx->distributed()
+    const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && ctx->distributed() == ctx->fd3_p.slab()
                                            : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
     if (fd && !pressure_pinned_anywhere(ctx) && direct) {
       rc = poisson_direct_step(ctx, opts->poisson, si);
@@ -2780,12 +2788,62 @@ extern "C" int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32
                 "fast diagonalisation: the local pressure space is not a run of whole lattice lines");
   NSFEM_REQUIRE((int64_t)W * H == ctx->n_p1_global, "fast diagonalisation: W x H must be the global number of pressure dofs");
   ctx->fd_p.set_rows(ctx->stream, W, H, first_line, (int)(np / W), Vx, Vy, inv);
+  if (ctx->fd3_p.ready()) {             // (the factors set last are the ones precond = 3 uses)
+    ctx->fd3_p.release();
+    ctx->graph_epoch++;
+  }
+  API_END(ctx)
+}
+
+// Partitioned slabs of a 3D box lattice: the factors of the GLOBAL Nz x Ny x Nx lattice; this rank's P1 space is the
+// lattice planes (first_plane + i) mod Nz, i < n_p1 / (Nx Ny) (ghost planes included), and the planes it owns (the P1
+// ghost flags of nsfem_set_partition) are one contiguous run.  precond = 3 then solves the projection step with one
+// all-reduce of Nz x Ny x Nx doubles (FastDiag3::apply_slab): directly for exact factors, as the preconditioner of CG
+// otherwise.
+extern "C" int nsfem_poisson_set_fast_diag_3d_planes(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz,
+                                                     int32_t first_plane, const double* Vx, const double* Vy,
+                                                     const double* Vz, const double* inv, int32_t exact) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && Vx && Vy && Vz && inv, "null argument");
+  NSFEM_REQUIRE(ctx->distributed(), "slab factors need a partitioned context with a communicator "
+                                    "(nsfem_set_partition, nsfem_comm_attach_*)");
+  NSFEM_REQUIRE(Nx >= 2 && Ny >= 2 && Nz >= 2, "fast diagonalisation (3D): bad dims");
+  const int64_t np = npre(ctx), pl = (int64_t)Nx * Ny;
+  NSFEM_REQUIRE(np % pl == 0, "fast diagonalisation (3D): the local pressure space is not a run of whole lattice planes");
+  NSFEM_REQUIRE(pl * Nz == ctx->n_p1_global,
+                "fast diagonalisation (3D): Nx x Ny x Nz must be the global number of pressure dofs");
+  const int64_t n_loc = np / pl;
+  NSFEM_REQUIRE(first_plane >= 0 && first_plane < Nz && n_loc <= 65535,
+                "fast diagonalisation (3D): first plane out of range / too many local planes");
+  NSFEM_REQUIRE(ctx->partition_periodic || first_plane + n_loc <= Nz,
+                "fast diagonalisation (3D): the local planes wrap around on a partition that is not periodic");
+  // the owned planes: every plane wholly owned or wholly ghost, the owned ones one contiguous run
+  const std::vector<uint8_t>& g = ctx->h_ghost_p1;
+  NSFEM_REQUIRE((int64_t)g.size() == np, "fast diagonalisation (3D): no P1 ghost flags (nsfem_set_partition)");
+  int64_t own0 = -1, own_end = -1;
+  bool run = true;
+  for (int64_t i = 0; i < n_loc && run; ++i) {
+    const uint8_t* q = g.data() + i * pl;
+    const bool owned = q[0] == 0;
+    for (int64_t j = 1; j < pl && run; ++j) run = (q[j] == 0) == owned;
+    if (!owned) continue;
+    if (own0 < 0) own0 = i;
+    else if (own_end != i) run = false;
+    own_end = i + 1;
+  }
+  NSFEM_REQUIRE(run && own0 >= 0,
+                "fast diagonalisation (3D): the owned pressure dofs are not one contiguous run of whole lattice planes");
+  ctx->fd3_p.set_planes(ctx->stream, ctx->comm, Nx, Ny, Nz, first_plane, (int)n_loc, (int)own0, (int)(own_end - own0),
+                        Vx, Vy, Vz, inv, exact != 0);
+  ctx->fd_p.release();                  // (the factors set last are the ones precond = 3 uses)
+  ctx->graph_epoch++;                   // captured CG bodies hold the addresses of the previous factors / work buffers
   API_END(ctx)
 }
 
 // Test hook: one application z = M^-1 r of a multigrid preconditioner on host vectors -- which = 0 pressure Poisson
 // hierarchy (mg_p), 1 velocity hierarchy (mg_v, the identity rows of the Newton preconditioner included), 2 the
-// fast-diagonalisation solve z = A^+ r (FastDiag::apply; on strip factors FastDiag::apply_strip, a collective).  Lets
+// fast-diagonalisation solve z = A^+ r (FastDiag::apply; on strip factors FastDiag::apply_strip, on slab factors
+// FastDiag3::apply_slab: collectives).  Lets
 // the parity tests compare the fused multi-level launches (mglegs.hip) with the separate launches cycle by cycle.
 extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double* z) {
   API_BEGIN
@@ -2796,7 +2854,7 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
     DevBuf<double> dr, dz;
     dr.upload(r, (size_t)n, s);
     dz.alloc((size_t)n);
-    if (ctx->fd3_p.ready()) {          // 3D box lattice: z = T^+ r
+    if (ctx->fd3_p.ready()) {          // 3D box lattice: z = T^+ r (slab factors: a collective, ghost planes ignored)
       ctx->fd3_p.apply(s, dr.p, dz.p);
     } else if (ctx->fd_p.strip()) {    // strips (a collective: every rank calls it): ghost rows zeroed, as the step does
       NSFEM_REQUIRE(ctx->distributed(), "strip factors need a partitioned context");

@@ -127,6 +127,9 @@ void FastDiag3::set(hipStream_t s, int Nx_, int Ny_, int Nz_, const double* vx, 
   Ny = Ny_;
   Nz = Nz_;
   exact = exact_;
+  first = n_loc = own0 = n_own = 0;
+  comm = nullptr;
+  tz.release();
   const size_t n = (size_t)Nx * Ny * Nz;
   Vx.upload(vx, (size_t)Nx * Nx, s);
   Vy.upload(vy, (size_t)Ny * Ny, s);
@@ -139,14 +142,77 @@ void FastDiag3::set(hipStream_t s, int Nx_, int Ny_, int Nz_, const double* vx, 
   NSFEM_HIP(hipStreamSynchronize(s));
 }
 
+// Partitioned slabs (rank r holds the lattice planes (first + i) mod N_z, i < n_loc, ghost planes included, and owns the
+// run own0 ... own0 + n_own - 1 of them; every node is owned by one rank): the contraction over z is a sum over the
+// ranks, the other two directions stay inside the planes,
+//
+//     T     = sum_ranks V_z[owned planes, :]^T (R_own x_1 V_x x_2 V_y)  .* inv      one all-reduce of N_z N_y N_x doubles
+//     Z_loc = (V_z[local planes, :] T) x_2 V_y^T x_1 V_x^T                           every local plane, ghosts included
+//
+// -- the strip design of FastDiag::apply_strip one dimension up.  Only owned planes enter the contraction (the ghost
+// planes of r are never read), so inv goes into that product's epilogue: an elementwise scale commutes with the sum.
+void FastDiag3::set_planes(hipStream_t s, Comm* comm_, int Nx_, int Ny_, int Nz_, int first_, int n_loc_, int own0_,
+                           int n_own_, const double* vx, const double* vy, const double* vz, const double* inv_,
+                           bool exact_) {
+  NSFEM_REQUIRE(comm_ && Nx_ >= 2 && Ny_ >= 2 && Nz_ >= 2 && vx && vy && vz && inv_, "fast diagonalisation (3D): bad factors");
+  NSFEM_REQUIRE(first_ >= 0 && first_ < Nz_ && n_loc_ >= 1 && n_loc_ <= 65535 && own0_ >= 0 && n_own_ >= 1 &&
+                    own0_ + n_own_ <= n_loc_ && n_own_ <= Nz_,
+                "fast diagonalisation (3D): bad local planes");
+  NSFEM_REQUIRE((int64_t)Nz_ * Ny_ < INT32_MAX && (int64_t)n_loc_ * Ny_ < INT32_MAX && (int64_t)Ny_ * Nx_ < INT32_MAX,
+                "fast diagonalisation (3D): lattice too large");
+  Nx = Nx_;
+  Ny = Ny_;
+  Nz = Nz_;
+  exact = exact_;
+  first = first_;
+  n_loc = n_loc_;
+  own0 = own0_;
+  n_own = n_own_;
+  comm = comm_;
+  const size_t pl = (size_t)Nx * Ny;
+  // rows (first + i) mod N_z of the row-major N_z x N_z matrix V_z (periodic slabs wrap around)
+  std::vector<double> rows((size_t)n_loc * Nz);
+  for (int i = 0; i < n_loc; ++i) {
+    const double* src = vz + (size_t)((first + i) % Nz) * Nz;
+    std::copy(src, src + Nz, rows.begin() + (size_t)i * Nz);
+  }
+  Vx.upload(vx, (size_t)Nx * Nx, s);
+  Vy.upload(vy, (size_t)Ny * Ny, s);
+  Vz.upload(rows.data(), rows.size(), s);
+  inv.upload(inv_, pl * Nz, s);
+  if (t1.n != pl * n_loc) t1.alloc(pl * n_loc);
+  if (t2.n != pl * n_loc) t2.alloc(pl * n_loc);
+  if (tz.n != pl * Nz) tz.alloc(pl * Nz);
+  NSFEM_HIP(hipStreamSynchronize(s));      // (rows is a pageable host vector)
+}
+
 void FastDiag3::release() {
   Nx = Ny = Nz = 0;
+  first = n_loc = own0 = n_own = 0;
+  comm = nullptr;
   exact = false;
-  for (DevBuf<double>* b : {&Vx, &Vy, &Vz, &inv, &t1, &t2}) b->release();
+  for (DevBuf<double>* b : {&Vx, &Vy, &Vz, &inv, &t1, &t2, &tz}) b->release();
+}
+
+// slabs: r on the local planes in (its ghost planes ignored), z on EVERY local plane out -- a collective
+void FastDiag3::apply_slab(hipStream_t s, const double* r, double* z) {
+  NSFEM_REQUIRE(ready() && slab() && comm, "fast diagonalisation (3D): slab factors / communicator not set");
+  const int pl = Ny * Nx;
+  const double* r_own = r + (size_t)own0 * pl;
+  launch_fd_gemm(s, false, false, n_own * Ny, Nx, Nx, r_own, Nx, Vx.p, Nx, t1.p, Nx, nullptr);    // x: owned planes
+  fd_gemm_planes<true>(s, Nx, Ny, n_own, Vy.p, t1.p, t2.p);                                        // y: V_y^T per plane
+  launch_fd_gemm(s, true, false, Nz, pl, n_own, Vz.p + (size_t)own0 * Nz, Nz, t2.p, pl, tz.p, pl,  // z: partial sum
+                 inv.p);                                                                            //    .* inv
+  comm->allreduce_sum(s, tz.p, (int64_t)Nz * pl);
+  launch_fd_gemm(s, false, false, n_loc, pl, Nz, Vz.p, Nz, tz.p, pl, t1.p, pl, nullptr);            // z: local planes
+  fd_gemm_planes<false>(s, Nx, Ny, n_loc, Vy.p, t1.p, t2.p);                                       // y: V_y per plane
+  launch_fd_gemm(s, false, true, n_loc * Ny, Nx, Nx, t2.p, Nx, Vx.p, Nx, z, Nx, nullptr);          // x: ... V_x^T
+  ++applications;
 }
 
 // z = T^+ r: six launches, r and z untouched until the first / last one
 void FastDiag3::apply(hipStream_t s, const double* r, double* z) {
+  if (slab()) return apply_slab(s, r, z);      // (CG preconditioned by the slab T^+: op.prec)
   NSFEM_REQUIRE(ready(), "fast diagonalisation (3D): factors not set");
   const int pl = Ny * Nx, rows = Nz * Ny;
   launch_fd_gemm(s, false, false, rows, Nx, Nx, r, Nx, Vx.p, Nx, t1.p, Nx, nullptr);        // x:  R x_1 V_x

@@ -884,16 +884,29 @@ void launch_fd_gemm(hipStream_t s, bool ta, bool tb, int M, int N, int K, const 
 // T is the P1 stiffness matrix itself (the projection step is one pass plus the residual check); otherwise T^+
 // preconditions CG.
 struct FastDiag3 : Precond {
-  int Nx = 0, Ny = 0, Nz = 0;
+  int Nx = 0, Ny = 0, Nz = 0;    // the GLOBAL lattice
   bool exact = false;
-  DevBuf<double> Vx, Vy, Vz, inv, t1, t2;
+  // partitioned slabs: this rank holds the n_loc lattice planes (first + i) mod Nz (ghost planes included) and owns
+  // the run own0 ... own0 + n_own - 1 of them; Vz then keeps the rows of V_z of its local planes.  n_loc == 0: the
+  // whole lattice (one rank)
+  int first = 0, n_loc = 0, own0 = 0, n_own = 0;
+  Comm* comm = nullptr;          // slabs: the context's communicator (the apply is a collective)
+  DevBuf<double> Vx, Vy, Vz, inv, t1, t2, tz;
   int64_t applications = 0;      // apply() calls issued by the host (a CG iteration replayed from a graph: not counted)
   int64_t solves = 0;            // projection solves that ran with these factors
   bool ready() const { return Nx > 0 && Vx.p && Vy.p && Vz.p && inv.p; }
+  bool slab() const { return n_loc > 0; }
   void set(hipStream_t s, int Nx_, int Ny_, int Nz_, const double* vx, const double* vy, const double* vz,
            const double* inv_, bool exact_);
+  // vz: the GLOBAL Nz x Nz matrix (its rows of the local planes are gathered here)
+  void set_planes(hipStream_t s, Comm* comm_, int Nx_, int Ny_, int Nz_, int first_, int n_loc_, int own0_,
+                  int n_own_, const double* vx, const double* vy, const double* vz, const double* inv_, bool exact_);
   void release();
+  // one rank: z = T^+ r; slabs: apply_slab
   void apply(hipStream_t s, const double* r, double* z) override;
+  // slabs: r on the local planes in (ghost planes never read), z on EVERY local plane out (ghost planes included);
+  // one all-reduce of the Nz x Ny x Nx transformed array in between
+  void apply_slab(hipStream_t s, const double* r, double* z);
 };
 // x -= sum(parts) / count on n entries (k_sum fills the slot: launch_sum)
 void launch_sum(hipStream_t s, int64_t n, const double* x, double* parts);

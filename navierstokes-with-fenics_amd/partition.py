@@ -216,6 +216,17 @@ class SlabLevel:
         return self.row0 * self.w1
 
 
+def _attach_slab_fast_diag(ctx, part, periodic):
+    """poisson_fd.factors_3d of the global (nx, ny, nz) box of ``part`` sent with the rank's first lattice plane
+    (local P1 plane i is global plane (first + i) mod N_z) -> factors["exact"]"""
+    import poisson_fd
+    lines = [np.linspace(part.p0[a], part.p1[a], m + 1) for a, m in enumerate((part.nx, part.ny, part.nz))]
+    f = poisson_fd.factors_3d(*lines, periodic=periodic, dirichlet_nodes=np.zeros(0, np.int64))
+    plane = f["inv"].shape[1] * f["inv"].shape[2]
+    ctx.poisson_set_fast_diag_3d(f, first_plane=int(part.p1_global[0]) // plane)
+    return f["exact"]
+
+
 class SlabPartition:
     """3D counterpart of ``StripPartition``: rank ``rank`` of ``size`` owns nz / size cube layers
     of the (nx, ny, nz) Kuhn box mesh (dofs of its layers except the bottom lattice plane) and
@@ -301,6 +312,13 @@ class SlabPartition:
             ctx.mg_add_global_level(mesh.coords, mesh.cells, rowptr, col, val)
         ctx.mg_finalize(2 if degree is None else degree, 4.0 if eig_ratio is None else eig_ratio)
         return len(self.levels)
+
+    def attach_fast_diag(self, ctx):
+        """projection step by fast diagonalisation on this slab: the factors of the GLOBAL box lattice
+        (poisson_fd.factors_3d, no pressure Dirichlet nodes) and this rank's first lattice plane.  Krylov option
+        precond = 3 then solves it with one all-reduce of the transformed lattice array -> factors["exact"] (a direct
+        solve; False: CG preconditioned by the tensor-sum solve)"""
+        return _attach_slab_fast_diag(ctx, self, (False, False, False))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -464,6 +482,10 @@ class PeriodicSlabPartition:
             f_dof = c_dof
         ctx.mg_finalize(2 if degree is None else degree, 4.0 if eig_ratio is None else eig_ratio)
         return len(self.levels)
+
+    def attach_fast_diag(self, ctx):
+        """as SlabPartition.attach_fast_diag, on the triple-periodic lattice (the last rank's planes wrap around)"""
+        return _attach_slab_fast_diag(ctx, self, (True, True, True))
 
 
 # ---------------------------------------------------------------------------------------------
