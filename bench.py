@@ -16,15 +16,19 @@ Solver settings of the timed steps (SURVEY.md section 8d "throughput runs"): New
 reference's criterion (|F| < 1e-10 or |F|/|F0| < 1e-9, checked on the true nonlinear residual
 every iteration), the linear solves inside it are inexact (residual reduced by
 --newton-forcing = 1e-4, never below a tenth of the nonlinear target), Poisson / mass solves to
---krylov-rtol = 1e-8.  The same steps with direct-solver accuracy (rtol 1e-12, exact Newton) are
-timed right after and reported as config.ms_per_step_with_krylov_rtol_1e-12_exact_newton.
+--krylov-rtol = 1e-8.
 
-Prints ONE JSON line (driver contract) that also carries
-  "roofline":     dominant kernel (block-CSR SpMV of the momentum Jacobian), algorithmic
+Prints ONE JSON line (driver contract).  A plain run sets up, runs the warm-up and timed steps,
+dumps the fields if --dump-outputs asks, and prints the headline figure.  With --full, the
+same steps with direct-solver accuracy (rtol 1e-12, exact Newton) are timed right after and
+must reproduce the timed fields (config.ms_per_step_with_krylov_rtol_1e-12_exact_newton,
+config.validation), and the line also carries
+  "roofline":     dominant kernel (finest-level multigrid smoothing launch), algorithmic
                   bytes per launch / HIP-event time on the kernel's stream vs 8 TB/s HBM;
   "cpu_baseline": the CPU oracle configured as the reference works (full re-assembly +
                   sparse LU every Newton iteration, Poisson/mass re-factorised every step)
-                  timed on a bounded sample on this host (rank 0, N = 1 only).
+                  timed on a bounded sample on this host (rank 0, N = 1 only);
+and the other blocks --full lists in its help (solver classes, other_configs, strong_n1, weak).
 """
 import argparse
 import json
@@ -973,7 +977,7 @@ def _trace_numbers(n, world):
 
 
 def _other_configs(args):
-    """BASELINE configs[2..4] at their bench sizes in the default job, a few timed steps each, every one in a process
+    """BASELINE configs[2..4] at their bench sizes in a --full job, a few timed steps each, every one in a process
     of its own (fresh context, its own device memory): the driver's run then times them as well"""
     import subprocess
     out = []
@@ -1199,19 +1203,40 @@ def cavity_ipcs_bench(args):
     steps_per_s = args.steps / elapsed
     u_fast, p_fast = ctx.get_state(nat.U1), ctx.get_state(nat.P_OLD)
     _dump_outputs(args, rank, world, {"velocity": u_fast, "pressure": p_fast})
-    if args.timed_only:
+    out = {
+        "metric": "dof_updates_per_sec", "value": steps_per_s * n_dofs, "unit": "DoF-updates/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "time_steps_per_sec": steps_per_s,
+        "config": {"workload": "2D lid-driven cavity Re=100, %dx%d right-diagonal Taylor-Hood P2/P1 "
+                               "(%d dofs), IPCS, BDF-2, dt=%g, zero initial state" % (
+                                   n, ny_global, n_dofs, args.dt),
+                   "cells": n, "n_dofs": n_dofs, "newton_tol": 1e-10, "krylov_rtol": args.krylov_rtol,
+                   "newton_forcing": args.newton_forcing,
+                   "velocity_jacobian": {0: "matrix-free (default)", 1: "assembled block CSR",
+                                         2: "matrix-free"}[args.matrix_free],
+                   "poisson_solver": ("fast diagonalisation: x += V_y ((V_y^T R V_x) .* inv) V_x^T, four fp64 MFMA products "
+                                      "(csrc/fastdiag.hip), one pass + residual check" +
+                                      ("; strips: every rank contracts its own lattice lines, ONE all-reduce of the "
+                                       "%d x %d transformed array per solve, no halo exchange" % (ny_global + 1, n + 1)
+                                       if dist is not None else "") if fast_diag else
+                                      "CG preconditioned by the pressure V(2,2) cycle"),
+                   "preconditioner": "jacobi" if mg_levels is None else
+                   "geometric multigrid, Chebyshev-Jacobi smoothing: V(0,3) momentum, V(2,2) Poisson; %d coarse P1 levels" % mg_levels,
+                   "parallelism": "1 GPU" if world == 1 else
+                   "%d strips of %d cell rows, RCCL halo exchange (%s mode, overlap %s) + all-reduce" % (
+                       world, ny_global // world, args.halo_mode, args.overlap),
+                   "newton_its_per_step": float(its[0]),
+                   "bicgstab_its_per_step": float(its[1]), "poisson_cg_its_per_step": float(its[2]),
+                   "comm_per_step_rank0": comm_per_step},
+        "roofline": {"frac": None, "ms_per_launch": None, "note": "per-kernel figures are measured by --full runs"}}
+    if not args.full:
+        # a plain run: the headline figure is all it measures
         ctx.close()
         _finish_dist(dist)
-        return {"metric": "dof_updates_per_sec", "value": steps_per_s * n_dofs, "unit": "DoF-updates/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-                "scaling": "strong" if strong else "weak", "dtype": "f64", "data": "synthetic",
-                "time_steps_per_sec": steps_per_s,
-                "config": {"workload": "cavity-ipcs %dx%d, timed steps only" % (n, ny_global),
-                           "cells": n, "n_dofs": n_dofs, "poisson_solver": "fd" if fast_diag else "mg",
-                           "newton_its_per_step": float(its[0]), "bicgstab_its_per_step": float(its[1]),
-                           "poisson_cg_its_per_step": float(its[2]), "comm_per_step_rank0": comm_per_step},
-                "roofline": {"frac": None, "ms_per_launch": None}}
+        return out
 
     # ---- validation of what was timed: the SAME W + K steps from the same start with
     # direct-solver accuracy (rtol 1e-12, exact Newton, Jacobi-CG mass solve, untruncated cycle);
@@ -1344,44 +1369,18 @@ def cavity_ipcs_bench(args):
     tol_fields = 1.0e-6
     smoother_label, smoother_extra = (_smoother_roofline_extras(ctx, 2, ms_spmv, cold["ms_per_launch"] if cold else None)
                                       if mg_levels is not None else ("", {}))
-    out = {
-        "metric": "dof_updates_per_sec", "value": steps_per_s * n_dofs, "unit": "DoF-updates/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "time_steps_per_sec": steps_per_s,
-        "config": {"workload": "2D lid-driven cavity Re=100, %dx%d right-diagonal Taylor-Hood P2/P1 "
-                               "(%d dofs), IPCS, BDF-2, dt=%g, zero initial state" % (
-                                   n, ny_global, n_dofs, args.dt),
-                   "n_dofs": n_dofs, "newton_tol": 1e-10, "krylov_rtol": args.krylov_rtol,
-                   "newton_forcing": args.newton_forcing,
-                   "velocity_jacobian": {0: "matrix-free (default)", 1: "assembled block CSR",
-                                         2: "matrix-free"}[args.matrix_free],
-                   "ms_per_step_with_krylov_rtol_1e-12_exact_newton": ms_parity,
-                   "validation": {"what": "the %d timed + %d warm-up steps repeated from the same start with "
-                                          "Krylov rtol 1e-12, exact Newton, Jacobi-CG mass solve and the "
-                                          "untruncated velocity cycle; fields of the timed run vs those" % (
-                                              args.steps, args.warmup),
-                                  "max_rel_diff_velocity_vs_exact": du_l2,
-                                  "max_rel_diff_velocity_vs_exact_maxnorm": du_max,
-                                  "max_rel_diff_pressure_vs_exact": dp_l2,
-                                  "tolerance": tol_fields,
-                                  "newton_bicgstab_poisson_its_per_step_exact": [float(v) for v in its_exact]},
-                   "poisson_solver": ("fast diagonalisation: x += V_y ((V_y^T R V_x) .* inv) V_x^T, four fp64 MFMA products "
-                                      "(csrc/fastdiag.hip), one pass + residual check" +
-                                      ("; strips: every rank contracts its own lattice lines, ONE all-reduce of the "
-                                       "%d x %d transformed array per solve, no halo exchange" % (ny_global + 1, n + 1)
-                                       if dist is not None else "") if fast_diag else
-                                      "CG preconditioned by the pressure V(2,2) cycle"),
-                   "preconditioner": "jacobi" if mg_levels is None else
-                   "geometric multigrid, Chebyshev-Jacobi smoothing: V(0,3) momentum, V(2,2) Poisson; %d coarse P1 levels" % mg_levels,
-                   "parallelism": "1 GPU" if world == 1 else
-                   "%d strips of %d cell rows, RCCL halo exchange (%s mode, overlap %s) + all-reduce" % (
-                       world, ny_global // world, args.halo_mode, args.overlap),
-                   "newton_its_per_step": float(its[0]),
-                   "bicgstab_its_per_step": float(its[1]), "poisson_cg_its_per_step": float(its[2]),
-                   "comm_per_step_rank0": comm_per_step},
+    out["config"].update({
+        "ms_per_step_with_krylov_rtol_1e-12_exact_newton": ms_parity,
+        "validation": {"what": "the %d timed + %d warm-up steps repeated from the same start with "
+                               "Krylov rtol 1e-12, exact Newton, Jacobi-CG mass solve and the "
+                               "untruncated velocity cycle; fields of the timed run vs those" % (
+                                   args.steps, args.warmup),
+                       "max_rel_diff_velocity_vs_exact": du_l2,
+                       "max_rel_diff_velocity_vs_exact_maxnorm": du_max,
+                       "max_rel_diff_pressure_vs_exact": dp_l2,
+                       "tolerance": tol_fields,
+                       "newton_bicgstab_poisson_its_per_step_exact": [float(v) for v in its_exact]}})
+    out.update({
         "roofline": {"bound": "latency/issue" if lattice else "hbm",
                      "kernel": smoother_label if mg_levels is not None else "k_spmv_stream_v1<2,2,1,0> (momentum Jacobian)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1400,7 +1399,7 @@ def cavity_ipcs_bench(args):
                           "achieved": nbytes_jac / (ms_jac * 1e-3) / 1e9, "unit": "GB/s",
                           "frac": nbytes_jac / (ms_jac * 1e-3) / 1e9 / HBM_PEAK_GBS,
                           "algorithmic_bytes_per_launch": nbytes_jac, "ms_per_launch": ms_jac},
-    }
+    })
     out["roofline"].update(smoother_extra)
     if lattice:
         out["roofline"].update(_issue_floor(n))
@@ -1541,12 +1540,18 @@ def main():
     ap.add_argument("--strong-cells", type=int, default=None,
                     help="--gpus N > 1: cells per side of the strong-scaling mesh of the default job "
                          "(default 960 = 8.3 M dofs; with --cells n: n)")
+    ap.add_argument("--full", action="store_true",
+                    help="cavity-ipcs: besides the headline figure, everything else the benchmark measures and checks: "
+                         "the validation rerun with direct-solver accuracy, in-situ and cache-cold kernel timings, the "
+                         "pass through the solver classes, the CPU baseline, `other_configs`, `strong_n1` (one GPU) and "
+                         "`weak` (N > 1).  Without it a run sets up, warms up, times the steps, dumps its outputs if "
+                         "asked and prints the headline line.  (The other --workload runs print their whole line either way.)")
     ap.add_argument("--timed-only", action="store_true",
-                    help="profiling aid: only the warm-up and timed steps (no validation rerun, no in-situ / "
-                         "cold-cache kernel timing, no CPU baseline); the JSON line lacks those entries")
+                    help="profiling aid: only the warm-up and timed steps even with --full; with --gpus N > 1 the "
+                         "weak-scaling run of --cells cells per rank instead of the strong-scaling one")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false",
-                    help="skip the short runs of BASELINE configs[2..4] (dfg-bdf, tgv3d-ipcs 64, channel3d-bdf 48) that the "
-                         "default job appends as `other_configs`")
+                    help="skip the short runs of BASELINE configs[2..4] (dfg-bdf, tgv3d-ipcs 64, channel3d-bdf 48) that a "
+                         "--full run appends as `other_configs`")
     ap.add_argument("--trace-markers", action="store_true",
                     help="profiling aid: one k_cfl launch right before and right after the timed steps, so that a kernel "
                          "trace can be cut to the timed region (scripts/trace_gaps.py --between k_cfl)")
@@ -1590,6 +1595,7 @@ def main():
                     help="functional rehearsal of the N-rank paths on ONE GPU: N threads of this process, "
                          "in-process communicator (no RCCL; not a performance mode)")
     args = ap.parse_args()
+    args.full = args.full and not args.timed_only
     if args.cpu_samples is None:
         args.cpu_samples = "24:4,32:4,48:3,64:3" + (",128:1" if (os.cpu_count() or 1) >= 64 else "")
     if args.local_ranks > 1:
@@ -1642,7 +1648,7 @@ def _run_workload(args):
         return channel3d_bdf_bench(args)
     import copy
     rank = args.thread_rank if getattr(args, "thread_ranks", None) is not None else int(os.environ.get("RANK", "0"))
-    default_job = args.n is None and not args.timed_only
+    default_job = args.n is None and args.full
     both = args.gpus > 1 and args.scaling == "weak" and not args.timed_only and not args.no_strong
     if args.strong_cells is None:
         args.strong_cells = 960 if args.n in (None, 512) else args.n
@@ -1660,15 +1666,18 @@ def _run_workload(args):
         # N > 1 (round 4): the HEADLINE of the line is north_star's strong-scaling quantity -- ONE 960 x 960 mesh
         # (8.3 M dofs) cut into N strips, `"scaling": "strong"` --, the weak-scaling figure (512 x 512 cells per rank,
         # so N = 1 equals the single-GPU line) rides along as the `weak` block.  The one-GPU point of the strong
-        # curve is the `strong_n1` block of the N = 1 line (same mesh on one GPU).
+        # curve is the `strong_n1` block of the N = 1 line (same mesh on one GPU).  A plain run stops after the
+        # strong-scaling run; --full adds its validation and the `weak` block.
         a2 = copy.copy(args)
         a2.scaling, a2.n = "strong", args.strong_cells
         a2.no_cpu_baseline = a2.no_solver_classes = True
         a2.other_configs = False
         out = cavity_ipcs_bench(a2)
-        a1 = copy.copy(args)
-        a1.n, a1.timed_only, a1.dump_outputs = args.n or 512, True, None
-        wk = cavity_ipcs_bench(a1)
+        wk = None
+        if args.full:
+            a1 = copy.copy(args)
+            a1.n, a1.full, a1.dump_outputs = args.n or 512, False, None
+            wk = cavity_ipcs_bench(a1)
         if out is not None and wk is not None:
             out["weak"] = strong_block(wk, a1)
             out["weak"]["note"] = "512 x 512 cells PER RANK (fixed work per GPU); value = all ranks' DoF-updates per second"
@@ -1678,7 +1687,7 @@ def _run_workload(args):
         if default_job and args.gpus == 1 and out is not None and args.scaling == "weak" and not args.no_strong:
             # the one-GPU point of the strong-scaling curve the N > 1 lines report: the 960 x 960 mesh on one GPU
             a2 = copy.copy(args)
-            a2.scaling, a2.n, a2.timed_only, a2.dump_outputs = "strong", args.strong_cells, True, None
+            a2.scaling, a2.n, a2.full, a2.dump_outputs = "strong", args.strong_cells, False, None
             a2.steps, a2.warmup = min(args.steps, 10), min(args.warmup, 3)
             st = cavity_ipcs_bench(a2)
             out["strong_n1"] = strong_block(st, a2)

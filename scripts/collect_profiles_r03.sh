@@ -27,9 +27,9 @@ pmc() {  # name, bench args...
   rm -rf $O/p_${name}_FETCH_SIZE $O/p_${name}_WRITE_SIZE
   echo "pmc $name done"
 }
-trace bench_n512 --steps 20 --warmup 5 --no-cpu-baseline
+trace bench_n512 --full --steps 20 --warmup 5 --no-cpu-baseline
 trace bench_n512_timed_steps_only --steps 40 --warmup 10 --timed-only
-trace bench_n1024 --cells 1024 --steps 5 --warmup 2 --no-cpu-baseline --no-solver-classes
+trace bench_n1024 --full --cells 1024 --steps 5 --warmup 2 --no-cpu-baseline --no-solver-classes
 trace tgv3d_n64 --workload tgv3d-ipcs --cells 64 --steps 5 --warmup 2
 trace channel3d_n48 --workload channel3d-bdf --cells 48 --steps 3 --warmup 2
 export NSFEM_LATTICE=0
@@ -40,9 +40,9 @@ pmc bench_n1024 --cells 1024 --steps 1 --warmup 1 --timed-only
 pmc tgv3d_n64 --workload tgv3d-ipcs --cells 64 --steps 1 --warmup 1
 pmc channel3d_n64 --workload channel3d-bdf --cells 64 --steps 1 --warmup 1
 cd $REPO
-timeout -k 10 900 python3 bench.py > $O/${TAG}_bench_default.json 2> $O/bench_default.err
-timeout -k 10 600 python3 bench.py --cells 1024 --steps 20 --warmup 3 --no-cpu-baseline --no-solver-classes > $O/${TAG}_bench_n1024.json 2> $O/bench_1024.err
-timeout -k 10 600 python3 bench.py --cells 333 --steps 50 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_n333.json 2> $O/bench_333.err
+timeout -k 10 900 python3 bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python3 bench.py --full --cells 1024 --steps 20 --warmup 3 --no-cpu-baseline --no-solver-classes > $O/${TAG}_bench_n1024.json 2> $O/bench_1024.err
+timeout -k 10 600 python3 bench.py --full --cells 333 --steps 50 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_n333.json 2> $O/bench_333.err
 timeout -k 10 600 python3 bench.py --workload channel3d-bdf --cells 64 --steps 10 --warmup 3 > $O/${TAG}_bench_channel3d_n64.json 2> $O/bench_ch64.err
 timeout -k 10 600 python3 bench.py --workload channel3d-bdf --cells 48 --steps 10 --warmup 3 > $O/${TAG}_bench_channel3d_n48.json 2> $O/bench_ch48.err
 timeout -k 10 600 python3 bench.py --workload tgv3d-ipcs --cells 64 --steps 20 --warmup 3 > $O/${TAG}_bench_tgv3d_n64.json 2> $O/bench_tgv.err

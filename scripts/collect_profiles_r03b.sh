@@ -22,18 +22,18 @@ pmc() {  # name, bench args...
   rm -rf $O/p_${name}_FETCH_SIZE $O/p_${name}_WRITE_SIZE
   echo "pmc $name done"
 }
-trace bench_n512 --steps 20 --warmup 5 --no-cpu-baseline
+trace bench_n512 --full --steps 20 --warmup 5 --no-cpu-baseline
 trace bench_n512_timed_steps_only --steps 40 --warmup 10 --timed-only
-trace bench_n1024 --cells 1024 --steps 5 --warmup 2 --no-cpu-baseline --no-solver-classes
+trace bench_n1024 --full --cells 1024 --steps 5 --warmup 2 --no-cpu-baseline --no-solver-classes
 export NSFEM_JAC_LATTICE=0
 trace bench_n512_jacobian_launch_pair --steps 40 --warmup 10 --timed-only
 unset NSFEM_JAC_LATTICE
 pmc bench_n512 --steps 1 --warmup 1 --timed-only
 pmc bench_n1024 --cells 1024 --steps 1 --warmup 1 --timed-only
 cd $REPO
-timeout -k 10 900 python3 bench.py > $O/${TAG}_bench_default.json 2> $O/bench_default.err
-timeout -k 10 600 python3 bench.py --cells 1024 --steps 20 --warmup 3 --no-cpu-baseline --no-solver-classes > $O/${TAG}_bench_n1024.json 2> $O/bench_1024.err
-timeout -k 10 600 python3 bench.py --cells 336 --steps 50 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_n336.json 2> $O/bench_336.err
+timeout -k 10 900 python3 bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python3 bench.py --full --cells 1024 --steps 20 --warmup 3 --no-cpu-baseline --no-solver-classes > $O/${TAG}_bench_n1024.json 2> $O/bench_1024.err
+timeout -k 10 600 python3 bench.py --full --cells 336 --steps 50 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_n336.json 2> $O/bench_336.err
 timeout -k 10 600 python3 bench.py --workload tgv3d-ipcs --cells 64 --steps 20 --warmup 3 > $O/${TAG}_bench_tgv3d_n64.json 2> $O/bench_tgv.err
 timeout -k 10 600 python3 bench.py --workload channel3d-bdf --cells 48 --steps 10 --warmup 3 > $O/${TAG}_bench_channel3d_n48.json 2> $O/bench_ch48.err
 timeout -k 10 600 python3 bench.py --workload dfg-bdf --steps 20 --warmup 3 > $O/${TAG}_bench_dfg.json 2> $O/bench_dfg.err

@@ -52,12 +52,12 @@ PY
   rm -rf $REPO/gpurun_out/pmc_r04_sq_*
 fi
 if has default; then
-  timeout -k 10 1100 python3 bench.py > $O/r04_bench_default.json 2> $O/bench_default.err
+  timeout -k 10 1100 python3 bench.py --full > $O/r04_bench_default.json 2> $O/bench_default.err
   python3 scripts/show_bench.py $O/r04_bench_default.json
 fi
 if has configs; then
-  timeout -k 10 600 python3 bench.py --cells 1024 --steps 20 --warmup 3 --no-cpu-baseline --no-solver-classes --no-other-configs > $O/r04_bench_n1024.json 2> $O/bench_1024.err
-  timeout -k 10 600 python3 bench.py --cells 333 --steps 50 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r04_bench_n333.json 2> $O/bench_333.err
+  timeout -k 10 600 python3 bench.py --full --cells 1024 --steps 20 --warmup 3 --no-cpu-baseline --no-solver-classes --no-other-configs > $O/r04_bench_n1024.json 2> $O/bench_1024.err
+  timeout -k 10 600 python3 bench.py --full --cells 333 --steps 50 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r04_bench_n333.json 2> $O/bench_333.err
   timeout -k 10 600 python3 bench.py --workload tgv3d-ipcs --cells 64 --steps 20 --warmup 3 > $O/r04_bench_tgv3d_n64.json 2> $O/bench_tgv.err
   timeout -k 10 600 python3 bench.py --workload channel3d-bdf --cells 48 --steps 10 --warmup 3 > $O/r04_bench_channel3d_n48.json 2> $O/bench_ch48.err
   timeout -k 10 900 python3 bench.py --workload channel3d-bdf --cells 64 --steps 10 --warmup 3 > $O/r04_bench_channel3d_n64.json 2> $O/bench_ch64.err

@@ -735,7 +735,7 @@ def test_bench_through_rccl_single_rank():
     # (the projection step is the direct fast-diagonalisation solve in both runs; with the communicator its
     # contraction over y goes through ncclAllReduce: FastDiag::apply_strip)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "2", "--warmup",
-           "1", "--no-cpu-baseline", "--no-other-configs"]
+           "1", "--full", "--no-cpu-baseline", "--no-other-configs"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -770,6 +770,35 @@ def test_bench_dump_outputs_are_the_fields_of_the_last_timed_step(tmp_path):
     assert not np.array_equal(a["velocity"], c["velocity"])
 
 
+def test_plain_bench_run_times_the_steps_of_a_full_run_and_nothing_else(tmp_path):
+    """bench.py without --full: the headline line only (no validation rerun, kernel timings, solver-class pass or CPU
+    baseline), and its timed steps are those of a --full run with the same arguments: same iteration counts, same
+    dumped fields bit for bit"""
+    def run(name, extra):
+        d = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(d)] + extra
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        return (json.loads(res.stdout.strip().splitlines()[-1]),
+                {n: np.load(d / (n + ".npy")) for n in ("velocity", "pressure")})
+
+    plain, fields = run("plain", [])
+    full, fields_full = run("full", ["--full", "--no-cpu-baseline", "--no-other-configs"])
+    assert plain["metric"] == "dof_updates_per_sec" and plain["unit"] == "DoF-updates/s" and plain["dtype"] == "f64"
+    assert plain["higher_is_better"] is True and plain["steps"] == 3 and plain["warmup"] == 1
+    assert abs(plain["value"] - plain["config"]["n_dofs"] * 1e3 / plain["ms_per_step"]) < 1e-9 * plain["value"]
+    for key in ("validation", "ms_per_step_with_krylov_rtol_1e-12_exact_newton", "ms_per_step_through_solver_classes"):
+        assert key not in plain["config"] and key in full["config"], key
+    for key in ("cpu_baseline", "other_configs", "strong_n1", "assembly", "jacobian_spmv"):
+        assert key not in plain, key
+    assert plain["roofline"]["frac"] is None and full["roofline"]["frac"] > 0
+    for key in ("n_dofs", "newton_its_per_step", "bicgstab_its_per_step", "poisson_cg_its_per_step", "poisson_solver"):
+        assert plain["config"][key] == full["config"][key], key
+    for k in fields:
+        assert np.array_equal(fields[k], fields_full[k]), k
+
+
 def test_bench_writes_nothing_under_a_read_only_working_directory(tmp_path):
     """bench.py (including its pass through the solver classes, whose problem driver would write XDMF output) run from
     a read-only directory: it succeeds and leaves the directory empty"""
@@ -778,7 +807,7 @@ def test_bench_writes_nothing_under_a_read_only_working_directory(tmp_path):
     cwd.chmod(0o555)
     try:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "64", "--steps", "2", "--warmup", "1",
-               "--no-cpu-baseline", "--no-other-configs"]
+               "--full", "--no-cpu-baseline", "--no-other-configs"]
         res = subprocess.run(cmd, cwd=str(cwd), capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stderr[-2000:]
         line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -798,7 +827,7 @@ def test_bench_spawns_its_own_rank_processes_on_a_shared_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["NSFEM_SHARE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cells", "128", "--steps", "4", "--warmup", "2",
-           "--halo-mode", "exact", "--no-cpu-baseline"]
+           "--halo-mode", "exact", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.strip().splitlines() if l.startswith("{")]
@@ -863,7 +892,7 @@ def test_two_rccl_ranks_on_two_gpus_reproduce_the_single_gpu_run(scaling, overla
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2",
            "--cells", "128", "--steps", "4", "--warmup", "2", "--scaling", scaling, "--overlap", overlap,
-           "--halo-mode", "exact", "--no-cpu-baseline"]
+           "--halo-mode", "exact", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -872,7 +901,7 @@ def test_two_rccl_ranks_on_two_gpus_reproduce_the_single_gpu_run(scaling, overla
     assert line["config"]["comm_per_step_rank0"]["exchanges"] > 0
     if scaling == "strong":
         one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "128", "--steps", "4",
-                              "--warmup", "2", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                              "--warmup", "2", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
         assert one.returncode == 0, one.stderr[-3000:]
         ref = json.loads(one.stdout.strip().splitlines()[-1])
         for key in ("newton_its_per_step", "bicgstab_its_per_step", "poisson_cg_its_per_step"):
