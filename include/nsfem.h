@@ -538,8 +538,13 @@ int nsfem_profile_convection(nsfem_ctx* ctx, int enable, double* avg_ms, int64_t
  * 2  k_jac_lattice -- one launch (2D lattice meshes in rectangle_mesh numbering on one GPU, gradient-form viscosity,
  * no rotating frame; NSFEM_JAC_LATTICE=0 disables it).  out[1] = applications through k_jac_lattice so far,
  * out[2] = its algorithmic bytes per application (u, x read, y written: 48 B per P2 node; 3 B per node of
- * dictionary ids and masks; 48 B per cell of vertex coordinates), out[3] = 0. */
+ * dictionary ids and masks; 48 B per cell of vertex coordinates), out[3] = the k_jac_lattice variant (0 the
+ * round-4 kernel, NSFEM_JL_KERNEL=0; 1 one cell type per wave and node sums by gather; 2 the same with the physical
+ * gradients of a uniform lattice from tables). */
 int nsfem_jacobian_info(nsfem_ctx* ctx, int64_t out[4]);
+/* Test hook: *bad_cells = the number of cells whose basis gradients and weights, evaluated per cell as the element
+ * kernels do, differ in any bit from the tables k_jac_lattice reads on a uniform lattice; -1 when there are none. */
+int nsfem_jacobian_table_check(nsfem_ctx* ctx, int64_t* bad_cells);
 /* extreme eigenvalues of diag(M_e)^-1 M_e of the P2 element mass matrix (host arithmetic only) */
 int nsfem_p2_mass_bounds(int dim, double* lmin, double* lmax);
 int nsfem_synchronize(nsfem_ctx* ctx);

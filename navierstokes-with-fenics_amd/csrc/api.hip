@@ -3007,7 +3007,16 @@ extern "C" int nsfem_jacobian_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[0] = jacobian_path(ctx);
   out[1] = ctx->jac_lattice_launches;
   out[2] = jacobian_lattice_bytes(ctx->mesh);
-  out[3] = 0;
+  out[3] = jacobian_path(ctx) == 2 ? jacobian_lattice_variant(ctx->mesh) : -1;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_jacobian_table_check(nsfem_ctx* ctx, int64_t* bad_cells) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && bad_cells, "null argument");
+  ensure_L(ctx);
+  (void)jacobian_path(ctx);                          // (builds the cell lattice and the tables on first use)
+  *bad_cells = check_gradient_tables(ctx->stream, ctx->mesh);
   API_END(ctx)
 }
 

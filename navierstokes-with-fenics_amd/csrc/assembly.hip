@@ -457,10 +457,20 @@ void launch_cfl(hipStream_t s, const MeshDev& m, const double* u, double scale, 
 //   times v.  FORM as in k_conv_jac (0 standard, 1 rotational, 2 divergence, 3 skew-symmetric).
 // element vector of one cell: u (and the direction w) at the 6 nodes in registers; shared by the one-thread-per-cell
 // kernel below and the lattice kernel k_jac_lattice (same arithmetic, bit for bit)
-template <int FORM, int LIN>
-__device__ __forceinline__ void conv_cell_eval(const CellGeo& g, const double* ux, const double* uy,
-                                               const double* wx, const double* wy, double cc,
-                                               double* rx, double* ry) {
+// G supplies the physical gradients of the basis, G::grad(q, k, gx, gy), and the quadrature weight times |det J|,
+// G::wdet(q): from the cell's geometry (CellGrad: phys() on the spot) or from tables of a uniform lattice (TabGrad,
+// filled by phys() once per cell type: the same bits)
+struct CellGrad {
+  const CellGeo& g;
+  __device__ __forceinline__ void grad(int q, int k, double& gx, double& gy) const {
+    phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx, gy);
+  }
+  __device__ __forceinline__ double wdet(int q) const { return c_q.w[q] * g.adet; }
+};
+template <int FORM, int LIN, class G>
+__device__ __forceinline__ void conv_cell_eval_g(const G& gr, const double* ux, const double* uy,
+                                                 const double* wx, const double* wy, double cc,
+                                                 double* rx, double* ry) {
   // contraction inside statements only (not across them, which depends on the surrounding kernel): the two kernels
   // that inline this function produce the same element vectors bit for bit
 #pragma clang fp contract(on)
@@ -472,7 +482,7 @@ __device__ __forceinline__ void conv_cell_eval(const CellGeo& g, const double* u
     double vqx = 0.0, vqy = 0.0, h00 = 0.0, h01 = 0.0, h10 = 0.0, h11 = 0.0;
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx[k], gy[k]);
+      gr.grad(q, k, gx[k], gy[k]);
       const double ph = c_q.phi2[q][k];
       uqx += ph * ux[k];
       uqy += ph * uy[k];
@@ -489,7 +499,7 @@ __device__ __forceinline__ void conv_cell_eval(const CellGeo& g, const double* u
         h11 += gy[k] * wy[k];
       }
     }
-    const double w = c_q.w[q] * g.adet * cc;
+    const double w = gr.wdet(q) * cc;   // (c_q.w[q] * adet) * cc
     double fx, fy;                       // coefficient of phi_i
     if (LIN == 0) {
       const double ax = g00 * uqx + g01 * uqy, ay = g10 * uqx + g11 * uqy;       // (grad u) u
@@ -551,6 +561,12 @@ __device__ __forceinline__ void conv_cell_eval(const CellGeo& g, const double* u
       }
     }
   }
+}
+template <int FORM, int LIN>
+__device__ __forceinline__ void conv_cell_eval(const CellGeo& g, const double* ux, const double* uy,
+                                               const double* wx, const double* wy, double cc,
+                                               double* rx, double* ry) {
+  conv_cell_eval_g<FORM, LIN>(CellGrad{g}, ux, uy, wx, wy, cc, rx, ry);
 }
 
 template <int FORM, int LIN>
@@ -793,6 +809,20 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 // byte per node of dictionary ids and two of masks.
 // tile shapes: SX x SY squares per workgroup (powers of two; one cell per thread, 2 SX SY threads), of which the
 // workgroup owns the nodes of (SX - 1) x (SY - 1)
+// Variants (V): 0 the kernel above (NSFEM_JL_KERNEL=0, for A/B runs); 1 one cell type per wave (wave w holds the
+// cells of type w & 1: the type, its node template and rank template are wave-uniform) and phase 3 as a gather --
+// every cell stores its element vector to LDS once (over the dead staging buffers), and after ONE barrier the thread
+// of each owned node adds its <= 6 contributions in ascending cell order onto L x (+ g) kept in registers: the same
+// additions in the same order as the six rounds, bit for bit; 2 as 1 with the physical gradients and weights of the
+// two cell types read from tables (uniform lattices: phys() once per type in k_grad_tables, the same bits)
+struct TabGrad {
+  const double* __restrict__ t;   // [7][6][2] gradients, then [7] weights of one cell type (wave-uniform address)
+  __device__ __forceinline__ void grad(int q, int k, double& gx, double& gy) const {
+    gx = t[(q * 6 + k) * 2];
+    gy = t[(q * 6 + k) * 2 + 1];
+  }
+  __device__ __forceinline__ double wdet(int q) const { return t[84 + q]; }
+};
 
 struct JacLatArgs {
   int nx, ny, W, H, nc;
@@ -803,6 +833,11 @@ struct JacLatArgs {
   int lmax, lp, n_st;   // lp: table row stride (lmax rounded up to 4, zero padded)
   int dbg;              // knock-out build only (NSFEM_KNOCKOUTS): 1 no element kernel, 2 no L product, 4 no node sums
   double cc;
+  // node sums by gather (variants 1, 2): per parity class (i & 1) + 2 (j & 1) of a node, its six contributions in
+  // ascending cell order as element-vector offsets from the node's square ((j >> 1) SX + (i >> 1)) plus 2 SX, 16 bits
+  // each (two per int; classes with fewer than six cells point the rest at the plane of -0.0).  Indexed by constants
+  // only (selected per lane with v_cndmask)
+  int gl[4][3];
   // per cell type t and local node k, packed 6 x 5 bits (k-th field): the node's lattice offset from the square's corner
   // node as dj * 3 + di, and the cell's rank among the cells around that node (ascending cell number).  Plain
   // integers on purpose: an array indexed by the lane's cell type turns into VECTOR loads from the kernel-argument
@@ -810,7 +845,7 @@ struct JacLatArgs {
   int noff0, noff1, rank0, rank1;
 };
 
-template <int FORM, int LIN, int SX, int SY>
+template <int FORM, int LIN, int SX, int SY, int V>
 __global__ __launch_bounds__(2 * SX * SY) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __restrict__ u,
                    const double* __restrict__ x, const uint8_t* __restrict__ sid8,
@@ -819,7 +854,8 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
                    const double* __restrict__ gadd, double* __restrict__ y, const double* __restrict__ ugeo) {
   // LIN = 0: the momentum residual  y = L u + g + c_c conv(u)  (x is not read, no mask: the Dirichlet rows are
   // set by the caller afterwards); g joins the node's sum after the L product and before the element vectors,
-  // the order of the launches it replaces (product, axpby, k_conv_cell, k_res_gather)
+  // the order of the launches it replaces (product, axpby, k_conv_cell, k_res_gather).
+  // ugeo: V 0, 1 the two types' geometry [2][5] (uniform lattices; null: load_geo per cell), V 2 the gradient tables
   constexpr bool RES = LIN == 0;
   extern __shared__ __attribute__((aligned(16))) double sh_jl[];
   constexpr int NT = 2 * SX * SY;                                   // threads
@@ -828,10 +864,11 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   constexpr int LOGSX = SX == 32 ? 5 : SX == 16 ? 4 : 3;
   static_assert((1 << LOGSX) == SX, "SX: 8, 16 or 32");
   constexpr int NN = kJlNW * kJlNH;
-  double2* __restrict__ su = reinterpret_cast<double2*>(sh_jl);
+  // (V 1, 2: sa first, the element vectors of phase 3 then overlay su, sx and the tables: NN + 12 SX SY double2)
+  double2* __restrict__ su = reinterpret_cast<double2*>(sh_jl) + (V ? NN : 0);
   double2* __restrict__ sx = RES ? su : su + NN;
-  double2* __restrict__ sa = sx + NN;
-  double* __restrict__ tv = reinterpret_cast<double*>(sa + NN);       // [n_st * lp]
+  double2* __restrict__ sa = V ? reinterpret_cast<double2*>(sh_jl) : sx + NN;
+  double* __restrict__ tv = reinterpret_cast<double*>((V ? sx : sa) + NN);   // [n_st * lp]
   int* __restrict__ to = reinterpret_cast<int*>(tv + a.n_st * a.lp);
   int* __restrict__ tl = to + a.n_st * a.lp;
   // XCD x (workgroups b = x mod 8) walks a contiguous range of tiles: neighbouring tiles share their halo in L2
@@ -861,11 +898,20 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     }
   }
   // (this thread's cell, its two owned nodes)
-  const int ct = tid & 1, sxl = (tid >> 1) & (SX - 1), syl = tid >> (1 + LOGSX);
+  static_assert(NT % 128 == 0 && SX <= 64, "whole waves per cell type");
+  int ct, sxl, syl;
+  if constexpr (V == 0) {
+    ct = tid & 1; sxl = (tid >> 1) & (SX - 1); syl = tid >> (1 + LOGSX);
+  } else {
+    // wave w: cells of type w & 1 in the 64 / SX square rows from (w >> 1) 64 / SX on (readfirstlane: an SGPR)
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    ct = wv & 1; sxl = tid & (SX - 1); syl = ((wv >> 1) << (6 - LOGSX)) | ((tid & 63) >> LOGSX);
+  }
   const int sqx = (i0 >> 1) + sxl, sqy = (j0 >> 1) + syl;          // (i0, j0 even; >> is an arithmetic shift)
   const bool cell = sqx >= 0 && sqx < a.nx && sqy >= 0 && sqy < a.ny;
   CellGeo geo;
-  if (ugeo) {
+  if constexpr (V == 2) {
+  } else if (ugeo) {
     // uniform lattice: the two cell types' geometry through the scalar cache (wave-uniform addresses), picked per lane
     const double g0[5] = {ugeo[0], ugeo[1], ugeo[2], ugeo[3], ugeo[4]};
     const double g1[5] = {ugeo[5], ugeo[6], ugeo[7], ugeo[8], ugeo[9]};
@@ -937,6 +983,13 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       ax = fma(vb.y, x3.x, ax); ay = fma(vb.y, x3.y, ay);
     }
     if (RES) { ax += og[r].x; ay += og[r].y; }
+    if (V != 0 && !RES) {
+      // V 1, 2: the identity row's value now, while sx is staged (flag 1: identity row; flag 2: ghost row of a
+      // partitioned strip -> 0); the node sum does not enter it
+      const double2 xo = sx[base];
+      if (omask[r] & 0x00ff) ax = (omask[r] & 0x0002) ? 0.0 : xo.x;
+      if (omask[r] & 0xff00) ay = (omask[r] & 0x0200) ? 0.0 : xo.y;
+    }
     sa[base] = make_double2(ax, ay);
   }
   // ---- phase 2: the element vector of this thread's cell
@@ -965,10 +1018,51 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
 #pragma unroll
       for (int k = 0; k < 6; ++k) { rx[k] = ux[k]; ry[k] = uy[k]; }
     } else {
-      conv_cell_eval<FORM, LIN>(geo, ux, uy, wx, wy, a.cc, rx, ry);
+      if constexpr (V == 2) conv_cell_eval_g<FORM, LIN>(TabGrad{ugeo + kGradTab * ct}, ux, uy, wx, wy, a.cc, rx, ry);
+      else conv_cell_eval<FORM, LIN>(geo, ux, uy, wx, wy, a.cc, rx, ry);
     }
   }
   __syncthreads();
+  double2* __restrict__ y2 = reinterpret_cast<double2*>(y);
+  if constexpr (V != 0) {
+    // ---- phase 3 (gather): element vectors over the staging buffers, [t][k][SY][SX] (a wave stores contiguous runs),
+    // then a 13th plane of -0.0.  Squares outside the lattice store -0.0 as well: x + (-0.0) is x bit for bit (+0.0
+    // included), so every node adds six entries without a test and the sums keep the bits of the six rounds
+    constexpr int NSQ = SX * SY;
+    double2* __restrict__ se = reinterpret_cast<double2*>(sh_jl) + NN;
+    const double2 nz = make_double2(-0.0, -0.0);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) se[(ct * 6 + k) * NSQ + syl * SX + sxl] = cell ? make_double2(rx[k], ry[k]) : nz;
+    for (int t = tid; t < NSQ; t += NT) se[12 * NSQ + t] = nz;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < NOWN; ++r) {
+      if (obase[r] < 0) continue;
+      const int o = tid + r * NT;
+      const int oj = o / kJlOX, oi = o - oj * kJlOX;
+      const int li = oi + 2, lj = oj + 2;                          // LDS tile position (i0, j0 even: same parity)
+      int pe[3];
+#pragma unroll
+      for (int h = 0; h < 3; ++h) pe[h] = (lj & 1) ? ((li & 1) ? a.gl[3][h] : a.gl[2][h]) : ((li & 1) ? a.gl[1][h] : a.gl[0][h]);
+      const double2* __restrict__ sq = se + ((lj >> 1) * SX + (li >> 1) - 2 * SX);
+      const double2 a0 = sa[obase[r]];
+      double vx_ = a0.x, vy_ = a0.y;
+#pragma unroll
+      for (int e = 0; e < 6; ++e) {
+        if NSFEM_KO(a.dbg & 4) break;
+        const double2 v = sq[(pe[e >> 1] >> (16 * (e & 1))) & 0xffff];
+        vx_ += v.x;
+        vy_ += v.y;
+      }
+      double2 v = make_double2(vx_, vy_);
+      if (!RES) {
+        if (omask[r] & 0x00ff) v.x = a0.x;
+        if (omask[r] & 0xff00) v.y = a0.y;
+      }
+      if (!NSFEM_KO(a.dbg & 32) || v.x == 1.2345) y2[onode[r]] = v;
+    }
+    return;
+  }
   // ---- phase 3: node sums in ascending cell order
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
@@ -985,7 +1079,6 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     __syncthreads();
   }
   // ---- phase 4
-  double2* __restrict__ y2 = reinterpret_cast<double2*>(y);
 #pragma unroll
   for (int r = 0; r < NOWN; ++r) {
     if (obase[r] < 0) continue;
@@ -1059,6 +1152,41 @@ __global__ __launch_bounds__(256) void k_geo_uniform(int nc, const double* __res
     o[0] = g.ji00; o[1] = g.ji01; o[2] = g.ji10; o[3] = g.ji11; o[4] = g.adet;
   }
 }
+// the physical gradients and weights of the two cell types of a uniform lattice: phys() and the weight product of
+// conv_cell_eval on the geometry k_geo_uniform took from the cells themselves (same function, same bits).  One thread
+// per (type, q, k)
+__global__ __launch_bounds__(128) void k_grad_tables(const double* __restrict__ ugeo, double* __restrict__ tab) {
+  const int t = threadIdx.x;
+  if (t >= 2 * 7 * 6) return;
+  const int ty = t / 42, q = (t / 6) % 7, k = t % 6;
+  const double* r = ugeo + 5 * ty;
+  CellGeo g;
+  g.ji00 = r[0]; g.ji01 = r[1]; g.ji10 = r[2]; g.ji11 = r[3]; g.adet = r[4];
+  const CellGrad cg{g};
+  double* o = tab + kGradTab * ty;
+  cg.grad(q, k, o[(q * 6 + k) * 2], o[(q * 6 + k) * 2 + 1]);
+  if (k == 0) o[84 + q] = cg.wdet(q);
+}
+// test hook: count the cells whose per-cell phys() gradients or weights differ from the tables in any bit
+__global__ __launch_bounds__(256) void k_grad_tables_check(int nc, const double* __restrict__ vx,
+                                                           const double* __restrict__ tab, int* __restrict__ bad) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo g = load_geo(vx, nc, c);
+  const CellGrad cg{g};
+  const double* o = tab + kGradTab * (c & 1);
+  bool same = true;
+  for (int q = 0; q < 7; ++q) {
+    for (int k = 0; k < 6; ++k) {
+      double gx, gy;
+      cg.grad(q, k, gx, gy);
+      same = same && __double_as_longlong(gx) == __double_as_longlong(o[(q * 6 + k) * 2]) &&
+             __double_as_longlong(gy) == __double_as_longlong(o[(q * 6 + k) * 2 + 1]);
+    }
+    same = same && __double_as_longlong(cg.wdet(q)) == __double_as_longlong(o[84 + q]);
+  }
+  if (!same) atomicAdd(bad, 1);
+}
 void check_uniform_geometry(hipStream_t s, MeshDev& m) {
   CellLattice& cl = m.cl;
   cl.geo_uniform = false;
@@ -1074,6 +1202,26 @@ void check_uniform_geometry(hipStream_t s, MeshDev& m) {
   NSFEM_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
   cl.geo_uniform = h == 0;
+  if (cl.geo_uniform) {
+    cl.gtab.alloc(2 * kGradTab);
+    cl.gtab.zero(s);
+    hipLaunchKernelGGL(k_grad_tables, dim3(1), dim3(128), 0, s, (const double*)cl.ugeo.p, cl.gtab.p);
+    NSFEM_HIP(hipGetLastError());
+  }
+}
+int64_t check_gradient_tables(hipStream_t s, const MeshDev& m) {
+  const CellLattice& cl = m.cl;
+  if (!cl.geo_uniform || !cl.gtab.p) return -1;
+  DevBuf<int> bad;
+  bad.alloc(1);
+  bad.zero(s);
+  hipLaunchKernelGGL(k_grad_tables_check, dim3((m.n_cells + 255) / 256), dim3(256), 0, s, m.n_cells,
+                     (const double*)m.vx.p, (const double*)cl.gtab.p, bad.p);
+  NSFEM_HIP(hipGetLastError());
+  int h = -1;
+  NSFEM_HIP(hipMemcpyAsync(&h, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  return h;
 }
 
 static bool g_jac_lattice_on = true;
@@ -1085,12 +1233,15 @@ static int g_jac_lattice_dbg = 0;
 static int g_jac_lattice_tile = 0;
 static bool g_partitioned_lattice = true;
 static bool g_jac_uniform_geo = true;                 // NSFEM_JL_UNIFORM_GEO=0: always load the cell coordinates
+static bool g_jac_gather = true;                      // NSFEM_JL_KERNEL=0: the round-4 kernel (variant 0), for A/B runs
 bool partitioned_lattice_kernels() { return g_partitioned_lattice; }
 void refresh_assembly_switches() {
   const char* e = std::getenv("NSFEM_JAC_LATTICE");
   g_jac_lattice_on = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_JL_UNIFORM_GEO");
   g_jac_uniform_geo = e ? std::atoi(e) != 0 : true;
+  e = std::getenv("NSFEM_JL_KERNEL");
+  g_jac_gather = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_PARTITIONED_LATTICE");       // 0: partitioned strips keep the one-step / multi-launch kernels
   g_partitioned_lattice = e ? std::atoi(e) != 0 : true;
 #if NSFEM_KNOCKOUTS
@@ -1109,8 +1260,10 @@ static size_t jac_lattice_lds(const StencilDict& d) {
   const size_t lp = (size_t)((d.lmax + 3) & ~3);
   int sx, sy;
   jac_lattice_shape(sx, sy);
-  return (size_t)3 * (2 * sx + 1) * (2 * sy + 1) * sizeof(double2) + (size_t)d.n_stencils * lp * 12 +
-         (size_t)d.n_stencils * 4 + 16;
+  const size_t nn = (size_t)(2 * sx + 1) * (2 * sy + 1);
+  const size_t staged = 3 * nn * sizeof(double2) + (size_t)d.n_stencils * lp * 12 + (size_t)d.n_stencils * 4 + 16;
+  // variants 1, 2: sa, then the element vectors of the gather over su, sx and the tables
+  return g_jac_gather ? std::max(staged, (nn + (size_t)13 * sx * sy) * sizeof(double2)) : staged;
 }
 
 bool jacobian_lattice_available(const MeshDev& m, const BlockMat& L) {
@@ -1119,6 +1272,10 @@ bool jacobian_lattice_available(const MeshDev& m, const BlockMat& L) {
   const StencilDict& d = *L.dict;
   return d.lat_w == cl.W && d.lat_h == cl.H && d.lat_r <= 2 && !d.rect && L.br == 1 && L.bc == 1 &&
          d.n_stencils <= 64 && jac_lattice_lds(d) <= (size_t)96 * 1024;
+}
+int jacobian_lattice_variant(const MeshDev& m) {
+  if (!g_jac_gather) return 0;
+  return g_jac_uniform_geo && m.cl.geo_uniform && m.cl.gtab.p ? 2 : 1;
 }
 int64_t jacobian_lattice_bytes(const MeshDev& m) {
   // (uniform lattices: the cell geometry comes from 10 scalar loads, no coordinate stream)
@@ -1183,25 +1340,49 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
       pk[1][t] |= cl.rank[t][k] << (5 * k);
     }
   a.noff0 = pk[0][0]; a.noff1 = pk[0][1]; a.rank0 = pk[1][0]; a.rank1 = pk[1][1];
+  // gather lists per node parity class: the (t, k) of that class in rank order, as offsets into the element vectors
+  // [t][k][sy][sx] from the node's square: (j - dj) >> 1 = (j >> 1) - (dj >> 1) when j and dj have one parity
+  for (int c = 0; c < 4; ++c) {
+    int ent[6] = {-1, -1, -1, -1, -1, -1};
+    for (int t = 0; t < 2; ++t)
+      for (int k = 0; k < 6; ++k)
+        if ((cl.di[t][k] & 1) == (c & 1) && (cl.dj[t][k] & 1) == (c >> 1)) {
+          NSFEM_REQUIRE(ent[cl.rank[t][k]] < 0, "k_jac_lattice: two cells of one rank around a node");
+          ent[cl.rank[t][k]] = (6 * t + k) * sx * sy - (cl.dj[t][k] >> 1) * sx - (cl.di[t][k] >> 1);
+        }
+    int n = 0, packed[6];
+    for (int r = 0; r < 6; ++r)
+      if (ent[r] >= 0) packed[n++] = ent[r] + 2 * sx;
+    for (; n < 6; ++n) packed[n] = 12 * sx * sy + 2 * sx;     // the plane of -0.0
+    for (int h = 0; h < 3; ++h) a.gl[c][h] = packed[2 * h] | (packed[2 * h + 1] << 16);
+  }
+  const int var = jacobian_lattice_variant(m);
   const size_t lds = jac_lattice_lds(d);
   const int grid = ((a.ntiles + 7) / 8) * 8;
-#define NSFEM_JL_T(F, LIN, SX, SY)                                                                          \
+#define NSFEM_JL_V(F, LIN, SX, SY, V)                                                                       \
   do {                                                                                                      \
     static bool attr = false;                                                                               \
     if (!attr) {                                                                                            \
-      NSFEM_HIP(hipFuncSetAttribute((const void*)k_jac_lattice<F, LIN, SX, SY>,                             \
+      NSFEM_HIP(hipFuncSetAttribute((const void*)k_jac_lattice<F, LIN, SX, SY, V>,                          \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                \
       attr = true;                                                                                          \
       if (std::getenv("NSFEM_JL_OCC")) {                                                                    \
         int nb = 0;                                                                                         \
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_jac_lattice<F, LIN, SX, SY>, \
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_jac_lattice<F, LIN, SX, SY, V>, \
                                                            2 * SX * SY, lds);                               \
         std::fprintf(stderr, "k_jac_lattice<%d x %d>: %d workgroups per CU at %zu B of LDS\n", SX, SY, nb, lds); \
       }                                                                                                     \
     }                                                                                                       \
-    hipLaunchKernelGGL((k_jac_lattice<F, LIN, SX, SY>), dim3(grid), dim3(2 * SX * SY), lds, s, a, m.vx.p, u, x, \
-                       d.sid8.p, mask, d.len.p, d.pack.p, L.dict_vals.p, gadd, y,                           \
-                       (const double*)(g_jac_uniform_geo && cl.geo_uniform ? cl.ugeo.p : nullptr));         \
+    hipLaunchKernelGGL((k_jac_lattice<F, LIN, SX, SY, V>), dim3(grid), dim3(2 * SX * SY), lds, s, a, m.vx.p, u, \
+                       x, d.sid8.p, mask, d.len.p, d.pack.p, L.dict_vals.p, gadd, y,                        \
+                       (const double*)(V == 2 ? cl.gtab.p                                                   \
+                                              : g_jac_uniform_geo && cl.geo_uniform ? cl.ugeo.p : nullptr)); \
+  } while (0)
+#define NSFEM_JL_T(F, LIN, SX, SY)                                                                          \
+  do {                                                                                                      \
+    if (var == 2) NSFEM_JL_V(F, LIN, SX, SY, 2);                                                            \
+    else if (var == 1) NSFEM_JL_V(F, LIN, SX, SY, 1);                                                       \
+    else NSFEM_JL_V(F, LIN, SX, SY, 0);                                                                     \
   } while (0)
 #define NSFEM_JL(F, LIN)                                                                                    \
   do {                                                                                                      \
@@ -1222,6 +1403,7 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
   if (lin == 0) { NSFEM_JL_F(0) } else if (lin == 2) { NSFEM_JL_F(2) } else { NSFEM_JL_F(1) }
 #undef NSFEM_JL_F
 #undef NSFEM_JL_T
+#undef NSFEM_JL_V
 #undef NSFEM_JL
   NSFEM_HIP(hipGetLastError());
   return true;

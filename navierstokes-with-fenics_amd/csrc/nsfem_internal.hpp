@@ -327,10 +327,19 @@ struct CellLattice {
   // geometry from 10 scalar loads instead of six strided coordinate loads per cell (48 B per cell of the launch)
   bool geo_uniform = false;
   DevBuf<double> ugeo;                      // [2][5]
+  // and, from them, the physical basis gradients and weights of both types (phys() once per type, the same bits as
+  // per cell): [type][kGradTab] = gx, gy [7][6][2], then c_q.w[q] |det| [7]
+  DevBuf<double> gtab;
 };
+constexpr int kGradTab = 96;              // doubles per cell type (84 gradients + 7 weights, padded)
 bool build_cell_lattice(const int32_t* p2map /* [cell][6] */, int nc, int W, int H, CellLattice& cl);
 struct MeshDev;
-void check_uniform_geometry(hipStream_t s, MeshDev& m);   // fills m.cl.geo_uniform / ugeo (after build_cell_lattice)
+void check_uniform_geometry(hipStream_t s, MeshDev& m);   // fills m.cl.geo_uniform / ugeo / gtab (after build_cell_lattice)
+// cells whose phys() gradients or weights differ from m.cl.gtab (-1: no tables); test hook
+int64_t check_gradient_tables(hipStream_t s, const MeshDev& m);
+// k_jac_lattice variant the next launch takes: 0 the round-4 kernel (NSFEM_JL_KERNEL=0), 1 one cell type per wave and
+// node sums by gather, 2 the same with gradient tables (uniform lattices)
+int jacobian_lattice_variant(const MeshDev& m);
 
 struct MeshDev {
   int dim = 2;              // 2: triangles (6 + 3 nodes per cell), 3: tetrahedra (10 + 4)
