@@ -68,7 +68,9 @@ enum nsfem_slot {
   NSFEM_BODY_FORCE = 6, /* nodal P2 interpolant of f             [dim*n_p2]   */
   NSFEM_TRACTION = 7,   /* assembled boundary traction vector    [dim*n_p2]   */
   NSFEM_P2_OLD = 8,  /* BDF: pressure at t_{n-1} (keeps _solutions[2] whole)  */
-  NSFEM_N_SLOTS = 9
+  NSFEM_CONV_N1 = 9, /* IMEX: c_c N(u^n), written by nsfem_step_imex    [dim*n_p2] */
+  NSFEM_CONV_N2 = 10, /* IMEX: c_c N(u^(n-1)); nsfem_advance moves N1 here       */
+  NSFEM_N_SLOTS = 11
 };
 
 /* fields for Dirichlet sets */
@@ -176,6 +178,10 @@ int nsfem_version(void);
 int nsfem_set_coeffs(nsfem_ctx* ctx, const double c[6]);
 /* replaces _update_time_stepping_coefficients (ns_ipcs_solver.py:210-227) */
 int nsfem_set_bdf(nsfem_ctx* ctx, const double alpha[3], double k);
+/* coefficients of the IMEX pressure-correction step (imex_time_stepping.py: alpha, beta, gamma) and the step size k.
+ * The system matrix alpha0/k M + gamma0 c_v K and the velocity multigrid hierarchy are rebuilt only when alpha0/k or
+ * gamma0 changed.  nsfem_set_bdf switches back to the fully implicit schemes (gamma = (1, 0, 0)). */
+int nsfem_set_imex(nsfem_ctx* ctx, const double alpha[3], const double beta[2], const double gamma[3], double k);
 /* replaces DirichletBC lists (ns_solver_base.py:546-660); re-callable each step
  * (time dependent values, _set_time ns_solver_base.py:1033-1104).  dofs index the
  * velocity (interleaved) or pressure vector; later entries win on duplicates. */
@@ -405,6 +411,25 @@ int nsfem_comm_stats(nsfem_ctx* ctx, int64_t out[4], int reset);
 int nsfem_default_step_opts(nsfem_step_opts* opts);
 int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info);
 int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info);
+/* One IMEX pressure-correction step (coefficients: nsfem_set_imex).  Diffusion step: ONE CG solve of
+ *   (alpha0/k M + gamma0 c_v K) u* = -[ M (alpha1 u1 + alpha2 u2)/k + c_v K (gamma1 u1 + gamma2 u2)
+ *                                       + c_c (beta0 N(u1) + beta1 N(u2)) - c_p D^T p_old - c_b M f + traction ]
+ * with Dirichlet rows u*_i = g_i (opts->momentum: precond 0 Jacobi, 1 the velocity V-cycle; traction-form viscosity:
+ * K is the traction-form stiffness); projection and velocity correction as nsfem_step_ipcs.  c_c N(u1) is kept in
+ * NSFEM_CONV_N1, nsfem_advance moves it to NSFEM_CONV_N2 where the next step reads it as c_c N(u2) (recomputed only
+ * after NSFEM_U2 / NSFEM_CONV_N2 were set by hand or the convective form / coefficient changed).
+ * info->newton_iterations = 0, krylov_iterations_momentum = the CG count.  Rotating frames and partitioned meshes:
+ * NSFEM_ERR_ARG.  3D meshes, inexact dictionaries, traction-form viscosity: the generic right-hand-side path. */
+int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info);
+/* How the right-hand side of the last nsfem_step_imex was formed: out[0] = 1 generic path (products, element kernel,
+ * node gather, vector updates), 2 one launch of k_jac_lattice's right-hand-side mode (2D lattice meshes whose stencil
+ * dictionaries equal the assembled matrices bit for bit), 0 no step yet; out[1] = one-launch right-hand sides so far,
+ * out[2] = generic ones, out[3] = rebuilds of the system matrix.
+ * nsfem_imex_rhs (test hook): forms the right-hand side for the current state and coefficients WITHOUT the Dirichlet
+ * rows and without touching NSFEM_CONV_N1 / N2: path 1 generic, 2 one-launch (NSFEM_ERR_ARG where it does not apply);
+ * rhs and conv_n1 (c_c N(u1), may be null) are host arrays of dim * n_p2 doubles. */
+int nsfem_imex_info(nsfem_ctx* ctx, int64_t out[4]);
+int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, double* rhs, double* conv_n1);
 /* replaces _advance_solution (ns_solver_base.py:1012-1016, ns_ipcs_solver.py:35-43) */
 int nsfem_advance(nsfem_ctx* ctx, int scheme /* 0 ipcs, 1 bdf */);
 /* L2 projection solve  M x = b  (no Dirichlet rows) on the velocity (field 0, both

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libnsfem_hip.so")
 
 # ---- enums (mirror include/nsfem.h) ------------------------------------------
 OK, ERR_ARG, ERR_HIP, ERR_BREAKDOWN, ERR_NOT_CONVERGED, ERR_COMM = 0, -1, -2, -3, -4, -5
-U0, U1, U2, USTAR, P, P_OLD, BODY_FORCE, TRACTION, P2_OLD = range(9)
+U0, U1, U2, USTAR, P, P_OLD, BODY_FORCE, TRACTION, P2_OLD, CONV_N1, CONV_N2 = range(11)
 VELOCITY, PRESSURE, PRESSURE_PRECOND = 0, 1, 2
 (OP_MASS_P2, OP_STIFF_P2, OP_STIFF_P1, OP_MASS_P1, OP_DIV, OP_GRAD, OP_DIVT,
  OP_MOMENTUM_JAC, OP_VISCOUS_EXTRA, OP_MOMENTUM_JAC_MF, OP_MOMENTUM_SMOOTHER,
@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_mg_apply", "nsfem_mg_info", "nsfem_poisson_set_fast_diag", "nsfem_poisson_set_fast_diag_rows",
     "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_set_fast_diag_3d_planes", "nsfem_poisson_fast_diag_3d_info",
     "nsfem_operator_diagonal",
+    "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
 )
 
 
@@ -161,6 +162,10 @@ def load_library(path=None):
         "nsfem_version": (C.c_int, []),
         "nsfem_set_coeffs": (C.c_int, [vp, pd]),
         "nsfem_set_bdf": (C.c_int, [vp, pd, dbl]),
+        "nsfem_set_imex": (C.c_int, [vp, pd, pd, pd, dbl]),
+        "nsfem_step_imex": (C.c_int, [vp, C.POINTER(StepOpts), C.POINTER(StepInfo)]),
+        "nsfem_imex_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_imex_rhs": (C.c_int, [vp, C.c_int, C.c_int, pd, pd]),
         "nsfem_set_dirichlet": (C.c_int, [vp, C.c_int, i32, pi, pd]),
         "nsfem_set_viscous_form": (C.c_int, [vp, C.c_int]),
         "nsfem_set_convective_form": (C.c_int, [vp, C.c_int, C.c_int]),
@@ -324,6 +329,14 @@ class NsfemContext:
         assert a.shape == (3,)
         self._check(self._lib.nsfem_set_bdf(self._h, _dp(a), float(k)))
 
+    def set_imex(self, alpha, beta, gamma, k):
+        """coefficients of IMEXTimeStepping (alpha, beta, gamma) and the step size for step_imex"""
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        b = np.ascontiguousarray(beta, dtype=np.float64)
+        g = np.ascontiguousarray(gamma, dtype=np.float64)
+        assert a.shape == (3,) and b.shape == (2,) and g.shape == (3,)
+        self._check(self._lib.nsfem_set_imex(self._h, _dp(a), _dp(b), _dp(g), float(k)))
+
     def set_dirichlet(self, field, dofs, vals):
         d = np.ascontiguousarray(dofs, dtype=np.int32)
         v = np.ascontiguousarray(vals, dtype=np.float64)
@@ -383,6 +396,31 @@ class NsfemContext:
         info = StepInfo()
         self._check(self._lib.nsfem_step_ipcs(self._h, C.byref(o), C.byref(info)))
         return info
+
+    def step_imex(self, opts=None):
+        """one IMEX pressure-correction step (set_imex): a CG solve for the diffusion step, then projection and
+        velocity correction as step_ipcs"""
+        o = opts or self.default_step_opts()
+        info = StepInfo()
+        self._check(self._lib.nsfem_step_imex(self._h, C.byref(o), C.byref(info)))
+        return info
+
+    def imex_info(self):
+        """dict(path = None | "generic" | "lattice-kernel" of the last step_imex's right-hand side, lattice_rhs,
+        generic_rhs, matrix_builds)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_imex_info(self._h, out))
+        return dict(path=(None, "generic", "lattice-kernel")[int(out[0])], lattice_rhs=int(out[1]),
+                    generic_rhs=int(out[2]), matrix_builds=int(out[3]))
+
+    def imex_rhs(self, path, convective_form=0):
+        """test hook: (right-hand side of the IMEX diffusion step without its Dirichlet rows, c_c N(u1)) formed by
+        the "generic" or the "lattice-kernel" path from the current state; the stored vectors stay untouched"""
+        n = self.state_size(U0)
+        rhs, n1 = np.empty(n), np.empty(n)
+        self._check(self._lib.nsfem_imex_rhs(self._h, {"generic": 1, "lattice-kernel": 2}[path], int(convective_form),
+                                             _dp(rhs), _dp(n1)))
+        return rhs, n1
 
     def step_bdf(self, opts=None):
         o = opts or self.default_step_opts()

@@ -37,7 +37,7 @@ static inline int64_t npre(const nsfem_ctx* c) { return (int64_t)c->mesh.n_p1; }
 static int64_t slot_size(const nsfem_ctx* c, int slot) {
   switch (slot) {
     case NSFEM_U0: case NSFEM_U1: case NSFEM_U2: case NSFEM_USTAR:
-    case NSFEM_BODY_FORCE: case NSFEM_TRACTION:
+    case NSFEM_BODY_FORCE: case NSFEM_TRACTION: case NSFEM_CONV_N1: case NSFEM_CONV_N2:
       return nvel(c);
     case NSFEM_P: case NSFEM_P_OLD: case NSFEM_P2_OLD:
       return npre(c);
@@ -333,8 +333,29 @@ extern "C" int nsfem_set_coeffs(nsfem_ctx* ctx, const double c[6]) {
   NSFEM_REQUIRE(std::isfinite(c[1]) && std::isfinite(c[2]), "pressure and viscous coefficients are required");
   for (int i = 0; i < 6; ++i) ctx->coef[i] = c[i];
   ctx->L_dirty = true;
+  ctx->imex_ops_dirty = true;
   ctx->graph_epoch++;                  // (coefficients are baked into captured kernel arguments)
   API_END(ctx)
+}
+
+// the velocity V-cycle as a symmetric operator (CG, IMEX diffusion step) or as nsfem_mg_finalize set it up
+// (non-symmetric, BiCGStab); the hierarchy's smoother data and fused launches are planned again at the next refresh
+static void set_velocity_cycle_symmetric(nsfem_ctx* c, bool symmetric) {
+  if (!c->mg_built || c->mg_v_symmetric == symmetric) return;
+  Multigrid& mg = c->mg_v;
+  if (symmetric) {
+    c->mg_v_pre_saved = mg.pre_degree;
+    c->mg_v_degree_saved = mg.degree;
+    if (mg.pre_degree >= 0) {
+      mg.degree = std::max(1, mg.pre_degree == 0 ? mg.degree - 1 : mg.degree);
+      mg.pre_degree = -1;
+    }
+  } else {
+    mg.pre_degree = c->mg_v_pre_saved;
+    mg.degree = c->mg_v_degree_saved;
+  }
+  c->mg_v_symmetric = symmetric;
+  c->mg_v_dirty = true;
 }
 
 extern "C" int nsfem_set_bdf(nsfem_ctx* ctx, const double alpha[3], double k) {
@@ -344,8 +365,42 @@ extern "C" int nsfem_set_bdf(nsfem_ctx* ctx, const double alpha[3], double k) {
   NSFEM_REQUIRE(k > 0.0 && std::isfinite(k) && std::isfinite(alpha[0]), "bad BDF coefficients");
   if (alpha[0] != ctx->alpha[0] || k != ctx->k) ctx->L_dirty = true;
   if (alpha[0] != ctx->alpha[0] || alpha[1] != ctx->alpha[1] || alpha[2] != ctx->alpha[2] || k != ctx->k) ctx->graph_epoch++;
+  if (ctx->imex_active) {              // back to the fully implicit schemes: L = alpha0/k M + c_v K
+    ctx->imex_active = false;
+    ctx->L_dirty = true;
+    ctx->graph_epoch++;
+    set_velocity_cycle_symmetric(ctx, false);
+  }
   for (int i = 0; i < 3; ++i) ctx->alpha[i] = alpha[i];
   ctx->k = k;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_set_imex(nsfem_ctx* ctx, const double alpha[3], const double beta[2], const double gamma[3],
+                              double k) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && alpha && beta && gamma, "null argument");
+  bool finite = k > 0.0 && std::isfinite(k) && std::isfinite(beta[0]) && std::isfinite(beta[1]);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(alpha[i]) && std::isfinite(gamma[i]);
+  NSFEM_REQUIRE(finite, "bad IMEX coefficients");
+  // (the system matrix must be symmetric positive definite: CG solves the diffusion step)
+  NSFEM_REQUIRE(alpha[0] > 0.0 && gamma[0] >= 0.0, "IMEX scheme needs alpha0 > 0 and gamma0 >= 0");
+  const bool was = ctx->imex_active;
+  // the system matrix alpha0/k M + gamma0 c_v K (and the hierarchy built on it) depends on these two numbers only
+  if (!was || alpha[0] / k != ctx->alpha[0] / ctx->k || gamma[0] != ctx->imex_gamma[0]) ctx->L_dirty = true;
+  bool changed = !was || k != ctx->k || beta[0] != ctx->imex_beta[0] || beta[1] != ctx->imex_beta[1];
+  bool ops = !was || alpha[1] / k != ctx->alpha[1] / ctx->k || alpha[2] / k != ctx->alpha[2] / ctx->k;
+  for (int i = 0; i < 3; ++i) {
+    changed = changed || alpha[i] != ctx->alpha[i] || gamma[i] != ctx->imex_gamma[i];
+    if (i > 0) ops = ops || gamma[i] != ctx->imex_gamma[i];
+  }
+  if (ops) ctx->imex_ops_dirty = true;
+  if (changed) ctx->graph_epoch++;
+  for (int i = 0; i < 3; ++i) { ctx->alpha[i] = alpha[i]; ctx->imex_gamma[i] = gamma[i]; }
+  ctx->imex_beta[0] = beta[0];
+  ctx->imex_beta[1] = beta[1];
+  ctx->k = k;
+  ctx->imex_active = true;
   API_END(ctx)
 }
 
@@ -465,6 +520,10 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   if (slot == NSFEM_BODY_FORCE) ctx->have_body_force = true;
   if (slot == NSFEM_TRACTION) ctx->have_traction = true;
   if (slot == NSFEM_P || slot == NSFEM_P_OLD || slot == NSFEM_P2_OLD) ctx->pressure_history = 0;
+  // IMEX: the stored convection vectors follow the velocity levels they were evaluated at
+  if (slot == NSFEM_U1 || slot == NSFEM_CONV_N1) ctx->conv_n1_fresh = false;
+  if (slot == NSFEM_U2) ctx->conv_n2_valid = false;
+  if (slot == NSFEM_CONV_N2) { ctx->conv_n2_valid = true; ctx->conv_n_form = -2; }   // (the caller vouches for it)
   API_END(ctx)
 }
 
@@ -518,7 +577,9 @@ static void select_velocity_cycle_depth(nsfem_ctx* c, double ap, double b) {
 static void ensure_L(nsfem_ctx* c) {
   if (!c->L_dirty) return;
   // L = alpha0/k M + c_viscous K   (scalar P2; acts on all velocity components)
-  const double a = c->alpha[0] / c->k, b = c->coef[2];
+  // (IMEX pressure correction: alpha0/k M + gamma0 c_v K, the system matrix of its diffusion step)
+  const double a = c->alpha[0] / c->k, b = c->imex_active ? c->imex_gamma[0] * c->coef[2] : c->coef[2];
+  if (c->imex_active) ++c->imex_matrix_builds;
   launch_scale_combine(c->stream, c->p22.nnz, a, c->M2.vals.p, b, c->K2.vals.p, c->L.vals.p);
   if (!c->dict22_tried) {
     // stencil dictionary of the scalar P2 operators (lattice meshes only): shared by every
@@ -1839,6 +1900,7 @@ extern "C" int nsfem_mg_finalize(nsfem_ctx* ctx, const nsfem_mg_opts* o) {
     // cycle; measured 6 % faster steps than V(2,2) at equal iteration counts)
     mg.pre_degree = 0;
     mg.degree = degree + 1;
+    ctx->mg_v_symmetric = false;
     mg.identity_rows = true;     // z = r on Dirichlet rows, written by the last smoothing step
     if (const char* e = std::getenv("NSFEM_MGV_PRE")) mg.pre_degree = std::atoi(e);
     if (const char* e = std::getenv("NSFEM_MGV_POST")) mg.degree = std::atoi(e);
@@ -2022,6 +2084,7 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   NSFEM_REQUIRE(opts->newton_max_iter > 0 && opts->newton_max_iter < NSFEM_MAX_NEWTON,
                 "newton_max_iter out of range");
   NSFEM_REQUIRE(ctx->alpha[0] != 0.0, "the pressure-correction scheme needs alpha0 != 0");
+  NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
   if (ctx->conv_form != opts->convective_form || ctx->picard) ctx->graph_epoch++;
   ctx->conv_form = opts->convective_form;
   ctx->picard = false;
@@ -2088,6 +2151,235 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     if (rc != NSFEM_OK) throw Error(rc, "CG failed in the velocity correction step");
   }
   ctx->assembled_system = -1;
+  API_END(ctx)
+}
+
+
+// ---------------------------------------------------------------- IMEX pressure correction
+// the operators of the old levels in the right-hand side: L_i = alpha_i/k M + gamma_i c_v K, i = 1, 2 (built as
+// ensure_L builds L; they share its pattern and stencil dictionary)
+static void ensure_imex_ops(nsfem_ctx* c) {
+  ensure_L(c);
+  hipStream_t s = c->stream;
+  if (!c->L1.vals.p) {
+    c->L1.init(&c->p22, 1, 1, s);
+    c->L2.init(&c->p22, 1, 1, s);
+    c->imex_ops_dirty = true;
+  }
+  if (c->L1.dict != c->L.dict) {
+    c->L1.dict = c->L2.dict = c->L.dict;
+    c->imex_ops_dirty = true;
+  }
+  if (!c->imex_ops_dirty) return;
+  const double cv = c->coef[2];
+  launch_scale_combine(s, c->p22.nnz, c->alpha[1] / c->k, c->M2.vals.p, c->imex_gamma[1] * cv, c->K2.vals.p, c->L1.vals.p);
+  launch_scale_combine(s, c->p22.nnz, c->alpha[2] / c->k, c->M2.vals.p, c->imex_gamma[2] * cv, c->K2.vals.p, c->L2.vals.p);
+  c->L1.sell_update(s);
+  c->L2.sell_update(s);
+  c->imex_ops_dirty = false;
+}
+
+// step-constant part of the right-hand side:  g = - c_p D^T p_old - c_b M f + traction  (momentum_begin_step's signs)
+static void imex_begin_step(nsfem_ctx* c) {
+  hipStream_t s = c->stream;
+  const int64_t nv = nvel(c);
+  ensure_div_dicts(c);
+  if (c->have_body_force) {
+    NSFEM_REQUIRE(std::isfinite(c->coef[3]), "body force set but body_force_term coefficient is None");
+    launch_axpby(s, nv, -c->coef[3], c->state[NSFEM_BODY_FORCE].p, 0.0, c->state[NSFEM_BODY_FORCE].p, c->tmp_v.p);
+    launch_spmv(s, c->M2, c->mesh.dim, c->tmp_v.p, c->gconst.p, nullptr, MASK_NONE);
+  } else {
+    c->gconst.zero(s);
+  }
+  launch_spmv_axpy(s, c->DT, 1, -c->coef[1], c->state[NSFEM_P_OLD].p, c->gconst.p, nullptr);
+  if (c->have_traction)
+    launch_axpby(s, nv, 1.0, c->gconst.p, 1.0, c->state[NSFEM_TRACTION].p, c->gconst.p);
+}
+
+static bool imex_lattice_ok(nsfem_ctx* c) {
+  // (uniform lattices only: graded ones keep the generic path)
+  return jacobian_path(c) == 2 && c->L.dict && c->L.dict->exact && jacobian_lattice_variant(c->mesh) == 2;
+}
+
+// rhs = -[ L1 u1 + L2 u2 (+ c_v E (g1 u1 + g2 u2)) + g + (b0 n1 + b1 n2) ],  n1 = c_c conv(u1) -> `n1`;
+// n2 (null: not read, b1 = 0) = c_c conv(u2).  path: 0 the one-launch kernel where it applies, 1 generic, 2 one-launch
+// or error.  The generic sequence below DEFINES the summation order; k_jac_lattice<FORM, 3> reproduces it.
+static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double* rhs) {
+  hipStream_t s = c->stream;
+  const int64_t nv = nvel(c);
+  const double cc = cc_of(c);
+  const double *u1 = c->state[NSFEM_U1].p, *u2 = c->state[NSFEM_U2].p;
+  const double b0 = c->imex_beta[0], b1 = c->imex_beta[1];
+  if (path != 1 && imex_lattice_ok(c) &&
+      launch_imex_rhs_lattice(s, c->mesh, c->L1, c->L2, u1, u2, c->gconst.p, cc, c->conv_form, b0, b1, n2, n1, rhs))
+    return 2;
+  NSFEM_REQUIRE(path != 2, "one-launch IMEX right-hand side: not available on this mesh / these settings");
+  const int dim = c->mesh.dim;
+  launch_spmv(s, c->L1, dim, u1, rhs, nullptr, MASK_NONE);
+  launch_spmv(s, c->L2, dim, u2, c->tmp_v.p, nullptr, MASK_NONE);
+  launch_axpby(s, nv, 1.0, rhs, 1.0, c->tmp_v.p, rhs);
+  if (c->traction_form) {
+    launch_spmv_axpy(s, c->E, 1, c->imex_gamma[1] * c->coef[2], u1, rhs, nullptr);
+    launch_spmv_axpy(s, c->E, 1, c->imex_gamma[2] * c->coef[2], u2, rhs, nullptr);
+  }
+  launch_axpby(s, nv, 1.0, rhs, 1.0, c->gconst.p, rhs);
+  NSFEM_HIP(hipMemsetAsync(n1, 0, sizeof(double) * nv, s));
+  if (cc != 0.0) launch_convection_residual(s, c->mesh, u1, cc, n1, c->conv_form);
+  launch_imex_combine(s, nv, rhs, n1, n2, b0, b1, rhs);
+  return 1;
+}
+
+static void imex_require_supported(nsfem_ctx* c) {
+  NSFEM_REQUIRE(c->imex_active, "nsfem_set_imex has not been called");
+  NSFEM_REQUIRE(!c->distributed(), "IMEX pressure correction: partitioned meshes are not supported");
+  const bool euler = c->mesh.dim == 2 ? c->omega_dot != 0.0
+                                      : (c->omega_dot3[0] != 0.0 || c->omega_dot3[1] != 0.0 || c->omega_dot3[2] != 0.0);
+  NSFEM_REQUIRE(!coriolis_active(c) && !euler,
+                "IMEX pressure correction: rotating frames (Coriolis / Euler terms) are not supported");
+}
+
+extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
+  nsfem_step_info local;
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && opts, "null argument");
+  NSFEM_REQUIRE(opts->convective_form >= 0 && opts->convective_form <= 3, "unknown convective form");
+  NSFEM_REQUIRE(opts->momentum.precond == 0 || opts->momentum.precond == 1,
+                "IMEX diffusion step: momentum.precond must be 0 (Jacobi) or 1 (multigrid)");
+  imex_require_supported(ctx);
+  if (ctx->conv_form != opts->convective_form || ctx->picard) ctx->graph_epoch++;
+  ctx->conv_form = opts->convective_form;
+  ctx->picard = false;
+  nsfem_step_info& inf = info ? *info : local;
+  std::memset(&inf, 0, sizeof(inf));
+  hipStream_t s = ctx->stream;
+  const int64_t nv = nvel(ctx);
+  const double cc = cc_of(ctx);
+  // ---- diffusion step: one linear solve
+  ensure_imex_ops(ctx);
+  imex_begin_step(ctx);
+  const double* n2 = nullptr;
+  if (ctx->imex_beta[1] != 0.0) {
+    // c_c N(u2): what the previous step stored, unless the level, the form or the coefficient changed under it
+    const bool stored = ctx->conv_n2_valid && (ctx->conv_n_form == -2 ||
+                                               (ctx->conv_n_form == ctx->conv_form && ctx->conv_n_cc == cc));
+    if (!stored) {
+      ctx->state[NSFEM_CONV_N2].zero(s);
+      if (cc != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc, ctx->state[NSFEM_CONV_N2].p,
+                                                ctx->conv_form);
+      ctx->conv_n2_valid = true;
+    }
+    n2 = ctx->state[NSFEM_CONV_N2].p;
+  }
+  ctx->imex_last_path = imex_rhs(ctx, 0, n2, ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
+  ++(ctx->imex_last_path == 2 ? ctx->imex_lattice_rhs : ctx->imex_generic_rhs);
+  ctx->conv_n1_fresh = true;
+  ctx->conv_n_form = ctx->conv_form;
+  ctx->conv_n_cc = cc;
+  {
+    // Dirichlet rows u*_i = g_i; start vector u1 with the Dirichlet values
+    double* x = ctx->state[NSFEM_USTAR].p;
+    launch_set_values(s, ctx->nbc_v, ctx->bc_v_dofs.p, ctx->bc_v_vals.p, ctx->rhs_v.p);
+    NSFEM_HIP(hipMemcpyAsync(x, ctx->state[NSFEM_U1].p, sizeof(double) * nv, hipMemcpyDeviceToDevice, s));
+    launch_set_values(s, ctx->nbc_v, ctx->bc_v_dofs.p, ctx->bc_v_vals.p, x);
+    LinOp op;
+    if (ctx->traction_form) {       // block matrix  (alpha0/k M + gamma0 c_v K) I + gamma0 c_v E
+      const double cvE = ctx->imex_gamma[0] * ctx->coef[2];
+      if (ctx->mesh.dim == 3) jacobian_init_3d(s, ctx->p22.nnz, ctx->L.vals.p, ctx->E.vals.p, cvE, ctx->J.vals.p);
+      else launch_jacobian_init(s, ctx->p22.nnz, ctx->L.vals.p, ctx->E.vals.p, cvE, ctx->J.vals.p);
+      op.A = &ctx->J;
+      op.nv = 1;
+    } else {
+      op.A = &ctx->L;
+      op.nv = ctx->mesh.dim;
+    }
+    op.rowmask = ctx->mask_v.p;
+    op.maskmode = MASK_ZERO;
+    op.dinv = ctx->dinv_v.p;
+    fill_linop(ctx, op, true);
+    if (opts->momentum.precond == 1) {
+      NSFEM_REQUIRE(ctx->mg_built, "multigrid requested but no hierarchy was set (nsfem_mg_finalize)");
+      set_velocity_cycle_symmetric(ctx, true);
+      mg_refresh(ctx, true);
+      op.prec = &ctx->mom_prec;
+    } else {
+      launch_inv_diag(s, *op.A, op.nv, ctx->mask_v.p, ctx->dinv_v.p);
+    }
+    op.graph_epoch = ctx->graph_epoch;
+    nsfem_solve_info si;
+    nsfem_ctx::SolveHint& hint = ctx->hint_mom[0];
+    int rc = pcg(s, ctx->kw, op, ctx->rhs_v.p, x, hinted(opts->momentum, hint), si, false);
+    note_solve(hint, si, opts->momentum, ctx->kw.last_target);
+    inf.krylov_iterations_momentum = si.iterations;
+    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the IMEX diffusion step");
+    inf.newton_iterations = 0;
+    inf.converged = 1;
+  }
+  // ---- projection step (as nsfem_step_ipcs)
+  {
+    nsfem_solve_info si;
+    int rc;
+    const bool fd = opts->poisson.precond == 3;
+    const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && ctx->distributed() == ctx->fd3_p.slab()
+                                           : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
+    if (fd && !pressure_pinned_anywhere(ctx) && direct) {
+      rc = poisson_direct_step(ctx, opts->poisson, si);
+    } else {
+      poisson_assemble(ctx, opts->pressure_extrapolation != 0);
+      rc = poisson_solve(ctx, hinted(opts->poisson, ctx->hint_poi), si);
+    }
+    note_solve(ctx->hint_poi, si, opts->poisson, ctx->kw.last_target);
+    inf.krylov_iterations_poisson = si.iterations;
+    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the projection step");
+  }
+  // ---- velocity correction step (as nsfem_step_ipcs)
+  {
+    correction_assemble(ctx, opts->correction.precond == 2);
+    nsfem_solve_info si;
+    int rc = correction_solve(ctx, hinted(opts->correction, ctx->hint_cor, opts->correction.precond == 2), si);
+    note_solve(ctx->hint_cor, si, opts->correction, ctx->kw.last_target);
+    inf.krylov_iterations_correction = si.iterations;
+    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the velocity correction step");
+  }
+  ctx->assembled_system = -1;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_imex_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->imex_last_path;
+  out[1] = ctx->imex_lattice_rhs;
+  out[2] = ctx->imex_generic_rhs;
+  out[3] = ctx->imex_matrix_builds;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, double* rhs, double* conv_n1) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && rhs, "null argument");
+  NSFEM_REQUIRE(path == 1 || path == 2, "path: 1 generic, 2 one-launch");
+  NSFEM_REQUIRE(convective_form >= 0 && convective_form <= 3, "unknown convective form");
+  imex_require_supported(ctx);
+  if (ctx->conv_form != convective_form || ctx->picard) ctx->graph_epoch++;
+  ctx->conv_form = convective_form;
+  ctx->picard = false;
+  hipStream_t s = ctx->stream;
+  const int64_t nv = nvel(ctx);
+  ensure_imex_ops(ctx);
+  imex_begin_step(ctx);
+  // (work vectors of the Krylov solvers: nothing of the step's own state is touched; c_c N(u2) is evaluated afresh)
+  ctx->kw.ensure(nv);
+  ++ctx->kw.touch;
+  double *n1 = ctx->kw.p.p, *n2 = nullptr, *out = ctx->kw.q.p;
+  if (ctx->imex_beta[1] != 0.0) {
+    n2 = ctx->kw.z.p;
+    NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nv, s));
+    if (cc_of(ctx) != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form);
+  }
+  imex_rhs(ctx, path, n2, n1, out);
+  NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+  if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
   API_END(ctx)
 }
 
@@ -2256,6 +2548,14 @@ extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
     std::swap(ctx->state[NSFEM_P2_OLD].p, ctx->state[NSFEM_P_OLD].p);
     NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_P_OLD].p, ctx->state[NSFEM_P].p,
                              sizeof(double) * npre(ctx), hipMemcpyDeviceToDevice, s));
+  }
+  // IMEX: c_c N(u1) of the step becomes c_c N(u2) of the next one
+  if (ctx->conv_n1_fresh) {
+    std::swap(ctx->state[NSFEM_CONV_N2].p, ctx->state[NSFEM_CONV_N1].p);
+    ctx->conv_n2_valid = true;
+    ctx->conv_n1_fresh = false;
+  } else {
+    ctx->conv_n2_valid = false;
   }
   // (no synchronisation: everything that reads the state is ordered on the context's stream, nsfem_get_state and
   // nsfem_synchronize wait for it -- a host wait here left the GPU idle ~20 us in every time step)

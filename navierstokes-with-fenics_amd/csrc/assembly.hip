@@ -788,6 +788,29 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 }
 
 
+// ---------------------------------------------------------------- IMEX right-hand side
+// rhs = -(t + (b0 n1 + b1 n2)): the last operation of the right-hand side of nsfem_step_imex, shared by the generic
+// path (k_imex_combine) and the lattice kernel (k_jac_lattice<FORM, 3>).  No contraction: both callers must round
+// the same way whatever surrounds the call
+__device__ __forceinline__ double imex_rhs_value(double t, double n1, double n2, double b0, double b1, bool have_n2) {
+#pragma clang fp contract(off)
+  const double old = have_n2 ? b1 * n2 : 0.0;
+  const double e = fma(b0, n1, old);
+  return -(t + e);
+}
+__global__ __launch_bounds__(256) void k_imex_combine(int64_t n, const double* __restrict__ t,
+                                                      const double* __restrict__ n1, const double* __restrict__ n2,
+                                                      double b0, double b1, double* __restrict__ rhs) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  rhs[i] = imex_rhs_value(t[i], n1[i], n2 ? n2[i] : 0.0, b0, b1, n2 != nullptr);
+}
+void launch_imex_combine(hipStream_t s, int64_t n, const double* t, const double* n1, const double* n2, double b0,
+                         double b1, double* rhs) {
+  hipLaunchKernelGGL(k_imex_combine, dim3(grid_for(n)), dim3(kBlock), 0, s, n, t, n1, n2, b0, b1, rhs);
+  NSFEM_HIP(hipGetLastError());
+}
+
 // ---------------------------------------------------------------- lattice Jacobian action
 // y = L x + c_c [d conv(u)/du] x  (identity on the rows flagged in the mask) in ONE launch on 2D lattice meshes
 // (rectangle_mesh numbering: cell 2 (sy nx + sx) + t, P2 node j W + i): the pair of launches it replaces --
@@ -815,6 +838,12 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 // of each owned node adds its <= 6 contributions in ascending cell order onto L x (+ g) kept in registers: the same
 // additions in the same order as the six rounds, bit for bit; 2 as 1 with the physical gradients and weights of the
 // two cell types read from tables (uniform lattices: phys() once per type in k_grad_tables, the same bits)
+// LIN = 3 (variant 2 only: uniform lattices): the right-hand side of the IMEX diffusion step.  u = u1 AND ix.u2 are staged (the layout of
+// the Jacobian action: two staged vectors; the second value table of 8 B per dictionary entry fits under the element
+// vectors' overlay, the workgroup's LDS does not grow); phase 1 forms (L1 u1)(node) and (L2 u2)(node) from the two
+// value tables of the shared dictionary and adds them and g; phase 2 is the residual's element kernel on u1; the
+// gather sums the node's element vectors from +0.0 on -- c_c conv(u1), stored to ix.n1 -- and writes
+// imex_rhs_value(...) with the stored ix.n2: the generic sequence of nsfem_step_imex, bit for bit.
 struct TabGrad {
   const double* __restrict__ t;   // [7][6][2] gradients, then [7] weights of one cell type (wave-uniform address)
   __device__ __forceinline__ void grad(int q, int k, double& gx, double& gy) const {
@@ -851,12 +880,17 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
                    const double* __restrict__ x, const uint8_t* __restrict__ sid8,
                    const uint8_t* __restrict__ mask, const int32_t* __restrict__ slen,
                    const int32_t* __restrict__ spack, const double* __restrict__ sval,
-                   const double* __restrict__ gadd, double* __restrict__ y, const double* __restrict__ ugeo) {
+                   const double* __restrict__ gadd, double* __restrict__ y, const double* __restrict__ ugeo,
+                   ImexLatArgs ix) {
   // LIN = 0: the momentum residual  y = L u + g + c_c conv(u)  (x is not read, no mask: the Dirichlet rows are
   // set by the caller afterwards); g joins the node's sum after the L product and before the element vectors,
   // the order of the launches it replaces (product, axpby, k_conv_cell, k_res_gather).
   // ugeo: V 0, 1 the two types' geometry [2][5] (uniform lattices; null: load_geo per cell), V 2 the gradient tables
-  constexpr bool RES = LIN == 0;
+  constexpr bool IMX = LIN == 3;
+  constexpr bool RES = LIN == 0 || IMX;
+  constexpr bool TWO = LIN != 0;                                    // a second staged vector (x, or u2)
+  constexpr int CLIN = IMX ? 0 : LIN;                               // mode of the element kernel
+  static_assert(!IMX || V == 2, "the right-hand-side mode is built for the table variant only");
   extern __shared__ __attribute__((aligned(16))) double sh_jl[];
   constexpr int NT = 2 * SX * SY;                                   // threads
   constexpr int kJlNW = 2 * SX + 1, kJlNH = 2 * SY + 1;             // staged node lines
@@ -866,10 +900,11 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   constexpr int NN = kJlNW * kJlNH;
   // (V 1, 2: sa first, the element vectors of phase 3 then overlay su, sx and the tables: NN + 12 SX SY double2)
   double2* __restrict__ su = reinterpret_cast<double2*>(sh_jl) + (V ? NN : 0);
-  double2* __restrict__ sx = RES ? su : su + NN;
+  double2* __restrict__ sx = TWO ? su + NN : su;
   double2* __restrict__ sa = V ? reinterpret_cast<double2*>(sh_jl) : sx + NN;
   double* __restrict__ tv = reinterpret_cast<double*>((V ? sx : sa) + NN);   // [n_st * lp]
-  int* __restrict__ to = reinterpret_cast<int*>(tv + a.n_st * a.lp);
+  double* __restrict__ tv2 = tv + a.n_st * a.lp;                             // (LIN 3: the values of L2)
+  int* __restrict__ to = reinterpret_cast<int*>(tv + (IMX ? 2 : 1) * a.n_st * a.lp);
   int* __restrict__ tl = to + a.n_st * a.lp;
   // XCD x (workgroups b = x mod 8) walks a contiguous range of tiles: neighbouring tiles share their halo in L2
   const int per = (a.ntiles + 7) >> 3;
@@ -880,7 +915,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   const int i0 = tx * kJlOX - 2, j0 = ty * kJlOY - 2;               // lattice position of the LDS tile's corner
   const int tid = threadIdx.x;
   const double2* __restrict__ u2 = reinterpret_cast<const double2*>(u);
-  const double2* __restrict__ x2 = reinterpret_cast<const double2*>(x);
+  const double2* __restrict__ x2 = reinterpret_cast<const double2*>(IMX ? ix.u2 : x);
   // ---- phase 0: every global load of the workgroup is requested before the first one is waited for
   constexpr int NLD = (NN + NT - 1) / NT;
   double2 uv[NLD], xv[NLD];
@@ -894,7 +929,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     if (t < NN && gi >= 0 && gi < a.W && gj >= 0 && gj < a.H && !NSFEM_KO(a.dbg & 8)) {
       const size_t g = (size_t)gj * a.W + gi;
       uv[r] = u2[g];
-      if (!RES) xv[r] = x2[g];
+      if (TWO) xv[r] = x2[g];
     }
   }
   // (this thread's cell, its two owned nodes)
@@ -926,6 +961,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   int obase[NOWN], oent[NOWN], omask[NOWN];
   size_t onode[NOWN];
   double2 og[RES ? NOWN : 1];
+  double2 on2[IMX ? NOWN : 1];
 #pragma unroll
   for (int r = 0; r < NOWN; ++r) {
     const int o = tid + r * NT;
@@ -940,13 +976,15 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       onode[r] = (size_t)gj * a.W + gi;
       oent[r] = sid8[onode[r]];
       if (RES) og[r] = reinterpret_cast<const double2*>(gadd)[onode[r]];
-      else omask[r] = reinterpret_cast<const uint16_t*>(mask)[onode[r]];
+      if (IMX) on2[r] = ix.n2 ? reinterpret_cast<const double2*>(ix.n2)[onode[r]] : make_double2(0.0, 0.0);
+      if (!RES) omask[r] = reinterpret_cast<const uint16_t*>(mask)[onode[r]];
     }
   }
   for (int t = tid; t < a.n_st * a.lp; t += NT) {
     const int e = t / a.lp, k = t - e * a.lp;
     const bool in = k < a.lmax;
     tv[t] = in ? sval[e * a.lmax + k] : 0.0;
+    if (IMX) tv2[t] = in ? ix.sval2[e * a.lmax + k] : 0.0;
     const int pk = in ? spack[e * a.lmax + k] : (8 * 32 + 8);
     to[t] = ((pk >> 5) - 8) * kJlNW + ((pk & 31) - 8);
   }
@@ -957,7 +995,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     const int t = tid + r * NT;
     if (t < NN) {
       su[t] = uv[r];
-      if (!RES) sx[t] = xv[r];
+      if (TWO) sx[t] = xv[r];
     }
   }
   __syncthreads();
@@ -972,15 +1010,32 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     const int L = NSFEM_KO(a.dbg & 2) ? 0 : tl[oent[r]];
     const int* __restrict__ op = to + oent[r] * a.lp;
     const double* __restrict__ vp = tv + oent[r] * a.lp;
+    const double2* __restrict__ s1 = IMX ? su : sx;
     double ax = 0.0, ay = 0.0;
     for (int k = 0; k < L; k += 4) {
       const int4 o4 = *reinterpret_cast<const int4*>(op + k);
       const double2 va = *reinterpret_cast<const double2*>(vp + k), vb = *reinterpret_cast<const double2*>(vp + k + 2);
-      const double2 x0 = sx[base + o4.x], x1 = sx[base + o4.y], x2_ = sx[base + o4.z], x3 = sx[base + o4.w];
+      const double2 x0 = s1[base + o4.x], x1 = s1[base + o4.y], x2_ = s1[base + o4.z], x3 = s1[base + o4.w];
       ax = fma(va.x, x0.x, ax); ay = fma(va.x, x0.y, ay);
       ax = fma(va.y, x1.x, ax); ay = fma(va.y, x1.y, ay);
       ax = fma(vb.x, x2_.x, ax); ay = fma(vb.x, x2_.y, ay);
       ax = fma(vb.y, x3.x, ax); ay = fma(vb.y, x3.y, ay);
+    }
+    if constexpr (IMX) {
+      // (L2 u2)(node): the same row of the shared dictionary with L2's values, then L1 u1 + L2 u2 (the generic
+      // path's axpby with weights 1, 1)
+      const double* __restrict__ vq = tv2 + oent[r] * a.lp;
+      double bx = 0.0, by = 0.0;
+      for (int k = 0; k < L; k += 4) {
+        const int4 o4 = *reinterpret_cast<const int4*>(op + k);
+        const double2 va = *reinterpret_cast<const double2*>(vq + k), vb = *reinterpret_cast<const double2*>(vq + k + 2);
+        const double2 x0 = sx[base + o4.x], x1 = sx[base + o4.y], x2_ = sx[base + o4.z], x3 = sx[base + o4.w];
+        bx = fma(va.x, x0.x, bx); by = fma(va.x, x0.y, by);
+        bx = fma(va.y, x1.x, bx); by = fma(va.y, x1.y, by);
+        bx = fma(vb.x, x2_.x, bx); by = fma(vb.x, x2_.y, by);
+        bx = fma(vb.y, x3.x, bx); by = fma(vb.y, x3.y, by);
+      }
+      ax += bx; ay += by;
     }
     if (RES) { ax += og[r].x; ay += og[r].y; }
     if (V != 0 && !RES) {
@@ -1018,8 +1073,8 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
 #pragma unroll
       for (int k = 0; k < 6; ++k) { rx[k] = ux[k]; ry[k] = uy[k]; }
     } else {
-      if constexpr (V == 2) conv_cell_eval_g<FORM, LIN>(TabGrad{ugeo + kGradTab * ct}, ux, uy, wx, wy, a.cc, rx, ry);
-      else conv_cell_eval<FORM, LIN>(geo, ux, uy, wx, wy, a.cc, rx, ry);
+      if constexpr (V == 2) conv_cell_eval_g<FORM, CLIN>(TabGrad{ugeo + kGradTab * ct}, ux, uy, wx, wy, a.cc, rx, ry);
+      else conv_cell_eval<FORM, CLIN>(geo, ux, uy, wx, wy, a.cc, rx, ry);
     }
   }
   __syncthreads();
@@ -1046,7 +1101,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       for (int h = 0; h < 3; ++h) pe[h] = (lj & 1) ? ((li & 1) ? a.gl[3][h] : a.gl[2][h]) : ((li & 1) ? a.gl[1][h] : a.gl[0][h]);
       const double2* __restrict__ sq = se + ((lj >> 1) * SX + (li >> 1) - 2 * SX);
       const double2 a0 = sa[obase[r]];
-      double vx_ = a0.x, vy_ = a0.y;
+      double vx_ = IMX ? 0.0 : a0.x, vy_ = IMX ? 0.0 : a0.y;
 #pragma unroll
       for (int e = 0; e < 6; ++e) {
         if NSFEM_KO(a.dbg & 4) break;
@@ -1055,6 +1110,12 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
         vy_ += v.y;
       }
       double2 v = make_double2(vx_, vy_);
+      if constexpr (IMX) {
+        reinterpret_cast<double2*>(ix.n1)[onode[r]] = v;
+        const bool have = ix.n2 != nullptr;
+        v.x = imex_rhs_value(a0.x, vx_, on2[r].x, ix.b0, ix.b1, have);
+        v.y = imex_rhs_value(a0.y, vy_, on2[r].y, ix.b0, ix.b1, have);
+      }
       if (!RES) {
         if (omask[r] & 0x00ff) v.x = a0.x;
         if (omask[r] & 0xff00) v.y = a0.y;
@@ -1256,12 +1317,12 @@ static void jac_lattice_shape(int& sx, int& sy) {
   sx = shapes[g_jac_lattice_tile][0];
   sy = shapes[g_jac_lattice_tile][1];
 }
-static size_t jac_lattice_lds(const StencilDict& d) {
+static size_t jac_lattice_lds(const StencilDict& d, bool imex = false) {
   const size_t lp = (size_t)((d.lmax + 3) & ~3);
   int sx, sy;
   jac_lattice_shape(sx, sy);
   const size_t nn = (size_t)(2 * sx + 1) * (2 * sy + 1);
-  const size_t staged = 3 * nn * sizeof(double2) + (size_t)d.n_stencils * lp * 12 + (size_t)d.n_stencils * 4 + 16;
+  const size_t staged = 3 * nn * sizeof(double2) + (size_t)d.n_stencils * lp * (imex ? 20 : 12) + (size_t)d.n_stencils * 4 + 16;
   // variants 1, 2: sa, then the element vectors of the gather over su, sx and the tables
   return g_jac_gather ? std::max(staged, (nn + (size_t)13 * sx * sy) * sizeof(double2)) : staged;
 }
@@ -1282,7 +1343,7 @@ int64_t jacobian_lattice_bytes(const MeshDev& m) {
   return (int64_t)m.n_p2 * (3 * 16 + 1 + 2) + ((g_jac_uniform_geo && m.cl.geo_uniform) ? 0 : (int64_t)m.n_cells * 48);
 }
 
-// lin: 0 residual (x, mask unused; gadd = g), 1 Newton action, 2 Picard action
+// lin: 0 residual (x, mask unused; gadd = g), 1 Newton action, 2 Picard action, 3 IMEX right-hand side (ix; L = L1)
 // phase 0: every tile; 1: the tile rows that read no lattice line below `safe_lo` or from `safe_hi` on (the interior of
 // a partitioned strip, launched under the halo exchange); 2: the other tile rows.  jacobian_lattice_split tells
 // whether phases 1 / 2 exist for the given ghost lines
@@ -1304,9 +1365,11 @@ bool jacobian_lattice_split(const MeshDev& m, int gh_lo, int gh_hi) {
 }
 static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat& L, const double* u,
                                  const double* x, double cc, int form, int lin, const uint8_t* mask,
-                                 const double* gadd, double* y, int phase = 0, int gh_lo = 0, int gh_hi = 0) {
+                                 const double* gadd, double* y, int phase = 0, int gh_lo = 0, int gh_hi = 0,
+                                 const ImexLatArgs* imex = nullptr) {
   const CellLattice& cl = m.cl;
   if (!jacobian_lattice_available(m, L)) return false;
+  const ImexLatArgs ix = imex ? *imex : ImexLatArgs();
   const StencilDict& d = *L.dict;
   JacLatArgs a;
   a.nx = cl.nx; a.ny = cl.ny; a.W = cl.W; a.H = cl.H; a.nc = m.n_cells;
@@ -1357,7 +1420,8 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
     for (int h = 0; h < 3; ++h) a.gl[c][h] = packed[2 * h] | (packed[2 * h + 1] << 16);
   }
   const int var = jacobian_lattice_variant(m);
-  const size_t lds = jac_lattice_lds(d);
+  if (lin == 3 && var != 2) return false;           // (the right-hand-side mode: uniform lattices, gradient tables)
+  const size_t lds = jac_lattice_lds(d, lin == 3);
   const int grid = ((a.ntiles + 7) / 8) * 8;
 #define NSFEM_JL_V(F, LIN, SX, SY, V)                                                                       \
   do {                                                                                                      \
@@ -1376,7 +1440,7 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
     hipLaunchKernelGGL((k_jac_lattice<F, LIN, SX, SY, V>), dim3(grid), dim3(2 * SX * SY), lds, s, a, m.vx.p, u, \
                        x, d.sid8.p, mask, d.len.p, d.pack.p, L.dict_vals.p, gadd, y,                        \
                        (const double*)(V == 2 ? cl.gtab.p                                                   \
-                                              : g_jac_uniform_geo && cl.geo_uniform ? cl.ugeo.p : nullptr)); \
+                                              : g_jac_uniform_geo && cl.geo_uniform ? cl.ugeo.p : nullptr), ix); \
   } while (0)
 #define NSFEM_JL_T(F, LIN, SX, SY)                                                                          \
   do {                                                                                                      \
@@ -1400,7 +1464,10 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
     case 3: NSFEM_JL(3, LIN); break;                                                                        \
     default: throw Error(NSFEM_ERR_ARG, "unknown convective form");                                         \
   }
-  if (lin == 0) { NSFEM_JL_F(0) } else if (lin == 2) { NSFEM_JL_F(2) } else { NSFEM_JL_F(1) }
+  if (lin == 0) { NSFEM_JL_F(0) } else if (lin == 2) { NSFEM_JL_F(2) } else if (lin == 1) { NSFEM_JL_F(1) }
+#undef NSFEM_JL_T
+#define NSFEM_JL_T(F, LIN, SX, SY) NSFEM_JL_V(F, LIN, SX, SY, 2)
+  if (lin == 3) { NSFEM_JL_F(3) }
 #undef NSFEM_JL_F
 #undef NSFEM_JL_T
 #undef NSFEM_JL_V
@@ -1421,6 +1488,22 @@ bool launch_residual_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L,
                              double cc, int form, double* y) {
   if (!L.dict || !L.dict->exact || !g) return false;
   return launch_lattice_cells(s, m, L, u, u, cc, form, 0, nullptr, g, y);
+}
+
+// rhs = -((L1 u1 + L2 u2 + g) + (b0 n1 + b1 n2)) with n1 = c_c conv(u1) stored: the right-hand side of the IMEX
+// diffusion step before its Dirichlet rows are set.  Only on dictionaries that equal the assembled matrices bit for bit
+bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
+                             const double* u2, const double* g, double cc, int form, double b0, double b1,
+                             const double* n2, double* n1, double* rhs) {
+  if (!L1.dict || !L1.dict->exact || L2.dict != L1.dict || !L1.dict_ready || !L2.dict_ready || !g || !n1) return false;
+  ImexLatArgs ix;
+  ix.u2 = u2;
+  ix.sval2 = L2.dict_vals.p;
+  ix.n2 = n2;
+  ix.n1 = n1;
+  ix.b0 = b0;
+  ix.b1 = b1;
+  return launch_lattice_cells(s, m, L1, u1, u1, cc, form, 3, nullptr, g, rhs, 0, 0, 0, &ix);
 }
 
 }  // namespace nsfem

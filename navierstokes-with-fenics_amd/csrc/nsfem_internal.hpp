@@ -418,6 +418,25 @@ int64_t jacobian_lattice_bytes(const MeshDev& m);   // u, x read, y written, ids
 bool launch_jacobian_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L, const double* u, const double* x,
                              double cc, int form, bool picard, const uint8_t* mask, double* y, int phase = 0,
                              int gh_lo = 0, int gh_hi = 0);
+// IMEX right-hand side (nsfem_step_imex): with t = (L1 u1 + L2 u2) + g and n1 = 0 + c_c conv(u1) (the node sums of
+// launch_convection_residual on a zeroed vector)
+//   rhs = -(t + (b0 n1 + b1 n2))      (imex_rhs_value; n2 is not read when have_n2 is false)
+// and n1 is stored.  launch_imex_rhs_lattice: ONE launch of k_jac_lattice<FORM, 3> on 2D lattice meshes whose
+// dictionary equals the assembled matrices bit for bit (false = not available, nothing launched); it reproduces the
+// generic sequence -- launch_spmv (L1, L2), launch_axpby twice, launch_convection_residual, launch_imex_combine --
+// bit for bit.  L1, L2 share L's pattern and dictionary.
+struct ImexLatArgs {
+  const double* u2 = nullptr;      // velocity at t_(n-1)
+  const double* sval2 = nullptr;   // dictionary values of L2
+  const double* n2 = nullptr;      // c_c conv(u2) (null: not read)
+  double* n1 = nullptr;            // c_c conv(u1), written
+  double b0 = 1.0, b1 = 0.0;
+};
+bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
+                             const double* u2, const double* g, double cc, int form, double b0, double b1,
+                             const double* n2, double* n1, double* rhs);
+void launch_imex_combine(hipStream_t s, int64_t n, const double* t, const double* n1, const double* n2, double b0,
+                         double b1, double* rhs);
 // partitioned strips: can the launch be cut into tile rows that read no ghost line (phase 1, under the halo
 // exchange) and the rest (phase 2)?
 bool jacobian_lattice_split(const MeshDev& m, int gh_lo, int gh_hi);
@@ -964,6 +983,21 @@ struct nsfem_ctx {
   nsfem::DevBuf<double> rot_field, rot_tmp;
   double k = 1.0;
   bool L_dirty = true;
+  // IMEX pressure correction (nsfem_set_imex / nsfem_step_imex): gamma0 scales the stiffness part of L; L1, L2 are
+  // the operators of the old levels in the right-hand side, (alpha_i/k) M + gamma_i c_v K
+  bool imex_active = false;
+  double imex_beta[2] = {1.0, 0.0}, imex_gamma[3] = {1.0, 0.0, 0.0};
+  nsfem::BlockMat L1, L2;
+  bool imex_ops_dirty = true;
+  bool conv_n2_valid = false, conv_n1_fresh = false;   // N2 holds c_c N(u2) / N1 was written since the last advance
+  int conv_n_form = -1;                                // convective form and coefficient the stored vectors belong to
+  double conv_n_cc = 0.0;
+  // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the
+  // non-symmetric V(0, d + 1) the BiCGStab solves use (nsfem_set_bdf switches back)
+  bool mg_v_symmetric = false;
+  int mg_v_pre_saved = 0, mg_v_degree_saved = 0;
+  int imex_last_path = 0;
+  int64_t imex_lattice_rhs = 0, imex_generic_rhs = 0, imex_matrix_builds = 0;
   nsfem::DevBuf<double> state[NSFEM_N_SLOTS];
   bool have_body_force = false, have_traction = false;
   // Dirichlet data

@@ -9,9 +9,9 @@ For a scheme parameter pair (a, b) and the step ratio w = k_{n+1} / k_n the clas
   eta    linear Taylor extrapolation to t_{n+1} from levels n, n-1,
 
 with (a, b) = (1, 0) SBDF2, (1/2, 0) CNAB, (1/2, 1/8) modified CNAB, (0, 1) CNLF.  The very first
-step is first order (implicit Euler / explicit convection).  No solver of this repository uses
-the class yet (neither does the reference); it is pinned by golden trajectories produced by the
-reference's own module (tests/golden/imex_theta_tables.json).
+step is first order (implicit Euler / explicit convection).  ``ns_imex_solver.IMEXIPCSSolver``
+drives the class (the reference has no solver for it); it is pinned by golden trajectories
+produced by the reference's own module (tests/golden/imex_theta_tables.json).
 """
 import math
 from enum import Enum, auto

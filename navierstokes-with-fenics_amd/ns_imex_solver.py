@@ -1,0 +1,108 @@
+"""Implicit-explicit (IMEX) incremental pressure-correction scheme on the MI355X.
+
+The reference lists the decoupled IMEX schemes as solvers "to be included"; this class drives the
+coefficients of ``imex_time_stepping.IMEXTimeStepping`` (SBDF2, CNAB, mCNAB, CNLF).  The convective
+term is extrapolated from the known time levels, so the diffusion step is ONE linear solve with the
+constant, symmetric positive definite matrix  alpha_0/k M + gamma_0 c_v K  -- CG instead of the
+Newton / BiCGStab iteration of ``IPCSSolver``.  With alpha, beta, gamma of the time stepping, step
+size k, u1 = u^n, u2 = u^(n-1) and N(u) the convective weak form vector in the selected form:
+
+  1. diffusion step (CG):
+       (alpha_0/k M + gamma_0 c_v K) u* = -[ M (alpha_1 u1 + alpha_2 u2)/k
+           + c_v K (gamma_1 u1 + gamma_2 u2) + c_c (beta_0 N(u1) + beta_1 N(u2))
+           - c_p D^T p_old - c_b M f + traction ],     Dirichlet rows u*_i = g_i
+     (traction-form viscosity: K is the traction-form stiffness)
+  2. projection step:     A_p p = A_p p_old - alpha_0/k D u*          (as ``IPCSSolver``)
+  3. velocity correction: M u = M u* - k/alpha_0 G (p - p_old)        (as ``IPCSSolver``)
+
+N(u2) is not recomputed: the device keeps N(u1) of a step for the next one.  On 2D lattice meshes
+with exact stencil dictionaries the whole right-hand side of step 1 is one kernel launch.
+
+The scheme is conditionally stable (a CFL-type restriction on k, reported by the problem classes'
+CFL diagnostic).  Rotating frames (Coriolis / Euler terms) and partitioned meshes are refused with
+an error by the device driver; 3D meshes run through the generic right-hand-side path.
+"""
+import _native as nat
+from fem_function import DeviceFunction, MixedFunction
+from imex_time_stepping import IMEXTimeStepping, IMEXType
+from ns_ipcs_solver import _FORM_ID, _DeviceSystem
+from ns_solver_base import InstationarySolverBase
+
+
+class IMEXIPCSSolver(InstationarySolverBase):
+    _required_objects = ("_diffusion_solver", "_projection_solver", "_velocity_correction_solver")
+    _scheme_id = 0
+    #: what InstationaryProblem.solve_problem builds for this solver class
+    time_stepping_class = IMEXTimeStepping
+    imex_type = IMEXType.SBDF2
+
+    def __init__(self, mesh, boundary_markers, form_convective_term, time_stepping, tol=1e-10,
+                 max_iter=50, device=0):
+        assert isinstance(time_stepping, IMEXTimeStepping)
+        super().__init__(mesh, boundary_markers, form_convective_term, time_stepping, tol,
+                         max_iter, device=device)
+        self.last_step_info = None
+
+    def _setup_function_spaces(self):
+        if not hasattr(self, "_Wh"):
+            super()._setup_function_spaces()
+        slots = (nat.U0, nat.U1, nat.U2)
+        self._velocities = []
+        for i in range(self._n_time_levels() + 1):
+            name = i * "old" + (i > 0) * "_" + "velocity"
+            self._velocities.append(DeviceFunction(self, "velocity", slots[i], name))
+        self._intermediate_velocity = DeviceFunction(self, "velocity", nat.USTAR,
+                                                     "intermediate_velocity")
+        self._pressure = DeviceFunction(self, "pressure", nat.P, "pressure")
+        self._old_pressure = DeviceFunction(self, "pressure", nat.P_OLD, "old_pressure")
+
+    def _setup_problem(self):
+        if not all(hasattr(self, a) for a in ("_Wh", "_solutions", "_intermediate_velocity",
+                                              "_velocities", "_pressure", "_old_pressure")):  # pragma: no cover
+            self._setup_function_spaces()
+        self._ctx.set_convective_form(_FORM_ID[self._form_convective_term])
+        if not all(hasattr(self, a) for a in ("_next_step_size", "_alpha", "_beta", "_gamma")):
+            self._update_time_stepping_coefficients()
+        self._setup_boundary_conditions()
+        self._diffusion_solver = _DeviceSystem(self, nat.SYS_MOMENTUM)
+        self._projection_solver = _DeviceSystem(self, nat.SYS_POISSON)
+        self._velocity_correction_solver = _DeviceSystem(self, nat.SYS_CORRECTION)
+
+    def _update_time_stepping_coefficients(self):
+        """alpha, beta, gamma and the step size k -> device"""
+        ts = self._time_stepping
+        self._next_step_size = ts.get_next_step_size()
+        self._alpha, self._beta, self._gamma = list(ts.alpha), list(ts.beta), list(ts.gamma)
+        assert len(self._alpha) == 3 and len(self._beta) == 2 and len(self._gamma) == 3
+        self._ctx.set_imex(self._alpha, self._beta, self._gamma, self._next_step_size)
+
+    def _step_options(self):
+        o = self._common_step_options(self._ctx.default_step_opts())
+        o.convective_form = _FORM_ID[self._form_convective_term]
+        for k in (o.momentum, o.poisson, o.correction):
+            k.rtol = self.krylov_rtol
+            k.max_iter = self.krylov_max_iter
+        if self._mg_levels is not None:
+            o.momentum.precond = o.poisson.precond = 1
+        assert self.poisson_solver in ("multigrid", "fast_diagonalization")
+        if self.poisson_solver == "fast_diagonalization" and self._fast_diagonalization_ready():
+            o.poisson.precond = 3
+        assert self.mass_solver in ("chebyshev", "cg")
+        o.correction.precond = 2 if self.mass_solver == "chebyshev" else 0
+        return o
+
+    def _solve_time_step(self):
+        try:
+            self.last_step_info = self._ctx.step_imex(self._step_options())
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+
+    def set_initial_conditions(self, initial_conditions):
+        super().set_initial_conditions(initial_conditions)
+        assert all(hasattr(self, x) for x in ("_velocities", "_intermediate_velocity",
+                                              "_pressure", "_old_pressure"))
+
+    @property
+    def solution(self):
+        """(velocity, pressure) at the new time level (split fields on the device)"""
+        return MixedFunction(self, nat.U0, nat.P, name="solution")

@@ -351,8 +351,11 @@ class InstationaryProblem(ProblemBase):
     def solve_problem(self):
         assert hasattr(self, "_InstationarySolverClass")
         self._call_hooks(("periodic", "constraints", "rotation", "bcs", "force", "coefficients", "initial"))
-        self._time_stepping = BDFTimeStepping(self._start_time, self._end_time,
-                                              desired_start_time_step=self._desired_start_time_step)
+        # the solver class names the time stepping it needs (default: BDF; IMEX classes add their IMEXType)
+        ts_class = getattr(self._InstationarySolverClass, "time_stepping_class", BDFTimeStepping)
+        ts_args = () if ts_class is BDFTimeStepping else (self._InstationarySolverClass.imex_type, )
+        self._time_stepping = ts_class(self._start_time, self._end_time, *ts_args,
+                                       desired_start_time_step=self._desired_start_time_step)
         if not hasattr(self, "_navier_stokes_solver"):
             self._navier_stokes_solver = self._InstationarySolverClass(
                 self._mesh, self._boundary_markers, self._form_convective_term,

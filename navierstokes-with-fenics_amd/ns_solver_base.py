@@ -554,11 +554,16 @@ class InstationarySolverBase(SolverBase):
         return o
 
     # -- state ------------------------------------------------------------------
+    def _n_time_levels(self):
+        """old time levels of the scheme (BDFTimeStepping: a method, IMEXTimeStepping: a property)"""
+        n = self._time_stepping.n_levels
+        return n() if callable(n) else n
+
     def _setup_function_spaces(self):
         super()._setup_function_spaces()
         levels = ((nat.U0, nat.P), (nat.U1, nat.P_OLD), (nat.U2, nat.P2_OLD))
         self._solutions = []
-        for i in range(self._time_stepping.n_levels() + 1):
+        for i in range(self._n_time_levels() + 1):
             name = i * "old" + (i > 0) * "_" + "solution"
             self._solutions.append(MixedFunction(self, *levels[i], name=name))
 
