@@ -334,6 +334,7 @@ extern "C" int nsfem_set_coeffs(nsfem_ctx* ctx, const double c[6]) {
   for (int i = 0; i < 6; ++i) ctx->coef[i] = c[i];
   ctx->L_dirty = true;
   ctx->imex_ops_dirty = true;
+  ctx->imex_lattice_agreed = -1;
   ctx->graph_epoch++;                  // (coefficients are baked into captured kernel arguments)
   API_END(ctx)
 }
@@ -353,6 +354,11 @@ static void set_velocity_cycle_symmetric(nsfem_ctx* c, bool symmetric) {
   } else {
     mg.pre_degree = c->mg_v_pre_saved;
     mg.degree = c->mg_v_degree_saved;
+  }
+  // (partitioned hierarchies: the replicated levels below the global coarse mesh run the same cycle)
+  if (mg.tail) {
+    mg.tail->degree = mg.degree;
+    mg.tail->pre_degree = mg.pre_degree;
   }
   c->mg_v_symmetric = symmetric;
   c->mg_v_dirty = true;
@@ -418,6 +424,7 @@ extern "C" int nsfem_set_viscous_form(nsfem_ctx* ctx, int traction_form) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
   ctx->traction_form = traction_form ? 1 : 0;
+  ctx->imex_lattice_agreed = -1;
   ctx->graph_epoch++;
   if (ctx->traction_form && !ctx->have_E) {
     ctx->E.init(&ctx->p22, ctx->mesh.dim, ctx->mesh.dim, ctx->stream);
@@ -485,6 +492,7 @@ extern "C" int nsfem_set_dirichlet(nsfem_ctx* ctx, int field, int32_t n, const i
                                     // updates keep the pointers: captured graphs stay valid)
   if (field == NSFEM_VELOCITY) {
     ctx->nbc_v = (int)d.size();
+    ctx->imex_lattice_agreed = -1;
     if (changed) {
       ctx->dinv_m_ready = false;
       ctx->mg_v_dirty = true;
@@ -523,6 +531,9 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   // IMEX: the stored convection vectors follow the velocity levels they were evaluated at
   if (slot == NSFEM_U1 || slot == NSFEM_CONV_N1) ctx->conv_n1_fresh = false;
   if (slot == NSFEM_U2) ctx->conv_n2_valid = false;
+  // ... and on partitioned meshes the ghost entries of a slot written from the host are whatever the caller put there
+  if (slot == NSFEM_U1) ctx->u1_ghost_fresh = false;
+  if (slot == NSFEM_U2) ctx->u2_ghost_fresh = false;
   if (slot == NSFEM_CONV_N2) { ctx->conv_n2_valid = true; ctx->conv_n_form = -2; }   // (the caller vouches for it)
   API_END(ctx)
 }
@@ -884,6 +895,15 @@ static int jacobian_path(nsfem_ctx* c) {
   return c->distributed() ? 0 : 1;
 }
 
+// ghost lattice lines of the P2 lattice of a strip (looked at once; -1: the ghost nodes are not whole lines)
+static void strip_ghost_lines(nsfem_ctx* c) {
+  if (c->p2_gh_lo != -2) return;
+  int lo, hi;
+  const bool lines = c->L.dict && ghost_lattice_lines(c->h_ghost_p2, c->L.dict->lat_w, c->L.dict->lat_h, lo, hi);
+  c->p2_gh_lo = lines ? lo : -1;
+  c->p2_gh_hi = lines ? hi : -1;
+}
+
 void nsfem_ctx::MomentumMF::apply(hipStream_t s, const double* x, double* y) {
   const int64_t nv = nvel(c);
   const int dim = c->mesh.dim;
@@ -905,12 +925,7 @@ void nsfem_ctx::MomentumMF::apply(hipStream_t s, const double* x, double* y) {
       // strips: the ghost lines of the input first -- under the tile rows that read none of them when the overlap
       // mode is on and the strip is high enough; the kernel writes zeros to the ghost rows
       if (c->distributed()) {
-        if (c->p2_gh_lo == -2) {
-          int lo, hi;
-          const bool lines = c->L.dict && ghost_lattice_lines(c->h_ghost_p2, c->L.dict->lat_w, c->L.dict->lat_h, lo, hi);
-          c->p2_gh_lo = lines ? lo : -1;
-          c->p2_gh_hi = lines ? hi : -1;
-        }
+        strip_ghost_lines(c);
         if (c->comm->overlap && c->p2_gh_lo >= 0 && jacobian_lattice_split(c->mesh, c->p2_gh_lo, c->p2_gh_hi)) {
           c->comm->exchange_begin(s, c->halo_p2, const_cast<double*>(x), dim);
           bool ok = launch_jacobian_lattice(s, c->mesh, c->L, c->state[vel_slot].p, x, cc, c->conv_form, c->picard,
@@ -2158,6 +2173,8 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
 // ---------------------------------------------------------------- IMEX pressure correction
 // the operators of the old levels in the right-hand side: L_i = alpha_i/k M + gamma_i c_v K, i = 1, 2 (built as
 // ensure_L builds L; they share its pattern and stencil dictionary)
+static void imex_build_ops(nsfem_ctx* c);
+static void imex_agree_on_lattice(nsfem_ctx* c);
 static void ensure_imex_ops(nsfem_ctx* c) {
   ensure_L(c);
   hipStream_t s = c->stream;
@@ -2165,12 +2182,18 @@ static void ensure_imex_ops(nsfem_ctx* c) {
     c->L1.init(&c->p22, 1, 1, s);
     c->L2.init(&c->p22, 1, 1, s);
     c->imex_ops_dirty = true;
+    c->imex_lattice_agreed = -1;
   }
   if (c->L1.dict != c->L.dict) {
     c->L1.dict = c->L2.dict = c->L.dict;
     c->imex_ops_dirty = true;
+    c->imex_lattice_agreed = -1;
   }
-  if (!c->imex_ops_dirty) return;
+  if (c->imex_ops_dirty) imex_build_ops(c);
+  imex_agree_on_lattice(c);
+}
+static void imex_build_ops(nsfem_ctx* c) {
+  hipStream_t s = c->stream;
   const double cv = c->coef[2];
   launch_scale_combine(s, c->p22.nnz, c->alpha[1] / c->k, c->M2.vals.p, c->imex_gamma[1] * cv, c->K2.vals.p, c->L1.vals.p);
   launch_scale_combine(s, c->p22.nnz, c->alpha[2] / c->k, c->M2.vals.p, c->imex_gamma[2] * cv, c->K2.vals.p, c->L2.vals.p);
@@ -2196,26 +2219,97 @@ static void imex_begin_step(nsfem_ctx* c) {
     launch_axpby(s, nv, 1.0, c->gconst.p, 1.0, c->state[NSFEM_TRACTION].p, c->gconst.p);
 }
 
+// does the one-launch right-hand side apply?  (uniform lattices only: graded ones keep the generic path.)  On a
+// partitioned mesh the answer must be the same on every rank -- the two paths are different collective sequences when
+// the overlap mode is on, and nsfem_imex_rhs(path 2) must fail everywhere or nowhere --, so the ranks' own answers
+// are reduced ONCE (minimum), when the operators are built or something the answer depends on was set, and kept
+static bool imex_lattice_local(nsfem_ctx* c) {
+  return jacobian_path(c) == 2 && imex_rhs_lattice_available(c->mesh, c->L1, c->L2);
+}
+static void imex_agree_on_lattice(nsfem_ctx* c) {
+  if (!c->distributed() || c->imex_lattice_agreed >= 0) return;
+  hipStream_t s = c->stream;
+  c->kw.ensure(nvel(c));
+  double* parts = c->kw.parts.p + (size_t)P10 * kParts;
+  double no = imex_lattice_local(c) ? 0.0 : 1.0;
+  NSFEM_HIP(hipMemcpyAsync(parts, &no, sizeof(double), hipMemcpyHostToDevice, s));
+  c->comm->allreduce_max(s, parts, 1);
+  NSFEM_HIP(hipMemcpyAsync(&no, parts, sizeof(double), hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  c->imex_lattice_agreed = no == 0.0 ? 1 : 0;
+}
 static bool imex_lattice_ok(nsfem_ctx* c) {
-  // (uniform lattices only: graded ones keep the generic path)
-  return jacobian_path(c) == 2 && c->L.dict && c->L.dict->exact && jacobian_lattice_variant(c->mesh) == 2;
+  return c->distributed() ? c->imex_lattice_agreed == 1 : imex_lattice_local(c);
+}
+
+// partitioned meshes: the right-hand side reads the ghost entries of u1 and u2.  After a step they are copies of the
+// owners' values to round-off only, so u1 is exchanged before every right-hand side.  u2 is the u1 of the step before
+// (nsfem_advance rotates the pointers): its ghosts are the bit copies that exchange left, unless the slot was written
+// since (nsfem_set_state, the first step) -- then both levels travel in ONE message of 2 dim values per node, before
+// anything reads them.  true: u1 has travelled
+static bool imex_exchange_stale_levels(nsfem_ctx* c) {
+  if (!c->distributed() || c->u2_ghost_fresh) return false;
+  hipStream_t s = c->stream;
+  const int dim = c->mesh.dim;
+  const int64_t n = c->mesh.n_p2;
+  if (!c->imex_pack.p) c->imex_pack.alloc((size_t)(2 * nvel(c)));
+  double *u1 = c->state[NSFEM_U1].p, *u2 = c->state[NSFEM_U2].p;
+  launch_halo_pack2(s, n, c->halo_p2, dim, u1, u2, c->imex_pack.p);
+  c->comm->exchange(s, c->halo_p2, c->imex_pack.p, 2 * dim);
+  launch_halo_unpack2(s, n, c->halo_p2, dim, c->imex_pack.p, u1, u2);
+  c->u1_ghost_fresh = c->u2_ghost_fresh = true;
+  return true;
 }
 
 // rhs = -[ L1 u1 + L2 u2 (+ c_v E (g1 u1 + g2 u2)) + g + (b0 n1 + b1 n2) ],  n1 = c_c conv(u1) -> `n1`;
 // n2 (null: not read, b1 = 0) = c_c conv(u2).  path: 0 the one-launch kernel where it applies, 1 generic, 2 one-launch
 // or error.  The generic sequence below DEFINES the summation order; k_jac_lattice<FORM, 3> reproduces it.
-static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double* rhs) {
+// Partitioned meshes: ONE halo exchange (u1; `u1_travelled`: imex_exchange_stale_levels has sent it with u2), rows of
+// ghost nodes come out as zeros in rhs and n1 on both paths, the arithmetic on owned rows is the single context's.
+static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double* rhs, bool u1_travelled = false) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c);
   const double cc = cc_of(c);
-  const double *u1 = c->state[NSFEM_U1].p, *u2 = c->state[NSFEM_U2].p;
+  double* u1 = c->state[NSFEM_U1].p;
+  const double* u2 = c->state[NSFEM_U2].p;
   const double b0 = c->imex_beta[0], b1 = c->imex_beta[1];
-  if (path != 1 && imex_lattice_ok(c) &&
-      launch_imex_rhs_lattice(s, c->mesh, c->L1, c->L2, u1, u2, c->gconst.p, cc, c->conv_form, b0, b1, n2, n1, rhs))
-    return 2;
-  NSFEM_REQUIRE(path != 2, "one-launch IMEX right-hand side: not available on this mesh / these settings");
   const int dim = c->mesh.dim;
-  launch_spmv(s, c->L1, dim, u1, rhs, nullptr, MASK_NONE);
+  const bool dist = c->distributed();
+  bool need_u1 = dist && !u1_travelled;
+  if (path != 1 && imex_lattice_ok(c)) {
+    const uint8_t* gm = dist ? c->mask_v.p : nullptr;
+    auto launch = [&](int phase) {
+      return launch_imex_rhs_lattice(s, c->mesh, c->L1, c->L2, u1, u2, c->gconst.p, cc, c->conv_form, b0, b1, n2, n1,
+                                     rhs, gm, phase, c->p2_gh_lo, c->p2_gh_hi);
+    };
+    if (need_u1) {
+      // the tile rows that read no ghost line run under the exchange when the overlap mode is on and the strip is
+      // high enough (as the Jacobian action, MomentumMF::apply)
+      strip_ghost_lines(c);
+      need_u1 = false;
+      c->u1_ghost_fresh = true;
+      if (c->comm->overlap && c->p2_gh_lo >= 0 && jacobian_lattice_split(c->mesh, c->p2_gh_lo, c->p2_gh_hi)) {
+        c->comm->exchange_begin(s, c->halo_p2, u1, dim);
+        bool ok = launch(1);
+        c->comm->exchange_end(s);
+        ok = ok && launch(2);
+        NSFEM_REQUIRE(ok, "one-launch IMEX right-hand side: tile-row split failed");
+        return 2;
+      }
+      c->comm->exchange(s, c->halo_p2, u1, dim);
+    }
+    if (launch(0)) return 2;
+    // (the ranks agreed on this path: falling back here would leave them in different collective sequences)
+    NSFEM_REQUIRE(!dist, "one-launch IMEX right-hand side: launch failed on a rank of a partitioned mesh");
+  }
+  NSFEM_REQUIRE(path != 2, "one-launch IMEX right-hand side: not available on this mesh / these settings");
+  if (need_u1) {
+    product_with_halo(c->comm, &c->halo_p2, dim, s, u1, c->L1.pat,
+                      [&](int phase) { launch_spmv(s, c->L1, dim, u1, rhs, nullptr, MASK_NONE, 0, phase); });
+    c->u1_ghost_fresh = true;
+  } else {
+    launch_spmv(s, c->L1, dim, u1, rhs, nullptr, MASK_NONE);
+  }
   launch_spmv(s, c->L2, dim, u2, c->tmp_v.p, nullptr, MASK_NONE);
   launch_axpby(s, nv, 1.0, rhs, 1.0, c->tmp_v.p, rhs);
   if (c->traction_form) {
@@ -2226,12 +2320,15 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
   NSFEM_HIP(hipMemsetAsync(n1, 0, sizeof(double) * nv, s));
   if (cc != 0.0) launch_convection_residual(s, c->mesh, u1, cc, n1, c->conv_form);
   launch_imex_combine(s, nv, rhs, n1, n2, b0, b1, rhs);
+  if (dist && c->ghost_v.p) {
+    launch_zero_ghost(s, nv, c->mask_v.p, rhs);
+    launch_zero_ghost(s, nv, c->mask_v.p, n1);
+  }
   return 1;
 }
 
 static void imex_require_supported(nsfem_ctx* c) {
   NSFEM_REQUIRE(c->imex_active, "nsfem_set_imex has not been called");
-  NSFEM_REQUIRE(!c->distributed(), "IMEX pressure correction: partitioned meshes are not supported");
   const bool euler = c->mesh.dim == 2 ? c->omega_dot != 0.0
                                       : (c->omega_dot3[0] != 0.0 || c->omega_dot3[1] != 0.0 || c->omega_dot3[2] != 0.0);
   NSFEM_REQUIRE(!coriolis_active(c) && !euler,
@@ -2257,6 +2354,7 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   // ---- diffusion step: one linear solve
   ensure_imex_ops(ctx);
   imex_begin_step(ctx);
+  const bool u1_travelled = imex_exchange_stale_levels(ctx);
   const double* n2 = nullptr;
   if (ctx->imex_beta[1] != 0.0) {
     // c_c N(u2): what the previous step stored, unless the level, the form or the coefficient changed under it
@@ -2266,11 +2364,12 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
       ctx->state[NSFEM_CONV_N2].zero(s);
       if (cc != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc, ctx->state[NSFEM_CONV_N2].p,
                                                 ctx->conv_form);
+      if (ctx->distributed() && ctx->ghost_v.p) launch_zero_ghost(s, nv, ctx->mask_v.p, ctx->state[NSFEM_CONV_N2].p);
       ctx->conv_n2_valid = true;
     }
     n2 = ctx->state[NSFEM_CONV_N2].p;
   }
-  ctx->imex_last_path = imex_rhs(ctx, 0, n2, ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
+  ctx->imex_last_path = imex_rhs(ctx, 0, n2, ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p, u1_travelled);
   ++(ctx->imex_last_path == 2 ? ctx->imex_lattice_rhs : ctx->imex_generic_rhs);
   ctx->conv_n1_fresh = true;
   ctx->conv_n_form = ctx->conv_form;
@@ -2279,6 +2378,9 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     // Dirichlet rows u*_i = g_i; start vector u1 with the Dirichlet values
     double* x = ctx->state[NSFEM_USTAR].p;
     launch_set_values(s, ctx->nbc_v, ctx->bc_v_dofs.p, ctx->bc_v_vals.p, ctx->rhs_v.p);
+    // (partitioned: Dirichlet dofs on ghost nodes belong to their owners -- ghost rows stay out of the dot products;
+    // the ghost entries of the start vector are those of u1, exchanged for the right-hand side)
+    if (ctx->distributed() && ctx->ghost_v.p) launch_zero_ghost(s, nv, ctx->mask_v.p, ctx->rhs_v.p);
     NSFEM_HIP(hipMemcpyAsync(x, ctx->state[NSFEM_U1].p, sizeof(double) * nv, hipMemcpyDeviceToDevice, s));
     launch_set_values(s, ctx->nbc_v, ctx->bc_v_dofs.p, ctx->bc_v_vals.p, x);
     LinOp op;
@@ -2371,12 +2473,16 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
   ctx->kw.ensure(nv);
   ++ctx->kw.touch;
   double *n1 = ctx->kw.p.p, *n2 = nullptr, *out = ctx->kw.q.p;
+  // (every rank fails here or none: the path was agreed on when the operators were built)
+  NSFEM_REQUIRE(path != 2 || imex_lattice_ok(ctx),
+                "one-launch IMEX right-hand side: not available on this mesh / these settings");
+  const bool u1_travelled = imex_exchange_stale_levels(ctx);
   if (ctx->imex_beta[1] != 0.0) {
     n2 = ctx->kw.z.p;
     NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nv, s));
     if (cc_of(ctx) != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form);
   }
-  imex_rhs(ctx, path, n2, n1, out);
+  imex_rhs(ctx, path, n2, n1, out, u1_travelled);
   NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
@@ -2538,6 +2644,9 @@ extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
   std::swap(ctx->state[NSFEM_U2].p, ctx->state[NSFEM_U1].p);
   NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_U1].p, ctx->state[NSFEM_U0].p,
                            sizeof(double) * nvel(ctx), hipMemcpyDeviceToDevice, s));
+  // (partitioned IMEX steps: the ghost entries travel with the rotation; those of u0 are copies to round-off only)
+  ctx->u2_ghost_fresh = ctx->u1_ghost_fresh;
+  ctx->u1_ghost_fresh = false;
   if (scheme == 0) {
     // (p_(n-1) is kept for the optional extrapolated start vector of the projection step)
     std::swap(ctx->state[NSFEM_P2_OLD].p, ctx->state[NSFEM_P_OLD].p);

@@ -844,6 +844,10 @@ void launch_imex_combine(hipStream_t s, int64_t n, const double* t, const double
 // value tables of the shared dictionary and adds them and g; phase 2 is the residual's element kernel on u1; the
 // gather sums the node's element vectors from +0.0 on -- c_c conv(u1), stored to ix.n1 -- and writes
 // imex_rhs_value(...) with the stored ix.n2: the generic sequence of nsfem_step_imex, bit for bit.
+// LIN = 4: LIN 3 on the strip of a partitioned mesh (the rank's own lattice: own cell rows + the ghost row).  The row
+// mask is read as in the Jacobian action; on the rows of ghost nodes (mask value 2) the partial sums are dropped and
+// BOTH outputs are written as +0.0 -- the right-hand side and the stored c_c conv(u1) (no owned row ever reads the
+// latter: n2 is read row-wise).  Owned rows: the arithmetic and summation order of LIN 3, untouched.
 struct TabGrad {
   const double* __restrict__ t;   // [7][6][2] gradients, then [7] weights of one cell type (wave-uniform address)
   __device__ __forceinline__ void grad(int q, int k, double& gx, double& gy) const {
@@ -886,7 +890,8 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   // set by the caller afterwards); g joins the node's sum after the L product and before the element vectors,
   // the order of the launches it replaces (product, axpby, k_conv_cell, k_res_gather).
   // ugeo: V 0, 1 the two types' geometry [2][5] (uniform lattices; null: load_geo per cell), V 2 the gradient tables
-  constexpr bool IMX = LIN == 3;
+  constexpr bool IMX = LIN == 3 || LIN == 4;
+  constexpr bool GH = LIN == 4;                                     // ghost rows of a strip -> 0
   constexpr bool RES = LIN == 0 || IMX;
   constexpr bool TWO = LIN != 0;                                    // a second staged vector (x, or u2)
   constexpr int CLIN = IMX ? 0 : LIN;                               // mode of the element kernel
@@ -977,7 +982,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       oent[r] = sid8[onode[r]];
       if (RES) og[r] = reinterpret_cast<const double2*>(gadd)[onode[r]];
       if (IMX) on2[r] = ix.n2 ? reinterpret_cast<const double2*>(ix.n2)[onode[r]] : make_double2(0.0, 0.0);
-      if (!RES) omask[r] = reinterpret_cast<const uint16_t*>(mask)[onode[r]];
+      if (!RES || GH) omask[r] = reinterpret_cast<const uint16_t*>(mask)[onode[r]];
     }
   }
   for (int t = tid; t < a.n_st * a.lp; t += NT) {
@@ -1111,10 +1116,16 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       }
       double2 v = make_double2(vx_, vy_);
       if constexpr (IMX) {
+        if constexpr (GH) {
+          if (omask[r] & 0x0002) v = make_double2(0.0, 0.0);        // (ghost node: both components carry the flag)
+        }
         reinterpret_cast<double2*>(ix.n1)[onode[r]] = v;
         const bool have = ix.n2 != nullptr;
         v.x = imex_rhs_value(a0.x, vx_, on2[r].x, ix.b0, ix.b1, have);
         v.y = imex_rhs_value(a0.y, vy_, on2[r].y, ix.b0, ix.b1, have);
+        if constexpr (GH) {
+          if (omask[r] & 0x0002) v = make_double2(0.0, 0.0);
+        }
       }
       if (!RES) {
         if (omask[r] & 0x00ff) v.x = a0.x;
@@ -1343,7 +1354,8 @@ int64_t jacobian_lattice_bytes(const MeshDev& m) {
   return (int64_t)m.n_p2 * (3 * 16 + 1 + 2) + ((g_jac_uniform_geo && m.cl.geo_uniform) ? 0 : (int64_t)m.n_cells * 48);
 }
 
-// lin: 0 residual (x, mask unused; gadd = g), 1 Newton action, 2 Picard action, 3 IMEX right-hand side (ix; L = L1)
+// lin: 0 residual (x, mask unused; gadd = g), 1 Newton action, 2 Picard action, 3 IMEX right-hand side (ix; L = L1),
+// 4 the same on a partitioned strip (mask: ghost rows -> 0)
 // phase 0: every tile; 1: the tile rows that read no lattice line below `safe_lo` or from `safe_hi` on (the interior of
 // a partitioned strip, launched under the halo exchange); 2: the other tile rows.  jacobian_lattice_split tells
 // whether phases 1 / 2 exist for the given ghost lines
@@ -1420,8 +1432,8 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
     for (int h = 0; h < 3; ++h) a.gl[c][h] = packed[2 * h] | (packed[2 * h + 1] << 16);
   }
   const int var = jacobian_lattice_variant(m);
-  if (lin == 3 && var != 2) return false;           // (the right-hand-side mode: uniform lattices, gradient tables)
-  const size_t lds = jac_lattice_lds(d, lin == 3);
+  if (lin >= 3 && var != 2) return false;           // (the right-hand-side mode: uniform lattices, gradient tables)
+  const size_t lds = jac_lattice_lds(d, lin >= 3);
   const int grid = ((a.ntiles + 7) / 8) * 8;
 #define NSFEM_JL_V(F, LIN, SX, SY, V)                                                                       \
   do {                                                                                                      \
@@ -1467,7 +1479,7 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
   if (lin == 0) { NSFEM_JL_F(0) } else if (lin == 2) { NSFEM_JL_F(2) } else if (lin == 1) { NSFEM_JL_F(1) }
 #undef NSFEM_JL_T
 #define NSFEM_JL_T(F, LIN, SX, SY) NSFEM_JL_V(F, LIN, SX, SY, 2)
-  if (lin == 3) { NSFEM_JL_F(3) }
+  if (lin == 3) { NSFEM_JL_F(3) } else if (lin == 4) { NSFEM_JL_F(4) }
 #undef NSFEM_JL_F
 #undef NSFEM_JL_T
 #undef NSFEM_JL_V
@@ -1492,9 +1504,17 @@ bool launch_residual_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L,
 
 // rhs = -((L1 u1 + L2 u2 + g) + (b0 n1 + b1 n2)) with n1 = c_c conv(u1) stored: the right-hand side of the IMEX
 // diffusion step before its Dirichlet rows are set.  Only on dictionaries that equal the assembled matrices bit for bit
+// ghostmask (partitioned strips): the row mask whose value 2 flags the ghost rows -- both outputs are 0 there; phase,
+// gh_lo, gh_hi: the tile-row split of launch_jacobian_lattice
+bool imex_rhs_lattice_available(const MeshDev& m, const BlockMat& L1, const BlockMat& L2) {
+  if (!L1.dict || !L1.dict->exact || L2.dict != L1.dict || !L1.dict_ready || !L2.dict_ready) return false;
+  return jacobian_lattice_available(m, L1) && jacobian_lattice_variant(m) == 2 &&
+         jac_lattice_lds(*L1.dict, true) <= (size_t)96 * 1024;
+}
 bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
                              const double* u2, const double* g, double cc, int form, double b0, double b1,
-                             const double* n2, double* n1, double* rhs) {
+                             const double* n2, double* n1, double* rhs, const uint8_t* ghostmask, int phase, int gh_lo,
+                             int gh_hi) {
   if (!L1.dict || !L1.dict->exact || L2.dict != L1.dict || !L1.dict_ready || !L2.dict_ready || !g || !n1) return false;
   ImexLatArgs ix;
   ix.u2 = u2;
@@ -1503,7 +1523,8 @@ bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1
   ix.n1 = n1;
   ix.b0 = b0;
   ix.b1 = b1;
-  return launch_lattice_cells(s, m, L1, u1, u1, cc, form, 3, nullptr, g, rhs, 0, 0, 0, &ix);
+  return launch_lattice_cells(s, m, L1, u1, u1, cc, form, ghostmask ? 4 : 3, ghostmask, g, rhs, phase, gh_lo, gh_hi,
+                              &ix);
 }
 
 }  // namespace nsfem

@@ -101,6 +101,54 @@ static void move_idx(hipStream_t s, int64_t n, int width, const double* src, con
   NSFEM_HIP(hipGetLastError());
 }
 
+// packed exchange of two vectors: node i of the ranges / lists below <-> buf[i][2 width] = (a[i][:], b[i][:]).
+// dir 0: a, b -> buf (the nodes this rank sends), 1: buf -> a, b (its ghost nodes).  idx null: the node range
+// [off0, off0 + cnt0) followed by [off1, off1 + cnt1)
+__global__ __launch_bounds__(256) void k_halo_pack2(int64_t n_nodes, int64_t off0, int64_t cnt0, int64_t off1, int64_t cnt1,
+                                                    const int32_t* __restrict__ idx, int width, int dir,
+                                                    double* __restrict__ a, double* __restrict__ b,
+                                                    double* __restrict__ buf) {
+  const int64_t total = (cnt0 + cnt1) * width;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t k = t / width;
+    const int c = (int)(t - k * width);
+    const int64_t node = idx ? (int64_t)idx[k] : (k < cnt0 ? off0 + k : off1 + (k - cnt0));
+    if (node < 0 || node >= n_nodes) continue;
+    double* pa = a + node * width + c;
+    double* pb = b + node * width + c;
+    double* q = buf + node * 2 * width + c;
+    if (dir == 0) { q[0] = *pa; q[width] = *pb; }
+    else { *pa = q[0]; *pb = q[width]; }
+  }
+}
+static void halo_pack2(hipStream_t s, int64_t n_nodes, const HaloRange& h, int width, int dir, double* a, double* b,
+                       double* buf) {
+  int64_t off0, cnt0, off1 = 0, cnt1 = 0;
+  const int32_t* idx = nullptr;
+  if (h.lists) {
+    off0 = 0;
+    cnt0 = dir == 0 ? h.lists->n_send() : h.lists->n_recv();
+    idx = dir == 0 ? h.lists->send_idx.p : h.lists->recv_idx.p;
+  } else if (dir == 0) {
+    off0 = h.send_up_off; cnt0 = h.send_up_cnt; off1 = h.send_down_off; cnt1 = h.send_down_cnt;
+  } else {
+    off0 = h.recv_above_off; cnt0 = h.recv_above_cnt; off1 = h.recv_below_off; cnt1 = h.recv_below_cnt;
+  }
+  const int64_t total = (cnt0 + cnt1) * width;
+  if (total <= 0) return;
+  const int grid = (int)std::min<int64_t>((total + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_halo_pack2, dim3(grid), dim3(256), 0, s, n_nodes, off0, cnt0, off1, cnt1, idx, width, dir, a, b, buf);
+  NSFEM_HIP(hipGetLastError());
+}
+void launch_halo_pack2(hipStream_t s, int64_t n_nodes, const HaloRange& h, int width, const double* a, const double* b,
+                       double* buf) {
+  halo_pack2(s, n_nodes, h, width, 0, const_cast<double*>(a), const_cast<double*>(b), buf);
+}
+void launch_halo_unpack2(hipStream_t s, int64_t n_nodes, const HaloRange& h, int width, const double* buf, double* a,
+                         double* b) {
+  halo_pack2(s, n_nodes, h, width, 1, a, b, const_cast<double*>(buf));
+}
+
 struct LocalComm : Comm {
   LocalGroup* g = nullptr;
   DevBuf<double> scratch;

@@ -424,7 +424,8 @@ bool launch_jacobian_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L,
 // and n1 is stored.  launch_imex_rhs_lattice: ONE launch of k_jac_lattice<FORM, 3> on 2D lattice meshes whose
 // dictionary equals the assembled matrices bit for bit (false = not available, nothing launched); it reproduces the
 // generic sequence -- launch_spmv (L1, L2), launch_axpby twice, launch_convection_residual, launch_imex_combine --
-// bit for bit.  L1, L2 share L's pattern and dictionary.
+// bit for bit.  L1, L2 share L's pattern and dictionary.  ghostmask set (the strip of a partitioned mesh, after the
+// ghost lines of u1 and u2 were exchanged): k_jac_lattice<FORM, 4>, rows of ghost nodes get rhs = 0 and n1 = 0.
 struct ImexLatArgs {
   const double* u2 = nullptr;      // velocity at t_(n-1)
   const double* sval2 = nullptr;   // dictionary values of L2
@@ -434,7 +435,11 @@ struct ImexLatArgs {
 };
 bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
                              const double* u2, const double* g, double cc, int form, double b0, double b1,
-                             const double* n2, double* n1, double* rhs);
+                             const double* n2, double* n1, double* rhs, const uint8_t* ghostmask = nullptr,
+                             int phase = 0, int gh_lo = 0, int gh_hi = 0);
+// every precondition of launch_imex_rhs_lattice that depends on the mesh and the operators (the ranks of a partitioned
+// run agree on the path once, from this)
+bool imex_rhs_lattice_available(const MeshDev& m, const BlockMat& L1, const BlockMat& L2);
 void launch_imex_combine(hipStream_t s, int64_t n, const double* t, const double* n1, const double* n2, double b0,
                          double b1, double* rhs);
 // partitioned strips: can the launch be cut into tile rows that read no ghost line (phase 1, under the halo
@@ -621,6 +626,12 @@ struct Comm {
   }
 };
 void launch_zero_ghost(hipStream_t s, int64_t n, const uint8_t* mask, double* x);  // x[mask==2]=0
+// packed halo exchange of two vectors (width entries per node each): a, b -> buf[node][2 width] on the nodes this rank
+// sends, and buf -> a, b on its ghost nodes.  One message of width 2 * width instead of two
+void launch_halo_pack2(hipStream_t s, int64_t n_nodes, const HaloRange& h, int width, const double* a, const double* b,
+                       double* buf);
+void launch_halo_unpack2(hipStream_t s, int64_t n_nodes, const HaloRange& h, int width, const double* buf, double* a,
+                         double* b);
 
 // product with a halo-dependent input: exchange, then launch(0) -- or, when the communicator
 // overlaps and the pattern has interior row blocks, exchange on the communicator's stream under
@@ -990,6 +1001,11 @@ struct nsfem_ctx {
   nsfem::BlockMat L1, L2;
   bool imex_ops_dirty = true;
   bool conv_n2_valid = false, conv_n1_fresh = false;   // N2 holds c_c N(u2) / N1 was written since the last advance
+  // partitioned meshes: the ghost entries of the slot are bit copies of the owners' values (exchanged by an IMEX
+  // right-hand side and not written since) -- kept next to the flags above, nsfem_advance rotates them with the slots
+  bool u1_ghost_fresh = false, u2_ghost_fresh = false;
+  nsfem::DevBuf<double> imex_pack;                     // [n_p2][2 dim]: u1 and u2 in one halo message
+  int imex_lattice_agreed = -1;                        // the ranks' common answer to "one-launch right-hand side?" (-1: not asked)
   int conv_n_form = -1;                                // convective form and coefficient the stored vectors belong to
   double conv_n_cc = 0.0;
   // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the

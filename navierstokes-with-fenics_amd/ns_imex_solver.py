@@ -19,8 +19,14 @@ N(u2) is not recomputed: the device keeps N(u1) of a step for the next one.  On 
 with exact stencil dictionaries the whole right-hand side of step 1 is one kernel launch.
 
 The scheme is conditionally stable (a CFL-type restriction on k, reported by the problem classes'
-CFL diagnostic).  Rotating frames (Coriolis / Euler terms) and partitioned meshes are refused with
-an error by the device driver; 3D meshes run through the generic right-hand-side path.
+CFL diagnostic).  Rotating frames (Coriolis / Euler terms) are refused with an error by the device
+driver; 3D meshes run through the generic right-hand-side path.
+
+Partitioned meshes (a context with a communicator, ``partition.py``'s ``attach``): the step runs on
+strips, slabs and recursive-bisection partitions.  Its right-hand side costs one halo exchange (u1;
+u2 travels with it in one packed message only when its slot was written since the last step); on
+uniform strips it stays one kernel launch, which writes zeros to the rows of ghost nodes.  The ranks
+agree once on the right-hand-side path, so every rank runs the same sequence of collectives.
 """
 import _native as nat
 from fem_function import DeviceFunction, MixedFunction
