@@ -472,6 +472,30 @@ int nsfem_boundary_force(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, i
                          const int32_t* facet_cell, const int32_t* facet_local, double nu,
                          double sym, double* out);
 
+/* ---- volume functionals of the solution: replaces dolfin.assemble(... * dx) / dolfin.norm / dolfin.errornorm of a
+ * driver's post-processing (kinetic energy and enstrophy of the Taylor-Green runs, |div u| after a projection step,
+ * convergence_test/taylor_green_vortex.py:118-119).  With (v, q) = (u, p) of the two slots, or (u - ref_velocity,
+ * p - ref_pressure) where a reference field is given (host vectors in the layout of the slots, the difference is
+ * formed node by node on the device), out holds the integrals over the cells whose flag is nonzero (NULL: all cells):
+ *   out[0] = int 1              out[1] = int v.v            out[2] = int grad v : grad v
+ *   out[3] = int |curl v|^2     (2D: scalar curl)           out[4] = int (div v)^2
+ *   out[5..7] = int v_x, v_y, v_z   (out[7] = +0.0 in 2D)
+ *   out[8] = int q              out[9] = int q^2            out[10] = int |grad q|^2
+ * Degree-5 quadrature (7 points / 15-point Keast rule): exact up to rounding on affine cells.  One thread per cell,
+ * no atomics, every partial sum folded in a fixed order: two calls on the same state return the same bytes.  The call
+ * writes no state slot.  The reference fields and the flags are kept in buffers of the context; the flags are
+ * uploaded again only when their CONTENTS differ from the resident copy.
+ * Contexts with a communicator: the ghost entries are taken from their owners (halo exchange of copies of the two
+ * slots), then ONE all-reduce (sum) of the 11 values follows; every rank calls, and the flags must select each
+ * global cell on exactly one rank (partition.py: owned_cell_flags()).
+ * NSFEM_ERR_ARG: velocity_slot / pressure_slot not a velocity / pressure slot. */
+#define NSFEM_N_FUNCTIONALS 11
+int nsfem_volume_functionals(nsfem_ctx* ctx, int velocity_slot, int pressure_slot,
+                             const double* ref_velocity /* host, dim*n_p2, or NULL */,
+                             const double* ref_pressure /* host, n_p1, or NULL */,
+                             const uint8_t* cell_flags  /* host, n_cells, or NULL = all cells */,
+                             double out[NSFEM_N_FUNCTIONALS]);
+
 /* ---- measurement hooks (bench.py): time `reps` launches of the dominant SpMV
  * with HIP events on the context's stream; ms per launch returned ------------- */
 /* in-situ HIP-event timing of the finest-level smoothing launches of the velocity multigrid

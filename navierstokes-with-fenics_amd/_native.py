@@ -22,6 +22,7 @@ VELOCITY, PRESSURE, PRESSURE_PRECOND = 0, 1, 2
  OP_CONVECTION_ACTION) = range(12)
 SYS_MOMENTUM, SYS_POISSON, SYS_CORRECTION, SYS_MONOLITHIC = range(4)
 MAX_NEWTON = 64
+N_FUNCTIONALS = 11          # NSFEM_N_FUNCTIONALS
 
 EXPORTED_SYMBOLS = (
     "nsfem_create", "nsfem_destroy", "nsfem_last_error", "nsfem_version",
@@ -41,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_set_fast_diag_3d_planes", "nsfem_poisson_fast_diag_3d_info",
     "nsfem_operator_diagonal",
     "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
+    "nsfem_volume_functionals",
 )
 
 
@@ -199,6 +201,7 @@ def load_library(path=None):
         "nsfem_mg_set_halo_mode": (C.c_int, [vp, C.c_int]),
         "nsfem_set_overlap": (C.c_int, [vp, C.c_int]),
         "nsfem_boundary_force": (C.c_int, [vp, C.c_int, C.c_int, i32, pi, pi, dbl, dbl, pd]),
+        "nsfem_volume_functionals": (C.c_int, [vp, C.c_int, C.c_int, pd, pd, C.POINTER(C.c_uint8), pd]),
         "nsfem_comm_overlapped": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
         "nsfem_poisson_solve": (C.c_int, [vp, pd, i64, pi, pd, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_profile_smoother": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
@@ -293,6 +296,7 @@ class NsfemContext:
         assert cells.shape == (p2.shape[0], dim + 1) and p1.shape == cells.shape
         assert p2.shape[1] == (6 if dim == 2 else 10)
         self.dim = dim
+        self.n_cells = int(cells.shape[0])
         desc = MeshDesc(dim, cells.shape[0], coords.shape[0], int(n_p2), int(n_p1),
                         _dp(coords), _ip(cells), _ip(p2), _ip(p1))
         rc = self._lib.nsfem_create(C.byref(desc), int(device), C.byref(self._h))
@@ -814,6 +818,35 @@ class NsfemContext:
                                                    fc.size, _ip(fc), _ip(fl), float(nu),
                                                    float(symmetric), _dp(out)))
         return out[:self.dim].copy(), float(out[self.dim]), float(out[self.dim + 1])
+
+    def volume_functionals(self, velocity_slot=U0, pressure_slot=P, ref_velocity=None, ref_pressure=None,
+                           cell_flags=None):
+        """integrals over the cells with a nonzero flag (None: all cells) of (v, q) = (u, p) of the two slots, or of
+        (u - ref_velocity, p - ref_pressure) where a reference (host vector in the slot's layout) is given: dict of
+        measure, u_l2_sq = int v.v, grad_u_l2_sq = int grad v : grad v, curl_l2_sq, div_l2_sq, momentum [dim] = int v,
+        p_integral, p_l2_sq, grad_p_l2_sq, and values = the N_FUNCTIONALS doubles as returned.  One device call; on
+        contexts with a communicator every rank calls and receives the global sums."""
+        ru = rp = fl = None
+        if ref_velocity is not None:
+            ru = np.ascontiguousarray(ref_velocity, dtype=np.float64)
+            if ru.shape != (self.n_velocity, ):
+                raise ValueError("ref_velocity: expected %d values, got shape %s" % (self.n_velocity, ru.shape))
+        if ref_pressure is not None:
+            rp = np.ascontiguousarray(ref_pressure, dtype=np.float64)
+            if rp.shape != (self.n_p1, ):
+                raise ValueError("ref_pressure: expected %d values, got shape %s" % (self.n_p1, rp.shape))
+        if cell_flags is not None:
+            fl = np.ascontiguousarray(np.asarray(cell_flags) != 0, dtype=np.uint8)
+            if fl.shape != (self.n_cells, ):
+                raise ValueError("cell_flags: expected %d flags, got shape %s" % (self.n_cells, fl.shape))
+        out = np.zeros(N_FUNCTIONALS)
+        self._check(self._lib.nsfem_volume_functionals(
+            self._h, int(velocity_slot), int(pressure_slot), None if ru is None else _dp(ru),
+            None if rp is None else _dp(rp), None if fl is None else fl.ctypes.data_as(C.POINTER(C.c_uint8)),
+            _dp(out)))
+        return dict(measure=float(out[0]), u_l2_sq=float(out[1]), grad_u_l2_sq=float(out[2]),
+                    curl_l2_sq=float(out[3]), div_l2_sq=float(out[4]), momentum=out[5:5 + self.dim].copy(),
+                    p_integral=float(out[8]), p_l2_sq=float(out[9]), grad_p_l2_sq=float(out[10]), values=out)
 
     def cfl_number(self, slot, step_size):
         out = C.c_double()

@@ -248,6 +248,7 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   fill_quad_tables(qt);
   upload_quad_tables(qt);
   if (dim == 3) upload_quad_tables_3d();
+  upload_functional_tables(dim);
   fresh->M2.init(&fresh->p22, 1, 1, s);
   fresh->K2.init(&fresh->p22, 1, 1, s);
   fresh->L.init(&fresh->p22, 1, 1, s);
@@ -2867,6 +2868,64 @@ extern "C" int nsfem_boundary_force(nsfem_ctx* ctx, int velocity_slot, int press
   NSFEM_HIP(hipStreamSynchronize(s));
   for (int32_t f = 0; f < n_facets; ++f)
     for (int k = 0; k < w; ++k) out[k] += h[(size_t)f * w + k];
+  API_END(ctx)
+}
+
+// Volume integrals of the discrete solution or of its difference to a reference field (csrc/functionals.hip): one
+// thread per cell, one partial per workgroup and quantity, folded on the device in a fixed order.  Reads the two
+// slots, writes no state.
+extern "C" int nsfem_volume_functionals(nsfem_ctx* ctx, int velocity_slot, int pressure_slot,
+                                        const double* ref_velocity, const double* ref_pressure,
+                                        const uint8_t* cell_flags, double out[NSFEM_N_FUNCTIONALS]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  NSFEM_REQUIRE(velocity_slot >= 0 && velocity_slot < NSFEM_N_SLOTS && slot_size(ctx, velocity_slot) == nvel(ctx),
+                "not a velocity slot");
+  NSFEM_REQUIRE(pressure_slot >= 0 && pressure_slot < NSFEM_N_SLOTS && slot_size(ctx, pressure_slot) == npre(ctx),
+                "not a pressure slot");
+  hipStream_t s = ctx->stream;
+  const int dim = ctx->mesh.dim;
+  const size_t nc = (size_t)ctx->mesh.n_cells;
+  const size_t n_work = (size_t)NSFEM_N_FUNCTIONALS * (kVolParts + 1);
+  if (ctx->vf_parts.n != n_work) ctx->vf_parts.alloc(n_work);
+  double* parts = ctx->vf_parts.p;
+  double* res = parts + (size_t)NSFEM_N_FUNCTIONALS * kVolParts;
+  const double *ur = nullptr, *pr = nullptr;
+  if (ref_velocity) {
+    ctx->vf_ref_u.upload(ref_velocity, (size_t)nvel(ctx), s);
+    ur = ctx->vf_ref_u.p;
+  }
+  if (ref_pressure) {
+    ctx->vf_ref_p.upload(ref_pressure, (size_t)npre(ctx), s);
+    pr = ctx->vf_ref_p.p;
+  }
+  const uint8_t* flags = nullptr;
+  if (cell_flags) {
+    // the resident copy is replaced only when the CONTENTS differ (the same pointer may hold new flags)
+    if (ctx->vf_flags.n != nc || ctx->vf_flags_host.size() != nc ||
+        std::memcmp(ctx->vf_flags_host.data(), cell_flags, nc) != 0) {
+      ctx->vf_flags_host.assign(cell_flags, cell_flags + nc);
+      ctx->vf_flags.upload(ctx->vf_flags_host, s);
+    }
+    flags = ctx->vf_flags.p;
+  }
+  const double* u = ctx->state[velocity_slot].p;
+  const double* p = ctx->state[pressure_slot].p;
+  const bool dist = ctx->distributed();
+  if (dist) {   // ghost nodes take their owners' values -- in copies, the slots keep their bytes
+    if (ctx->vf_u.n != (size_t)nvel(ctx)) ctx->vf_u.alloc((size_t)nvel(ctx));
+    if (ctx->vf_p.n != (size_t)npre(ctx)) ctx->vf_p.alloc((size_t)npre(ctx));
+    NSFEM_HIP(hipMemcpyAsync(ctx->vf_u.p, u, sizeof(double) * nvel(ctx), hipMemcpyDeviceToDevice, s));
+    NSFEM_HIP(hipMemcpyAsync(ctx->vf_p.p, p, sizeof(double) * npre(ctx), hipMemcpyDeviceToDevice, s));
+    ctx->comm->exchange(s, ctx->halo_p2, ctx->vf_u.p, dim);
+    ctx->comm->exchange(s, ctx->halo_p1, ctx->vf_p.p, 1);
+    u = ctx->vf_u.p;
+    p = ctx->vf_p.p;
+  }
+  launch_vol_functionals(s, ctx->mesh, u, p, ur, pr, flags, parts, res);
+  if (dist) ctx->comm->allreduce_sum(s, res, NSFEM_N_FUNCTIONALS);
+  NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * NSFEM_N_FUNCTIONALS, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
   API_END(ctx)
 }
 

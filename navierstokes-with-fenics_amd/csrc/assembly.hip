@@ -20,6 +20,7 @@
 // All integrands are polynomials of degree <= 5 on affine cells, so the 7-point
 // degree-5 rule reproduces FEniCS' integrals to round-off.
 #include "nsfem_internal.hpp"
+#include "cell_geometry.hpp"
 
 namespace nsfem {
 
@@ -28,38 +29,6 @@ __constant__ QuadTables c_q;
 void upload_quad_tables(const QuadTables& t) {
   NSFEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_q), &t, sizeof(QuadTables)));
 }
-
-struct CellGeo {
-  double ji00, ji01, ji10, ji11;   // J^{-1}
-  double adet;
-};
-
-__device__ __forceinline__ CellGeo load_geo(const double* __restrict__ vx, int nc, int c) {
-  // (products fuse with the sums of their own statement only: every kernel that inlines this gets the same bits)
-#pragma clang fp contract(on)
-  const double x0 = vx[c], y0 = vx[(size_t)nc + c];
-  const double x1 = vx[(size_t)2 * nc + c], y1 = vx[(size_t)3 * nc + c];
-  const double x2 = vx[(size_t)4 * nc + c], y2 = vx[(size_t)5 * nc + c];
-  const double j00 = x1 - x0, j01 = x2 - x0, j10 = y1 - y0, j11 = y2 - y0;
-  const double det = j00 * j11 - j01 * j10;
-  const double id = 1.0 / det;
-  CellGeo g;
-  g.ji00 = j11 * id;
-  g.ji01 = -j01 * id;
-  g.ji10 = -j10 * id;
-  g.ji11 = j00 * id;
-  g.adet = fabs(det);
-  return g;
-}
-
-// physical gradient of a reference gradient (dr0, dr1): g_a = sum_b Jinv[b][a] dr_b
-__device__ __forceinline__ void phys(const CellGeo& g, double dr0, double dr1, double& gx,
-                                     double& gy) {
-#pragma clang fp contract(on)
-  gx = g.ji00 * dr0 + g.ji10 * dr1;
-  gy = g.ji01 * dr0 + g.ji11 * dr1;
-}
-
 
 // ------------------------------------------------------------------ scalar P2
 __global__ __launch_bounds__(256) void k_p2_scalar(int nc, const double* __restrict__ vx,

@@ -8,6 +8,7 @@
 // independently; its 3D branches are never exercised).  The 15-point Keast rule
 // is exact for degree 5, the highest degree any of these integrands reaches on affine cells.
 #include "nsfem_internal.hpp"
+#include "cell_geometry.hpp"
 
 namespace nsfem {
 
@@ -119,47 +120,6 @@ void upload_quad_tables_3d() {
   CflTables3 cf;
   fill_cfl_tables_3d(cf);
   NSFEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_cfl3), &cf, sizeof(CflTables3)));
-}
-
-struct CellGeo3 {
-  double ji[3][3];   // J^{-1}[b][a] = d xi_b / d x_a
-  double adet;
-};
-
-__device__ __forceinline__ CellGeo3 load_geo3(const double* __restrict__ vx, int nc, int c) {
-  double x[4][3];
-#pragma unroll
-  for (int v = 0; v < 4; ++v)
-#pragma unroll
-    for (int d = 0; d < 3; ++d) x[v][d] = vx[(size_t)(3 * v + d) * nc + c];
-  double J[3][3];   // J[a][b] = x_{b+1}[a] - x_0[a]
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) J[a][b] = x[b + 1][a] - x[0][a];
-  const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-  const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-  const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-  const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-  const double id = 1.0 / det;
-  CellGeo3 g;
-  g.ji[0][0] = c00 * id;
-  g.ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  g.ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
-  g.ji[1][0] = c01 * id;
-  g.ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  g.ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  g.ji[2][0] = c02 * id;
-  g.ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id;
-  g.ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
-  g.adet = fabs(det);
-  return g;
-}
-
-// physical gradient of a reference gradient dr: out_a = sum_b Jinv[b][a] dr_b
-__device__ __forceinline__ void phys3(const CellGeo3& g, const double* dr, double* out) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[a] = g.ji[0][a] * dr[0] + g.ji[1][a] * dr[1] + g.ji[2][a] * dr[2];
 }
 
 // ------------------------------------------------------------------ scalar P2

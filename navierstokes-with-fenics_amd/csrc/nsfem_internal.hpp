@@ -455,6 +455,13 @@ void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u
 void launch_boundary_force(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell,
                            const int32_t* flocal, const double* u, const double* p, double nu,
                            double sym, double* out);
+// volume functionals (functionals.hip): the NSFEM_N_FUNCTIONALS integrals of include/nsfem.h over the cells whose
+// flag is nonzero (flags null: all cells), of (u, p) or, with ur / pr set, of (u - ur, p - pr).  parts:
+// [NSFEM_N_FUNCTIONALS][kVolParts] work space, out: [NSFEM_N_FUNCTIONALS], both in device memory
+constexpr int kVolParts = 1024;
+void upload_functional_tables(int dim);
+void launch_vol_functionals(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* ur,
+                            const double* pr, const uint8_t* flags, double* parts, double* out);
 // diag extraction: d[(i,a)] = 1 / A_ii[a][a]  (mask rows -> 1)
 void launch_inv_diag(hipStream_t s, const BlockMat& A, int nv, const uint8_t* rowmask,
                      double* dinv);
@@ -1130,6 +1137,12 @@ struct nsfem_ctx {
     size_t n = 0;
     ~Probe() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
   } conv_probe;
+  // nsfem_volume_functionals: partial sums + results, resident reference fields and cell flags (with the host copy
+  // the next call's flags are compared against), and on partitioned meshes the copies of the two slots whose ghost
+  // entries are exchanged (the state itself is not written)
+  nsfem::DevBuf<double> vf_parts, vf_ref_u, vf_ref_p, vf_u, vf_p;
+  nsfem::DevBuf<uint8_t> vf_flags;
+  std::vector<uint8_t> vf_flags_host;
   int64_t jac_lattice_launches = 0;   // applications of the matrix-free Jacobian through k_jac_lattice
   bool mf_active = false;           // the running step driver applies the Jacobian matrix-free
   int pressure_history = 0;         // IPCS: pressure levels shifted since the state was last set (0..2)

@@ -11,8 +11,8 @@ import math
 
 import numpy as np
 
-from form_language import (FacetNormal, Measure, Operand, assemble, dot, ds, dx, grad, inner,  # noqa: F401
-                           sqrt)
+from form_language import (FacetNormal, Measure, Operand, assemble, dot, ds, dx, errornorm, grad, inner,  # noqa: F401
+                           norm, sqrt)
 
 pi = math.pi
 DOLFIN_EPS = 3.0e-16

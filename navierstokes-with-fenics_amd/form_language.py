@@ -14,7 +14,13 @@ cells every integrand the callers build is a polynomial of degree <= 4, the rule
 degree 6 (dx) / 7 (ds in 2D) / 5 (ds in 3D).  The mass solve of ``project`` runs on the GPU
 (nsfem_mass_solve), like the projections of the initial conditions.  The device kernel behind
 ``nsfem_boundary_force`` computes the same traction / flux functionals without this layer
-(bench.py, ProblemBase._compute_boundary_force)."""
+(bench.py, ProblemBase._compute_boundary_force).
+
+``norm`` / ``errornorm`` of a solver's velocity or pressure function are the exception: they are volume integrals of
+the finite element solution itself and run as one device call (``nsfem_volume_functionals``); only ``errornorm`` with
+``degree_rise > 0`` goes through the host ``dx`` quadrature."""
+import math
+
 import numpy as np
 
 import fem_host
@@ -427,3 +433,79 @@ def project_expression(expression, space):
         np.add.at(b, dm.p1_dofmap[c0:c1].astype(np.int64).ravel(), be.ravel())
     x = solver._ctx.mass_solve(nat.PRESSURE, b)
     return HostField(mesh, "projection", "Node", x[dm.p1_vertex_node])
+
+
+# ------------------------------------------------------------------------------- norms
+_NORM_TYPES = ("L2", "H10", "H1")
+
+
+def _device_field(f, what):
+    """(solver, context) of a velocity / pressure function that lives in a state slot of a live device context"""
+    ok = hasattr(f, "_solver") and hasattr(f, "field") and hasattr(f, "slot")
+    ctx = getattr(getattr(f, "_solver", None), "_ctx", None) if ok else None
+    if ctx is None or not getattr(getattr(ctx, "_h", None), "value", None):
+        raise TypeError("%s needs a velocity or pressure function owned by a solver with a live device context" % what)
+    return f._solver, ctx
+
+
+def _field_norm_sq(f, norm_type, reference=None):
+    """squared norm of f (minus the nodal reference vector) from ONE nsfem_volume_functionals call"""
+    import _native as nat
+    if norm_type not in _NORM_TYPES:
+        raise ValueError("norm_type %r: one of %s" % (norm_type, ", ".join(_NORM_TYPES)))
+    _, ctx = _device_field(f, "norm() / errornorm()")
+    if f.field == "velocity":
+        r = ctx.volume_functionals(f.slot, nat.P, ref_velocity=reference)
+        l2, h10 = r["u_l2_sq"], r["grad_u_l2_sq"]
+    else:
+        r = ctx.volume_functionals(nat.U0, f.slot, ref_pressure=reference)
+        l2, h10 = r["p_l2_sq"], r["grad_p_l2_sq"]
+    return {"L2": l2, "H10": h10, "H1": l2 + h10}[norm_type]
+
+
+def norm(f, norm_type="L2"):
+    """``dolfin.norm`` of a solver's velocity or pressure function: ``L2``, ``H10`` (the seminorm |grad f|) or ``H1``,
+    from one device call (nsfem_volume_functionals; exact quadrature of the finite element function)."""
+    return math.sqrt(_field_norm_sq(f, str(norm_type).upper()))
+
+
+def errornorm(u, uh, norm_type="L2", degree_rise=3):
+    """``dolfin.errornorm(u, uh)``: norm of u - uh for a velocity or pressure function ``uh`` (of a solver with a live
+    device context for ``degree_rise=0``; the host path takes any finite element function).
+
+    ``degree_rise=0``: u is interpolated at the nodes of uh's own space and uploaded as the reference field of one
+    device call -- the norm of the difference of two functions of that space, integrated exactly.
+    ``degree_rise > 0`` (dolfin's default, 3): the host ``dx`` quadrature of this module with u EVALUATED at the
+    quadrature points.  That is the limit of large ``degree_rise``, not dolfin's interpolation of u into
+    P(degree + degree_rise): the two differ at the order of that interpolation error (and by the error of the
+    degree-4 rule on a non-polynomial u).  The ``H10`` / ``H1`` norms of this path need the gradient of u and are
+    provided where u is a finite element function itself.  Parity with FEniCS output is not pinned."""
+    nt = str(norm_type).upper()
+    if nt not in _NORM_TYPES:
+        raise ValueError("norm_type %r: one of %s" % (norm_type, ", ".join(_NORM_TYPES)))
+    if not _is_fe_function(uh):
+        raise TypeError("errornorm(u, uh): uh must be a finite element function")
+    dm, field, _ = _fe_data(uh)
+    if int(degree_rise) == 0:
+        _device_field(uh, "errornorm(..., degree_rise=0)")
+        if _is_fe_function(u):
+            _, kind, ref = _fe_data(u)
+            assert kind == field, "errornorm of a %s against a %s function" % (field, kind)
+        else:
+            import dlfn_compat
+            X = dm.p2_coords if field == "velocity" else dm.p1_coords
+            ref = np.asarray(dlfn_compat.evaluate(u, X), dtype=np.float64)
+            assert ref.shape == ((X.shape[0], dm.dim) if field == "velocity" else (X.shape[0], )), \
+                "u has the wrong value shape for a %s function" % field
+        return math.sqrt(_field_norm_sq(uh, nt, reference=np.ascontiguousarray(ref).ravel()))
+    e = u - uh
+    total = 0.0
+    if nt in ("L2", "H1"):
+        total += assemble((inner(e, e) if field == "velocity" else e * e) * dx(domain=dm.mesh))
+    if nt in ("H10", "H1"):
+        if not _is_fe_function(u):
+            raise NotImplementedError("errornorm(..., %r, degree_rise > 0) needs the gradient of u: pass a finite "
+                                      "element function, or use degree_rise=0" % nt)
+        g = grad(e)
+        total += assemble(inner(g, g) * dx(domain=dm.mesh))
+    return math.sqrt(max(total, 0.0))

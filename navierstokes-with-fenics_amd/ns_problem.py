@@ -165,6 +165,22 @@ class ProblemBase:
         force, _, _ = solver._ctx.boundary_force(cells, local, nu, 1.0, nat.U0, nat.P)
         return tuple(float(v) for v in force)
 
+    def _compute_flow_diagnostics(self):
+        """Volume integrals of the current solution from ONE device call (nsfem_volume_functionals) -- callable from
+        ``postprocess_solution`` at every step: dict of ``kinetic_energy`` = 1/2 int u.u, ``enstrophy`` =
+        1/2 int |curl u|^2, ``divergence_l2`` = |div u|_L2, ``dissipation_integrand`` = int grad u : grad u,
+        ``pressure_l2`` = |p|_L2 and ``volume`` = |Omega|.  New helper (the reference's callers would spell these out
+        as ``assemble(... * dx)``).  A problem that runs on one rank of a partitioned mesh keeps its partition in
+        ``self._partition``: its ``owned_cell_flags()`` select every global cell on exactly one rank and every rank
+        receives the global values."""
+        import _native as nat
+        part = getattr(self, "_partition", None)
+        flags = part.owned_cell_flags() if part is not None else None
+        r = self._get_solver()._ctx.volume_functionals(nat.U0, nat.P, cell_flags=flags)
+        return dict(kinetic_energy=0.5 * r["u_l2_sq"], enstrophy=0.5 * r["curl_l2_sq"],
+                    divergence_l2=math.sqrt(max(r["div_l2_sq"], 0.0)), dissipation_integrand=r["grad_u_l2_sq"],
+                    pressure_l2=math.sqrt(max(r["p_l2_sq"], 0.0)), volume=r["measure"])
+
     def _compute_stream_potential(self):
         """Velocity potential phi (the reference's "stream potential", :105-176): P1 solution of
         (grad phi, grad psi) = (div u, psi) - sum over the remaining boundaries of (n . u, psi),

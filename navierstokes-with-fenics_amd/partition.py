@@ -68,6 +68,16 @@ class StripLevel:
         return self.row0 * self.w1
 
 
+def _layer_cell_flags(part, cells_per_layer, total_layers):
+    """(flags, global ids) of the local cells of a strip / slab: the local cells are numbered layer by layer (rows of
+    2 nx triangles, cube layers of 6 nx ny tetrahedra), the own layers come first and the ghost layer last"""
+    n = part.mesh.num_cells()
+    own = part.fine.own_rows
+    flags = (np.arange(n) < own * cells_per_layer).astype(np.uint8)
+    glob = (part.fine.row0 * cells_per_layer + np.arange(n, dtype=np.int64)) % (total_layers * cells_per_layer)
+    return flags, glob
+
+
 class StripPartition:
     """Everything rank ``rank`` of ``size`` needs: local fine mesh + dof map, ghost masks,
     halo ranges, local multigrid levels with prolongations, and the replicated coarsest mesh."""
@@ -149,6 +159,15 @@ class StripPartition:
             from multigrid import structured_hierarchy
             self.global_tail = structured_hierarchy(self.p0, self.p1, last.nx, ly,
                                                     coarsest=global_coarsest, allow_non_nested=False)
+
+    def owned_cell_flags(self):
+        """uint8 per local cell: 1 for the cells of the rank's own rows, 0 for the ghost cell row -- over all ranks
+        every global cell is flagged exactly once (volume integrals: NsfemContext.volume_functionals)"""
+        return _layer_cell_flags(self, 2 * self.nx, self.ny)[0]
+
+    def cell_global(self):
+        """global id (cell numbering of rectangle_mesh(p0, p1, nx, ny)) of every local cell"""
+        return _layer_cell_flags(self, 2 * self.nx, self.ny)[1]
 
     def attach(self, ctx, degree=None, eig_ratio=None):
         """Ship the partition, the local multigrid levels and the replicated global coarsest
@@ -295,6 +314,15 @@ class SlabPartition:
         if global_coarsest is not None:
             self.global_tail = structured_hierarchy(self.p0, self.p1, last.nx, last.ny, lz,
                                                     coarsest=global_coarsest, allow_non_nested=False)
+
+    def owned_cell_flags(self):
+        """uint8 per local cell: 1 for the cells of the rank's own cube layers, 0 for the ghost layer -- over all
+        ranks every global cell is flagged exactly once (volume integrals: NsfemContext.volume_functionals)"""
+        return _layer_cell_flags(self, 6 * self.nx * self.ny, self.nz)[0]
+
+    def cell_global(self):
+        """global id (cell numbering of box_mesh(p0, p1, nx, ny, nz)) of every local cell"""
+        return _layer_cell_flags(self, 6 * self.nx * self.ny, self.nz)[1]
 
     def attach(self, ctx, degree=None, eig_ratio=None):
         from fem_mesh import box_mesh
@@ -452,6 +480,15 @@ class PeriodicSlabPartition:
             tail = structured_hierarchy(self.p0, self.p1, cx, cy, cz, coarsest=self.global_coarsest, allow_non_nested=False)
         return mesh, vdof, tail
 
+    def owned_cell_flags(self):
+        """uint8 per local cell: 1 for the cells of the rank's own cube layers, 0 for the ghost layer -- over all
+        ranks every global cell is flagged exactly once (volume integrals: NsfemContext.volume_functionals)"""
+        return _layer_cell_flags(self, 6 * self.nx * self.ny, self.nz)[0]
+
+    def cell_global(self):
+        """global id (cell numbering of box_mesh(p0, p1, nx, ny, nz)) of every local cell"""
+        return _layer_cell_flags(self, 6 * self.nx * self.ny, self.nz)[1]
+
     def attach(self, ctx, degree=None, eig_ratio=None):
         import scipy.sparse as sp
         ctx.set_partition(self.rank, self.size, self.p2_ghost, self.p1_ghost, self.p2_halo,
@@ -554,6 +591,15 @@ class PeriodicStripPartition:
         self.coarse_global_shape = (last.nx, ly)
         self.coarse_global_offset = last.row0 * last.w1
         self.global_coarsest = global_coarsest
+
+    def owned_cell_flags(self):
+        """uint8 per local cell: 1 for the cells of the rank's own rows, 0 for the ghost cell row -- over all ranks
+        every global cell is flagged exactly once (volume integrals: NsfemContext.volume_functionals)"""
+        return _layer_cell_flags(self, 2 * self.nx, self.ny)[0]
+
+    def cell_global(self):
+        """global id (cell numbering of rectangle_mesh(p0, p1, nx, ny)) of every local cell"""
+        return _layer_cell_flags(self, 2 * self.nx, self.ny)[1]
 
     def attach(self, ctx, degree=None, eig_ratio=None):
         from fem_mesh import rectangle_mesh
@@ -796,6 +842,15 @@ class GraphPartition:
             Pl.sort_indices()
             self.levels.append((made[l], (Pl.indptr.astype(np.int32), Pl.indices.astype(np.int32), Pl.data.copy())))
         self.coarse_global_index = made[-1].vertices
+
+    def owned_cell_flags(self):
+        """uint8 per local cell of the finest level: 1 where the cell belongs to this rank (cell_owner == rank), 0 for
+        the cells held only for their nodes -- over all ranks every global cell is flagged exactly once"""
+        return (self.cell_owner[0][self.fine.cells] == self.rank).astype(np.uint8)
+
+    def cell_global(self):
+        """global id (cell of the global fine mesh) of every local cell"""
+        return np.asarray(self.fine.cells, dtype=np.int64)
 
     def p2_global(self, global_dofmap):
         """local P2 node -> node of a TaylorHoodDofMap of the GLOBAL fine mesh (comparisons)"""
