@@ -236,7 +236,7 @@ int nsfem_operator_apply(nsfem_ctx* ctx, int op, const double* x, double* y);
  *   b_formed    host [n * nv] or NULL: the right-hand side the launch stored (with rf)
  *   gh_lo, gh_hi, gh_zero   frozen ghost lines of a partitioned strip (flag every component of their rows)
  *   tile_lines  0 the launcher's choice; 16, 24, 32 or 48 forced (refused when the halo does not fit)
- *   fixed       -1 default (NSFEM_LATTICE_FIXED), 0 compile-time-offset stages off, 1 on
+ *   fixed       -1 default (on), 0 compile-time-offset stages off, 1 on
  *   lattice_*   out: the geometry of the launch and its fixed_shape
  * d_out NULL (family 4): the launch stores no direction. */
 
@@ -520,9 +520,8 @@ int nsfem_time_spmv(nsfem_ctx* ctx, int op, int reps, double* ms_per_launch,
  * returned; NSFEM_DICT=0 disables it. */
 int nsfem_smoother_info(nsfem_ctx* ctx, int64_t out[4]);
 /* Test hook: z = M^-1 r, one cycle of a multigrid preconditioner on host vectors (which: 0 = pressure Poisson
-   hierarchy, 1 = velocity hierarchy); nsfem_mg_info: out = {fused-leg kind (0 separate launches, 1 one launch below
-   the finest level of a truncated cycle, 2 down-legs + tail + up-legs), fused launches per cycle, levels in use,
-   fused launches so far}; which = 2 / 3: the multi-step lattice kernel on the Poisson / velocity hierarchy: out =
+   hierarchy, 1 = velocity hierarchy); nsfem_mg_info: out = {reserved (always 0), reserved (always 0), levels in use,
+   reserved (always 0)}; which = 2 / 3: the multi-step lattice kernel on the Poisson / velocity hierarchy: out =
    {levels whose smoothing sequences run in it (partitioned strips: relaxed halo mode only), its launches so far,
    levels in use, ghost lattice lines of the finest level as bottom * 256 + top}.  New functionality (the reference has no preconditioner: sparse LU,
    source/ns_ipcs_solver.py:171,205). */

@@ -571,12 +571,6 @@ class NsfemContext:
         return dict(shape=(int(out[0]), int(out[1]), int(out[2])), exact=bool(out[3]), applications=int(out[4]),
                     solves=int(out[5]))
 
-    def mg_info(self, which):
-        """dict(legs, launches_per_cycle, levels, leg_launches): how the cycles of a hierarchy run"""
-        out = (C.c_int64 * 4)()
-        self._check(self._lib.nsfem_mg_info(self._h, int(which), out))
-        return dict(legs=int(out[0]), launches_per_cycle=int(out[1]), levels=int(out[2]), leg_launches=int(out[3]))
-
     def mg_lattice_info(self, which):
         """dict(lattice_levels, lattice_launches, levels, ghost_lines): the multi-step lattice kernel on the Poisson
         (which = 0) / velocity (1) hierarchy; on partitioned strips it runs in relaxed halo mode only"""

@@ -96,7 +96,6 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   NSFEM_REQUIRE(m && out, "null argument");
   refresh_env_switches();
   refresh_assembly_switches();
-  refresh_leg_switches();
   *out = nullptr;
   NSFEM_REQUIRE(m->dim == 2 || m->dim == 3, "dim must be 2 (triangles) or 3 (tetrahedra)");
   NSFEM_REQUIRE(m->n_cells > 0 && m->n_vertices > 0 && m->n_p2 > 0 && m->n_p1 > 0, "empty mesh");
@@ -886,7 +885,6 @@ static void momentum_jacobian(nsfem_ctx* c, int vel_slot = NSFEM_USTAR) {
 // value 2).  Path 1 stays single-context (its node-sorted buffer has no interior / halo split).
 static int jacobian_path(nsfem_ctx* c) {
   if (c->mesh.dim != 2 || cc_of(c) == 0.0 || !c->L.dict_ready) return 0;
-  if (c->distributed() && !partitioned_lattice_kernels()) return 0;
   if (!c->mesh.cl.tried && c->L.dict && c->L.dict->lat_w > 0) {
     build_cell_lattice(c->h_p2map.data(), c->mesh.n_cells, c->L.dict->lat_w, c->L.dict->lat_h, c->mesh.cl);
     check_uniform_geometry(c->stream, c->mesh);
@@ -1505,8 +1503,7 @@ static void fill_p1_level(nsfem_ctx* ctx, nsfem_ctx::P1Level* lv, int n_vertices
   launch_assemble_p1_scalar(s, lv->mesh, lv->pat, lv->K.vals.p, lv->M.vals.p);
   // lattice levels: stencil dictionary of the level's operators (smoothing steps of both hierarchies;
   // the multi-step lattice kernel needs it)
-  // (2D: down to 3 x 3 nodes -- the fused legs of mglegs.hip run the whole bottom of a cycle from these tables)
-  if (build_stencil_dict(s, lv->pat, lv->M.vals.p, lv->K.vals.p, lv->dict, 1, false, dim == 2 ? 9 : 0))
+  if (build_stencil_dict(s, lv->pat, lv->M.vals.p, lv->K.vals.p, lv->dict))
     lv->K.dict = lv->M.dict = lv->Lc.dict = &lv->dict;
   lv->K.sell_update(s);
   lv->M.sell_update(s);
@@ -1889,8 +1886,7 @@ extern "C" int nsfem_mg_finalize(nsfem_ctx* ctx, const nsfem_mg_opts* o) {
   ctx->Lc0.init(&ctx->p11, 1, 1, s);
   const int degree = (o && o->smoother_degree > 0) ? o->smoother_degree : 2;
   const double ratio = (o && o->eig_ratio > 1.0) ? o->eig_ratio : 4.0;
-  int dense_max = (o && o->coarse_dense_max > 0) ? o->coarse_dense_max : 1200;
-  if (const char* e = std::getenv("NSFEM_DENSE_MAX")) dense_max = std::atoi(e);   // experiments
+  const int dense_max = (o && o->coarse_dense_max > 0) ? o->coarse_dense_max : 1200;
   // pressure Poisson hierarchy: P1 fine -> coarse P1 levels
   {
     Multigrid& mg = ctx->mg_p;
@@ -1918,8 +1914,6 @@ extern "C" int nsfem_mg_finalize(nsfem_ctx* ctx, const nsfem_mg_opts* o) {
     mg.degree = degree + 1;
     ctx->mg_v_symmetric = false;
     mg.identity_rows = true;     // z = r on Dirichlet rows, written by the last smoothing step
-    if (const char* e = std::getenv("NSFEM_MGV_PRE")) mg.pre_degree = std::atoi(e);
-    if (const char* e = std::getenv("NSFEM_MGV_POST")) mg.degree = std::atoi(e);
     mg.lv.clear();
     mg.lv.resize(2 + ctx->coarse.size());
     mg.lv[0].A = &ctx->L; mg.lv[0].n = ctx->mesh.n_p2; mg.lv[0].mask = ctx->mask_v.p;
@@ -3311,8 +3305,7 @@ extern "C" int nsfem_poisson_set_fast_diag_3d_planes(nsfem_ctx* ctx, int32_t Nx,
 // Test hook: one application z = M^-1 r of a multigrid preconditioner on host vectors -- which = 0 pressure Poisson
 // hierarchy (mg_p), 1 velocity hierarchy (mg_v, the identity rows of the Newton preconditioner included), 2 the
 // fast-diagonalisation solve z = A^+ r (FastDiag::apply; on strip factors FastDiag::apply_strip, on slab factors
-// FastDiag3::apply_slab: collectives).  Lets
-// the parity tests compare the fused multi-level launches (mglegs.hip) with the separate launches cycle by cycle.
+// FastDiag3::apply_slab: collectives).  Lets the parity tests compare kernel families cycle by cycle.
 extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double* z) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && r && z && (which == 0 || which == 1 || which == 2), "bad argument");
@@ -3337,7 +3330,7 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
   }
   NSFEM_REQUIRE(ctx->mg_built, "no multigrid hierarchy (nsfem_mg_finalize)");
   ensure_L(ctx);                       // (builds the dictionaries of the fine P1 operators as well)
-  if (which == 0 && ctx->mg_p.legs_kind == 0) ctx->mg_p_dirty = true;   // planned before the dictionaries existed
+  if (which == 0) ctx->mg_p_dirty = true;   // (refreshed before the dictionaries of the fine P1 operators existed)
   mg_refresh(ctx, which == 1);
   const int64_t n = which == 1 ? nvel(ctx) : npre(ctx);
   DevBuf<double> dr, dz;
@@ -3350,9 +3343,8 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
   API_END(ctx)
 }
 
-// How a multigrid cycle runs: out = {kind of the fused legs (0 separate launches, 1 one launch below the finest level
-// of a truncated cycle, 2 down-legs + single-workgroup tail + up-legs), launches of k_mg_leg per cycle, levels in use,
-// launches of k_mg_leg so far}
+// How a multigrid cycle runs: which = 0 / 1: out = {0, 0, levels in use, 0} (the two zero fields are reserved);
+// which = 2 / 3: the multi-step lattice kernel on the hierarchy
 extern "C" int nsfem_mg_info(nsfem_ctx* ctx, int which, int64_t out[4]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out && which >= 0 && which <= 3, "bad argument");
@@ -3370,11 +3362,10 @@ extern "C" int nsfem_mg_info(nsfem_ctx* ctx, int which, int64_t out[4]) {
     out[3] = mg.lv[0].ghost_lo >= 0 ? mg.lv[0].ghost_lo * 256 + mg.lv[0].ghost_hi : 0;
     return NSFEM_OK;
   }
-  if (mg.legs_kind < 0) mg.build_legs(ctx->stream);
-  out[0] = mg.legs_kind;
-  out[1] = mg.legs_kind == 1 ? 1 : (mg.legs_kind == 2 ? (int64_t)(mg.legs_down.size() + mg.legs_up.size() + 1) : 0);
+  out[0] = 0;
+  out[1] = 0;
   out[2] = (int64_t)(mg.truncated() ? mg.active : mg.lv.size());
-  out[3] = mg.leg_launches;
+  out[3] = 0;
   API_END(ctx)
 }
 

@@ -1267,15 +1267,13 @@ int64_t check_gradient_tables(hipStream_t s, const MeshDev& m) {
 
 static bool g_jac_lattice_on = true;
 static int g_jac_lattice_dbg = 0;
-// tile shape in use: 0 = 32 x 8 squares (512 threads), 1 = 16 x 8 (256).  Measured at n = 512 (us per launch of the
+// tile shape: 32 x 8 squares (512 threads).  Measured at n = 512 (us per launch of the
 // Newton action): 32 x 8: 48.3, 16 x 8: 50.4, 16 x 16: 50.5, 8 x 8: 55.5, 32 x 16 (1024 threads, one workgroup per CU):
 // 62.7 -- the launch is bound by the latency chain of
 // a wave (loads, barriers, LDS phases) at 4 waves per SIMD, not by the shape of the tile
-static int g_jac_lattice_tile = 0;
-static bool g_partitioned_lattice = true;
+constexpr int kJlSx = 32, kJlSy = 8;
 static bool g_jac_uniform_geo = true;                 // NSFEM_JL_UNIFORM_GEO=0: always load the cell coordinates
 static bool g_jac_gather = true;                      // NSFEM_JL_KERNEL=0: the round-4 kernel (variant 0), for A/B runs
-bool partitioned_lattice_kernels() { return g_partitioned_lattice; }
 void refresh_assembly_switches() {
   const char* e = std::getenv("NSFEM_JAC_LATTICE");
   g_jac_lattice_on = e ? std::atoi(e) != 0 : true;
@@ -1283,24 +1281,14 @@ void refresh_assembly_switches() {
   g_jac_uniform_geo = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_JL_KERNEL");
   g_jac_gather = e ? std::atoi(e) != 0 : true;
-  e = std::getenv("NSFEM_PARTITIONED_LATTICE");       // 0: partitioned strips keep the one-step / multi-launch kernels
-  g_partitioned_lattice = e ? std::atoi(e) != 0 : true;
 #if NSFEM_KNOCKOUTS
   e = std::getenv("NSFEM_JL_DBG");
   g_jac_lattice_dbg = e ? std::atoi(e) : 0;
 #endif
-  e = std::getenv("NSFEM_JL_TILE");
-  g_jac_lattice_tile = e ? std::max(0, std::min(1, std::atoi(e))) : 0;
-}
-static void jac_lattice_shape(int& sx, int& sy) {
-  static const int shapes[2][2] = {{32, 8}, {16, 8}};
-  sx = shapes[g_jac_lattice_tile][0];
-  sy = shapes[g_jac_lattice_tile][1];
 }
 static size_t jac_lattice_lds(const StencilDict& d, bool imex = false) {
   const size_t lp = (size_t)((d.lmax + 3) & ~3);
-  int sx, sy;
-  jac_lattice_shape(sx, sy);
+  const int sx = kJlSx, sy = kJlSy;
   const size_t nn = (size_t)(2 * sx + 1) * (2 * sy + 1);
   const size_t staged = 3 * nn * sizeof(double2) + (size_t)d.n_stencils * lp * (imex ? 20 : 12) + (size_t)d.n_stencils * 4 + 16;
   // variants 1, 2: sa, then the element vectors of the gather over su, sx and the tables
@@ -1329,9 +1317,7 @@ int64_t jacobian_lattice_bytes(const MeshDev& m) {
 // a partitioned strip, launched under the halo exchange); 2: the other tile rows.  jacobian_lattice_split tells
 // whether phases 1 / 2 exist for the given ghost lines
 static bool lattice_tile_rows(const CellLattice& cl, int gh_lo, int gh_hi, int& nty, int& r0, int& r1) {
-  int sx, sy;
-  jac_lattice_shape(sx, sy);
-  const int oy = 2 * (sy - 1);
+  const int oy = 2 * (kJlSy - 1);
   nty = (cl.H + oy - 1) / oy;
   // tile row ty reads the lattice lines ty * oy - 2 ... (ty + 1) * oy
   r0 = 0;
@@ -1354,8 +1340,7 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
   const StencilDict& d = *L.dict;
   JacLatArgs a;
   a.nx = cl.nx; a.ny = cl.ny; a.W = cl.W; a.H = cl.H; a.nc = m.n_cells;
-  int sx, sy;
-  jac_lattice_shape(sx, sy);
+  const int sx = kJlSx, sy = kJlSy;
   const int ox = 2 * (sx - 1), oy = 2 * (sy - 1);
   a.ntx = (cl.W + ox - 1) / ox;
   a.ntiles = a.ntx * ((cl.H + oy - 1) / oy);
@@ -1411,12 +1396,6 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
       NSFEM_HIP(hipFuncSetAttribute((const void*)k_jac_lattice<F, LIN, SX, SY, V>,                          \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                \
       attr = true;                                                                                          \
-      if (std::getenv("NSFEM_JL_OCC")) {                                                                    \
-        int nb = 0;                                                                                         \
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_jac_lattice<F, LIN, SX, SY, V>, \
-                                                           2 * SX * SY, lds);                               \
-        std::fprintf(stderr, "k_jac_lattice<%d x %d>: %d workgroups per CU at %zu B of LDS\n", SX, SY, nb, lds); \
-      }                                                                                                     \
     }                                                                                                       \
     hipLaunchKernelGGL((k_jac_lattice<F, LIN, SX, SY, V>), dim3(grid), dim3(2 * SX * SY), lds, s, a, m.vx.p, u, \
                        x, d.sid8.p, mask, d.len.p, d.pack.p, L.dict_vals.p, gadd, y,                        \
@@ -1429,13 +1408,7 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
     else if (var == 1) NSFEM_JL_V(F, LIN, SX, SY, 1);                                                       \
     else NSFEM_JL_V(F, LIN, SX, SY, 0);                                                                     \
   } while (0)
-#define NSFEM_JL(F, LIN)                                                                                    \
-  do {                                                                                                      \
-    switch (g_jac_lattice_tile) {                                                                           \
-      case 1: NSFEM_JL_T(F, LIN, 16, 8); break;                                                             \
-      default: NSFEM_JL_T(F, LIN, 32, 8); break;                                                            \
-    }                                                                                                       \
-  } while (0)
+#define NSFEM_JL(F, LIN) NSFEM_JL_T(F, LIN, kJlSx, kJlSy)
   if (lds > 96 * 1024) return false;
 #define NSFEM_JL_F(LIN)                                                                                     \
   switch (form) {                                                                                           \

@@ -171,11 +171,7 @@ __global__ __launch_bounds__(256) void k_spmv(int n_rows, const int32_t* __restr
 #define NSFEM_STREAM_NNZ 1024
 #endif
 constexpr int kStreamNnz = NSFEM_STREAM_NNZ;
-// which shapes use the stream kernel unless NSFEM_SPMV_STREAM overrides it (set from the
-// measured sweep, see profiles/)
-static inline bool kStreamDefault(bool shape22) { (void)shape22; return true; }
 
-// version 1 (round 1) of the kernel: the default (NSFEM_STREAM_V=2 selects the wide-load variant below)
 template <int BR, int BC, int NV, int EPI>
 __global__ __launch_bounds__(256) void k_spmv_stream_v1(int n_rblk, const int32_t* __restrict__ rblk,
                                                      const int32_t* __restrict__ rowptr,
@@ -314,185 +310,6 @@ __global__ __launch_bounds__(256) void k_spmv_stream_v1(int n_rblk, const int32_
   }
 }
 
-// Version 2 of the streaming phase (round 2): the kernel was bound by the length of its dependent
-// load chain times the workgroups a CU can hold, not by HBM (scripts/micro/readbw.hip: 6.2 TB/s
-// read-only, 5.2 TB/s 3 reads + 1 write on the same box against 3.7-4.7 TB/s here):
-//   * every lane owns FOUR CONSECUTIVE nonzeros of a 16-byte aligned window over the chunk: one
-//     16-byte column load and two 16-byte value loads per lane (scalar blocks) instead of eight
-//     4 / 8-byte loads -- the chunk limit is 1020 nonzeros so that the aligned window fits;
-//   * one 16-byte record {r0, r1, s0, s1} per chunk instead of two dependent index loads;
-//   * the row pointers of the chunk's rows are fetched at the start (latency hidden behind the
-//     streaming phase) and parked in LDS for the reduction phase.
-template <int BR, int BC, int NV, int EPI>
-__global__ __launch_bounds__(256) void k_spmv_stream(int n_rblk, const int4* __restrict__ rbinfo,
-                                                     const int32_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ col,
-                                                     const double* __restrict__ vals, SpmvArgs a) {
-  constexpr int NO = BR * NV;
-  constexpr int BS = BR * BC;
-  // dynamic LDS: the products of the chunk, then its row pointers (sized for the pattern's
-  // longest chunk: the 3-component kernel must stay below 160 KB / 6 per workgroup)
-  extern __shared__ double smem[];
-  double* prod = smem;
-  int32_t* rp = reinterpret_cast<int32_t*>(smem + kStreamNnz * NO);
-  const int per = gridDim.x >> 3;
-  int lb = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (lb >= n_rblk) return;
-  if (lb >= a.skip0) lb += a.skipn;     // halo-adjacent launch: jump over the interior row blocks
-  const int4 info = rbinfo[lb];
-  const int r0 = info.x, r1 = info.y, s0 = info.z, s1 = info.w;
-  const double* __restrict__ x = a.x;
-  const int tid = threadIdx.x;
-  // row pointers of the chunk (relative to s0) -> LDS, needed after the barrier only
-  const int nrows = r1 - r0;
-  for (int t = tid; t <= nrows; t += 256) rp[t] = rowptr[r0 + t] - s0;
-  // epilogue operands of this thread's first output entry: issued before the streaming phase so
-  // that their latency hides behind it (the smoother epilogue reads b, dinv, d, x and the mask)
-  const int nout = nrows * NO;
-  const bool pre = tid < nout;
-  const size_t pidx = (size_t)r0 * NO + tid;
-  int pmv = 0;
-  double pb = 0.0, pdinv = 0.0, pd = 0.0, px = 0.0;
-  if (pre && (EPI == EPI_CHEB || EPI == EPI_RESID)) {
-    pmv = (a.maskmode != MASK_NONE) ? a.mask[pidx] : 0;
-    pb = a.b[pidx];
-    if (EPI == EPI_CHEB) {
-      pdinv = a.dinv[pidx];
-      if (a.c1 != 0.0) pd = a.d[pidx];
-      px = x[pidx];
-    }
-  }
-  // streaming phase: lane `tid` owns the nonzeros a0 + 4 tid .. a0 + 4 tid + 3 of the aligned
-  // window starting at a0 = s0 rounded down to a multiple of 4 (s1 - a0 <= 1023 by construction)
-  const int a0 = s0 & ~3;
-  const int k0 = a0 + 4 * tid;
-  int cc_[4];
-  double av[4][BS];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) cc_[u] = -1;
-  if (k0 < s1) {
-    // (k0 is a multiple of 4: 16-byte aligned column quad, 32-byte aligned value quad; every device
-    // buffer carries 64 bytes of slack (DevBuf::alloc), entries outside [s0, s1) are discarded)
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    const v4i* cq4 = reinterpret_cast<const v4i*>(col + k0);
-    const v4i c4 = a.nt ? __builtin_nontemporal_load(cq4) : *cq4;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) cc_[u] = (k0 + u >= s0 && k0 + u < s1) ? c4[u] : -1;
-    if (BS == 1) {
-      const v2d* vq = reinterpret_cast<const v2d*>(vals + k0);
-      const v2d v01 = a.nt ? __builtin_nontemporal_load(vq) : vq[0];
-      const v2d v23 = a.nt ? __builtin_nontemporal_load(vq + 1) : vq[1];
-      av[0][0] = v01[0]; av[1][0] = v01[1]; av[2][0] = v23[0]; av[3][0] = v23[1];
-    } else {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (cc_[u] >= 0) {
-#pragma unroll
-          for (int t = 0; t < BS; ++t)
-            av[u][t] = a.nt ? __builtin_nontemporal_load(vals + (size_t)(k0 + u) * BS + t)
-                            : vals[(size_t)(k0 + u) * BS + t];
-        }
-    }
-  }
-  if (NSFEM_KO(a.dbg == 1)) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (cc_[u] >= 0) cc_[u] = r0 + (4 * tid + u) % nrows;
-  }
-  double xv[4][BC * NV];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-    if (cc_[u] >= 0) {
-#pragma unroll
-      for (int t = 0; t < BC * NV; ++t)
-        xv[u][t] = NSFEM_KO(a.dbg == 2) ? (double)cc_[u] : x[(size_t)cc_[u] * (BC * NV) + t];
-    }
-  // products -> LDS.  Nonzero q = 4 tid + u of the aligned window is parked at slot u * 256 + tid:
-  // consecutive lanes write consecutive slots (the natural slot q would put the lanes 4 NO doubles
-  // apart: a 16-way bank conflict)
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-    if (cc_[u] >= 0) {
-      const int slot = u * 256 + tid;
-#pragma unroll
-      for (int r = 0; r < BR; ++r)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          double acc = 0.0;
-#pragma unroll
-          for (int cc = 0; cc < BC; ++cc) acc += av[u][r * BC + cc] * xv[u][cc * NV + v];
-          prod[slot * NO + r * NV + v] = acc;
-        }
-    }
-  __syncthreads();
-  // one thread per output entry (row, o); window position q of the row's k-th nonzero is
-  // k + (s0 - a0), its slot (q & 3) * 256 + (q >> 2)
-  const int shift = s0 - a0;
-  for (int t = tid; t < nout; t += 256) {
-    const int lrow = t / NO, o = t % NO;
-    const int row = r0 + lrow;
-    double val = 0.0;
-    int q = rp[lrow] + shift;
-    const int e = rp[lrow + 1] + shift;
-    for (; q + 4 <= e; q += 4) {          // 4 LDS reads in flight, summed in ascending order
-      const double v0 = prod[(((q)&3) * 256 + ((q) >> 2)) * NO + o];
-      const double v1 = prod[(((q + 1) & 3) * 256 + ((q + 1) >> 2)) * NO + o];
-      const double v2 = prod[(((q + 2) & 3) * 256 + ((q + 2) >> 2)) * NO + o];
-      const double v3 = prod[(((q + 3) & 3) * 256 + ((q + 3) >> 2)) * NO + o];
-      val += v0;
-      val += v1;
-      val += v2;
-      val += v3;
-    }
-    for (; q < e; ++q) val += prod[((q & 3) * 256 + (q >> 2)) * NO + o];
-    const size_t idx = (size_t)row * NO + o;
-    const bool first = (EPI == EPI_CHEB || EPI == EPI_RESID) && t == tid;
-    int mv = first ? pmv : ((a.maskmode != MASK_NONE) ? a.mask[idx] : 0);
-    if (mv == 2 && a.ghost == 2) mv = 0;
-    const bool m = mv != 0;
-    if (mv == 2) {
-      if (EPI == EPI_CHEB) {
-        a.d[idx] = 0.0;
-        a.y[idx] = a.ghost == 1 ? (first ? px : x[idx]) : 0.0;
-      } else {
-        a.y[idx] = 0.0;
-        if (EPI == EPI_STORE && a.y2) a.d[idx] = a.y2[idx] = 0.0;
-      }
-    } else if (EPI == EPI_RESID) {
-      const double bv = first ? pb : a.b[idx];
-      if (m)
-        val = (a.maskmode == MASK_IDENTITY) ? bv - x[idx] : 0.0;
-      else
-        val = bv - val;
-      a.y[idx] = val;
-    } else if (EPI == EPI_ACCUM) {
-      if (!m) a.y[idx] += a.c2 * val;
-      else if (a.maskmode == MASK_ZERO) a.y[idx] = 0.0;
-    } else if (EPI == EPI_CHEB) {
-      double dn = 0.0, xn = 0.0;
-      if (!m) {
-        dn = a.c2 * (first ? pdinv : a.dinv[idx]) * ((first ? pb : a.b[idx]) - val);
-        if (a.c1 != 0.0) dn += a.c1 * (first ? pd : a.d[idx]);
-        xn = (first ? px : x[idx]) + dn;
-      } else if (a.ident) {
-        xn = first ? pb : a.b[idx];
-      }
-      a.d[idx] = dn;
-      a.y[idx] = xn;
-    } else {
-      if (m) val = (a.maskmode == MASK_IDENTITY) ? x[idx] : 0.0;
-      else val *= a.c2;
-      a.y[idx] = val;
-      if (a.y2) {
-        const double dn = m ? 0.0 : a.c1 * a.dinv[idx] * val;
-        a.d[idx] = dn;
-        a.y2[idx] = dn;
-      }
-    }
-  }
-}
-
 // --- SELL-64 variant: one wavefront per slice of 64 rows, lane r walks row r through the
 // column-major slice (coalesced column / value loads, one entry of 64 different rows per pass).
 // On the parity-class numberings of the structured meshes the 64 column ids of a pass are
@@ -500,7 +317,7 @@ __global__ __launch_bounds__(256) void k_spmv_stream(int n_rblk, const int4* __r
 // ~50 scattered cache lines a CSR pass over 64 consecutive nonzeros of 2-3 rows touches.  No LDS,
 // no cross-lane reduction; the epilogues are those of the other kernels.  Same ascending order of
 // a row's entries as the CSR kernels.
-template <int NV, int EPI, int U, int PIPE>
+template <int NV, int EPI>
 __global__ __launch_bounds__(256) void k_spmv_sell(int n_rows, int n_slices, int n_wg,
                                                    const int32_t* __restrict__ sptr,
                                                    const int32_t* __restrict__ scol,
@@ -532,14 +349,14 @@ __global__ __launch_bounds__(256) void k_spmv_sell(int n_rows, int n_slices, int
   const int32_t* __restrict__ cp = scol + (size_t)base + lane;
   const double* __restrict__ vp = sval + (size_t)base + lane;
   // groups of U entries per lane: U column ids + U values (coalesced, non-temporal), then the U x
-  // gathers, all independent -> U (1 + NV) loads in flight per lane.  PIPE: the column ids / values
-  // of the next group are requested before the gathers of the current one are consumed.
+  // gathers, all independent -> U (1 + NV) loads in flight per lane.
   // branch-free: entries past the slice width re-read its last entry with a zero weight (the
   // select is wave-uniform); vmcnt retires loads in issue order, so the next group's column /
   // value loads are issued AFTER the gathers of the current group and stay in flight while the
   // gathers are consumed
-  int c[U], cn[U];
-  double v[U], vn[U];
+  constexpr int U = 4;
+  int c[U];
+  double v[U];
   auto fetch = [&](int k0, int* cc, double* vv) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -557,17 +374,11 @@ __global__ __launch_bounds__(256) void k_spmv_sell(int n_rows, int n_slices, int
       for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int t = 0; t < NV; ++t) xv[u][t] = x[(size_t)c[u] * NV + t];
-      if (PIPE && k + U < w) fetch(k + U, cn, vn);
 #pragma unroll
       for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int t = 0; t < NV; ++t) acc[t] += v[u] * xv[u][t];
-      if (PIPE) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) { c[u] = cn[u]; v[u] = vn[u]; }
-      } else if (k + U < w) {
-        fetch(k + U, c, v);
-      }
+      if (k + U < w) fetch(k + U, c, v);
     }
   }
   // epilogue with coalesced vector traffic: the wave's 64 rows x NV outputs are the CONTIGUOUS
@@ -1615,11 +1426,6 @@ bool lattice_smoother_available(const BlockMat& A, int nv) {
   const bool on = g_lattice_on;
   return on && A.dict_ready && A.dict && A.dict->lat_w >= 8 && A.br == 1 && A.bc == 1 && (nv == 1 || nv == 2);
 }
-bool lattice_tables_available(const BlockMat& A, int nv) {
-  return g_lattice_on && A.dict && A.dict->n_stencils > 0 && A.dict->n_stencils <= 64 && A.dict->lat_w > 0 &&
-         A.br == 1 && A.bc == 1 && (nv == 1 || nv == 2) && A.lat_vals.p != nullptr && A.dict_dinv.p != nullptr &&
-         (A.dict_ready || A.dict->tables_only);
-}
 int lattice_smoother_max_steps(const BlockMat& A, bool from_zero, bool with_resid) {
   // operator applications per launch: at most 3 (reach 2: halo 6) / 6 (reach 1: the same halo) -- the truncated
   // velocity cycle's coarse solve (7 steps from zero on a P1 level) is ONE launch
@@ -1699,10 +1505,9 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   a.from_zero = (x_in || xc) ? 0 : 1;
   a.xc = xc; a.rf = rf; a.b_out = b_out;
   a.gh_lo = gh_lo; a.gh_hi = gh_hi; a.gh_zero = gh_zero;
-  // entries of canonical interior shape (compile-time LDS offsets in the stages; NSFEM_LATTICE_FIXED=0: off)
+  // entries of canonical interior shape (compile-time LDS offsets in the stages)
   ensure_fixed_masks(d);
-  static const bool fixed_on = [] { const char* e = std::getenv("NSFEM_LATTICE_FIXED"); return e ? std::atoi(e) != 0 : true; }();
-  const bool fixed_use = (ovr && ovr->fixed >= 0) ? ovr->fixed != 0 : fixed_on;
+  const bool fixed_use = (ovr && ovr->fixed >= 0) ? ovr->fixed != 0 : true;
   a.fixed_shape = (fixed_use && d.fixed_shape > 0) ? d.fixed_shape : 0;
   for (int c = 0; c < 4; ++c) a.fixed_mask[c] = a.fixed_shape ? d.fixed_mask[c] : 0ull;
   a.Wc = (d.lat_w + 1) / 2; a.Wf = 2 * d.lat_w - 1; a.Hf = 2 * d.lat_h - 1;
@@ -1721,18 +1526,16 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   const int64_t nn = (int64_t)a.W * a.H;
   // (measured, 2D cavity n = 512, 3 steps on the P2 lattice: 24 lines 43 us warm / 49 us cold, 32 lines
   // 48 / 56 us -- 21 spilled registers under the 128-VGPR cap and 1040 tiles on 512 workgroup slots)
-  static const int64_t eh24_from = [] { const char* e = std::getenv("NSFEM_LATTICE_EH24_FROM"); return e ? std::atoll(e) : 20000ll; }();
-  int eh = nn >= eh24_from ? 24 : 16;
-  static const int force_eh = [] { const char* e = std::getenv("NSFEM_LATTICE_EH"); return e ? std::atoi(e) : 0; }();
+  constexpr int64_t kEh24From = 20000;
+  int eh = nn >= kEh24From ? 24 : 16;
   // 48 lines: ONE workgroup of 1024 threads per CU (four waves per parity class, the same three slots per thread and
   // the same 4 waves per SIMD as two 24-line workgroups): the halo is shared by twice the output lines -- 1.64
   // instead of 2.46 staged nodes per output node at a 6-line halo, 1.20 instead of 1.45 row-steps per useful one.
   // Measured (round 4): n = 512 (1.05 M nodes) 1.94 vs 1.925 ms/step with 24 lines, n = 1024 (4.2 M nodes) 7.21 vs
   // 7.29 -- the launch is bound by the latency chain of a workgroup, not by the halo; 16-wave barriers cost what the
   // halo saves.  On from 2 M lattice nodes.
-  static const int tall_from = [] { const char* e = std::getenv("NSFEM_LATTICE_TALL_FROM"); return e ? std::atoi(e) : 2000000; }();
-  if (nn >= tall_from && a.H >= 96) eh = 48;
-  if (force_eh == 16 || force_eh == 24 || force_eh == 32 || force_eh == 48) eh = force_eh;
+  constexpr int64_t kTallFrom = 2000000;
+  if (nn >= kTallFrom && a.H >= 96) eh = 48;
   if (ovr && ovr->tile_lines != 0) {
     // (a forced height is one the rule below could pick for this halo, or the call is refused)
     const int f = ovr->tile_lines;
@@ -1781,9 +1584,7 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   for (int k = 0; k < 8; ++k) { a.c1[k] = k < steps ? c1[k] : 0.0; a.c2[k] = k < steps ? c2[k] : 0.0; }
   const size_t lds = (size_t)2 * 4 * 32 * a.EHh * nv * 8;
   const int grid = (a.ntiles + 7) & ~7;
-  // launch shape (tuning switch NSFEM_LATTICE_SHAPE): 0 = 4 waves per SIMD (<= 128 VGPRs: two workgroups per
-  // CU), 1 = 2 waves per SIMD (no register cap: one workgroup per CU)
-  static const int shape = [] { const char* e = std::getenv("NSFEM_LATTICE_SHAPE"); return e ? std::atoi(e) : 0; }();
+  // launch shape: 4 waves per SIMD (<= 128 VGPRs: two workgroups per CU)
 #define NSFEM_LAT(NV, KK, WPE, WPC, GH, KIND)                                                          \
   do {                                                                                                 \
     static bool attr_dev[64];                                                                          \
@@ -1807,8 +1608,8 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
     else NSFEM_LAT(NV, 2, WPE, 2, GH, KIND);                  \
   } while (0)
   // launch kind: the specialised instantiations cover what the cycles and the mass solve launch on one context at the
-  // default shape; everything else (strips, tuning shapes, other operand sets) runs the runtime-flag kernel
-  const int kind = (shape == 0 && g_lattice_kinds_on && !(ovr && ovr->generic))
+  // default shape; everything else (strips, other operand sets) runs the runtime-flag kernel
+  const int kind = (g_lattice_kinds_on && !(ovr && ovr->generic))
                        ? lattice_launch_kind(x_in != nullptr, xc != nullptr, rf != nullptr, d_in != nullptr,
                                              d_out != nullptr, r_out != nullptr, gh_lo > 0 || gh_hi > 0)
                        : 0;
@@ -1831,17 +1632,13 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
     }                                                                                           \
   } while (0)
   // (the frozen ghost lines of partitioned strips are a template flag: the single-context launches do not pay for
-  // them -- 811 vs 758 VALU instructions per wave; strips always use the default launch shape)
+  // them -- 811 vs 758 VALU instructions per wave)
   const bool gh = gh_lo > 0 || gh_hi > 0;
   if (kind != 0 && nv == 2) NSFEM_LAT_KINDS(2);
   else if (kind != 0) NSFEM_LAT_KINDS(1);
   else if (gh && nv == 2) NSFEM_LAT_K(2, 4, true, 0);
   else if (gh) NSFEM_LAT_K(1, 4, true, 0);
-  else if (nv == 2 && shape == 1) NSFEM_LAT_K(2, 2, false, 0);
-  else if (nv == 2 && shape == 2) NSFEM_LAT_K(2, 6, false, 0);
   else if (nv == 2) NSFEM_LAT_K(2, 4, false, 0);
-  else if (shape == 1) NSFEM_LAT_K(1, 2, false, 0);
-  else if (shape == 2) NSFEM_LAT_K(1, 6, false, 0);
   else NSFEM_LAT_K(1, 4, false, 0);
 #undef NSFEM_LAT_KINDS
 #undef NSFEM_LAT_K
@@ -2029,18 +1826,12 @@ __global__ __launch_bounds__(256) void k_dict_fill(int64_t len, int bsz, const i
 }
 
 bool build_stencil_dict(hipStream_t s, const Pattern& p, const double* dev_a, const double* dev_b,
-                        StencilDict& d, int bsz, bool rect, int min_rows_lattice) {
+                        StencilDict& d, int bsz, bool rect) {
   d.n_stencils = 0;
   d.max_local = 0;
-  d.tables_only = false;
   const char* env = std::getenv("NSFEM_DICT");        // (read per context: tests switch it)
   const bool enabled = env ? std::atoi(env) != 0 : true;
-  // (>= 1024 rows: lattice levels down to 33 x 33 nodes get a dictionary; NSFEM_DICT_MIN_ROWS overrides)
-  const char* env_min = std::getenv("NSFEM_DICT_MIN_ROWS");
-  const int min_rows_full = env_min ? std::atoi(env_min) : 1024;
-  // (smaller patterns: accepted only as 2D lattices, for the fused multigrid legs -- see the end)
-  const bool small = p.n_rows < min_rows_full;
-  const int min_rows = (min_rows_lattice > 0 && !rect && bsz == 1) ? std::min(min_rows_lattice, min_rows_full) : min_rows_full;
+  constexpr int min_rows = 1024;     // (lattice levels down to 33 x 33 nodes get a dictionary)
   if (!enabled || p.n_rows < min_rows || p.h_rowptr.empty() || (!rect && p.n_rows != p.n_cols)) return false;
   const int n = p.n_rows;
   const size_t nval = (size_t)p.nnz * bsz;
@@ -2240,13 +2031,6 @@ bool build_stencil_dict(hipStream_t s, const Pattern& p, const double* dev_a, co
     }
   }
   NSFEM_HIP(hipStreamSynchronize(s));
-  if (small) {
-    if (d.lat_w == 0) {            // a small pattern that is no lattice: no dictionary (as before)
-      d.n_stencils = 0;
-      return false;
-    }
-    d.tables_only = true;
-  }
   return true;
 }
 
@@ -2271,7 +2055,7 @@ void BlockMat::sell_update(hipStream_t s) {
         NSFEM_HIP(hipGetLastError());
       }
     }
-    dict_ready = !dict->tables_only;
+    dict_ready = true;
   }
   sell_ready = false;
   if (!pat || pat->n_slices == 0 || br != 1 || bc != 1) return;
@@ -2286,8 +2070,7 @@ void BlockMat::sell_update(hipStream_t s) {
 // greedy row blocks with <= kStreamNnz nonzeros (host, once per pattern); patterns with a
 // longer row keep n_rblk = 0 and use the lane-group kernel
 void build_rowblocks(Pattern& p, hipStream_t s) {
-  // (1020 = 1024 - 4: the kernel reads a 16-byte aligned window of 256 column quads over the chunk)
-  constexpr int kLimit = kStreamNnz - 4;
+  constexpr int kLimit = kStreamNnz - 4;   // (4 short of the LDS product buffer: the chunking of every recorded profile)
   std::vector<int32_t> blk;
   blk.push_back(0);
   int start = 0;
@@ -2304,17 +2087,7 @@ void build_rowblocks(Pattern& p, hipStream_t s) {
   if (ok) {
     blk.push_back(p.n_rows);
     p.n_rblk = (int)blk.size() - 1;
-    std::vector<int32_t> info((size_t)p.n_rblk * 4);
-    for (int b = 0; b < p.n_rblk; ++b) {
-      info[4 * b] = blk[b];
-      info[4 * b + 1] = blk[b + 1];
-      info[4 * b + 2] = p.h_rowptr[blk[b]];
-      info[4 * b + 3] = p.h_rowptr[blk[b + 1]];
-    }
-    p.rblk.upload(info, s);
     p.rblk1.upload(blk, s);
-    p.max_chunk_rows = 0;
-    for (int b = 0; b < p.n_rblk; ++b) p.max_chunk_rows = std::max(p.max_chunk_rows, blk[b + 1] - blk[b]);
     p.h_rblk.swap(blk);
   }
   p.int_b0 = p.int_b1 = 0;
@@ -2378,10 +2151,6 @@ void mark_interior_blocks(Pattern& p, const std::vector<uint8_t>& ghost_cols) {
 template <int EPI>
 static void spmv_dispatch(hipStream_t s, const BlockMat& A, int nv, const SpmvArgs& a_in) {
   const Pattern& p = *A.pat;
-  static const int use_stream = [] {
-    const char* e = std::getenv("NSFEM_SPMV_STREAM");
-    return e ? std::atoi(e) : -1;          // -1: per-shape default
-  }();
   if (A.dict_ready && A.dict->rect && (a_in.dict_ok || A.dict->exact) && a_in.phase == 0 && nv == 1 &&
       (EPI == EPI_STORE || EPI == EPI_ACCUM) && !a_in.y2) {
     const StencilDict& d = *A.dict;
@@ -2453,58 +2222,36 @@ static void spmv_dispatch(hipStream_t s, const BlockMat& A, int nv, const SpmvAr
     XcdSplit xs;
     for (int x = 0; x < 9; ++x) xs.s[x] = 0;
     int grid = (nwg + 7) & ~7;
-    static const int balance = [] {
-      const char* e = std::getenv("NSFEM_SELL_BALANCE");
-      return e ? std::atoi(e) : 1;
-    }();
-    if (a.phase == 0 && balance) {          // whole operator: balanced contiguous XCD ranges
+    if (a.phase == 0) {          // whole operator: balanced contiguous XCD ranges
       int most = 0;
       for (int x = 0; x < 9; ++x) xs.s[x] = p.sell_xcd[x];
       for (int x = 0; x < 8; ++x) most = std::max(most, xs.s[x + 1] - xs.s[x]);
       grid = 8 * most;
     }
-#define NSFEM_SELL_LAUNCH(NV, U, PIPE)                                                               \
-  hipLaunchKernelGGL((k_spmv_sell<NV, EPI, U, PIPE>), dim3(grid), dim3(256), 0, s, p.n_rows,         \
+    // groups of 4 entries per lane, 8 waves per SIMD: measured 247-253 us on the 3D n = 64 smoothing launch against
+    // groups of 8: 264 us, 8 software pipelined: 255-263 us, 12 / 10 pipelined: 256-267 us
+#define NSFEM_SELL_LAUNCH(NV)                                                                        \
+  hipLaunchKernelGGL((k_spmv_sell<NV, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows,                  \
                      p.n_slices, nwg, p.sell_ptr.p, p.sell_col.p, A.sell_vals.p, a, xs)
-    // tuning switch (smoother epilogue only): NSFEM_SELL_VARIANT = 0 (groups of 4 entries, 8 waves
-    // per SIMD: default -- measured 247-253 us on the 3D n = 64 smoothing launch), 1 (groups of 8:
-    // 264 us), 2 (8, software pipelined: 255-263 us), 3 (12 / 10 pipelined: 256-267 us)
-    static const int variant = [] {
-      const char* e = std::getenv("NSFEM_SELL_VARIANT");
-      return e ? std::atoi(e) : 0;
-    }();
-    const int var = EPI == EPI_CHEB ? variant : 0;
-#define NSFEM_SELL_NV(NV, UBIG)                        \
-  do {                                                 \
-    if (var == 0) NSFEM_SELL_LAUNCH(NV, 4, 0);         \
-    else if (var == 1) NSFEM_SELL_LAUNCH(NV, 8, 0);    \
-    else if (var == 3) NSFEM_SELL_LAUNCH(NV, UBIG, 1); \
-    else NSFEM_SELL_LAUNCH(NV, 8, 1);                  \
-  } while (0)
-    if (nv == 1) NSFEM_SELL_NV(1, 12);
-    else if (nv == 2) NSFEM_SELL_NV(2, 12);
-    else NSFEM_SELL_NV(3, 10);
-#undef NSFEM_SELL_NV
+    if (nv == 1) NSFEM_SELL_LAUNCH(1);
+    else if (nv == 2) NSFEM_SELL_LAUNCH(2);
+    else NSFEM_SELL_LAUNCH(3);
 #undef NSFEM_SELL_LAUNCH
     NSFEM_HIP(hipGetLastError());
     return;
   }
-  const bool shape22 = A.br == 2 && A.bc == 2;
   // measured (n = 512): the stream kernel wins on every operator except the short-row P2 x P1
   // gradient (4.6 entries per row), which keeps the lane-group kernel
   const bool long_rows = (double)p.nnz >= 6.0 * p.n_rows;
-  const bool stream = p.n_rblk > 0 &&
-                      (use_stream == 1 || (use_stream == -1 && kStreamDefault(shape22) && long_rows));
+  const bool stream = p.n_rblk > 0 && long_rows;
   if (stream) {
     // interior / halo-adjacent split of a partitioned product (see product_with_halo)
     SpmvArgs a = a_in;
     int nb = p.n_rblk;
-    const int4* rb = reinterpret_cast<const int4*>(p.rblk.p);
     a.skip0 = nb;
     a.skipn = 0;
     if (a.phase == 1) {
       nb = p.int_b1 - p.int_b0;
-      rb += p.int_b0;
       a.skip0 = nb;
     } else if (a.phase == 2) {
       nb = p.n_rblk - (p.int_b1 - p.int_b0);
@@ -2513,23 +2260,10 @@ static void spmv_dispatch(hipStream_t s, const BlockMat& A, int nv, const SpmvAr
     }
     if (nb <= 0) return;
     const int grid = (nb + 7) & ~7;
-    static const int version = [] {
-      // measured in situ (round 2): v1 44-46 us / 278 us (2D n = 512 / 3D n = 64 finest-level smoothing
-      // launch), v2 45-47 us / 303 us -- v2 only wins cache-cold in 2D (49-52 vs 54-58 us)
-      const char* e = std::getenv("NSFEM_STREAM_V");
-      return e ? std::atoi(e) : 1;
-    }();
     const int32_t* rb1 = p.rblk1.p + (a.phase == 1 ? p.int_b0 : 0);
-#define NSFEM_STREAM(BR, BC, NV)                                                              \
-  do {                                                                                        \
-    if (version == 1)                                                                         \
-      hipLaunchKernelGGL((k_spmv_stream_v1<BR, BC, NV, EPI>), dim3(grid), dim3(256), 0, s, nb, \
-                         rb1, p.rowptr.p, p.col.p, A.vals.p, a);                              \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_spmv_stream<BR, BC, NV, EPI>), dim3(grid), dim3(256),              \
-                         (size_t)kStreamNnz * (BR * NV) * 8 + (size_t)(p.max_chunk_rows + 2) * 4, s, \
-                         nb, rb, p.rowptr.p, p.col.p, A.vals.p, a);                           \
-  } while (0)
+#define NSFEM_STREAM(BR, BC, NV)                                                            \
+  hipLaunchKernelGGL((k_spmv_stream_v1<BR, BC, NV, EPI>), dim3(grid), dim3(256), 0, s, nb,  \
+                     rb1, p.rowptr.p, p.col.p, A.vals.p, a)
     if (A.br == 2 && A.bc == 2 && nv == 1) NSFEM_STREAM(2, 2, 1);
     else if (A.br == 1 && A.bc == 1 && nv == 2) NSFEM_STREAM(1, 1, 2);
     else if (A.br == 1 && A.bc == 1 && nv == 1) NSFEM_STREAM(1, 1, 1);
@@ -2548,21 +2282,15 @@ static void spmv_dispatch(hipStream_t s, const BlockMat& A, int nv, const SpmvAr
   // phase computes every row)
   if (a_in.phase == 1) return;
   const SpmvArgs& a = a_in;
-  // lanes per block row: 4 for short rows (P1 7-point, P2 x P1), 8 otherwise; the
-  // NSFEM_SPMV_G environment variable overrides it (tuning experiments only)
-  static const int forced = [] {
-    const char* e = std::getenv("NSFEM_SPMV_G");
-    return e ? std::atoi(e) : 0;
-  }();
-  // measured on MI355X (scripts/gpu_spmv_sweep.py, n = 512): rows with <= ~200 B of matrix data
+  // lanes per block row: 4 for short rows (P1 7-point, P2 x P1), 8 otherwise
+  // measured on MI355X (n = 512): rows with <= ~200 B of matrix data
   // (scalar P2 / P1 operators, grad) run 15-30 % faster with 4 lanes per row, the 2x2
   // Jacobian (414 B/row) and div (460 B/row) with 8
   const double row_bytes = (double)p.nnz / (p.n_rows > 0 ? p.n_rows : 1) * (8.0 * A.br * A.bc + 4.0);
-  int G = forced ? forced : (row_bytes <= 200.0 ? 4 : (row_bytes <= 1600.0 ? 8 : 16));
+  int G = row_bytes <= 200.0 ? 4 : (row_bytes <= 1600.0 ? 8 : 16);
   // interpolation-type operators (<= 2 entries per row, e.g. the P2 <- P1 prolongation): two
   // lanes per row are enough and halve the idle lanes (needs G >= outputs per row)
-  if (!forced && (double)p.nnz <= 2.2 * p.n_rows && A.br * nv <= 2) G = 2;
-  if (G != 2 && G != 4 && G != 8 && G != 16) G = 8;
+  if ((double)p.nnz <= 2.2 * p.n_rows && A.br * nv <= 2) G = 2;
   if (G < A.br * nv) G = 4;
   const int rpb = 256 / G;
   int grid = (p.n_rows + rpb - 1) / rpb;
@@ -2602,12 +2330,7 @@ static SpmvArgs make_args(const double* x, const double* b, double* y, const uin
   a.x = x; a.b = b; a.y = y; a.mask = mask;
   a.maskmode = mask ? maskmode : MASK_NONE;
   a.dinv = nullptr; a.d = nullptr; a.c1 = 0.0; a.c2 = 1.0;
-  static const int nt = [] {
-    // measured (n = 512, in-situ smoother launches, 3 runs each): 52.8 us vs 53.6 us without
-    const char* e = std::getenv("NSFEM_SPMV_NT");
-    return e ? std::atoi(e) : 1;
-  }();
-  a.nt = nt;
+  a.nt = 1;       // measured (n = 512, in-situ smoother launches, 3 runs each): 52.8 us vs 53.6 us without
   a.ghost = 0;
   a.skip0 = 0x7fffffff;
   a.skipn = 0;
@@ -2634,8 +2357,7 @@ static SpmvArgs make_args(const double* x, const double* b, double* y, const uin
 // dictionary copy (the caller multiplies and gathers separately).
 bool launch_spmv_with_gather(hipStream_t s, const BlockMat& A, int nv, const double* x, double* y,
                              const uint8_t* rowmask, int maskmode, const int32_t* gptr, const double* gbuf) {
-  static const bool on = [] { const char* e = std::getenv("NSFEM_FUSED_GATHER"); return e ? std::atoi(e) != 0 : true; }();
-  if (!on || !A.dict_ready || A.dict->rect || A.br != 1 || A.bc != 1 || nv < 1 || nv > 3) return false;
+  if (!A.dict_ready || A.dict->rect || A.br != 1 || A.bc != 1 || nv < 1 || nv > 3) return false;
   SpmvArgs a = make_args(x, nullptr, y, rowmask, maskmode);
   a.dict_ok = 1;
   a.gptr = gptr;
@@ -3097,8 +2819,7 @@ __global__ __launch_bounds__(256) void k_publish(const double* __restrict__ part
 // the host side: launch, spin on the sequence number (the stream is in order: everything queued before has finished
 // when it arrives); a stream error ends the wait
 static void publish_and_wait(hipStream_t s, KrylovWork& w, int n, const int slot[4], double out[4]) {
-  static const bool copy_path = std::getenv("NSFEM_SYNC_COPY") != nullptr;      // (the round-3 path, for A/B timing)
-  if (copy_path || !w.h_res) {
+  if (!w.h_res) {
     int lo = slot[0], hi = slot[0];
     for (int k = 1; k < n; ++k) { lo = std::min(lo, slot[k]); hi = std::max(hi, slot[k]); }
     NSFEM_HIP(hipMemcpyAsync(w.h_parts + (size_t)lo * kParts, w.parts.p + (size_t)lo * kParts,
@@ -3724,12 +3445,11 @@ int pcg(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, double* 
     if (op.ghostmask) launch_zero_ghost(s, n, op.ghostmask, w.t.p);
     rhs = w.t.p;
   }
-  static const bool single_reduction = std::getenv("NSFEM_CG_TWO_REDUCTIONS") == nullptr;
-  if (op.prec && single_reduction) return pcg_single_reduction(s, w, op, rhs, x, o, info);
+  if (op.prec) return pcg_single_reduction(s, w, op, rhs, x, o, info);
+  // classic CG with the Jacobi preconditioner op.dinv
   launch_residual(s, *op.A, op.nv, x, rhs, w.r.p, op.rowmask, op.maskmode);
   int cur = P_RZ0, nxt = P_RZ1;
-  if (op.prec) op.prec->apply(s, w.r.p, w.p.p);
-  LAUNCH(k_cg_start, kParts, s, n, w.r.p, op.prec ? nullptr : op.dinv, w.p.p, parts, cur);
+  LAUNCH(k_cg_start, kParts, s, n, w.r.p, op.dinv, w.p.p, parts, cur);
   // |b| next to (r.z, |r0|^2) -- the first slot of the other (r.z, |r|^2) pair, rewritten by the
   // first iteration: one all-reduce for the three start-up sums
   launch_dot(s, n, rhs, rhs, parts + (cur + 2) * kParts);
@@ -3752,12 +3472,7 @@ int pcg(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, double* 
     });
     launch_dot(s, n, w.p.p, w.q.p, parts + P_PQ * kParts);
     reduce_slots(op, s, parts, P_PQ, 1);
-    LAUNCH(k_cg_update, kParts, s, n, w.p.p, w.q.p, op.prec ? nullptr : op.dinv, x, w.r.p, w.z.p,
-           parts, cur_, nxt_);
-    if (op.prec) {
-      op.prec->apply(s, w.r.p, w.z.p);
-      launch_dot(s, n, w.r.p, w.z.p, parts + nxt_ * kParts);
-    }
+    LAUNCH(k_cg_update, kParts, s, n, w.p.p, w.q.p, op.dinv, x, w.r.p, w.z.p, parts, cur_, nxt_);
     reduce_slots(op, s, parts, nxt_, 2);
     LAUNCH(k_cg_p, kParts, s, n, w.z.p, w.p.p, parts, cur_, nxt_);
   };

@@ -388,7 +388,6 @@ void Multigrid::setup_work(hipStream_t s) {
 
 // masks (host, level 0) -> coarse levels by injection; dinv, lambda_max, coarse inverse
 void Multigrid::refresh(hipStream_t s, const std::vector<uint8_t>& mask0, bool singular) {
-  legs_kind = -1;                  // fused launches are planned again from the new masks / coefficients
   std::vector<uint8_t> cur = mask0, nxt;
   std::vector<double> hp(kParts);
   const size_t n_used = truncated() ? active : lv.size();
@@ -635,8 +634,8 @@ bool ghost_lattice_lines(const std::vector<uint8_t>& g, int W, int H, int& lo, i
 }
 
 bool Multigrid::lattice_ok_relaxed(MGLevel& L) {
-  if (L.additive || !(comm_active() && L.has_halo) || !relaxed_halo || !partitioned_lattice_kernels() ||
-      !lattice_smoother_available(*L.A, nv) || !L.h_ghost)
+  if (L.additive || !(comm_active() && L.has_halo) || !relaxed_halo || !lattice_smoother_available(*L.A, nv) ||
+      !L.h_ghost)
     return false;
   if (L.ghost_lo == -2) {
     int lo, hi;
@@ -869,9 +868,8 @@ bool Multigrid::starts_from_zero(size_t l) const {
 bool Multigrid::restrict_to(hipStream_t s, size_t l, const double* src) {
   MGLevel& L = lv[l];
   MGLevel& C = lv[l + 1];
-  static const bool fuse = std::getenv("NSFEM_NO_FUSED_FIRST") == nullptr;
   // (levels smoothed by the lattice kernel run their first step themselves)
-  if (fuse && starts_from_zero(l + 1) && !lattice_ok(C) && !lattice_ok_relaxed(C)) {
+  if (starts_from_zero(l + 1) && !lattice_ok(C) && !lattice_ok_relaxed(C)) {
     double c1, c2, rho;
     cheb_coeffs(C, 0, 0.0, c1, c2, rho);
     launch_spmv_cheb_first(s, *L.R, nv, src, C.b.p, C.mask, C.dinv.p, c2, C.d.p, C.xa.p);
@@ -1079,7 +1077,6 @@ const double* Multigrid::vcycle(hipStream_t s, size_t l, const double* b, double
 void Multigrid::apply(hipStream_t s, const double* r, double* z) {
   NSFEM_REQUIRE(ready, "multigrid hierarchy not refreshed");
   restricted_to = 0;
-  if (vcycle_legs(s, r, z)) return;                 // fused multi-level launches (mglegs.hip)
   (void)vcycle(s, 0, r, z);                         // (level 0: the result is in z)
 }
 

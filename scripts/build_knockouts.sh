@@ -9,7 +9,7 @@ SRC=navierstokes-with-fenics_amd/csrc
 OUT=build/knockouts
 mkdir -p $OUT
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DNSFEM_KNOCKOUTS=1"
-for f in assembly assembly3d boundary linalg multigrid mglegs comm api; do
+for f in assembly assembly3d boundary linalg multigrid comm api; do
   [ -f $SRC/$f.hip ] && /opt/rocm/bin/hipcc $FLAGS -c $SRC/$f.hip -o $OUT/$f.o &
 done
 /opt/rocm/bin/hipcc $FLAGS -x hip -c $SRC/pattern.cpp -o $OUT/pattern.o

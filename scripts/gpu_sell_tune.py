@@ -1,5 +1,5 @@
 """Scratch: cold-cache (flush-interleaved) time of the finest-level smoothing launch for one
-numbering / kernel variant.  usage: gpu_sell_tune.py DIM N lex|parity   (env NSFEM_SELL, NSFEM_SELL_VARIANT)"""
+numbering / kernel variant.  usage: gpu_sell_tune.py DIM N lex|parity   (env NSFEM_SELL, NSFEM_DICT)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "navierstokes-with-fenics_amd")]
@@ -17,7 +17,7 @@ attach_hierarchy(ctx, mesh)
 ctx.set_coeffs(1.0, 1.0, 0.01)
 ctx.set_bdf((1.5, -2.0, 0.5), 1e-3 if dim == 2 else 0.25 / n)
 ms, nb = ctx.time_spmv(nat.OP_MOMENTUM_SMOOTHER, 100)
-print("block %s balance %s " % (os.environ.get("PARITY_BLOCK", "-"), os.environ.get("NSFEM_SELL_BALANCE", "1")), end="")
+print("block %s " % os.environ.get("PARITY_BLOCK", "-"), end="")
 info = ctx.smoother_info()
 print("dim %d n %d %-6s kernel %s (NSFEM_DICT=%s NSFEM_SELL=%s): smoother cold %.1f us  %.2f TB/s of its own algorithmic bytes "
       "(%.0f MB; CSR-equivalent %.0f MB = %.2f TB/s)" % (

@@ -166,8 +166,8 @@ def _same(a, b, key):
         assert np.array_equal(a[k], b[k]), (key, k, diff, rel(a[k], b[k]))
 
 
-# (space, nx, ny); the kernel runs on lattices of >= 1024 rows and >= 8 columns (smaller levels keep their
-# dictionary tables for the fused multigrid legs only)
+# (space, nx, ny); the kernel runs on lattices of >= 1024 rows and >= 8 columns (smaller levels get no stencil
+# dictionary)
 SHAPE_CASES = [
     (1, 8, 120),         # P1 9 x 121: the narrowest lattice the kernel takes, one tile in x, taller than wide
     (1, 56, 24),         # P1 57 x 25: just above the 56-node output width of a 4-node halo, wider than tall
