@@ -997,8 +997,10 @@ static bool use_matrix_free(const nsfem_ctx* c, const nsfem_step_opts* o) {
 // J dx = b ; u* -= dx
 // known_rhs_norm >= 0: |rhs_v|_2 as the caller has just evaluated it (the Newton residual norm): the solve starts
 // without reading its start-up sums back
+// rhs_dead: the caller recomputes rhs_v before anything reads it again (the Newton loops: momentum_residual follows);
+// the solver may then use it as scratch.  Not so behind nsfem_solve: nsfem_get_rhs / nsfem_residual_norm may follow.
 static int momentum_solve_update(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_info& info,
-                                 double known_rhs_norm = -1.0) {
+                                 double known_rhs_norm = -1.0, bool rhs_dead = false) {
   hipStream_t s = c->stream;
   LinOp op;
   op.A = &c->J;
@@ -1022,6 +1024,7 @@ static int momentum_solve_update(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem
   op.graph_epoch = c->graph_epoch;
   op.x_zero = true;                 // (dx_v is not read: the first update of the solve writes it)
   op.known_bnorm = known_rhs_norm;
+  op.b_scratch = rhs_dead;
   int rc = bicgstab(s, c->kw, op, c->rhs_v.p, c->dx_v.p, o, info);
   if (rc != NSFEM_OK) return rc;
   double* u = c->state[NSFEM_USTAR].p;
@@ -2113,7 +2116,7 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     nsfem_solve_info si;
     nsfem_ctx::SolveHint& hint = ctx->hint_mom[std::min(it, 3)];
     const nsfem_krylov_opts ko = forced_opts(opts, opts->momentum, r0);
-    int rc = momentum_solve_update(ctx, hinted(ko, hint), si, r);
+    int rc = momentum_solve_update(ctx, hinted(ko, hint), si, r, true);
     note_solve(hint, si, ko, ctx->kw.last_target);
     inf.krylov_iterations_momentum += si.iterations;
     if (rc == NSFEM_ERR_BREAKDOWN) throw Error(rc, "BiCGStab breakdown in the diffusion step");
@@ -2605,6 +2608,7 @@ extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem
     const nsfem_krylov_opts ko = forced_opts(opts, opts->momentum, r0);
     op.x_zero = true;               // (dx_m is not read: the first update of the solve writes it)
     op.known_bnorm = r;             // |rhs_m| = the Newton residual norm just evaluated (bdf_residual)
+    op.b_scratch = true;            // (bdf_residual below rewrites rhs_m before anything reads it)
     int rc = bicgstab(s, ctx->kw, op, ctx->rhs_m.p, ctx->dx_m.p, hinted(ko, hint), si);
     note_solve(hint, si, ko, ctx->kw.last_target);
     inf.krylov_iterations_momentum += si.iterations;

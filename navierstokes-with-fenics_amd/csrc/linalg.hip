@@ -1413,9 +1413,12 @@ bool lattice_offsets_fit(int64_t w, int64_t h, int nv, bool rf) {
 // can smoothing steps of this operator run in the lattice kernel?
 // tuning / test switches, re-read whenever a context is created (tests switch them between contexts)
 static bool g_lattice_on = true, g_lattice_transfers_on = true, g_lattice_kinds_on = true;
+static bool g_bicg_fused = true;     // NSFEM_BICG_FUSED=0: BiCGStab with the start kernel and one launch per update (A/B, tests)
 void refresh_env_switches() {
   const char* e = std::getenv("NSFEM_LATTICE");
   g_lattice_on = e ? std::atoi(e) != 0 : true;
+  e = std::getenv("NSFEM_BICG_FUSED");
+  g_bicg_fused = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_LATTICE_KINDS");           // 0: every launch runs the runtime-flag kernel (A/B, tests)
   g_lattice_kinds_on = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_LATTICE_TRANSFERS");
@@ -2889,7 +2892,9 @@ enum { P_RHO = 0, P_RR = 1, P_TS = 2, P_TT = 3, P_RTV = 4, P_PQ = 5, P_RZ0 = 6, 
 // (P_R0, P_B0: |r0|^2 and |b|^2 of the running solve, kept until the first convergence check reads them together
 // with the current residual -- a solve without communicator starts without a device -> host round trip)
 // device scalars
-enum { S_RHO_OLD = 0, S_ALPHA = 1, S_OMEGA = 2, S_RHO = 3, S_RHAT2 = 4, S_RHAT2_NEXT = 5 };
+enum { S_RHO_OLD = 0, S_ALPHA = 1, S_OMEGA = 2, S_RHO = 3, S_RHAT2 = 4, S_RHAT2_NEXT = 5, S_RHO_NEXT = 6 };
+// (S_RHO_NEXT: the fused update k_bicg_xr<true> reads S_RHO in every block while block 0 stores the next rho, so the
+// next rho goes to a slot of its own and the following k_bicg_s moves it to S_RHO)
 
 // rhat = r ; parts[RHO] = parts[RR] = r.r
 // (rcopy: the residual is `r` itself still in the caller's right-hand side -- zero start vector -- and is stored
@@ -2931,10 +2936,12 @@ __global__ __launch_bounds__(256) void k_bicg_start(int64_t n, const double* __r
 __global__ __launch_bounds__(256) void k_bicg_p(int64_t n, int first, const double* __restrict__ r,
                                                 const double* __restrict__ v,
                                                 const double* __restrict__ dinv,
-                                                double* __restrict__ p, double* __restrict__ phat,
-                                                double* __restrict__ rhat,
+                                                const double* pold, double* p, double* __restrict__ phat,
+                                                double* rhat,
                                                 const double* __restrict__ parts,
                                                 double* __restrict__ scal) {
+  // (pold: the previous direction -- p itself, or the caller's right-hand side after the first iteration of a
+  // zero-start solve, where p1 = b was never stored; rhat may be that right-hand side too: no __restrict__ on them)
   __shared__ double sh[4];
   double rho = sum_parts(parts + P_RHO * kParts, sh);
   const double rr = sum_parts(parts + P_RR * kParts, sh);
@@ -2950,7 +2957,7 @@ __global__ __launch_bounds__(256) void k_bicg_p(int64_t n, int first, const doub
   }
   GRID_STRIDE(i, n) {
     const double ri = r[i];
-    const double pi = (first || restart) ? ri : ri + beta * (p[i] - omega * v[i]);
+    const double pi = (first || restart) ? ri : ri + beta * (pold[i] - omega * v[i]);
     p[i] = pi;
     if (restart) rhat[i] = ri;
     if (dinv) phat[i] = dinv[i] * pi;
@@ -2961,16 +2968,53 @@ __global__ __launch_bounds__(256) void k_bicg_p(int64_t n, int first, const doub
   }
 }
 
+// phat = dinv * b: the Jacobi-preconditioned first direction of a zero-start solve (p1 = b is not stored)
+__global__ __launch_bounds__(256) void k_bicg_phat0(int64_t n, const double* __restrict__ b,
+                                                    const double* __restrict__ dinv, double* __restrict__ phat) {
+  GRID_STRIDE(i, n) phat[i] = dinv[i] * b[i];
+}
+
+// First rhat.v of a zero-start solve (r0 = rhat = p1 = b): parts[RTV] = b.v, and beside it the start sums b.b that
+// k_bicg_start would have stored (the same loop, the same v += ri * ri: the same bits) -- no start kernel, no copies.
+// rhat: where the shadow residual is kept when it may not stay in b (nullptr: it stays there)
+__global__ __launch_bounds__(256) void k_bicg_dot0(int64_t n, const double* __restrict__ b,
+                                                   const double* __restrict__ vv, double* __restrict__ rhat,
+                                                   double* __restrict__ parts) {
+  __shared__ double sh[4];
+  double d = 0.0, v = 0.0;
+  GRID_STRIDE(i, n) {
+    const double ri = b[i];
+    if (rhat) rhat[i] = ri;
+    d += ri * vv[i];
+    v += ri * ri;
+  }
+  d = block_sum(d, sh);
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) {
+    parts[P_RTV * kParts + blockIdx.x] = d;
+    parts[P_RHO * kParts + blockIdx.x] = v;
+    parts[P_RR * kParts + blockIdx.x] = v;
+    parts[P_R0 * kParts + blockIdx.x] = v;
+    parts[P_TS * kParts + blockIdx.x] = v;
+    parts[P_B0 * kParts + blockIdx.x] = v;
+  }
+}
+
 // alpha = rho / (rhat.v) ; s = r - alpha v ; shat = dinv * s
+// rho comes from (mode) 0: scal[S_RHO] (k_bicg_p ran), 1: scal[S_RHO_NEXT] (the fused update of the previous iteration
+// formed p), 2: the start sums of k_bicg_dot0 (first iteration of a zero-start solve: this kernel also sets the
+// scalars k_bicg_start and k_bicg_p(first) would have set)
 __global__ __launch_bounds__(256) void k_bicg_s(int64_t n, const double* __restrict__ r,
                                                 const double* __restrict__ v,
                                                 const double* __restrict__ dinv,
                                                 double* __restrict__ sv, double* __restrict__ shat,
                                                 const double* __restrict__ parts,
-                                                double* __restrict__ scal) {
+                                                double* __restrict__ scal, int mode) {
   __shared__ double sh[4];
   const double rtv = sum_parts(parts + P_RTV * kParts, sh);
-  const double rho = scal[S_RHO];
+  double rho;
+  if (mode == 2) rho = sum_parts(parts + P_RHO * kParts, sh);
+  else rho = scal[mode == 1 ? S_RHO_NEXT : S_RHO];
   const double alpha = (rtv != 0.0) ? rho / rtv : 0.0;
   GRID_STRIDE(i, n) {
     const double si = r[i] - alpha * v[i];
@@ -2979,7 +3023,16 @@ __global__ __launch_bounds__(256) void k_bicg_s(int64_t n, const double* __restr
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     scal[S_ALPHA] = alpha;
-    scal[S_RHAT2] = scal[S_RHAT2_NEXT];
+    if (mode == 2) {
+      scal[S_RHO_OLD] = 1.0;
+      scal[S_OMEGA] = 1.0;
+      scal[S_RHO] = rho;
+      scal[S_RHAT2_NEXT] = rho;
+      scal[S_RHAT2] = rho;
+    } else {
+      if (mode == 1) scal[S_RHO] = rho;          // (no block reads S_RHO in this mode)
+      scal[S_RHAT2] = scal[S_RHAT2_NEXT];
+    }
   }
 }
 
@@ -3017,14 +3070,21 @@ __global__ __launch_bounds__(256) void k_dot_ts_tt(int64_t n, const double* __re
 }
 
 // omega = ts/tt ; x += alpha phat + omega shat ; r = s - omega t ; rho and |r|^2 of the new
-// residual from the five (already global) sums: block 0 stores them as the only non-zero partial
-__global__ __launch_bounds__(256) void k_bicg_xr(int64_t n, const double* __restrict__ phat,
+// residual from the five (already global) sums: block 0 stores them as the only non-zero partial.
+// FUSE: no convergence check follows, so the next direction is formed here as well (k_bicg_p's decision and per-entry
+// work with r_i from the register): p = r + beta (pold - omega v), rhat = r on restart, phat = dinv * p.  Every block
+// derives rho and |r|^2 from the five global sums itself -- never from the partials block 0 is writing -- and takes
+// the same decision.  (pold, p, rhat, phat may share storage with each other or the caller's b: no __restrict__)
+template <bool FUSE>
+__global__ __launch_bounds__(256) void k_bicg_xr(int64_t n, double* phat,
                                                  const double* __restrict__ shat,
                                                  const double* __restrict__ sv,
                                                  const double* __restrict__ t,
                                                  double* __restrict__ x, double* __restrict__ r,
                                                  double* __restrict__ parts,
-                                                 double* __restrict__ scal, int x_is_zero) {
+                                                 double* __restrict__ scal, int x_is_zero,
+                                                 const double* __restrict__ v, const double* __restrict__ dinv,
+                                                 const double* pold, double* p, double* rhat) {
   __shared__ double sh[4];
   const double ts = sum_parts(parts + P_TS * kParts, sh);
   const double tt = sum_parts(parts + P_TT * kParts, sh);
@@ -3034,25 +3094,55 @@ __global__ __launch_bounds__(256) void k_bicg_xr(int64_t n, const double* __rest
   const double omega = (tt > 0.0) ? ts / tt : 0.0;
   const double alpha = scal[S_ALPHA];
   const double rho = scal[S_RHO];
+  const double rr_new = fmax(ss - 2.0 * omega * ts + omega * omega * tt, 0.0);
+  const double rho_new = rhs - omega * rht;
+  // k_bicg_p's decision.  It reads the two values back through sum_parts, i.e. as value + 0.0 + ... + 0.0 (a -0.0
+  // becomes +0.0); rho_old is the rho of this iteration
+  double rho_p = rho_new + 0.0, rhat2 = 0.0, beta = 0.0;
+  bool restart = false;
+  if (FUSE) {
+    const double rr_p = rr_new + 0.0;
+    rhat2 = scal[S_RHAT2];
+    restart = rho_p * rho_p <= 1e-16 * rr_p * rhat2 || rho == 0.0 || omega == 0.0;
+    if (restart) {
+      rho_p = rr_p;
+      rhat2 = rr_p;
+    } else {
+      beta = (rho_p / rho) * (alpha / omega);
+    }
+  }
+  auto next_p = [&](int64_t i, double ri) {
+    const double pi = restart ? ri : ri + beta * (pold[i] - omega * v[i]);
+    p[i] = pi;
+    if (restart) rhat[i] = ri;
+    if (dinv) phat[i] = dinv[i] * pi;
+  };
   if (x_is_zero) {                       // (first iteration from a zero start vector: x is not read -- the caller
     GRID_STRIDE(i, n) {                  // did not have to clear it; 0 + v == v, the same bits)
       x[i] = alpha * phat[i] + omega * shat[i];
-      r[i] = sv[i] - omega * t[i];
+      const double ri = sv[i] - omega * t[i];
+      r[i] = ri;
+      if (FUSE) next_p(i, ri);
     }
   } else {
     GRID_STRIDE(i, n) {
       x[i] += alpha * phat[i] + omega * shat[i];
-      r[i] = sv[i] - omega * t[i];
+      const double ri = sv[i] - omega * t[i];
+      r[i] = ri;
+      if (FUSE) next_p(i, ri);
     }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const double rr = fmax(ss - 2.0 * omega * ts + omega * omega * tt, 0.0);
-    parts[P_RR * kParts + blockIdx.x] = blockIdx.x == 0 ? rr : 0.0;
-    parts[P_RHO * kParts + blockIdx.x] = blockIdx.x == 0 ? rhs - omega * rht : 0.0;
+    parts[P_RR * kParts + blockIdx.x] = blockIdx.x == 0 ? rr_new : 0.0;
+    parts[P_RHO * kParts + blockIdx.x] = blockIdx.x == 0 ? rho_new : 0.0;
     if (blockIdx.x == 0) {
       scal[S_OMEGA] = omega;
       scal[S_RHO_OLD] = rho;
+      if (FUSE) {
+        scal[S_RHO_NEXT] = rho_p;
+        scal[S_RHAT2_NEXT] = rhat2;
+      }
     }
   }
 }
@@ -3079,6 +3169,20 @@ int bicgstab(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, dou
       });
     }
   };
+  // The criterion below runs on RECURRENCE quantities (|r|^2 = s.s - 2 omega t.s + omega^2 t.t is
+  // prone to cancellation).  Solves to direct-solver accuracy (rtol <= 1e-10: the parity settings)
+  // confirm the TRUE residual b - A x once on reported convergence; if it misses the target the
+  // iteration restarts from it (at most twice -- round-off may put a floor under the true residual).
+  int confirmations = o.rtol <= kConfirmRtol ? 2 : 0;
+  // Zero-start solves on one rank begin WITHOUT the start kernel: r0 = rhat = p1 = b are read where they lie, the
+  // start sums come out of the first rhat.v launch (k_bicg_dot0) and the start scalars out of the first k_bicg_s.
+  // (Partitioned solves keep the start kernel: their host reads |r0|, |b| after the start-up all-reduce.)
+  const bool fused = g_bicg_fused;
+  const bool zstart = fused && op.x_zero && op.comm == nullptr && o.max_iter > 0;
+  // ... and keep the shadow residual in b itself where the caller gives b up and nothing reads b again (the
+  // confirmation forms b - A x); the in-kernel restart (rhat = r) then writes into b
+  const bool rhat_in_b = zstart && op.b_scratch && confirmations == 0;
+  double* const rhat = rhat_in_b ? const_cast<double*>(b) : w.rhat.p;
   if (op.x_zero) {
     // zero start vector (Newton updates): r = b - A 0 = b, no operator application (A 0 = 0 on every row,
     // identity rows included); the start kernel below stores it
@@ -3088,12 +3192,13 @@ int bicgstab(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, dou
   } else {
     launch_residual(s, *op.A, op.nv, x, b, w.r.p, op.rowmask, op.maskmode);
   }
-  LAUNCH(k_bicg_start, kParts, s, n, op.x_zero ? b : w.r.p, w.rhat.p, parts, scal, op.x_zero ? w.r.p : (double*)nullptr);
+  if (!zstart)
+    LAUNCH(k_bicg_start, kParts, s, n, op.x_zero ? b : w.r.p, w.rhat.p, parts, scal, op.x_zero ? w.r.p : (double*)nullptr);
   // |b| for the relative criterion goes into the slot next to (rho, |r0|^2): ONE all-reduce for
   // the three start-up sums and one read-back for the two the host needs
   static_assert(P_RR == P_RHO + 1 && P_TS == P_RHO + 2, "start-up slots must be adjacent");
   if (!op.x_zero) launch_dot(s, n, b, b, parts + (op.comm ? P_TS : P_B0) * kParts);
-  reduce_slots(op, s, parts, P_RHO, 3);
+  if (!zstart) reduce_slots(op, s, parts, P_RHO, 3);
   // The host needs |r0| and |b| only to form the target of the convergence checks.  Known to the caller (Newton:
   // |b| = the nonlinear residual norm just evaluated, zero start): no round trip.  Otherwise (one rank) the two
   // sums wait in their own slots and the FIRST check reads them together with the residual of that iteration.
@@ -3119,40 +3224,62 @@ int bicgstab(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, dou
   // (op.x_zero: the start vector is zero BY CONTRACT and need not be stored: the first update writes x, and a solve
   // that ends without an iteration clears it)
   bool x_unwritten = op.x_zero;
-  auto body = [&](int first) {
-    LAUNCH(k_bicg_p, kParts, s, n, first, w.r.p, w.v.p, op.prec ? nullptr : op.dinv,
-           w.p.p, w.phat.p, w.rhat.p, parts, scal);
-    if (op.prec) op.prec->apply(s, w.p.p, w.phat.p);
+  // shape of one iteration body:
+  //   z0     first iteration of a zero-start solve without start kernel (r = p = b)
+  //   p_done the previous iteration's fused update has formed p (and phat = dinv * p) already
+  //   p_in_b the previous direction is b (the iteration after z0, when a check lay between)
+  //   tail   no convergence check follows this iteration: its update also forms the next direction
+  auto body = [&](int first, bool z0, bool p_done, bool p_in_b, bool tail, bool x_zero_now) {
+    const double* dinv = op.prec ? nullptr : op.dinv;
+    const double* r = z0 ? b : w.r.p;
+    if (z0) {
+      if (op.prec) op.prec->apply(s, b, w.phat.p);
+      else LAUNCH(k_bicg_phat0, vgrid(n), s, n, b, op.dinv, w.phat.p);
+    } else {
+      if (!p_done)
+        LAUNCH(k_bicg_p, kParts, s, n, first, w.r.p, w.v.p, dinv, p_in_b ? b : w.p.p, w.p.p, w.phat.p, rhat, parts, scal);
+      if (op.prec) op.prec->apply(s, w.p.p, w.phat.p);
+    }
     apply(w.phat.p, w.v.p);
-    launch_dot(s, n, w.rhat.p, w.v.p, parts + P_RTV * kParts);
+    if (z0) LAUNCH(k_bicg_dot0, kParts, s, n, b, w.v.p, rhat_in_b ? (double*)nullptr : w.rhat.p, parts);
+    else launch_dot(s, n, rhat, w.v.p, parts + P_RTV * kParts);
     reduce_slots(op, s, parts, P_RTV, 1);
-    LAUNCH(k_bicg_s, kParts, s, n, w.r.p, w.v.p, op.prec ? nullptr : op.dinv, w.s.p, w.shat.p,
-           parts, scal);
+    LAUNCH(k_bicg_s, kParts, s, n, r, w.v.p, dinv, w.s.p, w.shat.p, parts, scal, z0 ? 2 : (p_done ? 1 : 0));
     if (op.prec) op.prec->apply(s, w.s.p, w.shat.p);
     apply(w.shat.p, w.t.p);
-    LAUNCH(k_dot_ts_tt, kParts, s, n, w.t.p, w.s.p, w.rhat.p, parts);
+    LAUNCH(k_dot_ts_tt, kParts, s, n, w.t.p, w.s.p, rhat, parts);
     reduce_slots(op, s, parts, P_TS, 5);
-    LAUNCH(k_bicg_xr, kParts, s, n, w.phat.p, w.shat.p, w.s.p, w.t.p, x, w.r.p, parts, scal, x_unwritten ? 1 : 0);
+    if (tail)
+      LAUNCH(k_bicg_xr<true>, kParts, s, n, w.phat.p, w.shat.p, w.s.p, w.t.p, x, w.r.p, parts, scal, x_zero_now ? 1 : 0,
+             w.v.p, dinv, z0 ? b : w.p.p, w.p.p, rhat);
+    else
+      LAUNCH(k_bicg_xr<false>, kParts, s, n, w.phat.p, w.shat.p, w.s.p, w.t.p, x, w.r.p, parts, scal, x_zero_now ? 1 : 0,
+             (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, (double*)nullptr);
   };
   // iterations >= 1 replay one captured HIP graph (same kernels, same arguments): removes the
   // host launch cost of the ~100 small multigrid kernels per iteration
   const GraphKey key{op.custom ? (const void*)op.custom : (const void*)op.A, (const void*)op.prec,
                      (const void*)x, (const void*)op.dinv, n, 0, op.graph_epoch};
-  // The criterion above runs on RECURRENCE quantities (|r|^2 = s.s - 2 omega t.s + omega^2 t.t is
-  // prone to cancellation).  Solves to direct-solver accuracy (rtol <= 1e-10: the parity settings)
-  // confirm the TRUE residual b - A x once on reported convergence; if it misses the target the
-  // iteration restarts from it (at most twice -- round-off may put a floor under the true residual).
-  int confirmations = o.rtol <= kConfirmRtol ? 2 : 0;
   bool restart = false;
+  bool p_done = false, p_in_b = false;
   for (;;) {
     while (!info.converged && it < o.max_iter) {
       const int first = (it == 0 || restart) ? 1 : 0;
-      if (!w.graphs_enabled(op)) body(first);
+      const bool z0 = zstart && it == 0;
+      const int itn = it + 1;
+      const bool tail = fused && !((itn >= o.first_check && itn % check == 0) || itn == o.max_iter);
+      const bool xz = x_unwritten;
+      if (!w.graphs_enabled(op)) body(first, z0, p_done, p_in_b, tail, xz);
       else {
         GraphKey k2 = key;
-        k2.parity = first | (x_unwritten ? 2 : 0);
-        w.replay(s, k2, [&] { body(first); });
+        k2.parity = first | (xz ? 2 : 0) | (z0 ? 4 : 0) | (p_done ? 8 : 0) | (p_in_b ? 16 : 0) | (tail ? 32 : 0) |
+                    (rhat_in_b ? 64 : 0);
+        if (z0 || p_in_b || rhat_in_b) k2.b = (const void*)b;          // (baked into these bodies)
+        const bool pd = p_done, pb = p_in_b;
+        w.replay(s, k2, [&] { body(first, z0, pd, pb, tail, xz); });
       }
+      p_done = tail;
+      p_in_b = z0 && !tail;
       x_unwritten = false;
       restart = false;
       ++it;
@@ -3189,7 +3316,7 @@ int bicgstab(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, dou
         launch_residual(s, *op.A, op.nv, x, b, w.r.p, op.rowmask, op.maskmode, phase);
       });
     }
-    LAUNCH(k_bicg_start, kParts, s, n, w.r.p, w.rhat.p, parts, scal, (double*)nullptr);
+    LAUNCH(k_bicg_start, kParts, s, n, w.r.p, w.rhat.p, parts, scal, (double*)nullptr);     // (confirming solves keep rhat)
     reduce_slots(op, s, parts, P_RHO, 2);
     const double true_r = std::sqrt(host_sum_parts(s, w, P_RR));
     if (!std::isfinite(true_r)) return NSFEM_ERR_BREAKDOWN;

@@ -493,9 +493,10 @@ struct GraphKey {
   int64_t n;
   int parity;
   uint64_t epoch;
+  const void* b = nullptr;          // right-hand side, where the body reads or writes it (BiCGStab: zero-start bodies)
   bool operator==(const GraphKey& o) const {
     return op == o.op && prec == o.prec && x == o.x && dinv == o.dinv && n == o.n &&
-           parity == o.parity && epoch == o.epoch;
+           parity == o.parity && epoch == o.epoch && b == o.b;
   }
 };
 struct KrylovWork {
@@ -677,6 +678,8 @@ struct LinOp {
                                     // (BiCGStab skips the operator application that would compute b - A 0)
   double known_bnorm = -1.0;        // >= 0: |b|_2 (all ranks), already on the host -- with x_zero it is the start
                                     // residual too and the solve begins without a device -> host round trip
+  bool b_scratch = false;           // the solver may overwrite b (the caller recomputes it before reading it again):
+                                    // a zero-start BiCGStab solve then keeps its shadow residual IN b, without a copy
 };
 
 // ---- multigrid ------------------------------------------------------------------
