@@ -70,16 +70,25 @@ enum nsfem_slot {
   NSFEM_P2_OLD = 8,  /* BDF: pressure at t_{n-1} (keeps _solutions[2] whole)  */
   NSFEM_CONV_N1 = 9, /* IMEX: c_c N(u^n), written by nsfem_step_imex    [dim*n_p2] */
   NSFEM_CONV_N2 = 10, /* IMEX: c_c N(u^(n-1)); nsfem_advance moves N1 here       */
-  NSFEM_N_SLOTS = 11
+  /* scalar transport (nsfem_set_scalar): a P2 scalar on the velocity nodes, [n_p2] each, allocated on first use */
+  NSFEM_T0 = 11,       /* scalar at t_{n+1}, written by nsfem_step_scalar_imex                  */
+  NSFEM_T1 = 12,       /* scalar at t_n                                                          */
+  NSFEM_T2 = 13,       /* scalar at t_{n-1}                                                      */
+  NSFEM_T_SOURCE = 14, /* nodal P2 interpolant of the source q (optional)                        */
+  NSFEM_TCONV_1 = 15,  /* beta0 C(u^n) T^n, written by nsfem_step_scalar_imex                    */
+  NSFEM_TCONV_2 = 16,  /* the vector of the step before; nsfem_advance moves TCONV_1 here.  Set by hand it is
+                          read as the unweighted C(u^(n-1)) T^(n-1)                              */
+  NSFEM_N_SLOTS = 17
 };
 
 /* fields for Dirichlet sets */
 enum nsfem_field {
   NSFEM_VELOCITY = 0,
   NSFEM_PRESSURE = 1,
-  NSFEM_PRESSURE_PRECOND = 2   /* Dirichlet set of the pressure Laplacian used inside the
+  NSFEM_PRESSURE_PRECOND = 2,  /* Dirichlet set of the pressure Laplacian used inside the
                                   Schur-complement preconditioner of the monolithic scheme
                                   (P1 nodes on open boundaries + true pressure conditions) */
+  NSFEM_SCALAR = 3             /* transported P2 scalar (nsfem_step_scalar_imex): dofs index the P2 nodes */
 };
 
 /* operators that can be exported / applied (parity tests, _assemble_system) */
@@ -184,7 +193,7 @@ int nsfem_set_bdf(nsfem_ctx* ctx, const double alpha[3], double k);
 int nsfem_set_imex(nsfem_ctx* ctx, const double alpha[3], const double beta[2], const double gamma[3], double k);
 /* replaces DirichletBC lists (ns_solver_base.py:546-660); re-callable each step
  * (time dependent values, _set_time ns_solver_base.py:1033-1104).  dofs index the
- * velocity (interleaved) or pressure vector; later entries win on duplicates. */
+ * velocity (interleaved) or pressure vector (NSFEM_SCALAR: the P2 nodes); later entries win on duplicates. */
 int nsfem_set_dirichlet(nsfem_ctx* ctx, int field, int32_t n, const int32_t* dofs,
                         const double* vals);
 /* convective term form (ns_solver_base.py:370-390): 0 standard, 1 rotational, 2 divergence,
@@ -430,7 +439,38 @@ int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info
  * rhs and conv_n1 (c_c N(u1), may be null) are host arrays of dim * n_p2 doubles. */
 int nsfem_imex_info(nsfem_ctx* ctx, int64_t out[4]);
 int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, double* rhs, double* conv_n1);
-/* replaces _advance_solution (ns_solver_base.py:1012-1016, ns_ipcs_solver.py:35-43) */
+/* ---- IMEX transport of a P2 scalar T on the velocity nodes with Boussinesq buoyancy (new; the reference's gravity
+ * driven cases prescribe their body force).  diffusivity kappa >= 0; buoyancy: dim entries b (NULL = 0); convective
+ * form 0 standard C_ij = int (u . grad phi_j) phi_i, 1 skew-symmetric 1/2 (C - C^T).  With a nonzero b,
+ * nsfem_step_imex uses the body force  f_eff = f + T^{n+1} b  (T^{n+1} = NSFEM_T0; formed in a work buffer,
+ * NSFEM_BODY_FORCE is never written; body_force_term must be set) exactly where it uses f.  With b = 0 it launches what
+ * it launches without a scalar.  NSFEM_ERR_ARG on contexts with a communicator. */
+int nsfem_set_scalar(nsfem_ctx* ctx, double diffusivity, const double* buoyancy /* dim, NULL = 0 */,
+                     int convective_form);
+/* One transport step with alpha, beta, gamma, k of nsfem_set_imex, T1 = NSFEM_T1, T2 = NSFEM_T2, u1 = NSFEM_U1,
+ * u2 = NSFEM_U2, q = NSFEM_T_SOURCE (when set):
+ *   (alpha0/k M + gamma0 kappa K) T0 = -[ M (alpha1 T1 + alpha2 T2)/k + kappa K (gamma1 T1 + gamma2 T2)
+ *                                         + beta0 C(u1) T1 + beta1 C(u2) T2 ] + M q
+ * with Dirichlet rows T_i = g_i (field NSFEM_SCALAR; symmetric elimination), solved by Jacobi-preconditioned CG
+ * (opts NULL: rtol 1e-12, 20000 iterations).  Call it BEFORE nsfem_step_imex of the same time step: it needs the known
+ * levels only, and the flow step reads T0.  beta0 C(u1) T1 is kept in NSFEM_TCONV_1; nsfem_advance(ctx, 0) rotates
+ * T2 <- T1 <- T0 and moves it to NSFEM_TCONV_2, where the next step reads it as beta1 C(u2) T2 (scaled by beta1 over
+ * the beta0 it was evaluated with; recomputed only after a level or a stored vector was set by hand or the form
+ * changed).  The system matrix is rebuilt only when alpha0/k, gamma0 or kappa change.
+ * NSFEM_ERR_ARG: no nsfem_set_scalar / nsfem_set_imex, contexts with a communicator, rotating frames. */
+int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* opts /* may be NULL */,
+                           nsfem_solve_info* info /* may be NULL */);
+/* Test hook: out_host [n_p2] = weight * C(u) T in the given form (0 / 1) for u = velocity_slot and T = scalar_slot (one
+ * of NSFEM_T0 .. NSFEM_T_SOURCE) -- the element kernel plus the per-node sums, no Dirichlet rows; no stored state is
+ * touched.  Two calls on the same state return the same bytes. */
+int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
+                            double* out_host);
+/* out = {rebuilds of the system matrix, convection launches of the steps, stored-convection reuses, 1 when the products
+ * of the last solve ran on the stencil-dictionary copy of the matrix (dictionaries equal to the matrix bit for bit:
+ * binary lattice spacings), else 0 (CSR)} */
+int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]);
+/* replaces _advance_solution (ns_solver_base.py:1012-1016, ns_ipcs_solver.py:35-43); scheme 0 with a scalar
+ * configured: also T2 <- T1 <- T0 and the stored scalar convection */
 int nsfem_advance(nsfem_ctx* ctx, int scheme /* 0 ipcs, 1 bdf */);
 /* L2 projection solve  M x = b  (no Dirichlet rows) on the velocity (field 0, both
  * components, b/x node-interleaved) or pressure (field 1) space; replaces the

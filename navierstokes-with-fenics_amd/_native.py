@@ -16,7 +16,8 @@ LIB_PATH = os.path.join(_HERE, "libnsfem_hip.so")
 # ---- enums (mirror include/nsfem.h) ------------------------------------------
 OK, ERR_ARG, ERR_HIP, ERR_BREAKDOWN, ERR_NOT_CONVERGED, ERR_COMM = 0, -1, -2, -3, -4, -5
 U0, U1, U2, USTAR, P, P_OLD, BODY_FORCE, TRACTION, P2_OLD, CONV_N1, CONV_N2 = range(11)
-VELOCITY, PRESSURE, PRESSURE_PRECOND = 0, 1, 2
+T0, T1, T2, T_SOURCE, TCONV_1, TCONV_2 = range(11, 17)       # transported P2 scalar (set_scalar / step_scalar_imex)
+VELOCITY, PRESSURE, PRESSURE_PRECOND, SCALAR = 0, 1, 2, 3
 (OP_MASS_P2, OP_STIFF_P2, OP_STIFF_P1, OP_MASS_P1, OP_DIV, OP_GRAD, OP_DIVT,
  OP_MOMENTUM_JAC, OP_VISCOUS_EXTRA, OP_MOMENTUM_JAC_MF, OP_MOMENTUM_SMOOTHER,
  OP_CONVECTION_ACTION) = range(12)
@@ -43,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_operator_diagonal",
     "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
     "nsfem_volume_functionals",
+    "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
 )
 
 
@@ -169,6 +171,10 @@ def load_library(path=None):
         "nsfem_imex_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_imex_rhs": (C.c_int, [vp, C.c_int, C.c_int, pd, pd]),
         "nsfem_set_dirichlet": (C.c_int, [vp, C.c_int, i32, pi, pd]),
+        "nsfem_set_scalar": (C.c_int, [vp, dbl, pd, C.c_int]),
+        "nsfem_step_scalar_imex": (C.c_int, [vp, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
+        "nsfem_scalar_convection": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, pd]),
+        "nsfem_scalar_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_viscous_form": (C.c_int, [vp, C.c_int]),
         "nsfem_set_convective_form": (C.c_int, [vp, C.c_int, C.c_int]),
         "nsfem_set_state": (C.c_int, [vp, C.c_int, pd, i64]),
@@ -425,6 +431,40 @@ class NsfemContext:
         self._check(self._lib.nsfem_imex_rhs(self._h, {"generic": 1, "lattice-kernel": 2}[path], int(convective_form),
                                              _dp(rhs), _dp(n1)))
         return rhs, n1
+
+    # -- IMEX scalar transport with Boussinesq buoyancy ----------------------------------
+    def set_scalar(self, diffusivity, buoyancy=None, convective_form=0):
+        """configure the transported P2 scalar: diffusivity kappa, buoyancy vector b (dim entries, None = 0: step_imex
+        then runs exactly as without a scalar) and the convective form 0 standard / 1 skew-symmetric"""
+        b = None
+        if buoyancy is not None:
+            b = np.ascontiguousarray(buoyancy, dtype=np.float64)
+            assert b.shape == (self.dim, )
+        self._check(self._lib.nsfem_set_scalar(self._h, float(diffusivity), None if b is None else _dp(b),
+                                               int(convective_form)))
+
+    def step_scalar_imex(self, rtol=1e-12, atol=0.0, max_iter=20000):
+        """one IMEX transport step (coefficients: set_imex) T1, T2, u1, u2 -> T0, Jacobi-CG; call it before step_imex
+        of the same time step.  Returns the SolveInfo of the CG solve"""
+        o = KrylovOpts(rtol, atol, max_iter, 0, 1, 0)
+        info = SolveInfo()
+        self._check(self._lib.nsfem_step_scalar_imex(self._h, C.byref(o), C.byref(info)))
+        return info
+
+    def scalar_convection(self, velocity_slot=U1, scalar_slot=T1, form=0, weight=1.0):
+        """test hook: weight * C(u) T (element kernel + node sums; no Dirichlet rows, no stored state touched)"""
+        out = np.empty(self.n_p2, dtype=np.float64)
+        self._check(self._lib.nsfem_scalar_convection(self._h, int(velocity_slot), int(scalar_slot), int(form),
+                                                      float(weight), _dp(out)))
+        return out
+
+    def scalar_info(self):
+        """dict(matrix_builds, convection_launches, convection_reuses, dictionary) of the transport steps so far;
+        dictionary: the last solve's products ran on the stencil-dictionary copy of the matrix"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_scalar_info(self._h, out))
+        return dict(matrix_builds=int(out[0]), convection_launches=int(out[1]), convection_reuses=int(out[2]),
+                    dictionary=bool(out[3]))
 
     def step_bdf(self, opts=None):
         o = opts or self.default_step_opts()

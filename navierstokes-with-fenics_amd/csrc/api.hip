@@ -41,9 +41,19 @@ static int64_t slot_size(const nsfem_ctx* c, int slot) {
       return nvel(c);
     case NSFEM_P: case NSFEM_P_OLD: case NSFEM_P2_OLD:
       return npre(c);
+    case NSFEM_T0: case NSFEM_T1: case NSFEM_T2: case NSFEM_T_SOURCE: case NSFEM_TCONV_1: case NSFEM_TCONV_2:
+      return (int64_t)c->mesh.n_p2;
     default:
       return -1;
   }
+}
+
+// the slots of the transported scalar are allocated (zeroed) when something first touches them
+static inline bool scalar_slot(int slot) { return slot >= NSFEM_T0 && slot <= NSFEM_TCONV_2; }
+static void ensure_scalar_slot(nsfem_ctx* c, int slot) {
+  if (!scalar_slot(slot) || c->state[slot].p) return;
+  c->state[slot].alloc((size_t)c->mesh.n_p2);
+  c->state[slot].zero(c->stream);
 }
 
 static HaloRange to_halo(const nsfem_halo& h) {
@@ -83,7 +93,7 @@ static void upload_pattern(hipStream_t s, HostPattern& h, Pattern& d, bool want_
   std::vector<int32_t>().swap(h.slot);
 }
 
-extern "C" int nsfem_version(void) { return 1; }
+extern "C" int nsfem_version(void) { return 2; }
 
 extern "C" const char* nsfem_last_error(const nsfem_ctx* ctx) {
   return ctx ? ctx->err.c_str() : g_create_error.c_str();
@@ -266,6 +276,7 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   lap("SELL / dictionary copies");
   // ---- state + work vectors
   for (int i = 0; i < NSFEM_N_SLOTS; ++i) {
+    if (scalar_slot(i)) continue;
     fresh->state[i].alloc((size_t)slot_size(fresh, i));
     fresh->state[i].zero(s);
   }
@@ -439,8 +450,39 @@ extern "C" int nsfem_set_dirichlet(nsfem_ctx* ctx, int field, int32_t n, const i
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
   NSFEM_REQUIRE(field == NSFEM_VELOCITY || field == NSFEM_PRESSURE ||
-                    field == NSFEM_PRESSURE_PRECOND, "bad field");
+                    field == NSFEM_PRESSURE_PRECOND || field == NSFEM_SCALAR, "bad field");
   NSFEM_REQUIRE(n >= 0 && (n == 0 || dofs), "bad Dirichlet arrays");
+  if (field == NSFEM_SCALAR) {
+    // transported scalar: dofs are P2 nodes; later entries win on duplicates, as below
+    NSFEM_REQUIRE(n == 0 || vals, "bad Dirichlet arrays");
+    const int64_t size = ctx->mesh.n_p2;
+    std::vector<int32_t> last((size_t)size, -1), d;
+    std::vector<double> v;
+    for (int32_t i = 0; i < n; ++i) {
+      NSFEM_REQUIRE(dofs[i] >= 0 && dofs[i] < size, "Dirichlet dof out of range");
+      last[dofs[i]] = i;
+    }
+    for (int64_t k = 0; k < size; ++k)
+      if (last[k] >= 0) {
+        d.push_back((int32_t)k);
+        v.push_back(vals[last[k]]);
+      }
+    nsfem_ctx::Scalar& sc = ctx->sc;
+    hipStream_t s = ctx->stream;
+    sc.bc_dofs.upload(d, s);
+    sc.bc_vals.upload(v, s);
+    if (!sc.mask.p) sc.mask.alloc((size_t)size);
+    sc.mask.zero(s);
+    launch_fill_mask(s, (int)d.size(), sc.bc_dofs.p, sc.mask.p);
+    if (sc.h_bc != d) {                     // (re-allocated dof arrays are baked into captured iteration graphs)
+      ctx->graph_epoch++;
+      sc.dinv_dirty = true;
+    }
+    sc.nbc = (int)d.size();
+    sc.h_bc.swap(d);
+    NSFEM_HIP(hipStreamSynchronize(s));
+    return NSFEM_OK;
+  }
   if (field == NSFEM_PRESSURE_PRECOND) {
     // Dirichlet set of the pressure Laplacian inside the Schur-complement preconditioner of
     // the monolithic scheme (open boundaries + true pressure conditions); values unused
@@ -515,6 +557,9 @@ extern "C" int64_t nsfem_state_size(const nsfem_ctx* ctx, int slot) {
 
 extern "C" void* nsfem_state_devptr(nsfem_ctx* ctx, int slot) {
   if (!ctx || slot < 0 || slot >= NSFEM_N_SLOTS) return nullptr;
+  if (scalar_slot(slot) && !ctx->state[slot].p) {
+    try { ensure_scalar_slot(ctx, slot); } catch (const std::exception&) { return nullptr; }
+  }
   return ctx->state[slot].p;
 }
 
@@ -522,6 +567,7 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   API_BEGIN
   NSFEM_REQUIRE(ctx && host, "null argument");
   NSFEM_REQUIRE(slot >= 0 && slot < NSFEM_N_SLOTS && n == slot_size(ctx, slot), "bad slot / size");
+  ensure_scalar_slot(ctx, slot);
   NSFEM_HIP(hipMemcpyAsync(ctx->state[slot].p, host, sizeof(double) * n, hipMemcpyHostToDevice,
                            ctx->stream));
   NSFEM_HIP(hipStreamSynchronize(ctx->stream));
@@ -535,6 +581,11 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   if (slot == NSFEM_U1) ctx->u1_ghost_fresh = false;
   if (slot == NSFEM_U2) ctx->u2_ghost_fresh = false;
   if (slot == NSFEM_CONV_N2) { ctx->conv_n2_valid = true; ctx->conv_n_form = -2; }   // (the caller vouches for it)
+  // scalar transport: the stored convection vectors follow the levels (velocity and scalar) they were evaluated at
+  if (slot == NSFEM_U1 || slot == NSFEM_T1 || slot == NSFEM_TCONV_1) ctx->sc.conv1_fresh = false;
+  if (slot == NSFEM_U2 || slot == NSFEM_T2) ctx->sc.conv2_valid = false;
+  if (slot == NSFEM_TCONV_2) { ctx->sc.conv2_valid = true; ctx->sc.conv2_weight = 1.0; ctx->sc.conv_form = -2; }
+  if (slot == NSFEM_T_SOURCE) ctx->sc.have_source = true;
   API_END(ctx)
 }
 
@@ -542,6 +593,7 @@ extern "C" int nsfem_get_state(nsfem_ctx* ctx, int slot, double* host, int64_t n
   API_BEGIN
   NSFEM_REQUIRE(ctx && host, "null argument");
   NSFEM_REQUIRE(slot >= 0 && slot < NSFEM_N_SLOTS && n == slot_size(ctx, slot), "bad slot / size");
+  ensure_scalar_slot(ctx, slot);
   NSFEM_HIP(hipMemcpyAsync(host, ctx->state[slot].p, sizeof(double) * n, hipMemcpyDeviceToHost,
                            ctx->stream));
   NSFEM_HIP(hipStreamSynchronize(ctx->stream));
@@ -585,6 +637,21 @@ static void select_velocity_cycle_depth(nsfem_ctx* c, double ap, double b) {
   }
 }
 
+// stencil dictionary of the scalar P2 operators (lattice meshes only): shared by every a M + b K; used by the
+// smoothing steps of the velocity multigrid (and, where it equals the matrices bit for bit, by every product)
+static void ensure_dict22(nsfem_ctx* c) {
+  if (c->dict22_tried) return;
+  c->dict22_tried = true;
+  if (build_stencil_dict(c->stream, c->p22, c->M2.vals.p, c->K2.vals.p, c->dict22)) {
+    c->L.dict = &c->dict22;
+    c->Lprec.dict = &c->dict22;
+    if (c->dict22.exact) {       // the Chebyshev / CG mass solves may use it too
+      c->M2.dict = &c->dict22;
+      c->M2.sell_update(c->stream);
+    }
+  }
+}
+
 static void ensure_L(nsfem_ctx* c) {
   if (!c->L_dirty) return;
   // L = alpha0/k M + c_viscous K   (scalar P2; acts on all velocity components)
@@ -592,19 +659,7 @@ static void ensure_L(nsfem_ctx* c) {
   const double a = c->alpha[0] / c->k, b = c->imex_active ? c->imex_gamma[0] * c->coef[2] : c->coef[2];
   if (c->imex_active) ++c->imex_matrix_builds;
   launch_scale_combine(c->stream, c->p22.nnz, a, c->M2.vals.p, b, c->K2.vals.p, c->L.vals.p);
-  if (!c->dict22_tried) {
-    // stencil dictionary of the scalar P2 operators (lattice meshes only): shared by every
-    // a M + b K; used by the smoothing steps of the velocity multigrid
-    c->dict22_tried = true;
-    if (build_stencil_dict(c->stream, c->p22, c->M2.vals.p, c->K2.vals.p, c->dict22)) {
-      c->L.dict = &c->dict22;
-      c->Lprec.dict = &c->dict22;
-      if (c->dict22.exact) {       // the Chebyshev / CG mass solves may use it too
-        c->M2.dict = &c->dict22;
-        c->M2.sell_update(c->stream);
-      }
-    }
-  }
+  ensure_dict22(c);
   c->L.sell_update(c->stream);
   // preconditioner version: (alpha0/k + shift) M + c_viscous K -- the multigrid hierarchy of the
   // velocity block is built on it.  shift = 0 (all transient problems): the operator itself.
@@ -2205,9 +2260,18 @@ static void imex_begin_step(nsfem_ctx* c) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c);
   ensure_div_dicts(c);
-  if (c->have_body_force) {
+  // Boussinesq buoyancy (nsfem_set_scalar with b != 0): f_eff = f + T^{n+1} b in a work buffer takes the place of f
+  const double* f = c->have_body_force ? c->state[NSFEM_BODY_FORCE].p : nullptr;
+  if (c->sc.configured && c->sc.buoyant) {
+    NSFEM_REQUIRE(std::isfinite(c->coef[3]), "buoyancy set but body_force_term coefficient is None");
+    ensure_scalar_slot(c, NSFEM_T0);
+    if (!c->sc.f_eff.p) c->sc.f_eff.alloc((size_t)nv);
+    launch_buoyancy_force(s, c->mesh, f, c->state[NSFEM_T0].p, c->sc.b, c->sc.f_eff.p);
+    f = c->sc.f_eff.p;
+  }
+  if (f) {
     NSFEM_REQUIRE(std::isfinite(c->coef[3]), "body force set but body_force_term coefficient is None");
-    launch_axpby(s, nv, -c->coef[3], c->state[NSFEM_BODY_FORCE].p, 0.0, c->state[NSFEM_BODY_FORCE].p, c->tmp_v.p);
+    launch_axpby(s, nv, -c->coef[3], f, 0.0, f, c->tmp_v.p);
     launch_spmv(s, c->M2, c->mesh.dim, c->tmp_v.p, c->gconst.p, nullptr, MASK_NONE);
   } else {
     c->gconst.zero(s);
@@ -2487,6 +2551,172 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
   API_END(ctx)
 }
 
+// ---------------------------------------------------------------- IMEX scalar transport
+extern "C" int nsfem_set_scalar(nsfem_ctx* ctx, double diffusivity, const double* buoyancy, int convective_form) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(std::isfinite(diffusivity) && diffusivity >= 0.0, "scalar transport: diffusivity must be finite and >= 0");
+  NSFEM_REQUIRE(convective_form == 0 || convective_form == 1,
+                "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
+  nsfem_ctx::Scalar& sc = ctx->sc;
+  bool buoyant = false;
+  for (int d = 0; d < 3; ++d) {
+    const double b = buoyancy && d < ctx->mesh.dim ? buoyancy[d] : 0.0;
+    NSFEM_REQUIRE(std::isfinite(b), "scalar transport: buoyancy vector must be finite");
+    sc.b[d] = b;
+    buoyant = buoyant || b != 0.0;
+  }
+  sc.buoyant = buoyant;
+  sc.kappa = diffusivity;
+  sc.form = convective_form;
+  sc.configured = true;
+  API_END(ctx)
+}
+
+// A = alpha0/k M + gamma0 kappa K, rebuilt only when one of the three numbers changed
+static void ensure_scalar_matrix(nsfem_ctx* c) {
+  nsfem_ctx::Scalar& sc = c->sc;
+  hipStream_t s = c->stream;
+  const double a = c->alpha[0] / c->k, g0 = c->imex_gamma[0];
+  if (!sc.A.vals.p) sc.A.init(&c->p22, 1, 1, s);
+  ensure_dict22(c);
+  const StencilDict* dict = c->dict22.n_stencils > 0 ? &c->dict22 : nullptr;
+  const bool rebuild = !(a == sc.built_a && g0 == sc.built_g0 && sc.kappa == sc.built_kappa) || sc.A.dict != dict;
+  if (!rebuild) return;
+  sc.A.dict = dict;
+  launch_scale_combine(s, c->p22.nnz, a, c->M2.vals.p, g0 * sc.kappa, c->K2.vals.p, sc.A.vals.p);
+  sc.A.sell_update(s);
+  sc.built_a = a;
+  sc.built_g0 = g0;
+  sc.built_kappa = sc.kappa;
+  ++sc.matrix_builds;
+  sc.dinv_dirty = true;
+}
+
+static void scalar_require_supported(nsfem_ctx* c) {
+  NSFEM_REQUIRE(c->sc.configured, "nsfem_set_scalar has not been called");
+  NSFEM_REQUIRE(!c->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  imex_require_supported(c);
+}
+
+extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* opts, nsfem_solve_info* info) {
+  nsfem_solve_info local;
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  scalar_require_supported(ctx);
+  nsfem_ctx::Scalar& sc = ctx->sc;
+  hipStream_t s = ctx->stream;
+  const int64_t n = ctx->mesh.n_p2;
+  for (int slot : {NSFEM_T0, NSFEM_T1, NSFEM_T2, NSFEM_TCONV_1, NSFEM_TCONV_2}) ensure_scalar_slot(ctx, slot);
+  if (!sc.rhs.p) {
+    sc.dinv_dirty = true;
+    sc.rhs.alloc((size_t)n);
+    sc.tmp.alloc((size_t)n);
+    sc.dinv.alloc((size_t)n);
+  }
+  if (!sc.mask.p) {
+    sc.mask.alloc((size_t)n);
+    sc.mask.zero(s);
+  }
+  ensure_scalar_matrix(ctx);
+  const double k = ctx->k, *al = ctx->alpha, *ga = ctx->imex_gamma;
+  const double b0 = ctx->imex_beta[0], b1 = ctx->imex_beta[1];
+  double *T1 = ctx->state[NSFEM_T1].p, *T2 = ctx->state[NSFEM_T2].p;
+  double *rhs = sc.rhs.p, *tmp = sc.tmp.p;
+  // rhs = M ((alpha1 T1 + alpha2 T2)/k - q) + kappa K (gamma1 T1 + gamma2 T2)
+  if (sc.have_source) launch_lincomb3(s, n, al[1] / k, T1, al[2] / k, T2, -1.0, ctx->state[NSFEM_T_SOURCE].p, tmp);
+  else launch_axpby(s, n, al[1] / k, T1, al[2] / k, T2, tmp);
+  launch_spmv(s, ctx->M2, 1, tmp, rhs, nullptr, MASK_NONE);
+  if (sc.kappa != 0.0 && (ga[1] != 0.0 || ga[2] != 0.0)) {
+    launch_axpby(s, n, ga[1], T1, ga[2], T2, tmp);
+    launch_spmv_axpy(s, ctx->K2, 1, sc.kappa, tmp, rhs, nullptr);
+  }
+  // beta1 C(u2) T2: the vector the previous step stored (beta0' C(u1) T1 then), unless a level, a stored vector or
+  // the form changed under it
+  double f2 = 0.0;
+  if (b1 != 0.0) {
+    const bool stored = sc.conv2_valid && sc.conv2_weight != 0.0 && (sc.conv_form == -2 || sc.conv_form == sc.form);
+    if (stored) {
+      ++sc.conv_reuses;
+    } else {
+      launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, ctx->state[NSFEM_TCONV_2].p);
+      ++sc.conv_launches;
+      sc.conv2_weight = 1.0;
+      sc.conv2_valid = true;
+    }
+    f2 = b1 / sc.conv2_weight;
+  }
+  // beta0 C(u1) T1: beta0 rides in the kernel's weight, the node sums are the stored copy
+  launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p);
+  ++sc.conv_launches;
+  sc.conv1_fresh = true;
+  sc.conv1_weight = b0;
+  sc.conv_form = sc.form;
+  if (b1 != 0.0) launch_lincomb3(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, -f2, ctx->state[NSFEM_TCONV_2].p, rhs);
+  else launch_axpby(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, rhs);
+  // Dirichlet rows T_i = g_i; start vector T1 with the Dirichlet values (as the IMEX diffusion step)
+  double* x = ctx->state[NSFEM_T0].p;
+  launch_set_values(s, sc.nbc, sc.bc_dofs.p, sc.bc_vals.p, rhs);
+  NSFEM_HIP(hipMemcpyAsync(x, T1, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  launch_set_values(s, sc.nbc, sc.bc_dofs.p, sc.bc_vals.p, x);
+  LinOp op;
+  op.A = &sc.A;
+  op.nv = 1;
+  op.rowmask = sc.mask.p;
+  op.maskmode = MASK_ZERO;
+  op.dinv = sc.dinv.p;
+  op.graph_epoch = ctx->graph_epoch;
+  if (sc.dinv_dirty) {              // (the matrix and the mask change only on a rebuild / a new Dirichlet set)
+    launch_inv_diag(s, sc.A, 1, sc.mask.p, sc.dinv.p);
+    sc.dinv_dirty = false;
+  }
+  sc.dict_used = sc.A.dict_ready && sc.A.dict->exact ? 1 : 0;
+  nsfem_krylov_opts ko;
+  if (opts) ko = *opts;
+  else { ko.rtol = 1e-12; ko.atol = 0.0; ko.max_iter = 20000; ko.precond = 0; ko.check_every = 1; ko.first_check = 0; }
+  NSFEM_REQUIRE(ko.precond == 0, "scalar transport: precond must be 0 (Jacobi)");
+  nsfem_solve_info& si = info ? *info : local;
+  ctx->kw.ensure(nvel(ctx));
+  int rc = pcg(s, ctx->kw, op, rhs, x, hinted(ko, ctx->hint_sc), si, false);
+  note_solve(ctx->hint_sc, si, ko, ctx->kw.last_target);
+  if (rc != NSFEM_OK) throw Error(rc, "CG failed in the scalar transport step");
+  API_END(ctx)
+}
+
+extern "C" int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
+                                       double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+  NSFEM_REQUIRE(scalar_slot >= NSFEM_T0 && scalar_slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
+  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
+  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  hipStream_t s = ctx->stream;
+  const int64_t n = ctx->mesh.n_p2;
+  ensure_scalar_slot(ctx, scalar_slot);
+  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
+  ctx->kw.ensure(nvel(ctx));
+  ++ctx->kw.touch;
+  double* out = ctx->kw.q.p;
+  launch_scalar_convection(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, out);
+  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->sc.matrix_builds;
+  out[1] = ctx->sc.conv_launches;
+  out[2] = ctx->sc.conv_reuses;
+  out[3] = ctx->sc.dict_used;
+  API_END(ctx)
+}
+
 // Krylov tolerances of one Newton linear solve.  newton_forcing = 0: the caller's tolerances
 // (a direct solver's accuracy, as the reference's LU).  newton_forcing = eta > 0 (inexact
 // Newton): reduce the linear residual by eta, but never below a tenth of what the nonlinear
@@ -2664,6 +2894,22 @@ extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
     ctx->conv_n1_fresh = false;
   } else {
     ctx->conv_n2_valid = false;
+  }
+  // scalar transport: T2 <- T1 (pointer swap), T1 <- T0 (copy), and the stored convection as above
+  if (scheme == 0 && ctx->sc.configured) {
+    nsfem_ctx::Scalar& sc = ctx->sc;
+    for (int slot : {NSFEM_T0, NSFEM_T1, NSFEM_T2, NSFEM_TCONV_1, NSFEM_TCONV_2}) ensure_scalar_slot(ctx, slot);
+    std::swap(ctx->state[NSFEM_T2].p, ctx->state[NSFEM_T1].p);
+    NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_T1].p, ctx->state[NSFEM_T0].p, sizeof(double) * ctx->mesh.n_p2,
+                             hipMemcpyDeviceToDevice, s));
+    if (sc.conv1_fresh) {
+      std::swap(ctx->state[NSFEM_TCONV_2].p, ctx->state[NSFEM_TCONV_1].p);
+      sc.conv2_weight = sc.conv1_weight;
+      sc.conv2_valid = true;
+      sc.conv1_fresh = false;
+    } else {
+      sc.conv2_valid = false;
+    }
   }
   // (no synchronisation: everything that reads the state is ordered on the context's stream, nsfem_get_state and
   // nsfem_synchronize wait for it -- a host wait here left the GPU idle ~20 us in every time step)

@@ -756,6 +756,121 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
   else launch_conv_cell<1>(s, m, u, v, cc, form);
 }
 
+// ---------------------------------------------------------------- scalar transport (nsfem_step_scalar_imex)
+// Convection of a P2 scalar T by the P2 velocity u, one thread per CELL: u and T at the 6 nodes in registers, u_q and
+// grad T_q formed once per quadrature point and shared by the 6 test functions.
+//   FORM 0 (standard)        r_i = wgt int (u . grad T) phi_i
+//   FORM 1 (skew-symmetric)  r_i = wgt/2 int [ (u . grad T) phi_i - (u . grad phi_i) T ]      (= 1/2 (C - C^T) T)
+// The element vector goes node-sorted into the first 6 n_cells doubles of m.rbuf (ndst, as k_conv_cell);
+// k_scalar_gather sums the run of every node in ascending cell order: no atomics, the same state gives the same bytes.
+template <int FORM>
+__global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* __restrict__ vx,
+                                                          const int32_t* __restrict__ p2,
+                                                          const double* __restrict__ u,
+                                                          const double* __restrict__ T, double wgt,
+                                                          const int32_t* __restrict__ ndst,
+                                                          double* __restrict__ rbuf) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo g = load_geo(vx, nc, c);
+  double ux[6], uy[6], t[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int node = p2[(size_t)k * nc + c];
+    const double2 a = reinterpret_cast<const double2*>(u)[node];
+    ux[k] = a.x;
+    uy[k] = a.y;
+    t[k] = T[node];
+  }
+  double r[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) r[i] = 0.0;
+  for (int q = 0; q < 7; ++q) {
+    double gx[6], gy[6];
+    double uqx = 0.0, uqy = 0.0, tq = 0.0, dtx = 0.0, dty = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx[k], gy[k]);
+      const double ph = c_q.phi2[q][k];
+      uqx += ph * ux[k];
+      uqy += ph * uy[k];
+      dtx += gx[k] * t[k];
+      dty += gy[k] * t[k];
+      if (FORM == 1) tq += ph * t[k];
+    }
+    const double w = c_q.w[q] * g.adet * wgt;
+    const double adv = uqx * dtx + uqy * dty;           // u . grad T
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      if (FORM == 0) {
+        r[i] += w * c_q.phi2[q][i] * adv;
+      } else {
+        const double ugi = uqx * gx[i] + uqy * gy[i];   // u . grad phi_i
+        r[i] += 0.5 * w * (c_q.phi2[q][i] * adv - ugi * tq);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rbuf[ndst[(size_t)i * nc + c]] = r[i];
+}
+
+// out[n] = sum of the node's run nptr[n] .. nptr[n + 1] of the node-sorted scalar element vectors (ascending cells)
+__global__ __launch_bounds__(256) void k_scalar_gather(int n_nodes, const int32_t* __restrict__ nptr,
+                                                       const double* __restrict__ rbuf, double* __restrict__ out) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= n_nodes) return;
+  double acc = 0.0;
+  int k = nptr[n];
+  const int e = nptr[n + 1];
+  for (; k + 4 <= e; k += 4) {          // four independent loads in flight per lane
+    const double v0 = rbuf[k], v1 = rbuf[k + 1], v2 = rbuf[k + 2], v3 = rbuf[k + 3];
+    acc += v0;
+    acc += v1;
+    acc += v2;
+    acc += v3;
+  }
+  for (; k < e; ++k) acc += rbuf[k];
+  out[n] = acc;
+}
+
+// f_eff[n dim + c] = f[n dim + c] + T[n] b[c]   (f null: no body force set, f_eff = T b)
+__global__ __launch_bounds__(256) void k_buoyancy_force(int64_t n_nodes, int dim, const double* __restrict__ f,
+                                                        const double* __restrict__ T, double b0, double b1, double b2,
+                                                        double* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_nodes * dim) return;
+  const int c = (int)(t % dim);
+  const double b = c == 0 ? b0 : (c == 1 ? b1 : b2);
+  const double tb = T[t / dim] * b;
+  out[t] = f ? f[t] + tb : tb;
+}
+
+void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                              int form, double* out) {
+  NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
+  if (m.dim == 3) {
+    scalar_convection_cells_3d(s, m, u, T, weight, form);
+  } else {
+    const dim3 grid(grid_for(m.n_cells)), block(kBlock);
+    if (form == 0)
+      hipLaunchKernelGGL((k_scalar_conv_cell<0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
+                         m.rbuf.p);
+    else
+      hipLaunchKernelGGL((k_scalar_conv_cell<1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
+                         m.rbuf.p);
+  }
+  hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
+  NSFEM_HIP(hipGetLastError());
+}
+
+void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, const double* T, const double b[3],
+                           double* out) {
+  const int64_t n = (int64_t)m.n_p2 * m.dim;
+  hipLaunchKernelGGL(k_buoyancy_force, dim3(grid_for(n)), dim3(kBlock), 0, s, (int64_t)m.n_p2, m.dim, f, T, b[0], b[1],
+                     m.dim == 3 ? b[2] : 0.0, out);
+  NSFEM_HIP(hipGetLastError());
+}
+
 
 // ---------------------------------------------------------------- IMEX right-hand side
 // rhs = -(t + (b0 n1 + b1 n2)): the last operation of the right-hand side of nsfem_step_imex, shared by the generic

@@ -654,6 +654,77 @@ void convection_action_3d(hipStream_t s, const MeshDev& m, const double* u, cons
   NSFEM_HIP(hipGetLastError());
 }
 
+// ---- scalar transport on tetrahedra (the 2D kernel is k_scalar_conv_cell, assembly.hip): convection of a P2 scalar T
+// by the P2 velocity u, one thread per cell, 15-point rule.  FORM 0: r_i = wgt int (u . grad T) phi_i; FORM 1:
+// r_i = wgt/2 int [(u . grad T) phi_i - (u . grad phi_i) T].  Element vector node-sorted into the first 10 n_cells
+// doubles of m.rbuf; the caller sums the node runs (k_scalar_gather).
+// FORM 0 does not keep the gradients of a quadrature point (the test functions need phi_i only): grad T_q is summed
+// as they are formed.
+template <int FORM>
+__global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double* __restrict__ vx,
+                                                           const int32_t* __restrict__ p2,
+                                                           const double* __restrict__ u,
+                                                           const double* __restrict__ T, double wgt,
+                                                           const int32_t* __restrict__ ndst,
+                                                           double* __restrict__ rbuf) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo3 g = load_geo3(vx, nc, c);
+  double un[10][3], t[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const size_t node = (size_t)p2[(size_t)k * nc + c];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
+    t[k] = T[node];
+  }
+  double r[10];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) r[i] = 0.0;
+  for (int q = 0; q < 15; ++q) {
+    double gk[FORM == 1 ? 10 : 1][3];
+    double uq[3] = {0.0, 0.0, 0.0}, dt[3] = {0.0, 0.0, 0.0}, tq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      double gl[3];
+      phys3(g, c_q3.dphi2[q][k], gl);
+      const double ph = c_q3.phi2[q][k];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        uq[a] += ph * un[k][a];
+        dt[a] += gl[a] * t[k];
+        if constexpr (FORM == 1) gk[k][a] = gl[a];
+      }
+      if (FORM == 1) tq += ph * t[k];
+    }
+    const double w = c_q3.w[q] * g.adet * wgt;
+    const double adv = uq[0] * dt[0] + uq[1] * dt[1] + uq[2] * dt[2];       // u . grad T
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      if constexpr (FORM == 0) {
+        r[i] += w * c_q3.phi2[q][i] * adv;
+      } else {
+        const double ugi = uq[0] * gk[i][0] + uq[1] * gk[i][1] + uq[2] * gk[i][2];   // u . grad phi_i
+        r[i] += 0.5 * w * (c_q3.phi2[q][i] * adv - ugi * tq);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 10; ++i) rbuf[ndst[(size_t)i * nc + c]] = r[i];
+}
+
+void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                                int form) {
+  const dim3 grid(grid3(m.n_cells)), block(kBlock);
+  if (form == 0)
+    hipLaunchKernelGGL((k3_scalar_conv_cell<0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
+                       m.rbuf.p);
+  else
+    hipLaunchKernelGGL((k3_scalar_conv_cell<1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
+                       m.rbuf.p);
+  NSFEM_HIP(hipGetLastError());
+}
+
 // ---- CFL diagnostic on tetrahedra (reference source/ns_problem.py:554-587; the 2D kernel is
 // k_cfl): cell-local L2 projection onto DG2 of  2 |u| k / h  (h = dolfin CellDiameter = diameter of
 // the circumsphere) with the 14-point degree-4 rule, then the max-norm of the 10 coefficients.

@@ -443,6 +443,16 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
                              int form, bool picard);
 void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u, double cc,
                                 double* b, int form);
+// scalar transport (nsfem_step_scalar_imex): out = weight * C(u) T for the P2 scalar T on the velocity nodes, form 0
+// standard C_ij = int (u . grad phi_j) phi_i, 1 skew-symmetric 1/2 (C - C^T) -- element kernel (k_scalar_conv_cell /
+// k3_scalar_conv_cell, node-sorted element vectors in m.rbuf) plus the per-node sums in ascending cell order
+void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                              int form, double* out);
+void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                                int form);
+// out[n dim + c] = f[n dim + c] + T[n] b[c] on the P2 nodes (f null: out = T b)
+void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, const double* T, const double b[3],
+                           double* out);
 // per-facet surface force / flux / measure (boundary.hip): out[nf][dim + 2]
 void launch_boundary_force(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell,
                            const int32_t* flocal, const double* u, const double* p, double nu,
@@ -940,6 +950,28 @@ struct nsfem_ctx {
   int mg_v_pre_saved = 0, mg_v_degree_saved = 0;
   int imex_last_path = 0;
   int64_t imex_lattice_rhs = 0, imex_generic_rhs = 0, imex_matrix_builds = 0;
+  // IMEX scalar transport (nsfem_set_scalar / nsfem_step_scalar_imex): a P2 scalar on the velocity nodes, slots
+  // NSFEM_T0 .. NSFEM_TCONV_2 (allocated on first use).  A = alpha0/k M + gamma0 kappa K on p22, rebuilt only when one
+  // of the three numbers it was built from changes.  The stored convection vectors carry the weight (beta0 of their
+  // step) they were evaluated with: the next step scales by beta1 / weight.
+  struct Scalar {
+    bool configured = false, buoyant = false, have_source = false;
+    double kappa = 0.0, b[3] = {0.0, 0.0, 0.0};
+    int form = 0;
+    nsfem::BlockMat A;
+    double built_a = NAN, built_g0 = NAN, built_kappa = NAN;
+    nsfem::DevBuf<double> rhs, tmp, dinv, f_eff, bc_vals;
+    nsfem::DevBuf<int32_t> bc_dofs;
+    nsfem::DevBuf<uint8_t> mask;
+    std::vector<int32_t> h_bc;
+    int nbc = 0;
+    bool conv1_fresh = false, conv2_valid = false;   // TCONV_1 written since the last advance / TCONV_2 usable
+    double conv1_weight = 0.0, conv2_weight = 0.0;
+    int conv_form = -1;                              // form the stored vectors belong to
+    int64_t matrix_builds = 0, conv_launches = 0, conv_reuses = 0;
+    int dict_used = 0;
+    bool dinv_dirty = true;                          // 1 / diagonal belongs to an older matrix or Dirichlet set
+  } sc;
   nsfem::DevBuf<double> state[NSFEM_N_SLOTS];
   bool have_body_force = false, have_traction = false;
   // Dirichlet data
@@ -1047,7 +1079,7 @@ struct nsfem_ctx {
   // iteration predictor of a recurring solve (see hinted / next_hint in api.hip): the count the same solve needed
   // in the previous step, how many solves in a row needed exactly that count, and the number of solves so far
   struct SolveHint { int its = 0, same = 0; int64_t count = 0; };
-  SolveHint hint_mom[4], hint_poi, hint_cor;
+  SolveHint hint_mom[4], hint_poi, hint_cor, hint_sc;
   // in-situ timing of the matrix-free convection action (k_conv_cell + k_res_gather): one HIP-event
   // pair per application while enabled (nsfem_profile_convection; bench.py's assembly roofline)
   struct Probe {

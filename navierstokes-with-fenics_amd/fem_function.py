@@ -11,11 +11,12 @@ from form_language import Operand
 
 
 class DeviceFunction(Operand):
-    """One field (velocity: node-interleaved P2^2, or pressure: P1) in one state slot."""
+    """One field (velocity: node-interleaved P2^d, pressure: P1, or scalar: P2 on the velocity nodes) in one state
+    slot."""
 
     def __init__(self, solver, field, slot, name=None):
         self._solver = solver
-        self.field = field            # "velocity" | "pressure"
+        self.field = field            # "velocity" | "pressure" | "scalar"
         self.slot = slot
         self._name = name or field
 
@@ -36,7 +37,7 @@ class DeviceFunction(Operand):
 
     def dof_coordinates(self):
         dm = self._solver._dofmap
-        return dm.p2_coords if self.field == "velocity" else dm.p1_coords
+        return dm.p2_coords if self.field in ("velocity", "scalar") else dm.p1_coords
 
     def nodal_values(self):
         v = self.vector()
@@ -102,7 +103,7 @@ def vertex_or_cell_values(function):
     cells = mesh.cells.astype(np.int64)
     nv = mesh.coords.shape[0]
     node_of_vertex = np.empty(nv, dtype=np.int64)
-    if function.field == "velocity":
+    if function.field in ("velocity", "scalar"):
         node_of_vertex[cells.ravel()] = np.asarray(dm.p2_dofmap)[:, :cells.shape[1]].ravel()
     else:
         node_of_vertex[cells.ravel()] = np.asarray(dm.p1_dofmap).ravel()

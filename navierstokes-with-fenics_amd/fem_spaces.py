@@ -23,7 +23,7 @@ _KINDS = ("mixed", "velocity", "pressure")
 
 def evaluate_lagrange(dofmap, field, values, point):
     """Value at ``point`` of the P2 vector (field "velocity", values [n_p2 * dim]) or P1 scalar
-    (field "pressure") function; brute-force cell search (tests / diagnostics)."""
+    (field "pressure") or P2 scalar (field "scalar") function; brute-force cell search (tests / diagnostics)."""
     mesh, dim = dofmap.mesh, dofmap.dim
     p = np.asarray(point, dtype=np.float64).reshape(-1)[:dim]
     x = mesh.coords[mesh.cells.astype(np.int64)]
@@ -38,6 +38,8 @@ def evaluate_lagrange(dofmap, field, values, point):
         return float(l @ np.asarray(values)[dofmap.p1_dofmap[c]])
     pairs = ((1, 2), (0, 2), (0, 1)) if dim == 2 else ((2, 3), (1, 3), (1, 2), (0, 3), (0, 2), (0, 1))
     N = np.array([li * (2 * li - 1) for li in l] + [4 * l[a] * l[b] for a, b in pairs])
+    if field == "scalar":                                            # P2 scalar on the velocity nodes
+        return float(N @ np.asarray(values)[dofmap.p2_dofmap[c]])
     return N @ np.asarray(values).reshape(-1, dim)[dofmap.p2_dofmap[c]]
 
 

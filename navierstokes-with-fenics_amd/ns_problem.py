@@ -66,6 +66,12 @@ class ProblemBase:
               "rotation": "set_angular_velocity", "bcs": "set_boundary_conditions", "force": "set_body_force",
               "coefficients": "set_equation_coefficients", "initial": "set_initial_conditions"}
 
+    # A problem with a transported temperature defines any of these; they leave ``_temperature_bcs``
+    # ([(boundary_id, value), ...]), ``_temperature_coefficients`` (dict(diffusivity=..., buoyancy=..., convective_form=...))
+    # and ``_temperature_source`` behind, which go to the solver's set_scalar_* setters where it has them
+    _TEMPERATURE_HOOKS = ("set_temperature_coefficients", "set_temperature_boundary_conditions",
+                          "set_temperature_source")
+
     def _call_hooks(self, order):
         """mesh, then the hooks named in ``order``; afterwards the consistency checks of the reference"""
         self.setup_mesh()
@@ -77,6 +83,10 @@ class ProblemBase:
             if key == "coefficients":
                 assert isinstance(getattr(self, "_coefficient_handler", None), EquationCoefficientHandler)
                 self._coefficient_handler.close()
+        # optional hooks of a transported temperature (BoussinesqIMEXSolver): called only where the problem defines them
+        for hook in self._TEMPERATURE_HOOKS:
+            if hasattr(self, hook):
+                getattr(self, hook)()
         if not hasattr(self, "_bcs"):
             assert hasattr(self, "_periodic_bcs")
         if hasattr(self, "_internal_constraints"):
@@ -100,7 +110,19 @@ class ProblemBase:
                 constraints = (self._internal_constraints,) if hasattr(self, "_internal_constraints") else ()
                 solver.set_boundary_conditions(self._bcs, *constraints)
             elif key == "initial":
+                self._hand_over_temperature(solver)
                 solver.set_initial_conditions(self._initial_conditions)
+        if "initial" not in order:
+            self._hand_over_temperature(solver)
+
+    def _hand_over_temperature(self, solver):
+        """what the temperature hooks left behind -> solver, where the solver class has the setters"""
+        if hasattr(self, "_temperature_coefficients") and hasattr(solver, "set_scalar_coefficients"):
+            solver.set_scalar_coefficients(**self._temperature_coefficients)
+        if hasattr(self, "_temperature_bcs") and hasattr(solver, "set_scalar_boundary_conditions"):
+            solver.set_scalar_boundary_conditions(self._temperature_bcs)
+        if hasattr(self, "_temperature_source") and hasattr(solver, "set_scalar_source"):
+            solver.set_scalar_source(self._temperature_source)
 
     # -- field access ------------------------------------------------------------------
     def _get_solver(self):  # pragma: no cover
@@ -310,6 +332,8 @@ class ProblemBase:
         for index, name in solver.sub_space_association.items():
             components[index].rename(name, "")
             self._xdmf_file.write(components[index], current_time)
+        if any(hasattr(self, hook) for hook in self._TEMPERATURE_HOOKS) and hasattr(solver, "temperature"):
+            self._xdmf_file.write(solver.temperature, current_time)
         if hasattr(self, "_additional_field_output"):
             for field in self._additional_field_output:
                 if field is not None:
