@@ -536,6 +536,41 @@ int nsfem_volume_functionals(nsfem_ctx* ctx, int velocity_slot, int pressure_slo
                              const uint8_t* cell_flags  /* host, n_cells, or NULL = all cells */,
                              double out[NSFEM_N_FUNCTIONALS]);
 
+/* ---- point location, point evaluation and passive tracer particles (csrc/points.hip): replaces the point
+ * evaluation u(x), p(x) of a dolfin.Function in a driver's post-processing (probe time series, centre-line profiles)
+ * and adds particle tracking (new).  One context without a communicator; NSFEM_ERR_ARG on contexts with one (a point
+ * can lie in another rank's cells).
+ *
+ * nsfem_set_point_locator uploads, once, a uniform grid of bins over the mesh (host: point_locator.build_bins):
+ * bin of a point = floor((x_d - origin[d]) * inv_h[d]) per direction (x fastest, nbins[d] bins), candidates of bin b =
+ * bin_cells[bin_ptr[b] .. bin_ptr[b + 1]) in ascending cell id; all lists are checked against the mesh.
+ * nsfem_locate_points: cells[i] = the FIRST candidate of the bin of x[i] whose dim + 1 barycentric coordinates are all
+ * >= -1e-12, -1 for a point outside the mesh (a hole, outside the grid of bins, NaN).
+ * nsfem_eval_points: value at x[i] of the field in `slot` -- NSFEM_U0/U1/U2/USTAR: velocity, out [n][dim];
+ * NSFEM_P/P_OLD/P2_OLD: pressure, out [n]; NSFEM_T0/T1/T2 (after nsfem_set_scalar): P2 scalar, out [n]; any other slot
+ * is refused.  cells NULL: the points are located first; a cell of -1 gives NaN.  n = 0 launches nothing.
+ * One thread per point, plain loads and stores: two calls on the same input return the same bytes; no state slot is
+ * written. */
+int nsfem_set_point_locator(nsfem_ctx* ctx, const double* origin, const double* inv_h, const int32_t* nbins,
+                            const int32_t* bin_ptr, const int32_t* bin_cells);
+int nsfem_locate_points(nsfem_ctx* ctx, int64_t n, const double* x /* [n][dim] */, int32_t* cells);
+int nsfem_eval_points(nsfem_ctx* ctx, int slot, int64_t n, const double* x, const int32_t* cells /* NULL: locate */,
+                      double* out);
+/* Tracer particles, kept in the context: positions [n][dim], a cell that contains each, status (0 moving, 1 left).
+ * nsfem_tracers_set locates the points (outside the mesh: status 1) and replaces the cloud.
+ * nsfem_tracers_advect: classical RK4 over n_sub equal substeps of dt / n_sub in the velocity blended linearly in
+ * time, u(x, theta) = (1 - theta) U[slot_begin] + theta U[slot_end], theta from 0 to 1 over the whole dt (equal slots:
+ * frozen field).  Every stage point and the end point of a substep are located, the last known cell first and the
+ * bins only when the point is not in it.  A particle one of whose points lies outside the mesh gets status 1, keeps
+ * the position it had at the start of that substep and is never moved again.  Periodic sides are not wrapped.
+ * NSFEM_ERR_ARG: n_sub < 1, dt not finite, slots that are no velocity slots, no nsfem_tracers_set.
+ * nsfem_tracers_info: out = {particles, particles with status 1, advect calls since nsfem_tracers_set, bin-search
+ * fallbacks of the last advect call}. */
+int nsfem_tracers_set(nsfem_ctx* ctx, int64_t n, const double* x);
+int nsfem_tracers_advect(nsfem_ctx* ctx, int slot_begin, int slot_end, double dt, int n_sub);
+int nsfem_tracers_get(nsfem_ctx* ctx, double* x, int32_t* cells, uint8_t* status);   /* any may be NULL */
+int nsfem_tracers_info(nsfem_ctx* ctx, int64_t out[4]);
+
 /* ---- measurement hooks (bench.py): time `reps` launches of the dominant SpMV
  * with HIP events on the context's stream; ms per launch returned ------------- */
 /* in-situ HIP-event timing of the finest-level smoothing launches of the velocity multigrid

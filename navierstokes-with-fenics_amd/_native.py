@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
     "nsfem_volume_functionals",
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
+    "nsfem_set_point_locator", "nsfem_locate_points", "nsfem_eval_points",
+    "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
 )
 
 
@@ -209,6 +211,13 @@ def load_library(path=None):
         "nsfem_boundary_force": (C.c_int, [vp, C.c_int, C.c_int, i32, pi, pi, dbl, dbl, pd]),
         "nsfem_volume_functionals": (C.c_int, [vp, C.c_int, C.c_int, pd, pd, C.POINTER(C.c_uint8), pd]),
         "nsfem_comm_overlapped": (C.c_int, [vp, C.POINTER(C.c_int64), C.c_int]),
+        "nsfem_set_point_locator": (C.c_int, [vp, pd, pd, pi, pi, pi]),
+        "nsfem_locate_points": (C.c_int, [vp, i64, pd, pi]),
+        "nsfem_eval_points": (C.c_int, [vp, C.c_int, i64, pd, pi, pd]),
+        "nsfem_tracers_set": (C.c_int, [vp, i64, pd]),
+        "nsfem_tracers_advect": (C.c_int, [vp, C.c_int, C.c_int, dbl, C.c_int]),
+        "nsfem_tracers_get": (C.c_int, [vp, pd, pi, C.POINTER(C.c_uint8)]),
+        "nsfem_tracers_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_poisson_solve": (C.c_int, [vp, pd, i64, pi, pd, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_profile_smoother": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
         "nsfem_profile_convection": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
@@ -881,6 +890,74 @@ class NsfemContext:
         return dict(measure=float(out[0]), u_l2_sq=float(out[1]), grad_u_l2_sq=float(out[2]),
                     curl_l2_sq=float(out[3]), div_l2_sq=float(out[4]), momentum=out[5:5 + self.dim].copy(),
                     p_integral=float(out[8]), p_l2_sq=float(out[9]), grad_p_l2_sq=float(out[10]), values=out)
+
+    # -- point location / evaluation / tracer particles (csrc/points.hip) ------------
+    def set_point_locator(self, origin, inv_h, nbins, bin_ptr, bin_cells):
+        """upload the bins of point_locator.build_bins (once per context; ``set_point_locator(**build_bins(..))``)"""
+        o = np.ascontiguousarray(origin, dtype=np.float64)
+        ih = np.ascontiguousarray(inv_h, dtype=np.float64)
+        nb = np.ascontiguousarray(nbins, dtype=np.int32)
+        bp = np.ascontiguousarray(bin_ptr, dtype=np.int32)
+        bc = np.ascontiguousarray(bin_cells, dtype=np.int32)
+        if not (o.shape == ih.shape == nb.shape == (self.dim, )):
+            raise ValueError("origin, inv_h, nbins: expected %d entries each" % self.dim)
+        if bp.shape != (int(np.prod(nb.astype(np.int64))) + 1, ) or bc.shape != (int(bp[-1]), ):
+            raise ValueError("bin_ptr / bin_cells do not match nbins")
+        self._check(self._lib.nsfem_set_point_locator(self._h, _dp(o), _dp(ih), _ip(nb), _ip(bp), _ip(bc)))
+
+    def _points(self, X):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[1] != self.dim:
+            raise ValueError("points: expected shape [m, %d], got %s" % (self.dim, X.shape))
+        return X
+
+    def locate_points(self, X):
+        """int32 [m]: the lowest-id cell containing each point of X [m, dim] (-1: outside the mesh)"""
+        X = self._points(X)
+        cells = np.empty(X.shape[0], dtype=np.int32)
+        self._check(self._lib.nsfem_locate_points(self._h, X.shape[0], _dp(X), _ip(cells)))
+        return cells
+
+    def eval_points(self, slot, X, cells=None):
+        """values at X [m, dim] of the field in ``slot``: [m, dim] for a velocity slot, [m] for a pressure or scalar
+        slot; ``cells``: their cells if already known (locate_points), NaN where a cell is -1"""
+        X = self._points(X)
+        m = X.shape[0]
+        c = None
+        if cells is not None:
+            c = np.ascontiguousarray(cells, dtype=np.int32)
+            if c.shape != (m, ):
+                raise ValueError("cells: expected %d entries, got shape %s" % (m, c.shape))
+        vector = self.state_size(slot) == self.n_velocity
+        out = np.empty((m, self.dim) if vector else m, dtype=np.float64)
+        self._check(self._lib.nsfem_eval_points(self._h, int(slot), m, _dp(X), None if c is None else _ip(c),
+                                                _dp(out)))
+        return out
+
+    def tracers_set(self, X):
+        """replace the context's particle cloud by the points X [n, dim] (located; outside the mesh: status 1)"""
+        X = self._points(X)
+        self._check(self._lib.nsfem_tracers_set(self._h, X.shape[0], _dp(X)))
+        self._n_tracers = X.shape[0]
+
+    def tracers_advect(self, slot_begin, slot_end, dt, n_sub=1):
+        """RK4 over n_sub substeps of dt / n_sub in the velocity blended linearly from slot_begin to slot_end"""
+        self._check(self._lib.nsfem_tracers_advect(self._h, int(slot_begin), int(slot_end), float(dt), int(n_sub)))
+
+    def tracers_get(self):
+        """(positions [n, dim], cells int32 [n], status uint8 [n]: 0 moving, 1 left)"""
+        n = int(self.tracers_info()["n"])
+        x = np.empty((n, self.dim), dtype=np.float64)
+        cells = np.empty(n, dtype=np.int32)
+        status = np.empty(n, dtype=np.uint8)
+        self._check(self._lib.nsfem_tracers_get(self._h, _dp(x), _ip(cells), status.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return x, cells, status
+
+    def tracers_info(self):
+        """dict(n, n_left, advect_calls, fallbacks = bin searches of the last advect call)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_tracers_info(self._h, out))
+        return dict(n=int(out[0]), n_left=int(out[1]), advect_calls=int(out[2]), fallbacks=int(out[3]))
 
     def cfl_number(self, slot, step_size):
         out = C.c_double()

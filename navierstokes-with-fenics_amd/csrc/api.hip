@@ -3173,6 +3173,185 @@ extern "C" int nsfem_volume_functionals(nsfem_ctx* ctx, int velocity_slot, int p
   API_END(ctx)
 }
 
+// ------------------------------------------------- point location, point evaluation, tracer particles (points.hip)
+static void points_require_supported(nsfem_ctx* c, bool need_locator = true) {
+  NSFEM_REQUIRE(!c->comm, "point evaluation / tracers: contexts with a communicator (partitioned meshes) are not "
+                          "supported -- a point can lie in another rank's cells");
+  if (need_locator) NSFEM_REQUIRE(c->pts.have_locator, "nsfem_set_point_locator has not been called");
+}
+
+// field kind of a state slot for point evaluation: 0 velocity, 1 pressure, 2 P2 scalar; anything else is refused
+static int point_field_kind(nsfem_ctx* c, int slot) {
+  switch (slot) {
+    case NSFEM_U0: case NSFEM_U1: case NSFEM_U2: case NSFEM_USTAR: return 0;
+    case NSFEM_P: case NSFEM_P_OLD: case NSFEM_P2_OLD: return 1;
+    case NSFEM_T0: case NSFEM_T1: case NSFEM_T2:
+      NSFEM_REQUIRE(c->sc.configured, "temperature slot without nsfem_set_scalar");
+      ensure_scalar_slot(c, slot);
+      return 2;
+    default: throw Error(NSFEM_ERR_ARG, "not a state slot (velocity, pressure or transported scalar level)");
+  }
+}
+
+template <class T>
+static void grow(DevBuf<T>& b, size_t count) {
+  if (b.n < count) b.alloc(count);
+}
+
+extern "C" int nsfem_set_point_locator(nsfem_ctx* ctx, const double* origin, const double* inv_h,
+                                       const int32_t* nbins, const int32_t* bin_ptr, const int32_t* bin_cells) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && origin && inv_h && nbins && bin_ptr, "null argument");
+  points_require_supported(ctx, false);
+  const int dim = ctx->mesh.dim;
+  int64_t nb = 1;
+  for (int d = 0; d < dim; ++d) {
+    NSFEM_REQUIRE(std::isfinite(origin[d]) && std::isfinite(inv_h[d]) && inv_h[d] > 0.0, "point locator: bad grid");
+    NSFEM_REQUIRE(nbins[d] >= 1, "point locator: nbins must be >= 1");
+    nb *= nbins[d];
+    NSFEM_REQUIRE(nb < ((int64_t)1 << 31) - 1, "point locator: too many bins");
+  }
+  // the kernels index the mesh with these lists: every entry is checked here, once
+  NSFEM_REQUIRE(bin_ptr[0] == 0, "point locator: bin_ptr[0] != 0");
+  for (int64_t b = 0; b < nb; ++b) NSFEM_REQUIRE(bin_ptr[b + 1] >= bin_ptr[b], "point locator: bin_ptr decreases");
+  const int64_t len = bin_ptr[nb];
+  NSFEM_REQUIRE(len == 0 || bin_cells, "null argument");
+  for (int64_t k = 0; k < len; ++k)
+    NSFEM_REQUIRE(bin_cells[k] >= 0 && bin_cells[k] < ctx->mesh.n_cells, "point locator: cell id out of range");
+  nsfem_ctx::Points& P = ctx->pts;
+  hipStream_t s = ctx->stream;
+  P.have_locator = false;
+  P.bin_ptr.upload(bin_ptr, (size_t)nb + 1, s);
+  P.bin_cells.upload(bin_cells, (size_t)len, s);
+  NSFEM_HIP(hipStreamSynchronize(s));
+  P.loc = PointLocatorDev();
+  for (int d = 0; d < dim; ++d) {
+    P.loc.origin[d] = origin[d];
+    P.loc.inv_h[d] = inv_h[d];
+    P.loc.nbins[d] = nbins[d];
+  }
+  P.loc.bin_ptr = P.bin_ptr.p;
+  P.loc.bin_cells = P.bin_cells.p;
+  P.have_locator = true;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_locate_points(nsfem_ctx* ctx, int64_t n, const double* x, int32_t* cells) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  points_require_supported(ctx);
+  NSFEM_REQUIRE(n >= 0 && (n == 0 || (x && cells)), "n < 0 or null argument");
+  if (n == 0) return NSFEM_OK;
+  nsfem_ctx::Points& P = ctx->pts;
+  hipStream_t s = ctx->stream;
+  const size_t dim = (size_t)ctx->mesh.dim;
+  grow(P.x, (size_t)n * dim);
+  grow(P.cells, (size_t)n);
+  NSFEM_HIP(hipMemcpyAsync(P.x.p, x, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+  launch_locate_points(s, ctx->mesh, P.loc, n, P.x.p, P.cells.p);
+  NSFEM_HIP(hipMemcpyAsync(cells, P.cells.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_eval_points(nsfem_ctx* ctx, int slot, int64_t n, const double* x, const int32_t* cells,
+                                 double* out) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  points_require_supported(ctx);
+  const int kind = point_field_kind(ctx, slot);
+  NSFEM_REQUIRE(n >= 0 && (n == 0 || (x && out)), "n < 0 or null argument");
+  if (n == 0) return NSFEM_OK;
+  nsfem_ctx::Points& P = ctx->pts;
+  hipStream_t s = ctx->stream;
+  const size_t dim = (size_t)ctx->mesh.dim, nv = kind == 0 ? dim : 1;
+  grow(P.x, (size_t)n * dim);
+  grow(P.cells, (size_t)n);
+  grow(P.out, (size_t)n * dim);
+  NSFEM_HIP(hipMemcpyAsync(P.x.p, x, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+  if (cells) NSFEM_HIP(hipMemcpyAsync(P.cells.p, cells, sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+  else launch_locate_points(s, ctx->mesh, P.loc, n, P.x.p, P.cells.p);
+  launch_eval_points(s, ctx->mesh, kind, ctx->state[slot].p, n, P.x.p, P.cells.p, P.out.p);
+  NSFEM_HIP(hipMemcpyAsync(out, P.out.p, sizeof(double) * n * nv, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_tracers_set(nsfem_ctx* ctx, int64_t n, const double* x) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  points_require_supported(ctx);
+  NSFEM_REQUIRE(n >= 0 && (n == 0 || x), "n < 0 or null argument");
+  nsfem_ctx::Points& P = ctx->pts;
+  hipStream_t s = ctx->stream;
+  const size_t dim = (size_t)ctx->mesh.dim, blocks = (size_t)((n + 255) / 256);
+  grow(P.tx, (size_t)n * dim);
+  grow(P.tcell, (size_t)n);
+  grow(P.tstatus, (size_t)n);
+  grow(P.tcounts, 2 * blocks);
+  if (n > 0) NSFEM_HIP(hipMemcpyAsync(P.tx.p, x, sizeof(double) * n * dim, hipMemcpyHostToDevice, s));
+  launch_locate_points(s, ctx->mesh, P.loc, n, P.tx.p, P.tcell.p);
+  launch_tracer_init(s, n, P.tcell.p, P.tstatus.p, P.tcounts.p);
+  NSFEM_HIP(hipStreamSynchronize(s));
+  P.n_tracers = n;
+  P.advect_calls = 0;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_tracers_advect(nsfem_ctx* ctx, int slot_begin, int slot_end, double dt, int n_sub) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  points_require_supported(ctx);
+  nsfem_ctx::Points& P = ctx->pts;
+  NSFEM_REQUIRE(P.n_tracers >= 0, "nsfem_tracers_set has not been called");
+  NSFEM_REQUIRE(point_field_kind(ctx, slot_begin) == 0 && point_field_kind(ctx, slot_end) == 0,
+                "tracers move in a velocity slot");
+  NSFEM_REQUIRE(n_sub >= 1, "n_sub < 1");
+  NSFEM_REQUIRE(std::isfinite(dt), "dt is not finite");
+  const double* ua = ctx->state[slot_begin].p;
+  const double* ub = slot_end == slot_begin ? nullptr : ctx->state[slot_end].p;
+  launch_advect_tracers(ctx->stream, ctx->mesh, P.loc, ua, ub, dt, n_sub, P.n_tracers, P.tx.p, P.tcell.p, P.tstatus.p,
+                        P.tcounts.p);
+  ++P.advect_calls;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_tracers_get(nsfem_ctx* ctx, double* x, int32_t* cells, uint8_t* status) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  points_require_supported(ctx, false);
+  nsfem_ctx::Points& P = ctx->pts;
+  NSFEM_REQUIRE(P.n_tracers >= 0, "nsfem_tracers_set has not been called");
+  hipStream_t s = ctx->stream;
+  const size_t n = (size_t)P.n_tracers, dim = (size_t)ctx->mesh.dim;
+  if (n && x) NSFEM_HIP(hipMemcpyAsync(x, P.tx.p, sizeof(double) * n * dim, hipMemcpyDeviceToHost, s));
+  if (n && cells) NSFEM_HIP(hipMemcpyAsync(cells, P.tcell.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  if (n && status) NSFEM_HIP(hipMemcpyAsync(status, P.tstatus.p, n, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_tracers_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  nsfem_ctx::Points& P = ctx->pts;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (P.n_tracers < 0) return NSFEM_OK;
+  const size_t blocks = (size_t)((P.n_tracers + 255) / 256);
+  std::vector<int32_t> h(2 * blocks);
+  if (blocks) {
+    NSFEM_HIP(hipMemcpyAsync(h.data(), P.tcounts.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    NSFEM_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  out[0] = P.n_tracers;
+  for (size_t b = 0; b < blocks; ++b) {
+    out[1] += h[2 * b];
+    out[3] += h[2 * b + 1];
+  }
+  out[2] = P.advect_calls;
+  API_END(ctx)
+}
+
 // ----------------------------------------------------------- operator access
 static const BlockMat* get_op(nsfem_ctx* c, int op, int* nv_apply) {
   *nv_apply = 1;

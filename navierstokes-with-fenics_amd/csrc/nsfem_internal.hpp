@@ -464,6 +464,30 @@ constexpr int kVolParts = 1024;
 void upload_functional_tables(int dim);
 void launch_vol_functionals(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* ur,
                             const double* pr, const uint8_t* flags, double* parts, double* out);
+
+// ---- point location, point evaluation and tracer particles (points.hip).  The uniform grid of bins over the mesh
+// (host: point_locator.build_bins): bin of a point = floor((x - origin) * inv_h) per direction, x fastest; the
+// candidates of bin b are bin_cells[bin_ptr[b] .. bin_ptr[b + 1]), ascending cell ids.
+struct PointLocatorDev {
+  double origin[3] = {0.0, 0.0, 0.0}, inv_h[3] = {0.0, 0.0, 0.0};
+  int32_t nbins[3] = {1, 1, 1};
+  const int32_t* bin_ptr = nullptr;
+  const int32_t* bin_cells = nullptr;
+};
+// cells[i] = lowest-id candidate cell containing x[i] (all barycentric coordinates >= -1e-12), -1: outside
+void launch_locate_points(hipStream_t s, const MeshDev& m, const PointLocatorDev& L, int64_t n, const double* x,
+                          int32_t* cells);
+// kind 0: velocity f [dim n_p2] -> out [n][dim]; 1: P1 field f [n_p1]; 2: P2 scalar f [n_p2] -> out [n]; NaN where the
+// cell is not one of the mesh
+void launch_eval_points(hipStream_t s, const MeshDev& m, int kind, const double* f, int64_t n, const double* x,
+                        const int32_t* cells, double* out);
+// status[i] = cells[i] < 0; counts [2][workgroups of 256 particles]: (left, 0) per workgroup
+void launch_tracer_init(hipStream_t s, int64_t n, const int32_t* cells, uint8_t* status, int32_t* counts);
+// RK4 over n_sub substeps of dt / n_sub in (1 - theta) ua + theta ub (ub null: frozen ua); counts: (left, bin-search
+// fallbacks) per workgroup
+void launch_advect_tracers(hipStream_t s, const MeshDev& m, const PointLocatorDev& L, const double* ua,
+                           const double* ub, double dt, int n_sub, int64_t n, double* x, int32_t* cells,
+                           uint8_t* status, int32_t* counts);
 // diag extraction: d[(i,a)] = 1 / A_ii[a][a]  (mask rows -> 1)
 void launch_inv_diag(hipStream_t s, const BlockMat& A, int nv, const uint8_t* rowmask,
                      double* dinv);
@@ -1094,6 +1118,20 @@ struct nsfem_ctx {
   nsfem::DevBuf<double> vf_parts, vf_ref_u, vf_ref_p, vf_u, vf_p;
   nsfem::DevBuf<uint8_t> vf_flags;
   std::vector<uint8_t> vf_flags_host;
+  // point location / evaluation / tracers (points.hip): the bins of nsfem_set_point_locator, grow-only work buffers of
+  // nsfem_locate_points / nsfem_eval_points, and the particle cloud of nsfem_tracers_*
+  struct Points {
+    bool have_locator = false;
+    nsfem::PointLocatorDev loc;
+    nsfem::DevBuf<int32_t> bin_ptr, bin_cells;
+    nsfem::DevBuf<double> x, out;
+    nsfem::DevBuf<int32_t> cells;
+    int64_t n_tracers = -1;                     // -1: nsfem_tracers_set has not been called
+    nsfem::DevBuf<double> tx;                   // [n][dim]
+    nsfem::DevBuf<int32_t> tcell, tcounts;      // [n]; [workgroups][2]: (left, bin-search fallbacks of the last call)
+    nsfem::DevBuf<uint8_t> tstatus;             // [n] 0 moving, 1 left
+    int64_t advect_calls = 0;
+  } pts;
   int64_t jac_lattice_launches = 0;   // applications of the matrix-free Jacobian through k_jac_lattice
   bool mf_active = false;           // the running step driver applies the Jacobian matrix-free
   int pressure_history = 0;         // IPCS: pressure levels shifted since the state was last set (0..2)

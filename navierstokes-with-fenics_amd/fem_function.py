@@ -48,6 +48,14 @@ class DeviceFunction(Operand):
         from fem_spaces import evaluate_lagrange
         return evaluate_lagrange(self._solver._dofmap, self.field, self.vector(), point)
 
+    def eval_points(self, X):
+        """Values at the points X [m, dim] from ONE device call (nsfem_eval_points: bin search + basis + gather per
+        point, nothing but X and the values crosses the bus): [m, dim] for the velocity, [m] otherwise; NaN at points
+        outside the mesh.  The bins of the locator are built on the first use (tracers.ensure_point_locator)."""
+        from tracers import ensure_point_locator
+        ensure_point_locator(self._solver)
+        return self._solver._ctx.eval_points(self.slot, X)
+
 
 class MixedFunction:
     """(velocity, pressure) pair standing in for a Function on the mixed space."""

@@ -203,6 +203,23 @@ class ProblemBase:
                     divergence_l2=math.sqrt(max(r["div_l2_sq"], 0.0)), dissipation_integrand=r["grad_u_l2_sq"],
                     pressure_l2=math.sqrt(max(r["p_l2_sq"], 0.0)), volume=r["measure"])
 
+    def _add_tracer_cloud(self, X):
+        """Register passive tracer particles starting at X [n, dim]: ``solve_problem`` advects them through every time
+        step (after ``solver.solve()``, over the interval just solved) on the device.  Returns the
+        ``tracers.TracerCloud`` (bound to the solver once it exists).  New; the reference has no particles."""
+        from tracers import TracerCloud
+        cloud = TracerCloud(getattr(self, "_navier_stokes_solver", None), X)
+        self.__dict__.setdefault("_tracer_clouds", []).append(cloud)
+        return cloud
+
+    def _add_point_probes(self, X):
+        """Register probe points X [m, dim]: ``solve_problem`` records velocity, pressure (and temperature) there
+        after every ``solver.solve()``.  Returns the ``tracers.PointProbes``."""
+        from tracers import PointProbes
+        probes = PointProbes(getattr(self, "_navier_stokes_solver", None), X)
+        self.__dict__.setdefault("_point_probes", []).append(probes)
+        return probes
+
     def _compute_stream_potential(self):
         """Velocity potential phi (the reference's "stream potential", :105-176): P1 solution of
         (grad phi, grad psi) = (div u, psi) - sum over the remaining boundaries of (n . u, psi),
@@ -415,6 +432,8 @@ class InstationaryProblem(ProblemBase):
                 assert hasattr(solver, key), "unknown solver setting %r" % (key,)
                 setattr(solver, key, value)
         self._hand_over_to_solver(solver, ("coefficients", "force", "periodic", "rotation", "bcs", "initial"))
+        for registered in getattr(self, "_tracer_clouds", []) + getattr(self, "_point_probes", []):
+            registered.bind(solver)
         self._write_xdmf_file(current_time=0.0)
         print("Solving problem until time = {:0.2f}".format(self._time_stepping.end_time))
 
@@ -429,6 +448,11 @@ class InstationaryProblem(ProblemBase):
             t_wall = time.perf_counter()
             solver.solve()
             self.step_wall_times.append(time.perf_counter() - t_wall)
+            # registered particles move through the interval just solved (U1 -> U0), probes sample its end
+            for cloud in getattr(self, "_tracer_clouds", ()):
+                cloud.advect()
+            for probes in getattr(self, "_point_probes", ()):
+                probes.record(ts.next_time)
             if self._postprocessing_frequency > 0 and \
                     ts.step_number % self._postprocessing_frequency == 0:
                 self.postprocess_solution()
