@@ -469,6 +469,31 @@ int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, 
  * of the last solve ran on the stencil-dictionary copy of the matrix (dictionaries equal to the matrix bit for bit:
  * binary lattice spacings), else 0 (CSR)} */
 int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]);
+/* ---- variable viscosity in the IMEX step (new; the reference knows one constant viscosity).  nu = c_v + nu_x(gamma,
+ * Delta_K) with gamma = sqrt(2 S:S) = sqrt(1/2 sum_ab (g_ab + g_ba)^2), g_ab = d_b u_a, and Delta_K = |K|^(1/dim),
+ * |K| = |det J_K| / dim!.  The constant part c_v K stays in the implicit matrix; the remainder
+ *   V(u)_(i,a) = sum_K sum_q w_q |det J_K| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i
+ * (7-point Radon rule on triangles, 15-point Keast rule on tetrahedra: the integrand is no polynomial, the rule is part
+ * of the definition; always the symmetric form, whatever nsfem_set_viscous_form says) is explicit: nsfem_step_imex then
+ * stores and extrapolates N(u) = c_c conv(u) + V(u).  nu_x is used as given (not multiplied by c_v); V has the sign of
+ * c_v K u.
+ *   law 0  none: nsfem_step_imex launches exactly what it launches without this call (params may be NULL)
+ *   law 1  Smagorinsky  nu_x = (C_s Delta_K)^2 gamma                         params = {C_s >= 0}
+ *   law 2  Carreau      nu_x = a [ (1 + (lambda gamma)^2)^((n-1)/2) - 1 ]    params = {a finite, lambda >= 0, n > 0};
+ *          c_v is the zero-shear viscosity, a = c_v - nu_inf
+ * A change of law or parameters invalidates the stored vectors.  NSFEM_ERR_ARG: unknown law, parameters outside these
+ * ranges or not finite, a law other than 0 on contexts with a communicator; nsfem_step_ipcs and nsfem_step_bdf refuse
+ * to run while a law other than 0 is set. */
+int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double params[4]);
+/* Test hook: out_host [dim n_p2] = weight * V(u) for u = velocity_slot (NSFEM_U0, U1, U2 or USTAR) -- the element kernel
+ * plus the per-node sums, no Dirichlet rows; no stored state is touched.  Two calls on the same state return the same
+ * bytes.  NSFEM_ERR_ARG: no law set, other slots, contexts with a communicator. */
+int nsfem_viscosity_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host);
+/* Output: out_host [n_cells] = sum_q w_q nu_x(gamma_q) / sum_q w_q, the cell mean of nu_x for u = velocity_slot */
+int nsfem_viscosity_cells(nsfem_ctx* ctx, int velocity_slot, double* out_host);
+/* out = {current law, element-kernel launches so far (steps, hook and cell means), stored vectors N(u2) that had to be
+ * recomputed with a law set, 0} */
+int nsfem_viscosity_info(nsfem_ctx* ctx, int64_t out[4]);
 /* replaces _advance_solution (ns_solver_base.py:1012-1016, ns_ipcs_solver.py:35-43); scheme 0 with a scalar
  * configured: also T2 <- T1 <- T0 and the stored scalar convection */
 int nsfem_advance(nsfem_ctx* ctx, int scheme /* 0 ipcs, 1 bdf */);

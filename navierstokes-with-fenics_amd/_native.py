@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
     "nsfem_volume_functionals",
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
+    "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
     "nsfem_set_point_locator", "nsfem_locate_points", "nsfem_eval_points",
     "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
 )
@@ -177,6 +178,10 @@ def load_library(path=None):
         "nsfem_step_scalar_imex": (C.c_int, [vp, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_scalar_convection": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, pd]),
         "nsfem_scalar_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_viscosity_law": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_viscosity_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
+        "nsfem_viscosity_cells": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_viscosity_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_viscous_form": (C.c_int, [vp, C.c_int]),
         "nsfem_set_convective_form": (C.c_int, [vp, C.c_int, C.c_int]),
         "nsfem_set_state": (C.c_int, [vp, C.c_int, pd, i64]),
@@ -474,6 +479,36 @@ class NsfemContext:
         self._check(self._lib.nsfem_scalar_info(self._h, out))
         return dict(matrix_builds=int(out[0]), convection_launches=int(out[1]), convection_reuses=int(out[2]),
                     dictionary=bool(out[3]))
+
+    # -- variable viscosity in the IMEX step ---------------------------------------------
+    def set_viscosity_law(self, law, params=None):
+        """law 0 none (step_imex runs exactly as without this call), 1 Smagorinsky params = (C_s, ), 2 Carreau
+        params = (a, lambda, n); up to four numbers, the rest are zeros"""
+        p = np.zeros(4, dtype=np.float64)
+        if params is not None:
+            given = np.asarray(params, dtype=np.float64).ravel()
+            assert given.size <= 4
+            p[:given.size] = given
+        self._check(self._lib.nsfem_set_viscosity_law(self._h, int(law), _dp(p)))
+
+    def viscosity_residual(self, velocity_slot=U1, weight=1.0):
+        """test hook: weight * V(u), interleaved [dim * n_p2] (element kernel + node sums; no stored state touched)"""
+        out = np.empty(self.dim * self.n_p2, dtype=np.float64)
+        self._check(self._lib.nsfem_viscosity_residual(self._h, int(velocity_slot), float(weight), _dp(out)))
+        return out
+
+    def viscosity_cells(self, velocity_slot=U0):
+        """cell means of nu_x for the velocity of the slot, [n_cells]"""
+        out = np.empty(self.n_cells, dtype=np.float64)
+        self._check(self._lib.nsfem_viscosity_cells(self._h, int(velocity_slot), _dp(out)))
+        return out
+
+    def viscosity_info(self):
+        """dict(law, element_launches, recomputed): the current law, the element-kernel launches so far and how
+        often a stored explicit vector had to be recomputed with a law set"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_viscosity_info(self._h, out))
+        return dict(law=int(out[0]), element_launches=int(out[1]), recomputed=int(out[2]))
 
     def step_bdf(self, opts=None):
         o = opts or self.default_step_opts()

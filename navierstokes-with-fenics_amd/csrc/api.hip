@@ -2152,6 +2152,7 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   NSFEM_REQUIRE(opts->newton_max_iter > 0 && opts->newton_max_iter < NSFEM_MAX_NEWTON,
                 "newton_max_iter out of range");
   NSFEM_REQUIRE(ctx->alpha[0] != 0.0, "the pressure-correction scheme needs alpha0 != 0");
+  NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
   NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
   if (ctx->conv_form != opts->convective_form || ctx->picard) ctx->graph_epoch++;
   ctx->conv_form = opts->convective_form;
@@ -2389,8 +2390,23 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
   return 1;
 }
 
+// Variable viscosity (nsfem_set_viscosity_law): the stored explicit vector is N(u) = c_c conv(u) + V(u).  imex_rhs runs
+// unchanged on either path; then, BEFORE the Dirichlet rows are set, TWO more launches: the element kernel on u
+// (weight 1, element vectors node-sorted in mesh.rbuf) and k_visc_gather, which forms v = the per-node sums from zero in
+// ascending cell order and then, per entry,  n1 <- n1 + v,  rhs <- rhs - b0 v  (two roundings, no contraction).  That
+// is the summation order with a law set: rhs = [ -(t + (b0 c_c conv(u1) + b1 N2)) ] - b0 V(u1), the bracket as imex_rhs
+// leaves it.  N2 is read as stored (it already holds V(u2)); where it is computed afresh, V(u2) is added the same way
+// with rhs = null.  With law 0 nothing is launched.
+static void viscosity_add(nsfem_ctx* c, const double* u, double b0, double* n1, double* rhs) {
+  launch_viscosity_cells(c->stream, c->mesh, u, 1.0, c->visc.law, c->visc.p, false);
+  launch_viscosity_gather(c->stream, c->mesh, b0, n1, rhs);
+  ++c->visc.launches;
+}
+
 static void imex_require_supported(nsfem_ctx* c) {
   NSFEM_REQUIRE(c->imex_active, "nsfem_set_imex has not been called");
+  NSFEM_REQUIRE(c->visc.law == 0 || !c->comm,
+                "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   const bool euler = c->mesh.dim == 2 ? c->omega_dot != 0.0
                                       : (c->omega_dot3[0] != 0.0 || c->omega_dot3[1] != 0.0 || c->omega_dot3[2] != 0.0);
   NSFEM_REQUIRE(!coriolis_active(c) && !euler,
@@ -2421,11 +2437,16 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   if (ctx->imex_beta[1] != 0.0) {
     // c_c N(u2): what the previous step stored, unless the level, the form or the coefficient changed under it
     const bool stored = ctx->conv_n2_valid && (ctx->conv_n_form == -2 ||
-                                               (ctx->conv_n_form == ctx->conv_form && ctx->conv_n_cc == cc));
+                                               (ctx->conv_n_form == ctx->conv_form && ctx->conv_n_cc == cc &&
+                                                ctx->conv_n_visc == ctx->visc.epoch));
     if (!stored) {
       ctx->state[NSFEM_CONV_N2].zero(s);
       if (cc != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc, ctx->state[NSFEM_CONV_N2].p,
                                                 ctx->conv_form);
+      if (ctx->visc.law != 0) {
+        viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, ctx->state[NSFEM_CONV_N2].p, nullptr);
+        ++ctx->visc.recomputed;
+      }
       if (ctx->distributed() && ctx->ghost_v.p) launch_zero_ghost(s, nv, ctx->mask_v.p, ctx->state[NSFEM_CONV_N2].p);
       ctx->conv_n2_valid = true;
     }
@@ -2433,9 +2454,12 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   }
   ctx->imex_last_path = imex_rhs(ctx, 0, n2, ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p, u1_travelled);
   ++(ctx->imex_last_path == 2 ? ctx->imex_lattice_rhs : ctx->imex_generic_rhs);
+  if (ctx->visc.law != 0)
+    viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
   ctx->conv_n1_fresh = true;
   ctx->conv_n_form = ctx->conv_form;
   ctx->conv_n_cc = cc;
+  ctx->conv_n_visc = ctx->visc.epoch;
   {
     // Dirichlet rows u*_i = g_i; start vector u1 with the Dirichlet values
     double* x = ctx->state[NSFEM_USTAR].p;
@@ -2543,11 +2567,92 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
     n2 = ctx->kw.z.p;
     NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nv, s));
     if (cc_of(ctx) != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form);
+    if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, n2, nullptr);
   }
   imex_rhs(ctx, path, n2, n1, out, u1_travelled);
+  if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], n1, out);
   NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+// ---------------------------------------------------------------- variable viscosity
+extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double params[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(law >= 0 && law <= 2, "variable viscosity: unknown law (0 none, 1 Smagorinsky, 2 Carreau)");
+  NSFEM_REQUIRE(law == 0 || !ctx->comm,
+                "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(law == 0 || params, "variable viscosity: the law needs its parameters");
+  double p[4] = {0.0, 0.0, 0.0, 0.0};
+  if (law == 1) {
+    NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] >= 0.0, "Smagorinsky: C_s must be finite and >= 0");
+    p[0] = params[0];
+  } else if (law == 2) {
+    NSFEM_REQUIRE(std::isfinite(params[0]), "Carreau: a = c_v - nu_inf must be finite");
+    NSFEM_REQUIRE(std::isfinite(params[1]) && params[1] >= 0.0, "Carreau: lambda must be finite and >= 0");
+    NSFEM_REQUIRE(std::isfinite(params[2]) && params[2] > 0.0, "Carreau: n must be finite and > 0");
+    p[0] = params[0];
+    p[1] = params[1];
+    p[2] = params[2];
+  }
+  nsfem_ctx::Viscosity& v = ctx->visc;
+  // (the stored explicit vectors belong to the law and parameters they were evaluated with; the law enters no
+  // captured Krylov body -- its launches precede the solve --, so graph_epoch stays)
+  if (law != v.law || std::memcmp(p, v.p, sizeof(p)) != 0) ++v.epoch;
+  v.law = law;
+  std::memcpy(v.p, p, sizeof(p));
+  API_END(ctx)
+}
+
+static void viscosity_require(nsfem_ctx* ctx, int velocity_slot) {
+  NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->visc.law != 0, "variable viscosity: no law set (nsfem_set_viscosity_law)");
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+}
+
+extern "C" int nsfem_viscosity_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  viscosity_require(ctx, velocity_slot);
+  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  hipStream_t s = ctx->stream;
+  const int64_t nv = nvel(ctx);
+  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
+  ctx->kw.ensure(nv);
+  ++ctx->kw.touch;
+  double* out = ctx->kw.q.p;
+  NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
+  launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->visc.law, ctx->visc.p, false);
+  launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
+  ++ctx->visc.launches;
+  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_viscosity_cells(nsfem_ctx* ctx, int velocity_slot, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  viscosity_require(ctx, velocity_slot);
+  hipStream_t s = ctx->stream;
+  // (the cell means land in the element buffer, which every user fills before it reads)
+  launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, 1.0, ctx->visc.law, ctx->visc.p, true);
+  ++ctx->visc.launches;
+  NSFEM_HIP(hipMemcpyAsync(out_host, ctx->mesh.rbuf.p, sizeof(double) * ctx->mesh.n_cells, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_viscosity_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->visc.law;
+  out[1] = ctx->visc.launches;
+  out[2] = ctx->visc.recomputed;
+  out[3] = 0;
   API_END(ctx)
 }
 
@@ -2791,6 +2896,7 @@ extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem
   nsfem_step_info local;
   API_BEGIN
   NSFEM_REQUIRE(ctx && opts, "null argument");
+  NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
   NSFEM_REQUIRE(opts->convective_form >= 0 && opts->convective_form <= 3, "unknown convective form");
   NSFEM_REQUIRE(opts->newton_max_iter > 0 && opts->newton_max_iter < NSFEM_MAX_NEWTON,
                 "newton_max_iter out of range");

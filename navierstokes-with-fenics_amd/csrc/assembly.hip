@@ -871,6 +871,118 @@ void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, con
   NSFEM_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------- variable viscosity (nsfem_set_viscosity_law)
+// Explicit remainder of a strain-rate dependent viscosity, one thread per CELL, 7-point rule (part of the definition:
+// the integrand is no polynomial):
+//   r_(i,a) = wgt sum_q w_q |det J| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i,   g_ab = d_b u_a,
+//   gamma = sqrt(1/2 sum_ab (g_ab + g_ba)^2),   Delta_K^2 = |det J| / 2
+// u at the 6 nodes in registers; the physical gradients, g, gamma and nu_x of a quadrature point are formed once and
+// shared by the 6 test functions.  The element vector goes node-sorted into m.rbuf (ndst, as k_conv_cell); k_visc_gather
+// sums the run of every node in ascending cell order: no atomics, the same state gives the same bytes.
+// MEAN: no element vector; rbuf[c] = sum_q w_q nu_x(gamma_q) / sum_q w_q, the cell mean of nu_x (output).
+template <int LAW, bool MEAN>
+__global__ __launch_bounds__(256) void k_visc_var_cell(int nc, const double* __restrict__ vx,
+                                                       const int32_t* __restrict__ p2,
+                                                       const double* __restrict__ u, double wgt, double p0, double p1,
+                                                       double pp2, const int32_t* __restrict__ ndst,
+                                                       double* __restrict__ rbuf) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo g = load_geo(vx, nc, c);
+  const double delta2 = 0.5 * g.adet;
+  double ux[6], uy[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int node = p2[(size_t)k * nc + c];
+    const double2 a = reinterpret_cast<const double2*>(u)[node];
+    ux[k] = a.x;
+    uy[k] = a.y;
+  }
+  double rx[6], ry[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rx[i] = ry[i] = 0.0;
+  double mean = 0.0, wsum = 0.0;
+  for (int q = 0; q < 7; ++q) {
+    double gx[6], gy[6];
+    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx[k], gy[k]);
+      g00 += gx[k] * ux[k];
+      g01 += gy[k] * ux[k];
+      g10 += gx[k] * uy[k];
+      g11 += gy[k] * uy[k];
+    }
+    const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T
+    const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
+    const double nu = visc_law_nu<LAW>(gamma, delta2, p0, p1, pp2);
+    if (MEAN) {
+      mean += c_q.w[q] * nu;
+      wsum += c_q.w[q];
+    } else {
+      const double w = c_q.w[q] * g.adet * wgt * nu;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        rx[i] += w * (s00 * gx[i] + s01 * gy[i]);
+        ry[i] += w * (s01 * gx[i] + s11 * gy[i]);
+      }
+    }
+  }
+  if (MEAN) {
+    rbuf[c] = mean / wsum;
+  } else {
+    double2* out = reinterpret_cast<double2*>(rbuf);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) out[ndst[(size_t)i * nc + c]] = make_double2(rx[i], ry[i]);
+  }
+}
+
+// v = sum of the run nptr[n] .. nptr[n + 1] of the node-sorted element vectors (dim components per entry, ascending
+// cell order, as k_res_gather), one thread per (node, component); in the same launch  n1 += v  and  rhs -= b0 v
+// (rhs null: the plain sum, nsfem_viscosity_residual and the stored vector of the old level)
+__global__ __launch_bounds__(256) void k_visc_gather(int64_t n_entries, int dim, const int32_t* __restrict__ nptr,
+                                                     const double* __restrict__ rbuf, double b0,
+                                                     double* __restrict__ n1, double* __restrict__ rhs) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_entries) return;
+  const int n = (int)(t / dim), a = (int)(t % dim);
+  double v = 0.0;
+  int k = nptr[n];
+  const int e = nptr[n + 1];
+  for (; k + 4 <= e; k += 4) {          // four independent loads in flight per lane
+    const double v0 = rbuf[(size_t)k * dim + a], v1 = rbuf[(size_t)(k + 1) * dim + a];
+    const double v2 = rbuf[(size_t)(k + 2) * dim + a], v3 = rbuf[(size_t)(k + 3) * dim + a];
+    v += v0;
+    v += v1;
+    v += v2;
+    v += v3;
+  }
+  for (; k < e; ++k) v += rbuf[(size_t)k * dim + a];
+  n1[t] += v;
+  if (rhs) rhs[t] -= b0 * v;
+}
+
+void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
+                            const double p[4], bool mean) {
+  NSFEM_REQUIRE(law == 1 || law == 2, "variable viscosity: no law set");
+  if (m.dim == 3) return viscosity_cells_3d(s, m, u, weight, law, p, mean);
+  const dim3 grid(grid_for(m.n_cells)), block(kBlock);
+#define NSFEM_VV(L, M) \
+  hipLaunchKernelGGL((k_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], p[2], \
+                     m.ndst.p, m.rbuf.p)
+  if (law == 1) { if (mean) NSFEM_VV(1, true); else NSFEM_VV(1, false); }
+  else { if (mean) NSFEM_VV(2, true); else NSFEM_VV(2, false); }
+#undef NSFEM_VV
+  NSFEM_HIP(hipGetLastError());
+}
+
+void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double* n1, double* rhs) {
+  const int64_t n = (int64_t)m.n_p2 * m.dim;
+  hipLaunchKernelGGL(k_visc_gather, dim3(grid_for(n)), dim3(kBlock), 0, s, n, m.dim, m.nptr.p, m.rbuf.p, b0, n1, rhs);
+  NSFEM_HIP(hipGetLastError());
+}
+
 
 // ---------------------------------------------------------------- IMEX right-hand side
 // rhs = -(t + (b0 n1 + b1 n2)): the last operation of the right-hand side of nsfem_step_imex, shared by the generic

@@ -654,6 +654,88 @@ void convection_action_3d(hipStream_t s, const MeshDev& m, const double* u, cons
   NSFEM_HIP(hipGetLastError());
 }
 
+// ---- variable viscosity on tetrahedra (the 2D kernel is k_visc_var_cell, assembly.hip; the law is visc_law_nu,
+// cell_geometry.hpp), one thread per cell, 15-point rule:
+//   r_(i,a) = wgt sum_q w_q |det J| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i,   g_ab = d_b u_a,
+//   gamma = sqrt(1/2 sum_ab (g_ab + g_ba)^2),   Delta_K = (|det J| / 6)^(1/3)
+// Element vector node-sorted into m.rbuf; the caller sums the node runs (k_visc_gather).
+// MEAN: rbuf[c] = sum_q w_q nu_x(gamma_q) / sum_q w_q instead.
+template <int LAW, bool MEAN>
+__global__ __launch_bounds__(256) void k3_visc_var_cell(int nc, const double* __restrict__ vx,
+                                                        const int32_t* __restrict__ p2,
+                                                        const double* __restrict__ u, double wgt, double p0, double p1,
+                                                        double pp2, const int32_t* __restrict__ ndst,
+                                                        double* __restrict__ rbuf) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo3 g = load_geo3(vx, nc, c);
+  const double delta = cbrt(g.adet / 6.0);
+  const double delta2 = delta * delta;
+  double un[10][3];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const size_t node = (size_t)p2[(size_t)k * nc + c];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
+  }
+  double r[MEAN ? 1 : 10][3];
+#pragma unroll
+  for (int i = 0; i < (MEAN ? 1 : 10); ++i) r[i][0] = r[i][1] = r[i][2] = 0.0;
+  double mean = 0.0, wsum = 0.0;
+  for (int q = 0; q < 15; ++q) {
+    double gk[10][3];
+    double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};     // G[a][b] = d_b u_a
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      phys3(g, c_q3.dphi2[q][k], gk[k]);
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) G[a][b] += gk[k][b] * un[k][a];
+    }
+    // g + g^T (6 entries) and gamma^2 = 1/2 sum_ab (g_ab + g_ba)^2
+    const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
+    const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
+    const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
+    const double nu = visc_law_nu<LAW>(gamma, delta2, p0, p1, pp2);
+    if constexpr (MEAN) {
+      mean += c_q3.w[q] * nu;
+      wsum += c_q3.w[q];
+    } else {
+      const double w = c_q3.w[q] * g.adet * wgt * nu;
+#pragma unroll
+      for (int i = 0; i < 10; ++i) {
+        r[i][0] += w * (s00 * gk[i][0] + s01 * gk[i][1] + s02 * gk[i][2]);
+        r[i][1] += w * (s01 * gk[i][0] + s11 * gk[i][1] + s12 * gk[i][2]);
+        r[i][2] += w * (s02 * gk[i][0] + s12 * gk[i][1] + s22 * gk[i][2]);
+      }
+    }
+  }
+  if constexpr (MEAN) {
+    rbuf[c] = mean / wsum;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      double* out = rbuf + (size_t)ndst[(size_t)i * nc + c] * 3;
+      out[0] = r[i][0];
+      out[1] = r[i][1];
+      out[2] = r[i][2];
+    }
+  }
+}
+
+void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, int law, const double p[4],
+                        bool mean) {
+  const dim3 grid(grid3(m.n_cells)), block(kBlock);
+#define NSFEM_VV3(L, M) \
+  hipLaunchKernelGGL((k3_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], \
+                     p[2], m.ndst.p, m.rbuf.p)
+  if (law == 1) { if (mean) NSFEM_VV3(1, true); else NSFEM_VV3(1, false); }
+  else { if (mean) NSFEM_VV3(2, true); else NSFEM_VV3(2, false); }
+#undef NSFEM_VV3
+  NSFEM_HIP(hipGetLastError());
+}
+
 // ---- scalar transport on tetrahedra (the 2D kernel is k_scalar_conv_cell, assembly.hip): convection of a P2 scalar T
 // by the P2 velocity u, one thread per cell, 15-point rule.  FORM 0: r_i = wgt int (u . grad T) phi_i; FORM 1:
 // r_i = wgt/2 int [(u . grad T) phi_i - (u . grad phi_i) T].  Element vector node-sorted into the first 10 n_cells

@@ -78,4 +78,18 @@ __device__ __forceinline__ void phys3(const CellGeo3& g, const double* dr, doubl
   for (int a = 0; a < 3; ++a) out[a] = g.ji[0][a] * dr[0] + g.ji[1][a] * dr[1] + g.ji[2][a] * dr[2];
 }
 
+// Variable-viscosity laws (nsfem_set_viscosity_law): the ONE copy of nu_x(gamma, Delta_K) the element kernels of both
+// dimensions and their cell-mean variants inline.  gamma = sqrt(2 S:S) >= 0, delta2 = Delta_K^2, p = params[0..2].
+//   LAW 1 Smagorinsky  (C_s Delta_K)^2 gamma                          p0 = C_s
+//   LAW 2 Carreau      a [ (1 + (lambda gamma)^2)^((n - 1)/2) - 1 ]   p0 = a, p1 = lambda, p2 = n
+template <int LAW>
+__device__ __forceinline__ double visc_law_nu(double gamma, double delta2, double p0, double p1, double p2) {
+  if constexpr (LAW == 1) {
+    return (p0 * p0 * delta2) * gamma;
+  } else {
+    const double lg = p1 * gamma;
+    return p0 * (pow(1.0 + lg * lg, 0.5 * (p2 - 1.0)) - 1.0);
+  }
+}
+
 }  // namespace nsfem

@@ -450,6 +450,15 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
                               int form, double* out);
 void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
                                 int form);
+// variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, p = params): the element kernel
+// k_visc_var_cell / k3_visc_var_cell on the velocity u, element vectors weight * V_K(u) node-sorted into m.rbuf --
+// mean: the cell means of nu_x into the first n_cells doubles of m.rbuf instead
+void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
+                            const double p[4], bool mean);
+void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, int law, const double p[4],
+                        bool mean);
+// k_visc_gather: v = per-node sums of m.rbuf in ascending cell order; n1 += v, rhs -= b0 v (rhs may be null)
+void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double* n1, double* rhs);
 // out[n dim + c] = f[n dim + c] + T[n] b[c] on the P2 nodes (f null: out = T b)
 void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, const double* T, const double b[3],
                            double* out);
@@ -968,6 +977,15 @@ struct nsfem_ctx {
   int imex_lattice_agreed = -1;                        // the ranks' common answer to "one-launch right-hand side?" (-1: not asked)
   int conv_n_form = -1;                                // convective form and coefficient the stored vectors belong to
   double conv_n_cc = 0.0;
+  // variable viscosity (nsfem_set_viscosity_law): law 0 none, 1 Smagorinsky, 2 Carreau.  With a law the stored
+  // vectors N1, N2 are c_c conv(u) + V(u); `epoch` counts the changes of law or parameters, conv_n_visc is the epoch
+  // the stored vectors belong to
+  struct Viscosity {
+    int law = 0;
+    double p[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t epoch = 0, launches = 0, recomputed = 0;
+  } visc;
+  int64_t conv_n_visc = 0;
   // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the
   // non-symmetric V(0, d + 1) the BiCGStab solves use (nsfem_set_bdf switches back)
   bool mg_v_symmetric = false;

@@ -19,7 +19,10 @@ N(u2) is not recomputed: the device keeps N(u1) of a step for the next one.  On 
 with exact stencil dictionaries the whole right-hand side of step 1 is one kernel launch.
 
 The scheme is conditionally stable (a CFL-type restriction on k, reported by the problem classes'
-CFL diagnostic).  Rotating frames (Coriolis / Euler terms) are refused with an error by the device
+CFL diagnostic).  A strain-rate dependent viscosity (``set_viscosity_model``, ``viscosity_models``) keeps
+all of this: c_v K stays in the matrix and the remainder V(u) joins the extrapolated vector,
+N(u) = c_c conv(u) + V(u); that treatment is unconditionally stable only while |nu_x| stays a fraction
+of c_v, otherwise k is bounded by about Delta^2 / nu_x.  Rotating frames (Coriolis / Euler terms) are refused with an error by the device
 driver; 3D meshes run through the generic right-hand-side path.
 
 Partitioned meshes (a context with a communicator, ``partition.py``'s ``attach``): the step runs on
@@ -49,6 +52,30 @@ class IMEXIPCSSolver(InstationarySolverBase):
                          max_iter, device=device)
         self.last_step_info = None
 
+    def set_viscosity_model(self, model):
+        """a model of ``viscosity_models`` (``SmagorinskyModel``, ``CarreauModel``) or None for the constant
+        viscosity.  Its parameters are formed from the equation coefficients, so it is pushed to the device again
+        whenever they change; partitioned meshes are refused by the device driver."""
+        assert model is None or (hasattr(model, "law_id") and hasattr(model, "params"))
+        self._viscosity_model = model
+        self._push_viscosity_model()
+
+    def _push_viscosity_model(self):
+        if not (hasattr(self, "_ctx") and hasattr(self, "_viscosity_model")):
+            return
+        model = self._viscosity_model
+        try:
+            if model is None:
+                self._ctx.set_viscosity_law(0)
+            elif hasattr(self, "_equation_coefficients"):
+                self._ctx.set_viscosity_law(model.law_id, model.params(self._equation_coefficients))
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+
+    def _push_coefficients(self):
+        super()._push_coefficients()
+        self._push_viscosity_model()
+
     def _setup_function_spaces(self):
         if not hasattr(self, "_Wh"):
             super()._setup_function_spaces()
@@ -70,6 +97,7 @@ class IMEXIPCSSolver(InstationarySolverBase):
         if not all(hasattr(self, a) for a in ("_next_step_size", "_alpha", "_beta", "_gamma")):
             self._update_time_stepping_coefficients()
         self._setup_boundary_conditions()
+        self._push_viscosity_model()
         self._diffusion_solver = _DeviceSystem(self, nat.SYS_MOMENTUM)
         self._projection_solver = _DeviceSystem(self, nat.SYS_POISSON)
         self._velocity_correction_solver = _DeviceSystem(self, nat.SYS_CORRECTION)

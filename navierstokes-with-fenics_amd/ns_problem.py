@@ -72,6 +72,10 @@ class ProblemBase:
     _TEMPERATURE_HOOKS = ("set_temperature_coefficients", "set_temperature_boundary_conditions",
                           "set_temperature_source")
 
+    # A problem with a strain-rate dependent viscosity defines ``set_viscosity_model``; it leaves ``_viscosity_model``
+    # (a model of viscosity_models.py) behind, which goes to the solver's set_viscosity_model where it has one
+    _VISCOSITY_HOOK = "set_viscosity_model"
+
     def _call_hooks(self, order):
         """mesh, then the hooks named in ``order``; afterwards the consistency checks of the reference"""
         self.setup_mesh()
@@ -87,6 +91,8 @@ class ProblemBase:
         for hook in self._TEMPERATURE_HOOKS:
             if hasattr(self, hook):
                 getattr(self, hook)()
+        if hasattr(self, self._VISCOSITY_HOOK):
+            getattr(self, self._VISCOSITY_HOOK)()
         if not hasattr(self, "_bcs"):
             assert hasattr(self, "_periodic_bcs")
         if hasattr(self, "_internal_constraints"):
@@ -116,7 +122,10 @@ class ProblemBase:
             self._hand_over_temperature(solver)
 
     def _hand_over_temperature(self, solver):
-        """what the temperature hooks left behind -> solver, where the solver class has the setters"""
+        """what the temperature hooks (and the viscosity hook) left behind -> solver, where the solver class has the
+        setters"""
+        if hasattr(self, "_viscosity_model") and hasattr(solver, "set_viscosity_model"):
+            solver.set_viscosity_model(self._viscosity_model)
         if hasattr(self, "_temperature_coefficients") and hasattr(solver, "set_scalar_coefficients"):
             solver.set_scalar_coefficients(**self._temperature_coefficients)
         if hasattr(self, "_temperature_bcs") and hasattr(solver, "set_scalar_boundary_conditions"):
@@ -329,6 +338,19 @@ class ProblemBase:
         field = HostField(self._mesh, "vorticity", "Cell", curl.mean(axis=1))
         field.vertex_values = curl
         return field
+
+    def _compute_model_viscosity(self):
+        """cell means of the model viscosity nu_x (``set_viscosity_model``) for the current velocity, from the device
+        (nsfem_viscosity_cells): sum_q w_q nu_x(gamma_q) / sum_q w_q per cell.  New helper; valid for
+        ``_add_to_field_output``."""
+        import _native as nat
+        from fem_function import HostField
+        solver = self._get_solver()
+        try:
+            values = solver._ctx.viscosity_cells(nat.U0)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+        return HostField(self._mesh, "model viscosity", "Cell", values)
 
     def _compute_pressure_gradient(self):
         """grad of the P1 pressure: piecewise constant = its DG0 projection (:85-103)."""

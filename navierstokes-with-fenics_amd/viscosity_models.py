@@ -1,0 +1,48 @@
+"""Strain-rate dependent viscosity models of the IMEX pressure-correction step.
+
+The viscosity is  nu = c_v + nu_x(gamma, Delta_K)  with the shear rate gamma = sqrt(2 S:S) of the P2 velocity and the
+filter width Delta_K = |K|^(1/dim) of the cell.  c_v (the solver's ``viscous_term`` coefficient) stays in the
+implicit matrix; the device evaluates the remainder explicitly (``nsfem_set_viscosity_law``, include/nsfem.h).  A model
+exposes ``law_id`` and ``params(coefficients)`` -- the four numbers the device driver takes, formed from the solver's
+equation coefficients where the model needs them -- and goes to ``IMEXIPCSSolver.set_viscosity_model``.
+"""
+import math
+
+LAW_NONE, LAW_SMAGORINSKY, LAW_CARREAU = 0, 1, 2
+
+
+class SmagorinskyModel:
+    """nu_x = (C_s Delta_K)^2 gamma: the Smagorinsky subgrid viscosity with the constant ``cs`` >= 0"""
+    law_id = LAW_SMAGORINSKY
+
+    def __init__(self, cs):
+        cs = float(cs)
+        if not (math.isfinite(cs) and cs >= 0.0):
+            raise ValueError("SmagorinskyModel: cs must be finite and >= 0, got %r" % (cs, ))
+        self.cs = cs
+
+    def params(self, coefficients=None):
+        return (self.cs, 0.0, 0.0, 0.0)
+
+
+class CarreauModel:
+    """nu = nu_inf + (nu_0 - nu_inf) (1 + (lam gamma)^2)^((n - 1)/2): the Carreau law.  nu_0, the zero-shear
+    viscosity, is the solver's ``viscous_term`` coefficient, so nu_x = a [(1 + (lam gamma)^2)^((n - 1)/2) - 1] with
+    a = viscous_term - nu_inf.  ``nu_inf`` finite, ``lam`` >= 0, ``n`` > 0 (n < 1 shear thinning)."""
+    law_id = LAW_CARREAU
+
+    def __init__(self, nu_inf, lam, n):
+        nu_inf, lam, n = float(nu_inf), float(lam), float(n)
+        if not math.isfinite(nu_inf):
+            raise ValueError("CarreauModel: nu_inf must be finite, got %r" % (nu_inf, ))
+        if not (math.isfinite(lam) and lam >= 0.0):
+            raise ValueError("CarreauModel: lam must be finite and >= 0, got %r" % (lam, ))
+        if not (math.isfinite(n) and n > 0.0):
+            raise ValueError("CarreauModel: n must be finite and > 0, got %r" % (n, ))
+        self.nu_inf, self.lam, self.n = nu_inf, lam, n
+
+    def params(self, coefficients):
+        nu0 = coefficients["viscous_term"]
+        if nu0 is None or not math.isfinite(float(nu0)):
+            raise ValueError("CarreauModel: the viscous_term coefficient (zero-shear viscosity) is not set")
+        return (float(nu0) - self.nu_inf, self.lam, self.n, 0.0)
