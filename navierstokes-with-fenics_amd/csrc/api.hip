@@ -773,6 +773,11 @@ static bool coriolis_active(const nsfem_ctx* c) {
   if (c->mesh.dim == 2) return c->omega != 0.0;
   return c->omega3[0] != 0.0 || c->omega3[1] != 0.0 || c->omega3[2] != 0.0;
 }
+// Euler acceleration c_e (d Omega/dt) x x: is an angular acceleration set?
+static bool euler_active(const nsfem_ctx* c) {
+  if (c->mesh.dim == 2) return c->omega_dot != 0.0;
+  return c->omega_dot3[0] != 0.0 || c->omega_dot3[1] != 0.0 || c->omega_dot3[2] != 0.0;
+}
 static double coriolis_gamma(const nsfem_ctx* c) {
   if (!coriolis_active(c)) return 0.0;
   if (!std::isfinite(c->coef[4])) throw Error(NSFEM_ERR_ARG, "angular velocity set but coriolis_term coefficient is None");
@@ -829,9 +834,7 @@ static void momentum_begin_step(nsfem_ctx* c, bool with_old_pressure = true) {
   } else {
     launch_axpby(s, nv, a1, c->state[NSFEM_U1].p, a2, c->state[NSFEM_U2].p, c->tmp_v.p);
   }
-  const bool euler = c->mesh.dim == 2 ? c->omega_dot != 0.0
-                                      : (c->omega_dot3[0] != 0.0 || c->omega_dot3[1] != 0.0 || c->omega_dot3[2] != 0.0);
-  if (euler) {      // Euler acceleration  c_e (d Omega/dt) x x  (ns_solver_base.py:193-211)
+  if (euler_active(c)) {      // Euler acceleration  c_e (d Omega/dt) x x  (ns_solver_base.py:193-211)
     NSFEM_REQUIRE(std::isfinite(c->coef[5]), "angular acceleration set but euler_term coefficient is None");
     if (!c->rot_field.p) {
       c->rot_field.alloc((size_t)nv);
@@ -918,8 +921,7 @@ static void momentum_jacobian(nsfem_ctx* c, int vel_slot = NSFEM_USTAR) {
     launch_convection_jacobian(s, c->mesh, c->p22, c->state[vel_slot].p, cc, c->L.vals.p, E,
                                c->coef[2], c->J.vals.p, c->conv_form, c->picard);
   else
-    if (c->mesh.dim == 3) jacobian_init_3d(s, c->p22.nnz, c->L.vals.p, E, c->coef[2], c->J.vals.p);
-    else launch_jacobian_init(s, c->p22.nnz, c->L.vals.p, E, c->coef[2], c->J.vals.p);
+    launch_jacobian_init(s, c->mesh.dim, c->p22.nnz, c->L.vals.p, E, c->coef[2], c->J.vals.p);
   const double g = coriolis_gamma(c);
   if (g != 0.0) {
     if (c->mesh.dim == 2) {
@@ -1495,9 +1497,50 @@ extern "C" int nsfem_get_rhs(nsfem_ctx* ctx, int system, double* host, int64_t n
   API_END(ctx)
 }
 
-static nsfem_krylov_opts hinted(nsfem_krylov_opts k, const nsfem_ctx::SolveHint& h, bool exact = false);
-static void note_solve(nsfem_ctx::SolveHint& h, const nsfem_solve_info& si, const nsfem_krylov_opts& k, double target);
-static int next_hint(const nsfem_solve_info& si, const nsfem_krylov_opts& k, double target);
+// Every host convergence check of a Krylov solve is a device -> host round trip during which the
+// GPU runs dry.  The same solve of the previous time step is an excellent predictor of the
+// iteration count: the first check is postponed to one iteration before that count.
+// Round 4: a check costs ~15 - 20 us of idle GPU, an iteration too many costs the iteration.  While the count is
+// steady (the last two solves needed exactly the prediction) the first check sits AT the predicted count -- one round
+// trip per solve --, otherwise and at every 8th solve (the probe that notices a falling count) one iteration before
+// it.  exact: the prediction itself (the Chebyshev mass solve runs exactly that many steps before its only check).
+static nsfem_krylov_opts hinted(nsfem_krylov_opts k, const nsfem_ctx::SolveHint& h, bool exact = false) {
+  const bool steady = h.same >= 2 && (h.count & 7) != 7;
+  k.first_check = std::max(k.first_check, (exact || steady) ? h.its : h.its - 1);
+  return k;
+}
+// The predictor for the next solve: the iteration count of this one, reduced when the postponed
+// first check found the residual far below the target (linear-convergence estimate of the count
+// that would have sufficed) -- otherwise a single long solve would keep all later ones long.
+static int next_hint(const nsfem_solve_info& si, const nsfem_krylov_opts& k, double target) {
+  (void)k;
+  if (!si.converged) return 0;                     // a failed solve predicts nothing
+  if (si.iterations <= 1 || !(si.residual > 0.0) || !(si.residual0 > si.residual)) return si.iterations;
+  // (target: the solve's own absolute target max(atol, rtol |b|) -- with a good start vector |r0| << |b|)
+  if (!(si.residual < target) || !(si.residual0 > target)) return si.iterations;
+  const double need = si.iterations * std::log(si.residual0 / target) / std::log(si.residual0 / si.residual);
+  return std::max(1, std::min(si.iterations, (int)std::ceil(need)));
+}
+static void note_solve(nsfem_ctx::SolveHint& h, const nsfem_solve_info& si, const nsfem_krylov_opts& k, double target) {
+  const int next = next_hint(si, k, target);
+  h.same = (si.converged && next == h.its && si.iterations == h.its) ? h.same + 1 : 0;
+  h.its = next;
+  ++h.count;
+}
+// Krylov tolerances of one Newton linear solve.  newton_forcing = 0: the caller's tolerances
+// (a direct solver's accuracy, as the reference's LU).  newton_forcing = eta > 0 (inexact
+// Newton): reduce the linear residual by eta, but never below a tenth of what the nonlinear
+// criterion itself asks for -- the Newton loop still terminates on the reference's criterion,
+// evaluated on the true nonlinear residual.
+static nsfem_krylov_opts forced_opts(const nsfem_step_opts* o, const nsfem_krylov_opts& base, double r0) {
+  nsfem_krylov_opts k = base;
+  if (o->newton_forcing > 0.0) {
+    k.rtol = std::max(k.rtol, o->newton_forcing);
+    k.atol = std::max(k.atol, 0.1 * std::max(o->newton_atol, o->newton_rtol * r0));
+  }
+  return k;
+}
+
 extern "C" int nsfem_solve(nsfem_ctx* ctx, int system, const nsfem_krylov_opts* opts,
                            nsfem_solve_info* info) {
   nsfem_solve_info local;
@@ -2112,74 +2155,48 @@ extern "C" int nsfem_default_step_opts(nsfem_step_opts* o) {
   return NSFEM_OK;
 }
 
-static nsfem_krylov_opts forced_opts(const nsfem_step_opts* o, const nsfem_krylov_opts& base, double r0);
-// Every host convergence check of a Krylov solve is a device -> host round trip during which the
-// GPU runs dry.  The same solve of the previous time step is an excellent predictor of the
-// iteration count: the first check is postponed to one iteration before that count.
-// Round 4: a check costs ~15 - 20 us of idle GPU, an iteration too many costs the iteration.  While the count is
-// steady (the last two solves needed exactly the prediction) the first check sits AT the predicted count -- one round
-// trip per solve --, otherwise and at every 8th solve (the probe that notices a falling count) one iteration before
-// it.  exact: the prediction itself (the Chebyshev mass solve runs exactly that many steps before its only check).
-static nsfem_krylov_opts hinted(nsfem_krylov_opts k, const nsfem_ctx::SolveHint& h, bool exact) {
-  const bool steady = h.same >= 2 && (h.count & 7) != 7;
-  k.first_check = std::max(k.first_check, (exact || steady) ? h.its : h.its - 1);
-  return k;
-}
-static void note_solve(nsfem_ctx::SolveHint& h, const nsfem_solve_info& si, const nsfem_krylov_opts& k, double target) {
-  const int next = next_hint(si, k, target);
-  h.same = (si.converged && next == h.its && si.iterations == h.its) ? h.same + 1 : 0;
-  h.its = next;
-  ++h.count;
-}
-// The predictor for the next solve: the iteration count of this one, reduced when the postponed
-// first check found the residual far below the target (linear-convergence estimate of the count
-// that would have sufficed) -- otherwise a single long solve would keep all later ones long.
-static int next_hint(const nsfem_solve_info& si, const nsfem_krylov_opts& k, double target) {
-  (void)k;
-  if (!si.converged) return 0;                     // a failed solve predicts nothing
-  if (si.iterations <= 1 || !(si.residual > 0.0) || !(si.residual0 > si.residual)) return si.iterations;
-  // (target: the solve's own absolute target max(atol, rtol |b|) -- with a good start vector |r0| << |b|)
-  if (!(si.residual < target) || !(si.residual0 > target)) return si.iterations;
-  const double need = si.iterations * std::log(si.residual0 / target) / std::log(si.residual0 / si.residual);
-  return std::max(1, std::min(si.iterations, (int)std::ceil(need)));
-}
 
-extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
-  nsfem_step_info local;
-  API_BEGIN
+// ---------------------------------------------------------------- parts the step calls share
+// What every step call does first: the checks on its options, the graph epoch (captured Krylov bodies bake in the
+// convective form and the Picard flag) and the cleared record of the step -- the caller's, or `local`
+static nsfem_step_info& step_begin(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info,
+                                   nsfem_step_info& local, bool newton, bool picard) {
   NSFEM_REQUIRE(ctx && opts, "null argument");
   NSFEM_REQUIRE(opts->convective_form >= 0 && opts->convective_form <= 3, "unknown convective form");
-  NSFEM_REQUIRE(opts->newton_max_iter > 0 && opts->newton_max_iter < NSFEM_MAX_NEWTON,
+  NSFEM_REQUIRE(!newton || (opts->newton_max_iter > 0 && opts->newton_max_iter < NSFEM_MAX_NEWTON),
                 "newton_max_iter out of range");
-  NSFEM_REQUIRE(ctx->alpha[0] != 0.0, "the pressure-correction scheme needs alpha0 != 0");
-  NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
-  NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
-  if (ctx->conv_form != opts->convective_form || ctx->picard) ctx->graph_epoch++;
+  if (ctx->conv_form != opts->convective_form || ctx->picard != picard) ctx->graph_epoch++;
   ctx->conv_form = opts->convective_form;
-  ctx->picard = false;
+  ctx->picard = picard;
   nsfem_step_info& inf = info ? *info : local;
   std::memset(&inf, 0, sizeof(inf));
-  // ---- diffusion step: Newton (dolfin NewtonSolver, residual criterion)
-  momentum_begin_step(ctx);
-  double r = momentum_residual(ctx);
+  return inf;
+}
+
+// Newton iteration of the diffusion step and of the monolithic step (dolfin NewtonSolver: residual criterion,
+// relaxation 1).  residual() evaluates the residual at the iterate and returns its norm; solve_update(r, k, si) solves
+// the linearised system with the Krylov options k (r: the norm just evaluated), updates the iterate and returns the
+// solver's status.  `where` names the step in the error messages.
+template <class Residual, class SolveUpdate>
+static void newton_solve(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info& inf, const char* where,
+                         bool allow_nonconvergence, Residual residual, SolveUpdate solve_update) {
+  double r = residual();
   const double r0 = r;
   inf.newton_residuals[0] = r;
   int it = 0;
   bool converged = r < opts->newton_atol;
   ctx->mf_active = use_matrix_free(ctx, opts);
   while (!converged && it < opts->newton_max_iter) {
-    if (!ctx->mf_active) momentum_jacobian(ctx);
     nsfem_solve_info si;
     nsfem_ctx::SolveHint& hint = ctx->hint_mom[std::min(it, 3)];
     const nsfem_krylov_opts ko = forced_opts(opts, opts->momentum, r0);
-    int rc = momentum_solve_update(ctx, hinted(ko, hint), si, r, true);
+    const int rc = solve_update(r, hinted(ko, hint), si);
     note_solve(hint, si, ko, ctx->kw.last_target);
     inf.krylov_iterations_momentum += si.iterations;
-    if (rc == NSFEM_ERR_BREAKDOWN) throw Error(rc, "BiCGStab breakdown in the diffusion step");
-    if (rc == NSFEM_ERR_NOT_CONVERGED)
-      throw Error(rc, "BiCGStab did not converge in the diffusion step");
+    if (rc == NSFEM_ERR_BREAKDOWN) throw Error(rc, std::string("BiCGStab breakdown in the ") + where);
+    if (rc == NSFEM_ERR_NOT_CONVERGED) throw Error(rc, std::string("BiCGStab did not converge in the ") + where);
     ++it;
-    r = momentum_residual(ctx);
+    r = residual();
     inf.newton_residuals[it] = r;
     if (!std::isfinite(r)) throw Error(NSFEM_ERR_BREAKDOWN, "Newton residual is not finite");
     converged = (r / r0 < opts->newton_rtol) || (r < opts->newton_atol);
@@ -2187,38 +2204,59 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   inf.newton_iterations = it;
   inf.converged = converged ? 1 : 0;
   ctx->mf_active = false;
-  if (!converged) throw Error(NSFEM_ERR_NOT_CONVERGED, "Newton solver did not converge");
-  // ---- projection step
-  {
-    nsfem_solve_info si;
-    int rc;
-    // (every rank must take the same branch: the pressure Dirichlet set is judged globally)
-    const bool fd = opts->poisson.precond == 3;
-    NSFEM_REQUIRE(!fd || !ctx->distributed() || !pressure_pinned_anywhere(ctx),
-                  "fast diagonalisation on a partitioned mesh solves the pure Neumann projection step only "
-                  "(pressure Dirichlet nodes are set): use another Poisson preconditioner");
-    // (3D box lattices: the pass-plus-check driver for exact factors; inexact ones assemble and run CG with T^+)
-    const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && ctx->distributed() == ctx->fd3_p.slab()
-                                           : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
-    if (fd && !pressure_pinned_anywhere(ctx) && direct) {
-      rc = poisson_direct_step(ctx, opts->poisson, si);
-    } else {
-      poisson_assemble(ctx, opts->pressure_extrapolation != 0);
-      rc = poisson_solve(ctx, hinted(opts->poisson, ctx->hint_poi), si);
-    }
-    note_solve(ctx->hint_poi, si, opts->poisson, ctx->kw.last_target);
-    inf.krylov_iterations_poisson = si.iterations;
-    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the projection step");
+  ctx->picard = false;
+  if (!converged && !allow_nonconvergence) throw Error(NSFEM_ERR_NOT_CONVERGED, "Newton solver did not converge");
+}
+
+// Projection step of the pressure-correction schemes (nsfem_step_ipcs, nsfem_step_imex)
+static void projection_step(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info& inf) {
+  nsfem_solve_info si;
+  int rc;
+  // (every rank must take the same branch: the pressure Dirichlet set is judged globally)
+  const bool fd = opts->poisson.precond == 3;
+  NSFEM_REQUIRE(!fd || !ctx->distributed() || !pressure_pinned_anywhere(ctx),
+                "fast diagonalisation on a partitioned mesh solves the pure Neumann projection step only "
+                "(pressure Dirichlet nodes are set): use another Poisson preconditioner");
+  // (3D box lattices: the pass-plus-check driver for exact factors; inexact ones assemble and run CG with T^+)
+  const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && ctx->distributed() == ctx->fd3_p.slab()
+                                         : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
+  if (fd && !pressure_pinned_anywhere(ctx) && direct) {
+    rc = poisson_direct_step(ctx, opts->poisson, si);
+  } else {
+    poisson_assemble(ctx, opts->pressure_extrapolation != 0);
+    rc = poisson_solve(ctx, hinted(opts->poisson, ctx->hint_poi), si);
   }
-  // ---- velocity correction step
-  {
-    correction_assemble(ctx, opts->correction.precond == 2);
-    nsfem_solve_info si;
-    int rc = correction_solve(ctx, hinted(opts->correction, ctx->hint_cor, opts->correction.precond == 2), si);
-    note_solve(ctx->hint_cor, si, opts->correction, ctx->kw.last_target);
-    inf.krylov_iterations_correction = si.iterations;
-    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the velocity correction step");
-  }
+  note_solve(ctx->hint_poi, si, opts->poisson, ctx->kw.last_target);
+  inf.krylov_iterations_poisson = si.iterations;
+  if (rc != NSFEM_OK) throw Error(rc, "CG failed in the projection step");
+}
+
+// Velocity correction step of the pressure-correction schemes
+static void correction_step(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info& inf) {
+  correction_assemble(ctx, opts->correction.precond == 2);
+  nsfem_solve_info si;
+  int rc = correction_solve(ctx, hinted(opts->correction, ctx->hint_cor, opts->correction.precond == 2), si);
+  note_solve(ctx->hint_cor, si, opts->correction, ctx->kw.last_target);
+  inf.krylov_iterations_correction = si.iterations;
+  if (rc != NSFEM_OK) throw Error(rc, "CG failed in the velocity correction step");
+}
+
+extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
+  nsfem_step_info local;
+  API_BEGIN
+  nsfem_step_info& inf = step_begin(ctx, opts, info, local, true, false);
+  NSFEM_REQUIRE(ctx->alpha[0] != 0.0, "the pressure-correction scheme needs alpha0 != 0");
+  NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
+  NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
+  // ---- diffusion step: Newton
+  momentum_begin_step(ctx);
+  newton_solve(ctx, opts, inf, "diffusion step", false, [&] { return momentum_residual(ctx); },
+               [&](double r, const nsfem_krylov_opts& k, nsfem_solve_info& si) {
+                 if (!ctx->mf_active) momentum_jacobian(ctx);
+                 return momentum_solve_update(ctx, k, si, r, true);
+               });
+  projection_step(ctx, opts, inf);
+  correction_step(ctx, opts, inf);
   ctx->assembled_system = -1;
   API_END(ctx)
 }
@@ -2407,25 +2445,17 @@ static void imex_require_supported(nsfem_ctx* c) {
   NSFEM_REQUIRE(c->imex_active, "nsfem_set_imex has not been called");
   NSFEM_REQUIRE(c->visc.law == 0 || !c->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
-  const bool euler = c->mesh.dim == 2 ? c->omega_dot != 0.0
-                                      : (c->omega_dot3[0] != 0.0 || c->omega_dot3[1] != 0.0 || c->omega_dot3[2] != 0.0);
-  NSFEM_REQUIRE(!coriolis_active(c) && !euler,
+  NSFEM_REQUIRE(!coriolis_active(c) && !euler_active(c),
                 "IMEX pressure correction: rotating frames (Coriolis / Euler terms) are not supported");
 }
 
 extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
   nsfem_step_info local;
   API_BEGIN
-  NSFEM_REQUIRE(ctx && opts, "null argument");
-  NSFEM_REQUIRE(opts->convective_form >= 0 && opts->convective_form <= 3, "unknown convective form");
+  nsfem_step_info& inf = step_begin(ctx, opts, info, local, false, false);
   NSFEM_REQUIRE(opts->momentum.precond == 0 || opts->momentum.precond == 1,
                 "IMEX diffusion step: momentum.precond must be 0 (Jacobi) or 1 (multigrid)");
   imex_require_supported(ctx);
-  if (ctx->conv_form != opts->convective_form || ctx->picard) ctx->graph_epoch++;
-  ctx->conv_form = opts->convective_form;
-  ctx->picard = false;
-  nsfem_step_info& inf = info ? *info : local;
-  std::memset(&inf, 0, sizeof(inf));
   hipStream_t s = ctx->stream;
   const int64_t nv = nvel(ctx);
   const double cc = cc_of(ctx);
@@ -2472,8 +2502,7 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     LinOp op;
     if (ctx->traction_form) {       // block matrix  (alpha0/k M + gamma0 c_v K) I + gamma0 c_v E
       const double cvE = ctx->imex_gamma[0] * ctx->coef[2];
-      if (ctx->mesh.dim == 3) jacobian_init_3d(s, ctx->p22.nnz, ctx->L.vals.p, ctx->E.vals.p, cvE, ctx->J.vals.p);
-      else launch_jacobian_init(s, ctx->p22.nnz, ctx->L.vals.p, ctx->E.vals.p, cvE, ctx->J.vals.p);
+      launch_jacobian_init(s, ctx->mesh.dim, ctx->p22.nnz, ctx->L.vals.p, ctx->E.vals.p, cvE, ctx->J.vals.p);
       op.A = &ctx->J;
       op.nv = 1;
     } else {
@@ -2502,32 +2531,8 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     inf.newton_iterations = 0;
     inf.converged = 1;
   }
-  // ---- projection step (as nsfem_step_ipcs)
-  {
-    nsfem_solve_info si;
-    int rc;
-    const bool fd = opts->poisson.precond == 3;
-    const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && ctx->distributed() == ctx->fd3_p.slab()
-                                           : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
-    if (fd && !pressure_pinned_anywhere(ctx) && direct) {
-      rc = poisson_direct_step(ctx, opts->poisson, si);
-    } else {
-      poisson_assemble(ctx, opts->pressure_extrapolation != 0);
-      rc = poisson_solve(ctx, hinted(opts->poisson, ctx->hint_poi), si);
-    }
-    note_solve(ctx->hint_poi, si, opts->poisson, ctx->kw.last_target);
-    inf.krylov_iterations_poisson = si.iterations;
-    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the projection step");
-  }
-  // ---- velocity correction step (as nsfem_step_ipcs)
-  {
-    correction_assemble(ctx, opts->correction.precond == 2);
-    nsfem_solve_info si;
-    int rc = correction_solve(ctx, hinted(opts->correction, ctx->hint_cor, opts->correction.precond == 2), si);
-    note_solve(ctx->hint_cor, si, opts->correction, ctx->kw.last_target);
-    inf.krylov_iterations_correction = si.iterations;
-    if (rc != NSFEM_OK) throw Error(rc, "CG failed in the velocity correction step");
-  }
+  projection_step(ctx, opts, inf);
+  correction_step(ctx, opts, inf);
   ctx->assembled_system = -1;
   API_END(ctx)
 }
@@ -2822,20 +2827,6 @@ extern "C" int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_END(ctx)
 }
 
-// Krylov tolerances of one Newton linear solve.  newton_forcing = 0: the caller's tolerances
-// (a direct solver's accuracy, as the reference's LU).  newton_forcing = eta > 0 (inexact
-// Newton): reduce the linear residual by eta, but never below a tenth of what the nonlinear
-// criterion itself asks for -- the Newton loop still terminates on the reference's criterion,
-// evaluated on the true nonlinear residual.
-static nsfem_krylov_opts forced_opts(const nsfem_step_opts* o, const nsfem_krylov_opts& base, double r0) {
-  nsfem_krylov_opts k = base;
-  if (o->newton_forcing > 0.0) {
-    k.rtol = std::max(k.rtol, o->newton_forcing);
-    k.atol = std::max(k.atol, 0.1 * std::max(o->newton_atol, o->newton_rtol * r0));
-  }
-  return k;
-}
-
 // ---------------------------------------------------------------- monolithic BDF
 // mixed operator  [[J, -c_p D^T], [-c_p D, 0]]  with identity rows on Dirichlet dofs
 void nsfem_ctx::MixedOp::apply(hipStream_t s, const double* x, double* y) {
@@ -2895,20 +2886,13 @@ static double bdf_residual(nsfem_ctx* c) {
 extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
   nsfem_step_info local;
   API_BEGIN
-  NSFEM_REQUIRE(ctx && opts, "null argument");
+  nsfem_step_info& inf = step_begin(ctx, opts, info, local, true, opts && opts->picard != 0);
   NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
-  NSFEM_REQUIRE(opts->convective_form >= 0 && opts->convective_form <= 3, "unknown convective form");
-  NSFEM_REQUIRE(opts->newton_max_iter > 0 && opts->newton_max_iter < NSFEM_MAX_NEWTON,
-                "newton_max_iter out of range");
-  if (ctx->conv_form != opts->convective_form || ctx->picard != (opts->picard != 0)) ctx->graph_epoch++;
-  ctx->conv_form = opts->convective_form;
   NSFEM_REQUIRE(!ctx->distributed() || ctx->schur_singular < 0 || ctx->schur_additive,
                 "partitioned meshes take the algebraic Schur Laplacian as additive rank parts "
                 "(nsfem_mg_set_schur_mode)");
   NSFEM_REQUIRE(ctx->mg_built, "the monolithic step needs the multigrid hierarchy "
                                "(block preconditioner): call nsfem_mg_finalize");
-  nsfem_step_info& inf = info ? *info : local;
-  std::memset(&inf, 0, sizeof(inf));
   hipStream_t s = ctx->stream;
   const int64_t nv = nvel(ctx), np = npre(ctx);
   if (!ctx->rhs_m.p) {
@@ -2918,57 +2902,42 @@ extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem
   ctx->mixed_op.c = ctx;
   ctx->mixed_op.n = nv + np;
   ctx->block_prec.c = ctx;
-  ctx->picard = opts->picard != 0;
-  ensure_div_dicts(ctx);
-  momentum_begin_step(ctx, false);
-  double r = bdf_residual(ctx);
-  const double r0 = r;
-  inf.newton_residuals[0] = r;
-  int it = 0;
-  bool converged = r < opts->newton_atol;
-  ctx->mf_active = use_matrix_free(ctx, opts);
   ctx->mom_mf.c = ctx;
   ctx->mom_mf.n = nv;
   ctx->mom_mf.vel_slot = NSFEM_U0;
-  while (!converged && it < opts->newton_max_iter) {
-    if (!ctx->mf_active) momentum_jacobian(ctx, NSFEM_U0);
-    mg_refresh(ctx, true);
-    mg_refresh_schur(ctx);
-    LinOp op;
-    op.custom = &ctx->mixed_op;
-    op.prec = &ctx->block_prec;
-    if (ctx->distributed()) op.comm = ctx->comm;        // all-reduce of the partial dot products
-    op.graph_epoch = ctx->graph_epoch;
-    nsfem_solve_info si;
-    nsfem_ctx::SolveHint& hint = ctx->hint_mom[std::min(it, 3)];
-    const nsfem_krylov_opts ko = forced_opts(opts, opts->momentum, r0);
-    op.x_zero = true;               // (dx_m is not read: the first update of the solve writes it)
-    op.known_bnorm = r;             // |rhs_m| = the Newton residual norm just evaluated (bdf_residual)
-    op.b_scratch = true;            // (bdf_residual below rewrites rhs_m before anything reads it)
-    int rc = bicgstab(s, ctx->kw, op, ctx->rhs_m.p, ctx->dx_m.p, hinted(ko, hint), si);
-    note_solve(hint, si, ko, ctx->kw.last_target);
-    inf.krylov_iterations_momentum += si.iterations;
-    if (rc == NSFEM_ERR_BREAKDOWN) throw Error(rc, "BiCGStab breakdown in the monolithic step");
-    if (rc == NSFEM_ERR_NOT_CONVERGED)
-      throw Error(rc, "BiCGStab did not converge in the monolithic step");
-    double* u = ctx->state[NSFEM_U0].p;
-    double* p = ctx->state[NSFEM_P].p;
-    launch_axpby(s, nv, 1.0, u, -1.0, ctx->dx_m.p, u);
-    launch_axpby(s, np, 1.0, p, -1.0, ctx->dx_m.p + nv, p);
-    ++it;
-    r = bdf_residual(ctx);
-    inf.newton_residuals[it] = r;
-    if (!std::isfinite(r)) throw Error(NSFEM_ERR_BREAKDOWN, "Newton residual is not finite");
-    converged = (r / r0 < opts->newton_rtol) || (r < opts->newton_atol);
-  }
-  inf.newton_iterations = it;
-  inf.converged = converged ? 1 : 0;
-  ctx->mf_active = false;
-  ctx->picard = false;
-  if (!converged && !opts->allow_nonconvergence)
-    throw Error(NSFEM_ERR_NOT_CONVERGED, "Newton solver did not converge");
+  ensure_div_dicts(ctx);
+  momentum_begin_step(ctx, false);
+  newton_solve(ctx, opts, inf, "monolithic step", opts->allow_nonconvergence != 0, [&] { return bdf_residual(ctx); },
+               [&](double r, const nsfem_krylov_opts& k, nsfem_solve_info& si) {
+                 if (!ctx->mf_active) momentum_jacobian(ctx, NSFEM_U0);
+                 mg_refresh(ctx, true);
+                 mg_refresh_schur(ctx);
+                 LinOp op;
+                 op.custom = &ctx->mixed_op;
+                 op.prec = &ctx->block_prec;
+                 if (ctx->distributed()) op.comm = ctx->comm;        // all-reduce of the partial dot products
+                 op.graph_epoch = ctx->graph_epoch;
+                 op.x_zero = true;               // (dx_m is not read: the first update of the solve writes it)
+                 op.known_bnorm = r;             // |rhs_m| = the Newton residual norm just evaluated (bdf_residual)
+                 op.b_scratch = true;            // (bdf_residual rewrites rhs_m before anything reads it)
+                 const int rc = bicgstab(s, ctx->kw, op, ctx->rhs_m.p, ctx->dx_m.p, k, si);
+                 if (rc != NSFEM_OK) return rc;  // (a failed solve leaves the iterate: the caller may resume from it)
+                 double* u = ctx->state[NSFEM_U0].p;
+                 double* p = ctx->state[NSFEM_P].p;
+                 launch_axpby(s, nv, 1.0, u, -1.0, ctx->dx_m.p, u);
+                 launch_axpby(s, np, 1.0, p, -1.0, ctx->dx_m.p + nv, p);
+                 return rc;
+               });
   ctx->assembled_system = -1;
   API_END(ctx)
+}
+
+// the explicit vector a step stored (slot `one`) becomes the next step's old one (slot `two`); without a fresh vector
+// the old one is no longer that of the level before
+static void rotate_stored_vector(nsfem_ctx* ctx, int one, int two, bool& fresh1, bool& valid2) {
+  if (fresh1) std::swap(ctx->state[two].p, ctx->state[one].p);
+  valid2 = fresh1;
+  fresh1 = false;
 }
 
 extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
@@ -2982,25 +2951,13 @@ extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
   // (partitioned IMEX steps: the ghost entries travel with the rotation; those of u0 are copies to round-off only)
   ctx->u2_ghost_fresh = ctx->u1_ghost_fresh;
   ctx->u1_ghost_fresh = false;
-  if (scheme == 0) {
-    // (p_(n-1) is kept for the optional extrapolated start vector of the projection step)
-    std::swap(ctx->state[NSFEM_P2_OLD].p, ctx->state[NSFEM_P_OLD].p);
-    NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_P_OLD].p, ctx->state[NSFEM_P].p,
-                             sizeof(double) * npre(ctx), hipMemcpyDeviceToDevice, s));
-    if (ctx->pressure_history < 2) ctx->pressure_history++;
-  } else {
-    std::swap(ctx->state[NSFEM_P2_OLD].p, ctx->state[NSFEM_P_OLD].p);
-    NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_P_OLD].p, ctx->state[NSFEM_P].p,
-                             sizeof(double) * npre(ctx), hipMemcpyDeviceToDevice, s));
-  }
+  // (p_(n-1) is kept for the optional extrapolated start vector of the projection step)
+  std::swap(ctx->state[NSFEM_P2_OLD].p, ctx->state[NSFEM_P_OLD].p);
+  NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_P_OLD].p, ctx->state[NSFEM_P].p,
+                           sizeof(double) * npre(ctx), hipMemcpyDeviceToDevice, s));
+  if (scheme == 0 && ctx->pressure_history < 2) ctx->pressure_history++;
   // IMEX: c_c N(u1) of the step becomes c_c N(u2) of the next one
-  if (ctx->conv_n1_fresh) {
-    std::swap(ctx->state[NSFEM_CONV_N2].p, ctx->state[NSFEM_CONV_N1].p);
-    ctx->conv_n2_valid = true;
-    ctx->conv_n1_fresh = false;
-  } else {
-    ctx->conv_n2_valid = false;
-  }
+  rotate_stored_vector(ctx, NSFEM_CONV_N1, NSFEM_CONV_N2, ctx->conv_n1_fresh, ctx->conv_n2_valid);
   // scalar transport: T2 <- T1 (pointer swap), T1 <- T0 (copy), and the stored convection as above
   if (scheme == 0 && ctx->sc.configured) {
     nsfem_ctx::Scalar& sc = ctx->sc;
@@ -3008,14 +2965,8 @@ extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
     std::swap(ctx->state[NSFEM_T2].p, ctx->state[NSFEM_T1].p);
     NSFEM_HIP(hipMemcpyAsync(ctx->state[NSFEM_T1].p, ctx->state[NSFEM_T0].p, sizeof(double) * ctx->mesh.n_p2,
                              hipMemcpyDeviceToDevice, s));
-    if (sc.conv1_fresh) {
-      std::swap(ctx->state[NSFEM_TCONV_2].p, ctx->state[NSFEM_TCONV_1].p);
-      sc.conv2_weight = sc.conv1_weight;
-      sc.conv2_valid = true;
-      sc.conv1_fresh = false;
-    } else {
-      sc.conv2_valid = false;
-    }
+    sc.conv2_weight = sc.conv1_weight;
+    rotate_stored_vector(ctx, NSFEM_TCONV_1, NSFEM_TCONV_2, sc.conv1_fresh, sc.conv2_valid);
   }
   // (no synchronisation: everything that reads the state is ordered on the context's stream, nsfem_get_state and
   // nsfem_synchronize wait for it -- a host wait here left the GPU idle ~20 us in every time step)

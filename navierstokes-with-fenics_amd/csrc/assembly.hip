@@ -681,8 +681,9 @@ void launch_assemble_viscous_extra(hipStream_t s, const MeshDev& m, const Patter
   gather_vals(s, p22, 4, tmp.p, extra);
   NSFEM_HIP(hipStreamSynchronize(s));
 }
-void launch_jacobian_init(hipStream_t s, int nnz, const double* L, const double* E, double cvE,
+void launch_jacobian_init(hipStream_t s, int dim, int nnz, const double* L, const double* E, double cvE,
                           double* J) {
+  if (dim == 3) return jacobian_init_3d(s, nnz, L, E, cvE, J);
   int grid = grid_for(nnz);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(k_jac_init, dim3(grid), dim3(kBlock), 0, s, nnz, L, E, cvE, J);

@@ -389,7 +389,7 @@ void launch_assemble_div_grad(hipStream_t s, const MeshDev& m, const Pattern& p1
 void launch_assemble_viscous_extra(hipStream_t s, const MeshDev& m, const Pattern& p22,
                                    double* extra);
 // J(2x2 blocks) = L (scalar) (x) I_2 [+ cv_extra * E]  then  += cc * conv'(u)
-void launch_jacobian_init(hipStream_t s, int nnz, const double* L, const double* E,
+void launch_jacobian_init(hipStream_t s, int dim, int nnz, const double* L, const double* E,
                           double cvE, double* J);
 // J = L (x) I_2 + cvE * E + cc * conv'(u): element blocks are stored, then gathered per slot
 void launch_convection_jacobian(hipStream_t s, const MeshDev& m, const Pattern& p22,

@@ -413,3 +413,40 @@ def test_pressure_dirichlet_nodes_on_slabs_are_refused():
         c.close()
     nat.local_group_destroy(group)
     assert all(out[r] is not None and "pure Neumann projection step only" in out[r] for r in range(size)), out
+
+
+def test_pressure_dirichlet_nodes_on_slabs_are_refused_by_the_imex_step():
+    """the same refusal from step_imex (it shares the projection step with step_ipcs): every rank raises it before the
+    Poisson system is assembled, and the pressure slot keeps its bits"""
+    n, size = (4, 4, 4), 2
+    parts = _parts(False, n, size, coarsest=2)
+    group = nat.local_group_create(size)
+    ctxs = _contexts(parts, group)
+
+    def rank(r):
+        ctx, part = ctxs[r], parts[r]
+        part.attach(ctx)
+        part.attach_fast_diag(ctx)
+        _cavity_start(ctx, part.dofmap)
+        face = np.nonzero((np.abs(part.dofmap.p1_coords[:, 0]) < 1e-12) & part.p1_owned)[0].astype(np.int32)
+        assert face.size > 0
+        ctx.set_dirichlet(nat.PRESSURE, face, np.zeros(face.size))
+        ctx.set_imex((1.0, -1.0, 0.0), (1.0, 0.0), (1.0, 0.0, 0.0), K)
+        ctx.set_state(nat.P, np.sin(part.dofmap.p1_coords @ np.array([1.0, 2.0, 3.0])))
+        before = ctx.get_state(nat.P)
+        try:
+            ctx.step_imex(_opts(ctx, True))
+        except nat.NativeError as exc:
+            return str(exc), before, ctx.get_state(nat.P)
+        return None
+
+    out = _on_ranks(size, rank)
+    for c in ctxs:
+        c.close()
+    nat.local_group_destroy(group)
+    for r in range(size):
+        assert out[r] is not None, r
+        msg, before, after = out[r]
+        assert "pure Neumann projection step only" in msg, (r, msg)
+        assert before.any() and np.array_equal(before.view(np.uint64), after.view(np.uint64)), r
+
