@@ -596,6 +596,51 @@ int nsfem_tracers_advect(nsfem_ctx* ctx, int slot_begin, int slot_end, double dt
 int nsfem_tracers_get(nsfem_ctx* ctx, double* x, int32_t* cells, uint8_t* status);   /* any may be NULL */
 int nsfem_tracers_info(nsfem_ctx* ctx, int64_t out[4]);
 
+/* ---- running flow statistics (csrc/statistics.hip): time averages of the device-resident solution without a copy per
+ * step -- mean velocity, Reynolds stresses <u_i' u_j'>, turbulent kinetic energy, mean and variance of the pressure and
+ * of the transported scalar, the turbulent flux <u' T'>, and their profiles over groups of nodes.  New; a reference
+ * driver would keep numpy sums of get_state copies.
+ *
+ * Per node the context keeps, in fp64 and one array per quantity, the weighted mean m and the weighted central second
+ * moment C of the samples so far (P2 nodes: m_u[dim], C_uu[dim (dim + 1) / 2] in the order xx, xy, yy / xx, xy, xz, yy,
+ * yz, zz, and with NSFEM_STATS_SCALAR m_T, C_TT, C_uT[dim]; P1 nodes with NSFEM_STATS_PRESSURE: m_p, C_pp) and on the
+ * host the accumulated weight W.  nsfem_stats_sample(.., w) is ONE launch (weighted Welford / Chan update):
+ *   d_i = x_i - m_i;   m_i += w / (W + w) d_i;   C_ij += w W / (W + w) d_i d_j   (d taken before the mean moves)
+ * The first sample gives m == x bit for bit and C == 0; a field that never changes keeps C == 0 exactly.  Elementwise,
+ * no atomics: the same samples give the same bytes.  No state slot is written.
+ *
+ * nsfem_stats_enable allocates and zeroes the accumulators for `flags` (NSFEM_STATS_VELOCITY is mandatory, the scalar
+ * needs nsfem_set_scalar); calling it again starts over; flags = 0 frees everything, the groups included.
+ * nsfem_stats_get: one quantity at every node, covariances divided by W; vectors and tensors node-interleaved
+ * (MEAN_U, FLUX_UT: [n_p2][dim]; COV_U: [n_p2][dim (dim + 1) / 2]; TKE = trace(C_uu) / (2 W), MEAN_T, VAR_T: [n_p2];
+ * MEAN_P, VAR_P: [n_p1]); n = the number of doubles.
+ * nsfem_stats_set_groups: groups of nodes of one field (0: P2 nodes, 1: P1 nodes) as a CSR -- nodes and weights of
+ * group g at [group_ptr[g], group_ptr[g + 1]); every group has an entry, every weight is finite and > 0, a node may
+ * appear in any number of groups.  nsfem_stats_profiles reduces the node statistics over each group, with
+ * A = sum_n a_n, to the pooled mean and covariance (within-node plus between-node part)
+ *   m_g = sum_n a_n m_n / A      C_g = sum_n a_n (C_n / W) / A + sum_n a_n (m_n - m_g)(m_n - m_g)^T / A
+ * out [n_groups][n_q], the columns in the order of the accumulators above: P2 n_q = dim + dim (dim + 1) / 2 (m_u, C_uu)
+ * and with the scalar 2 + dim more (m_T, C_TT, C_uT); P1 n_q = 2 (m_p, C_pp).  One workgroup per group, every sum in a
+ * fixed order, no atomics.
+ * nsfem_stats_info: out = {samples, flags, bytes of the accumulators, update launches}; nsfem_stats_weight: W.
+ * NSFEM_ERR_ARG (the accumulators keep their bytes): weight not finite or <= 0, a slot of the wrong kind, the scalar
+ * without nsfem_set_scalar, a quantity that is not enabled, get / profiles before the first sample or with the wrong n,
+ * group lists with an index out of range, contexts on a partitioned mesh (profiles would need a merge across ranks). */
+enum nsfem_stats_flags { NSFEM_STATS_VELOCITY = 1, NSFEM_STATS_PRESSURE = 2, NSFEM_STATS_SCALAR = 4 };
+enum nsfem_stats_quantity {
+  NSFEM_STATS_MEAN_U = 0, NSFEM_STATS_COV_U = 1, NSFEM_STATS_TKE = 2, NSFEM_STATS_MEAN_P = 3, NSFEM_STATS_VAR_P = 4,
+  NSFEM_STATS_MEAN_T = 5, NSFEM_STATS_VAR_T = 6, NSFEM_STATS_FLUX_UT = 7
+};
+int nsfem_stats_enable(nsfem_ctx* ctx, uint32_t flags);
+int nsfem_stats_sample(nsfem_ctx* ctx, int velocity_slot, int pressure_slot /* -1: none */,
+                       int scalar_slot /* -1: none */, double weight);
+int nsfem_stats_get(nsfem_ctx* ctx, int quantity, double* host, int64_t n);
+int nsfem_stats_set_groups(nsfem_ctx* ctx, int field /* 0 P2, 1 P1 */, int32_t n_groups, const int32_t* group_ptr,
+                           const int32_t* nodes, const double* weights);
+int nsfem_stats_profiles(nsfem_ctx* ctx, int field, double* out /* [n_groups][n_q] */, int64_t n);
+int nsfem_stats_info(nsfem_ctx* ctx, int64_t out[4]);
+int nsfem_stats_weight(nsfem_ctx* ctx, double* W);
+
 /* ---- measurement hooks (bench.py): time `reps` launches of the dominant SpMV
  * with HIP events on the context's stream; ms per launch returned ------------- */
 /* in-situ HIP-event timing of the finest-level smoothing launches of the velocity multigrid

@@ -24,6 +24,9 @@ VELOCITY, PRESSURE, PRESSURE_PRECOND, SCALAR = 0, 1, 2, 3
 SYS_MOMENTUM, SYS_POISSON, SYS_CORRECTION, SYS_MONOLITHIC = range(4)
 MAX_NEWTON = 64
 N_FUNCTIONALS = 11          # NSFEM_N_FUNCTIONALS
+STATS_VELOCITY, STATS_PRESSURE, STATS_SCALAR = 1, 2, 4      # nsfem_stats_flags
+(STATS_MEAN_U, STATS_COV_U, STATS_TKE, STATS_MEAN_P, STATS_VAR_P, STATS_MEAN_T, STATS_VAR_T,
+ STATS_FLUX_UT) = range(8)                                  # nsfem_stats_quantity
 
 EXPORTED_SYMBOLS = (
     "nsfem_create", "nsfem_destroy", "nsfem_last_error", "nsfem_version",
@@ -48,6 +51,8 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
     "nsfem_set_point_locator", "nsfem_locate_points", "nsfem_eval_points",
     "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
+    "nsfem_stats_enable", "nsfem_stats_sample", "nsfem_stats_get", "nsfem_stats_set_groups", "nsfem_stats_profiles",
+    "nsfem_stats_info", "nsfem_stats_weight",
 )
 
 
@@ -223,6 +228,13 @@ def load_library(path=None):
         "nsfem_tracers_advect": (C.c_int, [vp, C.c_int, C.c_int, dbl, C.c_int]),
         "nsfem_tracers_get": (C.c_int, [vp, pd, pi, C.POINTER(C.c_uint8)]),
         "nsfem_tracers_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_stats_enable": (C.c_int, [vp, C.c_uint32]),
+        "nsfem_stats_sample": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl]),
+        "nsfem_stats_get": (C.c_int, [vp, C.c_int, pd, i64]),
+        "nsfem_stats_set_groups": (C.c_int, [vp, C.c_int, i32, pi, pi, pd]),
+        "nsfem_stats_profiles": (C.c_int, [vp, C.c_int, pd, i64]),
+        "nsfem_stats_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_stats_weight": (C.c_int, [vp, pd]),
         "nsfem_poisson_solve": (C.c_int, [vp, pd, i64, pi, pd, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_profile_smoother": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
         "nsfem_profile_convection": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
@@ -993,6 +1005,71 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_tracers_info(self._h, out))
         return dict(n=int(out[0]), n_left=int(out[1]), advect_calls=int(out[2]), fallbacks=int(out[3]))
+
+    # -- running flow statistics (csrc/statistics.hip) ----------------------------------
+    def stats_enable(self, flags):
+        """allocate and zero the accumulators for ``flags`` (STATS_VELOCITY [| STATS_PRESSURE] [| STATS_SCALAR]);
+        calling again drops the samples and keeps the groups of ``stats_set_groups``, 0 frees everything"""
+        self._check(self._lib.nsfem_stats_enable(self._h, int(flags)))
+        if int(flags) == 0 or not hasattr(self, "_stats_groups"):
+            self._stats_groups = {}      # field -> number of groups, as the library keeps them
+
+    def stats_sample(self, velocity_slot=U0, pressure_slot=-1, scalar_slot=-1, weight=1.0):
+        """one launch: add the fields of the slots (-1: none) with ``weight`` to the running means and moments"""
+        self._check(self._lib.nsfem_stats_sample(self._h, int(velocity_slot), int(pressure_slot), int(scalar_slot),
+                                                 float(weight)))
+
+    def stats_columns(self, field=0):
+        """columns of a profile row: P2 (field 0) dim + dim (dim + 1) / 2, + 2 + dim with the scalar; P1 (field 1) 2"""
+        if field == 1:
+            return 2
+        dim = self.dim
+        return dim + dim * (dim + 1) // 2 + (2 + dim if self.stats_info()["flags"] & STATS_SCALAR else 0)
+
+    def stats_get(self, quantity):
+        """one quantity at every node (covariances divided by the accumulated weight): MEAN_U, FLUX_UT [n_p2, dim];
+        COV_U [n_p2, dim (dim + 1) / 2] (xx, xy, yy / xx, xy, xz, yy, yz, zz); TKE, MEAN_T, VAR_T [n_p2]; MEAN_P,
+        VAR_P [n_p1]"""
+        dim = self.dim
+        shape = {STATS_MEAN_U: (self.n_p2, dim), STATS_COV_U: (self.n_p2, dim * (dim + 1) // 2),
+                 STATS_TKE: (self.n_p2, ), STATS_MEAN_P: (self.n_p1, ), STATS_VAR_P: (self.n_p1, ),
+                 STATS_MEAN_T: (self.n_p2, ), STATS_VAR_T: (self.n_p2, ), STATS_FLUX_UT: (self.n_p2, dim)}.get(
+                     int(quantity))
+        if shape is None:
+            raise ValueError("unknown statistics quantity %r" % (quantity, ))
+        out = np.empty(shape, dtype=np.float64)
+        self._check(self._lib.nsfem_stats_get(self._h, int(quantity), _dp(out), out.size))
+        return out
+
+    def stats_set_groups(self, field, group_ptr, nodes, weights=None):
+        """groups of nodes of ``field`` (0: P2, 1: P1) as a CSR; ``weights`` None: uniform"""
+        gp = np.ascontiguousarray(group_ptr, dtype=np.int32)
+        nd = np.ascontiguousarray(nodes, dtype=np.int32)
+        w = np.ones(nd.size) if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if gp.ndim != 1 or gp.size < 2 or nd.shape != (int(gp[-1]), ) or w.shape != nd.shape:
+            raise ValueError("group_ptr / nodes / weights do not match")
+        self._check(self._lib.nsfem_stats_set_groups(self._h, int(field), gp.size - 1, _ip(gp), _ip(nd), _dp(w)))
+        self._stats_groups[int(field)] = gp.size - 1
+
+    def stats_profiles(self, field=0):
+        """[n_groups, n_q]: pooled means and covariances (within-node plus between-node part) of every group, columns
+        in the order of the accumulators (m_u, C_uu[, m_T, C_TT, C_uT] / m_p, C_pp)"""
+        n_groups = getattr(self, "_stats_groups", {}).get(int(field), 0)
+        ncol = self.stats_columns(field)
+        out = np.empty((max(n_groups, 1), ncol), dtype=np.float64)      # (no groups yet: the library says so)
+        self._check(self._lib.nsfem_stats_profiles(self._h, int(field), _dp(out), n_groups * ncol))
+        return out
+
+    def stats_info(self):
+        """dict(samples, flags, bytes = size of the accumulators, launches = update launches)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_stats_info(self._h, out))
+        return dict(samples=int(out[0]), flags=int(out[1]), bytes=int(out[2]), launches=int(out[3]))
+
+    def stats_weight(self):
+        out = C.c_double()
+        self._check(self._lib.nsfem_stats_weight(self._h, C.byref(out)))
+        return out.value
 
     def cfl_number(self, slot, step_size):
         out = C.c_double()

@@ -3409,6 +3409,209 @@ extern "C" int nsfem_tracers_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_END(ctx)
 }
 
+// ------------------------------------------------------------------ running flow statistics (statistics.hip)
+// every check of a call comes before its first launch: a refused call leaves the accumulators as they were
+static void stats_require_supported(nsfem_ctx* c) {
+  NSFEM_REQUIRE(!c->distributed(), "flow statistics: partitioned contexts are not supported -- the profiles need a "
+                                   "merge of the group sums across ranks");
+}
+
+static void stats_require_enabled(nsfem_ctx* c) {
+  stats_require_supported(c);
+  NSFEM_REQUIRE(c->stats.flags != 0, "flow statistics: nsfem_stats_enable has not been called");
+}
+
+extern "C" int nsfem_stats_enable(nsfem_ctx* ctx, uint32_t flags) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  stats_require_supported(ctx);
+  nsfem_ctx::Stats& S = ctx->stats;
+  if (flags == 0) {
+    S.acc2.release();
+    S.acc1.release();
+    S.out.release();
+    for (nsfem_ctx::Stats::Groups& g : S.groups) {
+      g.n = -1;
+      g.ptr.release();
+      g.nodes.release();
+      g.weights.release();
+    }
+    S.flags = 0;
+    S.W = 0.0;
+    S.samples = S.launches = 0;
+    return NSFEM_OK;
+  }
+  NSFEM_REQUIRE((flags & ~7u) == 0, "flow statistics: unknown flag");
+  NSFEM_REQUIRE(flags & NSFEM_STATS_VELOCITY, "flow statistics: NSFEM_STATS_VELOCITY is mandatory");
+  const bool scalar = (flags & NSFEM_STATS_SCALAR) != 0;
+  NSFEM_REQUIRE(!scalar || ctx->sc.configured, "flow statistics: scalar requested, but nsfem_set_scalar has not been "
+                                               "called");
+  hipStream_t s = ctx->stream;
+  const size_t stride2 = ((size_t)ctx->mesh.n_p2 + 1) & ~(size_t)1, stride1 = ((size_t)ctx->mesh.n_p1 + 1) & ~(size_t)1;
+  const size_t len2 = (size_t)stats_columns(ctx->mesh.dim, scalar) * stride2;
+  const size_t len1 = flags & NSFEM_STATS_PRESSURE ? 2 * stride1 : 0;
+  if (S.acc2.n != len2) S.acc2.alloc(len2);
+  if (S.acc1.n != len1) S.acc1.alloc(len1);
+  S.acc2.zero(s);
+  S.acc1.zero(s);
+  NSFEM_HIP(hipStreamSynchronize(s));
+  S.stride2 = stride2;
+  S.stride1 = stride1;
+  S.flags = flags;
+  S.W = 0.0;
+  S.samples = S.launches = 0;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_stats_sample(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, int scalar_slot,
+                                  double weight) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  stats_require_enabled(ctx);
+  nsfem_ctx::Stats& S = ctx->stats;
+  NSFEM_REQUIRE(std::isfinite(weight) && weight > 0.0, "flow statistics: the weight of a sample must be finite and > 0");
+  NSFEM_REQUIRE(velocity_slot >= 0 && velocity_slot < NSFEM_N_SLOTS && slot_size(ctx, velocity_slot) == nvel(ctx),
+                "flow statistics: not a velocity slot");
+  const bool pressure = (S.flags & NSFEM_STATS_PRESSURE) != 0, scalar = (S.flags & NSFEM_STATS_SCALAR) != 0;
+  if (pressure)
+    NSFEM_REQUIRE(pressure_slot >= 0 && pressure_slot < NSFEM_N_SLOTS && slot_size(ctx, pressure_slot) == npre(ctx),
+                  "flow statistics: not a pressure slot");
+  else NSFEM_REQUIRE(pressure_slot == -1, "flow statistics: pressure slot given, but NSFEM_STATS_PRESSURE is not enabled");
+  if (scalar) {
+    NSFEM_REQUIRE(ctx->sc.configured, "flow statistics: scalar requested, but nsfem_set_scalar has not been called");
+    NSFEM_REQUIRE(scalar_slot >= 0 && scalar_slot < NSFEM_N_SLOTS && ::scalar_slot(scalar_slot),
+                  "flow statistics: not a scalar slot");
+    ensure_scalar_slot(ctx, scalar_slot);
+  } else {
+    NSFEM_REQUIRE(scalar_slot == -1, "flow statistics: scalar slot given, but NSFEM_STATS_SCALAR is not enabled");
+  }
+  StatsUpdate a;
+  a.n2 = ctx->mesh.n_p2;
+  a.stride2 = S.stride2;
+  a.u = ctx->state[velocity_slot].p;
+  a.T = scalar ? ctx->state[scalar_slot].p : nullptr;
+  a.acc2 = S.acc2.p;
+  if (pressure) {
+    a.n1 = ctx->mesh.n_p1;
+    a.stride1 = S.stride1;
+    a.p = ctx->state[pressure_slot].p;
+    a.acc1 = S.acc1.p;
+  }
+  const double W1 = S.W + weight;
+  a.a = weight / W1;
+  a.b = weight * S.W / W1;
+  a.first = S.W == 0.0;
+  launch_stats_update(ctx->stream, ctx->mesh.dim, scalar, a);
+  S.W = W1;
+  ++S.samples;
+  ++S.launches;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_stats_get(nsfem_ctx* ctx, int quantity, double* host, int64_t n) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && host, "null argument");
+  stats_require_enabled(ctx);
+  nsfem_ctx::Stats& S = ctx->stats;
+  NSFEM_REQUIRE(S.samples > 0, "flow statistics: no sample has been taken");
+  const int dim = ctx->mesh.dim, ncov = dim * (dim + 1) / 2;
+  const bool p1 = quantity == NSFEM_STATS_MEAN_P || quantity == NSFEM_STATS_VAR_P;
+  int col = 0, nc = 1;                      // first column, columns (0: trace of C_uu)
+  bool moment = true;                       // divided by W
+  const int tr[3] = {dim, dim == 2 ? dim + 2 : dim + 3, dim + 5};
+  switch (quantity) {
+    case NSFEM_STATS_MEAN_U: col = 0; nc = dim; moment = false; break;
+    case NSFEM_STATS_COV_U: col = dim; nc = ncov; break;
+    case NSFEM_STATS_TKE: nc = 0; break;
+    case NSFEM_STATS_MEAN_P: col = 0; moment = false; break;
+    case NSFEM_STATS_VAR_P: col = 1; break;
+    case NSFEM_STATS_MEAN_T: col = dim + ncov; moment = false; break;
+    case NSFEM_STATS_VAR_T: col = dim + ncov + 1; break;
+    case NSFEM_STATS_FLUX_UT: col = dim + ncov + 2; nc = dim; break;
+    default: throw Error(NSFEM_ERR_ARG, "flow statistics: unknown quantity");
+  }
+  if (p1) NSFEM_REQUIRE(S.flags & NSFEM_STATS_PRESSURE, "flow statistics: NSFEM_STATS_PRESSURE is not enabled");
+  if (quantity >= NSFEM_STATS_MEAN_T) NSFEM_REQUIRE(S.flags & NSFEM_STATS_SCALAR, "flow statistics: NSFEM_STATS_SCALAR is not enabled");
+  const int64_t nodes = p1 ? ctx->mesh.n_p1 : ctx->mesh.n_p2, len = nodes * (nc ? nc : 1);
+  NSFEM_REQUIRE(n == len, "flow statistics: wrong size of the output");
+  hipStream_t s = ctx->stream;
+  grow(S.out, (size_t)len);
+  const double scale = moment ? (nc ? 1.0 : 0.5) / S.W : 1.0;
+  launch_stats_gather(s, nodes, p1 ? S.acc1.p : S.acc2.p, p1 ? S.stride1 : S.stride2, col, nc, scale, dim, tr, S.out.p);
+  NSFEM_HIP(hipMemcpyAsync(host, S.out.p, sizeof(double) * len, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_stats_set_groups(nsfem_ctx* ctx, int field, int32_t n_groups, const int32_t* group_ptr,
+                                      const int32_t* nodes, const double* weights) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && group_ptr && nodes && weights, "null argument");
+  stats_require_enabled(ctx);
+  NSFEM_REQUIRE(field == 0 || field == 1, "flow statistics: field must be 0 (P2 nodes) or 1 (P1 nodes)");
+  NSFEM_REQUIRE(n_groups >= 1, "flow statistics: n_groups < 1");
+  // the profile kernel indexes the accumulators with these lists: every entry is checked here, before the upload
+  const int32_t n_nodes = field == 0 ? ctx->mesh.n_p2 : ctx->mesh.n_p1;
+  NSFEM_REQUIRE(group_ptr[0] == 0, "flow statistics: group_ptr[0] != 0");
+  for (int32_t g = 0; g < n_groups; ++g)
+    NSFEM_REQUIRE(group_ptr[g + 1] > group_ptr[g], "flow statistics: group_ptr must increase (no empty group)");
+  const int32_t len = group_ptr[n_groups];
+  for (int32_t k = 0; k < len; ++k) {
+    NSFEM_REQUIRE(nodes[k] >= 0 && nodes[k] < n_nodes, "flow statistics: group node index out of range");
+    NSFEM_REQUIRE(std::isfinite(weights[k]) && weights[k] > 0.0, "flow statistics: group weights must be finite and > 0");
+  }
+  nsfem_ctx::Stats::Groups& G = ctx->stats.groups[field];
+  hipStream_t s = ctx->stream;
+  G.n = -1;
+  G.ptr.upload(group_ptr, (size_t)n_groups + 1, s);
+  G.nodes.upload(nodes, (size_t)len, s);
+  G.weights.upload(weights, (size_t)len, s);
+  NSFEM_HIP(hipStreamSynchronize(s));
+  G.n = n_groups;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_stats_profiles(nsfem_ctx* ctx, int field, double* out, int64_t n) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  stats_require_enabled(ctx);
+  nsfem_ctx::Stats& S = ctx->stats;
+  NSFEM_REQUIRE(field == 0 || field == 1, "flow statistics: field must be 0 (P2 nodes) or 1 (P1 nodes)");
+  NSFEM_REQUIRE(field == 0 || (S.flags & NSFEM_STATS_PRESSURE), "flow statistics: NSFEM_STATS_PRESSURE is not enabled");
+  NSFEM_REQUIRE(S.samples > 0, "flow statistics: no sample has been taken");
+  const nsfem_ctx::Stats::Groups& G = S.groups[field];
+  NSFEM_REQUIRE(G.n >= 1, "flow statistics: nsfem_stats_set_groups has not been called for this field");
+  const bool scalar = field == 0 && (S.flags & NSFEM_STATS_SCALAR);
+  const int dim = field == 0 ? ctx->mesh.dim : 1;
+  const int64_t len = (int64_t)G.n * stats_columns(dim, scalar);
+  NSFEM_REQUIRE(n == len, "flow statistics: wrong size of the output");
+  hipStream_t s = ctx->stream;
+  grow(S.out, (size_t)len);
+  launch_stats_profile(s, dim, scalar, field == 0 ? S.acc2.p : S.acc1.p, field == 0 ? S.stride2 : S.stride1, 1.0 / S.W,
+                       G.n, G.ptr.p, G.nodes.p, G.weights.p, S.out.p);
+  NSFEM_HIP(hipMemcpyAsync(out, S.out.p, sizeof(double) * len, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_stats_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  const nsfem_ctx::Stats& S = ctx->stats;
+  out[0] = S.samples;
+  out[1] = S.flags;
+  out[2] = (int64_t)(sizeof(double) * (S.acc2.n + S.acc1.n));
+  out[3] = S.launches;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_stats_weight(nsfem_ctx* ctx, double* W) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && W, "null argument");
+  *W = ctx->stats.W;
+  API_END(ctx)
+}
+
 // ----------------------------------------------------------- operator access
 static const BlockMat* get_op(nsfem_ctx* c, int op, int* nv_apply) {
   *nv_apply = 1;

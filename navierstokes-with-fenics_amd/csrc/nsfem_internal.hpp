@@ -497,6 +497,34 @@ void launch_tracer_init(hipStream_t s, int64_t n, const int32_t* cells, uint8_t*
 void launch_advect_tracers(hipStream_t s, const MeshDev& m, const PointLocatorDev& L, const double* ua,
                            const double* ub, double dt, int n_sub, int64_t n, double* x, int32_t* cells,
                            uint8_t* status, int32_t* counts);
+
+// ---- running flow statistics (statistics.hip).  Accumulators of one field: n_q arrays of `stride` doubles each
+// (stride = the node count rounded up to even: every array starts 16-byte aligned), array q at acc + q * stride, in
+// the column order of nsfem_stats_profiles -- `dim` variables u with SCALAR = false: m_u[dim], C_uu[dim (dim + 1) / 2];
+// SCALAR = true appends m_T, C_TT, C_uT[dim].  The P1 accumulators (m_p, C_pp) are the case dim = 1 without a scalar.
+inline int stats_columns(int dim, bool scalar) { return dim + dim * (dim + 1) / 2 + (scalar ? 2 + dim : 0); }
+struct StatsUpdate {
+  int64_t n2 = 0, n1 = 0;          // P2 / P1 nodes (n1 = 0: no pressure)
+  size_t stride2 = 0, stride1 = 0;
+  const double* u = nullptr;       // [n2][dim]
+  const double* T = nullptr;       // [n2], scalar only
+  const double* p = nullptr;       // [n1]
+  double* acc2 = nullptr;
+  double* acc1 = nullptr;
+  double a = 1.0, b = 0.0;         // w / (W + w), w W / (W + w)
+  int first = 1;                   // W == 0: the means take the sample's bytes
+  int blocks2 = 0;                 // workgroups [0, blocks2) work on the P2 nodes, the rest on the P1 nodes
+};
+// ONE launch: weighted Welford / Chan update of all accumulators
+void launch_stats_update(hipStream_t s, int dim, bool scalar, StatsUpdate a);
+// pooled mean and covariance over groups of nodes (CSR), out [n_groups][stats_columns(dim, scalar)]; dim = 1: P1
+void launch_stats_profile(hipStream_t s, int dim, bool scalar, const double* acc, size_t stride, double inv_w,
+                          int32_t n_groups, const int32_t* group_ptr, const int32_t* nodes, const double* weights,
+                          double* out);
+// out[node * nc + c] = scale * acc[(col + c) * stride + node]; nc = 0: out[node] = scale * sum of the `dim` arrays
+// col_trace[0 .. dim) (turbulent kinetic energy)
+void launch_stats_gather(hipStream_t s, int64_t n, const double* acc, size_t stride, int col, int nc, double scale,
+                         int dim, const int col_trace[3], double* out);
 // diag extraction: d[(i,a)] = 1 / A_ii[a][a]  (mask rows -> 1)
 void launch_inv_diag(hipStream_t s, const BlockMat& A, int nv, const uint8_t* rowmask,
                      double* dinv);
@@ -1150,6 +1178,19 @@ struct nsfem_ctx {
     nsfem::DevBuf<uint8_t> tstatus;             // [n] 0 moving, 1 left
     int64_t advect_calls = 0;
   } pts;
+  // running flow statistics (statistics.hip, nsfem_stats_*): nothing is allocated before nsfem_stats_enable
+  struct Stats {
+    uint32_t flags = 0;                         // 0: not enabled
+    double W = 0.0;                             // accumulated weight, the same for every node
+    int64_t samples = 0, launches = 0;
+    size_t stride2 = 0, stride1 = 0;
+    nsfem::DevBuf<double> acc2, acc1, out;      // P2 / P1 accumulators; grow-only read-out buffer
+    struct Groups {
+      int32_t n = -1;                           // -1: nsfem_stats_set_groups has not been called
+      nsfem::DevBuf<int32_t> ptr, nodes;
+      nsfem::DevBuf<double> weights;
+    } groups[2];
+  } stats;
   int64_t jac_lattice_launches = 0;   // applications of the matrix-free Jacobian through k_jac_lattice
   bool mf_active = false;           // the running step driver applies the Jacobian matrix-free
   int pressure_history = 0;         // IPCS: pressure levels shifted since the state was last set (0..2)

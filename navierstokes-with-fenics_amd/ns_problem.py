@@ -229,6 +229,19 @@ class ProblemBase:
         self.__dict__.setdefault("_point_probes", []).append(probes)
         return probes
 
+    def _add_flow_statistics(self, **kw):
+        """Register running statistics of the solution (``flow_statistics.FlowStatistics``; keywords ``pressure``,
+        ``scalar``, ``start_time``, ``every``): ``solve_problem`` samples the new time level after every
+        ``solver.solve()``, weighted with the step size just taken, once ``next_time >= start_time`` and on every
+        ``every``-th step -- one device launch per sample.  Returns the instance (bound to the solver once it exists).
+        New; the reference has no time averages."""
+        from flow_statistics import FlowStatistics
+        if getattr(self, "_flow_statistics", None):
+            raise ValueError("flow statistics are already registered (the context keeps one set of accumulators)")
+        stats = FlowStatistics(getattr(self, "_navier_stokes_solver", None), **kw)
+        self.__dict__.setdefault("_flow_statistics", []).append(stats)
+        return stats
+
     def _compute_stream_potential(self):
         """Velocity potential phi (the reference's "stream potential", :105-176): P1 solution of
         (grad phi, grad psi) = (div u, psi) - sum over the remaining boundaries of (n . u, psi),
@@ -454,7 +467,8 @@ class InstationaryProblem(ProblemBase):
                 assert hasattr(solver, key), "unknown solver setting %r" % (key,)
                 setattr(solver, key, value)
         self._hand_over_to_solver(solver, ("coefficients", "force", "periodic", "rotation", "bcs", "initial"))
-        for registered in getattr(self, "_tracer_clouds", []) + getattr(self, "_point_probes", []):
+        for registered in getattr(self, "_tracer_clouds", []) + getattr(self, "_point_probes", []) + \
+                getattr(self, "_flow_statistics", []):
             registered.bind(solver)
         self._write_xdmf_file(current_time=0.0)
         print("Solving problem until time = {:0.2f}".format(self._time_stepping.end_time))
@@ -470,11 +484,14 @@ class InstationaryProblem(ProblemBase):
             t_wall = time.perf_counter()
             solver.solve()
             self.step_wall_times.append(time.perf_counter() - t_wall)
-            # registered particles move through the interval just solved (U1 -> U0), probes sample its end
+            # registered particles move through the interval just solved (U1 -> U0), probes and statistics sample
+            # its end
             for cloud in getattr(self, "_tracer_clouds", ()):
                 cloud.advect()
             for probes in getattr(self, "_point_probes", ()):
                 probes.record(ts.next_time)
+            for stats in getattr(self, "_flow_statistics", ()):
+                stats.sample_step(ts.next_time, ts.get_next_step_size())
             if self._postprocessing_frequency > 0 and \
                     ts.step_number % self._postprocessing_frequency == 0:
                 self.postprocess_solution()
