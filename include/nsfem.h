@@ -641,6 +641,58 @@ int nsfem_stats_profiles(nsfem_ctx* ctx, int field, double* out /* [n_groups][n_
 int nsfem_stats_info(nsfem_ctx* ctx, int64_t out[4]);
 int nsfem_stats_weight(nsfem_ctx* ctx, double* W);
 
+/* ---- gradient-derived fields of the current solution (csrc/derived.hip): vorticity, divergence, shear rate,
+ * Q-criterion, velocity gradient, pressure gradient and the gradient of the transported scalar, from ONE element-kernel
+ * launch whatever the mask -- replaces the get_state copy plus numpy einsums of ProblemBase._compute_vorticity /
+ * _compute_pressure_gradient / _cell_gradients (which stay as the host yardstick) and adds what they do not have.
+ *
+ * With G_ab = d_b u_a at a point of a cell (linear on the cell for the P2 velocity):
+ *   NSFEM_DERIVED_VORTICITY          1 (2D) / 3 (3D)  2D: G_10 - G_01;  3D: (G_21 - G_12, G_02 - G_20, G_10 - G_01)
+ *   NSFEM_DERIVED_DIVERGENCE         1                tr G
+ *   NSFEM_DERIVED_SHEAR_RATE         1                gamma = sqrt(2 S:S), S = (G + G^T) / 2 (the gamma of the
+ *                                                     viscosity laws, nsfem_set_viscosity_law)
+ *   NSFEM_DERIVED_Q_CRITERION        1                Q = (|W|_F^2 - |S|_F^2) / 2 = -1/2 G_ab G_ba, W = (G - G^T) / 2
+ *   NSFEM_DERIVED_VELOCITY_GRADIENT  dim^2            G_ab, row-major in (a, b)
+ *   NSFEM_DERIVED_PRESSURE_GRADIENT  dim              constant on a cell
+ *   NSFEM_DERIVED_SCALAR_GRADIENT    dim              gradient of the P2 scalar of nsfem_set_scalar
+ * Centres:
+ *   NSFEM_DERIVED_CELL    [n_cells][ncomp]           cell means (1/|K|) int_K q by the degree-5 rule (7 / 15 points) of
+ *                                                    nsfem_viscosity_cells: exact up to rounding except SHEAR_RATE,
+ *                                                    for which the rule is part of the definition
+ *   NSFEM_DERIVED_VERTEX  [n_cells][dim + 1][ncomp]  q at every vertex of every cell (DG1 data; exact representation
+ *                                                    of the quantities linear in G)
+ *   NSFEM_DERIVED_NODE    [n_p2][ncomp]              volume-weighted recovery at the P2 nodes,
+ *                                                    sum_{K contains n} |K| q(G_K(x_n)) / sum_{K contains n} |K|
+ *                                                    with G_K(x_n) the cell's own gradient at the node's position in K
+ *                                                    (a vertex or an edge midpoint); nonlinear quantities are formed
+ *                                                    before averaging, the pressure gradient averages the cell
+ *                                                    constants; identified nodes of a periodic mesh sum over all
+ *                                                    their cells
+ * out_host is [entities][total components], the requested quantities in ascending id order within a row; out_len =
+ * the number of doubles (checked).  quantity_mask = the OR of 1 << NSFEM_DERIVED_<quantity>.  pressure_slot /
+ * scalar_slot may be -1 when the mask does not need them.
+ * NODE: the element kernel stores |K| q and |K| node-sorted (the index of the assembly kernels) into a buffer of the
+ * context's own -- allocated at the first call, grown when a call needs more, never the buffers of the step --, one
+ * second launch sums the run of every node in ascending cell order and divides.  No atomics: the same state gives the
+ * same bytes, and a quantity has the same bytes whatever else is in the mask.  No state slot is written.
+ * nsfem_derived_components: components of one quantity on this context's mesh.
+ * nsfem_derived_info: out = {element launches, gather launches, calls, bytes of the private buffer}.
+ * NSFEM_ERR_ARG, with a message and nothing launched: an unknown quantity bit or centre, an empty mask, a slot of the
+ * wrong kind, SCALAR_GRADIENT without nsfem_set_scalar, a wrong out_len, a context with a communicator.  Partitioned
+ * meshes are out of scope on purpose: the recovery at a node on a partition boundary needs the cells of other
+ * ranks. */
+enum nsfem_derived_quantity {
+  NSFEM_DERIVED_VORTICITY = 0, NSFEM_DERIVED_DIVERGENCE = 1, NSFEM_DERIVED_SHEAR_RATE = 2,
+  NSFEM_DERIVED_Q_CRITERION = 3, NSFEM_DERIVED_VELOCITY_GRADIENT = 4, NSFEM_DERIVED_PRESSURE_GRADIENT = 5,
+  NSFEM_DERIVED_SCALAR_GRADIENT = 6
+};
+#define NSFEM_N_DERIVED 7
+enum nsfem_derived_center { NSFEM_DERIVED_CELL = 0, NSFEM_DERIVED_VERTEX = 1, NSFEM_DERIVED_NODE = 2 };
+int nsfem_derived_components(nsfem_ctx* ctx, int quantity, int* ncomp);
+int nsfem_derived_fields(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, int scalar_slot,
+                         unsigned quantity_mask, int center, double* out_host, int64_t out_len);
+int nsfem_derived_info(nsfem_ctx* ctx, int64_t out[4]);
+
 /* ---- measurement hooks (bench.py): time `reps` launches of the dominant SpMV
  * with HIP events on the context's stream; ms per launch returned ------------- */
 /* in-situ HIP-event timing of the finest-level smoothing launches of the velocity multigrid

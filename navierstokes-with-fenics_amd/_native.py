@@ -27,6 +27,10 @@ N_FUNCTIONALS = 11          # NSFEM_N_FUNCTIONALS
 STATS_VELOCITY, STATS_PRESSURE, STATS_SCALAR = 1, 2, 4      # nsfem_stats_flags
 (STATS_MEAN_U, STATS_COV_U, STATS_TKE, STATS_MEAN_P, STATS_VAR_P, STATS_MEAN_T, STATS_VAR_T,
  STATS_FLUX_UT) = range(8)                                  # nsfem_stats_quantity
+(DERIVED_VORTICITY, DERIVED_DIVERGENCE, DERIVED_SHEAR_RATE, DERIVED_Q_CRITERION, DERIVED_VELOCITY_GRADIENT,
+ DERIVED_PRESSURE_GRADIENT, DERIVED_SCALAR_GRADIENT) = range(7)      # nsfem_derived_quantity
+N_DERIVED = 7
+DERIVED_CELL, DERIVED_VERTEX, DERIVED_NODE = range(3)      # nsfem_derived_center
 
 EXPORTED_SYMBOLS = (
     "nsfem_create", "nsfem_destroy", "nsfem_last_error", "nsfem_version",
@@ -53,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
     "nsfem_stats_enable", "nsfem_stats_sample", "nsfem_stats_get", "nsfem_stats_set_groups", "nsfem_stats_profiles",
     "nsfem_stats_info", "nsfem_stats_weight",
+    "nsfem_derived_components", "nsfem_derived_fields", "nsfem_derived_info",
 )
 
 
@@ -235,6 +240,9 @@ def load_library(path=None):
         "nsfem_stats_profiles": (C.c_int, [vp, C.c_int, pd, i64]),
         "nsfem_stats_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_stats_weight": (C.c_int, [vp, pd]),
+        "nsfem_derived_components": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
+        "nsfem_derived_fields": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, pd, i64]),
+        "nsfem_derived_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_poisson_solve": (C.c_int, [vp, pd, i64, pi, pd, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_profile_smoother": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
         "nsfem_profile_convection": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
@@ -1070,6 +1078,47 @@ class NsfemContext:
         out = C.c_double()
         self._check(self._lib.nsfem_stats_weight(self._h, C.byref(out)))
         return out.value
+
+    # -- gradient-derived fields (csrc/derived.hip) -------------------------------------
+    def derived_components(self, quantity):
+        """components of one DERIVED_* quantity on this mesh (vorticity 1 / 3, velocity gradient dim^2, ...)"""
+        out = C.c_int()
+        self._check(self._lib.nsfem_derived_components(self._h, int(quantity), C.byref(out)))
+        return out.value
+
+    def derived_fields(self, quantities, center, velocity_slot=U0, pressure_slot=P, scalar_slot=-1):
+        """{quantity: array} of the DERIVED_* ``quantities`` (one id or several) of the state in the slots, from ONE
+        element launch (DERIVED_NODE: plus one gather launch) and one copy: DERIVED_CELL [n_cells, ncomp] cell means,
+        DERIVED_VERTEX [n_cells, dim + 1, ncomp] values at the vertices of every cell, DERIVED_NODE [n_p2, ncomp]
+        volume-weighted recovery at the P2 nodes; quantities with one component come without the last axis"""
+        ids = [int(quantities)] if np.isscalar(quantities) else [int(q) for q in quantities]
+        mask = 0
+        for q in ids:
+            if not 0 <= q < 32:
+                raise ValueError("unknown derived quantity %r" % (q, ))
+            mask |= 1 << q
+        ids = sorted(set(ids))
+        center = int(center)
+        lead = {DERIVED_CELL: (self.n_cells, ), DERIVED_VERTEX: (self.n_cells, self.dim + 1),
+                DERIVED_NODE: (self.n_p2, )}.get(center, (0, ))
+        # (an unknown quantity or centre, or an empty mask, is the library's to refuse: it says why)
+        ncomp = [self.derived_components(q) if q < N_DERIVED else 0 for q in ids]
+        n_out = int(np.prod(lead)) * sum(ncomp)
+        flat = np.empty(max(n_out, 1), dtype=np.float64)
+        self._check(self._lib.nsfem_derived_fields(self._h, int(velocity_slot), int(pressure_slot), int(scalar_slot),
+                                                   mask, center, _dp(flat), n_out))
+        out = flat[:n_out].reshape(lead + (sum(ncomp), ))
+        res, col = {}, 0
+        for q, n in zip(ids, ncomp):
+            res[q] = out[..., col].copy() if n == 1 else out[..., col:col + n].copy()
+            col += n
+        return res
+
+    def derived_info(self):
+        """dict(cell_launches, gather_launches, calls, bytes = size of the private work buffer)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_derived_info(self._h, out))
+        return dict(cell_launches=int(out[0]), gather_launches=int(out[1]), calls=int(out[2]), bytes=int(out[3]))
 
     def cfl_number(self, slot, step_size):
         out = C.c_double()

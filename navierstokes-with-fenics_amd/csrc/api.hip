@@ -258,6 +258,7 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   upload_quad_tables(qt);
   if (dim == 3) upload_quad_tables_3d();
   upload_functional_tables(dim);
+  upload_derived_tables();
   fresh->M2.init(&fresh->p22, 1, 1, s);
   fresh->K2.init(&fresh->p22, 1, 1, s);
   fresh->L.init(&fresh->p22, 1, 1, s);
@@ -3609,6 +3610,74 @@ extern "C" int nsfem_stats_weight(nsfem_ctx* ctx, double* W) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && W, "null argument");
   *W = ctx->stats.W;
+  API_END(ctx)
+}
+
+// ------------------------------------------------------------------ gradient-derived fields (derived.hip)
+static void derived_require_supported(nsfem_ctx* c) {
+  NSFEM_REQUIRE(!c->comm, "derived fields: contexts with a communicator (partitioned meshes) are not supported -- the "
+                          "recovery at a node on a partition boundary needs the cells of other ranks");
+}
+
+extern "C" int nsfem_derived_components(nsfem_ctx* ctx, int quantity, int* ncomp) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && ncomp, "null argument");
+  const int n = derived_components(ctx->mesh.dim, quantity);
+  NSFEM_REQUIRE(n > 0, "derived fields: unknown quantity");
+  *ncomp = n;
+  API_END(ctx)
+}
+
+// every check comes before the first launch; reads the slots, writes the context's own work buffer only
+extern "C" int nsfem_derived_fields(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, int scalar_slot,
+                                    unsigned quantity_mask, int center, double* out_host, int64_t out_len) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  derived_require_supported(ctx);
+  NSFEM_REQUIRE(quantity_mask != 0, "derived fields: empty quantity mask");
+  NSFEM_REQUIRE((quantity_mask >> NSFEM_N_DERIVED) == 0, "derived fields: unknown quantity bit");
+  NSFEM_REQUIRE(center == NSFEM_DERIVED_CELL || center == NSFEM_DERIVED_VERTEX || center == NSFEM_DERIVED_NODE,
+                "derived fields: unknown centre");
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "derived fields: velocity_slot is not a velocity slot");
+  const bool want_p = (quantity_mask & (1u << NSFEM_DERIVED_PRESSURE_GRADIENT)) != 0;
+  const bool want_T = (quantity_mask & (1u << NSFEM_DERIVED_SCALAR_GRADIENT)) != 0;
+  if (want_p || pressure_slot != -1)
+    NSFEM_REQUIRE(pressure_slot == NSFEM_P || pressure_slot == NSFEM_P_OLD || pressure_slot == NSFEM_P2_OLD,
+                  "derived fields: pressure_slot is not a pressure slot");
+  if (want_T) NSFEM_REQUIRE(ctx->sc.configured, "derived fields: SCALAR_GRADIENT without nsfem_set_scalar");
+  if (want_T || scalar_slot != -1)
+    NSFEM_REQUIRE(scalar_slot == NSFEM_T0 || scalar_slot == NSFEM_T1 || scalar_slot == NSFEM_T2,
+                  "derived fields: scalar_slot is not a level of the transported scalar");
+  const MeshDev& m = ctx->mesh;
+  int ncomp = 0;
+  for (int q = 0; q < NSFEM_N_DERIVED; ++q)
+    if (quantity_mask & (1u << q)) ncomp += derived_components(m.dim, q);
+  const int64_t entities = center == NSFEM_DERIVED_CELL ? (int64_t)m.n_cells
+                           : center == NSFEM_DERIVED_VERTEX ? (int64_t)m.n_cells * (m.dim + 1) : (int64_t)m.n_p2;
+  NSFEM_REQUIRE(out_len == entities * ncomp, "derived fields: wrong size of the output");
+  if (want_T) ensure_scalar_slot(ctx, scalar_slot);
+  nsfem_ctx::Derived& D = ctx->derived;
+  hipStream_t s = ctx->stream;
+  grow(D.work, (size_t)derived_work_doubles(m, center, ncomp));
+  const double* res = launch_derived_fields(s, m, ctx->state[velocity_slot].p, want_p ? ctx->state[pressure_slot].p : nullptr,
+                                            want_T ? ctx->state[scalar_slot].p : nullptr, quantity_mask, center, ncomp,
+                                            D.work.p);
+  ++D.cell_launches;
+  if (center == NSFEM_DERIVED_NODE) ++D.gather_launches;
+  ++D.calls;
+  NSFEM_HIP(hipMemcpyAsync(out_host, res, sizeof(double) * (size_t)out_len, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_derived_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->derived.cell_launches;
+  out[1] = ctx->derived.gather_launches;
+  out[2] = ctx->derived.calls;
+  out[3] = (int64_t)(ctx->derived.work.n * sizeof(double));
   API_END(ctx)
 }
 

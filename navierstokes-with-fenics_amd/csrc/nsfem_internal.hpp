@@ -525,6 +525,25 @@ void launch_stats_profile(hipStream_t s, int dim, bool scalar, const double* acc
 // col_trace[0 .. dim) (turbulent kinetic energy)
 void launch_stats_gather(hipStream_t s, int64_t n, const double* acc, size_t stride, int col, int nc, double scale,
                          int dim, const int col_trace[3], double* out);
+// ---- gradient-derived fields (derived.hip): the quantities NSFEM_DERIVED_* of include/nsfem.h at the centring
+// NSFEM_DERIVED_CELL / VERTEX / NODE.  Components of a quantity (-1: no such quantity):
+inline int derived_components(int dim, int quantity) {
+  switch (quantity) {
+    case NSFEM_DERIVED_VORTICITY: return dim == 2 ? 1 : 3;
+    case NSFEM_DERIVED_DIVERGENCE: case NSFEM_DERIVED_SHEAR_RATE: case NSFEM_DERIVED_Q_CRITERION: return 1;
+    case NSFEM_DERIVED_VELOCITY_GRADIENT: return dim * dim;
+    case NSFEM_DERIVED_PRESSURE_GRADIENT: case NSFEM_DERIVED_SCALAR_GRADIENT: return dim;
+    default: return -1;
+  }
+}
+void upload_derived_tables();   // the rules of both dimensions (nsfem_create)
+// doubles of work space a call needs: the result in its host layout ([entities][ncomp]) and, for NODE, the ncomp + 1
+// node-sorted element planes behind it
+int64_t derived_work_doubles(const MeshDev& m, int center, int ncomp);
+// ONE element launch (plus ONE gather launch for NODE); returns where the result lies in `work`.  p / T may be null
+// when the mask does not ask for their gradients
+const double* launch_derived_fields(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* T,
+                                    unsigned mask, int center, int ncomp, double* work);
 // diag extraction: d[(i,a)] = 1 / A_ii[a][a]  (mask rows -> 1)
 void launch_inv_diag(hipStream_t s, const BlockMat& A, int nv, const uint8_t* rowmask,
                      double* dinv);
@@ -1191,6 +1210,12 @@ struct nsfem_ctx {
       nsfem::DevBuf<double> weights;
     } groups[2];
   } stats;
+  // nsfem_derived_fields (derived.hip): the grow-only work buffer of its own (result + node-sorted element planes;
+  // never m.rbuf / m.ebuf) and the counters of nsfem_derived_info
+  struct Derived {
+    nsfem::DevBuf<double> work;
+    int64_t cell_launches = 0, gather_launches = 0, calls = 0;
+  } derived;
   int64_t jac_lattice_launches = 0;   // applications of the matrix-free Jacobian through k_jac_lattice
   bool mf_active = false;           // the running step driver applies the Jacobian matrix-free
   int pressure_history = 0;         // IPCS: pressure levels shifted since the state was last set (0..2)

@@ -372,6 +372,37 @@ class ProblemBase:
         g = self._cell_gradients(self._get_pressure().nodal_values(), dm.p1_dofmap, False)
         return HostField(self._mesh, "pressure gradient", "Cell", g[:, 0, 0, :])
 
+    def _compute_derived_fields(self, names, center="Node"):
+        """``HostField``s of the gradient-derived quantities ``names`` (keys of ``derived_fields.QUANTITIES``:
+        "vorticity", "divergence", "shear rate", "q criterion", "velocity gradient", "pressure gradient", "temperature
+        gradient") of the current solution, all from ONE device call (nsfem_derived_fields) -- callable from
+        ``postprocess_solution`` at every step, valid for ``_add_to_field_output``.  ``center`` "Cell": the cell means;
+        "Node": the volume-weighted recovery at the P2 nodes, picked at the mesh vertices.  The velocity gradient is
+        stored as a 3 x 3 tensor per entity (zero-padded in 2D).  New helper; ``_compute_vorticity`` and
+        ``_compute_pressure_gradient`` remain the host evaluation."""
+        import derived_fields
+        from fem_function import HostField
+        assert center in ("Node", "Cell")
+        names = [names] if isinstance(names, str) else list(names)
+        solver = self._get_solver()
+        values = derived_fields.compute(solver, names, center)
+        fields = []
+        for name in names:
+            v = values[name]
+            if center == "Node":
+                v = v[solver._dofmap.vertex_node]
+            if name == "velocity gradient":
+                full = np.zeros((v.shape[0], 3, 3))
+                full[:, :v.shape[1], :v.shape[2]] = v
+                v = full.reshape(-1, 9)
+            fields.append(HostField(self._mesh, name, center, v))
+        return fields
+
+    def _compute_derived_field(self, name, center="Node"):
+        """one field of ``_compute_derived_fields`` (several fields of one post-processing pass: ask for them together,
+        they then share the device call)"""
+        return self._compute_derived_fields([name], center)[0]
+
     def _write_xdmf_file(self, current_time=0.0):
         """velocity, pressure and the additional fields at ``current_time`` (:244-264)."""
         assert isinstance(current_time, float)

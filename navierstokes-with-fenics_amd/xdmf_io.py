@@ -73,7 +73,7 @@ class XDMFFile:
         values = np.asarray(values, dtype=np.float64)
         if values.ndim == 2 and values.shape[1] == 2:            # ParaView wants 3-vectors
             values = np.concatenate([values, np.zeros((values.shape[0], 1))], axis=1)
-        kind = "Scalar" if values.ndim == 1 else "Vector"
+        kind = "Scalar" if values.ndim == 1 else "Tensor" if values.shape[1] == 9 else "Vector"
         attr = ('<Attribute Name="%s" AttributeType="%s" Center="%s">\n%s\n</Attribute>'
                 % (function.name(), kind, center, self._data_item(values, "Float")))
         t = float(t)
