@@ -745,7 +745,7 @@ int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32_t H, int32
    matrix itself when exact != 0 (uniform lines, every box edge between two non-periodic faces next to a Dirichlet
    face): precond = 3 then solves the projection step directly (one pass plus the residual check); with exact == 0 it
    runs CG preconditioned by T^+ (mesh-independent iteration counts).  Six dense mode products on the matrix cores
-   (csrc/fastdiag3d.hip).  Refused on partitioned contexts.  Replaces 2D factors set before, and vice versa.  Host side:
+   (csrc/fastdiag.hip).  Refused on partitioned contexts.  Replaces 2D factors set before, and vice versa.  Host side:
    poisson_fd.factors_3d(). */
 int nsfem_poisson_set_fast_diag_3d(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz, const double* Vx,
                                    const double* Vy, const double* Vz, const double* inv, int32_t exact);

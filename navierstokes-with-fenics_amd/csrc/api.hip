@@ -1136,13 +1136,12 @@ static bool pressure_pinned_anywhere(nsfem_ctx* c) {
 static int poisson_solve_fast_diag(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_info& info) {
   hipStream_t s = c->stream;
   const int64_t np = npre(c);
-  // (3D box lattices: exact factors only -- inexact ones precondition CG, poisson_solve)
-  const bool box = c->fd3_p.ready();
-  NSFEM_REQUIRE(box ? c->fd3_p.exact && (int64_t)c->fd3_p.Nx * c->fd3_p.Ny * c->fd3_p.Nz == np
-                    : c->fd_p.ready() && (int64_t)c->fd_p.W * c->fd_p.H == np,
+  // (one-rank factors of the whole pressure space; 3D box lattices: exact factors only -- inexact ones precondition
+  // CG, poisson_solve)
+  FastDiagBase* fd = c->fast_diag();
+  NSFEM_REQUIRE(fd && fd->exact && fd->fits(np, np, false),
                 "fast diagonalisation requested but no factors were set (nsfem_poisson_set_fast_diag)");
-  Precond& fd = box ? (Precond&)c->fd3_p : (Precond&)c->fd_p;
-  if (box) ++c->fd3_p.solves;
+  ++fd->solves;
   NSFEM_REQUIRE(!c->distributed(), "fast diagonalisation: one rank only");
   KrylovWork& w = c->kw;
   w.ensure(std::max<int64_t>(np, nvel(c)));
@@ -1163,7 +1162,7 @@ static int poisson_solve_fast_diag(nsfem_ctx* c, const nsfem_krylov_opts& o, nsf
   double bnorm = 0.0, target = 0.0;
   launch_residual(s, c->Ap, 1, x, rhs, w.r.p, c->mask_p.p, MASK_ZERO);
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
-    fd.apply(s, w.r.p, w.z.p);
+    fd->apply(s, w.r.p, w.z.p);
     launch_axpby(s, np, 1.0, x, 1.0, w.z.p, x);
     ++info.iterations;
     // the residual of the corrected iterate (the next pass's right-hand side)
@@ -1196,16 +1195,16 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   ++w.touch;
   double* parts = w.parts.p;
   constexpr int PR = 10, PB0 = 13;
-  // Partitioned strips / slabs: the same solve with ONE collective (FastDiag::apply_strip, FastDiag3::apply_slab).
+  // Partitioned strips / slabs: the same solve with ONE collective (FastDiagBase::apply on partitioned factors).
   // u* carries valid ghost values (every Krylov solve fills the ghosts of its solution), so D u* is complete on the
   // owned rows; ghost rows are zeroed (every node counts once in the sums over the ranks); z comes back on every local
   // row, ghost lines / planes included, so p = p_old + z needs no halo exchange and the check r - A z none either.
   const bool dist = c->distributed();
   const uint8_t* gm = dist ? c->mask_p.p : nullptr;                            // (flag 2 on ghost rows)
-  const bool box = c->fd3_p.ready();            // exact 3D factors (the caller checks)
-  NSFEM_REQUIRE(!dist || ((box ? c->fd3_p.slab() : c->fd_p.strip()) && gm),
+  FastDiagBase& fd = *c->fast_diag();           // (the caller checked fast_diag_direct())
+  NSFEM_REQUIRE(!dist || (fd.partitioned() && gm),
                 "fast diagonalisation on a partitioned mesh: strip or slab factors not set");
-  if (box) ++c->fd3_p.solves;
+  ++fd.solves;
   launch_spmv_scaled(s, c->Dv, 1, -c->alpha[0] / c->k, c->state[NSFEM_USTAR].p, w.r.p);
   if (dist) {
     launch_zero_ghost(s, np, gm, w.r.p);
@@ -1225,9 +1224,7 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   info.iterations = 0;
   info.converged = 0;
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
-    if (box) c->fd3_p.apply(s, r, w.z.p);                                      // (slab factors: a collective)
-    else if (dist) c->fd_p.apply_strip(s, c->comm, r, w.z.p);
-    else c->fd_p.apply(s, r, w.z.p);
+    fd.apply(s, r, w.z.p);                                                     // (partitioned factors: a collective)
     launch_axpby(s, np, 1.0, base, 1.0, w.z.p, c->state[NSFEM_P].p);          // p = p_old + z (later passes: p += z)
     base = c->state[NSFEM_P].p;
     ++info.iterations;
@@ -1251,7 +1248,8 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
 
 static int poisson_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_info& info) {
   // (3D box lattices with inexact factors: CG preconditioned by T^+ below)
-  const bool box_pcg = o.precond == 3 && c->fd3_p.ready() && !c->fd3_p.exact;
+  FastDiagBase* fd = c->fast_diag();
+  const bool box_pcg = o.precond == 3 && fd && !fd->exact;
   if (o.precond == 3 && !box_pcg) return poisson_solve_fast_diag(c, o, info);
   LinOp op;
   op.A = &c->Ap;
@@ -1267,13 +1265,10 @@ static int poisson_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_i
   }
   if (box_pcg) {
     // (slab factors: T^+ is a collective with valid ghost planes in z; the CG iteration itself exchanges halos)
-    const FastDiag3& f = c->fd3_p;
-    const int64_t pl = (int64_t)f.Nx * f.Ny;
-    NSFEM_REQUIRE(c->distributed() == f.slab() &&
-                      (f.slab() ? pl * f.Nz == c->n_p1_global && pl * f.n_loc == npre(c) : pl * f.Nz == npre(c)),
+    NSFEM_REQUIRE(fd->fits(npre(c), c->n_p1_global, c->distributed()),
                   "fast diagonalisation (3D): factors do not fit the pressure space");
-    op.prec = &c->fd3_p;
-    ++c->fd3_p.solves;
+    op.prec = fd;
+    ++fd->solves;
   }
   op.graph_epoch = c->graph_epoch;
   return pcg(c->stream, c->kw, op, c->rhs_p.p, c->state[NSFEM_P].p, o, info, !pressure_pinned_anywhere(c));
@@ -1863,15 +1858,24 @@ extern "C" int nsfem_set_partition(nsfem_ctx* ctx, const nsfem_partition_desc* d
   API_END(ctx)
 }
 
+// A context's communicator is replaced: the old one goes before the new one is made (a rank holds one slot of its
+// group / segment), the new one takes the context's settings.  (Nobody keeps a copy of ctx->comm across an attach:
+// the fast-diagonalisation objects hold the address of the member.)
+static void drop_comm(nsfem_ctx* ctx) {
+  delete ctx->comm;
+  ctx->comm = nullptr;
+}
+static void adopt_comm(nsfem_ctx* ctx, Comm* comm) {
+  ctx->comm = comm;
+  comm->periodic = ctx->partition_periodic;
+  comm->overlap = ctx->overlap;
+}
+
 extern "C" int nsfem_comm_attach_local(nsfem_ctx* ctx, void* group, int rank) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && group, "null argument");
-  delete ctx->comm;
-  ctx->comm = nullptr;
-  ctx->comm = make_local_comm(group, rank);
-  ctx->comm->periodic = ctx->partition_periodic;
-  ctx->comm->overlap = ctx->overlap;
-  if (ctx->fd3_p.slab()) ctx->fd3_p.comm = ctx->comm;
+  drop_comm(ctx);
+  adopt_comm(ctx, make_local_comm(group, rank));
   API_END(ctx)
 }
 
@@ -1879,12 +1883,8 @@ extern "C" int nsfem_comm_attach_rccl(nsfem_ctx* ctx, const char* id128, int ran
   API_BEGIN
   NSFEM_REQUIRE(ctx && id128, "null argument");
   NSFEM_HIP(hipSetDevice(ctx->device));
-  delete ctx->comm;
-  ctx->comm = nullptr;
-  ctx->comm = make_rccl_comm(id128, rank, size);
-  ctx->comm->periodic = ctx->partition_periodic;
-  ctx->comm->overlap = ctx->overlap;
-  if (ctx->fd3_p.slab()) ctx->fd3_p.comm = ctx->comm;
+  drop_comm(ctx);
+  adopt_comm(ctx, make_rccl_comm(id128, rank, size));
   API_END(ctx)
 }
 
@@ -1892,12 +1892,8 @@ extern "C" int nsfem_comm_attach_shm(nsfem_ctx* ctx, const char* name, int rank,
   API_BEGIN
   NSFEM_REQUIRE(ctx && name, "null argument");
   NSFEM_HIP(hipSetDevice(ctx->device));
-  delete ctx->comm;
-  ctx->comm = nullptr;
-  ctx->comm = make_shm_comm(name, rank, size, slot_bytes);
-  ctx->comm->periodic = ctx->partition_periodic;
-  ctx->comm->overlap = ctx->overlap;
-  if (ctx->fd3_p.slab()) ctx->fd3_p.comm = ctx->comm;
+  drop_comm(ctx);
+  adopt_comm(ctx, make_shm_comm(name, rank, size, slot_bytes));
   API_END(ctx)
 }
 
@@ -2219,9 +2215,7 @@ static void projection_step(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_s
                 "fast diagonalisation on a partitioned mesh solves the pure Neumann projection step only "
                 "(pressure Dirichlet nodes are set): use another Poisson preconditioner");
   // (3D box lattices: the pass-plus-check driver for exact factors; inexact ones assemble and run CG with T^+)
-  const bool direct = ctx->fd3_p.ready() ? ctx->fd3_p.exact && ctx->distributed() == ctx->fd3_p.slab()
-                                         : ctx->fd_p.ready() && ctx->distributed() == ctx->fd_p.strip();
-  if (fd && !pressure_pinned_anywhere(ctx) && direct) {
+  if (fd && !pressure_pinned_anywhere(ctx) && ctx->fast_diag_direct()) {
     rc = poisson_direct_step(ctx, opts->poisson, si);
   } else {
     poisson_assemble(ctx, opts->pressure_extrapolation != 0);
@@ -3947,6 +3941,15 @@ extern "C" int nsfem_lattice_restrict(nsfem_ctx* ctx, int nv, int levels, int w,
   API_END(ctx)
 }
 
+// The shared tail of the four setters: the factors set last are the ones precond = 3 uses, so the other object is
+// released.  Captured CG bodies hold the addresses of 3D factors and work buffers (FastDiag3 as op.prec): the graph
+// epoch moves whenever 3D factors are installed or released (not for a plain 2D re-set: nothing captures those).
+static void fast_diag_installed(nsfem_ctx* ctx, bool box) {
+  if (box || ctx->fd3_p.ready()) ctx->graph_epoch++;
+  if (box) ctx->fd_p.release();
+  else ctx->fd3_p.release();
+}
+
 // Factors of the fast diagonalisation of the pressure Poisson operator (poisson_fd.factors): the P1 space must be
 // the W x H lattice in lexicographic numbering, the pressure Dirichlet set a union of whole sides (or empty).
 // Krylov option precond = 3 of the projection step then solves it directly (four dense products on the matrix cores).
@@ -3957,10 +3960,7 @@ extern "C" int nsfem_poisson_set_fast_diag(nsfem_ctx* ctx, int32_t W, int32_t H,
   NSFEM_REQUIRE((int64_t)W * H == npre(ctx), "fast diagonalisation: W x H must be the number of pressure dofs");
   NSFEM_REQUIRE(!ctx->distributed(), "partitioned context: nsfem_poisson_set_fast_diag_rows");
   ctx->fd_p.set(ctx->stream, W, H, Vx, Vy, inv);
-  if (ctx->fd3_p.ready()) {             // (the factors set last are the ones precond = 3 uses)
-    ctx->fd3_p.release();
-    ctx->graph_epoch++;                 // captured CG bodies may hold the freed 3D buffers (FastDiag3 as op.prec)
-  }
+  fast_diag_installed(ctx, false);
   API_END(ctx)
 }
 
@@ -3975,8 +3975,7 @@ extern "C" int nsfem_poisson_set_fast_diag_3d(nsfem_ctx* ctx, int32_t Nx, int32_
   NSFEM_REQUIRE(Nx >= 2 && Ny >= 2 && Nz >= 2 && (int64_t)Nx * Ny * Nz == npre(ctx),
                 "fast diagonalisation (3D): Nx x Ny x Nz must be the number of pressure dofs");
   ctx->fd3_p.set(ctx->stream, Nx, Ny, Nz, Vx, Vy, Vz, inv, exact != 0);
-  ctx->fd_p.release();                  // (the factors set last are the ones precond = 3 uses)
-  ctx->graph_epoch++;                   // captured CG bodies hold the addresses of the previous factors / work buffers
+  fast_diag_installed(ctx, true);
   API_END(ctx)
 }
 
@@ -3997,7 +3996,7 @@ extern "C" int nsfem_poisson_fast_diag_3d_info(nsfem_ctx* ctx, int64_t out[6]) {
 
 // Partitioned strips: the factors of the GLOBAL W x H lattice; this rank's P1 space is the lattice lines
 // first_line ... first_line + n_p1 / W - 1 (ghost lines included).  The fused step driver then solves the projection
-// step with one all-reduce of H x W doubles (FastDiag::apply_strip).
+// step with one all-reduce of H x W doubles (FastDiag::apply on strip factors).
 extern "C" int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32_t H, int32_t first_line,
                                                 const double* Vx, const double* Vy, const double* inv) {
   API_BEGIN
@@ -4008,18 +4007,15 @@ extern "C" int nsfem_poisson_set_fast_diag_rows(nsfem_ctx* ctx, int32_t W, int32
                 "fast diagonalisation: the local pressure space is not a run of whole lattice lines");
   NSFEM_REQUIRE((int64_t)W * H == ctx->n_p1_global, "fast diagonalisation: W x H must be the global number of pressure dofs");
   ctx->fd_p.set_rows(ctx->stream, W, H, first_line, (int)(np / W), Vx, Vy, inv);
-  if (ctx->fd3_p.ready()) {             // (the factors set last are the ones precond = 3 uses)
-    ctx->fd3_p.release();
-    ctx->graph_epoch++;
-  }
+  fast_diag_installed(ctx, false);
   API_END(ctx)
 }
 
 // Partitioned slabs of a 3D box lattice: the factors of the GLOBAL Nz x Ny x Nx lattice; this rank's P1 space is the
 // lattice planes (first_plane + i) mod Nz, i < n_p1 / (Nx Ny) (ghost planes included), and the planes it owns (the P1
 // ghost flags of nsfem_set_partition) are one contiguous run.  precond = 3 then solves the projection step with one
-// all-reduce of Nz x Ny x Nx doubles (FastDiag3::apply_slab): directly for exact factors, as the preconditioner of CG
-// otherwise.
+// all-reduce of Nz x Ny x Nx doubles (FastDiag3::apply on slab factors): directly for exact factors, as the
+// preconditioner of CG otherwise.
 extern "C" int nsfem_poisson_set_fast_diag_3d_planes(nsfem_ctx* ctx, int32_t Nx, int32_t Ny, int32_t Nz,
                                                      int32_t first_plane, const double* Vx, const double* Vy,
                                                      const double* Vz, const double* inv, int32_t exact) {
@@ -4053,17 +4049,16 @@ extern "C" int nsfem_poisson_set_fast_diag_3d_planes(nsfem_ctx* ctx, int32_t Nx,
   }
   NSFEM_REQUIRE(run && own0 >= 0,
                 "fast diagonalisation (3D): the owned pressure dofs are not one contiguous run of whole lattice planes");
-  ctx->fd3_p.set_planes(ctx->stream, ctx->comm, Nx, Ny, Nz, first_plane, (int)n_loc, (int)own0, (int)(own_end - own0),
-                        Vx, Vy, Vz, inv, exact != 0);
-  ctx->fd_p.release();                  // (the factors set last are the ones precond = 3 uses)
-  ctx->graph_epoch++;                   // captured CG bodies hold the addresses of the previous factors / work buffers
+  ctx->fd3_p.set_planes(ctx->stream, Nx, Ny, Nz, first_plane, (int)n_loc, (int)own0, (int)(own_end - own0), Vx, Vy, Vz,
+                        inv, exact != 0);
+  fast_diag_installed(ctx, true);
   API_END(ctx)
 }
 
 // Test hook: one application z = M^-1 r of a multigrid preconditioner on host vectors -- which = 0 pressure Poisson
 // hierarchy (mg_p), 1 velocity hierarchy (mg_v, the identity rows of the Newton preconditioner included), 2 the
-// fast-diagonalisation solve z = A^+ r (FastDiag::apply; on strip factors FastDiag::apply_strip, on slab factors
-// FastDiag3::apply_slab: collectives).  Lets the parity tests compare kernel families cycle by cycle.
+// fast-diagonalisation solve z = A^+ r of the active factors (FastDiagBase::apply; on strip and slab factors a
+// collective).  Lets the parity tests compare kernel families cycle by cycle.
 extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double* z) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && r && z && (which == 0 || which == 1 || which == 2), "bad argument");
@@ -4073,15 +4068,13 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
     DevBuf<double> dr, dz;
     dr.upload(r, (size_t)n, s);
     dz.alloc((size_t)n);
-    if (ctx->fd3_p.ready()) {          // 3D box lattice: z = T^+ r (slab factors: a collective, ghost planes ignored)
-      ctx->fd3_p.apply(s, dr.p, dz.p);
-    } else if (ctx->fd_p.strip()) {    // strips (a collective: every rank calls it): ghost rows zeroed, as the step does
+    nsfem::FastDiagBase* fd = ctx->fast_diag();
+    NSFEM_REQUIRE(fd, "fast diagonalisation: factors not set (or set for a strip)");
+    if (fd->reads_ghosts()) {          // strips (a collective: every rank calls it): ghost rows zeroed, as the step does
       NSFEM_REQUIRE(ctx->distributed(), "strip factors need a partitioned context");
       launch_zero_ghost(s, n, ctx->mask_p.p, dr.p);
-      ctx->fd_p.apply_strip(s, ctx->comm, dr.p, dz.p);
-    } else {
-      ctx->fd_p.apply(s, dr.p, dz.p);
     }
+    fd->apply(s, dr.p, dz.p);          // (slab factors: a collective as well, ghost planes of r ignored)
     NSFEM_HIP(hipMemcpyAsync(z, dz.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     NSFEM_HIP(hipStreamSynchronize(s));
     return NSFEM_OK;

@@ -909,58 +909,78 @@ struct Multigrid : Precond {
                    double& rho) const;
 };
 
-// Fast diagonalisation of the P1 stiffness matrix of a tensor-product lattice (fastdiag.hip, poisson_fd.py):
-// z = A^+ r by four dense products on the matrix cores
-struct FastDiag : Precond {
+// Fast diagonalisation of the pressure Poisson operator on tensor-product lattices (fastdiag.hip, poisson_fd.py): what
+// the callers need of either solver object.  apply(s, r, z) is z = A^+ r on one rank and a COLLECTIVE (one all-reduce
+// of the transformed global lattice array between the forward and the backward products) when the factors are
+// partitioned.  Contracts of the partitioned forms: strips sum over every local row, so r must carry ZERO ghost rows
+// (reads_ghosts()); slabs contract the owned planes only and never read the ghost planes of r; both return z on EVERY
+// local row / plane, ghosts included (no halo exchange afterwards).
+struct FastDiagBase : Precond {
+  Comm* const* comm;             // the owner's communicator slot, read at every partitioned apply (no copy to patch)
+  bool exact = true;             // the tensor sum is the stiffness matrix itself (2D: always); else it preconditions CG
+  int64_t applications = 0;      // apply() calls issued by the host (a CG iteration replayed from a graph: not counted)
+  int64_t solves = 0;            // projection solves that ran with these factors
+  explicit FastDiagBase(Comm* const* comm_) : comm(comm_) {}
+  virtual bool ready() const = 0;
+  virtual bool partitioned() const = 0;            // strip or slab factors
+  virtual bool reads_ghosts() const { return false; }
+  // the factors fit a pressure space of n_local dofs on this rank, n_global in all: partitioned exactly when the
+  // context is, this rank's lines / planes n_local nodes, and then the GLOBAL lattice n_global nodes
+  virtual bool fits(int64_t n_local, int64_t n_global, bool distributed) const = 0;
+  virtual void release() = 0;    // frees the factors and work buffers (ready() false); the counters stay
+};
+
+// 2D: z = A^+ r by four dense products on the matrix cores
+struct FastDiag : FastDiagBase {
+  using FastDiagBase::FastDiagBase;
   int W = 0, H = 0;
   // partitioned strips: this rank holds the lattice lines j0 ... j0 + h_loc - 1 (ghost lines included) of the GLOBAL
   // W x H lattice; Vy then keeps those rows of V_y only.  h_loc == 0: the whole lattice (one rank)
   int j0 = 0, h_loc = 0;
   DevBuf<double> Vx, Vy, inv, t1, t2;
-  int64_t applications = 0;
-  bool ready() const { return W > 0 && Vx.p && Vy.p && inv.p; }
-  bool strip() const { return h_loc > 0; }
+  bool ready() const override { return W > 0 && Vx.p && Vy.p && inv.p; }
+  bool partitioned() const override { return h_loc > 0; }
+  bool reads_ghosts() const override { return partitioned(); }
+  bool fits(int64_t n_local, int64_t n_global, bool distributed) const override {
+    return ready() && distributed == partitioned() && (int64_t)W * (partitioned() ? h_loc : H) == n_local &&
+           (!distributed || (int64_t)W * H == n_global);
+  }
   void set(hipStream_t s, int W_, int H_, const double* vx, const double* vy, const double* inv_);
   void set_rows(hipStream_t s, int W_, int H_, int j0_, int h_loc_, const double* vx, const double* vy,
                 const double* inv_);
-  void release();                // frees the factors and work buffers (ready() false)
-  void apply(hipStream_t s, const double* r, double* z) override;
-  // strips: r with zero ghost rows in, z on EVERY local row (ghost lines included) out; one all-reduce of the
-  // H x W transformed array in between
-  void apply_strip(hipStream_t s, Comm* comm, const double* r, double* z);
-};
-// k_fd_gemm (fastdiag.hip): C = op(A) op(B) (.* scale), row-major; ta: A(m, k) = A[k * lda + m], tb: B(k, n) =
-// B[n * ldb + k] (not both)
-void launch_fd_gemm(hipStream_t s, bool ta, bool tb, int M, int N, int K, const double* A, int lda, const double* B,
-                    int ldb, double* C, int ldc, const double* scale);
+  void release() override;
+  void apply(hipStream_t s, const double* r, double* z) override;      // strip factors: apply_strip
 
-// Fast diagonalisation on 3D box lattices (fastdiag3d.hip, poisson_fd.factors_3d): z = T^+ r, T the tensor sum of the
-// 1D stiffness / lumped mass matrices, by six mode products of the N_z x N_y x N_x array on the matrix cores.  exact:
-// T is the P1 stiffness matrix itself (the projection step is one pass plus the residual check); otherwise T^+
-// preconditions CG.
-struct FastDiag3 : Precond {
+ private:
+  void apply_strip(hipStream_t s, const double* r, double* z);
+};
+
+// 3D box lattices (poisson_fd.factors_3d): z = T^+ r, T the tensor sum of the 1D stiffness / lumped mass matrices, by
+// six mode products of the N_z x N_y x N_x array on the matrix cores.  exact: T is the P1 stiffness matrix itself (the
+// projection step is one pass plus the residual check); otherwise T^+ preconditions CG.
+struct FastDiag3 : FastDiagBase {
+  using FastDiagBase::FastDiagBase;
   int Nx = 0, Ny = 0, Nz = 0;    // the GLOBAL lattice
-  bool exact = false;
   // partitioned slabs: this rank holds the n_loc lattice planes (first + i) mod Nz (ghost planes included) and owns
   // the run own0 ... own0 + n_own - 1 of them; Vz then keeps the rows of V_z of its local planes.  n_loc == 0: the
   // whole lattice (one rank)
   int first = 0, n_loc = 0, own0 = 0, n_own = 0;
-  Comm* comm = nullptr;          // slabs: the context's communicator (the apply is a collective)
   DevBuf<double> Vx, Vy, Vz, inv, t1, t2, tz;
-  int64_t applications = 0;      // apply() calls issued by the host (a CG iteration replayed from a graph: not counted)
-  int64_t solves = 0;            // projection solves that ran with these factors
-  bool ready() const { return Nx > 0 && Vx.p && Vy.p && Vz.p && inv.p; }
-  bool slab() const { return n_loc > 0; }
+  bool ready() const override { return Nx > 0 && Vx.p && Vy.p && Vz.p && inv.p; }
+  bool partitioned() const override { return n_loc > 0; }
+  bool fits(int64_t n_local, int64_t n_global, bool distributed) const override {
+    return ready() && distributed == partitioned() && (int64_t)Nx * Ny * (partitioned() ? n_loc : Nz) == n_local &&
+           (!distributed || (int64_t)Nx * Ny * Nz == n_global);
+  }
   void set(hipStream_t s, int Nx_, int Ny_, int Nz_, const double* vx, const double* vy, const double* vz,
            const double* inv_, bool exact_);
   // vz: the GLOBAL Nz x Nz matrix (its rows of the local planes are gathered here)
-  void set_planes(hipStream_t s, Comm* comm_, int Nx_, int Ny_, int Nz_, int first_, int n_loc_, int own0_,
-                  int n_own_, const double* vx, const double* vy, const double* vz, const double* inv_, bool exact_);
-  void release();
-  // one rank: z = T^+ r; slabs: apply_slab
-  void apply(hipStream_t s, const double* r, double* z) override;
-  // slabs: r on the local planes in (ghost planes never read), z on EVERY local plane out (ghost planes included);
-  // one all-reduce of the Nz x Ny x Nx transformed array in between
+  void set_planes(hipStream_t s, int Nx_, int Ny_, int Nz_, int first_, int n_loc_, int own0_, int n_own_,
+                  const double* vx, const double* vy, const double* vz, const double* inv_, bool exact_);
+  void release() override;
+  void apply(hipStream_t s, const double* r, double* z) override;      // slab factors: apply_slab
+
+ private:
   void apply_slab(hipStream_t s, const double* r, double* z);
 };
 // x -= sum(parts) / count on n entries (k_sum fills the slot: launch_sum)
@@ -1124,8 +1144,19 @@ struct nsfem_ctx {
   nsfem::Multigrid mg_p, mg_v;
   bool cor_start_ready = false;                // correction_assemble produced the mass solve's start residual and sums
   uint64_t cor_start_touch = 0;                //   ... and nobody has used the Krylov work vectors since (kw.touch)
-  nsfem::FastDiag fd_p;                        // direct projection-step solver on tensor-product lattices
-  nsfem::FastDiag3 fd3_p;                      // the same on 3D box lattices (direct or CG preconditioner)
+  nsfem::FastDiag fd_p{&comm};                 // direct projection-step solver on tensor-product lattices
+  nsfem::FastDiag3 fd3_p{&comm};               // the same on 3D box lattices (direct or CG preconditioner)
+  // the factors precond = 3 uses: the 3D ones if set, else the 2D ones, else none (a setter releases the other object)
+  nsfem::FastDiagBase* fast_diag() {
+    if (fd3_p.ready()) return &fd3_p;
+    return fd_p.ready() ? &fd_p : nullptr;
+  }
+  // the projection step can take the pass-and-check driver (poisson_direct_step): exact factors, partitioned exactly
+  // when the context is
+  bool fast_diag_direct() {
+    nsfem::FastDiagBase* fd = fast_diag();
+    return fd && fd->exact && distributed() == fd->partitioned();
+  }
   bool fd_p_singular = false;
   bool mg_built = false, mg_p_dirty = true, mg_v_dirty = true;
   std::vector<int32_t> h_bc_v, h_bc_p;         // host copies of the Dirichlet dof sets

@@ -122,7 +122,7 @@ def lattice_lines(mesh):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 3D box lattices (fem_mesh.box_mesh: six Kuhn tetrahedra per cube around the main diagonal; csrc/fastdiag3d.hip).
+# 3D box lattices (fem_mesh.box_mesh: six Kuhn tetrahedra per cube around the main diagonal; csrc/fastdiag.hip).
 #
 # With the 1D matrices of the three line meshes, T = K_z (x) W_y (x) W_x + W_z (x) K_y (x) W_x + W_z (x) W_y (x) K_x
 # equals the P1 stiffness matrix A on every row away from the box's edges when each direction is uniformly spaced (the

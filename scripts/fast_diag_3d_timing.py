@@ -1,5 +1,5 @@
 """Times the 3D projection-step solvers through the solver classes: poisson_solver = "fast_diagonalization" (the tensor
-solve of csrc/fastdiag3d.hip, direct or as a CG preconditioner) against "multigrid" (CG with the pressure V-cycle).
+solve of csrc/fastdiag.hip, direct or as a CG preconditioner) against "multigrid" (CG with the pressure V-cycle).
 
 For every case and solver: ms per time step (IPCSSolver.solve() + advance inside the InstationaryProblem loop, after
 the warm-up steps of solve_problem()), the projection solve alone (nsfem_solve on the assembled Poisson system of the

@@ -1,5 +1,6 @@
-"""Fast diagonalisation on 3D box lattices (csrc/fastdiag3d.hip, poisson_fd.factors_3d): the six mode products against
-the numpy formula at the edges of the k-loop pipeline; the projection step with precond = 3 against the LU oracle --
+"""Fast diagonalisation on 3D box lattices (FastDiag3 in csrc/fastdiag.hip, poisson_fd.factors_3d): the six mode
+products against the numpy formula at the edges of the k-loop pipeline; the projection step with precond = 3 against
+the LU oracle --
 a direct solve where the tensor sum is the stiffness matrix (triple-periodic Taylor-Green box), CG preconditioned by it
 where it is not (closed cavity, open-outlet channel); the option poisson_solver = "fast_diagonalization" through the
 solver classes; and the refusals."""
@@ -225,6 +226,55 @@ def test_projection_step_triple_periodic_taylor_green_is_one_direct_pass():
     assert its == [1, 1, 1], its
     assert info["solves"] == 3 and info["applications"] == 3
     assert eu < 1e-9 and ep < 1e-9, (eu, ep)
+
+
+def test_refinement_passes_of_the_direct_step_on_a_box():
+    """The same triple-periodic Taylor-Green box with the exact factors and with inv * (1 + DELTA) (constants and
+    derivation of test_gpu_fast_diag: uniformly scaled factors leave DELTA^k |r| after pass k, so rtol = 3e-11 with
+    atol = 0 takes SIX passes): poisson_direct_step refines with the 3D object -- one pass per step with the exact
+    factors, six with the perturbed ones, one solve per step and one application per pass, and the same fields to
+    1e-10 (the pressure modulo a constant)."""
+    from test_gpu_fast_diag import DELTA, PASSES, RTOL
+    mesh, dm = _box((8, 8, 8), (1.0, 1.0, 1.0), (0, 1, 2))
+    g = 2.0 * np.pi
+    X, Y = dm.p2_coords, dm.p1_coords
+    u0 = np.stack([np.cos(g * X[:, 0]) * np.sin(g * X[:, 1]), -np.sin(g * X[:, 0]) * np.cos(g * X[:, 1]),
+                   np.zeros(dm.n_p2)], axis=1).ravel()
+    p0 = -0.25 * (np.cos(2 * g * Y[:, 0]) + np.cos(2 * g * Y[:, 1]))
+    f = pf.factors_3d(*pf.box_lattice(mesh, dm), np.zeros(0, np.int64))
+    assert f["exact"] and f["singular"]
+    nsteps, fields = 3, {}
+    for refine in (False, True):
+        ctx = _context(mesh, dm)
+        ctx.poisson_set_fast_diag_3d(dict(f, inv=f["inv"] * (1.0 + DELTA)) if refine else f)
+        for slot in (nat.U0, nat.U1, nat.U2):
+            ctx.set_state(slot, u0)
+        for slot in (nat.P, nat.P_OLD):
+            ctx.set_state(slot, p0)
+        ctx.set_coeffs(1.0, 1.0, 0.01)
+        ctx.set_dirichlet(nat.VELOCITY, np.zeros(0, np.int64), np.zeros(0))
+        ctx.set_dirichlet(nat.PRESSURE, np.zeros(0, np.int64), np.zeros(0))
+        opts = ctx.default_step_opts()
+        for o in (opts.momentum, opts.correction):
+            o.rtol = 1e-13
+        opts.poisson.precond = 3
+        opts.poisson.rtol = RTOL
+        opts.poisson.atol = 0.0
+        passes = []
+        for step in range(nsteps):
+            ctx.set_bdf(fo.bdf_alpha(step, 1.0), 0.25 / 8)
+            passes.append(ctx.step_ipcs(opts).krylov_iterations_poisson)
+            ctx.advance(0)
+        info = ctx.poisson_fast_diag_3d_info()
+        print("refine", refine, "passes", passes, "solves", info["solves"], "applications", info["applications"])
+        assert passes == [PASSES if refine else 1] * nsteps, passes
+        assert info["solves"] == nsteps and info["applications"] == (PASSES if refine else 1) * nsteps
+        fields[refine] = (ctx.get_state(nat.U1), ctx.get_state(nat.P_OLD))
+        ctx.close()
+    (ua, pa), (ub, pb) = fields[False], fields[True]
+    eu, ep = rel(ub, ua), rel(pb - pb.mean(), pa - pa.mean())
+    print("velocity", eu, "pressure", ep)
+    assert eu < 1e-10 and ep < 1e-10, (eu, ep)
 
 
 @pytest.mark.parametrize("n", [6, 10])

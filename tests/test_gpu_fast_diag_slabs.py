@@ -1,4 +1,4 @@
-"""Fast diagonalisation on partitioned 3D slabs (FastDiag3::apply_slab in csrc/fastdiag3d.hip,
+"""Fast diagonalisation on partitioned 3D slabs (FastDiag3::apply_slab in csrc/fastdiag.hip,
 nsfem_poisson_set_fast_diag_3d_planes, partition.*SlabPartition.attach_fast_diag), in-process thread ranks on one GPU:
 the slab solve against the one-rank formula on every rank's local planes, ghost planes included; the projection step
 of periodic slabs (one direct pass) and of closed-cavity slabs (CG preconditioned by the slab T^+) against a single
@@ -245,6 +245,75 @@ def test_periodic_slabs_direct_step_equals_the_single_context(n, size, relaxed):
         n, size, "relaxed" if relaxed else "exact", st_mg["exchanges"] / NSTEPS, st_fd["exchanges"] / NSTEPS,
         st_mg["allreduce_calls"] / NSTEPS, st_fd["allreduce_calls"] / NSTEPS))
     assert st_fd["exchanges"] < st_mg["exchanges"] and st_fd["allreduce_calls"] < st_mg["allreduce_calls"]
+
+
+def test_refinement_passes_on_periodic_slabs_equal_the_single_context():
+    """poisson_direct_step on two periodic slabs with perturbed factors (inv * (1 + DELTA) on every rank; constants
+    and derivation of test_gpu_fast_diag: SIX passes per step at rtol = 3e-11, atol = 0): the same pass count on every
+    rank as on the single context, and the same fields to 1e-10, as the strip counterpart
+    test_refinement_passes_on_strips_equal_the_single_context asks.  The target is rtol |r| with |r|^2 all-reduced
+    once: reducing it again in every pass would multiply it by the rank count each time and stop the slabs early."""
+    from fem_mesh import TaylorHoodDofMap, box_mesh, periodic_entity_map
+    from multigrid import attach_hierarchy
+    from test_gpu_fast_diag import DELTA, PASSES, RTOL
+    from test_gpu_fast_diag_3d import _TriplePeriodic
+    n, size = 8, 2
+    mesh = box_mesh(LO, HI, n, n, n)
+    domain = _TriplePeriodic((1.0, 1.0, 1.0)).domain
+    dm = TaylorHoodDofMap(mesh, periodic_map=periodic_entity_map(mesh, domain))
+    f = pf.factors_3d(*pf.box_lattice(mesh, dm))
+    assert f["exact"] and f["inv"].shape == (n, n, n)
+    f = dict(f, inv=f["inv"] * (1.0 + DELTA))
+
+    def opts(ctx):
+        o = _opts(ctx, True)
+        o.poisson.rtol = RTOL
+        o.poisson.atol = 0.0
+        return o
+
+    ctx0 = context(mesh, dm)
+    attach_hierarchy(ctx0, mesh, coarsest=2, periodic=(domain, dm.p1_vertex_node))
+    ctx0.poisson_set_fast_diag_3d(f)
+    _tg_start(ctx0, dm)
+    u_ref, p_ref, inf_ref, _, info0 = _steps(ctx0, opts(ctx0))
+    ctx0.close()
+    passes_ref = [i.krylov_iterations_poisson for i in inf_ref]
+    print("single context: passes", passes_ref, "applications", info0["applications"])
+    assert passes_ref == [PASSES] * NSTEPS
+    assert info0["solves"] == NSTEPS and info0["applications"] == PASSES * NSTEPS
+
+    parts = _parts(True, (n, n, n), size, coarsest=2)
+    group = nat.local_group_create(size)
+    ctxs = _contexts(parts, group)
+
+    def rank(r):
+        parts[r].attach(ctxs[r])
+        ctxs[r].poisson_set_fast_diag_3d(f, first_plane=int(parts[r].p1_global[0]) // (n * n))
+        _tg_start(ctxs[r], parts[r].dofmap)
+        return _steps(ctxs[r], opts(ctxs[r]))
+
+    out = _on_ranks(size, rank)
+    for c in ctxs:
+        c.close()
+    nat.local_group_destroy(group)
+    key = lambda X: [tuple(r) for r in (np.round(X * 4 * n).astype(np.int64) % (4 * n))]
+    ref2 = {kk: i for i, kk in enumerate(key(dm.p2_coords))}
+    ref1 = {kk: i for i, kk in enumerate(key(dm.p1_coords))}
+    u = np.full_like(u_ref, np.nan)
+    p = np.full_like(p_ref, np.nan)
+    for r, part in enumerate(parts):
+        ul, pl, infos, _, info = out[r]
+        own2, own1 = np.nonzero(part.p2_owned)[0], np.nonzero(part.p1_owned)[0]
+        u.reshape(-1, 3)[[ref2[kk] for kk in key(part.dofmap.p2_coords[own2])]] = ul.reshape(-1, 3)[own2]
+        p[[ref1[kk] for kk in key(part.dofmap.p1_coords[own1])]] = pl[own1]
+        passes = [i.krylov_iterations_poisson for i in infos]
+        print("rank", r, "passes", passes, "applications", info["applications"])
+        assert passes == passes_ref, (r, passes, passes_ref)
+        assert info["solves"] == NSTEPS and info["applications"] == PASSES * NSTEPS
+    assert np.isfinite(u).all() and np.isfinite(p).all()
+    eu, ep = rel(u, u_ref), rel(p - p.mean(), p_ref - p_ref.mean())
+    print("velocity", eu, "pressure", ep)
+    assert eu < 1e-10 and ep < 1e-10, (eu, ep)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
