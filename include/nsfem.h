@@ -693,6 +693,56 @@ int nsfem_derived_fields(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, i
                          unsigned quantity_mask, int center, double* out_host, int64_t out_len);
 int nsfem_derived_info(nsfem_ctx* ctx, int64_t out[4]);
 
+/* ---- wall quantities (csrc/wall.hip): everything evaluated on a set of facets -- measure, pressure force, viscous
+ * force, mass flux, mean temperature, conductive heat flux, torque -- per facet and summed per group of facets, from a
+ * facet set that stays resident on the device.  The facet side of the device post-processing; nsfem_boundary_force
+ * stays as the one-shot call (one summed traction of one list, lists uploaded at every call).
+ *
+ * nsfem_wall_set_facets: n_facets facets, facet f = the facet of cell facet_cell[f] opposite its local vertex
+ * facet_local[f], in group facet_group[f] (NULL: all in group 0) of n_groups >= 1 groups.  Every cell, local index and
+ * group id is validated on the host, the facets are sorted by group (stable), and the lists and the group offsets are
+ * uploaded ONCE (the permutation back to the input order stays on the host, where facet rows are un-permuted); an
+ * earlier set is replaced.  n_facets = 0 is valid.  Facets need not lie on the
+ * boundary: an interior facet gives the one-sided trace from facet_cell.
+ *
+ * nsfem_wall_compute: with n = the unit normal pointing out of facet_cell, G_ab = d_b u_a, gamma = sqrt(2 S:S) and
+ * Delta_K of nsfem_set_viscosity_law, a row of NW = 9 (2D) / 13 (3D) doubles per facet, in this order:
+ *   1          |f|
+ *   dim        int -p n
+ *   dim        int [ nu (G + sym G^T) + nu_x(gamma, Delta_K) (G + G^T) ] n     nu_x = 0 unless opts->use_law != 0 and a
+ *                                                                             law is set
+ *   1          int u.n
+ *   1          int T                                                           +0.0 with scalar_slot = -1
+ *   1          int -kappa grad T . n   (conductive heat LEAVING the fluid)     +0.0 with scalar_slot = -1
+ *   1 / 3      int (x - x0) x t, t the sum of the two traction integrands, x0 = opts->origin (2D: the z component)
+ * Facet rules: 2-point Gauss on edges, the 3 edge midpoints on faces -- exact for every integrand without a law; with
+ * a law the rule is part of the definition (as for nsfem_viscosity_cells).  out_groups [n_groups][NW]: the sums of
+ * the rows of every group; out_facets NULL or [n_facets][NW]: the rows in the INPUT order of nsfem_wall_set_facets.
+ * ONE launch of k_wall_facets<DIM, LAW> (one thread per facet) and ONE of k_wall_reduce<NW> (one workgroup of 256
+ * threads per group: thread t adds the rows t, t + 256, ... of its group in ascending resident order from +0.0, then
+ * a xor-shuffle tree within every wave, then the four wave sums in order), one copy of n_groups * NW doubles, one more
+ * of the rows only when out_facets is given.  No atomics: the same state gives the same bytes and the sums of a group
+ * do not depend on which other groups exist; an empty group gives +0.0.  No allocation after nsfem_wall_set_facets,
+ * no state slot and no buffer of the step written.
+ * nsfem_wall_components: NW of this context's mesh.
+ * nsfem_wall_info: out = {facets, groups, compute calls, facet-set uploads}.
+ * NSFEM_ERR_ARG, with a message, nothing launched and the counters unchanged: no facet set; null opts or out_groups;
+ * slots of the wrong kind; a scalar slot without nsfem_set_scalar or one that was never set or stepped (no storage yet:
+ * nothing is allocated here); non-finite nu, sym, kappa or origin; a cell, local
+ * index or group out of range; n_groups < 1; a context with a communicator (partitioned meshes keep
+ * nsfem_boundary_force: out of scope here on purpose). */
+typedef struct {
+  double nu, sym, kappa, origin[3];
+  int use_law;
+} nsfem_wall_opts;
+int nsfem_wall_set_facets(nsfem_ctx* ctx, int32_t n_facets, const int32_t* facet_cell, const int32_t* facet_local,
+                          const int32_t* facet_group /* NULL: all 0 */, int32_t n_groups);
+int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, int scalar_slot /* -1: none */,
+                       const nsfem_wall_opts* opts, double* out_groups /* [n_groups][NW] */,
+                       double* out_facets /* NULL or [n_facets][NW], INPUT order */);
+int nsfem_wall_components(nsfem_ctx* ctx, int* nw);
+int nsfem_wall_info(nsfem_ctx* ctx, int64_t out[4]);
+
 /* ---- measurement hooks (bench.py): time `reps` launches of the dominant SpMV
  * with HIP events on the context's stream; ms per launch returned ------------- */
 /* in-situ HIP-event timing of the finest-level smoothing launches of the velocity multigrid

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libnsfem_hip.so")
 OK, ERR_ARG, ERR_HIP, ERR_BREAKDOWN, ERR_NOT_CONVERGED, ERR_COMM = 0, -1, -2, -3, -4, -5
 U0, U1, U2, USTAR, P, P_OLD, BODY_FORCE, TRACTION, P2_OLD, CONV_N1, CONV_N2 = range(11)
 T0, T1, T2, T_SOURCE, TCONV_1, TCONV_2 = range(11, 17)       # transported P2 scalar (set_scalar / step_scalar_imex)
+N_SLOTS = 17                # NSFEM_N_SLOTS
 VELOCITY, PRESSURE, PRESSURE_PRECOND, SCALAR = 0, 1, 2, 3
 (OP_MASS_P2, OP_STIFF_P2, OP_STIFF_P1, OP_MASS_P1, OP_DIV, OP_GRAD, OP_DIVT,
  OP_MOMENTUM_JAC, OP_VISCOUS_EXTRA, OP_MOMENTUM_JAC_MF, OP_MOMENTUM_SMOOTHER,
@@ -58,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_stats_enable", "nsfem_stats_sample", "nsfem_stats_get", "nsfem_stats_set_groups", "nsfem_stats_profiles",
     "nsfem_stats_info", "nsfem_stats_weight",
     "nsfem_derived_components", "nsfem_derived_fields", "nsfem_derived_info",
+    "nsfem_wall_set_facets", "nsfem_wall_compute", "nsfem_wall_components", "nsfem_wall_info",
 )
 
 
@@ -79,6 +81,12 @@ class KernelTest(C.Structure):
                 ("xc", C.POINTER(C.c_double)), ("rf", C.POINTER(C.c_double)), ("b_formed", C.POINTER(C.c_double))] + \
                [(k, C.c_int32) for k in ("gh_lo", "gh_hi", "gh_zero", "tile_lines", "fixed", "lattice_tile_lines",
                                           "lattice_tx", "lattice_ty", "lattice_tiles", "lattice_fixed_shape")]
+
+
+class WallOpts(C.Structure):
+    """nsfem_wall_opts"""
+    _fields_ = [("nu", C.c_double), ("sym", C.c_double), ("kappa", C.c_double), ("origin", C.c_double * 3),
+                ("use_law", C.c_int)]
 
 
 class KrylovOpts(C.Structure):
@@ -243,6 +251,10 @@ def load_library(path=None):
         "nsfem_derived_components": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
         "nsfem_derived_fields": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, pd, i64]),
         "nsfem_derived_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_wall_set_facets": (C.c_int, [vp, i32, pi, pi, pi, i32]),
+        "nsfem_wall_compute": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(WallOpts), pd, pd]),
+        "nsfem_wall_components": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "nsfem_wall_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_poisson_solve": (C.c_int, [vp, pd, i64, pi, pd, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_profile_smoother": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
         "nsfem_profile_convection": (C.c_int, [vp, C.c_int, pd, C.POINTER(i64), C.POINTER(i64)]),
@@ -1119,6 +1131,64 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_derived_info(self._h, out))
         return dict(cell_launches=int(out[0]), gather_launches=int(out[1]), calls=int(out[2]), bytes=int(out[3]))
+
+    # -- wall quantities (csrc/wall.hip) ------------------------------------------------
+    def wall_components(self):
+        """NW: doubles per facet / group row of wall_compute (9 in 2D, 13 in 3D)"""
+        out = C.c_int()
+        self._check(self._lib.nsfem_wall_components(self._h, C.byref(out)))
+        return out.value
+
+    def wall_set_facets(self, facet_cell, facet_local, facet_group=None, n_groups=1):
+        """make a facet set resident (validated, sorted by group, uploaded once; replaces an earlier set): facet f =
+        the facet of cell ``facet_cell[f]`` opposite its local vertex ``facet_local[f]``, in group ``facet_group[f]``
+        (None: all in group 0)"""
+        fc = np.ascontiguousarray(facet_cell, dtype=np.int32).ravel()
+        fl = np.ascontiguousarray(facet_local, dtype=np.int32).ravel()
+        if fl.size != fc.size:
+            raise ValueError("facet_cell and facet_local differ in length")
+        fg = None
+        if facet_group is not None:
+            fg = np.ascontiguousarray(facet_group, dtype=np.int32).ravel()
+            if fg.size != fc.size:
+                raise ValueError("facet_cell and facet_group differ in length")
+        # whoever calls this owns the context's one facet set from here on: a wall_quantities.WallQuantities that made
+        # its set resident earlier sees that it has to do so again
+        self._active_wall_set = None
+        self._check(self._lib.nsfem_wall_set_facets(self._h, fc.size, _ip(fc), _ip(fl),
+                                                    _ip(fg) if fg is not None else None, int(n_groups)))
+        # sizes of the resident set and its output buffers, kept for wall_compute: no ABI round trip and no
+        # allocation per call there
+        nw = self.wall_components()
+        self._wall = dict(facets=int(fc.size), groups=int(n_groups), nw=nw, opts=WallOpts(),
+                          group_rows=np.zeros((int(n_groups), nw)), facet_rows=np.zeros((int(fc.size), nw)))
+
+    def wall_compute(self, nu, symmetric=1.0, kappa=0.0, origin=None, use_law=False, velocity_slot=U0,
+                     pressure_slot=P, scalar_slot=-1, facets=False):
+        """group rows [n_groups, NW] of the resident facet set -- with ``facets`` the pair (group rows, facet rows
+        [n_facets, NW] in the input order of wall_set_facets).  Row: |f|, int -p n [dim], int viscous traction [dim],
+        int u.n, int T, int -kappa grad T.n, int (x - origin) x traction [1 / 3] (include/nsfem.h)"""
+        w = getattr(self, "_wall", None)
+        if w is None:       # no resident set: the library refuses the call and says why
+            w = dict(facets=0, groups=0, nw=1, opts=WallOpts(), group_rows=np.zeros((1, 1)), facet_rows=np.zeros((0, 1)))
+        opts = w["opts"]
+        opts.nu, opts.sym, opts.kappa = float(nu), float(symmetric), float(kappa)
+        opts.origin[0] = opts.origin[1] = opts.origin[2] = 0.0
+        if origin is not None:
+            for d, v in enumerate(origin):
+                opts.origin[d] = float(v)
+        opts.use_law = 1 if use_law else 0
+        groups, rows = w["group_rows"], w["facet_rows"]
+        self._check(self._lib.nsfem_wall_compute(self._h, int(velocity_slot), int(pressure_slot), int(scalar_slot),
+                                                 C.byref(opts), _dp(groups), _dp(rows) if facets and rows.size else None))
+        # (copies: the buffers are reused by the next call)
+        return (groups.copy(), rows.copy()) if facets else groups.copy()
+
+    def wall_info(self):
+        """dict(facets, groups, computes, uploads = facet sets made resident so far)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_wall_info(self._h, out))
+        return dict(facets=int(out[0]), groups=int(out[1]), computes=int(out[2]), uploads=int(out[3]))
 
     def cfl_number(self, slot, step_size):
         out = C.c_double()

@@ -3675,6 +3675,125 @@ extern "C" int nsfem_derived_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_END(ctx)
 }
 
+// ------------------------------------------------------------------ wall quantities (wall.hip)
+static void wall_require_supported(nsfem_ctx* c) {
+  NSFEM_REQUIRE(!c->comm, "wall quantities: contexts with a communicator (partitioned meshes) are not supported -- "
+                          "use nsfem_boundary_force there");
+}
+
+// validates everything on the host first, then replaces the resident set: lists sorted by group (stable), group
+// offsets, and the buffers nsfem_wall_compute writes -- the only allocations of the wall calls; the permutation back to
+// the caller's order stays on the host, where the rows are un-permuted
+extern "C" int nsfem_wall_set_facets(nsfem_ctx* ctx, int32_t n_facets, const int32_t* facet_cell,
+                                     const int32_t* facet_local, const int32_t* facet_group, int32_t n_groups) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null argument");
+  wall_require_supported(ctx);
+  NSFEM_REQUIRE(n_facets >= 0, "wall quantities: n_facets < 0");
+  NSFEM_REQUIRE(n_groups >= 1, "wall quantities: n_groups < 1");
+  NSFEM_REQUIRE(n_facets == 0 || (facet_cell && facet_local), "null argument");
+  const int dim = ctx->mesh.dim, nw = wall_components(dim);
+  for (int32_t f = 0; f < n_facets; ++f) {
+    NSFEM_REQUIRE(facet_cell[f] >= 0 && facet_cell[f] < ctx->mesh.n_cells, "wall quantities: facet cell out of range");
+    NSFEM_REQUIRE(facet_local[f] >= 0 && facet_local[f] <= dim, "wall quantities: local facet index out of range");
+    if (facet_group)
+      NSFEM_REQUIRE(facet_group[f] >= 0 && facet_group[f] < n_groups, "wall quantities: facet group out of range");
+  }
+  // counting sort by group: stable, goff[g] .. goff[g + 1] = the resident facets of group g
+  std::vector<int32_t> goff((size_t)n_groups + 1, 0), perm((size_t)n_facets), cell((size_t)n_facets),
+      local((size_t)n_facets);
+  for (int32_t f = 0; f < n_facets; ++f) ++goff[(size_t)(facet_group ? facet_group[f] : 0) + 1];
+  for (int32_t g = 0; g < n_groups; ++g) goff[(size_t)g + 1] += goff[g];
+  {
+    std::vector<int32_t> next(goff.begin(), goff.end() - 1);
+    for (int32_t f = 0; f < n_facets; ++f) perm[(size_t)next[facet_group ? facet_group[f] : 0]++] = f;
+  }
+  for (int32_t k = 0; k < n_facets; ++k) {
+    cell[k] = facet_cell[perm[k]];
+    local[k] = facet_local[perm[k]];
+  }
+  nsfem_ctx::Wall& W = ctx->wall;
+  hipStream_t s = ctx->stream;
+  W.have_set = false;
+  W.fcell.upload(cell.data(), cell.size(), s);
+  W.flocal.upload(local.data(), local.size(), s);
+  W.goff.upload(goff.data(), goff.size(), s);
+  NSFEM_HIP(hipStreamSynchronize(s));   // the host vectors die with the call
+  if (W.rows.n != (size_t)n_facets * nw) W.rows.alloc((size_t)n_facets * nw);
+  if (W.sums.n != (size_t)n_groups * nw) W.sums.alloc((size_t)n_groups * nw);
+  W.h_perm.swap(perm);
+  W.h_rows.assign((size_t)n_facets * nw, 0.0);
+  W.n_facets = n_facets;
+  W.n_groups = n_groups;
+  W.have_set = true;
+  ++W.uploads;
+  API_END(ctx)
+}
+
+// every check comes before the first launch; reads the slots, writes the context's wall buffers only
+extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, int scalar_slot,
+                                  const nsfem_wall_opts* opts, double* out_groups, double* out_facets) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null argument");
+  wall_require_supported(ctx);
+  NSFEM_REQUIRE(opts && out_groups, "wall quantities: null opts or out_groups");
+  nsfem_ctx::Wall& W = ctx->wall;
+  NSFEM_REQUIRE(W.have_set, "wall quantities: no facet set (nsfem_wall_set_facets)");
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "wall quantities: velocity_slot is not a velocity slot");
+  NSFEM_REQUIRE(pressure_slot == NSFEM_P || pressure_slot == NSFEM_P_OLD || pressure_slot == NSFEM_P2_OLD,
+                "wall quantities: pressure_slot is not a pressure slot");
+  if (scalar_slot != -1) {
+    NSFEM_REQUIRE(scalar_slot == NSFEM_T0 || scalar_slot == NSFEM_T1 || scalar_slot == NSFEM_T2,
+                  "wall quantities: scalar_slot is not a level of the transported scalar");
+    NSFEM_REQUIRE(ctx->sc.configured, "wall quantities: a scalar slot without nsfem_set_scalar");
+    // (a level that was never set or stepped has no storage: allocating it here would write state)
+    NSFEM_REQUIRE(ctx->state[scalar_slot].p, "wall quantities: the scalar slot holds no data yet");
+  }
+  NSFEM_REQUIRE(std::isfinite(opts->nu) && std::isfinite(opts->sym) && std::isfinite(opts->kappa) &&
+                    std::isfinite(opts->origin[0]) && std::isfinite(opts->origin[1]) && std::isfinite(opts->origin[2]),
+                "wall quantities: non-finite nu, sym, kappa or origin");
+  const MeshDev& m = ctx->mesh;
+  const int nw = wall_components(m.dim);
+  WallParams wp;
+  wp.nu = opts->nu;
+  wp.sym = opts->sym;
+  wp.kappa = opts->kappa;
+  for (int d = 0; d < 3; ++d) wp.origin[d] = opts->origin[d];
+  wp.law = opts->use_law != 0 ? ctx->visc.law : 0;
+  for (int k = 0; k < 3; ++k) wp.law_p[k] = ctx->visc.p[k];
+  hipStream_t s = ctx->stream;
+  launch_wall_facets(s, m, W.n_facets, W.fcell.p, W.flocal.p, ctx->state[velocity_slot].p, ctx->state[pressure_slot].p,
+                     scalar_slot != -1 ? ctx->state[scalar_slot].p : nullptr, wp, W.rows.p);
+  launch_wall_reduce(s, m.dim, W.n_groups, W.goff.p, W.rows.p, W.sums.p);
+  ++W.computes;
+  NSFEM_HIP(hipMemcpyAsync(out_groups, W.sums.p, sizeof(double) * (size_t)W.n_groups * nw, hipMemcpyDeviceToHost, s));
+  if (out_facets && W.n_facets > 0)
+    NSFEM_HIP(hipMemcpyAsync(W.h_rows.data(), W.rows.p, sizeof(double) * W.h_rows.size(), hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  if (out_facets)
+    for (int32_t k = 0; k < W.n_facets; ++k)
+      std::memcpy(out_facets + (size_t)W.h_perm[k] * nw, W.h_rows.data() + (size_t)k * nw, sizeof(double) * nw);
+  API_END(ctx)
+}
+
+extern "C" int nsfem_wall_components(nsfem_ctx* ctx, int* nw) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && nw, "null argument");
+  *nw = wall_components(ctx->mesh.dim);
+  API_END(ctx)
+}
+
+extern "C" int nsfem_wall_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->wall.have_set ? ctx->wall.n_facets : 0;
+  out[1] = ctx->wall.have_set ? ctx->wall.n_groups : 0;
+  out[2] = ctx->wall.computes;
+  out[3] = ctx->wall.uploads;
+  API_END(ctx)
+}
+
 // ----------------------------------------------------------- operator access
 static const BlockMat* get_op(nsfem_ctx* c, int op, int* nv_apply) {
   *nv_apply = 1;

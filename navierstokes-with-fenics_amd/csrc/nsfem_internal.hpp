@@ -544,6 +544,20 @@ int64_t derived_work_doubles(const MeshDev& m, int center, int ncomp);
 // when the mask does not ask for their gradients
 const double* launch_derived_fields(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* T,
                                     unsigned mask, int center, int ncomp, double* work);
+// ---- wall quantities (wall.hip): NW = wall_components(dim) integrals per facet of a resident, group-sorted facet set
+// (k_wall_facets<DIM, LAW>) and their sums per group in a fixed order (k_wall_reduce<NW>); the row layout is in
+// include/nsfem.h (nsfem_wall_compute)
+inline int wall_components(int dim) { return dim == 2 ? 9 : 13; }
+struct WallParams {
+  double nu = 0.0, sym = 0.0, kappa = 0.0, origin[3] = {0.0, 0.0, 0.0};
+  int law = 0;                               // 0: constant viscosity; 1, 2: + nu_x of visc_law_nu<law>
+  double law_p[3] = {0.0, 0.0, 0.0};
+};
+// ONE launch: rows[f][NW] of the nf facets (fcell, flocal: device lists); T may be null (no scalar: +0.0 entries)
+void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
+                        const double* u, const double* p, const double* T, const WallParams& w, double* rows);
+// ONE launch: out[g][NW] = sum of the rows goff[g] <= f < goff[g + 1], one workgroup per group
+void launch_wall_reduce(hipStream_t s, int dim, int n_groups, const int32_t* goff, const double* rows, double* out);
 // diag extraction: d[(i,a)] = 1 / A_ii[a][a]  (mask rows -> 1)
 void launch_inv_diag(hipStream_t s, const BlockMat& A, int nv, const uint8_t* rowmask,
                      double* dinv);
@@ -1247,6 +1261,18 @@ struct nsfem_ctx {
     nsfem::DevBuf<double> work;
     int64_t cell_launches = 0, gather_launches = 0, calls = 0;
   } derived;
+  // nsfem_wall_set_facets / nsfem_wall_compute (wall.hip): the resident facet set, sorted by group (stable), its
+  // group offsets, the permutation back to the caller's order (host only), the buffers of the rows and of the group sums -- all the
+  // context's own, sized by nsfem_wall_set_facets -- and the counters of nsfem_wall_info
+  struct Wall {
+    bool have_set = false;
+    int32_t n_facets = 0, n_groups = 0;
+    nsfem::DevBuf<int32_t> fcell, flocal, goff;
+    nsfem::DevBuf<double> rows, sums;
+    std::vector<int32_t> h_perm;             // h_perm[k] = input index of the k-th resident facet
+    std::vector<double> h_rows;              // staging of the rows for the un-permuted copy
+    int64_t computes = 0, uploads = 0;
+  } wall;
   int64_t jac_lattice_launches = 0;   // applications of the matrix-free Jacobian through k_jac_lattice
   bool mf_active = false;           // the running step driver applies the Jacobian matrix-free
   int pressure_history = 0;         // IPCS: pressure levels shifted since the state was last set (0..2)

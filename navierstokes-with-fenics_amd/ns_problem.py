@@ -242,6 +242,31 @@ class ProblemBase:
         self.__dict__.setdefault("_flow_statistics", []).append(stats)
         return stats
 
+    def _add_wall_quantities(self, boundary_ids, origin=None, every=1, symmetric_gradient_factor=1.0):
+        """Register the wall quantities of the boundary parts ``boundary_ids`` (``wall_quantities.WallQuantities``: area,
+        pressure / viscous force, torque about ``origin``, mass flux, mean temperature and heat flux per boundary id):
+        ``solve_problem`` records them at the new time level after every ``every``-th ``solver.solve()``, directly
+        after the probes -- two device launches per record on a facet set made resident once.  Returns the instance
+        (bound to the solver once it exists); its ``times`` / ``series`` hold the records.  New; the reference's
+        drivers spell such integrals out as ``assemble(... * ds(id))``."""
+        from wall_quantities import WallQuantities
+        wall = WallQuantities(getattr(self, "_navier_stokes_solver", None), boundary_ids, origin=origin,
+                              symmetric_gradient_factor=symmetric_gradient_factor, every=every)
+        self.__dict__.setdefault("_wall_quantities", []).append(wall)
+        return wall
+
+    def _compute_wall_quantities(self, boundary_ids, origin=None, symmetric_gradient_factor=1.0):
+        """One-shot form of ``_add_wall_quantities``: ``{boundary_id: dict}`` of the current solution (stationary
+        problems as well).  The facet set of the same ids, origin and factor stays resident between calls."""
+        from wall_quantities import WallQuantities
+        solver = self._get_solver()
+        ids = (boundary_ids, ) if np.isscalar(boundary_ids) else tuple(boundary_ids)
+        key = (ids, None if origin is None else tuple(float(v) for v in origin), float(symmetric_gradient_factor))
+        cache = solver.__dict__.setdefault("_wall_one_shot", {})     # kept on the solver: it lives as long as its context
+        if key not in cache:
+            cache[key] = WallQuantities(solver, ids, origin=origin, symmetric_gradient_factor=symmetric_gradient_factor)
+        return cache[key].compute()
+
     def _compute_stream_potential(self):
         """Velocity potential phi (the reference's "stream potential", :105-176): P1 solution of
         (grad phi, grad psi) = (div u, psi) - sum over the remaining boundaries of (n . u, psi),
@@ -499,7 +524,7 @@ class InstationaryProblem(ProblemBase):
                 setattr(solver, key, value)
         self._hand_over_to_solver(solver, ("coefficients", "force", "periodic", "rotation", "bcs", "initial"))
         for registered in getattr(self, "_tracer_clouds", []) + getattr(self, "_point_probes", []) + \
-                getattr(self, "_flow_statistics", []):
+                getattr(self, "_flow_statistics", []) + getattr(self, "_wall_quantities", []):
             registered.bind(solver)
         self._write_xdmf_file(current_time=0.0)
         print("Solving problem until time = {:0.2f}".format(self._time_stepping.end_time))
@@ -521,6 +546,8 @@ class InstationaryProblem(ProblemBase):
                 cloud.advect()
             for probes in getattr(self, "_point_probes", ()):
                 probes.record(ts.next_time)
+            for wall in getattr(self, "_wall_quantities", ()):
+                wall.record_step(ts.next_time)
             for stats in getattr(self, "_flow_statistics", ()):
                 stats.sample_step(ts.next_time, ts.get_next_step_size())
             if self._postprocessing_frequency > 0 and \
