@@ -427,8 +427,8 @@ int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info*
  * K is the traction-form stiffness); projection and velocity correction as nsfem_step_ipcs.  c_c N(u1) is kept in
  * NSFEM_CONV_N1, nsfem_advance moves it to NSFEM_CONV_N2 where the next step reads it as c_c N(u2) (recomputed only
  * after NSFEM_U2 / NSFEM_CONV_N2 were set by hand or the convective form / coefficient changed).
- * info->newton_iterations = 0, krylov_iterations_momentum = the CG count.  Rotating frames and partitioned meshes:
- * NSFEM_ERR_ARG.  3D meshes, inexact dictionaries, traction-form viscosity: the generic right-hand-side path. */
+ * info->newton_iterations = 0, krylov_iterations_momentum = the CG count.  Rotating frames: NSFEM_ERR_ARG unless
+ * nsfem_set_imex_rotation(1) was called.  3D meshes, inexact dictionaries, traction-form viscosity: the generic right-hand-side path. */
 int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info);
 /* How the right-hand side of the last nsfem_step_imex was formed: out[0] = 1 generic path (products, element kernel,
  * node gather, vector updates), 2 one launch of k_jac_lattice's right-hand-side mode (2D lattice meshes whose stencil
@@ -439,6 +439,21 @@ int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info
  * rhs and conv_n1 (c_c N(u1), may be null) are host arrays of dim * n_p2 doubles. */
 int nsfem_imex_info(nsfem_ctx* ctx, int64_t out[4]);
 int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, double* rhs, double* conv_n1);
+/* Rotating frames in the IMEX calls (nsfem_step_imex, nsfem_imex_rhs, nsfem_step_scalar_imex): opt-in.
+ * treatment 0: rotating frames are refused by the IMEX calls (default, as before).
+ * treatment 1: Coriolis term extrapolated with the convective term, Euler term in the step-constant vector: the stored
+ *   explicit vector is N(u) = c_c conv(u) + V(u) + R(u), R(u) = M (2 c_cor Omega x u) (2D: 2 c_cor omega M (-u_y, u_x)),
+ *   formed by the convection element kernel itself (no launch, no pass over memory and no halo exchange of its own;
+ *   on uniform 2D lattices inside the one-launch right-hand side), and c_e M (dOmega/dt x x) with the dOmega/dt last
+ *   given to nsfem_set_angular_velocity joins g.  Matrix, CG solve, projection and correction are unchanged.
+ * omega_n / omega_nm1: angular velocity at t^n / t^(n-1) (1 double in 2D, 3 in 3D);
+ * NULL = the value of nsfem_set_angular_velocity (steady frame).  The stored N(u2) is reused only if the 2 c_cor Omega
+ * it was formed with equals the one now given for t^(n-1) bit for bit.  With zero rotation the non-rotating kernels
+ * run: every output is that of a context that never made the call. */
+int nsfem_set_imex_rotation(nsfem_ctx* ctx, int treatment, const double* omega_n, const double* omega_nm1);
+int nsfem_imex_rotation_info(nsfem_ctx* ctx, int64_t out[4]);
+/* out[0] treatment; out[1] right-hand sides formed with rotation folded in;
+   out[2] recomputations of the stored N(u2); out[3] 0 */
 /* ---- IMEX transport of a P2 scalar T on the velocity nodes with Boussinesq buoyancy (new; the reference's gravity
  * driven cases prescribe their body force).  diffusivity kappa >= 0; buoyancy: dim entries b (NULL = 0); convective
  * form 0 standard C_ij = int (u . grad phi_j) phi_i, 1 skew-symmetric 1/2 (C - C^T).  With a nonzero b,

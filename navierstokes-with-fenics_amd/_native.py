@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_set_fast_diag_3d_planes", "nsfem_poisson_fast_diag_3d_info",
     "nsfem_operator_diagonal",
     "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
+    "nsfem_set_imex_rotation", "nsfem_imex_rotation_info",
     "nsfem_volume_functionals",
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
@@ -191,6 +192,8 @@ def load_library(path=None):
         "nsfem_step_imex": (C.c_int, [vp, C.POINTER(StepOpts), C.POINTER(StepInfo)]),
         "nsfem_imex_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_imex_rhs": (C.c_int, [vp, C.c_int, C.c_int, pd, pd]),
+        "nsfem_set_imex_rotation": (C.c_int, [vp, C.c_int, pd, pd]),
+        "nsfem_imex_rotation_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_dirichlet": (C.c_int, [vp, C.c_int, i32, pi, pd]),
         "nsfem_set_scalar": (C.c_int, [vp, dbl, pd, C.c_int]),
         "nsfem_step_scalar_imex": (C.c_int, [vp, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
@@ -477,6 +480,28 @@ class NsfemContext:
         self._check(self._lib.nsfem_imex_rhs(self._h, {"generic": 1, "lattice-kernel": 2}[path], int(convective_form),
                                              _dp(rhs), _dp(n1)))
         return rhs, n1
+
+    def set_imex_rotation(self, treatment, omega_n=None, omega_nm1=None):
+        """rotating frames in the IMEX calls: treatment 0 refuse (default), 1 Coriolis term extrapolated with the
+        convective term and Euler term in the step-constant vector.  omega_n / omega_nm1: the angular velocity at
+        t^n / t^(n-1) (a number in 2D, 3 numbers in 3D); None = the value of set_angular_velocity (steady frame)"""
+        ptr = []
+        for w in (omega_n, omega_nm1):
+            if w is None:
+                ptr.append(None)
+                continue
+            w = np.ascontiguousarray(np.atleast_1d(w), dtype=np.float64)
+            assert w.shape == ((1, ) if self.dim == 2 else (3, ))
+            ptr.append(w)
+        self._check(self._lib.nsfem_set_imex_rotation(self._h, int(treatment), *[None if w is None else _dp(w)
+                                                                                 for w in ptr]))
+
+    def imex_rotation_info(self):
+        """dict(treatment, rotating_rhs = right-hand sides formed with the rotation folded in, recomputed = times
+        the stored N(u2) was formed again because it belonged to another angular velocity)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_imex_rotation_info(self._h, out))
+        return dict(treatment=int(out[0]), rotating_rhs=int(out[1]), recomputed=int(out[2]))
 
     # -- IMEX scalar transport with Boussinesq buoyancy ----------------------------------
     def set_scalar(self, diffusivity, buoyancy=None, convective_form=0):

@@ -5,6 +5,7 @@ Restates ``EquationCoefficientHandler`` of the reference
 pressure 1, viscous 1/Re (or Ek/Ro, Ek, 1 in rotating frames), body force 1/Fr^2,
 Coriolis/Euler 1/Ro, 1/(Ek Re) or 1.  Pure host arithmetic.
 """
+import copy
 import math
 
 
@@ -167,6 +168,13 @@ class AngularVelocityVector:
         self._current_time = current_time
         self._angular_velocity.set_time(self._current_time)
         self._modify_time()
+
+    def value_at(self, time):
+        """the angular velocity at an arbitrary time (new; the IMEX solvers extrapolate the Coriolis term from the
+        old time levels).  The vector's own time does not move."""
+        function = copy.copy(self._angular_velocity)
+        function._current_time = float(time)
+        return self._convert(function.value())
 
     @property
     def derivative(self):

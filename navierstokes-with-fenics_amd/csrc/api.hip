@@ -820,6 +820,27 @@ static void ensure_div_dicts(nsfem_ctx* ctx) {
   }
 }
 
+// v += c_e (d Omega/dt) x x, nodal: the Euler acceleration before the mass product (ns_solver_base.py:193-211)
+static void euler_add(nsfem_ctx* c, double* v) {
+  hipStream_t s = c->stream;
+  const int64_t nv = nvel(c);
+  NSFEM_REQUIRE(std::isfinite(c->coef[5]), "angular acceleration set but euler_term coefficient is None");
+  if (!c->rot_field.p) {
+    c->rot_field.alloc((size_t)nv);
+    if (c->mesh.dim == 2) launch_rot_field(s, c->mesh, c->rot_field.p);       // e_z x x
+    else launch_coord_field_3d(s, c->mesh, c->rot_field.p);                    // x
+  }
+  if (c->mesh.dim == 2) {
+    launch_axpby(s, nv, 1.0, v, c->coef[5] * c->omega_dot, c->rot_field.p, v);
+  } else {
+    if (!c->rot_tmp.p) c->rot_tmp.alloc((size_t)nv);
+    const double a[3] = {c->coef[5] * c->omega_dot3[0], c->coef[5] * c->omega_dot3[1],
+                         c->coef[5] * c->omega_dot3[2]};
+    launch_cross3(s, c->mesh.n_p2, a, c->rot_field.p, c->rot_tmp.p);
+    launch_axpby(s, nv, 1.0, v, 1.0, c->rot_tmp.p, v);
+  }
+}
+
 // time-step constant part of the momentum residual:
 //   g = M (a1 u1 + a2 u2) / k - c_p (p_old, div w) - c_b M f + traction
 static void momentum_begin_step(nsfem_ctx* c, bool with_old_pressure = true) {
@@ -835,23 +856,7 @@ static void momentum_begin_step(nsfem_ctx* c, bool with_old_pressure = true) {
   } else {
     launch_axpby(s, nv, a1, c->state[NSFEM_U1].p, a2, c->state[NSFEM_U2].p, c->tmp_v.p);
   }
-  if (euler_active(c)) {      // Euler acceleration  c_e (d Omega/dt) x x  (ns_solver_base.py:193-211)
-    NSFEM_REQUIRE(std::isfinite(c->coef[5]), "angular acceleration set but euler_term coefficient is None");
-    if (!c->rot_field.p) {
-      c->rot_field.alloc((size_t)nv);
-      if (c->mesh.dim == 2) launch_rot_field(s, c->mesh, c->rot_field.p);       // e_z x x
-      else launch_coord_field_3d(s, c->mesh, c->rot_field.p);                    // x
-    }
-    if (c->mesh.dim == 2) {
-      launch_axpby(s, nv, 1.0, c->tmp_v.p, c->coef[5] * c->omega_dot, c->rot_field.p, c->tmp_v.p);
-    } else {
-      if (!c->rot_tmp.p) c->rot_tmp.alloc((size_t)nv);
-      const double a[3] = {c->coef[5] * c->omega_dot3[0], c->coef[5] * c->omega_dot3[1],
-                           c->coef[5] * c->omega_dot3[2]};
-      launch_cross3(s, c->mesh.n_p2, a, c->rot_field.p, c->rot_tmp.p);
-      launch_axpby(s, nv, 1.0, c->tmp_v.p, 1.0, c->rot_tmp.p, c->tmp_v.p);
-    }
-  }
+  if (euler_active(c)) euler_add(c, c->tmp_v.p);
   launch_spmv(s, c->M2, c->mesh.dim, c->tmp_v.p, c->gconst.p, nullptr, MASK_NONE);
   if (with_old_pressure)   // IPCS: - c_p (p_old, div w); the monolithic scheme keeps p unknown
     launch_spmv_axpy(s, c->DT, 1, -c->coef[1], c->state[NSFEM_P_OLD].p, c->gconst.p, nullptr);
@@ -880,7 +885,7 @@ static void fill_linop(nsfem_ctx* c, LinOp& op, bool velocity) {
   op.n_global = velocity ? 2 * c->n_p2_global : c->n_p1_global;
 }
 
-static int jacobian_path(nsfem_ctx* c);
+static int jacobian_path(nsfem_ctx* c, bool explicit_rotation = false);
 static void momentum_residual_raw(nsfem_ctx* c, const double* u, double* out) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c);
@@ -941,13 +946,15 @@ static void momentum_jacobian(nsfem_ctx* c, int vel_slot = NSFEM_USTAR) {
 // Partitioned strips (round 4): the local mesh of a rank is a lattice of its own (own cell rows + the ghost row), so
 // path 2 runs there as well -- after ONE halo exchange of the input; rows of ghost nodes come out as zeros (mask
 // value 2).  Path 1 stays single-context (its node-sorted buffer has no interior / halo split).
-static int jacobian_path(nsfem_ctx* c) {
+// explicit_rotation (the IMEX right-hand side): a rotating frame does not enter the operator, the lattice path stays
+static int jacobian_path(nsfem_ctx* c, bool explicit_rotation) {
   if (c->mesh.dim != 2 || cc_of(c) == 0.0 || !c->L.dict_ready) return 0;
   if (!c->mesh.cl.tried && c->L.dict && c->L.dict->lat_w > 0) {
     build_cell_lattice(c->h_p2map.data(), c->mesh.n_cells, c->L.dict->lat_w, c->L.dict->lat_h, c->mesh.cl);
     check_uniform_geometry(c->stream, c->mesh);
   }
-  if (!c->traction_form && coriolis_gamma(c) == 0.0 && c->mask_v.p && jacobian_lattice_available(c->mesh, c->L))
+  if (!c->traction_form && (explicit_rotation || coriolis_gamma(c) == 0.0) && c->mask_v.p &&
+      jacobian_lattice_available(c->mesh, c->L))
     return 2;
   return c->distributed() ? 0 : 1;
 }
@@ -2289,7 +2296,9 @@ static void imex_build_ops(nsfem_ctx* c) {
   c->imex_ops_dirty = false;
 }
 
-// step-constant part of the right-hand side:  g = - c_p D^T p_old - c_b M f + traction  (momentum_begin_step's signs)
+// step-constant part of the right-hand side:  g = - c_p D^T p_old + M (- c_b f + c_e dOmega/dt x x) + traction
+// (momentum_begin_step's signs; the Euler term only with nsfem_set_imex_rotation(1), from the value last given to
+// nsfem_set_angular_velocity -- the convention of the body-force slot)
 static void imex_begin_step(nsfem_ctx* c) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c);
@@ -2303,9 +2312,15 @@ static void imex_begin_step(nsfem_ctx* c) {
     launch_buoyancy_force(s, c->mesh, f, c->state[NSFEM_T0].p, c->sc.b, c->sc.f_eff.p);
     f = c->sc.f_eff.p;
   }
-  if (f) {
-    NSFEM_REQUIRE(std::isfinite(c->coef[3]), "body force set but body_force_term coefficient is None");
-    launch_axpby(s, nv, -c->coef[3], f, 0.0, f, c->tmp_v.p);
+  const bool euler = euler_active(c);
+  if (f || euler) {
+    if (f) {
+      NSFEM_REQUIRE(std::isfinite(c->coef[3]), "body force set but body_force_term coefficient is None");
+      launch_axpby(s, nv, -c->coef[3], f, 0.0, f, c->tmp_v.p);
+    } else {
+      c->tmp_v.zero(s);
+    }
+    if (euler) euler_add(c, c->tmp_v.p);
     launch_spmv(s, c->M2, c->mesh.dim, c->tmp_v.p, c->gconst.p, nullptr, MASK_NONE);
   } else {
     c->gconst.zero(s);
@@ -2320,7 +2335,7 @@ static void imex_begin_step(nsfem_ctx* c) {
 // the overlap mode is on, and nsfem_imex_rhs(path 2) must fail everywhere or nowhere --, so the ranks' own answers
 // are reduced ONCE (minimum), when the operators are built or something the answer depends on was set, and kept
 static bool imex_lattice_local(nsfem_ctx* c) {
-  return jacobian_path(c) == 2 && imex_rhs_lattice_available(c->mesh, c->L1, c->L2);
+  return jacobian_path(c, true) == 2 && imex_rhs_lattice_available(c->mesh, c->L1, c->L2);
 }
 static void imex_agree_on_lattice(nsfem_ctx* c) {
   if (!c->distributed() || c->imex_lattice_agreed >= 0) return;
@@ -2362,7 +2377,10 @@ static bool imex_exchange_stale_levels(nsfem_ctx* c) {
 // or error.  The generic sequence below DEFINES the summation order; k_jac_lattice<FORM, 3> reproduces it.
 // Partitioned meshes: ONE halo exchange (u1; `u1_travelled`: imex_exchange_stale_levels has sent it with u2), rows of
 // ghost nodes come out as zeros in rhs and n1 on both paths, the arithmetic on owned rows is the single context's.
-static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double* rhs, bool u1_travelled = false) {
+// gam (null: no rotation): 2 c_cor Omega(t^n); the element kernel of either path adds M (gam x u1) to n1 -- no launch
+// and no exchange of its own.
+static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double* rhs, bool u1_travelled = false,
+                    const double* gam = nullptr) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c);
   const double cc = cc_of(c);
@@ -2376,7 +2394,7 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
     const uint8_t* gm = dist ? c->mask_v.p : nullptr;
     auto launch = [&](int phase) {
       return launch_imex_rhs_lattice(s, c->mesh, c->L1, c->L2, u1, u2, c->gconst.p, cc, c->conv_form, b0, b1, n2, n1,
-                                     rhs, gm, phase, c->p2_gh_lo, c->p2_gh_hi);
+                                     rhs, gm, phase, c->p2_gh_lo, c->p2_gh_hi, gam ? gam[0] : 0.0);
     };
     if (need_u1) {
       // the tile rows that read no ghost line run under the exchange when the overlap mode is on and the strip is
@@ -2414,7 +2432,7 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
   }
   launch_axpby(s, nv, 1.0, rhs, 1.0, c->gconst.p, rhs);
   NSFEM_HIP(hipMemsetAsync(n1, 0, sizeof(double) * nv, s));
-  if (cc != 0.0) launch_convection_residual(s, c->mesh, u1, cc, n1, c->conv_form);
+  if (cc != 0.0 || gam) launch_convection_residual(s, c->mesh, u1, cc, n1, c->conv_form, gam);
   launch_imex_combine(s, nv, rhs, n1, n2, b0, b1, rhs);
   if (dist && c->ghost_v.p) {
     launch_zero_ghost(s, nv, c->mask_v.p, rhs);
@@ -2440,8 +2458,25 @@ static void imex_require_supported(nsfem_ctx* c) {
   NSFEM_REQUIRE(c->imex_active, "nsfem_set_imex has not been called");
   NSFEM_REQUIRE(c->visc.law == 0 || !c->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
-  NSFEM_REQUIRE(!coriolis_active(c) && !euler_active(c),
+  NSFEM_REQUIRE(c->imex_rot.treatment == 1 || (!coriolis_active(c) && !euler_active(c)),
                 "IMEX pressure correction: rotating frames (Coriolis / Euler terms) are not supported");
+}
+
+// 2 c_cor Omega at the old level `lev` (0: t^n, 1: t^(n-1)) -> gam[3] (2D: gam[0]); false: no rotation at that level,
+// the non-rotating kernels run
+static bool imex_rotation_gamma(const nsfem_ctx* c, int lev, double gam[3]) {
+  gam[0] = gam[1] = gam[2] = 0.0;
+  if (c->imex_rot.treatment != 1) return false;
+  const int nc = c->mesh.dim == 2 ? 1 : 3;
+  double w[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; a < nc; ++a)
+    w[a] = c->imex_rot.given[lev] ? c->imex_rot.w[lev][a] : (c->mesh.dim == 2 ? c->omega : c->omega3[a]);
+  if (w[0] == 0.0 && w[1] == 0.0 && w[2] == 0.0) return false;      // (gam stays +0.0: the stored vector's key)
+  NSFEM_REQUIRE(std::isfinite(c->coef[4]), "angular velocity set but coriolis_term coefficient is None");
+  for (int a = 0; a < nc; ++a) gam[a] = 2.0 * c->coef[4] * w[a];
+  if (gam[0] != 0.0 || gam[1] != 0.0 || gam[2] != 0.0) return true;
+  gam[0] = gam[1] = gam[2] = 0.0;
+  return false;
 }
 
 extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
@@ -2458,16 +2493,22 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   ensure_imex_ops(ctx);
   imex_begin_step(ctx);
   const bool u1_travelled = imex_exchange_stale_levels(ctx);
+  double gam1[3], gam2[3];
+  const bool rot1 = imex_rotation_gamma(ctx, 0, gam1), rot2 = imex_rotation_gamma(ctx, 1, gam2);
   const double* n2 = nullptr;
   if (ctx->imex_beta[1] != 0.0) {
     // c_c N(u2): what the previous step stored, unless the level, the form or the coefficient changed under it
+    // (rotating frame: nor the 2 c_cor Omega(t^(n-1)) it was formed with, bit for bit)
+    const bool same_rot = std::memcmp(ctx->conv_n_gam, gam2, sizeof(gam2)) == 0;
     const bool stored = ctx->conv_n2_valid && (ctx->conv_n_form == -2 ||
                                                (ctx->conv_n_form == ctx->conv_form && ctx->conv_n_cc == cc &&
-                                                ctx->conv_n_visc == ctx->visc.epoch));
+                                                ctx->conv_n_visc == ctx->visc.epoch && same_rot));
     if (!stored) {
       ctx->state[NSFEM_CONV_N2].zero(s);
-      if (cc != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc, ctx->state[NSFEM_CONV_N2].p,
-                                                ctx->conv_form);
+      if (cc != 0.0 || rot2)
+        launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc, ctx->state[NSFEM_CONV_N2].p,
+                                   ctx->conv_form, rot2 ? gam2 : nullptr);
+      if (ctx->imex_rot.treatment == 1 && ctx->conv_n2_valid) ++ctx->imex_rot.recomputed;
       if (ctx->visc.law != 0) {
         viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, ctx->state[NSFEM_CONV_N2].p, nullptr);
         ++ctx->visc.recomputed;
@@ -2477,8 +2518,11 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     }
     n2 = ctx->state[NSFEM_CONV_N2].p;
   }
-  ctx->imex_last_path = imex_rhs(ctx, 0, n2, ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p, u1_travelled);
+  ctx->imex_last_path = imex_rhs(ctx, 0, n2, ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p, u1_travelled,
+                                 rot1 ? gam1 : nullptr);
   ++(ctx->imex_last_path == 2 ? ctx->imex_lattice_rhs : ctx->imex_generic_rhs);
+  if (rot1) ++ctx->imex_rot.rhs;
+  std::memcpy(ctx->conv_n_gam, gam1, sizeof(gam1));
   if (ctx->visc.law != 0)
     viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
   ctx->conv_n1_fresh = true;
@@ -2563,17 +2607,51 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
   NSFEM_REQUIRE(path != 2 || imex_lattice_ok(ctx),
                 "one-launch IMEX right-hand side: not available on this mesh / these settings");
   const bool u1_travelled = imex_exchange_stale_levels(ctx);
+  double gam1[3], gam2[3];
+  const bool rot1 = imex_rotation_gamma(ctx, 0, gam1), rot2 = imex_rotation_gamma(ctx, 1, gam2);
   if (ctx->imex_beta[1] != 0.0) {
     n2 = ctx->kw.z.p;
     NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nv, s));
-    if (cc_of(ctx) != 0.0) launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form);
+    if (cc_of(ctx) != 0.0 || rot2)
+      launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form,
+                                 rot2 ? gam2 : nullptr);
     if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, n2, nullptr);
   }
-  imex_rhs(ctx, path, n2, n1, out, u1_travelled);
+  imex_rhs(ctx, path, n2, n1, out, u1_travelled, rot1 ? gam1 : nullptr);
+  if (rot1) ++ctx->imex_rot.rhs;
   if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], n1, out);
   NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+// rotating frame in the IMEX calls: opt-in (the default refuses, imex_require_supported)
+extern "C" int nsfem_set_imex_rotation(nsfem_ctx* ctx, int treatment, const double* omega_n, const double* omega_nm1) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(treatment == 0 || treatment == 1, "IMEX rotation: treatment 0 (refuse) or 1 (explicit Coriolis term)");
+  nsfem_ctx::ImexRotation& r = ctx->imex_rot;
+  const int nc = ctx->mesh.dim == 2 ? 1 : 3;
+  const double* w[2] = {omega_n, omega_nm1};
+  for (int lev = 0; lev < 2; ++lev)
+    for (int a = 0; a < nc && w[lev]; ++a)
+      NSFEM_REQUIRE(std::isfinite(w[lev][a]), "non-finite angular velocity");
+  r.treatment = treatment;
+  for (int lev = 0; lev < 2; ++lev) {
+    r.given[lev] = treatment == 1 && w[lev] != nullptr;
+    for (int a = 0; a < 3; ++a) r.w[lev][a] = r.given[lev] && a < nc ? w[lev][a] : 0.0;
+  }
+  API_END(ctx)
+}
+
+extern "C" int nsfem_imex_rotation_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->imex_rot.treatment;
+  out[1] = ctx->imex_rot.rhs;
+  out[2] = ctx->imex_rot.recomputed;
+  out[3] = 0;
   API_END(ctx)
 }
 

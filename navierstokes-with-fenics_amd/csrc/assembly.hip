@@ -436,13 +436,18 @@ struct CellGrad {
   }
   __device__ __forceinline__ double wdet(int q) const { return c_q.w[q] * g.adet; }
 };
-template <int FORM, int LIN, class G>
+// ROT (residual mode only): the explicit Coriolis vector of the IMEX step joins the element vector, gam = 2 c_cor omega:
+//   r_(i,.) += wdet(q) phi_i gam (e_z x u_q),   e_z x u = (-u_y, u_x)
+// weighted by the quadrature weight alone, not by cc.  phi_i phi_j has degree 4 and the rule is exact to degree 5: the
+// node sums are M (gam e_z x u) to rounding.
+template <int FORM, int LIN, bool ROT, class G>
 __device__ __forceinline__ void conv_cell_eval_g(const G& gr, const double* ux, const double* uy,
                                                  const double* wx, const double* wy, double cc,
-                                                 double* rx, double* ry) {
+                                                 double* rx, double* ry, double gam = 0.0) {
   // contraction inside statements only (not across them, which depends on the surrounding kernel): the two kernels
   // that inline this function produce the same element vectors bit for bit
 #pragma clang fp contract(on)
+  static_assert(!ROT || LIN == 0, "the rotation term belongs to the residual mode");
 #pragma unroll
   for (int i = 0; i < 6; ++i) rx[i] = ry[i] = 0.0;
   for (int q = 0; q < 7; ++q) {
@@ -529,22 +534,34 @@ __device__ __forceinline__ void conv_cell_eval_g(const G& gr, const double* ux, 
         }
       }
     }
+    if (ROT) {
+      // (statements of their own: the contraction rule above keeps the two inlining kernels bit-equal)
+      const double wr = gr.wdet(q);
+      const double cx = -gam * uqy;
+      const double cy = gam * uqx;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const double rpi = wr * c_q.phi2[q][i];
+        rx[i] += rpi * cx;
+        ry[i] += rpi * cy;
+      }
+    }
   }
 }
-template <int FORM, int LIN>
+template <int FORM, int LIN, bool ROT = false>
 __device__ __forceinline__ void conv_cell_eval(const CellGeo& g, const double* ux, const double* uy,
                                                const double* wx, const double* wy, double cc,
-                                               double* rx, double* ry) {
-  conv_cell_eval_g<FORM, LIN>(CellGrad{g}, ux, uy, wx, wy, cc, rx, ry);
+                                               double* rx, double* ry, double gam = 0.0) {
+  conv_cell_eval_g<FORM, LIN, ROT>(CellGrad{g}, ux, uy, wx, wy, cc, rx, ry, gam);
 }
 
-template <int FORM, int LIN>
+template <int FORM, int LIN, bool ROT = false>
 __global__ __launch_bounds__(256) void k_conv_cell(int nc, const double* __restrict__ vx,
                                                    const int32_t* __restrict__ p2,
                                                    const double* __restrict__ u,
                                                    const double* __restrict__ v, double cc,
                                                    const int32_t* __restrict__ ndst,
-                                                   double* __restrict__ rbuf) {
+                                                   double* __restrict__ rbuf, double gam) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const CellGeo g = load_geo(vx, nc, c);
@@ -562,7 +579,7 @@ __global__ __launch_bounds__(256) void k_conv_cell(int nc, const double* __restr
     }
   }
   double rx[6], ry[6];
-  conv_cell_eval<FORM, LIN>(g, ux, uy, wx, wy, cc, rx, ry);
+  conv_cell_eval<FORM, LIN, ROT>(g, ux, uy, wx, wy, cc, rx, ry, gam);
   // node-sorted element buffer: entry (c, i) lands inside the contiguous run of its node
   double2* out = reinterpret_cast<double2*>(rbuf);
 #pragma unroll
@@ -712,12 +729,13 @@ void launch_convection_jacobian(hipStream_t s, const MeshDev& m, const Pattern& 
                      p22.cptr.p, p22.cidx.p, m.ebuf.p, L, E, cvE, J);
   NSFEM_HIP(hipGetLastError());
 }
-template <int LIN>
+template <int LIN, bool ROT = false>
 static void launch_conv_cell(hipStream_t s, const MeshDev& m, const double* u, const double* v,
-                             double cc, int form) {
+                             double cc, int form, double gam = 0.0) {
   const dim3 grid(grid_for(m.n_cells)), block(kBlock);
 #define NSFEM_CC(F) \
-  hipLaunchKernelGGL((k_conv_cell<F, LIN>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, v, cc, m.ndst.p, m.rbuf.p)
+  hipLaunchKernelGGL((k_conv_cell<F, LIN, ROT>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, v, cc, m.ndst.p, \
+                     m.rbuf.p, gam)
   switch (form) {
     case 0: NSFEM_CC(0); break;
     case 1: NSFEM_CC(1); break;
@@ -730,9 +748,10 @@ static void launch_conv_cell(hipStream_t s, const MeshDev& m, const double* u, c
 }
 
 void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u, double cc,
-                                double* b, int form) {
-  if (m.dim == 3) return convection_residual_3d(s, m, u, cc, b, form);
-  launch_conv_cell<0>(s, m, u, nullptr, cc, form);
+                                double* b, int form, const double* gam) {
+  if (m.dim == 3) return convection_residual_3d(s, m, u, cc, b, form, gam);
+  if (gam && gam[0] != 0.0) launch_conv_cell<0, true>(s, m, u, nullptr, cc, form, gam[0]);
+  else launch_conv_cell<0>(s, m, u, nullptr, cc, form);
   hipLaunchKernelGGL(k_res_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p,
                      m.rbuf.p, (const uint8_t*)nullptr, b);
   NSFEM_HIP(hipGetLastError());
@@ -1045,6 +1064,9 @@ void launch_imex_combine(hipStream_t s, int64_t n, const double* t, const double
 // mask is read as in the Jacobian action; on the rows of ghost nodes (mask value 2) the partial sums are dropped and
 // BOTH outputs are written as +0.0 -- the right-hand side and the stored c_c conv(u1) (no owned row ever reads the
 // latter: n2 is read row-wise).  Owned rows: the arithmetic and summation order of LIN 3, untouched.
+// LIN = 5, 6: LIN 3, 4 with the rotation flag of conv_cell_eval_g set -- the stored vector is c_c conv(u1) + M (gam e_z x
+// u1), gam = ix.gam = 2 c_cor omega(t^n) (the rotating frame of the IMEX step).  Instantiations of their own: modes 0 - 4
+// compile as without them.
 struct TabGrad {
   const double* __restrict__ t;   // [7][6][2] gradients, then [7] weights of one cell type (wave-uniform address)
   __device__ __forceinline__ void grad(int q, int k, double& gx, double& gy) const {
@@ -1087,8 +1109,9 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   // set by the caller afterwards); g joins the node's sum after the L product and before the element vectors,
   // the order of the launches it replaces (product, axpby, k_conv_cell, k_res_gather).
   // ugeo: V 0, 1 the two types' geometry [2][5] (uniform lattices; null: load_geo per cell), V 2 the gradient tables
-  constexpr bool IMX = LIN == 3 || LIN == 4;
-  constexpr bool GH = LIN == 4;                                     // ghost rows of a strip -> 0
+  constexpr bool IMX = LIN >= 3;
+  constexpr bool GH = LIN == 4 || LIN == 6;                         // ghost rows of a strip -> 0
+  constexpr bool ROT = LIN >= 5;                                    // Coriolis term in the element vector
   constexpr bool RES = LIN == 0 || IMX;
   constexpr bool TWO = LIN != 0;                                    // a second staged vector (x, or u2)
   constexpr int CLIN = IMX ? 0 : LIN;                               // mode of the element kernel
@@ -1275,7 +1298,8 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
 #pragma unroll
       for (int k = 0; k < 6; ++k) { rx[k] = ux[k]; ry[k] = uy[k]; }
     } else {
-      if constexpr (V == 2) conv_cell_eval_g<FORM, CLIN>(TabGrad{ugeo + kGradTab * ct}, ux, uy, wx, wy, a.cc, rx, ry);
+      if constexpr (V == 2)
+        conv_cell_eval_g<FORM, CLIN, ROT>(TabGrad{ugeo + kGradTab * ct}, ux, uy, wx, wy, a.cc, rx, ry, ROT ? ix.gam : 0.0);
       else conv_cell_eval<FORM, CLIN>(geo, ux, uy, wx, wy, a.cc, rx, ry);
     }
   }
@@ -1540,7 +1564,7 @@ int64_t jacobian_lattice_bytes(const MeshDev& m) {
 }
 
 // lin: 0 residual (x, mask unused; gadd = g), 1 Newton action, 2 Picard action, 3 IMEX right-hand side (ix; L = L1),
-// 4 the same on a partitioned strip (mask: ghost rows -> 0)
+// 4 the same on a partitioned strip (mask: ghost rows -> 0), 5 / 6: 3 / 4 with the Coriolis term (ix.gam)
 // phase 0: every tile; 1: the tile rows that read no lattice line below `safe_lo` or from `safe_hi` on (the interior of
 // a partitioned strip, launched under the halo exchange); 2: the other tile rows.  jacobian_lattice_split tells
 // whether phases 1 / 2 exist for the given ghost lines
@@ -1650,6 +1674,7 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
 #undef NSFEM_JL_T
 #define NSFEM_JL_T(F, LIN, SX, SY) NSFEM_JL_V(F, LIN, SX, SY, 2)
   if (lin == 3) { NSFEM_JL_F(3) } else if (lin == 4) { NSFEM_JL_F(4) }
+  else if (lin == 5) { NSFEM_JL_F(5) } else if (lin == 6) { NSFEM_JL_F(6) }
 #undef NSFEM_JL_F
 #undef NSFEM_JL_T
 #undef NSFEM_JL_V
@@ -1684,7 +1709,7 @@ bool imex_rhs_lattice_available(const MeshDev& m, const BlockMat& L1, const Bloc
 bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
                              const double* u2, const double* g, double cc, int form, double b0, double b1,
                              const double* n2, double* n1, double* rhs, const uint8_t* ghostmask, int phase, int gh_lo,
-                             int gh_hi) {
+                             int gh_hi, double gam) {
   if (!L1.dict || !L1.dict->exact || L2.dict != L1.dict || !L1.dict_ready || !L2.dict_ready || !g || !n1) return false;
   ImexLatArgs ix;
   ix.u2 = u2;
@@ -1693,8 +1718,10 @@ bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1
   ix.n1 = n1;
   ix.b0 = b0;
   ix.b1 = b1;
-  return launch_lattice_cells(s, m, L1, u1, u1, cc, form, ghostmask ? 4 : 3, ghostmask, g, rhs, phase, gh_lo, gh_hi,
-                              &ix);
+  ix.gam = gam;
+  // (gam == 0: the non-rotating instantiations, whatever was asked for)
+  return launch_lattice_cells(s, m, L1, u1, u1, cc, form, (ghostmask ? 4 : 3) + (gam != 0.0 ? 2 : 0), ghostmask, g, rhs,
+                              phase, gh_lo, gh_hi, &ix);
 }
 
 }  // namespace nsfem

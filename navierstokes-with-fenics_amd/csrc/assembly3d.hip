@@ -350,13 +350,18 @@ __global__ __launch_bounds__(256) void k3_conv_jac(int nc, const double* __restr
 //   LIN = 2   Picard linearisation times v (source/ns_solver_base.py:478-499)
 // forms: 0 standard (grad u) u; 1 rotational curl(u) x u; 2 divergence + 1/2 div(u) u; 3 skew-symmetric
 //   1/2 [ (grad u) u . phi - ((grad phi) u) . u ]
-template <int FORM, int LIN>
+// ROT (LIN = 0 only): the explicit Coriolis vector of the IMEX step joins the element vector,
+//   r_(i,.) += w_q |det J| phi_i (gam x u_q),   gam = 2 c_cor Omega
+// weighted by the quadrature weight alone, not by cc (degree 4 under a rule exact to degree 5: M (gam x u) to rounding)
+struct Gam3 { double x, y, z; };
+template <int FORM, int LIN, bool ROT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k3_conv_cell(int nc, const double* __restrict__ vx,
                                                     const int32_t* __restrict__ p2,
                                                     const double* __restrict__ u,
                                                     const double* __restrict__ v, double cc,
                                                     const int32_t* __restrict__ ndst,
-                                                    double* __restrict__ rbuf) {
+                                                    double* __restrict__ rbuf, Gam3 gam) {
+  static_assert(!ROT || LIN == 0, "the rotation term belongs to the residual mode");
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const CellGeo3 g = load_geo3(vx, nc, c);
@@ -446,6 +451,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           for (int a = 0; a < 3; ++a)
             r[i][a] -= 0.5 * w * (ugi * vq[a] + (LIN == 1 ? vgi * uq[a] : 0.0));
         }
+      }
+    }
+    if (ROT) {
+      const double wr = c_q3.w[q] * g.adet;
+      const double cr[3] = {gam.y * uq[2] - gam.z * uq[1], gam.z * uq[0] - gam.x * uq[2], gam.x * uq[1] - gam.y * uq[0]};
+#pragma unroll
+      for (int i = 0; i < 10; ++i) {
+        const double rpi = wr * c_q3.phi2[q][i];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) r[i][a] += rpi * cr[a];
       }
     }
   }
@@ -618,12 +633,13 @@ void convection_jacobian_3d(hipStream_t s, const MeshDev& m, const Pattern& p22,
                      p22.cptr.p, p22.cidx.p, m.ebuf.p, L, E, cvE, J);
   NSFEM_HIP(hipGetLastError());
 }
-template <int LIN>
+template <int LIN, bool ROT = false>
 static void launch_conv_cell(hipStream_t s, const MeshDev& m, const double* u, const double* v,
-                             double cc, int form) {
+                             double cc, int form, Gam3 gam = Gam3{0.0, 0.0, 0.0}) {
   const dim3 grid(grid3(m.n_cells)), block(kBlock);
 #define NSFEM_CC3(F) \
-  hipLaunchKernelGGL((k3_conv_cell<F, LIN>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, v, cc, m.ndst.p, m.rbuf.p)
+  hipLaunchKernelGGL((k3_conv_cell<F, LIN, ROT>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, v, cc, m.ndst.p, \
+                     m.rbuf.p, gam)
   switch (form) {
     case 0: NSFEM_CC3(0); break;
     case 1: NSFEM_CC3(1); break;
@@ -636,8 +652,10 @@ static void launch_conv_cell(hipStream_t s, const MeshDev& m, const double* u, c
 }
 
 void convection_residual_3d(hipStream_t s, const MeshDev& m, const double* u, double cc, double* b,
-                            int form) {
-  launch_conv_cell<0>(s, m, u, nullptr, cc, form);
+                            int form, const double* gam) {
+  if (gam && (gam[0] != 0.0 || gam[1] != 0.0 || gam[2] != 0.0))
+    launch_conv_cell<0, true>(s, m, u, nullptr, cc, form, Gam3{gam[0], gam[1], gam[2]});
+  else launch_conv_cell<0>(s, m, u, nullptr, cc, form);
   hipLaunchKernelGGL(k3_res_gather, dim3(grid3((int64_t)m.n_p2 * 3)), dim3(kBlock), 0, s, m.n_p2,
                      m.nptr.p, m.rbuf.p, (const uint8_t*)nullptr, b);
   NSFEM_HIP(hipGetLastError());

@@ -379,7 +379,7 @@ void convection_jacobian_3d(hipStream_t s, const MeshDev& m, const Pattern& p22,
                             double cc, const double* L, const double* E, double cvE, double* J,
                             int form, bool picard);
 void convection_residual_3d(hipStream_t s, const MeshDev& m, const double* u, double cc, double* b,
-                            int form);
+                            int form, const double* gam = nullptr);
 void convection_action_3d(hipStream_t s, const MeshDev& m, const double* u, const double* v,
                           double cc, double* y, int form, bool picard, const uint8_t* skipmask = nullptr);
 void launch_assemble_p1_scalar(hipStream_t s, const MeshDev& m, const Pattern& p11,
@@ -418,17 +418,20 @@ bool launch_jacobian_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L,
 // generic sequence -- launch_spmv (L1, L2), launch_axpby twice, launch_convection_residual, launch_imex_combine --
 // bit for bit.  L1, L2 share L's pattern and dictionary.  ghostmask set (the strip of a partitioned mesh, after the
 // ghost lines of u1 and u2 were exchanged): k_jac_lattice<FORM, 4>, rows of ghost nodes get rhs = 0 and n1 = 0.
+// gam != 0 (rotating frame, nsfem_set_imex_rotation): k_jac_lattice<FORM, 5 / 6>, n1 = c_c conv(u1) + M (gam e_z x u1)
+// from the same element kernel -- as launch_convection_residual with gam forms it.
 struct ImexLatArgs {
   const double* u2 = nullptr;      // velocity at t_(n-1)
   const double* sval2 = nullptr;   // dictionary values of L2
   const double* n2 = nullptr;      // c_c conv(u2) (null: not read)
   double* n1 = nullptr;            // c_c conv(u1), written
   double b0 = 1.0, b1 = 0.0;
+  double gam = 0.0;                // 2 c_cor omega(t^n): read by the rotating modes (LIN 5, 6) only
 };
 bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
                              const double* u2, const double* g, double cc, int form, double b0, double b1,
                              const double* n2, double* n1, double* rhs, const uint8_t* ghostmask = nullptr,
-                             int phase = 0, int gh_lo = 0, int gh_hi = 0);
+                             int phase = 0, int gh_lo = 0, int gh_hi = 0, double gam = 0.0);
 // every precondition of launch_imex_rhs_lattice that depends on the mesh and the operators (the ranks of a partitioned
 // run agree on the path once, from this)
 bool imex_rhs_lattice_available(const MeshDev& m, const BlockMat& L1, const BlockMat& L2);
@@ -441,8 +444,10 @@ bool jacobian_lattice_split(const MeshDev& m, int gh_lo, int gh_hi);
 bool ghost_lattice_lines(const std::vector<uint8_t>& ghost, int W, int H, int& lo, int& hi);
 void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, const double* v, double cc,
                              int form, bool picard);
+// gam (null: none): 2 c_cor Omega, 1 double in 2D and 3 in 3D -- the element kernel adds M (gam x u) to the node sums
+// (the explicit Coriolis vector of the IMEX step; weighted by the quadrature weights alone, so it survives cc = 0)
 void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u, double cc,
-                                double* b, int form);
+                                double* b, int form, const double* gam = nullptr);
 // scalar transport (nsfem_step_scalar_imex): out = weight * C(u) T for the P2 scalar T on the velocity nodes, form 0
 // standard C_ij = int (u . grad phi_j) phi_i, 1 skew-symmetric 1/2 (C - C^T) -- element kernel (k_scalar_conv_cell /
 // k3_scalar_conv_cell, node-sorted element vectors in m.rbuf) plus the per-node sums in ascending cell order
@@ -1058,6 +1063,16 @@ struct nsfem_ctx {
   int imex_lattice_agreed = -1;                        // the ranks' common answer to "one-launch right-hand side?" (-1: not asked)
   int conv_n_form = -1;                                // convective form and coefficient the stored vectors belong to
   double conv_n_cc = 0.0;
+  // rotating frame in the IMEX calls (nsfem_set_imex_rotation): treatment 0 refuse, 1 Coriolis term extrapolated with
+  // the convective term.  w[0], w[1]: the angular velocity at t^n, t^(n-1) where `given` (else the value of
+  // nsfem_set_angular_velocity); conv_n_gam: the 2 c_cor Omega the stored N1 was formed with
+  struct ImexRotation {
+    int treatment = 0;
+    bool given[2] = {false, false};
+    double w[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    int64_t rhs = 0, recomputed = 0;
+  } imex_rot;
+  double conv_n_gam[3] = {0.0, 0.0, 0.0};
   // variable viscosity (nsfem_set_viscosity_law): law 0 none, 1 Smagorinsky, 2 Carreau.  With a law the stored
   // vectors N1, N2 are c_c conv(u) + V(u); `epoch` counts the changes of law or parameters, conv_n_visc is the epoch
   // the stored vectors belong to

@@ -14,8 +14,9 @@ matrix in the chosen form (standard: C_ij = int (u . grad phi_j) phi_i; skew-sym
 The transport step comes first (it needs the known levels only); b is the constant buoyancy vector.
 The device keeps beta_0 C(u1) T1 of a step for the next one and rebuilds the system matrix only when
 alpha_0/k, gamma_0 or kappa change.  The reference has no transported quantity: its gravity-driven
-cases prescribe the body force.  Partitioned meshes and rotating frames are refused by the device
-driver.
+cases prescribe the body force.  Partitioned meshes are refused by the device driver.  Rotating
+frames (rotating convection) run as in ``IMEXIPCSSolver``: explicit Coriolis term, opted in by the
+solver when an angular velocity has been set.
 """
 import numpy as np
 

@@ -22,8 +22,17 @@ The scheme is conditionally stable (a CFL-type restriction on k, reported by the
 CFL diagnostic).  A strain-rate dependent viscosity (``set_viscosity_model``, ``viscosity_models``) keeps
 all of this: c_v K stays in the matrix and the remainder V(u) joins the extrapolated vector,
 N(u) = c_c conv(u) + V(u); that treatment is unconditionally stable only while |nu_x| stays a fraction
-of c_v, otherwise k is bounded by about Delta^2 / nu_x.  Rotating frames (Coriolis / Euler terms) are refused with an error by the device
-driver; 3D meshes run through the generic right-hand-side path.
+of c_v, otherwise k is bounded by about Delta^2 / nu_x.
+
+Rotating frames (``set_angular_velocity``): the Coriolis term is extrapolated with the convective
+term, N(u) = c_c conv(u) + V(u) + M (2 c_cor Omega x u) with Omega taken at the time of the level
+u belongs to, and the Euler term c_e M (dOmega/dt x x) joins the step-constant vector.  The
+convection element kernel forms the Coriolis vector itself: no launch, no pass over memory and no
+halo exchange is added, and uniform 2D lattices keep the one-launch right-hand side.  The device
+driver refuses rotating frames unless asked (``nsfem_set_imex_rotation``); the solver asks on its
+own when an angular velocity has been set, and hands over Omega(t^n), Omega(t^(n-1)) before every
+step.  The explicit treatment bounds the step: keep 2 c_cor |Omega| k at or below about 0.1 unless
+viscosity damps the mode.  3D meshes run through the generic right-hand-side path.
 
 Partitioned meshes (a context with a communicator, ``partition.py``'s ``attach``): the step runs on
 strips, slabs and recursive-bisection partitions.  Its right-hand side costs one halo exchange (u1;
@@ -109,6 +118,18 @@ class IMEXIPCSSolver(InstationarySolverBase):
         self._alpha, self._beta, self._gamma = list(ts.alpha), list(ts.beta), list(ts.gamma)
         assert len(self._alpha) == 3 and len(self._beta) == 2 and len(self._gamma) == 3
         self._ctx.set_imex(self._alpha, self._beta, self._gamma, self._next_step_size)
+        self._push_imex_rotation()
+
+    def _push_imex_rotation(self):
+        """rotating frame: opt in and hand the device Omega(t^n), Omega(t^(n-1)) -- the levels the Coriolis term is
+        extrapolated from (the first step reads t^n only: beta_1 = 0).  The base class pushes the new level's Omega
+        and dOmega/dt.  Without an angular velocity nothing is called."""
+        if not hasattr(self, "_angular_velocity"):
+            return
+        ts, av = self._time_stepping, self._angular_velocity
+        omega_n = av.value_at(ts.current_time)
+        omega_nm1 = av.value_at(ts.previous_time) if ts.step_number > 0 else None
+        self._ctx.set_imex_rotation(1, omega_n, omega_nm1)
 
     def _step_options(self):
         o = self._common_step_options(self._ctx.default_step_opts())
