@@ -509,6 +509,52 @@ int nsfem_viscosity_cells(nsfem_ctx* ctx, int velocity_slot, double* out_host);
 /* out = {current law, element-kernel launches so far (steps, hook and cell means), stored vectors N(u2) that had to be
  * recomputed with a law set, 0} */
 int nsfem_viscosity_info(nsfem_ctx* ctx, int64_t out[4]);
+/* ---- immersed bodies in the IMEX step: Brinkman volume penalisation (new; the reference has body-fitted meshes only).
+ * The momentum equation gains (chi / eta) (u - u_s), chi the indicator of the solid, u_s its rigid velocity.  Up to
+ * NSFEM_MAX_BODIES bodies, each a primitive with a signed distance d(x), negative inside:
+ *   kind 1  ball (disc in 2D)   d = |x - c| - r                                  size = {r > 0}
+ *   kind 2  axis-aligned box    d = |max(q, 0)| + min(max_a q_a, 0),  q = |x - c| - h componentwise
+ *                                                                               size = half widths h_a > 0
+ *   kind 3  half-space          d = (x - c) . n                                  size = unit normal n, | |n| - 1 | <= 1e-12
+ * Mask: smoothing eps = 0: chi = 1 where d <= 0, else 0;  eps > 0: chi = 1 for d <= -eps, 0 for d >= eps and
+ * 0.5 (1 - d/eps - sin(pi d/eps)/pi) between.  Body velocity u_s(x) = U + W x (x - c); 2D: U + w (-(y - c_y), x - c_x)
+ * with w = angular[2].  Where bodies overlap the one with the largest chi counts, the lowest index on ties.
+ *   B(u)_(i,a) = (1/eta) sum_K sum_q w_q |det J_K| chi(x_q) (u(x_q) - u_s(x_q))_a phi_i(x_q)
+ * with the 7-point Radon rule on triangles and the 15-point Keast rule on tetrahedra (the rules of the viscosity
+ * laws: the integrand is no polynomial, the rule is part of the definition), x_q the affine image of the reference
+ * point.  eta > 0 is used as given, multiplied by no equation coefficient; B has the sign of c_c conv(u).
+ * nsfem_step_imex then stores and extrapolates N(u) = c_c conv(u) + V(u) + R(u) + B(u); the matrices, the CG solve
+ * and the one-launch right-hand side stay as they are.  The term is explicit, so k / eta is bounded by the scheme
+ * (4/3 SBDF2, 1 CNAB and mCNAB, 0 CNLF for uniform steps); nothing here checks that. */
+#define NSFEM_MAX_BODIES 16
+typedef struct {
+  int32_t kind;
+  double centre[3], size[3], velocity[3], angular[3];
+} nsfem_body;
+/* n = 0 removes the bodies: nothing is launched after that (bodies may be NULL).  A change of the set, eta or the
+ * smoothing invalidates the stored vectors; the same set again does not.  NSFEM_ERR_ARG: contexts with a
+ * communicator (n > 0), n > NSFEM_MAX_BODIES, unknown kinds, sizes <= 0 or not finite (kind 3: no unit normal), centres
+ * or velocities not finite, eta <= 0, smoothing < 0; nsfem_step_ipcs and nsfem_step_bdf refuse to run while bodies
+ * are set. */
+int nsfem_set_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bodies, double eta, double smoothing);
+/* Pose and velocity at t^n of the bodies set: centre, velocity, angular (kind 3: the normal in size as well; other
+ * sizes are kept as set).  Call it once per step, before nsfem_step_imex: the pose it replaces becomes that of
+ * t^(n-1), which the stored N(u2) was formed with -- that vector is kept, and one that has to be recomputed is formed
+ * with that pose again.  NSFEM_ERR_ARG: another count or kind than set. */
+int nsfem_move_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bodies);
+/* Test hook: out_host [dim n_p2] = weight * B(u) for u = velocity_slot (NSFEM_U0, U1, U2 or USTAR) with the pose of
+ * t^n -- the element kernel plus the per-node sums, no Dirichlet rows; no stored state is touched.  Two calls on the
+ * same state return the same bytes.  NSFEM_ERR_ARG: no body set, other slots. */
+int nsfem_body_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host);
+/* Output: out_host [n_cells] = sum_q w_q chi(x_q) / sum_q w_q, the cell mean of the winning chi */
+int nsfem_body_mask_cells(nsfem_ctx* ctx, double* out_host);
+/* out [n][1 + dim + ntorque] (ntorque 1 in 2D, 3 in 3D), per body s: the volume int chi_s, the force
+ * F_s = (1/eta) int chi_s (u - u_s) the body takes from the fluid, and its torque about c_s; each quadrature point
+ * counts for its winning body only, so sum_s F_(s,a) = sum_i B(u)_(i,a).  Bitwise reproducible. */
+int nsfem_body_forces(nsfem_ctx* ctx, int velocity_slot, double* out);
+/* out = {bodies, element-kernel launches so far (steps, hook and cell means), stored vectors N(u2) that had to be
+ * recomputed with bodies set, 0} */
+int nsfem_body_info(nsfem_ctx* ctx, int64_t out[4]);
 /* replaces _advance_solution (ns_solver_base.py:1012-1016, ns_ipcs_solver.py:35-43); scheme 0 with a scalar
  * configured: also T2 <- T1 <- T0 and the stored scalar convection */
 int nsfem_advance(nsfem_ctx* ctx, int scheme /* 0 ipcs, 1 bdf */);

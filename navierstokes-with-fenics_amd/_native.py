@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "nsfem_volume_functionals",
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
+    "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
+    "nsfem_body_info",
     "nsfem_set_point_locator", "nsfem_locate_points", "nsfem_eval_points",
     "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
     "nsfem_stats_enable", "nsfem_stats_sample", "nsfem_stats_get", "nsfem_stats_set_groups", "nsfem_stats_profiles",
@@ -88,6 +90,15 @@ class WallOpts(C.Structure):
     """nsfem_wall_opts"""
     _fields_ = [("nu", C.c_double), ("sym", C.c_double), ("kappa", C.c_double), ("origin", C.c_double * 3),
                 ("use_law", C.c_int)]
+
+
+class Body(C.Structure):
+    """nsfem_body: kind 1 ball, 2 axis-aligned box, 3 half-space (include/nsfem.h)"""
+    _fields_ = [("kind", C.c_int32), ("centre", C.c_double * 3), ("size", C.c_double * 3),
+                ("velocity", C.c_double * 3), ("angular", C.c_double * 3)]
+
+
+MAX_BODIES = 16
 
 
 class KrylovOpts(C.Structure):
@@ -203,6 +214,12 @@ def load_library(path=None):
         "nsfem_viscosity_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
         "nsfem_viscosity_cells": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_viscosity_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_bodies": (C.c_int, [vp, C.c_int32, C.POINTER(Body), dbl, dbl]),
+        "nsfem_move_bodies": (C.c_int, [vp, C.c_int32, C.POINTER(Body)]),
+        "nsfem_body_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
+        "nsfem_body_mask_cells": (C.c_int, [vp, pd]),
+        "nsfem_body_forces": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_body_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_viscous_form": (C.c_int, [vp, C.c_int]),
         "nsfem_set_convective_form": (C.c_int, [vp, C.c_int, C.c_int]),
         "nsfem_set_state": (C.c_int, [vp, C.c_int, pd, i64]),
@@ -566,6 +583,64 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_viscosity_info(self._h, out))
         return dict(law=int(out[0]), element_launches=int(out[1]), recomputed=int(out[2]))
+
+    # -- immersed bodies in the IMEX step (volume penalisation) --------------------------
+    def _body_array(self, bodies):
+        """rows (kind, centre, size, velocity, angular) -> a C array of nsfem_body; short vectors are padded with
+        zeros, a scalar angular velocity (2D) goes to the z component"""
+        arr = (Body * max(len(bodies), 1))()
+        for b, row in zip(arr, bodies):
+            kind, centre, size, velocity, angular = row
+            b.kind = int(kind)
+            for name, val in (("centre", centre), ("size", size), ("velocity", velocity)):
+                v = np.atleast_1d(np.asarray(val, dtype=np.float64)).ravel()
+                assert v.size <= 3
+                for a in range(v.size):
+                    getattr(b, name)[a] = v[a]
+            w = np.atleast_1d(np.asarray(angular, dtype=np.float64)).ravel()
+            assert w.size in (1, 3)
+            if w.size == 1:
+                b.angular[2] = w[0]
+            else:
+                b.angular[0], b.angular[1], b.angular[2] = w
+        return arr
+
+    def set_bodies(self, bodies, eta=1.0, smoothing=0.0):
+        """bodies: rows (kind, centre, size, velocity, angular); an empty list removes them"""
+        bodies = list(bodies)
+        self._check(self._lib.nsfem_set_bodies(self._h, len(bodies), self._body_array(bodies), float(eta),
+                                               float(smoothing)))
+
+    def move_bodies(self, bodies):
+        """pose and velocity of the bodies at t^n (same count and kinds as set); once per step"""
+        bodies = list(bodies)
+        self._check(self._lib.nsfem_move_bodies(self._h, len(bodies), self._body_array(bodies)))
+
+    def body_residual(self, velocity_slot=U1, weight=1.0):
+        """test hook: weight * B(u), interleaved [dim * n_p2] (element kernel + node sums; no stored state touched)"""
+        out = np.empty(self.dim * self.n_p2, dtype=np.float64)
+        self._check(self._lib.nsfem_body_residual(self._h, int(velocity_slot), float(weight), _dp(out)))
+        return out
+
+    def body_mask_cells(self):
+        """cell means of chi, [n_cells]"""
+        out = np.empty(self.n_cells, dtype=np.float64)
+        self._check(self._lib.nsfem_body_mask_cells(self._h, _dp(out)))
+        return out
+
+    def body_forces(self, velocity_slot=U0):
+        """[n_bodies, 1 + dim + ntorque]: volume, force on the body, torque about its centre (2D: 1, 3D: 3)"""
+        n = self.body_info()["bodies"]
+        out = np.empty((max(n, 1), 4 if self.dim == 2 else 7), dtype=np.float64)
+        self._check(self._lib.nsfem_body_forces(self._h, int(velocity_slot), _dp(out)))
+        return out[:n]
+
+    def body_info(self):
+        """dict(bodies, element_launches, recomputed): the number of bodies set, the element-kernel launches so far
+        and how often a stored explicit vector had to be recomputed with bodies set"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_body_info(self._h, out))
+        return dict(bodies=int(out[0]), element_launches=int(out[1]), recomputed=int(out[2]))
 
     def step_bdf(self, opts=None):
         o = opts or self.default_step_opts()

@@ -258,6 +258,7 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   upload_quad_tables(qt);
   if (dim == 3) upload_quad_tables_3d();
   upload_functional_tables(dim);
+  upload_body_tables(dim);
   upload_derived_tables();
   fresh->M2.init(&fresh->p22, 1, 1, s);
   fresh->K2.init(&fresh->p22, 1, 1, s);
@@ -2249,6 +2250,7 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   nsfem_step_info& inf = step_begin(ctx, opts, info, local, true, false);
   NSFEM_REQUIRE(ctx->alpha[0] != 0.0, "the pressure-correction scheme needs alpha0 != 0");
   NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
+  NSFEM_REQUIRE(ctx->bodies.cur.n == 0, "immersed bodies: only nsfem_step_imex takes bodies (remove them with n = 0 first)");
   NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
   // ---- diffusion step: Newton
   momentum_begin_step(ctx);
@@ -2454,8 +2456,20 @@ static void viscosity_add(nsfem_ctx* c, const double* u, double b0, double* n1, 
   ++c->visc.launches;
 }
 
+// Immersed bodies (nsfem_set_bodies): the stored explicit vector gains B(u).  As viscosity_add, after it: the element
+// kernel on u (weight 1, element vectors node-sorted in mesh.rbuf) and k_visc_gather, n1 <- n1 + v, rhs <- rhs - b0 v.
+// So with a law and bodies the order is viscosity cells, gather, penalisation cells, gather.  bt: the pose that
+// belongs to the level of u (cur for u1, prev for a recomputed N(u2)).  Without bodies nothing is launched.
+static void penalty_add(nsfem_ctx* c, const BodyTable& bt, const double* u, double b0, double* n1, double* rhs) {
+  launch_penalty_cells(c->stream, c->mesh, u, 1.0, bt, false);
+  launch_viscosity_gather(c->stream, c->mesh, b0, n1, rhs);
+  ++c->bodies.launches;
+}
+
 static void imex_require_supported(nsfem_ctx* c) {
   NSFEM_REQUIRE(c->imex_active, "nsfem_set_imex has not been called");
+  NSFEM_REQUIRE(c->bodies.cur.n == 0 || !c->comm,
+                "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(c->visc.law == 0 || !c->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(c->imex_rot.treatment == 1 || (!coriolis_active(c) && !euler_active(c)),
@@ -2502,7 +2516,8 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
     const bool same_rot = std::memcmp(ctx->conv_n_gam, gam2, sizeof(gam2)) == 0;
     const bool stored = ctx->conv_n2_valid && (ctx->conv_n_form == -2 ||
                                                (ctx->conv_n_form == ctx->conv_form && ctx->conv_n_cc == cc &&
-                                                ctx->conv_n_visc == ctx->visc.epoch && same_rot));
+                                                ctx->conv_n_visc == ctx->visc.epoch &&
+                                                ctx->conv_n_body == ctx->bodies.epoch && same_rot));
     if (!stored) {
       ctx->state[NSFEM_CONV_N2].zero(s);
       if (cc != 0.0 || rot2)
@@ -2512,6 +2527,10 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
       if (ctx->visc.law != 0) {
         viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, ctx->state[NSFEM_CONV_N2].p, nullptr);
         ++ctx->visc.recomputed;
+      }
+      if (ctx->bodies.cur.n != 0) {
+        penalty_add(ctx, ctx->bodies.prev, ctx->state[NSFEM_U2].p, 0.0, ctx->state[NSFEM_CONV_N2].p, nullptr);
+        ++ctx->bodies.recomputed;
       }
       if (ctx->distributed() && ctx->ghost_v.p) launch_zero_ghost(s, nv, ctx->mask_v.p, ctx->state[NSFEM_CONV_N2].p);
       ctx->conv_n2_valid = true;
@@ -2525,10 +2544,14 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   std::memcpy(ctx->conv_n_gam, gam1, sizeof(gam1));
   if (ctx->visc.law != 0)
     viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
+  if (ctx->bodies.cur.n != 0)
+    penalty_add(ctx, ctx->bodies.cur, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p,
+                ctx->rhs_v.p);
   ctx->conv_n1_fresh = true;
   ctx->conv_n_form = ctx->conv_form;
   ctx->conv_n_cc = cc;
   ctx->conv_n_visc = ctx->visc.epoch;
+  ctx->conv_n_body = ctx->bodies.epoch;
   {
     // Dirichlet rows u*_i = g_i; start vector u1 with the Dirichlet values
     double* x = ctx->state[NSFEM_USTAR].p;
@@ -2616,10 +2639,12 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
       launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form,
                                  rot2 ? gam2 : nullptr);
     if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, n2, nullptr);
+    if (ctx->bodies.cur.n != 0) penalty_add(ctx, ctx->bodies.prev, ctx->state[NSFEM_U2].p, 0.0, n2, nullptr);
   }
   imex_rhs(ctx, path, n2, n1, out, u1_travelled, rot1 ? gam1 : nullptr);
   if (rot1) ++ctx->imex_rot.rhs;
   if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], n1, out);
+  if (ctx->bodies.cur.n != 0) penalty_add(ctx, ctx->bodies.cur, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], n1, out);
   NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
@@ -2730,6 +2755,155 @@ extern "C" int nsfem_viscosity_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[0] = ctx->visc.law;
   out[1] = ctx->visc.launches;
   out[2] = ctx->visc.recomputed;
+  out[3] = 0;
+  API_END(ctx)
+}
+
+// ---------------------------------------------------------------- immersed bodies
+// nsfem_body -> row s of the table.  move: the kind is the one set and the sizes of kinds 1 and 2 stay as set (the
+// normal of a half-space is part of its pose and is taken)
+static void body_to_table(const nsfem_body& b, int dim, BodyTable& t, int s, bool move) {
+  const int kind = move ? t.kind[s] : b.kind;
+  for (int a = 0; a < 3; ++a) {
+    const bool in = a < dim;
+    NSFEM_REQUIRE(std::isfinite(b.centre[a]) || !in, "immersed bodies: centre not finite");
+    NSFEM_REQUIRE(std::isfinite(b.velocity[a]) || !in, "immersed bodies: velocity not finite");
+    NSFEM_REQUIRE(std::isfinite(b.angular[a]) || (dim == 2 && a != 2), "immersed bodies: angular velocity not finite");
+    t.centre[s][a] = in ? b.centre[a] : 0.0;
+    t.velocity[s][a] = in ? b.velocity[a] : 0.0;
+    t.angular[s][a] = (dim == 3 || a == 2) ? b.angular[a] : 0.0;
+  }
+  if (move && kind != 3) return;
+  double size[3] = {0.0, 0.0, 0.0};
+  if (kind == 1) {
+    NSFEM_REQUIRE(std::isfinite(b.size[0]) && b.size[0] > 0.0, "immersed bodies: size (radius) must be finite and > 0");
+    size[0] = b.size[0];
+  } else if (kind == 2) {
+    for (int a = 0; a < dim; ++a) {
+      NSFEM_REQUIRE(std::isfinite(b.size[a]) && b.size[a] > 0.0,
+                    "immersed bodies: size (half widths) must be finite and > 0");
+      size[a] = b.size[a];
+    }
+  } else {
+    double nn = 0.0;
+    for (int a = 0; a < dim; ++a) {
+      NSFEM_REQUIRE(std::isfinite(b.size[a]), "immersed bodies: size (normal) not finite");
+      size[a] = b.size[a];
+      nn += size[a] * size[a];
+    }
+    NSFEM_REQUIRE(std::fabs(std::sqrt(nn) - 1.0) <= 1e-12, "immersed bodies: size of a half-space must be a unit normal");
+  }
+  for (int a = 0; a < 3; ++a) t.size[s][a] = size[a];
+}
+
+extern "C" int nsfem_set_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bodies, double eta, double smoothing) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(n >= 0 && n <= NSFEM_MAX_BODIES, "immersed bodies: n must be 0 .. NSFEM_MAX_BODIES (16)");
+  BodyTable t;
+  if (n > 0) {
+    NSFEM_REQUIRE(!ctx->comm, "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
+    NSFEM_REQUIRE(bodies, "immersed bodies: null body array");
+    NSFEM_REQUIRE(std::isfinite(eta) && eta > 0.0, "immersed bodies: eta must be finite and > 0");
+    NSFEM_REQUIRE(std::isfinite(smoothing) && smoothing >= 0.0, "immersed bodies: smoothing must be finite and >= 0");
+    t.n = n;
+    for (int s = 0; s < n; ++s) {
+      NSFEM_REQUIRE(bodies[s].kind >= 1 && bodies[s].kind <= 3,
+                    "immersed bodies: unknown kind (1 ball, 2 box, 3 half-space)");
+      t.kind[s] = bodies[s].kind;
+      body_to_table(bodies[s], ctx->mesh.dim, t, s, false);
+    }
+    t.eps = smoothing;
+    t.inv_eta = 1.0 / eta;
+  }
+  nsfem_ctx::Bodies& b = ctx->bodies;
+  // (the stored explicit vectors belong to the set they were evaluated with; the bodies enter no captured Krylov
+  // body -- their launches precede the solve --, so graph_epoch stays)
+  if (std::memcmp(&t, &b.cur, sizeof(BodyTable)) != 0 || std::memcmp(&t, &b.prev, sizeof(BodyTable)) != 0) ++b.epoch;
+  std::memcpy(&b.cur, &t, sizeof(BodyTable));
+  std::memcpy(&b.prev, &t, sizeof(BodyTable));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_move_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bodies) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && bodies, "null argument");
+  nsfem_ctx::Bodies& b = ctx->bodies;
+  NSFEM_REQUIRE(b.cur.n > 0, "immersed bodies: no body set (nsfem_set_bodies)");
+  NSFEM_REQUIRE(n == b.cur.n, "immersed bodies: nsfem_move_bodies with another count than set");
+  BodyTable t;
+  std::memcpy(&t, &b.cur, sizeof(BodyTable));
+  for (int s = 0; s < n; ++s) {
+    NSFEM_REQUIRE(bodies[s].kind == t.kind[s], "immersed bodies: nsfem_move_bodies with another kind than set");
+    body_to_table(bodies[s], ctx->mesh.dim, t, s, true);
+  }
+  std::memcpy(&b.prev, &b.cur, sizeof(BodyTable));
+  std::memcpy(&b.cur, &t, sizeof(BodyTable));
+  API_END(ctx)
+}
+
+static void bodies_require(nsfem_ctx* ctx, int velocity_slot) {
+  NSFEM_REQUIRE(!ctx->comm, "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->bodies.cur.n != 0, "immersed bodies: no body set (nsfem_set_bodies)");
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+}
+
+extern "C" int nsfem_body_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  bodies_require(ctx, velocity_slot);
+  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  hipStream_t s = ctx->stream;
+  const int64_t nv = nvel(ctx);
+  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
+  ctx->kw.ensure(nv);
+  ++ctx->kw.touch;
+  double* out = ctx->kw.q.p;
+  NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
+  launch_penalty_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->bodies.cur, false);
+  launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
+  ++ctx->bodies.launches;
+  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_body_mask_cells(nsfem_ctx* ctx, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  bodies_require(ctx, NSFEM_U0);
+  hipStream_t s = ctx->stream;
+  // (the cell means land in the element buffer, which every user fills before it reads; MEAN reads no velocity)
+  launch_penalty_cells(s, ctx->mesh, ctx->state[NSFEM_U0].p, 1.0, ctx->bodies.cur, true);
+  ++ctx->bodies.launches;
+  NSFEM_HIP(hipMemcpyAsync(out_host, ctx->mesh.rbuf.p, sizeof(double) * ctx->mesh.n_cells, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_body_forces(nsfem_ctx* ctx, int velocity_slot, double* out) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  bodies_require(ctx, velocity_slot);
+  hipStream_t s = ctx->stream;
+  const size_t n_out = (size_t)ctx->bodies.cur.n * body_numbers(ctx->mesh.dim);
+  const size_t n_work = n_out * (kBodyParts + 1);
+  if (ctx->bodies.work.n != n_work) ctx->bodies.work.alloc(n_work);
+  double* parts = ctx->bodies.work.p;
+  double* res = parts + n_out * kBodyParts;
+  launch_penalty_forces(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->bodies.cur, parts, res);
+  NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_body_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->bodies.cur.n;
+  out[1] = ctx->bodies.launches;
+  out[2] = ctx->bodies.recomputed;
   out[3] = 0;
   API_END(ctx)
 }
@@ -2961,6 +3135,7 @@ extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem
   API_BEGIN
   nsfem_step_info& inf = step_begin(ctx, opts, info, local, true, opts && opts->picard != 0);
   NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
+  NSFEM_REQUIRE(ctx->bodies.cur.n == 0, "immersed bodies: only nsfem_step_imex takes bodies (remove them with n = 0 first)");
   NSFEM_REQUIRE(!ctx->distributed() || ctx->schur_singular < 0 || ctx->schur_additive,
                 "partitioned meshes take the algebraic Schur Laplacian as additive rank parts "
                 "(nsfem_mg_set_schur_mode)");

@@ -21,6 +21,7 @@
 // degree-5 rule reproduces FEniCS' integrals to round-off.
 #include "nsfem_internal.hpp"
 #include "cell_geometry.hpp"
+#include "bodies.hpp"
 
 namespace nsfem {
 
@@ -1003,6 +1004,94 @@ void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double*
   NSFEM_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------- immersed bodies (nsfem_set_bodies)
+// Brinkman volume penalisation, one thread per CELL, 7-point rule (part of the definition: the integrand is no
+// polynomial):
+//   r_(i,a) = scale sum_q w_q |det J| chi(x_q) (u(x_q) - u_s(x_q))_a phi_i(x_q),   scale = weight / eta,
+// x_q the affine image of the reference point (the P1 basis values are its barycentric coordinates), chi and u_s those
+// of the body with the largest chi at x_q (bodies.hpp).  u at the 6 nodes in registers; x_q, the winning body, chi and
+// u - u_s of a quadrature point are formed once and shared by the 6 test functions.  The element vector goes
+// node-sorted into m.rbuf (ndst, as k_visc_var_cell); k_visc_gather sums the node runs: no atomics, no LDS, the same
+// state gives the same bytes.  Quadrature points with chi = 0 are skipped: a cell no body reaches stores zeros.
+// SMOOTH false: every mask is sharp and no sin is called.  MEAN: rbuf[c] = sum_q w_q chi(x_q) / sum_q w_q instead.
+template <bool SMOOTH, bool MEAN>
+__global__ __launch_bounds__(256) void k_penal_cell(int nc, const double* __restrict__ vx,
+                                                    const int32_t* __restrict__ p2,
+                                                    const double* __restrict__ u, double scale, const BodyTable bt,
+                                                    const int32_t* __restrict__ ndst, double* __restrict__ rbuf) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  double xv[3][2];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    xv[v][0] = vx[(size_t)(2 * v) * nc + c];
+    xv[v][1] = vx[(size_t)(2 * v + 1) * nc + c];
+  }
+  const CellGeo g = load_geo(vx, nc, c);
+  double ux[6], uy[6];
+  if (!MEAN) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const int node = p2[(size_t)k * nc + c];
+      const double2 a = reinterpret_cast<const double2*>(u)[node];
+      ux[k] = a.x;
+      uy[k] = a.y;
+    }
+  }
+  double rx[6], ry[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) rx[i] = ry[i] = 0.0;
+  double mean = 0.0, wsum = 0.0;
+  for (int q = 0; q < 7; ++q) {
+    double x[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+      x[a] = c_q.phi1[q][0] * xv[0][a] + c_q.phi1[q][1] * xv[1][a] + c_q.phi1[q][2] * xv[2][a];
+    int win;
+    const double chi = body_winner<2, SMOOTH>(bt, x, win);
+    if (MEAN) {
+      mean += c_q.w[q] * chi;
+      wsum += c_q.w[q];
+      continue;
+    }
+    if (!(chi > 0.0)) continue;
+    double us[2], uqx = 0.0, uqy = 0.0;
+    body_velocity<2>(bt, win, x, us);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      uqx += c_q.phi2[q][k] * ux[k];
+      uqy += c_q.phi2[q][k] * uy[k];
+    }
+    const double w = c_q.w[q] * g.adet * scale * chi;
+    const double fx = w * (uqx - us[0]), fy = w * (uqy - us[1]);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      rx[i] += fx * c_q.phi2[q][i];
+      ry[i] += fy * c_q.phi2[q][i];
+    }
+  }
+  if (MEAN) {
+    rbuf[c] = mean / wsum;
+  } else {
+    double2* out = reinterpret_cast<double2*>(rbuf);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) out[ndst[(size_t)i * nc + c]] = make_double2(rx[i], ry[i]);
+  }
+}
+
+void launch_penalty_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, const BodyTable& bt,
+                          bool mean) {
+  NSFEM_REQUIRE(bt.n > 0, "immersed bodies: no body set");
+  if (m.dim == 3) return penalty_cells_3d(s, m, u, weight, bt, mean);
+  const dim3 grid(grid_for(m.n_cells)), block(kBlock);
+  const double scale = weight * bt.inv_eta;
+#define NSFEM_PC(S, M) \
+  hipLaunchKernelGGL((k_penal_cell<S, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, scale, bt, m.ndst.p, m.rbuf.p)
+  if (bt.eps > 0.0) { if (mean) NSFEM_PC(true, true); else NSFEM_PC(true, false); }
+  else { if (mean) NSFEM_PC(false, true); else NSFEM_PC(false, false); }
+#undef NSFEM_PC
+  NSFEM_HIP(hipGetLastError());
+}
 
 // ---------------------------------------------------------------- IMEX right-hand side
 // rhs = -(t + (b0 n1 + b1 n2)): the last operation of the right-hand side of nsfem_step_imex, shared by the generic

@@ -9,6 +9,7 @@
 // is exact for degree 5, the highest degree any of these integrands reaches on affine cells.
 #include "nsfem_internal.hpp"
 #include "cell_geometry.hpp"
+#include "bodies.hpp"
 
 namespace nsfem {
 
@@ -751,6 +752,92 @@ void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double
   if (law == 1) { if (mean) NSFEM_VV3(1, true); else NSFEM_VV3(1, false); }
   else { if (mean) NSFEM_VV3(2, true); else NSFEM_VV3(2, false); }
 #undef NSFEM_VV3
+  NSFEM_HIP(hipGetLastError());
+}
+
+// ---- immersed bodies on tetrahedra (the 2D kernel is k_penal_cell, assembly.hip; distances, mask and the winning
+// body are bodies.hpp), one thread per cell, 15-point rule:
+//   r_(i,a) = scale sum_q w_q |det J| chi(x_q) (u(x_q) - u_s(x_q))_a phi_i(x_q),   scale = weight / eta
+// Element vector node-sorted into m.rbuf; the caller sums the node runs (k_visc_gather).  Quadrature points with
+// chi = 0 are skipped.  MEAN: rbuf[c] = sum_q w_q chi(x_q) / sum_q w_q instead.
+template <bool SMOOTH, bool MEAN>
+__global__ __launch_bounds__(256) void k3_penal_cell(int nc, const double* __restrict__ vx,
+                                                     const int32_t* __restrict__ p2,
+                                                     const double* __restrict__ u, double scale, const BodyTable bt,
+                                                     const int32_t* __restrict__ ndst, double* __restrict__ rbuf) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  double xv[4][3];
+#pragma unroll
+  for (int v = 0; v < 4; ++v)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) xv[v][d] = vx[(size_t)(3 * v + d) * nc + c];
+  if constexpr (MEAN) {
+    double mean = 0.0, wsum = 0.0;
+    for (int q = 0; q < 15; ++q) {
+      double x[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        x[a] = c_q3.phi1[q][0] * xv[0][a] + c_q3.phi1[q][1] * xv[1][a] + c_q3.phi1[q][2] * xv[2][a] +
+               c_q3.phi1[q][3] * xv[3][a];
+      int win;
+      mean += c_q3.w[q] * body_winner<3, SMOOTH>(bt, x, win);
+      wsum += c_q3.w[q];
+    }
+    rbuf[c] = mean / wsum;
+  } else {
+    const CellGeo3 g = load_geo3(vx, nc, c);
+    double un[10][3];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const size_t node = (size_t)p2[(size_t)k * nc + c];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
+    }
+    double r[10][3];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) r[i][0] = r[i][1] = r[i][2] = 0.0;
+    for (int q = 0; q < 15; ++q) {
+      double x[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        x[a] = c_q3.phi1[q][0] * xv[0][a] + c_q3.phi1[q][1] * xv[1][a] + c_q3.phi1[q][2] * xv[2][a] +
+               c_q3.phi1[q][3] * xv[3][a];
+      int win;
+      const double chi = body_winner<3, SMOOTH>(bt, x, win);
+      if (!(chi > 0.0)) continue;
+      double us[3], uq[3] = {0.0, 0.0, 0.0};
+      body_velocity<3>(bt, win, x, us);
+#pragma unroll
+      for (int k = 0; k < 10; ++k)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) uq[a] += c_q3.phi2[q][k] * un[k][a];
+      const double w = c_q3.w[q] * g.adet * scale * chi;
+      const double f[3] = {w * (uq[0] - us[0]), w * (uq[1] - us[1]), w * (uq[2] - us[2])};
+#pragma unroll
+      for (int i = 0; i < 10; ++i)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) r[i][a] += f[a] * c_q3.phi2[q][i];
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+      double* out = rbuf + (size_t)ndst[(size_t)i * nc + c] * 3;
+      out[0] = r[i][0];
+      out[1] = r[i][1];
+      out[2] = r[i][2];
+    }
+  }
+}
+
+void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, const BodyTable& bt, bool mean) {
+  const dim3 grid(grid3(m.n_cells)), block(kBlock);
+  const double scale = weight * bt.inv_eta;
+#define NSFEM_PC3(S, M) \
+  hipLaunchKernelGGL((k3_penal_cell<S, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, scale, bt, m.ndst.p, \
+                     m.rbuf.p)
+  if (bt.eps > 0.0) { if (mean) NSFEM_PC3(true, true); else NSFEM_PC3(true, false); }
+  else { if (mean) NSFEM_PC3(false, true); else NSFEM_PC3(false, false); }
+#undef NSFEM_PC3
   NSFEM_HIP(hipGetLastError());
 }
 

@@ -464,6 +464,30 @@ void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double
                         bool mean);
 // k_visc_gather: v = per-node sums of m.rbuf in ascending cell order; n1 += v, rhs -= b0 v (rhs may be null)
 void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double* n1, double* rhs);
+// immersed bodies (nsfem_set_bodies): the table the penalisation kernels take as a kernel ARGUMENT (1.6 kB; entries
+// are read with wave-uniform indices).  size: kind 1 {r}, kind 2 half widths, kind 3 the unit normal; 2D reads
+// angular[2].  eps the smoothing half width (0: every mask sharp), inv_eta = 1 / eta
+struct BodyTable {
+  int32_t n = 0;
+  int32_t kind[NSFEM_MAX_BODIES] = {};
+  int32_t pad_ = 0;                  // (no padding bytes: the table is compared with memcmp)
+  double centre[NSFEM_MAX_BODIES][3] = {}, size[NSFEM_MAX_BODIES][3] = {};
+  double velocity[NSFEM_MAX_BODIES][3] = {}, angular[NSFEM_MAX_BODIES][3] = {};
+  double eps = 0.0, inv_eta = 0.0;
+};
+// numbers per body of nsfem_body_forces: volume, dim force components, 1 (2D) or 3 torque components
+inline int body_numbers(int dim) { return dim == 2 ? 4 : 7; }
+constexpr int kBodyParts = 256;
+// k_penal_cell / k3_penal_cell on the velocity u: element vectors (weight / eta) B_K(u) node-sorted into m.rbuf, to be
+// summed by launch_viscosity_gather -- mean: the cell means of chi into the first n_cells doubles of m.rbuf instead
+void launch_penalty_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, const BodyTable& bt,
+                          bool mean);
+void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, const BodyTable& bt, bool mean);
+// k_penal_forces + k_penal_finish (bodies.hip): out[s][body_numbers] in device memory, parts
+// [n body_numbers kBodyParts] work space
+void upload_body_tables(int dim);
+void launch_penalty_forces(hipStream_t s, const MeshDev& m, const double* u, const BodyTable& bt, double* parts,
+                           double* out);
 // out[n dim + c] = f[n dim + c] + T[n] b[c] on the P2 nodes (f null: out = T b)
 void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, const double* T, const double b[3],
                            double* out);
@@ -1082,6 +1106,16 @@ struct nsfem_ctx {
     int64_t epoch = 0, launches = 0, recomputed = 0;
   } visc;
   int64_t conv_n_visc = 0;
+  // immersed bodies (nsfem_set_bodies): with bodies the stored vectors carry B(u) as well.  `cur` is the pose of t^n,
+  // `prev` that of t^(n-1) (nsfem_move_bodies shifts cur to prev; without a move they are equal): a stored N(u2) was
+  // formed with prev and one that has to be recomputed is formed with it again.  `epoch` counts the changes of the set,
+  // eta or the smoothing; conv_n_body is the epoch the stored vectors belong to
+  struct Bodies {
+    nsfem::BodyTable cur, prev;
+    int64_t epoch = 0, launches = 0, recomputed = 0;
+    nsfem::DevBuf<double> work;     // partials and results of nsfem_body_forces
+  } bodies;
+  int64_t conv_n_body = 0;
   // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the
   // non-symmetric V(0, d + 1) the BiCGStab solves use (nsfem_set_bdf switches back)
   bool mg_v_symmetric = false;

@@ -70,6 +70,16 @@ class IMEXTimeStepping(DiscreteTime):
         self._eta[:] = [1.0 + w, -w]
         self._coefficients_changed = True
 
+    def uniform_coefficients(self):
+        """(alpha, beta, gamma) of this scheme once the steps are uniform: what ``update_coefficients`` leaves on a
+        scratch instance after two equal steps (new helper; the start-up step is first order and has other values)"""
+        scratch = type(self)(0.0, 4.0, self._type, desired_start_time_step=1.0)
+        for _ in range(2):
+            scratch.update_coefficients()
+            scratch.advance_time()
+        scratch.update_coefficients()
+        return list(scratch.alpha), list(scratch.beta), list(scratch.gamma)
+
     def print_coefficients(self):
         """table of the four coefficient sets over the time levels n+1, n, n-1"""
         cell = "{:12.2e}".format
@@ -83,6 +93,7 @@ class IMEXTimeStepping(DiscreteTime):
         for row in rows:
             print("| " + " | ".join("{:12}".format(c) for c in row) + " |")
 
+    imex_type = property(lambda self: self._type)
     alpha = property(lambda self: self._alpha)
     beta = property(lambda self: self._beta)
     gamma = property(lambda self: self._gamma)

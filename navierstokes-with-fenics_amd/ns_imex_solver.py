@@ -22,7 +22,9 @@ The scheme is conditionally stable (a CFL-type restriction on k, reported by the
 CFL diagnostic).  A strain-rate dependent viscosity (``set_viscosity_model``, ``viscosity_models``) keeps
 all of this: c_v K stays in the matrix and the remainder V(u) joins the extrapolated vector,
 N(u) = c_c conv(u) + V(u); that treatment is unconditionally stable only while |nu_x| stays a fraction
-of c_v, otherwise k is bounded by about Delta^2 / nu_x.
+of c_v, otherwise k is bounded by about Delta^2 / nu_x.  Solid bodies inside the box
+(``set_immersed_bodies``, ``immersed_bodies``) join the same vector as a Brinkman penalisation term B(u); that term
+bounds k / eta.
 
 Rotating frames (``set_angular_velocity``): the Coriolis term is extrapolated with the convective
 term, N(u) = c_c conv(u) + V(u) + M (2 c_cor Omega x u) with Omega taken at the time of the level
@@ -43,6 +45,7 @@ agree once on the right-hand-side path, so every rank runs the same sequence of 
 import _native as nat
 from fem_function import DeviceFunction, MixedFunction
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from immersed_bodies import ImmersedBodies, stiff_step_bound, stiff_step_stable
 from ns_ipcs_solver import _FORM_ID, _DeviceSystem
 from ns_solver_base import InstationarySolverBase
 
@@ -85,6 +88,93 @@ class IMEXIPCSSolver(InstationarySolverBase):
         super()._push_coefficients()
         self._push_viscosity_model()
 
+    def set_immersed_bodies(self, bodies, allow_stiff=False):
+        """an ``immersed_bodies.ImmersedBodies`` or None for none.  The penalisation term is explicit: a step with
+        k / eta above ``stiff_step_bound`` of the scheme's coefficients (always the case for CNLF) raises ValueError
+        unless ``allow_stiff``.  Bodies with a ``motion`` are moved to t^n once before every step; a set handed over in
+        the middle of a run goes to the device with its poses of t^(n-1) and t^n.  Partitioned meshes are refused by
+        the device driver."""
+        assert bodies is None or isinstance(bodies, ImmersedBodies)
+        self._immersed_bodies = bodies
+        self._immersed_allow_stiff = bool(allow_stiff)
+        self._immersed_on_device = False
+        self._push_immersed_bodies()
+
+    def _push_immersed_bodies(self):
+        if not (hasattr(self, "_ctx") and hasattr(self, "_immersed_bodies")):
+            return
+        bodies, ts = self._immersed_bodies, self._time_stepping
+        self._immersed_moved_to = None
+        try:
+            if bodies is None:
+                self._ctx.set_bodies([])
+            elif not bodies.moving:
+                assert bodies.dim == self._space_dim
+                self._ctx.set_bodies(bodies.rows(), bodies.eta, bodies.smoothing)
+            else:
+                assert bodies.dim == self._space_dim
+                # (a new set makes the next step form N(u2) afresh, with the older of the device's two poses: in the
+                # middle of a run that is the pose of t^(n-1), and the pose of t^n follows as a move)
+                if ts.step_number > 0:
+                    self._ctx.set_bodies(bodies.rows(ts.previous_time), bodies.eta, bodies.smoothing)
+                    self._move_immersed_bodies()
+                else:
+                    self._ctx.set_bodies(bodies.rows(ts.current_time), bodies.eta, bodies.smoothing)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+        self._immersed_on_device = True
+
+    def _move_immersed_bodies(self):
+        """the pose of t^n -> device, once per time level: a second call for the same t^n (the coefficients are
+        refreshed again, a step is tried again) would push the pose of t^(n-1) out of the device's memory"""
+        t = self._time_stepping.current_time
+        if getattr(self, "_immersed_moved_to", None) == t:
+            return
+        self._ctx.move_bodies(self._immersed_bodies.rows(t))
+        self._immersed_moved_to = t
+
+    def immersed_step_bound(self):
+        """the largest admissible k / eta: ``stiff_step_bound`` of the current coefficients and of the scheme's
+        uniform-step coefficients (the first step is first order and would admit more than the steps after it).  Two
+        bisections, about a millisecond: for diagnostics and the error message, not for every step"""
+        ts = self._time_stepping
+        alpha, beta, _ = ts.uniform_coefficients()
+        return min(stiff_step_bound(alpha, beta), stiff_step_bound(ts.alpha, ts.beta))
+
+    def _immersed_step_is_stable(self, ratio):
+        """k / eta = ratio against the current and the uniform-step coefficients: two root solves, and none while
+        coefficients and ratio stay what they were at the last step (uniform steps).  With adaptive steps every step
+        asks anew, at the cost of the two root solves"""
+        ts = self._time_stepping
+        key = (ts.imex_type, tuple(ts.alpha), tuple(ts.beta), ratio)
+        if getattr(self, "_immersed_stable_memo", (None, None))[0] != key:
+            uniform = self.__dict__.setdefault("_immersed_uniform", {})
+            if ts.imex_type not in uniform:
+                uniform[ts.imex_type] = ts.uniform_coefficients()
+            alpha, beta, _ = uniform[ts.imex_type]
+            ok = stiff_step_stable(alpha, beta, ratio) and stiff_step_stable(ts.alpha, ts.beta, ratio)
+            self._immersed_stable_memo = (key, ok)
+        return self._immersed_stable_memo[1]
+
+    def _step_immersed_bodies(self):
+        """before a step: the stability check, and the pose of t^n for bodies that move"""
+        bodies = getattr(self, "_immersed_bodies", None)
+        if bodies is None:
+            return
+        ts = self._time_stepping
+        ratio = ts.get_next_step_size() / bodies.eta
+        if not self._immersed_allow_stiff and not self._immersed_step_is_stable(ratio):
+            raise ValueError("immersed bodies: k / eta = %.6g exceeds %.6g, the stability bound of the explicit "
+                             "penalisation term for %s (raise eta, lower k, or pass allow_stiff=True)"
+                             % (ratio, self.immersed_step_bound(), ts.imex_type.name))
+        if not getattr(self, "_immersed_on_device", False):
+            self._push_immersed_bodies()
+        if bodies.moving:
+            try:
+                self._move_immersed_bodies()
+            except nat.NativeError as err:
+                raise RuntimeError(str(err))
+
     def _setup_function_spaces(self):
         if not hasattr(self, "_Wh"):
             super()._setup_function_spaces()
@@ -107,6 +197,8 @@ class IMEXIPCSSolver(InstationarySolverBase):
             self._update_time_stepping_coefficients()
         self._setup_boundary_conditions()
         self._push_viscosity_model()
+        if not getattr(self, "_immersed_on_device", False):
+            self._push_immersed_bodies()
         self._diffusion_solver = _DeviceSystem(self, nat.SYS_MOMENTUM)
         self._projection_solver = _DeviceSystem(self, nat.SYS_POISSON)
         self._velocity_correction_solver = _DeviceSystem(self, nat.SYS_CORRECTION)
@@ -119,6 +211,7 @@ class IMEXIPCSSolver(InstationarySolverBase):
         assert len(self._alpha) == 3 and len(self._beta) == 2 and len(self._gamma) == 3
         self._ctx.set_imex(self._alpha, self._beta, self._gamma, self._next_step_size)
         self._push_imex_rotation()
+        self._step_immersed_bodies()
 
     def _push_imex_rotation(self):
         """rotating frame: opt in and hand the device Omega(t^n), Omega(t^(n-1)) -- the levels the Coriolis term is

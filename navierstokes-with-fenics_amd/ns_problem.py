@@ -76,6 +76,10 @@ class ProblemBase:
     # (a model of viscosity_models.py) behind, which goes to the solver's set_viscosity_model where it has one
     _VISCOSITY_HOOK = "set_viscosity_model"
 
+    # A problem with solid bodies inside the domain defines ``set_immersed_bodies``; it leaves ``_immersed_bodies``
+    # (an immersed_bodies.ImmersedBodies) behind, which goes to the solver's set_immersed_bodies where it has one
+    _BODIES_HOOK = "set_immersed_bodies"
+
     def _call_hooks(self, order):
         """mesh, then the hooks named in ``order``; afterwards the consistency checks of the reference"""
         self.setup_mesh()
@@ -93,6 +97,8 @@ class ProblemBase:
                 getattr(self, hook)()
         if hasattr(self, self._VISCOSITY_HOOK):
             getattr(self, self._VISCOSITY_HOOK)()
+        if hasattr(self, self._BODIES_HOOK):
+            getattr(self, self._BODIES_HOOK)()
         if not hasattr(self, "_bcs"):
             assert hasattr(self, "_periodic_bcs")
         if hasattr(self, "_internal_constraints"):
@@ -126,6 +132,8 @@ class ProblemBase:
         setters"""
         if hasattr(self, "_viscosity_model") and hasattr(solver, "set_viscosity_model"):
             solver.set_viscosity_model(self._viscosity_model)
+        if hasattr(self, "_immersed_bodies") and hasattr(solver, "set_immersed_bodies"):
+            solver.set_immersed_bodies(self._immersed_bodies, getattr(self, "_immersed_allow_stiff", False))
         if hasattr(self, "_temperature_coefficients") and hasattr(solver, "set_scalar_coefficients"):
             solver.set_scalar_coefficients(**self._temperature_coefficients)
         if hasattr(self, "_temperature_bcs") and hasattr(solver, "set_scalar_boundary_conditions"):
@@ -389,6 +397,29 @@ class ProblemBase:
         except nat.NativeError as err:
             raise RuntimeError(str(err))
         return HostField(self._mesh, "model viscosity", "Cell", values)
+
+    def _compute_body_forces(self):
+        """per immersed body (``set_immersed_bodies``) the volume, the force the fluid exerts on it and its torque
+        about the body's centre for the current velocity, from the device (nsfem_body_forces):
+        [n_bodies, 1 + dim + ntorque].  New helper."""
+        import _native as nat
+        solver = self._get_solver()
+        try:
+            return solver._ctx.body_forces(nat.U0)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+
+    def _compute_body_mask(self):
+        """cell means of the solid indicator chi of the immersed bodies, from the device (nsfem_body_mask_cells).
+        New helper; valid for ``_add_to_field_output``."""
+        import _native as nat
+        from fem_function import HostField
+        solver = self._get_solver()
+        try:
+            values = solver._ctx.body_mask_cells()
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+        return HostField(self._mesh, "body mask", "Cell", values)
 
     def _compute_pressure_gradient(self):
         """grad of the P1 pressure: piecewise constant = its DG0 projection (:85-103)."""

@@ -1,0 +1,143 @@
+"""Timing record of the immersed bodies in the IMEX step.
+
+    python scripts/immersed_bodies_timing.py steps --n 512
+        the lid-driven cavity on n x n squares through ``IMEXIPCSSolver`` (SBDF2) with ``throughput_settings()``,
+        alternating no body and one disc of radius 0.1 (eta = k) in one process; wall clock of ``solver.solve()`` per
+        step, median and minimum of ``--steps`` steps after ``--warmup``; one JSON line per case.
+
+    rocprofv3 --kernel-trace -d DIR -- python scripts/immersed_bodies_timing.py kernels [--lib PATH]
+        ``--reps`` dispatches each of the penalisation kernel (k_penal_cell / k3_penal_cell + k_visc_gather, through
+        nsfem_body_residual) and of the convection kernel of the same dimension (k_conv_cell / k3_conv_cell, through
+        the generic nsfem_imex_rhs) on the cavity at n = 512 with one disc of radius 0.1 and on a 64^3 box with one ball
+        of radius 0.1, sharp and smoothed.  ``--lib``: another build of the library, to compare two builds.
+
+    python scripts/immersed_bodies_timing.py summary DIR
+        median, minimum and maximum per kernel name and grid size of the trace under DIR, microseconds.
+"""
+import argparse
+import contextlib
+import csv
+import glob
+import io
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, d) for d in ("navierstokes-with-fenics_amd", "tests", "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+os.environ.setdefault("NSFEM_NO_OUTPUT", "1")      # no XDMF files: the run is a timing
+
+
+def run_steps(args):
+    from immersed_bodies import Ball, ImmersedBodies
+    from ns_imex_solver import IMEXIPCSSolver
+    from problem_specs import build_problem
+    for round_ in range(args.rounds):
+        for name in ("plain", "disc"):
+            spec = dict(name=name, mesh=("cube", 2, args.n), scheme="ipcs", numbers=dict(Re=100.0),
+                        clock=dict(dt=args.dt, steps=args.warmup + args.steps),
+                        start={"velocity": (0.0, 0.0), "pressure": 0.0},
+                        bcs=[("no_slip", "left"), ("no_slip", "right"), ("no_slip", "bottom"),
+                             ("velocity", "top", (1.0, 0.0))])
+            problem = build_problem(spec)
+            if name == "disc":
+                bodies = ImmersedBodies([Ball((0.5, 0.5), 0.1)], args.dt, args.smoothing)
+
+                def set_immersed_bodies(self, bodies=bodies):
+                    self._immersed_bodies = bodies
+                type(problem).set_immersed_bodies = set_immersed_bodies
+            problem.set_solver_class(IMEXIPCSSolver)
+            problem.compute_cfl = False
+            problem.solver_settings = "throughput"
+            with contextlib.redirect_stdout(io.StringIO()):
+                problem.solve_problem()
+            solver = problem._get_solver()
+            ms = [1e3 * t for t in problem.step_wall_times[args.warmup:]]
+            out = dict(case=name, round=round_, n=args.n, dt=args.dt, steps=args.steps, warmup=args.warmup,
+                       step_ms=dict(median=statistics.median(ms), min=min(ms)), imex=solver._ctx.imex_info(),
+                       bodies=solver._ctx.body_info(), cg_momentum=solver.last_step_info.krylov_iterations_momentum)
+            if name == "disc":
+                out["forces"] = problem._compute_body_forces().tolist()
+            print(json.dumps(out), flush=True)
+
+
+def run_kernels(args):
+    import numpy as np
+    import _native as nat
+    if args.lib:
+        nat.load_library(args.lib)
+    from gpu_common import box, cavity_bc, context
+    from test_gpu_3d import box3, context3, lid_bc
+    from test_scalar_transport_host import smooth_fields
+    cases = [("2d", lambda: box(args.n, args.n), context, cavity_bc, (1, (0.5, 0.5), (0.1, ), (0.0, 0.0), 0.0)),
+             ("3d", lambda: box3((args.n3, ) * 3), context3, lid_bc,
+              (1, (0.5, 0.5, 0.5), (0.1, ), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)))]
+    for tag, make_mesh, make_ctx, bc, body in cases:
+        mesh, dm, marks = make_mesh()
+        u, _ = smooth_fields(dm.p2_coords)
+        ctx = make_ctx(mesh, dm)
+        try:
+            ctx.set_coeffs(1.0, 1.0, 0.01)
+            ctx.set_dirichlet(nat.VELOCITY, *bc(dm, marks))
+            ctx.set_dirichlet(nat.PRESSURE, np.zeros(0, np.int32), np.zeros(0))
+            ctx.set_imex((1.5, -2.0, 0.5), (2.0, -1.0), (1.0, 0.0, 0.0), 1.0e-3)
+            for slot in (nat.U1, nat.U2):
+                ctx.set_state(slot, u)
+            for eps in (0.0, args.smoothing):
+                ctx.set_bodies([body], 1.0e-3, eps)
+                for _ in range(args.reps):
+                    ctx.body_residual(nat.U1, 1.0)
+                vol = float(ctx.body_forces(nat.U1)[0, 0])
+                print(json.dumps(dict(case=tag, cells=int(mesh.cells.shape[0]), smoothing=eps, volume=vol,
+                                      touched_cells=int((ctx.body_mask_cells() > 0.0).sum()))), flush=True)
+            ctx.set_bodies([])
+            for _ in range(args.reps):
+                ctx.imex_rhs("generic", 0)
+        finally:
+            ctx.close()
+
+
+def run_summary(args):
+    """per kernel name AND grid size: the 2D and the 3D mesh launch the shared kernels with different grids"""
+    rows = {}
+    for path in glob.glob(os.path.join(args.dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path, newline="") as fh:
+            for r in csv.DictReader(fh):
+                key = (r["Kernel_Name"], int(r["Grid_Size_X"]))
+                rows.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3)
+    for name, grid in sorted(rows):
+        if any(w in name for w in args.match.split(",")):
+            v = rows[(name, grid)]
+            print("%6d  median %9.2f  min %9.2f  max %9.2f  grid %10d  %s" % (len(v), statistics.median(v), min(v), max(v),
+                                                                            grid, name))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="mode", required=True)
+    p = sub.add_parser("steps")
+    p.add_argument("--n", type=int, default=512)
+    p.add_argument("--dt", type=float, default=1.0e-3)
+    p.add_argument("--steps", type=int, default=30)
+    p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--rounds", type=int, default=2)
+    p.add_argument("--smoothing", type=float, default=0.0)
+    p = sub.add_parser("kernels")
+    p.add_argument("--n", type=int, default=512)
+    p.add_argument("--n3", type=int, default=64)
+    p.add_argument("--reps", type=int, default=30)
+    p.add_argument("--smoothing", type=float, default=0.01)
+    p.add_argument("--lib", default=None)
+    p = sub.add_parser("summary")
+    p.add_argument("dir")
+    p.add_argument("--match", default="penal,conv_cell,visc_gather,res_gather")
+    args = ap.parse_args()
+    dict(steps=run_steps, kernels=run_kernels, summary=run_summary)[args.mode](args)
+
+
+if __name__ == "__main__":
+    main()
