@@ -456,10 +456,16 @@ class NsfemContext:
         self._check(self._lib.nsfem_get_rhs(self._h, system, _dp(out), n))
         return out
 
-    def solve(self, system, rtol=1e-12, atol=1e-14, max_iter=20000, precond=0, check_every=1):
-        o = KrylovOpts(rtol, atol, max_iter, precond, check_every, 0)
+    def solve(self, system, rtol=1e-12, atol=1e-14, max_iter=20000, precond=0, check_every=1, first_check=0):
+        """a failed solve raises NativeError with the status in `code` (ERR_NOT_CONVERGED, ERR_BREAKDOWN, ...) and
+        what the solver reported up to then in `info`"""
+        o = KrylovOpts(rtol, atol, max_iter, precond, check_every, first_check)
         info = SolveInfo()
-        self._check(self._lib.nsfem_solve(self._h, system, C.byref(o), C.byref(info)))
+        try:
+            self._check(self._lib.nsfem_solve(self._h, system, C.byref(o), C.byref(info)))
+        except NativeError as err:
+            err.info = info
+            raise
         return info
 
     def default_step_opts(self):
