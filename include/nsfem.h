@@ -555,6 +555,42 @@ int nsfem_body_forces(nsfem_ctx* ctx, int velocity_slot, double* out);
 /* out = {bodies, element-kernel launches so far (steps, hook and cell means), stored vectors N(u2) that had to be
  * recomputed with bodies set, 0} */
 int nsfem_body_info(nsfem_ctx* ctx, int64_t out[4]);
+
+/* ---- heated immersed bodies: scalar penalisation in the convection kernel of nsfem_step_scalar_imex (new).
+ * Each body s of the set given to nsfem_set_bodies gets a thermal flag theta_s in {0, 1} and a temperature T_s; one
+ * eta_T > 0 holds for the set.  The scalar equation gains (chi theta / eta_T)(T - T_s), as the vector
+ *   H(T)_i = (1/eta_T) sum_K sum_q w_q |det J_K| chi(x_q) theta_win (T(x_q) - T_win) phi_i(x_q)
+ * with the rules of B(u) (7-point Radon on triangles, 15-point Keast on tetrahedra), x_q the affine image of the
+ * reference point, chi and the winning body as for B(u) (largest chi, lowest index on ties).  A point whose winner has
+ * theta = 0 adds nothing: that body stays thermally passive, as every body is without this call.  eta_T is used as
+ * given and nothing here checks k / eta_T; H has the sign of C(u) T.
+ * The term is explicit and rides with the convection, in ONE element launch: NSFEM_TCONV_1 = beta0 (C(u1) T1 + H^n(T1))
+ * with the pose of t^n; a NSFEM_TCONV_2 that has to be formed afresh uses the pose of t^(n-1), as N(u2) does.
+ * nsfem_move_bodies invalidates nothing.  The stored scalar vectors count as stale after a change of the flags, the
+ * temperatures of thermal bodies or eta_T, and -- while a body is thermal -- of the body set or the smoothing; the
+ * same data again is no change.  With no temperatures, or all flags 0, nsfem_step_scalar_imex launches exactly what
+ * it launches without this call.
+ * n must equal the number of bodies set; n = 0 removes the temperatures (the arrays may be NULL).  A later
+ * nsfem_set_bodies with ANOTHER count drops them; one with the same count keeps them, body by index.
+ * NSFEM_ERR_ARG: another n, a flag other than 0 / 1, a temperature that is not finite, eta_T <= 0 or not finite, no
+ * bodies set. */
+int nsfem_set_body_temperatures(nsfem_ctx* ctx, int32_t n, const int32_t* thermal, const double* temperature,
+                                double eta_T);
+/* test hook: out_host [n_p2] = weight (C(u) T + H(T)) from the fused element launch plus the node sums, u and T the
+ * given slots, form 0 standard / 1 skew-symmetric, pose 0 the bodies at t^n, 1 at t^(n-1).  No stored state is
+ * touched; two calls return the same bytes.  nsfem_scalar_convection keeps returning the convection alone.
+ * NSFEM_ERR_ARG: no bodies or no temperatures set, other slots, form or pose. */
+int nsfem_body_scalar_residual(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
+                               int pose /* 0: t^n, 1: t^(n-1) */, double* out_host /* [n_p2] */);
+/* out [n_bodies][3], per body s (pose of t^n): the volume int chi_s, the heat rate
+ * Q_s = (1/eta_T) int chi_s theta_s (T - T_s) the body takes from the fluid (0 for passive bodies) and int chi_s T,
+ * whose ratio to the volume is the mean temperature inside.  Each quadrature point counts for its winning body only,
+ * so sum_s Q_s = sum_i H(T)_i.  Bitwise reproducible.  NSFEM_ERR_ARG: no bodies or no temperatures set, scalar_slot
+ * not a scalar slot. */
+int nsfem_body_heat(nsfem_ctx* ctx, int scalar_slot, double* out /* [n_bodies][3] */);
+/* out = {thermal bodies (flag 1), fused element launches so far (steps and hook), stored scalar vectors recomputed
+ * because of a change of the thermal data or the body set, 0} */
+int nsfem_body_heat_info(nsfem_ctx* ctx, int64_t out[4]);
 /* replaces _advance_solution (ns_solver_base.py:1012-1016, ns_ipcs_solver.py:35-43); scheme 0 with a scalar
  * configured: also T2 <- T1 <- T0 and the stored scalar convection */
 int nsfem_advance(nsfem_ctx* ctx, int scheme /* 0 ipcs, 1 bdf */);

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
     "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
     "nsfem_body_info",
+    "nsfem_set_body_temperatures", "nsfem_body_scalar_residual", "nsfem_body_heat", "nsfem_body_heat_info",
     "nsfem_set_point_locator", "nsfem_locate_points", "nsfem_eval_points",
     "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
     "nsfem_stats_enable", "nsfem_stats_sample", "nsfem_stats_get", "nsfem_stats_set_groups", "nsfem_stats_profiles",
@@ -220,6 +221,10 @@ def load_library(path=None):
         "nsfem_body_mask_cells": (C.c_int, [vp, pd]),
         "nsfem_body_forces": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_body_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_body_temperatures": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_int32), pd, dbl]),
+        "nsfem_body_scalar_residual": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, C.c_int, pd]),
+        "nsfem_body_heat": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_body_heat_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_viscous_form": (C.c_int, [vp, C.c_int]),
         "nsfem_set_convective_form": (C.c_int, [vp, C.c_int, C.c_int]),
         "nsfem_set_state": (C.c_int, [vp, C.c_int, pd, i64]),
@@ -647,6 +652,37 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_body_info(self._h, out))
         return dict(bodies=int(out[0]), element_launches=int(out[1]), recomputed=int(out[2]))
+
+    # -- heated immersed bodies (scalar penalisation in the convection kernel) -----------
+    def set_body_temperatures(self, thermal, temperatures, eta_scalar=1.0):
+        """flag (0 passive, 1 thermal) and temperature per body set, one eta_T; empty lists remove them"""
+        flags = np.ascontiguousarray(thermal, dtype=np.int32).ravel()
+        values = np.ascontiguousarray(temperatures, dtype=np.float64).ravel()
+        assert flags.size == values.size
+        self._check(self._lib.nsfem_set_body_temperatures(self._h, flags.size, _ip(flags), _dp(values),
+                                                          float(eta_scalar)))
+
+    def body_scalar_residual(self, velocity_slot=U1, scalar_slot=T1, form=0, weight=1.0, pose=0):
+        """test hook: weight * (C(u) T + H(T)), [n_p2], from the fused element launch; pose 0 the bodies at t^n, 1 at
+        t^(n-1); no stored state touched"""
+        out = np.empty(self.n_p2, dtype=np.float64)
+        self._check(self._lib.nsfem_body_scalar_residual(self._h, int(velocity_slot), int(scalar_slot), int(form),
+                                                         float(weight), int(pose), _dp(out)))
+        return out
+
+    def body_heat(self, scalar_slot=T0):
+        """[n_bodies, 3]: volume, heat rate the body takes from the fluid (0 for passive bodies), int chi_s T"""
+        n = self.body_info()["bodies"]
+        out = np.empty((max(n, 1), 3), dtype=np.float64)
+        self._check(self._lib.nsfem_body_heat(self._h, int(scalar_slot), _dp(out)))
+        return out[:n]
+
+    def body_heat_info(self):
+        """dict(thermal, fused_launches, recomputed): bodies with flag 1, fused element launches so far and how often
+        a stored scalar vector had to be recomputed because the thermal data or the body set changed"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_body_heat_info(self._h, out))
+        return dict(thermal=int(out[0]), fused_launches=int(out[1]), recomputed=int(out[2]))
 
     def step_bdf(self, opts=None):
         o = opts or self.default_step_opts()

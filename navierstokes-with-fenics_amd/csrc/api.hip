@@ -586,7 +586,11 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   // scalar transport: the stored convection vectors follow the levels (velocity and scalar) they were evaluated at
   if (slot == NSFEM_U1 || slot == NSFEM_T1 || slot == NSFEM_TCONV_1) ctx->sc.conv1_fresh = false;
   if (slot == NSFEM_U2 || slot == NSFEM_T2) ctx->sc.conv2_valid = false;
-  if (slot == NSFEM_TCONV_2) { ctx->sc.conv2_valid = true; ctx->sc.conv2_weight = 1.0; ctx->sc.conv_form = -2; }
+  if (slot == NSFEM_TCONV_2) {
+    ctx->sc.conv2_valid = true; ctx->sc.conv2_weight = 1.0; ctx->sc.conv_form = -2;
+    ctx->sc.conv_thermal_epoch = ctx->bodies.thermal_epoch;
+    ctx->sc.conv_body_epoch = ctx->bodies.epoch;
+  }
   if (slot == NSFEM_T_SOURCE) ctx->sc.have_source = true;
   API_END(ctx)
 }
@@ -2796,6 +2800,21 @@ static void body_to_table(const nsfem_body& b, int dim, BodyTable& t, int s, boo
   for (int a = 0; a < 3; ++a) t.size[s][a] = size[a];
 }
 
+// Heated bodies: t becomes the table (have: temperatures are set).  The epoch counts the changes of what the scalar
+// step's kernels see -- the table where a flag is 1, nothing where none is --, so the same data again, or passive
+// bodies coming and going, leave the stored scalar vectors valid
+static void store_thermal(nsfem_ctx::Bodies& b, const ThermalTable& t, bool have) {
+  int n_thermal = 0;
+  for (int s = 0; s < t.n; ++s) n_thermal += t.flag[s];
+  const ThermalTable none;
+  const ThermalTable& seen_new = n_thermal > 0 ? t : none;
+  const ThermalTable& seen_old = b.n_thermal > 0 ? b.thermal : none;
+  if (std::memcmp(&seen_new, &seen_old, sizeof(ThermalTable)) != 0) ++b.thermal_epoch;
+  std::memcpy(&b.thermal, &t, sizeof(ThermalTable));
+  b.have_thermal = have;
+  b.n_thermal = n_thermal;
+}
+
 extern "C" int nsfem_set_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bodies, double eta, double smoothing) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
@@ -2822,6 +2841,8 @@ extern "C" int nsfem_set_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bod
   if (std::memcmp(&t, &b.cur, sizeof(BodyTable)) != 0 || std::memcmp(&t, &b.prev, sizeof(BodyTable)) != 0) ++b.epoch;
   std::memcpy(&b.cur, &t, sizeof(BodyTable));
   std::memcpy(&b.prev, &t, sizeof(BodyTable));
+  // (temperatures belong to the bodies by index: another count drops them)
+  if (b.have_thermal && b.thermal.n != n) store_thermal(b, ThermalTable(), false);
   API_END(ctx)
 }
 
@@ -2904,6 +2925,89 @@ extern "C" int nsfem_body_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[0] = ctx->bodies.cur.n;
   out[1] = ctx->bodies.launches;
   out[2] = ctx->bodies.recomputed;
+  out[3] = 0;
+  API_END(ctx)
+}
+
+// ---------------------------------------------------------------- heated bodies
+extern "C" int nsfem_set_body_temperatures(nsfem_ctx* ctx, int32_t n, const int32_t* thermal, const double* temperature,
+                                           double eta_T) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  nsfem_ctx::Bodies& b = ctx->bodies;
+  ThermalTable t;
+  if (n != 0) {
+    NSFEM_REQUIRE(b.cur.n > 0, "heated bodies: no body set (nsfem_set_bodies)");
+    NSFEM_REQUIRE(n == b.cur.n, "heated bodies: nsfem_set_body_temperatures with another count than bodies set");
+    NSFEM_REQUIRE(thermal && temperature, "heated bodies: null flag or temperature array");
+    NSFEM_REQUIRE(std::isfinite(eta_T) && eta_T > 0.0, "heated bodies: eta_T must be finite and > 0");
+    t.n = n;
+    for (int s = 0; s < n; ++s) {
+      NSFEM_REQUIRE(thermal[s] == 0 || thermal[s] == 1, "heated bodies: flag must be 0 (passive) or 1 (thermal)");
+      NSFEM_REQUIRE(std::isfinite(temperature[s]), "heated bodies: temperature not finite");
+      t.flag[s] = thermal[s];
+      t.temperature[s] = thermal[s] ? temperature[s] : 0.0;      // (a passive body's temperature is read nowhere)
+    }
+    t.inv_eta = 1.0 / eta_T;
+  }
+  store_thermal(b, t, n != 0);
+  API_END(ctx)
+}
+
+static void heated_require(nsfem_ctx* ctx, int scalar_slot) {
+  NSFEM_REQUIRE(!ctx->comm, "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->bodies.cur.n != 0, "immersed bodies: no body set (nsfem_set_bodies)");
+  NSFEM_REQUIRE(ctx->bodies.have_thermal, "heated bodies: no temperatures set (nsfem_set_body_temperatures)");
+  NSFEM_REQUIRE(scalar_slot >= NSFEM_T0 && scalar_slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
+}
+
+extern "C" int nsfem_body_scalar_residual(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
+                                          int pose, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  heated_require(ctx, scalar_slot);
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
+  NSFEM_REQUIRE(pose == 0 || pose == 1, "heated bodies: pose must be 0 (t^n) or 1 (t^(n-1))");
+  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  hipStream_t s = ctx->stream;
+  ensure_scalar_slot(ctx, scalar_slot);
+  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
+  ctx->kw.ensure(nvel(ctx));
+  ++ctx->kw.touch;
+  double* out = ctx->kw.q.p;
+  launch_scalar_convection_heated(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form,
+                                  pose == 0 ? ctx->bodies.cur : ctx->bodies.prev, ctx->bodies.thermal, out);
+  ++ctx->bodies.fused_launches;
+  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * ctx->mesh.n_p2, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_body_heat(nsfem_ctx* ctx, int scalar_slot, double* out) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  heated_require(ctx, scalar_slot);
+  hipStream_t s = ctx->stream;
+  ensure_scalar_slot(ctx, scalar_slot);
+  const size_t n_out = (size_t)ctx->bodies.cur.n * 3;
+  const size_t n_work = n_out * (kBodyParts + 1);
+  if (ctx->bodies.heat_work.n != n_work) ctx->bodies.heat_work.alloc(n_work);
+  double* parts = ctx->bodies.heat_work.p;
+  double* res = parts + n_out * kBodyParts;
+  launch_body_heat(s, ctx->mesh, ctx->state[scalar_slot].p, ctx->bodies.cur, ctx->bodies.thermal, parts, res);
+  NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_body_heat_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->bodies.n_thermal;
+  out[1] = ctx->bodies.fused_launches;
+  out[2] = ctx->bodies.thermal_recomputed;
   out[3] = 0;
   API_END(ctx)
 }
@@ -2991,13 +3095,26 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   }
   // beta1 C(u2) T2: the vector the previous step stored (beta0' C(u1) T1 then), unless a level, a stored vector or
   // the form changed under it
+  // Heated bodies (nsfem_set_body_temperatures, at least one flag 1): the same launches form C(u) T + H(T), with the
+  // pose of the level (cur for T1, prev for a T2 vector formed afresh); the stored vectors are stale after a change
+  // of the thermal table or, while a body is thermal, of the body set.  Without a thermal body: the launches of old
+  nsfem_ctx::Bodies& bd = ctx->bodies;
+  const bool heated = bd.n_thermal > 0 && bd.cur.n > 0;
   double f2 = 0.0;
   if (b1 != 0.0) {
-    const bool stored = sc.conv2_valid && sc.conv2_weight != 0.0 && (sc.conv_form == -2 || sc.conv_form == sc.form);
-    if (stored) {
+    const bool usable = sc.conv2_valid && sc.conv2_weight != 0.0 && (sc.conv_form == -2 || sc.conv_form == sc.form);
+    const bool same_heat = sc.conv_thermal_epoch == bd.thermal_epoch && (!heated || sc.conv_body_epoch == bd.epoch);
+    if (usable && same_heat) {
       ++sc.conv_reuses;
     } else {
-      launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, ctx->state[NSFEM_TCONV_2].p);
+      if (usable) ++bd.thermal_recomputed;
+      if (heated) {
+        launch_scalar_convection_heated(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, bd.prev, bd.thermal,
+                                        ctx->state[NSFEM_TCONV_2].p);
+        ++bd.fused_launches;
+      } else {
+        launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, ctx->state[NSFEM_TCONV_2].p);
+      }
       ++sc.conv_launches;
       sc.conv2_weight = 1.0;
       sc.conv2_valid = true;
@@ -3005,11 +3122,19 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
     f2 = b1 / sc.conv2_weight;
   }
   // beta0 C(u1) T1: beta0 rides in the kernel's weight, the node sums are the stored copy
-  launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p);
+  if (heated) {
+    launch_scalar_convection_heated(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, bd.cur, bd.thermal,
+                                    ctx->state[NSFEM_TCONV_1].p);
+    ++bd.fused_launches;
+  } else {
+    launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p);
+  }
   ++sc.conv_launches;
   sc.conv1_fresh = true;
   sc.conv1_weight = b0;
   sc.conv_form = sc.form;
+  sc.conv_thermal_epoch = bd.thermal_epoch;
+  sc.conv_body_epoch = bd.epoch;
   if (b1 != 0.0) launch_lincomb3(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, -f2, ctx->state[NSFEM_TCONV_2].p, rhs);
   else launch_axpby(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, rhs);
   // Dirichlet rows T_i = g_i; start vector T1 with the Dirichlet values (as the IMEX diffusion step)

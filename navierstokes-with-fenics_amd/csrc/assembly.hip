@@ -784,11 +784,17 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 //   FORM 1 (skew-symmetric)  r_i = wgt/2 int [ (u . grad T) phi_i - (u . grad phi_i) T ]      (= 1/2 (C - C^T) T)
 // The element vector goes node-sorted into the first 6 n_cells doubles of m.rbuf (ndst, as k_conv_cell);
 // k_scalar_gather sums the run of every node in ascending cell order: no atomics, the same state gives the same bytes.
-template <int FORM>
+// PENAL 1 (sharp masks) / 2 (smoothed): heated bodies (nsfem_set_body_temperatures) -- the same launch adds
+//   wgt/eta_T sum_q w_q |det J| chi(x_q) theta_win (T(x_q) - T_win) phi_i(x_q)
+// x_q the affine image of the reference point, chi and the winner from body_winner (bodies.hpp) as in k_penal_cell;
+// x_q, the winner, chi and T_q are formed once per quadrature point, points with chi = 0 or a passive winner add
+// nothing.  PENAL 0 takes no table at all and is the code of every run without temperatures.
+template <int FORM, int PENAL>
 __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                           const int32_t* __restrict__ p2,
                                                           const double* __restrict__ u,
                                                           const double* __restrict__ T, double wgt,
+                                                          const ScalarPenalArgs<PENAL> pa,
                                                           const int32_t* __restrict__ ndst,
                                                           double* __restrict__ rbuf) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -802,6 +808,17 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
     ux[k] = a.x;
     uy[k] = a.y;
     t[k] = T[node];
+  }
+  // (reach: can the support of any body touch the cell?  body_misses_cell, bodies.hpp -- most cells skip the winner)
+  double xv[3][2];
+  bool reach = false;
+  if constexpr (PENAL != 0) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      xv[v][0] = vx[(size_t)(2 * v) * nc + c];
+      xv[v][1] = vx[(size_t)(2 * v + 1) * nc + c];
+    }
+    for (int s = 0; s < pa.bt.n; ++s) reach = reach || !body_misses_cell<2>(pa.bt, s, xv);
   }
   double r[6];
 #pragma unroll
@@ -817,7 +834,7 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
       uqy += ph * uy[k];
       dtx += gx[k] * t[k];
       dty += gy[k] * t[k];
-      if (FORM == 1) tq += ph * t[k];
+      if (FORM == 1 || PENAL != 0) tq += ph * t[k];
     }
     const double w = c_q.w[q] * g.adet * wgt;
     const double adv = uqx * dtx + uqy * dty;           // u . grad T
@@ -829,6 +846,19 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
         const double ugi = uqx * gx[i] + uqy * gy[i];   // u . grad phi_i
         r[i] += 0.5 * w * (c_q.phi2[q][i] * adv - ugi * tq);
       }
+    }
+    if constexpr (PENAL != 0) {
+      if (!reach) continue;
+      double x[2];
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+        x[a] = c_q.phi1[q][0] * xv[0][a] + c_q.phi1[q][1] * xv[1][a] + c_q.phi1[q][2] * xv[2][a];
+      int win;
+      const double chi = body_winner<2, PENAL == 2>(pa.bt, x, win);
+      if (!(chi > 0.0) || pa.th.flag[win] == 0) continue;
+      const double h = w * pa.th.inv_eta * chi * (tq - pa.th.temperature[win]);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) r[i] += h * c_q.phi2[q][i];
     }
   }
 #pragma unroll
@@ -874,11 +904,30 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
   } else {
     const dim3 grid(grid_for(m.n_cells)), block(kBlock);
     if (form == 0)
-      hipLaunchKernelGGL((k_scalar_conv_cell<0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
-                         m.rbuf.p);
+      hipLaunchKernelGGL((k_scalar_conv_cell<0, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
+                         ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
     else
-      hipLaunchKernelGGL((k_scalar_conv_cell<1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
-                         m.rbuf.p);
+      hipLaunchKernelGGL((k_scalar_conv_cell<1, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
+                         ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
+  }
+  hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
+  NSFEM_HIP(hipGetLastError());
+}
+
+void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                                     int form, const BodyTable& bt, const ThermalTable& th, double* out) {
+  NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
+  NSFEM_REQUIRE(bt.n > 0 && th.n == bt.n, "heated bodies: no temperatures set for the bodies");
+  if (m.dim == 3) {
+    scalar_convection_heated_cells_3d(s, m, u, T, weight, form, bt, th);
+  } else {
+    const dim3 grid(grid_for(m.n_cells)), block(kBlock);
+#define NSFEM_SCH(F, P) \
+  hipLaunchKernelGGL((k_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<P>{bt, th}, m.ndst.p, m.rbuf.p)
+    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH(0, 2); else NSFEM_SCH(1, 2); }
+    else { if (form == 0) NSFEM_SCH(0, 1); else NSFEM_SCH(1, 1); }
+#undef NSFEM_SCH
   }
   hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
   NSFEM_HIP(hipGetLastError());

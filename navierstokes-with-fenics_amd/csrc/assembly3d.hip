@@ -847,11 +847,14 @@ void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double w
 // doubles of m.rbuf; the caller sums the node runs (k_scalar_gather).
 // FORM 0 does not keep the gradients of a quadrature point (the test functions need phi_i only): grad T_q is summed
 // as they are formed.
-template <int FORM>
+// PENAL 1 / 2: heated bodies, as k_scalar_conv_cell (assembly.hip) -- the same launch adds
+// wgt/eta_T sum_q w_q |det J| chi(x_q) theta_win (T(x_q) - T_win) phi_i(x_q); PENAL 0 takes no table.
+template <int FORM, int PENAL>
 __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                            const int32_t* __restrict__ p2,
                                                            const double* __restrict__ u,
                                                            const double* __restrict__ T, double wgt,
+                                                           const ScalarPenalArgs<PENAL> pa,
                                                            const int32_t* __restrict__ ndst,
                                                            double* __restrict__ rbuf) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -864,6 +867,15 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
 #pragma unroll
     for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
     t[k] = T[node];
+  }
+  double xv[4][3];
+  bool reach = false;                    // (can the support of any body touch the cell?  As k_scalar_conv_cell)
+  if constexpr (PENAL != 0) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) xv[v][d] = vx[(size_t)(3 * v + d) * nc + c];
+    for (int s = 0; s < pa.bt.n; ++s) reach = reach || !body_misses_cell<3>(pa.bt, s, xv);
   }
   double r[10];
 #pragma unroll
@@ -882,7 +894,7 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
         dt[a] += gl[a] * t[k];
         if constexpr (FORM == 1) gk[k][a] = gl[a];
       }
-      if (FORM == 1) tq += ph * t[k];
+      if (FORM == 1 || PENAL != 0) tq += ph * t[k];
     }
     const double w = c_q3.w[q] * g.adet * wgt;
     const double adv = uq[0] * dt[0] + uq[1] * dt[1] + uq[2] * dt[2];       // u . grad T
@@ -895,6 +907,20 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
         r[i] += 0.5 * w * (c_q3.phi2[q][i] * adv - ugi * tq);
       }
     }
+    if constexpr (PENAL != 0) {
+      if (!reach) continue;
+      double x[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        x[a] = c_q3.phi1[q][0] * xv[0][a] + c_q3.phi1[q][1] * xv[1][a] + c_q3.phi1[q][2] * xv[2][a] +
+               c_q3.phi1[q][3] * xv[3][a];
+      int win;
+      const double chi = body_winner<3, PENAL == 2>(pa.bt, x, win);
+      if (!(chi > 0.0) || pa.th.flag[win] == 0) continue;
+      const double h = w * pa.th.inv_eta * chi * (tq - pa.th.temperature[win]);
+#pragma unroll
+      for (int i = 0; i < 10; ++i) r[i] += h * c_q3.phi2[q][i];
+    }
   }
 #pragma unroll
   for (int i = 0; i < 10; ++i) rbuf[ndst[(size_t)i * nc + c]] = r[i];
@@ -904,11 +930,23 @@ void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u
                                 int form) {
   const dim3 grid(grid3(m.n_cells)), block(kBlock);
   if (form == 0)
-    hipLaunchKernelGGL((k3_scalar_conv_cell<0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
-                       m.rbuf.p);
+    hipLaunchKernelGGL((k3_scalar_conv_cell<0, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
+                       ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
   else
-    hipLaunchKernelGGL((k3_scalar_conv_cell<1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, m.ndst.p,
-                       m.rbuf.p);
+    hipLaunchKernelGGL((k3_scalar_conv_cell<1, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
+                       ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
+  NSFEM_HIP(hipGetLastError());
+}
+
+void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T,
+                                       double weight, int form, const BodyTable& bt, const ThermalTable& th) {
+  const dim3 grid(grid3(m.n_cells)), block(kBlock);
+#define NSFEM_SCH3(F, P) \
+  hipLaunchKernelGGL((k3_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<P>{bt, th}, m.ndst.p, m.rbuf.p)
+  if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3(0, 2); else NSFEM_SCH3(1, 2); }
+  else { if (form == 0) NSFEM_SCH3(0, 1); else NSFEM_SCH3(1, 1); }
+#undef NSFEM_SCH3
   NSFEM_HIP(hipGetLastError());
 }
 

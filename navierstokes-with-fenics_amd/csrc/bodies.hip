@@ -105,6 +105,67 @@ __global__ __launch_bounds__(256) void k_penal_forces(int nc, const double* __re
         ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
 }
 
+// Heated bodies (nsfem_set_body_temperatures): per body the volume int chi_s, the heat rate
+// Q_s = (1/eta_T) int chi_s theta_s (T - T_s) the body takes from the fluid (0 for a passive body) and int chi_s T,
+// with the rule, the points and the winner of k_scalar_conv_cell<FORM, PENAL> / k3_scalar_conv_cell: a point counts
+// for its winning body only, so sum_s Q_s = sum_i H(T)_i.  Shape and reduction of k_penal_forces.
+// parts[(s 3 + j) kBodyParts + block]
+template <int DIM, bool SMOOTH>
+__global__ __launch_bounds__(256) void k_body_heat(int nc, const double* __restrict__ vx,
+                                                   const int32_t* __restrict__ p2, const double* __restrict__ T,
+                                                   const BodyTable bt, const ThermalTable th,
+                                                   double* __restrict__ parts) {
+  constexpr int N2 = DIM == 2 ? 6 : 10, NQ = DIM == 2 ? 7 : 15, NO = 3;
+  __shared__ double sh[4][NO];
+  const int s = blockIdx.y;
+  const double scale = th.flag[s] != 0 ? th.inv_eta : 0.0, ts = th.temperature[s];
+  double acc[NO] = {0.0, 0.0, 0.0};
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x) {
+    double xv[DIM + 1][DIM];
+#pragma unroll
+    for (int v = 0; v <= DIM; ++v)
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) xv[v][d] = vx[(size_t)(DIM * v + d) * nc + c];
+    if (body_misses_cell<DIM>(bt, s, xv)) continue;
+    double adet;
+    if constexpr (DIM == 2) adet = load_geo(vx, nc, c).adet;
+    else adet = load_geo3(vx, nc, c).adet;
+    double t[N2];
+#pragma unroll
+    for (int k = 0; k < N2; ++k) t[k] = T[(size_t)p2[(size_t)k * nc + c]];
+    for (int q = 0; q < NQ; ++q) {
+      double x[DIM];
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) {
+        double xa = 0.0;
+#pragma unroll
+        for (int v = 0; v <= DIM; ++v) xa += (DIM == 2 ? c_bq.phi1[q][v] : c_bq3.phi1[q][v]) * xv[v][a];
+        x[a] = xa;
+      }
+      int win;
+      const double chi = body_winner<DIM, SMOOTH>(bt, x, win);
+      if (!(chi > 0.0) || win != s) continue;
+      double tq = 0.0;
+#pragma unroll
+      for (int k = 0; k < N2; ++k) tq += (DIM == 2 ? c_bq.phi2[q][k] : c_bq3.phi2[q][k]) * t[k];
+      const double w = (DIM == 2 ? c_bq.w[q] : c_bq3.w[q]) * adet * chi;
+      acc[0] += w;
+      acc[1] += w * scale * (tq - ts);
+      acc[2] += w * tq;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NO; ++j) {
+    double v = acc[j];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][j] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NO)
+    parts[((size_t)s * NO + threadIdx.x) * gridDim.x + blockIdx.x] =
+        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
 // out[b] = sum of the n_parts partials of number b: one wave per number, lane l adds its n_parts / 64 consecutive
 // partials in index order, then the xor-shuffle tree (a fixed order, as k_vol_finish)
 __global__ __launch_bounds__(64) void k_penal_finish(int n_parts, const double* __restrict__ parts,
@@ -132,6 +193,23 @@ void launch_penalty_forces(hipStream_t s, const MeshDev& m, const double* u, con
   }
   NSFEM_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_penal_finish, dim3(bt.n * body_numbers(m.dim)), dim3(64), 0, s, kBodyParts, parts, out);
+  NSFEM_HIP(hipGetLastError());
+}
+
+void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const BodyTable& bt, const ThermalTable& th,
+                      double* parts, double* out) {
+  NSFEM_REQUIRE(bt.n > 0 && th.n == bt.n, "heated bodies: no temperatures set for the bodies");
+  const dim3 grid(kBodyParts, bt.n), block(256);
+  const bool smooth = bt.eps > 0.0;
+  if (m.dim == 3) {
+    if (smooth) hipLaunchKernelGGL((k_body_heat<3, true>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, T, bt, th, parts);
+    else hipLaunchKernelGGL((k_body_heat<3, false>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, T, bt, th, parts);
+  } else {
+    if (smooth) hipLaunchKernelGGL((k_body_heat<2, true>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, T, bt, th, parts);
+    else hipLaunchKernelGGL((k_body_heat<2, false>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, T, bt, th, parts);
+  }
+  NSFEM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_penal_finish, dim3(bt.n * 3), dim3(64), 0, s, kBodyParts, parts, out);
   NSFEM_HIP(hipGetLastError());
 }
 

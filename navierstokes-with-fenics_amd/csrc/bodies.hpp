@@ -1,7 +1,8 @@
 // Immersed bodies (nsfem_set_bodies, include/nsfem.h): the ONE copy of the signed distances, the mask and the
 // "largest chi wins" rule that the penalisation element kernels of both dimensions (k_penal_cell, assembly.hip;
-// k3_penal_cell, assembly3d.hip) and the force kernel (k_penal_forces, bodies.hip) inline.  The body table is a kernel
-// argument: its entries are read with wave-uniform indices, i.e. as scalar loads.
+// k3_penal_cell, assembly3d.hip) and the force kernel (k_penal_forces, bodies.hip) inline -- and, for heated bodies, the
+// scalar convection kernels with PENAL != 0 (k_scalar_conv_cell / k3_scalar_conv_cell) and k_body_heat.  The body table
+// is a kernel argument: its entries are read with wave-uniform indices, i.e. as scalar loads.
 #pragma once
 #include "nsfem_internal.hpp"
 

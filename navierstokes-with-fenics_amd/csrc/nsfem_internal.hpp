@@ -475,6 +475,35 @@ struct BodyTable {
   double velocity[NSFEM_MAX_BODIES][3] = {}, angular[NSFEM_MAX_BODIES][3] = {};
   double eps = 0.0, inv_eta = 0.0;
 };
+// heated bodies (nsfem_set_body_temperatures): flag theta_s in {0, 1} and temperature T_s per body of the table,
+// inv_eta = 1 / eta_T.  A kernel argument beside the BodyTable, read with the same wave-uniform indices.  Rows of
+// passive bodies hold temperature 0, so that what is compared (memcmp; store_thermal, api.hip) is what the kernels
+// can see
+struct ThermalTable {
+  int32_t n = 0;
+  int32_t flag[NSFEM_MAX_BODIES] = {};
+  int32_t pad_ = 0;                  // (no padding bytes)
+  double temperature[NSFEM_MAX_BODIES] = {};
+  double inv_eta = 0.0;
+};
+// what the scalar convection kernels take when they add H(T): nothing at all without it (PENAL 0)
+template <int PENAL>
+struct ScalarPenalArgs {
+  BodyTable bt;
+  ThermalTable th;
+};
+template <>
+struct ScalarPenalArgs<0> {};
+// out = weight (C(u) T + H(T)): the fused element kernel k_scalar_conv_cell<FORM, PENAL> / k3_scalar_conv_cell (PENAL
+// 1 sharp, 2 smoothed masks; bt the pose that belongs to the level of T) plus k_scalar_gather
+void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                                     int form, const BodyTable& bt, const ThermalTable& th, double* out);
+void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T,
+                                       double weight, int form, const BodyTable& bt, const ThermalTable& th);
+// k_body_heat + k_penal_finish (bodies.hip): out[s][3] = {int chi_s, Q_s, int chi_s T} in device memory, parts
+// [n 3 kBodyParts] work space
+void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const BodyTable& bt, const ThermalTable& th,
+                      double* parts, double* out);
 // numbers per body of nsfem_body_forces: volume, dim force components, 1 (2D) or 3 torque components
 inline int body_numbers(int dim) { return dim == 2 ? 4 : 7; }
 constexpr int kBodyParts = 256;
@@ -1114,6 +1143,14 @@ struct nsfem_ctx {
     nsfem::BodyTable cur, prev;
     int64_t epoch = 0, launches = 0, recomputed = 0;
     nsfem::DevBuf<double> work;     // partials and results of nsfem_body_forces
+    // heated bodies (nsfem_set_body_temperatures): with a thermal body the stored scalar vectors carry H(T) as
+    // well.  have_thermal: temperatures are set (n_thermal of them with flag 1); thermal_epoch counts the changes of
+    // what the step's kernels see: the table with a thermal body, nothing without one
+    nsfem::ThermalTable thermal;
+    bool have_thermal = false;
+    int n_thermal = 0;
+    int64_t thermal_epoch = 0, fused_launches = 0, thermal_recomputed = 0;
+    nsfem::DevBuf<double> heat_work;   // partials and results of nsfem_body_heat
   } bodies;
   int64_t conv_n_body = 0;
   // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the
@@ -1140,6 +1177,8 @@ struct nsfem_ctx {
     bool conv1_fresh = false, conv2_valid = false;   // TCONV_1 written since the last advance / TCONV_2 usable
     double conv1_weight = 0.0, conv2_weight = 0.0;
     int conv_form = -1;                              // form the stored vectors belong to
+    // heated bodies: bodies.thermal_epoch and (read only while a thermal body is set) bodies.epoch of the stored vectors
+    int64_t conv_thermal_epoch = 0, conv_body_epoch = 0;
     int64_t matrix_builds = 0, conv_launches = 0, conv_reuses = 0;
     int dict_used = 0;
     bool dinv_dirty = true;                          // 1 / diagonal belongs to an older matrix or Dirichlet set

@@ -9,6 +9,12 @@ price is a bound on k / eta, ``stiff_step_bound``.
 A body is a ``Ball`` (disc in 2D), an axis-aligned ``Box`` or a ``HalfSpace``; ``ImmersedBodies`` collects up to 16
 of them with eta and the smoothing and goes to ``IMEXIPCSSolver.set_immersed_bodies``.  A body with ``motion`` (a
 function t -> (centre, velocity, angular velocity)) is moved by the solver before every step.
+
+Heated bodies: a body with a ``temperature`` T_s is thermal -- where a scalar is transported
+(``BoussinesqIMEXSolver``) its equation gains (chi / eta_scalar) (T - T_s), evaluated explicitly inside the scalar
+convection kernel (``nsfem_set_body_temperatures``) and bounded by the same ``stiff_step_bound`` on
+k / eta_scalar.  A body without a temperature is thermally passive: the scalar passes through it as through fluid.
+``IMEXIPCSSolver`` without a scalar ignores the temperatures.
 """
 import math
 
@@ -28,7 +34,7 @@ def _vector(name, value, dim=None):
 class _Body:
     kind = None
 
-    def __init__(self, centre, size, velocity=None, angular=None, motion=None):
+    def __init__(self, centre, size, velocity=None, angular=None, motion=None, temperature=None):
         self.centre = _vector("centre", centre)
         self.dim = self.centre.size
         self.size = self._check_size(size)
@@ -37,6 +43,12 @@ class _Body:
         if motion is not None and not callable(motion):
             raise ValueError("motion must be a function t -> (centre, velocity, angular)")
         self.motion = motion
+        if temperature is not None:
+            temperature = float(temperature)
+            if not math.isfinite(temperature):
+                raise ValueError("temperature must be a finite number or None, got %r" % (temperature, ))
+        #: T_s of a thermal body; None: thermally passive
+        self.temperature = temperature
 
     def _check_angular(self, angular):
         w = np.atleast_1d(np.asarray(angular, dtype=np.float64)).ravel()
@@ -50,7 +62,8 @@ class _Body:
         if self.motion is None:
             return self
         centre, velocity, angular = self.motion(float(t))
-        moved = type(self)(centre, self.size if self.kind != KIND_BALL else self.size[0], velocity, angular)
+        moved = type(self)(centre, self.size if self.kind != KIND_BALL else self.size[0], velocity, angular,
+                           temperature=self.temperature)
         if moved.dim != self.dim:
             raise ValueError("motion changed the dimension of the body")
         return moved
@@ -122,9 +135,10 @@ def mask(distance, smoothing=0.0):
 
 
 class ImmersedBodies:
-    """up to 16 bodies of one dimension, the penalisation parameter ``eta`` > 0 and the smoothing half width >= 0"""
+    """up to 16 bodies of one dimension, the penalisation parameter ``eta`` > 0 and the smoothing half width >= 0;
+    ``eta_scalar`` > 0 is the eta_T of the thermal bodies (None: ``eta``)"""
 
-    def __init__(self, bodies, eta, smoothing=0.0):
+    def __init__(self, bodies, eta, smoothing=0.0, eta_scalar=None):
         bodies = list(bodies)
         if not 1 <= len(bodies) <= MAX_BODIES:
             raise ValueError("ImmersedBodies: 1 to %d bodies, got %d" % (MAX_BODIES, len(bodies)))
@@ -135,12 +149,27 @@ class ImmersedBodies:
             raise ValueError("ImmersedBodies: eta must be finite and > 0, got %r" % (eta, ))
         if not (math.isfinite(smoothing) and smoothing >= 0.0):
             raise ValueError("ImmersedBodies: smoothing must be finite and >= 0, got %r" % (smoothing, ))
-        self.bodies, self.eta, self.smoothing = bodies, eta, smoothing
+        eta_scalar = eta if eta_scalar is None else float(eta_scalar)
+        if not (math.isfinite(eta_scalar) and eta_scalar > 0.0):
+            raise ValueError("ImmersedBodies: eta_scalar must be finite and > 0, got %r" % (eta_scalar, ))
+        self.bodies, self.eta, self.smoothing, self.eta_scalar = bodies, eta, smoothing, eta_scalar
         self.dim = bodies[0].dim
 
     @property
     def moving(self):
         return any(b.motion is not None for b in self.bodies)
+
+    @property
+    def thermal(self):
+        """is any body thermal (has a temperature)?"""
+        return any(b.temperature is not None for b in self.bodies)
+
+    def temperatures(self):
+        """(flags, values) of ``NsfemContext.set_body_temperatures``: flag 1 and T_s for a thermal body, 0 and 0.0
+        for a passive one"""
+        flags = np.array([0 if b.temperature is None else 1 for b in self.bodies], dtype=np.int32)
+        values = np.array([0.0 if b.temperature is None else b.temperature for b in self.bodies])
+        return flags, values
 
     def rows(self, t=None):
         """the rows of ``NsfemContext.set_bodies`` / ``move_bodies``, at time t where a body has a motion"""

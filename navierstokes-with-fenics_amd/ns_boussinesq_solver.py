@@ -17,6 +17,11 @@ alpha_0/k, gamma_0 or kappa change.  The reference has no transported quantity: 
 cases prescribe the body force.  Partitioned meshes are refused by the device driver.  Rotating
 frames (rotating convection) run as in ``IMEXIPCSSolver``: explicit Coriolis term, opted in by the
 solver when an angular velocity has been set.
+
+Heated bodies: immersed bodies with a ``temperature`` (``immersed_bodies``) add the explicit term
+H(T) = (chi / eta_scalar) (T - T_s) to the transport step, inside the convection launch.
+The solver pushes the temperatures wherever it pushes the bodies and holds k / eta_scalar to the same
+stability test as k / eta.
 """
 import numpy as np
 
@@ -124,6 +129,29 @@ class BoussinesqIMEXSolver(IMEXIPCSSolver):
             self._push_scalar_boundary_conditions(t)
         if hasattr(self, "_scalar_source") and self._moves_in_time(self._scalar_source):
             self._push_scalar_source(t)
+
+    # ------------------------------------------------------------------ heated bodies
+    def _push_immersed_bodies(self):
+        """the bodies as ``IMEXIPCSSolver`` pushes them, then their temperatures (none: removed)"""
+        super()._push_immersed_bodies()
+        if not (hasattr(self, "_ctx") and hasattr(self, "_immersed_bodies")):
+            return
+        bodies = self._immersed_bodies
+        try:
+            if bodies is None or not bodies.thermal:
+                self._ctx.set_body_temperatures([], [])
+            else:
+                flags, values = bodies.temperatures()
+                self._ctx.set_body_temperatures(flags, values, bodies.eta_scalar)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+
+    def _immersed_ratios(self, bodies, k):
+        """with a thermal body k / eta_scalar is held to the test of k / eta: the scalar recursion is the same"""
+        ratios = super()._immersed_ratios(bodies, k)
+        if bodies.thermal:
+            ratios += (("k / eta_scalar", k / bodies.eta_scalar), )
+        return ratios
 
     # ------------------------------------------------------------------ set-up
     def _setup_function_spaces(self):

@@ -93,7 +93,8 @@ class IMEXIPCSSolver(InstationarySolverBase):
         k / eta above ``stiff_step_bound`` of the scheme's coefficients (always the case for CNLF) raises ValueError
         unless ``allow_stiff``.  Bodies with a ``motion`` are moved to t^n once before every step; a set handed over in
         the middle of a run goes to the device with its poses of t^(n-1) and t^n.  Partitioned meshes are refused by
-        the device driver."""
+        the device driver.  Temperatures of the bodies (heated bodies) act on a transported scalar only: this class has
+        none and ignores them, ``BoussinesqIMEXSolver`` pushes them with the bodies."""
         assert bodies is None or isinstance(bodies, ImmersedBodies)
         self._immersed_bodies = bodies
         self._immersed_allow_stiff = bool(allow_stiff)
@@ -141,18 +142,24 @@ class IMEXIPCSSolver(InstationarySolverBase):
         alpha, beta, _ = ts.uniform_coefficients()
         return min(stiff_step_bound(alpha, beta), stiff_step_bound(ts.alpha, ts.beta))
 
-    def _immersed_step_is_stable(self, ratio):
-        """k / eta = ratio against the current and the uniform-step coefficients: two root solves, and none while
-        coefficients and ratio stay what they were at the last step (uniform steps).  With adaptive steps every step
-        asks anew, at the cost of the two root solves"""
+    def _immersed_ratios(self, bodies, k):
+        """the ratios held to the stability test, as (name, value) pairs: k / eta of the flow's term here; a solver
+        with a transported scalar adds k / eta_scalar"""
+        return (("k / eta", k / bodies.eta), )
+
+    def _immersed_step_is_stable(self, ratio, ratio_scalar=None):
+        """k / eta = ratio (and k / eta_scalar = ratio_scalar, where a body is thermal) against the current and the
+        uniform-step coefficients: two root solves each, and none while coefficients and ratios stay what they were at
+        the last step (uniform steps).  With adaptive steps every step asks anew, at the cost of the root solves"""
         ts = self._time_stepping
-        key = (ts.imex_type, tuple(ts.alpha), tuple(ts.beta), ratio)
+        key = (ts.imex_type, tuple(ts.alpha), tuple(ts.beta), ratio, ratio_scalar)
         if getattr(self, "_immersed_stable_memo", (None, None))[0] != key:
             uniform = self.__dict__.setdefault("_immersed_uniform", {})
             if ts.imex_type not in uniform:
                 uniform[ts.imex_type] = ts.uniform_coefficients()
             alpha, beta, _ = uniform[ts.imex_type]
-            ok = stiff_step_stable(alpha, beta, ratio) and stiff_step_stable(ts.alpha, ts.beta, ratio)
+            ok = all(stiff_step_stable(alpha, beta, x) and stiff_step_stable(ts.alpha, ts.beta, x)
+                     for x in (ratio, ratio_scalar) if x is not None)
             self._immersed_stable_memo = (key, ok)
         return self._immersed_stable_memo[1]
 
@@ -162,11 +169,12 @@ class IMEXIPCSSolver(InstationarySolverBase):
         if bodies is None:
             return
         ts = self._time_stepping
-        ratio = ts.get_next_step_size() / bodies.eta
-        if not self._immersed_allow_stiff and not self._immersed_step_is_stable(ratio):
-            raise ValueError("immersed bodies: k / eta = %.6g exceeds %.6g, the stability bound of the explicit "
+        ratios = self._immersed_ratios(bodies, ts.get_next_step_size())
+        if not self._immersed_allow_stiff and not self._immersed_step_is_stable(*(x for _, x in ratios)):
+            name, ratio = next(((n, x) for n, x in ratios if not self._immersed_step_is_stable(x)), ratios[0])
+            raise ValueError("immersed bodies: %s = %.6g exceeds %.6g, the stability bound of the explicit "
                              "penalisation term for %s (raise eta, lower k, or pass allow_stiff=True)"
-                             % (ratio, self.immersed_step_bound(), ts.imex_type.name))
+                             % (name, ratio, self.immersed_step_bound(), ts.imex_type.name))
         if not getattr(self, "_immersed_on_device", False):
             self._push_immersed_bodies()
         if bodies.moving:

@@ -409,6 +409,20 @@ class ProblemBase:
         except nat.NativeError as err:
             raise RuntimeError(str(err))
 
+    def _compute_body_heat(self):
+        """per immersed body the volume, the heat rate Q_s the body takes from the fluid (0 for a body without a
+        temperature) and the mean temperature inside it, for the current scalar, from the device (nsfem_body_heat):
+        [n_bodies, 3].  Needs a solver with a transported scalar and temperatures on the bodies.  New helper."""
+        import _native as nat
+        solver = self._get_solver()
+        try:
+            heat = solver._ctx.body_heat(nat.T0)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+        # (a body that lies outside the mesh has no volume and no mean temperature: NaN)
+        heat[:, 2] = np.divide(heat[:, 2], heat[:, 0], out=np.full(heat.shape[0], np.nan), where=heat[:, 0] > 0.0)
+        return heat
+
     def _compute_body_mask(self):
         """cell means of the solid indicator chi of the immersed bodies, from the device (nsfem_body_mask_cells).
         New helper; valid for ``_add_to_field_output``."""

@@ -1,0 +1,341 @@
+"""Heated immersed bodies (scalar penalisation inside the scalar convection kernel): the numpy restatements -- the
+oracles of tests/test_gpu_heated_bodies.py -- and what can be checked without a GPU.
+
+The term (include/nsfem.h), for a P2 scalar T, bodies with masks chi_s, thermal flags theta_s in {0, 1}
+and temperatures T_s; at a point the body with the largest chi counts (lowest index on ties):
+
+    H(T)_i = (1/eta_T) sum_K sum_q w_q |det J_K| chi(x_q) theta_win (T(x_q) - T_win) phi_i(x_q)
+
+with the Radon / Keast rules of tests/test_variable_viscosity_host.py (``rule_space``) and x_q the affine image of the
+reference point, exactly as B(u) of tests/test_immersed_bodies_host.py.
+
+Clearances.  The GPU tests use the bodies ``bodies_2d`` / ``bodies_3d`` on the boxes whose quadrature clearance
+tests/test_immersed_bodies_host.py pins (>= 1.2e-4 in 2D, >= 1e-5 in 3D), so nothing is left to prove for them.  The
+mapped box(8, 8) is not among those: its nearest Radon point lies 5.2e-5 from the surface of the box body, below the
+2D bound, so the GPU tests run that mesh with the smoothed mask only."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import fem_oracle as fo
+from imex_time_stepping import IMEXTimeStepping, IMEXType
+from immersed_bodies import Ball, Box, HalfSpace, ImmersedBodies
+from test_immersed_bodies_host import BODY_NAMES, _recursion, bodies_2d, bodies_3d, cube, square
+from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
+
+NO_BC = (np.zeros(0, np.int64), np.zeros(0))
+#: temperatures of the bodies of the GPU tests, by index in the set
+BODY_TEMPERATURES = (0.9, -0.35)
+
+
+# ---------------------------------------------------------------- the restatements
+class ScalarPenalRestatement:
+    """``space`` from ``rule_space``, ``bodies`` an ImmersedBodies whose thermal bodies carry a ``temperature``;
+    ``t``: the time of the pose of moving bodies"""
+
+    def __init__(self, space, bodies, t=None):
+        self.s, self.bodies = space, bodies
+        s = space
+        nv = s.dim + 1
+        assert s.cells.shape[1] == nv and s.phi1.shape == (len(s.wts), nv)
+        self.xq = np.einsum("qv,cvd->cqd", s.phi1, s.coords[s.cells])          # affine image of the rule's points
+        chi, win = bodies.winner(self.xq.reshape(-1, s.dim), t)
+        self.chi, self.win = chi.reshape(self.xq.shape[:2]), win.reshape(self.xq.shape[:2])
+        flags, values = bodies.temperatures()
+        self.theta, self.ts = flags.astype(np.float64)[self.win], values[self.win]      # [c, q] of the winner
+        self.inv_eta = 1.0 / bodies.eta_scalar
+
+    def _tq(self, T):
+        return np.einsum("qk,ck->cq", self.s.phi2, T[self.s.p2])
+
+    def _density(self, T):
+        """chi theta_win (T - T_win) / eta_T at the quadrature points, [c, q]"""
+        return self.chi * self.theta * (self._tq(T) - self.ts) * self.inv_eta
+
+    def residual(self, T):
+        he = np.einsum("cq,cq,qi->ci", self.s.wdet, self._density(T), self.s.phi2)
+        h = np.zeros(self.s.n2)
+        np.add.at(h, self.s.p2.ravel(), he.ravel())
+        return h
+
+    def heat(self, T):
+        """[n_bodies, 3]: the volume int chi_s, the heat rate Q_s, int chi_s T"""
+        dens, tq = self._density(T), self._tq(T)
+        out = np.zeros((len(self.bodies.bodies), 3))
+        for i in range(out.shape[0]):
+            w = self.s.wdet * (self.win == i)
+            out[i] = (float((w * self.chi).sum()), float((w * dens).sum()), float((w * self.chi * tq).sum()))
+        return out
+
+
+class ScalarIMEXPenalRestatement(ScalarIMEXRestatement):
+    """ScalarIMEXRestatement whose stored explicit vector is C(u) T + H(T): ``penal`` is a ScalarPenalRestatement
+    (None: no thermal body).  For moving bodies the caller replaces ``penal`` by the pose of t^n before each step; the
+    stored N2 keeps the pose it was formed with, and one that has to be formed afresh takes ``penal_prev`` (None: the
+    pose of ``penal``)."""
+
+    def __init__(self, space, diffusivity, form="standard", penal=None):
+        super().__init__(space, diffusivity, form)
+        self.penal, self.penal_prev = penal, None
+
+    def explicit(self, u, T, penal):
+        N = self.convection_matrix(u) @ T
+        return N + penal.residual(T) if penal is not None else N
+
+    def step(self, alpha, beta, gamma, k, u1, u2, bc=NO_BC):
+        T1, T2 = self.T[1], self.T[2]
+        self.N1 = self.explicit(u1, T1, self.penal)
+        N2 = self.N2
+        if N2 is None:
+            older = self.penal_prev if self.penal_prev is not None else self.penal
+            N2 = self.explicit(u2, T2, older) if beta[1] != 0.0 else np.zeros_like(T1)
+        b = self.M @ (alpha[1] * T1 + alpha[2] * T2) / k + self.kappa * (self.K @ (gamma[1] * T1 + gamma[2] * T2))
+        b += beta[0] * self.N1 + beta[1] * N2
+        rhs = -b
+        if self.source is not None:
+            rhs += self.M @ self.source
+        A = (alpha[0] / k) * self.M + gamma[0] * self.kappa * self.K
+        self.T[0] = fo.linear_solve_dirichlet(A.tocsr(), rhs, *bc)
+
+
+def heated(bodies, temperatures=BODY_TEMPERATURES, passive=()):
+    """the bodies with temperatures by index; indices in ``passive`` stay without one"""
+    for i, b in enumerate(bodies):
+        b.temperature = None if i in passive else float(temperatures[i])
+    return bodies
+
+
+def heated_set(dim, name, eta, eps, eta_scalar, moving=False):
+    """the body sets of the GPU kernel tests: ``bodies_2d`` / ``bodies_3d`` with temperatures; in ``overlap`` the
+    disc is thermal and the box passive"""
+    bodies = (bodies_2d if dim == 2 else bodies_3d)(name, moving)
+    return ImmersedBodies(heated(bodies, passive=(1, ) if name == "overlap" else ()), eta, eps, eta_scalar)
+
+
+def _meshes(dim):
+    if dim == 2:
+        mesh, dm, marks, s = square(4)
+    else:
+        mesh, dm, s = cube((3, 2, 2), (1.0, 0.8, 0.6))
+    return dm, s
+
+
+# ---------------------------------------------------------------- tests
+@pytest.mark.parametrize("dim", (2, 3))
+def test_a_thermal_half_space_over_the_whole_mesh_gives_the_mass_matrix(dim):
+    """chi = 1 everywhere: H(T) = (M T - T_s M 1) / eta_T; the integrand has degree 4, the rules degree 5: 1e-14 of
+    the largest entry (the flow analogue measures 2e-16 to 4e-16)"""
+    dm, s = _meshes(dim)
+    hs = HalfSpace((2.0, 0.0, 0.0)[:dim], (1.0, 0.0, 0.0)[:dim], temperature=0.7)
+    _, T = smooth_fields(dm.p2_coords)
+    eta_T = 0.037
+    got = ScalarPenalRestatement(s, ImmersedBodies([hs], 1.0, eta_scalar=eta_T)).residual(T)
+    M = s.mass_p2()
+    want = (M @ T - 0.7 * (M @ np.ones(s.n2))) / eta_T
+    err = np.abs(got - want).max() / np.abs(want).max()
+    print("full thermal half-space dim %d: %.2e of the largest entry" % (dim, err))
+    assert err < 1e-14
+
+
+@pytest.mark.parametrize("dim", (2, 3))
+def test_a_scalar_at_the_body_temperature_feels_nothing(dim):
+    """T = T_s (a constant: in P2): |H| below 1e-14 of the H of T = 0"""
+    dm, s = _meshes(dim)
+    orc = ScalarPenalRestatement(s, heated_set(dim, "disc", 1.0, 0.07, 0.01))
+    same = np.abs(orc.residual(np.full(s.n2, BODY_TEMPERATURES[0]))).max()
+    rest = np.abs(orc.residual(np.zeros(s.n2))).max()
+    print("T = T_s dim %d: %.2e of %.2e" % (dim, same, rest))
+    assert rest > 1e-3 and same < 1e-14 * rest
+
+
+@pytest.mark.parametrize("dim", (2, 3))
+def test_passive_bodies_give_exactly_zero(dim):
+    """no body with a temperature: H = 0 exactly.  ``overlap`` with the disc thermal and the box passive: the points the
+    box wins -- some of them inside the disc -- add nothing, i.e. H is that of the disc alone with those points
+    struck out"""
+    dm, s = _meshes(dim) if dim == 3 else square(8)[1::2]
+    _, T = smooth_fields(dm.p2_coords)
+    make = bodies_2d if dim == 2 else bodies_3d
+    for name in BODY_NAMES:
+        orc = ScalarPenalRestatement(s, ImmersedBodies(make(name), 1.0, 0.07, 0.02))
+        assert not orc.bodies.thermal and orc.chi.max() > 0.0
+        assert not orc.residual(T).any() and not orc.heat(T)[:, 1].any()
+    both = ScalarPenalRestatement(s, heated_set(dim, "overlap", 1.0, 0.07, 0.02))
+    alone = ScalarPenalRestatement(s, ImmersedBodies(heated(make("overlap")[:1]), 1.0, 0.07, 0.02))
+    taken = (both.win == 1) & (both.chi > 0.0) & (alone.chi > 0.0)
+    assert taken.sum() >= 3 and not both._density(T)[both.win == 1].any()
+    # (where the disc wins its chi is the winning chi: the densities agree bit for bit)
+    dens = np.where(both.win == 0, alone._density(T), 0.0)
+    assert np.array_equal(dens, both._density(T)) and np.abs(dens).max() > 1e-3
+    assert both.heat(T)[1, 1] == 0.0 and both.heat(T)[1, 0] > 0.0
+
+
+@pytest.mark.parametrize("dim", (2, 3))
+@pytest.mark.parametrize("name", BODY_NAMES)
+def test_node_sums_equal_the_heat_rates(dim, name):
+    """sum_i phi_i = 1, so sum_i H_i = sum_s Q_s: to n_entries * 2.2e-16 * sum |H_i|"""
+    dm, s = _meshes(dim) if dim == 3 else square(8)[1::2]
+    _, T = smooth_fields(dm.p2_coords)
+    orc = ScalarPenalRestatement(s, heated_set(dim, name, 1.0, 0.07, 0.02))
+    H, Q = orc.residual(T), orc.heat(T)
+    assert np.abs(Q[:, 1]).max() > 1e-3 and (Q[:, 0] > 0.0).all()
+    assert abs(H.sum() - Q[:, 1].sum()) <= H.size * 2.2e-16 * np.abs(H).sum()
+
+
+@pytest.mark.parametrize("typ", (IMEXType.SBDF2, IMEXType.CNAB, IMEXType.mCNAB), ids=lambda t: t.name)
+def test_thermal_decay_follows_the_scalar_recursion(typ):
+    """fully masked box(4, 4), kappa = 0, u = 0, no Dirichlet node: nothing but the term acts, H = M (T - T_s) / eta_T,
+    and every step multiplies T - T_s at all 81 nodes (a smooth, non-uniform field) as the scalar recursion of the
+    scheme's coefficients does; 8 steps to 1e-12"""
+    mesh, dm, marks, s = square(4)
+    base = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+    k, eta_T, T_s = 0.1, 0.25, 0.6
+    hs = HalfSpace((2.0, 0.0), (1.0, 0.0), temperature=T_s)
+    penal = ScalarPenalRestatement(s, ImmersedBodies([hs], 1.0, eta_scalar=eta_T))
+    orc = ScalarIMEXPenalRestatement(base, 0.0, penal=penal)
+    d0 = smooth_fields(dm.p2_coords)[1]
+    assert dm.n_p2 == 81 and d0.max() > 1.5 * d0.min() > 0.0
+    orc.T[1], orc.T[2] = T_s + d0, T_s + d0
+    u = np.zeros(2 * dm.n_p2)
+    ts = IMEXTimeStepping(0.0, 1.0e9, typ, desired_start_time_step=k)
+    y1 = y2 = 1.0
+    worst = 0.0
+    for _ in range(8):
+        ts.update_coefficients()
+        y0 = _recursion(ts.alpha, ts.beta, k / eta_T, y1, y2)
+        orc.step(ts.alpha, ts.beta, ts.gamma, k, u, u)
+        worst = max(worst, float(np.abs(orc.T[0] - T_s - y0 * d0).max()))
+        orc.advance()
+        ts.advance_time()
+        y1, y2 = y0, y1
+    print("thermal decay %s: y after 8 steps %.6e, worst difference %.2e" % (typ.name, y1, worst))
+    assert 0.0 < abs(y1) < 0.2 and worst < 1e-12
+
+
+def test_steady_heat_balance_of_a_heated_disc():
+    """box(8, 8), u = 0, kappa = 1, T = 0 on all four walls, a smoothed thermal disc (centre (0.5, 0.5), r = 0.2,
+    eps = 0.07, T_s = 1: r + eps = 0.27 leaves 0.23 to every wall, more than one cell of 0.125, so H_i = 0 on the
+    Dirichlet nodes), eta_T = k = 1/16, SBDF2 until max |T^(n+1) - T^n| <= 1e-13 max |T|, within 400 steps.  At the
+    steady state kappa K T + H(T) = 0 on the free rows; the columns of K sum to zero and H vanishes on the walls, so
+    sum_s Q_s = sum_{i Dirichlet} kappa (K T)_i exactly: asserted to 1e-9 of |Q| (measured: see the print, DESIGN.md
+    4p).  The disc gives heat (Q < 0) and its mean temperature lies between 0.5 and 1."""
+    mesh, dm, marks, s = square(8)
+    base = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+    k = 1.0 / 128.0
+    bodies = ImmersedBodies([Ball((0.5, 0.5), 0.2, temperature=1.0)], 1.0, 0.07, eta_scalar=k)
+    penal = ScalarPenalRestatement(s, bodies)
+    orc = ScalarIMEXPenalRestatement(base, 1.0, penal=penal)
+    walls = np.unique(np.concatenate([dm.facet_p2_nodes(marks.facets_with_id(m)).ravel() for m in (1, 2, 3, 4)]))
+    assert walls.size == 64 and not penal.residual(np.ones(s.n2))[walls].any()
+    bc = (walls, np.zeros(walls.size))
+    u = np.zeros(2 * s.n2)
+    ts = IMEXTimeStepping(0.0, 1.0e9, IMEXType.SBDF2, desired_start_time_step=k)
+    steps = 0
+    while True:
+        ts.update_coefficients()
+        orc.step(ts.alpha, ts.beta, ts.gamma, k, u, u, bc)
+        steps += 1
+        change = np.abs(orc.T[0] - orc.T[1]).max() / np.abs(orc.T[0]).max()
+        orc.advance()
+        ts.advance_time()
+        if change <= 1e-13:
+            break
+        assert steps < 400, change
+    T = orc.T[1]
+    heat = penal.heat(T)[0]
+    wall_flux = float((orc.K @ T)[walls].sum())
+    mean = heat[2] / heat[0]
+    print("steady heat balance: %d steps, Q %.12e, wall sum %.12e, residual %.2e of |Q|, mean T inside %.4f" % (
+        steps, heat[1], wall_flux, abs(heat[1] - wall_flux) / abs(heat[1]), mean))
+    assert steps <= 400
+    assert abs(heat[1] - wall_flux) <= 1e-9 * abs(heat[1])
+    assert heat[1] < 0.0 and 0.5 < mean < 1.0
+
+
+# ---------------------------------------------------------------- layers
+def test_every_layer_carries_the_feature():
+    """the C header declares the four entry points, _native lists and binds them and leaves nsfem_body alone, the body
+    classes take a temperature, the Boussinesq solver pushes the temperatures with the bodies and holds k / eta_scalar
+    to the stability test, the problem base has the output helper"""
+    import _native as nat
+    from ns_boussinesq_solver import BoussinesqIMEXSolver
+    from ns_imex_solver import IMEXIPCSSolver
+    from ns_problem import ProblemBase
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "nsfem.h")) as fh:
+        header = fh.read()
+    names = ("nsfem_set_body_temperatures", "nsfem_body_scalar_residual", "nsfem_body_heat", "nsfem_body_heat_info")
+    for name in names:
+        assert re.search(r"\bint\s+%s\s*\(\s*nsfem_ctx\s*\*" % name, header), name
+        assert name in nat.EXPORTED_SYMBOLS
+    assert [f[0] for f in nat.Body._fields_] == ["kind", "centre", "size", "velocity", "angular"]
+    assert ctypes.sizeof(nat.Body) == 8 + 12 * 8
+    for method in ("set_body_temperatures", "body_scalar_residual", "body_heat", "body_heat_info"):
+        assert callable(getattr(nat.NsfemContext, method))
+    assert BoussinesqIMEXSolver._push_immersed_bodies is not IMEXIPCSSolver._push_immersed_bodies
+    assert BoussinesqIMEXSolver._immersed_ratios is not IMEXIPCSSolver._immersed_ratios
+    assert BoussinesqIMEXSolver.set_immersed_bodies is IMEXIPCSSolver.set_immersed_bodies
+    assert callable(ProblemBase._compute_body_heat)
+    csrc = os.path.join(root, "navierstokes-with-fenics_amd", "csrc")
+    with open(os.path.join(csrc, "Makefile")) as fh:
+        assert "bodies.hip" in fh.read()
+    for source, kernel in (("assembly.hip", "k_scalar_conv_cell<F, P>"), ("assembly3d.hip", "k3_scalar_conv_cell<F, P>"),
+                           ("bodies.hip", "k_body_heat<")):
+        with open(os.path.join(csrc, source)) as fh:
+            assert kernel in fh.read(), (source, kernel)
+    # the Python objects
+    hot = Ball((0.2, 0.3), 0.1, temperature=1.5, motion=lambda t: ((0.2 + t, 0.3), (1.0, 0.0), 0.5))
+    cold = Box((0.5, 0.5), (0.1, 0.2))
+    set_ = ImmersedBodies([hot, cold], 0.01, 0.02)
+    assert set_.thermal and set_.eta_scalar == set_.eta == 0.01
+    flags, values = set_.temperatures()
+    assert flags.dtype == np.int32 and flags.tolist() == [1, 0] and values.tolist() == [1.5, 0.0]
+    assert hot.at(0.25).temperature == 1.5 and hot.at(0.25).centre.tolist() == [0.45, 0.3]
+    assert len(set_.rows(0.25)[0]) == 5                                   # (rows() is what it was)
+    assert ImmersedBodies([hot], 0.01, eta_scalar=0.5).eta_scalar == 0.5
+    assert not ImmersedBodies([cold], 1.0).thermal
+    for bad in (float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            Ball((0.0, 0.0), 1.0, temperature=bad)
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            ImmersedBodies([hot], 1.0, eta_scalar=bad)
+
+
+def test_the_step_check_holds_the_scalar_ratio_to_the_same_bound():
+    """BoussinesqIMEXSolver: with a thermal body k / eta_scalar joins k / eta in the stability test (and in the memo
+    key); without one, or in IMEXIPCSSolver, it does not"""
+    from grid_generator import hyper_cube
+    from ns_boussinesq_solver import BoussinesqIMEXSolver
+    from ns_imex_solver import IMEXIPCSSolver
+    mesh, marks = hyper_cube(2, 4)
+    k = 0.1
+
+    def solver(cls, typ=IMEXType.SBDF2):
+        return cls(mesh, marks, "standard", IMEXTimeStepping(0.0, 1.0, typ, desired_start_time_step=k))
+
+    hot = Ball((0.5, 0.5), 0.2, temperature=1.0)
+    fine = ImmersedBodies([hot], k / 1.0, eta_scalar=k / 1.3)
+    stiff = ImmersedBodies([hot], k / 1.0, eta_scalar=k / 1.4)
+    passive = ImmersedBodies([Ball((0.5, 0.5), 0.2)], k / 1.0, eta_scalar=k / 1.4)
+    b = solver(BoussinesqIMEXSolver)
+    assert [n for n, _ in b._immersed_ratios(fine, k)] == ["k / eta", "k / eta_scalar"]
+    assert len(b._immersed_ratios(passive, k)) == 1 and len(solver(IMEXIPCSSolver)._immersed_ratios(stiff, k)) == 1
+    b._time_stepping.update_coefficients()
+    for bodies, ok in ((fine, True), (stiff, False), (passive, True)):
+        ratios = [x for _, x in b._immersed_ratios(bodies, k)]
+        assert b._immersed_step_is_stable(*ratios) is ok
+        assert b._immersed_stable_memo[0][-2:] == (ratios[0], ratios[1] if len(ratios) > 1 else None)
+    b.set_immersed_bodies(stiff)
+    with pytest.raises(ValueError, match="k / eta_scalar"):
+        b._step_immersed_bodies()
+    b.set_immersed_bodies(stiff, allow_stiff=True)
+    b._step_immersed_bodies()
+    leap = solver(BoussinesqIMEXSolver, IMEXType.CNLF)
+    leap._time_stepping.update_coefficients()
+    leap.set_immersed_bodies(ImmersedBodies([hot], 1.0e3 * k, eta_scalar=1.0e3 * k))
+    with pytest.raises(ValueError, match="CNLF"):
+        leap._step_immersed_bodies()
