@@ -211,7 +211,12 @@ void* nsfem_state_devptr(nsfem_ctx* ctx, int slot);   /* device pointer (plumbin
 
 /* ---- the explicit assembly seam (_assemble_system) ------------
  * Assembles matrix and right-hand side / residual of one system from the current
- * state; replaces the implicit dolfin assemble() inside *VariationalSolver.solve() */
+ * state; replaces the implicit dolfin assemble() inside *VariationalSolver.solve().
+ * NSFEM_SYS_MONOLITHIC (single contexts, multigrid hierarchy attached): the Newton residual of nsfem_step_bdf about
+ * U0 / P in a mixed vector of nvel + npre entries (nsfem_get_rhs, nsfem_residual_norm), the Jacobian and the block
+ * preconditioner's hierarchies; flags bit 0: a new time step, bit 1: the Jacobian is applied matrix-free.
+ * nsfem_solve then runs the step's block-preconditioned BiCGStab from zero with the caller's options and subtracts
+ * the solution from U0 and P: one Newton iteration of nsfem_step_bdf. */
 int nsfem_assemble(nsfem_ctx* ctx, int system, uint32_t flags);
 /* 2-norm of the assembled residual / rhs (Dirichlet rows: x_i - g_i for Newton) */
 int nsfem_residual_norm(nsfem_ctx* ctx, int system, double* out);
@@ -870,6 +875,16 @@ int nsfem_smoother_info(nsfem_ctx* ctx, int64_t out[4]);
    levels in use, ghost lattice lines of the finest level as bottom * 256 + top}.  New functionality (the reference has no preconditioner: sparse LU,
    source/ns_ipcs_solver.py:171,205). */
 int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double* z);   /* which = 2: fast diagonalisation */
+/* which = 3 / 4 (single contexts): the two pressure hierarchies of the monolithic block preconditioner, refreshed as
+   nsfem_step_bdf refreshes them -- 3 the Schur hierarchy (Dirichlet set NSFEM_PRESSURE_PRECOND; geometric or
+   nsfem_mg_set_schur_operator levels), 4 the pressure mass smoother (four Chebyshev-Jacobi steps).  nsfem_mg_info:
+   which = 4 / 5 the record of which = 0 / 1 for these two, which = 6 / 7 the record of which = 2 / 3.
+   Test hook nsfem_monolithic_apply (single contexts), host vectors of nvel + npre entries: what = 0: y = the mixed
+   operator [[J, -c_p D^T], [-c_p D, 0]] of nsfem_step_bdf's linear solve applied to x, linearised about U0 with the
+   context's convective form and Picard flag, identity rows on Dirichlet dofs; what = 1: y = the block-triangular
+   Cahouet-Chabard preconditioner applied to x.  matrix_free != 0: the velocity Jacobian is applied matrix-free.
+   Prepares what that linear solve prepares; writes no state slot. */
+int nsfem_monolithic_apply(nsfem_ctx* ctx, int what, int matrix_free, const double* x, double* y);
 /* Direct solver of the projection step on tensor-product lattices (replaces the sparse LU of
    source/ns_ipcs_solver.py:160-171 where it applies): Vx [W x W], Vy [H x H] generalised eigenvectors of the 1D
    stiffness / lumped-mass pairs of the two directions (row-major, V^T W V = I, zero rows on Dirichlet sides),

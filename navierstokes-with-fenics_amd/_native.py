@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_mg_set_schur_operator", "nsfem_mg_set_schur_mode", "nsfem_set_halo_lists", "nsfem_smoother_info", "nsfem_mg_set_global_index", "nsfem_comm_allreduce", "nsfem_mg_add_global_level", "nsfem_cfl_number", "nsfem_set_angular_velocity", "nsfem_set_angular_velocity_3d", "nsfem_profile_smoother", "nsfem_profile_smoother_detail", "nsfem_profile_convection", "nsfem_jacobian_info", "nsfem_jacobian_table_check", "nsfem_set_preconditioner_shift", "nsfem_poisson_solve", "nsfem_p2_mass_bounds", "nsfem_mg_set_truncation", "nsfem_comm_stats", "nsfem_mg_set_halo_mode", "nsfem_set_overlap", "nsfem_comm_overlapped", "nsfem_boundary_force",
     "nsfem_set_partition", "nsfem_comm_unique_id", "nsfem_comm_attach_rccl",
     "nsfem_comm_local_create", "nsfem_comm_local_destroy", "nsfem_comm_attach_local", "nsfem_comm_attach_shm",
-    "nsfem_mg_apply", "nsfem_mg_info", "nsfem_poisson_set_fast_diag", "nsfem_poisson_set_fast_diag_rows",
+    "nsfem_mg_apply", "nsfem_mg_info", "nsfem_monolithic_apply", "nsfem_poisson_set_fast_diag", "nsfem_poisson_set_fast_diag_rows",
     "nsfem_poisson_set_fast_diag_3d", "nsfem_poisson_set_fast_diag_3d_planes", "nsfem_poisson_fast_diag_3d_info",
     "nsfem_operator_diagonal",
     "nsfem_set_imex", "nsfem_step_imex", "nsfem_imex_info", "nsfem_imex_rhs",
@@ -298,6 +298,7 @@ def load_library(path=None):
         "nsfem_jacobian_table_check": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_mg_apply": (C.c_int, [vp, C.c_int, pd, pd]),
         "nsfem_mg_info": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64)]),
+        "nsfem_monolithic_apply": (C.c_int, [vp, C.c_int, C.c_int, pd, pd]),
         "nsfem_poisson_set_fast_diag": (C.c_int, [vp, i32, i32, pd, pd, pd]),
         "nsfem_operator_diagonal": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_poisson_set_fast_diag_rows": (C.c_int, [vp, i32, i32, i32, pd, pd, pd]),
@@ -447,8 +448,9 @@ class NsfemContext:
         return self._lib.nsfem_state_devptr(self._h, slot)
 
     # -- assembly seam + solves -------------------------------------------------
-    def assemble(self, system, new_step=False):
-        self._check(self._lib.nsfem_assemble(self._h, system, 1 if new_step else 0))
+    def assemble(self, system, new_step=False, matrix_free=False):
+        """matrix_free (SYS_MONOLITHIC only): the solve that follows applies the velocity Jacobian matrix-free"""
+        self._check(self._lib.nsfem_assemble(self._h, system, (1 if new_step else 0) | (2 if matrix_free else 0)))
 
     def residual_norm(self, system):
         out = C.c_double()
@@ -457,6 +459,8 @@ class NsfemContext:
 
     def get_rhs(self, system):
         n = self.n_p1 if system == SYS_POISSON else self.n_velocity
+        if system == SYS_MONOLITHIC:
+            n = self.n_velocity + self.n_p1
         out = np.empty(n, dtype=np.float64)
         self._check(self._lib.nsfem_get_rhs(self._h, system, _dp(out), n))
         return out
@@ -782,11 +786,21 @@ class NsfemContext:
 
     def mg_apply(self, which, r):
         """one cycle z = M^-1 r of the pressure (which=0) or velocity (which=1) multigrid preconditioner; which=2: the
-        fast-diagonalisation solve z = A^+ r (strip factors: a collective, every rank calls it; 3D factors: z = T^+ r)"""
+        fast-diagonalisation solve z = A^+ r (strip factors: a collective, every rank calls it; 3D factors: z = T^+ r);
+        which=3: the Schur hierarchy of the monolithic block preconditioner, which=4: its pressure mass smoother"""
         r = np.ascontiguousarray(r, dtype=np.float64)
         z = np.zeros_like(r)
         self._check(self._lib.nsfem_mg_apply(self._h, int(which), _dp(r), _dp(z)))
         return z
+
+    def monolithic_apply(self, what, x, matrix_free=False):
+        """what=0: y = MixedOp x, the operator of the monolithic step's linear solve about U0 (convective form and
+        Picard flag: set_convective_form); what=1: y = BlockPrec x, its block preconditioner; mixed host vectors"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.size == self.n_velocity + self.n_p1
+        y = np.zeros_like(x)
+        self._check(self._lib.nsfem_monolithic_apply(self._h, int(what), 1 if matrix_free else 0, _dp(x), _dp(y)))
+        return y
 
     def poisson_set_fast_diag(self, factors, first_line=None):
         """factors of poisson_fd.factors(): the projection step may then run with Krylov option precond = 3.
@@ -831,9 +845,10 @@ class NsfemContext:
 
     def mg_lattice_info(self, which):
         """dict(lattice_levels, lattice_launches, levels, ghost_lines): the multi-step lattice kernel on the Poisson
-        (which = 0) / velocity (1) hierarchy; on partitioned strips it runs in relaxed halo mode only"""
+        (which = 0) / velocity (1) hierarchy; on partitioned strips it runs in relaxed halo mode only.  which = 3 / 4:
+        the Schur hierarchy / the pressure mass smoother of the monolithic block preconditioner (as mg_apply)"""
         out = (C.c_int64 * 4)()
-        self._check(self._lib.nsfem_mg_info(self._h, 2 + int(which), out))
+        self._check(self._lib.nsfem_mg_info(self._h, (3 + int(which)) if int(which) >= 3 else 2 + int(which), out))
         return dict(lattice_levels=int(out[0]), lattice_launches=int(out[1]), levels=int(out[2]),
                     ghost_lines=(int(out[3]) // 256, int(out[3]) % 256))
 

@@ -1460,6 +1460,9 @@ static int correction_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solv
 }
 
 // ------------------------------------------------------- assembly seam + solve
+static void monolithic_assemble(nsfem_ctx* ctx, uint32_t flags);
+static int monolithic_solve(nsfem_ctx* ctx, const nsfem_krylov_opts& o, nsfem_solve_info& inf);
+
 extern "C" int nsfem_assemble(nsfem_ctx* ctx, int system, uint32_t flags) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
@@ -1475,6 +1478,9 @@ extern "C" int nsfem_assemble(nsfem_ctx* ctx, int system, uint32_t flags) {
     case NSFEM_SYS_CORRECTION:
       correction_assemble(ctx, true);      // (the same pass as the fused driver: its Chebyshev solve may start from it)
       break;
+    case NSFEM_SYS_MONOLITHIC:
+      monolithic_assemble(ctx, flags);
+      break;
     default:
       throw Error(NSFEM_ERR_ARG, "nsfem_assemble: system not available");
   }
@@ -1487,9 +1493,9 @@ extern "C" int nsfem_residual_norm(nsfem_ctx* ctx, int system, double* out) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out, "null argument");
   NSFEM_REQUIRE(system == ctx->assembled_system, "system not assembled");
-  const bool vel = (system != NSFEM_SYS_POISSON);
-  const double* b = vel ? ctx->rhs_v.p : ctx->rhs_p.p;
-  const int64_t n = vel ? nvel(ctx) : npre(ctx);
+  const bool vel = (system != NSFEM_SYS_POISSON), mixed = (system == NSFEM_SYS_MONOLITHIC);
+  const double* b = mixed ? ctx->rhs_m.p : vel ? ctx->rhs_v.p : ctx->rhs_p.p;
+  const int64_t n = mixed ? nvel(ctx) + npre(ctx) : vel ? nvel(ctx) : npre(ctx);
   *out = global_norm(ctx, n, const_cast<double*>(b), nullptr);
   API_END(ctx)
 }
@@ -1497,9 +1503,10 @@ extern "C" int nsfem_residual_norm(nsfem_ctx* ctx, int system, double* out) {
 extern "C" int nsfem_get_rhs(nsfem_ctx* ctx, int system, double* host, int64_t n) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && host, "null argument");
-  const bool vel = (system != NSFEM_SYS_POISSON);
-  NSFEM_REQUIRE(n == (vel ? nvel(ctx) : npre(ctx)), "bad size");
-  NSFEM_HIP(hipMemcpyAsync(host, vel ? ctx->rhs_v.p : ctx->rhs_p.p, sizeof(double) * n,
+  const bool vel = (system != NSFEM_SYS_POISSON), mixed = (system == NSFEM_SYS_MONOLITHIC);
+  NSFEM_REQUIRE(n == (mixed ? nvel(ctx) + npre(ctx) : vel ? nvel(ctx) : npre(ctx)), "bad size");
+  NSFEM_REQUIRE(!mixed || ctx->rhs_m.p, "system not assembled");
+  NSFEM_HIP(hipMemcpyAsync(host, mixed ? ctx->rhs_m.p : vel ? ctx->rhs_v.p : ctx->rhs_p.p, sizeof(double) * n,
                            hipMemcpyDeviceToHost, ctx->stream));
   NSFEM_HIP(hipStreamSynchronize(ctx->stream));
   API_END(ctx)
@@ -1566,6 +1573,7 @@ extern "C" int nsfem_solve(nsfem_ctx* ctx, int system, const nsfem_krylov_opts* 
       rc = correction_solve(ctx, hinted(*opts, ctx->hint_cor, opts->precond == 2), inf);
       note_solve(ctx->hint_cor, inf, *opts, ctx->kw.last_target);
       break;
+    case NSFEM_SYS_MONOLITHIC: rc = monolithic_solve(ctx, *opts, inf); break;
     default: throw Error(NSFEM_ERR_ARG, "nsfem_solve: system not available");
   }
   if (rc == NSFEM_ERR_BREAKDOWN) throw Error(rc, "Krylov breakdown");
@@ -3255,10 +3263,9 @@ static double bdf_residual(nsfem_ctx* c) {
   return global_norm(c, nv + np, b, nullptr);
 }
 
-extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
-  nsfem_step_info local;
-  API_BEGIN
-  nsfem_step_info& inf = step_begin(ctx, opts, info, local, true, opts && opts->picard != 0);
+// What every entry to the mixed system does first (nsfem_step_bdf, the explicit seam with NSFEM_SYS_MONOLITHIC, the
+// test hook nsfem_monolithic_apply): the checks, the mixed vectors, the operator objects, the dictionary copies of D / D^T
+static void monolithic_setup(nsfem_ctx* ctx) {
   NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
   NSFEM_REQUIRE(ctx->bodies.cur.n == 0, "immersed bodies: only nsfem_step_imex takes bodies (remove them with n = 0 first)");
   NSFEM_REQUIRE(!ctx->distributed() || ctx->schur_singular < 0 || ctx->schur_additive,
@@ -3266,7 +3273,6 @@ extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem
                 "(nsfem_mg_set_schur_mode)");
   NSFEM_REQUIRE(ctx->mg_built, "the monolithic step needs the multigrid hierarchy "
                                "(block preconditioner): call nsfem_mg_finalize");
-  hipStream_t s = ctx->stream;
   const int64_t nv = nvel(ctx), np = npre(ctx);
   if (!ctx->rhs_m.p) {
     ctx->rhs_m.alloc((size_t)(nv + np));
@@ -3279,29 +3285,113 @@ extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem
   ctx->mom_mf.n = nv;
   ctx->mom_mf.vel_slot = NSFEM_U0;
   ensure_div_dicts(ctx);
+}
+
+// What the linear solve of one Newton iteration prepares: the Jacobian about U0 (unless it is applied matrix-free) and
+// the three hierarchies of the block preconditioner
+static void monolithic_linearise(nsfem_ctx* ctx) {
+  if (!ctx->mf_active) momentum_jacobian(ctx, NSFEM_U0);
+  mg_refresh(ctx, true);
+  mg_refresh_schur(ctx);
+}
+
+// MixedOp dx = rhs_m by block-preconditioned BiCGStab from zero; u -= dx, p -= dx.  r: |rhs_m| as bdf_residual has just
+// returned it; rhs_dead: the caller recomputes rhs_m before anything reads it again (the Newton loop; not so behind
+// nsfem_solve, where nsfem_get_rhs / nsfem_residual_norm may follow)
+static int monolithic_solve_update(nsfem_ctx* ctx, double r, bool rhs_dead, const nsfem_krylov_opts& k,
+                                   nsfem_solve_info& si) {
+  hipStream_t s = ctx->stream;
+  const int64_t nv = nvel(ctx), np = npre(ctx);
+  LinOp op;
+  op.custom = &ctx->mixed_op;
+  op.prec = &ctx->block_prec;
+  if (ctx->distributed()) op.comm = ctx->comm;        // all-reduce of the partial dot products
+  op.graph_epoch = ctx->graph_epoch;
+  op.x_zero = true;               // (dx_m is not read: the first update of the solve writes it)
+  op.known_bnorm = r;             // |rhs_m| = the Newton residual norm just evaluated (bdf_residual)
+  op.b_scratch = rhs_dead;        // (bdf_residual rewrites rhs_m before anything reads it)
+  const int rc = bicgstab(s, ctx->kw, op, ctx->rhs_m.p, ctx->dx_m.p, k, si);
+  if (rc != NSFEM_OK) return rc;  // (a failed solve leaves the iterate: the caller may resume from it)
+  double* u = ctx->state[NSFEM_U0].p;
+  double* p = ctx->state[NSFEM_P].p;
+  launch_axpby(s, nv, 1.0, u, -1.0, ctx->dx_m.p, u);
+  launch_axpby(s, np, 1.0, p, -1.0, ctx->dx_m.p + nv, p);
+  return rc;
+}
+
+extern "C" int nsfem_step_bdf(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info* info) {
+  nsfem_step_info local;
+  API_BEGIN
+  nsfem_step_info& inf = step_begin(ctx, opts, info, local, true, opts && opts->picard != 0);
+  monolithic_setup(ctx);
   momentum_begin_step(ctx, false);
   newton_solve(ctx, opts, inf, "monolithic step", opts->allow_nonconvergence != 0, [&] { return bdf_residual(ctx); },
                [&](double r, const nsfem_krylov_opts& k, nsfem_solve_info& si) {
-                 if (!ctx->mf_active) momentum_jacobian(ctx, NSFEM_U0);
-                 mg_refresh(ctx, true);
-                 mg_refresh_schur(ctx);
-                 LinOp op;
-                 op.custom = &ctx->mixed_op;
-                 op.prec = &ctx->block_prec;
-                 if (ctx->distributed()) op.comm = ctx->comm;        // all-reduce of the partial dot products
-                 op.graph_epoch = ctx->graph_epoch;
-                 op.x_zero = true;               // (dx_m is not read: the first update of the solve writes it)
-                 op.known_bnorm = r;             // |rhs_m| = the Newton residual norm just evaluated (bdf_residual)
-                 op.b_scratch = true;            // (bdf_residual rewrites rhs_m before anything reads it)
-                 const int rc = bicgstab(s, ctx->kw, op, ctx->rhs_m.p, ctx->dx_m.p, k, si);
-                 if (rc != NSFEM_OK) return rc;  // (a failed solve leaves the iterate: the caller may resume from it)
-                 double* u = ctx->state[NSFEM_U0].p;
-                 double* p = ctx->state[NSFEM_P].p;
-                 launch_axpby(s, nv, 1.0, u, -1.0, ctx->dx_m.p, u);
-                 launch_axpby(s, np, 1.0, p, -1.0, ctx->dx_m.p + nv, p);
-                 return rc;
+                 monolithic_linearise(ctx);
+                 return monolithic_solve_update(ctx, r, true, k, si);
                });
   ctx->assembled_system = -1;
+  API_END(ctx)
+}
+
+// The explicit seam for the mixed system (nsfem_assemble / nsfem_solve with NSFEM_SYS_MONOLITHIC; single contexts).
+// flags: bit 0 -- a new time step (the step-constant vector g is formed first); bit 1 -- the velocity Jacobian is
+// applied matrix-free by the solve that follows, as the step does with nsfem_step_opts.matrix_free != 1
+static void monolithic_assemble(nsfem_ctx* ctx, uint32_t flags) {
+  NSFEM_REQUIRE(!ctx->distributed(), "the explicit seam of the monolithic system takes single contexts only "
+                                     "(this context has a communicator)");
+  monolithic_setup(ctx);
+  if (flags & 1u) momentum_begin_step(ctx, false);
+  ctx->mono_rnorm = bdf_residual(ctx);
+  ctx->mono_mf = (flags & 2u) != 0;
+  ctx->mf_active = ctx->mono_mf;
+  monolithic_linearise(ctx);
+  ctx->mf_active = false;
+}
+
+static int monolithic_solve(nsfem_ctx* ctx, const nsfem_krylov_opts& o, nsfem_solve_info& inf) {
+  ctx->mf_active = ctx->mono_mf;
+  int rc;
+  try {
+    rc = monolithic_solve_update(ctx, ctx->mono_rnorm, false, o, inf);
+  } catch (...) {
+    ctx->mf_active = false;
+    throw;
+  }
+  ctx->mf_active = false;
+  return rc;
+}
+
+// Test hook: the two composite objects of the monolithic linear solve on host vectors of nvel + npre entries, prepared
+// as the linear solve of nsfem_step_bdf prepares them (and nothing else; no state slot is written, and what = 0
+// writes no right-hand side either -- the preconditioner uses rhs_p as scratch, as it does inside the step).  what = 0: y = MixedOp x, linearised about U0 with the convective form and Picard flag the context holds
+// (nsfem_set_convective_form); what = 1: y = BlockPrec x.  matrix_free != 0: the velocity Jacobian is applied
+// matrix-free, as in a step with nsfem_step_opts.matrix_free != 1.  Single contexts only.
+extern "C" int nsfem_monolithic_apply(nsfem_ctx* ctx, int what, int matrix_free, const double* x, double* y) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && x && y && (what == 0 || what == 1), "bad argument");
+  NSFEM_REQUIRE(!ctx->distributed(), "nsfem_monolithic_apply takes single contexts only (this context has a "
+                                     "communicator)");
+  hipStream_t s = ctx->stream;
+  monolithic_setup(ctx);
+  momentum_begin_step(ctx, false);
+  ctx->mf_active = matrix_free != 0;
+  try {
+    monolithic_linearise(ctx);
+    const int64_t n = nvel(ctx) + npre(ctx);
+    DevBuf<double> dx, dy;
+    dx.upload(x, (size_t)n, s);
+    dy.alloc((size_t)n);
+    dy.zero(s);
+    if (what == 0) ctx->mixed_op.apply(s, dx.p, dy.p);
+    else ctx->block_prec.apply(s, dx.p, dy.p);
+    NSFEM_HIP(hipMemcpyAsync(y, dy.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    NSFEM_HIP(hipStreamSynchronize(s));
+  } catch (...) {
+    ctx->mf_active = false;
+    throw;
+  }
+  ctx->mf_active = false;
   API_END(ctx)
 }
 
@@ -4555,11 +4645,29 @@ extern "C" int nsfem_poisson_set_fast_diag_3d_planes(nsfem_ctx* ctx, int32_t Nx,
 // Test hook: one application z = M^-1 r of a multigrid preconditioner on host vectors -- which = 0 pressure Poisson
 // hierarchy (mg_p), 1 velocity hierarchy (mg_v, the identity rows of the Newton preconditioner included), 2 the
 // fast-diagonalisation solve z = A^+ r of the active factors (FastDiagBase::apply; on strip and slab factors a
-// collective).  Lets the parity tests compare kernel families cycle by cycle.
+// collective), 3 the Schur hierarchy (mg_s: its own Dirichlet set NSFEM_PRESSURE_PRECOND, geometric or algebraic
+// level operators), 4 the pressure mass smoother (mg_m) -- the last two after the refreshes nsfem_step_bdf makes, on
+// single contexts only.  Lets the parity tests compare kernel families cycle by cycle.
 extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double* z) {
   API_BEGIN
-  NSFEM_REQUIRE(ctx && r && z && (which == 0 || which == 1 || which == 2), "bad argument");
+  NSFEM_REQUIRE(ctx && r && z && which >= 0 && which <= 4, "bad argument");
   hipStream_t s = ctx->stream;
+  if (which >= 3) {                    // the two hierarchies of the block preconditioner's pressure part
+    NSFEM_REQUIRE(!ctx->distributed(), "nsfem_mg_apply(3 | 4) takes single contexts only (this context has a "
+                                       "communicator)");
+    NSFEM_REQUIRE(ctx->mg_built, "no multigrid hierarchy (nsfem_mg_finalize)");
+    ensure_L(ctx);                     // (builds the dictionaries of the fine P1 operators as well)
+    mg_refresh_schur(ctx);
+    const int64_t n = npre(ctx);
+    DevBuf<double> dr, dz;
+    dr.upload(r, (size_t)n, s);
+    dz.alloc((size_t)n);
+    dz.zero(s);
+    (which == 3 ? ctx->mg_s : ctx->mg_m).apply(s, dr.p, dz.p);
+    NSFEM_HIP(hipMemcpyAsync(z, dz.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    NSFEM_HIP(hipStreamSynchronize(s));
+    return NSFEM_OK;
+  }
   if (which == 2) {                    // the fast-diagonalisation Poisson solve z = A^+ r
     const int64_t n = npre(ctx);
     DevBuf<double> dr, dz;
@@ -4592,14 +4700,18 @@ extern "C" int nsfem_mg_apply(nsfem_ctx* ctx, int which, const double* r, double
 }
 
 // How a multigrid cycle runs: which = 0 / 1: out = {0, 0, levels in use, 0} (the two zero fields are reserved);
-// which = 2 / 3: the multi-step lattice kernel on the hierarchy
+// which = 2 / 3: the multi-step lattice kernel on the hierarchy; which = 4 / 5 and 6 / 7: the same two records for the
+// Schur hierarchy mg_s / the mass smoother mg_m (single contexts)
 extern "C" int nsfem_mg_info(nsfem_ctx* ctx, int which, int64_t out[4]) {
   API_BEGIN
-  NSFEM_REQUIRE(ctx && out && which >= 0 && which <= 3, "bad argument");
+  NSFEM_REQUIRE(ctx && out && which >= 0 && which <= 7, "bad argument");
+  NSFEM_REQUIRE(which < 4 || !ctx->distributed(), "nsfem_mg_info(4 .. 7) takes single contexts only (this context "
+                                                  "has a communicator)");
   NSFEM_REQUIRE(ctx->mg_built, "no multigrid hierarchy (nsfem_mg_finalize)");
   ensure_L(ctx);
-  mg_refresh(ctx, (which & 1) == 1);
-  Multigrid& mg = (which & 1) ? ctx->mg_v : ctx->mg_p;
+  if (which >= 4) mg_refresh_schur(ctx);
+  else mg_refresh(ctx, (which & 1) == 1);
+  Multigrid& mg = which >= 4 ? ((which & 1) ? ctx->mg_m : ctx->mg_s) : ((which & 1) ? ctx->mg_v : ctx->mg_p);
   if (which & 2) {                     // the multi-step lattice kernel on this hierarchy (strips: relaxed halo mode)
     const size_t n_used = mg.truncated() ? mg.active : mg.lv.size();
     int64_t levels = 0;

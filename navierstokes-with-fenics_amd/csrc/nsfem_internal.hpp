@@ -1363,6 +1363,8 @@ struct nsfem_ctx {
   } wall;
   int64_t jac_lattice_launches = 0;   // applications of the matrix-free Jacobian through k_jac_lattice
   bool mf_active = false;           // the running step driver applies the Jacobian matrix-free
+  bool mono_mf = false;             // nsfem_assemble(NSFEM_SYS_MONOLITHIC): the solve that follows runs matrix-free
+  double mono_rnorm = -1.0;         // ... and |rhs_m| as that assembly evaluated it
   int pressure_history = 0;         // IPCS: pressure levels shifted since the state was last set (0..2)
   struct MixedOp : nsfem::Operator {
     nsfem_ctx* c = nullptr;

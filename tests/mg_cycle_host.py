@@ -32,13 +32,20 @@ truncated   (velocity, mass-dominated operators) the first P1 level with r = max
             (sqrt(kappa) - 1)))).
 shapes      V(2,2) pressure; V(0, degree + 1) default velocity cycle; V(degree, degree) symmetric velocity cycle
             (set_velocity_cycle_symmetric: what CG and the IMEX diffusion step run).
+schur       (mg_s, `Hierarchy.schur`) the pressure cycle with a Dirichlet set of its own (PRESSURE_PRECOND) on K, or on
+            the algebraic Laplacian A_L = D_f diag(M_v)^-1 D_f^T (D_f: the divergence block without the Dirichlet
+            velocity columns) and its Galerkin coarsenings P^T A P (`Hierarchy.algebraic_laplacian`: formed here, entry
+            by entry in the precision asked for, from the oracle's divergence(), the diagonal of mass_p2() and the
+            prolongation triplets).  singular: geometric levels -- the Dirichlet set is empty; algebraic levels --
+            max_i |A_L 1|_i <= 1e-10 max_i |A_L,ii| (attach_schur_laplacian), whatever the Dirichlet set holds.
+mass        (mg_m, `Hierarchy.mass_smoother`) one level M_p without flags, never solved: four Chebyshev-Jacobi steps
+            from zero over [1.05 lmax / 8, 1.05 lmax].
 
 Precision: every cycle exists in float64 (scipy products) and in numpy.longdouble (dense matrices, or -- levels too
 large for that -- the same row sums on the CSR arrays); `rel(z64, zld)` measures what rounding does to one case and
 sets the tolerance of the device comparison (tests/test_gpu_multigrid_cycle.py).
 
-Out of scope: partitioned contexts (additive levels, relaxed halo mode, global coarse solve), the Schur hierarchy
-mg_s and the mass smoother mg_m -- the hook nsfem_mg_apply does not reach the last two."""
+Out of scope: partitioned contexts (additive levels, relaxed halo mode, global coarse solve)."""
 import math
 
 import numpy as np
@@ -114,6 +121,29 @@ def combine(a, M, b, K, dtype):
     M.sort_indices()
     assert np.array_equal(M.indptr, K.indptr) and np.array_equal(M.indices, K.indices)
     return _Mat(K, dtype, data=dtype(a) * M.data.astype(dtype) + dtype(b) * K.data.astype(dtype))
+
+
+def spgemm(A, B, dtype, a_data=None, b_data=None):
+    """A B with every product and every sum in `dtype`: (scipy CSR pattern of the result, its values in `dtype`, in
+    the order of the pattern's sorted indices).  a_data / b_data replace the values of A / B (sorted CSR order)"""
+    A, B = sp.csr_matrix(A), sp.csr_matrix(B)
+    A.sort_indices()
+    B.sort_indices()
+    av = (A.data if a_data is None else a_data).astype(dtype)
+    bv = (B.data if b_data is None else b_data).astype(dtype)
+    rows = np.repeat(np.arange(A.shape[0], dtype=np.int64), np.diff(A.indptr))
+    k = A.indices.astype(np.int64)
+    cnt = np.diff(B.indptr).astype(np.int64)[k]                   # products per entry of A
+    a = np.repeat(np.arange(A.nnz, dtype=np.int64), cnt)
+    b = np.repeat(B.indptr[:-1].astype(np.int64)[k], cnt) + (np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    key = rows[a] * B.shape[1] + B.indices.astype(np.int64)[b]
+    uniq, inv = np.unique(key, return_inverse=True)
+    vals = np.zeros(uniq.size, dtype=dtype)
+    np.add.at(vals, inv, av[a] * bv[b])
+    r, c = uniq // B.shape[1], uniq % B.shape[1]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=A.shape[0]))])
+    pattern = sp.csr_matrix((vals.astype(np.float64), c, indptr), shape=(A.shape[0], B.shape[1]))
+    return pattern, vals
 
 
 def operator_coefficients(alpha0, k, viscous, gamma0=None, prec_shift=0.0):
@@ -323,6 +353,7 @@ class Hierarchy:
         from fem_mesh import TaylorHoodDofMap
         assert np.array_equal(dm.p1_dofmap, mesh.cells), "P1 dofs are the vertices"
         s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+        self.space = s
         self.dim = s.dim
         self.n_p2, self.n_p1 = dm.n_p2, dm.n_p1
         self.M2, self.K2 = s.mass_p2(), s.stiffness_p2()
@@ -343,6 +374,55 @@ class Hierarchy:
         ops = [combine(0.0, None, 1.0, K, dtype) for K in self.K1]
         return HostCycle(ops, self.transfers, self.nested, flags, 1, degree, degree, eig_ratio,
                          singular=len(dirichlet) == 0, coarse_dense_max=coarse_dense_max, dtype=dtype)
+
+    def divergence(self):
+        if not hasattr(self, "_D"):
+            self._D = sp.csr_matrix(self.space.divergence())
+            self._D.sort_indices()
+        return self._D
+
+    def algebraic_laplacian(self, velocity_dirichlet, dtype=np.float64):
+        """(level operators, singular) of the algebraic Schur Laplacian: A_L = D diag(w) D^T with w = 1 / M_v,jj on
+        free velocity dofs and 0 on the Dirichlet ones, then P^T A P level by level -- every entry summed in `dtype`"""
+        D = self.divergence()
+        w = np.repeat(dtype(1.0) / self.M2.diagonal().astype(dtype), self.dim)
+        w[np.asarray(velocity_dirichlet, dtype=np.int64)] = dtype(0.0)
+        Dt = sp.csr_matrix(D.T)
+        Dt.sort_indices()
+        pat, vals = spgemm(D, Dt, dtype, a_data=D.data.astype(dtype) * w[D.indices])
+        ops = [_Mat(pat, dtype, data=vals)]
+        for l, t in enumerate(self.transfers):
+            P = sp.csr_matrix((t[2], t[1], t[0]), shape=(pat.shape[0], self.K1[l + 1].shape[0]))
+            P.sort_indices()
+            Pt = sp.csr_matrix(P.T)
+            Pt.sort_indices()
+            ap, apv = spgemm(pat, P, dtype, a_data=vals)
+            pat, vals = spgemm(Pt, ap, dtype, b_data=apv)
+            ops.append(_Mat(pat, dtype, data=vals))
+        A0 = ops[0]
+        ones = A0.dot(np.ones(A0.shape[0], dtype=dtype))
+        singular = bool(float(np.abs(ones).max()) / max(float(np.abs(A0.diagonal()).max()), 1e-300) <= 1e-10)
+        return ops, singular
+
+    def schur(self, dirichlet, degree=2, eig_ratio=4.0, coarse_dense_max=1200, dtype=np.float64, operators=None,
+              singular=None):
+        """mg_s: V(degree, degree) with the flags of the PRESSURE_PRECOND set `dirichlet`, on K (singular when the
+        set is empty: mg_refresh_schur) or on the caller's level operators with the caller's singular flag
+        (`algebraic_laplacian`: nsfem_mg_set_schur_operator fixes the flag whatever the set holds)"""
+        flags = np.zeros((self.n_p1, 1), dtype=bool)
+        flags[np.asarray(dirichlet, dtype=np.int64)] = True
+        if operators is None:
+            operators = [combine(0.0, None, 1.0, K, dtype) for K in self.K1]
+            singular = len(dirichlet) == 0
+        assert singular is not None and len(operators) == len(self.K1)
+        return HostCycle(operators, self.transfers, self.nested, flags, 1, degree, degree, eig_ratio,
+                         singular=singular, coarse_dense_max=coarse_dense_max, dtype=dtype)
+
+    def mass_smoother(self, dtype=np.float64):
+        """mg_m: one level M_p, no flags, four Chebyshev-Jacobi steps from zero, ratio 8"""
+        flags = np.zeros((self.n_p1, 1), dtype=bool)
+        return HostCycle([combine(0.0, None, 1.0, self.M1[0], dtype)], [], [], flags, 1, 0, 0, eig_ratio=8.0,
+                         singular=False, coarse_dense_max=0, coarse_steps=4, dtype=dtype)
 
     def truncation(self, a, b, trunc_ratio, trunc_tol):
         """select_velocity_cycle_depth: (levels in use, lower spectral bound, tolerance) or None"""
