@@ -949,6 +949,12 @@ int nsfem_profile_convection(nsfem_ctx* ctx, int enable, double* avg_ms, int64_t
  * round-4 kernel, NSFEM_JL_KERNEL=0; 1 one cell type per wave and node sums by gather; 2 the same with the physical
  * gradients of a uniform lattice from tables). */
 int nsfem_jacobian_info(nsfem_ctx* ctx, int64_t out[4]);
+/* Launches so far of the fused step frame of the pressure-correction steps (NSFEM_STEP_FUSED, default on, read when
+ * the context is created; 0 keeps one launch per vector pass): out[0] = k_spmv_dict_pair in the begin step
+ * (M x + c D^T p_old), out[1] = k_spmv_dict_pair in the correction assembly, out[2] = k_correction_finish,
+ * out[3] = projection checks whose launch also stored p = p_old + z.  Each stays 0 where its path does not apply
+ * (partitioned contexts, no exact stencil dictionaries, 3D, optional right-hand-side terms, other solvers). */
+int nsfem_step_frame_info(nsfem_ctx* ctx, int64_t out[4]);
 /* Test hook: *bad_cells = the number of cells whose basis gradients and weights, evaluated per cell as the element
  * kernels do, differ in any bit from the tables k_jac_lattice reads on a uniform lattice; -1 when there are none. */
 int nsfem_jacobian_table_check(nsfem_ctx* ctx, int64_t* bad_cells);

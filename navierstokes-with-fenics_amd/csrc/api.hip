@@ -116,6 +116,7 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   NSFEM_HIP(hipSetDevice(device));
   fresh = new nsfem_ctx();
   fresh->device = device;
+  fresh->step_fused = step_fused_enabled();
   NSFEM_HIP(hipStreamCreate(&fresh->stream));
   hipStream_t s = fresh->stream;
   const int nc = m->n_cells;
@@ -862,6 +863,14 @@ static void momentum_begin_step(nsfem_ctx* c, bool with_old_pressure = true) {
     launch_axpby(s, nv, a1, c->state[NSFEM_U1].p, a2, c->state[NSFEM_U2].p, c->tmp_v.p);
   }
   if (euler_active(c)) euler_add(c, c->tmp_v.p);
+  // fused step frame (one rank, 2D, exact dictionaries of both operators, none of the optional terms): the product
+  // with M and the accumulated D^T p_old in ONE launch, gconst written once
+  if (c->step_fused && with_old_pressure && !c->distributed() && c->mesh.dim == 2 && !c->have_body_force &&
+      !c->have_traction && !euler_active(c) && spmv_pair_available(c->M2, c->DT)) {
+    launch_spmv_pair_accum(s, c->M2, c->DT, c->tmp_v.p, -c->coef[1], c->state[NSFEM_P_OLD].p, c->gconst.p);
+    ++c->step_frame_launches[0];
+    return;
+  }
   launch_spmv(s, c->M2, c->mesh.dim, c->tmp_v.p, c->gconst.p, nullptr, MASK_NONE);
   if (with_old_pressure)   // IPCS: - c_p (p_old, div w); the monolithic scheme keeps p unknown
     launch_spmv_axpy(s, c->DT, 1, -c->coef[1], c->state[NSFEM_P_OLD].p, c->gconst.p, nullptr);
@@ -1224,10 +1233,12 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
     c->comm->allreduce_sum(s, parts + PR * kParts, kParts);
     launch_sub_mean(s, np, c->n_p1_global, parts + PR * kParts, w.r.p);
     launch_zero_ghost(s, np, gm, w.r.p);
+  } else if (c->step_fused) {
+    launch_sum_sub_mean_dot(s, np, w.r.p, parts + PR * kParts, parts + PB0 * kParts);   // (|r|^2 with the subtraction)
   } else {
     launch_sum_sub_mean(s, np, w.r.p, parts + PR * kParts);
   }
-  launch_dot(s, np, w.r.p, w.r.p, parts + PB0 * kParts);
+  if (dist || !c->step_fused) launch_dot(s, np, w.r.p, w.r.p, parts + PB0 * kParts);
   const double* base = c->state[NSFEM_P_OLD].p;
   // (local names for the two work vectors: refinement alternates them without permuting the KrylovWork buffers,
   // whose pointers the captured graphs of the other solvers hold)
@@ -1237,10 +1248,16 @@ static int poisson_direct_step(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_s
   info.converged = 0;
   for (int pass = 0; pass < std::max(1, std::min(o.max_iter, 8)); ++pass) {
     fd.apply(s, r, w.z.p);                                                     // (partitioned factors: a collective)
-    launch_axpby(s, np, 1.0, base, 1.0, w.z.p, c->state[NSFEM_P].p);          // p = p_old + z (later passes: p += z)
+    // fused step frame, first pass on one rank: p = p_old + z is stored by the check's launch q = r - A z
+    if (c->step_fused && !dist && pass == 0 &&
+        launch_residual_sum(s, c->Ap, w.z.p, r, q, base, c->state[NSFEM_P].p)) {
+      ++c->step_frame_launches[3];
+    } else {
+      launch_axpby(s, np, 1.0, base, 1.0, w.z.p, c->state[NSFEM_P].p);        // p = p_old + z (later passes: p += z)
+      launch_residual(s, c->Ap, 1, w.z.p, r, q, gm, gm ? MASK_ZERO : MASK_NONE);    // q = r - A z
+    }
     base = c->state[NSFEM_P].p;
     ++info.iterations;
-    launch_residual(s, c->Ap, 1, w.z.p, r, q, gm, gm ? MASK_ZERO : MASK_NONE);    // q = r - A z
     launch_dot(s, np, q, q, parts + PR * kParts);
     // (slots 10 ... 13 in the first pass, |r|^2 included; afterwards slot PB0 already holds the global sum)
     if (dist) c->comm->allreduce_sum(s, parts + PR * kParts, (pass == 0 ? PB0 - PR + 1 : 1) * kParts);
@@ -1290,9 +1307,24 @@ static int poisson_solve(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_i
 // with_start_residual (fused step, one rank, Chebyshev mass solve): the start residual of the solve and the two sums
 // its convergence check needs come out of the same pass as the right-hand side (k_correction_setup): r0 in kw.r,
 // |r0|^2 and |rhs|^2 in the partial-sum slots 12, 13
-static void correction_assemble(nsfem_ctx* c, bool with_start_residual = false) {
+// defer_finish (correction_step: the Chebyshev solve has a predicted step count and runs the lattice kernel): the fused
+// step frame -- ONE pair launch forms rhs and r0 without writing p - p_old or G (p - p_old); U0 and the two sums are
+// left to k_correction_finish after the solve's first sequence (cor_finish_pending)
+static void correction_assemble(nsfem_ctx* c, bool with_start_residual = false, bool defer_finish = false) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c), np = npre(c);
+  c->cor_finish_pending = false;
+  if (defer_finish && with_start_residual && c->step_fused && !c->distributed() && c->mask_v.p && !c->ghost_v.p &&
+      c->mesh.dim == 2 && c->dinv_m_ready && (ensure_div_dicts(c), spmv_pair_available(c->M2, c->Gr))) {
+    c->kw.ensure(nv);
+    launch_spmv_pair_correction(s, c->M2, c->Gr, c->state[NSFEM_USTAR].p, -c->k / c->alpha[0], c->state[NSFEM_P].p,
+                                c->state[NSFEM_P_OLD].p, c->mask_v.p, c->rhs_v.p, c->kw.r.p);
+    ++c->step_frame_launches[1];
+    c->cor_start_ready = true;
+    c->cor_start_touch = ++c->kw.touch;
+    c->cor_finish_pending = true;
+    return;
+  }
   launch_spmv(s, c->M2, c->mesh.dim, c->state[NSFEM_USTAR].p, c->rhs_v.p, nullptr, MASK_NONE);
   launch_axpby(s, np, 1.0, c->state[NSFEM_P].p, -1.0, c->state[NSFEM_P_OLD].p, c->tmp_p.p);
   launch_spmv(s, c->Gr, 1, c->tmp_p.p, c->tmp_v.p, nullptr, MASK_NONE);
@@ -1374,6 +1406,17 @@ static int correction_solve_chebyshev(nsfem_ctx* c, const nsfem_krylov_opts& o, 
   ++w.touch;
   const bool deferred = (k_hint > 0 || start_ready) && !c->distributed();
   constexpr int PR0 = 12, PB0 = 13;
+  // fused step frame: correction_assemble left U0 and the sums of slots 12, 13 to the launch after the first sequence
+  bool finish = c->cor_finish_pending;
+  c->cor_finish_pending = false;
+  if (finish && !(start_ready && k_hint > 0 && o.max_iter > 0 && !c->distributed() && mg.lattice_ok(L))) {
+    // (not the sequence the assembly counted on: supply them now, the way the unfused assembly does)
+    finish = false;
+    NSFEM_HIP(hipMemcpyAsync(x, c->state[NSFEM_USTAR].p, sizeof(double) * nv, hipMemcpyDeviceToDevice, s));
+    launch_set_values(s, c->nbc_v, c->bc_v_dofs.p, c->bc_v_vals.p, x);
+    launch_dot(s, nv, w.r.p, w.r.p, parts + PR0 * kParts);
+    launch_dot(s, nv, c->rhs_v.p, c->rhs_v.p, parts + PB0 * kParts);
+  }
   if (!start_ready) {
     residual_norm(w.r.p, deferred ? PR0 : P10);
     launch_dot(s, nv, c->rhs_v.p, c->rhs_v.p, parts + (deferred ? PB0 : P10 + 1) * kParts);
@@ -1416,10 +1459,20 @@ static int correction_solve_chebyshev(nsfem_ctx* c, const nsfem_krylov_opts& o, 
       // lattice kernel: the residual of the correction equation r - M e (= rhs - M (x + e)) rides along in the last
       // launch of the sequence -- no separate product with M for the check
       mg.smooth_lattice(s, L, w.r.p, nullptr, w.q.p, k, false, w.t.p);
-      launch_axpby(s, nv, 1.0, x, 1.0, w.q.p, x);
-      info.iterations += k;
-      std::swap(w.r.p, w.t.p);
-      launch_dot(s, nv, w.r.p, w.r.p, parts + P10 * kParts);
+      if (finish && first_pass) {
+        // U0 = u* + e, |r|^2 and the two start sums in one launch (r0 now lies in the buffer renamed w.t)
+        info.iterations += k;
+        std::swap(w.r.p, w.t.p);
+        launch_correction_finish(s, nv, c->state[NSFEM_USTAR].p, w.q.p, x, w.r.p, w.t.p, c->rhs_v.p,
+                                 parts + P10 * kParts, parts + PR0 * kParts, parts + PB0 * kParts);
+        launch_set_values(s, c->nbc_v, c->bc_v_dofs.p, c->bc_v_vals.p, x);
+        ++c->step_frame_launches[2];
+      } else {
+        launch_axpby(s, nv, 1.0, x, 1.0, w.q.p, x);
+        info.iterations += k;
+        std::swap(w.r.p, w.t.p);
+        launch_dot(s, nv, w.r.p, w.r.p, parts + P10 * kParts);
+      }
     } else {
       mg.smooth(s, L, w.r.p, nullptr, w.q.p, k);                       // e ~ M^{-1} r
       launch_axpby(s, nv, 1.0, x, 1.0, w.q.p, x);                      // x += e (e = 0 on Dirichlet dofs)
@@ -2248,9 +2301,15 @@ static void projection_step(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_s
 
 // Velocity correction step of the pressure-correction schemes
 static void correction_step(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfem_step_info& inf) {
-  correction_assemble(ctx, opts->correction.precond == 2);
+  const bool cheb = opts->correction.precond == 2;
+  const nsfem_krylov_opts ko = hinted(opts->correction, ctx->hint_cor, cheb);
+  // (the fused frame needs the solve to run a predicted number of steps in the lattice kernel before its only check;
+  // the first steps, which read the start sums before the sequence, keep the present launches)
+  const bool defer = cheb && ko.first_check >= 1 && ko.max_iter > 0 && !ctx->mg_mv.lv.empty() &&
+                     ctx->mg_mv.lattice_ok(ctx->mg_mv.lv[0]);
+  correction_assemble(ctx, cheb, defer);
   nsfem_solve_info si;
-  int rc = correction_solve(ctx, hinted(opts->correction, ctx->hint_cor, opts->correction.precond == 2), si);
+  int rc = correction_solve(ctx, ko, si);
   note_solve(ctx->hint_cor, si, opts->correction, ctx->kw.last_target);
   inf.krylov_iterations_correction = si.iterations;
   if (rc != NSFEM_OK) throw Error(rc, "CG failed in the velocity correction step");
@@ -4816,6 +4875,15 @@ extern "C" int nsfem_smoother_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[1] = A.dict_ready ? A.dict->n_stencils : 0;
   out[2] = A.dict_ready ? (A.dict->exact ? -A.dict->lmax : A.dict->lmax) : 0;
   out[3] = smoother_launch_bytes(A, mg.nv, true);
+  API_END(ctx)
+}
+
+// launches so far of the fused step frame (NSFEM_STEP_FUSED): out = {pair kernel in the begin step, pair kernel in the
+// correction assembly, k_correction_finish, fused projection epilogue}
+extern "C" int nsfem_step_frame_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  for (int i = 0; i < 4; ++i) out[i] = ctx->step_frame_launches[i];
   API_END(ctx)
 }
 

@@ -32,7 +32,9 @@ namespace nsfem {
 //                                            d = c1 d + c2 dinv (b - A x); y = x + d
 // Row masks (Dirichlet dofs): identity rows (dolfin's non-symmetric bc.apply) or zero
 // rows (symmetric elimination on vectors that vanish on the constrained dofs).
-enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_ACCUM = 2, EPI_CHEB = 3 };
+// EPI_RESID_SUM (scalar dictionary kernel only): EPI_RESID and, from the operand x it already holds,
+//   psum = base + x  (the projection step: p = p_old + z rides along in the check q = r - A z)
+enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_ACCUM = 2, EPI_CHEB = 3, EPI_RESID_SUM = 4 };
 
 struct SpmvArgs {
   const double* x;
@@ -61,6 +63,9 @@ struct SpmvArgs {
   // gather fused into the product with the constant part of the Jacobian); null: off
   const int32_t* gptr;
   const double* gbuf;
+  // dictionary kernel, EPI_RESID_SUM: psum = base + x on every row
+  const double* base;
+  double* psum;
 };
 struct XcdSplit { int s[9]; };   // SELL kernel: workgroup range [s[x], s[x+1]) of XCD x (s[8] = 0: round robin)
 
@@ -569,7 +574,7 @@ __device__ __forceinline__ void spmv_dict_body(int n_rows, int n_wg, const uint8
   // epilogue operands of this lane's NV output entries (see below for the entry <-> lane map)
   const size_t ebase = (size_t)wave * 64 * NV;
   int pm[NV];
-  double pb[NV], pdi[NV], pd[NV], px[NV];
+  double pb[NV], pdi[NV], pd[NV], px[NV], pbase[NV];
 #pragma unroll
   for (int p = 0; p < NV; ++p) {
     const int e = p * 64 + lane;
@@ -577,6 +582,7 @@ __device__ __forceinline__ void spmv_dict_body(int n_rows, int n_wg, const uint8
     const size_t idx = ebase + e;
     pm[p] = (in && a.maskmode != MASK_NONE) ? a.mask[idx] : 0;
     pb[p] = (in && EPI != EPI_STORE) ? a.b[idx] : 0.0;
+    pbase[p] = (in && EPI == EPI_RESID_SUM) ? a.base[idx] : 0.0;
     pdi[p] = 0.0;
     pd[p] = (in && EPI == EPI_CHEB && a.c1 != 0.0) ? a.d[idx] : 0.0;
     px[p] = in ? x[idx] : 0.0;
@@ -648,6 +654,7 @@ __device__ __forceinline__ void spmv_dict_body(int n_rows, int n_wg, const uint8
     int m_ = pm[p];
     if (m_ == 2 && a.ghost == 2) m_ = 0;
     const bool m = m_ != 0;
+    if (EPI == EPI_RESID_SUM) a.psum[idx] = pbase[p] + px[p];
     if (m_ == 2) {
       if (EPI == EPI_CHEB) {
         a.d[idx] = 0.0;
@@ -655,7 +662,7 @@ __device__ __forceinline__ void spmv_dict_body(int n_rows, int n_wg, const uint8
       } else {
         a.y[idx] = 0.0;
       }
-    } else if (EPI == EPI_RESID) {
+    } else if (EPI == EPI_RESID || EPI == EPI_RESID_SUM) {
       if (m) val = (a.maskmode == MASK_IDENTITY) ? pb[p] - px[p] : 0.0;
       else val = pb[p] - val;
       a.y[idx] = val;
@@ -787,6 +794,174 @@ __global__ __launch_bounds__(256) void k_spmv_dict_blk(int n_rows, int n_wg, con
       else if (a.maskmode == MASK_ZERO) a.y[idx] = 0.0;
     } else {
       a.y[idx] = m_ ? 0.0 : a.c2 * val;
+    }
+  }
+}
+
+// A square scalar operator on two interleaved components (k_spmv_dict_w8<2, .>) and a rectangular 2 x 1 block
+// operator (k_spmv_dict_blk<2, 1, .>) on the SAME P2 rows in one launch: both give a workgroup the same 256 rows on
+// the same XCD walk, so the workgroup stages both local dictionaries and every lane forms both row sums, each in its
+// own accumulators with the entry order and unroll of its own body (the sums carry the bits of the two launches).
+// The intermediate vector of the pair is never written:
+//   EPI_PAIR_ACCUM       y = (M x) + c2 (B z)                  -- the EPI_STORE launch followed by the EPI_ACCUM one
+//   EPI_PAIR_CORRECTION  B acts on z - z2, formed at the gather (k_axpby's value); with at = c2 (B (z - z2))_i:
+//                        y_i = (M x)_i + at,  r0_i = mask_i ? 0 : at   -- k_correction_setup's expressions, no sums
+enum PairEpi { EPI_PAIR_ACCUM = 0, EPI_PAIR_CORRECTION = 1 };
+struct PairDicts {
+  const uint8_t* lid_m;              // square operator
+  const int32_t *wg_ptr_m, *wg_list_m, *slen_m, *soff_m;
+  const double* sval_m;
+  int lmax_m, max_local_m;
+  const uint8_t* lid_b;              // rectangular operator
+  const int32_t *cbase_b, *wg_ptr_b, *wg_list_b, *slen_b, *soff_b;
+  const double* sval_b;
+  int lmax_b, max_local_b;
+};
+struct PairArgs {
+  const double* x;                   // operand of the square operator (two interleaved components)
+  const double* z;                   // operand of the rectangular operator
+  const double* z2;                  // EPI_PAIR_CORRECTION: subtracted from z at the gather
+  double* y;
+  double* r0;                        // EPI_PAIR_CORRECTION
+  const uint8_t* mask;               // EPI_PAIR_CORRECTION: Dirichlet flags, one per entry
+  double c2;
+};
+template <int EPI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void k_spmv_dict_pair(int n_rows, int n_wg, PairDicts d, PairArgs a) {
+  constexpr int NV = 2, BR = 2;
+  extern __shared__ double sh_dict[];
+  // doubles first (both value tables), then the ints
+  double* __restrict__ lv = sh_dict;                                            // [max_local_m * lmax_m]
+  double* __restrict__ lvb = lv + (size_t)d.max_local_m * d.lmax_m;             // [max_local_b * lmax_b * BR]
+  int* __restrict__ lo = reinterpret_cast<int*>(lvb + (size_t)d.max_local_b * d.lmax_b * BR);
+  int* __restrict__ ll = lo + d.max_local_m * d.lmax_m;
+  int* __restrict__ lob = ll + d.max_local_m;
+  int* __restrict__ llb = lob + d.max_local_b * d.lmax_b;
+  const int per = gridDim.x >> 3;
+  const int wg = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+  if (wg >= n_wg) return;                                                       // (whole workgroup)
+  {
+    const int l0 = d.wg_ptr_m[wg], nl = d.wg_ptr_m[wg + 1] - l0;
+    for (int t = threadIdx.x; t < nl * d.lmax_m; t += 256) {
+      const int j = t / d.lmax_m, k = t - j * d.lmax_m;
+      const size_t g = (size_t)d.wg_list_m[l0 + j] * d.lmax_m + k;
+      lv[t] = d.sval_m[g];
+      lo[t] = d.soff_m[g];
+    }
+    if ((int)threadIdx.x < nl) ll[threadIdx.x] = d.slen_m[d.wg_list_m[l0 + threadIdx.x]];
+  }
+  {
+    const int l0 = d.wg_ptr_b[wg], nl = d.wg_ptr_b[wg + 1] - l0;
+    for (int t = threadIdx.x; t < nl * d.lmax_b; t += 256) {
+      const int j = t / d.lmax_b, k = t - j * d.lmax_b;
+      const size_t g = (size_t)d.wg_list_b[l0 + j] * d.lmax_b + k;
+      lob[t] = d.soff_b[g];
+#pragma unroll
+      for (int q = 0; q < BR; ++q) lvb[(size_t)t * BR + q] = d.sval_b[g * BR + q];
+    }
+    if ((int)threadIdx.x < nl) llb[threadIdx.x] = d.slen_b[d.wg_list_b[l0 + threadIdx.x]];
+  }
+  const int wave = wg * 4 + ((int)threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int row = wave * 64 + lane;
+  const bool live = row < n_rows;
+  const double* __restrict__ x = a.x;
+  const double* __restrict__ z = a.z;
+  const double* __restrict__ z2 = a.z2;
+  const int st = live ? d.lid_m[row] : 0;
+  const int stb = live ? d.lid_b[row] : 0;
+  const int cb = live ? d.cbase_b[row] : 0;
+  // the epilogue's mask bytes are requested before the gather loops (entry <-> lane map as in the two bodies)
+  const size_t ebase = (size_t)wave * 64 * NV;
+  int pm[NV];
+#pragma unroll
+  for (int p = 0; p < NV; ++p) {
+    const int e = p * 64 + lane;
+    const bool in = wave * 64 + e / NV < n_rows;
+    pm[p] = (in && EPI == EPI_PAIR_CORRECTION) ? a.mask[ebase + e] : 0;
+  }
+  __syncthreads();
+  // ---- rectangular part (the body of k_spmv_dict_blk<2, 1, .>: 4 entries in flight)
+  double accb[BR];
+#pragma unroll
+  for (int o = 0; o < BR; ++o) accb[o] = 0.0;
+  {
+    const int L = live ? llb[stb] : 0;
+    const int* __restrict__ op = lob + stb * d.lmax_b;
+    const double* __restrict__ vp = lvb + (size_t)stb * d.lmax_b * BR;
+    constexpr int U = 4;
+    for (int k = 0; k < L; k += U) {
+      double xv[U];
+      int kk[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        kk[u] = k + u < L ? k + u : L - 1;
+        const int c = cb + op[kk[u]];
+        if (EPI == EPI_PAIR_CORRECTION) xv[u] = z[c] - z2[c];
+        else xv[u] = z[c];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const double w = k + u < L ? 1.0 : 0.0;
+#pragma unroll
+        for (int r = 0; r < BR; ++r) accb[r] += w * vp[(size_t)kk[u] * BR + r] * xv[u];
+      }
+    }
+  }
+  // ---- square part (spmv_dict_body<2, EPI_STORE, 2>)
+  double acc[NV];
+#pragma unroll
+  for (int o = 0; o < NV; ++o) acc[o] = 0.0;
+  {
+    const int L = live ? ll[st] : 0;
+    const int* __restrict__ op = lo + st * d.lmax_m;
+    const double* __restrict__ vp = lv + st * d.lmax_m;
+    constexpr int U = 2;
+    for (int k = 0; k < L; k += U) {
+      int c[U];
+      double v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int kk = k + u < L ? k + u : L - 1;        // past the end: last entry again, weight 0
+        c[u] = row + op[kk];
+        const double t = vp[kk];
+        v[u] = k + u < L ? t : 0.0;
+      }
+      double xv[U][NV];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int t = 0; t < NV; ++t) xv[u][t] = x[(size_t)c[u] * NV + t];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int t = 0; t < NV; ++t) acc[t] += v[u] * xv[u][t];
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < NV; ++p) {
+    const int e = p * 64 + lane;
+    const int owner = e / NV, comp = e % NV;
+    double val = 0.0, valb = 0.0;
+#pragma unroll
+    for (int o = 0; o < NV; ++o) {
+      const double t = __shfl(acc[o], owner, 64);
+      const double tb = __shfl(accb[o], owner, 64);
+      if (comp == o) { val = t; valb = tb; }
+    }
+    if (wave * 64 + owner >= n_rows) continue;
+    const size_t idx = ebase + e;
+    if (EPI == EPI_PAIR_ACCUM) {
+      double yv = val;
+      yv += a.c2 * valb;
+      a.y[idx] = yv;
+    } else {
+      const double at = a.c2 * valb;
+      const double b = val + at;
+      const double r = pm[p] ? 0.0 : at;
+      a.y[idx] = b;
+      a.r0[idx] = r;
     }
   }
 }
@@ -1414,12 +1589,18 @@ bool lattice_offsets_fit(int64_t w, int64_t h, int nv, bool rf) {
 // tuning / test switches, re-read whenever a context is created (tests switch them between contexts)
 static bool g_lattice_on = true, g_lattice_transfers_on = true, g_lattice_kinds_on = true;
 static bool g_bicg_fused = true;     // NSFEM_BICG_FUSED=0: BiCGStab with the start kernel and one launch per update (A/B, tests)
+// NSFEM_STEP_FUSED=0: the step frame (begin step, projection check, correction assembly and finish) with one launch
+// per vector pass, as before the fused kernels (A/B, tests); a context keeps the value it was created under
+static bool g_step_fused = true;
+bool step_fused_enabled() { return g_step_fused; }
 void refresh_env_switches() {
   const char* e = std::getenv("NSFEM_LATTICE");
   g_lattice_on = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_BICG_FUSED");
   g_bicg_fused = e ? std::atoi(e) != 0 : true;
-  e = std::getenv("NSFEM_LATTICE_KINDS");           // 0: every launch runs the runtime-flag kernel (A/B, tests)
+  e = std::getenv("NSFEM_STEP_FUSED");
+  g_step_fused = e ? std::atoi(e) != 0 : true;
+  e = std::getenv("NSFEM_LATTICE_KINDS");          // 0: every launch runs the runtime-flag kernel (A/B, tests)
   g_lattice_kinds_on = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_LATTICE_TRANSFERS");
   g_lattice_transfers_on = e ? std::atoi(e) != 0 : true;
@@ -2352,6 +2533,8 @@ static SpmvArgs make_args(const double* x, const double* b, double* y, const uin
 #endif
   a.gptr = nullptr;
   a.gbuf = nullptr;
+  a.base = nullptr;
+  a.psum = nullptr;
   return a;
 }
 
@@ -2411,6 +2594,61 @@ void launch_spmv_axpy(hipStream_t s, const BlockMat& A, int nv, double scale, co
   a.c2 = scale;
   a.dict_ok = dict_ok;
   spmv_dispatch<EPI_ACCUM>(s, A, nv, a);
+}
+// q = r - A z and psum = base + z in one launch of the scalar dictionary kernel (no row mask).  false: A has no
+// dictionary copy a residual may use (the caller runs the two launches)
+bool launch_residual_sum(hipStream_t s, const BlockMat& A, const double* z, const double* r, double* q,
+                         const double* base, double* psum) {
+  if (!A.dict_ready || A.dict->rect || A.br != 1 || A.bc != 1 || !A.dict->exact) return false;
+  const StencilDict& d = *A.dict;
+  SpmvArgs a = make_args(z, r, q, nullptr, MASK_NONE);
+  a.base = base;
+  a.psum = psum;
+  const int n_wg = (d.n_rows + 255) / 256;
+  a.skip0 = n_wg;
+  a.skipn = 0;
+  const int grid = (n_wg + 7) & ~7;
+  const size_t lds = (size_t)d.max_local * d.lmax * 12 + (size_t)d.max_local * 12;
+  hipLaunchKernelGGL((k_spmv_dict_w8<1, EPI_RESID_SUM>), dim3(grid), dim3(256), lds, s, d.n_rows, n_wg, d.lid.p,
+                     d.wg_ptr.p, d.wg_list.p, d.len.p, d.off.p, A.dict_vals.p, d.dpos.p, d.lmax, d.max_local, a);
+  NSFEM_HIP(hipGetLastError());
+  return true;
+}
+
+// Can the pair kernel replace the products with M (two interleaved components) and B (2 x 1 blocks) on the same rows?
+// Only where both run on exact dictionary copies today (k_spmv_dict_w8<2, .> and k_spmv_dict_blk<2, 1, .>).
+bool spmv_pair_available(const BlockMat& M, const BlockMat& B) {
+  if (!M.dict_ready || !B.dict_ready) return false;
+  const StencilDict &dm = *M.dict, &db = *B.dict;
+  return !dm.rect && dm.exact && M.br == 1 && M.bc == 1 && db.rect && db.exact && B.br == 2 && B.bc == 1 &&
+         dm.n_rows == db.n_rows;
+}
+template <int EPI>
+static void launch_pair(hipStream_t s, const BlockMat& M, const BlockMat& B, const PairArgs& a) {
+  const StencilDict &dm = *M.dict, &db = *B.dict;
+  PairDicts d;
+  d.lid_m = dm.lid.p; d.wg_ptr_m = dm.wg_ptr.p; d.wg_list_m = dm.wg_list.p; d.slen_m = dm.len.p; d.soff_m = dm.off.p;
+  d.sval_m = M.dict_vals.p; d.lmax_m = dm.lmax; d.max_local_m = dm.max_local;
+  d.lid_b = db.lid.p; d.cbase_b = db.cbase.p; d.wg_ptr_b = db.wg_ptr.p; d.wg_list_b = db.wg_list.p;
+  d.slen_b = db.len.p; d.soff_b = db.off.p; d.sval_b = B.dict_vals.p; d.lmax_b = db.lmax; d.max_local_b = db.max_local;
+  const int n_wg = (dm.n_rows + 255) / 256;
+  const int grid = (n_wg + 7) & ~7;
+  const size_t lds = (size_t)dm.max_local * dm.lmax * 12 + (size_t)dm.max_local * 4 +
+                     (size_t)db.max_local * db.lmax * (8 * 2 + 4) + (size_t)db.max_local * 4;
+  hipLaunchKernelGGL((k_spmv_dict_pair<EPI>), dim3(grid), dim3(256), lds, s, dm.n_rows, n_wg, d, a);
+  NSFEM_HIP(hipGetLastError());
+}
+// y = M x + c2 B z  (spmv_pair_available(M, B))
+void launch_spmv_pair_accum(hipStream_t s, const BlockMat& M, const BlockMat& B, const double* x, double c2,
+                            const double* z, double* y) {
+  PairArgs a{x, z, nullptr, y, nullptr, nullptr, c2};
+  launch_pair<EPI_PAIR_ACCUM>(s, M, B, a);
+}
+// rhs = M x + a B (z - z2),  r0 = a B (z - z2) on rows with mask = 0, 0 elsewhere  (spmv_pair_available(M, B))
+void launch_spmv_pair_correction(hipStream_t s, const BlockMat& M, const BlockMat& B, const double* x, double a_,
+                                 const double* z, const double* z2, const uint8_t* mask, double* rhs, double* r0) {
+  PairArgs a{x, z, z2, rhs, r0, mask, a_};
+  launch_pair<EPI_PAIR_CORRECTION>(s, M, B, a);
 }
 void launch_cheb_step(hipStream_t s, const BlockMat& A, int nv, const double* x, const double* b,
                       const double* dinv, double* d, double c1, double c2, double* xout,
@@ -2497,6 +2735,37 @@ __global__ __launch_bounds__(256) void k_correction_setup(int64_t n, double a, d
     parts_b[blockIdx.x] = sb;
   }
 }
+// What follows the first Chebyshev sequence of the velocity-correction mass solve, in one pass (one rank, fused
+// step, predicted step count):  u0 = u* + e  and the three sums of the solve's only check -- |r_new|^2 (k_dot's
+// partition and loop), |r0|^2 and |rhs|^2 (k_correction_setup's loop shape: the bits of its sums).  k_set_values
+// then puts the Dirichlet values into u0 (e vanishes there), instead of into a copy of u* before the solve.
+// u0 equals the copy-then-add result except that a Dirichlet value of -0.0 keeps its sign: the add gave
+// vals + e_bc = -0.0 + 0.0 = +0.0.
+__global__ __launch_bounds__(256) void k_correction_finish(int64_t n, const double* __restrict__ ustar,
+                                                           const double* __restrict__ e, double* __restrict__ u0,
+                                                           const double* __restrict__ rn, const double* __restrict__ r0,
+                                                           const double* __restrict__ rhs, double* __restrict__ parts_n,
+                                                           double* __restrict__ parts_r, double* __restrict__ parts_b) {
+  __shared__ double sh[4];
+  double v = 0.0, sr = 0.0, sb = 0.0;
+  GRID_STRIDE(i, n) {
+    u0[i] = ustar[i] + e[i];
+    const double q = rn[i];
+    const double b = rhs[i];
+    const double r = r0[i];
+    v += q * q;
+    sb += b * b;
+    sr += r * r;
+  }
+  v = block_sum(v, sh);
+  sr = block_sum(sr, sh);
+  sb = block_sum(sb, sh);
+  if (threadIdx.x == 0) {
+    parts_n[blockIdx.x] = v;
+    parts_r[blockIdx.x] = sr;
+    parts_b[blockIdx.x] = sb;
+  }
+}
 // Dirichlet rows of a Newton residual AND its squared norm in one launch (one rank): b[dof_j] = x[dof_j] - g_j on the
 // nbc constrained dofs (their rows carry mask != 0 and are skipped by the sum over the free rows, so the two parts
 // of the kernel touch disjoint entries), parts = sum over all rows of b^2
@@ -2551,6 +2820,21 @@ __global__ __launch_bounds__(256) void k_sub_mean(int64_t n, int64_t n_global,
   __shared__ double sh[4];
   const double mean = sum_parts(parts, sh) / (double)n_global;
   GRID_STRIDE(i, n) x[i] -= mean;
+}
+// x -= mean(x) and the partial sums of x . x afterwards (k_dot's partition) in one pass: every block re-reduces the
+// mean as k_sub_mean does
+__global__ __launch_bounds__(256) void k_sub_mean_dot(int64_t n, int64_t n_global, const double* __restrict__ parts,
+                                                      double* __restrict__ x, double* __restrict__ parts_out) {
+  __shared__ double sh[4];
+  const double mean = sum_parts(parts, sh) / (double)n_global;
+  double v = 0.0;
+  GRID_STRIDE(i, n) {
+    const double t = x[i] - mean;
+    x[i] = t;
+    v += t * t;
+  }
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) parts_out[blockIdx.x] = v;
 }
 __global__ __launch_bounds__(256) void k_sum(int64_t n, const double* __restrict__ x,
                                              double* __restrict__ parts) {
@@ -2657,6 +2941,16 @@ void launch_correction_setup(hipStream_t s, int64_t n, double a, double* rhs, co
 void launch_sum_sub_mean(hipStream_t s, int64_t n, double* x, double* parts) {
   LAUNCH(k_sum, kParts, s, n, x, parts);
   LAUNCH(k_sub_mean, vgrid(n), s, n, n, parts, x);
+}
+// the same and, fused into the subtraction, the partial sums of x . x of the shifted vector (slot `parts_dot`)
+void launch_sum_sub_mean_dot(hipStream_t s, int64_t n, double* x, double* parts, double* parts_dot) {
+  LAUNCH(k_sum, kParts, s, n, x, parts);
+  LAUNCH(k_sub_mean_dot, kParts, s, n, n, parts, x, parts_dot);
+}
+void launch_correction_finish(hipStream_t s, int64_t n, const double* ustar, const double* e, double* u0,
+                              const double* rn, const double* r0, const double* rhs, double* parts_n, double* parts_r,
+                              double* parts_b) {
+  LAUNCH(k_correction_finish, kParts, s, n, ustar, e, u0, rn, r0, rhs, parts_n, parts_r, parts_b);
 }
 void launch_sum(hipStream_t s, int64_t n, const double* x, double* parts) { LAUNCH(k_sum, kParts, s, n, x, parts); }
 void launch_sub_mean(hipStream_t s, int64_t n, int64_t count, const double* parts, double* x) {

@@ -270,6 +270,18 @@ void launch_cheb_step(hipStream_t s, const BlockMat& A, int nv, const double* x,
                       const uint8_t* rowmask, int ghost = 0 /* 1: ghost rows keep x */, int phase = 0,
                       int ident = 0 /* 1: rows flagged 1 take xout = b (identity rows) */);
 
+// Fused launches of the step frame (NSFEM_STEP_FUSED, linalg.hip); each reproduces the launches it replaces bit for bit
+// q = r - A z and psum = base + z (scalar dictionary kernel, no mask); false: no exact dictionary copy, nothing launched
+bool launch_residual_sum(hipStream_t s, const BlockMat& A, const double* z, const double* r, double* q,
+                         const double* base, double* psum);
+// M (scalar P2 x P2, two interleaved components) and B (2 x 1 blocks, P2 rows) both run on exact dictionaries today
+bool spmv_pair_available(const BlockMat& M, const BlockMat& B);
+void launch_spmv_pair_accum(hipStream_t s, const BlockMat& M, const BlockMat& B, const double* x, double c2,
+                            const double* z, double* y);                          // y = M x + c2 B z
+void launch_spmv_pair_correction(hipStream_t s, const BlockMat& M, const BlockMat& B, const double* x, double a,
+                                 const double* z, const double* z2, const uint8_t* mask, double* rhs, double* r0);
+bool step_fused_enabled();              // NSFEM_STEP_FUSED as last read by refresh_env_switches
+
 // multi-step lattice smoother (2D lexicographic lattices with a stencil dictionary; linalg.hip)
 void refresh_env_switches();            // NSFEM_LATTICE, NSFEM_LATTICE_TRANSFERS (re-read by nsfem_create)
 void refresh_assembly_switches();       // NSFEM_JAC_LATTICE
@@ -637,6 +649,12 @@ void launch_dot(hipStream_t s, int64_t n, const double* x, const double* y, doub
 void launch_sum_sub_mean(hipStream_t s, int64_t n, double* x, double* parts);
 void launch_correction_setup(hipStream_t s, int64_t n, double a, double* rhs, const double* t, const uint8_t* mask,
                              double* r0, double* parts_r, double* parts_b);
+// x -= mean(x), then x . x of the shifted vector into `parts_dot`, the subtraction and the dot in one launch
+void launch_sum_sub_mean_dot(hipStream_t s, int64_t n, double* x, double* parts, double* parts_dot);
+// u0 = ustar + e ; partial sums of rn . rn, r0 . r0, rhs . rhs (the partitions of k_dot / k_correction_setup)
+void launch_correction_finish(hipStream_t s, int64_t n, const double* ustar, const double* e, double* u0,
+                              const double* rn, const double* r0, const double* rhs, double* parts_n, double* parts_r,
+                              double* parts_b);
 // the same together with |b|^2 (512 partial sums) in one launch; rows with mask != 0 must be exactly the nbc dofs
 void launch_bc_residual_norm(hipStream_t s, int64_t n, double* b, const uint8_t* mask, int nbc, const int32_t* dofs,
                              const double* g, const double* x, double* parts);
@@ -1246,6 +1264,12 @@ struct nsfem_ctx {
   nsfem::Multigrid mg_p, mg_v;
   bool cor_start_ready = false;                // correction_assemble produced the mass solve's start residual and sums
   uint64_t cor_start_touch = 0;                //   ... and nobody has used the Krylov work vectors since (kw.touch)
+  // fused step frame (NSFEM_STEP_FUSED at creation).  cor_finish_pending: correction_assemble left U0 unwritten and
+  // the sums of slots 12, 13 unformed -- k_correction_finish after the first Chebyshev sequence supplies them
+  bool step_fused = true;
+  bool cor_finish_pending = false;
+  // launches so far: pair kernel begin step / correction, k_correction_finish, fused projection epilogue
+  int64_t step_frame_launches[4] = {0, 0, 0, 0};
   nsfem::FastDiag fd_p{&comm};                 // direct projection-step solver on tensor-product lattices
   nsfem::FastDiag3 fd3_p{&comm};               // the same on 3D box lattices (direct or CG preconditioner)
   // the factors precond = 3 uses: the 3D ones if set, else the 2D ones, else none (a setter releases the other object)
