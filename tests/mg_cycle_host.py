@@ -45,7 +45,11 @@ Precision: every cycle exists in float64 (scipy products) and in numpy.longdoubl
 large for that -- the same row sums on the CSR arrays); `rel(z64, zld)` measures what rounding does to one case and
 sets the tolerance of the device comparison (tests/test_gpu_multigrid_cycle.py).
 
-Out of scope: partitioned contexts (additive levels, relaxed halo mode, global coarse solve)."""
+Partitioned contexts (strips, slabs): `PartitionedCycle` below -- exact halo mode is the serial cycle, relaxed halo
+mode freezes the ghost values inside a smoothing sequence; the replicated global coarse solve and its tail are levels of
+the serial hierarchy.  Checked on the host by tests/test_partitioned_cycle_host.py, on the device by
+tests/test_gpu_partitioned_cycle.py.  Still out of scope: additive (algebraic Schur) levels, periodic partitions with
+wrapped global numbering, the RCB graph partition, Krylov iterates on N ranks."""
 import math
 
 import numpy as np
@@ -241,6 +245,7 @@ class HostCycle:
         cur = np.asarray(flags0, dtype=bool).reshape(self.A[0].shape[0], nv)
         for l in range(self.active):
             A = self.A[l]
+            cur = self.level_flags(l, cur)
             self.flags.append(cur)
             dinv = np.where(cur, dtype(0.0), (dtype(1.0) / A.diagonal())[:, None])
             gersh = (A.abs_row_sums()[:, None] * dinv)[~cur]
@@ -262,6 +267,10 @@ class HostCycle:
         elif self.A[-1].shape[0] <= coarse_dense_max:
             self.coarse_inv = [self._coarse_inverse(c, singular) for c in range(nv)]
 
+    def level_flags(self, l, flags):
+        """the row flags of level l as injection hands them down (PartitionedCycle: the global coarse mask)"""
+        return flags
+
     def _coarse_inverse(self, c, singular):
         dtype = self.dtype
         a = self.A[-1].toarray()
@@ -281,9 +290,9 @@ class HostCycle:
         a[:, m] = 0.0
         return a
 
-    def cheb(self, l, k, rho_prev):
+    def cheb(self, l, k, rho_prev, lmax=None):
         dtype = self.dtype
-        b = dtype(1.05) * self.lmax[l]
+        b = dtype(1.05) * (self.lmax[l] if lmax is None else lmax)
         a = b / self.ratio[l]
         theta, delta = dtype(0.5) * (b + a), dtype(0.5) * (b - a)
         sigma = theta / delta
@@ -322,6 +331,10 @@ class HostCycle:
             x, r = None, b                             # (the input as it is, flagged rows included)
         bc = np.where(mc, self.dtype(0.0), self.R[l].dot(r))
         px = np.where(m, self.dtype(0.0), self.P[l].dot(self.cycle(l + 1, bc)))
+        return self.post_smooth(l, b, x, px)
+
+    def post_smooth(self, l, b, x, px):
+        """the `post` steps from x + P x_c (x None: no pre-smoothing, the start vector is P x_c)"""
         x = px if x is None else x + px
         return self.smooth(l, b, x, self.post, self.identity_rows and l == 0)
 
@@ -342,6 +355,124 @@ class HostCycle:
         A = self.A[0]
         S = sp.csr_matrix((A.data.astype(np.float64), A.indices, A.indptr), shape=A.shape)
         return sp.kron(S, sp.identity(self.nv), format="csr")
+
+
+def submatrix(M, rows, cols):
+    """the rows `rows` of the _Mat M over the columns `cols` (both global ids; every entry of those rows has to lie in
+    `cols`: an owned row of a partition is complete), values untouched, column ids sorted as in M"""
+    nnz = M.data.size
+    pos = sp.csr_matrix((np.arange(1, nnz + 1, dtype=np.int64), M.indices, M.indptr), shape=M.shape)
+    where = np.full(M.shape[1], -1, dtype=np.int64)
+    where[cols] = np.arange(len(cols))
+    S = pos[rows]
+    assert (where[S.indices] >= 0).all(), "an owned row reaches a column that is neither owned nor a ghost"
+    S = sp.csr_matrix((S.data, where[S.indices], S.indptr), shape=(len(rows), len(cols)))
+    S.sort_indices()
+    return _Mat(S, M.dtype, data=M.data[S.data - 1])
+
+
+RULES = ("refresh_every_step", "zero_ghosts", "no_ghost_correction", "local_lmax", "rank0_coarse_mask")
+
+
+class PartitionedCycle(HostCycle):
+    """The cycle of a partitioned context (strips, slabs: Multigrid::vcycle / smooth with a communicator), stated on
+    the GLOBAL matrices of `Hierarchy`.  `ranks[l]`, one entry per partitioned level l (finest first; the last one is
+    the level that is gathered and solved on the replicated mesh): per rank (O_r, G_r), the global rows it owns and
+    the global rows it keeps ghost copies of.  The levels after the last partitioned one are the replicated tail (or
+    none: the last partitioned level is the dense coarsest level) -- together the serial hierarchy.
+
+    exact halo mode (relaxed=False)   the serial cycle: every product sees ghosts exchanged just before it.
+    relaxed halo mode                 a smoothing sequence of s steps on a partitioned level other than the last, from
+        x or from zero, is run by every rank on its own: y = x[O_r u G_r] (zeros from zero), d = 0; per step and owned
+        unflagged row i: res_i = b_i - sum_{j in O_r u G_r} A_ij y_j, d_i = c1_k d_i + c2_k dinv_i res_i, y_i += d_i;
+        ghost rows of y never change; x[O_r] = y[O_r].  Coefficients from the global lmax (Multigrid::refresh
+        all-reduces the maximum, and every owned row is complete, so that is the serial number).  Everything else is
+        the serial algorithm on global vectors: the residual after pre-smoothing sees exact ghosts (halo_fill before
+        launch_residual), restriction and prolongation are serial, post-smoothing starts from x + P x_c with the
+        owners' values of x + P x_c on the ghost rows (the `ghost = 2` prolongation), the last partitioned level is
+        solved by the replicated hierarchy or the dense (pseudo-)inverse under the union of the ranks' masks.
+
+    `revert`: names out of RULES, each putting one plausible bug in the place of one rule (host tests only):
+        refresh_every_step    ghosts exchanged before every step (the exact cycle)
+        zero_ghosts           ghost values zero instead of the start vector's
+        no_ghost_correction   post-smoothing: ghost rows hold x without the prolongated correction
+        local_lmax            every rank smooths with the Gershgorin bound of its own rows
+        rank0_coarse_mask     the replicated solve flags the rows that rank 0 owns and flags, not the union"""
+
+    def __init__(self, *args, ranks, relaxed=True, revert=(), **kw):
+        assert set(revert) <= set(RULES), revert
+        self.ranks, self.relaxed, self.revert = ranks, relaxed, tuple(revert)
+        self.n_part = len(ranks)
+        super().__init__(*args, **kw)
+        assert self.n_part <= self.active
+        self.local, self.local_lmax = [], []
+        for l in range(self.n_part - 1):
+            A, n = self.A[l], self.A[l].shape[0]
+            own = np.concatenate([O for O, _ in ranks[l]])
+            assert np.array_equal(np.sort(own), np.arange(n)), "the ranks' owned rows partition the level"
+            self.local.append([submatrix(A, O, np.concatenate([O, G])) for O, G in ranks[l]])
+            gersh = A.abs_row_sums()[:, None] * self.dinv[l]
+            lm = []
+            for O, _ in ranks[l]:
+                g = gersh[O][~self.flags[l][O]]
+                v = g.max() if g.size else self.dtype(0.0)
+                lm.append(v if v > 0.0 else self.dtype(2.0))
+            self.local_lmax.append(lm)
+
+    def level_flags(self, l, flags):
+        if "rank0_coarse_mask" in self.revert and l == self.n_part - 1:
+            mine = np.zeros(flags.shape[0], dtype=bool)
+            mine[self.ranks[l][0][0]] = True
+            return flags & mine[:, None]
+        return flags
+
+    def smooth(self, l, b, x, steps, ident=False, ghost_x=None):
+        if not self.relaxed or l >= self.n_part - 1 or "refresh_every_step" in self.revert:
+            return super().smooth(l, b, x, steps, ident)
+        zero = self.dtype(0.0)
+        out = np.zeros_like(b)
+        for r, (O, G) in enumerate(self.ranks[l]):
+            A, no = self.local[l][r], len(O)
+            m, dinv, bo = self.flags[l][O][:, :, None], self.dinv[l][O][:, :, None], b[O]
+            y = np.zeros((no + len(G),) + b.shape[1:], dtype=self.dtype)
+            if x is not None:
+                y[:no] = x[O]
+                if "zero_ghosts" not in self.revert:
+                    y[no:] = (x if ghost_x is None else ghost_x)[G]
+            d = np.zeros_like(bo)
+            rho = zero
+            lmax = self.local_lmax[l][r] if "local_lmax" in self.revert else None
+            for k in range(steps):
+                c1, c2, rho = self.cheb(l, k, rho, lmax)
+                res = bo if x is None and k == 0 else bo - A.dot(y)
+                d = np.where(m, zero, c1 * d + c2 * dinv * res)
+                y[:no] = d if x is None and k == 0 else np.where(m, zero, y[:no] + d)
+                if ident and k == steps - 1:
+                    y[:no] = np.where(m, bo, y[:no])
+            out[O] = y[:no]
+        return out
+
+    def post_smooth(self, l, b, x, px):
+        ghost_x = None
+        if "no_ghost_correction" in self.revert:
+            ghost_x = np.zeros_like(px) if x is None else x
+        x = px if x is None else x + px
+        return self.smooth(l, b, x, self.post, self.identity_rows and l == 0, ghost_x=ghost_x)
+
+
+def partition_ranks(parts, velocity):
+    """`ranks` of PartitionedCycle from the StripPartition / SlabPartition objects of all ranks: the P1 fine level and
+    every local level (global ids: global_p1_offset + local id), for the velocity hierarchy the P2 level first"""
+    def split(glob, ghost):
+        glob, ghost = np.asarray(glob, dtype=np.int64), np.asarray(ghost) != 0
+        return glob[~ghost], glob[ghost]
+
+    levels = [[split(p.p2_global, p.p2_ghost) for p in parts]] if velocity else []
+    levels.append([split(p.p1_global, p.p1_ghost) for p in parts])
+    for k in range(len(parts[0].levels)):
+        levs = [p.levels[k][0] for p in parts]
+        levels.append([split(lv.global_p1_offset() + np.arange(lv.n_p1), lv.p1_ghost) for lv in levs])
+    return levels
 
 
 class Hierarchy:
@@ -367,13 +498,14 @@ class Hierarchy:
             self.nested.append(getattr(cm, "nested_in_finer", None))
         self.p2p1 = p2_from_p1(dm.p2_dofmap, dm.p1_dofmap)
 
-    def pressure(self, dirichlet, degree=2, eig_ratio=4.0, coarse_dense_max=1200, dtype=np.float64):
-        """mg_p: V(degree, degree) on K; singular when the Dirichlet set is empty"""
+    def pressure(self, dirichlet, degree=2, eig_ratio=4.0, coarse_dense_max=1200, dtype=np.float64, make=None):
+        """mg_p: V(degree, degree) on K; singular when the Dirichlet set is empty.  make: the cycle class (HostCycle;
+        functools.partial(PartitionedCycle, ranks=...) for a partitioned context)"""
         flags = np.zeros((self.n_p1, 1), dtype=bool)
         flags[np.asarray(dirichlet, dtype=np.int64)] = True
         ops = [combine(0.0, None, 1.0, K, dtype) for K in self.K1]
-        return HostCycle(ops, self.transfers, self.nested, flags, 1, degree, degree, eig_ratio,
-                         singular=len(dirichlet) == 0, coarse_dense_max=coarse_dense_max, dtype=dtype)
+        return (make or HostCycle)(ops, self.transfers, self.nested, flags, 1, degree, degree, eig_ratio,
+                                   singular=len(dirichlet) == 0, coarse_dense_max=coarse_dense_max, dtype=dtype)
 
     def divergence(self):
         if not hasattr(self, "_D"):
@@ -437,14 +569,15 @@ class Hierarchy:
         return None
 
     def velocity(self, dirichlet, a, b, degree=2, eig_ratio=4.0, symmetric=False, coarse_dense_max=1200,
-                 trunc_ratio=4.0, trunc_tol=0.1, dtype=np.float64):
+                 trunc_ratio=4.0, trunc_tol=0.1, dtype=np.float64, make=None):
         """mg_v on a M + b K: V(0, degree + 1), or V(degree, degree) in symmetric mode; identity rows on level 0;
-        `dirichlet`: interleaved velocity dofs"""
+        `dirichlet`: interleaved velocity dofs; make: as in `pressure`"""
         flags = np.zeros(self.n_p2 * self.dim, dtype=bool)
         flags[np.asarray(dirichlet, dtype=np.int64)] = True
         post = degree + 1
         pre, post = (max(1, post - 1),) * 2 if symmetric else (0, post)
         ops = [combine(a, self.M2, b, self.K2, dtype)] + [combine(a, M, b, K, dtype) for M, K in zip(self.M1, self.K1)]
-        return HostCycle(ops, [self.p2p1] + self.transfers, [True] + self.nested, flags.reshape(self.n_p2, self.dim),
-                         self.dim, pre, post, eig_ratio, singular=False, coarse_dense_max=coarse_dense_max,
-                         identity_rows=True, truncation=self.truncation(a, b, trunc_ratio, trunc_tol), dtype=dtype)
+        return (make or HostCycle)(ops, [self.p2p1] + self.transfers, [True] + self.nested,
+                                   flags.reshape(self.n_p2, self.dim), self.dim, pre, post, eig_ratio, singular=False,
+                                   coarse_dense_max=coarse_dense_max, identity_rows=True,
+                                   truncation=self.truncation(a, b, trunc_ratio, trunc_tol), dtype=dtype)

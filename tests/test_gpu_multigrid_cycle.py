@@ -48,7 +48,9 @@ velocity 2 / 2; box48 pressure 1 / 2, velocity 2 / 2; box96x40 pressure 2 / 4, v
 box16x8, cube8, dfg 0 / 0; box32 truncated velocity 2 / 2; box32flat (smoothed lattice coarsest level) pressure
 1 / 5, velocity 2 / 6.
 
-Out of scope: partitioned contexts (additive levels, relaxed halo mode, global coarse solve).  The Schur hierarchy
+Partitioned contexts (strips, slabs, exact and relaxed halo mode, the replicated coarse solve):
+tests/test_gpu_partitioned_cycle.py; still out of scope there: additive (algebraic Schur) levels, periodic partitions
+with wrapped global numbering, the RCB graph partition, Krylov iterates on N ranks.  The Schur hierarchy
 mg_s and the mass smoother mg_m (nsfem_mg_apply 3 / 4): tests/test_gpu_monolithic_linear.py."""
 import numpy as np
 import pytest
