@@ -795,6 +795,51 @@ int nsfem_derived_fields(nsfem_ctx* ctx, int velocity_slot, int pressure_slot, i
                          unsigned quantity_mask, int center, double* out_host, int64_t out_len);
 int nsfem_derived_info(nsfem_ctx* ctx, int64_t out[4]);
 
+/* ---- energy spectra on box lattices (csrc/spectrum.hip, the axis passes through the tile body of csrc/fastdiag.hip):
+ * a separable linear transform of a nodal field on its lattice followed by binned sums of squares -- the wavenumber
+ * spectrum E(k) of a periodic box, the one-dimensional spectra E(k_x; y) of a channel.  Replaces get_state plus
+ * numpy.fft.fftn plus a Python binning loop per sample; new, the reference has no spectra.
+ *
+ * On a box mesh the P2 nodes (vertices and edge midpoints) occupy every point of the half-spacing lattice exactly once,
+ * the P1 nodes every point of the vertex lattice: the nodal values are a regular sample, n_a = 2 cells_a (P1: cells_a)
+ * points along a periodic axis and one more along a walled one.  The device part is generic; what a bin means (a
+ * shell, a (y, |k_x|) pair) is decided on the host (energy_spectrum.py).
+ *
+ * nsfem_spectrum_set: the plan of this context (one per context; setting again replaces it, n[0] = 0 frees it).  n: the
+ * lattice points per axis, x fastest, n[2] = 1 in 2D.  Fx, Fy, Fz: row-major [n_a][n_a], row = basis function; NULL:
+ * the axis is not transformed.  node_of_point [n0 n1 n2]: the node that carries each lattice point.  The bins are a CSR
+ * of lattice points: bin b holds bin_points[bin_ptr[b] .. bin_ptr[b + 1]); bins may overlap, leave points out or be
+ * empty.  Validated on the host before anything is uploaded -- every node_of_point inside the P2 node count (the
+ * largest one is kept: nsfem_spectrum_compute refuses a slot whose field has fewer nodes), every bin point inside the
+ * lattice, bin_ptr starting at 0 and not decreasing, the matrices finite -- so no kernel can index out of range.  The
+ * plan owns two work arrays of n0 n1 n2 doubles (components are processed one after the other), the chunk partials
+ * and the result; nothing else is allocated later.
+ *
+ * nsfem_spectrum_compute: out [n_bins][ncomp] = sum over the points of the bin of c^2, c the transformed values of
+ * one component, RAW (normalisation is the host's business).  slot: any slot of nodal values -- NSFEM_U0 .. NSFEM_USTAR
+ * and NSFEM_BODY_FORCE give ncomp = dim (node-interleaved), NSFEM_T0 .. NSFEM_T_SOURCE and the pressure slots 1.  Per
+ * component: k_spec_pack (w[point] = state[node_of_point[point] ncomp + c], coalesced writes, gathered reads), one
+ * launch per transformed axis (x: a plain GEMM over [n2 n1] x n0, y: the batched plane product, z: a plain GEMM over
+ * n2 x [n1 n0]), k_spec_bin (one workgroup of 256 threads per chunk of at most 2048 CSR entries, chunks never straddle
+ * a bin: thread t adds the squares of the entries t, t + 256, ... in ascending order, then a fixed tree in LDS) and
+ * k_spec_bin_sum (one thread per bin adds its chunk partials in ascending order; +0.0 for an empty bin).  No atomics:
+ * the same state gives the same bytes, whatever ran in between.  No state slot and no buffer of the step is written.
+ *
+ * With the real orthonormal Fourier basis of n points (row 0 constant, then cos / sin pairs scaled sqrt(2 / n), then
+ * the alternating row when n is even) the squares of the cos and sin coefficients of wavenumber k add up to
+ * n (|u^_k|^2 + |u^_-k|^2), u^ the normalised DFT; in d dimensions the sum over the 2^d cos / sin products is the
+ * energy of all sign combinations of (k_x, k_y, k_z).  No complex arithmetic is needed.
+ *
+ * nsfem_spectrum_info: out = {transform launches, bin launches, calls, bytes of the plan}.
+ * NSFEM_ERR_ARG, with a message, nothing launched and the plan and counters unchanged: a context with a communicator
+ * (partitioned meshes are out of scope, as for the statistics and the derived fields), a non-positive n, a failed
+ * validation, a slot of no nodal kind or without storage, a wrong out_len, compute or info before set. */
+int nsfem_spectrum_set(nsfem_ctx* ctx, const int32_t n[3], const double* Fx, const double* Fy, const double* Fz,
+                       const int32_t* node_of_point, int32_t n_bins, const int32_t* bin_ptr,
+                       const int32_t* bin_points);
+int nsfem_spectrum_compute(nsfem_ctx* ctx, int slot, double* out /* [n_bins][ncomp] */, int64_t out_len);
+int nsfem_spectrum_info(nsfem_ctx* ctx, int64_t out[4]);
+
 /* ---- wall quantities (csrc/wall.hip): everything evaluated on a set of facets -- measure, pressure force, viscous
  * force, mass flux, mean temperature, conductive heat flux, torque -- per facet and summed per group of facets, from a
  * facet set that stays resident on the device.  The facet side of the device post-processing; nsfem_boundary_force

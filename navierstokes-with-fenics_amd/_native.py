@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_stats_enable", "nsfem_stats_sample", "nsfem_stats_get", "nsfem_stats_set_groups", "nsfem_stats_profiles",
     "nsfem_stats_info", "nsfem_stats_weight",
     "nsfem_derived_components", "nsfem_derived_fields", "nsfem_derived_info",
+    "nsfem_spectrum_set", "nsfem_spectrum_compute", "nsfem_spectrum_info",
     "nsfem_wall_set_facets", "nsfem_wall_compute", "nsfem_wall_components", "nsfem_wall_info",
 )
 
@@ -276,6 +277,9 @@ def load_library(path=None):
         "nsfem_derived_components": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int)]),
         "nsfem_derived_fields": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, pd, i64]),
         "nsfem_derived_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_spectrum_set": (C.c_int, [vp, pi, pd, pd, pd, pi, i32, pi, pi]),
+        "nsfem_spectrum_compute": (C.c_int, [vp, C.c_int, pd, i64]),
+        "nsfem_spectrum_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_wall_set_facets": (C.c_int, [vp, i32, pi, pi, pi, i32]),
         "nsfem_wall_compute": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(WallOpts), pd, pd]),
         "nsfem_wall_components": (C.c_int, [vp, C.POINTER(C.c_int)]),
@@ -1289,6 +1293,60 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_derived_info(self._h, out))
         return dict(cell_launches=int(out[0]), gather_launches=int(out[1]), calls=int(out[2]), bytes=int(out[3]))
+
+    # -- energy spectra (csrc/spectrum.hip) ----------------------------------------------
+    def spectrum_set(self, shape, matrices, node_of_point, bin_ptr, bin_points):
+        """the transform-and-bin plan of this context (replaces an earlier one): ``shape`` = lattice points per axis, x
+        first (2 or 3 entries); ``matrices`` = per axis a row-major [n_a, n_a] matrix (row = basis function) or None
+        (axis not transformed); ``node_of_point`` [prod(shape)] with x fastest; the bins as a CSR of lattice points.
+        ``shape = None`` frees the plan."""
+        n = np.ones(3, dtype=np.int32)
+        if shape is None:
+            n[0] = 0
+            self._check(self._lib.nsfem_spectrum_set(self._h, _ip(n), None, None, None, None, 0, None, None))
+            self._spectrum_bins = 0
+            return
+        shape = [int(v) for v in shape]
+        matrices = list(matrices)
+        if not 1 <= len(shape) <= 3 or len(matrices) != len(shape):
+            raise ValueError("shape / matrices do not match")
+        n[:len(shape)] = shape
+        F = []
+        for a, m in enumerate(matrices):
+            if m is None:
+                F.append(None)
+                continue
+            m = np.ascontiguousarray(m, dtype=np.float64)
+            if m.shape != (shape[a], shape[a]):
+                raise ValueError("matrix of axis %d is not [%d, %d]" % (a, shape[a], shape[a]))
+            F.append(m)
+        F += [None] * (3 - len(F))
+        nop = np.ascontiguousarray(node_of_point, dtype=np.int32).ravel()
+        gp = np.ascontiguousarray(bin_ptr, dtype=np.int32)
+        bp = np.ascontiguousarray(bin_points, dtype=np.int32).ravel()
+        if min(shape) >= 1 and nop.size != int(np.prod(shape, dtype=np.int64)):
+            raise ValueError("node_of_point does not match the lattice")
+        if gp.ndim != 1 or gp.size < 2 or bp.size != int(gp[-1]):
+            raise ValueError("bin_ptr / bin_points do not match")
+        self._check(self._lib.nsfem_spectrum_set(self._h, _ip(n), *[None if m is None else _dp(m) for m in F],
+                                                 _ip(nop), gp.size - 1, _ip(gp), _ip(bp)))
+        self._spectrum_bins = gp.size - 1
+
+    def spectrum_compute(self, slot=U0):
+        """[n_bins, ncomp]: the raw sums of squares of the transformed values per bin and component of the nodal field
+        in ``slot`` (velocity slots: ncomp = dim; scalar and pressure slots: 1)"""
+        slot = int(slot)
+        ncomp = self.dim if slot in (U0, U1, U2, USTAR, BODY_FORCE) else 1
+        n_bins = getattr(self, "_spectrum_bins", 0)
+        out = np.empty((max(n_bins, 1), ncomp), dtype=np.float64)      # (no plan yet: the library says so)
+        self._check(self._lib.nsfem_spectrum_compute(self._h, slot, _dp(out), n_bins * ncomp))
+        return out[:n_bins]
+
+    def spectrum_info(self):
+        """dict(transform_launches, bin_launches, calls, bytes = size of the plan)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_spectrum_info(self._h, out))
+        return dict(transform_launches=int(out[0]), bin_launches=int(out[1]), calls=int(out[2]), bytes=int(out[3]))
 
     # -- wall quantities (csrc/wall.hip) ------------------------------------------------
     def wall_components(self):

@@ -4202,6 +4202,139 @@ extern "C" int nsfem_derived_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_END(ctx)
 }
 
+// ------------------------------------------------------------------ energy spectra (spectrum.hip, fd_transform_axes)
+static void spectrum_require_supported(nsfem_ctx* c) {
+  NSFEM_REQUIRE(!c->comm, "energy spectrum: contexts with a communicator (partitioned meshes) are not supported -- "
+                          "the lattice of a rank is a strip or slab of the box");
+}
+
+// components and nodes of a nodal slot (0 components: no nodal slot)
+static int spectrum_slot_kind(const nsfem_ctx* c, int slot, int64_t* nodes) {
+  switch (slot) {
+    case NSFEM_U0: case NSFEM_U1: case NSFEM_U2: case NSFEM_USTAR: case NSFEM_BODY_FORCE:
+      *nodes = c->mesh.n_p2;
+      return c->mesh.dim;
+    case NSFEM_T0: case NSFEM_T1: case NSFEM_T2: case NSFEM_T_SOURCE:
+      *nodes = c->mesh.n_p2;
+      return 1;
+    case NSFEM_P: case NSFEM_P_OLD: case NSFEM_P2_OLD:
+      *nodes = c->mesh.n_p1;
+      return 1;
+    default:      // assembled vectors (traction, stored convection terms) are no nodal values
+      return 0;
+  }
+}
+
+// everything is validated on the host before the first upload: no kernel of the plan can index out of range
+extern "C" int nsfem_spectrum_set(nsfem_ctx* ctx, const int32_t n[3], const double* Fx, const double* Fy,
+                                  const double* Fz, const int32_t* node_of_point, int32_t n_bins,
+                                  const int32_t* bin_ptr, const int32_t* bin_points) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && n, "null argument");
+  spectrum_require_supported(ctx);
+  nsfem_ctx::Spectrum& S = ctx->spectrum;
+  if (n[0] == 0) {      // frees the plan; the counters stay
+    NSFEM_HIP(hipStreamSynchronize(ctx->stream));
+    S.release();
+    return NSFEM_OK;
+  }
+  NSFEM_REQUIRE(n[0] >= 1 && n[1] >= 1 && n[2] >= 1, "energy spectrum: non-positive lattice size");
+  NSFEM_REQUIRE(node_of_point && bin_ptr, "null argument");
+  NSFEM_REQUIRE(n_bins >= 1, "energy spectrum: n_bins < 1");
+  const int64_t np = (int64_t)n[0] * n[1] * n[2];
+  NSFEM_REQUIRE(np < INT32_MAX && n[2] <= 65535 && ((int64_t)n[2] * n[1] + 31) / 32 <= 65535,
+                "energy spectrum: lattice too large");
+  // a P1 field has fewer nodes than a P2 field: the largest index decides at nsfem_spectrum_compute which slots the
+  // plan fits; none that no field has passes here
+  int32_t max_node = -1;
+  for (int64_t i = 0; i < np; ++i) {
+    NSFEM_REQUIRE(node_of_point[i] >= 0 && node_of_point[i] < ctx->mesh.n_p2,
+                  "energy spectrum: node_of_point out of range");
+    max_node = std::max(max_node, node_of_point[i]);
+  }
+  NSFEM_REQUIRE(bin_ptr[0] == 0, "energy spectrum: bin_ptr[0] != 0");
+  for (int32_t b = 0; b < n_bins; ++b)
+    NSFEM_REQUIRE(bin_ptr[b + 1] >= bin_ptr[b], "energy spectrum: bin_ptr must not decrease");
+  const int32_t len = bin_ptr[n_bins];
+  NSFEM_REQUIRE(len == 0 || bin_points, "null argument");
+  for (int32_t k = 0; k < len; ++k)
+    NSFEM_REQUIRE(bin_points[k] >= 0 && bin_points[k] < np, "energy spectrum: bin point out of range");
+  const double* F[3] = {Fx, Fy, Fz};
+  for (int a = 0; a < 3; ++a)
+    if (F[a])
+      for (int64_t i = 0; i < (int64_t)n[a] * n[a]; ++i)
+        NSFEM_REQUIRE(std::isfinite(F[a][i]), "energy spectrum: transform matrix is not finite");
+  // chunks of at most kSpecChunk entries that never straddle a bin
+  std::vector<int32_t> chunk_ptr{0}, bin_chunk_ptr((size_t)n_bins + 1, 0);
+  for (int32_t b = 0; b < n_bins; ++b) {
+    for (int32_t k = bin_ptr[b]; k < bin_ptr[b + 1]; k += kSpecChunk)
+      chunk_ptr.push_back(std::min(k + kSpecChunk, bin_ptr[b + 1]));
+    bin_chunk_ptr[b + 1] = (int32_t)chunk_ptr.size() - 1;
+  }
+  hipStream_t s = ctx->stream;
+  NSFEM_HIP(hipStreamSynchronize(s));
+  S.release();
+  for (int a = 0; a < 3; ++a)
+    if (F[a]) S.F[a].upload(F[a], (size_t)n[a] * n[a], s);
+  S.node_of_point.upload(node_of_point, (size_t)np, s);
+  S.bin_points.upload(bin_points, (size_t)len, s);
+  S.chunk_ptr.upload(chunk_ptr.data(), chunk_ptr.size(), s);
+  S.bin_chunk_ptr.upload(bin_chunk_ptr.data(), bin_chunk_ptr.size(), s);
+  S.w0.alloc((size_t)np);
+  S.w1.alloc((size_t)np);
+  S.parts.alloc(std::max<size_t>(chunk_ptr.size() - 1, 1));
+  S.out.alloc((size_t)n_bins * 3);
+  NSFEM_HIP(hipStreamSynchronize(s));      // (the chunk lists are host vectors of this call)
+  for (int a = 0; a < 3; ++a) S.n[a] = n[a];
+  S.n_bins = n_bins;
+  S.n_chunks = (int32_t)chunk_ptr.size() - 1;
+  S.max_node = max_node;
+  S.have_plan = true;
+  API_END(ctx)
+}
+
+// per component: pack, the axis passes, the two bin launches; one copy of the result.  Reads the slot, writes the
+// plan's own arrays only
+extern "C" int nsfem_spectrum_compute(nsfem_ctx* ctx, int slot, double* out, int64_t out_len) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  spectrum_require_supported(ctx);
+  nsfem_ctx::Spectrum& S = ctx->spectrum;
+  NSFEM_REQUIRE(S.have_plan, "energy spectrum: nsfem_spectrum_set has not been called");
+  int64_t nodes = 0;
+  const int ncomp = spectrum_slot_kind(ctx, slot, &nodes);
+  NSFEM_REQUIRE(ncomp > 0, "energy spectrum: the slot holds no nodal field");
+  NSFEM_REQUIRE(ctx->state[slot].p && (int64_t)ctx->state[slot].n == nodes * ncomp,
+                "energy spectrum: the slot has no storage yet (a scalar slot that was never set or stepped)");
+  NSFEM_REQUIRE((int64_t)S.max_node < nodes, "energy spectrum: the plan names nodes the field of this slot does not have");
+  NSFEM_REQUIRE(out_len == (int64_t)S.n_bins * ncomp, "energy spectrum: wrong size of the output");
+  hipStream_t s = ctx->stream;
+  const int64_t np = (int64_t)S.n[0] * S.n[1] * S.n[2];
+  for (int c = 0; c < ncomp; ++c) {
+    launch_spec_pack(s, np, S.node_of_point.p, ctx->state[slot].p, ncomp, c, S.w0.p);
+    const double* w = fd_transform_axes(s, S.n[0], S.n[1], S.n[2], S.F[0].p, S.F[1].p, S.F[2].p, S.w0.p, S.w1.p,
+                                        &S.transform_launches);
+    launch_spec_bin(s, w, S.n_chunks, S.chunk_ptr.p, S.bin_points.p, S.parts.p, S.n_bins, S.bin_chunk_ptr.p, ncomp, c,
+                    S.out.p);
+    S.bin_launches += S.n_chunks > 0 ? 2 : 1;
+  }
+  ++S.calls;
+  NSFEM_HIP(hipMemcpyAsync(out, S.out.p, sizeof(double) * (size_t)out_len, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_spectrum_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  NSFEM_REQUIRE(ctx->spectrum.have_plan, "energy spectrum: nsfem_spectrum_set has not been called");
+  out[0] = ctx->spectrum.transform_launches;
+  out[1] = ctx->spectrum.bin_launches;
+  out[2] = ctx->spectrum.calls;
+  out[3] = ctx->spectrum.bytes();
+  API_END(ctx)
+}
+
 // ------------------------------------------------------------------ wall quantities (wall.hip)
 static void wall_require_supported(nsfem_ctx* c) {
   NSFEM_REQUIRE(!c->comm, "wall quantities: contexts with a communicator (partitioned meshes) are not supported -- "

@@ -343,4 +343,32 @@ void FastDiag3::apply(hipStream_t s, const double* r, double* z) {
   ++applications;
 }
 
+// ---- separable transform (energy spectra: spectrum.hip) -----------------------------------------------------------------
+// the forward products of FastDiag3::apply with matrices stored row = basis function: the same three kernels, nothing
+// of the solvers changes
+double* fd_transform_axes(hipStream_t s, int n0, int n1, int n2, const double* Fx, const double* Fy, const double* Fz,
+                          double* a, double* b, int64_t* launches) {
+  NSFEM_REQUIRE(n0 >= 1 && n1 >= 1 && n2 >= 1 && n2 <= 65535 && (int64_t)n2 * n1 < INT32_MAX &&
+                    (int64_t)n1 * n0 < INT32_MAX && ((int64_t)n2 * n1 + kFdBM - 1) / kFdBM <= 65535 &&
+                    (n1 + kFdBM - 1) / kFdBM <= 65535,
+                "separable transform: lattice too large");
+  double *src = a, *dst = b;
+  if (Fx) {
+    fd_gemm<false, true>(s, n2 * n1, n0, n0, src, n0, Fx, n0, dst, n0, nullptr);      // x:  ... F_x^T
+    std::swap(src, dst);
+    ++*launches;
+  }
+  if (Fy) {
+    fd_gemm_planes<false>(s, n0, n1, n2, Fy, src, dst);                               // y:  F_y per plane
+    std::swap(src, dst);
+    ++*launches;
+  }
+  if (Fz) {
+    fd_gemm<false, false>(s, n2, n1 * n0, n2, Fz, n2, src, n1 * n0, dst, n1 * n0, nullptr);   // z:  F_z
+    std::swap(src, dst);
+    ++*launches;
+  }
+  return src;
+}
+
 }  // namespace nsfem

@@ -614,6 +614,17 @@ int64_t derived_work_doubles(const MeshDev& m, int center, int ncomp);
 // when the mask does not ask for their gradients
 const double* launch_derived_fields(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* T,
                                     unsigned mask, int center, int ncomp, double* work);
+// ---- energy spectra (spectrum.hip): a nodal field packed onto its lattice, and the binned sums of squares of its
+// transformed values.  The axis passes between the two are fd_transform_axes (fastdiag.hip).
+constexpr int kSpecChunk = 2048;   // entries of the bin CSR one workgroup reduces; a chunk never straddles a bin
+// w[point] = state[node_of_point[point] * ncomp + c]
+void launch_spec_pack(hipStream_t s, int64_t n_points, const int32_t* node_of_point, const double* state, int ncomp,
+                      int c, double* w);
+// parts[k] = sum of w[bin_points[e]]^2 over the entries chunk_ptr[k] .. chunk_ptr[k + 1] (fixed tree), then
+// out[b * ncomp + c] = parts[bin_chunk_ptr[b]] + ... in ascending order (+0.0 for a bin without entries)
+void launch_spec_bin(hipStream_t s, const double* w, int32_t n_chunks, const int32_t* chunk_ptr,
+                     const int32_t* bin_points, double* parts, int32_t n_bins, const int32_t* bin_chunk_ptr, int ncomp,
+                     int c, double* out);
 // ---- wall quantities (wall.hip): NW = wall_components(dim) integrals per facet of a resident, group-sorted facet set
 // (k_wall_facets<DIM, LAW>) and their sums per group in a fixed order (k_wall_reduce<NW>); the row layout is in
 // include/nsfem.h (nsfem_wall_compute)
@@ -1073,6 +1084,13 @@ struct FastDiag3 : FastDiagBase {
  private:
   void apply_slab(hipStream_t s, const double* r, double* z);
 };
+// Separable transform of an [n2][n1][n0] array (x fastest) through the tile body of the solvers above: along every
+// axis a with a matrix, out[.., k, ..] = sum_i F_a[k][i] in[.., i, ..] (row-major [n_a][n_a], row = basis function); a
+// null matrix skips its pass.  x is one plain GEMM over [n2 n1] x n0, y the batched plane product, z one plain GEMM over
+// n2 x [n1 n0]; the passes alternate between a (the input) and b.  Returns the array that holds the result (a when
+// nothing was transformed) and adds the launches it made to *launches.
+double* fd_transform_axes(hipStream_t s, int n0, int n1, int n2, const double* Fx, const double* Fy, const double* Fz,
+                          double* a, double* b, int64_t* launches);
 // x -= sum(parts) / count on n entries (k_sum fills the slot: launch_sum)
 void launch_sum(hipStream_t s, int64_t n, const double* x, double* parts);
 void launch_gather_diag(hipStream_t s, int n, const int32_t* diag, const double* vals, double* out);   // out[i] = vals[diag[i]]
@@ -1373,6 +1391,29 @@ struct nsfem_ctx {
     nsfem::DevBuf<double> work;
     int64_t cell_launches = 0, gather_launches = 0, calls = 0;
   } derived;
+  // nsfem_spectrum_set / nsfem_spectrum_compute (spectrum.hip): the one transform-and-bin plan of the context -- the
+  // matrices of the transformed axes, the node of every lattice point, the bin CSR cut into chunks, two work arrays of
+  // one component each, the chunk partials and the result -- and the counters of nsfem_spectrum_info.  All of it is
+  // allocated by nsfem_spectrum_set; nsfem_spectrum_compute allocates nothing
+  struct Spectrum {
+    bool have_plan = false;
+    int32_t n[3] = {0, 0, 0}, n_bins = 0, n_chunks = 0, max_node = -1;
+    nsfem::DevBuf<double> F[3], w0, w1, parts, out;
+    nsfem::DevBuf<int32_t> node_of_point, bin_points, chunk_ptr, bin_chunk_ptr;
+    int64_t transform_launches = 0, bin_launches = 0, calls = 0;
+    int64_t bytes() const {
+      size_t d = w0.n + w1.n + parts.n + out.n, i = node_of_point.n + bin_points.n + chunk_ptr.n + bin_chunk_ptr.n;
+      for (const auto& f : F) d += f.n;
+      return (int64_t)(d * sizeof(double) + i * sizeof(int32_t));
+    }
+    void release() {
+      have_plan = false;
+      n[0] = n[1] = n[2] = n_bins = n_chunks = 0;
+      max_node = -1;
+      for (nsfem::DevBuf<double>* b : {&F[0], &F[1], &F[2], &w0, &w1, &parts, &out}) b->release();
+      for (nsfem::DevBuf<int32_t>* b : {&node_of_point, &bin_points, &chunk_ptr, &bin_chunk_ptr}) b->release();
+    }
+  } spectrum;
   // nsfem_wall_set_facets / nsfem_wall_compute (wall.hip): the resident facet set, sorted by group (stable), its
   // group offsets, the permutation back to the caller's order (host only), the buffers of the rows and of the group sums -- all the
   // context's own, sized by nsfem_wall_set_facets -- and the counters of nsfem_wall_info

@@ -250,6 +250,31 @@ class ProblemBase:
         self.__dict__.setdefault("_flow_statistics", []).append(stats)
         return stats
 
+    def _add_energy_spectrum(self, **kw):
+        """Register an energy spectrum of the solution on a box lattice (``energy_spectrum.EnergySpectrum``; keywords
+        ``kind``, ``axis``, ``field``, ``start_time``, ``every``): ``solve_problem`` samples the new time level after
+        the flow statistics, weighted with the step size just taken, once ``next_time >= start_time`` and on every
+        ``every``-th step.  Returns the instance (bound to the solver once it exists).  New; the reference has no
+        spectra."""
+        from energy_spectrum import EnergySpectrum
+        if getattr(self, "_energy_spectrum", None):
+            raise ValueError("an energy spectrum is already registered (the context keeps one plan)")
+        spectrum = EnergySpectrum(getattr(self, "_navier_stokes_solver", None), **kw)
+        self.__dict__.setdefault("_energy_spectrum", []).append(spectrum)
+        return spectrum
+
+    def _compute_energy_spectrum(self, kind="shell", axis=None, field="velocity"):
+        """One-shot form of ``_add_energy_spectrum``: the dict of ``EnergySpectrum.compute()`` for the current
+        solution.  The bins of the same kind, axis and field are built once and kept on the solver; the context's one
+        plan goes to whichever instance computes."""
+        from energy_spectrum import EnergySpectrum
+        solver = self._get_solver()
+        key = (kind, axis, field)
+        cache = solver.__dict__.setdefault("_spectrum_one_shot", {})     # kept on the solver: it lives as long as its context
+        if key not in cache:
+            cache[key] = EnergySpectrum.one_shot(solver, kind=kind, axis=axis, field=field)
+        return cache[key].compute()
+
     def _add_wall_quantities(self, boundary_ids, origin=None, every=1, symmetric_gradient_factor=1.0):
         """Register the wall quantities of the boundary parts ``boundary_ids`` (``wall_quantities.WallQuantities``: area,
         pressure / viscous force, torque about ``origin``, mass flux, mean temperature and heat flux per boundary id):
@@ -569,7 +594,8 @@ class InstationaryProblem(ProblemBase):
                 setattr(solver, key, value)
         self._hand_over_to_solver(solver, ("coefficients", "force", "periodic", "rotation", "bcs", "initial"))
         for registered in getattr(self, "_tracer_clouds", []) + getattr(self, "_point_probes", []) + \
-                getattr(self, "_flow_statistics", []) + getattr(self, "_wall_quantities", []):
+                getattr(self, "_flow_statistics", []) + getattr(self, "_wall_quantities", []) + \
+                getattr(self, "_energy_spectrum", []):
             registered.bind(solver)
         self._write_xdmf_file(current_time=0.0)
         print("Solving problem until time = {:0.2f}".format(self._time_stepping.end_time))
@@ -595,6 +621,8 @@ class InstationaryProblem(ProblemBase):
                 wall.record_step(ts.next_time)
             for stats in getattr(self, "_flow_statistics", ()):
                 stats.sample_step(ts.next_time, ts.get_next_step_size())
+            for spectrum in getattr(self, "_energy_spectrum", ()):
+                spectrum.sample_step(ts.next_time, ts.get_next_step_size())
             if self._postprocessing_frequency > 0 and \
                     ts.step_number % self._postprocessing_frequency == 0:
                 self.postprocess_solution()
