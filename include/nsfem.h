@@ -1000,6 +1000,14 @@ int nsfem_jacobian_info(nsfem_ctx* ctx, int64_t out[4]);
  * out[3] = projection checks whose launch also stored p = p_old + z.  Each stays 0 where its path does not apply
  * (partitioned contexts, no exact stencil dictionaries, 3D, optional right-hand-side terms, other solvers). */
 int nsfem_step_frame_info(nsfem_ctx* ctx, int64_t out[4]);
+/* Residual launches so far of nsfem_step_ipcs that carried the frame of its Newton iteration (NSFEM_NEWTON_FUSED,
+ * default on, read when the context is created; 0 keeps the update u* -= dx, the Dirichlet rows of the residual and
+ * its norm as launches of their own): out[0] = launches of k_jac_lattice that also set the Dirichlet rows and left
+ * the sum of squares per tile, out[1] = those among them that first applied the pending update.  Both stay 0 where
+ * the path does not apply (partitioned contexts, no exact stencil dictionary, 3D, NSFEM_JAC_LATTICE=0, NSFEM_GRAPHS=1,
+ * every caller but nsfem_step_ipcs).  The update is written to a second buffer that then takes the place of the
+ * NSFEM_USTAR slot: a pointer from nsfem_state_devptr(NSFEM_USTAR) is good until the next step call only. */
+int nsfem_newton_frame_info(nsfem_ctx* ctx, int64_t out[2]);
 /* Test hook: *bad_cells = the number of cells whose basis gradients and weights, evaluated per cell as the element
  * kernels do, differ in any bit from the tables k_jac_lattice reads on a uniform lattice; -1 when there are none. */
 int nsfem_jacobian_table_check(nsfem_ctx* ctx, int64_t* bad_cells);

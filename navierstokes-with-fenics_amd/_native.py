@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_default_step_opts", "nsfem_step_ipcs", "nsfem_step_bdf", "nsfem_advance",
     "nsfem_shift_mean_pressure", "nsfem_time_spmv", "nsfem_synchronize", "nsfem_mass_solve",
     "nsfem_mg_add_level", "nsfem_mg_finalize", "nsfem_mg_set_global_coarse", "nsfem_mg_set_global_coarse_constrained",
-    "nsfem_mg_set_schur_operator", "nsfem_mg_set_schur_mode", "nsfem_set_halo_lists", "nsfem_smoother_info", "nsfem_mg_set_global_index", "nsfem_comm_allreduce", "nsfem_mg_add_global_level", "nsfem_cfl_number", "nsfem_set_angular_velocity", "nsfem_set_angular_velocity_3d", "nsfem_profile_smoother", "nsfem_profile_smoother_detail", "nsfem_profile_convection", "nsfem_jacobian_info", "nsfem_step_frame_info", "nsfem_jacobian_table_check", "nsfem_set_preconditioner_shift", "nsfem_poisson_solve", "nsfem_p2_mass_bounds", "nsfem_mg_set_truncation", "nsfem_comm_stats", "nsfem_mg_set_halo_mode", "nsfem_set_overlap", "nsfem_comm_overlapped", "nsfem_boundary_force",
+    "nsfem_mg_set_schur_operator", "nsfem_mg_set_schur_mode", "nsfem_set_halo_lists", "nsfem_smoother_info", "nsfem_mg_set_global_index", "nsfem_comm_allreduce", "nsfem_mg_add_global_level", "nsfem_cfl_number", "nsfem_set_angular_velocity", "nsfem_set_angular_velocity_3d", "nsfem_profile_smoother", "nsfem_profile_smoother_detail", "nsfem_profile_convection", "nsfem_jacobian_info", "nsfem_step_frame_info", "nsfem_newton_frame_info", "nsfem_jacobian_table_check", "nsfem_set_preconditioner_shift", "nsfem_poisson_solve", "nsfem_p2_mass_bounds", "nsfem_mg_set_truncation", "nsfem_comm_stats", "nsfem_mg_set_halo_mode", "nsfem_set_overlap", "nsfem_comm_overlapped", "nsfem_boundary_force",
     "nsfem_set_partition", "nsfem_comm_unique_id", "nsfem_comm_attach_rccl",
     "nsfem_comm_local_create", "nsfem_comm_local_destroy", "nsfem_comm_attach_local", "nsfem_comm_attach_shm",
     "nsfem_mg_apply", "nsfem_mg_info", "nsfem_monolithic_apply", "nsfem_poisson_set_fast_diag", "nsfem_poisson_set_fast_diag_rows",
@@ -300,6 +300,7 @@ def load_library(path=None):
         "nsfem_smoother_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_jacobian_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_step_frame_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_newton_frame_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_jacobian_table_check": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_mg_apply": (C.c_int, [vp, C.c_int, pd, pd]),
         "nsfem_mg_info": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int64)]),
@@ -1440,6 +1441,13 @@ class NsfemContext:
         self._check(self._lib.nsfem_step_frame_info(self._h, out))
         return dict(pair_begin=int(out[0]), pair_correction=int(out[1]), correction_finish=int(out[2]),
                     projection_sum=int(out[3]))
+
+    def newton_frame_info(self):
+        """residual launches so far with the frame of the Newton iteration (NSFEM_NEWTON_FUSED): dict(residuals,
+        updates)"""
+        out = (C.c_int64 * 2)()
+        self._check(self._lib.nsfem_newton_frame_info(self._h, out))
+        return dict(residuals=int(out[0]), updates=int(out[1]))
 
     def jacobian_table_check(self):
         """cells whose per-cell basis gradients / weights differ from k_jac_lattice's tables in any bit (-1: no tables)"""

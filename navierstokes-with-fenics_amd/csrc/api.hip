@@ -117,6 +117,7 @@ extern "C" int nsfem_create(const nsfem_mesh_desc* m, int device, nsfem_ctx** ou
   fresh = new nsfem_ctx();
   fresh->device = device;
   fresh->step_fused = step_fused_enabled();
+  fresh->newton_fused = newton_fused_enabled();
   NSFEM_HIP(hipStreamCreate(&fresh->stream));
   hipStream_t s = fresh->stream;
   const int nc = m->n_cells;
@@ -536,6 +537,13 @@ extern "C" int nsfem_set_dirichlet(nsfem_ctx* ctx, int field, int32_t n, const i
   if (changed) ctx->graph_epoch++;  // the device dof arrays were re-allocated (values-only
                                     // updates keep the pointers: captured graphs stay valid)
   if (field == NSFEM_VELOCITY) {
+    // the values as a dense vector for the residual launch that sets its own Dirichlet rows (one rank, 2D), refreshed
+    // with every call
+    if (ctx->newton_fused && ctx->mesh.dim == 2 && !ctx->ghost_v.p) {
+      if (!ctx->bc_v_dense.p) ctx->bc_v_dense.alloc((size_t)size);
+      ctx->bc_v_dense.zero(s);
+      launch_set_values(s, (int)d.size(), dd.p, dv.p, ctx->bc_v_dense.p);
+    }
     ctx->nbc_v = (int)d.size();
     ctx->imex_lattice_agreed = -1;
     if (changed) {
@@ -919,9 +927,39 @@ static void momentum_residual_raw(nsfem_ctx* c, const double* u, double* out) {
   if (g != 0.0) coriolis_apply(c, g, u, out);
 }
 
-static double momentum_residual(nsfem_ctx* c) {
+// The frame of the Newton iteration inside the residual launch (k_jac_lattice<FORM, 7 / 8>): one rank, the one-launch
+// lattice path on a dictionary that equals the matrix, a velocity mask, the switch on
+static bool newton_frame_available(nsfem_ctx* c) {
+  return c->newton_fused && !c->distributed() && c->mask_v.p && !c->ghost_v.p && c->bc_v_dense.p &&
+         jacobian_path(c) == 2 && residual_frame_lattice_available(c->mesh, c->L);
+}
+// frame: the caller is the Newton loop of nsfem_step_ipcs -- Dirichlet rows and the sum of squares come out of the
+// residual launch, and so does a pending update u* -= dx (momentum_solve_update left it)
+static double momentum_residual(nsfem_ctx* c, bool frame = false) {
   hipStream_t s = c->stream;
   const int64_t nv = nvel(c);
+  if (frame && newton_frame_available(c)) {
+    const bool upd = c->newton_update_pending;
+    const int ntiles = lattice_tile_count(c->mesh);
+    if (!c->tile_parts.p) c->tile_parts.alloc((size_t)ntiles);
+    if (upd && !c->ustar_alt.p) c->ustar_alt.alloc((size_t)nv);
+    if (launch_residual_frame_lattice(s, c->mesh, c->L, c->state[NSFEM_USTAR].p, upd ? c->dx_v.p : nullptr,
+                                      upd ? c->ustar_alt.p : nullptr, c->gconst.p, cc_of(c), c->conv_form, c->mask_v.p,
+                                      c->bc_v_dense.p, c->rhs_v.p, c->tile_parts.p)) {
+      ++c->jac_lattice_launches;
+      ++c->newton_frame_launches[0];
+      if (upd) {
+        std::swap(c->state[NSFEM_USTAR].p, c->ustar_alt.p);
+        c->newton_update_pending = false;
+        ++c->newton_frame_launches[1];
+      }
+      return std::sqrt(host_sum_run(s, c->kw, c->tile_parts.p, ntiles));
+    }
+  }
+  if (c->newton_update_pending) {              // (the launch was refused after all: the update as a launch of its own)
+    launch_axpby(s, nv, 1.0, c->state[NSFEM_USTAR].p, -1.0, c->dx_v.p, c->state[NSFEM_USTAR].p);
+    c->newton_update_pending = false;
+  }
   double* u = c->state[NSFEM_USTAR].p;
   momentum_residual_raw(c, u, c->rhs_v.p);
   if (!c->distributed() && c->mask_v.p) {      // Dirichlet rows and the norm in one launch (mask != 0 <=> bc dof)
@@ -1078,8 +1116,9 @@ static bool use_matrix_free(const nsfem_ctx* c, const nsfem_step_opts* o) {
 // without reading its start-up sums back
 // rhs_dead: the caller recomputes rhs_v before anything reads it again (the Newton loops: momentum_residual follows);
 // the solver may then use it as scratch.  Not so behind nsfem_solve: nsfem_get_rhs / nsfem_residual_norm may follow.
+// defer_update: u* -= dx is left to the residual launch the caller runs next (momentum_residual with the frame)
 static int momentum_solve_update(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem_solve_info& info,
-                                 double known_rhs_norm = -1.0, bool rhs_dead = false) {
+                                 double known_rhs_norm = -1.0, bool rhs_dead = false, bool defer_update = false) {
   hipStream_t s = c->stream;
   LinOp op;
   op.A = &c->J;
@@ -1106,6 +1145,10 @@ static int momentum_solve_update(nsfem_ctx* c, const nsfem_krylov_opts& o, nsfem
   op.b_scratch = rhs_dead;
   int rc = bicgstab(s, c->kw, op, c->rhs_v.p, c->dx_v.p, o, info);
   if (rc != NSFEM_OK) return rc;
+  if (defer_update) {
+    c->newton_update_pending = true;
+    return NSFEM_OK;
+  }
   double* u = c->state[NSFEM_USTAR].p;
   launch_axpby(s, nvel(c), 1.0, u, -1.0, c->dx_v.p, u);
   return NSFEM_OK;
@@ -2325,10 +2368,11 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
   // ---- diffusion step: Newton
   momentum_begin_step(ctx);
-  newton_solve(ctx, opts, inf, "diffusion step", false, [&] { return momentum_residual(ctx); },
+  // (the residual evaluation that follows every solve applies the update the solve left pending)
+  newton_solve(ctx, opts, inf, "diffusion step", false, [&] { return momentum_residual(ctx, true); },
                [&](double r, const nsfem_krylov_opts& k, nsfem_solve_info& si) {
                  if (!ctx->mf_active) momentum_jacobian(ctx);
-                 return momentum_solve_update(ctx, k, si, r, true);
+                 return momentum_solve_update(ctx, k, si, r, true, newton_frame_available(ctx));
                });
   projection_step(ctx, opts, inf);
   correction_step(ctx, opts, inf);
@@ -5017,6 +5061,15 @@ extern "C" int nsfem_step_frame_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out, "null argument");
   for (int i = 0; i < 4; ++i) out[i] = ctx->step_frame_launches[i];
+  API_END(ctx)
+}
+
+// residual launches so far that carried the frame of the Newton iteration (NSFEM_NEWTON_FUSED): out = {launches with
+// the Dirichlet rows and the sum of squares, those among them that also applied the update u* -= dx}
+extern "C" int nsfem_newton_frame_info(nsfem_ctx* ctx, int64_t out[2]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  for (int i = 0; i < 2; ++i) out[i] = ctx->newton_frame_launches[i];
   API_END(ctx)
 }
 

@@ -1152,6 +1152,9 @@ __device__ __forceinline__ double imex_rhs_value(double t, double n1, double n2,
   const double e = fma(b0, n1, old);
   return -(t + e);
 }
+// u* - dx of the Newton update: the expression of the vector launch it replaces, k_axpby(1, u, -1, dx) =
+// a x + b y (contracted or not, the products with 1 and -1 are exact: one rounding, that of the difference)
+__device__ __forceinline__ double newton_update_value(double u, double dx) { return 1.0 * u + (-1.0 * dx); }
 __global__ __launch_bounds__(256) void k_imex_combine(int64_t n, const double* __restrict__ t,
                                                       const double* __restrict__ n1, const double* __restrict__ n2,
                                                       double b0, double b1, double* __restrict__ rhs) {
@@ -1247,12 +1250,17 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   // set by the caller afterwards); g joins the node's sum after the L product and before the element vectors,
   // the order of the launches it replaces (product, axpby, k_conv_cell, k_res_gather).
   // ugeo: V 0, 1 the two types' geometry [2][5] (uniform lattices; null: load_geo per cell), V 2 the gradient tables
-  constexpr bool IMX = LIN >= 3;
-  constexpr bool GH = LIN == 4 || LIN == 6;                         // ghost rows of a strip -> 0
-  constexpr bool ROT = LIN >= 5;                                    // Coriolis term in the element vector
-  constexpr bool RES = LIN == 0 || IMX;
-  constexpr bool TWO = LIN != 0;                                    // a second staged vector (x, or u2)
-  constexpr int CLIN = IMX ? 0 : LIN;                               // mode of the element kernel
+  // LIN = 7, 8 (variants 1, 2): LIN 0 with the frame of the Newton iteration (see launch_residual_frame_lattice)
+  constexpr bool ROWS = LIN == 7 || LIN == 8;                       // Dirichlet rows u - g_D and the tile's sum of squares
+  constexpr bool UPD = LIN == 8;                                    // u = u_old - x staged, and stored to ix.unew
+  constexpr int BL = ROWS ? 0 : LIN;                                // the mode underneath
+  constexpr bool IMX = BL >= 3;
+  constexpr bool GH = BL == 4 || BL == 6;                           // ghost rows of a strip -> 0
+  constexpr bool ROT = BL >= 5;                                     // Coriolis term in the element vector
+  constexpr bool RES = BL == 0 || IMX;
+  constexpr bool TWO = BL != 0;                                     // a second staged vector (x, or u2)
+  constexpr int CLIN = IMX ? 0 : BL;                                // mode of the element kernel
+  static_assert(!ROWS || V != 0, "the Newton frame is built for the gather variants only");
   static_assert(!IMX || V == 2, "the right-hand-side mode is built for the table variant only");
   extern __shared__ __attribute__((aligned(16))) double sh_jl[];
   constexpr int NT = 2 * SX * SY;                                   // threads
@@ -1292,7 +1300,12 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     if (t < NN && gi >= 0 && gi < a.W && gj >= 0 && gj < a.H && !NSFEM_KO(a.dbg & 8)) {
       const size_t g = (size_t)gj * a.W + gi;
       uv[r] = u2[g];
-      if (TWO) xv[r] = x2[g];
+      if (TWO || UPD) xv[r] = x2[g];
+    }
+    if constexpr (UPD) {
+      // the Newton update u_old - dx, entry by entry as the launch it replaces forms it (outside the lattice: 0 - 0)
+      uv[r].x = newton_update_value(uv[r].x, xv[r].x);
+      uv[r].y = newton_update_value(uv[r].y, xv[r].y);
     }
   }
   // (this thread's cell, its two owned nodes)
@@ -1325,6 +1338,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
   size_t onode[NOWN];
   double2 og[RES ? NOWN : 1];
   double2 on2[IMX ? NOWN : 1];
+  double2 ogd[ROWS ? NOWN : 1];
 #pragma unroll
   for (int r = 0; r < NOWN; ++r) {
     const int o = tid + r * NT;
@@ -1340,7 +1354,13 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       oent[r] = sid8[onode[r]];
       if (RES) og[r] = reinterpret_cast<const double2*>(gadd)[onode[r]];
       if (IMX) on2[r] = ix.n2 ? reinterpret_cast<const double2*>(ix.n2)[onode[r]] : make_double2(0.0, 0.0);
-      if (!RES || GH) omask[r] = reinterpret_cast<const uint16_t*>(mask)[onode[r]];
+      if (!RES || GH || ROWS) omask[r] = reinterpret_cast<const uint16_t*>(mask)[onode[r]];
+      if constexpr (ROWS) {
+        // Dirichlet values: fetched by the lanes of flagged components only (the dense vector of nsfem_set_dirichlet)
+        ogd[r] = make_double2(0.0, 0.0);
+        if (omask[r] & 0x00ff) ogd[r].x = ix.gd[2 * onode[r]];
+        if (omask[r] & 0xff00) ogd[r].y = ix.gd[2 * onode[r] + 1];
+      }
     }
   }
   for (int t = tid; t < a.n_st * a.lp; t += NT) {
@@ -1401,6 +1421,14 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
       ax += bx; ay += by;
     }
     if (RES) { ax += og[r].x; ay += og[r].y; }
+    if constexpr (ROWS) {
+      // the node's new u* while su is staged: written out (never in place: the neighbouring tiles read the old halo),
+      // and on a flagged component the row's value u - g_D takes the place of the partial sum (the gather skips it)
+      const double2 uo = su[base];
+      if (UPD) reinterpret_cast<double2*>(ix.unew)[onode[r]] = uo;
+      if (omask[r] & 0x00ff) ax = uo.x - ogd[r].x;
+      if (omask[r] & 0xff00) ay = uo.y - ogd[r].y;
+    }
     if (V != 0 && !RES) {
       // V 1, 2: the identity row's value now, while sx is staged (flag 1: identity row; flag 2: ghost row of a
       // partitioned strip -> 0); the node sum does not enter it
@@ -1454,6 +1482,7 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
     for (int k = 0; k < 6; ++k) se[(ct * 6 + k) * NSQ + syl * SX + sxl] = cell ? make_double2(rx[k], ry[k]) : nz;
     for (int t = tid; t < NSQ; t += NT) se[12 * NSQ + t] = nz;
     __syncthreads();
+    double ssq = 0.0;                                              // (ROWS) squares of what this thread stores
 #pragma unroll
     for (int r = 0; r < NOWN; ++r) {
       if (obase[r] < 0) continue;
@@ -1486,11 +1515,30 @@ void k_jac_lattice(JacLatArgs a, const double* __restrict__ vx, const double* __
           if (omask[r] & 0x0002) v = make_double2(0.0, 0.0);
         }
       }
-      if (!RES) {
+      if (!RES || ROWS) {
         if (omask[r] & 0x00ff) v.x = a0.x;
         if (omask[r] & 0xff00) v.y = a0.y;
       }
       if (!NSFEM_KO(a.dbg & 32) || v.x == 1.2345) y2[onode[r]] = v;
+      if constexpr (ROWS) {
+        const double qx = v.x, qy = v.y;
+        ssq = fma(qx, qx, ssq);
+        ssq = fma(qy, qy, ssq);
+      }
+    }
+    if constexpr (ROWS) {
+      // the tile's sum of squares in a fixed order: lanes of a wave (shuffle tree), then the waves in ascending order.
+      // The wave sums go to the first entries of sa: the halo lines of the tile, which no phase reads or writes
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) ssq += __shfl_down(ssq, off, 64);
+      if ((tid & 63) == 0) sh_jl[tid >> 6] = ssq;
+      __syncthreads();
+      if (tid == 0) {
+        double t = sh_jl[0];
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) t += sh_jl[w];
+        ix.tparts[tlin] = t;
+      }
     }
     return;
   }
@@ -1702,7 +1750,8 @@ int64_t jacobian_lattice_bytes(const MeshDev& m) {
 }
 
 // lin: 0 residual (x, mask unused; gadd = g), 1 Newton action, 2 Picard action, 3 IMEX right-hand side (ix; L = L1),
-// 4 the same on a partitioned strip (mask: ghost rows -> 0), 5 / 6: 3 / 4 with the Coriolis term (ix.gam)
+// 4 the same on a partitioned strip (mask: ghost rows -> 0), 5 / 6: 3 / 4 with the Coriolis term (ix.gam), 7 / 8: the
+// residual with its Dirichlet rows and sum of squares (ix.gd, ix.tparts), 8 at u - x with the difference stored (ix.unew)
 // phase 0: every tile; 1: the tile rows that read no lattice line below `safe_lo` or from `safe_hi` on (the interior of
 // a partitioned strip, launched under the halo exchange); 2: the other tile rows.  jacobian_lattice_split tells
 // whether phases 1 / 2 exist for the given ghost lines
@@ -1776,8 +1825,10 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
     for (int h = 0; h < 3; ++h) a.gl[c][h] = packed[2 * h] | (packed[2 * h + 1] << 16);
   }
   const int var = jacobian_lattice_variant(m);
-  if (lin >= 3 && var != 2) return false;           // (the right-hand-side mode: uniform lattices, gradient tables)
-  const size_t lds = jac_lattice_lds(d, lin >= 3);
+  const bool imx = lin >= 3 && lin <= 6;
+  if (imx && var != 2) return false;                // (the right-hand-side mode: uniform lattices, gradient tables)
+  if (lin >= 7 && var == 0) return false;           // (the Newton frame: the gather variants)
+  const size_t lds = jac_lattice_lds(d, imx);
   const int grid = ((a.ntiles + 7) / 8) * 8;
 #define NSFEM_JL_V(F, LIN, SX, SY, V)                                                                       \
   do {                                                                                                      \
@@ -1813,6 +1864,13 @@ static bool launch_lattice_cells(hipStream_t s, const MeshDev& m, const BlockMat
 #define NSFEM_JL_T(F, LIN, SX, SY) NSFEM_JL_V(F, LIN, SX, SY, 2)
   if (lin == 3) { NSFEM_JL_F(3) } else if (lin == 4) { NSFEM_JL_F(4) }
   else if (lin == 5) { NSFEM_JL_F(5) } else if (lin == 6) { NSFEM_JL_F(6) }
+#undef NSFEM_JL_T
+#define NSFEM_JL_T(F, LIN, SX, SY)                                                                          \
+  do {                                                                                                      \
+    if (var == 2) NSFEM_JL_V(F, LIN, SX, SY, 2);                                                            \
+    else NSFEM_JL_V(F, LIN, SX, SY, 1);                                                                     \
+  } while (0)
+  if (lin == 7) { NSFEM_JL_F(7) } else if (lin == 8) { NSFEM_JL_F(8) }
 #undef NSFEM_JL_F
 #undef NSFEM_JL_T
 #undef NSFEM_JL_V
@@ -1833,6 +1891,34 @@ bool launch_residual_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L,
                              double cc, int form, double* y) {
   if (!L.dict || !L.dict->exact || !g) return false;
   return launch_lattice_cells(s, m, L, u, u, cc, form, 0, nullptr, g, y);
+}
+
+// The residual launch with the frame of the Newton iteration around it (k_jac_lattice<FORM, 7 / 8>, variants 1, 2):
+//   dx set    the pending update first: u_new = u - dx formed while staging, stored to `unew` by the thread of each
+//             owned node (a second buffer: the neighbouring tiles still read the old halo), the residual taken at u_new;
+//   rows      on the components flagged in `mask` the row's value u_new - g_D (`gdense`: the Dirichlet values as a dense
+//             velocity vector) is stored in place of the node sum: what k_bc_residual_norm writes afterwards;
+//   norm      every workgroup leaves the sum of the squares of what it stored in tparts[0 .. lattice_tile_count): one
+//             entry per tile, written by every launch, summed by launch-order-independent code (host_sum_run).
+// y and every entry of u_new carry the bits of the launches replaced; the sum of squares is ordered differently
+int lattice_tile_count(const MeshDev& m) {
+  const CellLattice& cl = m.cl;
+  if (!cl.ok) return 0;
+  const int ox = 2 * (kJlSx - 1), oy = 2 * (kJlSy - 1);
+  return ((cl.W + ox - 1) / ox) * ((cl.H + oy - 1) / oy);
+}
+bool residual_frame_lattice_available(const MeshDev& m, const BlockMat& L) {
+  return L.dict && L.dict->exact && jacobian_lattice_available(m, L) && jacobian_lattice_variant(m) != 0;
+}
+bool launch_residual_frame_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L, const double* u, const double* dx,
+                                   double* unew, const double* g, double cc, int form, const uint8_t* mask,
+                                   const double* gdense, double* y, double* tparts) {
+  if (!residual_frame_lattice_available(m, L) || !g || !mask || !gdense || !tparts || (dx && !unew)) return false;
+  ImexLatArgs ix;
+  ix.gd = gdense;
+  ix.unew = unew;
+  ix.tparts = tparts;
+  return launch_lattice_cells(s, m, L, u, dx ? dx : u, cc, form, dx ? 8 : 7, mask, g, y, 0, 0, 0, &ix);
 }
 
 // rhs = -((L1 u1 + L2 u2 + g) + (b0 n1 + b1 n2)) with n1 = c_c conv(u1) stored: the right-hand side of the IMEX

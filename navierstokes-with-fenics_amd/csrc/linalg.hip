@@ -1593,6 +1593,12 @@ static bool g_bicg_fused = true;     // NSFEM_BICG_FUSED=0: BiCGStab with the st
 // per vector pass, as before the fused kernels (A/B, tests); a context keeps the value it was created under
 static bool g_step_fused = true;
 bool step_fused_enabled() { return g_step_fused; }
+// NSFEM_NEWTON_FUSED=0: the Newton iteration of the IPCS step with its update, the Dirichlet rows of the residual and
+// the residual norm as launches of their own, as before launch_residual_frame_lattice (A/B, tests); a context keeps the
+// value it was created under.  Off as well under NSFEM_GRAPHS=1: a captured Krylov body bakes in the pointer behind
+// the u* slot, which the fused update exchanges
+static bool g_newton_fused = true;
+bool newton_fused_enabled() { return g_newton_fused; }
 void refresh_env_switches() {
   const char* e = std::getenv("NSFEM_LATTICE");
   g_lattice_on = e ? std::atoi(e) != 0 : true;
@@ -1600,6 +1606,10 @@ void refresh_env_switches() {
   g_bicg_fused = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_STEP_FUSED");
   g_step_fused = e ? std::atoi(e) != 0 : true;
+  e = std::getenv("NSFEM_NEWTON_FUSED");
+  g_newton_fused = e ? std::atoi(e) != 0 : true;
+  e = std::getenv("NSFEM_GRAPHS");
+  if (e && std::atoi(e) != 0) g_newton_fused = false;
   e = std::getenv("NSFEM_LATTICE_KINDS");          // 0: every launch runs the runtime-flag kernel (A/B, tests)
   g_lattice_kinds_on = e ? std::atoi(e) != 0 : true;
   e = std::getenv("NSFEM_LATTICE_TRANSFERS");
@@ -2776,7 +2786,10 @@ __global__ __launch_bounds__(256) void k_bc_residual_norm(int64_t n, double* __r
   __shared__ double sh[4];
   double v = 0.0;
   GRID_STRIDE(i, n) {
-    const double bi = mask[i] ? 0.0 : b[i];
+    // (b[i] is loaded whatever the flag says and selected afterwards: one memory round trip per trip of the loop
+    // instead of the load of b behind the load of the flag; the same values enter the sum in the same order)
+    const double bv = b[i];
+    const double bi = mask[i] ? 0.0 : bv;
     v += bi * bi;
   }
   GRID_STRIDE(j, nbc) {
@@ -3113,8 +3126,41 @@ __global__ __launch_bounds__(256) void k_publish(const double* __restrict__ part
   }
 }
 
+// the sum of a run of n partial sums (one per tile of a lattice launch: more than a slot holds) -> out->v[0], then the
+// sequence number.  Fixed order: thread t adds the entries t, t + 256, ... in ascending order, then block_sum
+__global__ __launch_bounds__(256) void k_publish_run(const double* __restrict__ parts, int n,
+                                                     KrylovWork::HostResult* __restrict__ out, uint64_t seq) {
+  __shared__ double sh[4];
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) v += parts[i];
+  v = block_sum(v, sh);
+  if (threadIdx.x == 0) {
+    out->v[0] = v;
+    __threadfence_system();
+    __hip_atomic_store(&out->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // the host side: launch, spin on the sequence number (the stream is in order: everything queued before has finished
 // when it arrives); a stream error ends the wait
+static void wait_for_result(hipStream_t s, KrylovWork& w, uint64_t seq) {
+  volatile uint64_t* flag = &w.h_res->seq;
+  for (uint64_t spins = 0;; ++spins) {
+    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) break;
+    if ((spins & 0xffff) == 0xffff) {
+      const hipError_t e = hipStreamQuery(s);
+      if (e != hipSuccess && e != hipErrorNotReady)
+        throw Error(NSFEM_ERR_HIP, std::string("stream error while waiting for a reduction: ") + hipGetErrorString(e));
+      if (e == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
+        // (the stream drained but the flag store is not visible yet: one more look after a full synchronisation)
+        NSFEM_HIP(hipStreamSynchronize(s));
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
+          throw Error(NSFEM_ERR_HIP, "reduction result never reached the host");
+        break;
+      }
+    }
+  }
+}
 static void publish_and_wait(hipStream_t s, KrylovWork& w, int n, const int slot[4], double out[4]) {
   if (!w.h_res) {
     int lo = slot[0], hi = slot[0];
@@ -3133,23 +3179,25 @@ static void publish_and_wait(hipStream_t s, KrylovWork& w, int n, const int slot
   hipLaunchKernelGGL(k_publish, dim3(1), dim3(kBlock), 0, s, (const double*)w.parts.p, n, slot[0], slot[1], slot[2],
                      slot[3], w.h_res, seq);
   NSFEM_HIP(hipGetLastError());
-  volatile uint64_t* flag = &w.h_res->seq;
-  for (uint64_t spins = 0;; ++spins) {
-    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) break;
-    if ((spins & 0xffff) == 0xffff) {
-      const hipError_t e = hipStreamQuery(s);
-      if (e != hipSuccess && e != hipErrorNotReady)
-        throw Error(NSFEM_ERR_HIP, std::string("stream error while waiting for a reduction: ") + hipGetErrorString(e));
-      if (e == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-        // (the stream drained but the flag store is not visible yet: one more look after a full synchronisation)
-        NSFEM_HIP(hipStreamSynchronize(s));
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq)
-          throw Error(NSFEM_ERR_HIP, "reduction result never reached the host");
-        break;
-      }
-    }
-  }
+  wait_for_result(s, w, seq);
   for (int k = 0; k < n; ++k) out[k] = w.h_res->v[k];
+}
+
+// sum of the n entries of `run` (device memory, e.g. the per-tile sums of launch_residual_frame_lattice) on the host
+double host_sum_run(hipStream_t s, KrylovWork& w, const double* run, int n) {
+  if (!w.h_res) {                  // (no coherent host memory: copy the run, add it up in ascending order)
+    std::vector<double> h((size_t)n);
+    NSFEM_HIP(hipMemcpyAsync(h.data(), run, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+    NSFEM_HIP(hipStreamSynchronize(s));
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) acc += h[(size_t)i];
+    return acc;
+  }
+  const uint64_t seq = ++w.seq_no;
+  hipLaunchKernelGGL(k_publish_run, dim3(1), dim3(kBlock), 0, s, run, n, w.h_res, seq);
+  NSFEM_HIP(hipGetLastError());
+  wait_for_result(s, w, seq);
+  return w.h_res->v[0];
 }
 
 double host_sum_parts(hipStream_t s, KrylovWork& w, int which) {

@@ -280,6 +280,7 @@ void launch_spmv_pair_accum(hipStream_t s, const BlockMat& M, const BlockMat& B,
                             const double* z, double* y);                          // y = M x + c2 B z
 void launch_spmv_pair_correction(hipStream_t s, const BlockMat& M, const BlockMat& B, const double* x, double a,
                                  const double* z, const double* z2, const uint8_t* mask, double* rhs, double* r0);
+bool newton_fused_enabled();            // NSFEM_NEWTON_FUSED (and not NSFEM_GRAPHS) as last read by refresh_env_switches
 bool step_fused_enabled();              // NSFEM_STEP_FUSED as last read by refresh_env_switches
 
 // multi-step lattice smoother (2D lexicographic lattices with a stencil dictionary; linalg.hip)
@@ -439,7 +440,18 @@ struct ImexLatArgs {
   double* n1 = nullptr;            // c_c conv(u1), written
   double b0 = 1.0, b1 = 0.0;
   double gam = 0.0;                // 2 c_cor omega(t^n): read by the rotating modes (LIN 5, 6) only
+  // the frame of the Newton iteration (LIN 7, 8; launch_residual_frame_lattice): read by those modes only
+  const double* gd = nullptr;      // Dirichlet values as a dense velocity vector
+  double* unew = nullptr;          // LIN 8: u - x, written
+  double* tparts = nullptr;        // one sum of squares per tile, written
 };
+// The momentum residual with its Dirichlet rows, the sum of its squares per tile and, with dx set, the Newton update
+// u - dx (stored to unew) in ONE launch; false = not available, nothing launched.  Comment at the definition
+int lattice_tile_count(const MeshDev& m);
+bool residual_frame_lattice_available(const MeshDev& m, const BlockMat& L);
+bool launch_residual_frame_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L, const double* u, const double* dx,
+                                   double* unew, const double* g, double cc, int form, const uint8_t* mask,
+                                   const double* gdense, double* y, double* tparts);
 bool launch_imex_rhs_lattice(hipStream_t s, const MeshDev& m, const BlockMat& L1, const BlockMat& L2, const double* u1,
                              const double* u2, const double* g, double cc, int form, double b0, double b1,
                              const double* n2, double* n1, double* rhs, const uint8_t* ghostmask = nullptr,
@@ -1114,6 +1126,7 @@ int pcg(hipStream_t s, KrylovWork& w, const LinOp& op, const double* b, double* 
         const nsfem_krylov_opts& o, nsfem_solve_info& info, bool project_mean);
 
 double host_sum_parts(hipStream_t s, KrylovWork& w, int which);   // sync + sum
+double host_sum_run(hipStream_t s, KrylovWork& w, const double* run, int n);   // sum of n device entries, fixed order
 void host_sum_parts2(hipStream_t s, KrylovWork& w, int a, int b, double& ra, double& rb);   // two slots, one round trip
 void host_sum_parts3(hipStream_t s, KrylovWork& w, int a, int b, int c, double& ra, double& rb, double& rc);
 
@@ -1288,6 +1301,15 @@ struct nsfem_ctx {
   bool cor_finish_pending = false;
   // launches so far: pair kernel begin step / correction, k_correction_finish, fused projection epilogue
   int64_t step_frame_launches[4] = {0, 0, 0, 0};
+  // frame of the Newton iteration of nsfem_step_ipcs in the residual launch (NSFEM_NEWTON_FUSED at creation; see
+  // launch_residual_frame_lattice).  newton_update_pending: the solve left u* -= dx to the residual launch that follows;
+  // that launch writes the new u* to ustar_alt and the two buffers are exchanged behind state[NSFEM_USTAR]
+  bool newton_fused = true;
+  bool newton_update_pending = false;
+  nsfem::DevBuf<double> bc_v_dense;            // the velocity Dirichlet values as a dense vector (0 elsewhere)
+  nsfem::DevBuf<double> ustar_alt;             // second u* buffer
+  nsfem::DevBuf<double> tile_parts;            // one sum of squares per tile of the residual launch
+  int64_t newton_frame_launches[2] = {0, 0};   // residual launches with the frame, those among them with the update
   nsfem::FastDiag fd_p{&comm};                 // direct projection-step solver on tensor-product lattices
   nsfem::FastDiag3 fd3_p{&comm};               // the same on 3D box lattices (direct or CG preconditioner)
   // the factors precond = 3 uses: the 3D ones if set, else the 2D ones, else none (a setter releases the other object)
