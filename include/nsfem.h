@@ -489,6 +489,32 @@ int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, 
  * of the last solve ran on the stencil-dictionary copy of the matrix (dictionaries equal to the matrix bit for bit:
  * binary lattice spacings), else 0 (CSR)} */
 int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]);
+/* ---- subgrid heat flux: Smagorinsky eddy diffusivity in the scalar step (new).  With law 1 of
+ * nsfem_set_viscosity_law (C_s), g_ab = d_b u_a, gamma and Delta_K as there, and a turbulent Prandtl number Pr_t > 0:
+ *   kappa_x(gamma, Delta_K) = (C_s Delta_K)^2 gamma / Pr_t
+ *   D(u, T)_i = sum_K sum_q w_q |det J_K| kappa_x(gamma_q, Delta_K) grad T_q . grad phi_i(x_q)
+ * by the 7-point (triangles) / 15-point (tetrahedra) rule of the scalar convection kernels; the rule is part of the
+ * definition.  kappa K stays in the implicit matrix (no rebuild, the one CG solve); D joins the extrapolated vector,
+ * formed inside the convection launch (k_scalar_conv_cell<FORM, PENAL, 1>): NSFEM_TCONV_1 = beta0 [C(u1) T1 +
+ * D(u1, T1) (+ H)], likewise NSFEM_TCONV_2.  The explicit treatment is stable for every k only while kappa_x <
+ * kappa / 3 (SBDF2); otherwise k is bounded by about Delta^2 / kappa_x.
+ * prandtl_t = 0 switches the term off (nsfem_step_scalar_imex then launches what it launches without this call), a
+ * finite value > 0 switches it on; the same value again changes nothing.  The stored NSFEM_TCONV_2 counts as stale
+ * after a change of Pr_t and, while the term is on, of the law or its parameters; it is then formed again with the
+ * level's own data.  NSFEM_ERR_ARG: any other value, contexts with a communicator.
+ * With the term on, nsfem_step_scalar_imex and nsfem_scalar_explicit refuse (NSFEM_ERR_ARG, state untouched) unless the
+ * viscosity law is 1: law 0 and Carreau are errors, not molecular runs.  nsfem_wall_compute with use_law and law 1 forms
+ * its conductive heat row with kappa + nu_x / Pr_t; with the term off that row keeps its bytes. */
+int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t);
+/* Test hook: out_host [n_p2] = what ONE launch of the step forms for a level, weight [C(u) T + D(u, T) (+ H(T))] -- D
+ * while the term is on, H while a body is thermal (pose of t^(n-1) for scalar_slot NSFEM_T2, of t^n otherwise).  It
+ * goes into a Krylov work vector: no slot is written.  With the term off and no thermal body it returns the bytes of
+ * nsfem_scalar_convection, which keeps returning C(u) T alone. */
+int nsfem_scalar_explicit(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
+                          double* out_host);
+/* out = {1 while the term is on else 0, launches of the SGS = 1 kernels, stored vectors formed again because Pr_t or
+ * (with the term on) the law changed, 0} */
+int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]);
 /* ---- variable viscosity in the IMEX step (new; the reference knows one constant viscosity).  nu = c_v + nu_x(gamma,
  * Delta_K) with gamma = sqrt(2 S:S) = sqrt(1/2 sum_ab (g_ab + g_ba)^2), g_ab = d_b u_a, and Delta_K = |K|^(1/dim),
  * |K| = |det J_K| / dim!.  The constant part c_v K stays in the implicit matrix; the remainder

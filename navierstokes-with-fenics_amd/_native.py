@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_imex_rotation", "nsfem_imex_rotation_info",
     "nsfem_volume_functionals",
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
+    "nsfem_set_scalar_sgs", "nsfem_scalar_explicit", "nsfem_scalar_sgs_info",
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
     "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
     "nsfem_body_info",
@@ -212,6 +213,9 @@ def load_library(path=None):
         "nsfem_step_scalar_imex": (C.c_int, [vp, C.POINTER(KrylovOpts), C.POINTER(SolveInfo)]),
         "nsfem_scalar_convection": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, pd]),
         "nsfem_scalar_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_scalar_sgs": (C.c_int, [vp, dbl]),
+        "nsfem_scalar_explicit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, pd]),
+        "nsfem_scalar_sgs_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_viscosity_law": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_viscosity_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
         "nsfem_viscosity_cells": (C.c_int, [vp, C.c_int, pd]),
@@ -574,6 +578,27 @@ class NsfemContext:
         self._check(self._lib.nsfem_scalar_info(self._h, out))
         return dict(matrix_builds=int(out[0]), convection_launches=int(out[1]), convection_reuses=int(out[2]),
                     dictionary=bool(out[3]))
+
+    # -- subgrid heat flux in the scalar step ---------------------------------------------
+    def set_scalar_sgs(self, prandtl_t):
+        """turbulent Prandtl number of the subgrid heat flux kappa_x = nu_x / Pr_t (Smagorinsky law, set_viscosity_law
+        1): 0 switches the term off (step_scalar_imex runs exactly as without this call), a finite value > 0 on"""
+        self._check(self._lib.nsfem_set_scalar_sgs(self._h, float(prandtl_t)))
+
+    def scalar_explicit(self, velocity_slot=U1, scalar_slot=T1, form=0, weight=1.0):
+        """test hook: what one launch of the transport step forms, weight * [C(u) T + D(u, T) (+ H(T))] (element kernel
+        + node sums; no stored state touched); D with the subgrid heat flux on, H with a thermal body"""
+        out = np.empty(self.n_p2, dtype=np.float64)
+        self._check(self._lib.nsfem_scalar_explicit(self._h, int(velocity_slot), int(scalar_slot), int(form),
+                                                    float(weight), _dp(out)))
+        return out
+
+    def scalar_sgs_info(self):
+        """dict(active, launches = launches of the kernels with the subgrid term, recomputed = stored vectors formed
+        again because Pr_t or, with the term on, the viscosity law changed)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_scalar_sgs_info(self._h, out))
+        return dict(active=bool(out[0]), launches=int(out[1]), recomputed=int(out[2]))
 
     # -- variable viscosity in the IMEX step ---------------------------------------------
     def set_viscosity_law(self, law, params=None):

@@ -599,6 +599,8 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
     ctx->sc.conv2_valid = true; ctx->sc.conv2_weight = 1.0; ctx->sc.conv_form = -2;
     ctx->sc.conv_thermal_epoch = ctx->bodies.thermal_epoch;
     ctx->sc.conv_body_epoch = ctx->bodies.epoch;
+    ctx->sc.conv_sgs_epoch = ctx->sc.sgs_epoch;
+    ctx->sc.conv_visc_epoch = ctx->visc.epoch;
   }
   if (slot == NSFEM_T_SOURCE) ctx->sc.have_source = true;
   API_END(ctx)
@@ -3146,6 +3148,37 @@ extern "C" int nsfem_set_scalar(nsfem_ctx* ctx, double diffusivity, const double
   API_END(ctx)
 }
 
+// Subgrid heat flux: kappa_x = nu_x / Pr_t of the Smagorinsky law under the gradients of the scalar, explicit, inside
+// the convection launch (k_scalar_conv_cell<FORM, PENAL, 1>).  kappa K stays in the matrix: no rebuild, no new solve
+extern "C" int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(std::isfinite(prandtl_t) && prandtl_t >= 0.0,
+                "subgrid heat flux: Pr_t must be 0 (off) or finite and > 0");
+  nsfem_ctx::Scalar& sc = ctx->sc;
+  // (the stored vectors belong to the Pr_t they were evaluated with; the term enters no captured Krylov body)
+  if (prandtl_t != sc.prandtl_t) ++sc.sgs_epoch;
+  sc.prandtl_t = prandtl_t == 0.0 ? 0.0 : prandtl_t;
+  API_END(ctx)
+}
+
+// what the convection launches take: C_s of the viscosity law and 1 / Pr_t while the term is on, nothing otherwise
+static ScalarSgsArgs scalar_sgs_args(const nsfem_ctx* c) {
+  ScalarSgsArgs a;
+  if (c->sc.prandtl_t > 0.0) {
+    a.cs = c->visc.p[0];
+    a.inv_prt = 1.0 / c->sc.prandtl_t;
+    a.active = 1;
+  }
+  return a;
+}
+
+static void scalar_sgs_require_law(const nsfem_ctx* c) {
+  NSFEM_REQUIRE(c->sc.prandtl_t == 0.0 || c->visc.law == 1,
+                "subgrid heat flux: Pr_t is set but the viscosity law is not 1 (Smagorinsky, nsfem_set_viscosity_law)");
+}
+
 // A = alpha0/k M + gamma0 kappa K, rebuilt only when one of the three numbers changed
 static void ensure_scalar_matrix(nsfem_ctx* c) {
   nsfem_ctx::Scalar& sc = c->sc;
@@ -3177,6 +3210,7 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
   scalar_require_supported(ctx);
+  scalar_sgs_require_law(ctx);
   nsfem_ctx::Scalar& sc = ctx->sc;
   hipStream_t s = ctx->stream;
   const int64_t n = ctx->mesh.n_p2;
@@ -3209,24 +3243,31 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   // Heated bodies (nsfem_set_body_temperatures, at least one flag 1): the same launches form C(u) T + H(T), with the
   // pose of the level (cur for T1, prev for a T2 vector formed afresh); the stored vectors are stale after a change
   // of the thermal table or, while a body is thermal, of the body set.  Without a thermal body: the launches of old
+  // Subgrid heat flux (nsfem_set_scalar_sgs, Pr_t > 0): the same launches add D(u, T) (SGS = 1 kernels); the stored
+  // vectors are stale after a change of Pr_t or, while the term is on, of the viscosity law's parameters (C_s)
   nsfem_ctx::Bodies& bd = ctx->bodies;
   const bool heated = bd.n_thermal > 0 && bd.cur.n > 0;
+  const ScalarSgsArgs sgs = scalar_sgs_args(ctx);
   double f2 = 0.0;
   if (b1 != 0.0) {
     const bool usable = sc.conv2_valid && sc.conv2_weight != 0.0 && (sc.conv_form == -2 || sc.conv_form == sc.form);
     const bool same_heat = sc.conv_thermal_epoch == bd.thermal_epoch && (!heated || sc.conv_body_epoch == bd.epoch);
-    if (usable && same_heat) {
+    const bool same_sgs = sc.conv_sgs_epoch == sc.sgs_epoch && (!sgs.active || sc.conv_visc_epoch == ctx->visc.epoch);
+    if (usable && same_heat && same_sgs) {
       ++sc.conv_reuses;
     } else {
-      if (usable) ++bd.thermal_recomputed;
+      if (usable && !same_heat) ++bd.thermal_recomputed;
+      if (usable && !same_sgs) ++sc.sgs_recomputed;
       if (heated) {
         launch_scalar_convection_heated(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, bd.prev, bd.thermal,
-                                        ctx->state[NSFEM_TCONV_2].p);
+                                        ctx->state[NSFEM_TCONV_2].p, sgs);
         ++bd.fused_launches;
       } else {
-        launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, ctx->state[NSFEM_TCONV_2].p);
+        launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, ctx->state[NSFEM_TCONV_2].p,
+                                 sgs);
       }
       ++sc.conv_launches;
+      if (sgs.active) ++sc.sgs_launches;
       sc.conv2_weight = 1.0;
       sc.conv2_valid = true;
     }
@@ -3235,17 +3276,20 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   // beta0 C(u1) T1: beta0 rides in the kernel's weight, the node sums are the stored copy
   if (heated) {
     launch_scalar_convection_heated(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, bd.cur, bd.thermal,
-                                    ctx->state[NSFEM_TCONV_1].p);
+                                    ctx->state[NSFEM_TCONV_1].p, sgs);
     ++bd.fused_launches;
   } else {
-    launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p);
+    launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p, sgs);
   }
   ++sc.conv_launches;
+  if (sgs.active) ++sc.sgs_launches;
   sc.conv1_fresh = true;
   sc.conv1_weight = b0;
   sc.conv_form = sc.form;
   sc.conv_thermal_epoch = bd.thermal_epoch;
   sc.conv_body_epoch = bd.epoch;
+  sc.conv_sgs_epoch = sc.sgs_epoch;
+  sc.conv_visc_epoch = ctx->visc.epoch;
   if (b1 != 0.0) launch_lincomb3(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, -f2, ctx->state[NSFEM_TCONV_2].p, rhs);
   else launch_axpby(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, rhs);
   // Dirichlet rows T_i = g_i; start vector T1 with the Dirichlet values (as the IMEX diffusion step)
@@ -3297,6 +3341,52 @@ extern "C" int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int sc
   launch_scalar_convection(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, out);
   NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+// what ONE launch of the step forms for a level: weight [C(u) T + D(u, T) (+ H(T))] -- D while the subgrid heat flux is
+// on, H while a body is thermal (pose: prev for the level T2, cur otherwise, as the step takes them)
+extern "C" int nsfem_scalar_explicit(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
+                                     double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
+                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+  NSFEM_REQUIRE(scalar_slot >= NSFEM_T0 && scalar_slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
+  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
+  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  scalar_sgs_require_law(ctx);
+  hipStream_t s = ctx->stream;
+  const int64_t n = ctx->mesh.n_p2;
+  ensure_scalar_slot(ctx, scalar_slot);
+  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
+  ctx->kw.ensure(nvel(ctx));
+  ++ctx->kw.touch;
+  double* out = ctx->kw.q.p;
+  nsfem_ctx::Bodies& bd = ctx->bodies;
+  const ScalarSgsArgs sgs = scalar_sgs_args(ctx);
+  if (bd.n_thermal > 0 && bd.cur.n > 0) {
+    launch_scalar_convection_heated(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form,
+                                    scalar_slot == NSFEM_T2 ? bd.prev : bd.cur, bd.thermal, out, sgs);
+    ++bd.fused_launches;
+  } else {
+    launch_scalar_convection(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, out,
+                             sgs);
+  }
+  if (sgs.active) ++ctx->sc.sgs_launches;
+  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->sc.prandtl_t > 0.0 ? 1 : 0;
+  out[1] = ctx->sc.sgs_launches;
+  out[2] = ctx->sc.sgs_recomputed;
+  out[3] = 0;
   API_END(ctx)
 }
 
@@ -4466,6 +4556,8 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   for (int d = 0; d < 3; ++d) wp.origin[d] = opts->origin[d];
   wp.law = opts->use_law != 0 ? ctx->visc.law : 0;
   for (int k = 0; k < 3; ++k) wp.law_p[k] = ctx->visc.p[k];
+  // subgrid heat flux: the conductive row carries kappa + nu_x / Pr_t where the traction carries nu_x (law 1 only)
+  wp.inv_prt = wp.law == 1 && scalar_slot != -1 && ctx->sc.prandtl_t > 0.0 ? 1.0 / ctx->sc.prandtl_t : 0.0;
   hipStream_t s = ctx->stream;
   launch_wall_facets(s, m, W.n_facets, W.fcell.p, W.flocal.p, ctx->state[velocity_slot].p, ctx->state[pressure_slot].p,
                      scalar_slot != -1 ? ctx->state[scalar_slot].p : nullptr, wp, W.rows.p);

@@ -789,12 +789,18 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 // x_q the affine image of the reference point, chi and the winner from body_winner (bodies.hpp) as in k_penal_cell;
 // x_q, the winner, chi and T_q are formed once per quadrature point, points with chi = 0 or a passive winner add
 // nothing.  PENAL 0 takes no table at all and is the code of every run without temperatures.
-template <int FORM, int PENAL>
+// SGS 1: subgrid heat flux (nsfem_set_scalar_sgs) -- the same launch adds
+//   wgt sum_q w_q |det J| kappa_x(gamma_q, Delta_K) grad T_q . grad phi_i(x_q),   kappa_x = (C_s Delta_K)^2 gamma / Pr_t
+// with g_ab = d_b u_a summed from the gradients the point forms anyway, gamma and Delta_K^2 = |det J| / 2 as in
+// k_visc_var_cell and the law visc_law_nu<1> (cell_geometry.hpp).  SGS 0 takes nothing and is the code of every run
+// without the setting.
+template <int FORM, int PENAL, int SGS = 0>
 __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                           const int32_t* __restrict__ p2,
                                                           const double* __restrict__ u,
                                                           const double* __restrict__ T, double wgt,
                                                           const ScalarPenalArgs<PENAL> pa,
+                                                          const ScalarSgsKernelArgs<SGS> sg,
                                                           const int32_t* __restrict__ ndst,
                                                           double* __restrict__ rbuf) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -826,6 +832,7 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
   for (int q = 0; q < 7; ++q) {
     double gx[6], gy[6];
     double uqx = 0.0, uqy = 0.0, tq = 0.0, dtx = 0.0, dty = 0.0;
+    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a (SGS)
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx[k], gy[k]);
@@ -835,6 +842,12 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
       dtx += gx[k] * t[k];
       dty += gy[k] * t[k];
       if (FORM == 1 || PENAL != 0) tq += ph * t[k];
+      if constexpr (SGS != 0) {
+        g00 += gx[k] * ux[k];
+        g01 += gy[k] * ux[k];
+        g10 += gx[k] * uy[k];
+        g11 += gy[k] * uy[k];
+      }
     }
     const double w = c_q.w[q] * g.adet * wgt;
     const double adv = uqx * dtx + uqy * dty;           // u . grad T
@@ -846,6 +859,13 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
         const double ugi = uqx * gx[i] + uqy * gy[i];   // u . grad phi_i
         r[i] += 0.5 * w * (c_q.phi2[q][i] * adv - ugi * tq);
       }
+    }
+    if constexpr (SGS != 0) {
+      const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T
+      const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
+      const double wk = w * (visc_law_nu<1>(gamma, 0.5 * g.adet, sg.cs, 0.0, 0.0) * sg.inv_prt);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) r[i] += wk * (dtx * gx[i] + dty * gy[i]);
     }
     if constexpr (PENAL != 0) {
       if (!reach) continue;
@@ -897,36 +917,51 @@ __global__ __launch_bounds__(256) void k_buoyancy_force(int64_t n_nodes, int dim
 }
 
 void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                              int form, double* out) {
+                              int form, double* out, ScalarSgsArgs sgs) {
   NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
   if (m.dim == 3) {
-    scalar_convection_cells_3d(s, m, u, T, weight, form);
+    scalar_convection_cells_3d(s, m, u, T, weight, form, sgs);
   } else {
     const dim3 grid(grid_for(m.n_cells)), block(kBlock);
-    if (form == 0)
-      hipLaunchKernelGGL((k_scalar_conv_cell<0, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
-                         ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
-    else
-      hipLaunchKernelGGL((k_scalar_conv_cell<1, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
-                         ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
+    // (SGS defaults to 0: without the term these are the launches of old)
+#define NSFEM_SC(F) \
+  hipLaunchKernelGGL((k_scalar_conv_cell<F, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SCS(F) \
+  hipLaunchKernelGGL((k_scalar_conv_cell<F, 0, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+    if (sgs.active) { if (form == 0) NSFEM_SCS(0); else NSFEM_SCS(1); }
+    else { if (form == 0) NSFEM_SC(0); else NSFEM_SC(1); }
+#undef NSFEM_SCS
+#undef NSFEM_SC
   }
   hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
   NSFEM_HIP(hipGetLastError());
 }
 
 void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                     int form, const BodyTable& bt, const ThermalTable& th, double* out) {
+                                     int form, const BodyTable& bt, const ThermalTable& th, double* out,
+                                     ScalarSgsArgs sgs) {
   NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
   NSFEM_REQUIRE(bt.n > 0 && th.n == bt.n, "heated bodies: no temperatures set for the bodies");
   if (m.dim == 3) {
-    scalar_convection_heated_cells_3d(s, m, u, T, weight, form, bt, th);
+    scalar_convection_heated_cells_3d(s, m, u, T, weight, form, bt, th, sgs);
   } else {
     const dim3 grid(grid_for(m.n_cells)), block(kBlock);
 #define NSFEM_SCH(F, P) \
   hipLaunchKernelGGL((k_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, m.ndst.p, m.rbuf.p)
-    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH(0, 2); else NSFEM_SCH(1, 2); }
-    else { if (form == 0) NSFEM_SCH(0, 1); else NSFEM_SCH(1, 1); }
+                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SCHS(F, P) \
+  hipLaunchKernelGGL((k_scalar_conv_cell<F, P, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+    if (sgs.active) {
+      if (bt.eps > 0.0) { if (form == 0) NSFEM_SCHS(0, 2); else NSFEM_SCHS(1, 2); }
+      else { if (form == 0) NSFEM_SCHS(0, 1); else NSFEM_SCHS(1, 1); }
+    } else {
+      if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH(0, 2); else NSFEM_SCH(1, 2); }
+      else { if (form == 0) NSFEM_SCH(0, 1); else NSFEM_SCH(1, 1); }
+    }
+#undef NSFEM_SCHS
 #undef NSFEM_SCH
   }
   hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);

@@ -849,17 +849,26 @@ void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double w
 // as they are formed.
 // PENAL 1 / 2: heated bodies, as k_scalar_conv_cell (assembly.hip) -- the same launch adds
 // wgt/eta_T sum_q w_q |det J| chi(x_q) theta_win (T(x_q) - T_win) phi_i(x_q); PENAL 0 takes no table.
-template <int FORM, int PENAL>
+// SGS 1: subgrid heat flux, as k_scalar_conv_cell -- the same launch adds
+// wgt sum_q w_q |det J| kappa_x(gamma_q, Delta_K) grad T_q . grad phi_i(x_q), kappa_x = (C_s Delta_K)^2 gamma / Pr_t,
+// gamma and Delta_K as in k3_visc_var_cell; the gradients of a point are kept in either form then.  SGS 0 takes nothing.
+template <int FORM, int PENAL, int SGS = 0>
 __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                            const int32_t* __restrict__ p2,
                                                            const double* __restrict__ u,
                                                            const double* __restrict__ T, double wgt,
                                                            const ScalarPenalArgs<PENAL> pa,
+                                                           const ScalarSgsKernelArgs<SGS> sg,
                                                            const int32_t* __restrict__ ndst,
                                                            double* __restrict__ rbuf) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const CellGeo3 g = load_geo3(vx, nc, c);
+  double delta2 = 0.0;                   // Delta_K^2 (SGS)
+  if constexpr (SGS != 0) {
+    const double delta = cbrt(g.adet / 6.0);
+    delta2 = delta * delta;
+  }
   double un[10][3], t[10];
 #pragma unroll
   for (int k = 0; k < 10; ++k) {
@@ -881,8 +890,9 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
 #pragma unroll
   for (int i = 0; i < 10; ++i) r[i] = 0.0;
   for (int q = 0; q < 15; ++q) {
-    double gk[FORM == 1 ? 10 : 1][3];
+    double gk[FORM == 1 || SGS != 0 ? 10 : 1][3];
     double uq[3] = {0.0, 0.0, 0.0}, dt[3] = {0.0, 0.0, 0.0}, tq = 0.0;
+    double G[SGS != 0 ? 3 : 1][3] = {};   // G[a][b] = d_b u_a (SGS)
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
       double gl[3];
@@ -892,7 +902,11 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
       for (int a = 0; a < 3; ++a) {
         uq[a] += ph * un[k][a];
         dt[a] += gl[a] * t[k];
-        if constexpr (FORM == 1) gk[k][a] = gl[a];
+        if constexpr (FORM == 1 || SGS != 0) gk[k][a] = gl[a];
+        if constexpr (SGS != 0) {
+#pragma unroll
+          for (int b = 0; b < 3; ++b) G[a][b] += gl[b] * un[k][a];
+        }
       }
       if (FORM == 1 || PENAL != 0) tq += ph * t[k];
     }
@@ -906,6 +920,14 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
         const double ugi = uq[0] * gk[i][0] + uq[1] * gk[i][1] + uq[2] * gk[i][2];   // u . grad phi_i
         r[i] += 0.5 * w * (c_q3.phi2[q][i] * adv - ugi * tq);
       }
+    }
+    if constexpr (SGS != 0) {
+      const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
+      const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
+      const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
+      const double wk = w * (visc_law_nu<1>(gamma, delta2, sg.cs, 0.0, 0.0) * sg.inv_prt);
+#pragma unroll
+      for (int i = 0; i < 10; ++i) r[i] += wk * (dt[0] * gk[i][0] + dt[1] * gk[i][1] + dt[2] * gk[i][2]);
     }
     if constexpr (PENAL != 0) {
       if (!reach) continue;
@@ -927,25 +949,39 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
 }
 
 void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                int form) {
+                                int form, ScalarSgsArgs sgs) {
   const dim3 grid(grid3(m.n_cells)), block(kBlock);
-  if (form == 0)
-    hipLaunchKernelGGL((k3_scalar_conv_cell<0, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
-                       ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
-  else
-    hipLaunchKernelGGL((k3_scalar_conv_cell<1, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
-                       ScalarPenalArgs<0>{}, m.ndst.p, m.rbuf.p);
+#define NSFEM_SC3(F) \
+  hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SC3S(F) \
+  hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+  if (sgs.active) { if (form == 0) NSFEM_SC3S(0); else NSFEM_SC3S(1); }
+  else { if (form == 0) NSFEM_SC3(0); else NSFEM_SC3(1); }
+#undef NSFEM_SC3S
+#undef NSFEM_SC3
   NSFEM_HIP(hipGetLastError());
 }
 
 void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T,
-                                       double weight, int form, const BodyTable& bt, const ThermalTable& th) {
+                                       double weight, int form, const BodyTable& bt, const ThermalTable& th,
+                                       ScalarSgsArgs sgs) {
   const dim3 grid(grid3(m.n_cells)), block(kBlock);
 #define NSFEM_SCH3(F, P) \
   hipLaunchKernelGGL((k3_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, m.ndst.p, m.rbuf.p)
-  if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3(0, 2); else NSFEM_SCH3(1, 2); }
-  else { if (form == 0) NSFEM_SCH3(0, 1); else NSFEM_SCH3(1, 1); }
+                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SCH3S(F, P) \
+  hipLaunchKernelGGL((k3_scalar_conv_cell<F, P, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+  if (sgs.active) {
+    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3S(0, 2); else NSFEM_SCH3S(1, 2); }
+    else { if (form == 0) NSFEM_SCH3S(0, 1); else NSFEM_SCH3S(1, 1); }
+  } else {
+    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3(0, 2); else NSFEM_SCH3(1, 2); }
+    else { if (form == 0) NSFEM_SCH3(0, 1); else NSFEM_SCH3(1, 1); }
+  }
+#undef NSFEM_SCH3S
 #undef NSFEM_SCH3
   NSFEM_HIP(hipGetLastError());
 }

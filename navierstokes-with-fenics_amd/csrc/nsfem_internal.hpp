@@ -474,11 +474,26 @@ void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u
                                 double* b, int form, const double* gam = nullptr);
 // scalar transport (nsfem_step_scalar_imex): out = weight * C(u) T for the P2 scalar T on the velocity nodes, form 0
 // standard C_ij = int (u . grad phi_j) phi_i, 1 skew-symmetric 1/2 (C - C^T) -- element kernel (k_scalar_conv_cell /
-// k3_scalar_conv_cell, node-sorted element vectors in m.rbuf) plus the per-node sums in ascending cell order
+// k3_scalar_conv_cell, node-sorted element vectors in m.rbuf) plus the per-node sums in ascending cell order.
+// Subgrid heat flux (nsfem_set_scalar_sgs): the launchers take ScalarSgsArgs by value.  active: the same launch adds
+// D(u, T), the Smagorinsky eddy diffusivity kappa_x = (cs Delta_K)^2 gamma inv_prt under the gradients (the SGS = 1
+// instantiations), out = weight (C(u) T + D(u, T)); not active: the SGS = 0 kernels, which take nothing
+struct ScalarSgsArgs {
+  double cs = 0.0, inv_prt = 0.0;
+  int32_t active = 0;
+  int32_t pad_ = 0;
+};
+// ... and what the kernels take: the two numbers with SGS = 1, nothing at all with SGS = 0
+template <int SGS>
+struct ScalarSgsKernelArgs {
+  double cs, inv_prt;
+};
+template <>
+struct ScalarSgsKernelArgs<0> {};
 void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                              int form, double* out);
+                              int form, double* out, ScalarSgsArgs sgs = ScalarSgsArgs{});
 void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                int form);
+                                int form, ScalarSgsArgs sgs);
 // variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, p = params): the element kernel
 // k_visc_var_cell / k3_visc_var_cell on the velocity u, element vectors weight * V_K(u) node-sorted into m.rbuf --
 // mean: the cell means of nu_x into the first n_cells doubles of m.rbuf instead
@@ -518,12 +533,14 @@ struct ScalarPenalArgs {
 };
 template <>
 struct ScalarPenalArgs<0> {};
-// out = weight (C(u) T + H(T)): the fused element kernel k_scalar_conv_cell<FORM, PENAL> / k3_scalar_conv_cell (PENAL
-// 1 sharp, 2 smoothed masks; bt the pose that belongs to the level of T) plus k_scalar_gather
+// out = weight (C(u) T + H(T)): the fused element kernel k_scalar_conv_cell<FORM, PENAL, SGS> / k3_scalar_conv_cell
+// (PENAL 1 sharp, 2 smoothed masks; bt the pose that belongs to the level of T) plus k_scalar_gather
 void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                     int form, const BodyTable& bt, const ThermalTable& th, double* out);
+                                     int form, const BodyTable& bt, const ThermalTable& th, double* out,
+                                     ScalarSgsArgs sgs = ScalarSgsArgs{});
 void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T,
-                                       double weight, int form, const BodyTable& bt, const ThermalTable& th);
+                                       double weight, int form, const BodyTable& bt, const ThermalTable& th,
+                                       ScalarSgsArgs sgs);
 // k_body_heat + k_penal_finish (bodies.hip): out[s][3] = {int chi_s, Q_s, int chi_s T} in device memory, parts
 // [n 3 kBodyParts] work space
 void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const BodyTable& bt, const ThermalTable& th,
@@ -645,6 +662,7 @@ struct WallParams {
   double nu = 0.0, sym = 0.0, kappa = 0.0, origin[3] = {0.0, 0.0, 0.0};
   int law = 0;                               // 0: constant viscosity; 1, 2: + nu_x of visc_law_nu<law>
   double law_p[3] = {0.0, 0.0, 0.0};
+  double inv_prt = 0.0;                      // law 1 and != 0: the heat row uses kappa + nu_x inv_prt (subgrid heat flux)
 };
 // ONE launch: rows[f][NW] of the nf facets (fcell, flocal: device lists); T may be null (no scalar: +0.0 entries)
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
@@ -1228,6 +1246,12 @@ struct nsfem_ctx {
     int conv_form = -1;                              // form the stored vectors belong to
     // heated bodies: bodies.thermal_epoch and (read only while a thermal body is set) bodies.epoch of the stored vectors
     int64_t conv_thermal_epoch = 0, conv_body_epoch = 0;
+    // subgrid heat flux (nsfem_set_scalar_sgs): prandtl_t > 0 switches D(u, T) on, the stored vectors carry it then.
+    // sgs_epoch counts the changes of prandtl_t; conv_sgs_epoch and (read only while the term is on) conv_visc_epoch
+    // are sgs_epoch and visc.epoch of the stored vectors
+    double prandtl_t = 0.0;
+    int64_t sgs_epoch = 0, sgs_launches = 0, sgs_recomputed = 0;
+    int64_t conv_sgs_epoch = 0, conv_visc_epoch = 0;
     int64_t matrix_builds = 0, conv_launches = 0, conv_reuses = 0;
     int dict_used = 0;
     bool dinv_dirty = true;                          // 1 / diagonal belongs to an older matrix or Dirichlet set

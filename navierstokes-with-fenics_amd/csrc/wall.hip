@@ -46,7 +46,8 @@ __device__ __forceinline__ void wall_p2_at(const double* lam, const double (*gl)
 //   [1 + DIM .. 2 DIM]        int [ nu (G + sym G^T) + nu_x (G + G^T) ] n        G_ab = d_b u_a
 //   [1 + 2 DIM]               int u.n
 //   [2 + 2 DIM]               int T                  (+0.0 without a scalar)
-//   [3 + 2 DIM]               int -kappa grad T . n  (+0.0 without a scalar)
+//   [3 + 2 DIM]               int -kappa grad T . n  (+0.0 without a scalar); with LAW = 1 and ipr = 1 / Pr_t != 0
+//                             (subgrid heat flux, nsfem_set_scalar_sgs): int -(kappa + nu_x ipr) grad T . n
 //   [4 + 2 DIM ..]            int (x - x0) x t, t the sum of the two traction integrands (2D: the z component)
 // n = the unit normal pointing out of the facet's cell.
 template <int DIM, int LAW>
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
                                                      const int32_t* __restrict__ p1, const double* __restrict__ u,
                                                      const double* __restrict__ p, const double* __restrict__ T,
                                                      double nu, double sym, double kappa, double ox, double oy,
-                                                     double oz, double lp0, double lp1, double lp2,
+                                                     double oz, double lp0, double lp1, double lp2, double ipr,
                                                      double* __restrict__ out) {
   constexpr int NV = DIM + 1, N2 = DIM == 2 ? 6 : 10, NQ = DIM == 2 ? 2 : 3;
   constexpr int NT = DIM == 2 ? 1 : 3, NW = 2 * DIM + 4 + NT;
@@ -222,7 +223,8 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
       hq += gT[a] * nrm[a];
     }
     sT += w * Tq;
-    heat += w * (-kappa * hq);
+    if (LAW == 1 && ipr != 0.0) heat += w * (-(kappa + nux * ipr) * hq);
+    else heat += w * (-kappa * hq);
     if (DIM == 2) {
       tq[0] += w * (r[0] * tr[1] - r[1] * tr[0]);
     } else {
@@ -281,7 +283,7 @@ static void launch_wall_facets_t(hipStream_t s, const MeshDev& m, int nf, const 
   const int grid = (nf + 255) / 256;
   hipLaunchKernelGGL((k_wall_facets<DIM, LAW>), dim3(grid), dim3(256), 0, s, nf, m.n_cells, fcell, flocal, m.vx.p,
                      m.p2.p, m.p1.p, u, p, T, w.nu, w.sym, w.kappa, w.origin[0], w.origin[1], w.origin[2], w.law_p[0],
-                     w.law_p[1], w.law_p[2], rows);
+                     w.law_p[1], w.law_p[2], w.inv_prt, rows);
 }
 
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,

@@ -22,6 +22,12 @@ Heated bodies: immersed bodies with a ``temperature`` (``immersed_bodies``) add 
 H(T) = (chi / eta_scalar) (T - T_s) to the transport step, inside the convection launch.
 The solver pushes the temperatures wherever it pushes the bodies and holds k / eta_scalar to the same
 stability test as k / eta.
+
+Subgrid heat flux: a ``viscosity_models.SmagorinskyModel(cs, prandtl_t)`` adds the explicit term D(u, T) with the
+eddy diffusivity kappa_x = nu_x / prandtl_t to the transport step, inside the same convection launch (DESIGN.md
+4r).  The solver pushes prandtl_t wherever it pushes the viscosity model and the scalar coefficients; a model
+without prandtl_t, or no model, pushes 0 (off).  The term is explicit: unconditionally stable only while kappa_x <
+kappa / 3, otherwise k is bounded by about Delta^2 / kappa_x.
 """
 import numpy as np
 
@@ -105,6 +111,21 @@ class BoussinesqIMEXSolver(IMEXIPCSSolver):
                 self._ctx.set_scalar(kappa, b, _SCALAR_FORM_ID[form])
             except nat.NativeError as err:
                 raise RuntimeError(str(err))
+            self._push_scalar_sgs()
+
+    def _push_viscosity_model(self):
+        """the model as ``IMEXIPCSSolver`` pushes it, then its turbulent Prandtl number (none: 0, the term off)"""
+        super()._push_viscosity_model()
+        self._push_scalar_sgs()
+
+    def _push_scalar_sgs(self):
+        if not hasattr(self, "_ctx"):
+            return
+        prandtl_t = getattr(getattr(self, "_viscosity_model", None), "prandtl_t", None)
+        try:
+            self._ctx.set_scalar_sgs(0.0 if prandtl_t is None else prandtl_t)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
 
     def _push_scalar_boundary_conditions(self, t=None):
         if hasattr(self, "_ctx") and hasattr(self, "_scalar_bcs"):

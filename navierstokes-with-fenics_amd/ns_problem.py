@@ -423,6 +423,17 @@ class ProblemBase:
             raise RuntimeError(str(err))
         return HostField(self._mesh, "model viscosity", "Cell", values)
 
+    def _compute_model_diffusivity(self):
+        """cell means of the eddy diffusivity kappa_x = nu_x / Pr_t of the subgrid heat flux (a ``SmagorinskyModel``
+        with ``prandtl_t``) for the current velocity: the cell means of ``_compute_model_viscosity`` divided by Pr_t.
+        New helper; valid for ``_add_to_field_output``."""
+        from fem_function import HostField
+        prandtl_t = getattr(getattr(self._get_solver(), "_viscosity_model", None), "prandtl_t", None)
+        if prandtl_t is None:
+            raise RuntimeError("model diffusivity: the viscosity model has no turbulent Prandtl number (prandtl_t)")
+        values = self._compute_model_viscosity().values / prandtl_t
+        return HostField(self._mesh, "model diffusivity", "Cell", values)
+
     def _compute_body_forces(self):
         """per immersed body (``set_immersed_bodies``) the volume, the force the fluid exerts on it and its torque
         about the body's centre for the current velocity, from the device (nsfem_body_forces):

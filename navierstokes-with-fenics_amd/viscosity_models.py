@@ -12,14 +12,22 @@ LAW_NONE, LAW_SMAGORINSKY, LAW_CARREAU = 0, 1, 2
 
 
 class SmagorinskyModel:
-    """nu_x = (C_s Delta_K)^2 gamma: the Smagorinsky subgrid viscosity with the constant ``cs`` >= 0"""
+    """nu_x = (C_s Delta_K)^2 gamma: the Smagorinsky subgrid viscosity with the constant ``cs`` >= 0.  With a
+    turbulent Prandtl number ``prandtl_t`` > 0 a solver with a transported scalar (``BoussinesqIMEXSolver``) adds the
+    subgrid heat flux with the eddy diffusivity kappa_x = nu_x / prandtl_t to its transport step
+    (``nsfem_set_scalar_sgs``); None: the scalar sees its molecular diffusivity alone."""
     law_id = LAW_SMAGORINSKY
 
-    def __init__(self, cs):
+    def __init__(self, cs, prandtl_t=None):
         cs = float(cs)
         if not (math.isfinite(cs) and cs >= 0.0):
             raise ValueError("SmagorinskyModel: cs must be finite and >= 0, got %r" % (cs, ))
+        if prandtl_t is not None:
+            prandtl_t = float(prandtl_t)
+            if not (math.isfinite(prandtl_t) and prandtl_t > 0.0):
+                raise ValueError("SmagorinskyModel: prandtl_t must be finite and > 0, got %r" % (prandtl_t, ))
         self.cs = cs
+        self.prandtl_t = prandtl_t
 
     def params(self, coefficients=None):
         return (self.cs, 0.0, 0.0, 0.0)

@@ -1,0 +1,171 @@
+"""Timing record of the subgrid heat flux of the scalar step (Smagorinsky eddy diffusivity inside the convection
+kernel).
+
+    python scripts/scalar_sgs_timing.py steps --n 512
+        the lid-driven cavity with a transported temperature on n x n squares through ``BoussinesqIMEXSolver`` (SBDF2)
+        with ``throughput_settings()`` and ``SmagorinskyModel(cs)``, alternating the model without and with
+        ``prandtl_t`` in one process; wall clock of ``solver.solve()`` and of the transport step inside it
+        (synchronised before and after) per step, median and minimum of ``--steps`` steps after ``--warmup``; one JSON
+        line per case.
+
+    rocprofv3 --kernel-trace -d DIR -- python scripts/scalar_sgs_timing.py kernels
+        ``--reps`` dispatches each of the scalar convection kernel with the term (k_scalar_conv_cell<FORM, 0, 1> /
+        k3_scalar_conv_cell, through nsfem_scalar_explicit), without it (SGS 0, through nsfem_scalar_convection) and of
+        the flow's viscosity pair (k_visc_var_cell<1> / k3_visc_var_cell<1> + k_visc_gather, through
+        nsfem_viscosity_residual) -- what a launch of its own for the term would cost -- on the cavity at n = 512 and on
+        a 64^3 box, both forms.
+
+    python scripts/scalar_sgs_timing.py summary DIR
+        median, minimum and maximum per kernel name and grid size of the trace under DIR, microseconds.
+"""
+import argparse
+import contextlib
+import csv
+import glob
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, d) for d in ("navierstokes-with-fenics_amd", "tests", "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+os.environ.setdefault("NSFEM_NO_OUTPUT", "1")      # no XDMF files: the run is a timing
+
+
+def run_steps(args):
+    from ns_boussinesq_solver import BoussinesqIMEXSolver
+    from problem_specs import build_problem
+    from viscosity_models import SmagorinskyModel
+
+    class TimedSolver(BoussinesqIMEXSolver):
+        """the transport step timed on its own: the stream is idle before it and after it"""
+        transport_times = []
+
+        def _solve_time_step(self):
+            ctx = self._ctx
+            real = ctx.step_scalar_imex
+
+            def timed(*a, **kw):
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                out = real(*a, **kw)
+                ctx.synchronize()
+                type(self).transport_times.append(time.perf_counter() - t0)
+                return out
+            ctx.step_scalar_imex = timed
+            try:
+                super()._solve_time_step()
+            finally:
+                del ctx.step_scalar_imex
+
+    for round_ in range(args.rounds):
+        for name, prandtl_t in (("molecular", None), ("subgrid flux", args.prandtl_t)):
+            spec = dict(name="cavity", mesh=("cube", 2, args.n), scheme="ipcs", numbers=dict(Re=100.0, Fr=1.0),
+                        clock=dict(dt=args.dt, steps=args.warmup + args.steps),
+                        start={"velocity": (0.0, 0.0), "pressure": 0.0, "temperature": 0.5},
+                        bcs=[("no_slip", "left"), ("no_slip", "right"), ("no_slip", "bottom"),
+                             ("velocity", "top", (1.0, 0.0))])
+            problem = build_problem(spec)
+            cls = type(problem)
+
+            def set_temperature_coefficients(self):
+                self._temperature_coefficients = dict(diffusivity=0.01, buoyancy=(0.0, 1.0), convective_form="standard")
+
+            def set_temperature_boundary_conditions(self):
+                self._temperature_bcs = [(self._sides["left"], 1.0), (self._sides["right"], 0.0)]
+
+            def set_viscosity_model(self, prandtl_t=prandtl_t):
+                self._viscosity_model = SmagorinskyModel(args.cs, prandtl_t=prandtl_t)
+            cls.set_temperature_coefficients = set_temperature_coefficients
+            cls.set_temperature_boundary_conditions = set_temperature_boundary_conditions
+            cls.set_viscosity_model = set_viscosity_model
+            TimedSolver.transport_times = []
+            problem.set_solver_class(TimedSolver)
+            problem.compute_cfl = False
+            problem.solver_settings = "throughput"
+            with contextlib.redirect_stdout(io.StringIO()):
+                problem.solve_problem()
+            solver = problem._get_solver()
+            ms = [1e3 * t for t in problem.step_wall_times[args.warmup:]]
+            tr = [1e3 * t for t in TimedSolver.transport_times[args.warmup:]]
+            print(json.dumps(dict(case=name, round=round_, n=args.n, dt=args.dt, steps=args.steps, warmup=args.warmup,
+                                  step_ms=dict(median=statistics.median(ms), min=min(ms)),
+                                  transport_ms=dict(median=statistics.median(tr), min=min(tr)),
+                                  imex=solver._ctx.imex_info(), scalar=solver._ctx.scalar_info(),
+                                  sgs=solver._ctx.scalar_sgs_info(), viscosity=solver._ctx.viscosity_info(),
+                                  cg_scalar=solver.last_scalar_solve.iterations)), flush=True)
+
+
+def run_kernels(args):
+    import _native as nat
+    from gpu_common import box, context
+    from test_gpu_3d import box3, context3
+    from test_scalar_transport_host import smooth_fields
+    cases = [("2d", lambda: box(args.n, args.n), context), ("3d", lambda: box3((args.n3, ) * 3), context3)]
+    for tag, make_mesh, make_ctx in cases:
+        mesh, dm, marks = make_mesh()
+        u, T = smooth_fields(dm.p2_coords)
+        ctx = make_ctx(mesh, dm)
+        try:
+            ctx.set_state(nat.U1, u)
+            ctx.set_state(nat.T1, T)
+            ctx.set_viscosity_law(1, (args.cs, ))
+            ctx.set_scalar_sgs(args.prandtl_t)
+            for form in (0, 1):
+                for _ in range(args.reps):
+                    ctx.scalar_explicit(nat.U1, nat.T1, form, 1.0)
+                for _ in range(args.reps):
+                    ctx.scalar_convection(nat.U1, nat.T1, form, 1.0)
+            for _ in range(args.reps):
+                ctx.viscosity_residual(nat.U1, 1.0)
+            print(json.dumps(dict(case=tag, cells=int(mesh.cells.shape[0]), sgs=ctx.scalar_sgs_info())), flush=True)
+        finally:
+            ctx.close()
+
+
+def run_summary(args):
+    """per kernel name AND grid size: the 2D and the 3D mesh launch the shared kernels with different grids"""
+    rows = {}
+    for path in glob.glob(os.path.join(args.dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path, newline="") as fh:
+            for r in csv.DictReader(fh):
+                key = (r["Kernel_Name"], int(r["Grid_Size_X"]))
+                rows.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3)
+    for name, grid in sorted(rows):
+        if any(w in name for w in args.match.split(",")):
+            v = rows[(name, grid)]
+            print("%6d  median %9.2f  min %9.2f  max %9.2f  grid %10d  %s" % (len(v), statistics.median(v), min(v), max(v),
+                                                                            grid, name))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="mode", required=True)
+    p = sub.add_parser("steps")
+    p.add_argument("--n", type=int, default=512)
+    p.add_argument("--dt", type=float, default=1.0e-3)
+    p.add_argument("--steps", type=int, default=30)
+    p.add_argument("--warmup", type=int, default=10)
+    p.add_argument("--rounds", type=int, default=2)
+    p.add_argument("--cs", type=float, default=0.17)
+    p.add_argument("--prandtl-t", dest="prandtl_t", type=float, default=0.85)
+    p = sub.add_parser("kernels")
+    p.add_argument("--n", type=int, default=512)
+    p.add_argument("--n3", type=int, default=64)
+    p.add_argument("--reps", type=int, default=30)
+    p.add_argument("--cs", type=float, default=0.17)
+    p.add_argument("--prandtl-t", dest="prandtl_t", type=float, default=0.85)
+    p = sub.add_parser("summary")
+    p.add_argument("dir")
+    p.add_argument("--match", default="scalar_conv_cell,scalar_gather,visc_var_cell,visc_gather")
+    args = ap.parse_args()
+    dict(steps=run_steps, kernels=run_kernels, summary=run_summary)[args.mode](args)
+
+
+if __name__ == "__main__":
+    main()
