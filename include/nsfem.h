@@ -489,13 +489,14 @@ int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, 
  * of the last solve ran on the stencil-dictionary copy of the matrix (dictionaries equal to the matrix bit for bit:
  * binary lattice spacings), else 0 (CSR)} */
 int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]);
-/* ---- subgrid heat flux: Smagorinsky eddy diffusivity in the scalar step (new).  With law 1 of
- * nsfem_set_viscosity_law (C_s), g_ab = d_b u_a, gamma and Delta_K as there, and a turbulent Prandtl number Pr_t > 0:
- *   kappa_x(gamma, Delta_K) = (C_s Delta_K)^2 gamma / Pr_t
+/* ---- subgrid heat flux: eddy diffusivity of a subgrid law in the scalar step (new).  With law 1 (Smagorinsky, C_s),
+ * 4 (WALE, C_w) or 5 (Vreman, c) of nsfem_set_viscosity_law, g_ab = d_b u_a, gamma and Delta_K as there, and a
+ * turbulent Prandtl number Pr_t > 0:
+ *   kappa_x = nu_x / Pr_t          (law 1: kappa_x(gamma, Delta_K) = (C_s Delta_K)^2 gamma / Pr_t)
  *   D(u, T)_i = sum_K sum_q w_q |det J_K| kappa_x(gamma_q, Delta_K) grad T_q . grad phi_i(x_q)
  * by the 7-point (triangles) / 15-point (tetrahedra) rule of the scalar convection kernels; the rule is part of the
  * definition.  kappa K stays in the implicit matrix (no rebuild, the one CG solve); D joins the extrapolated vector,
- * formed inside the convection launch (k_scalar_conv_cell<FORM, PENAL, 1>): NSFEM_TCONV_1 = beta0 [C(u1) T1 +
+ * formed inside the convection launch (k_scalar_conv_cell<FORM, PENAL, law>): NSFEM_TCONV_1 = beta0 [C(u1) T1 +
  * D(u1, T1) (+ H)], likewise NSFEM_TCONV_2.  The explicit treatment is stable for every k only while kappa_x <
  * kappa / 3 (SBDF2); otherwise k is bounded by about Delta^2 / kappa_x.
  * prandtl_t = 0 switches the term off (nsfem_step_scalar_imex then launches what it launches without this call), a
@@ -503,8 +504,8 @@ int nsfem_scalar_info(nsfem_ctx* ctx, int64_t out[4]);
  * after a change of Pr_t and, while the term is on, of the law or its parameters; it is then formed again with the
  * level's own data.  NSFEM_ERR_ARG: any other value, contexts with a communicator.
  * With the term on, nsfem_step_scalar_imex and nsfem_scalar_explicit refuse (NSFEM_ERR_ARG, state untouched) unless the
- * viscosity law is 1: law 0 and Carreau are errors, not molecular runs.  nsfem_wall_compute with use_law and law 1 forms
- * its conductive heat row with kappa + nu_x / Pr_t; with the term off that row keeps its bytes. */
+ * viscosity law is 1, 4 or 5: law 0 and Carreau are errors, not molecular runs.  nsfem_wall_compute with use_law and
+ * one of these laws forms its conductive heat row with kappa + nu_x / Pr_t; with the term off that row keeps its bytes. */
 int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t);
 /* Test hook: out_host [n_p2] = what ONE launch of the step forms for a level, weight [C(u) T + D(u, T) (+ H(T))] -- D
  * while the term is on, H while a body is thermal (pose of t^(n-1) for scalar_slot NSFEM_T2, of t^n otherwise).  It
@@ -512,7 +513,7 @@ int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t);
  * nsfem_scalar_convection, which keeps returning C(u) T alone. */
 int nsfem_scalar_explicit(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
                           double* out_host);
-/* out = {1 while the term is on else 0, launches of the SGS = 1 kernels, stored vectors formed again because Pr_t or
+/* out = {1 while the term is on else 0, launches of the SGS != 0 kernels, stored vectors formed again because Pr_t or
  * (with the term on) the law changed, 0} */
 int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]);
 /* ---- variable viscosity in the IMEX step (new; the reference knows one constant viscosity).  nu = c_v + nu_x(gamma,
@@ -527,6 +528,19 @@ int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]);
  *   law 1  Smagorinsky  nu_x = (C_s Delta_K)^2 gamma                         params = {C_s >= 0}
  *   law 2  Carreau      nu_x = a [ (1 + (lambda gamma)^2)^((n-1)/2) - 1 ]    params = {a finite, lambda >= 0, n > 0};
  *          c_v is the zero-shear viscosity, a = c_v - nu_inf
+ *   law 4  WALE (Nicoud & Ducros 1999)                                       params = {C_w finite and >= 0}
+ *          S = 1/2 (G + G^T), H = G G (matrix square), Sd = 1/2 (H + H^T) - (tr H / 3) I_3, A = S:S, B = Sd:Sd summed
+ *          entry by entry (never as sym(H):sym(H) - tr^2/3, which cancels):
+ *          nu_x = (C_w Delta_K)^2 B sqrt(B) / (A^2 sqrt(A) + B sqrt(sqrt(B))), 0 wherever the denominator is not > 0.
+ *          The fractional powers are products and sqrt, not pow.  Zero in pure shear, O(y^3) at a wall
+ *   law 5  Vreman (2004)                                                     params = {c finite and >= 0}, c ~ 2.5 C_s^2
+ *          B_beta = the sum of the squares of all 2x2 minors of G (nine in 3D; one, det G, in 2D) -- by Cauchy-Binet
+ *          the second invariant of alpha^T alpha of the paper, non-negative by construction, no clamp, no cancellation:
+ *          nu_x = c Delta_K^2 sqrt(B_beta / G:G), 0 where G:G is not > 0.  Zero in pure shear, O(y) at a wall
+ * Laws 4 and 5 take the whole tensor G_ab = g_ab = d_b u_a, not gamma alone.  A 2D field counts as the 3D field that
+ * does not depend on z: G is the 3x3 tensor with a zero third row and column (so Sd_33 = -tr H / 3 is kept in B).
+ * V(u), the cell means, the stored vectors and the explicit treatment are those of laws 1 and 2 with this nu_x.  There
+ * is no law 3: ids 3 and 6 and above are unknown.
  * A change of law or parameters invalidates the stored vectors.  NSFEM_ERR_ARG: unknown law, parameters outside these
  * ranges or not finite, a law other than 0 on contexts with a communicator; nsfem_step_ipcs and nsfem_step_bdf refuse
  * to run while a law other than 0 is set. */

@@ -581,8 +581,8 @@ class NsfemContext:
 
     # -- subgrid heat flux in the scalar step ---------------------------------------------
     def set_scalar_sgs(self, prandtl_t):
-        """turbulent Prandtl number of the subgrid heat flux kappa_x = nu_x / Pr_t (Smagorinsky law, set_viscosity_law
-        1): 0 switches the term off (step_scalar_imex runs exactly as without this call), a finite value > 0 on"""
+        """turbulent Prandtl number of the subgrid heat flux kappa_x = nu_x / Pr_t (a subgrid law of
+        set_viscosity_law: 1 Smagorinsky, 4 WALE, 5 Vreman): 0 switches the term off (step_scalar_imex runs exactly as without this call), a finite value > 0 on"""
         self._check(self._lib.nsfem_set_scalar_sgs(self._h, float(prandtl_t)))
 
     def scalar_explicit(self, velocity_slot=U1, scalar_slot=T1, form=0, weight=1.0):
@@ -603,7 +603,8 @@ class NsfemContext:
     # -- variable viscosity in the IMEX step ---------------------------------------------
     def set_viscosity_law(self, law, params=None):
         """law 0 none (step_imex runs exactly as without this call), 1 Smagorinsky params = (C_s, ), 2 Carreau
-        params = (a, lambda, n); up to four numbers, the rest are zeros"""
+        params = (a, lambda, n), 4 WALE params = (C_w, ), 5 Vreman params = (c, ) -- the last two from the whole
+        velocity-gradient tensor (include/nsfem.h); 3 is no law; up to four numbers, the rest are zeros"""
         p = np.zeros(4, dtype=np.float64)
         if params is not None:
             given = np.asarray(params, dtype=np.float64).ravel()

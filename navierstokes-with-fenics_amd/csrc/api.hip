@@ -2801,7 +2801,8 @@ extern "C" int nsfem_imex_rotation_info(nsfem_ctx* ctx, int64_t out[4]) {
 extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double params[4]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
-  NSFEM_REQUIRE(law >= 0 && law <= 2, "variable viscosity: unknown law (0 none, 1 Smagorinsky, 2 Carreau)");
+  NSFEM_REQUIRE((law >= 0 && law <= 2) || law == 4 || law == 5,
+                "variable viscosity: unknown law (0 none, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman)");
   NSFEM_REQUIRE(law == 0 || !ctx->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(law == 0 || params, "variable viscosity: the law needs its parameters");
@@ -2816,6 +2817,12 @@ extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double par
     p[0] = params[0];
     p[1] = params[1];
     p[2] = params[2];
+  } else if (law == 4) {
+    NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] >= 0.0, "WALE: C_w must be finite and >= 0");
+    p[0] = params[0];
+  } else if (law == 5) {
+    NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] >= 0.0, "Vreman: c must be finite and >= 0");
+    p[0] = params[0];
   }
   nsfem_ctx::Viscosity& v = ctx->visc;
   // (the stored explicit vectors belong to the law and parameters they were evaluated with; the law enters no
@@ -3148,8 +3155,9 @@ extern "C" int nsfem_set_scalar(nsfem_ctx* ctx, double diffusivity, const double
   API_END(ctx)
 }
 
-// Subgrid heat flux: kappa_x = nu_x / Pr_t of the Smagorinsky law under the gradients of the scalar, explicit, inside
-// the convection launch (k_scalar_conv_cell<FORM, PENAL, 1>).  kappa K stays in the matrix: no rebuild, no new solve
+// Subgrid heat flux: kappa_x = nu_x / Pr_t of the subgrid law (1 Smagorinsky, 4 WALE, 5 Vreman) under the gradients of
+// the scalar, explicit, inside the convection launch (k_scalar_conv_cell<FORM, PENAL, law>).  kappa K stays in the
+// matrix: no rebuild, no new solve
 extern "C" int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
@@ -3163,20 +3171,23 @@ extern "C" int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t) {
   API_END(ctx)
 }
 
-// what the convection launches take: C_s of the viscosity law and 1 / Pr_t while the term is on, nothing otherwise
+// what the convection launches take: the law, its constant (C_s, C_w, c) and 1 / Pr_t while the term is on, nothing
+// otherwise
 static ScalarSgsArgs scalar_sgs_args(const nsfem_ctx* c) {
   ScalarSgsArgs a;
   if (c->sc.prandtl_t > 0.0) {
-    a.cs = c->visc.p[0];
+    a.c0 = c->visc.p[0];
     a.inv_prt = 1.0 / c->sc.prandtl_t;
-    a.active = 1;
+    a.law = c->visc.law;
   }
   return a;
 }
 
 static void scalar_sgs_require_law(const nsfem_ctx* c) {
-  NSFEM_REQUIRE(c->sc.prandtl_t == 0.0 || c->visc.law == 1,
-                "subgrid heat flux: Pr_t is set but the viscosity law is not 1 (Smagorinsky, nsfem_set_viscosity_law)");
+  const int law = c->visc.law;
+  NSFEM_REQUIRE(c->sc.prandtl_t == 0.0 || law == 1 || law == 4 || law == 5,
+                "subgrid heat flux: Pr_t is set but the viscosity law is not 1 (Smagorinsky), 4 (WALE) or 5 (Vreman) "
+                "(nsfem_set_viscosity_law)");
 }
 
 // A = alpha0/k M + gamma0 kappa K, rebuilt only when one of the three numbers changed
@@ -3243,8 +3254,8 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   // Heated bodies (nsfem_set_body_temperatures, at least one flag 1): the same launches form C(u) T + H(T), with the
   // pose of the level (cur for T1, prev for a T2 vector formed afresh); the stored vectors are stale after a change
   // of the thermal table or, while a body is thermal, of the body set.  Without a thermal body: the launches of old
-  // Subgrid heat flux (nsfem_set_scalar_sgs, Pr_t > 0): the same launches add D(u, T) (SGS = 1 kernels); the stored
-  // vectors are stale after a change of Pr_t or, while the term is on, of the viscosity law's parameters (C_s)
+  // Subgrid heat flux (nsfem_set_scalar_sgs, Pr_t > 0): the same launches add D(u, T) (SGS = law kernels); the stored
+  // vectors are stale after a change of Pr_t or, while the term is on, of the viscosity law or its parameters
   nsfem_ctx::Bodies& bd = ctx->bodies;
   const bool heated = bd.n_thermal > 0 && bd.cur.n > 0;
   const ScalarSgsArgs sgs = scalar_sgs_args(ctx);
@@ -3252,7 +3263,7 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   if (b1 != 0.0) {
     const bool usable = sc.conv2_valid && sc.conv2_weight != 0.0 && (sc.conv_form == -2 || sc.conv_form == sc.form);
     const bool same_heat = sc.conv_thermal_epoch == bd.thermal_epoch && (!heated || sc.conv_body_epoch == bd.epoch);
-    const bool same_sgs = sc.conv_sgs_epoch == sc.sgs_epoch && (!sgs.active || sc.conv_visc_epoch == ctx->visc.epoch);
+    const bool same_sgs = sc.conv_sgs_epoch == sc.sgs_epoch && (sgs.law == 0 || sc.conv_visc_epoch == ctx->visc.epoch);
     if (usable && same_heat && same_sgs) {
       ++sc.conv_reuses;
     } else {
@@ -3267,7 +3278,7 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
                                  sgs);
       }
       ++sc.conv_launches;
-      if (sgs.active) ++sc.sgs_launches;
+      if (sgs.law != 0) ++sc.sgs_launches;
       sc.conv2_weight = 1.0;
       sc.conv2_valid = true;
     }
@@ -3282,7 +3293,7 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
     launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p, sgs);
   }
   ++sc.conv_launches;
-  if (sgs.active) ++sc.sgs_launches;
+  if (sgs.law != 0) ++sc.sgs_launches;
   sc.conv1_fresh = true;
   sc.conv1_weight = b0;
   sc.conv_form = sc.form;
@@ -3374,7 +3385,7 @@ extern "C" int nsfem_scalar_explicit(nsfem_ctx* ctx, int velocity_slot, int scal
     launch_scalar_convection(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, out,
                              sgs);
   }
-  if (sgs.active) ++ctx->sc.sgs_launches;
+  if (sgs.law != 0) ++ctx->sc.sgs_launches;
   NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
   API_END(ctx)
@@ -4556,8 +4567,10 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   for (int d = 0; d < 3; ++d) wp.origin[d] = opts->origin[d];
   wp.law = opts->use_law != 0 ? ctx->visc.law : 0;
   for (int k = 0; k < 3; ++k) wp.law_p[k] = ctx->visc.p[k];
-  // subgrid heat flux: the conductive row carries kappa + nu_x / Pr_t where the traction carries nu_x (law 1 only)
-  wp.inv_prt = wp.law == 1 && scalar_slot != -1 && ctx->sc.prandtl_t > 0.0 ? 1.0 / ctx->sc.prandtl_t : 0.0;
+  // subgrid heat flux: the conductive row carries kappa + nu_x / Pr_t where the traction carries nu_x (the subgrid
+  // laws 1, 4 and 5 only)
+  const bool subgrid = wp.law == 1 || wp.law == 4 || wp.law == 5;
+  wp.inv_prt = subgrid && scalar_slot != -1 && ctx->sc.prandtl_t > 0.0 ? 1.0 / ctx->sc.prandtl_t : 0.0;
   hipStream_t s = ctx->stream;
   launch_wall_facets(s, m, W.n_facets, W.fcell.p, W.flocal.p, ctx->state[velocity_slot].p, ctx->state[pressure_slot].p,
                      scalar_slot != -1 ? ctx->state[scalar_slot].p : nullptr, wp, W.rows.p);

@@ -789,11 +789,12 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 // x_q the affine image of the reference point, chi and the winner from body_winner (bodies.hpp) as in k_penal_cell;
 // x_q, the winner, chi and T_q are formed once per quadrature point, points with chi = 0 or a passive winner add
 // nothing.  PENAL 0 takes no table at all and is the code of every run without temperatures.
-// SGS 1: subgrid heat flux (nsfem_set_scalar_sgs) -- the same launch adds
-//   wgt sum_q w_q |det J| kappa_x(gamma_q, Delta_K) grad T_q . grad phi_i(x_q),   kappa_x = (C_s Delta_K)^2 gamma / Pr_t
+// SGS 1, 4, 5 (the subgrid law: Smagorinsky, WALE, Vreman): subgrid heat flux (nsfem_set_scalar_sgs) -- the same
+// launch adds
+//   wgt sum_q w_q |det J| kappa_x grad T_q . grad phi_i(x_q),   kappa_x = nu_x / Pr_t   (SGS 1: (C_s Delta_K)^2 gamma / Pr_t)
 // with g_ab = d_b u_a summed from the gradients the point forms anyway, gamma and Delta_K^2 = |det J| / 2 as in
-// k_visc_var_cell and the law visc_law_nu<1> (cell_geometry.hpp).  SGS 0 takes nothing and is the code of every run
-// without the setting.
+// k_visc_var_cell and the law of cell_geometry.hpp (visc_law_nu<1> of gamma, visc_law_nu_grad<4 | 5, 2> of g).  SGS 0
+// takes nothing and is the code of every run without the setting.
 template <int FORM, int PENAL, int SGS = 0>
 __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                           const int32_t* __restrict__ p2,
@@ -863,7 +864,14 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
     if constexpr (SGS != 0) {
       const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T
       const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
-      const double wk = w * (visc_law_nu<1>(gamma, 0.5 * g.adet, sg.cs, 0.0, 0.0) * sg.inv_prt);
+      double nux;
+      if constexpr (SGS == 1) {
+        nux = visc_law_nu<1>(gamma, 0.5 * g.adet, sg.c0, 0.0, 0.0);
+      } else {
+        const double G[2][2] = {{g00, g01}, {g10, g11}};
+        nux = visc_law_nu_grad<SGS, 2>(G, 0.5 * g.adet, sg.c0);
+      }
+      const double wk = w * (nux * sg.inv_prt);
 #pragma unroll
       for (int i = 0; i < 6; ++i) r[i] += wk * (dtx * gx[i] + dty * gy[i]);
     }
@@ -927,11 +935,15 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
 #define NSFEM_SC(F) \
   hipLaunchKernelGGL((k_scalar_conv_cell<F, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
                      ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCS(F) \
-  hipLaunchKernelGGL((k_scalar_conv_cell<F, 0, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-    if (sgs.active) { if (form == 0) NSFEM_SCS(0); else NSFEM_SCS(1); }
+#define NSFEM_SCS(F, L) \
+  hipLaunchKernelGGL((k_scalar_conv_cell<F, 0, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SCSF(L) do { if (form == 0) NSFEM_SCS(0, L); else NSFEM_SCS(1, L); } while (0)
+    if (sgs.law == 1) NSFEM_SCSF(1);
+    else if (sgs.law == 4) NSFEM_SCSF(4);
+    else if (sgs.law == 5) NSFEM_SCSF(5);
     else { if (form == 0) NSFEM_SC(0); else NSFEM_SC(1); }
+#undef NSFEM_SCSF
 #undef NSFEM_SCS
 #undef NSFEM_SC
   }
@@ -951,16 +963,20 @@ void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const doub
 #define NSFEM_SCH(F, P) \
   hipLaunchKernelGGL((k_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
                      ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCHS(F, P) \
-  hipLaunchKernelGGL((k_scalar_conv_cell<F, P, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-    if (sgs.active) {
-      if (bt.eps > 0.0) { if (form == 0) NSFEM_SCHS(0, 2); else NSFEM_SCHS(1, 2); }
-      else { if (form == 0) NSFEM_SCHS(0, 1); else NSFEM_SCHS(1, 1); }
-    } else {
+#define NSFEM_SCHS(F, P, L) \
+  hipLaunchKernelGGL((k_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SCHSF(L) do { \
+      if (bt.eps > 0.0) { if (form == 0) NSFEM_SCHS(0, 2, L); else NSFEM_SCHS(1, 2, L); } \
+      else { if (form == 0) NSFEM_SCHS(0, 1, L); else NSFEM_SCHS(1, 1, L); } } while (0)
+    if (sgs.law == 1) NSFEM_SCHSF(1);
+    else if (sgs.law == 4) NSFEM_SCHSF(4);
+    else if (sgs.law == 5) NSFEM_SCHSF(5);
+    else {
       if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH(0, 2); else NSFEM_SCH(1, 2); }
       else { if (form == 0) NSFEM_SCH(0, 1); else NSFEM_SCH(1, 1); }
     }
+#undef NSFEM_SCHSF
 #undef NSFEM_SCHS
 #undef NSFEM_SCH
   }
@@ -981,6 +997,8 @@ void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, con
 // the integrand is no polynomial):
 //   r_(i,a) = wgt sum_q w_q |det J| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i,   g_ab = d_b u_a,
 //   gamma = sqrt(1/2 sum_ab (g_ab + g_ba)^2),   Delta_K^2 = |det J| / 2
+// LAW 1, 2: nu_x of gamma (visc_law_nu); LAW 4, 5 (WALE, Vreman): nu_x of the tensor g itself (visc_law_nu_grad<LAW, 2>:
+// the 2D field as the z-independent 3D one), cell_geometry.hpp.
 // u at the 6 nodes in registers; the physical gradients, g, gamma and nu_x of a quadrature point are formed once and
 // shared by the 6 test functions.  The element vector goes node-sorted into m.rbuf (ndst, as k_conv_cell); k_visc_gather
 // sums the run of every node in ascending cell order: no atomics, the same state gives the same bytes.
@@ -1020,7 +1038,13 @@ __global__ __launch_bounds__(256) void k_visc_var_cell(int nc, const double* __r
     }
     const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T
     const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
-    const double nu = visc_law_nu<LAW>(gamma, delta2, p0, p1, pp2);
+    double nu;
+    if constexpr (LAW == 4 || LAW == 5) {
+      const double G[2][2] = {{g00, g01}, {g10, g11}};
+      nu = visc_law_nu_grad<LAW, 2>(G, delta2, p0);
+    } else {
+      nu = visc_law_nu<LAW>(gamma, delta2, p0, p1, pp2);
+    }
     if (MEAN) {
       mean += c_q.w[q] * nu;
       wsum += c_q.w[q];
@@ -1070,14 +1094,16 @@ __global__ __launch_bounds__(256) void k_visc_gather(int64_t n_entries, int dim,
 
 void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
                             const double p[4], bool mean) {
-  NSFEM_REQUIRE(law == 1 || law == 2, "variable viscosity: no law set");
+  NSFEM_REQUIRE(law == 1 || law == 2 || law == 4 || law == 5, "variable viscosity: no law set");
   if (m.dim == 3) return viscosity_cells_3d(s, m, u, weight, law, p, mean);
   const dim3 grid(grid_for(m.n_cells)), block(kBlock);
 #define NSFEM_VV(L, M) \
   hipLaunchKernelGGL((k_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], p[2], \
                      m.ndst.p, m.rbuf.p)
   if (law == 1) { if (mean) NSFEM_VV(1, true); else NSFEM_VV(1, false); }
-  else { if (mean) NSFEM_VV(2, true); else NSFEM_VV(2, false); }
+  else if (law == 2) { if (mean) NSFEM_VV(2, true); else NSFEM_VV(2, false); }
+  else if (law == 4) { if (mean) NSFEM_VV(4, true); else NSFEM_VV(4, false); }
+  else { if (mean) NSFEM_VV(5, true); else NSFEM_VV(5, false); }
 #undef NSFEM_VV
   NSFEM_HIP(hipGetLastError());
 }

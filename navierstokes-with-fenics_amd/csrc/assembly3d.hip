@@ -677,6 +677,7 @@ void convection_action_3d(hipStream_t s, const MeshDev& m, const double* u, cons
 // cell_geometry.hpp), one thread per cell, 15-point rule:
 //   r_(i,a) = wgt sum_q w_q |det J| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i,   g_ab = d_b u_a,
 //   gamma = sqrt(1/2 sum_ab (g_ab + g_ba)^2),   Delta_K = (|det J| / 6)^(1/3)
+// nu_x = visc_law_at<LAW, 3>: of gamma for LAW 1, 2, of the tensor g for LAW 4, 5 (WALE, Vreman).
 // Element vector node-sorted into m.rbuf; the caller sums the node runs (k_visc_gather).
 // MEAN: rbuf[c] = sum_q w_q nu_x(gamma_q) / sum_q w_q instead.
 template <int LAW, bool MEAN>
@@ -716,7 +717,7 @@ __global__ __launch_bounds__(256) void k3_visc_var_cell(int nc, const double* __
     const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
     const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
     const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
-    const double nu = visc_law_nu<LAW>(gamma, delta2, p0, p1, pp2);
+    const double nu = visc_law_at<LAW, 3>(G, gamma, delta2, p0, p1, pp2);
     if constexpr (MEAN) {
       mean += c_q3.w[q] * nu;
       wsum += c_q3.w[q];
@@ -750,7 +751,9 @@ void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double
   hipLaunchKernelGGL((k3_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], \
                      p[2], m.ndst.p, m.rbuf.p)
   if (law == 1) { if (mean) NSFEM_VV3(1, true); else NSFEM_VV3(1, false); }
-  else { if (mean) NSFEM_VV3(2, true); else NSFEM_VV3(2, false); }
+  else if (law == 2) { if (mean) NSFEM_VV3(2, true); else NSFEM_VV3(2, false); }
+  else if (law == 4) { if (mean) NSFEM_VV3(4, true); else NSFEM_VV3(4, false); }
+  else { if (mean) NSFEM_VV3(5, true); else NSFEM_VV3(5, false); }
 #undef NSFEM_VV3
   NSFEM_HIP(hipGetLastError());
 }
@@ -849,9 +852,10 @@ void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double w
 // as they are formed.
 // PENAL 1 / 2: heated bodies, as k_scalar_conv_cell (assembly.hip) -- the same launch adds
 // wgt/eta_T sum_q w_q |det J| chi(x_q) theta_win (T(x_q) - T_win) phi_i(x_q); PENAL 0 takes no table.
-// SGS 1: subgrid heat flux, as k_scalar_conv_cell -- the same launch adds
-// wgt sum_q w_q |det J| kappa_x(gamma_q, Delta_K) grad T_q . grad phi_i(x_q), kappa_x = (C_s Delta_K)^2 gamma / Pr_t,
-// gamma and Delta_K as in k3_visc_var_cell; the gradients of a point are kept in either form then.  SGS 0 takes nothing.
+// SGS 1, 4, 5 (the subgrid law): subgrid heat flux, as k_scalar_conv_cell -- the same launch adds
+// wgt sum_q w_q |det J| kappa_x grad T_q . grad phi_i(x_q), kappa_x = nu_x / Pr_t (SGS 1: (C_s Delta_K)^2 gamma / Pr_t),
+// nu_x (visc_law_at<SGS, 3>) and Delta_K as in k3_visc_var_cell; the gradients of a point are kept in either form then.
+// SGS 0 takes nothing.
 template <int FORM, int PENAL, int SGS = 0>
 __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                            const int32_t* __restrict__ p2,
@@ -925,7 +929,7 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
       const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
       const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
       const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
-      const double wk = w * (visc_law_nu<1>(gamma, delta2, sg.cs, 0.0, 0.0) * sg.inv_prt);
+      const double wk = w * (visc_law_at<SGS, 3>(G, gamma, delta2, sg.c0, 0.0, 0.0) * sg.inv_prt);
 #pragma unroll
       for (int i = 0; i < 10; ++i) r[i] += wk * (dt[0] * gk[i][0] + dt[1] * gk[i][1] + dt[2] * gk[i][2]);
     }
@@ -954,11 +958,15 @@ void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u
 #define NSFEM_SC3(F) \
   hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
                      ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SC3S(F) \
-  hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-  if (sgs.active) { if (form == 0) NSFEM_SC3S(0); else NSFEM_SC3S(1); }
+#define NSFEM_SC3S(F, L) \
+  hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SC3SF(L) do { if (form == 0) NSFEM_SC3S(0, L); else NSFEM_SC3S(1, L); } while (0)
+  if (sgs.law == 1) NSFEM_SC3SF(1);
+  else if (sgs.law == 4) NSFEM_SC3SF(4);
+  else if (sgs.law == 5) NSFEM_SC3SF(5);
   else { if (form == 0) NSFEM_SC3(0); else NSFEM_SC3(1); }
+#undef NSFEM_SC3SF
 #undef NSFEM_SC3S
 #undef NSFEM_SC3
   NSFEM_HIP(hipGetLastError());
@@ -971,16 +979,20 @@ void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const do
 #define NSFEM_SCH3(F, P) \
   hipLaunchKernelGGL((k3_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
                      ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCH3S(F, P) \
-  hipLaunchKernelGGL((k3_scalar_conv_cell<F, P, 1>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<1>{sgs.cs, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-  if (sgs.active) {
-    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3S(0, 2); else NSFEM_SCH3S(1, 2); }
-    else { if (form == 0) NSFEM_SCH3S(0, 1); else NSFEM_SCH3S(1, 1); }
-  } else {
+#define NSFEM_SCH3S(F, P, L) \
+  hipLaunchKernelGGL((k3_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
+                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
+#define NSFEM_SCH3SF(L) do { \
+    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3S(0, 2, L); else NSFEM_SCH3S(1, 2, L); } \
+    else { if (form == 0) NSFEM_SCH3S(0, 1, L); else NSFEM_SCH3S(1, 1, L); } } while (0)
+  if (sgs.law == 1) NSFEM_SCH3SF(1);
+  else if (sgs.law == 4) NSFEM_SCH3SF(4);
+  else if (sgs.law == 5) NSFEM_SCH3SF(5);
+  else {
     if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3(0, 2); else NSFEM_SCH3(1, 2); }
     else { if (form == 0) NSFEM_SCH3(0, 1); else NSFEM_SCH3(1, 1); }
   }
+#undef NSFEM_SCH3SF
 #undef NSFEM_SCH3S
 #undef NSFEM_SCH3
   NSFEM_HIP(hipGetLastError());

@@ -92,4 +92,73 @@ __device__ __forceinline__ double visc_law_nu(double gamma, double delta2, doubl
   }
 }
 
+// Laws of the velocity-gradient tensor G[a][b] = d_b u_a (laws 4 and 5 of nsfem_set_viscosity_law): the ONE copy as
+// above.  A DIM = 2 field is the 3D field that does not depend on z: G has a zero third row and column, which the
+// DIM = 2 instantiations never form.
+//   LAW 4 WALE    (C_w Delta_K)^2 B^(3/2) / (A^(5/2) + B^(5/4))   p0 = C_w
+//                 A = S:S, S = sym G;  B = Sd:Sd, Sd = sym(G G) - tr(G G)/3 I_3, summed entry by entry (in 2D with
+//                 Sd_33 = -tr(G G)/3); 0 where the denominator is not > 0.  Powers by products and sqrt
+//   LAW 5 Vreman  c Delta_K^2 sqrt(B_beta / G:G)                  p0 = c
+//                 B_beta = the sum of the squares of the 2x2 minors of G (nine in 3D, det G in 2D), >= 0 by
+//                 construction; 0 where G:G is not > 0
+template <int LAW, int DIM>
+__device__ __forceinline__ double visc_law_nu_grad(const double (&G)[DIM][DIM], double delta2, double p0) {
+  static_assert(LAW == 4 || LAW == 5, "gradient-tensor laws are 4 (WALE) and 5 (Vreman)");
+  if constexpr (LAW == 4) {
+    double A = 0.0, trh = 0.0;
+    double H[DIM][DIM];                  // H = G G
+#pragma unroll
+    for (int a = 0; a < DIM; ++a)
+#pragma unroll
+      for (int b = 0; b < DIM; ++b) {
+        const double s = 0.5 * (G[a][b] + G[b][a]);
+        A += s * s;
+        double h = 0.0;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) h += G[a][k] * G[k][b];
+        H[a][b] = h;
+      }
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) trh += H[a][a];
+    const double t3 = trh / 3.0;
+    double B = DIM == 2 ? t3 * t3 : 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a)
+#pragma unroll
+      for (int b = 0; b < DIM; ++b) {
+        const double sd = 0.5 * (H[a][b] + H[b][a]) - (a == b ? t3 : 0.0);
+        B += sd * sd;
+      }
+    const double den = A * A * sqrt(A) + B * sqrt(sqrt(B));
+    return den > 0.0 ? (p0 * p0 * delta2) * (B * sqrt(B) / den) : 0.0;
+  } else {
+    double gg = 0.0, bb = 0.0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a)
+#pragma unroll
+      for (int b = 0; b < DIM; ++b) gg += G[a][b] * G[a][b];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a)
+#pragma unroll
+      for (int a2 = a + 1; a2 < DIM; ++a2)
+#pragma unroll
+        for (int b = 0; b < DIM; ++b)
+#pragma unroll
+          for (int b2 = b + 1; b2 < DIM; ++b2) {
+            const double mnr = G[a][b] * G[a2][b2] - G[a][b2] * G[a2][b];
+            bb += mnr * mnr;
+          }
+    return gg > 0.0 ? (p0 * delta2) * sqrt(bb / gg) : 0.0;
+  }
+}
+
+// nu_x of any law at a point: laws 1 and 2 from the shear rate alone (nothing of G is touched in their
+// instantiations), laws 4 and 5 from the tensor
+template <int LAW, int DIM>
+__device__ __forceinline__ double visc_law_at(const double (&G)[DIM][DIM], double gamma, double delta2, double p0,
+                                              double p1, double p2) {
+  if constexpr (LAW == 4 || LAW == 5) return visc_law_nu_grad<LAW, DIM>(G, delta2, p0);
+  else return visc_law_nu<LAW>(gamma, delta2, p0, p1, p2);
+}
+
 }  // namespace nsfem

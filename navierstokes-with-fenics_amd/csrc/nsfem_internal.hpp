@@ -475,18 +475,19 @@ void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u
 // scalar transport (nsfem_step_scalar_imex): out = weight * C(u) T for the P2 scalar T on the velocity nodes, form 0
 // standard C_ij = int (u . grad phi_j) phi_i, 1 skew-symmetric 1/2 (C - C^T) -- element kernel (k_scalar_conv_cell /
 // k3_scalar_conv_cell, node-sorted element vectors in m.rbuf) plus the per-node sums in ascending cell order.
-// Subgrid heat flux (nsfem_set_scalar_sgs): the launchers take ScalarSgsArgs by value.  active: the same launch adds
-// D(u, T), the Smagorinsky eddy diffusivity kappa_x = (cs Delta_K)^2 gamma inv_prt under the gradients (the SGS = 1
-// instantiations), out = weight (C(u) T + D(u, T)); not active: the SGS = 0 kernels, which take nothing
+// Subgrid heat flux (nsfem_set_scalar_sgs): the launchers take ScalarSgsArgs by value.  law 1, 4 or 5 (Smagorinsky,
+// WALE, Vreman): the same launch adds D(u, T), the eddy diffusivity kappa_x = nu_x inv_prt of that law with its
+// constant c0 (C_s, C_w, c) under the gradients (the SGS = law instantiations), out = weight (C(u) T + D(u, T));
+// law 0: the term is off, the SGS = 0 kernels, which take nothing
 struct ScalarSgsArgs {
-  double cs = 0.0, inv_prt = 0.0;
-  int32_t active = 0;
+  double c0 = 0.0, inv_prt = 0.0;
+  int32_t law = 0;
   int32_t pad_ = 0;
 };
-// ... and what the kernels take: the two numbers with SGS = 1, nothing at all with SGS = 0
+// ... and what the kernels take: the two numbers with SGS != 0, nothing at all with SGS = 0
 template <int SGS>
 struct ScalarSgsKernelArgs {
-  double cs, inv_prt;
+  double c0, inv_prt;
 };
 template <>
 struct ScalarSgsKernelArgs<0> {};
@@ -494,7 +495,7 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
                               int form, double* out, ScalarSgsArgs sgs = ScalarSgsArgs{});
 void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
                                 int form, ScalarSgsArgs sgs);
-// variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, p = params): the element kernel
+// variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman, p = params): the element kernel
 // k_visc_var_cell / k3_visc_var_cell on the velocity u, element vectors weight * V_K(u) node-sorted into m.rbuf --
 // mean: the cell means of nu_x into the first n_cells doubles of m.rbuf instead
 void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
@@ -660,9 +661,9 @@ void launch_spec_bin(hipStream_t s, const double* w, int32_t n_chunks, const int
 inline int wall_components(int dim) { return dim == 2 ? 9 : 13; }
 struct WallParams {
   double nu = 0.0, sym = 0.0, kappa = 0.0, origin[3] = {0.0, 0.0, 0.0};
-  int law = 0;                               // 0: constant viscosity; 1, 2: + nu_x of visc_law_nu<law>
+  int law = 0;                               // 0: constant viscosity; 1, 2, 4, 5: + nu_x of visc_law_at<law>
   double law_p[3] = {0.0, 0.0, 0.0};
-  double inv_prt = 0.0;                      // law 1 and != 0: the heat row uses kappa + nu_x inv_prt (subgrid heat flux)
+  double inv_prt = 0.0;                      // law 1, 4, 5 and != 0: the heat row uses kappa + nu_x inv_prt (subgrid heat flux)
 };
 // ONE launch: rows[f][NW] of the nf facets (fcell, flocal: device lists); T may be null (no scalar: +0.0 entries)
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
@@ -1193,7 +1194,7 @@ struct nsfem_ctx {
     int64_t rhs = 0, recomputed = 0;
   } imex_rot;
   double conv_n_gam[3] = {0.0, 0.0, 0.0};
-  // variable viscosity (nsfem_set_viscosity_law): law 0 none, 1 Smagorinsky, 2 Carreau.  With a law the stored
+  // variable viscosity (nsfem_set_viscosity_law): law 0 none, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman.  With a law the stored
   // vectors N1, N2 are c_c conv(u) + V(u); `epoch` counts the changes of law or parameters, conv_n_visc is the epoch
   // the stored vectors belong to
   struct Viscosity {

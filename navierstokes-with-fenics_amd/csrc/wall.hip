@@ -11,8 +11,9 @@
 //
 // Facet rules as in k_boundary_force: the 2-point Gauss rule on an edge, the 3 edge midpoints on a face.  grad u, p
 // and grad T are linear on an affine facet, u.n and T quadratic, (x - x0) x t quadratic: the rules are exact for
-// every integrand when LAW = 0.  With a law, nu_x(gamma, Delta_K) is evaluated at the points of the rule and the
-// rule is part of the definition (as the degree-5 rule is for nsfem_viscosity_cells).
+// every integrand when LAW = 0.  With a law, nu_x (of gamma and Delta_K for laws 1 and 2, of the gradient tensor for
+// laws 4 and 5: cell_geometry.hpp) is evaluated at the points of the rule and the rule is part of the
+// definition (as the degree-5 rule is for nsfem_viscosity_cells).
 #include "cell_geometry.hpp"
 
 namespace nsfem {
@@ -46,7 +47,7 @@ __device__ __forceinline__ void wall_p2_at(const double* lam, const double (*gl)
 //   [1 + DIM .. 2 DIM]        int [ nu (G + sym G^T) + nu_x (G + G^T) ] n        G_ab = d_b u_a
 //   [1 + 2 DIM]               int u.n
 //   [2 + 2 DIM]               int T                  (+0.0 without a scalar)
-//   [3 + 2 DIM]               int -kappa grad T . n  (+0.0 without a scalar); with LAW = 1 and ipr = 1 / Pr_t != 0
+//   [3 + 2 DIM]               int -kappa grad T . n  (+0.0 without a scalar); with LAW = 1, 4, 5 and ipr = 1 / Pr_t != 0
 //                             (subgrid heat flux, nsfem_set_scalar_sgs): int -(kappa + nu_x ipr) grad T . n
 //   [4 + 2 DIM ..]            int (x - x0) x t, t the sum of the two traction integrands (2D: the z component)
 // n = the unit normal pointing out of the facet's cell.
@@ -203,7 +204,16 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
           const double s = G[a][b] + G[b][a];
           ss += s * s;
         }
-      nux = visc_law_nu<LAW>(sqrt(0.5 * ss), delta2, lp0, lp1, lp2);
+      if constexpr (LAW == 4 || LAW == 5) {
+        double Gd[DIM][DIM];                            // the DIM x DIM block the tensor laws take
+#pragma unroll
+        for (int a = 0; a < DIM; ++a)
+#pragma unroll
+          for (int b = 0; b < DIM; ++b) Gd[a][b] = G[a][b];
+        nux = visc_law_nu_grad<LAW, DIM>(Gd, delta2, lp0);
+      } else {
+        nux = visc_law_nu<LAW>(sqrt(0.5 * ss), delta2, lp0, lp1, lp2);
+      }
     }
     double tr[3] = {0.0, 0.0, 0.0};                     // traction at the point
     double hq = 0.0;
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
       hq += gT[a] * nrm[a];
     }
     sT += w * Tq;
-    if (LAW == 1 && ipr != 0.0) heat += w * (-(kappa + nux * ipr) * hq);
+    if ((LAW == 1 || LAW == 4 || LAW == 5) && ipr != 0.0) heat += w * (-(kappa + nux * ipr) * hq);
     else heat += w * (-kappa * hq);
     if (DIM == 2) {
       tq[0] += w * (r[0] * tr[1] - r[1] * tr[0]);
@@ -289,12 +299,15 @@ static void launch_wall_facets_t(hipStream_t s, const MeshDev& m, int nf, const 
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
                         const double* u, const double* p, const double* T, const WallParams& w, double* rows) {
   if (nf <= 0) return;
-  NSFEM_REQUIRE(w.law >= 0 && w.law <= 2, "wall quantities: unknown viscosity law");
+  NSFEM_REQUIRE((w.law >= 0 && w.law <= 2) || w.law == 4 || w.law == 5, "wall quantities: unknown viscosity law");
   using Fn = void (*)(hipStream_t, const MeshDev&, int, const int32_t*, const int32_t*, const double*, const double*,
                       const double*, const WallParams&, double*);
-  static const Fn table[2][3] = {
-      {launch_wall_facets_t<2, 0>, launch_wall_facets_t<2, 1>, launch_wall_facets_t<2, 2>},
-      {launch_wall_facets_t<3, 0>, launch_wall_facets_t<3, 1>, launch_wall_facets_t<3, 2>}};
+  // (law 3 is no law: its column is never taken)
+  static const Fn table[2][6] = {
+      {launch_wall_facets_t<2, 0>, launch_wall_facets_t<2, 1>, launch_wall_facets_t<2, 2>, nullptr,
+       launch_wall_facets_t<2, 4>, launch_wall_facets_t<2, 5>},
+      {launch_wall_facets_t<3, 0>, launch_wall_facets_t<3, 1>, launch_wall_facets_t<3, 2>, nullptr,
+       launch_wall_facets_t<3, 4>, launch_wall_facets_t<3, 5>}};
   table[m.dim == 3][w.law](s, m, nf, fcell, flocal, u, p, T, w, rows);
   NSFEM_HIP(hipGetLastError());
 }

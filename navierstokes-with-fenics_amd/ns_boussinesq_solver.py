@@ -23,7 +23,8 @@ H(T) = (chi / eta_scalar) (T - T_s) to the transport step, inside the convection
 The solver pushes the temperatures wherever it pushes the bodies and holds k / eta_scalar to the same
 stability test as k / eta.
 
-Subgrid heat flux: a ``viscosity_models.SmagorinskyModel(cs, prandtl_t)`` adds the explicit term D(u, T) with the
+Subgrid heat flux: a subgrid model of ``viscosity_models`` with a turbulent Prandtl number --
+``SmagorinskyModel(cs, prandtl_t)``, ``WALEModel(cw, prandtl_t)`` or ``VremanModel(c, prandtl_t)`` -- adds the explicit term D(u, T) with the
 eddy diffusivity kappa_x = nu_x / prandtl_t to the transport step, inside the same convection launch (DESIGN.md
 4r).  The solver pushes prandtl_t wherever it pushes the viscosity model and the scalar coefficients; a model
 without prandtl_t, or no model, pushes 0 (off).  The term is explicit: unconditionally stable only while kappa_x <

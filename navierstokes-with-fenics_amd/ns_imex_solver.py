@@ -65,7 +65,7 @@ class IMEXIPCSSolver(InstationarySolverBase):
         self.last_step_info = None
 
     def set_viscosity_model(self, model):
-        """a model of ``viscosity_models`` (``SmagorinskyModel``, ``CarreauModel``) or None for the constant
+        """a model of ``viscosity_models`` (``SmagorinskyModel``, ``WALEModel``, ``VremanModel``, ``CarreauModel``) or None for the constant
         viscosity.  Its parameters are formed from the equation coefficients, so it is pushed to the device again
         whenever they change; partitioned meshes are refused by the device driver."""
         assert model is None or (hasattr(model, "law_id") and hasattr(model, "params"))

@@ -9,6 +9,23 @@ equation coefficients where the model needs them -- and goes to ``IMEXIPCSSolver
 import math
 
 LAW_NONE, LAW_SMAGORINSKY, LAW_CARREAU = 0, 1, 2
+LAW_WALE, LAW_VREMAN = 4, 5          # (3 is no law)
+
+
+def _checked_constant(model, name, value):
+    value = float(value)
+    if not (math.isfinite(value) and value >= 0.0):
+        raise ValueError("%s: %s must be finite and >= 0, got %r" % (model, name, value))
+    return value
+
+
+def _checked_prandtl_t(model, prandtl_t):
+    if prandtl_t is None:
+        return None
+    prandtl_t = float(prandtl_t)
+    if not (math.isfinite(prandtl_t) and prandtl_t > 0.0):
+        raise ValueError("%s: prandtl_t must be finite and > 0, got %r" % (model, prandtl_t))
+    return prandtl_t
 
 
 class SmagorinskyModel:
@@ -31,6 +48,35 @@ class SmagorinskyModel:
 
     def params(self, coefficients=None):
         return (self.cs, 0.0, 0.0, 0.0)
+
+
+class WALEModel:
+    """nu_x = (C_w Delta_K)^2 (Sd:Sd)^(3/2) / ((S:S)^(5/2) + (Sd:Sd)^(5/4)): the wall-adapting local eddy viscosity of
+    Nicoud & Ducros (1999) with the constant ``cw`` >= 0; S = sym G, Sd the traceless symmetric part of G G,
+    G_ab = d_b u_a (law 4 of ``nsfem_set_viscosity_law``).  Zero in pure shear, O(y^3) at a wall.  ``prandtl_t`` as in
+    ``SmagorinskyModel``."""
+    law_id = LAW_WALE
+
+    def __init__(self, cw, prandtl_t=None):
+        self.cw = _checked_constant("WALEModel", "cw", cw)
+        self.prandtl_t = _checked_prandtl_t("WALEModel", prandtl_t)
+
+    def params(self, coefficients=None):
+        return (self.cw, 0.0, 0.0, 0.0)
+
+
+class VremanModel:
+    """nu_x = c Delta_K^2 sqrt(B_beta / G:G): the eddy viscosity of Vreman (2004) with the constant ``c`` >= 0
+    (c ~ 2.5 C_s^2); B_beta is the sum of the squares of the 2x2 minors of G_ab = d_b u_a (law 5 of
+    ``nsfem_set_viscosity_law``).  Zero in pure shear, O(y) at a wall.  ``prandtl_t`` as in ``SmagorinskyModel``."""
+    law_id = LAW_VREMAN
+
+    def __init__(self, c, prandtl_t=None):
+        self.c = _checked_constant("VremanModel", "c", c)
+        self.prandtl_t = _checked_prandtl_t("VremanModel", prandtl_t)
+
+    def params(self, coefficients=None):
+        return (self.c, 0.0, 0.0, 0.0)
 
 
 class CarreauModel:
