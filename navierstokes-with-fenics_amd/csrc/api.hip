@@ -56,6 +56,31 @@ static void ensure_scalar_slot(nsfem_ctx* c, int slot) {
   c->state[slot].zero(c->stream);
 }
 
+// what the test hooks of the explicit terms check about their arguments
+static void require_velocity_slot(int slot) {
+  NSFEM_REQUIRE(slot == NSFEM_U0 || slot == NSFEM_U1 || slot == NSFEM_U2 || slot == NSFEM_USTAR,
+                "velocity_slot is not a velocity slot");
+}
+static void require_scalar_slot(int slot) {
+  NSFEM_REQUIRE(slot >= NSFEM_T0 && slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
+}
+static void require_scalar_form(int form) {
+  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
+}
+static void require_finite_weight(double weight) { NSFEM_REQUIRE(std::isfinite(weight), "bad weight"); }
+
+// ... and how they return a vector: fill(out) runs on a work vector of the Krylov solvers (no slot and none of the
+// step's buffers is written), n doubles of it go to the host
+template <class Fill>
+static void hook_to_host(nsfem_ctx* c, int64_t n, double* out_host, Fill&& fill) {
+  c->kw.ensure(nvel(c));
+  ++c->kw.touch;
+  double* out = c->kw.q.p;
+  fill(out);
+  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  NSFEM_HIP(hipStreamSynchronize(c->stream));
+}
+
 static HaloRange to_halo(const nsfem_halo& h) {
   HaloRange r;
   r.send_up_off = h.send_up_off; r.send_up_cnt = h.send_up_cnt;
@@ -591,16 +616,14 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   // ... and on partitioned meshes the ghost entries of a slot written from the host are whatever the caller put there
   if (slot == NSFEM_U1) ctx->u1_ghost_fresh = false;
   if (slot == NSFEM_U2) ctx->u2_ghost_fresh = false;
-  if (slot == NSFEM_CONV_N2) { ctx->conv_n2_valid = true; ctx->conv_n_form = -2; }   // (the caller vouches for it)
+  if (slot == NSFEM_CONV_N2) { ctx->conv_n2_valid = true; ctx->conv_key.vouched = true; }   // (the caller vouches for it)
   // scalar transport: the stored convection vectors follow the levels (velocity and scalar) they were evaluated at
   if (slot == NSFEM_U1 || slot == NSFEM_T1 || slot == NSFEM_TCONV_1) ctx->sc.conv1_fresh = false;
   if (slot == NSFEM_U2 || slot == NSFEM_T2) ctx->sc.conv2_valid = false;
   if (slot == NSFEM_TCONV_2) {
-    ctx->sc.conv2_valid = true; ctx->sc.conv2_weight = 1.0; ctx->sc.conv_form = -2;
-    ctx->sc.conv_thermal_epoch = ctx->bodies.thermal_epoch;
-    ctx->sc.conv_body_epoch = ctx->bodies.epoch;
-    ctx->sc.conv_sgs_epoch = ctx->sc.sgs_epoch;
-    ctx->sc.conv_visc_epoch = ctx->visc.epoch;
+    ctx->sc.conv2_valid = true; ctx->sc.conv2_weight = 1.0;
+    ctx->sc.conv_key = nsfem_ctx::Scalar::Key::of(*ctx);
+    ctx->sc.conv_key.vouched = true;
   }
   if (slot == NSFEM_T_SOURCE) ctx->sc.have_source = true;
   API_END(ctx)
@@ -2560,27 +2583,47 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
   return 1;
 }
 
-// Variable viscosity (nsfem_set_viscosity_law): the stored explicit vector is N(u) = c_c conv(u) + V(u).  imex_rhs runs
-// unchanged on either path; then, BEFORE the Dirichlet rows are set, TWO more launches: the element kernel on u
-// (weight 1, element vectors node-sorted in mesh.rbuf) and k_visc_gather, which forms v = the per-node sums from zero in
-// ascending cell order and then, per entry,  n1 <- n1 + v,  rhs <- rhs - b0 v  (two roundings, no contraction).  That
-// is the summation order with a law set: rhs = [ -(t + (b0 c_c conv(u1) + b1 N2)) ] - b0 V(u1), the bracket as imex_rhs
-// leaves it.  N2 is read as stored (it already holds V(u2)); where it is computed afresh, V(u2) is added the same way
-// with rhs = null.  With law 0 nothing is launched.
-static void viscosity_add(nsfem_ctx* c, const double* u, double b0, double* n1, double* rhs) {
-  launch_viscosity_cells(c->stream, c->mesh, u, 1.0, c->visc.law, c->visc.p, false);
-  launch_viscosity_gather(c->stream, c->mesh, b0, n1, rhs);
-  ++c->visc.launches;
+// The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u).  The convective part
+// (with the Coriolis vector of the level) is in `n` already -- imex_rhs for u1, imex_form_n2 for u2; this adds the rest,
+// V (nsfem_set_viscosity_law) first and B (nsfem_set_bodies) second, each only when switched on: with law 0 / without
+// bodies nothing is launched.  Each term is TWO launches, after imex_rhs (which runs unchanged on either path) and
+// BEFORE the Dirichlet rows are set: the element kernel on u (weight 1, element vectors node-sorted in mesh.rbuf) and
+// k_visc_gather, which forms v = the per-node sums from zero in ascending cell order and then, per entry,
+// n <- n + v,  rhs <- rhs - b0 v  (two roundings, no contraction).  So with a law and bodies the order is viscosity
+// cells, gather, penalisation cells, gather, and the summation order is
+//   rhs = [ [ -(t + (b0 c_c conv(u1) + b1 N2)) ] - b0 V(u1) ] - b0 B(u1),   the inner bracket as imex_rhs leaves it.
+// level_n: u is the level n (u1; the bodies' pose `cur`), else n-1 (u2; `prev`).  N2 is read as stored (it already
+// holds V(u2) + B(u2)); where it is formed afresh the terms are added the same way with b0 = 0 and rhs = null.
+static void imex_explicit_add(nsfem_ctx* c, const double* u, bool level_n, double b0, double* n, double* rhs) {
+  if (c->visc.law != 0) {
+    launch_viscosity_cells(c->stream, c->mesh, u, 1.0, c->visc.law, c->visc.p, false);
+    launch_viscosity_gather(c->stream, c->mesh, b0, n, rhs);
+    ++c->visc.launches;
+  }
+  if (c->bodies.cur.n != 0) {
+    launch_penalty_cells(c->stream, c->mesh, u, 1.0, level_n ? c->bodies.cur : c->bodies.prev, false);
+    launch_viscosity_gather(c->stream, c->mesh, b0, n, rhs);
+    ++c->bodies.launches;
+  }
 }
 
-// Immersed bodies (nsfem_set_bodies): the stored explicit vector gains B(u).  As viscosity_add, after it: the element
-// kernel on u (weight 1, element vectors node-sorted in mesh.rbuf) and k_visc_gather, n1 <- n1 + v, rhs <- rhs - b0 v.
-// So with a law and bodies the order is viscosity cells, gather, penalisation cells, gather.  bt: the pose that
-// belongs to the level of u (cur for u1, prev for a recomputed N(u2)).  Without bodies nothing is launched.
-static void penalty_add(nsfem_ctx* c, const BodyTable& bt, const double* u, double b0, double* n1, double* rhs) {
-  launch_penalty_cells(c->stream, c->mesh, u, 1.0, bt, false);
-  launch_viscosity_gather(c->stream, c->mesh, b0, n1, rhs);
-  ++c->bodies.launches;
+// n2 <- N(u2) from scratch (nsfem_step_imex where the stored N2 does not serve; nsfem_imex_rhs always).  gam2: the
+// 2 c_cor Omega(t^(n-1)), null without rotation at that level
+static void imex_form_n2(nsfem_ctx* c, const double* gam2, double* n2) {
+  const double cc = cc_of(c);
+  NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nvel(c), c->stream));
+  if (cc != 0.0 || gam2) launch_convection_residual(c->stream, c->mesh, c->state[NSFEM_U2].p, cc, n2, c->conv_form, gam2);
+  imex_explicit_add(c, c->state[NSFEM_U2].p, false, 0.0, n2, nullptr);
+}
+
+nsfem_ctx::ImexKey nsfem_ctx::ImexKey::of(const nsfem_ctx& c, const double gam[3]) {
+  ImexKey k;
+  k.form = c.conv_form;
+  k.cc = cc_of(&c);
+  k.visc = c.visc.epoch;
+  k.body = c.bodies.epoch;
+  std::memcpy(k.gam, gam, sizeof(k.gam));
+  return k;
 }
 
 static void imex_require_supported(nsfem_ctx* c) {
@@ -2619,7 +2662,6 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   imex_require_supported(ctx);
   hipStream_t s = ctx->stream;
   const int64_t nv = nvel(ctx);
-  const double cc = cc_of(ctx);
   // ---- diffusion step: one linear solve
   ensure_imex_ops(ctx);
   imex_begin_step(ctx);
@@ -2628,27 +2670,13 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   const bool rot1 = imex_rotation_gamma(ctx, 0, gam1), rot2 = imex_rotation_gamma(ctx, 1, gam2);
   const double* n2 = nullptr;
   if (ctx->imex_beta[1] != 0.0) {
-    // c_c N(u2): what the previous step stored, unless the level, the form or the coefficient changed under it
-    // (rotating frame: nor the 2 c_cor Omega(t^(n-1)) it was formed with, bit for bit)
-    const bool same_rot = std::memcmp(ctx->conv_n_gam, gam2, sizeof(gam2)) == 0;
-    const bool stored = ctx->conv_n2_valid && (ctx->conv_n_form == -2 ||
-                                               (ctx->conv_n_form == ctx->conv_form && ctx->conv_n_cc == cc &&
-                                                ctx->conv_n_visc == ctx->visc.epoch &&
-                                                ctx->conv_n_body == ctx->bodies.epoch && same_rot));
-    if (!stored) {
-      ctx->state[NSFEM_CONV_N2].zero(s);
-      if (cc != 0.0 || rot2)
-        launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc, ctx->state[NSFEM_CONV_N2].p,
-                                   ctx->conv_form, rot2 ? gam2 : nullptr);
+    // c_c N(u2): what the previous step stored, unless the level or a component of its key changed under it (the
+    // key it must have now is that of the 2 c_cor Omega(t^(n-1)) of this step)
+    if (!(ctx->conv_n2_valid && ctx->conv_key.serves(nsfem_ctx::ImexKey::of(*ctx, gam2)))) {
+      imex_form_n2(ctx, rot2 ? gam2 : nullptr, ctx->state[NSFEM_CONV_N2].p);
       if (ctx->imex_rot.treatment == 1 && ctx->conv_n2_valid) ++ctx->imex_rot.recomputed;
-      if (ctx->visc.law != 0) {
-        viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, ctx->state[NSFEM_CONV_N2].p, nullptr);
-        ++ctx->visc.recomputed;
-      }
-      if (ctx->bodies.cur.n != 0) {
-        penalty_add(ctx, ctx->bodies.prev, ctx->state[NSFEM_U2].p, 0.0, ctx->state[NSFEM_CONV_N2].p, nullptr);
-        ++ctx->bodies.recomputed;
-      }
+      if (ctx->visc.law != 0) ++ctx->visc.recomputed;
+      if (ctx->bodies.cur.n != 0) ++ctx->bodies.recomputed;
       if (ctx->distributed() && ctx->ghost_v.p) launch_zero_ghost(s, nv, ctx->mask_v.p, ctx->state[NSFEM_CONV_N2].p);
       ctx->conv_n2_valid = true;
     }
@@ -2658,17 +2686,9 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
                                  rot1 ? gam1 : nullptr);
   ++(ctx->imex_last_path == 2 ? ctx->imex_lattice_rhs : ctx->imex_generic_rhs);
   if (rot1) ++ctx->imex_rot.rhs;
-  std::memcpy(ctx->conv_n_gam, gam1, sizeof(gam1));
-  if (ctx->visc.law != 0)
-    viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
-  if (ctx->bodies.cur.n != 0)
-    penalty_add(ctx, ctx->bodies.cur, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p,
-                ctx->rhs_v.p);
+  imex_explicit_add(ctx, ctx->state[NSFEM_U1].p, true, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
   ctx->conv_n1_fresh = true;
-  ctx->conv_n_form = ctx->conv_form;
-  ctx->conv_n_cc = cc;
-  ctx->conv_n_visc = ctx->visc.epoch;
-  ctx->conv_n_body = ctx->bodies.epoch;
+  ctx->conv_key = nsfem_ctx::ImexKey::of(*ctx, gam1);       // (the next step's N2: formed with Omega(t^n))
   {
     // Dirichlet rows u*_i = g_i; start vector u1 with the Dirichlet values
     double* x = ctx->state[NSFEM_USTAR].p;
@@ -2751,17 +2771,11 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
   const bool rot1 = imex_rotation_gamma(ctx, 0, gam1), rot2 = imex_rotation_gamma(ctx, 1, gam2);
   if (ctx->imex_beta[1] != 0.0) {
     n2 = ctx->kw.z.p;
-    NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nv, s));
-    if (cc_of(ctx) != 0.0 || rot2)
-      launch_convection_residual(s, ctx->mesh, ctx->state[NSFEM_U2].p, cc_of(ctx), n2, ctx->conv_form,
-                                 rot2 ? gam2 : nullptr);
-    if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U2].p, 0.0, n2, nullptr);
-    if (ctx->bodies.cur.n != 0) penalty_add(ctx, ctx->bodies.prev, ctx->state[NSFEM_U2].p, 0.0, n2, nullptr);
+    imex_form_n2(ctx, rot2 ? gam2 : nullptr, n2);
   }
   imex_rhs(ctx, path, n2, n1, out, u1_travelled, rot1 ? gam1 : nullptr);
   if (rot1) ++ctx->imex_rot.rhs;
-  if (ctx->visc.law != 0) viscosity_add(ctx, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], n1, out);
-  if (ctx->bodies.cur.n != 0) penalty_add(ctx, ctx->bodies.cur, ctx->state[NSFEM_U1].p, ctx->imex_beta[0], n1, out);
+  imex_explicit_add(ctx, ctx->state[NSFEM_U1].p, true, ctx->imex_beta[0], n1, out);
   NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
@@ -2836,27 +2850,22 @@ extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double par
 static void viscosity_require(nsfem_ctx* ctx, int velocity_slot) {
   NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(ctx->visc.law != 0, "variable viscosity: no law set (nsfem_set_viscosity_law)");
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+  require_velocity_slot(velocity_slot);
 }
 
 extern "C" int nsfem_viscosity_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out_host, "null argument");
   viscosity_require(ctx, velocity_slot);
-  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  require_finite_weight(weight);
   hipStream_t s = ctx->stream;
   const int64_t nv = nvel(ctx);
-  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
-  ctx->kw.ensure(nv);
-  ++ctx->kw.touch;
-  double* out = ctx->kw.q.p;
-  NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
-  launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->visc.law, ctx->visc.p, false);
-  launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
-  ++ctx->visc.launches;
-  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  hook_to_host(ctx, nv, out_host, [&](double* out) {
+    NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
+    launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->visc.law, ctx->visc.p, false);
+    launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
+    ++ctx->visc.launches;
+  });
   API_END(ctx)
 }
 
@@ -2986,27 +2995,22 @@ extern "C" int nsfem_move_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bo
 static void bodies_require(nsfem_ctx* ctx, int velocity_slot) {
   NSFEM_REQUIRE(!ctx->comm, "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(ctx->bodies.cur.n != 0, "immersed bodies: no body set (nsfem_set_bodies)");
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
+  require_velocity_slot(velocity_slot);
 }
 
 extern "C" int nsfem_body_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out_host, "null argument");
   bodies_require(ctx, velocity_slot);
-  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
+  require_finite_weight(weight);
   hipStream_t s = ctx->stream;
   const int64_t nv = nvel(ctx);
-  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
-  ctx->kw.ensure(nv);
-  ++ctx->kw.touch;
-  double* out = ctx->kw.q.p;
-  NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
-  launch_penalty_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->bodies.cur, false);
-  launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
-  ++ctx->bodies.launches;
-  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  hook_to_host(ctx, nv, out_host, [&](double* out) {
+    NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
+    launch_penalty_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->bodies.cur, false);
+    launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
+    ++ctx->bodies.launches;
+  });
   API_END(ctx)
 }
 
@@ -3078,7 +3082,22 @@ static void heated_require(nsfem_ctx* ctx, int scalar_slot) {
   NSFEM_REQUIRE(!ctx->comm, "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(ctx->bodies.cur.n != 0, "immersed bodies: no body set (nsfem_set_bodies)");
   NSFEM_REQUIRE(ctx->bodies.have_thermal, "heated bodies: no temperatures set (nsfem_set_body_temperatures)");
-  NSFEM_REQUIRE(scalar_slot >= NSFEM_T0 && scalar_slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
+  require_scalar_slot(scalar_slot);
+}
+
+// The scalar explicit vector of a level in ONE element launch (plus k_scalar_gather):
+//   out = weight [ C(u) T  + D(u, T)  + H(T) ]
+// D (subgrid heat flux, nsfem_set_scalar_sgs) with sgs.law != 0: the SGS = law kernels; H (heated bodies,
+// nsfem_set_body_temperatures with at least one flag 1) with a pose: that of the level -- cur for T1, prev for a T2
+// vector formed afresh -- and the fused PENAL kernels.  pose null and sgs.law 0: the launches of old.
+// in_step: the launch is one of nsfem_step_scalar_imex and counts as a convection launch (the hooks' never did)
+static void scalar_explicit_launch(nsfem_ctx* c, const double* u, const double* T, double weight, int form,
+                                   const BodyTable* pose, double* out, const ScalarSgsArgs& sgs, bool in_step) {
+  const ScalarBodies hb{pose ? *pose : c->bodies.cur, c->bodies.thermal};
+  launch_scalar_convection(c->stream, c->mesh, u, T, weight, form, pose ? &hb : nullptr, out, sgs);
+  if (pose) ++c->bodies.fused_launches;
+  if (in_step) ++c->sc.conv_launches;
+  if (sgs.law != 0) ++c->sc.sgs_launches;
 }
 
 extern "C" int nsfem_body_scalar_residual(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
@@ -3086,22 +3105,15 @@ extern "C" int nsfem_body_scalar_residual(nsfem_ctx* ctx, int velocity_slot, int
   API_BEGIN
   NSFEM_REQUIRE(ctx && out_host, "null argument");
   heated_require(ctx, scalar_slot);
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
-  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
+  require_velocity_slot(velocity_slot);
+  require_scalar_form(form);
   NSFEM_REQUIRE(pose == 0 || pose == 1, "heated bodies: pose must be 0 (t^n) or 1 (t^(n-1))");
-  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
-  hipStream_t s = ctx->stream;
+  require_finite_weight(weight);
   ensure_scalar_slot(ctx, scalar_slot);
-  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
-  ctx->kw.ensure(nvel(ctx));
-  ++ctx->kw.touch;
-  double* out = ctx->kw.q.p;
-  launch_scalar_convection_heated(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form,
-                                  pose == 0 ? ctx->bodies.cur : ctx->bodies.prev, ctx->bodies.thermal, out);
-  ++ctx->bodies.fused_launches;
-  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * ctx->mesh.n_p2, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  hook_to_host(ctx, ctx->mesh.n_p2, out_host, [&](double* out) {
+    scalar_explicit_launch(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form,
+                           pose == 0 ? &ctx->bodies.cur : &ctx->bodies.prev, out, ScalarSgsArgs{}, false);
+  });
   API_END(ctx)
 }
 
@@ -3250,57 +3262,35 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
     launch_spmv_axpy(s, ctx->K2, 1, sc.kappa, tmp, rhs, nullptr);
   }
   // beta1 C(u2) T2: the vector the previous step stored (beta0' C(u1) T1 then), unless a level, a stored vector or
-  // the form changed under it
-  // Heated bodies (nsfem_set_body_temperatures, at least one flag 1): the same launches form C(u) T + H(T), with the
-  // pose of the level (cur for T1, prev for a T2 vector formed afresh); the stored vectors are stale after a change
-  // of the thermal table or, while a body is thermal, of the body set.  Without a thermal body: the launches of old
-  // Subgrid heat flux (nsfem_set_scalar_sgs, Pr_t > 0): the same launches add D(u, T) (SGS = law kernels); the stored
-  // vectors are stale after a change of Pr_t or, while the term is on, of the viscosity law or its parameters
+  // a component of its key changed under it: the form; with heated bodies the thermal table or, while a body is
+  // thermal, the body set; with the subgrid heat flux Pr_t or, while the term is on, the viscosity law or its
+  // parameters.  What the launches form: scalar_explicit_launch
   nsfem_ctx::Bodies& bd = ctx->bodies;
   const bool heated = bd.n_thermal > 0 && bd.cur.n > 0;
   const ScalarSgsArgs sgs = scalar_sgs_args(ctx);
+  const nsfem_ctx::Scalar::Key now = nsfem_ctx::Scalar::Key::of(*ctx);
   double f2 = 0.0;
   if (b1 != 0.0) {
-    const bool usable = sc.conv2_valid && sc.conv2_weight != 0.0 && (sc.conv_form == -2 || sc.conv_form == sc.form);
-    const bool same_heat = sc.conv_thermal_epoch == bd.thermal_epoch && (!heated || sc.conv_body_epoch == bd.epoch);
-    const bool same_sgs = sc.conv_sgs_epoch == sc.sgs_epoch && (sgs.law == 0 || sc.conv_visc_epoch == ctx->visc.epoch);
+    const bool usable = sc.conv2_valid && sc.conv2_weight != 0.0 && sc.conv_key.same_form(now);
+    const bool same_heat = sc.conv_key.same_heat(now, heated), same_sgs = sc.conv_key.same_sgs(now, sgs.law != 0);
     if (usable && same_heat && same_sgs) {
       ++sc.conv_reuses;
     } else {
       if (usable && !same_heat) ++bd.thermal_recomputed;
       if (usable && !same_sgs) ++sc.sgs_recomputed;
-      if (heated) {
-        launch_scalar_convection_heated(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, bd.prev, bd.thermal,
-                                        ctx->state[NSFEM_TCONV_2].p, sgs);
-        ++bd.fused_launches;
-      } else {
-        launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, ctx->state[NSFEM_TCONV_2].p,
-                                 sgs);
-      }
-      ++sc.conv_launches;
-      if (sgs.law != 0) ++sc.sgs_launches;
+      scalar_explicit_launch(ctx, ctx->state[NSFEM_U2].p, T2, 1.0, sc.form, heated ? &bd.prev : nullptr,
+                             ctx->state[NSFEM_TCONV_2].p, sgs, true);
       sc.conv2_weight = 1.0;
       sc.conv2_valid = true;
     }
     f2 = b1 / sc.conv2_weight;
   }
   // beta0 C(u1) T1: beta0 rides in the kernel's weight, the node sums are the stored copy
-  if (heated) {
-    launch_scalar_convection_heated(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, bd.cur, bd.thermal,
-                                    ctx->state[NSFEM_TCONV_1].p, sgs);
-    ++bd.fused_launches;
-  } else {
-    launch_scalar_convection(s, ctx->mesh, ctx->state[NSFEM_U1].p, T1, b0, sc.form, ctx->state[NSFEM_TCONV_1].p, sgs);
-  }
-  ++sc.conv_launches;
-  if (sgs.law != 0) ++sc.sgs_launches;
+  scalar_explicit_launch(ctx, ctx->state[NSFEM_U1].p, T1, b0, sc.form, heated ? &bd.cur : nullptr,
+                         ctx->state[NSFEM_TCONV_1].p, sgs, true);
   sc.conv1_fresh = true;
   sc.conv1_weight = b0;
-  sc.conv_form = sc.form;
-  sc.conv_thermal_epoch = bd.thermal_epoch;
-  sc.conv_body_epoch = bd.epoch;
-  sc.conv_sgs_epoch = sc.sgs_epoch;
-  sc.conv_visc_epoch = ctx->visc.epoch;
+  sc.conv_key = now;
   if (b1 != 0.0) launch_lincomb3(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, -f2, ctx->state[NSFEM_TCONV_2].p, rhs);
   else launch_axpby(s, n, -1.0, rhs, -1.0, ctx->state[NSFEM_TCONV_1].p, rhs);
   // Dirichlet rows T_i = g_i; start vector T1 with the Dirichlet values (as the IMEX diffusion step)
@@ -3332,62 +3322,40 @@ extern "C" int nsfem_step_scalar_imex(nsfem_ctx* ctx, const nsfem_krylov_opts* o
   API_END(ctx)
 }
 
+// The two test hooks of the scalar element launch: scalar_explicit_launch on a work vector.  all_terms false: C(u) T
+// alone, no bodies and no subgrid term; true: what ONE launch of the step forms for a level, weight [C(u) T + D(u, T)
+// (+ H(T))] -- D while the subgrid heat flux is on, H while a body is thermal (pose: prev for the level T2, cur
+// otherwise, as the step takes them)
+static void scalar_hook(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight, bool all_terms,
+                        double* out_host) {
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  require_velocity_slot(velocity_slot);
+  require_scalar_slot(scalar_slot);
+  require_scalar_form(form);
+  require_finite_weight(weight);
+  if (all_terms) scalar_sgs_require_law(ctx);
+  ensure_scalar_slot(ctx, scalar_slot);
+  nsfem_ctx::Bodies& bd = ctx->bodies;
+  const BodyTable* pose = scalar_slot == NSFEM_T2 ? &bd.prev : &bd.cur;
+  if (!all_terms || bd.n_thermal == 0 || bd.cur.n == 0) pose = nullptr;
+  hook_to_host(ctx, ctx->mesh.n_p2, out_host, [&](double* out) {
+    scalar_explicit_launch(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, pose, out,
+                           all_terms ? scalar_sgs_args(ctx) : ScalarSgsArgs{}, false);
+  });
+}
+
 extern "C" int nsfem_scalar_convection(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
                                        double* out_host) {
   API_BEGIN
-  NSFEM_REQUIRE(ctx && out_host, "null argument");
-  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
-  NSFEM_REQUIRE(scalar_slot >= NSFEM_T0 && scalar_slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
-  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
-  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
-  hipStream_t s = ctx->stream;
-  const int64_t n = ctx->mesh.n_p2;
-  ensure_scalar_slot(ctx, scalar_slot);
-  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
-  ctx->kw.ensure(nvel(ctx));
-  ++ctx->kw.touch;
-  double* out = ctx->kw.q.p;
-  launch_scalar_convection(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, out);
-  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  scalar_hook(ctx, velocity_slot, scalar_slot, form, weight, false, out_host);
   API_END(ctx)
 }
 
-// what ONE launch of the step forms for a level: weight [C(u) T + D(u, T) (+ H(T))] -- D while the subgrid heat flux is
-// on, H while a body is thermal (pose: prev for the level T2, cur otherwise, as the step takes them)
 extern "C" int nsfem_scalar_explicit(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, int form, double weight,
                                      double* out_host) {
   API_BEGIN
-  NSFEM_REQUIRE(ctx && out_host, "null argument");
-  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "velocity_slot is not a velocity slot");
-  NSFEM_REQUIRE(scalar_slot >= NSFEM_T0 && scalar_slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
-  NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
-  NSFEM_REQUIRE(std::isfinite(weight), "bad weight");
-  scalar_sgs_require_law(ctx);
-  hipStream_t s = ctx->stream;
-  const int64_t n = ctx->mesh.n_p2;
-  ensure_scalar_slot(ctx, scalar_slot);
-  // (a work vector of the Krylov solvers: no slot and none of the step's buffers is written)
-  ctx->kw.ensure(nvel(ctx));
-  ++ctx->kw.touch;
-  double* out = ctx->kw.q.p;
-  nsfem_ctx::Bodies& bd = ctx->bodies;
-  const ScalarSgsArgs sgs = scalar_sgs_args(ctx);
-  if (bd.n_thermal > 0 && bd.cur.n > 0) {
-    launch_scalar_convection_heated(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form,
-                                    scalar_slot == NSFEM_T2 ? bd.prev : bd.cur, bd.thermal, out, sgs);
-    ++bd.fused_launches;
-  } else {
-    launch_scalar_convection(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p, weight, form, out,
-                             sgs);
-  }
-  if (sgs.law != 0) ++ctx->sc.sgs_launches;
-  NSFEM_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  scalar_hook(ctx, velocity_slot, scalar_slot, form, weight, true, out_host);
   API_END(ctx)
 }
 

@@ -925,60 +925,19 @@ __global__ __launch_bounds__(256) void k_buoyancy_force(int64_t n_nodes, int dim
 }
 
 void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                              int form, double* out, ScalarSgsArgs sgs) {
+                              int form, const ScalarBodies* hb, double* out, ScalarSgsArgs sgs) {
   NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
+  NSFEM_REQUIRE(!hb || (hb->bt.n > 0 && hb->th.n == hb->bt.n), "heated bodies: no temperatures set for the bodies");
+  const int penal = !hb ? 0 : (hb->bt.eps > 0.0 ? 2 : 1);
   if (m.dim == 3) {
-    scalar_convection_cells_3d(s, m, u, T, weight, form, sgs);
+    scalar_convection_cells_3d(s, m, u, T, weight, form, penal, hb, sgs);
   } else {
     const dim3 grid(grid_for(m.n_cells)), block(kBlock);
-    // (SGS defaults to 0: without the term these are the launches of old)
-#define NSFEM_SC(F) \
-  hipLaunchKernelGGL((k_scalar_conv_cell<F, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCS(F, L) \
-  hipLaunchKernelGGL((k_scalar_conv_cell<F, 0, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCSF(L) do { if (form == 0) NSFEM_SCS(0, L); else NSFEM_SCS(1, L); } while (0)
-    if (sgs.law == 1) NSFEM_SCSF(1);
-    else if (sgs.law == 4) NSFEM_SCSF(4);
-    else if (sgs.law == 5) NSFEM_SCSF(5);
-    else { if (form == 0) NSFEM_SC(0); else NSFEM_SC(1); }
-#undef NSFEM_SCSF
-#undef NSFEM_SCS
-#undef NSFEM_SC
-  }
-  hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
-  NSFEM_HIP(hipGetLastError());
-}
-
-void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                     int form, const BodyTable& bt, const ThermalTable& th, double* out,
-                                     ScalarSgsArgs sgs) {
-  NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
-  NSFEM_REQUIRE(bt.n > 0 && th.n == bt.n, "heated bodies: no temperatures set for the bodies");
-  if (m.dim == 3) {
-    scalar_convection_heated_cells_3d(s, m, u, T, weight, form, bt, th, sgs);
-  } else {
-    const dim3 grid(grid_for(m.n_cells)), block(kBlock);
-#define NSFEM_SCH(F, P) \
-  hipLaunchKernelGGL((k_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCHS(F, P, L) \
-  hipLaunchKernelGGL((k_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCHSF(L) do { \
-      if (bt.eps > 0.0) { if (form == 0) NSFEM_SCHS(0, 2, L); else NSFEM_SCHS(1, 2, L); } \
-      else { if (form == 0) NSFEM_SCHS(0, 1, L); else NSFEM_SCHS(1, 1, L); } } while (0)
-    if (sgs.law == 1) NSFEM_SCHSF(1);
-    else if (sgs.law == 4) NSFEM_SCHSF(4);
-    else if (sgs.law == 5) NSFEM_SCHSF(5);
-    else {
-      if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH(0, 2); else NSFEM_SCH(1, 2); }
-      else { if (form == 0) NSFEM_SCH(0, 1); else NSFEM_SCH(1, 1); }
-    }
-#undef NSFEM_SCHSF
-#undef NSFEM_SCHS
-#undef NSFEM_SCH
+    with_scalar_kernel(form, penal, sgs.law, [&](auto fc, auto pc, auto lc) {
+      constexpr int F = decltype(fc)::value, P = decltype(pc)::value, L = decltype(lc)::value;
+      hipLaunchKernelGGL((k_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
+                         scalar_penal_args<P>(hb), scalar_sgs_kernel_args<L>(sgs), m.ndst.p, m.rbuf.p);
+    });
   }
   hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
   NSFEM_HIP(hipGetLastError());

@@ -953,48 +953,13 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
 }
 
 void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                int form, ScalarSgsArgs sgs) {
+                                int form, int penal, const ScalarBodies* hb, ScalarSgsArgs sgs) {
   const dim3 grid(grid3(m.n_cells)), block(kBlock);
-#define NSFEM_SC3(F) \
-  hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SC3S(F, L) \
-  hipLaunchKernelGGL((k3_scalar_conv_cell<F, 0, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<0>{}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SC3SF(L) do { if (form == 0) NSFEM_SC3S(0, L); else NSFEM_SC3S(1, L); } while (0)
-  if (sgs.law == 1) NSFEM_SC3SF(1);
-  else if (sgs.law == 4) NSFEM_SC3SF(4);
-  else if (sgs.law == 5) NSFEM_SC3SF(5);
-  else { if (form == 0) NSFEM_SC3(0); else NSFEM_SC3(1); }
-#undef NSFEM_SC3SF
-#undef NSFEM_SC3S
-#undef NSFEM_SC3
-  NSFEM_HIP(hipGetLastError());
-}
-
-void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T,
-                                       double weight, int form, const BodyTable& bt, const ThermalTable& th,
-                                       ScalarSgsArgs sgs) {
-  const dim3 grid(grid3(m.n_cells)), block(kBlock);
-#define NSFEM_SCH3(F, P) \
-  hipLaunchKernelGGL((k3_scalar_conv_cell<F, P>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<0>{}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCH3S(F, P, L) \
-  hipLaunchKernelGGL((k3_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight, \
-                     ScalarPenalArgs<P>{bt, th}, ScalarSgsKernelArgs<L>{sgs.c0, sgs.inv_prt}, m.ndst.p, m.rbuf.p)
-#define NSFEM_SCH3SF(L) do { \
-    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3S(0, 2, L); else NSFEM_SCH3S(1, 2, L); } \
-    else { if (form == 0) NSFEM_SCH3S(0, 1, L); else NSFEM_SCH3S(1, 1, L); } } while (0)
-  if (sgs.law == 1) NSFEM_SCH3SF(1);
-  else if (sgs.law == 4) NSFEM_SCH3SF(4);
-  else if (sgs.law == 5) NSFEM_SCH3SF(5);
-  else {
-    if (bt.eps > 0.0) { if (form == 0) NSFEM_SCH3(0, 2); else NSFEM_SCH3(1, 2); }
-    else { if (form == 0) NSFEM_SCH3(0, 1); else NSFEM_SCH3(1, 1); }
-  }
-#undef NSFEM_SCH3SF
-#undef NSFEM_SCH3S
-#undef NSFEM_SCH3
+  with_scalar_kernel(form, penal, sgs.law, [&](auto fc, auto pc, auto lc) {
+    constexpr int F = decltype(fc)::value, P = decltype(pc)::value, L = decltype(lc)::value;
+    hipLaunchKernelGGL((k3_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
+                       scalar_penal_args<P>(hb), scalar_sgs_kernel_args<L>(sgs), m.ndst.p, m.rbuf.p);
+  });
   NSFEM_HIP(hipGetLastError());
 }
 

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <stdexcept>
 #include <functional>
@@ -491,10 +492,6 @@ struct ScalarSgsKernelArgs {
 };
 template <>
 struct ScalarSgsKernelArgs<0> {};
-void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                              int form, double* out, ScalarSgsArgs sgs = ScalarSgsArgs{});
-void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                int form, ScalarSgsArgs sgs);
 // variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman, p = params): the element kernel
 // k_visc_var_cell / k3_visc_var_cell on the velocity u, element vectors weight * V_K(u) node-sorted into m.rbuf --
 // mean: the cell means of nu_x into the first n_cells doubles of m.rbuf instead
@@ -534,14 +531,45 @@ struct ScalarPenalArgs {
 };
 template <>
 struct ScalarPenalArgs<0> {};
-// out = weight (C(u) T + H(T)): the fused element kernel k_scalar_conv_cell<FORM, PENAL, SGS> / k3_scalar_conv_cell
-// (PENAL 1 sharp, 2 smoothed masks; bt the pose that belongs to the level of T) plus k_scalar_gather
-void launch_scalar_convection_heated(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
-                                     int form, const BodyTable& bt, const ThermalTable& th, double* out,
-                                     ScalarSgsArgs sgs = ScalarSgsArgs{});
-void scalar_convection_heated_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T,
-                                       double weight, int form, const BodyTable& bt, const ThermalTable& th,
-                                       ScalarSgsArgs sgs);
+// the pose that belongs to the level of T and the thermal table: what a launch with heated bodies takes
+struct ScalarBodies {
+  const BodyTable& bt;
+  const ThermalTable& th;
+};
+// f(std::integral_constant<int, V>) for the V that equals v; the LAST V stands for every other value
+template <int V0, int... Vs, class F>
+inline void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+  else if (v == V0) f(std::integral_constant<int, V0>{});
+  else with_int<Vs...>(v, f);
+}
+// The ONE place that turns the run-time (form, PENAL, law) of a scalar element launch into template arguments:
+// f(FORM, PENAL, SGS) gets three integral constants, so each translation unit holds one launch of k_scalar_conv_cell
+// <FORM, PENAL, SGS> / k3_scalar_conv_cell -- 2 forms x 3 PENAL x 4 SGS (the subgrid laws 1, 4, 5; 0 for all else)
+template <class F>
+inline void with_scalar_kernel(int form, int penal, int law, F&& f) {
+  with_int<0, 1>(form, [&](auto fc) {
+    with_int<0, 1, 2>(penal, [&](auto pc) { with_int<1, 4, 5, 0>(law, [&](auto lc) { f(fc, pc, lc); }); });
+  });
+}
+// (PENAL 0 and SGS 0 are the code of every run without temperatures / without the term: their kernels take nothing)
+template <int PENAL>
+inline ScalarPenalArgs<PENAL> scalar_penal_args(const ScalarBodies* hb) {
+  if constexpr (PENAL == 0) return {};
+  else return {hb->bt, hb->th};
+}
+template <int SGS>
+inline ScalarSgsKernelArgs<SGS> scalar_sgs_kernel_args(const ScalarSgsArgs& a) {
+  if constexpr (SGS == 0) return {};
+  else return {a.c0, a.inv_prt};
+}
+// out = weight (C(u) T + D(u, T) + H(T)): the fused element kernel k_scalar_conv_cell<FORM, PENAL, SGS> /
+// k3_scalar_conv_cell plus k_scalar_gather.  hb null: no heated bodies, PENAL 0; else PENAL 1 (sharp masks, bt.eps = 0)
+// or 2 (smoothed), bt the pose that belongs to the level of T
+void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                              int form, const ScalarBodies* hb, double* out, ScalarSgsArgs sgs = ScalarSgsArgs{});
+void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
+                                int form, int penal, const ScalarBodies* hb, ScalarSgsArgs sgs);
 // k_body_heat + k_penal_finish (bodies.hip): out[s][3] = {int chi_s, Q_s, int chi_s T} in device memory, parts
 // [n 3 kBodyParts] work space
 void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const BodyTable& bt, const ThermalTable& th,
@@ -1177,36 +1205,49 @@ struct nsfem_ctx {
   nsfem::BlockMat L1, L2;
   bool imex_ops_dirty = true;
   bool conv_n2_valid = false, conv_n1_fresh = false;   // N2 holds c_c N(u2) / N1 was written since the last advance
+  // Key of the stored explicit vectors N1, N2 (the vector itself: imex_explicit_add, api.hip): everything but the level
+  // that they were formed with -- convective form, c_c, visc.epoch, bodies.epoch and the 2 c_cor Omega of their level
+  // (compared bit for bit).  A step forms N(u2) again iff the key of its N2 is not the key the settings give now.
+  // vouched: the caller wrote the slot (nsfem_set_state).  The two sides differ here, on purpose: a
+  // vouched NSFEM_CONV_N2 is used whatever the other components say; a vouched NSFEM_TCONV_2 (Scalar::Key below)
+  // stands for every FORM only -- its epochs are those of the vouching call and are honoured afterwards
+  struct ImexKey {
+    int form = -1;
+    double cc = 0.0;
+    int64_t visc = 0, body = 0;
+    double gam[3] = {0.0, 0.0, 0.0};
+    bool vouched = false;
+    static ImexKey of(const nsfem_ctx& c, const double gam[3]);       // (api.hip: what the settings give now)
+    bool serves(const ImexKey& now) const {
+      return vouched || (form == now.form && cc == now.cc && visc == now.visc && body == now.body &&
+                         std::memcmp(gam, now.gam, sizeof(gam)) == 0);
+    }
+  } conv_key;
   // partitioned meshes: the ghost entries of the slot are bit copies of the owners' values (exchanged by an IMEX
   // right-hand side and not written since) -- kept next to the flags above, nsfem_advance rotates them with the slots
   bool u1_ghost_fresh = false, u2_ghost_fresh = false;
   nsfem::DevBuf<double> imex_pack;                     // [n_p2][2 dim]: u1 and u2 in one halo message
   int imex_lattice_agreed = -1;                        // the ranks' common answer to "one-launch right-hand side?" (-1: not asked)
-  int conv_n_form = -1;                                // convective form and coefficient the stored vectors belong to
-  double conv_n_cc = 0.0;
   // rotating frame in the IMEX calls (nsfem_set_imex_rotation): treatment 0 refuse, 1 Coriolis term extrapolated with
   // the convective term.  w[0], w[1]: the angular velocity at t^n, t^(n-1) where `given` (else the value of
-  // nsfem_set_angular_velocity); conv_n_gam: the 2 c_cor Omega the stored N1 was formed with
+  // nsfem_set_angular_velocity)
   struct ImexRotation {
     int treatment = 0;
     bool given[2] = {false, false};
     double w[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
     int64_t rhs = 0, recomputed = 0;
   } imex_rot;
-  double conv_n_gam[3] = {0.0, 0.0, 0.0};
   // variable viscosity (nsfem_set_viscosity_law): law 0 none, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman.  With a law the stored
-  // vectors N1, N2 are c_c conv(u) + V(u); `epoch` counts the changes of law or parameters, conv_n_visc is the epoch
-  // the stored vectors belong to
+  // vectors N1, N2 are c_c conv(u) + V(u); `epoch` counts the changes of law or parameters (a component of conv_key)
   struct Viscosity {
     int law = 0;
     double p[4] = {0.0, 0.0, 0.0, 0.0};
     int64_t epoch = 0, launches = 0, recomputed = 0;
   } visc;
-  int64_t conv_n_visc = 0;
   // immersed bodies (nsfem_set_bodies): with bodies the stored vectors carry B(u) as well.  `cur` is the pose of t^n,
   // `prev` that of t^(n-1) (nsfem_move_bodies shifts cur to prev; without a move they are equal): a stored N(u2) was
   // formed with prev and one that has to be recomputed is formed with it again.  `epoch` counts the changes of the set,
-  // eta or the smoothing; conv_n_body is the epoch the stored vectors belong to
+  // eta or the smoothing (a component of conv_key)
   struct Bodies {
     nsfem::BodyTable cur, prev;
     int64_t epoch = 0, launches = 0, recomputed = 0;
@@ -1220,7 +1261,6 @@ struct nsfem_ctx {
     int64_t thermal_epoch = 0, fused_launches = 0, thermal_recomputed = 0;
     nsfem::DevBuf<double> heat_work;   // partials and results of nsfem_body_heat
   } bodies;
-  int64_t conv_n_body = 0;
   // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the
   // non-symmetric V(0, d + 1) the BiCGStab solves use (nsfem_set_bdf switches back)
   bool mg_v_symmetric = false;
@@ -1244,15 +1284,31 @@ struct nsfem_ctx {
     int nbc = 0;
     bool conv1_fresh = false, conv2_valid = false;   // TCONV_1 written since the last advance / TCONV_2 usable
     double conv1_weight = 0.0, conv2_weight = 0.0;
-    int conv_form = -1;                              // form the stored vectors belong to
-    // heated bodies: bodies.thermal_epoch and (read only while a thermal body is set) bodies.epoch of the stored vectors
-    int64_t conv_thermal_epoch = 0, conv_body_epoch = 0;
     // subgrid heat flux (nsfem_set_scalar_sgs): prandtl_t > 0 switches D(u, T) on, the stored vectors carry it then.
-    // sgs_epoch counts the changes of prandtl_t; conv_sgs_epoch and (read only while the term is on) conv_visc_epoch
-    // are sgs_epoch and visc.epoch of the stored vectors
+    // sgs_epoch counts the changes of prandtl_t
     double prandtl_t = 0.0;
     int64_t sgs_epoch = 0, sgs_launches = 0, sgs_recomputed = 0;
-    int64_t conv_sgs_epoch = 0, conv_visc_epoch = 0;
+    // Key of the stored vectors TCONV_1, TCONV_2: the form, bodies.thermal_epoch, bodies.epoch (compared only while a
+    // body is thermal), sgs_epoch and visc.epoch (compared only while the subgrid term is on) they were formed with.
+    // The three answers are kept apart: a stale heat key and a stale subgrid key are counted each on its own.
+    // vouched (nsfem_set_state wrote NSFEM_TCONV_2): any form serves; the epochs are those of that call (ImexKey above)
+    struct Key {
+      int form = -1;
+      int64_t thermal = 0, body = 0, sgs = 0, visc = 0;
+      bool vouched = false;
+      static Key of(const nsfem_ctx& c) {
+        Key k;
+        k.form = c.sc.form;
+        k.thermal = c.bodies.thermal_epoch;
+        k.body = c.bodies.epoch;
+        k.sgs = c.sc.sgs_epoch;
+        k.visc = c.visc.epoch;
+        return k;
+      }
+      bool same_form(const Key& now) const { return vouched || form == now.form; }
+      bool same_heat(const Key& now, bool heated) const { return thermal == now.thermal && (!heated || body == now.body); }
+      bool same_sgs(const Key& now, bool sgs_on) const { return sgs == now.sgs && (!sgs_on || visc == now.visc); }
+    } conv_key;
     int64_t matrix_builds = 0, conv_launches = 0, conv_reuses = 0;
     int dict_used = 0;
     bool dinv_dirty = true;                          // 1 / diagonal belongs to an older matrix or Dirichlet set

@@ -42,11 +42,13 @@ That the module can fail: five libraries built with one line of the driver (csrc
 against this module and once against the six older IMEX feature modules (test_gpu_imex, _imex_rotation,
 _variable_viscosity, _immersed_bodies, _scalar_transport, _heated_bodies; 271 tests):
     one-line change                                                   this module    the six older modules
-    conv_n_visc dropped from the ``stored`` comparison                12 of 69 fail  1 of 271 fails (viscosity: stored vector)
-    same_rot dropped                                                   8 of 69 fail  6 of 271 fail (rotating cavity steps)
-    bodies.cur for bodies.prev in the recompute branch of the step    52 of 69 fail  0 of 271 fail
-    conv_body_epoch dropped from same_heat                            12 of 69 fail  1 of 271 fails (heated bodies: epoch)
-    viscosity_add and penalty_add swapped after imex_rhs in the step  50 of 69 fail  0 of 271 fail
+    visc dropped from ImexKey::serves (the step's ``stored`` test)    12 of 69 fail  1 of 271 fails (viscosity: stored vector)
+    gam dropped from ImexKey::serves                                   8 of 69 fail  6 of 271 fail (rotating cavity steps)
+    bodies.cur for bodies.prev where the step forms N(u2) afresh      52 of 69 fail  0 of 271 fail
+    body dropped from Scalar::Key::same_heat                          12 of 69 fail  1 of 271 fails (heated bodies: epoch)
+    V and B swapped after imex_rhs in the step                        50 of 69 fail  0 of 271 fail
+(The runs were made when the driver spelled these lines out in the step itself; the comparisons now live in the two
+keys of csrc/nsfem_internal.hpp, the order of V and B and the pose of a level in imex_explicit_add of csrc/api.hip.)
 The first, second and fourth fail in the sequences whose events move the dropped key (values against the host at 1e-2,
 or the counters where the vector happens to be the same); the third and fifth fail wherever the twin recomputes --
 the two mistakes the older modules cannot see, because no older test recomputes N(u2) with a moved pose in a step, and

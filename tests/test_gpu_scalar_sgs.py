@@ -345,6 +345,79 @@ def test_changes_of_prandtl_number_or_constant_recompute_the_stored_vector_once(
         ctx.close()
 
 
+def test_heat_and_sgs_keys_stale_in_one_gap():
+    """box(8, 8), SBDF2, the Smagorinsky term with Pr_t and the sharp heated disc, three full time steps (flow step,
+    scalar step, advance); then another Pr_t AND another body temperature before step four: the stored TCONV_2 is stale
+    on both counts, each cause is counted once, nothing is reused and both element launches of the step are fused ones
+    with the term.  A twin context that gets the same calls and forms TCONV_2 afresh in every step (T2 written back by
+    hand) agrees in T0 to 1e-13 of the largest entry after every step, the element-vector bound of
+    tests/test_gpu_imex_composed.py for the same comparison"""
+    mesh, dm, marks, s, rs, make = _mesh((8, 8))
+    X = dm.p2_coords
+    k = _step_size((8, 8))
+    bodies = heated_set(2, "disc", 2.0 * k, 0.0, 2.0 * k)
+    vbc, tbc = cavity_bc(dm, marks), _two_sides(dm, marks, X)
+    _, T_init = smooth_fields(X)
+    q = np.cos(2.0 * X[:, 0] + 0.3) * np.sin(1.5 * X[:, 1] + 0.2)
+    f = np.stack([np.sin(np.pi * X[:, 1]), -1.0 + X[:, 0]], axis=1).ravel()
+    flags, temps = bodies.temperatures()
+    ctxs = [make(mesh, dm), make(mesh, dm)]
+    try:
+        for ctx in ctxs:
+            ctx.set_coeffs(1.0, 1.0, 0.01, 1.0)
+            ctx.set_dirichlet(nat.VELOCITY, *vbc)
+            ctx.set_dirichlet(nat.PRESSURE, *NO_PBC)
+            ctx.set_dirichlet(nat.SCALAR, *tbc)
+            ctx.set_scalar(_KAPPA_STEPS, _B[:2], 0)
+            ctx.set_viscosity_law(SMAGORINSKY, (_CS_STEPS, ))
+            ctx.set_scalar_sgs(_PRT_STEPS)
+            ctx.set_state(nat.BODY_FORCE, f)
+            ctx.set_state(nat.T_SOURCE, q)
+            ctx.set_state(nat.T0, T_init)
+            ctx.set_state(nat.T1, T_init)
+            ctx.set_bodies(bodies.rows(0.0), bodies.eta, bodies.smoothing)
+            ctx.set_body_temperatures(flags, temps, bodies.eta_scalar)
+        dev, twin = ctxs
+        opts = [_opts(ctx) for ctx in ctxs]
+        ts = IMEXTimeStepping(0.0, 1.0e9, IMEXType.SBDF2, desired_start_time_step=k)
+
+        def counters():
+            sgs, heat, info = dev.scalar_sgs_info(), dev.body_heat_info(), dev.scalar_info()
+            return np.array([sgs["recomputed"], heat["recomputed"], info["convection_reuses"],
+                             info["convection_launches"], sgs["launches"], heat["fused_launches"]])
+
+        def full_step(step):
+            ts.update_coefficients()
+            for ctx, o in zip(ctxs, opts):
+                ctx.set_imex(ts.alpha, ts.beta, ts.gamma, ts.get_next_step_size())
+                ctx.step_imex(o)
+                if ctx is twin:
+                    ctx.set_state(nat.T2, ctx.get_state(nat.T2))
+                assert ctx.step_scalar_imex(rtol=1e-13).converged
+            T, Tt = dev.get_state(nat.T0), twin.get_state(nat.T0)
+            err = _max_rel(T, Tt)
+            print("stale in one gap, step %d: T0 against the twin %.2e of the largest entry" % (step, err))
+            assert err < 1e-13, (step, err)
+            for ctx in ctxs:
+                ctx.advance(0)
+            ts.advance_time()
+        for step in range(3):
+            full_step(step)
+        assert dev.scalar_info()["convection_reuses"] == 2 and dev.scalar_sgs_info()["recomputed"] == 0
+        assert dev.body_heat_info() == dict(thermal=1, fused_launches=3, recomputed=0)
+        for ctx in ctxs:
+            ctx.set_scalar_sgs(0.8)
+            ctx.set_body_temperatures(flags, np.where(flags == 1, temps + 0.35, 0.0), bodies.eta_scalar)
+        before = counters()
+        full_step(3)
+        diff = counters() - before
+        print("stale in one gap, step 3: sgs recomputed, heat recomputed, reuses, launches, sgs launches, fused", diff)
+        assert diff.tolist() == [1, 1, 0, 2, 2, 2], diff
+    finally:
+        for ctx in ctxs:
+            ctx.close()
+
+
 def test_same_state_gives_the_same_bytes_and_switching_off_returns_to_the_old_bytes():
     """three steps on two fresh contexts give the same bytes in every scalar slot; a context on which Pr_t was set and
     set back to 0 before the first step ends on the bytes of a context that never called the setter; one on which the

@@ -282,7 +282,7 @@ def test_every_layer_carries_the_feature():
     csrc = os.path.join(root, "navierstokes-with-fenics_amd", "csrc")
     with open(os.path.join(csrc, "Makefile")) as fh:
         assert "bodies.hip" in fh.read()
-    for source, kernel in (("assembly.hip", "k_scalar_conv_cell<F, P>"), ("assembly3d.hip", "k3_scalar_conv_cell<F, P>"),
+    for source, kernel in (("assembly.hip", "k_scalar_conv_cell<F, P, L>"), ("assembly3d.hip", "k3_scalar_conv_cell<F, P, L>"),
                            ("bodies.hip", "k_body_heat<")):
         with open(os.path.join(csrc, source)) as fh:
             assert kernel in fh.read(), (source, kernel)
