@@ -4727,19 +4727,17 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
   else if (family == 2) { T.dict_ready = false; NSFEM_REQUIRE(T.sell_ready, "no SELL-64 layout for this pattern"); }
   else if (family == 3) { NSFEM_REQUIRE(T.dict_ready, "no stencil dictionary for this pattern"); T.sell_ready = false; }
   else if (family == 4) { NSFEM_REQUIRE(lattice_smoother_available(T, nv), "no lattice structure for this pattern"); }
-  // what the dispatcher will pick
-  auto picked = [&](bool dict_ok) {
-    if (T.dict_ready && (dict_ok || T.dict->exact) && nv <= 3) return 3;
-    if (T.sell_ready && pat.n_slices > 0) return 2;
-    return 1;
+  // used_family: the dispatcher's own decision for the launch below (whole operator, one output) as a family number
+  auto family_of = [](SpmvPath path) {
+    return path == SpmvPath::DictBlock || path == SpmvPath::DictScalar ? 3 : (path == SpmvPath::Sell ? 2 : 1);
   };
   const double* result = y.p;
   if (t->epilogue == 0) {
-    t->used_family = picked(t->dict_ok != 0);
+    t->used_family = family_of(spmv_path(T, nv, EPI_STORE, 0, t->dict_ok != 0, false));
     launch_spmv(s, T, nv, x.p, y.p, mk, mk ? t->maskmode : MASK_NONE, t->ghost, 0, t->dict_ok);
   } else if (t->epilogue == 1) {
     NSFEM_REQUIRE(t->b, "residual needs b");
-    t->used_family = picked(false);
+    t->used_family = family_of(spmv_path(T, nv, EPI_RESID, 0, false, false));
     launch_residual(s, T, nv, x.p, b.p, y.p, mk, mk ? t->maskmode : MASK_NONE);
   } else {
     NSFEM_REQUIRE((t->b || (family == 4 && t->rf)) && t->steps >= 1, "smoothing needs b and steps >= 1");
@@ -4779,7 +4777,7 @@ extern "C" int nsfem_kernel_apply(nsfem_ctx* ctx, nsfem_kernel_test* t) {
       t->lattice_fixed_shape = ov.fixed_shape;
       t->lattice_kind = ov.kind;
     } else {
-      t->used_family = picked(true);
+      t->used_family = family_of(spmv_path(T, nv, EPI_CHEB, 0, true, false));
       dinv.alloc(n);
       launch_inv_diag(s, T, nv, mk, dinv.p);
       const double* cur = x.p;
@@ -5221,10 +5219,29 @@ extern "C" int nsfem_profile_convection(nsfem_ctx* ctx, int enable, double* avg_
   API_END(ctx)
 }
 
+// milliseconds of `reps` rounds (flush, step) on s between two events, after 3 rounds of warm-up
+template <class Flush, class Step>
+static double time_rounds(hipStream_t s, int reps, Flush&& flush, Step&& step) {
+  hipEvent_t e0, e1;
+  NSFEM_HIP(hipEventCreate(&e0));
+  NSFEM_HIP(hipEventCreate(&e1));
+  for (int i = 0; i < 3; ++i) { flush(); step(); }
+  NSFEM_HIP(hipEventRecord(e0, s));
+  for (int i = 0; i < reps; ++i) { flush(); step(); }
+  NSFEM_HIP(hipEventRecord(e1, s));
+  NSFEM_HIP(hipEventSynchronize(e1));
+  float t = 0.f;
+  NSFEM_HIP(hipEventElapsedTime(&t, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return (double)t;
+}
+
 extern "C" int nsfem_time_spmv(nsfem_ctx* ctx, int op, int reps, double* ms_per_launch,
                                int64_t* algorithmic_bytes) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && reps != 0 && ms_per_launch, "bad argument");
+  auto nothing = [] {};
   // reps < 0 (smoother only): |reps| back-to-back launches without the cache-flushing launches in
   // between (the operands stay in the 256 MiB Infinity Cache when they fit)
   const bool warm = reps < 0;
@@ -5245,22 +5262,7 @@ extern "C" int nsfem_time_spmv(nsfem_ctx* ctx, int op, int reps, double* ms_per_
       launch_convection_action(s, ctx->mesh, ctx->state[NSFEM_U1].p, ctx->state[NSFEM_U0].p, cc, y.p,
                                ctx->conv_form, false);
     };
-    hipEvent_t e0, e1;
-    NSFEM_HIP(hipEventCreate(&e0));
-    NSFEM_HIP(hipEventCreate(&e1));
-    auto timed = [&](bool with_step) {
-      for (int i = 0; i < 3; ++i) { flush(); if (with_step) step(); }
-      NSFEM_HIP(hipEventRecord(e0, s));
-      for (int i = 0; i < reps; ++i) { flush(); if (with_step) step(); }
-      NSFEM_HIP(hipEventRecord(e1, s));
-      NSFEM_HIP(hipEventSynchronize(e1));
-      float t = 0.f;
-      NSFEM_HIP(hipEventElapsedTime(&t, e0, e1));
-      return (double)t;
-    };
-    const double t_both = timed(true), t_flush = timed(false);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const double t_both = time_rounds(s, reps, flush, step), t_flush = time_rounds(s, reps, flush, nothing);
     *ms_per_launch = (t_both - t_flush) / reps;
     if (algorithmic_bytes) *algorithmic_bytes = convection_action_bytes(ctx);
     return NSFEM_OK;
@@ -5297,35 +5299,13 @@ extern "C" int nsfem_time_spmv(nsfem_ctx* ctx, int op, int reps, double* ms_per_
     fy.alloc((size_t)nvel(ctx));
     fx.zero(s);
     auto flush = [&] { launch_spmv(s, ctx->J, 1, fx.p, fy.p, nullptr, MASK_NONE); };
-    hipEvent_t e0, e1;
-    NSFEM_HIP(hipEventCreate(&e0));
-    NSFEM_HIP(hipEventCreate(&e1));
-    auto timed = [&](bool with_step) {
-      for (int i = 0; i < 3; ++i) { flush(); if (with_step) step(); }
-      NSFEM_HIP(hipEventRecord(e0, s));
-      for (int i = 0; i < reps; ++i) { flush(); if (with_step) step(); }
-      NSFEM_HIP(hipEventRecord(e1, s));
-      NSFEM_HIP(hipEventSynchronize(e1));
-      float t = 0.f;
-      NSFEM_HIP(hipEventElapsedTime(&t, e0, e1));
-      return (double)t;
-    };
     double ms;
     if (warm) {
-      for (int i = 0; i < 3; ++i) step();
-      NSFEM_HIP(hipEventRecord(e0, s));
-      for (int i = 0; i < reps; ++i) step();
-      NSFEM_HIP(hipEventRecord(e1, s));
-      NSFEM_HIP(hipEventSynchronize(e1));
-      float t = 0.f;
-      NSFEM_HIP(hipEventElapsedTime(&t, e0, e1));
-      ms = (double)t;
+      ms = time_rounds(s, reps, nothing, step);
     } else {
-      const double t_both = timed(true), t_flush = timed(false);
+      const double t_both = time_rounds(s, reps, flush, step), t_flush = time_rounds(s, reps, flush, nothing);
       ms = t_both - t_flush;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_per_launch = (double)ms / reps;
     (void)p;
     if (algorithmic_bytes)
@@ -5346,19 +5326,8 @@ extern "C" int nsfem_time_spmv(nsfem_ctx* ctx, int op, int reps, double* ms_per_
   std::vector<double> hx(nx);
   for (size_t i = 0; i < nx; ++i) hx[i] = std::sin((double)i);
   NSFEM_HIP(hipMemcpyAsync(dx.p, hx.data(), sizeof(double) * nx, hipMemcpyHostToDevice, s));
-  for (int i = 0; i < 3; ++i) launch_spmv(s, *A, nvv, dx.p, dy.p, nullptr, MASK_NONE);
-  hipEvent_t e0, e1;
-  NSFEM_HIP(hipEventCreate(&e0));
-  NSFEM_HIP(hipEventCreate(&e1));
-  NSFEM_HIP(hipEventRecord(e0, s));
-  for (int i = 0; i < reps; ++i) launch_spmv(s, *A, nvv, dx.p, dy.p, nullptr, MASK_NONE);
-  NSFEM_HIP(hipEventRecord(e1, s));
-  NSFEM_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  NSFEM_HIP(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms_per_launch = (double)ms / reps;
+  const double ms = time_rounds(s, reps, nothing, [&] { launch_spmv(s, *A, nvv, dx.p, dy.p, nullptr, MASK_NONE); });
+  *ms_per_launch = ms / reps;
   if (algorithmic_bytes)
     *algorithmic_bytes = (int64_t)p.nnz * (8 * A->br * A->bc + 4) + (int64_t)(p.n_rows + 1) * 4 +
                          (int64_t)(nx + ny) * 8;

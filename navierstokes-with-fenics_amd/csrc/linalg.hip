@@ -34,7 +34,7 @@ namespace nsfem {
 // rows (symmetric elimination on vectors that vanish on the constrained dofs).
 // EPI_RESID_SUM (scalar dictionary kernel only): EPI_RESID and, from the operand x it already holds,
 //   psum = base + x  (the projection step: p = p_old + z rides along in the check q = r - A z)
-enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_ACCUM = 2, EPI_CHEB = 3, EPI_RESID_SUM = 4 };
+// (enum Epi: nsfem_internal.hpp)
 
 struct SpmvArgs {
   const double* x;
@@ -1565,6 +1565,16 @@ void k_cheb_lattice(LatticeArgs a, const double* __restrict__ tval, const int32_
 #undef LAT_MK
 #undef LAT_ST
 
+// The operand sets with a specialised instantiation of k_cheb_lattice, written ONCE: lattice_launch_kind tests
+// membership, launch_cheb_lattice picks the instantiation LK_FIXED | set (or 0, the runtime-flag kernel) from it
+template <int... Ks>
+struct LatKindList {
+  static bool has(int k) { return ((k == Ks) || ...); }
+  template <class F>
+  static void pick(int kind, F&& f) { with_int<(LK_FIXED | Ks)..., 0>(kind, f); }
+};
+using LatKinds = LatKindList<LK_XC, LK_XIN | LK_XC, LK_RF, LK_RF | LK_ROUT, 0, LK_ROUT, LK_DOUT,
+                             LK_XIN | LK_DIN | LK_DOUT, LK_XIN | LK_DIN, LK_XIN | LK_DIN | LK_ROUT, LK_XIN>;
 // launch kind of k_cheb_lattice (LK_* flags): LK_FIXED | operands for the combinations with a specialised
 // instantiation, 0 (the runtime-flag kernel) for all others.  d_in is not read on a zero start.
 int lattice_launch_kind(bool x_in, bool xc, bool rf, bool d_in, bool d_out, bool r_out, bool ghost) {
@@ -1572,11 +1582,7 @@ int lattice_launch_kind(bool x_in, bool xc, bool rf, bool d_in, bool d_out, bool
   const bool fz = !x_in && !xc;
   const int k = (x_in ? LK_XIN : 0) | (xc ? LK_XC : 0) | (rf ? LK_RF : 0) | (d_in && !fz ? LK_DIN : 0) |
                 (d_out ? LK_DOUT : 0) | (r_out ? LK_ROUT : 0);
-  static const int specialised[] = {LK_XC, LK_XIN | LK_XC, LK_RF, LK_RF | LK_ROUT, 0, LK_ROUT, LK_DOUT,
-                                    LK_XIN | LK_DIN | LK_DOUT, LK_XIN | LK_DIN, LK_XIN | LK_DIN | LK_ROUT, LK_XIN};
-  for (int v : specialised)
-    if (k == v) return LK_FIXED | k;
-  return 0;
+  return LatKinds::has(k) ? LK_FIXED | k : 0;
 }
 // 32-bit operand offsets: the lattice's vectors (and the finer lattice's, under a fused restriction) in bytes < 2^31
 bool lattice_offsets_fit(int64_t w, int64_t h, int nv, bool rf) {
@@ -1681,6 +1687,24 @@ void ensure_fixed_masks(const StencilDict& d) {
   if (any) d.fixed_shape = shape;
 }
 
+// one launch of k_cheb_lattice<NV, K, WPE, WPC, GH, KIND>, its dynamic LDS limit raised once per device
+// launch shape: 4 waves per SIMD (<= 128 VGPRs: two workgroups per CU)
+template <int NV, int K, int WPE, int WPC, bool GH, int KIND>
+static void launch_lat(hipStream_t s, int grid, size_t lds, const LatticeArgs& a, const double* vals,
+                       const int32_t* toff, const int32_t* len, const double* dinv) {
+  static bool attr_dev[64];
+  int dev = 0;
+  NSFEM_HIP(hipGetDevice(&dev));
+  bool& attr_set = attr_dev[dev & 63];
+  if (!attr_set) {
+    NSFEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cheb_lattice<NV, K, WPE, WPC, GH, KIND>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((k_cheb_lattice<NV, K, WPE, WPC, GH, KIND>), dim3(grid), dim3(256 * WPC), lds, s, a, vals, toff,
+                     len, dinv);
+}
+
 // `steps` (<= lattice_smoother_max_steps) Chebyshev-Jacobi steps with the coefficients c1[k], c2[k]
 // supplied by the caller; x_in == nullptr: zero start
 void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double* x_in, const double* b,
@@ -1778,29 +1802,6 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
   for (int k = 0; k < 8; ++k) { a.c1[k] = k < steps ? c1[k] : 0.0; a.c2[k] = k < steps ? c2[k] : 0.0; }
   const size_t lds = (size_t)2 * 4 * 32 * a.EHh * nv * 8;
   const int grid = (a.ntiles + 7) & ~7;
-  // launch shape: 4 waves per SIMD (<= 128 VGPRs: two workgroups per CU)
-#define NSFEM_LAT(NV, KK, WPE, WPC, GH, KIND)                                                          \
-  do {                                                                                                 \
-    static bool attr_dev[64];                                                                          \
-    int dev_ = 0;                                                                                      \
-    NSFEM_HIP(hipGetDevice(&dev_));                                                                    \
-    bool& attr_set = attr_dev[dev_ & 63];                                                              \
-    if (!attr_set) {                                                                                   \
-      NSFEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cheb_lattice<NV, KK, WPE, WPC, GH, KIND>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));         \
-      attr_set = true;                                                                                 \
-    }                                                                                                  \
-    hipLaunchKernelGGL((k_cheb_lattice<NV, KK, WPE, WPC, GH, KIND>), dim3(grid), dim3(256 * WPC), lds, s, a, \
-                       (const double*)A.lat_vals.p, toff, (const int32_t*)d.len.p,                     \
-                       (const double*)A.dict_dinv.p);                                                  \
-  } while (0)
-#define NSFEM_LAT_K(NV, WPE, GH, KIND)                        \
-  do {                                                        \
-    if (eh == 48) NSFEM_LAT(NV, 3, 4, 4, GH, KIND);           \
-    else if (eh == 32) NSFEM_LAT(NV, 4, WPE, 2, GH, KIND);    \
-    else if (eh == 24) NSFEM_LAT(NV, 3, WPE, 2, GH, KIND);    \
-    else NSFEM_LAT(NV, 2, WPE, 2, GH, KIND);                  \
-  } while (0)
   // launch kind: the specialised instantiations cover what the cycles and the mass solve launch on one context at the
   // default shape; everything else (strips, other operand sets) runs the runtime-flag kernel
   const int kind = (g_lattice_kinds_on && !(ovr && ovr->generic))
@@ -1808,35 +1809,24 @@ void launch_cheb_lattice(hipStream_t s, const BlockMat& A, int nv, const double*
                                              d_out != nullptr, r_out != nullptr, gh_lo > 0 || gh_hi > 0)
                        : 0;
   if (ovr) ovr->kind = kind;
-#define NSFEM_LAT_KINDS(NV)                                                                     \
-  do {                                                                                          \
-    switch (kind) {                                                                             \
-      case LK_FIXED | LK_XC: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XC); break;                \
-      case LK_FIXED | LK_XIN | LK_XC: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_XC); break; \
-      case LK_FIXED | LK_RF: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_RF); break;                \
-      case LK_FIXED | LK_RF | LK_ROUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_RF | LK_ROUT); break; \
-      case LK_FIXED: NSFEM_LAT_K(NV, 4, false, LK_FIXED); break;                                \
-      case LK_FIXED | LK_ROUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_ROUT); break;            \
-      case LK_FIXED | LK_DOUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_DOUT); break;            \
-      case LK_FIXED | LK_XIN | LK_DIN | LK_DOUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_DIN | LK_DOUT); break; \
-      case LK_FIXED | LK_XIN | LK_DIN: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_DIN); break; \
-      case LK_FIXED | LK_XIN | LK_DIN | LK_ROUT: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN | LK_DIN | LK_ROUT); break; \
-      case LK_FIXED | LK_XIN: NSFEM_LAT_K(NV, 4, false, LK_FIXED | LK_XIN); break;              \
-      default: NSFEM_REQUIRE(false, "lattice smoother: launch kind without an instantiation");  \
-    }                                                                                           \
-  } while (0)
+  NSFEM_REQUIRE(kind == 0 || ((kind & LK_FIXED) && LatKinds::has(kind & ~LK_FIXED)),
+                "lattice smoother: launch kind without an instantiation");
   // (the frozen ghost lines of partitioned strips are a template flag: the single-context launches do not pay for
   // them -- 811 vs 758 VALU instructions per wave)
   const bool gh = gh_lo > 0 || gh_hi > 0;
-  if (kind != 0 && nv == 2) NSFEM_LAT_KINDS(2);
-  else if (kind != 0) NSFEM_LAT_KINDS(1);
-  else if (gh && nv == 2) NSFEM_LAT_K(2, 4, true, 0);
-  else if (gh) NSFEM_LAT_K(1, 4, true, 0);
-  else if (nv == 2) NSFEM_LAT_K(2, 4, false, 0);
-  else NSFEM_LAT_K(1, 4, false, 0);
-#undef NSFEM_LAT_KINDS
-#undef NSFEM_LAT_K
-#undef NSFEM_LAT
+  with_int<2, 1>(nv, [&](auto nvc) {
+    with_int<48, 32, 24, 16>(eh, [&](auto ehc) {        // tile height -> slots per thread K, waves per parity class WPC
+      constexpr int NV = decltype(nvc)::value, EH = decltype(ehc)::value;
+      constexpr int K = EH == 48 ? 3 : EH / 8, WPC = EH == 48 ? 4 : 2;
+      auto launch = [&](auto ghc, auto kc) {
+        launch_lat<NV, K, 4, WPC, decltype(ghc)::value, decltype(kc)::value>(s, grid, lds, a, A.lat_vals.p, toff,
+                                                                             d.len.p, A.dict_dinv.p);
+      };
+      // (ghost lines come with the runtime-flag kernel only: lattice_launch_kind gives them kind 0)
+      if (kind == 0 && gh) launch(std::true_type{}, std::integral_constant<int, 0>{});
+      else LatKinds::pick(kind, [&](auto kc) { launch(std::false_type{}, kc); });
+    });
+  });
   NSFEM_HIP(hipGetLastError());
 }
 
@@ -2342,181 +2332,178 @@ void mark_interior_blocks(Pattern& p, const std::vector<uint8_t>& ghost_cols) {
   }
 }
 
-template <int EPI>
-static void spmv_dispatch(hipStream_t s, const BlockMat& A, int nv, const SpmvArgs& a_in) {
+// ----- which kernel family a product runs on: the ONE statement of the path rule ("Which kernel family
+// a product runs on")
+// may the product run on the matrix's dictionary copy?  An inexact copy only where the caller allows it
+static bool dict_usable(const BlockMat& A, bool dict_ok) { return A.dict_ready && (dict_ok || A.dict->exact); }
+// scalar matrix on 1..3 interleaved components: what the scalar dictionary and the SELL-64 kernels take
+static bool scalar_operands(const BlockMat& A, int nv) { return A.br == 1 && A.bc == 1 && nv >= 1 && nv <= 3; }
+// the block shapes k_spmv_dict_blk is instantiated for
+static bool dict_blk_shape(int br, int bc) {
+  return (br == 3 && bc == 1) || (br == 1 && bc == 3) || (br == 2 && bc == 1) || (br == 1 && bc == 2);
+}
+SpmvPath spmv_path(const BlockMat& A, int nv, int epi, int phase, bool dict_ok, bool second_output) {
+  if (dict_usable(A, dict_ok)) {
+    if (A.dict->rect) {
+      if (dict_blk_shape(A.br, A.bc) && nv == 1 && phase == 0 && (epi == EPI_STORE || epi == EPI_ACCUM) &&
+          !second_output)
+        return SpmvPath::DictBlock;
+    } else if (scalar_operands(A, nv) && epi != EPI_ACCUM && !(epi == EPI_STORE && second_output)) {
+      return SpmvPath::DictScalar;
+    }
+  }
   const Pattern& p = *A.pat;
-  if (A.dict_ready && A.dict->rect && (a_in.dict_ok || A.dict->exact) && a_in.phase == 0 && nv == 1 &&
-      (EPI == EPI_STORE || EPI == EPI_ACCUM) && !a_in.y2) {
-    const StencilDict& d = *A.dict;
-    const int n_wg = (d.n_rows + 255) / 256;
-    const int grid = (n_wg + 7) & ~7;
-    const size_t lds = (size_t)d.max_local * d.lmax * (8 * d.bsz + 4) + (size_t)d.max_local * 4 + 8;
-#define NSFEM_DICTB(BR, BC)                                                                              \
-  hipLaunchKernelGGL((k_spmv_dict_blk<BR, BC, EPI>), dim3(grid), dim3(256), lds, s, d.n_rows, n_wg,     \
-                     d.lid.p, d.cbase.p, d.wg_ptr.p, d.wg_list.p, d.len.p, d.off.p, A.dict_vals.p,      \
-                     d.lmax, d.max_local, a_in)
-    bool done = true;
-    if (A.br == 3 && A.bc == 1) NSFEM_DICTB(3, 1);
-    else if (A.br == 1 && A.bc == 3) NSFEM_DICTB(1, 3);
-    else if (A.br == 2 && A.bc == 1) NSFEM_DICTB(2, 1);
-    else if (A.br == 1 && A.bc == 2) NSFEM_DICTB(1, 2);
-    else done = false;
-#undef NSFEM_DICTB
-    if (done) {
-      NSFEM_HIP(hipGetLastError());
-      return;
-    }
-  }
-  if (A.dict_ready && !A.dict->rect && A.br == 1 && A.bc == 1 && (a_in.dict_ok || A.dict->exact) && EPI != EPI_ACCUM && !(EPI == EPI_STORE && a_in.y2) && nv >= 1 && nv <= 3) {
-    const StencilDict& d = *A.dict;
-    const int n_all = (d.n_rows + 255) / 256;
-    int n_wg = n_all;
-    SpmvArgs a = a_in;
-    a.skip0 = n_all;
-    a.skipn = 0;
-    if (a.phase == 1) {                    // interior workgroups only: shift the logical index
-      n_wg = p.wg_w1 - p.wg_w0;
-      a.skip0 = 0;
-      a.skipn = p.wg_w0;
-    } else if (a.phase == 2) {
-      n_wg = n_all - (p.wg_w1 - p.wg_w0);
-      a.skip0 = p.wg_w0;
-      a.skipn = p.wg_w1 - p.wg_w0;
-    }
-    if (n_wg <= 0) return;
-    const int grid = (n_wg + 7) & ~7;
-    const size_t lds = (size_t)d.max_local * d.lmax * 12 + (size_t)d.max_local * 12;
-#define NSFEM_DICT_LAUNCH(KERNEL, NV)                                                                  \
-  hipLaunchKernelGGL((KERNEL<NV, EPI>), dim3(grid), dim3(256), lds, s, d.n_rows, n_wg, d.lid.p,        \
-                     d.wg_ptr.p, d.wg_list.p, d.len.p, d.off.p, A.dict_vals.p, d.dpos.p, d.lmax,       \
-                     d.max_local, a)
-    if (nv == 1) NSFEM_DICT_LAUNCH(k_spmv_dict_w8, 1);
-    else if (nv == 2) NSFEM_DICT_LAUNCH(k_spmv_dict_w8, 2);
-    else NSFEM_DICT_LAUNCH(k_spmv_dict, 3);
-#undef NSFEM_DICT_LAUNCH
-    NSFEM_HIP(hipGetLastError());
-    return;
-  }
-  if (A.sell_ready && p.n_slices > 0 && A.br == 1 && A.bc == 1 && nv >= 1 && nv <= 3) {
-    SpmvArgs a = a_in;
-    const int nwg_all = (p.n_slices + 3) / 4;
-    int nwg = nwg_all;
-    a.skip0 = nwg_all;
-    a.skipn = 0;
-    if (a.phase == 1) {                    // interior workgroups only: shift the logical index
-      nwg = p.sell_w1 - p.sell_w0;
-      a.skip0 = 0;
-      a.skipn = p.sell_w0;
-    } else if (a.phase == 2) {
-      nwg = nwg_all - (p.sell_w1 - p.sell_w0);
-      a.skip0 = p.sell_w0;
-      a.skipn = p.sell_w1 - p.sell_w0;
-    }
-    if (nwg <= 0) return;
-    XcdSplit xs;
-    for (int x = 0; x < 9; ++x) xs.s[x] = 0;
-    int grid = (nwg + 7) & ~7;
-    if (a.phase == 0) {          // whole operator: balanced contiguous XCD ranges
-      int most = 0;
-      for (int x = 0; x < 9; ++x) xs.s[x] = p.sell_xcd[x];
-      for (int x = 0; x < 8; ++x) most = std::max(most, xs.s[x + 1] - xs.s[x]);
-      grid = 8 * most;
-    }
-    // groups of 4 entries per lane, 8 waves per SIMD: measured 247-253 us on the 3D n = 64 smoothing launch against
-    // groups of 8: 264 us, 8 software pipelined: 255-263 us, 12 / 10 pipelined: 256-267 us
-#define NSFEM_SELL_LAUNCH(NV)                                                                        \
-  hipLaunchKernelGGL((k_spmv_sell<NV, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows,                  \
-                     p.n_slices, nwg, p.sell_ptr.p, p.sell_col.p, A.sell_vals.p, a, xs)
-    if (nv == 1) NSFEM_SELL_LAUNCH(1);
-    else if (nv == 2) NSFEM_SELL_LAUNCH(2);
-    else NSFEM_SELL_LAUNCH(3);
-#undef NSFEM_SELL_LAUNCH
-    NSFEM_HIP(hipGetLastError());
-    return;
-  }
+  if (A.sell_ready && p.n_slices > 0 && scalar_operands(A, nv)) return SpmvPath::Sell;
   // measured (n = 512): the stream kernel wins on every operator except the short-row P2 x P1
   // gradient (4.6 entries per row), which keeps the lane-group kernel
   const bool long_rows = (double)p.nnz >= 6.0 * p.n_rows;
-  const bool stream = p.n_rblk > 0 && long_rows;
-  if (stream) {
-    // interior / halo-adjacent split of a partitioned product (see product_with_halo)
-    SpmvArgs a = a_in;
-    int nb = p.n_rblk;
-    a.skip0 = nb;
-    a.skipn = 0;
-    if (a.phase == 1) {
-      nb = p.int_b1 - p.int_b0;
-      a.skip0 = nb;
-    } else if (a.phase == 2) {
-      nb = p.n_rblk - (p.int_b1 - p.int_b0);
-      a.skip0 = p.int_b0;
-      a.skipn = p.int_b1 - p.int_b0;
+  return p.n_rblk > 0 && long_rows ? SpmvPath::Stream : SpmvPath::LaneGroup;
+}
+
+// The ONE place that turns the run-time (br, bc, nv) of a CSR product into template arguments: f(SpmvShape<BR, BC, NV>)
+// for exactly the nine shapes the stream and the lane-group kernels are instantiated for
+template <int BR_, int BC_, int NV_>
+struct SpmvShape { static constexpr int BR = BR_, BC = BC_, NV = NV_; };
+template <class F, int... BR, int... BC, int... NV>
+static bool with_shape_of(int br, int bc, int nv, F&& f, SpmvShape<BR, BC, NV>...) {
+  return ((br == BR && bc == BC && nv == NV ? (f(SpmvShape<BR, BC, NV>{}), true) : false) || ...);
+}
+template <class F>
+static void with_spmv_shape(int br, int bc, int nv, F&& f) {
+  if (!with_shape_of(br, bc, nv, f, SpmvShape<2, 2, 1>{}, SpmvShape<1, 1, 2>{}, SpmvShape<1, 1, 1>{},
+                     SpmvShape<1, 2, 1>{}, SpmvShape<2, 1, 1>{}, SpmvShape<3, 3, 1>{}, SpmvShape<1, 1, 3>{},
+                     SpmvShape<1, 3, 1>{}, SpmvShape<3, 1, 1>{}))
+    throw Error(NSFEM_ERR_ARG, "unsupported block shape in spmv");
+}
+
+// Interior / halo-adjacent split of a partitioned product (see product_with_halo) over n_all workgroups (row blocks)
+// of which [w0, w1) touch no ghost column: the launch runs `count` of them and every kernel maps its logical index
+// by  if (i >= skip0) i += skipn.  Phase 0 all, 1 the interior ones, 2 the others.
+struct PhaseSplit { int count, skip0, skipn; };
+static PhaseSplit phase_split(int n_all, int w0, int w1, int phase) {
+  if (phase == 1) return {w1 - w0, 0, w0};                    // interior only: shift the logical index
+  if (phase == 2) return {n_all - (w1 - w0), w0, w1 - w0};    // jump over the interior
+  return {n_all, n_all, 0};
+}
+static SpmvArgs with_split(SpmvArgs a, const PhaseSplit& ps) {
+  a.skip0 = ps.skip0;
+  a.skipn = ps.skipn;
+  return a;
+}
+
+// Launch geometry of a dictionary kernel: workgroups of 256 rows, the grid rounded to the 8 XCDs, and the LDS copy of
+// the entries a workgroup uses -- (8 bsz + 4) bytes per stencil position and stencil_bytes per stencil (what the kernel
+// keeps beside the table) + pad
+struct DictGeom { int n_wg, grid; size_t lds; };
+static DictGeom dict_geom(const StencilDict& d, int stencil_bytes, int pad = 0) {
+  const int n_wg = (d.n_rows + 255) / 256;
+  return {n_wg, (n_wg + 7) & ~7,
+          (size_t)d.max_local * d.lmax * (8 * d.bsz + 4) + (size_t)d.max_local * stencil_bytes + pad};
+}
+constexpr int kDictScalarStencilBytes = 12;   // k_spmv_dict / k_spmv_dict_w8
+
+template <int EPI>
+static void spmv_dispatch(hipStream_t s, const BlockMat& A, int nv, const SpmvArgs& a_in) {
+  const Pattern& p = *A.pat;
+  switch (spmv_path(A, nv, EPI, a_in.phase, a_in.dict_ok != 0, a_in.y2 != nullptr)) {
+    case SpmvPath::DictBlock: {
+      const StencilDict& d = *A.dict;
+      const DictGeom g = dict_geom(d, 4, 8);
+      with_int<31, 13, 21, 12>(A.br * 10 + A.bc, [&](auto shape) {          // (dict_blk_shape: no other reaches here)
+        constexpr int BR = decltype(shape)::value / 10, BC = decltype(shape)::value % 10;
+        hipLaunchKernelGGL((k_spmv_dict_blk<BR, BC, EPI>), dim3(g.grid), dim3(256), g.lds, s, d.n_rows, g.n_wg,
+                           d.lid.p, d.cbase.p, d.wg_ptr.p, d.wg_list.p, d.len.p, d.off.p, A.dict_vals.p, d.lmax,
+                           d.max_local, a_in);
+      });
+      break;
     }
-    if (nb <= 0) return;
-    const int grid = (nb + 7) & ~7;
-    const int32_t* rb1 = p.rblk1.p + (a.phase == 1 ? p.int_b0 : 0);
-#define NSFEM_STREAM(BR, BC, NV)                                                            \
-  hipLaunchKernelGGL((k_spmv_stream_v1<BR, BC, NV, EPI>), dim3(grid), dim3(256), 0, s, nb,  \
-                     rb1, p.rowptr.p, p.col.p, A.vals.p, a)
-    if (A.br == 2 && A.bc == 2 && nv == 1) NSFEM_STREAM(2, 2, 1);
-    else if (A.br == 1 && A.bc == 1 && nv == 2) NSFEM_STREAM(1, 1, 2);
-    else if (A.br == 1 && A.bc == 1 && nv == 1) NSFEM_STREAM(1, 1, 1);
-    else if (A.br == 1 && A.bc == 2 && nv == 1) NSFEM_STREAM(1, 2, 1);
-    else if (A.br == 2 && A.bc == 1 && nv == 1) NSFEM_STREAM(2, 1, 1);
-    else if (A.br == 3 && A.bc == 3 && nv == 1) NSFEM_STREAM(3, 3, 1);
-    else if (A.br == 1 && A.bc == 1 && nv == 3) NSFEM_STREAM(1, 1, 3);
-    else if (A.br == 1 && A.bc == 3 && nv == 1) NSFEM_STREAM(1, 3, 1);
-    else if (A.br == 3 && A.bc == 1 && nv == 1) NSFEM_STREAM(3, 1, 1);
-    else throw Error(NSFEM_ERR_ARG, "unsupported block shape in spmv");
-#undef NSFEM_STREAM
-    NSFEM_HIP(hipGetLastError());
-    return;
+    case SpmvPath::DictScalar: {
+      const StencilDict& d = *A.dict;
+      const DictGeom g = dict_geom(d, kDictScalarStencilBytes);
+      const PhaseSplit ps = phase_split(g.n_wg, p.wg_w0, p.wg_w1, a_in.phase);
+      if (ps.count <= 0) return;
+      const SpmvArgs a = with_split(a_in, ps);
+      const int grid = (ps.count + 7) & ~7;
+      with_int<1, 2, 3>(nv, [&](auto nvc) {
+        constexpr int NV = decltype(nvc)::value;
+        auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), g.lds, s, d.n_rows, ps.count, d.lid.p, d.wg_ptr.p,
+                             d.wg_list.p, d.len.p, d.off.p, A.dict_vals.p, d.dpos.p, d.lmax, d.max_local, a);
+        };
+        if constexpr (NV == 3) launch(k_spmv_dict<3, EPI>);       // (the two launch shapes of spmv_dict_body)
+        else launch(k_spmv_dict_w8<NV, EPI>);
+      });
+      break;
+    }
+    case SpmvPath::Sell: {
+      const PhaseSplit ps = phase_split((p.n_slices + 3) / 4, p.sell_w0, p.sell_w1, a_in.phase);
+      if (ps.count <= 0) return;
+      const SpmvArgs a = with_split(a_in, ps);
+      XcdSplit xs;
+      for (int x = 0; x < 9; ++x) xs.s[x] = 0;
+      int grid = (ps.count + 7) & ~7;
+      if (a.phase == 0) {          // whole operator: balanced contiguous XCD ranges
+        int most = 0;
+        for (int x = 0; x < 9; ++x) xs.s[x] = p.sell_xcd[x];
+        for (int x = 0; x < 8; ++x) most = std::max(most, xs.s[x + 1] - xs.s[x]);
+        grid = 8 * most;
+      }
+      // groups of 4 entries per lane, 8 waves per SIMD: measured 247-253 us on the 3D n = 64 smoothing launch against
+      // groups of 8: 264 us, 8 software pipelined: 255-263 us, 12 / 10 pipelined: 256-267 us
+      with_int<1, 2, 3>(nv, [&](auto nvc) {
+        hipLaunchKernelGGL((k_spmv_sell<decltype(nvc)::value, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows,
+                           p.n_slices, ps.count, p.sell_ptr.p, p.sell_col.p, A.sell_vals.p, a, xs);
+      });
+      break;
+    }
+    case SpmvPath::Stream: {
+      // The same encoding as the dictionary and SELL kernels, with the unshifted rblk1 pointer: k_spmv_stream_v1
+      // tests lb < n_rblk on the logical index first and then applies  if (lb >= skip0) lb += skipn  before it reads
+      // rblk[lb], rblk[lb + 1] -- the interior launch (skip0 = 0, skipn = int_b0) reads rblk1[lb + int_b0], the entries
+      // a pointer shifted by int_b0 would give it.
+      const PhaseSplit ps = phase_split(p.n_rblk, p.int_b0, p.int_b1, a_in.phase);
+      if (ps.count <= 0) return;
+      const SpmvArgs a = with_split(a_in, ps);
+      const int grid = (ps.count + 7) & ~7;
+      with_spmv_shape(A.br, A.bc, nv, [&](auto sh) {
+        using S = decltype(sh);
+        hipLaunchKernelGGL((k_spmv_stream_v1<S::BR, S::BC, S::NV, EPI>), dim3(grid), dim3(256), 0, s, ps.count,
+                           p.rblk1.p, p.rowptr.p, p.col.p, A.vals.p, a);
+      });
+      break;
+    }
+    case SpmvPath::LaneGroup: {
+      // (the lane-group kernel has no row-block split: the interior phase is empty, the halo-adjacent
+      // phase computes every row)
+      if (a_in.phase == 1) return;
+      const SpmvArgs& a = a_in;
+      // lanes per block row: 4 for short rows (P1 7-point, P2 x P1), 8 otherwise
+      // measured on MI355X (n = 512): rows with <= ~200 B of matrix data
+      // (scalar P2 / P1 operators, grad) run 15-30 % faster with 4 lanes per row, the 2x2
+      // Jacobian (414 B/row) and div (460 B/row) with 8
+      const double row_bytes = (double)p.nnz / (p.n_rows > 0 ? p.n_rows : 1) * (8.0 * A.br * A.bc + 4.0);
+      int G = row_bytes <= 200.0 ? 4 : (row_bytes <= 1600.0 ? 8 : 16);
+      // interpolation-type operators (<= 2 entries per row, e.g. the P2 <- P1 prolongation): two
+      // lanes per row are enough and halve the idle lanes (needs G >= outputs per row)
+      if ((double)p.nnz <= 2.2 * p.n_rows && A.br * nv <= 2) G = 2;
+      if (G < A.br * nv) G = 4;
+      const int rpb = 256 / G;
+      const int grid = ((p.n_rows + rpb - 1) / rpb + 7) & ~7;
+      with_spmv_shape(A.br, A.bc, nv, [&](auto sh) {
+        using S = decltype(sh);
+        with_int<2, 4, 8, 16>(G, [&](auto gc) {
+          // (G = 2 is chosen above only where BR * NV <= 2: the other shapes have no two-lane instantiation)
+          constexpr int GG = (decltype(gc)::value == 2 && S::BR * S::NV > 2) ? 4 : decltype(gc)::value;
+          hipLaunchKernelGGL((k_spmv<S::BR, S::BC, S::NV, GG, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows,
+                             p.rowptr.p, p.col.p, A.vals.p, a);
+        });
+      });
+      break;
+    }
   }
-  // (the lane-group kernel has no row-block split: the interior phase is empty, the halo-adjacent
-  // phase computes every row)
-  if (a_in.phase == 1) return;
-  const SpmvArgs& a = a_in;
-  // lanes per block row: 4 for short rows (P1 7-point, P2 x P1), 8 otherwise
-  // measured on MI355X (n = 512): rows with <= ~200 B of matrix data
-  // (scalar P2 / P1 operators, grad) run 15-30 % faster with 4 lanes per row, the 2x2
-  // Jacobian (414 B/row) and div (460 B/row) with 8
-  const double row_bytes = (double)p.nnz / (p.n_rows > 0 ? p.n_rows : 1) * (8.0 * A.br * A.bc + 4.0);
-  int G = row_bytes <= 200.0 ? 4 : (row_bytes <= 1600.0 ? 8 : 16);
-  // interpolation-type operators (<= 2 entries per row, e.g. the P2 <- P1 prolongation): two
-  // lanes per row are enough and halve the idle lanes (needs G >= outputs per row)
-  if ((double)p.nnz <= 2.2 * p.n_rows && A.br * nv <= 2) G = 2;
-  if (G < A.br * nv) G = 4;
-  const int rpb = 256 / G;
-  int grid = (p.n_rows + rpb - 1) / rpb;
-  grid = (grid + 7) & ~7;
-#define NSFEM_SPMV(BR, BC, NV)                                                                \
-  do {                                                                                        \
-    if (G == 2 && BR * NV <= 2)                                                               \
-      hipLaunchKernelGGL((k_spmv<BR, BC, NV, (BR * NV <= 2 ? 2 : 4), EPI>), dim3(grid), dim3(256), 0, s, \
-                         p.n_rows, p.rowptr.p, p.col.p, A.vals.p, a);                         \
-    else if (G == 4)                                                                          \
-      hipLaunchKernelGGL((k_spmv<BR, BC, NV, 4, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows,  \
-                         p.rowptr.p, p.col.p, A.vals.p, a);                                   \
-    else if (G == 8)                                                                          \
-      hipLaunchKernelGGL((k_spmv<BR, BC, NV, 8, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows,  \
-                         p.rowptr.p, p.col.p, A.vals.p, a);                                   \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_spmv<BR, BC, NV, 16, EPI>), dim3(grid), dim3(256), 0, s, p.n_rows, \
-                         p.rowptr.p, p.col.p, A.vals.p, a);                                   \
-  } while (0)
-  if (A.br == 2 && A.bc == 2 && nv == 1) NSFEM_SPMV(2, 2, 1);
-  else if (A.br == 1 && A.bc == 1 && nv == 2) NSFEM_SPMV(1, 1, 2);
-  else if (A.br == 1 && A.bc == 1 && nv == 1) NSFEM_SPMV(1, 1, 1);
-  else if (A.br == 1 && A.bc == 2 && nv == 1) NSFEM_SPMV(1, 2, 1);
-  else if (A.br == 2 && A.bc == 1 && nv == 1) NSFEM_SPMV(2, 1, 1);
-  else if (A.br == 3 && A.bc == 3 && nv == 1) NSFEM_SPMV(3, 3, 1);
-  else if (A.br == 1 && A.bc == 1 && nv == 3) NSFEM_SPMV(1, 1, 3);
-  else if (A.br == 1 && A.bc == 3 && nv == 1) NSFEM_SPMV(1, 3, 1);
-  else if (A.br == 3 && A.bc == 1 && nv == 1) NSFEM_SPMV(3, 1, 1);
-  else throw Error(NSFEM_ERR_ARG, "unsupported block shape in spmv");
-#undef NSFEM_SPMV
   NSFEM_HIP(hipGetLastError());
 }
+
 
 static SpmvArgs make_args(const double* x, const double* b, double* y, const uint8_t* mask,
                           int maskmode) {
@@ -2553,7 +2540,7 @@ static SpmvArgs make_args(const double* x, const double* b, double* y, const uin
 // dictionary copy (the caller multiplies and gathers separately).
 bool launch_spmv_with_gather(hipStream_t s, const BlockMat& A, int nv, const double* x, double* y,
                              const uint8_t* rowmask, int maskmode, const int32_t* gptr, const double* gbuf) {
-  if (!A.dict_ready || A.dict->rect || A.br != 1 || A.bc != 1 || nv < 1 || nv > 3) return false;
+  if (spmv_path(A, nv, EPI_STORE, 0, true, false) != SpmvPath::DictScalar) return false;
   SpmvArgs a = make_args(x, nullptr, y, rowmask, maskmode);
   a.dict_ok = 1;
   a.gptr = gptr;
@@ -2609,17 +2596,13 @@ void launch_spmv_axpy(hipStream_t s, const BlockMat& A, int nv, double scale, co
 // dictionary copy a residual may use (the caller runs the two launches)
 bool launch_residual_sum(hipStream_t s, const BlockMat& A, const double* z, const double* r, double* q,
                          const double* base, double* psum) {
-  if (!A.dict_ready || A.dict->rect || A.br != 1 || A.bc != 1 || !A.dict->exact) return false;
+  if (spmv_path(A, 1, EPI_RESID_SUM, 0, false, false) != SpmvPath::DictScalar) return false;
   const StencilDict& d = *A.dict;
-  SpmvArgs a = make_args(z, r, q, nullptr, MASK_NONE);
+  const DictGeom g = dict_geom(d, kDictScalarStencilBytes);
+  SpmvArgs a = with_split(make_args(z, r, q, nullptr, MASK_NONE), phase_split(g.n_wg, 0, 0, 0));
   a.base = base;
   a.psum = psum;
-  const int n_wg = (d.n_rows + 255) / 256;
-  a.skip0 = n_wg;
-  a.skipn = 0;
-  const int grid = (n_wg + 7) & ~7;
-  const size_t lds = (size_t)d.max_local * d.lmax * 12 + (size_t)d.max_local * 12;
-  hipLaunchKernelGGL((k_spmv_dict_w8<1, EPI_RESID_SUM>), dim3(grid), dim3(256), lds, s, d.n_rows, n_wg, d.lid.p,
+  hipLaunchKernelGGL((k_spmv_dict_w8<1, EPI_RESID_SUM>), dim3(g.grid), dim3(256), g.lds, s, d.n_rows, g.n_wg, d.lid.p,
                      d.wg_ptr.p, d.wg_list.p, d.len.p, d.off.p, A.dict_vals.p, d.dpos.p, d.lmax, d.max_local, a);
   NSFEM_HIP(hipGetLastError());
   return true;
@@ -2628,10 +2611,8 @@ bool launch_residual_sum(hipStream_t s, const BlockMat& A, const double* z, cons
 // Can the pair kernel replace the products with M (two interleaved components) and B (2 x 1 blocks) on the same rows?
 // Only where both run on exact dictionary copies today (k_spmv_dict_w8<2, .> and k_spmv_dict_blk<2, 1, .>).
 bool spmv_pair_available(const BlockMat& M, const BlockMat& B) {
-  if (!M.dict_ready || !B.dict_ready) return false;
-  const StencilDict &dm = *M.dict, &db = *B.dict;
-  return !dm.rect && dm.exact && M.br == 1 && M.bc == 1 && db.rect && db.exact && B.br == 2 && B.bc == 1 &&
-         dm.n_rows == db.n_rows;
+  return spmv_path(M, 2, EPI_STORE, 0, false, false) == SpmvPath::DictScalar && B.br == 2 && B.bc == 1 &&
+         spmv_path(B, 1, EPI_ACCUM, 0, false, false) == SpmvPath::DictBlock && M.dict->n_rows == B.dict->n_rows;
 }
 template <int EPI>
 static void launch_pair(hipStream_t s, const BlockMat& M, const BlockMat& B, const PairArgs& a) {
@@ -2641,11 +2622,8 @@ static void launch_pair(hipStream_t s, const BlockMat& M, const BlockMat& B, con
   d.sval_m = M.dict_vals.p; d.lmax_m = dm.lmax; d.max_local_m = dm.max_local;
   d.lid_b = db.lid.p; d.cbase_b = db.cbase.p; d.wg_ptr_b = db.wg_ptr.p; d.wg_list_b = db.wg_list.p;
   d.slen_b = db.len.p; d.soff_b = db.off.p; d.sval_b = B.dict_vals.p; d.lmax_b = db.lmax; d.max_local_b = db.max_local;
-  const int n_wg = (dm.n_rows + 255) / 256;
-  const int grid = (n_wg + 7) & ~7;
-  const size_t lds = (size_t)dm.max_local * dm.lmax * 12 + (size_t)dm.max_local * 4 +
-                     (size_t)db.max_local * db.lmax * (8 * 2 + 4) + (size_t)db.max_local * 4;
-  hipLaunchKernelGGL((k_spmv_dict_pair<EPI>), dim3(grid), dim3(256), lds, s, dm.n_rows, n_wg, d, a);
+  const DictGeom gm = dict_geom(dm, 4), gb = dict_geom(db, 4);      // (both tables, 4 bytes per stencil each)
+  hipLaunchKernelGGL((k_spmv_dict_pair<EPI>), dim3(gm.grid), dim3(256), gm.lds + gb.lds, s, dm.n_rows, gm.n_wg, d, a);
   NSFEM_HIP(hipGetLastError());
 }
 // y = M x + c2 B z  (spmv_pair_available(M, B))

@@ -237,6 +237,14 @@ void launch_cfl(hipStream_t s, const MeshDev& m, const double* u, double scale, 
 
 // SpMV row-mask modes
 enum MaskMode { MASK_NONE = 0, MASK_IDENTITY = 1, MASK_ZERO = 2 };
+// SpMV epilogues (described at the kernels, linalg.hip)
+enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_ACCUM = 2, EPI_CHEB = 3, EPI_RESID_SUM = 4 };
+// The kernel family a product with A runs on.  spmv_path is the ONE statement of the rule ("Which kernel
+// family a product runs on"): the dispatcher switches on it, the fused launches state their preconditions through it
+// and the test hook reports it.
+// phase, dict_ok: as for launch_spmv below; second_output: EPI_STORE with the fused first smoothing step (y2)
+enum class SpmvPath { DictBlock, DictScalar, Sell, Stream, LaneGroup };
+SpmvPath spmv_path(const BlockMat& A, int nv, int epi, int phase, bool dict_ok, bool second_output);
 
 // -------------------------- kernel launch wrappers ------------------------------
 // y = A x.  nv = number of interleaved right-hand sides the scalar blocks act on

@@ -93,6 +93,74 @@ def test_products_and_residuals_of_every_family_match_the_oracle(dim, n, exact, 
     ctx.close()
 
 
+# The dispatcher's path rule, written out: used_family by (epilogue, family, dict_ok) on a mesh whose dictionary is
+# bitwise exact and on one whose is not, the same for nv = 1, 2, 3.  Epilogue 0 product, 1 residual, 2 smoothing step;
+# family 0 leaves the choice to the dispatcher.  None: the hook refuses the call (these meshes have no SELL-64 layout:
+# fewer than 2048 rows or fewer than 20 entries per row).  A residual never runs on an inexact dictionary, a product
+# only where the caller allows it (dict_ok), a smoothing step always.
+PATH_RULE = {
+    # (epilogue, family, dict_ok): (exact, inexact)
+    (0, 0, 0): (DICT, CSR), (0, 0, 1): (DICT, DICT),
+    (0, 1, 0): (CSR, CSR), (0, 1, 1): (CSR, CSR),
+    (0, 2, 0): (None, None), (0, 2, 1): (None, None),
+    (0, 3, 0): (DICT, CSR), (0, 3, 1): (DICT, DICT),
+    (1, 0, 0): (DICT, CSR), (1, 0, 1): (DICT, CSR),
+    (1, 1, 0): (CSR, CSR), (1, 1, 1): (CSR, CSR),
+    (1, 2, 0): (None, None), (1, 2, 1): (None, None),
+    (1, 3, 0): (DICT, CSR), (1, 3, 1): (DICT, CSR),
+    (2, 0, 0): (DICT, DICT), (2, 0, 1): (DICT, DICT),
+    (2, 1, 0): (CSR, CSR), (2, 1, 1): (CSR, CSR),
+    (2, 2, 0): (None, None), (2, 2, 1): (None, None),
+    (2, 3, 0): (DICT, DICT), (2, 3, 1): (DICT, DICT),
+}
+
+
+# (a dictionary needs 1024 rows: n = 16, 33 x 33 P2 nodes, is the smallest 2D lattice that gets one -- n = 12 has none --
+# and its spacing is binary; n = 17 is the smallest whose dictionary is not bitwise exact; 3D n = 8: 64 entries, exact)
+@pytest.mark.parametrize("dim,n,exact", [(2, 16, True), (2, 17, False), (3, 8, True)])
+def test_the_dispatchers_path_rule_is_the_table(dim, n, exact):
+    """used_family of every (epilogue, family, dict_ok, nv) against PATH_RULE on the smallest lattices that have an exact
+    and an inexact dictionary (P2 space), and the values of every call against the oracle's matrix at the tolerances
+    of the tests around this one"""
+    mesh, dm, s = _lattice_case(dim, n)
+    ctx = context(mesh, dm)
+    coef = {0: (1.7, 0.31), 1: (1.7, 0.31), 2: (1500.0, 0.01)}
+    mats = {ab: (ab[0] * s.mass_p2() + ab[1] * s.stiffness_p2()).tocsr() for ab in set(coef.values())}
+    nrows = dm.n_p2
+    rng = np.random.default_rng(11 * dim + n)
+    for nv in (1, 2, 3):
+        x, b, d, mask = _random_case(rng, nrows, nv)
+        for (epilogue, family, dict_ok), want in sorted(PATH_RULE.items()):
+            a, bc = coef[epilogue]
+            A = mats[(a, bc)]
+            args = dict(a=a, b_coef=bc, family=family, epilogue=epilogue, dict_ok=bool(dict_ok))
+            if epilogue == 1:
+                args.update(b=b, mask=mask, maskmode=1)
+            elif epilogue == 2:
+                args.update(b=b, d=d, mask=mask, maskmode=2, steps=1, c1=[0.25], c2=[0.55])
+            key = (epilogue, family, dict_ok, nv)
+            used = want[0 if exact else 1]
+            if used is None:
+                with pytest.raises(nat.NativeError):
+                    ctx.kernel_apply(0, nv, x, **args)
+                continue
+            out = ctx.kernel_apply(0, nv, x, **args)
+            assert out["dict_entries"] > 0 and out["dict_exact"] == exact, key
+            assert out["used_family"] == used, key
+            ref = (A @ x.reshape(nrows, nv)).ravel()
+            bound = abs(A).max() * np.abs(x).max() * 65
+            if epilogue == 0:
+                tol = 1e-13 if (exact or used == CSR) else 2.0 ** -38
+                assert np.abs(out["y"] - ref).max() <= tol * bound, key
+            elif epilogue == 1:
+                assert np.abs(out["y"] - np.where(mask == 1, b - x, b - ref)).max() <= 1e-13 * bound, key
+            else:
+                xr, dr = _cheb_reference(A, nv, x, b, d, mask, [0.25], [0.55])
+                tol = 1e-13 if (exact or used == CSR) else 2.0 ** -36
+                assert rel(out["y"], xr) < tol and rel(out["d"], dr) < tol, key
+    ctx.close()
+
+
 @pytest.mark.parametrize("dim,n,order", [(3, 16, "parity")])
 def test_sell_kernel_matches_the_oracle(dim, n, order):
     """SELL-64 (tetrahedral P2 operators, >= 20 entries per row, parity-class numbering: consecutive rows of equal
