@@ -540,7 +540,24 @@ int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]);
  * Laws 4 and 5 take the whole tensor G_ab = g_ab = d_b u_a, not gamma alone.  A 2D field counts as the 3D field that
  * does not depend on z: G is the 3x3 tensor with a zero third row and column (so Sd_33 = -tr H / 3 is kept in B).
  * V(u), the cell means, the stored vectors and the explicit treatment are those of laws 1 and 2 with this nu_x.  There
- * is no law 3: ids 3 and 6 and above are unknown.
+ * is no law 3: ids 3, 6, 7 and 9 and above are unknown.
+ *   law 8  dynamic Smagorinsky (Germano et al. 1991, Lilly 1992)              params = {alpha finite and > 1,
+ *          nu_x = c_K Delta_K^2 gamma with C_s^2 computed on the device       cs2_max finite and > 0}
+ *          from the velocity level the term is evaluated on.  With |K| = |det J_K| / dim! and the degree-5 rule:
+ *          1. cell moments m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q of f = u_a, u_a u_b, S_ab, Delta_K^2 gamma S_ab
+ *             (a <= b; G_ab from the differences u_k - u_0 of the nodal values, so a constant field has G = 0 exactly)
+ *          2. test filter at a vertex v over its patch of cells, ascending: W_v = sum |K|, hat f_v = (sum m_K[f]) / W_v,
+ *             Delta_v^2 = (sum |K| Delta_K^2) / W_v, hat gamma_v = sqrt(2 hat S : hat S)
+ *          3. L = hat(u u) - hat u hat u, Ld its deviator, M = 2 (hat(Delta^2 gamma S) - alpha^2 Delta_v^2 hat gamma
+ *             hat S), LM_v = Ld : M, MM_v = M : M
+ *          4. per averaging group g of vertices (nsfem_set_dynamic_groups; default: all vertices): num_g = sum W_v LM_v,
+ *             den_g = sum W_v MM_v in a fixed order, cs2_g = min(max(num_g / den_g, 0), cs2_max) where den_g > 0, else 0
+ *          5. c_K = the mean over the vertices of K of cs2_g(v)
+ *          alpha is the ratio of the test to the grid filter width (usually 2), cs2_max the clip (0.09 = 0.3^2).  Three
+ *          launches (k_dyn_moments, k_dyn_vertex, k_dyn_reduce) before every element launch of this law, on that
+ *          launch's velocity level: N(u^(n-1)) keeps the constant of its own level, and a new constant invalidates
+ *          nothing.  Setting law 8 resets the groups to the global one.  No subgrid heat flux goes with this law
+ *          (nsfem_set_scalar_sgs refuses as for law 0).
  * A change of law or parameters invalidates the stored vectors.  NSFEM_ERR_ARG: unknown law, parameters outside these
  * ranges or not finite, a law other than 0 on contexts with a communicator; nsfem_step_ipcs and nsfem_step_bdf refuse
  * to run while a law other than 0 is set. */
@@ -554,6 +571,17 @@ int nsfem_viscosity_cells(nsfem_ctx* ctx, int velocity_slot, double* out_host);
 /* out = {current law, element-kernel launches so far (steps, hook and cell means), stored vectors N(u2) that had to be
  * recomputed with a law set, 0} */
 int nsfem_viscosity_info(nsfem_ctx* ctx, int64_t out[4]);
+/* Averaging groups of law 8: group_of_vertex [n_p1] with ids in [0, n_groups), n_groups >= 1; vertex ids are P1 dof
+ * ids.  Empty groups are allowed (cs2 = 0).  Other groups invalidate the stored vectors; the same groups again change
+ * nothing.  NSFEM_ERR_ARG: law 8 not set, n_groups < 1, an id out of range. */
+int nsfem_set_dynamic_groups(nsfem_ctx* ctx, int n_groups, const int32_t* group_of_vertex);
+/* Output and test hook: runs the procedure of law 8 on u = velocity_slot.  cs2_groups [n_groups]; sums [n_groups][2] =
+ * num_g, den_g or NULL; vertices [n_p1][3] = W_v, LM_v, MM_v or NULL.  No stored state is touched; two calls on the same
+ * state return the same bytes.  NSFEM_ERR_ARG: law 8 not set, other slots, contexts with a communicator. */
+int nsfem_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, double* cs2_groups, double* sums, double* vertices);
+/* out = {n_groups (0 before law 8 was ever set), runs of the procedure so far, launches of its three kernels, bytes of
+ * its device buffers}.  nsfem_viscosity_info keeps counting the element launches alone. */
+int nsfem_dynamic_info(nsfem_ctx* ctx, int64_t out[4]);
 /* ---- immersed bodies in the IMEX step: Brinkman volume penalisation (new; the reference has body-fitted meshes only).
  * The momentum equation gains (chi / eta) (u - u_s), chi the indicator of the solid, u_s its rigid velocity.  Up to
  * NSFEM_MAX_BODIES bodies, each a primitive with a signed distance d(x), negative inside:

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
     "nsfem_set_scalar_sgs", "nsfem_scalar_explicit", "nsfem_scalar_sgs_info",
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
+    "nsfem_set_dynamic_groups", "nsfem_dynamic_constant", "nsfem_dynamic_info",
     "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
     "nsfem_body_info",
     "nsfem_set_body_temperatures", "nsfem_body_scalar_residual", "nsfem_body_heat", "nsfem_body_heat_info",
@@ -220,6 +221,9 @@ def load_library(path=None):
         "nsfem_viscosity_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
         "nsfem_viscosity_cells": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_viscosity_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_dynamic_groups": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32)]),
+        "nsfem_dynamic_constant": (C.c_int, [vp, C.c_int, pd, pd, pd]),
+        "nsfem_dynamic_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_bodies": (C.c_int, [vp, C.c_int32, C.POINTER(Body), dbl, dbl]),
         "nsfem_move_bodies": (C.c_int, [vp, C.c_int32, C.POINTER(Body)]),
         "nsfem_body_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
@@ -604,7 +608,9 @@ class NsfemContext:
     def set_viscosity_law(self, law, params=None):
         """law 0 none (step_imex runs exactly as without this call), 1 Smagorinsky params = (C_s, ), 2 Carreau
         params = (a, lambda, n), 4 WALE params = (C_w, ), 5 Vreman params = (c, ) -- the last two from the whole
-        velocity-gradient tensor (include/nsfem.h); 3 is no law; up to four numbers, the rest are zeros"""
+        velocity-gradient tensor (include/nsfem.h); 8 dynamic Smagorinsky params = (alpha, cs2_max), its constant
+        computed on the device, averaging groups reset to the global one (``set_dynamic_groups``); 3, 6 and 7 are no
+        laws; up to four numbers, the rest are zeros"""
         p = np.zeros(4, dtype=np.float64)
         if params is not None:
             given = np.asarray(params, dtype=np.float64).ravel()
@@ -630,6 +636,34 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_viscosity_info(self._h, out))
         return dict(law=int(out[0]), element_launches=int(out[1]), recomputed=int(out[2]))
+
+    # -- dynamic Smagorinsky (law 8) ------------------------------------------------------
+    def set_dynamic_groups(self, n_groups, group_of_vertex):
+        """averaging groups of law 8: ``group_of_vertex`` [n_p1] with ids in [0, n_groups); empty groups give cs2 = 0"""
+        ids = np.ascontiguousarray(np.asarray(group_of_vertex).ravel(), dtype=np.int32)
+        if ids.size != self.n_p1:
+            raise ValueError("set_dynamic_groups: %d group ids for %d vertices" % (ids.size, self.n_p1))
+        self._check(self._lib.nsfem_set_dynamic_groups(self._h, int(n_groups), ids.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def dynamic_constant(self, velocity_slot=U0, details=False):
+        """C_s^2 of every averaging group for the velocity of the slot, [n_groups] (law 8; no stored state touched);
+        ``details``: also the sums [n_groups, 2] = num, den and the vertex rows [n_p1, 3] = W, LM, MM"""
+        n = self.dynamic_info()["groups"]
+        if n == 0:                           # (law 8 never set: let the driver say so)
+            n = 1
+        cs2 = np.empty(n, dtype=np.float64)
+        sums = np.empty((n, 2), dtype=np.float64) if details else None
+        vert = np.empty((self.n_p1, 3), dtype=np.float64) if details else None
+        self._check(self._lib.nsfem_dynamic_constant(self._h, int(velocity_slot), _dp(cs2),
+                                                     _dp(sums) if details else None, _dp(vert) if details else None))
+        return (cs2, sums, vert) if details else cs2
+
+    def dynamic_info(self):
+        """dict(groups, runs, launches, bytes): the averaging groups, the runs of the procedure, the launches of its
+        three kernels and the bytes of its device buffers"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_dynamic_info(self._h, out))
+        return dict(groups=int(out[0]), runs=int(out[1]), launches=int(out[2]), bytes=int(out[3]))
 
     # -- immersed bodies in the IMEX step (volume penalisation) --------------------------
     def _body_array(self, bodies):

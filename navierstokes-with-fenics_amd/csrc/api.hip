@@ -2583,6 +2583,73 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
   return 1;
 }
 
+// ---- dynamic Smagorinsky (law 8): host side of the Germano-Lilly procedure (kernels: assembly.hip)
+// group-sorted vertex list of the averaging groups: gvert ascending within a group, goff the offsets.  group null: one
+// group of all vertices
+static void dynamic_upload_groups(nsfem_ctx* c, int n_groups, const int32_t* group) {
+  nsfem_ctx::Dynamic& D = c->dyn;
+  const int nv = c->mesh.n_p1;
+  std::vector<int32_t> goff((size_t)n_groups + 1, 0), gvert((size_t)nv);
+  for (int v = 0; v < nv; ++v) ++goff[(size_t)(group ? group[v] : 0) + 1];
+  for (int g = 0; g < n_groups; ++g) goff[(size_t)g + 1] += goff[g];
+  std::vector<int32_t> fill(goff.begin(), goff.end() - 1);
+  for (int v = 0; v < nv; ++v) gvert[(size_t)fill[group ? group[v] : 0]++] = v;
+  D.goff.upload(goff, c->stream);
+  D.gvert.upload(gvert, c->stream);
+  if (D.sums.n != (size_t)n_groups * 3) D.sums.alloc((size_t)n_groups * 3);
+  D.n_groups = n_groups;
+  D.global = group == nullptr;
+  if (group) D.h_group.assign(group, group + nv);
+  else D.h_group.clear();
+}
+
+// buffers and the vertex-to-cell CSR (from the P1 connectivity: vertex ids are P1 dof ids), once
+static void dynamic_ensure(nsfem_ctx* c) {
+  nsfem_ctx::Dynamic& D = c->dyn;
+  if (D.allocated) return;
+  const MeshDev& m = c->mesh;
+  const int nl1 = m.dim + 1, nv = m.n_p1, nc = m.n_cells;
+  NSFEM_REQUIRE(c->h_p1map.size() == (size_t)nl1 * nc, "dynamic Smagorinsky: no host copy of the P1 connectivity");
+  std::vector<int32_t> vptr((size_t)nv + 1, 0), vcell((size_t)nl1 * nc);
+  for (size_t i = 0; i < c->h_p1map.size(); ++i) {
+    NSFEM_REQUIRE(c->h_p1map[i] >= 0 && c->h_p1map[i] < nv, "dynamic Smagorinsky: P1 connectivity out of range");
+    ++vptr[(size_t)c->h_p1map[i] + 1];
+  }
+  for (int v = 0; v < nv; ++v) vptr[(size_t)v + 1] += vptr[v];
+  std::vector<int32_t> fill(vptr.begin(), vptr.end() - 1);
+  for (int k = 0; k < nc; ++k)                               // ascending cells: every run comes out sorted
+    for (int i = 0; i < nl1; ++i) vcell[(size_t)fill[c->h_p1map[(size_t)k * nl1 + i]]++] = k;
+  D.vptr.upload(vptr, c->stream);
+  D.vcell.upload(vcell, c->stream);
+  const int nm = m.dim + 3 * (m.dim * (m.dim + 1) / 2) + 2;
+  D.mom.alloc((size_t)nm * nc);
+  D.vert.alloc((size_t)nv * 3);
+  D.cs2v.alloc((size_t)nv);
+  D.allocated = true;
+}
+
+// law 8: the three launches on the level u; returns the vertex field the element / facet launch on the SAME u reads.
+// Every other law: null, nothing launched
+static const double* dynamic_run(nsfem_ctx* c, const double* u) {
+  if (c->visc.law != 8) return nullptr;
+  nsfem_ctx::Dynamic& D = c->dyn;
+  NSFEM_REQUIRE(D.allocated, "dynamic Smagorinsky: buffers not allocated");
+  DynamicDev d;
+  d.n_groups = D.n_groups;
+  d.vptr = D.vptr.p;
+  d.vcell = D.vcell.p;
+  d.goff = D.goff.p;
+  d.gvert = D.gvert.p;
+  d.mom = D.mom.p;
+  d.vert = D.vert.p;
+  d.sums = D.sums.p;
+  d.cs2v = D.cs2v.p;
+  launch_dynamic_constant(c->stream, c->mesh, u, c->visc.p[0], c->visc.p[1], d);
+  ++D.runs;
+  D.launches += 3;
+  return D.cs2v.p;
+}
+
 // The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u).  The convective part
 // (with the Coriolis vector of the level) is in `n` already -- imex_rhs for u1, imex_form_n2 for u2; this adds the rest,
 // V (nsfem_set_viscosity_law) first and B (nsfem_set_bodies) second, each only when switched on: with law 0 / without
@@ -2596,7 +2663,8 @@ static int imex_rhs(nsfem_ctx* c, int path, const double* n2, double* n1, double
 // holds V(u2) + B(u2)); where it is formed afresh the terms are added the same way with b0 = 0 and rhs = null.
 static void imex_explicit_add(nsfem_ctx* c, const double* u, bool level_n, double b0, double* n, double* rhs) {
   if (c->visc.law != 0) {
-    launch_viscosity_cells(c->stream, c->mesh, u, 1.0, c->visc.law, c->visc.p, false);
+    const double* cs2v = dynamic_run(c, u);       // (law 8: the constant of THIS level, three launches; else null)
+    launch_viscosity_cells(c->stream, c->mesh, u, 1.0, c->visc.law, c->visc.p, false, cs2v);
     launch_viscosity_gather(c->stream, c->mesh, b0, n, rhs);
     ++c->visc.launches;
   }
@@ -2815,8 +2883,8 @@ extern "C" int nsfem_imex_rotation_info(nsfem_ctx* ctx, int64_t out[4]) {
 extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double params[4]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
-  NSFEM_REQUIRE((law >= 0 && law <= 2) || law == 4 || law == 5,
-                "variable viscosity: unknown law (0 none, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman)");
+  NSFEM_REQUIRE((law >= 0 && law <= 2) || law == 4 || law == 5 || law == 8,
+                "variable viscosity: unknown law (0 none, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman, 8 dynamic Smagorinsky)");
   NSFEM_REQUIRE(law == 0 || !ctx->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(law == 0 || params, "variable viscosity: the law needs its parameters");
@@ -2837,8 +2905,21 @@ extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double par
   } else if (law == 5) {
     NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] >= 0.0, "Vreman: c must be finite and >= 0");
     p[0] = params[0];
+  } else if (law == 8) {
+    NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] > 1.0, "dynamic Smagorinsky: alpha must be finite and > 1");
+    NSFEM_REQUIRE(std::isfinite(params[1]) && params[1] > 0.0, "dynamic Smagorinsky: cs2_max must be finite and > 0");
+    p[0] = params[0];
+    p[1] = params[1];
   }
   nsfem_ctx::Viscosity& v = ctx->visc;
+  if (law == 8) {
+    // buffers on the first call, kept afterwards; the groups go back to global (other groups were another law)
+    dynamic_ensure(ctx);
+    if (!ctx->dyn.global || !ctx->dyn.goff.p) {
+      if (!ctx->dyn.global) ++v.epoch;
+      dynamic_upload_groups(ctx, 1, nullptr);
+    }
+  }
   // (the stored explicit vectors belong to the law and parameters they were evaluated with; the law enters no
   // captured Krylov body -- its launches precede the solve --, so graph_epoch stays)
   if (law != v.law || std::memcmp(p, v.p, sizeof(p)) != 0) ++v.epoch;
@@ -2862,7 +2943,8 @@ extern "C" int nsfem_viscosity_residual(nsfem_ctx* ctx, int velocity_slot, doubl
   const int64_t nv = nvel(ctx);
   hook_to_host(ctx, nv, out_host, [&](double* out) {
     NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
-    launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->visc.law, ctx->visc.p, false);
+    const double* cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
+    launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->visc.law, ctx->visc.p, false, cs2v);
     launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
     ++ctx->visc.launches;
   });
@@ -2875,7 +2957,8 @@ extern "C" int nsfem_viscosity_cells(nsfem_ctx* ctx, int velocity_slot, double* 
   viscosity_require(ctx, velocity_slot);
   hipStream_t s = ctx->stream;
   // (the cell means land in the element buffer, which every user fills before it reads)
-  launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, 1.0, ctx->visc.law, ctx->visc.p, true);
+  const double* cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
+  launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, 1.0, ctx->visc.law, ctx->visc.p, true, cs2v);
   ++ctx->visc.launches;
   NSFEM_HIP(hipMemcpyAsync(out_host, ctx->mesh.rbuf.p, sizeof(double) * ctx->mesh.n_cells, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
@@ -2889,6 +2972,63 @@ extern "C" int nsfem_viscosity_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[1] = ctx->visc.launches;
   out[2] = ctx->visc.recomputed;
   out[3] = 0;
+  API_END(ctx)
+}
+
+// ---- dynamic Smagorinsky: averaging groups, the constant as output / test hook, counters
+extern "C" int nsfem_set_dynamic_groups(nsfem_ctx* ctx, int n_groups, const int32_t* group_of_vertex) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && group_of_vertex, "null argument");
+  NSFEM_REQUIRE(ctx->visc.law == 8, "dynamic Smagorinsky: groups without law 8 (nsfem_set_viscosity_law)");
+  NSFEM_REQUIRE(n_groups >= 1, "dynamic Smagorinsky: n_groups must be >= 1");
+  const int nv = ctx->mesh.n_p1;
+  for (int v = 0; v < nv; ++v)
+    NSFEM_REQUIRE(group_of_vertex[v] >= 0 && group_of_vertex[v] < n_groups,
+                  "dynamic Smagorinsky: group id out of range");
+  nsfem_ctx::Dynamic& D = ctx->dyn;
+  const bool same = !D.global && D.n_groups == n_groups &&
+                    std::memcmp(D.h_group.data(), group_of_vertex, sizeof(int32_t) * (size_t)nv) == 0;
+  if (!same) {
+    dynamic_upload_groups(ctx, n_groups, group_of_vertex);
+    ++ctx->visc.epoch;               // (the stored explicit vectors belong to the groups they were evaluated with)
+  }
+  API_END(ctx)
+}
+
+extern "C" int nsfem_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, double* cs2_groups, double* sums,
+                                      double* vertices) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && cs2_groups, "null argument");
+  NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->visc.law == 8, "dynamic Smagorinsky: law 8 is not set (nsfem_set_viscosity_law)");
+  require_velocity_slot(velocity_slot);
+  nsfem_ctx::Dynamic& D = ctx->dyn;
+  hipStream_t s = ctx->stream;
+  dynamic_run(ctx, ctx->state[velocity_slot].p);
+  D.h_sums.resize((size_t)D.n_groups * 3);
+  NSFEM_HIP(hipMemcpyAsync(D.h_sums.data(), D.sums.p, sizeof(double) * D.h_sums.size(), hipMemcpyDeviceToHost, s));
+  if (vertices)
+    NSFEM_HIP(hipMemcpyAsync(vertices, D.vert.p, sizeof(double) * (size_t)ctx->mesh.n_p1 * 3, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  for (int g = 0; g < D.n_groups; ++g) {
+    cs2_groups[g] = D.h_sums[(size_t)g * 3 + 2];
+    if (sums) {
+      sums[(size_t)g * 2] = D.h_sums[(size_t)g * 3];
+      sums[(size_t)g * 2 + 1] = D.h_sums[(size_t)g * 3 + 1];
+    }
+  }
+  API_END(ctx)
+}
+
+extern "C" int nsfem_dynamic_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  const nsfem_ctx::Dynamic& D = ctx->dyn;
+  out[0] = D.allocated ? D.n_groups : 0;
+  out[1] = D.runs;
+  out[2] = D.launches;
+  out[3] = (int64_t)(sizeof(int32_t) * (D.vptr.n + D.vcell.n + D.goff.n + D.gvert.n) +
+                     sizeof(double) * (D.mom.n + D.vert.n + D.sums.n + D.cs2v.n));
   API_END(ctx)
 }
 
@@ -4540,6 +4680,8 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   const bool subgrid = wp.law == 1 || wp.law == 4 || wp.law == 5;
   wp.inv_prt = subgrid && scalar_slot != -1 && ctx->sc.prandtl_t > 0.0 ? 1.0 / ctx->sc.prandtl_t : 0.0;
   hipStream_t s = ctx->stream;
+  // (law 8: nu_x of a facet's cell takes the constant of the velocity level the rows are formed on)
+  if (wp.law == 8) wp.cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
   launch_wall_facets(s, m, W.n_facets, W.fcell.p, W.flocal.p, ctx->state[velocity_slot].p, ctx->state[pressure_slot].p,
                      scalar_slot != -1 ? ctx->state[scalar_slot].p : nullptr, wp, W.rows.p);
   launch_wall_reduce(s, m.dim, W.n_groups, W.goff.p, W.rows.p, W.sums.p);

@@ -957,7 +957,9 @@ void launch_buoyancy_force(hipStream_t s, const MeshDev& m, const double* f, con
 //   r_(i,a) = wgt sum_q w_q |det J| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i,   g_ab = d_b u_a,
 //   gamma = sqrt(1/2 sum_ab (g_ab + g_ba)^2),   Delta_K^2 = |det J| / 2
 // LAW 1, 2: nu_x of gamma (visc_law_nu); LAW 4, 5 (WALE, Vreman): nu_x of the tensor g itself (visc_law_nu_grad<LAW, 2>:
-// the 2D field as the z-independent 3D one), cell_geometry.hpp.
+// the 2D field as the z-independent 3D one), cell_geometry.hpp.  LAW 8 (dynamic Smagorinsky): the arithmetic of law 1
+// with c_K, the mean of the vertex field cs2v over the cell's vertices (through p1), in the place of C_s^2; the other
+// instantiations never touch vtx (the P1 connectivity) / cs2v.
 // u at the 6 nodes in registers; the physical gradients, g, gamma and nu_x of a quadrature point are formed once and
 // shared by the 6 test functions.  The element vector goes node-sorted into m.rbuf (ndst, as k_conv_cell); k_visc_gather
 // sums the run of every node in ascending cell order: no atomics, the same state gives the same bytes.
@@ -967,11 +969,13 @@ __global__ __launch_bounds__(256) void k_visc_var_cell(int nc, const double* __r
                                                        const int32_t* __restrict__ p2,
                                                        const double* __restrict__ u, double wgt, double p0, double p1,
                                                        double pp2, const int32_t* __restrict__ ndst,
-                                                       double* __restrict__ rbuf) {
+                                                       double* __restrict__ rbuf, const int32_t* __restrict__ vtx,
+                                                       const double* __restrict__ cs2v) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const CellGeo g = load_geo(vx, nc, c);
   const double delta2 = 0.5 * g.adet;
+  if constexpr (LAW == 8) p0 = dynamic_cell_constant<2>(vtx, cs2v, nc, c);      // c_K in the place of C_s
   double ux[6], uy[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -1052,18 +1056,228 @@ __global__ __launch_bounds__(256) void k_visc_gather(int64_t n_entries, int dim,
 }
 
 void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
-                            const double p[4], bool mean) {
-  NSFEM_REQUIRE(law == 1 || law == 2 || law == 4 || law == 5, "variable viscosity: no law set");
-  if (m.dim == 3) return viscosity_cells_3d(s, m, u, weight, law, p, mean);
+                            const double p[4], bool mean, const double* cs2v) {
+  NSFEM_REQUIRE(law == 1 || law == 2 || law == 4 || law == 5 || law == 8, "variable viscosity: no law set");
+  NSFEM_REQUIRE((law == 8) == (cs2v != nullptr), "variable viscosity: the vertex constants go with law 8 and only with it");
+  if (m.dim == 3) return viscosity_cells_3d(s, m, u, weight, law, p, mean, cs2v);
   const dim3 grid(grid_for(m.n_cells)), block(kBlock);
 #define NSFEM_VV(L, M) \
   hipLaunchKernelGGL((k_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], p[2], \
-                     m.ndst.p, m.rbuf.p)
+                     m.ndst.p, m.rbuf.p, m.p1.p, cs2v)
   if (law == 1) { if (mean) NSFEM_VV(1, true); else NSFEM_VV(1, false); }
   else if (law == 2) { if (mean) NSFEM_VV(2, true); else NSFEM_VV(2, false); }
   else if (law == 4) { if (mean) NSFEM_VV(4, true); else NSFEM_VV(4, false); }
-  else { if (mean) NSFEM_VV(5, true); else NSFEM_VV(5, false); }
+  else if (law == 5) { if (mean) NSFEM_VV(5, true); else NSFEM_VV(5, false); }
+  else { if (mean) NSFEM_VV(8, true); else NSFEM_VV(8, false); }
 #undef NSFEM_VV
+  NSFEM_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- dynamic Smagorinsky (law 8): the Germano-Lilly constant
+// Three launches on a velocity level u (launch_dynamic_constant), plain stores, no atomics, the same state gives the
+// same bytes:
+//   k_dyn_moments<DIM>  one thread per CELL: m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q by the degree-5 rule for
+//                       f = u_a | u_a u_b | S_ab | gamma S_ab (a <= b), the last scaled by Delta_K^2 at the store, then
+//                       |K| and |K| Delta_K^2: NM = DIM + 3 NS + 2 doubles per cell (NS = DIM (DIM + 1) / 2), SoA
+//                       [NM][n_cells].  G_ab = d_b u_a is formed from the differences u_k - u_0 (the basis gradients
+//                       sum to zero): a constant field has G = 0 exactly, not a rounding residue.
+//   k_dyn_vertex<DIM>   one thread per VERTEX: the patch sums of the moments through the vertex-to-cell CSR in ascending
+//                       cell order, the test-filtered fields, the Germano identity; writes W_v, LM_v, MM_v ([n_p1][3])
+//   k_dyn_reduce        one workgroup per averaging GROUP over the group-sorted vertex list (the scheme of
+//                       k_wall_reduce): num_g, den_g, cs2_g ([n_groups][3]) and cs2 at the vertices of the group
+// Register layout of the moment kernel as k_visc_var_cell: u at the cell nodes in registers, the physical gradients of
+// a quadrature point formed once.
+template <int DIM>
+__global__ void k_dyn_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
+                              const double* __restrict__ u, double* __restrict__ mom);     // <3>: assembly3d.hip
+
+template <>
+__global__ __launch_bounds__(256) void k_dyn_moments<2>(int nc, const double* __restrict__ vx,
+                                                        const int32_t* __restrict__ p2,
+                                                        const double* __restrict__ u, double* __restrict__ mom) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo g = load_geo(vx, nc, c);
+  const double vol = 0.5 * g.adet, delta2 = 0.5 * g.adet;      // |K| and Delta_K^2 = |K|^(2 / dim)
+  double ux[6], uy[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int node = p2[(size_t)k * nc + c];
+    const double2 a = reinterpret_cast<const double2*>(u)[node];
+    ux[k] = a.x;
+    uy[k] = a.y;
+  }
+  double mu[2] = {0.0, 0.0}, muu[3] = {0.0, 0.0, 0.0}, ms[3] = {0.0, 0.0, 0.0}, mg[3] = {0.0, 0.0, 0.0};
+  double wsum = 0.0;
+  for (int q = 0; q < 7; ++q) {
+    double uqx = 0.0, uqy = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      uqx += c_q.phi2[q][k] * ux[k];
+      uqy += c_q.phi2[q][k] * uy[k];
+    }
+    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+      double gx, gy;
+      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx, gy);
+      const double dx = ux[k] - ux[0], dy = uy[k] - uy[0];
+      g00 += gx * dx;
+      g01 += gy * dx;
+      g10 += gx * dy;
+      g11 += gy * dy;
+    }
+    const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T = 2 S
+    const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
+    const double w = c_q.w[q];
+    wsum += w;
+    mu[0] += w * uqx;
+    mu[1] += w * uqy;
+    muu[0] += w * (uqx * uqx);
+    muu[1] += w * (uqx * uqy);
+    muu[2] += w * (uqy * uqy);
+    const double S[3] = {0.5 * s00, 0.5 * s01, 0.5 * s11};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      ms[k] += w * S[k];
+      mg[k] += w * (gamma * S[k]);
+    }
+  }
+  const double f = vol / wsum;
+  double* o = mom + c;
+  o[0] = f * mu[0];
+  o[(size_t)nc] = f * mu[1];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    o[(size_t)(2 + k) * nc] = f * muu[k];
+    o[(size_t)(5 + k) * nc] = f * ms[k];
+    o[(size_t)(8 + k) * nc] = (f * delta2) * mg[k];
+  }
+  o[(size_t)11 * nc] = vol;
+  o[(size_t)12 * nc] = vol * delta2;
+}
+
+// vert[v] = {W_v, LM_v, MM_v}.  Pairs (a <= b) in row order: 00 01 11 | 00 01 02 11 12 22; full contractions count the
+// off-diagonal pairs twice.  alpha2 = alpha^2, the squared ratio of the test filter width to the grid filter width.
+template <int DIM>
+__global__ __launch_bounds__(256) void k_dyn_vertex(int nv, int nc, const int32_t* __restrict__ vptr,
+                                                    const int32_t* __restrict__ vcell,
+                                                    const double* __restrict__ mom, double alpha2,
+                                                    double* __restrict__ vert) {
+#pragma clang fp contract(off)
+  constexpr int NS = DIM * (DIM + 1) / 2, NM = DIM + 3 * NS + 2;
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  double a[NM];
+#pragma unroll
+  for (int i = 0; i < NM; ++i) a[i] = 0.0;
+  const int e = vptr[v + 1];
+  for (int k = vptr[v]; k < e; ++k) {
+    const double* m = mom + vcell[k];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) a[i] += m[(size_t)i * nc];
+  }
+  double* o = vert + (size_t)v * 3;
+  const double W = a[NM - 2];
+  if (!(W > 0.0)) {                     // (a vertex of no cell: no patch, no contribution)
+    o[0] = o[1] = o[2] = 0.0;
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < NM; ++i) a[i] /= W;
+  // the test-filtered fields: hat u = a[0 ..), hat(u u) = a[UU ..), hat S = a[SS ..), hat(Delta^2 gamma S) = a[GS ..)
+  constexpr int UU = DIM, SS = DIM + NS, GS = DIM + 2 * NS;
+  const double d2 = a[NM - 1];
+  double ss = 0.0, trl = 0.0;
+  double L[NS];
+  {
+    int i = 0;
+#pragma unroll
+    for (int r = 0; r < DIM; ++r)
+#pragma unroll
+      for (int c = r; c < DIM; ++c, ++i) {
+        ss += (r == c ? 1.0 : 2.0) * (a[SS + i] * a[SS + i]);
+        L[i] = a[UU + i] - a[r] * a[c];
+        if (r == c) trl += L[i];
+      }
+  }
+  const double hgam = sqrt(2.0 * ss);
+  const double coef = (alpha2 * d2) * hgam, tr = trl / (double)DIM;
+  double lm = 0.0, mm = 0.0;
+  {
+    int i = 0;
+#pragma unroll
+    for (int r = 0; r < DIM; ++r)
+#pragma unroll
+      for (int c = r; c < DIM; ++c, ++i) {
+        const double M = 2.0 * (a[GS + i] - coef * a[SS + i]);
+        const double ld = r == c ? L[i] - tr : L[i];
+        const double mult = r == c ? 1.0 : 2.0;
+        lm += mult * (ld * M);
+        mm += mult * (M * M);
+      }
+  }
+  o[0] = W;
+  o[1] = lm;
+  o[2] = mm;
+}
+
+// sums[g] = {num_g, den_g, cs2_g}, num_g = sum W_v LM_v, den_g = sum W_v MM_v over gvert[goff[g] .. goff[g + 1]): thread t
+// adds the entries t, t + 256, ... in ascending order from +0.0, the partials are folded by the xor-shuffle tree within
+// each wave and the four wave sums added in wave order through LDS (k_wall_reduce).  cs2_g = min(max(num / den, 0),
+// cs2_max) where den > 0, else 0 (an empty group, a field at rest); every vertex of the group receives it.
+__global__ __launch_bounds__(256) void k_dyn_reduce(const int32_t* __restrict__ goff, const int32_t* __restrict__ gvert,
+                                                    const double* __restrict__ vert, double cs2_max,
+                                                    double* __restrict__ sums, double* __restrict__ cs2v) {
+#pragma clang fp contract(off)
+  __shared__ double sh[4][2];
+  __shared__ double result;
+  const int g = blockIdx.x, t = threadIdx.x;
+  const int begin = goff[g], end = goff[g + 1];
+  double num = 0.0, den = 0.0;
+  for (int i = begin + t; i < end; i += 256) {
+    const double* r = vert + (size_t)gvert[i] * 3;
+    num += r[0] * r[1];
+    den += r[0] * r[2];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    num += __shfl_xor(num, off, 64);
+    den += __shfl_xor(den, off, 64);
+  }
+  if ((t & 63) == 0) {
+    sh[t >> 6][0] = num;
+    sh[t >> 6][1] = den;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const double n = ((sh[0][0] + sh[1][0]) + sh[2][0]) + sh[3][0];
+    const double d = ((sh[0][1] + sh[1][1]) + sh[2][1]) + sh[3][1];
+    const double cs2 = d > 0.0 ? fmin(fmax(n / d, 0.0), cs2_max) : 0.0;
+    sums[(size_t)g * 3] = n;
+    sums[(size_t)g * 3 + 1] = d;
+    sums[(size_t)g * 3 + 2] = cs2;
+    result = cs2;
+  }
+  __syncthreads();
+  const double cs2 = result;
+  for (int i = begin + t; i < end; i += 256) cs2v[gvert[i]] = cs2;
+}
+
+void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, double alpha, double cs2_max,
+                             const DynamicDev& d) {
+  NSFEM_REQUIRE(d.n_groups >= 1 && d.mom && d.vert && d.sums && d.cs2v, "dynamic Smagorinsky: buffers not allocated");
+  if (m.dim == 3) {
+    dynamic_moments_3d(s, m, u, d.mom);
+    hipLaunchKernelGGL((k_dyn_vertex<3>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell,
+                       d.mom, alpha * alpha, d.vert);
+  } else {
+    hipLaunchKernelGGL((k_dyn_moments<2>), dim3(grid_for(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u,
+                       d.mom);
+    hipLaunchKernelGGL((k_dyn_vertex<2>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell,
+                       d.mom, alpha * alpha, d.vert);
+  }
+  hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, cs2_max, d.sums, d.cs2v);
   NSFEM_HIP(hipGetLastError());
 }
 

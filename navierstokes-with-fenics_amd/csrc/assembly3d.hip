@@ -677,7 +677,8 @@ void convection_action_3d(hipStream_t s, const MeshDev& m, const double* u, cons
 // cell_geometry.hpp), one thread per cell, 15-point rule:
 //   r_(i,a) = wgt sum_q w_q |det J| nu_x(gamma_q, Delta_K) sum_b (g_ab + g_ba)_q d_b phi_i,   g_ab = d_b u_a,
 //   gamma = sqrt(1/2 sum_ab (g_ab + g_ba)^2),   Delta_K = (|det J| / 6)^(1/3)
-// nu_x = visc_law_at<LAW, 3>: of gamma for LAW 1, 2, of the tensor g for LAW 4, 5 (WALE, Vreman).
+// nu_x = visc_law_at<LAW, 3>: of gamma for LAW 1, 2, of the tensor g for LAW 4, 5 (WALE, Vreman); LAW 8 (dynamic
+// Smagorinsky): of gamma with c_K from the vertex field cs2v through vtx, the P1 connectivity (the other laws never read them).
 // Element vector node-sorted into m.rbuf; the caller sums the node runs (k_visc_gather).
 // MEAN: rbuf[c] = sum_q w_q nu_x(gamma_q) / sum_q w_q instead.
 template <int LAW, bool MEAN>
@@ -685,12 +686,14 @@ __global__ __launch_bounds__(256) void k3_visc_var_cell(int nc, const double* __
                                                         const int32_t* __restrict__ p2,
                                                         const double* __restrict__ u, double wgt, double p0, double p1,
                                                         double pp2, const int32_t* __restrict__ ndst,
-                                                        double* __restrict__ rbuf) {
+                                                        double* __restrict__ rbuf, const int32_t* __restrict__ vtx,
+                                                        const double* __restrict__ cs2v) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const CellGeo3 g = load_geo3(vx, nc, c);
   const double delta = cbrt(g.adet / 6.0);
   const double delta2 = delta * delta;
+  if constexpr (LAW == 8) p0 = dynamic_cell_constant<3>(vtx, cs2v, nc, c);      // c_K in the place of C_s
   double un[10][3];
 #pragma unroll
   for (int k = 0; k < 10; ++k) {
@@ -745,16 +748,100 @@ __global__ __launch_bounds__(256) void k3_visc_var_cell(int nc, const double* __
 }
 
 void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, int law, const double p[4],
-                        bool mean) {
+                        bool mean, const double* cs2v) {
   const dim3 grid(grid3(m.n_cells)), block(kBlock);
 #define NSFEM_VV3(L, M) \
   hipLaunchKernelGGL((k3_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], \
-                     p[2], m.ndst.p, m.rbuf.p)
+                     p[2], m.ndst.p, m.rbuf.p, m.p1.p, cs2v)
   if (law == 1) { if (mean) NSFEM_VV3(1, true); else NSFEM_VV3(1, false); }
   else if (law == 2) { if (mean) NSFEM_VV3(2, true); else NSFEM_VV3(2, false); }
   else if (law == 4) { if (mean) NSFEM_VV3(4, true); else NSFEM_VV3(4, false); }
-  else { if (mean) NSFEM_VV3(5, true); else NSFEM_VV3(5, false); }
+  else if (law == 5) { if (mean) NSFEM_VV3(5, true); else NSFEM_VV3(5, false); }
+  else { if (mean) NSFEM_VV3(8, true); else NSFEM_VV3(8, false); }
 #undef NSFEM_VV3
+  NSFEM_HIP(hipGetLastError());
+}
+
+// ---- dynamic Smagorinsky on tetrahedra: the cell moments of launch_dynamic_constant (assembly.hip, where the
+// definition, the vertex and the group kernels are), one thread per cell, 15-point rule.  NM = 23 rows, SoA
+// [23][n_cells]: u_a (3) | u_a u_b (6) | S_ab (6) | Delta_K^2 gamma S_ab (6) | |K| | |K| Delta_K^2, pairs a <= b in row
+// order.  G from the differences u_k - u_0, as in 2D.
+template <int DIM>
+__global__ void k_dyn_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
+                              const double* __restrict__ u, double* __restrict__ mom);     // <2>: assembly.hip
+
+template <>
+__global__ __launch_bounds__(256) void k_dyn_moments<3>(int nc, const double* __restrict__ vx,
+                                                        const int32_t* __restrict__ p2,
+                                                        const double* __restrict__ u, double* __restrict__ mom) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo3 g = load_geo3(vx, nc, c);
+  const double vol = g.adet / 6.0;
+  const double delta = cbrt(vol);
+  const double delta2 = delta * delta;
+  double un[10][3];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const size_t node = (size_t)p2[(size_t)k * nc + c];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
+  }
+  double mu[3] = {0.0, 0.0, 0.0};
+  double muu[6], ms[6], mg[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) muu[k] = ms[k] = mg[k] = 0.0;
+  double wsum = 0.0;
+  for (int q = 0; q < 15; ++q) {
+    double uq[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) uq[a] += c_q3.phi2[q][k] * un[k][a];
+    double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};     // G[a][b] = d_b u_a
+#pragma unroll
+    for (int k = 1; k < 10; ++k) {
+      double gk[3];
+      phys3(g, c_q3.dphi2[q][k], gk);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double d = un[k][a] - un[0][a];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) G[a][b] += gk[b] * d;
+      }
+    }
+    const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
+    const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
+    const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
+    const double w = c_q3.w[q];
+    wsum += w;
+    const double S[6] = {0.5 * s00, 0.5 * s01, 0.5 * s02, 0.5 * s11, 0.5 * s12, 0.5 * s22};
+    const double uu[6] = {uq[0] * uq[0], uq[0] * uq[1], uq[0] * uq[2], uq[1] * uq[1], uq[1] * uq[2], uq[2] * uq[2]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) mu[a] += w * uq[a];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      muu[k] += w * uu[k];
+      ms[k] += w * S[k];
+      mg[k] += w * (gamma * S[k]);
+    }
+  }
+  const double f = vol / wsum;
+  double* o = mom + c;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[(size_t)a * nc] = f * mu[a];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    o[(size_t)(3 + k) * nc] = f * muu[k];
+    o[(size_t)(9 + k) * nc] = f * ms[k];
+    o[(size_t)(15 + k) * nc] = (f * delta2) * mg[k];
+  }
+  o[(size_t)21 * nc] = vol;
+  o[(size_t)22 * nc] = vol * delta2;
+}
+
+void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, double* mom) {
+  hipLaunchKernelGGL((k_dyn_moments<3>), dim3(grid3(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u, mom);
   NSFEM_HIP(hipGetLastError());
 }
 

@@ -82,10 +82,14 @@ __device__ __forceinline__ void phys3(const CellGeo3& g, const double* dr, doubl
 // dimensions and their cell-mean variants inline.  gamma = sqrt(2 S:S) >= 0, delta2 = Delta_K^2, p = params[0..2].
 //   LAW 1 Smagorinsky  (C_s Delta_K)^2 gamma                          p0 = C_s
 //   LAW 2 Carreau      a [ (1 + (lambda gamma)^2)^((n - 1)/2) - 1 ]   p0 = a, p1 = lambda, p2 = n
+//   LAW 8 dynamic Smagorinsky  (c_K Delta_K^2) gamma                  p0 = c_K, the cell's C_s^2 (dynamic_cell_constant)
 template <int LAW>
 __device__ __forceinline__ double visc_law_nu(double gamma, double delta2, double p0, double p1, double p2) {
+  static_assert(LAW == 1 || LAW == 2 || LAW == 8, "shear-rate laws are 1 (Smagorinsky), 2 (Carreau) and 8 (dynamic)");
   if constexpr (LAW == 1) {
     return (p0 * p0 * delta2) * gamma;
+  } else if constexpr (LAW == 8) {
+    return (p0 * delta2) * gamma;
   } else {
     const double lg = p1 * gamma;
     return p0 * (pow(1.0 + lg * lg, 0.5 * (p2 - 1.0)) - 1.0);
@@ -152,7 +156,18 @@ __device__ __forceinline__ double visc_law_nu_grad(const double (&G)[DIM][DIM], 
   }
 }
 
-// nu_x of any law at a point: laws 1 and 2 from the shear rate alone (nothing of G is touched in their
+// Law 8: c_K = the mean over the DIM + 1 vertices of cell c of the vertex field C_s^2 (k_dyn_reduce), summed in local
+// vertex order -- the ONE copy the element and facet kernels inline.  p1 SoA [DIM + 1][nc].
+template <int DIM>
+__device__ __forceinline__ double dynamic_cell_constant(const int32_t* __restrict__ p1, const double* __restrict__ cs2v,
+                                                        int nc, int c) {
+  double s = cs2v[p1[c]];
+#pragma unroll
+  for (int v = 1; v <= DIM; ++v) s += cs2v[p1[(size_t)v * nc + c]];
+  return s / (double)(DIM + 1);
+}
+
+// nu_x of any law at a point: laws 1, 2 and 8 from the shear rate alone (nothing of G is touched in their
 // instantiations), laws 4 and 5 from the tensor
 template <int LAW, int DIM>
 __device__ __forceinline__ double visc_law_at(const double (&G)[DIM][DIM], double gamma, double delta2, double p0,

@@ -503,10 +503,25 @@ struct ScalarSgsKernelArgs<0> {};
 // variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman, p = params): the element kernel
 // k_visc_var_cell / k3_visc_var_cell on the velocity u, element vectors weight * V_K(u) node-sorted into m.rbuf --
 // mean: the cell means of nu_x into the first n_cells doubles of m.rbuf instead
+// law 8 (dynamic Smagorinsky): cs2v = the vertex field C_s^2 of launch_dynamic_constant on the same u; null for every
+// other law
 void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
-                            const double p[4], bool mean);
+                            const double p[4], bool mean, const double* cs2v = nullptr);
 void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, int law, const double p[4],
-                        bool mean);
+                        bool mean, const double* cs2v);
+// dynamic Smagorinsky (law 8): the device side of the Germano-Lilly procedure on the velocity u -- k_dyn_moments,
+// k_dyn_vertex, k_dyn_reduce (assembly.hip / assembly3d.hip).  vptr, vcell: the vertex-to-cell CSR (ascending cells);
+// goff [n_groups + 1], gvert [n_p1]: the group-sorted vertex list; mom [NM][n_cells], vert [n_p1][3] = W, LM, MM;
+// sums [n_groups][3] = num, den, cs2; cs2v [n_p1]: the constant at the vertices, what launch_viscosity_cells and
+// launch_wall_facets read with law 8
+struct DynamicDev {
+  int n_groups = 0;
+  const int32_t *vptr = nullptr, *vcell = nullptr, *goff = nullptr, *gvert = nullptr;
+  double *mom = nullptr, *vert = nullptr, *sums = nullptr, *cs2v = nullptr;
+};
+void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, double alpha, double cs2_max,
+                             const DynamicDev& d);
+void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, double* mom);
 // k_visc_gather: v = per-node sums of m.rbuf in ascending cell order; n1 += v, rhs -= b0 v (rhs may be null)
 void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double* n1, double* rhs);
 // immersed bodies (nsfem_set_bodies): the table the penalisation kernels take as a kernel ARGUMENT (1.6 kB; entries
@@ -697,8 +712,9 @@ void launch_spec_bin(hipStream_t s, const double* w, int32_t n_chunks, const int
 inline int wall_components(int dim) { return dim == 2 ? 9 : 13; }
 struct WallParams {
   double nu = 0.0, sym = 0.0, kappa = 0.0, origin[3] = {0.0, 0.0, 0.0};
-  int law = 0;                               // 0: constant viscosity; 1, 2, 4, 5: + nu_x of visc_law_at<law>
+  int law = 0;                               // 0: constant viscosity; 1, 2, 4, 5, 8: + nu_x of visc_law_at<law>
   double law_p[3] = {0.0, 0.0, 0.0};
+  const double* cs2v = nullptr;              // law 8: the vertex field C_s^2 (launch_dynamic_constant), else null
   double inv_prt = 0.0;                      // law 1, 4, 5 and != 0: the heat row uses kappa + nu_x inv_prt (subgrid heat flux)
 };
 // ONE launch: rows[f][NW] of the nf facets (fcell, flocal: device lists); T may be null (no scalar: +0.0 entries)
@@ -1252,6 +1268,19 @@ struct nsfem_ctx {
     double p[4] = {0.0, 0.0, 0.0, 0.0};
     int64_t epoch = 0, launches = 0, recomputed = 0;
   } visc;
+  // dynamic Smagorinsky (law 8; p = {alpha, cs2_max}): the buffers of launch_dynamic_constant, allocated when law 8
+  // is first set and kept; the averaging groups (nsfem_set_dynamic_groups; global: one group of all vertices).  The
+  // constant is a function of the level it is evaluated on -- it is formed before every law-8 element launch and is
+  // no stored state; a change of the groups is a change of the law (visc.epoch)
+  struct Dynamic {
+    bool allocated = false, global = true;
+    int n_groups = 1;
+    std::vector<int32_t> h_group;                   // [n_p1], what nsfem_set_dynamic_groups took (empty: global)
+    nsfem::DevBuf<int32_t> vptr, vcell, goff, gvert;
+    nsfem::DevBuf<double> mom, vert, sums, cs2v;
+    std::vector<double> h_sums;
+    int64_t runs = 0, launches = 0;
+  } dyn;
   // immersed bodies (nsfem_set_bodies): with bodies the stored vectors carry B(u) as well.  `cur` is the pose of t^n,
   // `prev` that of t^(n-1) (nsfem_move_bodies shifts cur to prev; without a move they are equal): a stored N(u2) was
   // formed with prev and one that has to be recomputed is formed with it again.  `epoch` counts the changes of the set,

@@ -12,7 +12,7 @@
 // Facet rules as in k_boundary_force: the 2-point Gauss rule on an edge, the 3 edge midpoints on a face.  grad u, p
 // and grad T are linear on an affine facet, u.n and T quadratic, (x - x0) x t quadratic: the rules are exact for
 // every integrand when LAW = 0.  With a law, nu_x (of gamma and Delta_K for laws 1 and 2, of the gradient tensor for
-// laws 4 and 5: cell_geometry.hpp) is evaluated at the points of the rule and the rule is part of the
+// laws 4 and 5, of gamma with the cell's dynamic constant c_K for law 8: cell_geometry.hpp) is evaluated at the points of the rule and the rule is part of the
 // definition (as the degree-5 rule is for nsfem_viscosity_cells).
 #include "cell_geometry.hpp"
 
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
                                                      const double* __restrict__ p, const double* __restrict__ T,
                                                      double nu, double sym, double kappa, double ox, double oy,
                                                      double oz, double lp0, double lp1, double lp2, double ipr,
-                                                     double* __restrict__ out) {
+                                                     double* __restrict__ out, const double* __restrict__ cs2v) {
   constexpr int NV = DIM + 1, N2 = DIM == 2 ? 6 : 10, NQ = DIM == 2 ? 2 : 3;
   constexpr int NT = DIM == 2 ? 1 : 3, NW = 2 * DIM + 4 + NT;
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -134,6 +134,8 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
       delta2 = delta * delta;
     }
   }
+  // LAW 8 (dynamic Smagorinsky): c_K of the facet's cell from the vertex field in the place of the constant
+  if constexpr (LAW == 8) lp0 = dynamic_cell_constant<DIM>(p1, cs2v, nc, c);
   // nodal data
   const bool have_T = T != nullptr;
   double un[N2][3], pn[NV], Tn[N2];
@@ -293,21 +295,23 @@ static void launch_wall_facets_t(hipStream_t s, const MeshDev& m, int nf, const 
   const int grid = (nf + 255) / 256;
   hipLaunchKernelGGL((k_wall_facets<DIM, LAW>), dim3(grid), dim3(256), 0, s, nf, m.n_cells, fcell, flocal, m.vx.p,
                      m.p2.p, m.p1.p, u, p, T, w.nu, w.sym, w.kappa, w.origin[0], w.origin[1], w.origin[2], w.law_p[0],
-                     w.law_p[1], w.law_p[2], w.inv_prt, rows);
+                     w.law_p[1], w.law_p[2], w.inv_prt, rows, w.cs2v);
 }
 
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
                         const double* u, const double* p, const double* T, const WallParams& w, double* rows) {
   if (nf <= 0) return;
-  NSFEM_REQUIRE((w.law >= 0 && w.law <= 2) || w.law == 4 || w.law == 5, "wall quantities: unknown viscosity law");
+  NSFEM_REQUIRE((w.law >= 0 && w.law <= 2) || w.law == 4 || w.law == 5 || w.law == 8,
+                "wall quantities: unknown viscosity law");
+  NSFEM_REQUIRE((w.law == 8) == (w.cs2v != nullptr), "wall quantities: the vertex constants go with law 8 and only with it");
   using Fn = void (*)(hipStream_t, const MeshDev&, int, const int32_t*, const int32_t*, const double*, const double*,
                       const double*, const WallParams&, double*);
-  // (law 3 is no law: its column is never taken)
-  static const Fn table[2][6] = {
+  // (3, 6 and 7 are no laws: their columns are never taken)
+  static const Fn table[2][9] = {
       {launch_wall_facets_t<2, 0>, launch_wall_facets_t<2, 1>, launch_wall_facets_t<2, 2>, nullptr,
-       launch_wall_facets_t<2, 4>, launch_wall_facets_t<2, 5>},
+       launch_wall_facets_t<2, 4>, launch_wall_facets_t<2, 5>, nullptr, nullptr, launch_wall_facets_t<2, 8>},
       {launch_wall_facets_t<3, 0>, launch_wall_facets_t<3, 1>, launch_wall_facets_t<3, 2>, nullptr,
-       launch_wall_facets_t<3, 4>, launch_wall_facets_t<3, 5>}};
+       launch_wall_facets_t<3, 4>, launch_wall_facets_t<3, 5>, nullptr, nullptr, launch_wall_facets_t<3, 8>}};
   table[m.dim == 3][w.law](s, m, nf, fcell, flocal, u, p, T, w, rows);
   NSFEM_HIP(hipGetLastError());
 }

@@ -65,7 +65,8 @@ class IMEXIPCSSolver(InstationarySolverBase):
         self.last_step_info = None
 
     def set_viscosity_model(self, model):
-        """a model of ``viscosity_models`` (``SmagorinskyModel``, ``WALEModel``, ``VremanModel``, ``CarreauModel``) or None for the constant
+        """a model of ``viscosity_models`` (``SmagorinskyModel``, ``WALEModel``, ``VremanModel``, ``CarreauModel``,
+        ``DynamicSmagorinskyModel``) or None for the constant
         viscosity.  Its parameters are formed from the equation coefficients, so it is pushed to the device again
         whenever they change; partitioned meshes are refused by the device driver."""
         assert model is None or (hasattr(model, "law_id") and hasattr(model, "params"))
@@ -80,7 +81,20 @@ class IMEXIPCSSolver(InstationarySolverBase):
             if model is None:
                 self._ctx.set_viscosity_law(0)
             elif hasattr(self, "_equation_coefficients"):
-                self._ctx.set_viscosity_law(model.law_id, model.params(self._equation_coefficients))
+                params = tuple(model.params(self._equation_coefficients))
+                if hasattr(model, "vertex_groups"):
+                    # the dynamic model: the law first (which resets the groups), then its groups -- and only when
+                    # something changed, since a push of other groups invalidates the stored explicit vectors
+                    n_groups, ids = model.vertex_groups(self._dofmap.p1_coords)
+                    pushed = (id(self._ctx), params, n_groups, ids.tobytes())
+                    if getattr(self, "_pushed_dynamic", None) == pushed and \
+                            self._ctx.viscosity_info()["law"] == model.law_id:
+                        return
+                    self._ctx.set_viscosity_law(model.law_id, params)
+                    self._ctx.set_dynamic_groups(n_groups, ids)
+                    self._pushed_dynamic = pushed
+                else:
+                    self._ctx.set_viscosity_law(model.law_id, params)
         except nat.NativeError as err:
             raise RuntimeError(str(err))
 

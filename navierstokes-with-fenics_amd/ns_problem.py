@@ -423,6 +423,15 @@ class ProblemBase:
             raise RuntimeError(str(err))
         return HostField(self._mesh, "model viscosity", "Cell", values)
 
+    def _compute_model_constant(self):
+        """C_s^2 of every averaging group of a ``DynamicSmagorinskyModel`` for the current velocity, from the device
+        (nsfem_dynamic_constant), [n_groups] in the order of the model's ``vertex_groups``.  New helper."""
+        import _native as nat
+        try:
+            return self._get_solver()._ctx.dynamic_constant(nat.U0)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+
     def _compute_model_diffusivity(self):
         """cell means of the eddy diffusivity kappa_x = nu_x / Pr_t of the subgrid heat flux (a ``SmagorinskyModel``
         with ``prandtl_t``) for the current velocity: the cell means of ``_compute_model_viscosity`` divided by Pr_t.

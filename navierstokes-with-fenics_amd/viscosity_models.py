@@ -10,6 +10,7 @@ import math
 
 LAW_NONE, LAW_SMAGORINSKY, LAW_CARREAU = 0, 1, 2
 LAW_WALE, LAW_VREMAN = 4, 5          # (3 is no law)
+LAW_DYNAMIC = 8                      # (6 and 7 are no laws)
 
 
 def _checked_constant(model, name, value):
@@ -100,3 +101,48 @@ class CarreauModel:
         if nu0 is None or not math.isfinite(float(nu0)):
             raise ValueError("CarreauModel: the viscous_term coefficient (zero-shear viscosity) is not set")
         return (float(nu0) - self.nu_inf, self.lam, self.n, 0.0)
+
+
+class DynamicSmagorinskyModel:
+    """nu_x = c_K Delta_K^2 gamma with C_s^2 computed on the device by the Germano-Lilly procedure (law 8 of
+    ``nsfem_set_viscosity_law``): test filter over the vertex patches of width ``filter_ratio`` > 1 times the grid
+    filter, least squares over averaging groups of vertices, clipped to [0, ``cs2_max``].  ``averaging``: "global" (one
+    group of all vertices) or ("planes", axis) -- one group per set of vertices of equal coordinate along ``axis``, for
+    a channel.  No subgrid heat flux goes with this model (``prandtl_t`` is None)."""
+    law_id = LAW_DYNAMIC
+    prandtl_t = None
+
+    def __init__(self, averaging="global", filter_ratio=2.0, cs2_max=0.09):
+        if averaging != "global":
+            ok = isinstance(averaging, (tuple, list)) and len(averaging) == 2 and averaging[0] == "planes"
+            ok = ok and isinstance(averaging[1], (int, )) and not isinstance(averaging[1], bool) and 0 <= averaging[1] <= 2
+            if not ok:
+                raise ValueError('DynamicSmagorinskyModel: averaging must be "global" or ("planes", axis) with axis 0, '
+                                 "1 or 2, got %r" % (averaging, ))
+            averaging = ("planes", int(averaging[1]))
+        filter_ratio, cs2_max = float(filter_ratio), float(cs2_max)
+        if not (math.isfinite(filter_ratio) and filter_ratio > 1.0):
+            raise ValueError("DynamicSmagorinskyModel: filter_ratio must be finite and > 1, got %r" % (filter_ratio, ))
+        if not (math.isfinite(cs2_max) and cs2_max > 0.0):
+            raise ValueError("DynamicSmagorinskyModel: cs2_max must be finite and > 0, got %r" % (cs2_max, ))
+        self.averaging, self.filter_ratio, self.cs2_max = averaging, filter_ratio, cs2_max
+
+    def params(self, coefficients=None):
+        return (self.filter_ratio, self.cs2_max, 0.0, 0.0)
+
+    def vertex_groups(self, coordinates):
+        """(n_groups, ids [n_vertices]) for the vertices at ``coordinates`` [n, dim]: planes in ascending coordinate,
+        by the binning of ``flow_statistics.groups_along_axis``"""
+        import numpy as np
+        coordinates = np.asarray(coordinates, dtype=np.float64)
+        if self.averaging == "global":
+            return 1, np.zeros(coordinates.shape[0], dtype=np.int32)
+        axis = self.averaging[1]
+        if axis >= coordinates.shape[1]:
+            raise ValueError("DynamicSmagorinskyModel: axis %d on a %dD mesh" % (axis, coordinates.shape[1]))
+        from flow_statistics import groups_along_axis
+        values, ptr, nodes = groups_along_axis(coordinates, axis)
+        ids = np.empty(coordinates.shape[0], dtype=np.int32)
+        for g in range(values.size):
+            ids[nodes[ptr[g]:ptr[g + 1]]] = g
+        return int(values.size), ids
