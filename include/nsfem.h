@@ -516,6 +516,47 @@ int nsfem_scalar_explicit(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, in
 /* out = {1 while the term is on else 0, launches of the SGS != 0 kernels, stored vectors formed again because Pr_t or
  * (with the term on) the law changed, 0} */
 int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]);
+/* ---- dynamic subgrid heat flux: the Germano-Lilly eddy diffusivity of the scalar (Moin et al. 1991, Lilly 1992), the
+ * partner of viscosity law 8.  kappa_x = c_K Delta_K^2 gamma -- no Pr_t, and C_s^2 is not read -- with the constant
+ * C_theta computed on the device from the pair (velocity level, scalar level) the explicit scalar term is evaluated on.
+ * With |K| = |det J_K| / dim!, Delta_K^2, gamma = sqrt(2 S:S), the degree-5 rule (7 / 15 points), p1 the P1
+ * connectivity, alpha the filter ratio of law 8 and the averaging groups of nsfem_set_dynamic_groups:
+ *   1. cell moments m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q of f = T, T u_a, u_a, d_a T, Delta_K^2 gamma d_a T, S_ab
+ *      (a <= b), then |K| and |K| Delta_K^2: 14 doubles per cell in 2D, 21 in 3D.  grad T and G_ab = d_b u_a from the
+ *      differences T_k - T_0, u_k - u_0 of the nodal values: a constant T or u gives an exact 0.0.  The set repeats u_a,
+ *      S_ab and the volumes of law 8 on purpose (the velocity moments of law 8 may belong to another level)
+ *   2. test filter at a vertex v over its cells, ascending: W_v = sum |K|, hat f_v = (sum m_K[f]) / W_v, Delta_v^2 =
+ *      (sum |K| Delta_K^2) / W_v, hat gamma_v = sqrt(2 hat S : hat S)
+ *   3. P_a = hat(T u_a) - hat T hat u_a, R_a = hat(Delta^2 gamma d_a T) - alpha^2 Delta_v^2 hat gamma hat(d_a T),
+ *      PR_v = P . R, RR_v = R . R   (the modelled flux is -C_theta Delta^2 gamma grad T, so P = C_theta R: the sign
+ *      convention of law 8's L = C M)
+ *   4. per group g: num_g = sum W_v PR_v, den_g = sum W_v RR_v in the fixed order of law 8 from +0.0, ctheta_g =
+ *      min(max(num_g / den_g, 0), ctheta_max) where den_g > 0, else 0
+ *   5. c_K = the mean over the vertices of K of ctheta_g(v); D(u, T) is that of nsfem_set_scalar_sgs with this kappa_x
+ * Three launches (k_dyn_scalar_moments, k_dyn_scalar_vertex, k_dyn_reduce) before every element launch of the term, on
+ * that launch's level pair: the constant is a pure function of the pair, NSFEM_TCONV_2 keeps the constant of its own
+ * level and a new constant invalidates nothing.  A change of the switch, of ctheta_max, of alpha or of the groups
+ * invalidates the stored scalar vector.  enable = 0 switches the term off (ctheta_max is not read); the same setting
+ * again changes nothing.  NSFEM_ERR_ARG: enable not 0 or 1, ctheta_max not finite or not > 0, contexts with a
+ * communicator, a fixed Pr_t that is on (nsfem_set_scalar_sgs with Pr_t > 0 is likewise refused while this switch is
+ * on).  With the switch on, nsfem_step_scalar_imex and nsfem_scalar_explicit refuse (NSFEM_ERR_ARG, state untouched)
+ * unless the viscosity law is 8.  nsfem_wall_compute with use_law, law 8, a scalar slot and the switch on forms its
+ * conductive row with kappa + c_K Delta_K^2 gamma, the procedure run on the call's velocity and scalar slots; with the
+ * switch off that row keeps its bytes.  A context that never calls this allocates and launches nothing new. */
+int nsfem_set_scalar_sgs_dynamic(nsfem_ctx* ctx, int enable, double ctheta_max);
+/* Output and test hook: runs the procedure on (velocity_slot, scalar_slot).  ctheta_groups [n_groups]; sums
+ * [n_groups][2] = num_g, den_g or NULL; vertices [n_p1][3] = W_v, PR_v, RR_v or NULL.  No stored state is touched; two
+ * calls on the same state return the same bytes.  NSFEM_ERR_ARG: the switch off, law 8 not set, other slots, contexts
+ * with a communicator. */
+int nsfem_scalar_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, double* ctheta_groups,
+                                  double* sums, double* vertices);
+/* out [n_cells] = the cell means of kappa_x = c_K Delta_K^2 gamma by the rule of nsfem_viscosity_cells, the constant
+ * formed on (velocity_slot, scalar_slot).  Refusals as nsfem_scalar_dynamic_constant. */
+int nsfem_scalar_diffusivity_cells(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, double* out);
+/* out = {1 while the switch is on else 0, runs of the procedure so far, launches of its three kernels, bytes of its
+ * device buffers (0 before the first run)}.  nsfem_scalar_sgs_info keeps its entries: its launch counter counts the
+ * element launches of the term, dynamic or not. */
+int nsfem_scalar_dynamic_info(nsfem_ctx* ctx, int64_t out[4]);
 /* ---- variable viscosity in the IMEX step (new; the reference knows one constant viscosity).  nu = c_v + nu_x(gamma,
  * Delta_K) with gamma = sqrt(2 S:S) = sqrt(1/2 sum_ab (g_ab + g_ba)^2), g_ab = d_b u_a, and Delta_K = |K|^(1/dim),
  * |K| = |det J_K| / dim!.  The constant part c_v K stays in the implicit matrix; the remainder
@@ -556,8 +597,9 @@ int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]);
  *          alpha is the ratio of the test to the grid filter width (usually 2), cs2_max the clip (0.09 = 0.3^2).  Three
  *          launches (k_dyn_moments, k_dyn_vertex, k_dyn_reduce) before every element launch of this law, on that
  *          launch's velocity level: N(u^(n-1)) keeps the constant of its own level, and a new constant invalidates
- *          nothing.  Setting law 8 resets the groups to the global one.  No subgrid heat flux goes with this law
- *          (nsfem_set_scalar_sgs refuses as for law 0).
+ *          nothing.  Setting law 8 resets the groups to the global one.  The subgrid heat flux that goes with this
+ *          law is the dynamic one (nsfem_set_scalar_sgs_dynamic); a fixed Pr_t is refused at the step as for law 0
+ *          (nsfem_set_scalar_sgs).
  * A change of law or parameters invalidates the stored vectors.  NSFEM_ERR_ARG: unknown law, parameters outside these
  * ranges or not finite, a law other than 0 on contexts with a communicator; nsfem_step_ipcs and nsfem_step_bdf refuse
  * to run while a law other than 0 is set. */

@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "nsfem_volume_functionals",
     "nsfem_set_scalar", "nsfem_step_scalar_imex", "nsfem_scalar_convection", "nsfem_scalar_info",
     "nsfem_set_scalar_sgs", "nsfem_scalar_explicit", "nsfem_scalar_sgs_info",
+    "nsfem_set_scalar_sgs_dynamic", "nsfem_scalar_dynamic_constant", "nsfem_scalar_diffusivity_cells",
+    "nsfem_scalar_dynamic_info",
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
     "nsfem_set_dynamic_groups", "nsfem_dynamic_constant", "nsfem_dynamic_info",
     "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
@@ -217,6 +219,10 @@ def load_library(path=None):
         "nsfem_set_scalar_sgs": (C.c_int, [vp, dbl]),
         "nsfem_scalar_explicit": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, pd]),
         "nsfem_scalar_sgs_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_scalar_sgs_dynamic": (C.c_int, [vp, C.c_int, dbl]),
+        "nsfem_scalar_dynamic_constant": (C.c_int, [vp, C.c_int, C.c_int, pd, pd, pd]),
+        "nsfem_scalar_diffusivity_cells": (C.c_int, [vp, C.c_int, C.c_int, pd]),
+        "nsfem_scalar_dynamic_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_viscosity_law": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_viscosity_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
         "nsfem_viscosity_cells": (C.c_int, [vp, C.c_int, pd]),
@@ -603,6 +609,38 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_scalar_sgs_info(self._h, out))
         return dict(active=bool(out[0]), launches=int(out[1]), recomputed=int(out[2]))
+
+    # -- dynamic subgrid heat flux (the partner of viscosity law 8) ------------------------
+    def set_scalar_sgs_dynamic(self, enable, ctheta_max=0.2):
+        """the eddy diffusivity kappa_x = c_K Delta_K^2 gamma with C_theta from the Germano identity of the scalar
+        flux, computed on the device on the level pair of every launch (include/nsfem.h); ``ctheta_max`` the clip.
+        Refused while a fixed Pr_t is on; the step then needs viscosity law 8"""
+        self._check(self._lib.nsfem_set_scalar_sgs_dynamic(self._h, 1 if enable else 0, float(ctheta_max)))
+
+    def scalar_dynamic_constant(self, velocity_slot=U0, scalar_slot=T0, details=False):
+        """C_theta of every averaging group for the pair of slots, [n_groups] (no stored state touched);
+        ``details``: also the sums [n_groups, 2] = num, den and the vertex rows [n_p1, 3] = W, PR, RR"""
+        n = max(self.dynamic_info()["groups"], 1)     # (law 8 never set: let the driver say so)
+        cth = np.empty(n, dtype=np.float64)
+        sums = np.empty((n, 2), dtype=np.float64) if details else None
+        vert = np.empty((self.n_p1, 3), dtype=np.float64) if details else None
+        self._check(self._lib.nsfem_scalar_dynamic_constant(self._h, int(velocity_slot), int(scalar_slot), _dp(cth),
+                                                            _dp(sums) if details else None,
+                                                            _dp(vert) if details else None))
+        return (cth, sums, vert) if details else cth
+
+    def scalar_diffusivity_cells(self, velocity_slot=U0, scalar_slot=T0):
+        """cell means of kappa_x = c_K Delta_K^2 gamma, the constant formed on the pair of slots, [n_cells]"""
+        out = np.empty(self.n_cells, dtype=np.float64)
+        self._check(self._lib.nsfem_scalar_diffusivity_cells(self._h, int(velocity_slot), int(scalar_slot), _dp(out)))
+        return out
+
+    def scalar_dynamic_info(self):
+        """dict(active, runs, launches, bytes): the switch, the runs of the procedure, the launches of its three
+        kernels and the bytes of its device buffers"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_scalar_dynamic_info(self._h, out))
+        return dict(active=bool(out[0]), runs=int(out[1]), launches=int(out[2]), bytes=int(out[3]))
 
     # -- variable viscosity in the IMEX step ---------------------------------------------
     def set_viscosity_law(self, law, params=None):

@@ -2650,6 +2650,38 @@ static const double* dynamic_run(nsfem_ctx* c, const double* u) {
   return D.cs2v.p;
 }
 
+// Dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic): the three launches on the level pair (u, T); returns the
+// vertex field C_theta that the element / facet launch on the SAME pair reads.  The buffers are allocated by the first
+// run (a context that never switches the term on allocates nothing); the vertex-to-cell CSR and the group list are
+// those of law 8, which the callers have required
+static const double* scalar_dynamic_run(nsfem_ctx* c, const double* u, const double* T) {
+  nsfem_ctx::Dynamic& D = c->dyn;
+  nsfem_ctx::Scalar::DynamicFlux& F = c->sc.dynflux;
+  NSFEM_REQUIRE(c->visc.law == 8 && D.allocated, "dynamic subgrid heat flux: law 8 is not set (nsfem_set_viscosity_law)");
+  const MeshDev& m = c->mesh;
+  if (!F.allocated) {
+    F.mom.alloc((size_t)scalar_dynamic_moments(m.dim) * m.n_cells);
+    F.vert.alloc((size_t)m.n_p1 * 3);
+    F.cthv.alloc((size_t)m.n_p1);
+    F.allocated = true;
+  }
+  if (F.sums.n != (size_t)D.n_groups * 3) F.sums.alloc((size_t)D.n_groups * 3);
+  DynamicDev d;
+  d.n_groups = D.n_groups;
+  d.vptr = D.vptr.p;
+  d.vcell = D.vcell.p;
+  d.goff = D.goff.p;
+  d.gvert = D.gvert.p;
+  d.mom = F.mom.p;
+  d.vert = F.vert.p;
+  d.sums = F.sums.p;
+  d.cs2v = F.cthv.p;
+  launch_scalar_dynamic_constant(c->stream, m, u, T, c->visc.p[0], F.ctheta_max, d);
+  ++F.runs;
+  F.launches += 3;
+  return F.cthv.p;
+}
+
 // The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u).  The convective part
 // (with the Coriolis vector of the level) is in `n` already -- imex_rhs for u1, imex_form_n2 for u2; this adds the rest,
 // V (nsfem_set_viscosity_law) first and B (nsfem_set_bodies) second, each only when switched on: with law 0 / without
@@ -3227,13 +3259,17 @@ static void heated_require(nsfem_ctx* ctx, int scalar_slot) {
 
 // The scalar explicit vector of a level in ONE element launch (plus k_scalar_gather):
 //   out = weight [ C(u) T  + D(u, T)  + H(T) ]
-// D (subgrid heat flux, nsfem_set_scalar_sgs) with sgs.law != 0: the SGS = law kernels; H (heated bodies,
+// D (subgrid heat flux, nsfem_set_scalar_sgs / nsfem_set_scalar_sgs_dynamic) with sgs.law != 0: the SGS = law kernels
+// (8: the dynamic diffusivity, whose constant is formed here on the pair (u, T) first); H (heated bodies,
 // nsfem_set_body_temperatures with at least one flag 1) with a pose: that of the level -- cur for T1, prev for a T2
 // vector formed afresh -- and the fused PENAL kernels.  pose null and sgs.law 0: the launches of old.
 // in_step: the launch is one of nsfem_step_scalar_imex and counts as a convection launch (the hooks' never did)
 static void scalar_explicit_launch(nsfem_ctx* c, const double* u, const double* T, double weight, int form,
-                                   const BodyTable* pose, double* out, const ScalarSgsArgs& sgs, bool in_step) {
+                                   const BodyTable* pose, double* out, const ScalarSgsArgs& sgs_in, bool in_step) {
   const ScalarBodies hb{pose ? *pose : c->bodies.cur, c->bodies.thermal};
+  ScalarSgsArgs sgs = sgs_in;
+  // (dynamic diffusivity: C_theta of THIS level pair, three launches before the element launch)
+  if (sgs.law == 8) sgs.cthv = scalar_dynamic_run(c, u, T);
   launch_scalar_convection(c->stream, c->mesh, u, T, weight, form, pose ? &hb : nullptr, out, sgs);
   if (pose) ++c->bodies.fused_launches;
   if (in_step) ++c->sc.conv_launches;
@@ -3317,16 +3353,45 @@ extern "C" int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t) {
   NSFEM_REQUIRE(std::isfinite(prandtl_t) && prandtl_t >= 0.0,
                 "subgrid heat flux: Pr_t must be 0 (off) or finite and > 0");
   nsfem_ctx::Scalar& sc = ctx->sc;
+  NSFEM_REQUIRE(prandtl_t == 0.0 || !sc.dynflux.on,
+                "subgrid heat flux: a fixed Pr_t while the dynamic diffusivity is on (nsfem_set_scalar_sgs_dynamic)");
   // (the stored vectors belong to the Pr_t they were evaluated with; the term enters no captured Krylov body)
   if (prandtl_t != sc.prandtl_t) ++sc.sgs_epoch;
   sc.prandtl_t = prandtl_t == 0.0 ? 0.0 : prandtl_t;
   API_END(ctx)
 }
 
-// what the convection launches take: the law, its constant (C_s, C_w, c) and 1 / Pr_t while the term is on, nothing
-// otherwise
+// Dynamic subgrid heat flux: kappa_x = c_K Delta_K^2 gamma with C_theta from the Germano identity of the scalar flux
+// (scalar_dynamic_run), no Pr_t.  The stored scalar vector belongs to the switch and the clip it was formed with
+extern "C" int nsfem_set_scalar_sgs_dynamic(nsfem_ctx* ctx, int enable, double ctheta_max) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(enable == 0 || enable == 1, "dynamic subgrid heat flux: enable must be 0 or 1");
+  nsfem_ctx::Scalar& sc = ctx->sc;
+  if (enable) {
+    NSFEM_REQUIRE(std::isfinite(ctheta_max) && ctheta_max > 0.0,
+                  "dynamic subgrid heat flux: ctheta_max must be finite and > 0");
+    NSFEM_REQUIRE(sc.prandtl_t == 0.0,
+                  "dynamic subgrid heat flux: a fixed Pr_t is on (nsfem_set_scalar_sgs); switch it off first");
+  }
+  nsfem_ctx::Scalar::DynamicFlux& F = sc.dynflux;
+  const bool on = enable != 0;
+  const double cmax = on ? ctheta_max : 0.0;
+  if (on != F.on || cmax != F.ctheta_max) ++sc.sgs_epoch;
+  F.on = on;
+  F.ctheta_max = cmax;
+  API_END(ctx)
+}
+
+// what the convection launches take: the law, its constant (C_s, C_w, c) and 1 / Pr_t while the term is on; law 8
+// alone with the dynamic diffusivity (its vertex field is formed by scalar_explicit_launch); nothing otherwise
 static ScalarSgsArgs scalar_sgs_args(const nsfem_ctx* c) {
   ScalarSgsArgs a;
+  if (c->sc.dynflux.on) {
+    a.law = 8;
+    return a;
+  }
   if (c->sc.prandtl_t > 0.0) {
     a.c0 = c->visc.p[0];
     a.inv_prt = 1.0 / c->sc.prandtl_t;
@@ -3339,6 +3404,9 @@ static void scalar_sgs_require_law(const nsfem_ctx* c) {
   const int law = c->visc.law;
   NSFEM_REQUIRE(c->sc.prandtl_t == 0.0 || law == 1 || law == 4 || law == 5,
                 "subgrid heat flux: Pr_t is set but the viscosity law is not 1 (Smagorinsky), 4 (WALE) or 5 (Vreman) "
+                "(nsfem_set_viscosity_law)");
+  NSFEM_REQUIRE(!c->sc.dynflux.on || law == 8,
+                "dynamic subgrid heat flux: the switch is on but the viscosity law is not 8 (dynamic Smagorinsky) "
                 "(nsfem_set_viscosity_law)");
 }
 
@@ -3506,6 +3574,66 @@ extern "C" int nsfem_scalar_sgs_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[1] = ctx->sc.sgs_launches;
   out[2] = ctx->sc.sgs_recomputed;
   out[3] = 0;
+  API_END(ctx)
+}
+
+// ---- dynamic subgrid heat flux: the constant as output / test hook, the cell means of kappa_x, counters
+static void scalar_dynamic_require(nsfem_ctx* ctx, int velocity_slot, int scalar_slot) {
+  NSFEM_REQUIRE(!ctx->comm, "scalar transport: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->sc.dynflux.on, "dynamic subgrid heat flux: the switch is off (nsfem_set_scalar_sgs_dynamic)");
+  scalar_sgs_require_law(ctx);
+  require_velocity_slot(velocity_slot);
+  require_scalar_slot(scalar_slot);
+  ensure_scalar_slot(ctx, scalar_slot);
+}
+
+extern "C" int nsfem_scalar_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, double* ctheta_groups,
+                                             double* sums, double* vertices) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && ctheta_groups, "null argument");
+  scalar_dynamic_require(ctx, velocity_slot, scalar_slot);
+  nsfem_ctx::Scalar::DynamicFlux& F = ctx->sc.dynflux;
+  hipStream_t s = ctx->stream;
+  scalar_dynamic_run(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p);
+  const int ng = ctx->dyn.n_groups;
+  F.h_sums.resize((size_t)ng * 3);
+  NSFEM_HIP(hipMemcpyAsync(F.h_sums.data(), F.sums.p, sizeof(double) * F.h_sums.size(), hipMemcpyDeviceToHost, s));
+  if (vertices)
+    NSFEM_HIP(hipMemcpyAsync(vertices, F.vert.p, sizeof(double) * (size_t)ctx->mesh.n_p1 * 3, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  for (int g = 0; g < ng; ++g) {
+    ctheta_groups[g] = F.h_sums[(size_t)g * 3 + 2];
+    if (sums) {
+      sums[(size_t)g * 2] = F.h_sums[(size_t)g * 3];
+      sums[(size_t)g * 2 + 1] = F.h_sums[(size_t)g * 3 + 1];
+    }
+  }
+  API_END(ctx)
+}
+
+extern "C" int nsfem_scalar_diffusivity_cells(nsfem_ctx* ctx, int velocity_slot, int scalar_slot, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  scalar_dynamic_require(ctx, velocity_slot, scalar_slot);
+  hipStream_t s = ctx->stream;
+  const double* u = ctx->state[velocity_slot].p;
+  // (the law-8 MEAN instantiation of the viscosity kernel with C_theta in the place of C_s^2; the cell means land in
+  // the element buffer, which every user fills before it reads)
+  const double* cthv = scalar_dynamic_run(ctx, u, ctx->state[scalar_slot].p);
+  launch_viscosity_cells(s, ctx->mesh, u, 1.0, 8, ctx->visc.p, true, cthv);
+  NSFEM_HIP(hipMemcpyAsync(out_host, ctx->mesh.rbuf.p, sizeof(double) * ctx->mesh.n_cells, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_scalar_dynamic_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  const nsfem_ctx::Scalar::DynamicFlux& F = ctx->sc.dynflux;
+  out[0] = F.on ? 1 : 0;
+  out[1] = F.runs;
+  out[2] = F.launches;
+  out[3] = (int64_t)(sizeof(double) * (F.mom.n + F.vert.n + F.sums.n + F.cthv.n));
   API_END(ctx)
 }
 
@@ -4682,6 +4810,10 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   hipStream_t s = ctx->stream;
   // (law 8: nu_x of a facet's cell takes the constant of the velocity level the rows are formed on)
   if (wp.law == 8) wp.cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
+  // (... and, with the dynamic subgrid heat flux on, the conductive row carries kappa + c_K Delta_K^2 gamma with C_theta
+  // of the call's level pair)
+  if (wp.law == 8 && scalar_slot != -1 && ctx->sc.dynflux.on)
+    wp.cthv = scalar_dynamic_run(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p);
   launch_wall_facets(s, m, W.n_facets, W.fcell.p, W.flocal.p, ctx->state[velocity_slot].p, ctx->state[pressure_slot].p,
                      scalar_slot != -1 ? ctx->state[scalar_slot].p : nullptr, wp, W.rows.p);
   launch_wall_reduce(s, m.dim, W.n_groups, W.goff.p, W.rows.p, W.sums.p);

@@ -795,6 +795,9 @@ void launch_convection_cells(hipStream_t s, const MeshDev& m, const double* u, c
 // with g_ab = d_b u_a summed from the gradients the point forms anyway, gamma and Delta_K^2 = |det J| / 2 as in
 // k_visc_var_cell and the law of cell_geometry.hpp (visc_law_nu<1> of gamma, visc_law_nu_grad<4 | 5, 2> of g).  SGS 0
 // takes nothing and is the code of every run without the setting.
+// SGS 8 (dynamic diffusivity, nsfem_set_scalar_sgs_dynamic): kappa_x = (c_K Delta_K^2) gamma, the arithmetic of SGS 1
+// with c_K -- the mean of the vertex field C_theta over the cell's vertices, dynamic_cell_constant -- in the place of
+// C_s^2 and no 1 / Pr_t; c_K Delta_K^2 is formed once before the quadrature loop.
 template <int FORM, int PENAL, int SGS = 0>
 __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                           const int32_t* __restrict__ p2,
@@ -827,6 +830,8 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
     }
     for (int s = 0; s < pa.bt.n; ++s) reach = reach || !body_misses_cell<2>(pa.bt, s, xv);
   }
+  double ckd2 = 0.0;                     // c_K Delta_K^2 (SGS 8)
+  if constexpr (SGS == 8) ckd2 = dynamic_cell_constant<2>(sg.vtx, sg.cthv, nc, c) * (0.5 * g.adet);
   double r[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) r[i] = 0.0;
@@ -863,15 +868,26 @@ __global__ __launch_bounds__(256) void k_scalar_conv_cell(int nc, const double* 
     }
     if constexpr (SGS != 0) {
       const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T
-      const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
-      double nux;
-      if constexpr (SGS == 1) {
-        nux = visc_law_nu<1>(gamma, 0.5 * g.adet, sg.c0, 0.0, 0.0);
+      double wk;
+      if constexpr (SGS == 8) {
+        // (the sum under the root written out as the fused sequence the SGS = 1 instantiations compile to with the
+        // present compiler -- left to itself the compiler contracts it in another order in this instantiation and the
+        // last bit of gamma differs.  With every group at the clip this instantiation then gives the bytes of SGS = 1
+        // with C_s^2 = ctheta_max, Pr_t = 1, which tests/test_gpu_dynamic_scalar.py pins; a compiler that contracts
+        // the expression of the other branch differently needs this line written to match)
+        const double gamma = sqrt(0.5 * fma(s11, s11, fma(2.0, s01 * s01, s00 * s00)));
+        wk = w * (ckd2 * gamma);
       } else {
-        const double G[2][2] = {{g00, g01}, {g10, g11}};
-        nux = visc_law_nu_grad<SGS, 2>(G, 0.5 * g.adet, sg.c0);
+        const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
+        double nux;
+        if constexpr (SGS == 1) {
+          nux = visc_law_nu<1>(gamma, 0.5 * g.adet, sg.c0, 0.0, 0.0);
+        } else {
+          const double G[2][2] = {{g00, g01}, {g10, g11}};
+          nux = visc_law_nu_grad<SGS, 2>(G, 0.5 * g.adet, sg.c0);
+        }
+        wk = w * (nux * sg.inv_prt);
       }
-      const double wk = w * (nux * sg.inv_prt);
 #pragma unroll
       for (int i = 0; i < 6; ++i) r[i] += wk * (dtx * gx[i] + dty * gy[i]);
     }
@@ -929,6 +945,8 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
   NSFEM_REQUIRE(form == 0 || form == 1, "scalar convection: form must be 0 (standard) or 1 (skew-symmetric)");
   NSFEM_REQUIRE(!hb || (hb->bt.n > 0 && hb->th.n == hb->bt.n), "heated bodies: no temperatures set for the bodies");
   const int penal = !hb ? 0 : (hb->bt.eps > 0.0 ? 2 : 1);
+  NSFEM_REQUIRE((sgs.law == 8) == (sgs.cthv != nullptr),
+                "scalar convection: the vertex constants go with the dynamic diffusivity and only with it");
   if (m.dim == 3) {
     scalar_convection_cells_3d(s, m, u, T, weight, form, penal, hb, sgs);
   } else {
@@ -936,7 +954,7 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
     with_scalar_kernel(form, penal, sgs.law, [&](auto fc, auto pc, auto lc) {
       constexpr int F = decltype(fc)::value, P = decltype(pc)::value, L = decltype(lc)::value;
       hipLaunchKernelGGL((k_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
-                         scalar_penal_args<P>(hb), scalar_sgs_kernel_args<L>(sgs), m.ndst.p, m.rbuf.p);
+                         scalar_penal_args<P>(hb), scalar_sgs_kernel_args<L>(sgs, m.p1.p), m.ndst.p, m.rbuf.p);
     });
   }
   hipLaunchKernelGGL(k_scalar_gather, dim3(grid_for(m.n_p2)), dim3(kBlock), 0, s, m.n_p2, m.nptr.p, m.rbuf.p, out);
@@ -1278,6 +1296,173 @@ void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, d
                        d.mom, alpha * alpha, d.vert);
   }
   hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, cs2_max, d.sums, d.cs2v);
+  NSFEM_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- dynamic subgrid heat flux: the Germano-Lilly C_theta
+// kappa_x = c_K Delta_K^2 gamma (nsfem_set_scalar_sgs_dynamic).  Three launches on a level pair (u, T)
+// (launch_scalar_dynamic_constant), plain stores, no atomics, the same state gives the same bytes:
+//   k_dyn_scalar_moments<DIM>  one thread per CELL: m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q by the degree-5 rule for
+//                              f = T | T u_a | u_a | d_a T | gamma d_a T (scaled by Delta_K^2 at the store) | S_ab
+//                              (a <= b), then |K| and |K| Delta_K^2: NM = 1 + 4 DIM + NS + 2 doubles per cell (14 | 21),
+//                              SoA [NM][n_cells].  grad T and G from the differences T_k - T_0, u_k - u_0: a constant T
+//                              or u gives an exact 0.0.  The set repeats u_a, S_ab and the volumes of k_dyn_moments on
+//                              purpose: the buffer of law 8 may hold another level when the scalar step runs.
+//   k_dyn_scalar_vertex<DIM>   one thread per VERTEX: the patch sums in ascending cell order, the test-filtered fields,
+//                              P_a = hat(T u_a) - hat T hat u_a, R_a = hat(Delta^2 gamma d_a T) - alpha^2 Delta_v^2
+//                              hat gamma hat(d_a T); writes W_v, PR_v = P . R, RR_v = R . R ([n_p1][3])
+//   k_dyn_reduce               unchanged, with ctheta_max as its clip: num_g, den_g, ctheta_g and C_theta at the vertices
+template <int DIM>
+__global__ void k_dyn_scalar_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
+                                     const double* __restrict__ u, const double* __restrict__ T,
+                                     double* __restrict__ mom);                             // <3>: assembly3d.hip
+
+template <>
+__global__ __launch_bounds__(256) void k_dyn_scalar_moments<2>(int nc, const double* __restrict__ vx,
+                                                               const int32_t* __restrict__ p2,
+                                                               const double* __restrict__ u,
+                                                               const double* __restrict__ T,
+                                                               double* __restrict__ mom) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo g = load_geo(vx, nc, c);
+  const double vol = 0.5 * g.adet, delta2 = 0.5 * g.adet;      // |K| and Delta_K^2 = |K|^(2 / dim)
+  double ux[6], uy[6], t[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int node = p2[(size_t)k * nc + c];
+    const double2 a = reinterpret_cast<const double2*>(u)[node];
+    ux[k] = a.x;
+    uy[k] = a.y;
+    t[k] = T[node];
+  }
+  double mt = 0.0, mtu[2] = {0.0, 0.0}, mu[2] = {0.0, 0.0}, md[2] = {0.0, 0.0}, mgd[2] = {0.0, 0.0};
+  double ms[3] = {0.0, 0.0, 0.0};
+  double wsum = 0.0;
+  for (int q = 0; q < 7; ++q) {
+    double uqx = 0.0, uqy = 0.0, tq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      uqx += c_q.phi2[q][k] * ux[k];
+      uqy += c_q.phi2[q][k] * uy[k];
+      tq += c_q.phi2[q][k] * t[k];
+    }
+    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a
+    double dtx = 0.0, dty = 0.0;                            // grad T
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+      double gx, gy;
+      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx, gy);
+      const double dx = ux[k] - ux[0], dy = uy[k] - uy[0], dt = t[k] - t[0];
+      g00 += gx * dx;
+      g01 += gy * dx;
+      g10 += gx * dy;
+      g11 += gy * dy;
+      dtx += gx * dt;
+      dty += gy * dt;
+    }
+    const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T = 2 S
+    const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
+    const double w = c_q.w[q];
+    wsum += w;
+    mt += w * tq;
+    mtu[0] += w * (tq * uqx);
+    mtu[1] += w * (tq * uqy);
+    mu[0] += w * uqx;
+    mu[1] += w * uqy;
+    md[0] += w * dtx;
+    md[1] += w * dty;
+    mgd[0] += w * (gamma * dtx);
+    mgd[1] += w * (gamma * dty);
+    ms[0] += w * (0.5 * s00);
+    ms[1] += w * (0.5 * s01);
+    ms[2] += w * (0.5 * s11);
+  }
+  const double f = vol / wsum;
+  double* o = mom + c;
+  o[0] = f * mt;
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    o[(size_t)(1 + a) * nc] = f * mtu[a];
+    o[(size_t)(3 + a) * nc] = f * mu[a];
+    o[(size_t)(5 + a) * nc] = f * md[a];
+    o[(size_t)(7 + a) * nc] = (f * delta2) * mgd[a];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[(size_t)(9 + k) * nc] = f * ms[k];
+  o[(size_t)12 * nc] = vol;
+  o[(size_t)13 * nc] = vol * delta2;
+}
+
+// vert[v] = {W_v, PR_v, RR_v}.  Rows of the moments: T | T u_a | u_a | d_a T | Delta^2 gamma d_a T | S_ab (a <= b in row
+// order; the contraction S : S counts the off-diagonal pairs twice) | |K| | |K| Delta^2.  alpha2 = alpha^2
+template <int DIM>
+__global__ __launch_bounds__(256) void k_dyn_scalar_vertex(int nv, int nc, const int32_t* __restrict__ vptr,
+                                                           const int32_t* __restrict__ vcell,
+                                                           const double* __restrict__ mom, double alpha2,
+                                                           double* __restrict__ vert) {
+#pragma clang fp contract(off)
+  constexpr int NS = DIM * (DIM + 1) / 2, NM = 1 + 4 * DIM + NS + 2;
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  double a[NM];
+#pragma unroll
+  for (int i = 0; i < NM; ++i) a[i] = 0.0;
+  const int e = vptr[v + 1];
+  for (int k = vptr[v]; k < e; ++k) {
+    const double* m = mom + vcell[k];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) a[i] += m[(size_t)i * nc];
+  }
+  double* o = vert + (size_t)v * 3;
+  const double W = a[NM - 2];
+  if (!(W > 0.0)) {                     // (a vertex of no cell: no patch, no contribution)
+    o[0] = o[1] = o[2] = 0.0;
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < NM; ++i) a[i] /= W;
+  constexpr int TU = 1, UU = 1 + DIM, DT = 1 + 2 * DIM, GD = 1 + 3 * DIM, SS = 1 + 4 * DIM;
+  const double d2 = a[NM - 1];
+  double ss = 0.0;
+  {
+    int i = 0;
+#pragma unroll
+    for (int r = 0; r < DIM; ++r)
+#pragma unroll
+      for (int c = r; c < DIM; ++c, ++i) ss += (r == c ? 1.0 : 2.0) * (a[SS + i] * a[SS + i]);
+  }
+  const double hgam = sqrt(2.0 * ss);
+  const double coef = (alpha2 * d2) * hgam;
+  double pr = 0.0, rr = 0.0;
+#pragma unroll
+  for (int r = 0; r < DIM; ++r) {
+    const double P = a[TU + r] - a[0] * a[UU + r];
+    const double R = a[GD + r] - coef * a[DT + r];
+    pr += P * R;
+    rr += R * R;
+  }
+  o[0] = W;
+  o[1] = pr;
+  o[2] = rr;
+}
+
+void launch_scalar_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
+                                    double ctheta_max, const DynamicDev& d) {
+  NSFEM_REQUIRE(d.n_groups >= 1 && d.vptr && d.vcell && d.goff && d.gvert && d.mom && d.vert && d.sums && d.cs2v,
+                "dynamic subgrid heat flux: buffers not allocated");
+  if (m.dim == 3) {
+    scalar_dynamic_moments_3d(s, m, u, T, d.mom);
+    hipLaunchKernelGGL((k_dyn_scalar_vertex<3>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr,
+                       d.vcell, d.mom, alpha * alpha, d.vert);
+  } else {
+    hipLaunchKernelGGL((k_dyn_scalar_moments<2>), dim3(grid_for(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p,
+                       m.p2.p, u, T, d.mom);
+    hipLaunchKernelGGL((k_dyn_scalar_vertex<2>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr,
+                       d.vcell, d.mom, alpha * alpha, d.vert);
+  }
+  hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, ctheta_max, d.sums,
+                     d.cs2v);
   NSFEM_HIP(hipGetLastError());
 }
 

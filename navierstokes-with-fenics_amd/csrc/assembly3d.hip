@@ -840,6 +840,103 @@ __global__ __launch_bounds__(256) void k_dyn_moments<3>(int nc, const double* __
   o[(size_t)22 * nc] = vol * delta2;
 }
 
+// ---- dynamic subgrid heat flux on tetrahedra: the cell moments of launch_scalar_dynamic_constant (assembly.hip, where
+// the definition, the vertex and the group kernels are), one thread per cell, 15-point rule.  NM = 21 rows, SoA
+// [21][n_cells]: T | T u_a (3) | u_a (3) | d_a T (3) | Delta_K^2 gamma d_a T (3) | S_ab (6, a <= b in row order) | |K| |
+// |K| Delta_K^2.  grad T and G from the differences T_k - T_0, u_k - u_0, as in 2D.
+template <int DIM>
+__global__ void k_dyn_scalar_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
+                                     const double* __restrict__ u, const double* __restrict__ T,
+                                     double* __restrict__ mom);                             // <2>: assembly.hip
+
+template <>
+__global__ __launch_bounds__(256) void k_dyn_scalar_moments<3>(int nc, const double* __restrict__ vx,
+                                                               const int32_t* __restrict__ p2,
+                                                               const double* __restrict__ u,
+                                                               const double* __restrict__ T,
+                                                               double* __restrict__ mom) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const CellGeo3 g = load_geo3(vx, nc, c);
+  const double vol = g.adet / 6.0;
+  const double delta = cbrt(vol);
+  const double delta2 = delta * delta;
+  double un[10][3], t[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    const size_t node = (size_t)p2[(size_t)k * nc + c];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
+    t[k] = T[node];
+  }
+  double mt = 0.0;
+  double mtu[3] = {0.0, 0.0, 0.0}, mu[3] = {0.0, 0.0, 0.0}, md[3] = {0.0, 0.0, 0.0}, mgd[3] = {0.0, 0.0, 0.0};
+  double ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double wsum = 0.0;
+  for (int q = 0; q < 15; ++q) {
+    double uq[3] = {0.0, 0.0, 0.0}, tq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const double ph = c_q3.phi2[q][k];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) uq[a] += ph * un[k][a];
+      tq += ph * t[k];
+    }
+    double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};     // G[a][b] = d_b u_a
+    double dt[3] = {0.0, 0.0, 0.0};                                            // grad T
+#pragma unroll
+    for (int k = 1; k < 10; ++k) {
+      double gk[3];
+      phys3(g, c_q3.dphi2[q][k], gk);
+      const double dtk = t[k] - t[0];
+#pragma unroll
+      for (int b = 0; b < 3; ++b) dt[b] += gk[b] * dtk;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double d = un[k][a] - un[0][a];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) G[a][b] += gk[b] * d;
+      }
+    }
+    const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
+    const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
+    const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
+    const double w = c_q3.w[q];
+    wsum += w;
+    const double S[6] = {0.5 * s00, 0.5 * s01, 0.5 * s02, 0.5 * s11, 0.5 * s12, 0.5 * s22};
+    mt += w * tq;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      mtu[a] += w * (tq * uq[a]);
+      mu[a] += w * uq[a];
+      md[a] += w * dt[a];
+      mgd[a] += w * (gamma * dt[a]);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ms[k] += w * S[k];
+  }
+  const double f = vol / wsum;
+  double* o = mom + c;
+  o[0] = f * mt;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    o[(size_t)(1 + a) * nc] = f * mtu[a];
+    o[(size_t)(4 + a) * nc] = f * mu[a];
+    o[(size_t)(7 + a) * nc] = f * md[a];
+    o[(size_t)(10 + a) * nc] = (f * delta2) * mgd[a];
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[(size_t)(13 + k) * nc] = f * ms[k];
+  o[(size_t)19 * nc] = vol;
+  o[(size_t)20 * nc] = vol * delta2;
+}
+
+void scalar_dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom) {
+  hipLaunchKernelGGL((k_dyn_scalar_moments<3>), dim3(grid3(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u,
+                     T, mom);
+  NSFEM_HIP(hipGetLastError());
+}
+
 void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, double* mom) {
   hipLaunchKernelGGL((k_dyn_moments<3>), dim3(grid3(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u, mom);
   NSFEM_HIP(hipGetLastError());
@@ -942,7 +1039,8 @@ void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double w
 // SGS 1, 4, 5 (the subgrid law): subgrid heat flux, as k_scalar_conv_cell -- the same launch adds
 // wgt sum_q w_q |det J| kappa_x grad T_q . grad phi_i(x_q), kappa_x = nu_x / Pr_t (SGS 1: (C_s Delta_K)^2 gamma / Pr_t),
 // nu_x (visc_law_at<SGS, 3>) and Delta_K as in k3_visc_var_cell; the gradients of a point are kept in either form then.
-// SGS 0 takes nothing.
+// SGS 0 takes nothing.  SGS 8 (dynamic diffusivity): kappa_x = (c_K Delta_K^2) gamma with c_K from the vertex field
+// C_theta (dynamic_cell_constant), formed once before the quadrature loop; no 1 / Pr_t.
 template <int FORM, int PENAL, int SGS = 0>
 __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double* __restrict__ vx,
                                                            const int32_t* __restrict__ p2,
@@ -960,6 +1058,8 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
     const double delta = cbrt(g.adet / 6.0);
     delta2 = delta * delta;
   }
+  double ckd2 = 0.0;                     // c_K Delta_K^2 (SGS 8)
+  if constexpr (SGS == 8) ckd2 = dynamic_cell_constant<3>(sg.vtx, sg.cthv, nc, c) * delta2;
   double un[10][3], t[10];
 #pragma unroll
   for (int k = 0; k < 10; ++k) {
@@ -1016,7 +1116,9 @@ __global__ __launch_bounds__(256) void k3_scalar_conv_cell(int nc, const double*
       const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
       const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
       const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
-      const double wk = w * (visc_law_at<SGS, 3>(G, gamma, delta2, sg.c0, 0.0, 0.0) * sg.inv_prt);
+      double wk;
+      if constexpr (SGS == 8) wk = w * (ckd2 * gamma);
+      else wk = w * (visc_law_at<SGS, 3>(G, gamma, delta2, sg.c0, 0.0, 0.0) * sg.inv_prt);
 #pragma unroll
       for (int i = 0; i < 10; ++i) r[i] += wk * (dt[0] * gk[i][0] + dt[1] * gk[i][1] + dt[2] * gk[i][2]);
     }
@@ -1045,7 +1147,7 @@ void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u
   with_scalar_kernel(form, penal, sgs.law, [&](auto fc, auto pc, auto lc) {
     constexpr int F = decltype(fc)::value, P = decltype(pc)::value, L = decltype(lc)::value;
     hipLaunchKernelGGL((k3_scalar_conv_cell<F, P, L>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, weight,
-                       scalar_penal_args<P>(hb), scalar_sgs_kernel_args<L>(sgs), m.ndst.p, m.rbuf.p);
+                       scalar_penal_args<P>(hb), scalar_sgs_kernel_args<L>(sgs, m.p1.p), m.ndst.p, m.rbuf.p);
   });
   NSFEM_HIP(hipGetLastError());
 }

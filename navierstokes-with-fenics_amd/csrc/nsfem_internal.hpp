@@ -487,19 +487,28 @@ void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u
 // Subgrid heat flux (nsfem_set_scalar_sgs): the launchers take ScalarSgsArgs by value.  law 1, 4 or 5 (Smagorinsky,
 // WALE, Vreman): the same launch adds D(u, T), the eddy diffusivity kappa_x = nu_x inv_prt of that law with its
 // constant c0 (C_s, C_w, c) under the gradients (the SGS = law instantiations), out = weight (C(u) T + D(u, T));
-// law 0: the term is off, the SGS = 0 kernels, which take nothing
+// law 0: the term is off, the SGS = 0 kernels, which take nothing.  law 8 (nsfem_set_scalar_sgs_dynamic): kappa_x =
+// c_K Delta_K^2 gamma with c_K from cthv, the vertex field C_theta of launch_scalar_dynamic_constant on the same level
+// pair (u, T); no Pr_t, c0 and inv_prt are not read
 struct ScalarSgsArgs {
   double c0 = 0.0, inv_prt = 0.0;
   int32_t law = 0;
   int32_t pad_ = 0;
+  const double* cthv = nullptr;
 };
-// ... and what the kernels take: the two numbers with SGS != 0, nothing at all with SGS = 0
+// ... and what the kernels take: the two numbers with SGS = 1, 4, 5, the P1 connectivity and the vertex field with
+// SGS = 8, nothing at all with SGS = 0
 template <int SGS>
 struct ScalarSgsKernelArgs {
   double c0, inv_prt;
 };
 template <>
 struct ScalarSgsKernelArgs<0> {};
+template <>
+struct ScalarSgsKernelArgs<8> {
+  const int32_t* vtx;
+  const double* cthv;
+};
 // variable viscosity (nsfem_set_viscosity_law; law 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman, p = params): the element kernel
 // k_visc_var_cell / k3_visc_var_cell on the velocity u, element vectors weight * V_K(u) node-sorted into m.rbuf --
 // mean: the cell means of nu_x into the first n_cells doubles of m.rbuf instead
@@ -522,6 +531,14 @@ struct DynamicDev {
 void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, double alpha, double cs2_max,
                              const DynamicDev& d);
 void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, double* mom);
+// dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic): the Germano identity of the scalar flux on the level pair
+// (u, T) -- k_dyn_scalar_moments, k_dyn_scalar_vertex, then k_dyn_reduce with ctheta_max as its clip.  d as above
+// with buffers of its own: mom [NM][n_cells] (NM = 14 | 21), vert [n_p1][3] = W, PR, RR, sums [n_groups][3] = num, den,
+// ctheta, cs2v [n_p1] = C_theta at the vertices; the CSR and the group list are those of law 8
+void launch_scalar_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
+                                    double ctheta_max, const DynamicDev& d);
+void scalar_dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom);
+inline int scalar_dynamic_moments(int dim) { return dim == 2 ? 14 : 21; }
 // k_visc_gather: v = per-node sums of m.rbuf in ascending cell order; n1 += v, rhs -= b0 v (rhs may be null)
 void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double* n1, double* rhs);
 // immersed bodies (nsfem_set_bodies): the table the penalisation kernels take as a kernel ARGUMENT (1.6 kB; entries
@@ -568,11 +585,12 @@ inline void with_int(int v, F&& f) {
 }
 // The ONE place that turns the run-time (form, PENAL, law) of a scalar element launch into template arguments:
 // f(FORM, PENAL, SGS) gets three integral constants, so each translation unit holds one launch of k_scalar_conv_cell
-// <FORM, PENAL, SGS> / k3_scalar_conv_cell -- 2 forms x 3 PENAL x 4 SGS (the subgrid laws 1, 4, 5; 0 for all else)
+// <FORM, PENAL, SGS> / k3_scalar_conv_cell -- 2 forms x 3 PENAL x 5 SGS (the subgrid laws 1, 4, 5, the dynamic
+// diffusivity 8; 0 for all else)
 template <class F>
 inline void with_scalar_kernel(int form, int penal, int law, F&& f) {
   with_int<0, 1>(form, [&](auto fc) {
-    with_int<0, 1, 2>(penal, [&](auto pc) { with_int<1, 4, 5, 0>(law, [&](auto lc) { f(fc, pc, lc); }); });
+    with_int<0, 1, 2>(penal, [&](auto pc) { with_int<1, 4, 5, 8, 0>(law, [&](auto lc) { f(fc, pc, lc); }); });
   });
 }
 // (PENAL 0 and SGS 0 are the code of every run without temperatures / without the term: their kernels take nothing)
@@ -582,8 +600,9 @@ inline ScalarPenalArgs<PENAL> scalar_penal_args(const ScalarBodies* hb) {
   else return {hb->bt, hb->th};
 }
 template <int SGS>
-inline ScalarSgsKernelArgs<SGS> scalar_sgs_kernel_args(const ScalarSgsArgs& a) {
+inline ScalarSgsKernelArgs<SGS> scalar_sgs_kernel_args(const ScalarSgsArgs& a, const int32_t* p1) {
   if constexpr (SGS == 0) return {};
+  else if constexpr (SGS == 8) return {p1, a.cthv};
   else return {a.c0, a.inv_prt};
 }
 // out = weight (C(u) T + D(u, T) + H(T)): the fused element kernel k_scalar_conv_cell<FORM, PENAL, SGS> /
@@ -715,6 +734,8 @@ struct WallParams {
   int law = 0;                               // 0: constant viscosity; 1, 2, 4, 5, 8: + nu_x of visc_law_at<law>
   double law_p[3] = {0.0, 0.0, 0.0};
   const double* cs2v = nullptr;              // law 8: the vertex field C_s^2 (launch_dynamic_constant), else null
+  const double* cthv = nullptr;              // law 8 and != null: the heat row uses kappa + c_K Delta_K^2 gamma, c_K from
+                                             // this vertex field C_theta (launch_scalar_dynamic_constant)
   double inv_prt = 0.0;                      // law 1, 4, 5 and != 0: the heat row uses kappa + nu_x inv_prt (subgrid heat flux)
 };
 // ONE launch: rows[f][NW] of the nf facets (fcell, flocal: device lists); T may be null (no scalar: +0.0 entries)
@@ -1325,6 +1346,18 @@ struct nsfem_ctx {
     // sgs_epoch counts the changes of prandtl_t
     double prandtl_t = 0.0;
     int64_t sgs_epoch = 0, sgs_launches = 0, sgs_recomputed = 0;
+    // dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic): kappa_x = c_K Delta_K^2 gamma with C_theta from the
+    // Germano identity of the scalar flux on the level pair of the launch -- formed before every SGS = 8 element
+    // launch, no stored state.  A change of the switch or of ctheta_max counts in sgs_epoch; alpha and the groups are
+    // the law's (visc.epoch).  The buffers are allocated by the first run and kept; the vertex-to-cell CSR and the
+    // group list are those of `dyn`
+    struct DynamicFlux {
+      bool on = false, allocated = false;
+      double ctheta_max = 0.0;
+      nsfem::DevBuf<double> mom, vert, sums, cthv;
+      std::vector<double> h_sums;
+      int64_t runs = 0, launches = 0;
+    } dynflux;
     // Key of the stored vectors TCONV_1, TCONV_2: the form, bodies.thermal_epoch, bodies.epoch (compared only while a
     // body is thermal), sgs_epoch and visc.epoch (compared only while the subgrid term is on) they were formed with.
     // The three answers are kept apart: a stale heat key and a stale subgrid key are counted each on its own.

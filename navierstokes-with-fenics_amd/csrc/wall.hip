@@ -48,7 +48,9 @@ __device__ __forceinline__ void wall_p2_at(const double* lam, const double (*gl)
 //   [1 + 2 DIM]               int u.n
 //   [2 + 2 DIM]               int T                  (+0.0 without a scalar)
 //   [3 + 2 DIM]               int -kappa grad T . n  (+0.0 without a scalar); with LAW = 1, 4, 5 and ipr = 1 / Pr_t != 0
-//                             (subgrid heat flux, nsfem_set_scalar_sgs): int -(kappa + nu_x ipr) grad T . n
+//                             (subgrid heat flux, nsfem_set_scalar_sgs): int -(kappa + nu_x ipr) grad T . n; with
+//                             LAW = 8 and cthv != null (nsfem_set_scalar_sgs_dynamic): int -(kappa + c_K Delta_K^2
+//                             gamma) grad T . n, c_K the cell mean of the vertex field C_theta
 //   [4 + 2 DIM ..]            int (x - x0) x t, t the sum of the two traction integrands (2D: the z component)
 // n = the unit normal pointing out of the facet's cell.
 template <int DIM, int LAW>
@@ -59,7 +61,8 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
                                                      const double* __restrict__ p, const double* __restrict__ T,
                                                      double nu, double sym, double kappa, double ox, double oy,
                                                      double oz, double lp0, double lp1, double lp2, double ipr,
-                                                     double* __restrict__ out, const double* __restrict__ cs2v) {
+                                                     double* __restrict__ out, const double* __restrict__ cs2v,
+                                                     const double* __restrict__ cthv) {
   constexpr int NV = DIM + 1, N2 = DIM == 2 ? 6 : 10, NQ = DIM == 2 ? 2 : 3;
   constexpr int NT = DIM == 2 ? 1 : 3, NW = 2 * DIM + 4 + NT;
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,6 +139,11 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
   }
   // LAW 8 (dynamic Smagorinsky): c_K of the facet's cell from the vertex field in the place of the constant
   if constexpr (LAW == 8) lp0 = dynamic_cell_constant<DIM>(p1, cs2v, nc, c);
+  // ... and, with the dynamic subgrid heat flux on, c_K Delta_K^2 of the eddy diffusivity from the second vertex field
+  double ckd2 = 0.0;
+  if constexpr (LAW == 8) {
+    if (cthv) ckd2 = dynamic_cell_constant<DIM>(p1, cthv, nc, c) * delta2;
+  }
   // nodal data
   const bool have_T = T != nullptr;
   double un[N2][3], pn[NV], Tn[N2];
@@ -196,7 +204,7 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
     }
 #pragma unroll
     for (int d = 0; d < DIM; ++d) r[d] -= org[d];
-    double nux = 0.0;
+    double nux = 0.0, kapx = 0.0;
     if constexpr (LAW != 0) {
       double ss = 0.0;                                  // sum_ab (G_ab + G_ba)^2
 #pragma unroll
@@ -215,6 +223,7 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
         nux = visc_law_nu_grad<LAW, DIM>(Gd, delta2, lp0);
       } else {
         nux = visc_law_nu<LAW>(sqrt(0.5 * ss), delta2, lp0, lp1, lp2);
+        if constexpr (LAW == 8) kapx = ckd2 * sqrt(0.5 * ss);
       }
     }
     double tr[3] = {0.0, 0.0, 0.0};                     // traction at the point
@@ -236,6 +245,7 @@ __global__ __launch_bounds__(256) void k_wall_facets(int nf, int nc, const int32
     }
     sT += w * Tq;
     if ((LAW == 1 || LAW == 4 || LAW == 5) && ipr != 0.0) heat += w * (-(kappa + nux * ipr) * hq);
+    else if (LAW == 8 && cthv != nullptr) heat += w * (-(kappa + kapx) * hq);
     else heat += w * (-kappa * hq);
     if (DIM == 2) {
       tq[0] += w * (r[0] * tr[1] - r[1] * tr[0]);
@@ -295,7 +305,7 @@ static void launch_wall_facets_t(hipStream_t s, const MeshDev& m, int nf, const 
   const int grid = (nf + 255) / 256;
   hipLaunchKernelGGL((k_wall_facets<DIM, LAW>), dim3(grid), dim3(256), 0, s, nf, m.n_cells, fcell, flocal, m.vx.p,
                      m.p2.p, m.p1.p, u, p, T, w.nu, w.sym, w.kappa, w.origin[0], w.origin[1], w.origin[2], w.law_p[0],
-                     w.law_p[1], w.law_p[2], w.inv_prt, rows, w.cs2v);
+                     w.law_p[1], w.law_p[2], w.inv_prt, rows, w.cs2v, w.cthv);
 }
 
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
@@ -304,6 +314,7 @@ void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* 
   NSFEM_REQUIRE((w.law >= 0 && w.law <= 2) || w.law == 4 || w.law == 5 || w.law == 8,
                 "wall quantities: unknown viscosity law");
   NSFEM_REQUIRE((w.law == 8) == (w.cs2v != nullptr), "wall quantities: the vertex constants go with law 8 and only with it");
+  NSFEM_REQUIRE(w.law == 8 || w.cthv == nullptr, "wall quantities: the vertex field C_theta goes with law 8 only");
   using Fn = void (*)(hipStream_t, const MeshDev&, int, const int32_t*, const int32_t*, const double*, const double*,
                       const double*, const WallParams&, double*);
   // (3, 6 and 7 are no laws: their columns are never taken)

@@ -29,6 +29,10 @@ eddy diffusivity kappa_x = nu_x / prandtl_t to the transport step, inside the sa
 4r).  The solver pushes prandtl_t wherever it pushes the viscosity model and the scalar coefficients; a model
 without prandtl_t, or no model, pushes 0 (off).  The term is explicit: unconditionally stable only while kappa_x <
 kappa / 3, otherwise k is bounded by about Delta^2 / kappa_x.
+
+Dynamic subgrid heat flux: ``DynamicSmagorinskyModel(..., heat_flux="dynamic", ctheta_max=...)`` adds D(u, T) with
+kappa_x = c_K Delta_K^2 gamma, C_theta computed on the device from the Germano identity of the scalar flux on the
+level pair of every launch.  The solver pushes the fixed switch as before and then the dynamic one.
 """
 import numpy as np
 
@@ -122,9 +126,19 @@ class BoussinesqIMEXSolver(IMEXIPCSSolver):
     def _push_scalar_sgs(self):
         if not hasattr(self, "_ctx"):
             return
-        prandtl_t = getattr(getattr(self, "_viscosity_model", None), "prandtl_t", None)
+        model = getattr(self, "_viscosity_model", None)
+        prandtl_t = getattr(model, "prandtl_t", None)
+        dynamic = getattr(model, "heat_flux", None) == "dynamic"
         try:
+            # (the two switches exclude each other on the device: the one that goes off goes first; a run that never
+            # asked for the dynamic one never calls its setter)
+            if not dynamic and getattr(self, "_pushed_dynamic_flux", None) is self._ctx:
+                self._ctx.set_scalar_sgs_dynamic(False)
+                self._pushed_dynamic_flux = None
             self._ctx.set_scalar_sgs(0.0 if prandtl_t is None else prandtl_t)
+            if dynamic:
+                self._ctx.set_scalar_sgs_dynamic(True, model.ctheta_max)
+                self._pushed_dynamic_flux = self._ctx
         except nat.NativeError as err:
             raise RuntimeError(str(err))
 

@@ -432,12 +432,37 @@ class ProblemBase:
         except nat.NativeError as err:
             raise RuntimeError(str(err))
 
+    def _compute_model_scalar_constant(self):
+        """(C_theta, Pr_t) of every averaging group of a ``DynamicSmagorinskyModel(heat_flux="dynamic")`` for the
+        current velocity and scalar, from the device (nsfem_scalar_dynamic_constant, nsfem_dynamic_constant): two
+        arrays [n_groups], Pr_t,g = cs2_g / ctheta_g, ``inf`` where ctheta_g = 0.  New helper."""
+        import _native as nat
+        ctx = self._get_solver()._ctx
+        try:
+            ctheta = ctx.scalar_dynamic_constant(nat.U0, nat.T0)
+            cs2 = ctx.dynamic_constant(nat.U0)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+        prandtl_t = np.full(ctheta.shape, np.inf)
+        np.divide(cs2, ctheta, out=prandtl_t, where=ctheta > 0.0)
+        return ctheta, prandtl_t
+
     def _compute_model_diffusivity(self):
-        """cell means of the eddy diffusivity kappa_x = nu_x / Pr_t of the subgrid heat flux (a ``SmagorinskyModel``
-        with ``prandtl_t``) for the current velocity: the cell means of ``_compute_model_viscosity`` divided by Pr_t.
+        """cell means of the eddy diffusivity of the subgrid heat flux for the current velocity: kappa_x = nu_x / Pr_t
+        (a model with ``prandtl_t``) -- the cell means of ``_compute_model_viscosity`` divided by Pr_t --, or kappa_x =
+        c_K Delta_K^2 gamma of a ``DynamicSmagorinskyModel(heat_flux="dynamic")`` from the device
+        (nsfem_scalar_diffusivity_cells, the constant formed on the current velocity and scalar).
         New helper; valid for ``_add_to_field_output``."""
         from fem_function import HostField
-        prandtl_t = getattr(getattr(self._get_solver(), "_viscosity_model", None), "prandtl_t", None)
+        model = getattr(self._get_solver(), "_viscosity_model", None)
+        if getattr(model, "heat_flux", None) == "dynamic":
+            import _native as nat
+            try:
+                values = self._get_solver()._ctx.scalar_diffusivity_cells(nat.U0, nat.T0)
+            except nat.NativeError as err:
+                raise RuntimeError(str(err))
+            return HostField(self._mesh, "model diffusivity", "Cell", values)
+        prandtl_t = getattr(model, "prandtl_t", None)
         if prandtl_t is None:
             raise RuntimeError("model diffusivity: the viscosity model has no turbulent Prandtl number (prandtl_t)")
         values = self._compute_model_viscosity().values / prandtl_t

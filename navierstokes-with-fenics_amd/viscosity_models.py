@@ -108,11 +108,15 @@ class DynamicSmagorinskyModel:
     ``nsfem_set_viscosity_law``): test filter over the vertex patches of width ``filter_ratio`` > 1 times the grid
     filter, least squares over averaging groups of vertices, clipped to [0, ``cs2_max``].  ``averaging``: "global" (one
     group of all vertices) or ("planes", axis) -- one group per set of vertices of equal coordinate along ``axis``, for
-    a channel.  No subgrid heat flux goes with this model (``prandtl_t`` is None)."""
+    a channel.  ``heat_flux``: None -- the scalar sees its molecular diffusivity alone -- or "dynamic": a solver with a
+    transported scalar (``BoussinesqIMEXSolver``) adds the subgrid heat flux with the eddy diffusivity kappa_x = c_K
+    Delta_K^2 gamma, its constant C_theta from the Germano identity of the scalar flux over the same groups, clipped to
+    [0, ``ctheta_max``] (``nsfem_set_scalar_sgs_dynamic``).  No fixed Pr_t goes with this model (``prandtl_t`` is
+    None): Pr_t = C_s^2 / C_theta is an output."""
     law_id = LAW_DYNAMIC
     prandtl_t = None
 
-    def __init__(self, averaging="global", filter_ratio=2.0, cs2_max=0.09):
+    def __init__(self, averaging="global", filter_ratio=2.0, cs2_max=0.09, heat_flux=None, ctheta_max=0.2):
         if averaging != "global":
             ok = isinstance(averaging, (tuple, list)) and len(averaging) == 2 and averaging[0] == "planes"
             ok = ok and isinstance(averaging[1], (int, )) and not isinstance(averaging[1], bool) and 0 <= averaging[1] <= 2
@@ -125,7 +129,15 @@ class DynamicSmagorinskyModel:
             raise ValueError("DynamicSmagorinskyModel: filter_ratio must be finite and > 1, got %r" % (filter_ratio, ))
         if not (math.isfinite(cs2_max) and cs2_max > 0.0):
             raise ValueError("DynamicSmagorinskyModel: cs2_max must be finite and > 0, got %r" % (cs2_max, ))
+        if heat_flux is not None and heat_flux != "dynamic":
+            raise ValueError('DynamicSmagorinskyModel: heat_flux must be None or "dynamic", got %r' % (heat_flux, ))
+        if isinstance(ctheta_max, bool):
+            raise ValueError("DynamicSmagorinskyModel: ctheta_max must be a number, got %r" % (ctheta_max, ))
+        ctheta_max = float(ctheta_max)
+        if not (math.isfinite(ctheta_max) and ctheta_max > 0.0):
+            raise ValueError("DynamicSmagorinskyModel: ctheta_max must be finite and > 0, got %r" % (ctheta_max, ))
         self.averaging, self.filter_ratio, self.cs2_max = averaging, filter_ratio, cs2_max
+        self.heat_flux, self.ctheta_max = heat_flux, ctheta_max
 
     def params(self, coefficients=None):
         return (self.filter_ratio, self.cs2_max, 0.0, 0.0)

@@ -14,7 +14,9 @@ traction of one boundary id, lists uploaded at every call) stays as it is.
   grad u^T) n`` when the solver has a viscosity model.  ``n`` points out of the fluid.
 * ``compute()``: ``{boundary_id: dict(area, pressure_force, viscous_force, force, torque, mass_flux, mean_temperature,
   heat_flux)}``; ``heat_flux`` = ``int -kappa grad T . n``, the conductive heat LEAVING the fluid (temperature
-  entries are 0 for a solver without a scalar).
+  entries are 0 for a solver without a scalar).  With a subgrid heat flux the device forms the row with ``kappa +
+  kappa_x``: ``nu_x / Pr_t`` of a model with ``prandtl_t``, ``c_K Delta_K^2 gamma`` of a
+  ``DynamicSmagorinskyModel(heat_flux="dynamic")`` with the constant of the evaluated velocity and scalar.
 * ``distribution(boundary_id)``: arrays in facet order (``midpoints``, ``normals``, ``area``, ``pressure``,
   ``wall_shear_stress``, ``normal_velocity``, ``heat_flux``).
 * ``nusselt_number(boundary_id, delta_T, length)`` = ``-heat_flux length / (kappa delta_T area)``: positive when heat
