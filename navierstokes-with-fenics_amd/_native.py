@@ -620,14 +620,7 @@ class NsfemContext:
     def scalar_dynamic_constant(self, velocity_slot=U0, scalar_slot=T0, details=False):
         """C_theta of every averaging group for the pair of slots, [n_groups] (no stored state touched);
         ``details``: also the sums [n_groups, 2] = num, den and the vertex rows [n_p1, 3] = W, PR, RR"""
-        n = max(self.dynamic_info()["groups"], 1)     # (law 8 never set: let the driver say so)
-        cth = np.empty(n, dtype=np.float64)
-        sums = np.empty((n, 2), dtype=np.float64) if details else None
-        vert = np.empty((self.n_p1, 3), dtype=np.float64) if details else None
-        self._check(self._lib.nsfem_scalar_dynamic_constant(self._h, int(velocity_slot), int(scalar_slot), _dp(cth),
-                                                            _dp(sums) if details else None,
-                                                            _dp(vert) if details else None))
-        return (cth, sums, vert) if details else cth
+        return self._dynamic_constant(self._lib.nsfem_scalar_dynamic_constant, (velocity_slot, scalar_slot), details)
 
     def scalar_diffusivity_cells(self, velocity_slot=U0, scalar_slot=T0):
         """cell means of kappa_x = c_K Delta_K^2 gamma, the constant formed on the pair of slots, [n_cells]"""
@@ -686,15 +679,18 @@ class NsfemContext:
     def dynamic_constant(self, velocity_slot=U0, details=False):
         """C_s^2 of every averaging group for the velocity of the slot, [n_groups] (law 8; no stored state touched);
         ``details``: also the sums [n_groups, 2] = num, den and the vertex rows [n_p1, 3] = W, LM, MM"""
-        n = self.dynamic_info()["groups"]
-        if n == 0:                           # (law 8 never set: let the driver say so)
-            n = 1
-        cs2 = np.empty(n, dtype=np.float64)
+        return self._dynamic_constant(self._lib.nsfem_dynamic_constant, (velocity_slot, ), details)
+
+    def _dynamic_constant(self, call, slots, details):
+        """one run of the Germano-Lilly procedure through ``call`` on ``slots``: the constant of every group, with
+        ``details`` the sums and the vertex rows as well"""
+        n = max(self.dynamic_info()["groups"], 1)     # (law 8 never set: let the driver say so)
+        const = np.empty(n, dtype=np.float64)
         sums = np.empty((n, 2), dtype=np.float64) if details else None
         vert = np.empty((self.n_p1, 3), dtype=np.float64) if details else None
-        self._check(self._lib.nsfem_dynamic_constant(self._h, int(velocity_slot), _dp(cs2),
-                                                     _dp(sums) if details else None, _dp(vert) if details else None))
-        return (cs2, sums, vert) if details else cs2
+        self._check(call(self._h, *map(int, slots), _dp(const), _dp(sums) if details else None,
+                         _dp(vert) if details else None))
+        return (const, sums, vert) if details else const
 
     def dynamic_info(self):
         """dict(groups, runs, launches, bytes): the averaging groups, the runs of the procedure, the launches of its

@@ -2596,17 +2596,29 @@ static void dynamic_upload_groups(nsfem_ctx* c, int n_groups, const int32_t* gro
   for (int v = 0; v < nv; ++v) gvert[(size_t)fill[group ? group[v] : 0]++] = v;
   D.goff.upload(goff, c->stream);
   D.gvert.upload(gvert, c->stream);
-  if (D.sums.n != (size_t)n_groups * 3) D.sums.alloc((size_t)n_groups * 3);
+  if (D.buf.sums.n != (size_t)n_groups * 3) D.buf.sums.alloc((size_t)n_groups * 3);
   D.n_groups = n_groups;
   D.global = group == nullptr;
   if (group) D.h_group.assign(group, group + nv);
   else D.h_group.clear();
 }
 
-// buffers and the vertex-to-cell CSR (from the P1 connectivity: vertex ids are P1 dof ids), once
+// mom, vert and the vertex field of one use of the procedure, once; sums follows the group count
+static void dynamic_alloc(nsfem_ctx* c, nsfem_ctx::DynamicBuffers& B, bool with_T) {
+  const MeshDev& m = c->mesh;
+  if (!B.allocated) {
+    B.mom.alloc((size_t)dynamic_moment_rows(m.dim, with_T) * m.n_cells);
+    B.vert.alloc((size_t)m.n_p1 * 3);
+    B.field.alloc((size_t)m.n_p1);
+    B.allocated = true;
+  }
+  if (B.sums.n != (size_t)c->dyn.n_groups * 3) B.sums.alloc((size_t)c->dyn.n_groups * 3);
+}
+
+// the buffers of law 8 and the vertex-to-cell CSR (from the P1 connectivity: vertex ids are P1 dof ids), once
 static void dynamic_ensure(nsfem_ctx* c) {
   nsfem_ctx::Dynamic& D = c->dyn;
-  if (D.allocated) return;
+  if (D.buf.allocated) return;
   const MeshDev& m = c->mesh;
   const int nl1 = m.dim + 1, nv = m.n_p1, nc = m.n_cells;
   NSFEM_REQUIRE(c->h_p1map.size() == (size_t)nl1 * nc, "dynamic Smagorinsky: no host copy of the P1 connectivity");
@@ -2621,65 +2633,28 @@ static void dynamic_ensure(nsfem_ctx* c) {
     for (int i = 0; i < nl1; ++i) vcell[(size_t)fill[c->h_p1map[(size_t)k * nl1 + i]]++] = k;
   D.vptr.upload(vptr, c->stream);
   D.vcell.upload(vcell, c->stream);
-  const int nm = m.dim + 3 * (m.dim * (m.dim + 1) / 2) + 2;
-  D.mom.alloc((size_t)nm * nc);
-  D.vert.alloc((size_t)nv * 3);
-  D.cs2v.alloc((size_t)nv);
-  D.allocated = true;
+  dynamic_alloc(c, D.buf, false);
 }
 
-// law 8: the three launches on the level u; returns the vertex field the element / facet launch on the SAME u reads.
-// Every other law: null, nothing launched
-static const double* dynamic_run(nsfem_ctx* c, const double* u) {
-  if (c->visc.law != 8) return nullptr;
-  nsfem_ctx::Dynamic& D = c->dyn;
-  NSFEM_REQUIRE(D.allocated, "dynamic Smagorinsky: buffers not allocated");
-  DynamicDev d;
-  d.n_groups = D.n_groups;
-  d.vptr = D.vptr.p;
-  d.vcell = D.vcell.p;
-  d.goff = D.goff.p;
-  d.gvert = D.gvert.p;
-  d.mom = D.mom.p;
-  d.vert = D.vert.p;
-  d.sums = D.sums.p;
-  d.cs2v = D.cs2v.p;
-  launch_dynamic_constant(c->stream, c->mesh, u, c->visc.p[0], c->visc.p[1], d);
-  ++D.runs;
-  D.launches += 3;
-  return D.cs2v.p;
-}
-
-// Dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic): the three launches on the level pair (u, T); returns the
-// vertex field C_theta that the element / facet launch on the SAME pair reads.  The buffers are allocated by the first
-// run (a context that never switches the term on allocates nothing); the vertex-to-cell CSR and the group list are
-// those of law 8, which the callers have required
-static const double* scalar_dynamic_run(nsfem_ctx* c, const double* u, const double* T) {
-  nsfem_ctx::Dynamic& D = c->dyn;
-  nsfem_ctx::Scalar::DynamicFlux& F = c->sc.dynflux;
-  NSFEM_REQUIRE(c->visc.law == 8 && D.allocated, "dynamic subgrid heat flux: law 8 is not set (nsfem_set_viscosity_law)");
-  const MeshDev& m = c->mesh;
-  if (!F.allocated) {
-    F.mom.alloc((size_t)scalar_dynamic_moments(m.dim) * m.n_cells);
-    F.vert.alloc((size_t)m.n_p1 * 3);
-    F.cthv.alloc((size_t)m.n_p1);
-    F.allocated = true;
-  }
-  if (F.sums.n != (size_t)D.n_groups * 3) F.sums.alloc((size_t)D.n_groups * 3);
-  DynamicDev d;
-  d.n_groups = D.n_groups;
-  d.vptr = D.vptr.p;
-  d.vcell = D.vcell.p;
-  d.goff = D.goff.p;
-  d.gvert = D.gvert.p;
-  d.mom = F.mom.p;
-  d.vert = F.vert.p;
-  d.sums = F.sums.p;
-  d.cs2v = F.cthv.p;
-  launch_scalar_dynamic_constant(c->stream, m, u, T, c->visc.p[0], F.ctheta_max, d);
-  ++F.runs;
-  F.launches += 3;
-  return F.cthv.p;
+// The three launches of the Germano-Lilly procedure; returns the vertex field that the element / facet launch on the
+// SAME level reads.
+//   T null   law 8: C_s^2 on the level u.  Every other law: null, nothing launched
+//   T given  the dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic): C_theta on the level pair (u, T).  Its
+//            buffers are allocated by the first run (a context that never switches the term on allocates nothing);
+//            the vertex-to-cell CSR and the group list are those of law 8
+static const double* dynamic_run(nsfem_ctx* c, const double* u, const double* T = nullptr) {
+  if (!T && c->visc.law != 8) return nullptr;
+  const nsfem_ctx::Dynamic& D = c->dyn;
+  NSFEM_REQUIRE(c->visc.law == 8 && D.buf.allocated,
+                T ? "dynamic subgrid heat flux: law 8 is not set (nsfem_set_viscosity_law)"
+                  : "dynamic Smagorinsky: buffers not allocated");
+  nsfem_ctx::DynamicBuffers& B = T ? c->sc.dynflux.buf : c->dyn.buf;
+  dynamic_alloc(c, B, T != nullptr);
+  const DynamicDev d{D.n_groups, D.vptr.p, D.vcell.p, D.goff.p, D.gvert.p, B.mom.p, B.vert.p, B.sums.p, B.field.p};
+  launch_dynamic_constant(c->stream, c->mesh, u, T, c->visc.p[0], T ? c->sc.dynflux.ctheta_max : c->visc.p[1], d);
+  ++B.runs;
+  B.launches += 3;
+  return B.field.p;
 }
 
 // The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u).  The convective part
@@ -2915,7 +2890,7 @@ extern "C" int nsfem_imex_rotation_info(nsfem_ctx* ctx, int64_t out[4]) {
 extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double params[4]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
-  NSFEM_REQUIRE((law >= 0 && law <= 2) || law == 4 || law == 5 || law == 8,
+  NSFEM_REQUIRE(is_viscosity_law(law),
                 "variable viscosity: unknown law (0 none, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman, 8 dynamic Smagorinsky)");
   NSFEM_REQUIRE(law == 0 || !ctx->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
@@ -3027,6 +3002,31 @@ extern "C" int nsfem_set_dynamic_groups(nsfem_ctx* ctx, int n_groups, const int3
   API_END(ctx)
 }
 
+// what a run has left, to the host: the constant of every group, sums [n_groups][2] = num, den (may be null) and the
+// vertex rows [n_p1][3] (may be null)
+static void dynamic_read_back(nsfem_ctx* c, nsfem_ctx::DynamicBuffers& B, double* groups, double* sums,
+                              double* vertices) {
+  hipStream_t s = c->stream;
+  const int ng = c->dyn.n_groups;
+  B.h_sums.resize((size_t)ng * 3);
+  NSFEM_HIP(hipMemcpyAsync(B.h_sums.data(), B.sums.p, sizeof(double) * B.h_sums.size(), hipMemcpyDeviceToHost, s));
+  if (vertices)
+    NSFEM_HIP(hipMemcpyAsync(vertices, B.vert.p, sizeof(double) * (size_t)c->mesh.n_p1 * 3, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  for (int g = 0; g < ng; ++g) {
+    groups[g] = B.h_sums[(size_t)g * 3 + 2];
+    if (sums) {
+      sums[(size_t)g * 2] = B.h_sums[(size_t)g * 3];
+      sums[(size_t)g * 2 + 1] = B.h_sums[(size_t)g * 3 + 1];
+    }
+  }
+}
+
+// (bytes of the buffers of one use, for the info calls)
+static int64_t dynamic_bytes(const nsfem_ctx::DynamicBuffers& B) {
+  return (int64_t)(sizeof(double) * (B.mom.n + B.vert.n + B.sums.n + B.field.n));
+}
+
 extern "C" int nsfem_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, double* cs2_groups, double* sums,
                                       double* vertices) {
   API_BEGIN
@@ -3034,21 +3034,8 @@ extern "C" int nsfem_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, double*
   NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(ctx->visc.law == 8, "dynamic Smagorinsky: law 8 is not set (nsfem_set_viscosity_law)");
   require_velocity_slot(velocity_slot);
-  nsfem_ctx::Dynamic& D = ctx->dyn;
-  hipStream_t s = ctx->stream;
   dynamic_run(ctx, ctx->state[velocity_slot].p);
-  D.h_sums.resize((size_t)D.n_groups * 3);
-  NSFEM_HIP(hipMemcpyAsync(D.h_sums.data(), D.sums.p, sizeof(double) * D.h_sums.size(), hipMemcpyDeviceToHost, s));
-  if (vertices)
-    NSFEM_HIP(hipMemcpyAsync(vertices, D.vert.p, sizeof(double) * (size_t)ctx->mesh.n_p1 * 3, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
-  for (int g = 0; g < D.n_groups; ++g) {
-    cs2_groups[g] = D.h_sums[(size_t)g * 3 + 2];
-    if (sums) {
-      sums[(size_t)g * 2] = D.h_sums[(size_t)g * 3];
-      sums[(size_t)g * 2 + 1] = D.h_sums[(size_t)g * 3 + 1];
-    }
-  }
+  dynamic_read_back(ctx, ctx->dyn.buf, cs2_groups, sums, vertices);
   API_END(ctx)
 }
 
@@ -3056,11 +3043,10 @@ extern "C" int nsfem_dynamic_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out, "null argument");
   const nsfem_ctx::Dynamic& D = ctx->dyn;
-  out[0] = D.allocated ? D.n_groups : 0;
-  out[1] = D.runs;
-  out[2] = D.launches;
-  out[3] = (int64_t)(sizeof(int32_t) * (D.vptr.n + D.vcell.n + D.goff.n + D.gvert.n) +
-                     sizeof(double) * (D.mom.n + D.vert.n + D.sums.n + D.cs2v.n));
+  out[0] = D.buf.allocated ? D.n_groups : 0;
+  out[1] = D.buf.runs;
+  out[2] = D.buf.launches;
+  out[3] = (int64_t)(sizeof(int32_t) * (D.vptr.n + D.vcell.n + D.goff.n + D.gvert.n)) + dynamic_bytes(D.buf);
   API_END(ctx)
 }
 
@@ -3269,7 +3255,7 @@ static void scalar_explicit_launch(nsfem_ctx* c, const double* u, const double* 
   const ScalarBodies hb{pose ? *pose : c->bodies.cur, c->bodies.thermal};
   ScalarSgsArgs sgs = sgs_in;
   // (dynamic diffusivity: C_theta of THIS level pair, three launches before the element launch)
-  if (sgs.law == 8) sgs.cthv = scalar_dynamic_run(c, u, T);
+  if (sgs.law == 8) sgs.cthv = dynamic_run(c, u, T);
   launch_scalar_convection(c->stream, c->mesh, u, T, weight, form, pose ? &hb : nullptr, out, sgs);
   if (pose) ++c->bodies.fused_launches;
   if (in_step) ++c->sc.conv_launches;
@@ -3362,7 +3348,7 @@ extern "C" int nsfem_set_scalar_sgs(nsfem_ctx* ctx, double prandtl_t) {
 }
 
 // Dynamic subgrid heat flux: kappa_x = c_K Delta_K^2 gamma with C_theta from the Germano identity of the scalar flux
-// (scalar_dynamic_run), no Pr_t.  The stored scalar vector belongs to the switch and the clip it was formed with
+// (dynamic_run on the pair), no Pr_t.  The stored scalar vector belongs to the switch and the clip it was formed with
 extern "C" int nsfem_set_scalar_sgs_dynamic(nsfem_ctx* ctx, int enable, double ctheta_max) {
   API_BEGIN
   NSFEM_REQUIRE(ctx, "null context");
@@ -3402,7 +3388,7 @@ static ScalarSgsArgs scalar_sgs_args(const nsfem_ctx* c) {
 
 static void scalar_sgs_require_law(const nsfem_ctx* c) {
   const int law = c->visc.law;
-  NSFEM_REQUIRE(c->sc.prandtl_t == 0.0 || law == 1 || law == 4 || law == 5,
+  NSFEM_REQUIRE(c->sc.prandtl_t == 0.0 || is_subgrid_law(law),
                 "subgrid heat flux: Pr_t is set but the viscosity law is not 1 (Smagorinsky), 4 (WALE) or 5 (Vreman) "
                 "(nsfem_set_viscosity_law)");
   NSFEM_REQUIRE(!c->sc.dynflux.on || law == 8,
@@ -3592,22 +3578,8 @@ extern "C" int nsfem_scalar_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, 
   API_BEGIN
   NSFEM_REQUIRE(ctx && ctheta_groups, "null argument");
   scalar_dynamic_require(ctx, velocity_slot, scalar_slot);
-  nsfem_ctx::Scalar::DynamicFlux& F = ctx->sc.dynflux;
-  hipStream_t s = ctx->stream;
-  scalar_dynamic_run(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p);
-  const int ng = ctx->dyn.n_groups;
-  F.h_sums.resize((size_t)ng * 3);
-  NSFEM_HIP(hipMemcpyAsync(F.h_sums.data(), F.sums.p, sizeof(double) * F.h_sums.size(), hipMemcpyDeviceToHost, s));
-  if (vertices)
-    NSFEM_HIP(hipMemcpyAsync(vertices, F.vert.p, sizeof(double) * (size_t)ctx->mesh.n_p1 * 3, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
-  for (int g = 0; g < ng; ++g) {
-    ctheta_groups[g] = F.h_sums[(size_t)g * 3 + 2];
-    if (sums) {
-      sums[(size_t)g * 2] = F.h_sums[(size_t)g * 3];
-      sums[(size_t)g * 2 + 1] = F.h_sums[(size_t)g * 3 + 1];
-    }
-  }
+  dynamic_run(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p);
+  dynamic_read_back(ctx, ctx->sc.dynflux.buf, ctheta_groups, sums, vertices);
   API_END(ctx)
 }
 
@@ -3619,7 +3591,7 @@ extern "C" int nsfem_scalar_diffusivity_cells(nsfem_ctx* ctx, int velocity_slot,
   const double* u = ctx->state[velocity_slot].p;
   // (the law-8 MEAN instantiation of the viscosity kernel with C_theta in the place of C_s^2; the cell means land in
   // the element buffer, which every user fills before it reads)
-  const double* cthv = scalar_dynamic_run(ctx, u, ctx->state[scalar_slot].p);
+  const double* cthv = dynamic_run(ctx, u, ctx->state[scalar_slot].p);
   launch_viscosity_cells(s, ctx->mesh, u, 1.0, 8, ctx->visc.p, true, cthv);
   NSFEM_HIP(hipMemcpyAsync(out_host, ctx->mesh.rbuf.p, sizeof(double) * ctx->mesh.n_cells, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
@@ -3631,9 +3603,9 @@ extern "C" int nsfem_scalar_dynamic_info(nsfem_ctx* ctx, int64_t out[4]) {
   NSFEM_REQUIRE(ctx && out, "null argument");
   const nsfem_ctx::Scalar::DynamicFlux& F = ctx->sc.dynflux;
   out[0] = F.on ? 1 : 0;
-  out[1] = F.runs;
-  out[2] = F.launches;
-  out[3] = (int64_t)(sizeof(double) * (F.mom.n + F.vert.n + F.sums.n + F.cthv.n));
+  out[1] = F.buf.runs;
+  out[2] = F.buf.launches;
+  out[3] = dynamic_bytes(F.buf);
   API_END(ctx)
 }
 
@@ -4805,7 +4777,7 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   for (int k = 0; k < 3; ++k) wp.law_p[k] = ctx->visc.p[k];
   // subgrid heat flux: the conductive row carries kappa + nu_x / Pr_t where the traction carries nu_x (the subgrid
   // laws 1, 4 and 5 only)
-  const bool subgrid = wp.law == 1 || wp.law == 4 || wp.law == 5;
+  const bool subgrid = is_subgrid_law(wp.law);
   wp.inv_prt = subgrid && scalar_slot != -1 && ctx->sc.prandtl_t > 0.0 ? 1.0 / ctx->sc.prandtl_t : 0.0;
   hipStream_t s = ctx->stream;
   // (law 8: nu_x of a facet's cell takes the constant of the velocity level the rows are formed on)
@@ -4813,7 +4785,7 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   // (... and, with the dynamic subgrid heat flux on, the conductive row carries kappa + c_K Delta_K^2 gamma with C_theta
   // of the call's level pair)
   if (wp.law == 8 && scalar_slot != -1 && ctx->sc.dynflux.on)
-    wp.cthv = scalar_dynamic_run(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p);
+    wp.cthv = dynamic_run(ctx, ctx->state[velocity_slot].p, ctx->state[scalar_slot].p);
   launch_wall_facets(s, m, W.n_facets, W.fcell.p, W.flocal.p, ctx->state[velocity_slot].p, ctx->state[pressure_slot].p,
                      scalar_slot != -1 ? ctx->state[scalar_slot].p : nullptr, wp, W.rows.p);
   launch_wall_reduce(s, m.dim, W.n_groups, W.goff.p, W.rows.p, W.sums.p);

@@ -1075,36 +1075,104 @@ __global__ __launch_bounds__(256) void k_visc_gather(int64_t n_entries, int dim,
 
 void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, int law,
                             const double p[4], bool mean, const double* cs2v) {
-  NSFEM_REQUIRE(law == 1 || law == 2 || law == 4 || law == 5 || law == 8, "variable viscosity: no law set");
+  NSFEM_REQUIRE(law != 0 && is_viscosity_law(law), "variable viscosity: no law set");
   NSFEM_REQUIRE((law == 8) == (cs2v != nullptr), "variable viscosity: the vertex constants go with law 8 and only with it");
   if (m.dim == 3) return viscosity_cells_3d(s, m, u, weight, law, p, mean, cs2v);
-  const dim3 grid(grid_for(m.n_cells)), block(kBlock);
-#define NSFEM_VV(L, M) \
-  hipLaunchKernelGGL((k_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], p[2], \
-                     m.ndst.p, m.rbuf.p, m.p1.p, cs2v)
-  if (law == 1) { if (mean) NSFEM_VV(1, true); else NSFEM_VV(1, false); }
-  else if (law == 2) { if (mean) NSFEM_VV(2, true); else NSFEM_VV(2, false); }
-  else if (law == 4) { if (mean) NSFEM_VV(4, true); else NSFEM_VV(4, false); }
-  else if (law == 5) { if (mean) NSFEM_VV(5, true); else NSFEM_VV(5, false); }
-  else { if (mean) NSFEM_VV(8, true); else NSFEM_VV(8, false); }
-#undef NSFEM_VV
+  with_variable_law(law, mean, [&](auto lc, auto mc) {
+    hipLaunchKernelGGL((k_visc_var_cell<decltype(lc)::value, decltype(mc)::value != 0>), dim3(grid_for(m.n_cells)),
+                       dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], p[2], m.ndst.p, m.rbuf.p,
+                       m.p1.p, cs2v);
+  });
   NSFEM_HIP(hipGetLastError());
 }
 
-// ---------------------------------------------------------------- dynamic Smagorinsky (law 8): the Germano-Lilly constant
-// Three launches on a velocity level u (launch_dynamic_constant), plain stores, no atomics, the same state gives the
-// same bytes:
-//   k_dyn_moments<DIM>  one thread per CELL: m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q by the degree-5 rule for
-//                       f = u_a | u_a u_b | S_ab | gamma S_ab (a <= b), the last scaled by Delta_K^2 at the store, then
-//                       |K| and |K| Delta_K^2: NM = DIM + 3 NS + 2 doubles per cell (NS = DIM (DIM + 1) / 2), SoA
-//                       [NM][n_cells].  G_ab = d_b u_a is formed from the differences u_k - u_0 (the basis gradients
-//                       sum to zero): a constant field has G = 0 exactly, not a rounding residue.
-//   k_dyn_vertex<DIM>   one thread per VERTEX: the patch sums of the moments through the vertex-to-cell CSR in ascending
-//                       cell order, the test-filtered fields, the Germano identity; writes W_v, LM_v, MM_v ([n_p1][3])
-//   k_dyn_reduce        one workgroup per averaging GROUP over the group-sorted vertex list (the scheme of
-//                       k_wall_reduce): num_g, den_g, cs2_g ([n_groups][3]) and cs2 at the vertices of the group
-// Register layout of the moment kernel as k_visc_var_cell: u at the cell nodes in registers, the physical gradients of
-// a quadrature point formed once.
+// ---------------------------------------------------------------- the Germano-Lilly procedure: C_s^2 (law 8) and C_theta
+// Three launches on a velocity level u, or on a level pair (u, T) for the dynamic subgrid heat flux kappa_x = c_K
+// Delta_K^2 gamma (nsfem_set_scalar_sgs_dynamic) -- launch_dynamic_constant; plain stores, no atomics, the same state
+// gives the same bytes:
+//   k_dyn_moments<DIM>         one thread per CELL: m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q by the degree-5 rule for
+//   k_dyn_scalar_moments<DIM>  u:       f = u_a | u_a u_b | S_ab | gamma S_ab (a <= b; NS = DIM (DIM + 1) / 2 pairs)
+//                              (u, T):  f = T | T u_a | u_a | d_a T | gamma d_a T | S_ab
+//                              the gamma rows scaled by Delta_K^2 at the store, then |K| and |K| Delta_K^2: SoA
+//                              [dynamic_moment_rows][n_cells].  G_ab = d_b u_a and grad T are formed from the
+//                              differences u_k - u_0, T_k - T_0 (the basis gradients sum to zero): a constant field
+//                              has G = 0 exactly, not a rounding residue.  The set on (u, T) repeats u_a, S_ab and
+//                              the volumes of the set on u on purpose: the buffer of law 8 may hold another level when
+//                              the scalar step runs.
+//   k_dyn_vertex<DIM>          one thread per VERTEX: the patch sums of the moments through the vertex-to-cell CSR in
+//   k_dyn_scalar_vertex<DIM>   ascending cell order (patch_mean), the test-filtered fields, the Germano identity;
+//                              writes W_v, LM_v, MM_v, on (u, T) W_v, PR_v = P . R, RR_v = R . R with P_a = hat(T u_a)
+//                              - hat T hat u_a, R_a = hat(Delta^2 gamma d_a T) - alpha^2 Delta_v^2 hat gamma hat(d_a T)
+//                              ([n_p1][3])
+//   k_dyn_reduce               one workgroup per averaging GROUP over the group-sorted vertex list (the scheme of
+//                              k_wall_reduce): num_g, den_g, the clipped constant ([n_groups][3]) and the constant at
+//                              the vertices of the group
+// Register layout of the moment kernels as k_visc_var_cell: the fields at the cell nodes in registers, the physical
+// gradients of a quadrature point formed once.
+//
+// DynFront: what both moment kernels of triangles need of a cell and of a quadrature point -- the nodal values, u_q
+// (and T_q), 2 S and gamma (and grad T), the weight sum; WITH_T = false carries nothing of T.  (Tetrahedra: DynFront3,
+// assembly3d.hip -- another geometry type and another grouping of the sum under gamma.)
+template <bool WITH_T>
+struct DynFront {
+  CellGeo g;
+  double vol, delta2;                        // |K| and Delta_K^2 = |K|^(2 / dim)
+  double ux[6], uy[6], t[WITH_T ? 6 : 1];
+  double wsum = 0.0;
+  double w, uqx, uqy, tq, dtx, dty, S[3], gamma;          // of the point: w_q, u, T, grad T, S (00 01 11), gamma
+  __device__ __forceinline__ DynFront(const double* __restrict__ vx, int nc, int c, const int32_t* __restrict__ p2,
+                                      const double* __restrict__ u, const double* __restrict__ T)
+      : g(load_geo(vx, nc, c)) {
+    vol = delta2 = 0.5 * g.adet;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const int node = p2[(size_t)k * nc + c];
+      const double2 a = reinterpret_cast<const double2*>(u)[node];
+      ux[k] = a.x;
+      uy[k] = a.y;
+      if constexpr (WITH_T) t[k] = T[node];
+    }
+  }
+  __device__ __forceinline__ void point(int q) {
+    uqx = uqy = tq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      uqx += c_q.phi2[q][k] * ux[k];
+      uqy += c_q.phi2[q][k] * uy[k];
+      if constexpr (WITH_T) tq += c_q.phi2[q][k] * t[k];
+    }
+    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a
+    dtx = dty = 0.0;
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+      double gx, gy;
+      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx, gy);
+      const double dx = ux[k] - ux[0], dy = uy[k] - uy[0];
+      g00 += gx * dx;
+      g01 += gy * dx;
+      g10 += gx * dy;
+      g11 += gy * dy;
+      if constexpr (WITH_T) {
+        const double dt = t[k] - t[0];
+        dtx += gx * dt;
+        dty += gy * dt;
+      }
+    }
+    const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T = 2 S
+    // gamma^2 = (s00^2 + 2 s01^2 + s11^2) / 2.  Written once per kernel, the first sum was contracted differently in
+    // the two: the product s00^2 fused on u, the product 2 s01^2 fused on (u, T).  Each keeps its rounding, written out
+    const double s01s = s01 * s01;
+    const double in = WITH_T ? fma(2.0, s01s, s00 * s00) : fma(s00, s00, 2.0 * s01s);
+    gamma = sqrt(0.5 * fma(s11, s11, in));
+    S[0] = 0.5 * s00;
+    S[1] = 0.5 * s01;
+    S[2] = 0.5 * s11;
+    w = c_q.w[q];
+    wsum += w;
+  }
+  __device__ __forceinline__ double scale() const { return vol / wsum; }
+};
+
 template <int DIM>
 __global__ void k_dyn_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
                               const double* __restrict__ u, double* __restrict__ mom);     // <3>: assembly3d.hip
@@ -1115,53 +1183,22 @@ __global__ __launch_bounds__(256) void k_dyn_moments<2>(int nc, const double* __
                                                         const double* __restrict__ u, double* __restrict__ mom) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
-  const CellGeo g = load_geo(vx, nc, c);
-  const double vol = 0.5 * g.adet, delta2 = 0.5 * g.adet;      // |K| and Delta_K^2 = |K|^(2 / dim)
-  double ux[6], uy[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const int node = p2[(size_t)k * nc + c];
-    const double2 a = reinterpret_cast<const double2*>(u)[node];
-    ux[k] = a.x;
-    uy[k] = a.y;
-  }
+  DynFront<false> p(vx, nc, c, p2, u, nullptr);
   double mu[2] = {0.0, 0.0}, muu[3] = {0.0, 0.0, 0.0}, ms[3] = {0.0, 0.0, 0.0}, mg[3] = {0.0, 0.0, 0.0};
-  double wsum = 0.0;
   for (int q = 0; q < 7; ++q) {
-    double uqx = 0.0, uqy = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      uqx += c_q.phi2[q][k] * ux[k];
-      uqy += c_q.phi2[q][k] * uy[k];
-    }
-    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a
-#pragma unroll
-    for (int k = 1; k < 6; ++k) {
-      double gx, gy;
-      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx, gy);
-      const double dx = ux[k] - ux[0], dy = uy[k] - uy[0];
-      g00 += gx * dx;
-      g01 += gy * dx;
-      g10 += gx * dy;
-      g11 += gy * dy;
-    }
-    const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T = 2 S
-    const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
-    const double w = c_q.w[q];
-    wsum += w;
-    mu[0] += w * uqx;
-    mu[1] += w * uqy;
-    muu[0] += w * (uqx * uqx);
-    muu[1] += w * (uqx * uqy);
-    muu[2] += w * (uqy * uqy);
-    const double S[3] = {0.5 * s00, 0.5 * s01, 0.5 * s11};
+    p.point(q);
+    mu[0] += p.w * p.uqx;
+    mu[1] += p.w * p.uqy;
+    muu[0] += p.w * (p.uqx * p.uqx);
+    muu[1] += p.w * (p.uqx * p.uqy);
+    muu[2] += p.w * (p.uqy * p.uqy);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      ms[k] += w * S[k];
-      mg[k] += w * (gamma * S[k]);
+      ms[k] += p.w * p.S[k];
+      mg[k] += p.w * (p.gamma * p.S[k]);
     }
   }
-  const double f = vol / wsum;
+  const double f = p.scale();
   double* o = mom + c;
   o[0] = f * mu[0];
   o[(size_t)nc] = f * mu[1];
@@ -1169,10 +1206,48 @@ __global__ __launch_bounds__(256) void k_dyn_moments<2>(int nc, const double* __
   for (int k = 0; k < 3; ++k) {
     o[(size_t)(2 + k) * nc] = f * muu[k];
     o[(size_t)(5 + k) * nc] = f * ms[k];
-    o[(size_t)(8 + k) * nc] = (f * delta2) * mg[k];
+    o[(size_t)(8 + k) * nc] = (f * p.delta2) * mg[k];
   }
-  o[(size_t)11 * nc] = vol;
-  o[(size_t)12 * nc] = vol * delta2;
+  o[(size_t)11 * nc] = p.vol;
+  o[(size_t)12 * nc] = p.vol * p.delta2;
+}
+
+// The patch of a vertex v: a[i] = the sum of row i of mom over the cells of v in ascending order (the vertex-to-cell
+// CSR), then divided by W = a[NM - 2], the patch volume -- the test-filtered fields.  false: a vertex of no cell, no
+// patch (a is not divided; the caller writes no contribution).  No contraction, as in the kernels that call it (their
+// pragma does not reach in here).
+template <int NM>
+__device__ __forceinline__ bool patch_mean(int v, int nc, const int32_t* __restrict__ vptr,
+                                           const int32_t* __restrict__ vcell, const double* __restrict__ mom,
+                                           double (&a)[NM], double& W) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < NM; ++i) a[i] = 0.0;
+  const int e = vptr[v + 1];
+  for (int k = vptr[v]; k < e; ++k) {
+    const double* m = mom + vcell[k];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) a[i] += m[(size_t)i * nc];
+  }
+  W = a[NM - 2];
+  if (!(W > 0.0)) return false;
+#pragma unroll
+  for (int i = 0; i < NM; ++i) a[i] /= W;
+  return true;
+}
+
+// the filtered shear rate hat gamma = sqrt(2 hat S : hat S) from the NS rows s of hat S (pairs a <= b in row order:
+// the contraction counts the off-diagonal pairs twice)
+template <int DIM>
+__device__ __forceinline__ double patch_shear_rate(const double* s) {
+#pragma clang fp contract(off)
+  double ss = 0.0;
+  int i = 0;
+#pragma unroll
+  for (int r = 0; r < DIM; ++r)
+#pragma unroll
+    for (int c = r; c < DIM; ++c, ++i) ss += (r == c ? 1.0 : 2.0) * (s[i] * s[i]);
+  return sqrt(2.0 * ss);
 }
 
 // vert[v] = {W_v, LM_v, MM_v}.  Pairs (a <= b) in row order: 00 01 11 | 00 01 02 11 12 22; full contractions count the
@@ -1183,30 +1258,19 @@ __global__ __launch_bounds__(256) void k_dyn_vertex(int nv, int nc, const int32_
                                                     const double* __restrict__ mom, double alpha2,
                                                     double* __restrict__ vert) {
 #pragma clang fp contract(off)
-  constexpr int NS = DIM * (DIM + 1) / 2, NM = DIM + 3 * NS + 2;
+  constexpr int NS = DIM * (DIM + 1) / 2, NM = dynamic_moment_rows(DIM, false);
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= nv) return;
-  double a[NM];
-#pragma unroll
-  for (int i = 0; i < NM; ++i) a[i] = 0.0;
-  const int e = vptr[v + 1];
-  for (int k = vptr[v]; k < e; ++k) {
-    const double* m = mom + vcell[k];
-#pragma unroll
-    for (int i = 0; i < NM; ++i) a[i] += m[(size_t)i * nc];
-  }
+  double a[NM], W;
   double* o = vert + (size_t)v * 3;
-  const double W = a[NM - 2];
-  if (!(W > 0.0)) {                     // (a vertex of no cell: no patch, no contribution)
+  if (!patch_mean(v, nc, vptr, vcell, mom, a, W)) {      // (a vertex of no cell: no contribution)
     o[0] = o[1] = o[2] = 0.0;
     return;
   }
-#pragma unroll
-  for (int i = 0; i < NM; ++i) a[i] /= W;
   // the test-filtered fields: hat u = a[0 ..), hat(u u) = a[UU ..), hat S = a[SS ..), hat(Delta^2 gamma S) = a[GS ..)
   constexpr int UU = DIM, SS = DIM + NS, GS = DIM + 2 * NS;
   const double d2 = a[NM - 1];
-  double ss = 0.0, trl = 0.0;
+  double trl = 0.0;
   double L[NS];
   {
     int i = 0;
@@ -1214,13 +1278,11 @@ __global__ __launch_bounds__(256) void k_dyn_vertex(int nv, int nc, const int32_
     for (int r = 0; r < DIM; ++r)
 #pragma unroll
       for (int c = r; c < DIM; ++c, ++i) {
-        ss += (r == c ? 1.0 : 2.0) * (a[SS + i] * a[SS + i]);
         L[i] = a[UU + i] - a[r] * a[c];
         if (r == c) trl += L[i];
       }
   }
-  const double hgam = sqrt(2.0 * ss);
-  const double coef = (alpha2 * d2) * hgam, tr = trl / (double)DIM;
+  const double coef = (alpha2 * d2) * patch_shear_rate<DIM>(a + SS), tr = trl / (double)DIM;
   double lm = 0.0, mm = 0.0;
   {
     int i = 0;
@@ -1282,36 +1344,6 @@ __global__ __launch_bounds__(256) void k_dyn_reduce(const int32_t* __restrict__ 
   for (int i = begin + t; i < end; i += 256) cs2v[gvert[i]] = cs2;
 }
 
-void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, double alpha, double cs2_max,
-                             const DynamicDev& d) {
-  NSFEM_REQUIRE(d.n_groups >= 1 && d.mom && d.vert && d.sums && d.cs2v, "dynamic Smagorinsky: buffers not allocated");
-  if (m.dim == 3) {
-    dynamic_moments_3d(s, m, u, d.mom);
-    hipLaunchKernelGGL((k_dyn_vertex<3>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell,
-                       d.mom, alpha * alpha, d.vert);
-  } else {
-    hipLaunchKernelGGL((k_dyn_moments<2>), dim3(grid_for(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u,
-                       d.mom);
-    hipLaunchKernelGGL((k_dyn_vertex<2>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell,
-                       d.mom, alpha * alpha, d.vert);
-  }
-  hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, cs2_max, d.sums, d.cs2v);
-  NSFEM_HIP(hipGetLastError());
-}
-
-// ---------------------------------------------------------------- dynamic subgrid heat flux: the Germano-Lilly C_theta
-// kappa_x = c_K Delta_K^2 gamma (nsfem_set_scalar_sgs_dynamic).  Three launches on a level pair (u, T)
-// (launch_scalar_dynamic_constant), plain stores, no atomics, the same state gives the same bytes:
-//   k_dyn_scalar_moments<DIM>  one thread per CELL: m_K[f] = |K| sum_q w_q f(x_q) / sum_q w_q by the degree-5 rule for
-//                              f = T | T u_a | u_a | d_a T | gamma d_a T (scaled by Delta_K^2 at the store) | S_ab
-//                              (a <= b), then |K| and |K| Delta_K^2: NM = 1 + 4 DIM + NS + 2 doubles per cell (14 | 21),
-//                              SoA [NM][n_cells].  grad T and G from the differences T_k - T_0, u_k - u_0: a constant T
-//                              or u gives an exact 0.0.  The set repeats u_a, S_ab and the volumes of k_dyn_moments on
-//                              purpose: the buffer of law 8 may hold another level when the scalar step runs.
-//   k_dyn_scalar_vertex<DIM>   one thread per VERTEX: the patch sums in ascending cell order, the test-filtered fields,
-//                              P_a = hat(T u_a) - hat T hat u_a, R_a = hat(Delta^2 gamma d_a T) - alpha^2 Delta_v^2
-//                              hat gamma hat(d_a T); writes W_v, PR_v = P . R, RR_v = R . R ([n_p1][3])
-//   k_dyn_reduce               unchanged, with ctheta_max as its clip: num_g, den_g, ctheta_g and C_theta at the vertices
 template <int DIM>
 __global__ void k_dyn_scalar_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
                                      const double* __restrict__ u, const double* __restrict__ T,
@@ -1325,60 +1357,24 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_moments<2>(int nc, const dou
                                                                double* __restrict__ mom) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
-  const CellGeo g = load_geo(vx, nc, c);
-  const double vol = 0.5 * g.adet, delta2 = 0.5 * g.adet;      // |K| and Delta_K^2 = |K|^(2 / dim)
-  double ux[6], uy[6], t[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const int node = p2[(size_t)k * nc + c];
-    const double2 a = reinterpret_cast<const double2*>(u)[node];
-    ux[k] = a.x;
-    uy[k] = a.y;
-    t[k] = T[node];
-  }
+  DynFront<true> p(vx, nc, c, p2, u, T);
   double mt = 0.0, mtu[2] = {0.0, 0.0}, mu[2] = {0.0, 0.0}, md[2] = {0.0, 0.0}, mgd[2] = {0.0, 0.0};
   double ms[3] = {0.0, 0.0, 0.0};
-  double wsum = 0.0;
   for (int q = 0; q < 7; ++q) {
-    double uqx = 0.0, uqy = 0.0, tq = 0.0;
+    p.point(q);
+    mt += p.w * p.tq;
+    mtu[0] += p.w * (p.tq * p.uqx);
+    mtu[1] += p.w * (p.tq * p.uqy);
+    mu[0] += p.w * p.uqx;
+    mu[1] += p.w * p.uqy;
+    md[0] += p.w * p.dtx;
+    md[1] += p.w * p.dty;
+    mgd[0] += p.w * (p.gamma * p.dtx);
+    mgd[1] += p.w * (p.gamma * p.dty);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      uqx += c_q.phi2[q][k] * ux[k];
-      uqy += c_q.phi2[q][k] * uy[k];
-      tq += c_q.phi2[q][k] * t[k];
-    }
-    double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;     // g_ab = d_b u_a
-    double dtx = 0.0, dty = 0.0;                            // grad T
-#pragma unroll
-    for (int k = 1; k < 6; ++k) {
-      double gx, gy;
-      phys(g, c_q.dphi2[q][k][0], c_q.dphi2[q][k][1], gx, gy);
-      const double dx = ux[k] - ux[0], dy = uy[k] - uy[0], dt = t[k] - t[0];
-      g00 += gx * dx;
-      g01 += gy * dx;
-      g10 += gx * dy;
-      g11 += gy * dy;
-      dtx += gx * dt;
-      dty += gy * dt;
-    }
-    const double s00 = 2.0 * g00, s01 = g01 + g10, s11 = 2.0 * g11;      // g + g^T = 2 S
-    const double gamma = sqrt(0.5 * (s00 * s00 + 2.0 * (s01 * s01) + s11 * s11));
-    const double w = c_q.w[q];
-    wsum += w;
-    mt += w * tq;
-    mtu[0] += w * (tq * uqx);
-    mtu[1] += w * (tq * uqy);
-    mu[0] += w * uqx;
-    mu[1] += w * uqy;
-    md[0] += w * dtx;
-    md[1] += w * dty;
-    mgd[0] += w * (gamma * dtx);
-    mgd[1] += w * (gamma * dty);
-    ms[0] += w * (0.5 * s00);
-    ms[1] += w * (0.5 * s01);
-    ms[2] += w * (0.5 * s11);
+    for (int k = 0; k < 3; ++k) ms[k] += p.w * p.S[k];
   }
-  const double f = vol / wsum;
+  const double f = p.scale();
   double* o = mom + c;
   o[0] = f * mt;
 #pragma unroll
@@ -1386,12 +1382,12 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_moments<2>(int nc, const dou
     o[(size_t)(1 + a) * nc] = f * mtu[a];
     o[(size_t)(3 + a) * nc] = f * mu[a];
     o[(size_t)(5 + a) * nc] = f * md[a];
-    o[(size_t)(7 + a) * nc] = (f * delta2) * mgd[a];
+    o[(size_t)(7 + a) * nc] = (f * p.delta2) * mgd[a];
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) o[(size_t)(9 + k) * nc] = f * ms[k];
-  o[(size_t)12 * nc] = vol;
-  o[(size_t)13 * nc] = vol * delta2;
+  o[(size_t)12 * nc] = p.vol;
+  o[(size_t)13 * nc] = p.vol * p.delta2;
 }
 
 // vert[v] = {W_v, PR_v, RR_v}.  Rows of the moments: T | T u_a | u_a | d_a T | Delta^2 gamma d_a T | S_ab (a <= b in row
@@ -1402,38 +1398,18 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_vertex(int nv, int nc, const
                                                            const double* __restrict__ mom, double alpha2,
                                                            double* __restrict__ vert) {
 #pragma clang fp contract(off)
-  constexpr int NS = DIM * (DIM + 1) / 2, NM = 1 + 4 * DIM + NS + 2;
+  constexpr int NM = dynamic_moment_rows(DIM, true);
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= nv) return;
-  double a[NM];
-#pragma unroll
-  for (int i = 0; i < NM; ++i) a[i] = 0.0;
-  const int e = vptr[v + 1];
-  for (int k = vptr[v]; k < e; ++k) {
-    const double* m = mom + vcell[k];
-#pragma unroll
-    for (int i = 0; i < NM; ++i) a[i] += m[(size_t)i * nc];
-  }
+  double a[NM], W;
   double* o = vert + (size_t)v * 3;
-  const double W = a[NM - 2];
-  if (!(W > 0.0)) {                     // (a vertex of no cell: no patch, no contribution)
+  if (!patch_mean(v, nc, vptr, vcell, mom, a, W)) {      // (a vertex of no cell: no contribution)
     o[0] = o[1] = o[2] = 0.0;
     return;
   }
-#pragma unroll
-  for (int i = 0; i < NM; ++i) a[i] /= W;
   constexpr int TU = 1, UU = 1 + DIM, DT = 1 + 2 * DIM, GD = 1 + 3 * DIM, SS = 1 + 4 * DIM;
   const double d2 = a[NM - 1];
-  double ss = 0.0;
-  {
-    int i = 0;
-#pragma unroll
-    for (int r = 0; r < DIM; ++r)
-#pragma unroll
-      for (int c = r; c < DIM; ++c, ++i) ss += (r == c ? 1.0 : 2.0) * (a[SS + i] * a[SS + i]);
-  }
-  const double hgam = sqrt(2.0 * ss);
-  const double coef = (alpha2 * d2) * hgam;
+  const double coef = (alpha2 * d2) * patch_shear_rate<DIM>(a + SS);
   double pr = 0.0, rr = 0.0;
 #pragma unroll
   for (int r = 0; r < DIM; ++r) {
@@ -1447,22 +1423,21 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_vertex(int nv, int nc, const
   o[2] = rr;
 }
 
-void launch_scalar_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
-                                    double ctheta_max, const DynamicDev& d) {
+// T null: C_s^2 on u (k_dyn_moments, k_dyn_vertex); else C_theta on (u, T) (the k_dyn_scalar_ pair)
+void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
+                             double clip, const DynamicDev& d) {
   NSFEM_REQUIRE(d.n_groups >= 1 && d.vptr && d.vcell && d.goff && d.gvert && d.mom && d.vert && d.sums && d.cs2v,
-                "dynamic subgrid heat flux: buffers not allocated");
-  if (m.dim == 3) {
-    scalar_dynamic_moments_3d(s, m, u, T, d.mom);
-    hipLaunchKernelGGL((k_dyn_scalar_vertex<3>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr,
-                       d.vcell, d.mom, alpha * alpha, d.vert);
-  } else {
-    hipLaunchKernelGGL((k_dyn_scalar_moments<2>), dim3(grid_for(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p,
-                       m.p2.p, u, T, d.mom);
-    hipLaunchKernelGGL((k_dyn_scalar_vertex<2>), dim3(grid_for(m.n_p1)), dim3(kBlock), 0, s, m.n_p1, m.n_cells, d.vptr,
-                       d.vcell, d.mom, alpha * alpha, d.vert);
-  }
-  hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, ctheta_max, d.sums,
-                     d.cs2v);
+                T ? "dynamic subgrid heat flux: buffers not allocated" : "dynamic Smagorinsky: buffers not allocated");
+  const dim3 cells(grid_for(m.n_cells)), verts(grid_for(m.n_p1)), block(kBlock);
+  if (m.dim == 3) dynamic_moments_3d(s, m, u, T, d.mom);
+  else if (T) hipLaunchKernelGGL((k_dyn_scalar_moments<2>), cells, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, d.mom);
+  else hipLaunchKernelGGL((k_dyn_moments<2>), cells, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, d.mom);
+  with_int<3, 2>(m.dim, [&](auto dc) {
+    constexpr int DIM = decltype(dc)::value;
+    const auto vertex = T ? k_dyn_scalar_vertex<DIM> : k_dyn_vertex<DIM>;
+    hipLaunchKernelGGL(vertex, verts, block, 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell, d.mom, alpha * alpha, d.vert);
+  });
+  hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, clip, d.sums, d.cs2v);
   NSFEM_HIP(hipGetLastError());
 }
 

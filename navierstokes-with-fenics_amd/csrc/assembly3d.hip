@@ -749,23 +749,84 @@ __global__ __launch_bounds__(256) void k3_visc_var_cell(int nc, const double* __
 
 void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, int law, const double p[4],
                         bool mean, const double* cs2v) {
-  const dim3 grid(grid3(m.n_cells)), block(kBlock);
-#define NSFEM_VV3(L, M) \
-  hipLaunchKernelGGL((k3_visc_var_cell<L, M>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], \
-                     p[2], m.ndst.p, m.rbuf.p, m.p1.p, cs2v)
-  if (law == 1) { if (mean) NSFEM_VV3(1, true); else NSFEM_VV3(1, false); }
-  else if (law == 2) { if (mean) NSFEM_VV3(2, true); else NSFEM_VV3(2, false); }
-  else if (law == 4) { if (mean) NSFEM_VV3(4, true); else NSFEM_VV3(4, false); }
-  else if (law == 5) { if (mean) NSFEM_VV3(5, true); else NSFEM_VV3(5, false); }
-  else { if (mean) NSFEM_VV3(8, true); else NSFEM_VV3(8, false); }
-#undef NSFEM_VV3
+  with_variable_law(law, mean, [&](auto lc, auto mc) {
+    hipLaunchKernelGGL((k3_visc_var_cell<decltype(lc)::value, decltype(mc)::value != 0>), dim3(grid3(m.n_cells)),
+                       dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u, weight, p[0], p[1], p[2], m.ndst.p, m.rbuf.p,
+                       m.p1.p, cs2v);
+  });
   NSFEM_HIP(hipGetLastError());
 }
 
-// ---- dynamic Smagorinsky on tetrahedra: the cell moments of launch_dynamic_constant (assembly.hip, where the
-// definition, the vertex and the group kernels are), one thread per cell, 15-point rule.  NM = 23 rows, SoA
-// [23][n_cells]: u_a (3) | u_a u_b (6) | S_ab (6) | Delta_K^2 gamma S_ab (6) | |K| | |K| Delta_K^2, pairs a <= b in row
-// order.  G from the differences u_k - u_0, as in 2D.
+// ---- the Germano-Lilly procedure on tetrahedra: the cell moments of launch_dynamic_constant (assembly.hip, where the
+// definition, the vertex and the group kernels are), one thread per cell, 15-point rule.  Pairs a <= b in row order.
+//   k_dyn_moments<3>         23 rows: u_a (3) | u_a u_b (6) | S_ab (6) | Delta_K^2 gamma S_ab (6) | |K| | |K| Delta_K^2
+//   k_dyn_scalar_moments<3>  21 rows: T | T u_a (3) | u_a (3) | d_a T (3) | Delta_K^2 gamma d_a T (3) | S_ab (6) | |K| |
+//                            |K| Delta_K^2
+// DynFront3: what both need of a cell and of a quadrature point (the DynFront of triangles, assembly.hip).  G and
+// grad T from the differences u_k - u_0, T_k - T_0, as in 2D.
+template <bool WITH_T>
+struct DynFront3 {
+  CellGeo3 g;
+  double vol, delta2;
+  double un[10][3], t[WITH_T ? 10 : 1];
+  double wsum = 0.0;
+  double w, uq[3], tq, dt[3], S[6], gamma;          // of the point: w_q, u, T, grad T, S (00 01 02 11 12 22), gamma
+  __device__ __forceinline__ DynFront3(const double* __restrict__ vx, int nc, int c, const int32_t* __restrict__ p2,
+                                       const double* __restrict__ u, const double* __restrict__ T)
+      : g(load_geo3(vx, nc, c)) {
+    vol = g.adet / 6.0;
+    const double delta = cbrt(vol);
+    delta2 = delta * delta;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const size_t node = (size_t)p2[(size_t)k * nc + c];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
+      if constexpr (WITH_T) t[k] = T[node];
+    }
+  }
+  __device__ __forceinline__ void point(int q) {
+    uq[0] = uq[1] = uq[2] = tq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const double ph = c_q3.phi2[q][k];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) uq[a] += ph * un[k][a];
+      if constexpr (WITH_T) tq += ph * t[k];
+    }
+    double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};     // G[a][b] = d_b u_a
+    dt[0] = dt[1] = dt[2] = 0.0;
+#pragma unroll
+    for (int k = 1; k < 10; ++k) {
+      double gk[3];
+      phys3(g, c_q3.dphi2[q][k], gk);
+      if constexpr (WITH_T) {
+        const double dtk = t[k] - t[0];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) dt[b] += gk[b] * dtk;
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double d = un[k][a] - un[0][a];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) G[a][b] += gk[b] * d;
+      }
+    }
+    const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
+    const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
+    gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
+    S[0] = 0.5 * s00;
+    S[1] = 0.5 * s01;
+    S[2] = 0.5 * s02;
+    S[3] = 0.5 * s11;
+    S[4] = 0.5 * s12;
+    S[5] = 0.5 * s22;
+    w = c_q3.w[q];
+    wsum += w;
+  }
+  __device__ __forceinline__ double scale() const { return vol / wsum; }
+};
+
 template <int DIM>
 __global__ void k_dyn_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
                               const double* __restrict__ u, double* __restrict__ mom);     // <2>: assembly.hip
@@ -776,57 +837,25 @@ __global__ __launch_bounds__(256) void k_dyn_moments<3>(int nc, const double* __
                                                         const double* __restrict__ u, double* __restrict__ mom) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
-  const CellGeo3 g = load_geo3(vx, nc, c);
-  const double vol = g.adet / 6.0;
-  const double delta = cbrt(vol);
-  const double delta2 = delta * delta;
-  double un[10][3];
-#pragma unroll
-  for (int k = 0; k < 10; ++k) {
-    const size_t node = (size_t)p2[(size_t)k * nc + c];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
-  }
+  DynFront3<false> p(vx, nc, c, p2, u, nullptr);
   double mu[3] = {0.0, 0.0, 0.0};
   double muu[6], ms[6], mg[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) muu[k] = ms[k] = mg[k] = 0.0;
-  double wsum = 0.0;
   for (int q = 0; q < 15; ++q) {
-    double uq[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < 10; ++k)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) uq[a] += c_q3.phi2[q][k] * un[k][a];
-    double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};     // G[a][b] = d_b u_a
-#pragma unroll
-    for (int k = 1; k < 10; ++k) {
-      double gk[3];
-      phys3(g, c_q3.dphi2[q][k], gk);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double d = un[k][a] - un[0][a];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) G[a][b] += gk[b] * d;
-      }
-    }
-    const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
-    const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
-    const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
-    const double w = c_q3.w[q];
-    wsum += w;
-    const double S[6] = {0.5 * s00, 0.5 * s01, 0.5 * s02, 0.5 * s11, 0.5 * s12, 0.5 * s22};
+    p.point(q);
+    const double* uq = p.uq;
     const double uu[6] = {uq[0] * uq[0], uq[0] * uq[1], uq[0] * uq[2], uq[1] * uq[1], uq[1] * uq[2], uq[2] * uq[2]};
 #pragma unroll
-    for (int a = 0; a < 3; ++a) mu[a] += w * uq[a];
+    for (int a = 0; a < 3; ++a) mu[a] += p.w * uq[a];
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      muu[k] += w * uu[k];
-      ms[k] += w * S[k];
-      mg[k] += w * (gamma * S[k]);
+      muu[k] += p.w * uu[k];
+      ms[k] += p.w * p.S[k];
+      mg[k] += p.w * (p.gamma * p.S[k]);
     }
   }
-  const double f = vol / wsum;
+  const double f = p.scale();
   double* o = mom + c;
 #pragma unroll
   for (int a = 0; a < 3; ++a) o[(size_t)a * nc] = f * mu[a];
@@ -834,16 +863,12 @@ __global__ __launch_bounds__(256) void k_dyn_moments<3>(int nc, const double* __
   for (int k = 0; k < 6; ++k) {
     o[(size_t)(3 + k) * nc] = f * muu[k];
     o[(size_t)(9 + k) * nc] = f * ms[k];
-    o[(size_t)(15 + k) * nc] = (f * delta2) * mg[k];
+    o[(size_t)(15 + k) * nc] = (f * p.delta2) * mg[k];
   }
-  o[(size_t)21 * nc] = vol;
-  o[(size_t)22 * nc] = vol * delta2;
+  o[(size_t)21 * nc] = p.vol;
+  o[(size_t)22 * nc] = p.vol * p.delta2;
 }
 
-// ---- dynamic subgrid heat flux on tetrahedra: the cell moments of launch_scalar_dynamic_constant (assembly.hip, where
-// the definition, the vertex and the group kernels are), one thread per cell, 15-point rule.  NM = 21 rows, SoA
-// [21][n_cells]: T | T u_a (3) | u_a (3) | d_a T (3) | Delta_K^2 gamma d_a T (3) | S_ab (6, a <= b in row order) | |K| |
-// |K| Delta_K^2.  grad T and G from the differences T_k - T_0, u_k - u_0, as in 2D.
 template <int DIM>
 __global__ void k_dyn_scalar_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
                                      const double* __restrict__ u, const double* __restrict__ T,
@@ -857,65 +882,24 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_moments<3>(int nc, const dou
                                                                double* __restrict__ mom) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
-  const CellGeo3 g = load_geo3(vx, nc, c);
-  const double vol = g.adet / 6.0;
-  const double delta = cbrt(vol);
-  const double delta2 = delta * delta;
-  double un[10][3], t[10];
-#pragma unroll
-  for (int k = 0; k < 10; ++k) {
-    const size_t node = (size_t)p2[(size_t)k * nc + c];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) un[k][a] = u[node * 3 + a];
-    t[k] = T[node];
-  }
+  DynFront3<true> p(vx, nc, c, p2, u, T);
   double mt = 0.0;
   double mtu[3] = {0.0, 0.0, 0.0}, mu[3] = {0.0, 0.0, 0.0}, md[3] = {0.0, 0.0, 0.0}, mgd[3] = {0.0, 0.0, 0.0};
   double ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  double wsum = 0.0;
   for (int q = 0; q < 15; ++q) {
-    double uq[3] = {0.0, 0.0, 0.0}, tq = 0.0;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      const double ph = c_q3.phi2[q][k];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) uq[a] += ph * un[k][a];
-      tq += ph * t[k];
-    }
-    double G[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};     // G[a][b] = d_b u_a
-    double dt[3] = {0.0, 0.0, 0.0};                                            // grad T
-#pragma unroll
-    for (int k = 1; k < 10; ++k) {
-      double gk[3];
-      phys3(g, c_q3.dphi2[q][k], gk);
-      const double dtk = t[k] - t[0];
-#pragma unroll
-      for (int b = 0; b < 3; ++b) dt[b] += gk[b] * dtk;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double d = un[k][a] - un[0][a];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) G[a][b] += gk[b] * d;
-      }
-    }
-    const double s00 = 2.0 * G[0][0], s11 = 2.0 * G[1][1], s22 = 2.0 * G[2][2];
-    const double s01 = G[0][1] + G[1][0], s02 = G[0][2] + G[2][0], s12 = G[1][2] + G[2][1];
-    const double gamma = sqrt(0.5 * (s00 * s00 + s11 * s11 + s22 * s22) + (s01 * s01 + s02 * s02 + s12 * s12));
-    const double w = c_q3.w[q];
-    wsum += w;
-    const double S[6] = {0.5 * s00, 0.5 * s01, 0.5 * s02, 0.5 * s11, 0.5 * s12, 0.5 * s22};
-    mt += w * tq;
+    p.point(q);
+    mt += p.w * p.tq;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      mtu[a] += w * (tq * uq[a]);
-      mu[a] += w * uq[a];
-      md[a] += w * dt[a];
-      mgd[a] += w * (gamma * dt[a]);
+      mtu[a] += p.w * (p.tq * p.uq[a]);
+      mu[a] += p.w * p.uq[a];
+      md[a] += p.w * p.dt[a];
+      mgd[a] += p.w * (p.gamma * p.dt[a]);
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) ms[k] += w * S[k];
+    for (int k = 0; k < 6; ++k) ms[k] += p.w * p.S[k];
   }
-  const double f = vol / wsum;
+  const double f = p.scale();
   double* o = mom + c;
   o[0] = f * mt;
 #pragma unroll
@@ -923,22 +907,18 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_moments<3>(int nc, const dou
     o[(size_t)(1 + a) * nc] = f * mtu[a];
     o[(size_t)(4 + a) * nc] = f * mu[a];
     o[(size_t)(7 + a) * nc] = f * md[a];
-    o[(size_t)(10 + a) * nc] = (f * delta2) * mgd[a];
+    o[(size_t)(10 + a) * nc] = (f * p.delta2) * mgd[a];
   }
 #pragma unroll
   for (int k = 0; k < 6; ++k) o[(size_t)(13 + k) * nc] = f * ms[k];
-  o[(size_t)19 * nc] = vol;
-  o[(size_t)20 * nc] = vol * delta2;
+  o[(size_t)19 * nc] = p.vol;
+  o[(size_t)20 * nc] = p.vol * p.delta2;
 }
 
-void scalar_dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom) {
-  hipLaunchKernelGGL((k_dyn_scalar_moments<3>), dim3(grid3(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u,
-                     T, mom);
-  NSFEM_HIP(hipGetLastError());
-}
-
-void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, double* mom) {
-  hipLaunchKernelGGL((k_dyn_moments<3>), dim3(grid3(m.n_cells)), dim3(kBlock), 0, s, m.n_cells, m.vx.p, m.p2.p, u, mom);
+void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom) {
+  const dim3 grid(grid3(m.n_cells)), block(kBlock);
+  if (T) hipLaunchKernelGGL((k_dyn_scalar_moments<3>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, mom);
+  else hipLaunchKernelGGL((k_dyn_moments<3>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, mom);
   NSFEM_HIP(hipGetLastError());
 }
 

@@ -488,7 +488,7 @@ void launch_convection_residual(hipStream_t s, const MeshDev& m, const double* u
 // WALE, Vreman): the same launch adds D(u, T), the eddy diffusivity kappa_x = nu_x inv_prt of that law with its
 // constant c0 (C_s, C_w, c) under the gradients (the SGS = law instantiations), out = weight (C(u) T + D(u, T));
 // law 0: the term is off, the SGS = 0 kernels, which take nothing.  law 8 (nsfem_set_scalar_sgs_dynamic): kappa_x =
-// c_K Delta_K^2 gamma with c_K from cthv, the vertex field C_theta of launch_scalar_dynamic_constant on the same level
+// c_K Delta_K^2 gamma with c_K from cthv, the vertex field C_theta of launch_dynamic_constant on the same level
 // pair (u, T); no Pr_t, c0 and inv_prt are not read
 struct ScalarSgsArgs {
   double c0 = 0.0, inv_prt = 0.0;
@@ -518,27 +518,30 @@ void launch_viscosity_cells(hipStream_t s, const MeshDev& m, const double* u, do
                             const double p[4], bool mean, const double* cs2v = nullptr);
 void viscosity_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, int law, const double p[4],
                         bool mean, const double* cs2v);
-// dynamic Smagorinsky (law 8): the device side of the Germano-Lilly procedure on the velocity u -- k_dyn_moments,
-// k_dyn_vertex, k_dyn_reduce (assembly.hip / assembly3d.hip).  vptr, vcell: the vertex-to-cell CSR (ascending cells);
-// goff [n_groups + 1], gvert [n_p1]: the group-sorted vertex list; mom [NM][n_cells], vert [n_p1][3] = W, LM, MM;
-// sums [n_groups][3] = num, den, cs2; cs2v [n_p1]: the constant at the vertices, what launch_viscosity_cells and
-// launch_wall_facets read with law 8
+// The device side of the Germano-Lilly procedure (assembly.hip / assembly3d.hip): three launches, cell moments, vertex
+// patches, group sums with the clip.  Two uses:
+//   T null   dynamic Smagorinsky (law 8) on the velocity u -- k_dyn_moments, k_dyn_vertex, k_dyn_reduce; vert rows W,
+//            LM, MM; sums rows num, den, cs2; cs2v = C_s^2 at the vertices, what launch_viscosity_cells and
+//            launch_wall_facets read with law 8; clip = cs2_max
+//   T given  dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic), the Germano identity of the scalar flux on the
+//            level pair (u, T) -- k_dyn_scalar_moments, k_dyn_scalar_vertex, k_dyn_reduce; vert rows W, PR, RR; sums
+//            rows num, den, ctheta; cs2v = C_theta at the vertices; clip = ctheta_max
+// vptr, vcell: the vertex-to-cell CSR (ascending cells); goff [n_groups + 1], gvert [n_p1]: the group-sorted vertex
+// list -- shared by the two uses; mom [dynamic_moment_rows][n_cells], vert [n_p1][3], sums [n_groups][3], cs2v [n_p1]:
+// each use has its own
 struct DynamicDev {
   int n_groups = 0;
   const int32_t *vptr = nullptr, *vcell = nullptr, *goff = nullptr, *gvert = nullptr;
   double *mom = nullptr, *vert = nullptr, *sums = nullptr, *cs2v = nullptr;
 };
-void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, double alpha, double cs2_max,
-                             const DynamicDev& d);
-void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, double* mom);
-// dynamic subgrid heat flux (nsfem_set_scalar_sgs_dynamic): the Germano identity of the scalar flux on the level pair
-// (u, T) -- k_dyn_scalar_moments, k_dyn_scalar_vertex, then k_dyn_reduce with ctheta_max as its clip.  d as above
-// with buffers of its own: mom [NM][n_cells] (NM = 14 | 21), vert [n_p1][3] = W, PR, RR, sums [n_groups][3] = num, den,
-// ctheta, cs2v [n_p1] = C_theta at the vertices; the CSR and the group list are those of law 8
-void launch_scalar_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
-                                    double ctheta_max, const DynamicDev& d);
-void scalar_dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom);
-inline int scalar_dynamic_moments(int dim) { return dim == 2 ? 14 : 21; }
+void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
+                             double clip, const DynamicDev& d);
+void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom);
+// rows of mom: DIM + 3 NS + 2 on u (13 | 23), 1 + 4 DIM + NS + 2 on (u, T) (14 | 21), NS = DIM (DIM + 1) / 2
+constexpr int dynamic_moment_rows(int dim, bool with_T) {
+  const int ns = dim * (dim + 1) / 2;
+  return (with_T ? 1 + 4 * dim + ns : dim + 3 * ns) + 2;
+}
 // k_visc_gather: v = per-node sums of m.rbuf in ascending cell order; n1 += v, rhs -= b0 v (rhs may be null)
 void launch_viscosity_gather(hipStream_t s, const MeshDev& m, double b0, double* n1, double* rhs);
 // immersed bodies (nsfem_set_bodies): the table the penalisation kernels take as a kernel ARGUMENT (1.6 kB; entries
@@ -582,6 +585,28 @@ inline void with_int(int v, F&& f) {
   if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
   else if (v == V0) f(std::integral_constant<int, V0>{});
   else with_int<Vs...>(v, f);
+}
+// The viscosity laws (nsfem_set_viscosity_law), written ONCE: 0 constant, 1 Smagorinsky, 2 Carreau, 4 WALE, 5 Vreman,
+// 8 dynamic Smagorinsky.  with_int lets its last value stand for every other one, so a caller asks is_viscosity_law
+// first
+template <class F>
+inline void with_viscosity_law(int law, F&& f) {
+  with_int<0, 1, 2, 4, 5, 8>(law, f);
+}
+inline bool is_viscosity_law(int law) {
+  bool is = false;
+  with_viscosity_law(law, [&](auto lc) { is = law == decltype(lc)::value; });
+  return is;
+}
+// ... and the subgrid laws among them that take a fixed Pr_t as the partner of the subgrid heat flux
+inline bool is_subgrid_law(int law) { return law == 1 || law == 4 || law == 5; }
+// f(LAW, MEAN) for the element kernels of a variable viscosity, k_visc_var_cell / k3_visc_var_cell <LAW, MEAN>: every
+// law but 0, which has no such kernel
+template <class F>
+inline void with_variable_law(int law, bool mean, F&& f) {
+  with_viscosity_law(law, [&](auto lc) {
+    if constexpr (decltype(lc)::value != 0) with_int<1, 0>(mean, [&](auto mc) { f(lc, mc); });
+  });
 }
 // The ONE place that turns the run-time (form, PENAL, law) of a scalar element launch into template arguments:
 // f(FORM, PENAL, SGS) gets three integral constants, so each translation unit holds one launch of k_scalar_conv_cell
@@ -735,7 +760,7 @@ struct WallParams {
   double law_p[3] = {0.0, 0.0, 0.0};
   const double* cs2v = nullptr;              // law 8: the vertex field C_s^2 (launch_dynamic_constant), else null
   const double* cthv = nullptr;              // law 8 and != null: the heat row uses kappa + c_K Delta_K^2 gamma, c_K from
-                                             // this vertex field C_theta (launch_scalar_dynamic_constant)
+                                             // this vertex field C_theta (launch_dynamic_constant on (u, T))
   double inv_prt = 0.0;                      // law 1, 4, 5 and != 0: the heat row uses kappa + nu_x inv_prt (subgrid heat flux)
 };
 // ONE launch: rows[f][NW] of the nf facets (fcell, flocal: device lists); T may be null (no scalar: +0.0 entries)
@@ -1289,18 +1314,26 @@ struct nsfem_ctx {
     double p[4] = {0.0, 0.0, 0.0, 0.0};
     int64_t epoch = 0, launches = 0, recomputed = 0;
   } visc;
-  // dynamic Smagorinsky (law 8; p = {alpha, cs2_max}): the buffers of launch_dynamic_constant, allocated when law 8
-  // is first set and kept; the averaging groups (nsfem_set_dynamic_groups; global: one group of all vertices).  The
-  // constant is a function of the level it is evaluated on -- it is formed before every law-8 element launch and is
-  // no stored state; a change of the groups is a change of the law (visc.epoch)
+  // What one use of the Germano-Lilly procedure (launch_dynamic_constant) owns: the buffers of its three launches,
+  // `field` the constant at the vertices, the host copy of `sums` and the counters.  Two uses: dyn.buf (law 8, C_s^2 on
+  // u) and sc.dynflux.buf (C_theta on (u, T)); each has buffers of its own because each may hold another level
+  struct DynamicBuffers {
+    bool allocated = false;
+    nsfem::DevBuf<double> mom, vert, sums, field;
+    std::vector<double> h_sums;
+    int64_t runs = 0, launches = 0;
+  };
+  // dynamic Smagorinsky (law 8; p = {alpha, cs2_max}): what both uses of the procedure share -- the vertex-to-cell
+  // CSR and the averaging groups (nsfem_set_dynamic_groups; global: one group of all vertices) -- and the buffers of
+  // law 8, allocated when law 8 is first set and kept.  The constant is a function of the level it is evaluated on --
+  // it is formed before every law-8 element launch and is no stored state; a change of the groups is a change of the
+  // law (visc.epoch)
   struct Dynamic {
-    bool allocated = false, global = true;
+    bool global = true;
     int n_groups = 1;
     std::vector<int32_t> h_group;                   // [n_p1], what nsfem_set_dynamic_groups took (empty: global)
     nsfem::DevBuf<int32_t> vptr, vcell, goff, gvert;
-    nsfem::DevBuf<double> mom, vert, sums, cs2v;
-    std::vector<double> h_sums;
-    int64_t runs = 0, launches = 0;
+    DynamicBuffers buf;
   } dyn;
   // immersed bodies (nsfem_set_bodies): with bodies the stored vectors carry B(u) as well.  `cur` is the pose of t^n,
   // `prev` that of t^(n-1) (nsfem_move_bodies shifts cur to prev; without a move they are equal): a stored N(u2) was
@@ -1352,11 +1385,9 @@ struct nsfem_ctx {
     // the law's (visc.epoch).  The buffers are allocated by the first run and kept; the vertex-to-cell CSR and the
     // group list are those of `dyn`
     struct DynamicFlux {
-      bool on = false, allocated = false;
+      bool on = false;
       double ctheta_max = 0.0;
-      nsfem::DevBuf<double> mom, vert, sums, cthv;
-      std::vector<double> h_sums;
-      int64_t runs = 0, launches = 0;
+      DynamicBuffers buf;
     } dynflux;
     // Key of the stored vectors TCONV_1, TCONV_2: the form, bodies.thermal_epoch, bodies.epoch (compared only while a
     // body is thermal), sgs_epoch and visc.epoch (compared only while the subgrid term is on) they were formed with.

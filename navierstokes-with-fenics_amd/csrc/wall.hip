@@ -299,31 +299,20 @@ __global__ __launch_bounds__(256) void k_wall_reduce(const int32_t* __restrict__
   if (t < NW) out[(size_t)g * NW + t] = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
 }
 
-template <int DIM, int LAW>
-static void launch_wall_facets_t(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
-                                 const double* u, const double* p, const double* T, const WallParams& w, double* rows) {
-  const int grid = (nf + 255) / 256;
-  hipLaunchKernelGGL((k_wall_facets<DIM, LAW>), dim3(grid), dim3(256), 0, s, nf, m.n_cells, fcell, flocal, m.vx.p,
-                     m.p2.p, m.p1.p, u, p, T, w.nu, w.sym, w.kappa, w.origin[0], w.origin[1], w.origin[2], w.law_p[0],
-                     w.law_p[1], w.law_p[2], w.inv_prt, rows, w.cs2v, w.cthv);
-}
-
 void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* fcell, const int32_t* flocal,
                         const double* u, const double* p, const double* T, const WallParams& w, double* rows) {
   if (nf <= 0) return;
-  NSFEM_REQUIRE((w.law >= 0 && w.law <= 2) || w.law == 4 || w.law == 5 || w.law == 8,
-                "wall quantities: unknown viscosity law");
+  NSFEM_REQUIRE(is_viscosity_law(w.law), "wall quantities: unknown viscosity law");
   NSFEM_REQUIRE((w.law == 8) == (w.cs2v != nullptr), "wall quantities: the vertex constants go with law 8 and only with it");
   NSFEM_REQUIRE(w.law == 8 || w.cthv == nullptr, "wall quantities: the vertex field C_theta goes with law 8 only");
-  using Fn = void (*)(hipStream_t, const MeshDev&, int, const int32_t*, const int32_t*, const double*, const double*,
-                      const double*, const WallParams&, double*);
-  // (3, 6 and 7 are no laws: their columns are never taken)
-  static const Fn table[2][9] = {
-      {launch_wall_facets_t<2, 0>, launch_wall_facets_t<2, 1>, launch_wall_facets_t<2, 2>, nullptr,
-       launch_wall_facets_t<2, 4>, launch_wall_facets_t<2, 5>, nullptr, nullptr, launch_wall_facets_t<2, 8>},
-      {launch_wall_facets_t<3, 0>, launch_wall_facets_t<3, 1>, launch_wall_facets_t<3, 2>, nullptr,
-       launch_wall_facets_t<3, 4>, launch_wall_facets_t<3, 5>, nullptr, nullptr, launch_wall_facets_t<3, 8>}};
-  table[m.dim == 3][w.law](s, m, nf, fcell, flocal, u, p, T, w, rows);
+  with_int<3, 2>(m.dim, [&](auto dc) {
+    with_viscosity_law(w.law, [&](auto lc) {
+      hipLaunchKernelGGL((k_wall_facets<decltype(dc)::value, decltype(lc)::value>), dim3((nf + 255) / 256), dim3(256), 0,
+                         s, nf, m.n_cells, fcell, flocal, m.vx.p, m.p2.p, m.p1.p, u, p, T, w.nu, w.sym, w.kappa,
+                         w.origin[0], w.origin[1], w.origin[2], w.law_p[0], w.law_p[1], w.law_p[2], w.inv_prt, rows,
+                         w.cs2v, w.cthv);
+    });
+  });
   NSFEM_HIP(hipGetLastError());
 }
 
