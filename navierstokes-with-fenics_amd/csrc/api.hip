@@ -56,14 +56,55 @@ static void ensure_scalar_slot(nsfem_ctx* c, int slot) {
   c->state[slot].zero(c->stream);
 }
 
+// The classes of slots an entry point asks for -- the strict ones by name, the loose ones "any slot of this size" --
+// and the one check of them.  The message is `prefix` (the feature, "" for none) and the text of the class.
+enum class SlotClass {
+  VelocityLevel,   // U0, U1, U2, USTAR
+  PressureSlot,    // P, P_OLD, P2_OLD
+  ScalarLevel,     // T0, T1, T2
+  ScalarSlot,      // T0 .. T_SOURCE
+  VelocitySized,   // dim * n_p2 doubles
+  PressureSized,   // n_p1 doubles
+  ScalarSized      // n_p2 doubles
+};
+static void require_slot(int slot, SlotClass cls, const char* prefix = "") {      // the classes by name
+  bool ok = false;
+  const char* what = "";
+  switch (cls) {
+    case SlotClass::VelocityLevel:
+      ok = slot == NSFEM_U0 || slot == NSFEM_U1 || slot == NSFEM_U2 || slot == NSFEM_USTAR;
+      what = "velocity_slot is not a velocity slot";
+      break;
+    case SlotClass::PressureSlot:
+      ok = slot == NSFEM_P || slot == NSFEM_P_OLD || slot == NSFEM_P2_OLD;
+      what = "pressure_slot is not a pressure slot";
+      break;
+    case SlotClass::ScalarLevel:
+      ok = slot == NSFEM_T0 || slot == NSFEM_T1 || slot == NSFEM_T2;
+      what = "scalar_slot is not a level of the transported scalar";
+      break;
+    case SlotClass::ScalarSlot:
+      ok = slot >= NSFEM_T0 && slot <= NSFEM_T_SOURCE;
+      what = "scalar_slot is not a scalar slot";
+      break;
+    default: throw Error(NSFEM_ERR_ARG, "a slot class by size needs the context");
+  }
+  NSFEM_REQUIRE(ok, std::string(prefix) + what);
+}
+static void require_slot(const nsfem_ctx* c, int slot, SlotClass cls, const char* prefix = "") {   // ... and by size
+  int64_t n = 0;
+  const char* what = "";
+  switch (cls) {
+    case SlotClass::VelocitySized: n = nvel(c); what = "not a velocity slot"; break;
+    case SlotClass::PressureSized: n = npre(c); what = "not a pressure slot"; break;
+    case SlotClass::ScalarSized: n = (int64_t)c->mesh.n_p2; what = "not a scalar slot"; break;
+    default: return require_slot(slot, cls, prefix);
+  }
+  NSFEM_REQUIRE(slot >= 0 && slot < NSFEM_N_SLOTS && slot_size(c, slot) == n, std::string(prefix) + what);
+}
 // what the test hooks of the explicit terms check about their arguments
-static void require_velocity_slot(int slot) {
-  NSFEM_REQUIRE(slot == NSFEM_U0 || slot == NSFEM_U1 || slot == NSFEM_U2 || slot == NSFEM_USTAR,
-                "velocity_slot is not a velocity slot");
-}
-static void require_scalar_slot(int slot) {
-  NSFEM_REQUIRE(slot >= NSFEM_T0 && slot <= NSFEM_T_SOURCE, "scalar_slot is not a scalar slot");
-}
+static void require_velocity_slot(int slot) { require_slot(slot, SlotClass::VelocityLevel); }
+static void require_scalar_slot(int slot) { require_slot(slot, SlotClass::ScalarSlot); }
 static void require_scalar_form(int form) {
   NSFEM_REQUIRE(form == 0 || form == 1, "scalar transport: convective form must be 0 (standard) or 1 (skew-symmetric)");
 }
@@ -3150,6 +3191,25 @@ extern "C" int nsfem_move_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bo
   API_END(ctx)
 }
 
+// The work buffer of a two-launch reduction (a kernel that stores n_parts partials per number, then k_fold_partials):
+// the n_out * n_parts partials, the n_out results behind them.  (Re)allocated when the size asked for changes.
+struct PartialsWork {
+  double* parts;
+  double* res;
+  size_t n_out;
+  PartialsWork(DevBuf<double>& buf, size_t n_out_, int n_parts) : n_out(n_out_) {
+    const size_t n_work = n_out * (size_t)(n_parts + 1);
+    if (buf.n != n_work) buf.alloc(n_work);
+    parts = buf.p;
+    res = parts + n_out * (size_t)n_parts;
+  }
+  // the results to the host: one copy, one synchronise
+  void read_back(hipStream_t s, double* out) const {
+    NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+    NSFEM_HIP(hipStreamSynchronize(s));
+  }
+};
+
 static void bodies_require(nsfem_ctx* ctx, int velocity_slot) {
   NSFEM_REQUIRE(!ctx->comm, "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(ctx->bodies.cur.n != 0, "immersed bodies: no body set (nsfem_set_bodies)");
@@ -3190,14 +3250,9 @@ extern "C" int nsfem_body_forces(nsfem_ctx* ctx, int velocity_slot, double* out)
   NSFEM_REQUIRE(ctx && out, "null argument");
   bodies_require(ctx, velocity_slot);
   hipStream_t s = ctx->stream;
-  const size_t n_out = (size_t)ctx->bodies.cur.n * body_numbers(ctx->mesh.dim);
-  const size_t n_work = n_out * (kBodyParts + 1);
-  if (ctx->bodies.work.n != n_work) ctx->bodies.work.alloc(n_work);
-  double* parts = ctx->bodies.work.p;
-  double* res = parts + n_out * kBodyParts;
-  launch_penalty_forces(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->bodies.cur, parts, res);
-  NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  const PartialsWork w(ctx->bodies.work, (size_t)ctx->bodies.cur.n * body_numbers(ctx->mesh.dim), kBodyParts);
+  launch_penalty_forces(s, ctx->mesh, ctx->state[velocity_slot].p, ctx->bodies.cur, w.parts, w.res);
+  w.read_back(s, out);
   API_END(ctx)
 }
 
@@ -3285,14 +3340,9 @@ extern "C" int nsfem_body_heat(nsfem_ctx* ctx, int scalar_slot, double* out) {
   heated_require(ctx, scalar_slot);
   hipStream_t s = ctx->stream;
   ensure_scalar_slot(ctx, scalar_slot);
-  const size_t n_out = (size_t)ctx->bodies.cur.n * 3;
-  const size_t n_work = n_out * (kBodyParts + 1);
-  if (ctx->bodies.heat_work.n != n_work) ctx->bodies.heat_work.alloc(n_work);
-  double* parts = ctx->bodies.heat_work.p;
-  double* res = parts + n_out * kBodyParts;
-  launch_body_heat(s, ctx->mesh, ctx->state[scalar_slot].p, ctx->bodies.cur, ctx->bodies.thermal, parts, res);
-  NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  const PartialsWork w(ctx->bodies.heat_work, (size_t)ctx->bodies.cur.n * 3, kBodyParts);
+  launch_body_heat(s, ctx->mesh, ctx->state[scalar_slot].p, ctx->bodies.cur, ctx->bodies.thermal, w.parts, w.res);
+  w.read_back(s, out);
   API_END(ctx)
 }
 
@@ -3995,8 +4045,7 @@ extern "C" int nsfem_set_angular_velocity_3d(nsfem_ctx* ctx, const double omega[
 extern "C" int nsfem_cfl_number(nsfem_ctx* ctx, int slot, double step_size, double* cfl) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && cfl, "null argument");
-  NSFEM_REQUIRE(slot >= 0 && slot < NSFEM_N_SLOTS && slot_size(ctx, slot) == nvel(ctx),
-                "not a velocity slot");
+  require_slot(ctx, slot, SlotClass::VelocitySized);
   hipStream_t s = ctx->stream;
   const int n_parts = 256;
   ctx->kw.ensure(nvel(ctx));
@@ -4020,10 +4069,8 @@ extern "C" int nsfem_boundary_force(nsfem_ctx* ctx, int velocity_slot, int press
                                     const int32_t* facet_local, double nu, double sym, double* out) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out && (n_facets == 0 || (facet_cell && facet_local)), "null argument");
-  NSFEM_REQUIRE(velocity_slot >= 0 && velocity_slot < NSFEM_N_SLOTS && slot_size(ctx, velocity_slot) == nvel(ctx),
-                "not a velocity slot");
-  NSFEM_REQUIRE(pressure_slot >= 0 && pressure_slot < NSFEM_N_SLOTS && slot_size(ctx, pressure_slot) == npre(ctx),
-                "not a pressure slot");
+  require_slot(ctx, velocity_slot, SlotClass::VelocitySized);
+  require_slot(ctx, pressure_slot, SlotClass::PressureSized);
   const int dim = ctx->mesh.dim, w = dim + 2;
   for (int k = 0; k < w; ++k) out[k] = 0.0;
   if (n_facets == 0) return NSFEM_OK;
@@ -4055,17 +4102,12 @@ extern "C" int nsfem_volume_functionals(nsfem_ctx* ctx, int velocity_slot, int p
                                         const uint8_t* cell_flags, double out[NSFEM_N_FUNCTIONALS]) {
   API_BEGIN
   NSFEM_REQUIRE(ctx && out, "null argument");
-  NSFEM_REQUIRE(velocity_slot >= 0 && velocity_slot < NSFEM_N_SLOTS && slot_size(ctx, velocity_slot) == nvel(ctx),
-                "not a velocity slot");
-  NSFEM_REQUIRE(pressure_slot >= 0 && pressure_slot < NSFEM_N_SLOTS && slot_size(ctx, pressure_slot) == npre(ctx),
-                "not a pressure slot");
+  require_slot(ctx, velocity_slot, SlotClass::VelocitySized);
+  require_slot(ctx, pressure_slot, SlotClass::PressureSized);
   hipStream_t s = ctx->stream;
   const int dim = ctx->mesh.dim;
   const size_t nc = (size_t)ctx->mesh.n_cells;
-  const size_t n_work = (size_t)NSFEM_N_FUNCTIONALS * (kVolParts + 1);
-  if (ctx->vf_parts.n != n_work) ctx->vf_parts.alloc(n_work);
-  double* parts = ctx->vf_parts.p;
-  double* res = parts + (size_t)NSFEM_N_FUNCTIONALS * kVolParts;
+  const PartialsWork w(ctx->vf_parts, NSFEM_N_FUNCTIONALS, kVolParts);
   const double *ur = nullptr, *pr = nullptr;
   if (ref_velocity) {
     ctx->vf_ref_u.upload(ref_velocity, (size_t)nvel(ctx), s);
@@ -4098,10 +4140,9 @@ extern "C" int nsfem_volume_functionals(nsfem_ctx* ctx, int velocity_slot, int p
     u = ctx->vf_u.p;
     p = ctx->vf_p.p;
   }
-  launch_vol_functionals(s, ctx->mesh, u, p, ur, pr, flags, parts, res);
-  if (dist) ctx->comm->allreduce_sum(s, res, NSFEM_N_FUNCTIONALS);
-  NSFEM_HIP(hipMemcpyAsync(out, res, sizeof(double) * NSFEM_N_FUNCTIONALS, hipMemcpyDeviceToHost, s));
-  NSFEM_HIP(hipStreamSynchronize(s));
+  launch_vol_functionals(s, ctx->mesh, u, p, ur, pr, flags, w.parts, w.res);
+  if (dist) ctx->comm->allreduce_sum(s, w.res, NSFEM_N_FUNCTIONALS);
+  w.read_back(s, out);
   API_END(ctx)
 }
 
@@ -4345,17 +4386,13 @@ extern "C" int nsfem_stats_sample(nsfem_ctx* ctx, int velocity_slot, int pressur
   stats_require_enabled(ctx);
   nsfem_ctx::Stats& S = ctx->stats;
   NSFEM_REQUIRE(std::isfinite(weight) && weight > 0.0, "flow statistics: the weight of a sample must be finite and > 0");
-  NSFEM_REQUIRE(velocity_slot >= 0 && velocity_slot < NSFEM_N_SLOTS && slot_size(ctx, velocity_slot) == nvel(ctx),
-                "flow statistics: not a velocity slot");
+  require_slot(ctx, velocity_slot, SlotClass::VelocitySized, "flow statistics: ");
   const bool pressure = (S.flags & NSFEM_STATS_PRESSURE) != 0, scalar = (S.flags & NSFEM_STATS_SCALAR) != 0;
-  if (pressure)
-    NSFEM_REQUIRE(pressure_slot >= 0 && pressure_slot < NSFEM_N_SLOTS && slot_size(ctx, pressure_slot) == npre(ctx),
-                  "flow statistics: not a pressure slot");
+  if (pressure) require_slot(ctx, pressure_slot, SlotClass::PressureSized, "flow statistics: ");
   else NSFEM_REQUIRE(pressure_slot == -1, "flow statistics: pressure slot given, but NSFEM_STATS_PRESSURE is not enabled");
   if (scalar) {
     NSFEM_REQUIRE(ctx->sc.configured, "flow statistics: scalar requested, but nsfem_set_scalar has not been called");
-    NSFEM_REQUIRE(scalar_slot >= 0 && scalar_slot < NSFEM_N_SLOTS && ::scalar_slot(scalar_slot),
-                  "flow statistics: not a scalar slot");
+    require_slot(ctx, scalar_slot, SlotClass::ScalarSized, "flow statistics: ");
     ensure_scalar_slot(ctx, scalar_slot);
   } else {
     NSFEM_REQUIRE(scalar_slot == -1, "flow statistics: scalar slot given, but NSFEM_STATS_SCALAR is not enabled");
@@ -4512,17 +4549,12 @@ extern "C" int nsfem_derived_fields(nsfem_ctx* ctx, int velocity_slot, int press
   NSFEM_REQUIRE((quantity_mask >> NSFEM_N_DERIVED) == 0, "derived fields: unknown quantity bit");
   NSFEM_REQUIRE(center == NSFEM_DERIVED_CELL || center == NSFEM_DERIVED_VERTEX || center == NSFEM_DERIVED_NODE,
                 "derived fields: unknown centre");
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "derived fields: velocity_slot is not a velocity slot");
+  require_slot(ctx, velocity_slot, SlotClass::VelocityLevel, "derived fields: ");
   const bool want_p = (quantity_mask & (1u << NSFEM_DERIVED_PRESSURE_GRADIENT)) != 0;
   const bool want_T = (quantity_mask & (1u << NSFEM_DERIVED_SCALAR_GRADIENT)) != 0;
-  if (want_p || pressure_slot != -1)
-    NSFEM_REQUIRE(pressure_slot == NSFEM_P || pressure_slot == NSFEM_P_OLD || pressure_slot == NSFEM_P2_OLD,
-                  "derived fields: pressure_slot is not a pressure slot");
+  if (want_p || pressure_slot != -1) require_slot(ctx, pressure_slot, SlotClass::PressureSlot, "derived fields: ");
   if (want_T) NSFEM_REQUIRE(ctx->sc.configured, "derived fields: SCALAR_GRADIENT without nsfem_set_scalar");
-  if (want_T || scalar_slot != -1)
-    NSFEM_REQUIRE(scalar_slot == NSFEM_T0 || scalar_slot == NSFEM_T1 || scalar_slot == NSFEM_T2,
-                  "derived fields: scalar_slot is not a level of the transported scalar");
+  if (want_T || scalar_slot != -1) require_slot(ctx, scalar_slot, SlotClass::ScalarLevel, "derived fields: ");
   const MeshDev& m = ctx->mesh;
   int ncomp = 0;
   for (int q = 0; q < NSFEM_N_DERIVED; ++q)
@@ -4752,13 +4784,10 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   NSFEM_REQUIRE(opts && out_groups, "wall quantities: null opts or out_groups");
   nsfem_ctx::Wall& W = ctx->wall;
   NSFEM_REQUIRE(W.have_set, "wall quantities: no facet set (nsfem_wall_set_facets)");
-  NSFEM_REQUIRE(velocity_slot == NSFEM_U0 || velocity_slot == NSFEM_U1 || velocity_slot == NSFEM_U2 ||
-                    velocity_slot == NSFEM_USTAR, "wall quantities: velocity_slot is not a velocity slot");
-  NSFEM_REQUIRE(pressure_slot == NSFEM_P || pressure_slot == NSFEM_P_OLD || pressure_slot == NSFEM_P2_OLD,
-                "wall quantities: pressure_slot is not a pressure slot");
+  require_slot(ctx, velocity_slot, SlotClass::VelocityLevel, "wall quantities: ");
+  require_slot(ctx, pressure_slot, SlotClass::PressureSlot, "wall quantities: ");
   if (scalar_slot != -1) {
-    NSFEM_REQUIRE(scalar_slot == NSFEM_T0 || scalar_slot == NSFEM_T1 || scalar_slot == NSFEM_T2,
-                  "wall quantities: scalar_slot is not a level of the transported scalar");
+    require_slot(ctx, scalar_slot, SlotClass::ScalarLevel, "wall quantities: ");
     NSFEM_REQUIRE(ctx->sc.configured, "wall quantities: a scalar slot without nsfem_set_scalar");
     // (a level that was never set or stepped has no storage: allocating it here would write state)
     NSFEM_REQUIRE(ctx->state[scalar_slot].p, "wall quantities: the scalar slot holds no data yet");

@@ -6,28 +6,16 @@
 // Shape of k_vol_functionals (functionals.hip): one thread per cell, grid-stride; row blockIdx.y of the grid integrates
 // body blockIdx.y and skips every cell its support cannot reach, so the accumulators are the 4 / 7 numbers of one body
 // and stay in registers.  Reduction without atomics: a thread adds its cells in ascending order, a wave folds its
-// lanes with a fixed xor-shuffle tree, the 4 waves of a workgroup are added in wave order, k_penal_finish folds the
+// lanes with a fixed xor-shuffle tree, the 4 waves of a workgroup are added in wave order, k_fold_partials folds the
 // kBodyParts partials of a number in a fixed order.  Same state, same bytes.
-#include "nsfem_internal.hpp"
 #include "cell_geometry.hpp"
 #include "bodies.hpp"
+#include "element_front.hpp"
 
 namespace nsfem {
 
-// own copies of the reference tables (a __constant__ symbol is private to its translation unit)
-__constant__ QuadTables c_bq;
-__constant__ QuadTables3 c_bq3;
-
-void upload_body_tables(int dim) {
-  QuadTables t;
-  fill_quad_tables(t);
-  NSFEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_bq), &t, sizeof(QuadTables)));
-  if (dim == 3) {
-    QuadTables3 t3;
-    fill_quad_tables_3d(t3);
-    NSFEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_bq3), &t3, sizeof(QuadTables3)));
-  }
-}
+NSFEM_FRONT_TABLES(c_bq, c_bq3)
+void upload_body_tables(int dim) { upload_front_tables(dim); }
 
 // parts[(s NQ + j) kBodyParts + block]: number j of body s over the cells of the block's threads;
 // j = 0 volume, 1 .. DIM force, then the torque about c_s (2D: z component; 3D: 3 components)
@@ -37,7 +25,7 @@ __global__ __launch_bounds__(256) void k_penal_forces(int nc, const double* __re
                                                       const double* __restrict__ u, const BodyTable bt,
                                                       double* __restrict__ parts) {
   constexpr int N2 = DIM == 2 ? 6 : 10, NQ = DIM == 2 ? 7 : 15, NO = DIM == 2 ? 4 : 7;
-  __shared__ double sh[4][NO];
+  __shared__ double sh[4 * NO];
   const int s = blockIdx.y;
   double acc[NO];
 #pragma unroll
@@ -53,12 +41,7 @@ __global__ __launch_bounds__(256) void k_penal_forces(int nc, const double* __re
     if constexpr (DIM == 2) adet = load_geo(vx, nc, c).adet;
     else adet = load_geo3(vx, nc, c).adet;
     double uu[N2][DIM];
-#pragma unroll
-    for (int k = 0; k < N2; ++k) {
-      const size_t node = (size_t)p2[(size_t)k * nc + c];
-#pragma unroll
-      for (int a = 0; a < DIM; ++a) uu[k][a] = u[DIM * node + a];
-    }
+    gather_p2_vector<DIM, DIM>(p2, nc, c, u, uu);
     for (int q = 0; q < NQ; ++q) {
       double x[DIM];
 #pragma unroll
@@ -93,16 +76,8 @@ __global__ __launch_bounds__(256) void k_penal_forces(int nc, const double* __re
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < NO; ++j) {
-    double v = acc[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][j] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NO)
-    parts[((size_t)s * NO + threadIdx.x) * gridDim.x + blockIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+  block_sum_fixed<NO>(acc, sh);
+  store_block_partials<NO>(sh, parts, (size_t)s * NO, gridDim.x, blockIdx.x);
 }
 
 // Heated bodies (nsfem_set_body_temperatures): per body the volume int chi_s, the heat rate
@@ -116,7 +91,7 @@ __global__ __launch_bounds__(256) void k_body_heat(int nc, const double* __restr
                                                    const BodyTable bt, const ThermalTable th,
                                                    double* __restrict__ parts) {
   constexpr int N2 = DIM == 2 ? 6 : 10, NQ = DIM == 2 ? 7 : 15, NO = 3;
-  __shared__ double sh[4][NO];
+  __shared__ double sh[4 * NO];
   const int s = blockIdx.y;
   const double scale = th.flag[s] != 0 ? th.inv_eta : 0.0, ts = th.temperature[s];
   double acc[NO] = {0.0, 0.0, 0.0};
@@ -131,8 +106,7 @@ __global__ __launch_bounds__(256) void k_body_heat(int nc, const double* __restr
     if constexpr (DIM == 2) adet = load_geo(vx, nc, c).adet;
     else adet = load_geo3(vx, nc, c).adet;
     double t[N2];
-#pragma unroll
-    for (int k = 0; k < N2; ++k) t[k] = T[(size_t)p2[(size_t)k * nc + c]];
+    gather_p2_scalar<DIM>(p2, nc, c, T, t);
     for (int q = 0; q < NQ; ++q) {
       double x[DIM];
 #pragma unroll
@@ -154,33 +128,13 @@ __global__ __launch_bounds__(256) void k_body_heat(int nc, const double* __restr
       acc[2] += w * tq;
     }
   }
-#pragma unroll
-  for (int j = 0; j < NO; ++j) {
-    double v = acc[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][j] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NO)
-    parts[((size_t)s * NO + threadIdx.x) * gridDim.x + blockIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
-}
-
-// out[b] = sum of the n_parts partials of number b: one wave per number, lane l adds its n_parts / 64 consecutive
-// partials in index order, then the xor-shuffle tree (a fixed order, as k_vol_finish)
-__global__ __launch_bounds__(64) void k_penal_finish(int n_parts, const double* __restrict__ parts,
-                                                     double* __restrict__ out) {
-  const int per = n_parts / 64;
-  const double* src = parts + (size_t)blockIdx.x * n_parts + (size_t)threadIdx.x * per;
-  double v = 0.0;
-  for (int i = 0; i < per; ++i) v += src[i];
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  if (threadIdx.x == 0) out[blockIdx.x] = v;
+  block_sum_fixed<NO>(acc, sh);
+  store_block_partials<NO>(sh, parts, (size_t)s * NO, gridDim.x, blockIdx.x);
 }
 
 void launch_penalty_forces(hipStream_t s, const MeshDev& m, const double* u, const BodyTable& bt, double* parts,
                            double* out) {
-  static_assert(kBodyParts % 64 == 0, "k_penal_finish gives every lane the same number of partials");
+  static_assert(kBodyParts % 64 == 0, "k_fold_partials gives every lane the same number of partials");
   NSFEM_REQUIRE(bt.n > 0, "immersed bodies: no body set");
   const dim3 grid(kBodyParts, bt.n), block(256);
   const bool smooth = bt.eps > 0.0;
@@ -192,8 +146,7 @@ void launch_penalty_forces(hipStream_t s, const MeshDev& m, const double* u, con
     else hipLaunchKernelGGL((k_penal_forces<2, false>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, bt, parts);
   }
   NSFEM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_penal_finish, dim3(bt.n * body_numbers(m.dim)), dim3(64), 0, s, kBodyParts, parts, out);
-  NSFEM_HIP(hipGetLastError());
+  launch_fold_partials(s, bt.n * body_numbers(m.dim), kBodyParts, parts, out);
 }
 
 void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const BodyTable& bt, const ThermalTable& th,
@@ -209,8 +162,7 @@ void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const Bo
     else hipLaunchKernelGGL((k_body_heat<2, false>), grid, block, 0, s, m.n_cells, m.vx.p, m.p2.p, T, bt, th, parts);
   }
   NSFEM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_penal_finish, dim3(bt.n * 3), dim3(64), 0, s, kBodyParts, parts, out);
-  NSFEM_HIP(hipGetLastError());
+  launch_fold_partials(s, bt.n * 3, kBodyParts, parts, out);
 }
 
 }  // namespace nsfem

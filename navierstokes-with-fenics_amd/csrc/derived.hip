@@ -18,8 +18,8 @@
 // buffer of the context's own (one plane per component: the stores of a wave are as coalesced as the node-sorted
 // order allows), k_derived_gather sums each run m.nptr[n] .. m.nptr[n + 1] in ascending cell order and divides.  Same
 // state, same bytes.  m.rbuf, m.ebuf and the state slots are never written.
-#include "nsfem_internal.hpp"
 #include "cell_geometry.hpp"
+#include "element_front.hpp"
 
 namespace nsfem {
 
@@ -54,19 +54,8 @@ void upload_derived_tables() {
 // unrolled: a zero entry costs nothing)
 // d lambda_i / d xi_b
 __host__ __device__ constexpr double dlam(int i, int b) { return i == 0 ? -1.0 : (i - 1 == b ? 1.0 : 0.0); }
-// the two vertices of edge node e (local node DIM + 1 + e), UFC order as fill_quad_tables / fill_quad_tables_3d
-template <int DIM>
-__host__ __device__ constexpr int edge_end(int e, int which) {
-  if (DIM == 2) {
-    constexpr int pr[3][2] = {{1, 2}, {0, 2}, {0, 1}};
-    return pr[e][which];
-  } else {
-    constexpr int pr[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
-    return pr[e][which];
-  }
-}
 // d phi_k / d xi_b at vertex v: vertex functions (4 lambda_k - 1) grad lambda_k, edge functions
-// 4 (lambda_a grad lambda_b + lambda_b grad lambda_a)
+// 4 (lambda_a grad lambda_b + lambda_b grad lambda_a), a and b the ends of the edge (edge_end, element_front.hpp)
 template <int DIM>
 __host__ __device__ constexpr double dphi2_at_vertex(int v, int k, int b) {
   if (k <= DIM) return (k == v ? 3.0 : -1.0) * dlam(k, b);

@@ -11,27 +11,16 @@
 //
 // Reduction without atomics: a thread accumulates its cells in ascending order, a wave folds its 64 lanes with a fixed
 // xor-shuffle tree, the 4 waves of a workgroup are added in wave order and stored as one partial per quantity;
-// k_vol_finish folds the kVolParts partials of a quantity in a fixed order as well.  Same state, same bytes.
-#include "nsfem_internal.hpp"
+// k_fold_partials folds the kVolParts partials of a quantity in a fixed order as well.  Same state, same bytes.
+// The P1 gather, the degree-5 tables and both levels of the reduction come from element_front.hpp; the gather of the
+// nodal velocities stays here (through the shared helper the compiler fuses the products of |u|^2 the other way round).
 #include "cell_geometry.hpp"
+#include "element_front.hpp"
 
 namespace nsfem {
 
-// own copies of the reference tables (a __constant__ symbol is private to its translation unit), filled by the
-// same fill_quad_tables / fill_quad_tables_3d
-__constant__ QuadTables c_fq;
-__constant__ QuadTables3 c_fq3;
-
-void upload_functional_tables(int dim) {
-  QuadTables t;
-  fill_quad_tables(t);
-  NSFEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_fq), &t, sizeof(QuadTables)));
-  if (dim == 3) {
-    QuadTables3 t3;
-    fill_quad_tables_3d(t3);
-    NSFEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_fq3), &t3, sizeof(QuadTables3)));
-  }
-}
+NSFEM_FRONT_TABLES(c_fq, c_fq3)
+void upload_functional_tables(int dim) { upload_front_tables(dim); }
 
 // parts[j][block]: quantity j of NSFEM_N_FUNCTIONALS (include/nsfem.h) over the cells of the block's threads.
 // ur / pr != null: the fields are u - ur / p - pr (formed at the nodes while loading); flags != null: cells with
@@ -48,7 +37,7 @@ __global__ __launch_bounds__(256) void k_vol_functionals(int nc, const double* _
                                                          double* __restrict__ parts) {
   constexpr int N2 = DIM == 2 ? 6 : 10, N1 = DIM + 1, NQ = DIM == 2 ? 7 : 15;
   constexpr int NF = NSFEM_N_FUNCTIONALS;
-  __shared__ double sh[4][NF];
+  __shared__ double sh[4 * NF];
   double acc[NF];
 #pragma unroll
   for (int j = 0; j < NF; ++j) acc[j] = 0.0;
@@ -76,12 +65,7 @@ __global__ __launch_bounds__(256) void k_vol_functionals(int nc, const double* _
         }
       }
     }
-#pragma unroll
-    for (int i = 0; i < N1; ++i) {
-      const size_t node = (size_t)p1[(size_t)i * nc + c];
-      pp[i] = p[node];
-      if (pr) pp[i] -= pr[node];
-    }
+    gather_p1<DIM>(p1, nc, c, p, pr, pp);
     // grad p is constant on the cell: sum_i p_i grad lambda_i, reference gradients (-1, .., -1), e_1, .., e_DIM
     double gp2, adet;
     if constexpr (DIM == 2) {
@@ -171,22 +155,15 @@ __global__ __launch_bounds__(256) void k_vol_functionals(int nc, const double* _
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < NF; ++j) {
-    double v = acc[j];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][j] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NF)
-    parts[(size_t)threadIdx.x * gridDim.x + blockIdx.x] =
-        ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+  block_sum_fixed<NF>(acc, sh);
+  store_block_partials<NF>(sh, parts, 0, gridDim.x, blockIdx.x);
 }
 
-// out[j] = sum of the n_parts partials of quantity j: one wave per quantity, lane l adds its n_parts / 64 consecutive
-// partials in index order, then the xor-shuffle tree (a fixed order)
-__global__ __launch_bounds__(64) void k_vol_finish(int n_parts, const double* __restrict__ parts,
-                                                   double* __restrict__ out) {
+// out[b] = sum of the n_parts partials parts[b][.] of number b: one wave per number, lane l adds its n_parts / 64
+// consecutive partials in index order, then the xor-shuffle tree (a fixed order).  The second level of every two-launch
+// reduction of the post-processing
+__global__ __launch_bounds__(64) void k_fold_partials(int n_parts, const double* __restrict__ parts,
+                                                      double* __restrict__ out) {
   const int per = n_parts / 64;
   const double* src = parts + (size_t)blockIdx.x * n_parts + (size_t)threadIdx.x * per;
   double v = 0.0;
@@ -195,9 +172,14 @@ __global__ __launch_bounds__(64) void k_vol_finish(int n_parts, const double* __
   if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
+void launch_fold_partials(hipStream_t s, int n_numbers, int n_parts, const double* parts, double* out) {
+  hipLaunchKernelGGL(k_fold_partials, dim3(n_numbers), dim3(64), 0, s, n_parts, parts, out);
+  NSFEM_HIP(hipGetLastError());
+}
+
 void launch_vol_functionals(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* ur,
                             const double* pr, const uint8_t* flags, double* parts, double* out) {
-  static_assert(kVolParts % 64 == 0, "k_vol_finish gives every lane the same number of partials");
+  static_assert(kVolParts % 64 == 0, "k_fold_partials gives every lane the same number of partials");
   if (m.dim == 3)
     hipLaunchKernelGGL(k_vol_functionals<3>, dim3(kVolParts), dim3(256), 0, s, m.n_cells, m.vx.p, m.p2.p, m.p1.p, u,
                        p, ur, pr, flags, parts);
@@ -205,8 +187,7 @@ void launch_vol_functionals(hipStream_t s, const MeshDev& m, const double* u, co
     hipLaunchKernelGGL(k_vol_functionals<2>, dim3(kVolParts), dim3(256), 0, s, m.n_cells, m.vx.p, m.p2.p, m.p1.p, u,
                        p, ur, pr, flags, parts);
   NSFEM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_vol_finish, dim3(NSFEM_N_FUNCTIONALS), dim3(64), 0, s, kVolParts, parts, out);
-  NSFEM_HIP(hipGetLastError());
+  launch_fold_partials(s, NSFEM_N_FUNCTIONALS, kVolParts, parts, out);
 }
 
 }  // namespace nsfem

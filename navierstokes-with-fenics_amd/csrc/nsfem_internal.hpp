@@ -637,7 +637,7 @@ void launch_scalar_convection(hipStream_t s, const MeshDev& m, const double* u, 
                               int form, const ScalarBodies* hb, double* out, ScalarSgsArgs sgs = ScalarSgsArgs{});
 void scalar_convection_cells_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double weight,
                                 int form, int penal, const ScalarBodies* hb, ScalarSgsArgs sgs);
-// k_body_heat + k_penal_finish (bodies.hip): out[s][3] = {int chi_s, Q_s, int chi_s T} in device memory, parts
+// k_body_heat + k_fold_partials (bodies.hip): out[s][3] = {int chi_s, Q_s, int chi_s T} in device memory, parts
 // [n 3 kBodyParts] work space
 void launch_body_heat(hipStream_t s, const MeshDev& m, const double* T, const BodyTable& bt, const ThermalTable& th,
                       double* parts, double* out);
@@ -649,7 +649,7 @@ constexpr int kBodyParts = 256;
 void launch_penalty_cells(hipStream_t s, const MeshDev& m, const double* u, double weight, const BodyTable& bt,
                           bool mean);
 void penalty_cells_3d(hipStream_t s, const MeshDev& m, const double* u, double weight, const BodyTable& bt, bool mean);
-// k_penal_forces + k_penal_finish (bodies.hip): out[s][body_numbers] in device memory, parts
+// k_penal_forces + k_fold_partials (bodies.hip): out[s][body_numbers] in device memory, parts
 // [n body_numbers kBodyParts] work space
 void upload_body_tables(int dim);
 void launch_penalty_forces(hipStream_t s, const MeshDev& m, const double* u, const BodyTable& bt, double* parts,
@@ -666,6 +666,8 @@ void launch_boundary_force(hipStream_t s, const MeshDev& m, int nf, const int32_
 // [NSFEM_N_FUNCTIONALS][kVolParts] work space, out: [NSFEM_N_FUNCTIONALS], both in device memory
 constexpr int kVolParts = 1024;
 void upload_functional_tables(int dim);
+// k_fold_partials (functionals.hip): out[b] = the sum of parts[b][0 .. n_parts) in a fixed order, n_parts a multiple of 64
+void launch_fold_partials(hipStream_t s, int n_numbers, int n_parts, const double* parts, double* out);
 void launch_vol_functionals(hipStream_t s, const MeshDev& m, const double* u, const double* p, const double* ur,
                             const double* pr, const uint8_t* flags, double* parts, double* out);
 

@@ -18,8 +18,8 @@
 // Plain loads and stores, no atomics, no floating point reduction: the same input gives the same bytes.  The two
 // counters of the tracer kernels (particles that have left, bin-search fallbacks) are integer sums per workgroup, added
 // on the host.
-#include "nsfem_internal.hpp"
 #include "cell_geometry.hpp"
+#include "element_front.hpp"
 
 namespace nsfem {
 
@@ -77,25 +77,6 @@ __device__ __forceinline__ int bin_search(const PointLocatorDev& L, const double
   return -1;
 }
 
-// P2 basis in the local numbering of evaluate_lagrange: vertices, then the edges opposite
-template <int DIM>
-__device__ __forceinline__ void p2_basis(const double* lam, double* N) {
-#pragma unroll
-  for (int i = 0; i <= DIM; ++i) N[i] = lam[i] * (2.0 * lam[i] - 1.0);
-  if constexpr (DIM == 2) {
-    N[3] = 4.0 * lam[1] * lam[2];
-    N[4] = 4.0 * lam[0] * lam[2];
-    N[5] = 4.0 * lam[0] * lam[1];
-  } else {
-    N[4] = 4.0 * lam[2] * lam[3];
-    N[5] = 4.0 * lam[1] * lam[3];
-    N[6] = 4.0 * lam[1] * lam[2];
-    N[7] = 4.0 * lam[0] * lam[3];
-    N[8] = 4.0 * lam[0] * lam[2];
-    N[9] = 4.0 * lam[0] * lam[1];
-  }
-}
-
 // sum_k N_k u[node_k] of a node-interleaved P2 field with NV components
 template <int DIM, int NV>
 __device__ __forceinline__ void p2_gather(const int32_t* __restrict__ p2, int nc, int c, const double* N,
@@ -105,15 +86,10 @@ __device__ __forceinline__ void p2_gather(const int32_t* __restrict__ p2, int nc
   for (int a = 0; a < NV; ++a) out[a] = 0.0;
 #pragma unroll
   for (int k = 0; k < N2; ++k) {
-    const size_t node = (size_t)p2[(size_t)k * nc + c];
-    if constexpr (NV == 2) {
-      const double2 v = reinterpret_cast<const double2*>(u)[node];
-      out[0] += N[k] * v.x;
-      out[1] += N[k] * v.y;
-    } else {
+    double v[NV];
+    load_node<NV, true>(u, (size_t)p2[(size_t)k * nc + c], v);
 #pragma unroll
-      for (int a = 0; a < NV; ++a) out[a] += N[k] * u[NV * node + a];
-    }
+    for (int a = 0; a < NV; ++a) out[a] += N[k] * v[a];
   }
 }
 
@@ -151,14 +127,15 @@ __global__ __launch_bounds__(256) void k_eval_points(int kind, int nc, const dou
   for (int d = 0; d < DIM; ++d) p[d] = x[DIM * i + d];
   barycentric<DIM>(vx, nc, c, p, lam);
   if (kind == 1) {
-    double v = 0.0;
+    double v = 0.0, fn[DIM + 1];
+    gather_p1<DIM>(p1, nc, c, f, nullptr, fn);
 #pragma unroll
-    for (int k = 0; k <= DIM; ++k) v += lam[k] * f[(size_t)p1[(size_t)k * nc + c]];
+    for (int k = 0; k <= DIM; ++k) v += lam[k] * fn[k];
     out[i] = v;
     return;
   }
   double N[DIM == 2 ? 6 : 10];
-  p2_basis<DIM>(lam, N);
+  p2_at<DIM>(lam, N);   // (the local numbering of evaluate_lagrange)
   if (kind == 0) {
     double v[DIM];
     p2_gather<DIM, DIM>(p2, nc, c, N, f, v);
@@ -181,11 +158,10 @@ __global__ __launch_bounds__(256) void k_tracer_init(int64_t n, const int32_t* _
     left = cells[i] < 0 ? 1 : 0;
     status[i] = (uint8_t)left;
   }
-  for (int off = 32; off > 0; off >>= 1) left += __shfl_xor(left, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = left;
-  __syncthreads();
+  const int sum[1] = {left};
+  block_sum_fixed<1>(sum, sh);
   if (threadIdx.x == 0) {
-    counts[2 * blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    counts[2 * blockIdx.x] = block_total<1>(sh, 0);
     counts[2 * blockIdx.x + 1] = 0;
   }
 }
@@ -206,7 +182,7 @@ __device__ __forceinline__ bool tracer_velocity(const PointLocatorDev& L, int nc
     cell = c;
   }
   double N[DIM == 2 ? 6 : 10];
-  p2_basis<DIM>(lam, N);
+  p2_at<DIM>(lam, N);   // (the local numbering of evaluate_lagrange)
   p2_gather<DIM, DIM>(p2, nc, cell, N, ua, vel);
   if (ub) {
     double vb[DIM];
@@ -225,7 +201,7 @@ __global__ __launch_bounds__(256) void k_advect_tracers(PointLocatorDev L, int n
                                                         double dt, int n_sub, int64_t n, double* __restrict__ x,
                                                         int32_t* __restrict__ cells, uint8_t* __restrict__ status,
                                                         int32_t* __restrict__ counts) {
-  __shared__ int sh[2][4];
+  __shared__ int sh[4 * 2];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int left = 0, fallbacks = 0;
   if (i < n) left = status[i] != 0 ? 1 : 0;
@@ -282,18 +258,9 @@ __global__ __launch_bounds__(256) void k_advect_tracers(PointLocatorDev L, int n
     cells[i] = cell;
     if (left) status[i] = 1;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    left += __shfl_xor(left, off);
-    fallbacks += __shfl_xor(fallbacks, off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = left;
-    sh[1][threadIdx.x >> 6] = fallbacks;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2)
-    counts[2 * blockIdx.x + threadIdx.x] =
-        sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+  const int sum[2] = {left, fallbacks};
+  block_sum_fixed<2>(sum, sh);
+  store_block_partials<2>(sh, counts, 2 * blockIdx.x, 1, 0);
 }
 
 static inline unsigned point_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }

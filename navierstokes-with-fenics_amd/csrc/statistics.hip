@@ -14,8 +14,8 @@
 //   d_i = x_i - m_i;   m_i += a d_i;   C_ij += b d_i d_j        (every d taken before a mean moves)
 // elementwise, no atomics, no LDS.  The profile kernel folds its sums as k_vol_functionals does: a thread adds its
 // nodes in ascending list order, a wave folds its lanes with a fixed xor-shuffle tree, the 4 waves are added in wave
-// order.  Same samples, same bytes.
-#include "nsfem_internal.hpp"
+// order (block_sum_all, element_front.hpp).  Same samples, same bytes.
+#include "element_front.hpp"
 
 namespace nsfem {
 
@@ -149,22 +149,6 @@ void launch_stats_update(hipStream_t s, int dim, bool scalar, StatsUpdate a) {
   NSFEM_HIP(hipGetLastError());
 }
 
-// v[0 .. N) summed over the workgroup, the total in every thread: lanes by the xor-shuffle tree, waves in wave order
-// (sh: 4 N doubles)
-template <int N>
-__device__ __forceinline__ void stats_block_sum(double (&v)[N], double* sh) {
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    double t = v[j];
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
-    if ((threadIdx.x & 63) == 0) sh[(threadIdx.x >> 6) * N + j] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < N; ++j) v[j] = ((sh[j] + sh[N + j]) + sh[2 * N + j]) + sh[3 * N + j];
-  __syncthreads();   // sh is used again
-}
-
 // One workgroup per group g.  Pass 1: A = sum a_n, sum a_n m_n and the within-node part sum a_n C_n / W; pass 2, with
 // the group means known: the between-node part sum a_n (m_n - m_g)(m_n - m_g)^T.  out[g][q], q as the accumulators.
 template <int DIM, bool SCALAR>
@@ -187,7 +171,7 @@ __global__ __launch_bounds__(256) void k_stats_profile(const double* __restrict_
 #pragma unroll
     for (int c = 0; c < NQ; ++c) s1[c] += a * acc[(size_t)c * stride + n];
   }
-  stats_block_sum<NQ + 1>(s1, sh);
+  block_sum_all<NQ + 1>(s1, sh);
   const double inv_a = 1.0 / s1[NQ];
   double mg[NV];
 #pragma unroll
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(256) void k_stats_profile(const double* __restrict_
     for (int v = 0; v < NV; ++v) d[v] = acc[(size_t)L::mean(v) * stride + n] - mg[v];
     stats_for_each_pair<DIM, SCALAR>([&](int, int k, int i, int j) { s2[k] += a * (d[i] * d[j]); });
   }
-  stats_block_sum<NM>(s2, sh);
+  block_sum_all<NM>(s2, sh);
   if (threadIdx.x == 0) {
     double* o = out + (size_t)g * NQ;
 #pragma unroll

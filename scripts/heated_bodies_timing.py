@@ -12,7 +12,7 @@
         nsfem_body_scalar_residual), of the plain scalar convection kernel (PENAL 0, through nsfem_scalar_convection)
         and of the flow's penalisation pair (k_penal_cell / k3_penal_cell + k_visc_gather, through
         nsfem_body_residual) on the cavity at n = 512 with one disc of radius 0.1 and on a 64^3 box with one ball of
-        radius 0.1, sharp and smoothed, both forms; then the heat numbers (k_body_heat + k_penal_finish).
+        radius 0.1, sharp and smoothed, both forms; then the heat numbers (k_body_heat + k_fold_partials).
 
     python scripts/heated_bodies_timing.py summary DIR
         median, minimum and maximum per kernel name and grid size of the trace under DIR, microseconds.
@@ -176,7 +176,7 @@ def main():
     p.add_argument("--smoothing", type=float, default=0.01)
     p = sub.add_parser("summary")
     p.add_argument("dir")
-    p.add_argument("--match", default="scalar_conv_cell,scalar_gather,penal,visc_gather,body_heat")
+    p.add_argument("--match", default="scalar_conv_cell,scalar_gather,penal,fold_partials,visc_gather,body_heat")
     args = ap.parse_args()
     dict(steps=run_steps, kernels=run_kernels, summary=run_summary)[args.mode](args)
 

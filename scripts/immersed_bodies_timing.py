@@ -134,7 +134,7 @@ def main():
     p.add_argument("--lib", default=None)
     p = sub.add_parser("summary")
     p.add_argument("dir")
-    p.add_argument("--match", default="penal,conv_cell,visc_gather,res_gather")
+    p.add_argument("--match", default="penal,fold_partials,conv_cell,visc_gather,res_gather")
     args = ap.parse_args()
     dict(steps=run_steps, kernels=run_kernels, summary=run_summary)[args.mode](args)
 

@@ -95,6 +95,33 @@ def test_body_kernels_match_the_restatement(kind, name):
         ctx.close()
 
 
+def test_body_forces_on_a_second_trip_of_the_cell_loop():
+    """box(192, 192) = 73,728 cells, the smallest square box with more cells than the 256 x 256 threads of a grid row
+    of k_penal_forces: 8,192 threads integrate a second cell.  Volume, force and torque of the moving disc, sharp and
+    smoothed, against the restatement under the tolerances of the kernel test"""
+    mesh, dm, marks, s, rs, make = _mesh((192, 192))
+    assert mesh.num_cells() == 73728 > 256 * 256
+    u, _ = smooth_fields(dm.p2_coords)
+    eta = 0.037
+    ctx = make(mesh, dm)
+    try:
+        ctx.set_state(nat.U1, u)
+        for eps in (0.0, EPS):
+            bodies = ImmersedBodies(bodies_2d("disc", True), eta, eps)
+            orc = PenalisationRestatement(rs, bodies)
+            assert orc.surface_clearance() >= 1e-9
+            forces = orc.forces(u)
+            ctx.set_bodies(bodies.rows(), eta, eps)
+            F = ctx.body_forces(nat.U1)
+            ferr = _max_rel(F, forces)
+            print("box(192, 192) disc eps %.2f: forces %.2e (of the largest entry)" % (eps, ferr))
+            assert F.shape == forces.shape == (1, 4) and np.abs(forces).min() > 1e-6
+            assert ferr < _TOL[eps], ferr
+            assert F.tobytes() == ctx.body_forces(nat.U1).tobytes()
+    finally:
+        ctx.close()
+
+
 # ---------------------------------------------------------------- 2. steps against the restatement
 def _setup(ctx, dm, marks, s, penal, visc=None):
     """coefficients, cavity / lid boundary values and the body force of the viscosity tests; two restatements, with

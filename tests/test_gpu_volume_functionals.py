@@ -1,4 +1,4 @@
-"""nsfem_volume_functionals on the device (csrc/functionals.hip: k_vol_functionals<2>, <3>, k_vol_finish) against the
+"""nsfem_volume_functionals on the device (csrc/functionals.hip: k_vol_functionals<2>, <3>, k_fold_partials) against the
 oracle's matrices and the numpy restatement pinned in tests/test_volume_functionals_host.py -- plain and reference
 mode, cell flags, determinism, thread ranks on one GPU, and the callers: ``norm`` / ``errornorm`` of the dolfin shim
 and ``ProblemBase._compute_flow_diagnostics``.
@@ -113,6 +113,30 @@ def test_values_equal_the_oracle(name):
     r2 = ctx.volume_functionals(nat.U1, nat.P_OLD)["values"]
     _compare(r2, mesh, dm, 2.0 * u, -p, name + " (U1, P_OLD)")
     ctx.close()
+
+
+def test_a_second_trip_of_the_cell_loop_equals_the_restatement():
+    """364 x 364 = 264,992 cells, the smallest square box with more cells than the 1024 x 256 threads of
+    k_vol_functionals: 2,848 threads integrate a second cell.  Against the pinned restatement alone (the oracle's
+    matrices are not formed at this size), under the file's TOL"""
+    mesh = rectangle_mesh((0.0, 0.0), (1.0, 1.0), 364, 364)
+    dm = TaylorHoodDofMap(mesh)
+    assert mesh.num_cells() == 264992 > 1024 * 256
+    u, p = smooth_fields(dm.p2_coords, dm.p1_coords)
+    u = u.ravel()
+    ctx = context(mesh, dm)
+    ctx.set_state(nat.U0, u)
+    ctx.set_state(nat.P, p)
+    got = ctx.volume_functionals(nat.U0, nat.P)["values"]
+    again = ctx.volume_functionals(nat.U0, nat.P)["values"]
+    ctx.close()
+    val, scale = vol_functionals_numpy(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap, u, p, None)
+    for j in range(N_FUNCTIONALS):
+        print("364x364 %-14s device %+.17e  reference %+.17e  error / scale %.2e" %
+              (NAMES[j], got[j], val[j], abs(got[j] - val[j]) / max(scale[j], 1e-300)))
+    for j in range(N_FUNCTIONALS):
+        assert abs(got[j] - val[j]) <= TOL * scale[j], (NAMES[j], got[j], val[j], scale[j])
+    assert got.tobytes() == again.tobytes()
 
 
 @pytest.mark.parametrize("name", MESHES)
