@@ -624,6 +624,74 @@ int nsfem_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, double* cs2_groups
 /* out = {n_groups (0 before law 8 was ever set), runs of the procedure so far, launches of its three kernels, bytes of
  * its device buffers}.  nsfem_viscosity_info keeps counting the element launches alone. */
 int nsfem_dynamic_info(nsfem_ctx* ctx, int64_t out[4]);
+/* ---- Lagrangian averaging of law 8 (Meneveau, Lund & Cabot, JFM 319, 1996): LM and MM are averaged along fluid path
+ * lines with an exponential memory instead of over groups -- no homogeneous direction is needed.  mode 0: the groups
+ * (nsfem_set_dynamic_groups; as before).  mode 1: params = {theta > 0 (1.5), cs2_init >= 0 (0.0256), cs2_floor >= 0
+ * (1e-12), 0}.  alpha and cs2_max stay those of law 8.  With k the step size of nsfem_set_imex, vert[v] = {W_v, LM_v,
+ * MM_v} of step 3 of law 8 on the level u = u^n, Delta_v^2 = (sum_K |K| Delta_K^2) / W_v over the patch in ascending
+ * cell order, p1 / p2 the connectivities and I = (I_LM, I_MM) the state at the vertices of the level before -- all
+ * arithmetic without contraction, sums from +0.0 in the order written:
+ *   1. displacement   u_v = the velocity at the P2 node p2[c0][i], c0 the first cell of the patch of v and i the local
+ *                     index with p1[c0][i] == v;  d = -k u_v
+ *   2. upstream cell  barycentric coordinates RELATIVE to v (d = 0 gives exactly lambda_i = 1, the others 0.0): for
+ *                     every patch cell c in ascending order, i the local index of v in c: lambda_j = grad(lambda_j) . d
+ *                     for j != i, lambda_i = 1 - sum_{j != i} lambda_j (j ascending), m_c = min_j lambda_j.  c* = the
+ *                     first cell with the largest m_c.  m_c* < 0 (the point left the patch: CFL > 1, an inflow
+ *                     boundary): lambda_j <- max(lambda_j, 0), each divided by their sum.  "The first cell with the
+ *                     largest m_c" compares rounded numbers.  Inside the patch a tie is harmless (P1 interpolation
+ *                     is continuous across faces).  Outside it is not: the clamped values of tied cells differ, and
+ *                     on structured meshes ties are exact by construction -- at an inflow vertex of a box the faces
+ *                     of several cells lie in the boundary plane and give the same limiting coordinate, and in 3D the
+ *                     far faces of two cells of a Kuhn patch lie in one coordinate plane.  Which of the tied cells
+ *                     is taken there depends on the rounding of m_c, and an implementation that rounds otherwise
+ *                     (another compiler, a host restatement) may take another one: the result is reproducible for
+ *                     one build, the same state gives the same bytes, but it is defined only up to that choice
+ *   3. upstream value I_up = sum_j lambda_j I[p1[c*][j]], j ascending, both components
+ *   4. relaxation     prod = I_LM_up I_MM_up;  prod > 0: T = theta sqrt(Delta_v^2) / sqrt(sqrt(sqrt(prod))),
+ *                     eps = k / (k + T); else eps = 1.  I_MM' = eps MM_v + (1 - eps) I_MM_up,
+ *                     I_LM' = max(eps LM_v + (1 - eps) I_LM_up, cs2_floor I_MM').  A vertex of no cell: I' = 0
+ *   5. constant       cs2_v = min(max(I_LM' / I_MM', 0), cs2_max) where I_MM' > 0, else 0; c_K and nu_x as in law 8
+ *   6. initialisation where no state exists it is formed from the first level evaluated: I_MM = MM_v, I_LM =
+ *                     cs2_init MM_v, cs2_v by rule 5
+ * Three launches as before (k_dyn_moments, k_dyn_vertex, k_dyn_lagrange in the place of k_dyn_reduce).
+ * Time levels: the constant is STATE that lives with the velocity slots.  The context keeps I of level n-1, I' and
+ * cs2_cur of level n (valid once formed) and cs2_prev of level n-1.  nsfem_step_imex forms level n once, when it forms
+ * N(u1); a second call without nsfem_advance reuses cs2_cur and launches nothing of the procedure.  nsfem_advance
+ * rotates (I <- I', cs2_prev <- cs2_cur) and clears the valid flag; without a formed level it drops cs2_prev and keeps
+ * I.  nsfem_set_state on NSFEM_U1 clears the valid flag as well (the level changed under its constant).  A stored
+ * N(u2) keeps the constant it was formed with; one that has to be formed again (a key that does not serve; always in
+ * nsfem_imex_rhs) reads cs2_prev, and without a cs2_prev the initialisation rule is applied to u2 and no state is
+ * written.  nsfem_imex_rhs reads cs2_cur where it exists, else applies the rules to the stored I into scratch: it
+ * never moves the state.  The hooks -- nsfem_viscosity_residual, nsfem_viscosity_cells, nsfem_wall_compute with
+ * use_law, nsfem_dynamic_constant -- read the stored field of the slot's level and never advance or recompute:
+ * cs2_prev for NSFEM_U2; for the other slots cs2_cur where formed, else the newest field there is (cs2_prev); a level
+ * without any field gets the initialisation rule on the slot's velocity, in scratch.  In mode 1 nsfem_dynamic_constant
+ * returns that vertex field in cs2_groups [n_p1], takes sums == NULL only, and vertices are the rows W, LM, MM of the
+ * slot's velocity (two launches).
+ * A change of mode, theta, cs2_init or cs2_floor resets the state and invalidates the stored vectors; so does setting
+ * law 8 (which returns to mode 0 with the global group) and nsfem_set_dynamic_groups (which returns to mode 0).  A
+ * change of k alone resets nothing.  NSFEM_ERR_ARG: law 8 not set, unknown mode, parameters out of range or not finite,
+ * contexts with a communicator, mode 1 while nsfem_set_scalar_sgs_dynamic is on (which refuses likewise while mode 1 is
+ * set: a Lagrangian C_theta is not supported).  A context that never calls this allocates and launches what it did. */
+int nsfem_set_dynamic_averaging(nsfem_ctx* ctx, int mode, const double params[4] /* mode 0: may be NULL */);
+/* The state for restart files: state [n_p1][4] = I_LM, I_MM, cs2 of level n, cs2 of level n-1; direction 0 get, 1 set.
+ * get: a column that does not exist is NaN in every row (I before the first advance, cs2 of level n-1 likewise); the
+ * third column is cs2_cur where formed, else a copy of the fourth.  set: columns 0, 1 and 3 count -- each is taken where
+ * no entry is NaN and absent where every entry is NaN (I_MM and cs2 >= 0, all finite) --, column 2 is NOT read: level n
+ * is formed by the next step.  With the velocity slots and NSFEM_CONV_N2 restored, a run continued in a fresh context
+ * forms bit for bit the explicit vectors and the state of the uninterrupted one; u and p are bit for bit the same only
+ * if the Krylov solves stop at the same iterations -- they postpone their first convergence check by the iteration count
+ * of the solve before, a memory that is no part of any state and that a fresh context does not have.  first_check of
+ * nsfem_krylov_opts at or above those counts takes that memory out.  NSFEM_ERR_ARG: mode 1 not set, a column NaN in part, values out of range. */
+int nsfem_dynamic_lagrangian_state(nsfem_ctx* ctx, int direction, double* state);
+/* Output and test hook: ONE application of rules 1 to 5 to the STORED I (rule 6 while there is none; the upstream
+ * pair is then that state) on u = velocity_slot with step size k > 0: out_state [n_p1][2] = I', out_upstream [n_p1][2]
+ * = I_up or NULL, out_cs2 [n_p1].  No stored state is touched; two calls on the same state return the same bytes. */
+int nsfem_dynamic_lagrangian_advance(nsfem_ctx* ctx, int velocity_slot, double k, double* out_state,
+                                     double* out_upstream, double* out_cs2);
+/* out = {1 while mode 1 is in force (law 8 set) else 0, 1 while I exists, 1 while level n is formed, 1 while cs2_prev
+ * exists}.  nsfem_dynamic_info counts k_dyn_lagrange among its launches and the state among its bytes. */
+int nsfem_dynamic_lagrangian_info(nsfem_ctx* ctx, int64_t out[4]);
 /* ---- immersed bodies in the IMEX step: Brinkman volume penalisation (new; the reference has body-fitted meshes only).
  * The momentum equation gains (chi / eta) (u - u_s), chi the indicator of the solid, u_s its rigid velocity.  Up to
  * NSFEM_MAX_BODIES bodies, each a primitive with a signed distance d(x), negative inside:

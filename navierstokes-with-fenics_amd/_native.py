@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = (
     "nsfem_scalar_dynamic_info",
     "nsfem_set_viscosity_law", "nsfem_viscosity_residual", "nsfem_viscosity_cells", "nsfem_viscosity_info",
     "nsfem_set_dynamic_groups", "nsfem_dynamic_constant", "nsfem_dynamic_info",
+    "nsfem_set_dynamic_averaging", "nsfem_dynamic_lagrangian_state", "nsfem_dynamic_lagrangian_advance",
+    "nsfem_dynamic_lagrangian_info",
     "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
     "nsfem_body_info",
     "nsfem_set_body_temperatures", "nsfem_body_scalar_residual", "nsfem_body_heat", "nsfem_body_heat_info",
@@ -230,6 +232,10 @@ def load_library(path=None):
         "nsfem_set_dynamic_groups": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32)]),
         "nsfem_dynamic_constant": (C.c_int, [vp, C.c_int, pd, pd, pd]),
         "nsfem_dynamic_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_dynamic_averaging": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_dynamic_lagrangian_state": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_dynamic_lagrangian_advance": (C.c_int, [vp, C.c_int, dbl, pd, pd, pd]),
+        "nsfem_dynamic_lagrangian_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_bodies": (C.c_int, [vp, C.c_int32, C.POINTER(Body), dbl, dbl]),
         "nsfem_move_bodies": (C.c_int, [vp, C.c_int32, C.POINTER(Body)]),
         "nsfem_body_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
@@ -678,8 +684,55 @@ class NsfemContext:
 
     def dynamic_constant(self, velocity_slot=U0, details=False):
         """C_s^2 of every averaging group for the velocity of the slot, [n_groups] (law 8; no stored state touched);
-        ``details``: also the sums [n_groups, 2] = num, den and the vertex rows [n_p1, 3] = W, LM, MM"""
+        ``details``: also the sums [n_groups, 2] = num, den and the vertex rows [n_p1, 3] = W, LM, MM.  With
+        Lagrangian averaging (``set_dynamic_averaging``): the stored vertex field of the slot's level, [n_p1]; with
+        ``details`` (field, None, vertex rows) -- there are no group sums"""
+        if self.dynamic_lagrangian_info()["active"]:
+            field = np.empty(self.n_p1, dtype=np.float64)
+            vert = np.empty((self.n_p1, 3), dtype=np.float64) if details else None
+            self._check(self._lib.nsfem_dynamic_constant(self._h, int(velocity_slot), _dp(field), None,
+                                                         _dp(vert) if details else None))
+            return (field, None, vert) if details else field
         return self._dynamic_constant(self._lib.nsfem_dynamic_constant, (velocity_slot, ), details)
+
+    def set_dynamic_averaging(self, mode, theta=1.5, cs2_init=0.0256, cs2_floor=1e-12):
+        """averaging of law 8: ``mode`` 0 / "groups" -- the averaging groups --, 1 / "lagrangian" -- along fluid path
+        lines with the relaxation time theta Delta (I_LM I_MM)^(-1/8) (include/nsfem.h); the state starts from
+        I_LM = cs2_init I_MM and I_LM stays above cs2_floor I_MM"""
+        mode = {"groups": 0, "lagrangian": 1}.get(mode, mode)
+        p = np.array([theta, cs2_init, cs2_floor, 0.0], dtype=np.float64)
+        self._check(self._lib.nsfem_set_dynamic_averaging(self._h, int(mode), _dp(p)))
+
+    def dynamic_lagrangian_state(self):
+        """[n_p1, 4] = I_LM, I_MM, cs2 of level n, cs2 of level n-1 for restart files; NaN columns do not exist yet"""
+        out = np.empty((self.n_p1, 4), dtype=np.float64)
+        self._check(self._lib.nsfem_dynamic_lagrangian_state(self._h, 0, _dp(out)))
+        return out
+
+    def set_dynamic_lagrangian_state(self, state):
+        """columns 0, 1 (I of level n-1) and 3 (cs2 of level n-1) are taken, each unless it is NaN throughout; column 2
+        is not read"""
+        state = np.ascontiguousarray(state, dtype=np.float64)
+        if state.shape != (self.n_p1, 4):
+            raise ValueError("set_dynamic_lagrangian_state: shape %r, expected (%d, 4)" % (state.shape, self.n_p1))
+        self._check(self._lib.nsfem_dynamic_lagrangian_state(self._h, 1, _dp(state)))
+
+    def dynamic_lagrangian_advance(self, velocity_slot, k, upstream=False):
+        """test and output hook: one application of the Lagrangian rules to the stored state on the slot's velocity
+        with step size k -> (I' [n_p1, 2], cs2 [n_p1]) or, with ``upstream``, (I', I_up [n_p1, 2], cs2); nothing stored
+        is touched"""
+        new = np.empty((self.n_p1, 2), dtype=np.float64)
+        up = np.empty((self.n_p1, 2), dtype=np.float64) if upstream else None
+        cs2 = np.empty(self.n_p1, dtype=np.float64)
+        self._check(self._lib.nsfem_dynamic_lagrangian_advance(self._h, int(velocity_slot), float(k), _dp(new),
+                                                               _dp(up) if upstream else None, _dp(cs2)))
+        return (new, up, cs2) if upstream else (new, cs2)
+
+    def dynamic_lagrangian_info(self):
+        """dict(active, have_state, level_formed, have_previous)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_dynamic_lagrangian_info(self._h, out))
+        return dict(active=bool(out[0]), have_state=bool(out[1]), level_formed=bool(out[2]), have_previous=bool(out[3]))
 
     def _dynamic_constant(self, call, slots, details):
         """one run of the Germano-Lilly procedure through ``call`` on ``slots``: the constant of every group, with

@@ -654,6 +654,9 @@ extern "C" int nsfem_set_state(nsfem_ctx* ctx, int slot, const double* host, int
   // IMEX: the stored convection vectors follow the velocity levels they were evaluated at
   if (slot == NSFEM_U1 || slot == NSFEM_CONV_N1) ctx->conv_n1_fresh = false;
   if (slot == NSFEM_U2) ctx->conv_n2_valid = false;
+  // (Lagrangian averaging: a constant of level n formed on another u1 is not that of this one; cs2_prev stays -- an
+  // N(u2) that is formed again reads it)
+  if (slot == NSFEM_U1) ctx->dyn.lag.cur_valid = false;
   // ... and on partitioned meshes the ghost entries of a slot written from the host are whatever the caller put there
   if (slot == NSFEM_U1) ctx->u1_ghost_fresh = false;
   if (slot == NSFEM_U2) ctx->u2_ghost_fresh = false;
@@ -2698,6 +2701,75 @@ static const double* dynamic_run(nsfem_ctx* c, const double* u, const double* T 
   return B.field.p;
 }
 
+// ---- Lagrangian averaging of law 8 (nsfem_set_dynamic_averaging mode 1): the constant is state of the time levels
+static bool lagrangian_on(const nsfem_ctx* c) { return c->visc.law == 8 && c->dyn.lag.mode == 1; }
+
+static void lagrangian_reset(nsfem_ctx* c) {
+  nsfem_ctx::Dynamic::Lagrangian& L = c->dyn.lag;
+  L.have_state = L.cur_valid = L.have_prev = false;
+}
+
+// One run in mode 1 on the velocity u: k_dyn_moments, k_dyn_vertex, k_dyn_lagrange -- rules 1 to 5 applied to the
+// stored I with step size k, or the initialisation rule (init, and always while no state exists).  Writes Inew
+// [n_p1][2], cs2 [n_p1] and, where not null, up [n_p1][2]; what of these is stored state is the caller's business.
+// vertex_only: the first two launches alone (the vertex rows in dyn.buf.vert)
+static void lagrangian_run(nsfem_ctx* c, const double* u, double k, bool init, double* Inew, double* cs2, double* up,
+                           bool vertex_only = false) {
+  nsfem_ctx::Dynamic& D = c->dyn;
+  nsfem_ctx::DynamicBuffers& B = D.buf;
+  NSFEM_REQUIRE(lagrangian_on(c) && B.allocated && D.lag.I.p, "dynamic Smagorinsky: Lagrangian averaging is not set");
+  dynamic_alloc(c, B, false);
+  const DynamicDev d{D.n_groups, D.vptr.p, D.vcell.p, D.goff.p, D.gvert.p, B.mom.p, B.vert.p, B.sums.p, cs2};
+  DynamicLagrangeDev l;
+  l.Iold = !init && D.lag.have_state ? D.lag.I.p : nullptr;
+  l.k = k;
+  l.theta = D.lag.theta;
+  l.cs2_init = D.lag.cs2_init;
+  l.cs2_floor = D.lag.cs2_floor;
+  l.Inew = Inew;
+  l.up = up;
+  l.vertex_only = vertex_only;
+  launch_dynamic_constant(c->stream, c->mesh, u, nullptr, c->visc.p[0], c->visc.p[1], d, &l);
+  if (!vertex_only) ++B.runs;
+  B.launches += vertex_only ? 2 : 3;
+}
+
+// The vertex field an explicit vector of mode 1 is formed with.  Level n (u1): cs2_cur, formed ONCE per level by
+// nsfem_step_imex (commit) and kept until nsfem_advance; nsfem_imex_rhs (no commit) reads it where it exists and else
+// applies the rules to the stored I into scratch.  Level n-1 (u2): cs2_prev; without one the initialisation rule on u2
+// into scratch.  Only the committing run writes state
+static const double* lagrangian_level_field(nsfem_ctx* c, const double* u, bool level_n, bool commit) {
+  nsfem_ctx::Dynamic::Lagrangian& L = c->dyn.lag;
+  if (level_n) {
+    if (L.cur_valid) return L.cs2_cur.p;
+    if (commit) {
+      lagrangian_run(c, u, c->k, false, L.Inew.p, L.cs2_cur.p, nullptr);
+      L.cur_valid = true;
+      return L.cs2_cur.p;
+    }
+    lagrangian_run(c, u, c->k, false, L.work.p, c->dyn.buf.field.p, nullptr);
+    return c->dyn.buf.field.p;
+  }
+  if (L.have_prev) return L.cs2_prev.p;
+  lagrangian_run(c, u, c->k, true, L.work.p, c->dyn.buf.field.p, nullptr);
+  return c->dyn.buf.field.p;
+}
+
+// The vertex field the hooks read for a velocity slot (nsfem_viscosity_residual, nsfem_viscosity_cells,
+// nsfem_wall_compute with use_law, nsfem_dynamic_constant).  Mode 0: the procedure on the slot.  Mode 1: the STORED
+// field of the slot's level, never advanced and never formed again -- NSFEM_U2: cs2_prev; the other slots: cs2_cur
+// where formed, else the newest field there is (cs2_prev); where the level has no field at all, the initialisation
+// rule on the slot into scratch, no state written
+static const double* dynamic_slot_field(nsfem_ctx* c, int velocity_slot) {
+  const double* u = c->state[velocity_slot].p;
+  if (!lagrangian_on(c)) return dynamic_run(c, u);
+  nsfem_ctx::Dynamic::Lagrangian& L = c->dyn.lag;
+  if (velocity_slot != NSFEM_U2 && L.cur_valid) return L.cs2_cur.p;
+  if (L.have_prev) return L.cs2_prev.p;
+  lagrangian_run(c, u, c->k, true, L.work.p, c->dyn.buf.field.p, nullptr);
+  return c->dyn.buf.field.p;
+}
+
 // The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u).  The convective part
 // (with the Coriolis vector of the level) is in `n` already -- imex_rhs for u1, imex_form_n2 for u2; this adds the rest,
 // V (nsfem_set_viscosity_law) first and B (nsfem_set_bodies) second, each only when switched on: with law 0 / without
@@ -2709,9 +2781,13 @@ static const double* dynamic_run(nsfem_ctx* c, const double* u, const double* T 
 //   rhs = [ [ -(t + (b0 c_c conv(u1) + b1 N2)) ] - b0 V(u1) ] - b0 B(u1),   the inner bracket as imex_rhs leaves it.
 // level_n: u is the level n (u1; the bodies' pose `cur`), else n-1 (u2; `prev`).  N2 is read as stored (it already
 // holds V(u2) + B(u2)); where it is formed afresh the terms are added the same way with b0 = 0 and rhs = null.
-static void imex_explicit_add(nsfem_ctx* c, const double* u, bool level_n, double b0, double* n, double* rhs) {
+// commit (nsfem_step_imex on u1 alone): with Lagrangian averaging the run that forms the constant of level n keeps it
+static void imex_explicit_add(nsfem_ctx* c, const double* u, bool level_n, bool commit, double b0, double* n,
+                              double* rhs) {
   if (c->visc.law != 0) {
-    const double* cs2v = dynamic_run(c, u);       // (law 8: the constant of THIS level, three launches; else null)
+    // (law 8: the constant of THIS level, three launches -- with Lagrangian averaging the level's stored field, formed
+    // once; else null)
+    const double* cs2v = lagrangian_on(c) ? lagrangian_level_field(c, u, level_n, commit) : dynamic_run(c, u);
     launch_viscosity_cells(c->stream, c->mesh, u, 1.0, c->visc.law, c->visc.p, false, cs2v);
     launch_viscosity_gather(c->stream, c->mesh, b0, n, rhs);
     ++c->visc.launches;
@@ -2729,7 +2805,7 @@ static void imex_form_n2(nsfem_ctx* c, const double* gam2, double* n2) {
   const double cc = cc_of(c);
   NSFEM_HIP(hipMemsetAsync(n2, 0, sizeof(double) * nvel(c), c->stream));
   if (cc != 0.0 || gam2) launch_convection_residual(c->stream, c->mesh, c->state[NSFEM_U2].p, cc, n2, c->conv_form, gam2);
-  imex_explicit_add(c, c->state[NSFEM_U2].p, false, 0.0, n2, nullptr);
+  imex_explicit_add(c, c->state[NSFEM_U2].p, false, false, 0.0, n2, nullptr);
 }
 
 nsfem_ctx::ImexKey nsfem_ctx::ImexKey::of(const nsfem_ctx& c, const double gam[3]) {
@@ -2802,7 +2878,8 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
                                  rot1 ? gam1 : nullptr);
   ++(ctx->imex_last_path == 2 ? ctx->imex_lattice_rhs : ctx->imex_generic_rhs);
   if (rot1) ++ctx->imex_rot.rhs;
-  imex_explicit_add(ctx, ctx->state[NSFEM_U1].p, true, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p, ctx->rhs_v.p);
+  imex_explicit_add(ctx, ctx->state[NSFEM_U1].p, true, true, ctx->imex_beta[0], ctx->state[NSFEM_CONV_N1].p,
+                    ctx->rhs_v.p);
   ctx->conv_n1_fresh = true;
   ctx->conv_key = nsfem_ctx::ImexKey::of(*ctx, gam1);       // (the next step's N2: formed with Omega(t^n))
   {
@@ -2891,7 +2968,7 @@ extern "C" int nsfem_imex_rhs(nsfem_ctx* ctx, int path, int convective_form, dou
   }
   imex_rhs(ctx, path, n2, n1, out, u1_travelled, rot1 ? gam1 : nullptr);
   if (rot1) ++ctx->imex_rot.rhs;
-  imex_explicit_add(ctx, ctx->state[NSFEM_U1].p, true, ctx->imex_beta[0], n1, out);
+  imex_explicit_add(ctx, ctx->state[NSFEM_U1].p, true, false, ctx->imex_beta[0], n1, out);
   NSFEM_HIP(hipMemcpyAsync(rhs, out, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   if (conv_n1) NSFEM_HIP(hipMemcpyAsync(conv_n1, n1, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
   NSFEM_HIP(hipStreamSynchronize(s));
@@ -2967,6 +3044,12 @@ extern "C" int nsfem_set_viscosity_law(nsfem_ctx* ctx, int law, const double par
       if (!ctx->dyn.global) ++v.epoch;
       dynamic_upload_groups(ctx, 1, nullptr);
     }
+    // (... and the averaging back to the groups: the Lagrangian state belonged to the law as it was set before)
+    if (ctx->dyn.lag.mode != 0) {
+      ctx->dyn.lag.mode = 0;
+      lagrangian_reset(ctx);
+      ++v.epoch;
+    }
   }
   // (the stored explicit vectors belong to the law and parameters they were evaluated with; the law enters no
   // captured Krylov body -- its launches precede the solve --, so graph_epoch stays)
@@ -2991,7 +3074,7 @@ extern "C" int nsfem_viscosity_residual(nsfem_ctx* ctx, int velocity_slot, doubl
   const int64_t nv = nvel(ctx);
   hook_to_host(ctx, nv, out_host, [&](double* out) {
     NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
-    const double* cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
+    const double* cs2v = dynamic_slot_field(ctx, velocity_slot);
     launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, weight, ctx->visc.law, ctx->visc.p, false, cs2v);
     launch_viscosity_gather(s, ctx->mesh, 0.0, out, nullptr);
     ++ctx->visc.launches;
@@ -3005,7 +3088,7 @@ extern "C" int nsfem_viscosity_cells(nsfem_ctx* ctx, int velocity_slot, double* 
   viscosity_require(ctx, velocity_slot);
   hipStream_t s = ctx->stream;
   // (the cell means land in the element buffer, which every user fills before it reads)
-  const double* cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
+  const double* cs2v = dynamic_slot_field(ctx, velocity_slot);
   launch_viscosity_cells(s, ctx->mesh, ctx->state[velocity_slot].p, 1.0, ctx->visc.law, ctx->visc.p, true, cs2v);
   ++ctx->visc.launches;
   NSFEM_HIP(hipMemcpyAsync(out_host, ctx->mesh.rbuf.p, sizeof(double) * ctx->mesh.n_cells, hipMemcpyDeviceToHost, s));
@@ -3034,6 +3117,11 @@ extern "C" int nsfem_set_dynamic_groups(nsfem_ctx* ctx, int n_groups, const int3
     NSFEM_REQUIRE(group_of_vertex[v] >= 0 && group_of_vertex[v] < n_groups,
                   "dynamic Smagorinsky: group id out of range");
   nsfem_ctx::Dynamic& D = ctx->dyn;
+  if (D.lag.mode != 0) {             // (groups are mode 0 of nsfem_set_dynamic_averaging)
+    D.lag.mode = 0;
+    lagrangian_reset(ctx);
+    ++ctx->visc.epoch;
+  }
   const bool same = !D.global && D.n_groups == n_groups &&
                     std::memcmp(D.h_group.data(), group_of_vertex, sizeof(int32_t) * (size_t)nv) == 0;
   if (!same) {
@@ -3075,8 +3163,155 @@ extern "C" int nsfem_dynamic_constant(nsfem_ctx* ctx, int velocity_slot, double*
   NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(ctx->visc.law == 8, "dynamic Smagorinsky: law 8 is not set (nsfem_set_viscosity_law)");
   require_velocity_slot(velocity_slot);
+  if (lagrangian_on(ctx)) {
+    // the stored vertex field of the slot's level, [n_p1]; the vertex rows are those of the slot's velocity (two
+    // launches); there are no group sums
+    NSFEM_REQUIRE(!sums, "dynamic Smagorinsky: Lagrangian averaging has no group sums (sums must be NULL)");
+    hipStream_t s = ctx->stream;
+    const size_t nv = (size_t)ctx->mesh.n_p1;
+    const double* field = dynamic_slot_field(ctx, velocity_slot);
+    NSFEM_HIP(hipMemcpyAsync(cs2_groups, field, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+    if (vertices) {
+      lagrangian_run(ctx, ctx->state[velocity_slot].p, ctx->k, true, nullptr, ctx->dyn.buf.field.p, nullptr, true);
+      NSFEM_HIP(hipMemcpyAsync(vertices, ctx->dyn.buf.vert.p, sizeof(double) * nv * 3, hipMemcpyDeviceToHost, s));
+    }
+    NSFEM_HIP(hipStreamSynchronize(s));
+    return NSFEM_OK;
+  }
   dynamic_run(ctx, ctx->state[velocity_slot].p);
   dynamic_read_back(ctx, ctx->dyn.buf, cs2_groups, sums, vertices);
+  API_END(ctx)
+}
+
+// ---- Lagrangian averaging: the setter, the state for restart files, one application as output / test hook
+extern "C" int nsfem_set_dynamic_averaging(nsfem_ctx* ctx, int mode, const double params[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->visc.law == 8, "dynamic Smagorinsky: averaging without law 8 (nsfem_set_viscosity_law)");
+  NSFEM_REQUIRE(mode == 0 || mode == 1, "dynamic Smagorinsky: unknown averaging mode (0 groups, 1 Lagrangian)");
+  nsfem_ctx::Dynamic::Lagrangian& L = ctx->dyn.lag;
+  if (mode == 0) {
+    if (L.mode != 0) {
+      L.mode = 0;
+      lagrangian_reset(ctx);
+      ++ctx->visc.epoch;
+    }
+    return NSFEM_OK;
+  }
+  NSFEM_REQUIRE(params, "dynamic Smagorinsky: Lagrangian averaging needs its parameters");
+  NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] > 0.0, "Lagrangian averaging: theta must be finite and > 0");
+  NSFEM_REQUIRE(std::isfinite(params[1]) && params[1] >= 0.0, "Lagrangian averaging: cs2_init must be finite and >= 0");
+  NSFEM_REQUIRE(std::isfinite(params[2]) && params[2] >= 0.0, "Lagrangian averaging: cs2_floor must be finite and >= 0");
+  NSFEM_REQUIRE(!ctx->sc.dynflux.on,
+                "Lagrangian averaging: the dynamic subgrid heat flux is on (nsfem_set_scalar_sgs_dynamic); a Lagrangian "
+                "C_theta is not supported");
+  const size_t nv = (size_t)ctx->mesh.n_p1;
+  if (!L.I.p) {
+    L.I.alloc(nv * 2);
+    L.Inew.alloc(nv * 2);
+    L.cs2_cur.alloc(nv);
+    L.cs2_prev.alloc(nv);
+    L.work.alloc(nv * 4);
+  }
+  if (L.mode != 1 || L.theta != params[0] || L.cs2_init != params[1] || L.cs2_floor != params[2]) {
+    lagrangian_reset(ctx);
+    ++ctx->visc.epoch;
+  }
+  L.mode = 1;
+  L.theta = params[0];
+  L.cs2_init = params[1];
+  L.cs2_floor = params[2];
+  API_END(ctx)
+}
+
+static void lagrangian_require(nsfem_ctx* ctx) {
+  NSFEM_REQUIRE(!ctx->comm, "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(lagrangian_on(ctx),
+                "dynamic Smagorinsky: Lagrangian averaging is not set (nsfem_set_viscosity_law 8, "
+                "nsfem_set_dynamic_averaging 1)");
+}
+
+extern "C" int nsfem_dynamic_lagrangian_state(nsfem_ctx* ctx, int direction, double* state) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && state, "null argument");
+  lagrangian_require(ctx);
+  NSFEM_REQUIRE(direction == 0 || direction == 1, "Lagrangian state: direction 0 (get) or 1 (set)");
+  nsfem_ctx::Dynamic::Lagrangian& L = ctx->dyn.lag;
+  hipStream_t s = ctx->stream;
+  const size_t nv = (size_t)ctx->mesh.n_p1;
+  std::vector<double> I(nv * 2), cur(nv), prev(nv);
+  if (direction == 0) {
+    const double* level_n = L.cur_valid ? L.cs2_cur.p : L.have_prev ? L.cs2_prev.p : nullptr;
+    if (L.have_state) NSFEM_HIP(hipMemcpyAsync(I.data(), L.I.p, sizeof(double) * nv * 2, hipMemcpyDeviceToHost, s));
+    if (level_n) NSFEM_HIP(hipMemcpyAsync(cur.data(), level_n, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+    if (L.have_prev) NSFEM_HIP(hipMemcpyAsync(prev.data(), L.cs2_prev.p, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+    NSFEM_HIP(hipStreamSynchronize(s));
+    for (size_t v = 0; v < nv; ++v) {               // (NaN: the column does not exist)
+      state[v * 4] = L.have_state ? I[v * 2] : NAN;
+      state[v * 4 + 1] = L.have_state ? I[v * 2 + 1] : NAN;
+      state[v * 4 + 2] = level_n ? cur[v] : NAN;
+      state[v * 4 + 3] = L.have_prev ? prev[v] : NAN;
+    }
+    return NSFEM_OK;
+  }
+  // set: columns 0, 1 (the state of level n-1) and 3 (cs2_prev) count, each taken where none of its entries is NaN and
+  // absent where all are; column 2 is not read -- level n is formed by the next step
+  size_t nan_I = 0, nan_prev = 0;
+  for (size_t v = 0; v < nv; ++v) {
+    nan_I += (std::isnan(state[v * 4]) ? 1 : 0) + (std::isnan(state[v * 4 + 1]) ? 1 : 0);
+    nan_prev += std::isnan(state[v * 4 + 3]) ? 1 : 0;
+  }
+  NSFEM_REQUIRE((nan_I == 0 || nan_I == 2 * nv) && (nan_prev == 0 || nan_prev == nv),
+                "Lagrangian state: a column is either given for every vertex or NaN for every vertex");
+  for (size_t v = 0; v < nv; ++v) {
+    if (nan_I == 0)
+      NSFEM_REQUIRE(std::isfinite(state[v * 4]) && std::isfinite(state[v * 4 + 1]) && state[v * 4 + 1] >= 0.0,
+                    "Lagrangian state: I_LM must be finite and I_MM finite and >= 0");
+    if (nan_prev == 0)
+      NSFEM_REQUIRE(std::isfinite(state[v * 4 + 3]) && state[v * 4 + 3] >= 0.0,
+                    "Lagrangian state: cs2 must be finite and >= 0");
+    I[v * 2] = state[v * 4];
+    I[v * 2 + 1] = state[v * 4 + 1];
+    prev[v] = state[v * 4 + 3];
+  }
+  if (nan_I == 0) NSFEM_HIP(hipMemcpyAsync(L.I.p, I.data(), sizeof(double) * nv * 2, hipMemcpyHostToDevice, s));
+  if (nan_prev == 0) NSFEM_HIP(hipMemcpyAsync(L.cs2_prev.p, prev.data(), sizeof(double) * nv, hipMemcpyHostToDevice, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  L.have_state = nan_I == 0;
+  L.have_prev = nan_prev == 0;
+  L.cur_valid = false;
+  API_END(ctx)
+}
+
+extern "C" int nsfem_dynamic_lagrangian_advance(nsfem_ctx* ctx, int velocity_slot, double k, double* out_state,
+                                                double* out_upstream, double* out_cs2) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_state && out_cs2, "null argument");
+  lagrangian_require(ctx);
+  require_velocity_slot(velocity_slot);
+  NSFEM_REQUIRE(std::isfinite(k) && k > 0.0, "Lagrangian averaging: the step size must be finite and > 0");
+  nsfem_ctx::Dynamic::Lagrangian& L = ctx->dyn.lag;
+  hipStream_t s = ctx->stream;
+  const size_t nv = (size_t)ctx->mesh.n_p1;
+  // (scratch only: work = I' | I_up, buf.field = cs2; the stored I is read, nothing stored is written)
+  lagrangian_run(ctx, ctx->state[velocity_slot].p, k, false, L.work.p, ctx->dyn.buf.field.p, L.work.p + nv * 2);
+  NSFEM_HIP(hipMemcpyAsync(out_state, L.work.p, sizeof(double) * nv * 2, hipMemcpyDeviceToHost, s));
+  if (out_upstream)
+    NSFEM_HIP(hipMemcpyAsync(out_upstream, L.work.p + nv * 2, sizeof(double) * nv * 2, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipMemcpyAsync(out_cs2, ctx->dyn.buf.field.p, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_dynamic_lagrangian_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  const nsfem_ctx::Dynamic::Lagrangian& L = ctx->dyn.lag;
+  out[0] = lagrangian_on(ctx) ? 1 : 0;
+  out[1] = L.have_state ? 1 : 0;
+  out[2] = L.cur_valid ? 1 : 0;
+  out[3] = L.have_prev ? 1 : 0;
   API_END(ctx)
 }
 
@@ -3087,7 +3322,8 @@ extern "C" int nsfem_dynamic_info(nsfem_ctx* ctx, int64_t out[4]) {
   out[0] = D.buf.allocated ? D.n_groups : 0;
   out[1] = D.buf.runs;
   out[2] = D.buf.launches;
-  out[3] = (int64_t)(sizeof(int32_t) * (D.vptr.n + D.vcell.n + D.goff.n + D.gvert.n)) + dynamic_bytes(D.buf);
+  out[3] = (int64_t)(sizeof(int32_t) * (D.vptr.n + D.vcell.n + D.goff.n + D.gvert.n)) + dynamic_bytes(D.buf) +
+           (int64_t)(sizeof(double) * (D.lag.I.n + D.lag.Inew.n + D.lag.cs2_cur.n + D.lag.cs2_prev.n + D.lag.work.n));
   API_END(ctx)
 }
 
@@ -3410,6 +3646,9 @@ extern "C" int nsfem_set_scalar_sgs_dynamic(nsfem_ctx* ctx, int enable, double c
                   "dynamic subgrid heat flux: ctheta_max must be finite and > 0");
     NSFEM_REQUIRE(sc.prandtl_t == 0.0,
                   "dynamic subgrid heat flux: a fixed Pr_t is on (nsfem_set_scalar_sgs); switch it off first");
+    NSFEM_REQUIRE(!lagrangian_on(ctx),
+                  "dynamic subgrid heat flux: Lagrangian averaging is on (nsfem_set_dynamic_averaging); a Lagrangian "
+                  "C_theta is not supported");
   }
   nsfem_ctx::Scalar::DynamicFlux& F = sc.dynflux;
   const bool on = enable != 0;
@@ -3883,6 +4122,18 @@ extern "C" int nsfem_advance(nsfem_ctx* ctx, int scheme) {
   if (scheme == 0 && ctx->pressure_history < 2) ctx->pressure_history++;
   // IMEX: c_c N(u1) of the step becomes c_c N(u2) of the next one
   rotate_stored_vector(ctx, NSFEM_CONV_N1, NSFEM_CONV_N2, ctx->conv_n1_fresh, ctx->conv_n2_valid);
+  // Lagrangian averaging of law 8: I <- I', cs2_prev <- cs2_cur (pointer swaps).  Without a formed level n the old
+  // cs2_prev is no longer that of level n-1; I stays (the memory along the path lines misses that step)
+  if (lagrangian_on(ctx)) {
+    nsfem_ctx::Dynamic::Lagrangian& L = ctx->dyn.lag;
+    if (L.cur_valid) {
+      std::swap(L.I.p, L.Inew.p);
+      std::swap(L.cs2_prev.p, L.cs2_cur.p);
+      L.have_state = true;
+    }
+    L.have_prev = L.cur_valid;
+    L.cur_valid = false;
+  }
   // scalar transport: T2 <- T1 (pointer swap), T1 <- T0 (copy), and the stored convection as above
   if (scheme == 0 && ctx->sc.configured) {
     nsfem_ctx::Scalar& sc = ctx->sc;
@@ -4810,7 +5061,7 @@ extern "C" int nsfem_wall_compute(nsfem_ctx* ctx, int velocity_slot, int pressur
   wp.inv_prt = subgrid && scalar_slot != -1 && ctx->sc.prandtl_t > 0.0 ? 1.0 / ctx->sc.prandtl_t : 0.0;
   hipStream_t s = ctx->stream;
   // (law 8: nu_x of a facet's cell takes the constant of the velocity level the rows are formed on)
-  if (wp.law == 8) wp.cs2v = dynamic_run(ctx, ctx->state[velocity_slot].p);
+  if (wp.law == 8) wp.cs2v = dynamic_slot_field(ctx, velocity_slot);
   // (... and, with the dynamic subgrid heat flux on, the conductive row carries kappa + c_K Delta_K^2 gamma with C_theta
   // of the call's level pair)
   if (wp.law == 8 && scalar_slot != -1 && ctx->sc.dynflux.on)

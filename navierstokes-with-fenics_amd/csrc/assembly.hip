@@ -1344,6 +1344,168 @@ __global__ __launch_bounds__(256) void k_dyn_reduce(const int32_t* __restrict__ 
   for (int i = begin + t; i < end; i += 256) cs2v[gvert[i]] = cs2;
 }
 
+// Lagrangian averaging (nsfem_set_dynamic_averaging mode 1; Meneveau, Lund & Cabot 1996) in the place of k_dyn_reduce:
+// one thread per VERTEX, plain stores, no atomics, no LDS.  The definition is that of include/nsfem.h, rule by rule:
+//   1. d = -k u_v, u_v at the P2 node of v in the first cell of its patch
+//   2. per patch cell (ascending) the barycentric coordinates of x_v + d RELATIVE to v -- lambda_j = grad(lambda_j) . d
+//      for j != i, lambda_i = 1 - their sum --, m_c their minimum; c* the first cell of the largest m_c; m_c* < 0: the
+//      point left the patch, the coordinates are clamped at 0 and divided by their sum
+//   3. I_up = sum_j lambda_j I[p1[c*][j]]
+//   4. eps = k / (k + T), T = theta Delta_v / (I_LM_up I_MM_up)^(1/8) where the product is > 0, else eps = 1;
+//      I_MM' = eps MM_v + (1 - eps) I_MM_up, I_LM' = max(eps LM_v + (1 - eps) I_LM_up, cs2_floor I_MM')
+//   5. cs2_v = min(max(I_LM' / I_MM', 0), cs2_max) where I_MM' > 0, else 0
+//   6. Iold null (no state yet): I_MM = MM_v, I_LM = cs2_init MM_v, cs2_v by 5; the upstream pair is that state
+// Iold and Inew [n_p1][2] = I_LM, I_MM are two buffers: neighbours' old values are read.  mom2: the last two moment
+// rows (|K|, |K| Delta_K^2), [2][n_cells].  up [n_p1][2] may be null.  A vertex of no cell: zeros.  The local index of
+// v in a cell is found by comparison and every array is indexed with compile-time constants (no scratch).
+template <int DIM>
+struct LagrangeGeo;
+template <>
+struct LagrangeGeo<2> {
+  // grad[j][a] = d lambda_j / d x_a: lambda_1 = xi_0, lambda_2 = xi_1, lambda_0 = 1 - xi_0 - xi_1
+  static __device__ __forceinline__ void gradients(const double* __restrict__ vx, int nc, int c, double (&g)[3][2]) {
+#pragma clang fp contract(off)
+    const CellGeo geo = load_geo(vx, nc, c);
+    g[1][0] = geo.ji00;
+    g[1][1] = geo.ji01;
+    g[2][0] = geo.ji10;
+    g[2][1] = geo.ji11;
+    g[0][0] = -(geo.ji00 + geo.ji10);
+    g[0][1] = -(geo.ji01 + geo.ji11);
+  }
+};
+template <>
+struct LagrangeGeo<3> {
+  static __device__ __forceinline__ void gradients(const double* __restrict__ vx, int nc, int c, double (&g)[4][3]) {
+#pragma clang fp contract(off)
+    const CellGeo3 geo = load_geo3(vx, nc, c);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      g[1][a] = geo.ji[0][a];
+      g[2][a] = geo.ji[1][a];
+      g[3][a] = geo.ji[2][a];
+      g[0][a] = -((geo.ji[0][a] + geo.ji[1][a]) + geo.ji[2][a]);
+    }
+  }
+};
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_dyn_lagrange(int nv, int nc, const int32_t* __restrict__ vptr,
+                                                      const int32_t* __restrict__ vcell,
+                                                      const int32_t* __restrict__ p1, const int32_t* __restrict__ p2,
+                                                      const double* __restrict__ vx, const double* __restrict__ u,
+                                                      const double* __restrict__ mom2, const double* __restrict__ vert,
+                                                      const double* __restrict__ Iold, double k, double theta,
+                                                      double cs2_init, double cs2_floor, double cs2_max,
+                                                      double* __restrict__ Inew, double* __restrict__ cs2v,
+                                                      double* __restrict__ up) {
+#pragma clang fp contract(off)
+  constexpr int NL = DIM + 1;
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nv) return;
+  const int begin = vptr[v], end = vptr[v + 1];
+  double W = 0.0, D = 0.0;
+  for (int e = begin; e < end; ++e) {
+    const int c = vcell[e];
+    W += mom2[c];
+    D += mom2[(size_t)nc + c];
+  }
+  double ilm = 0.0, imm = 0.0, ulm = 0.0, umm = 0.0;
+  if (W > 0.0) {
+    const double lm = vert[(size_t)v * 3 + 1], mm = vert[(size_t)v * 3 + 2];
+    if (!Iold) {
+      imm = mm;
+      ilm = cs2_init * mm;
+      ulm = ilm;
+      umm = imm;
+    } else {
+      const double delta2 = D / W;
+      // 1. the displacement
+      double d[DIM];
+      {
+        const int c0 = vcell[begin];
+        int node = p2[c0];
+#pragma unroll
+        for (int j = 1; j < NL; ++j)
+          if (p1[(size_t)j * nc + c0] == v) node = p2[(size_t)j * nc + c0];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) d[a] = -(k * u[(size_t)node * DIM + a]);
+      }
+      // 2. the upstream cell
+      double best = -INFINITY, lam[NL];
+      int vb[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) {
+        lam[j] = 0.0;
+        vb[j] = v;
+      }
+      for (int e = begin; e < end; ++e) {
+        const int c = vcell[e];
+        double g[NL][DIM];
+        LagrangeGeo<DIM>::gradients(vx, nc, c, g);
+        int vc[NL];
+        double l[NL], s = 0.0;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          vc[j] = p1[(size_t)j * nc + c];
+          double t = 0.0;
+#pragma unroll
+          for (int a = 0; a < DIM; ++a) t += g[j][a] * d[a];
+          l[j] = vc[j] == v ? 0.0 : t;           // (its own entry adds +0.0 to the sum, which changes no bit of it)
+          s += l[j];
+        }
+        const double own = 1.0 - s;
+        double m = INFINITY;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          if (vc[j] == v) l[j] = own;
+          m = fmin(m, l[j]);
+        }
+        if (m > best) {
+          best = m;
+#pragma unroll
+          for (int j = 0; j < NL; ++j) {
+            lam[j] = l[j];
+            vb[j] = vc[j];
+          }
+        }
+      }
+      if (best < 0.0) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < NL; ++j) {
+          lam[j] = fmax(lam[j], 0.0);
+          s += lam[j];
+        }
+#pragma unroll
+        for (int j = 0; j < NL; ++j) lam[j] /= s;
+      }
+      // 3. the upstream value
+#pragma unroll
+      for (int j = 0; j < NL; ++j) {
+        const double2 I = reinterpret_cast<const double2*>(Iold)[vb[j]];
+        ulm += lam[j] * I.x;
+        umm += lam[j] * I.y;
+      }
+      // 4. the relaxation
+      const double prod = ulm * umm;
+      double eps = 1.0;
+      if (prod > 0.0) {
+        const double T = (theta * sqrt(delta2)) / sqrt(sqrt(sqrt(prod)));
+        eps = k / (k + T);
+      }
+      const double keep = 1.0 - eps;
+      imm = eps * mm + keep * umm;
+      ilm = fmax(eps * lm + keep * ulm, cs2_floor * imm);
+    }
+  }
+  // 5. the constant
+  const double cs2 = imm > 0.0 ? fmin(fmax(ilm / imm, 0.0), cs2_max) : 0.0;
+  reinterpret_cast<double2*>(Inew)[v] = make_double2(ilm, imm);
+  cs2v[v] = cs2;
+  if (up) reinterpret_cast<double2*>(up)[v] = make_double2(ulm, umm);
+}
+
 template <int DIM>
 __global__ void k_dyn_scalar_moments(int nc, const double* __restrict__ vx, const int32_t* __restrict__ p2,
                                      const double* __restrict__ u, const double* __restrict__ T,
@@ -1424,10 +1586,14 @@ __global__ __launch_bounds__(256) void k_dyn_scalar_vertex(int nv, int nc, const
 }
 
 // T null: C_s^2 on u (k_dyn_moments, k_dyn_vertex); else C_theta on (u, T) (the k_dyn_scalar_ pair)
+// lag given (mode 1 of nsfem_set_dynamic_averaging, T null): k_dyn_lagrange in the place of k_dyn_reduce; with
+// lag->vertex_only the third launch is left out (the vertex rows alone, for the output hook)
 void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
-                             double clip, const DynamicDev& d) {
+                             double clip, const DynamicDev& d, const DynamicLagrangeDev* lag) {
   NSFEM_REQUIRE(d.n_groups >= 1 && d.vptr && d.vcell && d.goff && d.gvert && d.mom && d.vert && d.sums && d.cs2v,
                 T ? "dynamic subgrid heat flux: buffers not allocated" : "dynamic Smagorinsky: buffers not allocated");
+  NSFEM_REQUIRE(!lag || (!T && (lag->vertex_only || (lag->Inew && lag->Inew != lag->Iold))),
+                "dynamic Smagorinsky: Lagrangian averaging needs two state buffers and no scalar");
   const dim3 cells(grid_for(m.n_cells)), verts(grid_for(m.n_p1)), block(kBlock);
   if (m.dim == 3) dynamic_moments_3d(s, m, u, T, d.mom);
   else if (T) hipLaunchKernelGGL((k_dyn_scalar_moments<2>), cells, block, 0, s, m.n_cells, m.vx.p, m.p2.p, u, T, d.mom);
@@ -1437,7 +1603,17 @@ void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, c
     const auto vertex = T ? k_dyn_scalar_vertex<DIM> : k_dyn_vertex<DIM>;
     hipLaunchKernelGGL(vertex, verts, block, 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell, d.mom, alpha * alpha, d.vert);
   });
-  hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, clip, d.sums, d.cs2v);
+  if (!lag) {
+    hipLaunchKernelGGL(k_dyn_reduce, dim3(d.n_groups), dim3(256), 0, s, d.goff, d.gvert, d.vert, clip, d.sums, d.cs2v);
+  } else if (!lag->vertex_only) {
+    with_int<3, 2>(m.dim, [&](auto dc) {
+      constexpr int DIM = decltype(dc)::value;
+      const double* mom2 = d.mom + (size_t)(dynamic_moment_rows(DIM, false) - 2) * m.n_cells;
+      hipLaunchKernelGGL(k_dyn_lagrange<DIM>, verts, dim3(256), 0, s, m.n_p1, m.n_cells, d.vptr, d.vcell, m.p1.p, m.p2.p,
+                         m.vx.p, u, mom2, d.vert, lag->Iold, lag->k, lag->theta, lag->cs2_init, lag->cs2_floor, clip,
+                         lag->Inew, d.cs2v, lag->up);
+    });
+  }
   NSFEM_HIP(hipGetLastError());
 }
 

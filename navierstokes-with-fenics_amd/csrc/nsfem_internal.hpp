@@ -534,8 +534,18 @@ struct DynamicDev {
   const int32_t *vptr = nullptr, *vcell = nullptr, *goff = nullptr, *gvert = nullptr;
   double *mom = nullptr, *vert = nullptr, *sums = nullptr, *cs2v = nullptr;
 };
+// Lagrangian averaging (nsfem_set_dynamic_averaging mode 1): k_dyn_lagrange<DIM> in the place of k_dyn_reduce -- one
+// application of rules 1 to 5 of include/nsfem.h to the state Iold [n_p1][2] = I_LM, I_MM of the level before (null:
+// the initialisation rule), step size k; writes Inew (another buffer), the vertex field d.cs2v and, where up is not
+// null, the upstream pair [n_p1][2].  vertex_only: the first two launches alone (the vertex rows for the output hook)
+struct DynamicLagrangeDev {
+  const double* Iold = nullptr;
+  double k = 0.0, theta = 1.5, cs2_init = 0.0256, cs2_floor = 1e-12;
+  double *Inew = nullptr, *up = nullptr;
+  bool vertex_only = false;
+};
 void launch_dynamic_constant(hipStream_t s, const MeshDev& m, const double* u, const double* T, double alpha,
-                             double clip, const DynamicDev& d);
+                             double clip, const DynamicDev& d, const DynamicLagrangeDev* lag = nullptr);
 void dynamic_moments_3d(hipStream_t s, const MeshDev& m, const double* u, const double* T, double* mom);
 // rows of mom: DIM + 3 NS + 2 on u (13 | 23), 1 + 4 DIM + NS + 2 on (u, T) (14 | 21), NS = DIM (DIM + 1) / 2
 constexpr int dynamic_moment_rows(int dim, bool with_T) {
@@ -1336,6 +1346,18 @@ struct nsfem_ctx {
     std::vector<int32_t> h_group;                   // [n_p1], what nsfem_set_dynamic_groups took (empty: global)
     nsfem::DevBuf<int32_t> vptr, vcell, goff, gvert;
     DynamicBuffers buf;
+    // Lagrangian averaging (nsfem_set_dynamic_averaging mode 1): the constant is STATE that lives with the velocity
+    // slots.  I = (I_LM, I_MM) of level n-1 (have_state); Inew and cs2_cur of level n, formed once by nsfem_step_imex
+    // (cur_valid) and rotated by nsfem_advance (I <- Inew, cs2_prev <- cs2_cur, have_prev); buf.field is the scratch
+    // of the runs that write no state (an N(u2) without cs2_prev, nsfem_imex_rhs, the hooks), work [n_p1][4] that of
+    // nsfem_dynamic_lagrangian_advance.  Allocated by the first call of the setter with mode 1 and kept; a context
+    // that never makes that call allocates nothing
+    struct Lagrangian {
+      int mode = 0;
+      double theta = 1.5, cs2_init = 0.0256, cs2_floor = 1e-12;
+      bool have_state = false, cur_valid = false, have_prev = false;
+      nsfem::DevBuf<double> I, Inew, cs2_cur, cs2_prev, work;
+    } lag;
   } dyn;
   // immersed bodies (nsfem_set_bodies): with bodies the stored vectors carry B(u) as well.  `cur` is the pose of t^n,
   // `prev` that of t^(n-1) (nsfem_move_bodies shifts cur to prev; without a move they are equal): a stored N(u2) was

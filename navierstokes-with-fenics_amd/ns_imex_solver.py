@@ -85,13 +85,19 @@ class IMEXIPCSSolver(InstationarySolverBase):
                 if hasattr(model, "vertex_groups"):
                     # the dynamic model: the law first (which resets the groups), then its groups -- and only when
                     # something changed, since a push of other groups invalidates the stored explicit vectors
+                    # (Lagrangian averaging: the law, then the mode -- setting the law anew would reset its state)
+                    lagrangian = getattr(model, "lagrangian", False)
                     n_groups, ids = model.vertex_groups(self._dofmap.p1_coords)
-                    pushed = (id(self._ctx), params, n_groups, ids.tobytes())
+                    pushed = (id(self._ctx), params, n_groups, ids.tobytes(),
+                              tuple(model.averaging_params()) if lagrangian else None)
                     if getattr(self, "_pushed_dynamic", None) == pushed and \
                             self._ctx.viscosity_info()["law"] == model.law_id:
                         return
                     self._ctx.set_viscosity_law(model.law_id, params)
-                    self._ctx.set_dynamic_groups(n_groups, ids)
+                    if lagrangian:
+                        self._ctx.set_dynamic_averaging(1, *model.averaging_params())
+                    else:
+                        self._ctx.set_dynamic_groups(n_groups, ids)
                     self._pushed_dynamic = pushed
                 else:
                     self._ctx.set_viscosity_law(model.law_id, params)
@@ -101,6 +107,24 @@ class IMEXIPCSSolver(InstationarySolverBase):
     def _push_coefficients(self):
         super()._push_coefficients()
         self._push_viscosity_model()
+
+    def dynamic_lagrangian_state(self):
+        """the state of ``DynamicSmagorinskyModel(averaging="lagrangian")`` for a restart file, [n_p1, 4]
+        (``nsfem_dynamic_lagrangian_state``); it goes beside the velocity levels and the stored explicit vector"""
+        return self._ctx.dynamic_lagrangian_state()
+
+    def set_dynamic_lagrangian_state(self, state):
+        """restore what ``dynamic_lagrangian_state`` returned.  The model must be on the device already (set and
+        pushed with the equation coefficients): RuntimeError otherwise, since a later push of the law would drop the
+        restored state.  A push happens again only when the model's parameters change -- which resets the state by
+        definition -- so restore after the coefficients are final"""
+        if not (hasattr(self, "_ctx") and self._ctx.dynamic_lagrangian_info()["active"]):
+            raise RuntimeError("set_dynamic_lagrangian_state: no DynamicSmagorinskyModel(averaging=\"lagrangian\") is "
+                               "active on the device; set the model and the equation coefficients first")
+        try:
+            self._ctx.set_dynamic_lagrangian_state(state)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
 
     def set_immersed_bodies(self, bodies, allow_stiff=False):
         """an ``immersed_bodies.ImmersedBodies`` or None for none.  The penalisation term is explicit: a step with

@@ -425,7 +425,8 @@ class ProblemBase:
 
     def _compute_model_constant(self):
         """C_s^2 of every averaging group of a ``DynamicSmagorinskyModel`` for the current velocity, from the device
-        (nsfem_dynamic_constant), [n_groups] in the order of the model's ``vertex_groups``.  New helper."""
+        (nsfem_dynamic_constant), [n_groups] in the order of the model's ``vertex_groups``; with
+        ``averaging="lagrangian"`` the stored vertex field of the newest level, [n_p1].  New helper."""
         import _native as nat
         try:
             return self._get_solver()._ctx.dynamic_constant(nat.U0)

@@ -108,21 +108,27 @@ class DynamicSmagorinskyModel:
     ``nsfem_set_viscosity_law``): test filter over the vertex patches of width ``filter_ratio`` > 1 times the grid
     filter, least squares over averaging groups of vertices, clipped to [0, ``cs2_max``].  ``averaging``: "global" (one
     group of all vertices) or ("planes", axis) -- one group per set of vertices of equal coordinate along ``axis``, for
-    a channel.  ``heat_flux``: None -- the scalar sees its molecular diffusivity alone -- or "dynamic": a solver with a
+    a channel -- or "lagrangian": LM and MM averaged along fluid path lines with an exponential memory (Meneveau, Lund &
+    Cabot 1996; ``nsfem_set_dynamic_averaging``), which needs no homogeneous direction: the constant is a vertex field
+    and state of the time levels.  ``relaxation`` > 0 is theta of the memory time T = theta Delta (I_LM I_MM)^(-1/8),
+    ``cs2_init`` >= 0 the ratio I_LM / I_MM the state starts from and ``cs2_floor`` >= 0 the ratio it is kept above;
+    the three are read in this mode only.  ``heat_flux``: None -- the scalar sees its molecular diffusivity alone -- or "dynamic": a solver with a
     transported scalar (``BoussinesqIMEXSolver``) adds the subgrid heat flux with the eddy diffusivity kappa_x = c_K
     Delta_K^2 gamma, its constant C_theta from the Germano identity of the scalar flux over the same groups, clipped to
-    [0, ``ctheta_max``] (``nsfem_set_scalar_sgs_dynamic``).  No fixed Pr_t goes with this model (``prandtl_t`` is
+    [0, ``ctheta_max``] (``nsfem_set_scalar_sgs_dynamic``); refused with "lagrangian" (there is no Lagrangian
+    C_theta).  No fixed Pr_t goes with this model (``prandtl_t`` is
     None): Pr_t = C_s^2 / C_theta is an output."""
     law_id = LAW_DYNAMIC
     prandtl_t = None
 
-    def __init__(self, averaging="global", filter_ratio=2.0, cs2_max=0.09, heat_flux=None, ctheta_max=0.2):
-        if averaging != "global":
+    def __init__(self, averaging="global", filter_ratio=2.0, cs2_max=0.09, heat_flux=None, ctheta_max=0.2,
+                 relaxation=1.5, cs2_init=0.0256, cs2_floor=1e-12):
+        if averaging not in ("global", "lagrangian"):
             ok = isinstance(averaging, (tuple, list)) and len(averaging) == 2 and averaging[0] == "planes"
             ok = ok and isinstance(averaging[1], (int, )) and not isinstance(averaging[1], bool) and 0 <= averaging[1] <= 2
             if not ok:
-                raise ValueError('DynamicSmagorinskyModel: averaging must be "global" or ("planes", axis) with axis 0, '
-                                 "1 or 2, got %r" % (averaging, ))
+                raise ValueError('DynamicSmagorinskyModel: averaging must be "global", "lagrangian" or ("planes", axis) '
+                                 "with axis 0, 1 or 2, got %r" % (averaging, ))
             averaging = ("planes", int(averaging[1]))
         filter_ratio, cs2_max = float(filter_ratio), float(cs2_max)
         if not (math.isfinite(filter_ratio) and filter_ratio > 1.0):
@@ -136,18 +142,36 @@ class DynamicSmagorinskyModel:
         ctheta_max = float(ctheta_max)
         if not (math.isfinite(ctheta_max) and ctheta_max > 0.0):
             raise ValueError("DynamicSmagorinskyModel: ctheta_max must be finite and > 0, got %r" % (ctheta_max, ))
+        for name, value in (("relaxation", relaxation), ("cs2_init", cs2_init), ("cs2_floor", cs2_floor)):
+            if isinstance(value, bool) or not math.isfinite(float(value)) or float(value) < 0.0 or \
+                    (name == "relaxation" and float(value) == 0.0):
+                raise ValueError("DynamicSmagorinskyModel: %s must be finite and %s 0, got %r"
+                                 % (name, ">" if name == "relaxation" else ">=", value))
+        if averaging == "lagrangian" and heat_flux == "dynamic":
+            raise ValueError('DynamicSmagorinskyModel: heat_flux="dynamic" does not go with averaging="lagrangian" '
+                             "(a Lagrangian C_theta is not supported)")
         self.averaging, self.filter_ratio, self.cs2_max = averaging, filter_ratio, cs2_max
         self.heat_flux, self.ctheta_max = heat_flux, ctheta_max
+        self.relaxation, self.cs2_init, self.cs2_floor = float(relaxation), float(cs2_init), float(cs2_floor)
 
     def params(self, coefficients=None):
         return (self.filter_ratio, self.cs2_max, 0.0, 0.0)
 
+    @property
+    def lagrangian(self):
+        return self.averaging == "lagrangian"
+
+    def averaging_params(self):
+        """(theta, cs2_init, cs2_floor) of ``nsfem_set_dynamic_averaging`` mode 1"""
+        return (self.relaxation, self.cs2_init, self.cs2_floor)
+
     def vertex_groups(self, coordinates):
         """(n_groups, ids [n_vertices]) for the vertices at ``coordinates`` [n, dim]: planes in ascending coordinate,
-        by the binning of ``flow_statistics.groups_along_axis``"""
+        by the binning of ``flow_statistics.groups_along_axis``.  "lagrangian" has no groups: the global one, which
+        the device keeps beside the mode and does not read"""
         import numpy as np
         coordinates = np.asarray(coordinates, dtype=np.float64)
-        if self.averaging == "global":
+        if self.averaging in ("global", "lagrangian"):
             return 1, np.zeros(coordinates.shape[0], dtype=np.int32)
         axis = self.averaging[1]
         if axis >= coordinates.shape[1]:
