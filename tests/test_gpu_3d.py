@@ -2,7 +2,11 @@
 small): the 3D element kernels (csrc/assembly3d.hip), the 3x3 / 1x3 / 3x1 block SpMV
 instantiations and the IPCS / monolithic steps against the dimension-generic oracle, which is
 pinned in 3D by sympy-exact tetrahedron matrices and a polynomial Stokes solution
-(tests/test_oracle_pinning.py).  The reference never exercises its 3D branches."""
+(tests/test_oracle_pinning.py).  The reference never exercises its 3D branches.
+
+The constant operators and, form by form, the momentum residual, Jacobian and Newton update
+also run on the 72 general tetrahedra of tests/general_tet_mesh.py: cells of both orientations and
+of different volumes, no zero in any J^-1."""
 import numpy as np
 import pytest
 
@@ -49,8 +53,26 @@ def setup3():
     ctx.close()
 
 
+@pytest.fixture(scope="module")
+def setup_general():
+    from general_tet_mesh import SMALL, general_tets
+    mesh, dm, marks = general_tets(*SMALL)
+    ctx = context3(mesh, dm)
+    s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+    yield mesh, dm, marks, ctx, s
+    ctx.close()
+
+
 def test_3d_constant_operators_and_spmv(setup3):
-    _, dm, _, ctx, s = setup3
+    _constant_operators_case(setup3)
+
+
+def test_3d_constant_operators_and_spmv_on_general_tetrahedra(setup_general):
+    _constant_operators_case(setup_general)
+
+
+def _constant_operators_case(setup):
+    _, dm, _, ctx, s = setup
     pairs = [(nat.OP_MASS_P2, s.mass_p2()), (nat.OP_STIFF_P2, s.stiffness_p2()),
              (nat.OP_STIFF_P1, s.stiffness_p1()), (nat.OP_MASS_P1, s.mass_p1()),
              (nat.OP_DIV, s.divergence()), (nat.OP_GRAD, s.pressure_gradient()),
@@ -67,7 +89,17 @@ def test_3d_constant_operators_and_spmv(setup3):
 @pytest.mark.parametrize("form_id,form", [(0, "standard"), (1, "rotational"), (2, "divergence"),
                                           (3, "skew_symmetric")])
 def test_3d_momentum_residual_jacobian_and_newton_update(setup3, form_id, form):
-    _, dm, marks, ctx, s = setup3
+    _momentum_case(setup3, form_id, form)
+
+
+@pytest.mark.parametrize("form_id,form", [(0, "standard"), (1, "rotational"), (2, "divergence"),
+                                          (3, "skew_symmetric")])
+def test_3d_momentum_residual_jacobian_and_newton_update_on_general_tetrahedra(setup_general, form_id, form):
+    _momentum_case(setup_general, form_id, form)
+
+
+def _momentum_case(setup, form_id, form):
+    _, dm, marks, ctx, s = setup
     rng = np.random.default_rng(5)
     Re, k, alpha = 20.0, 0.05, (1.5, -2.0, 0.5)
     u = [rng.standard_normal(dm.n_velocity) for _ in range(4)]

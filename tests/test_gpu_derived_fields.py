@@ -12,7 +12,9 @@ restatement evaluates the basis gradients at every point itself -- two routes to
 
 Meshes: the smallest that take each path -- 48 cells (less than one wave), 768 cells (three workgroups, a ragged last
 one), two tetrahedral boxes (24-byte node stride), the unstructured fixture (runs of uneven length in the node index)
-and the periodic square (identified nodes)."""
+and the periodic square (identified nodes).  The general tetrahedra of tests/general_tet_mesh.py with 72 and 384 cells:
+cells of both orientations and of different volumes (the NODE weights |K| differ around a node), no zero in any
+J^-1 (every entry of it takes part in every G_ab), irregular runs of cells around the nodes."""
 import os
 
 import numpy as np
@@ -20,6 +22,7 @@ import pytest
 
 import _native as nat
 from fem_mesh import TaylorHoodDofMap, box_mesh, rectangle_mesh
+from general_tet_mesh import CUBE, SMALL, general_tets
 from gpu_common import context
 from test_derived_fields_host import (CENTERS, QUANTITIES, analytic, derived_bound, derived_reference,
                                       polynomial_fields, polynomial_nodal, smooth_fields)
@@ -27,8 +30,8 @@ from test_flow_statistics_host import periodic_square
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-MESHES = ("rect6x4", "rect24x16", "box3x2x2", "box4x4x4", "fixture", "periodic")
-EXPECTED_CELLS = dict(rect6x4=48, rect24x16=768, box3x2x2=72, box4x4x4=384)
+MESHES = ("rect6x4", "rect24x16", "box3x2x2", "box4x4x4", "fixture", "periodic", "general72", "general384")
+EXPECTED_CELLS = dict(rect6x4=48, rect24x16=768, box3x2x2=72, box4x4x4=384, general72=72, general384=384)
 CENTER_NAMES = {nat.DERIVED_CELL: "CELL", nat.DERIVED_VERTEX: "VERTEX", nat.DERIVED_NODE: "NODE"}
 _CACHE = {}
 
@@ -47,6 +50,8 @@ def _mesh(name):
         mesh = read_msh(os.path.join(HERE, "golden", "square_v41.msh"))[0]
     elif name == "periodic":
         return periodic_square(8)
+    elif name in ("general72", "general384"):
+        return general_tets(*(SMALL if name == "general72" else CUBE))[:2]
     else:
         raise ValueError(name)
     return mesh, TaylorHoodDofMap(mesh)
@@ -105,7 +110,7 @@ def test_every_quantity_at_every_centre_equals_the_restatement(name):
     assert not failures, failures
 
 
-@pytest.mark.parametrize("name", ["rect6x4", "box3x2x2", "fixture"])
+@pytest.mark.parametrize("name", ["rect6x4", "box3x2x2", "fixture", "general72", "general384"])
 def test_polynomial_fields_are_reproduced(name):
     """quadratic velocity, linear pressure, quadratic scalar: G is linear, every centre returns the analytic values"""
     ref = reference(name)

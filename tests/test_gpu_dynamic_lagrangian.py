@@ -21,7 +21,12 @@ Tolerances.
 The choice of the upstream cell is discrete: ``_advance_case`` asserts on the restatement alone that at every clamped
 vertex the best and the second-best m_c differ by more than 1e-9 (inside the patch a tie is harmless: P1 interpolation
 is continuous across faces); the seeds of ``_SEEDS`` were searched on the CPU so that every vertex of every case
-passes."""
+passes.  On the general tetrahedra of tests/general_tet_mesh.py the interior patches are generic: the advance cases
+assert first that NO displaced vertex, clamped or not, has a second cell within the restatement's tie margin of the
+best -- the upstream cell is unique there, and the choice of the definition is the only one accepted.  The boundary
+nodes are at rest in these cases: on four of the six faces the map of the mesh is a sum of functions of one surface
+coordinate each, so the two triangles of a boundary quad stay in one plane and an inflow vertex there meets the same
+exact tie as on a Kuhn box (tests/test_general_tet_mesh_host.py counts them)."""
 import math
 
 import numpy as np
@@ -34,18 +39,19 @@ from gpu_common import rel
 from imex_composed_host import ComposedIMEX
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from test_gpu_dynamic_model import CUBE, KUHN, _SPEC, _les, _step_setup
-from test_gpu_variable_viscosity import _COEF, NO_PBC, _mesh, _opts
+from test_gpu_variable_viscosity import _COEF, GENERAL72, GENERAL384, NO_PBC, _mesh, _opts, is_general
 from test_variable_viscosity_host import SMAGORINSKY
 from viscosity_models import DynamicSmagorinskyModel
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE]
+_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384]
 _CFLS = (0.4, 2.5)
 _SEEDS = {}                                            # (kind, cfl) -> seed; default 0
 # the mean direction of the seeded velocity of the advance cases (see ``_velocity``)
-_DIRECTION = {str(KUHN): (1.0, -0.738, -0.401), str(CUBE): (-1.0, 0.596, 0.978)}
+_DIRECTION = {str(KUHN): (1.0, -0.738, -0.401), str(CUBE): (-1.0, 0.596, 0.978),
+              str(GENERAL72): (1.0, -0.738, -0.401), str(GENERAL384): (-1.0, 0.596, 0.978)}
 _SLOTS = (nat.U0, nat.U1, nat.U2, nat.USTAR, nat.CONV_N1, nat.CONV_N2)
 NAN = float("nan")
 
@@ -85,10 +91,16 @@ def _velocity(kind, dm, rng):
     of several cells is the same number -- and the clamped values of tied cells differ: the definition settles them by
     the order of the cells, a comparison of roundings that no tolerance covers.  The directions of ``_DIRECTION`` were
     searched on the CPU so that the interior vertices leave their patches at CFL 2.5 through no such pair.  The inflow
-    boundaries of the Kuhn boxes have a test of their own, which accepts the choice of any tied cell"""
+    boundaries of the Kuhn boxes have a test of their own, which accepts the choice of any tied cell.  General
+    tetrahedra: the direction of the Kuhn box of the same size and 5 % noise at every interior node, zero at the nodes
+    of the boundary faces (module docstring)"""
     X = dm.p2_coords
     if dm.dim == 2:
         return (np.array([0.3, 1.0])[None, :] + 0.1 * rng.standard_normal((dm.n_p2, 2))).ravel()
+    if is_general(kind):
+        u = np.array(_DIRECTION[str(kind)])[None, :] + 0.05 * rng.standard_normal((dm.n_p2, 3))
+        u[np.unique(dm.facet_p2_nodes(np.flatnonzero(dm.mesh.facet_on_boundary)))] = 0.0
+        return u.ravel()
     bubble = np.prod(np.sin(np.pi * X / X.max(axis=0)[None, :]), axis=1) ** 0.5
     bubble[bubble < 1e-7] = 0.0
     return ((np.array(_DIRECTION[str(kind)])[None, :] + 0.05 * rng.standard_normal((dm.n_p2, 3))) * bubble[:, None]).ravel()
@@ -108,6 +120,13 @@ def _advance_case(kind, cfl):
         _, _, where = orc.locate(orc.vertex_velocity(u), k)
         gap = (where["best"] - where["second"])[where["clamped"]]
         assert gap.size == 0 or gap.min() > 1e-9, (key, gap.min())
+        if is_general(kind):
+            # generic patches: the upstream cell of every displaced vertex is unique (``tied`` counts the best cell
+            # itself); the others are the boundary vertices, at rest
+            moved = np.abs(orc.vertex_velocity(u)).max(axis=1) > 0.0
+            assert moved.sum() >= 2 and not where["clamped"][~moved].any()
+            assert np.all(where["tied"][moved] == 1), (key, np.bincount(where["tied"][moved]))
+            assert (where["best"] - where["second"])[moved].min() > 1e-9
         _ADVANCE[key] = (u, state, k, orc, where)
     return _ADVANCE[key]
 

@@ -21,7 +21,11 @@ Fields.  ``_sines``: every entry of G non-zero, for the procedure.  ``_les``: th
 tests -- in 2D a superposition of stream functions sin^2(k pi x) sin^2(l pi y) (no-slip traces), in 3D a perturbed
 Taylor-Green vortex; found by a search over a few seeded superpositions on the CPU (smooth solenoidal 2D fields have a
 vanishing leading order of L : M, most give a negative constant), written here with their coefficients.  ``_linear``:
-u = A x plus 5 % of ``_sines`` with alpha = 1.1, for which every group is clipped at cs2_max = 0.0625."""
+u = A x plus 5 % of ``_sines`` with alpha = 1.1, for which every group is clipped at cs2_max = 0.0625.
+
+Meshes.  Beside the 2D boxes and the Kuhn boxes, the general tetrahedra of tests/general_tet_mesh.py with 72 and 384
+cells, with the global group (there are no planes): the patch volumes differ, so the volume-weighted patch means are
+not the unweighted ones, and a moment read from the wrong cell is a wrong moment."""
 import math
 
 import numpy as np
@@ -32,7 +36,7 @@ from dynamic_model_host import DYNAMIC, DynamicSmagorinskyRestatement
 from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from test_gpu_3d import lid_bc
-from test_gpu_variable_viscosity import _COEF, NO_PBC, _max_rel, _mesh, _opts
+from test_gpu_variable_viscosity import _COEF, GENERAL72, GENERAL384, NO_PBC, _max_rel, _mesh, _opts, is_general
 from test_variable_viscosity_host import SMAGORINSKY, IMEXViscRestatement, VariableViscosityRestatement
 from viscosity_models import DynamicSmagorinskyModel
 
@@ -41,7 +45,7 @@ pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -53
 KUHN = ((3, 2, 2), (1.0, 0.8, 0.6))
 CUBE = ((4, 4, 4), (1.0, 1.0, 1.0))
-_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE]
+_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384]
 _N_VERTEX = {2: 80, 3: 160}
 _SLOTS = (nat.U0, nat.U1, nat.U2, nat.USTAR, nat.CONV_N1, nat.CONV_N2)
 
@@ -90,6 +94,8 @@ def _groups(dm, grouping):
 
 
 def _groupings(kind):
+    if is_general(kind):
+        return ["global"]
     dim = 2 if kind == "mapped" or isinstance(kind[0], int) else 3
     return ["global"] + [("planes", a) for a in range(dim)]
 
@@ -123,6 +129,8 @@ def test_procedure_matches_the_restatement(kind, grouping):
     dim = dm.dim
     g = orc.group
     assert np.abs(orc.gradient(u)).max(axis=(0, 1)).min() > 0.1              # (every entry of G takes part)
+    if is_general(kind):
+        assert orc.vol.max() > 3.0 * orc.vol.min()                           # (weighted patch means are not plain ones)
     n_v = _N_VERTEX[dim]
     bound_v = 2.0 * n_v * EPS * vert_abs
     counts = np.bincount(g, minlength=orc.n_groups)
@@ -156,7 +164,8 @@ def test_procedure_matches_the_restatement(kind, grouping):
 
 # ---------------------------------------------------------------- 2. the element kernel against the restatement
 # grouping of the kernel cases: one for which the restatement gives positive constants in some groups (asserted)
-_KERNEL_GROUPING = {(4, 4): ("planes", 1), (3, 5): ("planes", 1), "mapped": "global", KUHN: ("planes", 0), CUBE: ("planes", 1)}
+_KERNEL_GROUPING = {(4, 4): ("planes", 1), (3, 5): ("planes", 1), "mapped": "global", KUHN: ("planes", 0), CUBE: ("planes", 1),
+                    GENERAL72: "global", GENERAL384: "global"}
 
 
 @pytest.mark.parametrize("kind", _MESHES, ids=str)
@@ -431,7 +440,7 @@ def test_stored_vector_follows_law_groups_and_alpha_and_law_zero_returns_to_the_
 
 
 # ---------------------------------------------------------------- 7. the wall rows
-@pytest.mark.parametrize("name", ["box4x4", "kuhn3x2x2"])
+@pytest.mark.parametrize("name", ["box4x4", "kuhn3x2x2", "general72"])
 def test_wall_rows_carry_the_dynamic_viscosity(name):
     """every boundary facet, law 8 with the global group, use_law: c_K is the device's one constant in every cell, so the
     rows are those of the Smagorinsky restatement of tests/test_wall_quantities_host.py with C_s^2 = that constant --
@@ -439,7 +448,7 @@ def test_wall_rows_carry_the_dynamic_viscosity(name):
     sqrt and square); the conductive row is bitwise that of use_law off"""
     import test_wall_quantities_host as wh
     from test_derived_fields_host import smooth_fields as wall_fields
-    mesh, dm, marks, s, rs, make = _mesh((4, 4) if name == "box4x4" else KUHN)
+    mesh, dm, marks, s, rs, make = _mesh({"box4x4": (4, 4), "kuhn3x2x2": KUHN, "general72": GENERAL72}[name])
     dim = dm.dim
     ids, cells, local = wh.boundary_facets(mesh)
     _, p, T = wall_fields(dm.p2_coords, dm.p1_coords)

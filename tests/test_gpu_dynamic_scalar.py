@@ -25,7 +25,10 @@ Fields.  ``_sines`` with a sine temperature: every entry of G and grad T non-zer
 ``_t5`` (2D) / T = y (3D): the fields of the step tests; the kernel cases are listed in ``_KERNEL_CASES`` with the
 grouping, alpha and clip for which the restatement alone has c_K > 0 in at least half the cells and a term of at least
 a quarter of C T (found by a search over the groupings on the CPU).  ``_clipped``: the fields for which every group
-quotient is above 0.0625 at alpha = 1.1."""
+quotient is above 0.0625 at alpha = 1.1.
+
+Meshes.  Those of tests/test_gpu_dynamic_model.py: the general tetrahedra with 72 and 384 cells run the procedure and
+the element kernel with the global group."""
 
 import numpy as np
 import pytest
@@ -36,7 +39,7 @@ from dynamic_scalar_host import DynamicScalarIMEXRestatement, DynamicScalarResta
 from gpu_common import rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from test_gpu_dynamic_model import CUBE, KUHN, _groupings, _groups, _host_steps, _les, _set, _sines, _step_setup
-from test_gpu_variable_viscosity import NO_PBC, _max_rel, _mesh, _opts
+from test_gpu_variable_viscosity import GENERAL72, GENERAL384, NO_PBC, _max_rel, _mesh, _opts
 from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
 from test_variable_viscosity_host import SMAGORINSKY
 from viscosity_models import DynamicSmagorinskyModel
@@ -44,7 +47,7 @@ from viscosity_models import DynamicSmagorinskyModel
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE]
+_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384]
 _FORMS = ((0, "standard"), (1, "skew_symmetric"))
 _V_SLOTS = (nat.U0, nat.U1, nat.U2, nat.USTAR, nat.CONV_N1, nat.CONV_N2)
 _T_SLOTS = (nat.T0, nat.T1)
@@ -150,7 +153,8 @@ def _les_smooth(X):
 # a quarter of C T (the quotient grows as alpha -> 1: R carries 1 - alpha^2)
 _KERNEL_CASES = {(4, 4): (_les_fields, ("planes", 1), 2.0, 0.2), (3, 5): (_les_fields, ("planes", 0), 2.0, 0.2),
                  "mapped": (_les_fields, ("planes", 0), 2.0, 0.2), KUHN: (_les_smooth, ("planes", 0), 1.1, 1.0),
-                 CUBE: (smooth_fields, ("planes", 1), 1.1, 1.0)}
+                 CUBE: (smooth_fields, ("planes", 1), 1.1, 1.0), GENERAL72: (_les_smooth, "global", 1.1, 1.0),
+                 GENERAL384: (_les_smooth, "global", 1.1, 1.0)}
 
 
 @pytest.mark.parametrize("kind", _MESHES, ids=str)

@@ -14,6 +14,7 @@ import pytest
 
 import _native as nat
 from fem_mesh import TaylorHoodDofMap, box_mesh, rectangle_mesh
+from general_tet_mesh import CUBE, SMALL, general_tets
 from gpu_common import context
 from test_flow_statistics_host import (WEIGHTS, RunningStats, columns, periodic_square, pooled_profiles, two_pass)
 
@@ -41,12 +42,14 @@ def _mesh(name):
         mesh = read_msh(os.path.join(HERE, "golden", "square_v41.msh"))[0]
     elif name == "periodic":
         return periodic_square(8)
+    elif name in ("general72", "general384"):    # the general tetrahedra of tests/general_tet_mesh.py: the node and
+        return general_tets(*(SMALL if name == "general72" else CUBE))[:2]   # vertex numbering of a renumbered mesh
     else:
         raise ValueError(name)
     return mesh, TaylorHoodDofMap(mesh)
 
 
-EXPECTED_NODES = dict(rect6x4=117, rect24x16=1617, box3x2x2=175, box4x4x4=729)
+EXPECTED_NODES = dict(rect6x4=117, rect24x16=1617, box3x2x2=175, box4x4x4=729, general72=175, general384=729)
 _CACHE = {}
 
 
@@ -148,7 +151,8 @@ def compare_nodes(ctx, ref, scalar, label):
 
 
 CASES = [("rect6x4", True), ("rect6x4", False), ("rect24x16", True), ("rect160x2", False), ("box3x2x2", True),
-         ("box3x2x2", False), ("box4x4x4", True), ("fixture", True), ("periodic", False)]
+         ("box3x2x2", False), ("box4x4x4", True), ("fixture", True), ("periodic", False), ("general72", True),
+         ("general72", False), ("general384", True)]
 
 
 @pytest.mark.parametrize("name,scalar", CASES)
@@ -168,7 +172,7 @@ def test_eight_weighted_samples_equal_the_restatement_and_two_pass_numpy(name, s
     ctx.close()
 
 
-@pytest.mark.parametrize("name", ["rect6x4", "rect24x16", "box3x2x2"])
+@pytest.mark.parametrize("name", ["rect6x4", "rect24x16", "box3x2x2", "general72"])
 def test_first_sample_is_the_mean_bit_for_bit_and_a_constant_field_has_zero_moments(name):
     ref = reference(name)
     dm = ref["dm"]

@@ -10,7 +10,9 @@ minus its mean 1e-8, relative, with Krylov rtol 1e-13.
 Meshes.  Those of tests/test_gpu_immersed_bodies.py; bodies ``bodies_2d`` / ``bodies_3d`` with temperatures
 (``heated_set`` of the host file; in ``overlap`` the disc is thermal and the box passive).  The quadrature clearances of
 these pairs are pinned by tests/test_immersed_bodies_host.py; the mapped box(8, 8) is not among them and runs with the
-smoothed mask only, and so does every pose that is a shift of those bodies (the pose a ``nsfem_move_bodies`` brings)."""
+smoothed mask only, and so does every pose that is a shift of those bodies (the pose a ``nsfem_move_bodies`` brings).  On
+the general tetrahedra the clearance of the set pose is asserted here before the sharp comparison (>= 1e-9), and that
+every body cuts cells of both orientations."""
 import numpy as np
 import pytest
 
@@ -19,9 +21,9 @@ from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from immersed_bodies import Ball, Box, ImmersedBodies
 from test_gpu_3d import lid_bc
-from test_gpu_immersed_bodies import _dim, _step_size
+from test_gpu_immersed_bodies import _dim, _step_size, cut_cells_by_orientation
 from test_gpu_scalar_transport import _B, _two_sides
-from test_gpu_variable_viscosity import _COEF, _KERNEL_MESHES, NO_PBC, _mesh, _opts
+from test_gpu_variable_viscosity import _COEF, _KERNEL_MESHES, NO_PBC, _mesh, _opts, is_general
 from test_heated_bodies_host import ScalarIMEXPenalRestatement, ScalarPenalRestatement, heated, heated_set
 from test_immersed_bodies_host import BODY_NAMES, IMEXPenalRestatement, PenalisationRestatement, bodies_2d
 from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
@@ -89,6 +91,10 @@ def test_fused_kernel_and_heat_numbers_match_the_restatement(kind, name):
             bodies, moved = heated_set(dim, name, _ETA, eps, _ETA_T), _shifted(dim, name, eps)
             orc, orc_moved = ScalarPenalRestatement(rs, bodies), ScalarPenalRestatement(rs, moved)
             H, H_moved, heat = orc.residual(T), orc_moved.residual(T), orc.heat(T)
+            if is_general(kind) and eps == 0.0:
+                assert PenalisationRestatement(rs, bodies).surface_clearance() >= 1e-9
+                means = np.einsum("q,cq->c", rs.wts, orc.chi) / rs.wts.sum()
+                assert min(cut_cells_by_orientation(mesh, means)) >= 4
             ctx.set_bodies(bodies.rows(), bodies.eta, bodies.smoothing)
             ctx.set_body_temperatures(*bodies.temperatures(), bodies.eta_scalar)
             # ---- the pose set: H alone, the heat numbers, the sum identity

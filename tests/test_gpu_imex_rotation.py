@@ -14,6 +14,7 @@ import pytest
 
 import _native as nat
 import fem_oracle as fo
+from general_tet_mesh import SMALL, general_tets, shear_bc
 from gpu_common import box, cavity_bc, context, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from partition import StripPartition
@@ -159,6 +160,16 @@ def test_stored_vector_3d(form_id, form, cc):
     _stored_vector_case(mesh, dm, s, context3, lid_bc(dm, marks), np.array([0.3, -0.2, 0.5]), cc, form_id, form, 6)
 
 
+@pytest.mark.parametrize("cc", [0.8, None])
+@pytest.mark.parametrize("form_id,form", FORMS)
+def test_stored_vector_on_general_tetrahedra(form_id, form, cc):
+    """the 72 general tetrahedra of tests/general_tet_mesh.py (cells of both orientations and of different volumes, no
+    zero in any J^-1) with Omega = (0.3, -0.2, 0.5): the same instantiation, the same 1e-13"""
+    mesh, dm, marks = general_tets(*SMALL)
+    s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+    _stored_vector_case(mesh, dm, s, context3, lid_bc(dm, marks), np.array([0.3, -0.2, 0.5]), cc, form_id, form, 6)
+
+
 # ---------------------------------------------------------------- 3. one launch against generic, bit for bit
 @pytest.mark.parametrize("form_id,form", FORMS)
 def test_rotating_rhs_one_launch_equals_generic(form_id, form):
@@ -273,9 +284,19 @@ def test_rotating_steps_on_a_graded_lattice_take_the_generic_path():
 def test_rotating_3d_steps_match_restatement():
     """unit cube n = 4, lid-driven, SBDF2, 3 steps, Omega(t) = (0.3, -0.2, 0.5) (1 + t), dOmega/dt = (0.3, -0.2, 0.5);
     tolerances of test_imex_3d_steps_match_restatement"""
-    mesh, dm, marks = box3((4, 4, 4))
+    _rotating_3d_steps(*box3((4, 4, 4)), lid_bc)
+
+
+def test_rotating_3d_steps_on_general_tetrahedra_match_restatement():
+    """the same three steps on the 72 general tetrahedra: the Coriolis kernel and the Euler vector M (dOmega/dt x x) on
+    cells of both orientations, inside the steps; boundary values: the solenoidal shear of general_tet_mesh.shear_bc (a
+    lid on the oblique face 6 has a net flux: no pure Neumann projection step)"""
+    _rotating_3d_steps(*general_tets(*SMALL), shear_bc)
+
+
+def _rotating_3d_steps(mesh, dm, marks, boundary_values):
     s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
-    vbc = lid_bc(dm, marks)
+    vbc = boundary_values(dm, marks)
     axis = np.array([0.3, -0.2, 0.5])
     ctx = context3(mesh, dm)
     try:

@@ -8,7 +8,8 @@ entry (box(16, 16), moving disc; the sharp kernels show 1.15e-15, so this is the
 DESIGN.md 4o), asserted ten times that, 1.25e-14 (library roundings differ between compilers), below the cap of 1e-11.
 Steps: those of tests/test_gpu_imex.py -- u*, u 1e-9 and p minus its mean 1e-8, relative.
 
-Meshes.  Those of tests/test_gpu_variable_viscosity.py.  Bodies: ``bodies_2d`` / ``bodies_3d`` of the host file; no
+Meshes.  Those of tests/test_gpu_variable_viscosity.py; on its general tetrahedra every body cuts cells of both
+orientations (asserted on the host: cells whose sharp mask is neither empty nor full, by the sign of det J).  Bodies: ``bodies_2d`` / ``bodies_3d`` of the host file; no
 quadrature point lies within 1e-9 of a surface (asserted on the host before every sharp comparison, which would hang on
 one rounding otherwise; the host file pins the actual clearances, >= 1.2e-4 in 2D)."""
 import os
@@ -17,11 +18,12 @@ import numpy as np
 import pytest
 
 import _native as nat
+from general_tet_mesh import jacobians
 from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from immersed_bodies import Ball, Box, HalfSpace, ImmersedBodies
 from test_gpu_3d import lid_bc
-from test_gpu_variable_viscosity import _COEF, _CS_STEPS, _KERNEL_MESHES, NO_PBC, _advance, _mesh, _opts
+from test_gpu_variable_viscosity import _COEF, _CS_STEPS, _KERNEL_MESHES, NO_PBC, _advance, _mesh, _opts, is_general
 from test_immersed_bodies_host import (BODY_NAMES, IMEXPenalRestatement, PenalisationRestatement, bodies_2d,
                                        bodies_3d)
 from test_scalar_transport_host import smooth_fields
@@ -41,6 +43,13 @@ def _max_rel(got, want):
 
 def _dim(kind):
     return 2 if kind == "mapped" or isinstance(kind[0], int) else 3
+
+
+def cut_cells_by_orientation(mesh, means):
+    """(number of cut cells with det J > 0, with det J < 0): cells whose mean of the sharp mask is neither 0 nor 1"""
+    cut = (means > 0.0) & (means < 1.0)
+    det = np.linalg.det(jacobians(mesh))
+    return int((cut & (det > 0.0)).sum()), int((cut & (det < 0.0)).sum())
 
 
 # ---------------------------------------------------------------- 1. the kernels against the restatement
@@ -68,6 +77,8 @@ def test_body_kernels_match_the_restatement(kind, name):
                 orc = PenalisationRestatement(rs, bodies)
                 assert orc.surface_clearance() >= 1e-9
                 want, means, forces = orc.residual(u), orc.cell_means(), orc.forces(u)
+                if is_general(kind) and eps == 0.0:
+                    assert min(cut_cells_by_orientation(mesh, means)) >= 4
                 ctx.set_bodies(bodies.rows(), eta, eps)
                 got = ctx.body_residual(nat.U1, 1.0)
                 cells = ctx.body_mask_cells()

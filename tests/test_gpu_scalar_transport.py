@@ -10,12 +10,15 @@ Meshes.  box(4, 4), box(8, 8): binary spacing, 81 and 289 P2 nodes -- below the 
 builds a dictionary at all, so their products run on CSR; box(16, 16) (1089 nodes) is the smallest binary lattice on
 which the dictionary path runs; box(3, 5) is the small non-binary, non-square one and box(20, 28) (2337 nodes) the
 non-binary one that HAS a dictionary, which is not the matrix bit for bit: CSR is required there.  3D: the Kuhn boxes of
-tests/test_gpu_3d.py, (3, 2, 2) cells on a 1 x 0.8 x 0.6 box (unequal counts and lengths) and (4, 4, 4)."""
+tests/test_gpu_3d.py, (3, 2, 2) cells on a 1 x 0.8 x 0.6 box (unequal counts and lengths) and (4, 4, 4).  The kernel also
+runs on the mapped box(8, 8) of tests/test_gpu_variable_viscosity.py (cells of different size and shape) and on the
+general tetrahedra of tests/general_tet_mesh.py with 72 and 384 cells (both orientations, no zero in any J^-1)."""
 import numpy as np
 import pytest
 
 import _native as nat
 import fem_oracle as fo
+from general_tet_mesh import CUBE, SMALL, general_tets
 from gpu_common import box, cavity_bc, context, rel, velocity_bc
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from test_gpu_3d import box3, context3, lid_bc
@@ -30,10 +33,19 @@ NO_PBC = (np.zeros(0, np.int32), np.zeros(0))
 
 
 def _mesh(kind):
-    """(mesh, dm, marks, space, context factory) of a 2D box (nx, ny) or a 3D Kuhn box ((nx, ny, nz), lengths)"""
-    if len(kind) == 2 and isinstance(kind[0], int):
+    """(mesh, dm, marks, space, context factory) of a 2D box (nx, ny), the "mapped" box(8, 8), a 3D Kuhn box
+    ((nx, ny, nz), lengths) or the general tetrahedra ((nx, ny, nz), lengths, "general")"""
+    if kind == "mapped":
+        from test_gpu_variable_viscosity import _mapped_box
+        mesh, dm, marks = _mapped_box()
+        make = context
+    elif len(kind) == 2 and isinstance(kind[0], int):
         mesh, dm, marks = box(*kind)
         make = context
+    elif len(kind) == 3:
+        assert kind[2] == "general"
+        mesh, dm, marks = general_tets(kind[0], kind[1])
+        make = context3
     else:
         mesh, dm, marks = box3(*kind)
         make = context3
@@ -41,7 +53,8 @@ def _mesh(kind):
 
 
 # ---------------------------------------------------------------- 1. the kernel against the oracle
-_KERNEL_MESHES = [(4, 4), (8, 8), (3, 5), (16, 16), ((3, 2, 2), (1.0, 0.8, 0.6)), ((4, 4, 4), (1.0, 1.0, 1.0))]
+_KERNEL_MESHES = [(4, 4), (8, 8), (3, 5), (16, 16), ((3, 2, 2), (1.0, 0.8, 0.6)), ((4, 4, 4), (1.0, 1.0, 1.0)), "mapped",
+                  SMALL + ("general", ), CUBE + ("general", )]
 
 
 @pytest.mark.parametrize("form_id,form", FORMS)

@@ -27,7 +27,8 @@ from scalar_sgs_host import ScalarIMEXSgsRestatement
 from subgrid_models_host import VREMAN, WALE, SubgridModelRestatement, SubgridScalarSgsRestatement, tensor_nu
 from test_gpu_3d import lid_bc
 from test_gpu_scalar_transport import _B, _two_sides
-from test_gpu_variable_viscosity import _COEF, NO_PBC, _advance, _max_rel, _mesh, _opts, _setup, _solve, _step
+from test_gpu_variable_viscosity import (_COEF, GENERAL72, GENERAL384, NO_PBC, _advance, _max_rel, _mesh, _opts, _setup,
+                                         _solve, _step, is_general)
 from test_heated_bodies_host import ScalarPenalRestatement, heated_set
 from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
 from test_variable_viscosity_host import CARREAU, SMAGORINSKY, IMEXViscRestatement
@@ -35,7 +36,7 @@ from test_variable_viscosity_host import CARREAU, SMAGORINSKY, IMEXViscRestateme
 pytestmark = pytest.mark.gpu
 
 KUHN = ((3, 2, 2), (1.0, 0.8, 0.6))
-_KERNEL_MESHES = [(4, 4), (3, 5), (16, 16), "mapped", KUHN, ((4, 4, 4), (1.0, 1.0, 1.0))]
+_KERNEL_MESHES = [(4, 4), (3, 5), (16, 16), "mapped", KUHN, ((4, 4, 4), (1.0, 1.0, 1.0)), GENERAL72, GENERAL384]
 _KERNEL_LAWS = {WALE: (2.0, ), VREMAN: (1.0, )}
 _STEP_LAWS = {WALE: (0.5, ), VREMAN: (0.1, )}
 _CV = _COEF["viscous_term"]
@@ -83,8 +84,12 @@ def test_viscosity_kernel_matches_the_restatement(kind, law):
     bytes, a weight of -1.5 rides in the kernel, no slot is written, viscosity_info counts the launches"""
     mesh, dm, marks, s, rs, make = _mesh(kind)
     u, want, means, orc = _kernel_reference(kind, law)
-    if kind == "mapped":
+    if kind == "mapped" or is_general(kind):
         assert orc.delta.max() > 1.2 * orc.delta.min()
+    if is_general(kind):
+        # every entry of G takes part, and through a J^-1 without zeros: a transposed or mis-indexed J^-1 shows
+        assert np.abs(orc.gradient(u)).max(axis=(0, 1)).min() > 0.1
+        assert np.abs(rs.g1).min() > 1e-7 * np.abs(rs.g1).max()
     ctx = make(mesh, dm)
     try:
         ctx.set_state(nat.U1, u)
@@ -152,7 +157,7 @@ def _steps(kind, typ, law, steps=4):
     params = _STEP_LAWS[law]
     ctx = make(mesh, dm)
     try:
-        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params)
+        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params, general=is_general(kind))
         assert isinstance(orc.visc, SubgridModelRestatement) and orc.visc.law == law
         plain = IMEXViscRestatement(s, _COEF, "standard", visc=None)
         plain.body_force = orc.body_force
@@ -181,11 +186,12 @@ def _steps(kind, typ, law, steps=4):
     ((8, 8), IMEXType.SBDF2, WALE, "generic"), ((8, 8), IMEXType.SBDF2, VREMAN, "generic"),
     ((8, 8), IMEXType.CNAB, WALE, "generic"), ((16, 16), IMEXType.SBDF2, WALE, "lattice-kernel"),
     ("mapped", IMEXType.SBDF2, VREMAN, "generic"), (KUHN, IMEXType.SBDF2, WALE, "generic"),
-    (KUHN, IMEXType.SBDF2, VREMAN, "generic")], ids=str)
+    (KUHN, IMEXType.SBDF2, VREMAN, "generic"), (GENERAL72, IMEXType.SBDF2, WALE, "generic"),
+    (GENERAL72, IMEXType.SBDF2, VREMAN, "generic")], ids=str)
 def test_steps_match_the_restatement(kind, typ, law, path):
     """lid-driven cavity from rest, 4 steps: box(8, 8) on the generic right-hand side for both laws and CNAB for WALE,
-    box(16, 16) on the one-launch lattice right-hand side, the mapped box (varying Delta_K), the (3, 2, 2) Kuhn box (3D
-    kernels inside the steps).  One element launch per step, the stored vector is never recomputed"""
+    box(16, 16) on the one-launch lattice right-hand side, the mapped box (varying Delta_K), the (3, 2, 2) Kuhn box and the
+    72 general tetrahedra (3D kernels inside the steps).  One element launch per step, the stored vector is never recomputed"""
     info, vinfo = _steps(kind, typ, law)
     assert info["path"] == path, info
     if path == "lattice-kernel":

@@ -11,7 +11,9 @@ of pow), asserted ten times that, 3.95e-14 (library roundings differ between com
 Meshes.  box(4, 4), box(3, 5), box(8, 8): one partly filled block of cells; box(16, 16): two blocks, and the smallest
 lattice on which the one-launch right-hand side runs.  The mapped mesh is box(8, 8) whose vertices went through a
 smooth non-linear map (the boundary stays) before the dof map was built: cells of different size and shape, Delta_K
-varies.  3D: the Kuhn boxes of tests/test_gpu_3d.py, (3, 2, 2) on 1 x 0.8 x 0.6 and (4, 4, 4) (more than one block)."""
+varies.  3D: the Kuhn boxes of tests/test_gpu_3d.py, (3, 2, 2) on 1 x 0.8 x 0.6 and (4, 4, 4) (more than one block),
+and the general tetrahedra of tests/general_tet_mesh.py at the same two sizes (72 and 384 cells): cells of both
+orientations, Delta_K varies by a factor of 1.5 and more, no entry of any J^-1 is zero."""
 import os
 
 import numpy as np
@@ -20,6 +22,7 @@ import pytest
 import _native as nat
 import fem_oracle as fo
 from fem_mesh import FacetMarkers, Mesh, TaylorHoodDofMap, rectangle_mesh
+from general_tet_mesh import CUBE, SMALL, general_tets, shear_bc
 from gpu_common import box, cavity_bc, context, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from test_gpu_3d import box3, context3, lid_bc
@@ -58,8 +61,9 @@ _CACHE = {}
 
 
 def _mesh(kind):
-    """(mesh, dm, marks, oracle space, rule space, context factory) of a 2D box (nx, ny), "mapped", or a 3D Kuhn box
-    ((nx, ny, nz), lengths); built once per kind and left unchanged"""
+    """(mesh, dm, marks, oracle space, rule space, context factory) of a 2D box (nx, ny), "mapped", a 3D Kuhn box
+    ((nx, ny, nz), lengths) or the general tetrahedra ((nx, ny, nz), lengths, "general"); built once per kind and left
+    unchanged"""
     if kind not in _CACHE:
         if kind == "mapped":
             mesh, dm, marks = _mapped_box()
@@ -67,6 +71,10 @@ def _mesh(kind):
         elif isinstance(kind[0], int):
             mesh, dm, marks = box(*kind)
             make = context
+        elif len(kind) == 3:
+            assert kind[2] == "general"
+            mesh, dm, marks = general_tets(kind[0], kind[1])
+            make = context3
         else:
             mesh, dm, marks = box3(*kind)
             make = context3
@@ -75,7 +83,15 @@ def _mesh(kind):
     return _CACHE[kind]
 
 
-_KERNEL_MESHES = [(4, 4), (3, 5), (8, 8), (16, 16), "mapped", ((3, 2, 2), (1.0, 0.8, 0.6)), ((4, 4, 4), (1.0, 1.0, 1.0))]
+GENERAL72, GENERAL384 = SMALL + ("general", ), CUBE + ("general", )
+
+
+def is_general(kind):
+    return isinstance(kind, tuple) and len(kind) == 3 and kind[2] == "general"
+
+
+_KERNEL_MESHES = [(4, 4), (3, 5), (8, 8), (16, 16), "mapped", ((3, 2, 2), (1.0, 0.8, 0.6)), ((4, 4, 4), (1.0, 1.0, 1.0)),
+                  GENERAL72, GENERAL384]
 
 
 def _max_rel(got, want):
@@ -92,7 +108,7 @@ def test_viscosity_kernel_matches_the_restatement(kind, law):
     u, _ = smooth_fields(dm.p2_coords)
     orc = VariableViscosityRestatement(rs, law, _LAWS[law])
     want, means = orc.residual(u), orc.cell_means(u)
-    if kind == "mapped":
+    if kind == "mapped" or is_general(kind):
         assert orc.delta.max() > 1.2 * orc.delta.min()
     ctx = make(mesh, dm)
     try:
@@ -148,11 +164,12 @@ def test_bad_laws_and_parameters_raise():
 
 
 # ---------------------------------------------------------------- 2. steps against the restatement
-def _setup(ctx, dm, marks, s, rs, law, params, form="standard"):
-    """coefficients, cavity / lid boundary values and the body force of test_gpu_scalar_transport._drive"""
+def _setup(ctx, dm, marks, s, rs, law, params, form="standard", general=False):
+    """coefficients, cavity / lid boundary values and the body force of test_gpu_scalar_transport._drive; ``general``:
+    the solenoidal shear of general_tet_mesh.shear_bc on every face (a lid on an oblique face has a net flux)"""
     X = dm.p2_coords
     dim = X.shape[1]
-    vbc = cavity_bc(dm, marks) if dim == 2 else lid_bc(dm, marks)
+    vbc = cavity_bc(dm, marks) if dim == 2 else (shear_bc if general else lid_bc)(dm, marks)
     f = np.stack([np.sin(np.pi * X[:, 1]), -1.0 + X[:, 0], 0.5 * X[:, 1]][:dim], axis=1).ravel()
     visc = VariableViscosityRestatement(rs, law, params) if law else None
     orc = IMEXViscRestatement(s, _COEF, form, visc=visc)
@@ -204,7 +221,7 @@ def _run(kind, typ, law, params, steps=4, k=None):
     mesh, dm, marks, s, rs, make = _mesh(kind)
     ctx = make(mesh, dm)
     try:
-        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params)
+        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params, general=is_general(kind))
         n = kind[0] if isinstance(kind[0], int) else (8 if kind == "mapped" else kind[0][0])
         ts = IMEXTimeStepping(0.0, 1.0e9, typ, desired_start_time_step=k or 0.5 / n)
         opts = _opts(ctx)
@@ -251,10 +268,12 @@ def test_steps_with_smagorinsky_match_the_restatement(typ, newtonian_ustar):
     ((16, 16), SMAGORINSKY, (_CS_STEPS, ), "lattice-kernel"), ("mapped", SMAGORINSKY, (_CS_STEPS, ), "generic"),
     (((3, 2, 2), (1.0, 0.8, 0.6)), SMAGORINSKY, (_CS_STEPS, ), "generic"),
     (((3, 2, 2), (1.0, 0.8, 0.6)), CARREAU, (0.008, 1.0, 0.5), "generic"),
+    (GENERAL72, SMAGORINSKY, (_CS_STEPS, ), "generic"), (GENERAL72, CARREAU, (0.008, 1.0, 0.5), "generic"),
     ((8, 8), CARREAU, (0.008, 1.0, 0.5), "generic")], ids=str)
 def test_sbdf2_steps_on_the_other_meshes_and_the_carreau_law(kind, law, params, path):
     """SBDF2, 4 steps: box(16, 16) runs the one-launch lattice right-hand side and the two extra launches after it;
-    the mapped mesh has a varying Delta_K; the Kuhn box runs the 3D kernel inside the steps; the Carreau law (zero
+    the mapped mesh has a varying Delta_K; the Kuhn box and the general tetrahedra run the 3D kernel inside the steps; the
+    Carreau law (zero
     shear viscosity c_v = 0.01, nu_inf = 0.002) in both dimensions"""
     orc, info, vinfo = _run(kind, IMEXType.SBDF2, law, params)
     assert info["path"] == path, info

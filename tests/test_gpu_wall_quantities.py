@@ -14,7 +14,11 @@ to which the device math library is built) times |a| P times the rest of its ter
 
 Meshes: the smallest that take each path -- 20 facets (under one wave), 272 (two workgroups of k_wall_facets, a
 ragged last one), 64 faces (under one workgroup), 528 faces (three strided passes of k_wall_reduce when in one group),
-the unstructured fixture, the periodic square (identified nodes)."""
+the unstructured fixture, the periodic square (identified nodes).  The general tetrahedra of tests/general_tet_mesh.py:
+72 cells (64 faces) and 900 cells (340 faces: a second, ragged workgroup of k_wall_facets<3, ...>) -- cells of both
+orientations and of different sizes, no zero in any J^-1, boundary faces that are planar but not axis-aligned (every
+component of almost every normal is non-zero), so that the analytic integrals of the polynomial fields are the sums over
+the planar faces and the facet rules stay exact."""
 import math
 import os
 
@@ -24,6 +28,7 @@ import pytest
 import _native as nat
 import wall_quantities as wq
 from fem_mesh import TaylorHoodDofMap, box_mesh, rectangle_mesh
+from general_tet_mesh import LARGE, SMALL, general_tets
 from gpu_common import context
 from test_derived_fields_host import polynomial_fields, polynomial_nodal, smooth_fields
 from test_flow_statistics_host import periodic_square
@@ -32,8 +37,8 @@ from test_wall_quantities_host import (CARREAU, EPS, OPTS, SMAGORINSKY, analytic
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-MESHES = ("rect6x4", "rect96x40", "box3x2x2", "box8x6x6", "fixture", "periodic")
-EXPECTED_FACETS = dict(rect6x4=20, rect96x40=272, box3x2x2=64, box8x6x6=528)
+MESHES = ("rect6x4", "rect96x40", "box3x2x2", "box8x6x6", "fixture", "periodic", "general72", "general900")
+EXPECTED_FACETS = dict(rect6x4=20, rect96x40=272, box3x2x2=64, box8x6x6=528, general72=64, general900=340)
 N_GROUPS = 4                                           # interleaved ids 0, 1, 3; group 2 stays empty
 LAWS = {"smagorinsky": (SMAGORINSKY, (0.17, )), "carreau": (CARREAU, (0.8, 1.3, 0.4))}
 _CACHE = {}
@@ -53,6 +58,8 @@ def _mesh(name):
         mesh = read_msh(os.path.join(HERE, "golden", "square_v41.msh"))[0]
     elif name == "periodic":
         return periodic_square(8)
+    elif name in ("general72", "general900"):
+        return general_tets(*(SMALL if name == "general72" else LARGE))[:2]
     else:
         raise ValueError(name)
     return mesh, TaylorHoodDofMap(mesh)
@@ -125,7 +132,7 @@ def test_every_entry_equals_the_restatement(name):
     assert not failures, failures
 
 
-@pytest.mark.parametrize("name", ["rect6x4", "box3x2x2", "fixture"])
+@pytest.mark.parametrize("name", ["rect6x4", "box3x2x2", "fixture", "general72", "general900"])
 def test_polynomial_fields_return_the_analytic_integrals(name):
     """quadratic u, linear p, quadratic T: the facet rules are exact, every entry equals the integral of the exact
     fields written out from their coefficients"""
@@ -257,7 +264,7 @@ def test_interior_facets_give_the_one_sided_trace():
 
 
 # ---------------------------------------------------------------- viscosity laws
-@pytest.mark.parametrize("name", ["rect6x4", "rect96x40", "box3x2x2", "box8x6x6"])
+@pytest.mark.parametrize("name", ["rect6x4", "rect96x40", "box3x2x2", "box8x6x6", "general72", "general900"])
 @pytest.mark.parametrize("law", sorted(LAWS))
 def test_laws_equal_the_restatement(name, law):
     ref = reference(name)
