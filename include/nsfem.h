@@ -718,7 +718,7 @@ typedef struct {
  * smoothing invalidates the stored vectors; the same set again does not.  NSFEM_ERR_ARG: contexts with a
  * communicator (n > 0), n > NSFEM_MAX_BODIES, unknown kinds, sizes <= 0 or not finite (kind 3: no unit normal), centres
  * or velocities not finite, eta <= 0, smoothing < 0; nsfem_step_ipcs and nsfem_step_bdf refuse to run while bodies
- * are set. */
+ * are set.  Bodies are not wrapped at periodic sides (see the tracer particles below): no image at the opposite side. */
 int nsfem_set_bodies(nsfem_ctx* ctx, int32_t n, const nsfem_body* bodies, double eta, double smoothing);
 /* Pose and velocity at t^n of the bodies set: centre, velocity, angular (kind 3: the normal in size as well; other
  * sizes are kept as set).  Call it once per step, before nsfem_step_imex: the pose it replaces becomes that of
@@ -868,6 +868,8 @@ int nsfem_eval_points(nsfem_ctx* ctx, int slot, int64_t n, const double* x, cons
  * frozen field).  Every stage point and the end point of a substep are located, the last known cell first and the
  * bins only when the point is not in it.  A particle one of whose points lies outside the mesh gets status 1, keeps
  * the position it had at the start of that substep and is never moved again.  Periodic sides are not wrapped.
+ * Neither are immersed bodies (nsfem_set_bodies, heated or not): their masks are evaluated at the coordinates of the
+ * cells, so a body cut by a periodic side has no image at the opposite side -- give the image as a body of its own.
  * NSFEM_ERR_ARG: n_sub < 1, dt not finite, slots that are no velocity slots, no nsfem_tracers_set.
  * nsfem_tracers_info: out = {particles, particles with status 1, advect calls since nsfem_tracers_set, bin-search
  * fallbacks of the last advect call}. */

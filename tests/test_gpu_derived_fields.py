@@ -24,14 +24,15 @@ import _native as nat
 from fem_mesh import TaylorHoodDofMap, box_mesh, rectangle_mesh
 from general_tet_mesh import CUBE, SMALL, general_tets
 from gpu_common import context
+from periodic_meshes import periodic_fixture
 from test_derived_fields_host import (CENTERS, QUANTITIES, analytic, derived_bound, derived_reference,
                                       polynomial_fields, polynomial_nodal, smooth_fields)
 from test_flow_statistics_host import periodic_square
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-MESHES = ("rect6x4", "rect24x16", "box3x2x2", "box4x4x4", "fixture", "periodic", "general72", "general384")
-EXPECTED_CELLS = dict(rect6x4=48, rect24x16=768, box3x2x2=72, box4x4x4=384, general72=72, general384=384)
+MESHES = ("rect6x4", "rect24x16", "box3x2x2", "box4x4x4", "fixture", "periodic", "general72", "general384", "pchan3")
+EXPECTED_CELLS = dict(pchan3=108, rect6x4=48, rect24x16=768, box3x2x2=72, box4x4x4=384, general72=72, general384=384)
 CENTER_NAMES = {nat.DERIVED_CELL: "CELL", nat.DERIVED_VERTEX: "VERTEX", nat.DERIVED_NODE: "NODE"}
 _CACHE = {}
 
@@ -50,6 +51,8 @@ def _mesh(name):
         mesh = read_msh(os.path.join(HERE, "golden", "square_v41.msh"))[0]
     elif name == "periodic":
         return periodic_square(8)
+    elif name == "pchan3":                       # the 3D periodic channel of tests/periodic_meshes.py: identified nodes,
+        return periodic_fixture(name)[:2]        # VERTEX values per cell corner, NODE values through the seam patches
     elif name in ("general72", "general384"):
         return general_tets(*(SMALL if name == "general72" else CUBE))[:2]
     else:

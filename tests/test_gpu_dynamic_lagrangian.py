@@ -26,7 +26,14 @@ assert first that NO displaced vertex, clamped or not, has a second cell within 
 best -- the upstream cell is unique there, and the choice of the definition is the only one accepted.  The boundary
 nodes are at rest in these cases: on four of the six faces the map of the mesh is a sum of functions of one surface
 coordinate each, so the two triangles of a boundary quad stay in one plane and an inflow vertex there meets the same
-exact tie as on a Kuhn box (tests/test_general_tet_mesh_host.py counts them)."""
+exact tie as on a Kuhn box (tests/test_general_tet_mesh_host.py counts them).
+
+Periodic fixtures (tests/periodic_meshes.py).  k_dyn_lagrange works with barycentric coordinates relative to the vertex,
+so the upstream cell of a vertex on the seam may lie on the far side of the mesh: tests/periodic_inputs.py asserts, on the
+restatement alone, that it does for at least a quarter of the displaced seam vertices, that every displaced vertex has
+exactly one cell within the tie margin (directions and seeds searched on the CPU; on pchan3 the velocity vanishes on
+the two walls, whose coplanar faces give the exact inflow ties of a Kuhn box), and that at CFL 0.4 nothing is clamped
+on the square and the cube without a wall -- there is no boundary to leave through."""
 import math
 
 import numpy as np
@@ -38,6 +45,10 @@ from dynamic_model_host import DYNAMIC, DynamicSmagorinskyRestatement
 from gpu_common import rel
 from imex_composed_host import ComposedIMEX
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_inputs import DIRECTION as PERIODIC_DIRECTION
+from periodic_inputs import across_the_seam, lagrangian_advance_case
+from periodic_meshes import ALL as PERIODIC
+from periodic_meshes import is_periodic, lengths_of
 from test_gpu_dynamic_model import CUBE, KUHN, _SPEC, _les, _step_setup
 from test_gpu_variable_viscosity import _COEF, GENERAL72, GENERAL384, NO_PBC, _mesh, _opts, is_general
 from test_variable_viscosity_host import SMAGORINSKY
@@ -46,12 +57,13 @@ from viscosity_models import DynamicSmagorinskyModel
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384]
+_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384] + list(PERIODIC)
 _CFLS = (0.4, 2.5)
 _SEEDS = {}                                            # (kind, cfl) -> seed; default 0
 # the mean direction of the seeded velocity of the advance cases (see ``_velocity``)
 _DIRECTION = {str(KUHN): (1.0, -0.738, -0.401), str(CUBE): (-1.0, 0.596, 0.978),
               str(GENERAL72): (1.0, -0.738, -0.401), str(GENERAL384): (-1.0, 0.596, 0.978)}
+_DIRECTION.update(PERIODIC_DIRECTION)                  # (the periodic fixtures: tests/periodic_inputs.py)
 _SLOTS = (nat.U0, nat.U1, nat.U2, nat.USTAR, nat.CONV_N1, nat.CONV_N2)
 NAN = float("nan")
 
@@ -110,6 +122,8 @@ def _advance_case(kind, cfl):
     """inputs of one advance, host only, built once: the seeded velocity and positive state, k for the CFL number, and
     the discrete choices of the restatement (with the tie assertion)"""
     key = (str(kind), cfl)
+    if is_periodic(kind):
+        return lagrangian_advance_case(kind, cfl)        # (tests/periodic_inputs.py, with the assertions named above)
     if key not in _ADVANCE:
         mesh, dm, marks, s, rs, make = _mesh(kind)
         orc = LagrangianDynamicRestatement(rs, (2.0, 0.09))
@@ -256,6 +270,45 @@ def test_linear_state_is_interpolated_exactly_upstream(kind):
     assert (err <= bound)[inside].all() and np.abs(up - linear(X))[inside].max() > 1e-3
 
 
+@pytest.mark.parametrize("kind", ["psquare", "pbox3"])
+def test_periodic_state_is_interpolated_upstream_across_the_seam(kind):
+    """the periodic twin of the test above.  A linear function of x is no function of the dof on a periodic mesh (it
+    jumps by b . L at the seam), so the state is trigonometric, I = 2 + 0.5 sin(2 pi x / L + ...) > 0 per component, and
+    the yardstick is the restatement: uniform u with a component along every axis at CFL 0.4, nothing clamped, one
+    cell within the tie margin at every vertex (asserted on the restatement), I_up inside the bound of the advance
+    test.  Independent of the vertex rows: with the uniform velocity LM = MM = 0"""
+    mesh, dm, marks, s, rs, make = _mesh(kind)
+    dim = dm.dim
+    X = dm.p1_coords
+    w = np.array(_DIRECTION[kind])
+    orc = LagrangianDynamicRestatement(rs, (2.0, 0.09))
+    k = 0.4 * _height(orc) / np.abs(w).max()
+    phase = 2.0 * np.pi * X / np.array(lengths_of(kind))[None, :]
+    state = np.stack([2.0 + 0.5 * np.sin(phase @ np.array([1.0, -1.0, 1.0])[:dim] + 0.3),
+                      1.5 + 0.4 * np.cos(phase @ np.array([1.0, 1.0, -1.0])[:dim] - 0.8)], axis=1)
+    uv = np.tile(w, (dm.n_p1, 1))
+    lam, ids, where = orc.locate(uv, k)
+    assert not where["clamped"].any() and np.all(where["tied"] == 1)
+    across = across_the_seam(kind, dm, where["cstar"])[1]
+    assert 4 * across.sum() >= dm.n_p1
+    want = np.zeros((dm.n_p1, 2))
+    for j in range(dim + 1):
+        want = want + lam[:, j, None] * state[ids[:, j]]
+    ctx = make(mesh, dm)
+    try:
+        ctx.set_state(nat.U1, np.tile(w, dm.n_p2))
+        _lagrangian(ctx)
+        ctx.set_dynamic_lagrangian_state(_state4(state))
+        new, up, cs2 = ctx.dynamic_lagrangian_advance(nat.U1, k, upstream=True)
+    finally:
+        ctx.close()
+    bound = _n_ops(dim, 0.4) * EPS * np.abs(want)
+    err = np.abs(up - want)
+    print("periodic state %s: error / bound %.3f, %d of %d upstream cells across the seam" % (
+        kind, (err / bound).max(), across.sum(), dm.n_p1))
+    assert (err <= bound).all() and np.abs(up - state).max() > 1e-3
+
+
 # ---------------------------------------------------------------- 3. exact zeros
 @pytest.mark.parametrize("kind", [(4, 4), KUHN], ids=str)
 def test_exact_zeros(kind):
@@ -311,7 +364,7 @@ class _Composed(ComposedIMEX):
 
 
 # case: the mesh case of tests/test_gpu_dynamic_model.py and cs2_init (inside (0, cs2_max) of that case)
-_STEP_CASES = {"box8-global": 0.0256, "box16-planes": 0.0256, "kuhn4-global": 0.002}
+_STEP_CASES = {"box8-global": 0.0256, "box16-planes": 0.0256, "kuhn4-global": 0.002, "pchan2-planes": 0.0256}
 _STEP_HOST = {}
 
 

@@ -25,7 +25,10 @@ u = A x plus 5 % of ``_sines`` with alpha = 1.1, for which every group is clippe
 
 Meshes.  Beside the 2D boxes and the Kuhn boxes, the general tetrahedra of tests/general_tet_mesh.py with 72 and 384
 cells, with the global group (there are no planes): the patch volumes differ, so the volume-weighted patch means are
-not the unweighted ones, and a moment read from the wrong cell is a wrong moment."""
+not the unweighted ones, and a moment read from the wrong cell is a wrong moment.  The periodic fixtures of
+tests/periodic_meshes.py: the vertex-to-cell lists are those of the P1 dofs, so a patch reaches across the seam and a
+plane group along a periodic axis holds one image of each plane (``cells`` groups, not ``cells + 1``); the uniform ones
+with the global group and every plane grouping, the mapped ones (no planes) with the global group."""
 import math
 
 import numpy as np
@@ -35,6 +38,10 @@ import _native as nat
 from dynamic_model_host import DYNAMIC, DynamicSmagorinskyRestatement
 from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_inputs import KERNEL_CASES, dynamic_host_steps, dynamic_kernel_case, dynamic_step_setup, half_unclipped
+from periodic_inputs import STEP_CASES as PERIODIC_STEP_CASES
+from periodic_meshes import ALL as PERIODIC
+from periodic_meshes import MAPPED, cells_of, is_periodic, lengths_of, periodic_axes, periodic_fields
 from test_gpu_3d import lid_bc
 from test_gpu_variable_viscosity import _COEF, GENERAL72, GENERAL384, NO_PBC, _max_rel, _mesh, _opts, is_general
 from test_variable_viscosity_host import SMAGORINSKY, IMEXViscRestatement, VariableViscosityRestatement
@@ -45,7 +52,7 @@ pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -53
 KUHN = ((3, 2, 2), (1.0, 0.8, 0.6))
 CUBE = ((4, 4, 4), (1.0, 1.0, 1.0))
-_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384]
+_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384] + list(PERIODIC)
 _N_VERTEX = {2: 80, 3: 160}
 _SLOTS = (nat.U0, nat.U1, nat.U2, nat.USTAR, nat.CONV_N1, nat.CONV_N2)
 
@@ -94,8 +101,10 @@ def _groups(dm, grouping):
 
 
 def _groupings(kind):
-    if is_general(kind):
+    if is_general(kind) or kind in MAPPED:
         return ["global"]
+    if is_periodic(kind):
+        return ["global"] + [("planes", a) for a in range(len(cells_of(kind)))]
     dim = 2 if kind == "mapped" or isinstance(kind[0], int) else 3
     return ["global"] + [("planes", a) for a in range(dim)]
 
@@ -115,6 +124,8 @@ def _procedure_reference(kind, grouping):
     if key not in _PROC_REF:
         mesh, dm, marks, s, rs, make = _mesh(kind)
         u = _sines(dm.p2_coords)
+        if is_periodic(kind):
+            u = periodic_fields(dm.p2_coords, lengths_of(kind), periodic_axes(kind))[0]
         orc = DynamicSmagorinskyRestatement(rs, (2.0, 0.09), _groups(dm, grouping))
         _PROC_REF[key] = (u, orc, orc.vertices(u), orc.vertices(u, absolute=True), orc.sums(u), orc.sums(u, absolute=True))
     return _PROC_REF[key]
@@ -131,6 +142,14 @@ def test_procedure_matches_the_restatement(kind, grouping):
     assert np.abs(orc.gradient(u)).max(axis=(0, 1)).min() > 0.1              # (every entry of G takes part)
     if is_general(kind):
         assert orc.vol.max() > 3.0 * orc.vol.min()                           # (weighted patch means are not plain ones)
+    if is_periodic(kind):
+        assert dm.n_p1 < mesh.num_vertices()
+        # the patch bound of the operation count holds: 6 / 24 cells at an interior vertex, and every vertex of a
+        # fixture without a wall is one
+        assert np.bincount(dm.p1_dofmap.ravel()).max() == (6 if dim == 2 else 24)
+        if grouping != "global":
+            axis = grouping[1]
+            assert orc.n_groups == cells_of(kind)[axis] + (0 if axis in periodic_axes(kind) else 1)
     n_v = _N_VERTEX[dim]
     bound_v = 2.0 * n_v * EPS * vert_abs
     counts = np.bincount(g, minlength=orc.n_groups)
@@ -166,6 +185,9 @@ def test_procedure_matches_the_restatement(kind, grouping):
 # grouping of the kernel cases: one for which the restatement gives positive constants in some groups (asserted)
 _KERNEL_GROUPING = {(4, 4): ("planes", 1), (3, 5): ("planes", 1), "mapped": "global", KUHN: ("planes", 0), CUBE: ("planes", 1),
                     GENERAL72: "global", GENERAL384: "global"}
+# (the periodic fixtures: grouping and field of tests/periodic_inputs.py, where the restatement alone is asserted to give a
+# positive, unclipped constant on at least half the groups)
+_KERNEL_GROUPING.update({kind: case[0] for kind, case in KERNEL_CASES.items()})
 
 
 @pytest.mark.parametrize("kind", _MESHES, ids=str)
@@ -175,10 +197,12 @@ def test_viscosity_kernel_matches_the_restatement(kind):
     element launch"""
     mesh, dm, marks, s, rs, make = _mesh(kind)
     grouping = _KERNEL_GROUPING[kind]
-    u = _les(dm.p2_coords)
+    u = dynamic_kernel_case(kind)[1] if is_periodic(kind) else _les(dm.p2_coords)
     orc = DynamicSmagorinskyRestatement(rs, (2.0, 0.09), _groups(dm, grouping))
     own = orc.constant(u)
     assert own.max() > 1e-3, own                                   # (the restatement alone: the term is not zero)
+    if is_periodic(kind):
+        assert half_unclipped(own, 0.09), own
     ctx = make(mesh, dm)
     try:
         ctx.set_state(nat.U1, u)
@@ -253,7 +277,10 @@ def test_rest_and_constant_fields_give_exact_zeros(kind):
 # case: (mesh, grouping, cs2_max, step size, lid-driven boundary values?)
 _STEP_CASES = {"box8-global": ((8, 8), "global", 0.04, 0.05 / 8, False),
                "box16-planes": ((16, 16), ("planes", 1), 0.04, 0.05 / 16, False),
-               "kuhn4-global": (CUBE, "global", 0.005, 0.05 / 4, True)}
+               "kuhn4-global": (CUBE, "global", 0.005, 0.05 / 4, True),
+               # the periodic channels with plane groups parallel to their walls (tests/periodic_inputs.py)
+               "pchan2-planes": PERIODIC_STEP_CASES["pchan2-planes"][:4] + (False, ),
+               "pchan3-planes": PERIODIC_STEP_CASES["pchan3-planes"][:4] + (False, )}
 _STEP_HOST = {}
 
 
@@ -262,6 +289,9 @@ def _step_setup(name):
     mesh, dm, marks, s, rs, make = _mesh(kind)
     X = dm.p2_coords
     dim = dm.dim
+    if is_periodic(kind):
+        pm, pd, ps, prs, grouping, cs2_max, k, vbc, f, u0 = dynamic_step_setup(name)
+        return mesh, dm, s, rs, make, grouping, cs2_max, k, vbc, f, u0
     vbc = cavity_bc(dm, marks) if dim == 2 else lid_bc(dm, marks)
     if not lid:
         vbc = (vbc[0], np.zeros_like(vbc[1]))                  # (the 2D fields have no-slip traces)
@@ -272,6 +302,8 @@ def _step_setup(name):
 def _host_steps(name, steps=4):
     """the restatement with its own constants, and beside it the restatement without the term: per step the states, the
     constants of level n and the effect of the term on u*.  Host only; computed once"""
+    if name in PERIODIC_STEP_CASES:
+        return dynamic_host_steps(name, steps)           # (asserts half the groups positive and unclipped at every step)
     if name not in _STEP_HOST:
         mesh, dm, s, rs, make, grouping, cs2_max, k, vbc, f, u0 = _step_setup(name)
         visc = DynamicSmagorinskyRestatement(rs, (2.0, cs2_max), _groups(dm, grouping))
@@ -306,6 +338,8 @@ def _assert_not_vacuous(name, host):
                                                                h["effect"]))
         assert inside.any(), (name, i, h["cs2"])
         assert h["effect"] >= 1e-4, (name, i, h["effect"])
+        if name in PERIODIC_STEP_CASES:
+            assert half_unclipped(h["cs2"], cs2_max), (name, i, h["cs2"])
 
 
 @pytest.mark.parametrize("name", list(_STEP_CASES))
@@ -440,7 +474,7 @@ def test_stored_vector_follows_law_groups_and_alpha_and_law_zero_returns_to_the_
 
 
 # ---------------------------------------------------------------- 7. the wall rows
-@pytest.mark.parametrize("name", ["box4x4", "kuhn3x2x2", "general72"])
+@pytest.mark.parametrize("name", ["box4x4", "kuhn3x2x2", "general72", "pchan3"])
 def test_wall_rows_carry_the_dynamic_viscosity(name):
     """every boundary facet, law 8 with the global group, use_law: c_K is the device's one constant in every cell, so the
     rows are those of the Smagorinsky restatement of tests/test_wall_quantities_host.py with C_s^2 = that constant --
@@ -448,11 +482,17 @@ def test_wall_rows_carry_the_dynamic_viscosity(name):
     sqrt and square); the conductive row is bitwise that of use_law off"""
     import test_wall_quantities_host as wh
     from test_derived_fields_host import smooth_fields as wall_fields
-    mesh, dm, marks, s, rs, make = _mesh({"box4x4": (4, 4), "kuhn3x2x2": KUHN, "general72": GENERAL72}[name])
+    mesh, dm, marks, s, rs, make = _mesh({"box4x4": (4, 4), "kuhn3x2x2": KUHN, "general72": GENERAL72}.get(name, name))
     dim = dm.dim
     ids, cells, local = wh.boundary_facets(mesh)
     _, p, T = wall_fields(dm.p2_coords, dm.p1_coords)
     u = _les(dm.p2_coords).reshape(-1, dim)
+    if is_periodic(name):
+        # (the periodic velocity of tests/periodic_meshes.py.  ``_les`` is exactly 0 on the walls but for a term that is
+        # 0 in the identified nodes at z = L and 1e-16 at z = L / 2: the mass flux of three wall faces is a sum of such
+        # terms, 6e-18 in absolute value, beside a vertex value of 0.64 whose basis function vanishes at the rule points
+        # to rounding only; the per-entry bound, relative to the terms, cannot cover that entry -- DESIGN.md 5c)
+        u = periodic_fields(dm.p2_coords, lengths_of(name), periodic_axes(name))[0].reshape(-1, dim)
     o = wh.OPTS
     own = DynamicSmagorinskyRestatement(rs, (2.0, 0.09)).constant(u.ravel())[0]
     assert own > 1e-3
@@ -624,4 +664,66 @@ def test_imex_solver_with_the_dynamic_model_equals_driving_the_steps_by_hand(mon
     finally:
         ctx.close()
     assert np.abs(u_cls).max() > 0.5
+    assert np.array_equal(u_cls, u_abi) and np.array_equal(p_cls, p_abi)
+
+
+def test_imex_solver_on_a_periodic_channel_equals_driving_the_steps_by_hand(monkeypatch):
+    """the 4 x 4 unit square periodic in x (``periodic=`` of tests/problem_specs.py), no-slip on bottom and top, set in
+    motion from rest by a constant body force along x; IMEXIPCSSolver with DynamicSmagorinskyModel(("planes", 1)), 3 steps.
+    The dof map the class builds has the identified nodes, the plane groups come from its P1 dofs -- 5 planes between the
+    walls -- and u and p are bit for bit what the C ABI gives on a second context with that dof map"""
+    from multigrid import attach_hierarchy
+    from ns_imex_solver import IMEXIPCSSolver
+    from problem_specs import build_problem
+    n, steps, dt = 4, 3, 0.05
+    spec = dict(name="PeriodicChannel", mesh=("cube", 2, n), scheme="ipcs", clock=dict(dt=dt, steps=steps),
+                numbers=dict(Re=100.0, Fr=1.0), start={"velocity": (0.0, 0.0), "pressure": 0.0}, gravity=(1.0, 0.0),
+                periodic=((0, ), ("left", "right")), bcs=[("no_slip", "bottom"), ("no_slip", "top")])
+    model = DynamicSmagorinskyModel(("planes", 1), filter_ratio=2.0, cs2_max=0.09)
+    monkeypatch.setenv("NSFEM_NO_OUTPUT", "1")
+    problem = build_problem(spec)
+
+    def set_viscosity_model(self):
+        self._viscosity_model = model
+    type(problem).set_viscosity_model = set_viscosity_model
+    problem.set_solver_class(IMEXIPCSSolver)
+    problem.compute_cfl = False
+    problem.solve_problem()
+    solver = problem._get_solver()
+    assert isinstance(solver, IMEXIPCSSolver) and problem._time_stepping.step_number == steps
+    dm, mesh = solver._dofmap, solver._mesh
+    assert (mesh.num_vertices(), dm.n_p1, dm.n_p2) == ((n + 1) ** 2, n * (n + 1), 2 * n * (2 * n + 1))
+    cctx = solver._ctx
+    assert cctx.viscosity_info()["law"] == DYNAMIC and cctx.viscosity_info()["recomputed"] == 0
+    assert cctx.dynamic_info()["groups"] == n + 1 and cctx.dynamic_info()["runs"] == steps
+    u_cls, p_cls = cctx.get_state(nat.U1), cctx.get_state(nat.P_OLD)
+    constant = problem._compute_model_constant()
+    assert constant.shape == (n + 1, ) and np.array_equal(constant, cctx.dynamic_constant(nat.U0))
+    # ---- the same steps through the C ABI on a fresh context
+    ctx = nat.NsfemContext(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap, dm.n_p2, dm.n_p1)
+    try:
+        if solver._mg_levels is not None:
+            attach_hierarchy(ctx, mesh)
+        coef = solver._equation_coefficients
+        ctx.set_coeffs(coef["convective_term"], coef["pressure_term"], coef["viscous_term"], coef["body_force_term"])
+        bd, bv = solver._dirichlet_bcs["velocity"]
+        ctx.set_dirichlet(nat.VELOCITY, np.asarray(bd, np.int32), np.asarray(bv, float))
+        ctx.set_dirichlet(nat.PRESSURE, *NO_PBC)
+        ctx.set_state(nat.BODY_FORCE, np.tile([1.0, 0.0], dm.n_p2))
+        ctx.set_viscosity_law(DYNAMIC, model.params(coef))
+        groups = model.vertex_groups(dm.p1_coords)
+        assert groups[0] == n + 1
+        ctx.set_dynamic_groups(*groups)
+        opts = solver._step_options()
+        ts = IMEXTimeStepping(0.0, 1.0, IMEXType.SBDF2, desired_start_time_step=dt)
+        for _ in range(steps):
+            ts.update_coefficients()
+            ctx.set_imex(ts.alpha, ts.beta, ts.gamma, ts.get_next_step_size())
+            ctx.step_imex(opts)
+            ts.advance_time()
+            ctx.advance(0)
+        u_abi, p_abi = ctx.get_state(nat.U1), ctx.get_state(nat.P_OLD)
+    finally:
+        ctx.close()
+    assert np.abs(u_cls).max() > 0.05
     assert np.array_equal(u_cls, u_abi) and np.array_equal(p_cls, p_abi)

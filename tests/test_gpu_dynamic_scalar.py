@@ -38,6 +38,7 @@ from dynamic_model_host import DYNAMIC
 from dynamic_scalar_host import DynamicScalarIMEXRestatement, DynamicScalarRestatement
 from gpu_common import rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_meshes import is_periodic, lengths_of, periodic_axes, periodic_fields
 from test_gpu_dynamic_model import CUBE, KUHN, _groupings, _groups, _host_steps, _les, _set, _sines, _step_setup
 from test_gpu_variable_viscosity import GENERAL72, GENERAL384, NO_PBC, _max_rel, _mesh, _opts
 from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
@@ -47,7 +48,7 @@ from viscosity_models import DynamicSmagorinskyModel
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384]
+_MESHES = [(4, 4), (3, 5), "mapped", KUHN, CUBE, GENERAL72, GENERAL384, "pchan3"]
 _FORMS = ((0, "standard"), (1, "skew_symmetric"))
 _V_SLOTS = (nat.U0, nat.U1, nat.U2, nat.USTAR, nat.CONV_N1, nat.CONV_N2)
 _T_SLOTS = (nat.T0, nat.T1)
@@ -70,6 +71,11 @@ def _t5(X):
     return X[:, 1] + 0.9 * np.sin(3.0 * np.pi * X[:, 0] + 1.7) * np.sin(3.0 * np.pi * X[:, 1] + 2.1)
 
 
+def _periodic(X, kind="pchan3"):
+    """the periodic velocity and scalar of tests/periodic_meshes.py: every entry of G and of grad T non-zero"""
+    return periodic_fields(X, lengths_of(kind), periodic_axes(kind))
+
+
 def _switch_on(ctx, dm, grouping, alpha, ctheta_max, cs2_max=0.09):
     _set(ctx, dm, grouping, (alpha, cs2_max))
     ctx.set_scalar_sgs_dynamic(True, ctheta_max)
@@ -88,6 +94,8 @@ def _procedure_reference(kind, grouping):
     if key not in _PROC_REF:
         mesh, dm, marks, s, rs, make = _mesh(kind)
         u, T = _sines(dm.p2_coords), _sine_T(dm.p2_coords)
+        if is_periodic(kind):
+            u, T = _periodic(dm.p2_coords, kind)
         orc = DynamicScalarRestatement(rs, (2.0, 0.2), _groups(dm, grouping))
         _PROC_REF[key] = (u, T, orc, orc.vertices(u, T), orc.vertices(u, T, absolute=True), orc.sums(u, T),
                           orc.sums(u, T, absolute=True))
@@ -154,7 +162,9 @@ def _les_smooth(X):
 _KERNEL_CASES = {(4, 4): (_les_fields, ("planes", 1), 2.0, 0.2), (3, 5): (_les_fields, ("planes", 0), 2.0, 0.2),
                  "mapped": (_les_fields, ("planes", 0), 2.0, 0.2), KUHN: (_les_smooth, ("planes", 0), 1.1, 1.0),
                  CUBE: (smooth_fields, ("planes", 1), 1.1, 1.0), GENERAL72: (_les_smooth, "global", 1.1, 1.0),
-                 GENERAL384: (_les_smooth, "global", 1.1, 1.0)}
+                 GENERAL384: (_les_smooth, "global", 1.1, 1.0),
+                 # the periodic channel, plane groups parallel to the walls: the restatement gives 0.136, 0.267, 0.269
+                 "pchan3": (_periodic, ("planes", 1), 1.1, 1.0)}
 
 
 @pytest.mark.parametrize("kind", _MESHES, ids=str)
@@ -330,14 +340,20 @@ def test_rest_and_constant_fields_give_exact_zeros(kind):
 # case of tests/test_gpu_dynamic_model.py (mesh, grouping, flow with law 8): (ctheta_max, kappa).  3D: T0 = y is the
 # conductive state of its own trace, and with kappa = 2 the constant stays inside the window while the flow bends T
 # (0.32, 0.46, 0.58, 0.58 of the clip on the CPU); with kappa = 0.05 it triples within two steps
-_STEP_CASES = {"box8-global": (0.05, 0.05), "box16-planes": (0.05, 0.05), "kuhn4-global": (0.03, 2.0)}
+_STEP_CASES = {"box8-global": (0.05, 0.05), "box16-planes": (0.05, 0.05), "kuhn4-global": (0.03, 2.0),
+               "pchan3-planes": (0.03, 0.5)}
 _STEP_HOST = {}
+_PERIODIC_STEPS = {"pchan3-planes": 1.0}
+_STEP_CASES_KIND = {"pchan3-planes": "pchan3"}
 
 
 def _scalar_setup(name):
     mesh, dm, s, rs, make, grouping, cs2_max, k, vbc, f, u0 = _step_setup(name)
     X = dm.p2_coords
     T0 = _t5(X) if dm.dim == 2 else X[:, 1].copy()
+    if name in _PERIODIC_STEPS:
+        # between the walls the conductive profile, bent by the periodic scalar of tests/periodic_meshes.py
+        T0 = T0 + _PERIODIC_STEPS[name] * _periodic(X, _STEP_CASES_KIND[name])[1]
     nodes = np.unique(np.asarray(vbc[0]) // dm.dim).astype(np.int32)         # (every boundary node: the trace of T0)
     return T0, (nodes, T0[nodes])
 

@@ -16,6 +16,7 @@ import _native as nat
 from fem_mesh import TaylorHoodDofMap, box_mesh, rectangle_mesh
 from general_tet_mesh import CUBE, SMALL, general_tets
 from gpu_common import context
+from periodic_meshes import periodic_fixture
 from test_flow_statistics_host import (WEIGHTS, RunningStats, columns, periodic_square, pooled_profiles, two_pass)
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,8 @@ def _mesh(name):
         mesh = read_msh(os.path.join(HERE, "golden", "square_v41.msh"))[0]
     elif name == "periodic":
         return periodic_square(8)
+    elif name == "pchan3":                       # the 3D periodic channel of tests/periodic_meshes.py: 180 P2 nodes and
+        return periodic_fixture(name)[:2]        # 27 P1 nodes on 48 mesh vertices
     elif name in ("general72", "general384"):    # the general tetrahedra of tests/general_tet_mesh.py: the node and
         return general_tets(*(SMALL if name == "general72" else CUBE))[:2]   # vertex numbering of a renumbered mesh
     else:
@@ -49,7 +52,7 @@ def _mesh(name):
     return mesh, TaylorHoodDofMap(mesh)
 
 
-EXPECTED_NODES = dict(rect6x4=117, rect24x16=1617, box3x2x2=175, box4x4x4=729, general72=175, general384=729)
+EXPECTED_NODES = dict(pchan3=180, rect6x4=117, rect24x16=1617, box3x2x2=175, box4x4x4=729, general72=175, general384=729)
 _CACHE = {}
 
 
@@ -152,7 +155,7 @@ def compare_nodes(ctx, ref, scalar, label):
 
 CASES = [("rect6x4", True), ("rect6x4", False), ("rect24x16", True), ("rect160x2", False), ("box3x2x2", True),
          ("box3x2x2", False), ("box4x4x4", True), ("fixture", True), ("periodic", False), ("general72", True),
-         ("general72", False), ("general384", True)]
+         ("general72", False), ("general384", True), ("pchan3", True), ("pchan3", False)]
 
 
 @pytest.mark.parametrize("name,scalar", CASES)
@@ -267,13 +270,18 @@ def _axis_groups(dm, axis):
 
 
 @pytest.mark.parametrize("name,scalar,axis", [("rect160x2", False, 1), ("rect160x2", True, 0), ("rect24x16", True, 1),
-                                              ("box4x4x4", True, 2), ("box3x2x2", False, 0), ("periodic", False, 1)])
+                                              ("box4x4x4", True, 2), ("box3x2x2", False, 0), ("periodic", False, 1),
+                                              ("pchan3", True, 1)])
 def test_profiles_along_an_axis_equal_the_restatement(name, scalar, axis):
     ref = reference(name)
     ctx = feed(ref, scalar)
     g2, g1 = _axis_groups(ref["dm"], axis)
     if name == "rect160x2":
         assert np.diff(g2[0]).tolist() == ([321] * 5 if axis == 1 else [5] * 321)
+    if name == "pchan3":
+        # profiles along y, between the walls: 5 planes of P2 nodes and 3 of P1 nodes, each holding one image of every
+        # periodic node (6 x 6 and 3 x 3 of them, not 7 x 7 and 4 x 4)
+        assert np.diff(g2[0]).tolist() == [36] * 5 and np.diff(g1[0]).tolist() == [9] * 3
     res = compare_profiles(ctx, ref, scalar, g2, g1, "%s axis %d" % (name, axis))
     if name == "rect160x2" and axis == 1:
         # the mean velocity varies along the 321-node lines: the between-node part must be there -- at least 10 % of

@@ -21,7 +21,7 @@ from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from immersed_bodies import Ball, Box, ImmersedBodies
 from test_gpu_3d import lid_bc
-from test_gpu_immersed_bodies import _dim, _step_size, cut_cells_by_orientation
+from test_gpu_immersed_bodies import _dim, _step_size, body_cases, cut_cells_by_orientation, velocity_and_scalar
 from test_gpu_scalar_transport import _B, _two_sides
 from test_gpu_variable_viscosity import _COEF, _KERNEL_MESHES, NO_PBC, _mesh, _opts, is_general
 from test_heated_bodies_host import ScalarIMEXPenalRestatement, ScalarPenalRestatement, heated, heated_set
@@ -63,8 +63,7 @@ def _shifted(dim, name, eps):
 
 
 # ---------------------------------------------------------------- a. / b. the kernels against the restatement
-@pytest.mark.parametrize("name", BODY_NAMES)
-@pytest.mark.parametrize("kind", _KERNEL_MESHES, ids=str)
+@pytest.mark.parametrize("kind,name", body_cases(), ids=str)
 def test_fused_kernel_and_heat_numbers_match_the_restatement(kind, name):
     """weight (C(u) T + H(T)) from the fused launch and the heat numbers per body for the smooth non-polynomial fields:
     sharp and smoothed masks, both forms, weights 1 and -1.5 (other slots), the pose of t^n and -- after one
@@ -76,7 +75,7 @@ def test_fused_kernel_and_heat_numbers_match_the_restatement(kind, name):
     * (sum of the absolute terms) of the exact value, so their difference is within the sum of the two bounds."""
     mesh, dm, marks, s, rs, make = _mesh(kind)
     dim = _dim(kind)
-    u, T = smooth_fields(dm.p2_coords)
+    u, T = velocity_and_scalar(kind, dm)
     ctx = make(mesh, dm)
     try:
         for slot in (nat.U1, nat.USTAR):

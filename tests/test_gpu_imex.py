@@ -4,7 +4,11 @@ right-hand-side mode) against the generic launch sequence, bit for bit.
 
 Tolerances of the step comparisons: those of test_gpu_parity.test_ipcs_cavity_steps_match_oracle for the same
 quantities after the same number of steps -- u*, u 1e-9 and p minus its mean 1e-8, relative -- with its LU-accuracy
-Krylov tolerances (rtol 1e-13)."""
+Krylov tolerances (rtol 1e-13).
+
+Periodic meshes (tests/periodic_meshes.py): the right-hand side of the generic path against IMEXRestatement.rhs and
+three SBDF2 steps on the periodic channels and on the square and the cube without any wall, where the momentum system
+has no Dirichlet row and the projection step a constant kernel; what nsfem_imex_info reports there is asserted."""
 import numpy as np
 import pytest
 
@@ -12,6 +16,7 @@ import _native as nat
 import fem_oracle as fo
 from gpu_common import box, cavity_bc, context, rel, velocity_bc
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_meshes import UNIFORM, lengths_of, periodic_axes, periodic_fields, periodic_fixture, wall_bc
 from test_imex_solver_host import IMEXRestatement
 
 pytestmark = pytest.mark.gpu
@@ -307,6 +312,84 @@ def test_rotating_frame_and_wrong_call_order_are_refused():
         ctx.step_imex()
         ctx.set_bdf((1.0, -1.0, 0.0), 1.0 / 32.0)       # back to the implicit scheme on the same context
         assert ctx.step_ipcs().newton_iterations > 0
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------- periodic dof maps
+_PCOEF = dict(convective_term=0.8, pressure_term=1.0, viscous_term=0.02, body_force_term=0.7)
+# The one-launch right-hand side runs where the stencil dictionary of the operators found a 2D lattice: every column
+# offset of every row is dj * W + di with |di|, |dj| <= 2 and stays inside the W x H box (csrc/linalg.hip).  The seam
+# rows of a periodic lattice couple to columns a whole line away, so no periodic lattice is eligible (and no 3D mesh
+# is): nsfem_imex_info reports the generic path on all four fixtures, and asking for the other one is an argument error
+
+
+def _periodic_case(name):
+    mesh, dm, marks = periodic_fixture(name)
+    s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+    u, T = periodic_fields(dm.p2_coords, lengths_of(name), periodic_axes(name))
+    vbc = wall_bc(name)
+    assert (vbc[0].size == 0) == (name in ("psquare", "pbox3"))
+    u1 = u.copy()
+    u1[vbc[0]] = 0.0
+    dim = mesh._dim
+    f = np.roll(u.reshape(-1, dim), 1, axis=1).ravel() * 0.6
+    u2 = 0.9 * u1 + 0.02 * f
+    u2[vbc[0]] = 0.0
+    return mesh, dm, s, vbc, u1, u2, f
+
+
+@pytest.mark.parametrize("form_id,form", FORMS)
+@pytest.mark.parametrize("name", UNIFORM)
+def test_rhs_on_periodic_meshes_matches_the_restatement(name, form_id, form):
+    """nsfem_imex_rhs, generic path, against IMEXRestatement.rhs for the first-step and the SBDF2 coefficients: 1e-13
+    of the largest entry, the project's figure for element kernels against the oracle.  The one-launch path does not
+    apply on a periodic lattice (above): asking for it is an argument error, not a wrong vector"""
+    mesh, dm, s, vbc, u1, u2, f = _periodic_case(name)
+    _, T = periodic_fields(dm.p1_coords, lengths_of(name), periodic_axes(name))
+    orc = IMEXRestatement(s, _PCOEF, form)
+    orc.vel[1], orc.vel[2], orc.p_old, orc.body_force = u1, u2, T, f
+    ctx = context(mesh, dm)
+    try:
+        ctx.set_coeffs(0.8, 1.0, 0.02, 0.7)
+        ctx.set_dirichlet(nat.VELOCITY, vbc[0].astype(np.int32), vbc[1])
+        for slot, v in ((nat.U1, u1), (nat.U2, u2), (nat.P_OLD, T), (nat.BODY_FORCE, f)):
+            ctx.set_state(slot, v)
+        for tag, (alpha, beta, gamma) in (("first", _FIRST), ("SBDF2", _LATER["SBDF2"])):
+            ctx.set_imex(alpha, beta, gamma, 1.0 / 64.0)
+            orc.N2 = None
+            want = orc.rhs(alpha, beta, gamma, 1.0 / 64.0)
+            got, n1 = ctx.imex_rhs("generic", form_id)
+            err = float(np.abs(got - want).max() / np.abs(want).max())
+            nerr = float(np.abs(n1 - 0.8 * orc.N1).max() / np.abs(orc.N1).max())
+            print("rhs %s form %d %s: %.2e, c_c N(u1) %.2e (of the largest entry)" % (name, form_id, tag, err, nerr))
+            assert np.abs(orc.N1).max() > 1e-3
+            assert err < 1e-13 and nerr < 1e-13
+            with pytest.raises(nat.NativeError, match="one-launch") as refusal:
+                ctx.imex_rhs("lattice-kernel", form_id)
+            assert refusal.value.code == nat.ERR_ARG
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("name", UNIFORM)
+def test_imex_steps_on_periodic_meshes_match_restatement(name):
+    """three SBDF2 steps from a periodic velocity at two levels under a periodic body force, no-slip on the walls.  On
+    psquare and pbox3 nothing is prescribed: the momentum matrix has no Dirichlet row, and the projection step has the
+    constants in its kernel with no wall at all -- the device subtracts the mean, the restatement pins a node, the
+    right-hand side is compatible (no boundary, no flux), so p is compared minus its mean"""
+    mesh, dm, s, vbc, u1, u2, f = _periodic_case(name)
+    ctx = context(mesh, dm)
+    try:
+        ctx.set_coeffs(0.8, 1.0, 0.02, 0.7)
+        orc = IMEXRestatement(s, _PCOEF, "standard")
+        orc.vel[1], orc.vel[2], orc.body_force = u1.copy(), u2.copy(), f
+        for slot, v in ((nat.U1, u1), (nat.U2, u2), (nat.BODY_FORCE, f)):
+            ctx.set_state(slot, v)
+        _drive(ctx, orc, IMEXType.SBDF2, 0, 3, 0.02, (vbc[0].astype(np.int32), vbc[1]), NO_PBC)
+        info = ctx.imex_info()
+        assert info["path"] == "generic" and (info["lattice_rhs"], info["generic_rhs"]) == (0, 3), info
+        assert np.abs(orc.vel[1]).max() > 0.5 and np.abs(orc.p_old - orc.p_old.mean()).max() > 0.1
     finally:
         ctx.close()
 

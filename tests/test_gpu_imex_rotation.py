@@ -18,6 +18,7 @@ from general_tet_mesh import SMALL, general_tets, shear_bc
 from gpu_common import box, cavity_bc, context, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from partition import StripPartition
+from periodic_meshes import periodic_fixture, wall_bc
 from test_gpu_3d import box3, context3, lid_bc
 from test_gpu_imex import _LATER, _SETS, FORMS, NO_PBC, TYPES, _graded, _opts
 from test_gpu_imex_partition import _cavity_bc, _compare, _on_ranks, _plain_partition
@@ -168,6 +169,16 @@ def test_stored_vector_on_general_tetrahedra(form_id, form, cc):
     mesh, dm, marks = general_tets(*SMALL)
     s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
     _stored_vector_case(mesh, dm, s, context3, lid_bc(dm, marks), np.array([0.3, -0.2, 0.5]), cc, form_id, form, 6)
+
+
+def test_stored_vector_on_the_periodic_channel():
+    """pchan3 of tests/periodic_meshes.py (periodic in x and z, no-slip on the walls in y) with Omega = (0.3, -0.2, 0.5),
+    the skew-symmetric form: the Coriolis vector is gathered and scattered through the identified dofs of the seam
+    cells; the same 1e-13"""
+    mesh, dm, marks = periodic_fixture("pchan3")
+    assert dm.n_p2 == 180 and dm.n_p1 < mesh.num_vertices()
+    s = fo.Space(mesh.coords, mesh.cells, dm.p2_dofmap, dm.p1_dofmap)
+    _stored_vector_case(mesh, dm, s, context3, wall_bc("pchan3"), np.array([0.3, -0.2, 0.5]), 0.8, *FORMS[3], 6)
 
 
 # ---------------------------------------------------------------- 3. one launch against generic, bit for bit

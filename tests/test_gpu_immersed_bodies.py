@@ -9,7 +9,10 @@ DESIGN.md 4o), asserted ten times that, 1.25e-14 (library roundings differ betwe
 Steps: those of tests/test_gpu_imex.py -- u*, u 1e-9 and p minus its mean 1e-8, relative.
 
 Meshes.  Those of tests/test_gpu_variable_viscosity.py; on its general tetrahedra every body cuts cells of both
-orientations (asserted on the host: cells whose sharp mask is neither empty nor full, by the sign of det J).  Bodies: ``bodies_2d`` / ``bodies_3d`` of the host file; no
+orientations (asserted on the host: cells whose sharp mask is neither empty nor full, by the sign of det J).  On its
+periodic fixtures the body set "seam": one ball inside the domain and one cut by the periodic side x = 0.  The kernels
+take the coordinates of the cells, so the cut ball has NO periodic image at x = L (include/nsfem.h says so, and
+test_a_body_cut_by_a_periodic_side_has_no_image pins it).  Bodies: ``bodies_2d`` / ``bodies_3d`` of the host file; no
 quadrature point lies within 1e-9 of a surface (asserted on the host before every sharp comparison, which would hang on
 one rounding otherwise; the host file pins the actual clearances, >= 1.2e-4 in 2D)."""
 import os
@@ -22,6 +25,7 @@ from general_tet_mesh import jacobians
 from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
 from immersed_bodies import Ball, Box, HalfSpace, ImmersedBodies
+from periodic_meshes import CHANNELS, is_periodic, lengths_of, periodic_axes, periodic_fields
 from test_gpu_3d import lid_bc
 from test_gpu_variable_viscosity import _COEF, _CS_STEPS, _KERNEL_MESHES, NO_PBC, _advance, _mesh, _opts, is_general
 from test_immersed_bodies_host import (BODY_NAMES, IMEXPenalRestatement, PenalisationRestatement, bodies_2d,
@@ -42,7 +46,21 @@ def _max_rel(got, want):
 
 
 def _dim(kind):
+    if is_periodic(kind):
+        return len(lengths_of(kind))
     return 2 if kind == "mapped" or isinstance(kind[0], int) else 3
+
+
+def body_cases(names=BODY_NAMES):
+    """(mesh kind, body set) of the kernel tests: every set on the other meshes, "seam" on the periodic fixtures"""
+    return [(k, n) for k in _KERNEL_MESHES for n in (("seam", ) if is_periodic(k) else names)]
+
+
+def velocity_and_scalar(kind, dm):
+    """the smooth non-polynomial fields of the kernel tests; periodic ones on a periodic fixture"""
+    if is_periodic(kind):
+        return periodic_fields(dm.p2_coords, lengths_of(kind), periodic_axes(kind))
+    return smooth_fields(dm.p2_coords)
 
 
 def cut_cells_by_orientation(mesh, means):
@@ -53,8 +71,7 @@ def cut_cells_by_orientation(mesh, means):
 
 
 # ---------------------------------------------------------------- 1. the kernels against the restatement
-@pytest.mark.parametrize("name", BODY_NAMES)
-@pytest.mark.parametrize("kind", _KERNEL_MESHES, ids=str)
+@pytest.mark.parametrize("kind,name", body_cases(), ids=str)
 def test_body_kernels_match_the_restatement(kind, name):
     """(weight / eta) B(u), the cell means of chi and volumes / forces / torques for the smooth non-polynomial velocity,
     each body sharp and smoothed, at rest and with U and W; second calls return the same bytes, the weight rides in the
@@ -64,7 +81,7 @@ def test_body_kernels_match_the_restatement(kind, name):
     * (sum of the absolute terms) of the exact value, so their difference is within the sum of the two bounds."""
     mesh, dm, marks, s, rs, make = _mesh(kind)
     dim = _dim(kind)
-    u, _ = smooth_fields(dm.p2_coords)
+    u, _ = velocity_and_scalar(kind, dm)
     eta = 0.037
     ctx = make(mesh, dm)
     try:
@@ -131,6 +148,39 @@ def test_body_forces_on_a_second_trip_of_the_cell_loop():
             assert F.tobytes() == ctx.body_forces(nat.U1).tobytes()
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("kind", CHANNELS)
+def test_a_body_cut_by_a_periodic_side_has_no_image(kind):
+    """a ball of radius 0.2 centred on the periodic side x = 0 of a channel, sharp mask, on the device alone: every cell
+    with a vertex on x = 0 -- the seam cells of the low side -- may carry mask, the cells of the high half of the
+    domain (all vertices at x >= L / 2), where a periodic image would cover the last column, have exactly zero, and
+    the volume is that of the half ball inside the domain, not of the whole one: the kernels take cell coordinates, bodies are not periodic"""
+    mesh, dm, marks, s, rs, make = _mesh(kind)
+    dim = _dim(kind)
+    L = lengths_of(kind)
+    r = 0.2
+    ball = Ball((0.0, ) + tuple(0.5 * l for l in L[1:]), r)
+    bodies = ImmersedBodies([ball], 0.037, 0.0)
+    orc = PenalisationRestatement(rs, bodies)
+    assert orc.surface_clearance() >= 1e-9
+    x = mesh.coords[mesh.cells.astype(np.int64)][:, :, 0]
+    high, low = x.min(axis=1) > 0.5 * L[0] - 1e-12, x.min(axis=1) < 1e-12
+    assert high.sum() >= 2 and low.sum() >= 2
+    u, _ = velocity_and_scalar(kind, dm)
+    ctx = make(mesh, dm)
+    try:
+        ctx.set_state(nat.U1, u)
+        ctx.set_bodies(bodies.rows(), 0.037, 0.0)
+        cells, F = ctx.body_mask_cells(), ctx.body_forces(nat.U1)
+    finally:
+        ctx.close()
+    whole = np.pi * r * r if dim == 2 else 4.0 / 3.0 * np.pi * r ** 3
+    print("%s: mask at the low side up to %.3f, at the high side %.1e; volume %.5f of %.5f for the whole ball" % (
+        kind, cells[low].max(), cells[high].max(), F[0, 0], whole))
+    assert cells[low].max() > 0.05 and np.all(cells[high] == 0.0)
+    assert 0.3 * whole < F[0, 0] < 0.7 * whole
+    assert _max_rel(cells, orc.cell_means()) < 1e-13
 
 
 # ---------------------------------------------------------------- 2. steps against the restatement

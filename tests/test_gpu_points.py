@@ -16,6 +16,7 @@ import pytest
 import _native as nat
 from fem_spaces import evaluate_lagrange
 from gpu_common import context
+from periodic_meshes import CHANNELS, far_images, lengths_of, periodic_axes, periodic_fields, periodic_fixture
 from point_locator import barycentric, build_bins
 from test_point_locator_host import MESHES, brute_force, brute_force_cells, mesh_of, point_sets
 from test_volume_functionals_host import smooth_fields
@@ -131,6 +132,39 @@ def test_values_equal_evaluate_lagrange(name):
     for a, b in zip(before, _all_slots(ctx)):
         assert a.tobytes() == b.tobytes()
     ctx.close()
+
+
+@pytest.mark.parametrize("name", CHANNELS)
+def test_values_in_the_seam_cells_of_periodic_channels(name):
+    """pchan2 / pchan3 of tests/periodic_meshes.py: three points strictly inside every cell that reads a dof across the
+    seam (its vertex lies a period away from the coordinates stored for the dof).  The device finds the cell, and
+    velocity, pressure and scalar there equal evaluate_lagrange's arithmetic in that cell and evaluate_lagrange itself:
+    the nodal values come through the identified dofs, the geometry from the cell"""
+    mesh, dm, _ = periodic_fixture(name)
+    dim = dm.dim
+    seam = np.flatnonzero(far_images(name).any(axis=1))
+    assert seam.size >= 2 * (dim + 1) and dm.n_p1 < mesh.num_vertices()
+    rng = np.random.default_rng(29)
+    lam = rng.uniform(0.15, 1.0, (3 * seam.size, dim + 1))
+    lam /= lam.sum(axis=1, keepdims=True)
+    cells = np.repeat(seam, 3).astype(np.int32)
+    X = np.einsum("mk,mka->ma", lam, mesh.coords[mesh.cells.astype(np.int64)[cells]])
+    u, T = periodic_fields(dm.p2_coords, lengths_of(name), periodic_axes(name))
+    p = periodic_fields(dm.p1_coords, lengths_of(name), periodic_axes(name))[1]
+    ctx = context(mesh, dm)
+    try:
+        ctx.set_point_locator(**build_bins(mesh.coords, mesh.cells))
+        ctx.set_scalar(0.01)
+        assert np.array_equal(ctx.locate_points(X), cells)
+        for field, slot, values in (("velocity", nat.U0, u), ("pressure", nat.P, p), ("scalar", nat.T0, T)):
+            ctx.set_state(slot, values)
+            scale = float(np.abs(values).max())
+            got = ctx.eval_points(slot, X)
+            _check_field("%s / seam cells / %s" % (name, field), got, _lagrange_at(dm, field, values, X, cells), scale, cells)
+            for i in rng.permutation(X.shape[0])[:8]:
+                assert np.abs(got[i] - evaluate_lagrange(dm, field, values, X[i])).max() <= EVAL_TOL * scale
+    finally:
+        ctx.close()
 
 
 @pytest.mark.parametrize("name", MESHES)
@@ -304,6 +338,37 @@ def test_a_particle_that_leaves_keeps_its_last_position():
     ctx.tracers_advect(nat.U1, nat.U0, 0.2, 4)
     assert ctx.tracers_get()[0].shape == (0, 2) and ctx.tracers_info()["n"] == 0
     ctx.close()
+
+
+@pytest.mark.parametrize("name", CHANNELS)
+def test_a_particle_driven_through_a_periodic_side_has_left(name):
+    """tracers know the mesh, not the dof map: a periodic side is a side (include/nsfem.h).  Uniform flow along x in a
+    periodic channel: the particle that reaches x = L ends with status 1 at its last position inside the mesh and does
+    not come back in at x = 0; the other one goes on"""
+    mesh, dm, _ = periodic_fixture(name)
+    dim = dm.dim
+    L = lengths_of(name)
+    flow = np.tile([1.0, 0.0, 0.0][:dim], dm.n_p2)
+    mid = [0.43 * l for l in L[1:]]
+    ctx = context(mesh, dm)
+    try:
+        ctx.set_point_locator(**build_bins(mesh.coords, mesh.cells))
+        ctx.set_state(nat.U0, flow)
+        ctx.set_state(nat.U1, flow)
+        ctx.tracers_set(np.array([[0.2] + mid, [L[0] - 0.08] + mid]))
+        ctx.tracers_advect(nat.U1, nat.U0, 0.2, 4)
+        x, cells, status = ctx.tracers_get()
+        print("%s: positions %r status %r" % (name, x.tolist(), status.tolist()))
+        assert status.tolist() == [0, 1] and ctx.tracers_info()["n_left"] == 1
+        # (the last stage of the second substep is at L + 0.02: one substep of 0.05 was taken)
+        assert np.abs(x - np.array([[0.4] + mid, [L[0] - 0.03] + mid])).max() <= 1e-14
+        _assert_cells_contain(mesh, x, cells)
+        ctx.tracers_advect(nat.U1, nat.U0, 0.2, 4)
+        x2, cells2, status2 = ctx.tracers_get()
+        assert x2[1].tobytes() == x[1].tobytes() and cells2[1] == cells[1] and status2.tolist() == [0, 1]
+        assert abs(x2[0, 0] - 0.6) <= 1e-14
+    finally:
+        ctx.close()
 
 
 def test_a_particle_driven_into_the_hole_of_the_shell_stops_inside_the_mesh():

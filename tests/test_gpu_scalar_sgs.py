@@ -17,6 +17,7 @@ import pytest
 import _native as nat
 from gpu_common import cavity_bc, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_meshes import is_periodic, lengths_of, periodic_axes, periodic_fields
 from scalar_sgs_host import ScalarIMEXSgsRestatement, ScalarSgsRestatement
 from test_gpu_3d import lid_bc
 from test_gpu_scalar_transport import _B, _two_sides
@@ -44,6 +45,8 @@ def _kernel_reference(kind, form_id, form):
     if key not in _KERNEL_REF:
         mesh, dm, marks, s, rs, make = _mesh(kind)
         u, T = smooth_fields(dm.p2_coords)
+        if is_periodic(kind):
+            u, T = periodic_fields(dm.p2_coords, lengths_of(kind), periodic_axes(kind))
         conv = ScalarIMEXRestatement(s, 0.0, form).convection_matrix(u) @ T
         D = ScalarSgsRestatement(rs, _CS_KERNEL, _PRT_KERNEL[form_id]).residual(u, T)
         _KERNEL_REF[key] = (u, T, conv, D)

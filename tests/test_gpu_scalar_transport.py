@@ -21,6 +21,8 @@ import fem_oracle as fo
 from general_tet_mesh import CUBE, SMALL, general_tets
 from gpu_common import box, cavity_bc, context, rel, velocity_bc
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_meshes import ALL as PERIODIC
+from periodic_meshes import is_periodic, lengths_of, periodic_axes, periodic_fields, periodic_fixture
 from test_gpu_3d import box3, context3, lid_bc
 from test_imex_solver_host import IMEXRestatement
 from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
@@ -34,8 +36,12 @@ NO_PBC = (np.zeros(0, np.int32), np.zeros(0))
 
 def _mesh(kind):
     """(mesh, dm, marks, space, context factory) of a 2D box (nx, ny), the "mapped" box(8, 8), a 3D Kuhn box
-    ((nx, ny, nz), lengths) or the general tetrahedra ((nx, ny, nz), lengths, "general")"""
-    if kind == "mapped":
+    ((nx, ny, nz), lengths), the general tetrahedra ((nx, ny, nz), lengths, "general") or a periodic fixture of
+    tests/periodic_meshes.py by its name"""
+    if is_periodic(kind):
+        mesh, dm, marks = periodic_fixture(kind)
+        make = context if mesh._dim == 2 else context3
+    elif kind == "mapped":
         from test_gpu_variable_viscosity import _mapped_box
         mesh, dm, marks = _mapped_box()
         make = context
@@ -54,16 +60,20 @@ def _mesh(kind):
 
 # ---------------------------------------------------------------- 1. the kernel against the oracle
 _KERNEL_MESHES = [(4, 4), (8, 8), (3, 5), (16, 16), ((3, 2, 2), (1.0, 0.8, 0.6)), ((4, 4, 4), (1.0, 1.0, 1.0)), "mapped",
-                  SMALL + ("general", ), CUBE + ("general", )]
+                  SMALL + ("general", ), CUBE + ("general", )] + list(PERIODIC)
 
 
 @pytest.mark.parametrize("form_id,form", FORMS)
 @pytest.mark.parametrize("kind", _KERNEL_MESHES, ids=str)
 def test_scalar_convection_kernel_matches_the_oracle(kind, form_id, form):
     """weight * C(u) T for smooth, non-polynomial nodal u and T; (16, 16) and (4, 4, 4) have more than one block of 256
-    cells, the others one partly filled block; the second call returns the same bytes"""
+    cells, the others one partly filled block; the second call returns the same bytes.  The periodic fixtures (periodic
+    fields): the seam cells gather their nodal values through the identified dofs"""
     mesh, dm, marks, s, make = _mesh(kind)
     u, T = smooth_fields(dm.p2_coords)
+    if is_periodic(kind):
+        assert dm.n_p2 < mesh.num_vertices() + mesh.num_edges()
+        u, T = periodic_fields(dm.p2_coords, lengths_of(kind), periodic_axes(kind))
     want = ScalarIMEXRestatement(s, 0.0, form).convection_matrix(u) @ T
     ctx = make(mesh, dm)
     try:

@@ -28,7 +28,7 @@ from subgrid_models_host import VREMAN, WALE, SubgridModelRestatement, SubgridSc
 from test_gpu_3d import lid_bc
 from test_gpu_scalar_transport import _B, _two_sides
 from test_gpu_variable_viscosity import (_COEF, GENERAL72, GENERAL384, NO_PBC, _advance, _max_rel, _mesh, _opts, _setup,
-                                         _solve, _step, is_general)
+                                         _solve, _step, is_general, is_periodic)
 from test_heated_bodies_host import ScalarPenalRestatement, heated_set
 from test_scalar_transport_host import ScalarIMEXRestatement, smooth_fields
 from test_variable_viscosity_host import CARREAU, SMAGORINSKY, IMEXViscRestatement
@@ -36,10 +36,14 @@ from test_variable_viscosity_host import CARREAU, SMAGORINSKY, IMEXViscRestateme
 pytestmark = pytest.mark.gpu
 
 KUHN = ((3, 2, 2), (1.0, 0.8, 0.6))
-_KERNEL_MESHES = [(4, 4), (3, 5), (16, 16), "mapped", KUHN, ((4, 4, 4), (1.0, 1.0, 1.0)), GENERAL72, GENERAL384]
+_KERNEL_MESHES = [(4, 4), (3, 5), (16, 16), "mapped", KUHN, ((4, 4, 4), (1.0, 1.0, 1.0)), GENERAL72, GENERAL384] + \
+    list(tgv.PERIODIC)
 _KERNEL_LAWS = {WALE: (2.0, ), VREMAN: (1.0, )}
 _STEP_LAWS = {WALE: (0.5, ), VREMAN: (0.1, )}
 _CV = _COEF["viscous_term"]
+# amplitude of the periodic start velocity of the step cases on pchan2 / pchan3 (cells of width 1 / 4 and 1 / 3): with it
+# nu_x of both laws stays below c_v, as in the other step cases (asserted)
+_PERIODIC_AMP = 0.1
 
 
 @pytest.fixture(autouse=True)
@@ -71,7 +75,7 @@ _KERNEL_REF = {}
 def _kernel_reference(kind, law):
     if (kind, law) not in _KERNEL_REF:
         mesh, dm, marks, s, rs, make = _mesh(kind)
-        u, _ = smooth_fields(dm.p2_coords)
+        u = tgv.velocity_on(kind, dm)
         orc = SubgridModelRestatement(rs, law, _KERNEL_LAWS[law])
         _KERNEL_REF[kind, law] = (u, orc.residual(u), orc.cell_means(u), orc)
     return _KERNEL_REF[kind, law]
@@ -84,8 +88,11 @@ def test_viscosity_kernel_matches_the_restatement(kind, law):
     bytes, a weight of -1.5 rides in the kernel, no slot is written, viscosity_info counts the launches"""
     mesh, dm, marks, s, rs, make = _mesh(kind)
     u, want, means, orc = _kernel_reference(kind, law)
-    if kind == "mapped" or is_general(kind):
+    if kind == "mapped" or is_general(kind) or (is_periodic(kind) and kind.endswith("mapped")):
         assert orc.delta.max() > 1.2 * orc.delta.min()
+    if is_periodic(kind):
+        # the seam is there, and every entry of G takes part
+        assert dm.n_p1 < mesh.num_vertices() and np.abs(orc.gradient(u)).max(axis=(0, 1)).min() > 0.1
     if is_general(kind):
         # every entry of G takes part, and through a J^-1 without zeros: a transposed or mis-indexed J^-1 shows
         assert np.abs(orc.gradient(u)).max(axis=(0, 1)).min() > 0.1
@@ -157,11 +164,13 @@ def _steps(kind, typ, law, steps=4):
     params = _STEP_LAWS[law]
     ctx = make(mesh, dm)
     try:
-        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params, general=is_general(kind))
+        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params, general=is_general(kind),
+                          periodic=kind if is_periodic(kind) else None, amp=_PERIODIC_AMP)
         assert isinstance(orc.visc, SubgridModelRestatement) and orc.visc.law == law
         plain = IMEXViscRestatement(s, _COEF, "standard", visc=None)
         plain.body_force = orc.body_force
-        n = kind[0] if isinstance(kind[0], int) else (8 if kind == "mapped" else kind[0][0])
+        plain.vel[1], plain.vel[2] = orc.vel[1].copy(), orc.vel[2].copy()
+        n = 16 if is_periodic(kind) else kind[0] if isinstance(kind[0], int) else (8 if kind == "mapped" else kind[0][0])
         ts = IMEXTimeStepping(0.0, 1.0e9, typ, desired_start_time_step=0.5 / n)
         opts = _opts(ctx)
         nu_max = 0.0
@@ -187,11 +196,14 @@ def _steps(kind, typ, law, steps=4):
     ((8, 8), IMEXType.CNAB, WALE, "generic"), ((16, 16), IMEXType.SBDF2, WALE, "lattice-kernel"),
     ("mapped", IMEXType.SBDF2, VREMAN, "generic"), (KUHN, IMEXType.SBDF2, WALE, "generic"),
     (KUHN, IMEXType.SBDF2, VREMAN, "generic"), (GENERAL72, IMEXType.SBDF2, WALE, "generic"),
-    (GENERAL72, IMEXType.SBDF2, VREMAN, "generic")], ids=str)
+    (GENERAL72, IMEXType.SBDF2, VREMAN, "generic"),
+    ("pchan2", IMEXType.SBDF2, WALE, "generic"), ("pchan2", IMEXType.SBDF2, VREMAN, "generic"),
+    ("pchan3", IMEXType.SBDF2, WALE, "generic"), ("pchan3", IMEXType.SBDF2, VREMAN, "generic")], ids=str)
 def test_steps_match_the_restatement(kind, typ, law, path):
     """lid-driven cavity from rest, 4 steps: box(8, 8) on the generic right-hand side for both laws and CNAB for WALE,
     box(16, 16) on the one-launch lattice right-hand side, the mapped box (varying Delta_K), the (3, 2, 2) Kuhn box and the
-    72 general tetrahedra (3D kernels inside the steps).  One element launch per step, the stored vector is never recomputed"""
+    72 general tetrahedra (3D kernels inside the steps); the periodic channels of tests/periodic_meshes.py, no-slip on
+    their walls, from a periodic velocity at both old levels under a periodic body force.  One element launch per step, the stored vector is never recomputed"""
     info, vinfo = _steps(kind, typ, law)
     assert info["path"] == path, info
     if path == "lattice-kernel":

@@ -13,7 +13,10 @@ lattice on which the one-launch right-hand side runs.  The mapped mesh is box(8,
 smooth non-linear map (the boundary stays) before the dof map was built: cells of different size and shape, Delta_K
 varies.  3D: the Kuhn boxes of tests/test_gpu_3d.py, (3, 2, 2) on 1 x 0.8 x 0.6 and (4, 4, 4) (more than one block),
 and the general tetrahedra of tests/general_tet_mesh.py at the same two sizes (72 and 384 cells): cells of both
-orientations, Delta_K varies by a factor of 1.5 and more, no entry of any J^-1 is zero."""
+orientations, Delta_K varies by a factor of 1.5 and more, no entry of any J^-1 is zero.  Periodic dof maps: the six
+fixtures of tests/periodic_meshes.py (channels, the square and the cube without a wall, two mapped channels) with the
+periodic fields of that module; n_p1 is below the vertex count there and the seam cells read coordinates a period away
+from those of their dofs."""
 import os
 
 import numpy as np
@@ -25,6 +28,8 @@ from fem_mesh import FacetMarkers, Mesh, TaylorHoodDofMap, rectangle_mesh
 from general_tet_mesh import CUBE, SMALL, general_tets, shear_bc
 from gpu_common import box, cavity_bc, context, rel
 from imex_time_stepping import IMEXTimeStepping, IMEXType
+from periodic_meshes import ALL as PERIODIC
+from periodic_meshes import is_periodic, lengths_of, periodic_axes, periodic_fields, periodic_fixture, wall_bc
 from test_gpu_3d import box3, context3, lid_bc
 from test_scalar_transport_host import smooth_fields
 from test_variable_viscosity_host import (CARREAU, SMAGORINSKY, IMEXViscRestatement, VariableViscosityRestatement,
@@ -62,10 +67,13 @@ _CACHE = {}
 
 def _mesh(kind):
     """(mesh, dm, marks, oracle space, rule space, context factory) of a 2D box (nx, ny), "mapped", a 3D Kuhn box
-    ((nx, ny, nz), lengths) or the general tetrahedra ((nx, ny, nz), lengths, "general"); built once per kind and left
-    unchanged"""
+    ((nx, ny, nz), lengths), the general tetrahedra ((nx, ny, nz), lengths, "general") or a periodic fixture by its
+    name; built once per kind and left unchanged"""
     if kind not in _CACHE:
-        if kind == "mapped":
+        if is_periodic(kind):
+            mesh, dm, marks = periodic_fixture(kind)
+            make = context if mesh._dim == 2 else context3
+        elif kind == "mapped":
             mesh, dm, marks = _mapped_box()
             make = context
         elif isinstance(kind[0], int):
@@ -91,7 +99,14 @@ def is_general(kind):
 
 
 _KERNEL_MESHES = [(4, 4), (3, 5), (8, 8), (16, 16), "mapped", ((3, 2, 2), (1.0, 0.8, 0.6)), ((4, 4, 4), (1.0, 1.0, 1.0)),
-                  GENERAL72, GENERAL384]
+                  GENERAL72, GENERAL384] + list(PERIODIC)
+
+
+def velocity_on(kind, dm):
+    """the smooth non-polynomial velocity of the kernel tests; on a periodic fixture a periodic one"""
+    if is_periodic(kind):
+        return periodic_fields(dm.p2_coords, lengths_of(kind), periodic_axes(kind))[0]
+    return smooth_fields(dm.p2_coords)[0]
 
 
 def _max_rel(got, want):
@@ -105,10 +120,12 @@ def test_viscosity_kernel_matches_the_restatement(kind, law):
     """weight * V(u) and the cell means of nu_x for the smooth non-polynomial velocity; a second call returns the same
     bytes, the weight rides in the kernel, no stored state is touched, bad slots raise"""
     mesh, dm, marks, s, rs, make = _mesh(kind)
-    u, _ = smooth_fields(dm.p2_coords)
+    u = velocity_on(kind, dm)
     orc = VariableViscosityRestatement(rs, law, _LAWS[law])
     want, means = orc.residual(u), orc.cell_means(u)
-    if kind == "mapped" or is_general(kind):
+    if is_periodic(kind):
+        assert dm.n_p1 < mesh.num_vertices()
+    if kind == "mapped" or is_general(kind) or (is_periodic(kind) and kind.endswith("mapped")):
         assert orc.delta.max() > 1.2 * orc.delta.min()
     ctx = make(mesh, dm)
     try:
@@ -164,13 +181,21 @@ def test_bad_laws_and_parameters_raise():
 
 
 # ---------------------------------------------------------------- 2. steps against the restatement
-def _setup(ctx, dm, marks, s, rs, law, params, form="standard", general=False):
+def _setup(ctx, dm, marks, s, rs, law, params, form="standard", general=False, periodic=None, amp=1.0):
     """coefficients, cavity / lid boundary values and the body force of test_gpu_scalar_transport._drive; ``general``:
-    the solenoidal shear of general_tet_mesh.shear_bc on every face (a lid on an oblique face has a net flux)"""
+    the solenoidal shear of general_tet_mesh.shear_bc on every face (a lid on an oblique face has a net flux);
+    ``periodic``: the name of a periodic fixture -- no-slip on its walls, a periodic body force, and a periodic velocity
+    at both old levels, ``amp`` times that of tests/periodic_meshes.py (there is no lid to set the fluid in motion)"""
     X = dm.p2_coords
     dim = X.shape[1]
-    vbc = cavity_bc(dm, marks) if dim == 2 else (shear_bc if general else lid_bc)(dm, marks)
-    f = np.stack([np.sin(np.pi * X[:, 1]), -1.0 + X[:, 0], 0.5 * X[:, 1]][:dim], axis=1).ravel()
+    if periodic:
+        vbc = wall_bc(periodic)
+        u = amp * periodic_fields(X, lengths_of(periodic), periodic_axes(periodic))[0]
+        f = 0.6 * np.roll(u.reshape(-1, dim), 1, axis=1).ravel()
+        u[vbc[0]] = 0.0
+    else:
+        vbc = cavity_bc(dm, marks) if dim == 2 else (shear_bc if general else lid_bc)(dm, marks)
+        f = np.stack([np.sin(np.pi * X[:, 1]), -1.0 + X[:, 0], 0.5 * X[:, 1]][:dim], axis=1).ravel()
     visc = VariableViscosityRestatement(rs, law, params) if law else None
     orc = IMEXViscRestatement(s, _COEF, form, visc=visc)
     orc.body_force = f
@@ -180,6 +205,10 @@ def _setup(ctx, dm, marks, s, rs, law, params, form="standard", general=False):
     ctx.set_state(nat.BODY_FORCE, f)
     if law is not None:
         ctx.set_viscosity_law(law, params)
+    if periodic:
+        for lvl, slot, scale in ((1, nat.U1, 1.0), (2, nat.U2, 0.9)):
+            orc.vel[lvl] = scale * u
+            ctx.set_state(slot, scale * u)
     return orc, vbc
 
 
@@ -221,8 +250,9 @@ def _run(kind, typ, law, params, steps=4, k=None):
     mesh, dm, marks, s, rs, make = _mesh(kind)
     ctx = make(mesh, dm)
     try:
-        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params, general=is_general(kind))
-        n = kind[0] if isinstance(kind[0], int) else (8 if kind == "mapped" else kind[0][0])
+        orc, vbc = _setup(ctx, dm, marks, s, rs, law, params, general=is_general(kind),
+                          periodic=kind if is_periodic(kind) else None)
+        n = 16 if is_periodic(kind) else kind[0] if isinstance(kind[0], int) else (8 if kind == "mapped" else kind[0][0])
         ts = IMEXTimeStepping(0.0, 1.0e9, typ, desired_start_time_step=k or 0.5 / n)
         opts = _opts(ctx)
         for _ in range(steps):
@@ -269,12 +299,15 @@ def test_steps_with_smagorinsky_match_the_restatement(typ, newtonian_ustar):
     (((3, 2, 2), (1.0, 0.8, 0.6)), SMAGORINSKY, (_CS_STEPS, ), "generic"),
     (((3, 2, 2), (1.0, 0.8, 0.6)), CARREAU, (0.008, 1.0, 0.5), "generic"),
     (GENERAL72, SMAGORINSKY, (_CS_STEPS, ), "generic"), (GENERAL72, CARREAU, (0.008, 1.0, 0.5), "generic"),
-    ((8, 8), CARREAU, (0.008, 1.0, 0.5), "generic")], ids=str)
+    ((8, 8), CARREAU, (0.008, 1.0, 0.5), "generic"),
+    ("pchan2", SMAGORINSKY, (_CS_STEPS, ), "generic"), ("pchan2", CARREAU, (0.008, 1.0, 0.5), "generic"),
+    ("pchan3", SMAGORINSKY, (_CS_STEPS, ), "generic"), ("pchan3", CARREAU, (0.008, 1.0, 0.5), "generic")], ids=str)
 def test_sbdf2_steps_on_the_other_meshes_and_the_carreau_law(kind, law, params, path):
     """SBDF2, 4 steps: box(16, 16) runs the one-launch lattice right-hand side and the two extra launches after it;
     the mapped mesh has a varying Delta_K; the Kuhn box and the general tetrahedra run the 3D kernel inside the steps; the
     Carreau law (zero
-    shear viscosity c_v = 0.01, nu_inf = 0.002) in both dimensions"""
+    shear viscosity c_v = 0.01, nu_inf = 0.002) in both dimensions; the periodic channels, no-slip on their walls, from a
+    periodic velocity under a periodic body force"""
     orc, info, vinfo = _run(kind, IMEXType.SBDF2, law, params)
     assert info["path"] == path, info
     if path == "lattice-kernel":

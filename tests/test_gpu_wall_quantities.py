@@ -30,6 +30,7 @@ import wall_quantities as wq
 from fem_mesh import TaylorHoodDofMap, box_mesh, rectangle_mesh
 from general_tet_mesh import LARGE, SMALL, general_tets
 from gpu_common import context
+from periodic_meshes import periodic_fixture
 from test_derived_fields_host import polynomial_fields, polynomial_nodal, smooth_fields
 from test_flow_statistics_host import periodic_square
 from test_wall_quantities_host import (CARREAU, EPS, OPTS, SMAGORINSKY, analytic_rows, boundary_facets, group_sums,
@@ -37,8 +38,9 @@ from test_wall_quantities_host import (CARREAU, EPS, OPTS, SMAGORINSKY, analytic
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-MESHES = ("rect6x4", "rect96x40", "box3x2x2", "box8x6x6", "fixture", "periodic", "general72", "general900")
-EXPECTED_FACETS = dict(rect6x4=20, rect96x40=272, box3x2x2=64, box8x6x6=528, general72=64, general900=340)
+MESHES = ("rect6x4", "rect96x40", "box3x2x2", "box8x6x6", "fixture", "periodic", "general72", "general900", "pchan3")
+# (pchan3: the 2 x 18 wall faces and the 4 x 12 faces of the periodic sides, which are boundary faces of the mesh)
+EXPECTED_FACETS = dict(pchan3=84, rect6x4=20, rect96x40=272, box3x2x2=64, box8x6x6=528, general72=64, general900=340)
 N_GROUPS = 4                                           # interleaved ids 0, 1, 3; group 2 stays empty
 LAWS = {"smagorinsky": (SMAGORINSKY, (0.17, )), "carreau": (CARREAU, (0.8, 1.3, 0.4))}
 _CACHE = {}
@@ -58,6 +60,8 @@ def _mesh(name):
         mesh = read_msh(os.path.join(HERE, "golden", "square_v41.msh"))[0]
     elif name == "periodic":
         return periodic_square(8)
+    elif name == "pchan3":
+        return periodic_fixture(name)[:2]
     elif name in ("general72", "general900"):
         return general_tets(*(SMALL if name == "general72" else LARGE))[:2]
     else:

@@ -119,6 +119,9 @@ def bodies_2d(name, moving=False):
         return [Box((0.55, 0.4), (0.17, 0.23), **kw)]
     if name == "half-space":
         return [HalfSpace((0.3, 0.2), (0.6, 0.8), **kw)]
+    if name == "seam":
+        # for the periodic fixtures of tests/periodic_meshes.py: one disc inside the domain, one cut by the side x = 0
+        return [Ball((0.55, 0.4), 0.16, **kw), Ball((0.0, 0.33), 0.19, velocity=(-0.1, 0.25), angular=-0.4)]
     assert name == "overlap"
     return [Ball((0.43, 0.57), 0.21, **kw), Box((0.55, 0.4), (0.17, 0.23), velocity=(-0.1, 0.25), angular=-0.4)]
 
@@ -131,6 +134,9 @@ def bodies_3d(name, moving=False):
         return [Box((0.55, 0.4, 0.33), (0.17, 0.23, 0.19), **kw)]
     if name == "half-space":
         return [HalfSpace((0.3, 0.2, 0.1), (0.48, 0.64, 0.6), **kw)]
+    if name == "seam":
+        return [Ball((0.55, 0.4, 0.3), 0.17, **kw),
+                Ball((0.0, 0.42, 0.33), 0.21, velocity=(-0.1, 0.25, 0.05), angular=(0.0, -0.4, 0.2))]
     assert name == "overlap"
     return [Ball((0.43, 0.37, 0.31), 0.23, **kw),
             Box((0.55, 0.4, 0.33), (0.17, 0.23, 0.19), velocity=(-0.1, 0.25, 0.05), angular=(0.0, -0.4, 0.2))]
