@@ -739,6 +739,42 @@ int nsfem_body_forces(nsfem_ctx* ctx, int velocity_slot, double* out);
  * recomputed with bodies set, 0} */
 int nsfem_body_info(nsfem_ctx* ctx, int64_t out[4]);
 
+/* ---- wall-stress models in the IMEX step: wall-modelled LES (new; the reference resolves every wall).
+ * A modelled boundary facet f of cell K keeps u.n = 0 only (a component-wise Dirichlet row set by the caller); its
+ * tangential stress comes from a law of the wall sampled inside the flow.  n = the unit normal out of K.  Rule
+ * (x_q, w_q): 3-point Gauss-Legendre on an edge, the symmetric 6-point rule of degree 4 on a face (part of the
+ * definition).  Per quadrature point the caller fixes a sample cell, the barycentric coordinates lambda_s of the sample
+ * point x_s in it and a wall distance y > 0:
+ *   U = u(x_s) - u_w,  u_par = U - (U.n) n,  Re_y = y |u_par| / nu,  r(Re_y) = y+^2 / Re_y, r(0) = 1
+ *   W(u)_(i,a) = sum_f sum_q w_q (nu r / y) u_par,a phi_i(x_q)
+ * nu = the viscous_term coefficient.  W has the sign of c_c conv(u): nsfem_step_imex stores and extrapolates
+ * N(u) = c_c conv(u) + V(u) + B(u) + W(u), W added third; matrices, the CG solve and the one-launch right-hand side
+ * stay as they are.
+ *   law 1  Werner-Wengle   params = {A, B}: y+ = sqrt(Re_y) for Re_y <= A^(2/(1-B)), else (Re_y / A)^(1/(1+B))
+ *   law 2  Reichardt       params = {kappa, C}: u+ = log1p(kappa y+)/kappa + C (-expm1(-y+/11) - (y+/11) exp(-y+/3)),
+ *                          y+ u+(y+) = Re_y solved by 5 Newton steps from the law-1 value (A = 8.3, B = 1/7), each step
+ *                          floored at a quarter of the iterate; the count is the same at every point
+ * facet_cell, facet_local [n_facets] (local = index of the vertex opposite the facet), sample_cell [n_facets][NQ],
+ * sample_lambda [n_facets][NQ][dim + 1], sample_y [n_facets][NQ] with NQ = 3 (2D) / 6 (3D) in the order of the rule,
+ * wall_velocity [n_facets][dim] or NULL (u_w = 0).  law = 0 or n_facets = 0 switches the term off (the other arguments
+ * may be NULL): nothing is launched after that.  A change of the law, its parameters or any array invalidates the
+ * stored vectors; the same data again does not.  NSFEM_ERR_ARG: contexts with a communicator, unknown laws, parameters
+ * out of range, cells or local indices out of range, y <= 0, non-finite entries; nsfem_step_ipcs and nsfem_step_bdf
+ * refuse to run while a model is set.  nu is always a number: nsfem_set_coeffs refuses a viscous coefficient of None. */
+int nsfem_set_wall_model(nsfem_ctx* ctx, int law, const double params[4], int32_t n_facets, const int32_t* facet_cell,
+                         const int32_t* facet_local, const int32_t* sample_cell, const double* sample_lambda,
+                         const double* sample_y, const double* wall_velocity);
+/* Test hook: out_host [dim n_p2] = weight * W(u) for u = velocity_slot (NSFEM_U0, U1, U2 or USTAR) -- the facet kernel
+ * plus the per-node sums, no Dirichlet rows; no stored state is touched.  Two calls on the same state return the same
+ * bytes.  NSFEM_ERR_ARG: no model set, other slots. */
+int nsfem_wall_model_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host);
+/* out [n_facets][dim + 4] in input order, per facet: |f|, int tau_w [dim] with tau_w = (nu r / y) u_par, int u_tau with
+ * u_tau = nu y+ / y, int y+, max y+ over the facet's quadrature points */
+int nsfem_wall_model_facets(nsfem_ctx* ctx, int velocity_slot, double* out);
+/* out = {modelled facets, facet-kernel launches so far (steps and hooks), stored vectors N(u2) that had to be
+ * recomputed with a model set, the law} */
+int nsfem_wall_model_info(nsfem_ctx* ctx, int64_t out[4]);
+
 /* ---- heated immersed bodies: scalar penalisation in the convection kernel of nsfem_step_scalar_imex (new).
  * Each body s of the set given to nsfem_set_bodies gets a thermal flag theta_s in {0, 1} and a temperature T_s; one
  * eta_T > 0 holds for the set.  The scalar equation gains (chi theta / eta_T)(T - T_s), as the vector

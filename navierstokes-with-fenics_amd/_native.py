@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "nsfem_dynamic_lagrangian_info",
     "nsfem_set_bodies", "nsfem_move_bodies", "nsfem_body_residual", "nsfem_body_mask_cells", "nsfem_body_forces",
     "nsfem_body_info",
+    "nsfem_set_wall_model", "nsfem_wall_model_residual", "nsfem_wall_model_facets", "nsfem_wall_model_info",
     "nsfem_set_body_temperatures", "nsfem_body_scalar_residual", "nsfem_body_heat", "nsfem_body_heat_info",
     "nsfem_set_point_locator", "nsfem_locate_points", "nsfem_eval_points",
     "nsfem_tracers_set", "nsfem_tracers_advect", "nsfem_tracers_get", "nsfem_tracers_info",
@@ -242,6 +243,11 @@ def load_library(path=None):
         "nsfem_body_mask_cells": (C.c_int, [vp, pd]),
         "nsfem_body_forces": (C.c_int, [vp, C.c_int, pd]),
         "nsfem_body_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
+        "nsfem_set_wall_model": (C.c_int, [vp, C.c_int, pd, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), pd, pd, pd]),
+        "nsfem_wall_model_residual": (C.c_int, [vp, C.c_int, dbl, pd]),
+        "nsfem_wall_model_facets": (C.c_int, [vp, C.c_int, pd]),
+        "nsfem_wall_model_info": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "nsfem_set_body_temperatures": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_int32), pd, dbl]),
         "nsfem_body_scalar_residual": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dbl, C.c_int, pd]),
         "nsfem_body_heat": (C.c_int, [vp, C.c_int, pd]),
@@ -809,6 +815,52 @@ class NsfemContext:
         out = (C.c_int64 * 4)()
         self._check(self._lib.nsfem_body_info(self._h, out))
         return dict(bodies=int(out[0]), element_launches=int(out[1]), recomputed=int(out[2]))
+
+    # -- wall-stress models (the explicit term W(u) of the IMEX step) ---------------------
+    def set_wall_model(self, law, params=None, facet_cell=(), facet_local=(), sample_cell=(), sample_lambda=(),
+                       sample_y=(), wall_velocity=None):
+        """law 0 none, 1 Werner-Wengle (A, B), 2 Reichardt (kappa, C); facet_cell, facet_local [nf], sample_cell
+        [nf, NQ], sample_lambda [nf, NQ, dim + 1], sample_y [nf, NQ], wall_velocity [nf, dim] or None (the arrays of
+        ``wall_models.WallModel.build``).  Law 0 or no facet switches the term off"""
+        fc = np.ascontiguousarray(facet_cell, dtype=np.int32).ravel()
+        if int(law) == 0 or fc.size == 0:
+            self._check(self._lib.nsfem_set_wall_model(self._h, 0, None, 0, None, None, None, None, None, None))
+            return
+        nq, nv = (3 if self.dim == 2 else 6), self.dim + 1
+        fl = np.ascontiguousarray(facet_local, dtype=np.int32).ravel()
+        sc = np.ascontiguousarray(sample_cell, dtype=np.int32).ravel()
+        sl = np.ascontiguousarray(sample_lambda, dtype=np.float64).ravel()
+        sy = np.ascontiguousarray(sample_y, dtype=np.float64).ravel()
+        assert fl.size == fc.size and sc.size == fc.size * nq and sy.size == sc.size and sl.size == sc.size * nv
+        p = np.zeros(4)
+        params = tuple(params or ())
+        p[:len(params)] = params
+        uw = None
+        if wall_velocity is not None:
+            uw = np.ascontiguousarray(wall_velocity, dtype=np.float64).ravel()
+            assert uw.size == fc.size * self.dim
+        self._check(self._lib.nsfem_set_wall_model(self._h, int(law), _dp(p), fc.size, _ip(fc), _ip(fl), _ip(sc),
+                                                   _dp(sl), _dp(sy), None if uw is None else _dp(uw)))
+
+    def wall_model_residual(self, velocity_slot=U1, weight=1.0):
+        """test hook: weight * W(u), interleaved [dim * n_p2] (facet kernel + node sums; no stored state touched)"""
+        out = np.empty(self.dim * self.n_p2, dtype=np.float64)
+        self._check(self._lib.nsfem_wall_model_residual(self._h, int(velocity_slot), float(weight), _dp(out)))
+        return out
+
+    def wall_model_facets(self, velocity_slot=U0):
+        """[n_facets, dim + 4] in input order: |f|, int tau_w [dim], int u_tau, int y+, max y+"""
+        n = self.wall_model_info()["facets"]
+        out = np.empty((max(n, 1), self.dim + 4), dtype=np.float64)
+        self._check(self._lib.nsfem_wall_model_facets(self._h, int(velocity_slot), _dp(out)))
+        return out[:n]
+
+    def wall_model_info(self):
+        """dict(facets, launches, recomputed, law): modelled facets, facet-kernel launches so far, how often a stored
+        explicit vector had to be recomputed with a model set, and the law"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.nsfem_wall_model_info(self._h, out))
+        return dict(facets=int(out[0]), launches=int(out[1]), recomputed=int(out[2]), law=int(out[3]))
 
     # -- heated immersed bodies (scalar penalisation in the convection kernel) -----------
     def set_body_temperatures(self, thermal, temperatures, eta_scalar=1.0):

@@ -2434,6 +2434,7 @@ extern "C" int nsfem_step_ipcs(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
   NSFEM_REQUIRE(ctx->alpha[0] != 0.0, "the pressure-correction scheme needs alpha0 != 0");
   NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
   NSFEM_REQUIRE(ctx->bodies.cur.n == 0, "immersed bodies: only nsfem_step_imex takes bodies (remove them with n = 0 first)");
+  NSFEM_REQUIRE(ctx->wm.dev.law == 0, "wall model: only nsfem_step_imex takes a wall model (switch it off with law 0 first)");
   NSFEM_REQUIRE(!ctx->imex_active, "IMEX coefficients are set (nsfem_set_imex): call nsfem_set_bdf or nsfem_step_imex");
   // ---- diffusion step: Newton
   momentum_begin_step(ctx);
@@ -2770,10 +2771,10 @@ static const double* dynamic_slot_field(nsfem_ctx* c, int velocity_slot) {
   return c->dyn.buf.field.p;
 }
 
-// The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u).  The convective part
+// The explicit vector of a level, stated ONCE:  N(u) = c_c conv(u) (+ M (gam x u)) + V(u) + B(u) + W(u).  The convective part
 // (with the Coriolis vector of the level) is in `n` already -- imex_rhs for u1, imex_form_n2 for u2; this adds the rest,
-// V (nsfem_set_viscosity_law) first and B (nsfem_set_bodies) second, each only when switched on: with law 0 / without
-// bodies nothing is launched.  Each term is TWO launches, after imex_rhs (which runs unchanged on either path) and
+// V (nsfem_set_viscosity_law) first, B (nsfem_set_bodies) second and W (nsfem_set_wall_model) third, each only when
+// switched on: with law 0 / without bodies / without a wall model nothing is launched.  Each term is TWO launches, after imex_rhs (which runs unchanged on either path) and
 // BEFORE the Dirichlet rows are set: the element kernel on u (weight 1, element vectors node-sorted in mesh.rbuf) and
 // k_visc_gather, which forms v = the per-node sums from zero in ascending cell order and then, per entry,
 // n <- n + v,  rhs <- rhs - b0 v  (two roundings, no contraction).  So with a law and bodies the order is viscosity
@@ -2797,6 +2798,13 @@ static void imex_explicit_add(nsfem_ctx* c, const double* u, bool level_n, bool 
     launch_viscosity_gather(c->stream, c->mesh, b0, n, rhs);
     ++c->bodies.launches;
   }
+  // W (nsfem_set_wall_model) third, the same two-roundings rule: the facet kernel, then its gather over the nodes on
+  // modelled facets
+  if (c->wm.dev.law != 0) {
+    launch_wall_model_facets(c->stream, c->mesh, c->wm.dev, u, c->coef[2], 1.0);
+    launch_wall_model_gather(c->stream, c->mesh, c->wm.dev, b0, n, rhs);
+    ++c->wm.launches;
+  }
 }
 
 // n2 <- N(u2) from scratch (nsfem_step_imex where the stored N2 does not serve; nsfem_imex_rhs always).  gam2: the
@@ -2814,6 +2822,7 @@ nsfem_ctx::ImexKey nsfem_ctx::ImexKey::of(const nsfem_ctx& c, const double gam[3
   k.cc = cc_of(&c);
   k.visc = c.visc.epoch;
   k.body = c.bodies.epoch;
+  k.wall = c.wm.epoch;
   std::memcpy(k.gam, gam, sizeof(k.gam));
   return k;
 }
@@ -2824,6 +2833,8 @@ static void imex_require_supported(nsfem_ctx* c) {
                 "immersed bodies: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(c->visc.law == 0 || !c->comm,
                 "variable viscosity: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(c->wm.dev.law == 0 || !c->comm,
+                "wall model: contexts with a communicator (partitioned meshes) are not supported");
   NSFEM_REQUIRE(c->imex_rot.treatment == 1 || (!coriolis_active(c) && !euler_active(c)),
                 "IMEX pressure correction: rotating frames (Coriolis / Euler terms) are not supported");
 }
@@ -2869,6 +2880,7 @@ extern "C" int nsfem_step_imex(nsfem_ctx* ctx, const nsfem_step_opts* opts, nsfe
       if (ctx->imex_rot.treatment == 1 && ctx->conv_n2_valid) ++ctx->imex_rot.recomputed;
       if (ctx->visc.law != 0) ++ctx->visc.recomputed;
       if (ctx->bodies.cur.n != 0) ++ctx->bodies.recomputed;
+      if (ctx->wm.dev.law != 0) ++ctx->wm.recomputed;
       if (ctx->distributed() && ctx->ghost_v.p) launch_zero_ghost(s, nv, ctx->mask_v.p, ctx->state[NSFEM_CONV_N2].p);
       ctx->conv_n2_valid = true;
     }
@@ -3502,6 +3514,181 @@ extern "C" int nsfem_body_info(nsfem_ctx* ctx, int64_t out[4]) {
   API_END(ctx)
 }
 
+// ---------------------------------------------------------------- wall-stress models
+// validates everything on the host first, then replaces the resident set.  The node CSR of the gather is built here,
+// from the host copy of the P2 dof map: the nodes on modelled facets ascending, per node its (facet, local) entries in
+// ascending facet order.  Switching off (law 0 or no facet) keeps the buffers
+extern "C" int nsfem_set_wall_model(nsfem_ctx* ctx, int law, const double params[4], int32_t n_facets,
+                                    const int32_t* facet_cell, const int32_t* facet_local, const int32_t* sample_cell,
+                                    const double* sample_lambda, const double* sample_y, const double* wall_velocity) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx, "null context");
+  NSFEM_REQUIRE(law == 0 || law == 1 || law == 2, "wall model: unknown law (0 none, 1 Werner-Wengle, 2 Reichardt)");
+  NSFEM_REQUIRE(n_facets >= 0, "wall model: n_facets < 0");
+  nsfem_ctx::WallModel& W = ctx->wm;
+  WallModelDev& d = W.dev;
+  if (law == 0 || n_facets == 0) {
+    if (d.law != 0) ++W.epoch;
+    d.law = 0;
+    d.n_facets = d.n_nodes = 0;
+    W.h_int.clear();
+    W.h_dbl.clear();
+  } else {
+    NSFEM_REQUIRE(!ctx->comm, "wall model: contexts with a communicator (partitioned meshes) are not supported");
+    NSFEM_REQUIRE(params, "wall model: the law needs its parameters");
+    NSFEM_REQUIRE(facet_cell && facet_local && sample_cell && sample_lambda && sample_y, "null argument");
+    double p[4] = {0.0, 0.0, 0.0, 0.0}, start[3] = {8.3, 1.0 / (1.0 + 1.0 / 7.0), std::pow(8.3, 2.0 / (1.0 - 1.0 / 7.0))};
+    if (law == 1) {
+      NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] > 0.0, "Werner-Wengle: A must be finite and > 0");
+      NSFEM_REQUIRE(std::isfinite(params[1]) && params[1] > 0.0 && params[1] < 1.0,
+                    "Werner-Wengle: B must be finite and in (0, 1)");
+      start[0] = params[0];
+      start[1] = 1.0 / (1.0 + params[1]);
+      start[2] = std::pow(params[0], 2.0 / (1.0 - params[1]));
+    } else {
+      NSFEM_REQUIRE(std::isfinite(params[0]) && params[0] > 0.0, "Reichardt: kappa must be finite and > 0");
+      NSFEM_REQUIRE(std::isfinite(params[1]) && params[1] >= 0.0, "Reichardt: C must be finite and >= 0");
+    }
+    p[0] = params[0];
+    p[1] = params[1];
+    const int dim = ctx->mesh.dim, nv = dim + 1, nq = wall_model_points(dim), nf2 = wall_model_facet_nodes(dim);
+    const int nl2 = dim == 2 ? 6 : 10;
+    const size_t nf = (size_t)n_facets;
+    for (size_t f = 0; f < nf; ++f) {
+      NSFEM_REQUIRE(facet_cell[f] >= 0 && facet_cell[f] < ctx->mesh.n_cells, "wall model: facet cell out of range");
+      NSFEM_REQUIRE(facet_local[f] >= 0 && facet_local[f] <= dim, "wall model: local facet index out of range");
+      for (int q = 0; q < nq; ++q) {
+        const size_t fq = f * nq + q;
+        NSFEM_REQUIRE(sample_cell[fq] >= 0 && sample_cell[fq] < ctx->mesh.n_cells, "wall model: sample cell out of range");
+        NSFEM_REQUIRE(std::isfinite(sample_y[fq]) && sample_y[fq] > 0.0, "wall model: wall distance must be finite and > 0");
+        for (int v = 0; v < nv; ++v)
+          NSFEM_REQUIRE(std::isfinite(sample_lambda[fq * nv + v]), "wall model: non-finite sample coordinate");
+      }
+      for (int a = 0; a < dim && wall_velocity; ++a)
+        NSFEM_REQUIRE(std::isfinite(wall_velocity[f * dim + a]), "wall model: non-finite wall velocity");
+    }
+    // what the call took, in one integer and one double vector: the same data again changes nothing
+    std::vector<int32_t> h_int;
+    std::vector<double> h_dbl;
+    h_int.push_back(law);
+    h_int.push_back(wall_velocity ? 1 : 0);
+    h_int.insert(h_int.end(), facet_cell, facet_cell + nf);
+    h_int.insert(h_int.end(), facet_local, facet_local + nf);
+    h_int.insert(h_int.end(), sample_cell, sample_cell + nf * nq);
+    h_dbl.insert(h_dbl.end(), p, p + 4);
+    h_dbl.insert(h_dbl.end(), sample_lambda, sample_lambda + nf * nq * nv);
+    h_dbl.insert(h_dbl.end(), sample_y, sample_y + nf * nq);
+    if (wall_velocity) h_dbl.insert(h_dbl.end(), wall_velocity, wall_velocity + nf * dim);
+    const bool same = d.law != 0 && h_int == W.h_int && h_dbl.size() == W.h_dbl.size() &&
+                      std::memcmp(h_dbl.data(), W.h_dbl.data(), sizeof(double) * h_dbl.size()) == 0;
+    if (!same) {
+      // the node CSR: (node, facet NF2 + local) pairs sorted by node, then by facet
+      std::vector<std::pair<int32_t, int32_t>> pairs;
+      pairs.reserve(nf * nf2);
+      const int ends2[3][2] = {{1, 2}, {0, 2}, {0, 1}};                               // UFC edges
+      const int ends3[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
+      for (size_t f = 0; f < nf; ++f) {
+        const int32_t* p2 = &ctx->h_p2map[(size_t)facet_cell[f] * nl2];
+        const int opp = facet_local[f];
+        int t = 0;
+        for (int k = 0; k < nl2; ++k) {
+          bool on = k != opp;
+          if (k >= nv) {
+            const int* e = dim == 2 ? ends2[k - nv] : ends3[k - nv];
+            on = e[0] != opp && e[1] != opp;
+          }
+          if (on) pairs.emplace_back(p2[k], (int32_t)(f * nf2 + t++));
+        }
+      }
+      std::sort(pairs.begin(), pairs.end());
+      std::vector<int32_t> nodes, nptr, entry;
+      for (size_t i = 0; i < pairs.size(); ++i) {
+        if (i == 0 || pairs[i].first != pairs[i - 1].first) {
+          nodes.push_back(pairs[i].first);
+          nptr.push_back((int32_t)i);
+        }
+        entry.push_back(pairs[i].second);
+      }
+      nptr.push_back((int32_t)pairs.size());
+      hipStream_t s = ctx->stream;
+      d.law = 0;                                  // (off until everything is resident)
+      d.fcell.upload(facet_cell, nf, s);
+      d.flocal.upload(facet_local, nf, s);
+      d.scell.upload(sample_cell, nf * nq, s);
+      d.slam.upload(sample_lambda, nf * nq * nv, s);
+      d.sy.upload(sample_y, nf * nq, s);
+      if (wall_velocity) d.uw.upload(wall_velocity, nf * dim, s);
+      d.nodes.upload(nodes.data(), nodes.size(), s);
+      d.nptr.upload(nptr.data(), nptr.size(), s);
+      d.entry.upload(entry.data(), entry.size(), s);
+      NSFEM_HIP(hipStreamSynchronize(s));         // the host vectors die with the call
+      if (d.fvec.n != nf * nf2 * dim) d.fvec.alloc(nf * nf2 * dim);
+      if (d.rows.n != nf * wall_model_row(dim)) d.rows.alloc(nf * wall_model_row(dim));
+      d.have_uw = wall_velocity != nullptr;
+      d.n_facets = n_facets;
+      d.n_nodes = (int32_t)nodes.size();
+      std::memcpy(d.p, p, sizeof(p));
+      std::memcpy(d.start, start, sizeof(start));
+      d.law = law;
+      W.h_int.swap(h_int);
+      W.h_dbl.swap(h_dbl);
+      // (the stored explicit vectors belong to the model they were evaluated with; the model enters no captured
+      // Krylov body -- its launches precede the solve --, so graph_epoch stays)
+      ++W.epoch;
+    }
+  }
+  API_END(ctx)
+}
+
+static void wall_model_require(nsfem_ctx* ctx, int velocity_slot) {
+  NSFEM_REQUIRE(!ctx->comm, "wall model: contexts with a communicator (partitioned meshes) are not supported");
+  NSFEM_REQUIRE(ctx->wm.dev.law != 0, "wall model: no model set (nsfem_set_wall_model)");
+  // (nu = coef[2] is always a number: nsfem_set_coeffs refuses a viscous coefficient of None)
+  require_velocity_slot(velocity_slot);
+}
+
+extern "C" int nsfem_wall_model_residual(nsfem_ctx* ctx, int velocity_slot, double weight, double* out_host) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out_host, "null argument");
+  wall_model_require(ctx, velocity_slot);
+  require_finite_weight(weight);
+  hipStream_t s = ctx->stream;
+  const int64_t nv = nvel(ctx);
+  hook_to_host(ctx, nv, out_host, [&](double* out) {
+    NSFEM_HIP(hipMemsetAsync(out, 0, sizeof(double) * nv, s));
+    launch_wall_model_facets(s, ctx->mesh, ctx->wm.dev, ctx->state[velocity_slot].p, ctx->coef[2], weight);
+    launch_wall_model_gather(s, ctx->mesh, ctx->wm.dev, 0.0, out, nullptr);
+    ++ctx->wm.launches;
+  });
+  API_END(ctx)
+}
+
+extern "C" int nsfem_wall_model_facets(nsfem_ctx* ctx, int velocity_slot, double* out) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  wall_model_require(ctx, velocity_slot);
+  hipStream_t s = ctx->stream;
+  const WallModelDev& d = ctx->wm.dev;
+  // (the facet vectors land in the model's own buffer, which every user fills before it reads; the resident order is
+  // the input order)
+  launch_wall_model_facets(s, ctx->mesh, d, ctx->state[velocity_slot].p, ctx->coef[2], 1.0);
+  ++ctx->wm.launches;
+  NSFEM_HIP(hipMemcpyAsync(out, d.rows.p, sizeof(double) * (size_t)d.n_facets * wall_model_row(ctx->mesh.dim),
+                           hipMemcpyDeviceToHost, s));
+  NSFEM_HIP(hipStreamSynchronize(s));
+  API_END(ctx)
+}
+
+extern "C" int nsfem_wall_model_info(nsfem_ctx* ctx, int64_t out[4]) {
+  API_BEGIN
+  NSFEM_REQUIRE(ctx && out, "null argument");
+  out[0] = ctx->wm.dev.law != 0 ? ctx->wm.dev.n_facets : 0;
+  out[1] = ctx->wm.launches;
+  out[2] = ctx->wm.recomputed;
+  out[3] = ctx->wm.dev.law;
+  API_END(ctx)
+}
+
 // ---------------------------------------------------------------- heated bodies
 extern "C" int nsfem_set_body_temperatures(nsfem_ctx* ctx, int32_t n, const int32_t* thermal, const double* temperature,
                                            double eta_T) {
@@ -3969,6 +4156,7 @@ static double bdf_residual(nsfem_ctx* c) {
 static void monolithic_setup(nsfem_ctx* ctx) {
   NSFEM_REQUIRE(ctx->visc.law == 0, "variable viscosity: only nsfem_step_imex takes a viscosity law (set law 0 first)");
   NSFEM_REQUIRE(ctx->bodies.cur.n == 0, "immersed bodies: only nsfem_step_imex takes bodies (remove them with n = 0 first)");
+  NSFEM_REQUIRE(ctx->wm.dev.law == 0, "wall model: only nsfem_step_imex takes a wall model (switch it off with law 0 first)");
   NSFEM_REQUIRE(!ctx->distributed() || ctx->schur_singular < 0 || ctx->schur_additive,
                 "partitioned meshes take the algebraic Schur Laplacian as additive rank parts "
                 "(nsfem_mg_set_schur_mode)");

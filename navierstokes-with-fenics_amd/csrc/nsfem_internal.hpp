@@ -780,6 +780,29 @@ void launch_wall_facets(hipStream_t s, const MeshDev& m, int nf, const int32_t* 
                         const double* u, const double* p, const double* T, const WallParams& w, double* rows);
 // ONE launch: out[g][NW] = sum of the rows goff[g] <= f < goff[g + 1], one workgroup per group
 void launch_wall_reduce(hipStream_t s, int dim, int n_groups, const int32_t* goff, const double* rows, double* out);
+// ---- wall-stress models (wallmodel.hip, nsfem_set_wall_model): the resident facet set of the explicit term W(u), its
+// samples, the node CSR of the gather and the two buffers the launches write.  NQ = 3 / 6 points per facet, NF2 = 3 / 6
+// P2 nodes per facet.  law 0: the term is off (the buffers stay for the next call that needs them)
+inline int wall_model_points(int dim) { return dim == 2 ? 3 : 6; }
+inline int wall_model_facet_nodes(int dim) { return dim == 2 ? 3 : 6; }
+inline int wall_model_row(int dim) { return dim + 4; }
+struct WallModelDev {
+  int law = 0;                                // 1 Werner-Wengle (p = A, B), 2 Reichardt (p = kappa, C)
+  double p[4] = {0.0, 0.0, 0.0, 0.0};
+  double start[3] = {0.0, 0.0, 0.0};          // the Werner-Wengle triple A, 1 / (1 + B), A^(2 / (1 - B)) the kernel takes
+  int32_t n_facets = 0, n_nodes = 0;
+  bool have_uw = false;
+  DevBuf<int32_t> fcell, flocal, scell;       // [nf], [nf], [nf][NQ]
+  DevBuf<double> slam, sy, uw;                // [nf][NQ][dim + 1], [nf][NQ], [nf][dim]
+  DevBuf<int32_t> nodes, nptr, entry;         // the nodes on modelled facets, their runs, rows of fvec (facet NF2 + local)
+  DevBuf<double> fvec, rows;                  // [nf][NF2][dim], [nf][dim + 4]
+};
+// ONE launch: w.fvec = weight times the facet vectors of W(u), w.rows = the diagnostics rows
+void launch_wall_model_facets(hipStream_t s, const MeshDev& m, const WallModelDev& w, const double* u, double nu,
+                              double weight);
+// ONE launch: v = the node sums of w.fvec in ascending facet order;  n1 += v,  rhs -= b0 v  (rhs null: the plain sum)
+void launch_wall_model_gather(hipStream_t s, const MeshDev& m, const WallModelDev& w, double b0, double* n1,
+                              double* rhs);
 // diag extraction: d[(i,a)] = 1 / A_ii[a][a]  (mask rows -> 1)
 void launch_inv_diag(hipStream_t s, const BlockMat& A, int nv, const uint8_t* rowmask,
                      double* dinv);
@@ -1289,20 +1312,20 @@ struct nsfem_ctx {
   bool conv_n2_valid = false, conv_n1_fresh = false;   // N2 holds c_c N(u2) / N1 was written since the last advance
   // Key of the stored explicit vectors N1, N2 (the vector itself: imex_explicit_add, api.hip): everything but the level
   // that they were formed with -- convective form, c_c, visc.epoch, bodies.epoch and the 2 c_cor Omega of their level
-  // (compared bit for bit).  A step forms N(u2) again iff the key of its N2 is not the key the settings give now.
+  // (compared bit for bit), and wm.epoch.  A step forms N(u2) again iff the key of its N2 is not the key the settings give now.
   // vouched: the caller wrote the slot (nsfem_set_state).  The two sides differ here, on purpose: a
   // vouched NSFEM_CONV_N2 is used whatever the other components say; a vouched NSFEM_TCONV_2 (Scalar::Key below)
   // stands for every FORM only -- its epochs are those of the vouching call and are honoured afterwards
   struct ImexKey {
     int form = -1;
     double cc = 0.0;
-    int64_t visc = 0, body = 0;
+    int64_t visc = 0, body = 0, wall = 0;
     double gam[3] = {0.0, 0.0, 0.0};
     bool vouched = false;
     static ImexKey of(const nsfem_ctx& c, const double gam[3]);       // (api.hip: what the settings give now)
     bool serves(const ImexKey& now) const {
       return vouched || (form == now.form && cc == now.cc && visc == now.visc && body == now.body &&
-                         std::memcmp(gam, now.gam, sizeof(gam)) == 0);
+                         wall == now.wall && std::memcmp(gam, now.gam, sizeof(gam)) == 0);
     }
   } conv_key;
   // partitioned meshes: the ghost entries of the slot are bit copies of the owners' values (exchanged by an IMEX
@@ -1376,6 +1399,15 @@ struct nsfem_ctx {
     int64_t thermal_epoch = 0, fused_launches = 0, thermal_recomputed = 0;
     nsfem::DevBuf<double> heat_work;   // partials and results of nsfem_body_heat
   } bodies;
+  // wall-stress model (nsfem_set_wall_model): with a model the stored vectors carry W(u) as well, added third.  `epoch`
+  // counts the changes of the law, its parameters or the facet set (a component of conv_key); the host copies of what
+  // the last call took (h_int, h_dbl) tell a change from the same data again
+  struct WallModel {
+    nsfem::WallModelDev dev;
+    int64_t epoch = 0, launches = 0, recomputed = 0;
+    std::vector<int32_t> h_int;
+    std::vector<double> h_dbl;
+  } wm;
   // CG needs a symmetric preconditioner: while IMEX steps run, the velocity cycle is V(d, d) instead of the
   // non-symmetric V(0, d + 1) the BiCGStab solves use (nsfem_set_bdf switches back)
   bool mg_v_symmetric = false;

@@ -24,7 +24,8 @@ all of this: c_v K stays in the matrix and the remainder V(u) joins the extrapol
 N(u) = c_c conv(u) + V(u); that treatment is unconditionally stable only while |nu_x| stays a fraction
 of c_v, otherwise k is bounded by about Delta^2 / nu_x.  Solid bodies inside the box
 (``set_immersed_bodies``, ``immersed_bodies``) join the same vector as a Brinkman penalisation term B(u); that term
-bounds k / eta.
+bounds k / eta.  Modelled walls (``set_wall_model``, ``wall_models``) add a third explicit term W(u), the
+wall stress of a law of the wall sampled inside the flow; it bounds k nu r / (y h).
 
 Rotating frames (``set_angular_velocity``): the Coriolis term is extrapolated with the convective
 term, N(u) = c_c conv(u) + V(u) + M (2 c_cor Omega x u) with Omega taken at the time of the level
@@ -42,6 +43,8 @@ u2 travels with it in one packed message only when its slot was written since th
 uniform strips it stays one kernel launch, which writes zeros to the rows of ghost nodes.  The ranks
 agree once on the right-hand-side path, so every rank runs the same sequence of collectives.
 """
+import numpy as np
+
 import _native as nat
 from fem_function import DeviceFunction, MixedFunction
 from imex_time_stepping import IMEXTimeStepping, IMEXType
@@ -221,6 +224,63 @@ class IMEXIPCSSolver(InstationarySolverBase):
             except nat.NativeError as err:
                 raise RuntimeError(str(err))
 
+    def set_wall_model(self, model):
+        """a ``wall_models.WallModel`` or None for none: the walls with the model's boundary ids keep u.n = 0 only and
+        take their tangential stress from the law -- the explicit term W(u), third in the extrapolated vector after
+        V(u) and B(u).  ValueError if a modelled boundary id carries ``no_slip`` or any other condition
+        that fixes a tangential component, or no condition that fixes the normal component (``no_normal_flux``; that
+        condition is axis-aligned).  Partitioned meshes and a viscous coefficient of None are refused by the device
+        driver.  ``wall_quantities``' viscous row stays the RESOLVED stress on such a boundary; the modelled wall
+        stress is ``ProblemBase._compute_wall_model``."""
+        from wall_models import WallModel
+        assert model is None or isinstance(model, WallModel)
+        self._wall_model = model
+        if hasattr(self, "_velocity_bcs"):
+            self._check_wall_model_bcs()
+        self._push_wall_model()
+
+    def _check_wall_model_bcs(self):
+        from ns_solver_base import VelocityBCType as T
+        model = getattr(self, "_wall_model", None)
+        if model is None:
+            return
+        import fem_host
+        for bid in model.boundary_ids:
+            normal = np.array(fem_host.boundary_normal(self._mesh, self._boundary_markers, bid))
+            k = int(np.abs(normal).argmax())
+            if abs(abs(normal[k]) - 1.0) >= 5.0e-14:
+                raise ValueError("wall model: boundary id %d is not axis aligned (no_normal_flux needs that)" % bid)
+            normal_fixed = False
+            for bc in (bc for bc in self._velocity_bcs if bc[1] == bid):
+                if bc[0] is T.no_normal_flux:
+                    normal_fixed = True
+                elif bc[0] in (T.constant_component, T.function_component) and bc[2] == k:
+                    normal_fixed = True
+                else:
+                    raise ValueError("wall model: boundary id %d carries %s, which fixes a tangential component; a "
+                                     "modelled wall takes no_normal_flux only" % (bid, bc[0].name))
+            if not normal_fixed:
+                raise ValueError("wall model: boundary id %d carries no condition that fixes the normal component "
+                                 "(no_normal_flux)" % bid)
+
+    def _push_wall_model(self):
+        if not (hasattr(self, "_ctx") and hasattr(self, "_wall_model") and hasattr(self, "_dofmap")):
+            return
+        model = self._wall_model
+        try:
+            if model is None:
+                self._wall_model_arrays = None
+                self._ctx.set_wall_model(0)
+                return
+            if hasattr(self, "_velocity_bcs"):
+                self._check_wall_model_bcs()
+            a = model.build(self._mesh, self._boundary_markers, self._dofmap)
+            self._ctx.set_wall_model(model.law.law_id, model.law.params(), a.facet_cell, a.facet_local, a.sample_cell,
+                                     a.sample_lambda, a.sample_y, a.wall_velocity)
+            self._wall_model_arrays = a
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+
     def _setup_function_spaces(self):
         if not hasattr(self, "_Wh"):
             super()._setup_function_spaces()
@@ -245,6 +305,7 @@ class IMEXIPCSSolver(InstationarySolverBase):
         self._push_viscosity_model()
         if not getattr(self, "_immersed_on_device", False):
             self._push_immersed_bodies()
+        self._push_wall_model()
         self._diffusion_solver = _DeviceSystem(self, nat.SYS_MOMENTUM)
         self._projection_solver = _DeviceSystem(self, nat.SYS_POISSON)
         self._velocity_correction_solver = _DeviceSystem(self, nat.SYS_CORRECTION)

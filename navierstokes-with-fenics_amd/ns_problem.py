@@ -80,6 +80,10 @@ class ProblemBase:
     # (an immersed_bodies.ImmersedBodies) behind, which goes to the solver's set_immersed_bodies where it has one
     _BODIES_HOOK = "set_immersed_bodies"
 
+    # A problem with modelled walls defines ``set_wall_model``; it leaves ``_wall_model`` (a wall_models.WallModel)
+    # behind, which goes to the solver's set_wall_model where it has one
+    _WALL_MODEL_HOOK = "set_wall_model"
+
     def _call_hooks(self, order):
         """mesh, then the hooks named in ``order``; afterwards the consistency checks of the reference"""
         self.setup_mesh()
@@ -99,6 +103,8 @@ class ProblemBase:
             getattr(self, self._VISCOSITY_HOOK)()
         if hasattr(self, self._BODIES_HOOK):
             getattr(self, self._BODIES_HOOK)()
+        if hasattr(self, self._WALL_MODEL_HOOK):
+            getattr(self, self._WALL_MODEL_HOOK)()
         if not hasattr(self, "_bcs"):
             assert hasattr(self, "_periodic_bcs")
         if hasattr(self, "_internal_constraints"):
@@ -134,6 +140,8 @@ class ProblemBase:
             solver.set_viscosity_model(self._viscosity_model)
         if hasattr(self, "_immersed_bodies") and hasattr(solver, "set_immersed_bodies"):
             solver.set_immersed_bodies(self._immersed_bodies, getattr(self, "_immersed_allow_stiff", False))
+        if hasattr(self, "_wall_model") and hasattr(solver, "set_wall_model"):
+            solver.set_wall_model(self._wall_model)
         if hasattr(self, "_temperature_coefficients") and hasattr(solver, "set_scalar_coefficients"):
             solver.set_scalar_coefficients(**self._temperature_coefficients)
         if hasattr(self, "_temperature_bcs") and hasattr(solver, "set_scalar_boundary_conditions"):
@@ -479,6 +487,32 @@ class ProblemBase:
             return solver._ctx.body_forces(nat.U0)
         except nat.NativeError as err:
             raise RuntimeError(str(err))
+
+    def _compute_wall_model(self):
+        """what the wall-stress model (``set_wall_model``) gives for the current velocity, from the device
+        (nsfem_wall_model_facets): ``{boundary_id: dict(area, friction_force [dim], mean_u_tau, mean_y_plus,
+        max_y_plus)}`` and, under the key ``"facets"``, the per-facet rows [n_facets, dim + 4] (|f|, int tau_w, int
+        u_tau, int y+, max y+) in the order of the model's boundary ids.  ``friction_force`` = -int tau_w, the force the
+        modelled wall exerts on the fluid.  New helper."""
+        import _native as nat
+        solver = self._get_solver()
+        arrays = getattr(solver, "_wall_model_arrays", None)
+        if arrays is None:
+            raise RuntimeError("wall model: the solver has no wall model on the device (set_wall_model)")
+        try:
+            rows = solver._ctx.wall_model_facets(nat.U0)
+        except nat.NativeError as err:
+            raise RuntimeError(str(err))
+        dim = solver._ctx.dim
+        out = {"facets": rows}
+        for bid in np.unique(arrays.facet_id):
+            r = rows[arrays.facet_id == bid]
+            area = float(r[:, 0].sum())
+            out[int(bid)] = dict(area=area, friction_force=-r[:, 1:1 + dim].sum(axis=0),
+                                 mean_u_tau=float(r[:, 1 + dim].sum()) / area,
+                                 mean_y_plus=float(r[:, 2 + dim].sum()) / area,
+                                 max_y_plus=float(r[:, 3 + dim].max()))
+        return out
 
     def _compute_body_heat(self):
         """per immersed body the volume, the heat rate Q_s the body takes from the fluid (0 for a body without a

@@ -11,7 +11,9 @@ traction of one boundary id, lists uploaded at every call) stays as it is.
   solver comes later (``ProblemBase._add_wall_quantities``).  Traction ``-p n + c_v f (grad u + grad u^T) n`` with
   ``c_v`` the solver's viscous coefficient and ``f`` the factor (1: the Newtonian stress, 1/2: the traction of the
   reference's dfg_benchmark driver) -- the convention of ``_compute_boundary_force`` --, plus ``nu_x (grad u +
-  grad u^T) n`` when the solver has a viscosity model.  ``n`` points out of the fluid.
+  grad u^T) n`` when the solver has a viscosity model.  ``n`` points out of the fluid.  The viscous row is the
+  RESOLVED stress: on a boundary with a wall-stress model (``wall_models``, ``IMEXIPCSSolver.set_wall_model``) it is
+  not the wall stress -- ``ProblemBase._compute_wall_model`` returns that.
 * ``compute()``: ``{boundary_id: dict(area, pressure_force, viscous_force, force, torque, mass_flux, mean_temperature,
   heat_flux)}``; ``heat_flux`` = ``int -kappa grad T . n``, the conductive heat LEAVING the fluid (temperature
   entries are 0 for a solver without a scalar).  With a subgrid heat flux the device forms the row with ``kappa +
